@@ -6,8 +6,9 @@ HistEq64 windows -> WVM -> overlap elimination -> RBF-SVM -> block NMS) on 640x4
 fd_detect_five_stage_batch; every frame's fd_detection records reach the host inside the timed region.  One step =
 --frames-per-step frames (default 512, so that 20 steps take about a second).
 
-The other BASELINE configs ride along as sub-records under "also" (same JSON line), each with its own ms_per_step, roofline and
-cpu_baseline:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up the headline, warms it up, times its N steps and prints the JSON line
+of that figure, nothing else.  With --full the other BASELINE configs ride along as sub-records under "also" (same JSON line), each
+with its own ms_per_step, roofline and cpu_baseline, and the complete records go to a side file (--full-out):
   hog_svm  config 2: 640x480, 21-layer pyramid, 20x20 windows stride 2, HOG-324 + RBF-SVM 1024 SV   (fd_detect_hog_svm_begin/_end)
   ffp15    config 3: the 15 detectors of ffpDetectApp/*.cfg on 1920x1080 frames, 32 distinct ones    (fd_five_stage_batch_begin/_end)
   sdm      config 4: 256 face crops x 68 landmarks x 4 cascade steps                                 (fd_sdm_fit_batch)
@@ -17,9 +18,14 @@ Frames are resident in HBM before the timed region.  Multi-GPU (config 5): one p
 -> rank i mod N, no data-path collective, ONE all_gather of the real detection records {image, detector, cx, cy, w, h, score,
 prob} every --gather-every steps.  `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run.
 
-The cpu_baseline legs (rank 0, N=1 only) time the CPU oracle (oracle/, "port" of the reference's single-threaded CPU path) on a
+The cpu_baseline legs (--full; rank 0, N=1 only) time the CPU oracle (oracle/, "port" of the reference's single-threaded CPU path) on a
 bounded sample of the same workload: 1 thread with the update / extract / classify split of BASELINE.md section 3, and an
-image-parallel (detector-parallel for ffp15) run on every host core."""
+image-parallel (detector-parallel for ffp15) run on every host core.
+
+--dump-outputs DIR writes what the headline workload delivered in its LAST timed step as DIR/<name>.npy (float64): the detection
+records of the step's images (records.npy), the landmark shapes of its batches (sdm: shapes.npy, status.npy) or its boxes
+(aggregated: boxes.npy), rows in a canonical order.  The timed steps start the workload's input sequence afresh, so with the same
+arguments every run feeds the same inputs, whatever the warm-up did."""
 import argparse
 import gc
 import json
@@ -214,6 +220,17 @@ class Workload:
     def cpu_baseline(self):
         return None
 
+    def reset_feed(self):
+        """called before the timed steps: a workload that feeds its inputs from a running sequence starts it afresh"""
+
+    def step_ids(self, i):
+        """image ids of the records that step i delivers"""
+        return (i * self.FP + np.arange(self.FP)) * self.env.world + self.env.rank
+
+    def outputs(self, records):
+        """--dump-outputs: the arrays of the last timed step (records: its detection records, float64 [n, 8])"""
+        return dict(records=records)
+
 
 # Rejection profiles of the synthetic WVM (SURVEY.md H5: the rejection rate per level drives throughput).  "default" is the model of
 # the headline: 65 % of the calibration patches pass each filter until 32 are left (the cascade then stops rejecting, after ~13
@@ -323,6 +340,9 @@ class Cascade(Workload):
             done += m
             self.nframes_fed += m
         return ids
+
+    def reset_feed(self):
+        self.nframes_fed, self.order_rng = 0, np.random.default_rng(77 + self.env.rank)
 
     def step(self, i):
         capi, NB = self.capi, self.NB
@@ -713,6 +733,9 @@ class Ffp15(Workload):
         self.nfed += 1
         return self.dframes[int(self.order[pos])]
 
+    def reset_feed(self):
+        self.nfed, self.order_rng = 0, np.random.default_rng(78 + self.env.rank)
+
     def __init__(self, env, W=1920, H=1080, frames_per_step=8):   # 20 steps = 160 frames = five whole passes over the 32 distinct frames
         import torch  # noqa: F401
         from featuredetection_amd import capi, synth  # noqa: F401
@@ -941,6 +964,9 @@ class Config5(Ffp15):
             out.extend(self._feed(self.dframes[(int(img) - self.env.rank) // self.env.world], int(img)))
         return self.nwin * len(ids), out
 
+    def step_ids(self, i):
+        return self.step_images(i, self.env.rank, self.env.world, self.total_images, self.GATHER_IMAGES)
+
     def kernel_probe(self):
         return None
 
@@ -986,15 +1012,23 @@ class Sdm(Workload):
                            content="%d distinct batches of %d distinct crops each resident in HBM (device_frames), cycled" % (self.NBATCH, self.B))
 
     def step(self, i):
-        flying = []
+        flying, self.last = [], []
         for _ in range(self.FP):
             if len(flying) == self.inflight:
-                self.sdm.fit_end(flying.pop(0))
+                self.last.append(self.sdm.fit_end(flying.pop(0)))
             flying.append(self.sdm.fit_device_begin(self.dimgs[self.nfed % self.NBATCH].data_ptr(), self.W, self.H, self.B, self.boxes))
             self.nfed += 1
         for t in flying:
-            self.sdm.fit_end(t)
+            self.last.append(self.sdm.fit_end(t))
         return self.B * 4 * self.FP, []
+
+    def reset_feed(self):
+        self.nfed = 0
+
+    def outputs(self, records):
+        """the shapes (x then y of the 68 landmarks) and status of every face of the step's batches, in feeding order"""
+        return dict(shapes=np.concatenate([s for s, _ in self.last]).astype(np.float64),
+                    status=np.concatenate([st for _, st in self.last]).astype(np.float64))
 
     def kernel_probe(self):
         ctx = self.env.ctx
@@ -1064,6 +1098,9 @@ class Rvm(Workload):
         d_, _, _ = self.capi.detect_rvm(self.env.ctx, self.pyr, self.rvm, feature_space=self.capi.FEATURE_HQ64, conv_scale=1.0 / 255.0, want_all=False)
         return self.nwin, [(i * self.env.world + self.env.rank, 0, d_)]
 
+    def step_ids(self, i):
+        return np.array([i * self.env.world + self.env.rank])
+
 
 class Aggregated(Workload):
     """SURVEY 8(f) row 2 (not a BASELINE config): AggregatedFeaturesDetector (FHOG + linear SVM convolution + IoU NMS)"""
@@ -1092,8 +1129,13 @@ class Aggregated(Workload):
                                     "~%d window positions, IoU NMS 0.3 on the host" % (W, H, n), frames_per_step=1)
 
     def step(self, i):
-        self.det.detect_device(self.dframes[i % 2].data_ptr(), self.W, self.H, 3)
+        self.last, _ = self.det.detect_device(self.dframes[i % 2].data_ptr(), self.W, self.H, 3)
         return self.nwin, []
+
+    def outputs(self, records):
+        """the step's boxes {score, x, y, w, h}, sorted"""
+        b = np.stack([self.last[f].astype(np.float64) for f in ("score", "x", "y", "w", "h")], 1).reshape(-1, 5)
+        return dict(boxes=b[np.lexsort(b.T[::-1])])
 
 
 
@@ -1153,17 +1195,18 @@ def compact_record(rec, text=160):
 def emit(res, subs, names, full_out):
     """ONE line <= LINE_LIMIT bytes on stdout: the headline record (contract keys, roofline, roofline_issue, cpu_baseline) and a `summary`
     with value / ms_per_step / roofline fraction / CPU baseline of every workload of the run.  Everything else -- the complete
-    records of the headline and of the `also` workloads -- goes to the side file (`--full-out`, default bench_also.json beside bench.py;
-    tools/measure_r06.sh commits a copy as profiles/r06_bench_default.json)."""
+    records of the headline and of the `also` workloads -- goes to the side file (`--full-out`; with --full by default bench_also.json
+    beside bench.py; tools/measure_r06.sh commits a copy as profiles/r06_bench_default.json)."""
     full = dict(res)
     if subs:
         full["also"] = subs
-    try:
-        with open(full_out, "w") as f:
-            json.dump(full, f, indent=1)
-            f.write("\n")
-    except OSError as e:   # a read-only checkout must not cost the line
-        print("bench.py: side file %s not written: %s" % (full_out, e), file=sys.stderr)
+    if full_out:
+        try:
+            with open(full_out, "w") as f:
+                json.dump(full, f, indent=1)
+                f.write("\n")
+        except OSError as e:   # a read-only checkout must not cost the line
+            print("bench.py: side file %s not written: %s" % (full_out, e), file=sys.stderr)
     line = compact_record(res)
     if subs:
         summ = {}
@@ -1178,13 +1221,14 @@ def emit(res, subs, names, full_out):
                 e["cpu_1t"] = r2["cpu_baseline"]["value"]
             summ[nm] = e
         line["summary"] = summ
-    line["full_records"] = os.path.basename(full_out)
+    if full_out:
+        line["full_records"] = os.path.basename(full_out)
     line = _r(line)
     out = json.dumps(line, separators=(",", ":"))
     # a line that still came out too long loses its free text first, then the summary's extras: the contract keys always survive
     if len(out) > LINE_LIMIT:
         line = _r(dict(compact_record(res, text=60), summary={k: dict(value=v["value"], unit=v["unit"]) for k, v in line.get("summary", {}).items()},
-                       full_records=os.path.basename(full_out)))
+                       **({"full_records": os.path.basename(full_out)} if full_out else {})))
         out = json.dumps(line, separators=(",", ":"))
     print(out, flush=True)
     return out
@@ -1194,7 +1238,22 @@ class Env:
     pass
 
 
-def measure(wl, env, steps, warmup, gather_every, want_cpu):
+DUMP_LIMIT = 64 << 20   # bytes of all --dump-outputs arrays together
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (float64); an array beyond its share of DUMP_LIMIT keeps a fixed, seeded sample of its rows"""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), share // max(1, a.nbytes // len(a)), replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def measure(wl, env, steps, warmup, gather_every, want_cpu, dump_dir=None):
     import gc
     import torch
     import torch.distributed as dist
@@ -1233,6 +1292,7 @@ def measure(wl, env, steps, warmup, gather_every, want_cpu):
         wl.qlens = []
     if hasattr(wl, "stage_frames"):
         wl.stage_sum, wl.stage_frames = np.zeros(4, np.int64), 0
+    wl.reset_feed()
     t0 = time.perf_counter()
     units, ndet, pending, gathered = 0, 0, [], 0
     gather_open, gather_s, ngathers = False, 0.0, 0
@@ -1283,6 +1343,11 @@ def measure(wl, env, steps, warmup, gather_every, want_cpu):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dist.all_reduce(uu, op=dist.ReduceOp.SUM)
     dt, total_units, total_det = float(tt.item()), float(uu[0].item()), int(uu[1].item())
+    if dump_dir and env.rank == 0:
+        # the last gather interval holds every record of the last step (a call is never collected before the step that queued it);
+        # rows sorted, so that the order in which calls were collected does not matter
+        last = local[np.isin(local[:, 0], wl.step_ids(steps - 1))] if len(local) else local
+        write_outputs(dump_dir, wl.outputs(last[np.lexsort(last.T[::-1])]))
     rec = dict(metric=wl.metric, value=total_units / dt / 1e6, unit=wl.unit, n_gpus=world, steps=steps, warmup=warmup,
                ms_per_step=dt / steps * 1e3, higher_is_better=True, scaling=wl.scaling, vs_baseline=None, dtype=wl.dtype, data="synthetic",
                config=wl.config, detections_delivered=total_det)
@@ -1322,8 +1387,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cascade", choices=sorted(WORKLOADS) + ["wvm"], help="headline workload (wvm = cascade)")
-    ap.add_argument("--also", default=None, help="comma-separated sub-records (default: hog_svm,sdm,ffp15,cascade_late,cascade_group,cascade_8frames,ffp15_2frames,config5 "
-                                                 "when the headline is the default cascade; 'none' for none)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the `also` workloads, the kernel probes and roofline "
+                                                        "records, the CPU baselines and the side file of complete records")
+    ap.add_argument("--also", default=None, help="comma-separated sub-records (default with --full: hog_svm,sdm,ffp15,cascade_late,cascade_group,cascade_8frames,"
+                                                 "ffp15_2frames,config5 when the headline is the default cascade; 'none' for none)")
     ap.add_argument("--images", type=int, default=0, help="config5 workload: images of the job (default 10000; FD_BENCH_CONFIG5_IMAGES)")
     ap.add_argument("--gather-every", type=int, default=4)
     ap.add_argument("--size", default=None, help="frame size WxH of the headline workload (cascade, hog_svm, ffp15, rvm, aggregated)")
@@ -1331,12 +1398,16 @@ def main():
     ap.add_argument("--frames-per-call", type=int, default=0, help="cascade workload: frames per call (one multi-frame pyramid); 0 = default")
     ap.add_argument("--per-frame-launches", action="store_true", help="cascade workload: one pyramid + cascade per frame (fd_detect_five_stage_batch) "
                                                                       "instead of the multi-frame entry points")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_also.json"), help="side file for the complete records of the headline and the "
-                                                                                       "`also` workloads (stdout carries one line of at most 8 KB)")
-    ap.add_argument("--no-probe", action="store_true", help="skip kernel_probe (the HIP-event timing of the dominant kernel and the single-frame "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--full-out", default=None, help="side file for the complete records of the headline and the `also` workloads (stdout carries "
+                                                     "one line of at most 8 KB); with --full the default is bench_also.json beside bench.py")
+    ap.add_argument("--no-probe", action="store_true", help="--full without kernel_probe (the HIP-event timing of the dominant kernel and the single-frame "
                                                             "latency loop): profiler runs want the timed steps' launches only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the headline workload delivered in its last timed step as "
+                                                                       "DIR/<name>.npy (float64; rank 0's share with --gpus N)")
     args = ap.parse_args()
+    if args.full and args.full_out is None:
+        args.full_out = os.path.join(ROOT, "bench_also.json")
     if args.workload == "wvm":
         args.workload = "cascade"
     if args.images > 0:
@@ -1410,10 +1481,10 @@ def main():
     if also is None:
         # (sdm in front of the 15-detector batch: behind it -- behind the release of its four frames' worth of handles -- the same workload
         # measures 1.15 instead of 1.23 M iterations/s, with one frame in flight 1.23; the other workloads do not care where they stand)
-        also = "hog_svm,sdm,ffp15,cascade_late,cascade_group,cascade_8frames,ffp15_2frames,config5" if (args.workload == "cascade" and not args.size) else "none"
+        also = "hog_svm,sdm,ffp15,cascade_late,cascade_group,cascade_8frames,ffp15_2frames,config5" if (args.full and args.workload == "cascade" and not args.size) else "none"
     also = [a for a in also.split(",") if a and a != "none"]
-    want_cpu = not args.no_cpu_baseline
-    env.no_probe = args.no_probe
+    want_cpu = args.full and not args.no_cpu_baseline
+    env.no_probe = args.no_probe or not args.full
 
     wl = build(args.workload, True)
     def release(name):
@@ -1423,7 +1494,7 @@ def main():
             free, total = torch.cuda.mem_get_info()
             print("[mem] rank %d after %s: %.2f GB in use of %.0f" % (env.rank, name, (total - free) / 1e9, total / 1e9), file=sys.stderr, flush=True)
 
-    res = measure(wl, env, args.steps, args.warmup, args.gather_every, want_cpu)
+    res = measure(wl, env, args.steps, args.warmup, args.gather_every, want_cpu, args.dump_outputs)
     del wl
     release(args.workload)
     subs = []

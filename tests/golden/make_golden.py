@@ -87,7 +87,21 @@ def main():
         g["svm__" + k] = np.asarray(v)
     np.savez_compressed(os.path.join(OUT, "orc_cascade_160x120.npz"), **g)
     next_rows()
+    live_vlhog()
     print("golden fixtures written to", OUT)
+
+
+def live_vlhog():
+    """ref_vlhog_live.npz: the inputs of test_oracle_live_reference_units and what the reference's hog.c computes for them"""
+    assert O.ref() is not None, "oracle/_ref/libfdref.so missing (needs the reference tree, oracle/Makefile REF)"
+    rng = np.random.default_rng(123)
+    g = {"n": np.int32(5)}
+    for i in range(5):
+        g["img_a%d" % i] = rng.uniform(0, 255, (30, 30)).astype(np.float32)
+        g["out_a%d" % i] = O.ref_vlhog(g["img_a%d" % i], 10, 9, 1)
+        g["img_b%d" % i] = rng.uniform(0, 255, (27, 33)).astype(np.float32)
+        g["out_b%d" % i] = O.ref_vlhog(g["img_b%d" % i], 4, 6, 0)
+    np.savez_compressed(os.path.join(OUT, "ref_vlhog_live.npz"), **g)
 
 
 def next_rows():
@@ -134,5 +148,7 @@ def next_rows():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "next_rows":
         next_rows()
+    elif len(sys.argv) > 1 and sys.argv[1] == "live_vlhog":
+        live_vlhog()
     else:
         main()

@@ -765,7 +765,7 @@ def test_bench_config5_one_and_two_ranks(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_default_list_two_ranks_and_the_memory_it_leaves(tmp_path):
-    """The driver's N=2 command with bench.py's DEFAULT `also` list (two ranks on device 0, gloo + the librccl stand-in, config 5 cut to
+    """The driver's N=2 command with bench.py's `also` list of --full (two ranks on device 0, gloo + the librccl stand-in, config 5 cut to
     32 images): every record arrives with n_gpus 2 and all its detections gathered on rank 0, and each finished workload gives its
     device memory back -- capi's handles had no __del__ once, nine workloads left 160 GB behind and two ranks on one device ran out."""
     import json
@@ -777,7 +777,7 @@ def test_bench_default_list_two_ranks_and_the_memory_it_leaves(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FD_DIST_ONE_DEVICE="1", FD_BENCH_DIST_BACKEND="gloo", FD_RCCL_LIB=STUB_RCCL, FD_BENCH_CONFIG5_IMAGES="32", FD_BENCH_MEMLOG="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-probe",
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-probe",
            "--full-out", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -807,7 +807,7 @@ def test_bench_line_of_every_workload_with_its_probe(workload, tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--also", "none", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--also", "none", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--full-out", str(tmp_path / "full.json")]
     if workload.startswith("cascade"):
         cmd += ["--frames-per-step", "128"]
@@ -827,3 +827,29 @@ def test_bench_line_of_every_workload_with_its_probe(workload, tmp_path):
         assert "32 distinct frames" in full["config"]["content"]
     if workload == "sdm":   # 256 distinct crops per batch, >= 4 distinct batches
         assert "4 distinct batches of 256 distinct crops" in full["config"]["content"]
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain run is the headline alone: its line carries the contract's fields and nothing that takes runs of its own (no roofline,
+    no CPU baseline, no summary of other workloads, no side file named).  --dump-outputs writes the detection records of the last timed
+    step, and two runs with the same arguments write the same records."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for k in range(2):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames-per-step", "128",
+               "--dump-outputs", str(tmp_path / str(k))]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in rec, key
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "summary", "full_records", "latency_us_single_frame"} & set(rec), sorted(rec)
+        recs.append(np.load(tmp_path / str(k) / "records.npy"))
+    a, b = recs
+    assert a.dtype == np.float64 and a.shape[1] == 8 and len(a) > 0
+    assert a[:, 0].min() >= 2 * 128 and a[:, 0].max() < 3 * 128   # the images of step 3 of 3
+    assert np.array_equal(a, b)

@@ -4,7 +4,6 @@ vectors.  CPU only."""
 import os
 
 import numpy as np
-import pytest
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -78,16 +77,18 @@ def test_svm_kernels_match_reference_libsvm(oracle):
 
 
 def test_oracle_live_reference_units(oracle):
-    """When oracle/_ref is present (build container, or shipped prebuilt), cross-check on fresh random
-    inputs, beyond the committed vectors."""
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref/libfdref.so not available")
-    rng = np.random.default_rng(123)
-    for _ in range(5):
-        img = rng.uniform(0, 255, (30, 30)).astype(np.float32)
-        assert np.array_equal(oracle.vlhog(img, 10, 9, 1), oracle.ref_vlhog(img, 10, 9, 1))
-        img = rng.uniform(0, 255, (27, 33)).astype(np.float32)
-        assert np.array_equal(oracle.vlhog(img, 4, 6, 0), oracle.ref_vlhog(img, 4, 6, 0))
+    """Random inputs beyond the vectors above: the oracle equals what the reference's hog.c computed for them
+    (tests/golden/ref_vlhog_live.npz) and, when oracle/_ref is present (build container, or shipped prebuilt),
+    what hog.c computes for them now."""
+    g = np.load(os.path.join(G, "ref_vlhog_live.npz"))
+    live = oracle.ref() is not None
+    for i in range(int(g["n"])):
+        for case, (cell, nori, var) in (("a", (10, 9, 1)), ("b", (4, 6, 0))):
+            img = g["img_%s%d" % (case, i)]
+            out = oracle.vlhog(img, cell, nori, var)
+            assert np.array_equal(out, g["out_%s%d" % (case, i)]), (case, i)
+            if live:
+                assert np.array_equal(out, oracle.ref_vlhog(img, cell, nori, var)), (case, i)
 
 
 def test_cascade_regression_vectors(oracle):

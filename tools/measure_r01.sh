@@ -5,7 +5,7 @@ R=$PWD
 O=$R/gpurun_out/measure
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 for wl in hog_svm wvm sdm; do
   timeout 240 $B --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err
   timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$wl -- $B --workload $wl --steps 10 --warmup 3 --no-cpu-baseline > /dev/null 2>&1

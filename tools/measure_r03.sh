@@ -7,7 +7,7 @@ R=$PWD
 O=$R/gpurun_out/measure3
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 WHAT=${1:-all}
 HEAD=$(cat $R/.git_head 2>/dev/null || echo unknown)
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then

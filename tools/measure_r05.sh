@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/measure5
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 WHAT=${1:-all}
 HEAD=$(cat $R/.git_head 2>/dev/null || echo unknown)
 if [ "$WHAT" = stats ] || [ "$WHAT" = all ]; then
@@ -48,7 +48,7 @@ if [ "$WHAT" = pmc ] || [ "$WHAT" = all ]; then
   [ -f $O/r05_pmc.json ] && cp $O/r05_pmc.json $R/profiles/r05_pmc.json   # the bench line below cites it
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  ( cd $R && timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err )
+  ( cd $R && timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err )
   timeout 300 python $R/tools/latency_probe.py 1000 > $O/latency_single_frame.txt 2>&1
 fi
 ls $O | head -60

@@ -10,7 +10,7 @@ R=$PWD
 O=$R/gpurun_out/measure6
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 WHAT=${1:-all}
 HEAD=$(cat $R/.git_head 2>/dev/null || echo unknown)
 WLS=${WLS:-cascade cascade_late cascade_group hog_svm ffp15 sdm}
@@ -61,7 +61,7 @@ if [ "$WHAT" = pmc ] || [ "$WHAT" = all ]; then
   [ -f $O/r06_pmc.json ] && cp $O/r06_pmc.json $R/profiles/r06_pmc.json   # the bench line below cites it
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  ( cd $R && timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full-out $O/bench_also.json > $O/bench_line.json 2> $O/bench_default.err )
+  ( cd $R && timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full --full-out $O/bench_also.json > $O/bench_line.json 2> $O/bench_default.err )
   timeout 300 python $R/tools/latency_probe.py 1000 > $O/latency_single_frame.txt 2>&1
 fi
 if [ "$WHAT" = tail ]; then

@@ -1,6 +1,6 @@
 # counters of the pyramid kernels of the headline workload (isolated: one call in flight)
 R=$PWD; O=$R/gpurun_out/pmcp; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-CMD="python $R/bench.py --workload cascade --also none --steps 2 --warmup 1 --frames-per-step 64 --no-cpu-baseline"
+CMD="python $R/bench.py --full --workload cascade --also none --steps 2 --warmup 1 --frames-per-step 64 --no-cpu-baseline"
 i=0
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE" \
            "SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
