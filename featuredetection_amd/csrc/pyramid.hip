@@ -36,7 +36,8 @@ struct FusedJob {
     int dw0, dh0, dw1, dh1;
     uint32_t dst0_off;      // resized layer, written only when it is a kept layer (0xffffffff: stays in LDS)
     uint32_t dst1_off;      // its pyrDown
-    uint32_t xtab, ytab;    // offsets (in int2 entries) into the coordinate tables
+    uint32_t xtab;          // offset (in int2 entries) of the column table
+    double scale_y;         // cv::resize's vertical scale: the rows' coordinates are computed in the kernel, once per tile
 };
 struct FusedJobs {
     int n;
@@ -92,11 +93,12 @@ __device__ __forceinline__ unsigned int mad24(unsigned int a, unsigned int b, un
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ unsigned int mulhi24_s(unsigned int a_uniform, unsigned int b) {   // (a * b) >> 32 of two 24-bit factors
+__device__ __forceinline__ unsigned int mulhi24(unsigned int a, unsigned int b) {   // (a * b) >> 32 of two 24-bit factors
     unsigned int r;
-    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(r) : "s"(a_uniform), "v"(b));
+    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t ld_u32_unaligned(const uint8_t* p) {
     uint32_t v;
     __builtin_memcpy(&v, p, 4);
@@ -340,11 +342,12 @@ __global__ __launch_bounds__(256) void k_resize_tiled(const uint8_t* __restrict_
 // pyramid stage spent its time on.  A workgroup computes the resized pixels under one 62 x 16 tile of the pyrDown layer (127 x 35, the
 // 5-tap halo included; BORDER_REFLECT_101 columns / rows are the resized pixels at the reflected coordinates) into LDS and takes the
 // pyrDown from there; the resized layer goes to memory only when it is a kept layer.  Same integer arithmetic as k_resize_tiled /
-// k_pyrdown_tiled, value for value (ImagePyramid.cpp:177,186), with two savings per resized pixel:
-//   * the cv::resize coordinates and fixed-point weights come from per-layer tables built on the host with the kernel's own float
-//     expressions (xtab[dx] = {left source column, a0 | a1 << 16}, ytab[dy] = {y0 | y1 << 16, b0 | b1 << 16});
-//   * a thread walks down one column and keeps the horizontally interpolated value of the last two source rows: consecutive
-//     destination rows share them (1 <= scale < 2), so a destination pixel costs ~1.4 horizontal interpolations instead of 2.
+// k_pyrdown_tiled, value for value (ImagePyramid.cpp:177,186):
+//   * the cv::resize column coordinates and fixed-point weights come from a per-layer table built on the host with the kernel's own
+//     float expressions (xtab[dx] = {left source column, a0 | a1 << 16}); the rows' (k_resize_tiled's srcY) are worked out with the
+//     next tile's loads, one resized row per lane;
+//   * the stage holds the two source rows of every resized row of the tile in slots of their own (y0 in slot 2 i, y1 in slot 2 i + 1),
+//     so a resized row reads its four bytes at fixed offsets: no row record, scalar unpacking or address arithmetic per row.
 // -DFD_PYR_PROF (tools/build_prof_lib.sh, tools/pyr_phases.py): ticks thread 0 of every workgroup spends in the phases of k_resize_down
 #ifdef FD_PYR_PROF
 constexpr int PYR_PROF_WGS = 65536;
@@ -355,44 +358,48 @@ __device__ unsigned long long fd_pyr_prof[PYR_PROF_WGS * 8];   // one record per
 #endif
 constexpr int FT_W1 = 62, FT_H1 = 16;                    // pyrDown tile
 constexpr int G0_W = 2 * FT_W1 + 3, G0_H = 2 * FT_H1 + 3, G0_PITCH = 128;   // resized pixels under it: 127 x 35
-constexpr int FS_PITCH = 256, FS_ROWS = 76;             // source stage: 126 * 2.0 + 3 columns (64 dwords: one per lane), 34 * 2.05 + 3 rows
-// Persistent workgroups walk a host-built list of tiles ({source rectangle, tile position, chain} per entry: the layout is static) and keep
-// the NEXT tile's global loads -- ~20 source dwords, the column's xtab entry, a row's ytab entry per thread -- in flight in registers
-// while they resize the current one: a tile used to spend 45 % of its 7.6 us waiting for them (in-kernel timestamps, tools/pyr_phases.py).
+constexpr int FS_PITCH = 256;                           // source stage: 126 * 2.0 + 3 columns (64 dwords: one per lane) ...
+constexpr int FS_LOADS = (2 * G0_H + 3) / 4;            // ... in 2 * 35 slots: wavefront w holds slots w, w + 4, ..., a lane one dword of each
+// Persistent workgroups walk a host-built list of tiles ({source columns, tile position, chain} per entry: the layout is static) and keep
+// the NEXT tile's global loads -- 18 source dwords and the column's xtab entry per thread -- in flight in registers while they resize the
+// current one: a tile used to spend 45 % of its 7.6 us waiting for them (in-kernel timestamps, tools/pyr_phases.py).
 // Multi-frame pyramids: workgroup b runs on XCD b % 8 and takes the frames b % 8, b % 8 + 8, ...: a frame's gray image is read by one L2.
-constexpr int FS_LOADS = (FS_ROWS + 3) / 4;   // source rows per wavefront: wavefront w holds rows w, w + 4, ..., a lane one dword of each
 struct FusedFetch {   // what a thread holds for a tile before it is in LDS
     uint32_t v[FS_LOADS];
-    int2 ex, ey;   // ex: thread = column of the tile; ey: lane = resized row of the tile (every wavefront its own copy)
+    int2 ex;         // thread = column of the tile: its xtab entry
+    uint32_t taps;   // lane q = resized row (w >> 1) + 2 q of the tile: its vertical weights b0 | b1 << 16
 };
-__device__ __forceinline__ void fused_issue(FusedFetch& f, const uint8_t* __restrict__ src, int sw, const int2* __restrict__ tabs, const FusedJob& jb,
-                                            const int4 d) {
-    const int X0 = d.x & 0xffff, Y0 = (int)((uint32_t)d.x >> 16), ncol = d.y & 0xffff, nrow = (int)((uint32_t)d.y >> 16);
-    const int gx0 = 2 * (d.z & 0xffff) * FT_W1 - 2;
+__device__ __forceinline__ void fused_issue(FusedFetch& f, const uint8_t* __restrict__ src, int sw, int sh, const int2* __restrict__ tabs,
+                                            const FusedJob& jb, const int4 d) {
+    const int X0 = d.x, ncol = d.y;
+    const int gx0 = 2 * (d.z & 0xffff) * FT_W1 - 2, gy0 = 2 * (int)((uint32_t)d.z >> 16) * FT_H1 - 2;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t rowOff;
+    {   // slot w + 4 q holds source row y0 (even w) or y1 (odd w) of the tile's resized row (w >> 1) + 2 q, and lane q works that row out:
+        // BORDER_REFLECT_101 of the resized rows the kept pyrDown rows reach (one reflection; rows further out only feed pyrDown rows past
+        // the layer's end, any valid row will do for them), then k_resize_tiled's srcY / clampY
+        const int py = gy0 + min((wave >> 1) + 2 * lane, G0_H - 1), pr = py < 0 ? -py : (py >= jb.dh0 ? 2 * jb.dh0 - 2 - py : py);
+        float fy = (float)((min(max(pr, 0), jb.dh0 - 1) + 0.5) * jb.scale_y - 0.5);
+        const int sy = (int)floorf(fy);
+        fy -= sy;
+        f.taps = (uint32_t)__float2int_rn((1.f - fy) * 2048) | (uint32_t)__float2int_rn(fy * 2048) << 16;
+        rowOff = mul24((uint32_t)min(max(sy + (wave & 1), 0), sh - 1), (uint32_t)sw);
+    }
     // A dword that hangs over the right edge of the image takes its last bytes from the next row (or, in the last row, from the arena
     // behind the gray image): they stand for columns >= sw, which no tap reads (the last column's right neighbour has weight 0).
-    // No predication: lanes right of the rectangle and rows below it load its last dword / last row again (valid addresses, values
-    // nobody reads) -- with a test per load the 19 loads were 19 basic blocks of exec-mask bookkeeping, 400 instructions per tile.
+    // No predication: lanes right of the rectangle load its last dword again (valid addresses, values nobody reads) -- with a test per
+    // load the loads were as many basic blocks of exec-mask bookkeeping, 400 instructions per tile.
     const uint32_t voff = (uint32_t)(4 * min(lane, (ncol - 1) >> 2) + X0);
-    const int rlast = nrow - 1;
 #pragma unroll
-    for (int q = 0; q < FS_LOADS; ++q) {
-        const int r = min(wave + 4 * q, rlast);   // scalar
-        f.v[q] = ld_u32_unaligned(src + (uint32_t)((Y0 + r) * sw) + voff);
-    }
+    for (int q = 0; q < FS_LOADS; ++q) f.v[q] = ld_u32_unaligned(src + ((uint32_t)__builtin_amdgcn_readlane((int)rowOff, q) + voff));
     f.ex = tabs[jb.xtab + reflect101(gx0 + (int)(threadIdx.x & 127), jb.dw0)];
-    {   // BORDER_REFLECT_101 of the resized rows the kept pyrDown rows reach (one reflection); rows further out only feed pyrDown
-        // rows past the layer's end, any valid row will do for them
-        const int py = 2 * (int)((uint32_t)d.z >> 16) * FT_H1 - 2 + min(lane, G0_H - 1), pr = py < 0 ? -py : (py >= jb.dh0 ? 2 * jb.dh0 - 2 - py : py);
-        f.ey = tabs[jb.ytab + min(max(pr, 0), jb.dh0 - 1)];
-    }
 }
 
 __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena0, uint32_t src_off, int sw, int sh, const int2* __restrict__ tabs,
                                                      FusedJobs jobs, uint32_t tileTab, int tilesPerFrame, int nimg, size_t imageStride) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[FS_ROWS * FS_PITCH];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[4 * FS_LOADS * FS_PITCH];
     __shared__ __attribute__((aligned(16))) uint8_t g0[G0_H * G0_PITCH];
+    __shared__ uint2 taps[G0_H];   // per resized row of the tile: b0 << 12, b1 << 12 (read as a broadcast beside the row's bytes)
     const int4* tiles = reinterpret_cast<const int4*>(tabs + tileTab);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool byXcd = nimg >= 8 && (gridDim.x & 7u) == 0;
@@ -406,7 +413,7 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
     if (item >= items) return;
     int4 d = desc_of(item);
     FusedFetch f;
-    fused_issue(f, arena0 + (size_t)frame_of(item) * imageStride + src_off, sw, tabs, jobs.j[d.w], d);
+    fused_issue(f, arena0 + (size_t)frame_of(item) * imageStride + src_off, sw, sh, tabs, jobs.j[d.w], d);
     int itemN = item + nslot;
     int4 dN = desc_of(itemN);
 
@@ -417,59 +424,52 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
         PYR_T(p0);
         const FusedJob jb = jobs.j[d.w];
         uint8_t* arena = arena0 + (size_t)frame_of(item) * imageStride;
-        const int X0 = d.x & 0xffff, Y0 = (int)((uint32_t)d.x >> 16);
+        const int X0 = d.x;
         const int x1 = (d.z & 0xffff) * FT_W1, y1 = (int)((uint32_t)d.z >> 16) * FT_H1;   // first pyrDown pixel of the tile
         const int gx0 = 2 * x1 - 2, gy0 = 2 * y1 - 2;                      // resized pixel of tile entry (0, 0), before the border reflection
-        {   // the fetched source rectangle and row table -> LDS
-            // every lane stores its dword of every row (the stage has a dword per lane and FS_ROWS rows; what lies outside the
-            // rectangle is never read)
-            static_assert(4 * (FS_LOADS - 1) + 3 < FS_ROWS && FS_PITCH == 256, "stage holds a dword per lane for rows wave + 4 q");
+        {   // the fetched source rows and vertical taps -> LDS
+            // every lane stores its dword of every slot (a dword per lane; what lies right of the rectangle is never read)
+            static_assert(2 * G0_H <= 4 * FS_LOADS && FS_PITCH == 256, "stage holds a dword per lane for slots wave + 4 q");
 #pragma unroll
             for (int q = 0; q < FS_LOADS; ++q) *reinterpret_cast<uint32_t*>(&stage[(wave + 4 * q) * FS_PITCH + 4 * lane]) = f.v[q];
+            const int i = (wave >> 1) + 2 * lane;
+            if ((wave & 1) == 0 && i < G0_H) taps[i] = make_uint2((f.taps & 0xffffu) << 12, (f.taps >> 16) << 12);
         }
-        const int2 ex = f.ex, ey = f.ey;
+        const int2 ex = f.ex;
         PYR_T(p1);
         __syncthreads();
         PYR_T(p2);
         if (itemN < items)   // the next tile's loads fly while this one is resized
-            fused_issue(f, arena0 + (size_t)frame_of(itemN) * imageStride + src_off, sw, tabs, jobs.j[dN.w], dN);
+            fused_issue(f, arena0 + (size_t)frame_of(itemN) * imageStride + src_off, sw, sh, tabs, jobs.j[dN.w], dN);
         PYR_T(p3);
-        {   // ---- resize: thread = one column of the tile, half of its rows.  A row's vertical taps (ytab) are the same for the whole
-            //      wavefront (fetched with the tile, lane = row; v_readlane): scalar address arithmetic; every row reads its four source bytes whether or not the
-            //      previous row shared one (reusing them saved 0.6 interpolations per pixel but chained every row behind an LDS round trip)
+        {   // ---- resize: thread = one column of the tile, half of its rows (0..17 / 17..34: row 17 is computed by both halves, the same
+            //      value stored twice, and nothing is predicated).  A row: its two byte pairs at fixed offsets (each read as s0 | s1 << 16
+            //      for v_dot2_u32_u16 against a0 | a1 << 16) and its taps as an LDS broadcast that no address waits for
             const int c = threadIdx.x & 127, half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
             if (c < G0_W) {
-                // the right neighbour is the next byte except in the image's last column, where its weight a1 is 0
-                const uint8_t* sp = stage + (ex.x - X0);
-                const unsigned int a0 = ex.y & 0xffff, a1 = (unsigned int)ex.y >> 16;
-                uint8_t* gp = g0 + c;
-                // A row's record in ONE register (lane == row): stage row of y0 (7 bits), b0, b1 (12 bits each).  The lower tap's row is the
-                // next stage row -- the table builder only fuses layers where y1 == y0 + 1 or b1 == 0 (every down-scaling layer) -- so a row
-                // costs one v_readlane, a handful of scalar instructions and one address add (round 5: two v_readlane, nine scalar
-                // instructions and two address computations per row and wavefront: as many scalar as vector instructions).
-                const unsigned int rowRec = (unsigned int)((ey.x & 0xffff) - Y0) | (((unsigned int)ey.y & 0xfffu) << 7) | ((((unsigned int)ey.y >> 16) & 0xfffu) << 19);
-                // three rows at a time: their twelve byte loads first, then the arithmetic (one LDS round trip per three rows).  The 35 rows
-                // are dealt as 0..17 / 17..34: row 17 is computed by both halves (the same value, stored twice) and nothing is predicated
                 const int rBase = half * (G0_H - 18);
-#pragma unroll 2
-                for (int i = 0; i < 18; i += 3) {
-                    unsigned int s00[3], s01[3], s10[3], s11[3], b0s[3], b1s[3];
+                // the right neighbour is the next byte except in the image's last column, where its weight a1 is 0.  A column that the
+                // reflection on a layer's right edge takes back left of the tile's first source column (e.g. 374 against 494 on the last
+                // tile of a 498-wide layer) only feeds pyrDown outputs past the layer's end: the clamp keeps its reads inside its slot
+                // (columns the tile keeps lie in 0 .. FS_PITCH - 1 already; 255 is the image's last column, whose neighbour weighs 0)
+                const int lx = min(max(ex.x - X0, 0), FS_PITCH - 1) + 2 * rBase * FS_PITCH;
+                // the right neighbour through an offset the compiler cannot relate to lx: it would otherwise merge the two byte reads into
+                // one ds_read_u16 at an odd address, which the LDS serves so slowly that the kernel took 4x as long (363 against 85 us)
+                int lx1 = lx + 1;
+                asm("" : "+v"(lx1));
+                const uint8_t *sp = stage + lx, *sp1 = stage + lx1;
+                const uint2* tp = taps + rBase;
+                const u16x2 aw = __builtin_bit_cast(u16x2, ex.y);
+                uint8_t* gp = g0 + rBase * G0_PITCH + c;
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const int r = rBase + i + q;
-                        const unsigned int e = (unsigned int)__builtin_amdgcn_readlane((int)rowRec, r);
-                        b0s[q] = ((e >> 7) & 0xfffu) << 12;   // b << 12 (<= 2^23): (b << 12) * (h & ~15) >> 32 == (b * (h >> 4)) >> 16
-                        b1s[q] = (e >> 19) << 12;
-                        const uint8_t* sr = sp + ((e & 127u) << 8);
-                        s00[q] = sr[0]; s01[q] = sr[1]; s10[q] = sr[FS_PITCH]; s11[q] = sr[FS_PITCH + 1];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const unsigned int h0 = mad24(s01[q], a1, mul24(s00[q], a0)) & ~15u;   // cv::resize's horizontal intermediate, times 16
-                        const unsigned int h1 = mad24(s11[q], a1, mul24(s10[q], a0)) & ~15u;
-                        const unsigned int v = (mulhi24_s(b0s[q], h0) + mulhi24_s(b1s[q], h1) + 2) >> 2;
-                        gp[(rBase + i + q) * G0_PITCH] = (uint8_t)v;
-                    }
+                for (int i = 0; i < 18; ++i) {
+                    const uint8_t *s = sp + 2 * i * FS_PITCH, *s1 = sp1 + 2 * i * FS_PITCH;
+                    const u16x2 p0 = {s[0], s1[0]}, p1 = {s[FS_PITCH], s1[FS_PITCH]};
+                    const uint2 t = tp[i];
+                    const unsigned int h0 = __builtin_amdgcn_udot2(p0, aw, 0u, false) & ~15u;   // cv::resize's horizontal intermediate, times 16
+                    const unsigned int h1 = __builtin_amdgcn_udot2(p1, aw, 0u, false) & ~15u;
+                    // b << 12 (<= 2^23): (b << 12) * (h & ~15) >> 32 == (b * (h >> 4)) >> 16
+                    gp[i * G0_PITCH] = (uint8_t)((mulhi24(t.x, h0) + mulhi24(t.y, h1) + 2) >> 2);
                 }
             }
         }
@@ -835,15 +835,14 @@ void build_gradient_lut(int bins, bool signedGradients, bool interpolate, std::v
     }
 }
 
-// cv::resize coordinate tables of the first-octave layers that feed a pyrDown chain (k_resize_down): the kernel's own float
-// expressions (k_resize_tiled's srcX / srcY), evaluated once per geometry on the host (this file is built with -ffp-contract=off)
+// cv::resize column tables of the first-octave layers that feed a pyrDown chain (k_resize_down): the kernel's own float
+// expressions (k_resize_tiled's srcX), evaluated once per geometry on the host (this file is built with -ffp-contract=off)
 void build_resize_tables(fd_pyramid* p, int W, int H) {
     p->rtab_x.assign(p->all.size(), ~0u);
-    p->rtab_y.assign(p->all.size(), ~0u);
     static const int mode = [] { const char* e = getenv("FD_PYR_FUSED"); return e ? atoi(e) : 1; }();   // 0: never, 1: default, 2: kept layers too
     if (mode == 0) return;
     std::vector<int2> tab;
-    // tiles of k_resize_down, one list per launch (MAXJ chains): {X0 | Y0 << 16, ncol | nrow << 16, tx | ty << 16, chain of the launch}
+    // tiles of k_resize_down, one list per launch (MAXJ chains): {X0, ncol, tx | ty << 16, chain of the launch}
     std::vector<std::vector<int4>> tiles;
     p->rtile_off.clear();
     p->rtile_cnt.clear();
@@ -861,8 +860,8 @@ void build_resize_tables(fd_pyramid* p, int W, int H) {
         // 101 + 4 x 68 us, round 4).  FD_PYR_FUSED=2 fuses those too (A/B).  Also measured in round 4 and dropped: persistent
         // k_pyrdown_tiled workgroups with the next tile's loads in flight (69 vs 63 us per 64-frame headline call).
         if (L.kept && mode != 2) continue;
-        const double scale_x = 1. / ((double)L.w / W), scale_y = 1. / ((double)L.h / H);
-        std::vector<int2> xt((size_t)L.w), yt((size_t)L.h);
+        const double scale_x = 1. / ((double)L.w / W);
+        std::vector<int2> xt((size_t)L.w);
         for (int dx = 0; dx < L.w; ++dx) {
             float fx = (float)((dx + 0.5) * scale_x - 0.5);
             int sx = (int)floorf(fx);
@@ -872,48 +871,27 @@ void build_resize_tables(fd_pyramid* p, int W, int H) {
             const int a0 = (int)nearbyintf((1.f - fx) * 2048), a1 = (int)nearbyintf(fx * 2048);
             xt[(size_t)dx] = make_int2(sx, a0 | (a1 << 16));
         }
-        for (int dy = 0; dy < L.h; ++dy) {
-            float fy = (float)((dy + 0.5) * scale_y - 0.5);
-            const int sy = (int)floorf(fy);
-            fy -= sy;
-            const int b0 = (int)nearbyintf((1.f - fy) * 2048), b1 = (int)nearbyintf(fy * 2048);
-            const int y0 = sy < 0 ? 0 : (sy >= H ? H - 1 : sy), y1 = sy + 1 < 0 ? 0 : (sy + 1 >= H ? H - 1 : sy + 1);
-            yt[(size_t)dy] = make_int2(y0 | (y1 << 16), b0 | (b1 << 16));
-        }
-        // every tile's source rectangle must fit the kernel's stage
+        // every tile's source columns must fit the kernel's stage (its rows are staged per resized row: no limit there)
         bool fits = true;
-        // the kernel reads a row's lower tap from the stage row behind its upper tap, and packs b0 / b1 into 12 bits each
-        for (int dy = 0; dy < L.h && fits; ++dy) {
-            const int y0 = yt[(size_t)dy].x & 0xffff, y1 = (int)((uint32_t)yt[(size_t)dy].x >> 16), b0 = yt[(size_t)dy].y & 0xffff, b1 = (int)((uint32_t)yt[(size_t)dy].y >> 16);
-            fits = (y1 == y0 + 1 || b1 == 0) && b0 >= 0 && b0 <= 2048 && b1 >= 0 && b1 <= 2048 && y1 >= y0;
-        }
         for (int x1 = 0; x1 < D.w && fits; x1 += FT_W1) {
             const int cLo = std::max(0, 2 * x1 - 2), cHi = std::min(L.w - 1, 2 * x1 - 2 + G0_W - 1);
             fits = std::min(W - 1, xt[(size_t)cHi].x + 1) - xt[(size_t)cLo].x + 1 <= FS_PITCH;
         }
-        for (int y1 = 0; y1 < D.h && fits; y1 += FT_H1) {
-            const int rLo = std::max(0, 2 * y1 - 2), rHi = std::min(L.h - 1, 2 * y1 - 2 + G0_H - 1);
-            fits = (yt[(size_t)rHi].x >> 16) - (yt[(size_t)rLo].x & 0xffff) + 1 <= FS_ROWS;
-        }
         if (!fits) continue;
-        {   // the source rectangle of every tile, exactly as the kernel's addressing expects it
+        {   // the source columns of every tile, exactly as the kernel's addressing expects them
             if (nfused % MAXJ == 0) tiles.emplace_back();
             std::vector<int4>& tl = tiles.back();
             for (int ty = 0; ty * FT_H1 < D.h; ++ty)
                 for (int tx = 0; tx * FT_W1 < D.w; ++tx) {
-                    const int gx0 = 2 * tx * FT_W1 - 2, gy0 = 2 * ty * FT_H1 - 2;
-                    const int cLo = std::max(0, gx0), cHi = std::min(L.w - 1, gx0 + G0_W - 1), rLo = std::max(0, gy0), rHi = std::min(L.h - 1, gy0 + G0_H - 1);
-                    const int X0 = xt[(size_t)cLo].x, Y0 = yt[(size_t)rLo].x & 0xffff;
-                    const int ncol = std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1, nrow = (yt[(size_t)rHi].x >> 16) - Y0 + 1;
-                    tl.push_back(make_int4((int)((uint32_t)X0 | (uint32_t)Y0 << 16), (int)((uint32_t)ncol | (uint32_t)nrow << 16),
-                                           (int)((uint32_t)tx | (uint32_t)ty << 16), nfused % MAXJ));
+                    const int gx0 = 2 * tx * FT_W1 - 2;
+                    const int cLo = std::max(0, gx0), cHi = std::min(L.w - 1, gx0 + G0_W - 1);
+                    const int X0 = xt[(size_t)cLo].x, ncol = std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1;
+                    tl.push_back(make_int4(X0, ncol, (int)((uint32_t)tx | (uint32_t)ty << 16), nfused % MAXJ));
                 }
             ++nfused;
         }
         p->rtab_x[k] = (uint32_t)tab.size();
         tab.insert(tab.end(), xt.begin(), xt.end());
-        p->rtab_y[k] = (uint32_t)tab.size();
-        tab.insert(tab.end(), yt.begin(), yt.end());
     }
     if (tab.empty()) return;
     for (const std::vector<int4>& tl : tiles) {   // 16-byte entries behind the 8-byte ones, 16-byte aligned
@@ -1071,7 +1049,8 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
             j.dw0 = L.w; j.dh0 = L.h; j.dw1 = D.w; j.dh1 = D.h;
             j.dst0_off = (L.kept && L.gray_off != p->gray_full_off) ? L.gray_off : 0xffffffffu;   // the scale-1 layer IS the gray image
             j.dst1_off = D.gray_off;
-            j.xtab = p->rtab_x[k]; j.ytab = p->rtab_y[k];
+            j.xtab = p->rtab_x[k];
+            j.scale_y = 1. / ((double)L.h / H);
             if (jobs.n == MAXJ) flush();
         }
         flush();
