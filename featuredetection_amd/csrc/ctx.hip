@@ -115,19 +115,11 @@ int fd_last_kernel_ms(fd_ctx* ctx, const char** kernel_name, float* ms) {
 }  // extern "C"
 
 FdAsyncQueue& fd_async_queue() {
-    static FdAsyncQueue q([] {
-        const char* e = getenv("FD_ASYNC_THREADS");
-        const int n = e ? atoi(e) : 2;
-        return n < 1 ? 1 : (n > 16 ? 16 : n);
-    }());
+    static FdAsyncQueue q(fd_env_int("FD_ASYNC_THREADS", 2, 1, 16));
     return q;
 }
 
 FdAsyncQueue& fd_batch_queue() {
-    static FdAsyncQueue q([] {
-        const char* e = getenv("FD_BATCH_THREADS");
-        const int n = e ? atoi(e) : 8;
-        return n < 1 ? 1 : (n > 16 ? 16 : n);
-    }());
+    static FdAsyncQueue q(fd_knob_batch_threads());
     return q;
 }

@@ -1,6 +1,7 @@
 // featuredetection_amd/csrc/fd_internal.hpp -- internal declarations of libfd_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -201,21 +202,29 @@ struct FdError {
         if (_e != hipSuccess) FD_THROW(FD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
+// Inside a catch (...): the exception in flight as an FdError (the one place that knows what a foreign exception becomes).
+static inline FdError fd_current_error() {
+    try {
+        throw;
+    } catch (const FdError& e) {
+        return e;
+    } catch (const std::exception& e) {
+        return FdError{FD_ERR_RUNTIME, e.what()};
+    } catch (...) {
+        return FdError{FD_ERR_RUNTIME, "unknown error"};
+    }
+}
+
 // Runs body, converts exceptions into status codes + ctx->error (no exceptions cross the C ABI).
 template <class F>
 static inline int fd_guard(fd_ctx* ctx, F&& body) {
     try {
         body();
         return FD_OK;
-    } catch (const FdError& e) {
+    } catch (...) {
+        const FdError e = fd_current_error();
         if (ctx) ctx->error = e.msg;
         return e.code;
-    } catch (const std::exception& e) {
-        if (ctx) ctx->error = e.what();
-        return FD_ERR_RUNTIME;
-    } catch (...) {
-        if (ctx) ctx->error = "unknown error";
-        return FD_ERR_RUNTIME;
     }
 }
 
@@ -286,8 +295,38 @@ static inline hipStream_t fd_tail_stream(fd_ctx* ctx) {
     return ctx->tail;
 }
 
+// ---- FD_* environment knobs that more than one place reads: one reader each, holding the default and the clamp.
+// Read once per process unless noted.
+static inline int fd_env_int(const char* name, int dflt, int lo, int hi) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : dflt;
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+// host threads of a large batch: the pool that queues its kernels / runs its host stages, and the threads of fd_batch_queue()
+static inline int fd_knob_batch_threads() { static const int v = fd_env_int("FD_BATCH_THREADS", 8, 1, 16); return v; }
+// rounds of resident workgroups the pre-filter's tiles are dealt over
+static inline int fd_knob_wvd_rounds() { static const int v = fd_env_int("FD_WVD_ROUNDS", 2, 1, 64); return v; }
+static inline bool fd_knob_trace() { static const bool on = getenv("FD_TRACE") != nullptr; return on; }
+// stages 2-3 on the device: 0 never, 1 always (batch jobs too), -1 (unset): multi-frame calls only.  Read per call: the tests flip it.
+static inline int fd_knob_fs_tail() { const char* e = getenv("FD_FS_TAIL"); return e ? atoi(e) : -1; }
+
+// FD_TRACE's stopwatch: lap_ns() is the time since the start (or the previous lap) and starts the next lap; off: no clock is read.
+struct FdStopwatch {
+    bool on = fd_knob_trace();
+    std::chrono::steady_clock::time_point t;
+    FdStopwatch() { restart(); }
+    void restart() { if (on) t = std::chrono::steady_clock::now(); }
+    int64_t lap_ns() {
+        if (!on) return 0;
+        const std::chrono::steady_clock::time_point n = std::chrono::steady_clock::now();
+        const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(n - t).count();
+        t = n;
+        return ns;
+    }
+};
+
 static inline hipStream_t fd_pool_stream(fd_ctx* ctx, int i) {
-    static const int nstreams = [] { const char* e = getenv("FD_BATCH_STREAMS"); int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 8 ? 8 : v); }();   // (8 since round 6: config 3 with the batch queue 9280 against 8910 Mpatches/s with 4)
+    static const int nstreams = fd_env_int("FD_BATCH_STREAMS", 8, 1, 8);
     hipStream_t& s = ctx->pool[i % nstreams];
     if (!s) HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     return s;

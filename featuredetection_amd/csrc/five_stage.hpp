@@ -2,10 +2,16 @@
 // behind the WVM entry points it builds on).
 //
 // detection::FiveStageSlidingWindowDetector::detect (FiveStageSlidingWindowDetector.cpp:187-320, :331-380) around the WVM cascade of
-// wvm.hip: the host tail (overlap elimination -> SVM launch -> block NMS: FiveStageTail), the device tail (fs_tail.hpp: k_fs_oe + the
-// counted SVM launch queued behind the cascade), and the entry points fd_detect_five_stage, fd_detect_five_stage_image,
-// fd_detect_five_stage_frames[_begin / _end] (all frames of a multi-frame pyramid in one cascade run) and
-// fd_detect_five_stage_batch / fd_five_stage_batch_begin / _end (several detectors on shared pyramids, ffpDetectApp.cpp:557-600).
+// wvm.hip.  Host code only.  Each stage exists once, and every entry point calls it:
+//   five_stage_nms                               stages 4-5: block NMS, sort
+//   five_stage_accept / five_stage_verdicts      stage 3's verdict (threshold, score, probability 0.5), host-tail flavour
+//   five_stage_svm_launch                        stage 3 of a host tail: slot list + distances in pinned memory, one generic SVM launch
+//   FiveStageTail                                the host tail in two halves (overlap elimination -> SVM launch | wait -> NMS)
+//   fst_launch / fst_collect / fst_verdicts / fst_frame   the device tail (fs_tail.hpp: k_fs_oe + the counted SVM launch queued behind
+//                                                the cascade) and what the host does with its survivor records
+// Entry points: fd_detect_five_stage, fd_detect_five_stage_image, fd_detect_five_stage_frames[_begin / _end] (all frames of a
+// multi-frame pyramid in one cascade run) and fd_detect_five_stage_batch / fd_five_stage_batch_begin / _end (several detectors on
+// shared pyramids, ffpDetectApp.cpp:557-600).  FD_TRACE timings go through FdStopwatch; exceptions become FdError in fd_current_error.
 #pragma once
 // Stages 4-5 of FiveStageSlidingWindowDetector::detect on the SVM positives of one image (FiveStageSlidingWindowDetector.cpp:
 // 262-320; the roi variant :360-380 only sorts): block NMS on the probability map, one detection per maximum, sorted by probability.
@@ -38,12 +44,47 @@ static void five_stage_nms(const fd_pyramid* p, const int* roi, std::vector<fd_d
     if (out && (int)svmPos.size() > cap) FD_THROW(FD_ERR_CAPACITY, "five-stage: %zu detections, capacity %d", svmPos.size(), cap);
 }
 
+// Stage 3's verdict on one survivor: strongClassifier->classify() gives a bool only, so a survivor at or above the SVM's threshold becomes
+// an SVM positive with the distance as its score and ClassifiedPatch(patch, bool)'s default probability (ClassifiedPatch.hpp:29-30).
+static inline void five_stage_accept(const fd_detection& survivor, double dist, std::vector<fd_detection>& svmPos) {
+    fd_detection d = survivor;
+    d.score = (float)dist;
+    d.positive = 1;
+    d.probability = 0.5;
+    svmPos.push_back(d);
+}
+// The verdicts of a host tail: survivor i is dets[keep[i]]; its distance is dist[i], or dist[slots[keep[i]]] where the SVM launch
+// covered every WVM positive by patch slot (the speculative launch of fd_detect_five_stage).
+static void five_stage_verdicts(const fd_svm* svm, const fd_detection* dets, const std::vector<int>& keep, const double* dist, const uint32_t* slots,
+                                std::vector<fd_detection>& svmPos) {
+    const double thr = (double)fd_svm_threshold(svm);
+    for (size_t i = 0; i < keep.size(); ++i) {
+        const double dv = dist[slots ? slots[keep[i]] : i];
+        if (dv >= thr) five_stage_accept(dets[keep[i]], dv, svmPos);
+    }
+}
+
+// Stage 3 of a host tail: the SVM on the survivors' HistEq64 patches (still resident in HBM, gathered by slot), queued on `st` with
+// m->tailDone recorded behind it.  The kernel reads the slot list from, and writes the distances to, the detector's pinned staging
+// [slots (u32) | distances (f64)] directly (a few KB over the fabric instead of two blit kernels and their launch gaps).  Returns where
+// the distances arrive.  Launches on `st` explicitly and touches the detector's own handle only: the tails of different jobs may run
+// on different host threads.
+static const double* five_stage_svm_launch(hipStream_t st, fd_wvm* m, const fd_svm* svm, const std::vector<uint32_t>& slots) {
+    const size_t distOff = (sizeof(uint32_t) * slots.size() + 15) & ~(size_t)15;
+    m->h_tail.reserve(distOff + sizeof(double) * slots.size());
+    char* pin = m->h_tail.as<char>();
+    std::memcpy(pin, slots.data(), sizeof(uint32_t) * slots.size());
+    fd_svm_generic_launch_on(st, svm, m->pos_patches.p, (const uint32_t*)pin, (int64_t)m->dev.d, (int64_t)slots.size(), (double*)(pin + distOff));
+    if (!m->tailDone) HIP_CHECK(hipEventCreateWithFlags(&m->tailDone, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(m->tailDone, st));
+    return (const double*)(pin + distOff);
+}
+
 // Stages 2-5 of FiveStageSlidingWindowDetector::detect (FiveStageSlidingWindowDetector.cpp:200-320 / :340-380) on a
 // finished WVM run, in two halves so that a batch can keep the host busy while the GPU is: begin() does the host stages up to
-// overlap elimination and queues the SVM on the survivors + its read-back on the stream `st` (event m->tailDone); end() waits
-// for that event and finishes with the block NMS.
+// overlap elimination and queues the SVM on the survivors on the stream `st` (event m->tailDone); end() waits for that event and
+// finishes with the block NMS.
 struct FiveStageTail {
-    fd_ctx* ctx = nullptr;
     fd_pyramid* p = nullptr;
     fd_wvm* m = nullptr;
     const fd_svm* svm = nullptr;
@@ -54,24 +95,18 @@ struct FiveStageTail {
     int32_t* stage_counts = nullptr;
     std::vector<fd_detection> wvmPos;
     std::vector<int> keep;
-    size_t distOff = 0;
+    const double* dist = nullptr;   // the survivors' distances once m->tailDone has passed
     bool pending = false, finished = false;
-    std::chrono::steady_clock::time_point t0;
+    FdStopwatch sw;
 
     void lap(const char* what) {
-        static const bool trace = getenv("FD_TRACE") != nullptr;
-        if (!trace) return;
-        auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[fd five-stage] %-12s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count());
-        t0 = t1;
+        if (sw.on) fprintf(stderr, "[fd five-stage] %-12s %8.1f us\n", what, sw.lap_ns() / 1e3);
     }
 
-    void begin(fd_ctx* ctx_, fd_pyramid* p_, fd_wvm* m_, const fd_svm* svm_, const WvmRun& run, float oe_dist, float oe_ratio, int sx, int sy,
-               const int* roi_, hipStream_t st, fd_detection* out_, int cap_, int* count_, int32_t* stage_counts_) {
-        ctx = ctx_; p = p_; m = m_; svm = svm_; roi = roi_; out = out_; cap = cap_; count = count_; stage_counts = stage_counts_;
-        t0 = std::chrono::steady_clock::now();
-        // everything below launches on `st` explicitly and touches no shared context state: tails of different jobs may run on
-        // different host threads (five_stage_batch_end)
+    void begin(fd_pyramid* p_, fd_wvm* m_, const fd_svm* svm_, const WvmRun& run, float oe_dist, float oe_ratio, int sx, int sy, const int* roi_,
+               hipStream_t st, fd_detection* out_, int cap_, int* count_, int32_t* stage_counts_) {
+        p = p_; m = m_; svm = svm_; roi = roi_; out = out_; cap = cap_; count = count_; stage_counts = stage_counts_;
+        sw.restart();
         fd_wvm_positives_to_detections(p, m, run, sx, sy, wvmPos);
         if (stage_counts) stage_counts[0] = (int)wvmPos.size();
         lap("to_dets");
@@ -79,30 +114,11 @@ struct FiveStageTail {
         fd_host_overlap_elimination(wvmPos.data(), (int)wvmPos.size(), oe_dist, oe_ratio, keep);
         if (stage_counts) stage_counts[1] = (int)keep.size();
         lap("oe");
-        // stage 3: SVM on the survivors' HistEq64 patches (still resident in HBM, gathered by slot)
+        // stage 3: SVM on the survivors
         if (!keep.empty()) {
             std::vector<uint32_t> slots(keep.size());
             for (size_t i = 0; i < keep.size(); ++i) slots[i] = run.slots[keep[i]];
-            DevBuf& idx = m->all_level;  // reuse scratch (not used by this call)
-            idx.reserve(sizeof(uint32_t) * slots.size());
-            m->all_fout.reserve(sizeof(double) * slots.size());
-            // pinned staging of this detector: [slots (u32) | distances (f64)].  The kernel reads the slot list from, and writes
-            // the distances to, this host-mapped buffer directly (a few KB over the fabric instead of two blit kernels and their
-            // launch gaps on the tail stream); FD_WVM_ZEROCOPY=0: explicit copies through device scratch.
-            static const bool zcOff = [] { const char* e = getenv("FD_WVM_ZEROCOPY"); return e && atoi(e) == 0; }();
-            distOff = (sizeof(uint32_t) * slots.size() + 15) & ~(size_t)15;
-            m->h_tail.reserve(distOff + sizeof(double) * slots.size());
-            char* pin = m->h_tail.as<char>();
-            std::memcpy(pin, slots.data(), sizeof(uint32_t) * slots.size());
-            if (zcOff) {
-                HIP_CHECK(hipMemcpyAsync(idx.p, pin, sizeof(uint32_t) * slots.size(), hipMemcpyHostToDevice, st));
-                fd_svm_generic_launch_on(st, svm, m->pos_patches.p, idx.as<uint32_t>(), (int64_t)m->dev.d, (int64_t)slots.size(), m->all_fout.as<double>());
-                HIP_CHECK(hipMemcpyAsync(pin + distOff, m->all_fout.p, sizeof(double) * slots.size(), hipMemcpyDeviceToHost, st));
-            } else {
-                fd_svm_generic_launch_on(st, svm, m->pos_patches.p, (const uint32_t*)pin, (int64_t)m->dev.d, (int64_t)slots.size(), (double*)(pin + distOff));
-            }
-            if (!m->tailDone) HIP_CHECK(hipEventCreateWithFlags(&m->tailDone, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(m->tailDone, st));
+            dist = five_stage_svm_launch(st, m, svm, slots);
             pending = true;
         }
         lap("svm launch");
@@ -114,21 +130,12 @@ struct FiveStageTail {
     void end() {
         if (finished) return;
         finished = true;
-        t0 = std::chrono::steady_clock::now();
+        sw.restart();
         std::vector<fd_detection> svmPos;
         if (pending) {
             HIP_CHECK(hipEventSynchronize(m->tailDone));
             pending = false;
-            const double* dist = (const double*)(m->h_tail.as<char>() + distOff);
-            for (size_t i = 0; i < keep.size(); ++i) {
-                if (dist[i] >= (double)fd_svm_threshold(svm)) {  // strongClassifier->classify(): bool only
-                    fd_detection d = wvmPos[keep[i]];
-                    d.score = (float)dist[i];
-                    d.positive = 1;
-                    d.probability = 0.5;  // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                    svmPos.push_back(d);
-                }
-            }
+            five_stage_verdicts(svm, wvmPos.data(), keep, dist, nullptr, svmPos);
         }
         lap("svm wait");
         five_stage_nms(p, roi, svmPos, out, cap, count, stage_counts);
@@ -136,29 +143,22 @@ struct FiveStageTail {
     }
 };
 
-static void five_stage_tail(fd_ctx* ctx, fd_pyramid* p, fd_wvm* m, const fd_svm* svm, const WvmRun& run, float oe_dist, float oe_ratio,
-                            int sx, int sy, const int* roi, hipStream_t st, fd_detection* out, int cap, int* count, int32_t* stage_counts) {
-    FiveStageTail t;
-    t.begin(ctx, p, m, svm, run, oe_dist, oe_ratio, sx, sy, roi, st, out, cap, count, stage_counts);
-    t.end();
-}
-
 static void five_stage_check(const fd_wvm* m, const fd_svm* svm) {
     if (fd_svm_dim(svm) != m->dev.d || !fd_svm_is_u8(svm))
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "second classifier must work on the %d-byte HistEq64 patch", m->dev.d);
 }
 
 // ---- stages 2-3 on the device (fs_tail.hpp) ------------------------------------------------------------------------------------
-// Whether a five-stage run of (m, svm) can keep its tail on the device: the cascade ends in the dense stage B with its zero-copy
-// header, the second classifier has the u8 RBF MFMA kernel, and the window ids of the call fit 32 bits.  FD_FS_TAIL=0: never.
+// What a run of (m, svm) needs to keep its tail on the device, or to queue the SVM speculatively behind the cascade: the cascade ends
+// in the dense stage B with its zero-copy header, and the second classifier has the u8 RBF MFMA kernel.
+static bool fst_model_ok(const fd_wvm* m, const fd_svm* svm) { return m->wvbOk && m->dev.numUsed > WVM_LCAP && fd_svm_u8_mfma_available(svm); }
+// FD_FS_TAIL unset: the device tail for multi-frame calls only.  A single frame has ~150 positives: the host sorts and sweeps them in
+// ~7 us, less than k_fs_oe's launch + its 15 us (measured: 155 vs 167 us per blocking single-frame call); a 64-frame call has ~10 K,
+// 0.7 ms of host work that the device does in the shadow of the next call's kernels.
 static bool fst_possible(const fd_wvm* m, const fd_svm* svm, int nimg) {
-    // FD_FS_TAIL (read per call: tests toggle it): 0 never, 1 always, unset: for multi-frame calls only.  A single frame has ~150
-    // positives: the host sorts and sweeps them in ~7 us, less than k_fs_oe's launch + its 15 us (measured: 155 vs 167 us per blocking
-    // single-frame call); a 64-frame call has ~10 K, 0.7 ms of host work that the device does in the shadow of the next call's kernels.
-    const char* e = getenv("FD_FS_TAIL");
-    const int mode = e ? atoi(e) : -1;
+    const int mode = fd_knob_fs_tail();
     if (mode == 0 || (mode != 1 && nimg < 2)) return false;
-    return m->wvbOk && m->dev.numUsed > WVM_LCAP && fd_svm_u8_mfma_available(svm);
+    return fst_model_ok(m, svm);
 }
 // The jobs of a batch (one frame each, fd_detect_five_stage_batch / fd_five_stage_batch_begin): overlap elimination on the device by
 // k_fs_oe_big, whatever the number of positives (config 3 / 5: ~13 K per detector and frame, 0.9 ms of std::sort + painted map per job on a
@@ -167,15 +167,10 @@ static bool fst_possible(const fd_wvm* m, const fd_svm* svm, int nimg) {
 // compute unit on the job's stream, and with the default four queues the streams behind such a kernel stall (config 3: 4.8 G patches/s
 // against the host stages' 5.3 G on eight threads); with six queues the tails overlap and the device wins with a quarter of the host
 // threads (5.6 G on two threads).  The results are the same bytes either way.
-static bool fst_possible_batch(const fd_wvm* m, const fd_svm* svm) {
-    const char* e = getenv("FD_FS_TAIL");
-    if (!e || atoi(e) != 1) return false;
-    return m->wvbOk && m->dev.numUsed > WVM_LCAP && fd_svm_u8_mfma_available(svm);
-}
+static bool fst_possible_batch(const fd_wvm* m, const fd_svm* svm) { return fd_knob_fs_tail() == 1 && fst_model_ok(m, svm); }
 static bool spec_possible(const fd_wvm* m, const fd_svm* svm) {
     const char* e = getenv("FD_FS_SPEC");   // read per call: the tests compare both orders
-    const bool off = e && atoi(e) == 0;
-    return !off && m->wvbOk && m->dev.numUsed > WVM_LCAP && fd_svm_u8_mfma_available(svm);
+    return !(e && atoi(e) == 0) && fst_model_ok(m, svm);
 }
 static size_t fst_host_offsets(int nimg, int64_t cap, size_t& keepOff, size_t& distOff) {
     keepOff = (16 + sizeof(FstFrame) * (size_t)nimg + 15) & ~(size_t)15;
@@ -284,7 +279,6 @@ static bool fst_collect(fd_ctx* ctx, fd_wvm* m, const fd_svm* svm, const WvmRun&
     R.frames = reinterpret_cast<const FstFrame*>(hb + 16);
     R.keep = reinterpret_cast<const FstKeep*>(hb + keepOff);
     R.dist = reinterpret_cast<const double*>(hb + distOff);
-    (void)run;
     return true;
 }
 // a survivor record -> the detection the reference's ClassifiedPatch stands for
@@ -297,6 +291,31 @@ static fd_detection fst_detection(const fd_pyramid* p, const fd_wvm* m, const Wv
     d.score = k.fout;
     d.probability = wvm_probability(m, (double)k.fout);
     return d;
+}
+// The verdicts of a device tail on frame `fr`'s survivor records.  fouts: the bit patterns of the SVM positives' WVM outputs (batch jobs).
+static void fst_verdicts(const fd_pyramid* p, const fd_wvm* m, const fd_svm* svm, const WvmRun& run, int sx, int sy, const FstResult& R, const FstFrame& fr,
+                         std::vector<fd_detection>& svmPos, std::vector<uint32_t>* fouts = nullptr) {
+    const double thr = (double)fd_svm_threshold(svm);
+    for (uint32_t j = 0; j < fr.nkeep; ++j) {
+        const double dv = R.dist[fr.base + j];
+        if (!(dv >= thr)) continue;
+        const FstKeep& k = R.keep[fr.base + j];
+        five_stage_accept(fst_detection(p, m, run, sx, sy, k), dv, svmPos);
+        if (fouts) {
+            uint32_t fb;
+            std::memcpy(&fb, &k.fout, 4);
+            fouts->push_back(fb);
+        }
+    }
+}
+// Stages 4-5 of frame f behind a device tail that delivered (fst_collect): the stage counts, the SVM's verdicts, the block NMS; svmPos
+// becomes the frame's result.
+static void fst_frame(const fd_pyramid* p, const fd_wvm* m, const fd_svm* svm, const WvmRun& run, int sx, int sy, const int* roi, const FstResult& R, int f,
+                      std::vector<fd_detection>& svmPos, fd_detection* out, int cap, int* count, int32_t* stage_counts) {
+    const FstFrame fr = R.frames[f];
+    if (stage_counts) { stage_counts[0] = (int)fr.npos; stage_counts[1] = (int)fr.nkeep; }
+    fst_verdicts(p, m, svm, run, sx, sy, R, fr, svmPos);
+    five_stage_nms(p, roi, svmPos, out, cap, count, stage_counts);
 }
 
 // detection::FiveStageSlidingWindowDetector::detect, FiveStageSlidingWindowDetector.cpp:187-320 / :331-380
@@ -332,19 +351,8 @@ int fd_detect_five_stage(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, const f
             fst_launch(ctx, ctx->stream, p, m, svm, run, oe_dist, oe_ratio, sx, sy);
             FstResult R;
             if (fst_collect(ctx, m, svm, run, R)) {
-                const FstFrame fr = R.frames[0];
                 std::vector<fd_detection> svmPos;
-                for (uint32_t j = 0; j < fr.nkeep; ++j) {
-                    const double dv = R.dist[fr.base + j];
-                    if (dv >= (double)fd_svm_threshold(svm)) {
-                        fd_detection d = fst_detection(p, m, run, sx, sy, R.keep[fr.base + j]);
-                        d.score = (float)dv;
-                        d.probability = 0.5;   // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                        svmPos.push_back(d);
-                    }
-                }
-                if (stage_counts) { stage_counts[0] = (int)fr.npos; stage_counts[1] = (int)fr.nkeep; }
-                five_stage_nms(p, roi, svmPos, out, cap, count, stage_counts);
+                fst_frame(p, m, svm, run, sx, sy, roi, R, 0, svmPos, out, cap, count, stage_counts);
                 return;
             }
             run.timed = false;   // read above
@@ -360,22 +368,14 @@ int fd_detect_five_stage(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, const f
             if (stage_counts) stage_counts[0] = (int)wvmPos.size();
             fd_host_overlap_elimination(wvmPos.data(), (int)wvmPos.size(), oe_dist, oe_ratio, keep);
             if (stage_counts) stage_counts[1] = (int)keep.size();
-            const double* dist = m->h_spec.as<double>();
-            for (size_t i = 0; i < keep.size(); ++i) {
-                const double dv = dist[run.slots[keep[i]]];
-                if (dv >= (double)fd_svm_threshold(svm)) {   // strongClassifier->classify(): bool only
-                    fd_detection d = wvmPos[keep[i]];
-                    d.score = (float)dv;
-                    d.positive = 1;
-                    d.probability = 0.5;   // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                    svmPos.push_back(d);
-                }
-            }
+            five_stage_verdicts(svm, wvmPos.data(), keep, m->h_spec.as<double>(), run.slots.data(), svmPos);
             five_stage_nms(p, roi, svmPos, out, cap, count, stage_counts);
             return;
         }
         if (specQueued) m->specPrev = (int64_t)run.pos.size();
-        five_stage_tail(ctx, p, m, svm, run, oe_dist, oe_ratio, sx, sy, roi, ctx->stream, out, cap, count, stage_counts);
+        FiveStageTail t;
+        t.begin(p, m, svm, run, oe_dist, oe_ratio, sx, sy, roi, ctx->stream, out, cap, count, stage_counts);
+        t.end();
     });
 }
 
@@ -435,12 +435,11 @@ static void five_stage_frames_begin(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wv
 // ticket holds and the context's stream only.
 // FD_TRACE: where the host stages of the multi-frame calls spend their time (averages per call on stderr at process exit)
 struct FramesHostTrace {
-    const bool on = getenv("FD_TRACE") != nullptr;
     std::atomic<int64_t> ns[6], calls{0};
     FramesHostTrace() { for (auto& v : ns) v = 0; }
     ~FramesHostTrace() {
         const int64_t n = calls.load();
-        if (!on || n == 0) return;
+        if (n == 0) return;
         static const char* name[6] = {"wait for the cascade + order positives", "positives -> detections", "overlap elimination", "SVM launch + wait", "NMS", "total"};
         for (int i = 0; i < 6; ++i) fprintf(stderr, "[fd frames host] %-40s %9.1f us per call (%lld calls)\n", name[i], ns[i].load() / 1e3 / n, (long long)n);
     }
@@ -448,14 +447,11 @@ struct FramesHostTrace {
 static FramesHostTrace g_framesTrace;
 
 static void five_stage_frames_host(fd_ctx* ctx, fd_five_stage_frames& t) {
-    using clk = std::chrono::steady_clock;
-    const bool tr = g_framesTrace.on;
-    clk::time_point tp0 = tr ? clk::now() : clk::time_point(), tp = tp0;
-    auto lap = [&](int i) {
-        if (!tr) return;
-        const clk::time_point n = clk::now();
-        g_framesTrace.ns[i] += std::chrono::duration_cast<std::chrono::nanoseconds>(n - tp).count();
-        tp = n;
+    FdStopwatch sw, whole;
+    auto lap = [&](int i) { if (sw.on) g_framesTrace.ns[i] += sw.lap_ns(); };
+    auto done = [&] {
+        lap(4);
+        if (whole.on) { g_framesTrace.ns[5] += whole.lap_ns(); ++g_framesTrace.calls; }
     };
     fd_pyramid* p = t.p;
     fd_wvm* m = t.m;
@@ -463,34 +459,15 @@ static void five_stage_frames_host(fd_ctx* ctx, fd_five_stage_frames& t) {
     const int* roi = t.has_roi ? t.roi : nullptr;
     WvmRun& run = t.run;
     const int NF = p->nimg;
+    int cnt = 0;
     t.res.assign((size_t)NF, {});
     t.stages.assign((size_t)NF * 4, 0);
     if (t.tail) {
         FstResult R;
-        if (fst_collect(ctx, m, svm, run, R)) {   // the device did stages 2-3: per frame the SVM's verdicts, then the block NMS
+        if (fst_collect(ctx, m, svm, run, R)) {   // the device did stages 2-3
             lap(0);
-            for (int f = 0; f < NF; ++f) {
-                const FstFrame fr = R.frames[f];
-                t.stages[4 * (size_t)f] = (int)fr.npos;
-                t.stages[4 * (size_t)f + 1] = (int)fr.nkeep;
-                std::vector<fd_detection>& svmPos = t.res[(size_t)f];
-                for (uint32_t j = 0; j < fr.nkeep; ++j) {
-                    const double dv = R.dist[fr.base + j];
-                    if (dv >= (double)fd_svm_threshold(svm)) {
-                        fd_detection d = fst_detection(p, m, run, t.sx, t.sy, R.keep[fr.base + j]);
-                        d.score = (float)dv;
-                        d.probability = 0.5;   // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                        svmPos.push_back(d);
-                    }
-                }
-                int cnt = 0;
-                five_stage_nms(p, roi, svmPos, nullptr, 0, &cnt, &t.stages[4 * (size_t)f]);
-            }
-            lap(4);
-            if (tr) {
-                g_framesTrace.ns[5] += std::chrono::duration_cast<std::chrono::nanoseconds>(clk::now() - tp0).count();
-                ++g_framesTrace.calls;
-            }
+            for (int f = 0; f < NF; ++f) fst_frame(p, m, svm, run, t.sx, t.sy, roi, R, f, t.res[(size_t)f], nullptr, 0, &cnt, &t.stages[4 * (size_t)f]);
+            done();
             return;
         }
         run.timed = false;   // fst_collect has read the kernel timing
@@ -527,41 +504,17 @@ static void five_stage_frames_host(fd_ctx* ctx, fd_five_stage_frames& t) {
     }
     lap(2);
     const double* dist = nullptr;
-    if (!slots.empty()) {   // the SVM stage of all frames: the kernel reads the slot list from / writes the distances to pinned memory
-        hipStream_t st = ctx->stream;
-        const size_t distOff = (sizeof(uint32_t) * slots.size() + 15) & ~(size_t)15;
-        m->h_tail.reserve(distOff + sizeof(double) * slots.size());
-        char* pin = m->h_tail.as<char>();
-        std::memcpy(pin, slots.data(), sizeof(uint32_t) * slots.size());
-        fd_svm_generic_launch_on(st, svm, m->pos_patches.p, (const uint32_t*)pin, (int64_t)m->dev.d, (int64_t)slots.size(), (double*)(pin + distOff));
-        if (!m->tailDone) HIP_CHECK(hipEventCreateWithFlags(&m->tailDone, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(m->tailDone, st));
+    if (!slots.empty()) {   // the SVM stage of all frames in one launch
+        dist = five_stage_svm_launch(ctx->stream, m, svm, slots);
         HIP_CHECK(hipEventSynchronize(m->tailDone));   // only this call's SVM stage, not what the caller queued behind it
-        dist = (const double*)(pin + distOff);
     }
     lap(3);
-    size_t si = 0;
     for (int f = 0; f < NF; ++f) {
-        std::vector<fd_detection>& svmPos = t.res[(size_t)f];
-        const size_t b = begin[(size_t)f];
-        for (int k : keep[(size_t)f]) {
-            const double dv = dist[si++];
-            if (dv >= (double)fd_svm_threshold(svm)) {
-                fd_detection d = dets[b + (size_t)k];
-                d.score = (float)dv;
-                d.positive = 1;
-                d.probability = 0.5;   // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                svmPos.push_back(d);
-            }
-        }
-        int cnt = 0;
-        five_stage_nms(p, roi, svmPos, nullptr, 0, &cnt, &t.stages[4 * (size_t)f]);   // svmPos becomes the frame's result
+        five_stage_verdicts(svm, dets.data() + begin[(size_t)f], keep[(size_t)f], dist, nullptr, t.res[(size_t)f]);
+        dist += keep[(size_t)f].size();
+        five_stage_nms(p, roi, t.res[(size_t)f], nullptr, 0, &cnt, &t.stages[4 * (size_t)f]);   // the frame's result
     }
-    lap(4);
-    if (tr) {
-        g_framesTrace.ns[5] += std::chrono::duration_cast<std::chrono::nanoseconds>(clk::now() - tp0).count();
-        ++g_framesTrace.calls;
-    }
+    done();
 }
 
 static void five_stage_frames_end(fd_ctx* ctx, fd_five_stage_frames& t, fd_detection* out, int cap_per_frame, int32_t* counts, int32_t* stage_counts) {
@@ -668,7 +621,7 @@ static void five_stage_batch_submit(fd_ctx* ctx, fd_five_stage_batch& b) {
             fd_wvm* m = const_cast<fd_wvm*>(j.wvm);
             fd_wvm_finish(ctx, m, bp->runs[(size_t)i]);
             FiveStageTail& t = bp->tails[(size_t)i];
-            t.begin(ctx, j.pyramid, m, j.svm, bp->runs[(size_t)i], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi, tailStream, j.out, j.cap,
+            t.begin(j.pyramid, m, j.svm, bp->runs[(size_t)i], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi, tailStream, j.out, j.cap,
                     &bp->counts[(size_t)i], j.stage_counts);
             t.end();
             j.count = bp->counts[(size_t)i];
@@ -678,7 +631,7 @@ static void five_stage_batch_submit(fd_ctx* ctx, fd_five_stage_batch& b) {
 
 static void five_stage_batch_begin(fd_ctx* ctx, fd_five_stage_job* jobs, int n, fd_five_stage_batch& b) {
     if (!ctx || n < 0 || (n > 0 && !jobs)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_detect_five_stage_batch: bad argument");
-    const auto tBegin0 = std::chrono::steady_clock::now();
+    FdStopwatch sw;
     b.jobs = jobs;
     b.n = n;
     b.runs.assign((size_t)n, WvmRun());
@@ -769,7 +722,7 @@ static void five_stage_batch_begin(fd_ctx* ctx, fd_five_stage_job* jobs, int n, 
     // A frame costs ~15 runtime calls (pyramid kernels, cascade kernels, copies, events): with many small jobs the single host
     // thread issuing them is the bottleneck, so batches of >= 6 jobs are issued by the worker pool -- all pyramid updates first
     // (jobs may share a pyramid one of them updates), then all cascades.  Each job has its own stream, handles and buffers.
-    static const int nthreads = [] { const char* e = getenv("FD_BATCH_THREADS"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
+    const int nthreads = fd_knob_batch_threads();
     if (nthreads > 1 && n >= 6) {
         if (!ctx->workers) ctx->workers.reset(new FdWorkerPool(nthreads - 1));
         std::mutex errMu;
@@ -780,15 +733,10 @@ static void five_stage_batch_begin(fd_ctx* ctx, fd_five_stage_job* jobs, int n, 
                 (void)hipSetDevice(ctx->device);
                 for (int i; (i = next.fetch_add(1)) < count;) {
                     // nothing may leave a pool thread's body (std::terminate): vector / DevBuf growth can throw bad_alloc etc.
-                    try { f(i); } catch (const FdError& e) {
+                    try { f(i); } catch (...) {
+                        const FdError e = fd_current_error();
                         std::lock_guard<std::mutex> lk(errMu);
                         if (firstErr.code == FD_OK) firstErr = e;
-                    } catch (const std::exception& e) {
-                        std::lock_guard<std::mutex> lk(errMu);
-                        if (firstErr.code == FD_OK) firstErr = FdError{FD_ERR_RUNTIME, e.what()};
-                    } catch (...) {
-                        std::lock_guard<std::mutex> lk(errMu);
-                        if (firstErr.code == FD_OK) firstErr = FdError{FD_ERR_RUNTIME, "unknown error on a batch worker thread"};
                     }
                 }
             });
@@ -802,17 +750,13 @@ static void five_stage_batch_begin(fd_ctx* ctx, fd_five_stage_job* jobs, int n, 
         for (int i = 0; i < n; ++i) updateJob(i);
         for (int ui = 0; ui < nunits; ++ui) cascadeJob(ui);
     }
-    static const bool trace = getenv("FD_TRACE") != nullptr;
-    if (trace)
-        fprintf(stderr, "[fd batch] begin: %d cascades queued in %.1f us\n", n,
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tBegin0).count());
+    if (sw.on) fprintf(stderr, "[fd batch] begin: %d cascades queued in %.1f us\n", n, sw.lap_ns() / 1e3);
 }
 
 static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
     fd_five_stage_job* jobs = b.jobs;
     const int n = b.n;
-    static const bool trace = getenv("FD_TRACE") != nullptr;
-    const auto tEnd0 = std::chrono::steady_clock::now();
+    FdStopwatch whole;
     double waitUs = 0;
     // The host takes the detectors one by one: as soon as a cascade is done, its positives are read back and
     // thinned out by the overlap elimination while the GPU works on the later cascades; the SVM stage of the survivors is
@@ -835,7 +779,7 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
     // claims a detector whose cascade has finished, reads its positives back, runs the overlap elimination, queues the SVM stage
     // on the shared high-priority stream, waits for it and finishes with the NMS.  Everything a worker touches belongs to its
     // job (WVM handle, pinned staging, events); the streams are created up front.  FD_BATCH_THREADS=1 keeps it on the caller.
-    static const int nthreads = [] { const char* e = getenv("FD_BATCH_THREADS"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
+    const int nthreads = fd_knob_batch_threads();
     // ---- jobs whose stages 2-3 ran on the device: the SVM's verdicts, then the block NMS (a few hundred elements per job: this thread).
     // A job whose device tail gave up (overlapping ties, an overflow, parameters the painted map does not cover) or whose SVM positives
     // hold two equal WVM outputs (fs_tail.hpp: the order of tied survivors is the reference's std::sort's) takes the host stages below.
@@ -845,7 +789,7 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
         for (int i = 0; i < n; ++i) {
             if (!b.tasks[(size_t)i]) continue;
             std::shared_ptr<FdAsyncTask> task = std::move(b.tasks[(size_t)i]);
-            try { task->wait(); } catch (const FdError& e) { fail(i, e); } catch (const std::exception& e) { fail(i, FdError{FD_ERR_RUNTIME, e.what()}); }
+            try { task->wait(); } catch (...) { fail(i, fd_current_error()); }
             doneByTail[(size_t)i] = 1;
             tails[(size_t)i].finished = true;
             ++ndone;
@@ -861,22 +805,11 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
             const FstFrame fr = R.frames[0];
             std::vector<fd_detection> svmPos;
             std::vector<uint32_t> bits;
-            for (uint32_t q = 0; q < fr.nkeep; ++q) {
-                const double dv = R.dist[fr.base + q];
-                if (dv >= (double)fd_svm_threshold(j.svm)) {
-                    const FstKeep& k = R.keep[fr.base + q];
-                    fd_detection d = fst_detection(j.pyramid, m, b.runs[i], j.step_x, j.step_y, k);
-                    d.score = (float)dv;
-                    d.probability = 0.5;   // ClassifiedPatch(patch, bool) default probability (ClassifiedPatch.hpp:29-30)
-                    svmPos.push_back(d);
-                    uint32_t fb;
-                    std::memcpy(&fb, &k.fout, 4);
-                    bits.push_back(fb);
-                }
-            }
+            fst_verdicts(j.pyramid, m, j.svm, b.runs[i], j.step_x, j.step_y, R, fr, svmPos, &bits);
             std::sort(bits.begin(), bits.end());
             if (std::adjacent_find(bits.begin(), bits.end()) != bits.end()) { m->fstLastState = 0x200; continue; }   // tied survivors among the SVM positives
-            if (j.stage_counts) { j.stage_counts[0] = (int)fr.npos; j.stage_counts[1] = (int)fr.nkeep; }
+            j.stage_counts[0] = (int)fr.npos;
+            j.stage_counts[1] = (int)fr.nkeep;
             five_stage_nms(j.pyramid, j.roi, svmPos, j.out, j.cap, &counts[i], j.stage_counts);
             j.count = counts[i];
             doneByTail[i] = 1;
@@ -891,6 +824,9 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
         if (firstError != FD_OK) throw FdError{firstError, ctx->error};
         return;
     }
+    auto cascadeDone = [&](int i) {   // an error surfaces in fd_wvm_finish
+        return b.runs[i].total == 0 || hipEventQuery(jobs[i].wvm->done) != hipErrorNotReady;
+    };
     int64_t totalWindows = 0;
     for (int i = 0; i < n; ++i) totalWindows += b.runs[i].total;
     if (nthreads > 1 && (n - ndone >= 6 || totalWindows >= (int64_t)4 << 20) && n - ndone >= 2) {
@@ -900,9 +836,6 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
         std::vector<std::atomic<char>> claimed((size_t)n);
         for (int i = 0; i < n; ++i) claimed[i].store(doneByTail[i]);
         std::mutex errMu;
-        auto cascadeDone = [&](int i) {
-            return b.runs[i].total == 0 || hipEventQuery(jobs[i].wvm->done) != hipErrorNotReady;
-        };
         auto work = [&] {
             (void)hipSetDevice(ctx->device);
             for (;;) {
@@ -922,29 +855,20 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
                 fd_wvm* m = const_cast<fd_wvm*>(j.wvm);
                 try {
                     fd_wvm_finish(ctx, m, b.runs[pick]);
-                    tails[pick].begin(ctx, j.pyramid, m, j.svm, b.runs[pick], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi,
+                    tails[pick].begin(j.pyramid, m, j.svm, b.runs[pick], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi,
                                       tailStream, j.out, j.cap, &counts[pick], j.stage_counts);
                     tails[pick].end();
                     j.count = counts[pick];
-                } catch (const FdError& e) {
+                } catch (...) {   // pool thread: nothing may escape
+                    const FdError e = fd_current_error();
                     std::lock_guard<std::mutex> lk(errMu);
                     tails[pick].finished = true;
                     fail(pick, e);
-                } catch (const std::exception& e) {   // pool thread: nothing else may escape
-                    std::lock_guard<std::mutex> lk(errMu);
-                    tails[pick].finished = true;
-                    fail(pick, FdError{FD_ERR_RUNTIME, e.what()});
-                } catch (...) {
-                    std::lock_guard<std::mutex> lk(errMu);
-                    tails[pick].finished = true;
-                    fail(pick, FdError{FD_ERR_RUNTIME, "unknown error on a batch worker thread"});
                 }
             }
         };
         ctx->workers->run(work);
-        if (trace)
-            fprintf(stderr, "[fd batch] end: %.1f us in total on %d host threads\n",
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tEnd0).count(), nthreads);
+        if (whole.on) fprintf(stderr, "[fd batch] end: %.1f us in total on %d host threads\n", whole.lap_ns() / 1e3, nthreads);
         if (firstError != FD_OK) throw FdError{firstError, ctx->error};
         return;
     }
@@ -956,14 +880,10 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
     int nbegun0 = 0;
     for (int i = 0; i < n; ++i)
         if (doneByTail[i]) { begun[i] = 1; tails[i].finished = true; ++nbegun0; }
-    auto cascadeReady = [&](int i) {
-        const fd_wvm* m = jobs[i].wvm;
-        return b.runs[i].total == 0 || hipEventQuery(m->done) != hipErrorNotReady;   // an error surfaces in fd_wvm_finish
-    };
     for (int nbegun = nbegun0; nbegun < n;) {
         int pick = -1;
         for (int i = 0; i < n && pick < 0; ++i)
-            if (!begun[i] && cascadeReady(i)) pick = i;
+            if (!begun[i] && cascadeDone(i)) pick = i;
         if (pick < 0) {   // nothing to start: use the time for the NMS of a detector whose SVM stage has arrived, else yield
             bool did = false;
             for (int k = 0; k < n && !did; ++k)
@@ -977,14 +897,14 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
         fd_five_stage_job& j = jobs[i];
         fd_wvm* m = const_cast<fd_wvm*>(j.wvm);
         try {
-            const auto tw0 = std::chrono::steady_clock::now();
+            FdStopwatch sw;
             fd_wvm_finish(ctx, m, b.runs[i]);
-            if (trace) {
-                const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw0).count();
+            if (sw.on) {
+                const double us = sw.lap_ns() / 1e3;
                 waitUs += us;
                 fprintf(stderr, "[fd batch] job %2d cascade wait + read-back %8.1f us (%zu positives)\n", i, us, b.runs[i].pos.size());
             }
-            tails[i].begin(ctx, j.pyramid, m, j.svm, b.runs[i], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi,
+            tails[i].begin(j.pyramid, m, j.svm, b.runs[i], j.oe_dist, j.oe_ratio, j.step_x, j.step_y, j.roi,
                            fd_tail_stream(ctx), j.out, j.cap, &counts[i], j.stage_counts);
         } catch (const FdError& e) {
             tails[i].finished = true;
@@ -995,9 +915,7 @@ static void five_stage_batch_end(fd_ctx* ctx, fd_five_stage_batch& b) {
     }
     for (int i = 0; i < n; ++i)
         if (!tails[i].finished) finish(i);
-    if (trace)
-        fprintf(stderr, "[fd batch] end: %.1f us in total, %.1f us of it waiting for cascades\n",
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tEnd0).count(), waitUs);
+    if (whole.on) fprintf(stderr, "[fd batch] end: %.1f us in total, %.1f us of it waiting for cascades\n", whole.lap_ns() / 1e3, waitUs);
     if (firstError != FD_OK) throw FdError{firstError, ctx->error};
 }
 

@@ -1364,9 +1364,7 @@ static void launch_prefilter_sized(fd_ctx* ctx, hipStream_t st, const uint8_t* a
     if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_wvm_prefilter<PW_, PH_>, 256, 0) != hipSuccess || perCu < 1)) perCu = 2;
     const int slots = ctx->num_cus * perCu * 4;
     const int64_t tiles = (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, PH_)) * wt.nimg;
-    // rounds of resident workgroups the tiles are dealt over (FD_WVD_ROUNDS, default 2)
-    static const int rounds = [] { const char* e = getenv("FD_WVD_ROUNDS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
-    int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * rounds);
+    int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
     if (wt.nimg >= 8 && grid >= 64) grid &= ~7;   // a multiple of the 8 XCDs: the kernel then keeps every frame on one XCD
     hipLaunchKernelGGL((k_wvm_prefilter<PW_, PH_>), dim3(grid), dim3(256), 0, st, arena, wt, dv);
 }
@@ -1429,8 +1427,7 @@ static void launch_prefilter_group_sized(fd_ctx* ctx, hipStream_t st, const uint
     if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_wvm_prefilter_group<PW_, PH_>, 256, 0) != hipSuccess || perCu < 1)) perCu = 2;
     const int slots = ctx->num_cus * perCu * 4;
     const int64_t tiles = (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, PH_)) * wt.nimg;
-    static const int rounds = [] { const char* e = getenv("FD_WVD_ROUNDS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
-    int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * rounds);
+    int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
     if (wt.nimg >= 8 && grid >= 64) grid &= ~7;
     hipLaunchKernelGGL((k_wvm_prefilter_group<PW_, PH_>), dim3(grid), dim3(256), 0, st, arena, wt, g);
 }
@@ -1568,9 +1565,8 @@ static bool wvm_launch_head(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const WinTab
     if (!m->done) HIP_CHECK(hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
     m->deep_q.reserve(sizeof(int64_t) * (size_t)wt.total);
     // Zero-copy read-back when the run ends in a stage-B kernel (every production run of a model with more than WVM_LCAP
-    // filters): positives and their count go straight to the pinned host buffer.  FD_WVM_ZEROCOPY=0 restores copy + memset.
-    static const bool zcOff = [] { const char* e = getenv("FD_WVM_ZEROCOPY"); return e && atoi(e) == 0; }();
-    const bool zc = !zcOff && !want_all && m->dev.numUsed > WVM_LCAP;
+    // filters): positives and their count go straight to the pinned host buffer.
+    const bool zc = !want_all && m->dev.numUsed > WVM_LCAP;
     m->zcRun = zc;
     m->tailRun = tailWanted && zc && m->wvbOk && wt.total < ((int64_t)1 << 32);   // decided per run; the caller queues the tail kernels iff it is set
     L.zc = zc;
