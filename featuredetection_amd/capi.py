@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("FD_HIP_LIB", os.path.join(_HERE, "libfd_hip.so"))   #
 
 FD_OK, FD_ERR_INVALID_ARGUMENT, FD_ERR_RUNTIME, FD_ERR_LOGIC, FD_ERR_HIP, FD_ERR_CAPACITY, FD_ERR_DEVICE_CAPACITY = range(7)
 FD_LAYER_NONE, FD_LAYER_GRADBIN, FD_LAYER_LBP = 0, 1, 2
+IMAGE_GRAY, IMAGE_GREYWORLD_GRAY = 0, 1   # fd_pyramid_set_image_filter
 FD_KERNEL_LINEAR, FD_KERNEL_POLY, FD_KERNEL_RBF, FD_KERNEL_HIK = 0, 1, 2, 3
 FD_DTYPE_U8, FD_DTYPE_F32 = 0, 1
 
@@ -122,6 +123,8 @@ _SIGS = {
     "fd_pyramid_create_inc": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "fd_pyramid_destroy": (None, [C.c_void_p]),
     "fd_pyramid_set_layer_filter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fd_pyramid_set_image_filter": (C.c_int, [C.c_void_p, C.c_int]),
+    "fd_pyramid_image_filter": (C.c_int, [C.c_void_p]),
     "fd_pyramid_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fd_pyramid_octave_layer_count": (C.c_int, [C.c_void_p]),
     "fd_pyramid_incremental_scale": (C.c_double, [C.c_void_p]),
@@ -327,6 +330,14 @@ class Pyramid:
         self.ctx.check(lib().fd_pyramid_set_layer_filter(self.h, kind, bins, int(signed_gradients), int(interpolate), grad_kernel,
                                                          lbp_type))
         self.ctx.check(lib().fd_pyramid_set_gradient_blur(self.h, blur_kernel))
+
+    def set_image_filter(self, kind):
+        """IMAGE_GRAY (default) or IMAGE_GREYWORLD_GRAY: GreyWorldNormalizationFilter in front of the gray conversion, for every later update"""
+        self.ctx.check(lib().fd_pyramid_set_image_filter(self.h, kind))
+
+    @property
+    def image_filter(self):
+        return lib().fd_pyramid_image_filter(self.h)
 
     def update(self, image):
         image = _c(image, np.uint8)
@@ -744,7 +755,7 @@ class FiveStageFrames:
         return out[mask], np.repeat(np.arange(self.nframes), counts), stages
 
 
-def _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames):
+def _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames, host_frames=None):
     n = len(detectors)
     jobs = (fd_five_stage_job * n)()
     outs = [np.empty(cap, DET_DTYPE) for _ in range(n)]   # the library fills the first `count` records
@@ -755,6 +766,11 @@ def _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames):
     if device_frames is not None:
         for j, (ptr, w, h, ch) in zip(jobs, device_frames):
             j.image, j.image_w, j.image_h, j.image_channels, j.image_is_device = ptr, w, h, ch, 1
+    if host_frames is not None:
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in host_frames]
+        jobs._images = imgs   # the library reads them until the batch has ended: they live as long as the jobs
+        for j, im in zip(jobs, imgs):
+            j.image, j.image_w, j.image_h, j.image_channels, j.image_is_device = im.ctypes.data, im.shape[1], im.shape[0], 1 if im.ndim == 2 else im.shape[2], 0
     return jobs, outs
 
 
@@ -762,10 +778,11 @@ def _five_stage_results(jobs, outs):
     return [(o[:j.count].copy(), np.array(list(j.stage_counts), np.int32)) for j, o in zip(jobs, outs)]
 
 
-def detect_five_stage_batch(ctx, detectors, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1, cap=4096, device_frames=None):
+def detect_five_stage_batch(ctx, detectors, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1, cap=4096, device_frames=None, host_frames=None):
     """detectors: list of (pyramid, wvm, svm); returns [(detections, stage_counts)] in the same order.
-    device_frames: optional list of (device pointer, w, h, channels) per detector: the pyramid is updated inside the call"""
-    jobs, outs = _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames)
+    device_frames: optional list of (device pointer, w, h, channels) per detector: the pyramid is updated inside the call;
+    host_frames: the same with host images (numpy arrays)"""
+    jobs, outs = _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames, host_frames)
     ctx.check(lib().fd_detect_five_stage_batch(ctx.h, jobs, len(detectors)))
     return _five_stage_results(jobs, outs)
 
@@ -773,10 +790,10 @@ def detect_five_stage_batch(ctx, detectors, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=
 class FiveStageBatch:
     """fd_five_stage_batch_begin / _end: begin queues the pyramid updates and cascades of all detectors and returns;
     end() runs the host stages and returns [(detections, stage_counts)].  Batches in flight must use different handles."""
-    def __init__(self, ctx, detectors, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1, cap=4096, device_frames=None):
+    def __init__(self, ctx, detectors, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1, cap=4096, device_frames=None, host_frames=None):
         self.ctx = ctx
         self._keep = list(detectors)   # the handles in the jobs stay alive while the batch is in flight
-        self.jobs, self.outs = _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames)
+        self.jobs, self.outs = _five_stage_jobs(detectors, oe_dist, oe_ratio, sx, sy, cap, device_frames, host_frames)
         self.ticket = C.c_void_p()
         ctx.check(lib().fd_five_stage_batch_begin(ctx.h, self.jobs, len(detectors), C.byref(self.ticket)))
 

@@ -391,6 +391,8 @@ struct fd_pyramid {
     double inc, minS, maxS;
     int filter_kind = FD_LAYER_NONE, bins = 9, signed_gradients = 0, interpolate = 0, grad_kernel = 1, lbp_type = 0;
     int grad_blur = 0;               // GradientFilter's blurKernelSize (0: none); blurred copies of the kept layers live at blur_off
+    int image_filter = FD_IMAGE_GRAY;   // fd_pyramid_set_image_filter: the chain applied to the image before the layers are built
+    DevBuf gw_stats;                 // FD_IMAGE_GREYWORLD_GRAY: channel sums and maxima per frame (pyramid.hip), cleared by every update
     int img_w = 0, img_h = 0;
     std::vector<HostLayer> all;      // every computed layer (kept or only a pyrDown source)
     std::vector<int> kept;           // indices into all, sorted by layer index

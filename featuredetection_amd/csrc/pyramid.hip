@@ -1,7 +1,8 @@
 // featuredetection_amd/csrc/pyramid.hip -- image pyramid on the GPU (gfx950).
 //
 // Restates imageprocessing::ImagePyramid (ImagePyramid.cpp:67-92,116-128,170-198) with the
-// GrayscaleFilter image filter and optional layer filters.  All arithmetic is the integer-exact
+// GrayscaleFilter image filter (optionally behind GreyWorldNormalizationFilter: fd_pyramid_set_image_filter)
+// and optional layer filters.  All arithmetic is the integer-exact
 // OpenCV 2.4 fixed-point arithmetic (cvtColor, resize INTER_LINEAR, pyrDown, Sobel), so layers are
 // bit-identical to the CPU path.  Layout in HBM: ONE arena per pyramid holding the full-resolution
 // gray image, every computed layer (kept or only a pyrDown source) and the filtered kept layers,
@@ -798,6 +799,147 @@ __global__ void k_greyworld_apply(const uint8_t* __restrict__ bgr, uint8_t* __re
     }
 }
 
+// ---- FD_IMAGE_GREYWORLD_GRAY: GreyWorldNormalizationFilter -> GrayscaleFilter in front of the layers, no host round trip ----
+// Two launches replace the gray conversion, blockIdx.y = frame like k_frames_to_gray: k_gw_stats leaves every frame's channel sums
+// and maxima in the pyramid's GwStats records (integer atomics: the result does not depend on the arrival order), k_gw_gray turns
+// them into the three scales and converts.  The kernel boundary is the fence between the two.
+struct GwStats {   // one 64-byte record per frame, cleared on the stream before every update
+    unsigned long long sum[3];
+    unsigned int max[3];
+    unsigned int pad[7];
+};
+static_assert(sizeof(GwStats) == 64, "one record per 64-byte line");
+constexpr int GW_GQ = 4;   // quads (four pixels, three dwords) per thread and pass, their loads in flight together
+
+// three dwords = four BGR pixels (bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3), from an aligned or an unaligned frame
+__device__ __forceinline__ void gw_load3(const uint8_t* __restrict__ src, bool aligned, int q, uint32_t (&w)[3]) {
+    if (aligned) {
+        const uint32_t* s3 = reinterpret_cast<const uint32_t*>(src) + 3 * (size_t)q;
+        w[0] = s3[0]; w[1] = s3[1]; w[2] = s3[2];
+    } else {
+        const uint8_t* s1 = src + 12 * (size_t)q;
+        w[0] = ld_u32_unaligned(s1); w[1] = ld_u32_unaligned(s1 + 4); w[2] = ld_u32_unaligned(s1 + 8);
+    }
+}
+
+// A thread's sums stay in 32 bits: with 256 threads per workgroup a thread meets fewer than 2^31 / 256 pixels of at most 255.
+__global__ __launch_bounds__(256) void k_gw_stats(FramePtrs frames, GwStats* __restrict__ stats, int n) {
+    const uint8_t* __restrict__ src = frames.p[blockIdx.y];
+    const int nq = n >> 2;
+    const bool aligned = ((uintptr_t)src & 3) == 0;
+    const int stride = gridDim.x * blockDim.x;
+    uint32_t s[3] = {0, 0, 0}, m[3] = {0, 0, 0};
+    auto pixel = [&](uint32_t b, uint32_t g, uint32_t r) {
+        s[0] += b; s[1] += g; s[2] += r;
+        m[0] = max(m[0], b); m[1] = max(m[1], g); m[2] = max(m[2], r);
+    };
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += GW_GQ * stride) {
+        uint32_t w[GW_GQ][3];
+#pragma unroll
+        for (int i = 0; i < GW_GQ; ++i) gw_load3(src, aligned, min(q + i * stride, nq - 1), w[i]);
+#pragma unroll
+        for (int i = 0; i < GW_GQ; ++i)
+            if (q + i * stride < nq) {
+                pixel(w[i][0] & 255u, (w[i][0] >> 8) & 255u, (w[i][0] >> 16) & 255u);
+                pixel(w[i][0] >> 24, w[i][1] & 255u, (w[i][1] >> 8) & 255u);
+                pixel((w[i][1] >> 16) & 255u, w[i][1] >> 24, w[i][2] & 255u);
+                pixel((w[i][2] >> 8) & 255u, (w[i][2] >> 16) & 255u, w[i][2] >> 24);
+            }
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < (n & 3)) {   // tail
+        const size_t i = ((size_t)nq << 2) + threadIdx.x;
+        pixel(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+    }
+    // registers -> wave -> workgroup -> one atomic per statistic
+    __shared__ unsigned long long ls[4][3];
+    __shared__ unsigned int lm[4][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        unsigned long long sc = s[c];
+        unsigned int mc = m[c];
+        for (int o = 32; o > 0; o >>= 1) {
+            sc += __shfl_down(sc, o, 64);
+            mc = max(mc, (unsigned int)__shfl_down((int)mc, o, 64));
+        }
+        if ((threadIdx.x & 63) == 0) { ls[threadIdx.x >> 6][c] = sc; lm[threadIdx.x >> 6][c] = mc; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int c = threadIdx.x;
+        atomicAdd(&stats[blockIdx.y].sum[c], ls[0][c] + ls[1][c] + ls[2][c] + ls[3][c]);
+        atomicMax(&stats[blockIdx.y].max[c], max(max(lm[0][c], lm[1][c]), max(lm[2][c], lm[3][c])));
+    }
+}
+
+// The scales in double and in the reference's operation order (GreyWorldNormalizationFilter.cpp:46-60; the same operations and
+// comparisons as fd_greyworld's host code, so NaN and infinity propagate alike).  saturate(cvRound(scale_c * v)) depends only on
+// the channel and the byte value: the workgroup builds the three tables once, with the gray weights (and the rounding term)
+// folded in -- (tab[0][b] + tab[1][g] + tab[2][r]) >> 14 is gray_of() of the normalised pixel, which is never written to memory.
+// The first pass's loads are issued before the tables are built.
+__global__ __launch_bounds__(256) void k_gw_gray(FramePtrs frames, const GwStats* __restrict__ stats, uint8_t* __restrict__ grayBase,
+                                                 size_t imageStride, int n) {
+    __shared__ double scale[3];
+    __shared__ uint32_t tab[3][256];
+    const uint8_t* __restrict__ src = frames.p[blockIdx.y];
+    uint8_t* __restrict__ gray = grayBase + (size_t)blockIdx.y * imageStride;
+    const int nq = n >> 2;
+    const bool aligned = ((uintptr_t)src & 3) == 0;
+    const int stride = gridDim.x * blockDim.x;
+    int q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t w[GW_GQ][3] = {};
+    if (q < nq) {
+#pragma unroll
+        for (int i = 0; i < GW_GQ; ++i) gw_load3(src, aligned, min(q + i * stride, nq - 1), w[i]);
+    }
+    if (threadIdx.x < 64) {   // one wave, every lane the same values
+        const GwStats& S = stats[blockIdx.y];
+        double mean[3], maxNew[3];
+        for (int c = 0; c < 3; ++c) { mean[c] = (double)S.sum[c] / n; maxNew[c] = (uint8_t)S.max[c] / mean[c]; }
+        double mx = maxNew[0];
+        if (maxNew[1] > mx) mx = maxNew[1];
+        if (maxNew[2] > mx) mx = maxNew[2];
+        if (threadIdx.x == 0)
+            for (int c = 0; c < 3; ++c) scale[c] = 255.0 / (mean[c] * mx);
+    }
+    __syncthreads();
+    {
+        const uint32_t v = threadIdx.x;
+        const uint32_t wgt[3] = {1868u, 9617u, 4899u};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int r = __double2int_rn(scale[c] * (double)v);
+            tab[c][v] = (uint32_t)min(255, max(0, r)) * wgt[c] + (c == 0 ? 8192u : 0u);
+        }
+    }
+    __syncthreads();
+    auto gray1 = [&](uint32_t b, uint32_t g, uint32_t r) { return (tab[0][b] + tab[1][g] + tab[2][r]) >> 14; };
+    auto gray4 = [&](const uint32_t (&x)[3]) {
+        const uint32_t g0 = gray1(x[0] & 255u, (x[0] >> 8) & 255u, (x[0] >> 16) & 255u);
+        const uint32_t g1 = gray1(x[0] >> 24, x[1] & 255u, (x[1] >> 8) & 255u);
+        const uint32_t g2 = gray1((x[1] >> 16) & 255u, x[1] >> 24, x[2] & 255u);
+        const uint32_t g3 = gray1((x[2] >> 8) & 255u, (x[2] >> 16) & 255u, x[2] >> 24);
+        return g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+    };
+    while (q < nq) {
+        const int qn = q + GW_GQ * stride;
+        uint32_t wn[GW_GQ][3] = {};
+        if (qn < nq) {   // the next pass's loads in flight under this pass's table reads
+#pragma unroll
+            for (int i = 0; i < GW_GQ; ++i) gw_load3(src, aligned, min(qn + i * stride, nq - 1), wn[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < GW_GQ; ++i)
+            if (q + i * stride < nq) reinterpret_cast<uint32_t*>(gray)[q + i * stride] = gray4(w[i]);
+#pragma unroll
+        for (int i = 0; i < GW_GQ; ++i) { w[i][0] = wn[i][0]; w[i][1] = wn[i][1]; w[i][2] = wn[i][2]; }
+        q = qn;
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < (n & 3)) {   // tail
+        const size_t i = ((size_t)nq << 2) + threadIdx.x;
+        gray[i] = (uint8_t)gray1(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+    }
+}
+
 inline uint32_t align256(size_t v) { return (uint32_t)((v + 255) & ~(size_t)255); }
 
 // GradientBinningFilter.cpp:18-60 -- built on the host with libm, exactly like the reference ctor
@@ -983,6 +1125,9 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
     if (p->nimg > 1 && p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "multi-frame pyramids have no layer filters");
     if (W < 1 || H < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_update: empty image");
     if (ch != 1 && ch != 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_update: image must have 1 or 3 channels");
+    const bool greyworld = p->image_filter != FD_IMAGE_GRAY;
+    if (greyworld && ch != 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "GreyWorldNormalizationFilter: The image type must be CV_8UC3");
+    if (greyworld && (size_t)W * H > 0x7fffffffull) FD_THROW(FD_ERR_INVALID_ARGUMENT, "GreyWorldNormalizationFilter: image too large");
     if (W != p->img_w || H != p->img_h || p->all.empty()) build_layout(p, W, H);
     uint8_t* arena = p->arena.as<uint8_t>();
     const size_t npix = (size_t)W * H;
@@ -1138,6 +1283,19 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
         flush();
     }
     };   // enqueue_rest
+    // FD_IMAGE_GREYWORLD_GRAY: the statistics of every frame, then normalisation + gray conversion in one pass
+    auto enqueue_greyworld_gray = [&](const FramePtrs& fp) {
+        GwStats* stats = p->gw_stats.as<GwStats>();
+        HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(GwStats) * (size_t)NI, st));
+        // persistent workgroups, one pass of 1024 quads each where the frame is small.  At most one workgroup per CU and frame (a
+        // 1080p frame: 256 workgroups, 256 atomics per statistic) and about four per CU in all (64 frames: 16 per frame).  Twice
+        // and four times as many were slower in both shapes (one frame: the atomics on six addresses)
+        const int cus = std::max(1, p->ctx->num_cus);
+        const int perFrame = std::max(1, std::min(cus, 4 * cus / NI));
+        const int gx = std::max(1, std::min((int)((npix / 4 + 1023) / 1024), perFrame));
+        hipLaunchKernelGGL(k_gw_stats, dim3(gx, NI), dim3(256), 0, st, fp, stats, (int)npix);
+        hipLaunchKernelGGL(k_gw_gray, dim3(gx, NI), dim3(256), 0, st, fp, stats, arena + p->gray_full_off, IS, (int)npix);
+    };
     if (frames) {   // one launch converts / copies all frames into their arenas
         FramePtrs fp;
         if (!is_device) {
@@ -1149,7 +1307,9 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
         } else {
             for (int f = 0; f < NI; ++f) fp.p[f] = frames[f];
         }
-        hipLaunchKernelGGL(k_frames_to_gray, dim3(grid_for((int)(npix / 16 + 1)), NI), dim3(256), 0, st, fp, arena + p->gray_full_off, IS, (int)npix, ch);   // four quads per thread
+        if (greyworld) enqueue_greyworld_gray(fp);
+        else
+            hipLaunchKernelGGL(k_frames_to_gray, dim3(grid_for((int)(npix / 16 + 1)), NI), dim3(256), 0, st, fp, arena + p->gray_full_off, IS, (int)npix, ch);   // four quads per thread
     } else {
         const uint8_t* dimg = image;
         if (!is_device) {
@@ -1157,7 +1317,11 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
             HIP_CHECK(hipMemcpyAsync(p->input.p, image, npix * ch, hipMemcpyHostToDevice, st));
             dimg = p->input.as<uint8_t>();
         }
-        if (ch == 3) {
+        if (greyworld) {   // the same two kernels with one frame
+            FramePtrs fp{};
+            fp.p[0] = dimg;
+            enqueue_greyworld_gray(fp);
+        } else if (ch == 3) {
             hipLaunchKernelGGL(k_bgr2gray, dim3(grid_for((int)npix)), dim3(256), 0, st, dimg, arena + p->gray_full_off, (int)npix);
         } else {
             HIP_CHECK(hipMemcpyAsync(arena + p->gray_full_off, dimg, npix, hipMemcpyDeviceToDevice, st));
@@ -1295,6 +1459,21 @@ int fd_pyramid_set_layer_filter(fd_pyramid* p, int kind, int bins, int signed_gr
         p->img_w = p->img_h = 0;
     });
 }
+
+int fd_pyramid_set_image_filter(fd_pyramid* p, int kind) {
+    return fd_guard(p ? p->ctx : nullptr, [&] {
+        if (!p) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_set_image_filter: NULL pyramid");
+        if (kind != FD_IMAGE_GRAY && kind != FD_IMAGE_GREYWORLD_GRAY)
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_set_image_filter: unknown kind %d", kind);
+        if (kind == FD_IMAGE_GREYWORLD_GRAY) {   // allocated here: an update allocates nothing
+            HIP_CHECK(hipSetDevice(p->ctx->device));
+            p->gw_stats.reserve(sizeof(GwStats) * FD_MAX_FRAMES);
+        }
+        p->image_filter = kind;   // the layout does not depend on it
+    });
+}
+
+int fd_pyramid_image_filter(const fd_pyramid* p) { return p ? p->image_filter : FD_IMAGE_GRAY; }
 
 int fd_pyramid_update(fd_pyramid* p, const uint8_t* image, int w, int h, int ch, int is_device) {
     return fd_guard(p ? p->ctx : nullptr, [&] {

@@ -154,6 +154,11 @@ int main(int argc, char** argv) {
             // float-typed like ffpDetectApp.cpp:407 (imgpyr.get<float>(...))
             auto imgPyr = make_shared<ImagePyramid>((double)imgpyr.get<float>("incrementalScaleFactor", 0.9f), (double)imgpyr.get<float>("minScaleFactor", 0.09f),
                                                     (double)imgpyr.get<float>("maxScaleFactor", 0.25f));
+            // "imageFilter greyworld" is an extension of this backend (the reference's configs have no such key): a
+            // GreyWorldNormalizationFilter in front of the GrayscaleFilter
+            const string imageFilter = imgpyr.get<string>("imageFilter", "");
+            if (imageFilter == "greyworld") imgPyr->addImageFilter(make_shared<GreyWorldNormalizationFilter>());
+            else if (!imageFilter.empty()) throw std::invalid_argument("unknown image filter " + imageFilter);
             imgPyr->addImageFilter(make_shared<GrayscaleFilter>());
             auto featureExtractor = make_shared<DirectPyramidFeatureExtractor>(imgPyr, imgpyr.get<int>("patch.width"), imgpyr.get<int>("patch.height"));
             shared_ptr<Detector> det;

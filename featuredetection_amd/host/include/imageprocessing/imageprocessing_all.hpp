@@ -255,7 +255,8 @@ public:
     ~ImagePyramid();
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
-    void addImageFilter(const std::shared_ptr<ImageFilter>& filter);   // GrayscaleFilter
+    // chains: [GrayscaleFilter] or [GreyWorldNormalizationFilter, GrayscaleFilter]; anything else throws logic_error
+    void addImageFilter(const std::shared_ptr<ImageFilter>& filter);
     void addLayerFilter(const std::shared_ptr<ImageFilter>& filter);   // GradientFilter, GradientBinningFilter, LbpFilter
     void update(const cv::Mat& image);
     void update(const std::shared_ptr<VersionedImage>& image);
@@ -304,6 +305,7 @@ private:
     std::shared_ptr<GradientFilter> gradient;
     std::shared_ptr<GradientBinningFilter> binning;
     std::shared_ptr<LbpFilter> lbp;
+    std::vector<int> imageChain;          // addImageFilter: FD_IMAGE_GREYWORLD_GRAY for a GreyWorldNormalizationFilter, FD_IMAGE_GRAY for a GrayscaleFilter
     mutable std::vector<std::shared_ptr<ImagePyramidLayer>> layers;
     mutable bool layersValid;
 };

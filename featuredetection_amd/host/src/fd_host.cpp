@@ -251,6 +251,9 @@ static Mat hist_apply(const HistogramFilter& f, const Mat& image, Mat& filtered)
 Mat HogFilter::applyTo(const Mat& image, Mat& filtered) const { return hist_apply(*this, image, filtered); }
 
 // ---- ImagePyramid -------------------------------------------------------------------------------
+static const char* const kImageFilterChains =
+    "ImagePyramid: the image filter chains available on this backend are [GrayscaleFilter] and "
+    "[GreyWorldNormalizationFilter, GrayscaleFilter]";
 ImagePyramid::ImagePyramid(size_t octaveLayerCount, double minS, double maxS)
     : handle(nullptr), minScaleFactor(minS), maxScaleFactor(maxS), ctorOctaveLayers(octaveLayerCount), layersValid(false) {
     check(fd_pyramid_create(context(), (int)octaveLayerCount, minS, maxS, &handle));
@@ -261,10 +264,12 @@ ImagePyramid::ImagePyramid(double inc, double minS, double maxS)
 }
 fd_pyramid* ImagePyramid::createFramesPyramid(int frames) const {
     if (sourcePyramid || !handle || gradient || binning || lbp) return nullptr;
+    if (!imageChain.empty() && imageChain.back() != FD_IMAGE_GRAY) throw std::logic_error(kImageFilterChains);
     fd_pyramid* p = nullptr;
     if (ctorOctaveLayers) check(fd_pyramid_create(context(), (int)ctorOctaveLayers, minScaleFactor, maxScaleFactor, &p));
     else check(fd_pyramid_create_inc(context(), ctorIncremental, minScaleFactor, maxScaleFactor, &p));
-    const int rc = fd_pyramid_set_frames(p, frames);
+    int rc = fd_pyramid_set_frames(p, frames);
+    if (rc == FD_OK) rc = fd_pyramid_set_image_filter(p, fd_pyramid_image_filter(handle));
     if (rc != FD_OK) { fd_pyramid_destroy(p); check(rc); }
     return p;
 }
@@ -277,9 +282,17 @@ double ImagePyramid::getIncrementalScaleFactor() const { return fd_pyramid_incre
 static long g_pyramidBuilds = 0;
 long ImagePyramid::buildCount() { return g_pyramidBuilds; }
 
+// The image-filter chain is recorded and mapped to the native pyramid's setting (fd_pyramid_set_image_filter); the filters
+// themselves run inside the pyramid kernels.  A GrayscaleFilter behind a GrayscaleFilter copies (GrayscaleFilter.cpp:18-24) and is
+// not recorded again.
 void ImagePyramid::addImageFilter(const shared_ptr<ImageFilter>& filter) {
-    if (!std::dynamic_pointer_cast<GrayscaleFilter>(filter))
-        throw std::logic_error("ImagePyramid: only GrayscaleFilter is supported as image filter on this backend");
+    const bool gray = std::dynamic_pointer_cast<GrayscaleFilter>(filter) != nullptr;
+    const bool greyWorld = std::dynamic_pointer_cast<GreyWorldNormalizationFilter>(filter) != nullptr;
+    const bool endsGray = !imageChain.empty() && imageChain.back() == FD_IMAGE_GRAY;
+    if (!gray && !(greyWorld && imageChain.empty())) throw std::logic_error(kImageFilterChains);
+    if (!(gray && endsGray)) imageChain.push_back(gray ? FD_IMAGE_GRAY : FD_IMAGE_GREYWORLD_GRAY);
+    if (handle) check(fd_pyramid_set_image_filter(handle, imageChain.front()));
+    version = Version();   // the next update builds the layers again
     if (sourcePyramid) sourcePyramid->addImageFilter(filter);   // ImagePyramid.cpp:108-110
 }
 void ImagePyramid::setSource(const shared_ptr<VersionedImage>& image) {
@@ -364,6 +377,8 @@ void ImagePyramid::update(const shared_ptr<VersionedImage>& image) {
     }
     if ((gradient != nullptr) != (binning != nullptr))
         throw std::logic_error("ImagePyramid: GradientFilter and GradientBinningFilter have to be added together");
+    // a GreyWorldNormalizationFilter alone would give three-channel layers
+    if (!imageChain.empty() && imageChain.back() != FD_IMAGE_GRAY) throw std::logic_error(kImageFilterChains);
     sourceImage = image;
     if (version == image->getVersion()) return;   // ImagePyramid.cpp:150
     Mat src = contiguous(image->getData());

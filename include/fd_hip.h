@@ -68,6 +68,17 @@ enum { FD_GRAD_SCHARR = -1 };
 int fd_pyramid_set_layer_filter(fd_pyramid* p, int kind, int bins, int signed_gradients, int interpolate,
                                 int grad_kernel, int lbp_type);
 int fd_pyramid_set_gradient_blur(fd_pyramid* p, int blur_kernel);
+/* Image filters (ImagePyramid::addImageFilter, ImagePyramid.cpp:106-110,171), applied to the image before the layers are built:
+ *  FD_IMAGE_GRAY            GrayscaleFilter (default)
+ *  FD_IMAGE_GREYWORLD_GRAY  GreyWorldNormalizationFilter -> GrayscaleFilter (GreyWorldNormalizationFilter.cpp:20-71 on the BGR
+ *                           image, then the gray conversion); the image must have 3 channels
+ * Holds for every later update of the pyramid through any entry point (fd_pyramid_update, fd_pyramid_update_frames,
+ * fd_detect_five_stage_image, the image of a fd_five_stage_job); every frame of a multi-frame pyramid is normalised with its own
+ * statistics.  Does not change the layout; may be set or reset between updates.  The statistics and the scales stay on the device:
+ * an update with the filter returns without waiting, like one without. */
+enum { FD_IMAGE_GRAY = 0, FD_IMAGE_GREYWORLD_GRAY = 1 };
+int fd_pyramid_set_image_filter(fd_pyramid* p, int kind);
+int fd_pyramid_image_filter(const fd_pyramid* p);
 /* channels 1 (gray) or 3 (BGR, interleaved).  is_device != 0: image already resident in HBM. */
 int fd_pyramid_update(fd_pyramid* p, const uint8_t* image, int width, int height, int channels, int is_device);
 int fd_pyramid_octave_layer_count(const fd_pyramid* p);
