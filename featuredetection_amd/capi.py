@@ -204,6 +204,11 @@ _SIGS = {
     "fd_rvm_eval_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fd_detect_rvm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_rvm_detect_params), C.c_void_p, C.c_void_p, C.c_int64,
                                 C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "fd_detect_five_stage_rvm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_rvm_detect_params), C.c_void_p, C.c_void_p, C.c_float,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "fd_detect_five_stage_rvm_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_rvm_detect_params), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "fd_extract_hog": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_hog_params), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "fd_gradient_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "fd_gradient_filter_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -1004,6 +1009,61 @@ def detect_rvm(ctx, pyr, rvm, feature_space=FEATURE_HQ64, conv_scale=1.0, conv_s
     r = _c(roi, np.int32) if roi is not None else None
     ctx.check(lib().fd_detect_rvm(ctx.h, pyr.h, rvm.h, C.byref(dp), _ptr(r), _ptr(out), out.shape[0], C.byref(cnt), _ptr(lv), _ptr(dd)))
     return out[:cnt.value], lv, dd
+
+
+def _second_handles(second):
+    """(svm handle, rvm handle) of a five-stage second classifier: a capi.Svm or a capi.Rvm"""
+    if isinstance(second, Svm):
+        return second.h, None
+    if isinstance(second, Rvm):
+        return None, second.h
+    raise TypeError("second classifier must be a capi.Svm or a capi.Rvm")
+
+
+def detect_five_stage_rvm(ctx, pyr, rvm, second, feature_space=FEATURE_HQ64, conv_scale=1.0, conv_shift=0.0, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1,
+                          roi=None, cap=4096):
+    """fd_detect_five_stage_rvm: the five-stage detector with an RVM first stage; second: capi.Svm (f32) or capi.Rvm.  (dets, stage_counts)"""
+    out = np.zeros(cap, DET_DTYPE)
+    cnt = C.c_int()
+    stages = np.zeros(4, np.int32)
+    dp = fd_rvm_detect_params(feature_space, conv_scale, conv_shift, sx, sy)
+    r = _c(roi, np.int32) if roi is not None else None
+    hs, hr = _second_handles(second)
+    ctx.check(lib().fd_detect_five_stage_rvm(ctx.h, pyr.h, rvm.h, C.byref(dp), hs, hr, oe_dist, oe_ratio, _ptr(r), _ptr(out), cap, C.byref(cnt),
+                                             _ptr(stages)))
+    return out[:cnt.value], stages
+
+
+class FiveStageRvmImage:
+    """fd_detect_five_stage_rvm_image with preallocated result buffers, the twin of FiveStageImage (the output arrays are reused: copy what
+    must outlive the next call)"""
+
+    def __init__(self, ctx, pyr, rvm, second, feature_space=FEATURE_HQ64, conv_scale=1.0, conv_shift=0.0, oe_dist=5.0, oe_ratio=0.0, sx=1, sy=1,
+                 cap=4096):
+        self.ctx, self.pyr, self.rvm, self.second = ctx, pyr, rvm, second
+        self.dp = fd_rvm_detect_params(feature_space, conv_scale, conv_shift, sx, sy)
+        self.args = (oe_dist, oe_ratio)
+        self.cap = cap
+        self.out = np.zeros(cap, DET_DTYPE)
+        self.cnt = C.c_int()
+        self.stages = np.zeros(4, np.int32)
+        self._fn = lib().fd_detect_five_stage_rvm_image
+        self._hs, self._hr = _second_handles(second)
+        self._outp, self._stp, self._cntp = _ptr(self.out), _ptr(self.stages), C.byref(self.cnt)
+
+    def _run(self, iptr, w, h, ch, is_device):
+        a = self.args
+        self.ctx.check(self._fn(self.ctx.h, self.pyr.h, self.rvm.h, C.byref(self.dp), self._hs, self._hr, iptr, w, h, ch, is_device, a[0], a[1], None,
+                                self._outp, self.cap, self._cntp, self._stp))
+        return self.out[:self.cnt.value], self.stages
+
+    def detect_device(self, dev_ptr, w, h, ch):
+        return self._run(C.c_void_p(dev_ptr), w, h, ch, 1)
+
+    def detect(self, image):
+        image = np.ascontiguousarray(image, np.uint8)
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        return self._run(_ptr(image), image.shape[1], image.shape[0], ch, 0)
 
 
 def whi_batch(ctx, patches, alpha=1.0, cutoff=0.390625):

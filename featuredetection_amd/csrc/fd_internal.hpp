@@ -309,6 +309,9 @@ static inline int fd_knob_wvd_rounds() { static const int v = fd_env_int("FD_WVD
 static inline bool fd_knob_trace() { static const bool on = getenv("FD_TRACE") != nullptr; return on; }
 // stages 2-3 on the device: 0 never, 1 always (batch jobs too), -1 (unset): multi-frame calls only.  Read per call: the tests flip it.
 static inline int fd_knob_fs_tail() { const char* e = getenv("FD_FS_TAIL"); return e ? atoi(e) : -1; }
+// single-frame five-stage calls: the second stage over all first-stage positives behind the cascade (one host wait); 0: two waits.
+// Read per call: the tests compare both orders.
+static inline bool fd_knob_fs_spec() { const char* e = getenv("FD_FS_SPEC"); return !(e && atoi(e) == 0); }
 
 // FD_TRACE's stopwatch: lap_ns() is the time since the start (or the previous lap) and starts the next lap; off: no clock is read.
 struct FdStopwatch {

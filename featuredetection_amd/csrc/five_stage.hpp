@@ -1,10 +1,10 @@
-// featuredetection_amd/csrc/five_stage.hpp -- the five-stage detector's glue (included by wvm.hip only, inside its extern "C" block,
+// featuredetection_amd/csrc/five_stage.hpp -- the five-stage detector's glue around the WVM cascade (included by wvm.hip only, inside its extern "C" block,
 // behind the WVM entry points it builds on).
 //
 // detection::FiveStageSlidingWindowDetector::detect (FiveStageSlidingWindowDetector.cpp:187-320, :331-380) around the WVM cascade of
 // wvm.hip.  Host code only.  Each stage exists once, and every entry point calls it:
-//   five_stage_nms                               stages 4-5: block NMS, sort
-//   five_stage_accept / five_stage_verdicts      stage 3's verdict (threshold, score, probability 0.5), host-tail flavour
+//   five_stage_nms, five_stage_accept            stages 4-5 (block NMS, sort) and stage 3's verdict on one survivor: five_stage_stages.hpp
+//   five_stage_verdicts                          stage 3's verdicts (threshold, score, probability 0.5), host-tail flavour
 //   five_stage_svm_launch                        stage 3 of a host tail: slot list + distances in pinned memory, one generic SVM launch
 //   FiveStageTail                                the host tail in two halves (overlap elimination -> SVM launch | wait -> NMS)
 //   fst_launch / fst_collect / fst_verdicts / fst_frame   the device tail (fs_tail.hpp: k_fs_oe + the counted SVM launch queued behind
@@ -13,46 +13,7 @@
 // multi-frame pyramid in one cascade run) and fd_detect_five_stage_batch / fd_five_stage_batch_begin / _end (several detectors on
 // shared pyramids, ffpDetectApp.cpp:557-600).  FD_TRACE timings go through FdStopwatch; exceptions become FdError in fd_current_error.
 #pragma once
-// Stages 4-5 of FiveStageSlidingWindowDetector::detect on the SVM positives of one image (FiveStageSlidingWindowDetector.cpp:
-// 262-320; the roi variant :360-380 only sorts): block NMS on the probability map, one detection per maximum, sorted by probability.
-static void five_stage_nms(const fd_pyramid* p, const int* roi, std::vector<fd_detection>& svmPos, fd_detection* out, int cap, int* count,
-                           int32_t* stage_counts) {
-    if (stage_counts) stage_counts[2] = (int)svmPos.size();
-    auto byProb = [](const fd_detection& a, const fd_detection& b) { return a.probability > b.probability; };
-    bool sortAtEnd = true;
-    if (!roi) {
-        std::vector<int> maxima;
-        fd_host_block_nms_sparse(svmPos, p->img_w, p->img_h, 35, true, maxima);
-        if (maxima.empty()) fd_host_block_nms_sparse(svmPos, p->img_w, p->img_h, 35, false, maxima);
-        if (maxima.empty()) {
-            sortAtEnd = false;  // "return svmPatchesPositive; // Should be empty." (:292-294), unsorted
-        } else {
-            std::sort(svmPos.begin(), svmPos.end(), byProb);
-            std::vector<fd_detection> res;
-            for (size_t i = 0; i + 1 < maxima.size(); i += 2) {
-                const int x = maxima[i], y = maxima[i + 1];
-                auto it = std::find_if(svmPos.begin(), svmPos.end(), [&](const fd_detection& a) { return a.cx == x && a.cy == y; });
-                if (it != svmPos.end()) res.push_back(*it);
-            }
-            svmPos.swap(res);
-        }
-    }
-    if (sortAtEnd) std::sort(svmPos.begin(), svmPos.end(), byProb);
-    if (stage_counts) stage_counts[3] = (int)svmPos.size();
-    *count = (int)svmPos.size();
-    for (size_t i = 0; i < svmPos.size() && (int)i < cap && out; ++i) out[i] = svmPos[i];
-    if (out && (int)svmPos.size() > cap) FD_THROW(FD_ERR_CAPACITY, "five-stage: %zu detections, capacity %d", svmPos.size(), cap);
-}
-
-// Stage 3's verdict on one survivor: strongClassifier->classify() gives a bool only, so a survivor at or above the SVM's threshold becomes
-// an SVM positive with the distance as its score and ClassifiedPatch(patch, bool)'s default probability (ClassifiedPatch.hpp:29-30).
-static inline void five_stage_accept(const fd_detection& survivor, double dist, std::vector<fd_detection>& svmPos) {
-    fd_detection d = survivor;
-    d.score = (float)dist;
-    d.positive = 1;
-    d.probability = 0.5;
-    svmPos.push_back(d);
-}
+// (five_stage_nms and five_stage_accept come from five_stage_stages.hpp, which wvm.hip includes at its top: rvm_five_stage.hpp calls them too)
 // The verdicts of a host tail: survivor i is dets[keep[i]]; its distance is dist[i], or dist[slots[keep[i]]] where the SVM launch
 // covered every WVM positive by patch slot (the speculative launch of fd_detect_five_stage).
 static void five_stage_verdicts(const fd_svm* svm, const fd_detection* dets, const std::vector<int>& keep, const double* dist, const uint32_t* slots,
@@ -168,10 +129,7 @@ static bool fst_possible(const fd_wvm* m, const fd_svm* svm, int nimg) {
 // against the host stages' 5.3 G on eight threads); with six queues the tails overlap and the device wins with a quarter of the host
 // threads (5.6 G on two threads).  The results are the same bytes either way.
 static bool fst_possible_batch(const fd_wvm* m, const fd_svm* svm) { return fd_knob_fs_tail() == 1 && fst_model_ok(m, svm); }
-static bool spec_possible(const fd_wvm* m, const fd_svm* svm) {
-    const char* e = getenv("FD_FS_SPEC");   // read per call: the tests compare both orders
-    return !(e && atoi(e) == 0) && fst_model_ok(m, svm);
-}
+static bool spec_possible(const fd_wvm* m, const fd_svm* svm) { return fd_knob_fs_spec() && fst_model_ok(m, svm); }
 static size_t fst_host_offsets(int nimg, int64_t cap, size_t& keepOff, size_t& distOff) {
     keepOff = (16 + sizeof(FstFrame) * (size_t)nimg + 15) & ~(size_t)15;
     distOff = (keepOff + sizeof(FstKeep) * (size_t)cap + 15) & ~(size_t)15;

@@ -62,6 +62,8 @@ struct fd_rvm {
     std::vector<float> h_thr;
     DevBuf sv, svT, diag, thr;
     DevBuf feats, q0, q1, counters, level, dist, pos;   // scratch reused across calls
+    DevBuf rows;    // five-stage first stage (rvm_five_stage.hpp): the f32 feature rows the second classifier reads
+    HostBuf h_fs;   // ... and its pinned staging (count, records or window ids, the second stage's distances and levels)
 };
 
 namespace {
@@ -346,6 +348,66 @@ void run_cascade(fd_ctx* ctx, fd_rvm* m, const void* dfeats, int64_t rowBytes, f
     }
 }
 
+// ---- the window scan of fd_detect_rvm, in the pieces the five-stage entry points (rvm_five_stage.hpp) share with it ----------------
+struct RvmScan {
+    std::vector<WindowLayer> wls;
+    int64_t total = 0;
+    unsigned int pos_cap = 0;
+};
+
+void rvm_scan_check(fd_ctx* ctx, const fd_pyramid* p, const fd_rvm* m, const fd_rvm_detect_params* dp, const char* who, bool needImage = true) {
+    if (p->ctx != ctx || m->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+    if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "RVM detection needs a gray pyramid (no layer filter)");
+    fd_pyramid_require_single(p, who);
+    if (needImage && p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+    if (dp->feature_space < FD_FEATURE_GRAY || dp->feature_space > FD_FEATURE_HISTEQ)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "unknown feature space %d", dp->feature_space);
+    if (m->filter_w > RVM_MAX_DIM || m->filter_h > RVM_MAX_DIM) FD_THROW(FD_ERR_INVALID_ARGUMENT, "patch size must be within %d x %d", RVM_MAX_DIM, RVM_MAX_DIM);
+}
+
+// enumerates the windows and queues k_window_patches: m->feats holds every window's u8 feature row.  false: no window
+bool rvm_scan_windows(fd_ctx* ctx, fd_pyramid* p, fd_rvm* m, const fd_rvm_detect_params* dp, const int* roi, RvmScan& sc) {
+    const int pw = m->filter_w, ph = m->filter_h, dim = pw * ph;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    fd_enumerate_layers(p, pw, ph, dp->step_x, dp->step_y, roi, sc.wls, sc.total);
+    const int64_t total = sc.total;
+    if (total == 0) return false;
+    if (sc.wls.size() > (size_t)RVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", sc.wls.size());
+    RvmWinTable wt;
+    std::memset(&wt, 0, sizeof(wt));
+    wt.sx = dp->step_x; wt.sy = dp->step_y; wt.total = total;
+    for (const WindowLayer& w : sc.wls) {
+        if (w.nx == 0 || w.ny == 0) continue;
+        const HostLayer& L = p->all[p->kept[w.layer]];
+        RvmWinLayer& dl = wt.l[wt.n++];
+        dl.bx = w.bx; dl.by = w.by; dl.nx = w.nx; dl.ny = w.ny; dl.lw = L.w; dl.off = L.gray_off; dl.first = w.first;
+    }
+    m->feats.reserve((size_t)total * dim + 16);
+    hipLaunchKernelGGL(k_window_patches, dim3((unsigned)std::min<int64_t>(total, (int64_t)ctx->num_cus * 32)), dim3(64), 0, ctx->stream,
+                       p->arena.as<uint8_t>(), wt, pw, ph, dp->feature_space, m->feats.as<uint8_t>());
+    HIP_CHECK(hipGetLastError());
+    sc.pos_cap = (unsigned int)std::min<int64_t>(total, 1 << 22);
+    return true;
+}
+
+void rvm_scan_cascade(fd_ctx* ctx, fd_rvm* m, const fd_rvm_detect_params* dp, const RvmScan& sc, bool want_all) {
+    run_cascade<true>(ctx, m, m->feats.p, (int64_t)m->dev.dim, dp->conv_scale, dp->conv_shift, sc.total, want_all, sc.pos_cap);
+}
+
+inline uint64_t rvm_wid(const RvmRec& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; }
+
+// a positive record -> the ClassifiedPatch of SlidingWindowDetector::detect
+fd_detection rvm_detection(const fd_pyramid* p, const fd_rvm* m, const std::vector<WindowLayer>& wls, const fd_rvm_detect_params* dp, const RvmRec& r) {
+    fd_detection d;
+    std::memset(&d, 0, sizeof(d));
+    fd_window_to_detection(p, wls, dp->step_x, dp->step_y, (int64_t)rvm_wid(r), d);
+    d.level = m->dev.numUse - 1;
+    d.positive = 1;
+    d.score = (float)r.d;
+    d.probability = 1.0f / (1.0f + std::exp(m->logisticA + m->logisticB * r.d));   // ProbabilisticRvmClassifier.cpp:62
+    return d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -413,38 +475,16 @@ int fd_detect_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* rvm_, const fd_rvm_d
     return fd_guard(ctx, [&] {
         if (!ctx || !p || !rvm_ || !dp || !count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_detect_rvm: NULL argument");
         fd_rvm* m = const_cast<fd_rvm*>(rvm_);
-        if (p->ctx != ctx || m->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
-        if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "RVM detection needs a gray pyramid (no layer filter)");
-        fd_pyramid_require_single(p, "fd_detect_rvm");
-        if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
-        if (dp->feature_space < FD_FEATURE_GRAY || dp->feature_space > FD_FEATURE_HISTEQ)
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "unknown feature space %d", dp->feature_space);
-        const int pw = m->filter_w, ph = m->filter_h, dim = pw * ph;
-        if (pw > RVM_MAX_DIM || ph > RVM_MAX_DIM) FD_THROW(FD_ERR_INVALID_ARGUMENT, "patch size must be within %d x %d", RVM_MAX_DIM, RVM_MAX_DIM);
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::vector<WindowLayer> wls;
-        int64_t total;
-        fd_enumerate_layers(p, pw, ph, dp->step_x, dp->step_y, roi, wls, total);
+        RvmScan sc;
+        rvm_scan_check(ctx, p, m, dp, "fd_detect_rvm");
         *count = 0;
-        if (total == 0) return;
-        if (wls.size() > (size_t)RVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", wls.size());
-        RvmWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.sx = dp->step_x; wt.sy = dp->step_y; wt.total = total;
-        for (const WindowLayer& w : wls) {
-            if (w.nx == 0 || w.ny == 0) continue;
-            const HostLayer& L = p->all[p->kept[w.layer]];
-            RvmWinLayer& dl = wt.l[wt.n++];
-            dl.bx = w.bx; dl.by = w.by; dl.nx = w.nx; dl.ny = w.ny; dl.lw = L.w; dl.off = L.gray_off; dl.first = w.first;
-        }
+        if (!rvm_scan_windows(ctx, p, m, dp, roi, sc)) return;
+        const std::vector<WindowLayer>& wls = sc.wls;
+        const int64_t total = sc.total;
         hipStream_t st = ctx->stream;
-        m->feats.reserve((size_t)total * dim + 16);
-        hipLaunchKernelGGL(k_window_patches, dim3((unsigned)std::min<int64_t>(total, (int64_t)ctx->num_cus * 32)), dim3(64), 0, st,
-                           p->arena.as<uint8_t>(), wt, pw, ph, dp->feature_space, m->feats.as<uint8_t>());
-        HIP_CHECK(hipGetLastError());
         const bool want_all = all_level || all_distance;
-        const unsigned int pos_cap = (unsigned int)std::min<int64_t>(total, 1 << 22);
-        run_cascade<true>(ctx, m, m->feats.p, (int64_t)dim, dp->conv_scale, dp->conv_shift, total, want_all, pos_cap);
+        const unsigned int pos_cap = sc.pos_cap;
+        rvm_scan_cascade(ctx, m, dp, sc, want_all);
         unsigned int* hcnt = (unsigned int*)fd_pinned(ctx, 64);
         HIP_CHECK(hipMemcpyAsync(hcnt, m->counters.p, 4, hipMemcpyDeviceToHost, st));
         if (all_level) HIP_CHECK(hipMemcpyAsync(all_level, m->level.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, st));
@@ -454,21 +494,13 @@ int fd_detect_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* rvm_, const fd_rvm_d
         if (cnt > pos_cap) FD_THROW(FD_ERR_DEVICE_CAPACITY, "fd_detect_rvm: %u positives exceed the device buffer", cnt);
         std::vector<RvmRec> raw(cnt);
         if (cnt) HIP_CHECK(hipMemcpy(raw.data(), m->pos.p, sizeof(RvmRec) * cnt, hipMemcpyDeviceToHost));
-        auto widof = [](const RvmRec& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; };
-        std::sort(raw.begin(), raw.end(), [&](const RvmRec& a, const RvmRec& b) { return widof(a) < widof(b); });
+        std::sort(raw.begin(), raw.end(), [](const RvmRec& a, const RvmRec& b) { return rvm_wid(a) < rvm_wid(b); });
         *count = cnt;
-        for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i) {
-            fd_detection d;
-            std::memset(&d, 0, sizeof(d));
-            fd_window_to_detection(p, wls, dp->step_x, dp->step_y, (int64_t)widof(raw[i]), d);
-            d.level = m->dev.numUse - 1;
-            d.positive = 1;
-            d.score = (float)raw[i].d;
-            d.probability = 1.0f / (1.0f + std::exp(m->logisticA + m->logisticB * raw[i].d));   // ProbabilisticRvmClassifier.cpp:62
-            out[i] = d;
-        }
+        for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i) out[i] = rvm_detection(p, m, wls, dp, raw[i]);
         if (out && (int64_t)cnt > cap) FD_THROW(FD_ERR_CAPACITY, "fd_detect_rvm: %u positives, capacity %lld", cnt, (long long)cap);
     });
 }
 
 }  // extern "C"
+
+#include "rvm_five_stage.hpp"

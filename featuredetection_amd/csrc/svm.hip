@@ -93,10 +93,12 @@ __device__ __forceinline__ double powi(double base, int exponent) {  // Polynomi
 
 // One workgroup (256 threads) per feature vector; wave w handles support vectors w, w+4, ...
 // features: [n][dpad] (u8 or f32), optionally gathered through idx (slot indices).
+// dcount (may be NULL): the number of vectors lives on the device and the grid was sized for a capacity; workgroups past it leave at once.
 __global__ __launch_bounds__(256) void k_svm_generic(SvmDev m, const void* __restrict__ features, const uint32_t* __restrict__ idx,
-                                                     int64_t feat_stride_bytes, double* __restrict__ out) {
+                                                     int64_t feat_stride_bytes, double* __restrict__ out, const unsigned int* __restrict__ dcount) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ double red[4];
+    if (dcount && blockIdx.x >= *dcount) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t item = blockIdx.x;
     const int64_t slot = idx ? (int64_t)idx[item] : item;
@@ -751,7 +753,20 @@ void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat
     }
     const size_t ldsBytes = m->dev.dtype == FD_DTYPE_U8 ? (size_t)m->dev.dpad : (size_t)m->dev.dim * 4;
     if (ldsBytes > 64 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
-    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)n), dim3(256), ldsBytes, st, m->dev, dfeat, didx, stride_bytes, dout);
+    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)n), dim3(256), ldsBytes, st, m->dev, dfeat, didx, stride_bytes, dout, (const unsigned int*)nullptr);
+    HIP_CHECK(hipGetLastError());
+}
+
+// k_svm_generic on f32 rows with the row count on the device (the five-stage detector with an RVM first stage, rvm_five_stage.hpp: the
+// launch is queued behind the cascade whose positive counter it reads).  The launch covers nmax rows; min(*dcount, nmax) are scored, each
+// with the arithmetic of fd_svm_generic_launch_on.
+void fd_svm_f32_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, int64_t stride_bytes, int64_t nmax, const unsigned int* dcount,
+                               double* dout) {
+    if (nmax <= 0) return;
+    if (m->dev.dtype != FD_DTYPE_F32) FD_THROW(FD_ERR_LOGIC, "fd_svm_f32_launch_counted: f32 support vectors only");
+    const size_t ldsBytes = (size_t)m->dev.dim * 4;
+    if (ldsBytes > 64 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
+    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)nmax), dim3(256), ldsBytes, st, m->dev, dfeat, (const uint32_t*)nullptr, stride_bytes, dout, dcount);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -17,6 +17,7 @@
 // Roofline: nominally HBM (compulsory bytes/window = layer bytes / windows + 12 B record), in
 // practice VALU/LDS bound; both figures are reported by bench.py --workload wvm.
 #include "fd_internal.hpp"
+#include "five_stage_stages.hpp"
 #include <chrono>
 #include <thread>
 #include <algorithm>

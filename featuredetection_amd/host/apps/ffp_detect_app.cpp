@@ -162,17 +162,8 @@ int main(int argc, char** argv) {
             imgPyr->addImageFilter(make_shared<GrayscaleFilter>());
             auto featureExtractor = make_shared<DirectPyramidFeatureExtractor>(imgPyr, imgpyr.get<int>("patch.width"), imgpyr.get<int>("patch.height"));
             shared_ptr<Detector> det;
-            if (type == "fiveStageCascade") {
-                auto firstClassifier = ProbabilisticWvmClassifier::load(node.get_child("firstClassifier"));
-                auto secondClassifier = ProbabilisticSvmClassifier::load(node.get_child("secondClassifier"));
-                const ptree& oeCfg = node.get_child("overlapElimination");
-                auto oe = make_shared<OverlapElimination>(oeCfg.get<float>("dist", 5.0f), oeCfg.get<float>("ratio", 0.0f));
-                featureExtractor->addPatchFilter(make_shared<HistEq64Filter>());
-                auto swd = make_shared<SlidingWindowDetector>(firstClassifier, featureExtractor);
-                det = make_shared<FiveStageSlidingWindowDetector>(swd, oe, secondClassifier);
-            } else if (type == "single") {   // ffpDetectApp.cpp:427-500
-                // one DirectPyramidFeatureExtractor per pyramid, one FilteringPyramidFeatureExtractor per classifier (:445)
-                auto filteringExtractor = make_shared<FilteringPyramidFeatureExtractor>(featureExtractor);
+            // the patch filters of a "single" node (ffpDetectApp.cpp:446-476): the feature space, then the patchFilter list
+            auto addPatchFilters = [&node](const shared_ptr<FilteringPyramidFeatureExtractor>& filteringExtractor) {
                 const string featurespace = node.get<string>("feature", "hq64");
                 if (featurespace == "histeq") {
                     filteringExtractor->addPatchFilter(make_shared<HistogramEqualizationFilter>());
@@ -200,6 +191,35 @@ int main(int argc, char** argv) {
                         }
                     }
                 }
+            };
+            // the value of a classifier node selects its loader: pwvm | prvm | psvm (FaceFrontal.cfg:5); an empty value: `dflt`
+            auto loadClassifier = [](const ptree& classifierNode, const string& dflt) -> shared_ptr<ProbabilisticClassifier> {
+                string classifierType = classifierNode.get_value<string>();
+                if (classifierType.empty()) classifierType = dflt;
+                if (classifierType == "psvm") return ProbabilisticSvmClassifier::load(classifierNode);
+                if (classifierType == "prvm") return ProbabilisticRvmClassifier::load(classifierNode);
+                if (classifierType == "pwvm") return ProbabilisticWvmClassifier::load(classifierNode);
+                throw std::invalid_argument("unknown classifier type " + classifierType);
+            };
+            if (type == "fiveStageCascade") {
+                auto firstClassifier = loadClassifier(node.get_child("firstClassifier"), "pwvm");
+                auto secondClassifier = loadClassifier(node.get_child("secondClassifier"), "psvm");
+                const ptree& oeCfg = node.get_child("overlapElimination");
+                auto oe = make_shared<OverlapElimination>(oeCfg.get<float>("dist", 5.0f), oeCfg.get<float>("ratio", 0.0f));
+                shared_ptr<SlidingWindowDetector> swd;
+                if (std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(firstClassifier)) {   // ffpDetectApp.cpp:398-419: the WVM's HistEq64 patches
+                    featureExtractor->addPatchFilter(make_shared<HistEq64Filter>());
+                    swd = make_shared<SlidingWindowDetector>(firstClassifier, featureExtractor);
+                } else {   // prvm, psvm: the node's feature / patchFilter keys, as in a "single" node
+                    auto filteringExtractor = make_shared<FilteringPyramidFeatureExtractor>(featureExtractor);
+                    addPatchFilters(filteringExtractor);
+                    swd = make_shared<SlidingWindowDetector>(firstClassifier, filteringExtractor);
+                }
+                det = make_shared<FiveStageSlidingWindowDetector>(swd, oe, secondClassifier);
+            } else if (type == "single") {   // ffpDetectApp.cpp:427-500
+                // one DirectPyramidFeatureExtractor per pyramid, one FilteringPyramidFeatureExtractor per classifier (:445)
+                auto filteringExtractor = make_shared<FilteringPyramidFeatureExtractor>(featureExtractor);
+                addPatchFilters(filteringExtractor);
                 const ptree& classifierNode = node.get_child("classifier");
                 const string classifierType = classifierNode.get_value<string>();
                 shared_ptr<ProbabilisticClassifier> classifier;

@@ -734,6 +734,8 @@ const fd_svm* SvmClassifier::native(double la, double lb) const {
     return handle;
 }
 double SvmClassifier::computeHyperplaneDistance(const Mat& featureVector) const {
+    if (!supportVectors.empty() && featureVector.depth() != supportVectors[0].depth())   // as the reference's kernels (RbfKernel.hpp: lhs.flags != rhs.flags)
+        throw std::invalid_argument("SvmClassifier: feature vector and support vectors have to have the same type");
     Mat x = contiguous(featureVector);
     double out = 0;
     check(fd_svm_distance_batch(context(), native(), x.data, 1, &out));
@@ -1320,36 +1322,123 @@ FiveStageSlidingWindowDetector::FiveStageSlidingWindowDetector(shared_ptr<Slidin
                                                                shared_ptr<classification::ProbabilisticClassifier> strong)
     : slidingWindowDetector(swd), overlapElimination(oe), strongClassifier(strong) {}
 
+static bool svm_vectors_are_f32(const shared_ptr<ProbabilisticSvmClassifier>& psvm) {
+    return psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+}
+// path 1 below, for run and detectFrames alike: what fd_detect_five_stage and fd_detect_five_stage_frames accept
+static bool five_stage_wvm_pair(const shared_ptr<DirectPyramidFeatureExtractor>& direct, const shared_ptr<ProbabilisticWvmClassifier>& pwvm,
+                                const shared_ptr<ProbabilisticSvmClassifier>& psvm) {
+    return direct && pwvm && psvm && direct->hasHistEq64() && !svm_vectors_are_f32(psvm);
+}
+
+// Three paths:
+//  1. ProbabilisticWvmClassifier on HistEq64 patches + ProbabilisticSvmClassifier with u8 support vectors: fd_detect_five_stage
+//  2. the fused RVM case of SlidingWindowDetector::detectWindows ("prvm": a ConversionFilter behind a u8 feature space) + a
+//     ProbabilisticSvmClassifier with f32 support vectors or a ProbabilisticRvmClassifier: fd_detect_five_stage_rvm
+//  3. anything else: the reference's own composition, one classify() per survivor (FiveStageSlidingWindowDetector.cpp:187-320 / :331-380)
 vector<shared_ptr<ClassifiedPatch>> FiveStageSlidingWindowDetector::run(const Mat& image, const cv::Rect* roi) {
     auto direct = std::dynamic_pointer_cast<DirectPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor());
     if (auto filtering = std::dynamic_pointer_cast<imageprocessing::FilteringPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor()))
         direct = filtering->getFusedExtractor();
     auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(slidingWindowDetector->getClassifier());
     auto psvm = std::dynamic_pointer_cast<ProbabilisticSvmClassifier>(strongClassifier);
-    if (!direct || !pwvm || !psvm || !direct->hasHistEq64())
-        throw std::logic_error("FiveStageSlidingWindowDetector: this backend needs DirectPyramidFeatureExtractor + HistEq64Filter, a "
-                               "ProbabilisticWvmClassifier first stage and a ProbabilisticSvmClassifier second stage (ffpDetectApp.cpp:398-419)");
-    direct->update(image);
-    auto selection = direct->getPyramid()->select();   // the scale range of a pyramid built on another pyramid
+    const bool f32sv = svm_vectors_are_f32(psvm);
     int r[4] = {0, 0, 0, 0};
     if (roi) { r[0] = roi->x; r[1] = roi->y; r[2] = roi->width; r[3] = roi->height; }
-    int cnt = 0, cap = 4096;
-    vector<fd_detection> dets((size_t)cap);
-    int rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(pwvm->getLogisticA(), pwvm->getLogisticB()),
-                                  psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()), overlapElimination->getDist(),
-                                  overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(), slidingWindowDetector->getStepSizeY(),
-                                  roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
-    if (rc == FD_ERR_CAPACITY) {
-        dets.resize((size_t)cnt);
-        rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(), psvm->getSvm()->native(),
-                                  overlapElimination->getDist(), overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(),
-                                  slidingWindowDetector->getStepSizeY(), roi ? r : nullptr, dets.data(), cnt, &cnt, nullptr);
+    if (five_stage_wvm_pair(direct, pwvm, psvm)) {
+        direct->update(image);
+        auto selection = direct->getPyramid()->select();   // the scale range of a pyramid built on another pyramid
+        int cnt = 0, cap = 4096;
+        vector<fd_detection> dets((size_t)cap);
+        int rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(pwvm->getLogisticA(), pwvm->getLogisticB()),
+                                      psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()), overlapElimination->getDist(),
+                                      overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(), slidingWindowDetector->getStepSizeY(),
+                                      roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
+        if (rc == FD_ERR_CAPACITY) {
+            dets.resize((size_t)cnt);
+            rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(), psvm->getSvm()->native(),
+                                      overlapElimination->getDist(), overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(),
+                                      slidingWindowDetector->getStepSizeY(), roi ? r : nullptr, dets.data(), cnt, &cnt, nullptr);
+        }
+        check(rc);
+        vector<shared_ptr<ClassifiedPatch>> out;
+        for (int i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
+        if (patchData) fillPatchData(*slidingWindowDetector->getPyramidFeatureExtractor(), out);   // the patches of the shared extractor (FiveStageSlidingWindowDetector.cpp:187-380)
+        return out;
     }
-    check(rc);
-    vector<shared_ptr<ClassifiedPatch>> out;
-    for (int i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-    if (patchData) fillPatchData(*slidingWindowDetector->getPyramidFeatureExtractor(), out);   // the patches of the shared extractor (FiveStageSlidingWindowDetector.cpp:187-380)
-    return out;
+    auto prvm = std::dynamic_pointer_cast<classification::ProbabilisticRvmClassifier>(slidingWindowDetector->getClassifier());
+    auto prvm2 = std::dynamic_pointer_cast<classification::ProbabilisticRvmClassifier>(strongClassifier);
+    if (direct && prvm && direct->getConversion() && !direct->getHistogramFilter() && !direct->getWhiChain()) {
+        const classification::RvmClassifier::Model& m1 = prvm->getRvm()->getModel();
+        bool second = false;
+        if (f32sv) {
+            const Mat& sv = psvm->getSvm()->getSupportVectors()[0];
+            second = (int)(sv.total() * sv.channels()) == m1.filter_w * m1.filter_h;
+        } else if (prvm2 && prvm2->getRvm() != prvm->getRvm()) {
+            const classification::RvmClassifier::Model& m2 = prvm2->getRvm()->getModel();
+            second = m2.filter_w == m1.filter_w && m2.filter_h == m1.filter_h;
+        }
+        if (second) {
+            direct->update(image);
+            auto selection = direct->getPyramid()->select();
+            auto cf = direct->getConversion();
+            fd_rvm_detect_params dp = {direct->getU8FeatureSpace(), (float)cf->alpha, (float)cf->beta, slidingWindowDetector->getStepSizeX(),
+                                       slidingWindowDetector->getStepSizeY()};
+            const fd_rvm* first = prvm->getRvm()->native(prvm->getLogisticA(), prvm->getLogisticB());
+            const fd_svm* s2 = f32sv ? psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()) : nullptr;
+            const fd_rvm* r2 = f32sv ? nullptr : prvm2->getRvm()->native(prvm2->getLogisticA(), prvm2->getLogisticB());
+            int cnt = 0, cap = 4096;
+            vector<fd_detection> dets((size_t)cap);
+            int rc = fd_detect_five_stage_rvm(context(), direct->getPyramid()->native(), first, &dp, s2, r2, overlapElimination->getDist(),
+                                              overlapElimination->getRatio(), roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
+            if (rc == FD_ERR_CAPACITY) {
+                cap = cnt;
+                dets.resize((size_t)cap);
+                rc = fd_detect_five_stage_rvm(context(), direct->getPyramid()->native(), first, &dp, s2, r2, overlapElimination->getDist(),
+                                              overlapElimination->getRatio(), roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
+            }
+            check(rc);
+            vector<shared_ptr<ClassifiedPatch>> out;
+            for (int i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
+            if (patchData) fillPatchData(*slidingWindowDetector->getPyramidFeatureExtractor(), out);
+            return out;
+        }
+    }
+    // the reference's composition: the first detector's positives with their patch data, overlap elimination, one classify() per survivor
+    vector<shared_ptr<ClassifiedPatch>> first;
+    {
+        struct KeepData {   // the strong classifier needs the survivors' pixels whatever the caller asked this detector to keep
+            SlidingWindowDetector& d;
+            bool was;
+            explicit KeepData(SlidingWindowDetector& d_) : d(d_), was(d_.keepsPatchData()) { d.keepPatchData(true); }
+            ~KeepData() { d.keepPatchData(was); }
+        } keepData(*slidingWindowDetector);
+        first = roi ? slidingWindowDetector->detect(image, *roi) : slidingWindowDetector->detect(image);
+    }
+    vector<shared_ptr<ClassifiedPatch>> survivors = overlapElimination->eliminate(first), positives;
+    for (const auto& p : survivors)
+        if (strongClassifier->classify(p->getPatch()->getData())) positives.push_back(make_shared<ClassifiedPatch>(p->getPatch(), true));   // probability 0.5 (ClassifiedPatch.hpp:29-30)
+    auto byProb = [](const shared_ptr<ClassifiedPatch>& a, const shared_ptr<ClassifiedPatch>& b) { return *a > *b; };
+    if (!roi) {   // block NMS on the probability map (:262-320), as five_stage_nms of the fused paths
+        vector<fd_detection> dets;
+        for (const auto& p : positives) dets.push_back(from_patch(*p));
+        vector<int32_t> xy(2 * dets.size() + 2);
+        int n = 0;
+        for (int masked = 1; masked >= 0 && n == 0 && !dets.empty(); --masked)
+            check(fd_block_nms(dets.data(), (int)dets.size(), image.cols, image.rows, 35, masked, xy.data(), (int)dets.size() + 1, &n));
+        if (n == 0) return positives;   // "return svmPatchesPositive; // Should be empty." (:292-294), unsorted
+        std::sort(positives.begin(), positives.end(), byProb);
+        vector<shared_ptr<ClassifiedPatch>> res;
+        for (int i = 0; i < n; ++i) {
+            auto it = std::find_if(positives.begin(), positives.end(), [&](const shared_ptr<ClassifiedPatch>& p) {
+                return p->getPatch()->getX() == xy[2 * (size_t)i] && p->getPatch()->getY() == xy[2 * (size_t)i + 1];
+            });
+            if (it != positives.end()) res.push_back(*it);
+        }
+        positives.swap(res);
+    }
+    std::sort(positives.begin(), positives.end(), byProb);
+    return positives;
 }
 FiveStageSlidingWindowDetector::~FiveStageSlidingWindowDetector() { if (framesPyramid) fd_pyramid_destroy(framesPyramid); }
 
@@ -1368,7 +1457,7 @@ vector<vector<shared_ptr<ClassifiedPatch>>> FiveStageSlidingWindowDetector::dete
         const int n = (int)(j - i);
         const int ch = images[i].channels();
         // (keepPatchData: the patches are cut from the extractor's own pyramid, which the multi-frame path never fills: one image at a time)
-        bool fused = !patchData && direct && pwvm && psvm && direct->hasHistEq64() && n > 1 && images[i].depth() == CV_8U && (ch == 1 || ch == 3);
+        bool fused = !patchData && five_stage_wvm_pair(direct, pwvm, psvm) && n > 1 && images[i].depth() == CV_8U && (ch == 1 || ch == 3);
         if (fused && (!framesPyramid || framesCount != n)) {
             if (framesPyramid) { fd_pyramid_destroy(framesPyramid); framesPyramid = nullptr; }
             framesPyramid = direct->getPyramid()->createFramesPyramid(n);

@@ -436,6 +436,20 @@ typedef struct {
  * ffpDetectApp.cpp:484).  all_level / all_distance (may be NULL): per window in extraction order. */
 int fd_detect_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* rvm, const fd_rvm_detect_params* dp, const int* roi, fd_detection* out,
                   int64_t cap, int64_t* count, int32_t* all_level, double* all_distance);
+/* FiveStageSlidingWindowDetector::detect (:187-320, roi == NULL; :331-380 with roi) with a ProbabilisticRvmClassifier first stage
+ * ("firstClassifier prvm"): RVM cascade -> OverlapElimination(dist, ratio) -> second->classify(patch data) -> positives ->
+ * [block NMS, no-roi only] -> sort.  Stage 1 is fd_detect_rvm.  The second classifier sees the first stage's own feature vector,
+ * float(u8) * conv_scale + conv_shift: exactly one of second_svm (f32 support vectors of filter_w * filter_h values) and second_rvm
+ * (same filter size, another handle than `first`) is non-NULL.  A positive of the second stage carries its hyperplane distance as
+ * score and probability 0.5 (classify() gives a bool only).  stage_counts[4] as fd_detect_five_stage.  FD_ERR_INVALID_ARGUMENT, before
+ * anything runs, for any other pairing and for a multi-frame or layer-filtered pyramid. */
+int fd_detect_five_stage_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* first, const fd_rvm_detect_params* dp, const fd_svm* second_svm,
+                             const fd_rvm* second_rvm, float oe_dist, float oe_ratio, const int* roi, fd_detection* out, int cap, int* count,
+                             int32_t* stage_counts);
+/* fd_pyramid_update (with the pyramid's image filter) + fd_detect_five_stage_rvm in one call, as fd_detect_five_stage_image */
+int fd_detect_five_stage_rvm_image(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* first, const fd_rvm_detect_params* dp, const fd_svm* second_svm,
+                                   const fd_rvm* second_rvm, const uint8_t* image, int width, int height, int channels, int image_is_device,
+                                   float oe_dist, float oe_ratio, const int* roi, fd_detection* out, int cap, int* count, int32_t* stage_counts);
 
 /* ---- supervised descent: superviseddescent::SdmLandmarkModel / SdmLandmarkModelFitting ---------- */
 typedef struct {
