@@ -194,6 +194,11 @@ _SIGS = {
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                        C.POINTER(C.c_int), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_aggregated_create_approximated": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fd_aggregated_get_lambdas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_aggregated_get_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_aggregated_feature_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fd_aggregated_plan_layers": (C.c_int, [C.c_int] * 7 + [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "fd_nms_iou": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "fd_wvm_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_five_stage_batch_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -839,10 +844,30 @@ def fhog(ctx, gray=None, pyramid=None, layer=0, cell_size=8, unsigned_bins=9, in
     return out
 
 
+# fd_aggregated_layer: one feature layer of an aggregated-features detector
+AGG_LAYER_DTYPE = np.dtype([("index", "<i4"), ("approximated", "<i4"), ("parent", "<i4"), ("rows", "<i4"), ("cols", "<i4"),
+                            ("reserved", "<i4"), ("scale", "<f8"), ("scale_x", "<f8"), ("scale_y", "<f8")], align=True)
+
+
+def aggregated_plan_layers(window_w, window_h, cell_size, octave_layers, min_window_width, width, height):
+    """fd_aggregated_plan_layers (host only): the feature layers of an approximated detector on a width x height image as an
+    AGG_LAYER_DTYPE array; FdError (FD_ERR_RUNTIME) when fewer than two exact layers remain"""
+    out = np.zeros(1024, AGG_LAYER_DTYPE)
+    n = C.c_int()
+    rc = lib().fd_aggregated_plan_layers(window_w, window_h, cell_size, octave_layers, min_window_width, width, height, _ptr(out), len(out),
+                                         C.byref(n))
+    if rc != 0:
+        raise FdError(rc, "fd_aggregated_plan_layers: status %d (%d layers)" % (rc, n.value))
+    return out[:n.value].copy()
+
+
 class Aggregated:
-    """fd_aggregated handle: AggregatedFeaturesDetector with GrayscaleFilter + FhogFilter; weights (window_h, window_w, 3B+4)"""
+    """fd_aggregated handle: AggregatedFeaturesDetector with GrayscaleFilter + FhogFilter; weights (window_h, window_w, 3B+4).
+    approximate=True: the approximated feature pyramid (ImagePyramid::createApproximated) with the given per-channel lambdas,
+    or lambdas estimated per image when lambdas is None."""
     def __init__(self, ctx, weights, bias, threshold, cell_size=8, unsigned_bins=9, interpolate_bins=False, interpolate_cells=True, alpha=0.2,
-                 octave_layers=5, min_window_width=0, width_scale=1.0, height_scale=1.0, nms_overlap=0.3, nms_type=0):
+                 octave_layers=5, min_window_width=0, width_scale=1.0, height_scale=1.0, nms_overlap=0.3, nms_type=0, approximate=False,
+                 lambdas=None):
         self.ctx = ctx
         self._w = _c(weights, np.float32)
         wh, ww, d = self._w.shape
@@ -851,7 +876,36 @@ class Aggregated:
                                    octave_layers, min_window_width, width_scale, height_scale, self._w.ctypes.data, bias, threshold,
                                    nms_overlap, nms_type)
         self.h = C.c_void_p()
-        ctx.check(lib().fd_aggregated_create(ctx.h, C.byref(prm), C.byref(self.h)))
+        self.channels = d
+        if approximate:
+            lam = _c(lambdas, np.float64) if lambdas is not None else None
+            ctx.check(lib().fd_aggregated_create_approximated(ctx.h, C.byref(prm), _ptr(lam) if lam is not None else None,
+                                                              len(lam) if lam is not None else 0, C.byref(self.h)))
+        else:
+            if lambdas is not None:
+                raise ValueError("lambdas belong to the approximated feature pyramid (approximate=True)")
+            ctx.check(lib().fd_aggregated_create(ctx.h, C.byref(prm), C.byref(self.h)))
+
+    def lambdas(self):
+        """the lambdas the last detect used (approximated handles)"""
+        out = np.zeros(self.channels, np.float64)
+        n = C.c_int()
+        self.ctx.check(lib().fd_aggregated_get_lambdas(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def layers(self):
+        """feature layers of the last detect, in layer order (AGG_LAYER_DTYPE)"""
+        out = np.zeros(1024, AGG_LAYER_DTYPE)
+        n = C.c_int()
+        self.ctx.check(lib().fd_aggregated_get_layers(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def feature_layer(self, i):
+        """feature layer i (position in layers()) of the last detect: (rows, cols, 3B+4) float32"""
+        L = self.layers()[i]
+        out = np.empty((int(L["rows"]), int(L["cols"]), self.channels), np.float32)
+        self.ctx.check(lib().fd_aggregated_feature_layer(self.ctx.h, self.h, int(i), _ptr(out)))
+        return out
 
     def detect(self, image, cap=1 << 16, candidates=True):
         """(final detections, candidates) as BOX_DTYPE arrays (candidates None when not asked for)"""

@@ -450,3 +450,13 @@ void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, co
 void fd_host_overlap_elimination(const fd_detection* in, int n, float dist, float ratio, std::vector<int>& keep);
 void fd_host_block_nms_sparse(const std::vector<fd_detection>& pos, int imgW, int imgH, int sz, bool masked,
                               std::vector<int>& maxima_xy /* pairs x,y in row-major order */);
+// feature pyramid of the aggregated-features detector: scale limits, and the layer list of the approximated form
+struct FdAggregatedPlan {
+    double minScale = 0, maxScale = 0;
+    std::vector<fd_aggregated_layer> layers;       // layer order: every exact layer followed by its approximations
+    std::vector<std::pair<int, int>> exactPx;      // (w, h) in pixels of the exact layers' gray source layers, in layer order
+};
+void fd_host_aggregated_limits(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width, int height,
+                               double& minScale, double& maxScale);
+void fd_host_plan_aggregated(int cell_size, int octave_layer_count, double minScale, double maxScale, int width, int height,
+                             FdAggregatedPlan& plan);

@@ -46,6 +46,14 @@ struct FhogLayerDev {              // one gray image / pyramid layer of a launch
     int32_t posBlockBase;          // first 8-position block of the layer
 };
 
+struct FhogResizeTab { int32_t i0, i1; float w0, w1; };   // cv::resize INTER_LINEAR, one output row / column: two sources and weights
+struct FhogApproxDev {             // one approximated feature layer of a launch of k_fhog_approx
+    int32_t layer, parent;         // entries of the layer table: output and the exact layer it is resized from
+    int32_t blockBase;             // first 256-value block of the layer
+    int32_t xtab, ytab;            // its column / row tables in the launch-wide FhogResizeTab array
+    int32_t factorBase;            // its per-channel factors
+};
+
 struct FhogLayoutTotals { int cells = 0, coeffs = 0, cellBlocks = 0, positions = 0, posBlocks = 0, pixels = 0, pixBlocks = 0; };
 
 struct fd_aggregated {
@@ -59,6 +67,19 @@ struct fd_aggregated {
     FhogLayoutTotals layout;
     DevBuf dlayers;
     void* arenaAt = nullptr;
+    std::vector<fd_aggregated_layer> layers;   // feature layers of the last detect, layer order
+    std::vector<int> tableOf;                  // their entries in layerTable
+    // approximated feature pyramid (fd_aggregated_create_approximated): the exact layers are the first entries of layerTable,
+    // the approximated ones follow
+    bool approx = false;
+    std::vector<double> givenLambdas, lambdas;   // as created (empty: estimate per image) / used by the last detect
+    FhogLayoutTotals exactLayout;
+    std::vector<FhogApproxDev> approxTable;
+    std::vector<double> approxScale;             // pow(inc, i) per entry of approxTable
+    int approxBlocks = 0, sumChunks = 0, sumLayer[2] = {0, 0};
+    DevBuf dapprox, dresize, dfactors, dsums;
+    std::vector<float> factors;
+    std::vector<double> sums;
     ~fd_aggregated() { if (pyr) fd_pyramid_destroy(pyr); }
 };
 
@@ -268,6 +289,7 @@ struct FhogScratch {
     DevBuf lut, coeff, img, desc, energies, layers, grad, hist;
     fd_fhog_params lutFor;
     bool lutValid = false;
+    const void* descOwner = nullptr;   // the fd_aggregated whose last detect's feature layers `desc` still holds
 };
 FhogScratch& scratch(fd_ctx* ctx) { return fd_scratch<FhogScratch>(ctx); }
 
@@ -343,6 +365,7 @@ FhogLayout layout_layers(std::vector<FhogLayerDev>& layers, const fd_fhog_params
 FhogParamsDev run_fhog(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayout& t, const fd_fhog_params& fp) {
     check_fhog_params(fp);
     build_lut(ctx, S, fp);
+    S.descOwner = nullptr;
     FhogParamsDev d;
     std::memset(&d, 0, sizeof(d));
     d.cell = fp.cell_size; d.ubins = fp.unsigned_bins; d.sbins = 2 * fp.unsigned_bins; d.D = 3 * fp.unsigned_bins + 4;
@@ -456,6 +479,76 @@ __global__ __launch_bounds__(256) void k_fhog_score_wide(const FhogLayerDev* __r
     scores[L.posBase + i] = score;
 }
 
+// ---- approximated feature layers (ImagePyramid::createLayers(const ImagePyramid&), ImagePyramid.cpp:200-235,277-289) ----
+
+// Per-channel double sums of two feature layers (ImagePyramid::computeChannelMeans, :254-261), one launch: blockIdx.y picks the
+// layer, a block owns FHOG_SUM_CELLS consecutive cells.  Lane == channel (D <= 64), so a wavefront reads a cell's descriptor as one
+// run and every lane keeps its channel's sum in a register; the four wavefronts of a block take every fourth cell and meet in LDS,
+// where wavefront 0 adds the four in order and writes the block's partial: no atomics, and a fixed order of additions.  The host
+// adds the partials of a layer in block order.
+constexpr int FHOG_SUM_CELLS = 256;
+__global__ __launch_bounds__(256) void k_fhog_channel_sums(const FhogLayerDev* __restrict__ layers, int layerA, int layerB,
+                                                           const float* __restrict__ descAll, int D, double* __restrict__ partials) {
+    __shared__ double part[4][64];
+    const FhogLayerDev L = layers[blockIdx.y == 0 ? layerA : layerB];
+    const int c = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nCells = L.rows * L.cols;
+    const int first = blockIdx.x * FHOG_SUM_CELLS, last = min(first + FHOG_SUM_CELLS, nCells);
+    const float* F = descAll + (size_t)L.cellBase * D;
+    double sum = 0.0;
+    if (c < D)
+        for (int cell = first + wave; cell < last; cell += 4) sum = sum + (double)F[(size_t)cell * D + c];
+    part[wave][c] = sum;
+    __syncthreads();
+    if (wave == 0 && c < D)
+        partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * D + c] = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+}
+
+// Every approximated layer of every octave in one launch: ImagePyramid::resize (:277-289) = per channel cv::resize(INTER_LINEAR)
+// on CV_32F (float weights, horizontal pass, then vertical pass; the tables come from the host) and a float multiply by
+// (float)pow(s, -lambda[channel]).  One thread per output value, channel fastest: the reads of the four source cells and the write
+// are runs of D floats.  The file is compiled with -ffp-contract=off, so the products and sums below stay separate roundings.
+__global__ __launch_bounds__(256) void k_fhog_approx(const FhogLayerDev* __restrict__ layers, const FhogApproxDev* __restrict__ approx, int nApprox,
+                                                     const FhogResizeTab* __restrict__ tabs, const float* __restrict__ factors, int D,
+                                                     float* __restrict__ descAll) {
+    int ai = 0;
+    for (int i = 1; i < nApprox; ++i)
+        if ((int)blockIdx.x >= approx[i].blockBase) ai = i;
+    const FhogApproxDev A = approx[ai];
+    const FhogLayerDev L = layers[A.layer], P = layers[A.parent];
+    const int e = ((int)blockIdx.x - A.blockBase) * 256 + (int)threadIdx.x;
+    if (e >= L.rows * L.cols * D) return;
+    const int cell = e / D, c = e - cell * D;
+    const int y = cell / L.cols, x = cell - y * L.cols;
+    const FhogResizeTab tx = tabs[A.xtab + x], ty = tabs[A.ytab + y];
+    const float* S = descAll + (size_t)P.cellBase * D + c;
+    const float* S0 = S + (size_t)ty.i0 * P.cols * D;
+    const float* S1 = S + (size_t)ty.i1 * P.cols * D;
+    const float r0 = S0[(size_t)tx.i0 * D] * tx.w0 + S0[(size_t)tx.i1 * D] * tx.w1;
+    const float r1 = S1[(size_t)tx.i0 * D] * tx.w0 + S1[(size_t)tx.i1 * D] * tx.w1;
+    const float v = r0 * ty.w0 + r1 * ty.w1;
+    descAll[(size_t)L.cellBase * D + e] = v * factors[A.factorBase + c];
+}
+
+// cv::resize(INTER_LINEAR) source indices and float weights of `dn` outputs over `sn` inputs (the coordinate arithmetic of
+// OpenCV 2.4's resize, as in the pyramid's own tables); vertical: indices clipped into the image instead of zeroed weights
+void resize_tab(int sn, int dn, bool horizontal, std::vector<FhogResizeTab>& out) {
+    const double inv_scale = (double)dn / sn, scale = 1. / inv_scale;
+    for (int d = 0; d < dn; ++d) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s = (int)std::floor(f);
+        f -= s;
+        if (horizontal) {
+            if (s < 0) { f = 0; s = 0; }
+            if (s >= sn - 1) { f = 0; s = sn - 1; }
+            out.push_back(FhogResizeTab{s, std::min(s + 1, sn - 1), 1.f - f, f});
+        } else {
+            auto clip = [&](int v) { return v < 0 ? 0 : (v >= sn ? sn - 1 : v); };
+            out.push_back(FhogResizeTab{clip(s), clip(s + 1), 1.f - f, f});
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -507,7 +600,7 @@ int fd_pyramid_fhog_layer(fd_ctx* ctx, fd_pyramid* p, int layer, const fd_fhog_p
     });
 }
 
-int fd_aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, fd_aggregated** out) {
+static int aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, bool approx, const double* lambdas, int n_lambdas, fd_aggregated** out) {
     return fd_guard(ctx, [&] {
         if (!ctx || !prm || !out || !prm->svm_weights) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create: NULL argument");
         if (prm->window_w < 1 || prm->window_h < 1 || prm->octave_layer_count < 1)
@@ -523,11 +616,257 @@ int fd_aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, fd_aggreg
         a->prm.svm_weights = nullptr;
         a->dweights.reserve(sizeof(float) * nw);
         HIP_CHECK(hipMemcpy(a->dweights.p, a->weights.data(), sizeof(float) * nw, hipMemcpyHostToDevice));
+        a->approx = approx;
+        if (approx && n_lambdas != 0) {   // ImagePyramid.cpp:212-213
+            if (n_lambdas < 0 || !lambdas) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create_approximated: bad lambdas");
+            if (n_lambdas != 3 * prm->fhog.unsigned_bins + 4)
+                FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: the number of lambdas does not match the number of channels");
+            a->givenLambdas.assign(lambdas, lambdas + n_lambdas);
+        }
         *out = a.release();
     });
 }
 
+int fd_aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, fd_aggregated** out) {
+    return aggregated_create(ctx, prm, false, nullptr, 0, out);
+}
+
+int fd_aggregated_create_approximated(fd_ctx* ctx, const fd_aggregated_params* prm, const double* lambdas, int n_lambdas, fd_aggregated** out) {
+    return aggregated_create(ctx, prm, true, lambdas, n_lambdas, out);
+}
+
+int fd_aggregated_get_lambdas(fd_aggregated* a, double* out, int cap, int* n) {
+    if (!a || !n || cap < 0 || (cap > 0 && !out)) return FD_ERR_INVALID_ARGUMENT;
+    *n = (int)a->lambdas.size();
+    if (*n > cap) return FD_ERR_CAPACITY;
+    std::copy(a->lambdas.begin(), a->lambdas.end(), out);
+    return FD_OK;
+}
+
+int fd_aggregated_get_layers(fd_aggregated* a, fd_aggregated_layer* out, int cap, int* n) {
+    if (!a || !n || cap < 0 || (cap > 0 && !out)) return FD_ERR_INVALID_ARGUMENT;
+    *n = (int)a->layers.size();
+    if (*n > cap) return FD_ERR_CAPACITY;
+    std::copy(a->layers.begin(), a->layers.end(), out);
+    return FD_OK;
+}
+
+int fd_aggregated_feature_layer(fd_ctx* ctx, fd_aggregated* a, int layer, float* out) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !a || !out) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_feature_layer: NULL argument");
+        if (a->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+        FhogScratch& S = scratch(ctx);
+        if (S.descOwner != a) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_feature_layer: the feature layers of this detector's last detect are gone");
+        if (layer < 0 || layer >= (int)a->layers.size()) FD_THROW(FD_ERR_INVALID_ARGUMENT, "no such feature layer: %d", layer);
+        HIP_CHECK(hipSetDevice(ctx->device));
+        const FhogLayerDev& T = a->layerTable[a->tableOf[layer]];
+        const int D = 3 * a->prm.fhog.unsigned_bins + 4;
+        const size_t n = (size_t)T.rows * T.cols * D;
+        if (n) HIP_CHECK(hipMemcpyAsync(out, S.desc.as<float>() + (size_t)T.cellBase * D, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
 void fd_aggregated_destroy(fd_aggregated* a) { delete a; }
+
+// score maps of every layer of the handle's layer table (exact and approximated alike) from the descriptors in S.desc
+static void launch_scores(fd_ctx* ctx, fd_aggregated* a, FhogScratch& S) {
+    const fd_aggregated_params& P = a->prm;
+    const int D = 3 * P.fhog.unsigned_bins + 4, nLayers = (int)a->layerTable.size();
+    if (a->layout.positions <= 0) return;
+    if (D <= 32) {
+        hipLaunchKernelGGL(k_fhog_score, dim3(a->layout.posBlocks), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(), nLayers,
+                           S.desc.as<float>(), D, a->dweights.as<float>(), P.window_h, P.window_w, -P.svm_bias, a->scores.as<float>());
+    } else {
+        int maxPos = 0;
+        for (const FhogLayerDev& T : a->layerTable) maxPos = std::max(maxPos, T.vw * T.vh);
+        hipLaunchKernelGGL(k_fhog_score_wide, dim3((maxPos + 255) / 256, nLayers), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(),
+                           S.desc.as<float>(), D, a->dweights.as<float>(), P.window_h, P.window_w, -P.svm_bias, a->scores.as<float>());
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// a window with score > threshold as a candidate: computeBoundsInImagePixels (AggregatedFeaturesExtractor.cpp:121-128) through
+// the layer's x / y scales, Patch::computeCenter, rescaleWindow (AggregatedFeaturesDetector.cpp:108-112)
+static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float score, int x, int y, double scaleX, double scaleY) {
+    const int cs = P.fhog.cell_size;
+    const int bx = (int)std::round((x * cs) / scaleX), by = (int)std::round((y * cs) / scaleY);
+    const int bw = (int)std::round((P.window_w * cs) / scaleX), bh = (int)std::round((P.window_h * cs) / scaleY);
+    const int cx = bx + bw / 2, cy = by + bh / 2;
+    const int rw = (int)(P.width_scale * bw), rh = (int)(P.height_scale * bh);
+    return fd_box{score, cx - rw / 2, cy - rh / 2, rw, rh};
+}
+
+// Feature pyramid and score maps of an approximated handle.  Per image size: the layer plan, the one-layer-per-octave gray
+// pyramid, the layer table (exact layers first, so that run_fhog's launches see exactly them; the approximated ones follow in
+// the same descriptor buffer), the resize tables and, with given lambdas, the factors.  Per image: pyramid, FHOG of the exact
+// layers, [channel sums -> host: lambdas and factors], k_fhog_approx, the score kernel over all layers.
+static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
+                                     std::vector<fd_box>& cand) {
+    const fd_aggregated_params& P = a->prm;
+    const int D = 3 * P.fhog.unsigned_bins + 4, cs = P.fhog.cell_size, n = P.octave_layer_count;
+    if (!a->pyr || a->pyrW != width || a->pyrH != height) {
+        if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
+        a->layerTable.clear();
+        a->layers.clear();
+        double minScale, maxScale;
+        fd_host_aggregated_limits(P.window_w, P.window_h, cs, n, P.min_window_width, width, height, minScale, maxScale);
+        // both setters forward to the source pyramid (ImagePyramid.hpp:241-263), which has one layer per octave
+        const int rc = fd_pyramid_create(ctx, 1, minScale, maxScale, &a->pyr);
+        if (rc != FD_OK) throw FdError{rc, ctx->error};
+        a->pyrW = width; a->pyrH = height;
+    }
+    {
+        const int rc = fd_pyramid_update(a->pyr, image, width, height, channels, is_device);
+        if (rc != FD_OK) throw FdError{rc, ctx->error};
+    }
+    fd_pyramid* p = a->pyr;
+    const bool estimate = a->givenLambdas.empty();
+    if (estimate && p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:238-239); given lambdas need no second layer (:209-213)
+        FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
+    FhogScratch& S = scratch(ctx);
+    if (a->layerTable.empty() || a->arenaAt != p->arena.p) {
+        FdAggregatedPlan plan;
+        fd_host_plan_aggregated(cs, n, p->minS, p->maxS, width, height, plan);
+        const size_t E = p->kept.size();
+        bool same = plan.exactPx.size() == E;
+        for (size_t li = 0; same && li < E; ++li)
+            same = plan.exactPx[li].first == p->all[p->kept[li]].w && plan.exactPx[li].second == p->all[p->kept[li]].h;
+        if (!same) FD_THROW(FD_ERR_RUNTIME, "fd_aggregated_detect: the layer plan and the gray pyramid disagree");
+        a->layers = plan.layers;
+        a->tableOf.assign(plan.layers.size(), -1);
+        a->layerTable.assign(plan.layers.size(), FhogLayerDev{});
+        std::vector<int> exactPos;   // position in the layer list of the exact layers
+        for (size_t i = 0; i < plan.layers.size(); ++i)
+            if (!plan.layers[i].approximated) exactPos.push_back((int)i);
+        size_t nextApprox = E;
+        for (size_t i = 0, e = 0; i < plan.layers.size(); ++i) {
+            const fd_aggregated_layer& L = plan.layers[i];
+            const int ti = L.approximated ? (int)nextApprox++ : (int)e++;
+            a->tableOf[i] = ti;
+            FhogLayerDev& T = a->layerTable[ti];
+            std::memset(&T, 0, sizeof(T));
+            if (!L.approximated) {
+                const HostLayer& H = p->all[p->kept[ti]];
+                T.img = p->arena.as<uint8_t>() + H.gray_off; T.w = H.w; T.h = H.h; T.stride = H.w; T.channels = 1;
+            } else {   // no pixels: layout_layers derives rows / cols from w / h
+                const fd_aggregated_layer& X = plan.layers[L.parent];
+                const bool empty = X.rows < 1 || X.cols < 1;
+                T.w = empty ? 0 : L.cols * cs; T.h = empty ? 0 : L.rows * cs;
+            }
+            T.vh = std::max(T.h / cs - P.window_h + 1, 0);
+            T.vw = std::max(T.w / cs - P.window_w + 1, 0);
+            if (T.vw == 0 || T.vh == 0) T.vw = T.vh = 0;
+        }
+        {
+            std::vector<FhogLayerDev> exact(a->layerTable.begin(), a->layerTable.begin() + E);
+            a->exactLayout = layout_layers(exact, P.fhog);
+        }
+        a->layout = layout_layers(a->layerTable, P.fhog);
+        // approximated layers: launch table, cv::resize tables, factors
+        a->approxTable.clear();
+        a->approxScale.clear();
+        std::vector<FhogResizeTab> tabs;
+        int blocks = 0;
+        const double inc = std::pow(0.5, 1. / n);
+        for (size_t i = 0; i < plan.layers.size(); ++i) {
+            const fd_aggregated_layer& L = plan.layers[i];
+            if (!L.approximated) continue;
+            const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
+            const FhogLayerDev& X = a->layerTable[a->tableOf[L.parent]];
+            if (T.rows < 1 || T.cols < 1) continue;
+            FhogApproxDev A;
+            A.layer = a->tableOf[i]; A.parent = a->tableOf[L.parent];
+            A.blockBase = blocks;
+            A.xtab = (int)tabs.size();
+            resize_tab(X.cols, T.cols, true, tabs);
+            A.ytab = (int)tabs.size();
+            resize_tab(X.rows, T.rows, false, tabs);
+            A.factorBase = (int)a->approxTable.size() * D;
+            blocks += (int)(((int64_t)T.rows * T.cols * D + 255) / 256);
+            a->approxTable.push_back(A);
+            a->approxScale.push_back(std::pow(inc, L.index - plan.layers[L.parent].index));
+        }
+        a->approxBlocks = blocks;
+        a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
+        HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
+        if (!a->approxTable.empty()) {
+            a->dapprox.reserve(sizeof(FhogApproxDev) * a->approxTable.size());
+            HIP_CHECK(hipMemcpy(a->dapprox.p, a->approxTable.data(), sizeof(FhogApproxDev) * a->approxTable.size(), hipMemcpyHostToDevice));
+            a->dresize.reserve(sizeof(FhogResizeTab) * tabs.size());
+            HIP_CHECK(hipMemcpy(a->dresize.p, tabs.data(), sizeof(FhogResizeTab) * tabs.size(), hipMemcpyHostToDevice));
+            a->dfactors.reserve(sizeof(float) * a->approxTable.size() * D);
+        }
+        a->factors.assign(a->approxTable.size() * D, 0.f);
+        // the two exact layers the lambdas are estimated from (ImagePyramid.cpp:240-243)
+        if (estimate) {
+            a->sumLayer[0] = E > 2 ? 1 : 0;
+            a->sumLayer[1] = a->sumLayer[0] + 1;
+            const FhogLayerDev& SA = a->layerTable[a->sumLayer[0]];
+            a->sumChunks = std::max(1, (SA.rows * SA.cols + FHOG_SUM_CELLS - 1) / FHOG_SUM_CELLS);   // the larger of the two
+            a->dsums.reserve(sizeof(double) * 2 * a->sumChunks * D);
+            a->sums.assign((size_t)2 * a->sumChunks * D, 0.0);
+        }
+        a->lambdas.clear();
+        a->arenaAt = p->arena.p;
+    }
+    const int nExact = (int)p->kept.size(), nApprox = (int)a->approxTable.size();
+    a->scores.reserve(sizeof(float) * std::max<size_t>((size_t)a->layout.positions, 1));
+    S.desc.reserve(sizeof(float) * (size_t)std::max(a->layout.cells, 1) * D);   // before run_fhog: room for the approximated layers too
+    run_fhog(ctx, S, a->dlayers.as<FhogLayerDev>(), nExact, a->exactLayout, P.fhog);
+    // factors (float)pow(s, -lambda[c]) (ImagePyramid.cpp:284; Mat *= double on CV_32F multiplies by the float)
+    auto set_factors = [&](const std::vector<double>& lambdas) {
+        for (int k = 0; k < nApprox; ++k)
+            for (int c = 0; c < D; ++c) a->factors[(size_t)k * D + c] = (float)std::pow(a->approxScale[k], -lambdas[c]);
+        if (nApprox) HIP_CHECK(hipMemcpyAsync(a->dfactors.p, a->factors.data(), sizeof(float) * a->factors.size(), hipMemcpyHostToDevice, ctx->stream));
+    };
+    if (estimate) {
+        hipLaunchKernelGGL(k_fhog_channel_sums, dim3(a->sumChunks, 2), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(), a->sumLayer[0],
+                           a->sumLayer[1], S.desc.as<float>(), D, a->dsums.as<double>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(a->sums.data(), a->dsums.p, sizeof(double) * a->sums.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        // estimateLambdas(layer1, layer2) (ImagePyramid.cpp:246-275): means, ratios, -log(ratio) / log(scale1 / scale2), host libm
+        std::vector<double> lambdas(D);
+        double mean[2];
+        double scaleOf[2];
+        for (int k = 0; k < 2; ++k) scaleOf[k] = p->all[p->kept[a->sumLayer[k]]].scale;
+        for (int c = 0; c < D; ++c) {
+            for (int k = 0; k < 2; ++k) {
+                const FhogLayerDev& T = a->layerTable[a->sumLayer[k]];
+                double sum = 0.0;
+                for (int b = 0; b < a->sumChunks; ++b) sum += a->sums[((size_t)k * a->sumChunks + b) * D + c];
+                mean[k] = sum / ((double)T.rows * T.cols);
+            }
+            lambdas[c] = -std::log(mean[0] / mean[1]) / std::log(scaleOf[0] / scaleOf[1]);
+        }
+        a->lambdas = lambdas;
+        set_factors(a->lambdas);
+    } else if (a->lambdas.empty()) {   // given lambdas: once per geometry
+        a->lambdas = a->givenLambdas;
+        set_factors(a->lambdas);
+    }
+    if (nApprox && a->approxBlocks > 0) {
+        hipLaunchKernelGGL(k_fhog_approx, dim3(a->approxBlocks), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(),
+                           a->dapprox.as<FhogApproxDev>(), nApprox, a->dresize.as<FhogResizeTab>(), a->dfactors.as<float>(), D, S.desc.as<float>());
+        HIP_CHECK(hipGetLastError());
+    }
+    launch_scores(ctx, a, S);
+    std::vector<float> hs((size_t)a->layout.positions);
+    if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    S.descOwner = a;
+    // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106) over the layers in layer order
+    for (size_t i = 0; i < a->layers.size(); ++i) {
+        const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
+        const fd_aggregated_layer& L = a->layers[i];
+        for (int y = 0; y < T.vh; ++y)
+            for (int x = 0; x < T.vw; ++x) {
+                const float score = hs[(size_t)T.posBase + (size_t)y * T.vw + x];
+                if (score > P.score_threshold) cand.push_back(aggregated_candidate(P, score, x, y, L.scale_x, L.scale_y));
+            }
+    }
+}
 
 int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device, fd_box* out,
                          int cap, int* count, fd_box* candidates, int cand_cap, int* cand_count) {
@@ -536,23 +875,15 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         if (a->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
         const fd_aggregated_params& P = a->prm;
         HIP_CHECK(hipSetDevice(ctx->device));
+        std::vector<fd_box> cand;
+        if (a->approx) aggregated_detect_approx(ctx, a, image, width, height, channels, is_device, cand);
+        else {
         // feature pyramid limits (AggregatedFeaturesExtractor.cpp:30-31,47-52,58-77), recomputed when the image size changes
         if (!a->pyr || a->pyrW != width || a->pyrH != height) {
             if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
             a->layerTable.clear();
-            const int patchWpx = P.window_w * P.fhog.cell_size, patchHpx = P.window_h * P.fhog.cell_size;
-            const double inc = std::pow(0.5, 1. / P.octave_layer_count);
-            double maxScale = 1.0;
-            if (P.min_window_width > patchWpx) {
-                const double m = (double)patchWpx / P.min_window_width;
-                const int minLayerIndex = (int)std::ceil(std::log(m) / std::log(inc));
-                maxScale = std::pow(inc, minLayerIndex);
-            }
-            const double aspectRatio = (double)patchHpx / (double)patchWpx, imageAspectRatio = (double)height / (double)width;
-            const int maxWidth = aspectRatio > imageAspectRatio ? (int)(height / aspectRatio) : width;
-            const double m = (double)patchWpx / maxWidth;
-            const int maxLayerIndex = (int)(std::log(m) / std::log(inc));
-            const double minScale = std::pow(inc, maxLayerIndex);
+            double minScale, maxScale;
+            fd_host_aggregated_limits(P.window_w, P.window_h, P.fhog.cell_size, P.octave_layer_count, P.min_window_width, width, height, minScale, maxScale);
             const int rc = fd_pyramid_create(ctx, P.octave_layer_count, minScale, maxScale, &a->pyr);
             if (rc != FD_OK) throw FdError{rc, ctx->error};
             a->pyrW = width; a->pyrH = height;
@@ -565,7 +896,6 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         if (p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:240-242) of the score pyramid
             FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
         FhogScratch& S = scratch(ctx);
-        const int D = 3 * P.fhog.unsigned_bins + 4;
         // layer table of this pyramid geometry (rebuilt with the pyramid): descriptors and score maps of all layers run as
         // single launches over the table
         if (a->layerTable.empty() || a->arenaAt != p->arena.p) {
@@ -583,6 +913,14 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
             a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
             HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
             a->arenaAt = p->arena.p;
+            a->layers.resize(p->kept.size());
+            a->tableOf.resize(p->kept.size());
+            for (size_t li = 0; li < p->kept.size(); ++li) {
+                const HostLayer& L = p->all[p->kept[li]];
+                a->layers[li] = fd_aggregated_layer{L.index, 0, -1, a->layerTable[li].rows, a->layerTable[li].cols, 0, L.scale,
+                                                    (double)L.w / (double)width, (double)L.h / (double)height};
+                a->tableOf[li] = (int)li;
+            }
         }
         const int nLayers = (int)a->layerTable.size();
         std::vector<size_t> off(p->kept.size() + 1, 0);
@@ -594,37 +932,21 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         off[p->kept.size()] = (size_t)a->layout.positions;
         a->scores.reserve(sizeof(float) * std::max<size_t>(off.back(), 1));
         run_fhog(ctx, S, a->dlayers.as<FhogLayerDev>(), nLayers, a->layout, P.fhog);
-        if (a->layout.positions > 0) {
-            if (D <= 32) {
-                hipLaunchKernelGGL(k_fhog_score, dim3(a->layout.posBlocks), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(), nLayers,
-                                   S.desc.as<float>(), D, a->dweights.as<float>(), P.window_h, P.window_w, -P.svm_bias, a->scores.as<float>());
-            } else {
-                int maxPos = 0;
-                for (const FhogLayerDev& T : a->layerTable) maxPos = std::max(maxPos, T.vw * T.vh);
-                hipLaunchKernelGGL(k_fhog_score_wide, dim3((maxPos + 255) / 256, nLayers), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(),
-                                   S.desc.as<float>(), D, a->dweights.as<float>(), P.window_h, P.window_w, -P.svm_bias, a->scores.as<float>());
-            }
-            HIP_CHECK(hipGetLastError());
-        }
+        launch_scores(ctx, a, S);
         std::vector<float> hs(off.back());
         if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        S.descOwner = a;
         // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106): layer, row, column order
-        std::vector<fd_box> cand;
         for (size_t li = 0; li < p->kept.size(); ++li) {
             const HostLayer& L = p->all[p->kept[li]];
             const double scaleX = (double)L.w / (double)width, scaleY = (double)L.h / (double)height;   // ImagePyramid.cpp:178-179,187-188
             for (int y = 0; y < vh[li]; ++y)
                 for (int x = 0; x < vw[li]; ++x) {
                     const float score = hs[off[li] + (size_t)y * vw[li] + x];
-                    if (!(score > P.score_threshold)) continue;
-                    const int cs = P.fhog.cell_size;
-                    const int bx = (int)std::round((x * cs) / scaleX), by = (int)std::round((y * cs) / scaleY);
-                    const int bw = (int)std::round((P.window_w * cs) / scaleX), bh = (int)std::round((P.window_h * cs) / scaleY);
-                    const int cx = bx + bw / 2, cy = by + bh / 2;                                // Patch::computeCenter
-                    const int rw = (int)(P.width_scale * bw), rh = (int)(P.height_scale * bh);  // rescaleWindow :108-112
-                    cand.push_back(fd_box{score, cx - rw / 2, cy - rh / 2, rw, rh});
+                    if (score > P.score_threshold) cand.push_back(aggregated_candidate(P, score, x, y, scaleX, scaleY));
                 }
+        }
         }
         if (cand_count) *cand_count = (int)cand.size();
         if (candidates)

@@ -4,6 +4,7 @@
 // thousand records and the algorithms are sequential by definition (sort + greedy erase).
 #include "fd_internal.hpp"
 #include <algorithm>
+#include <cstring>
 #include <map>
 
 // detection::OverlapElimination::eliminate (OverlapElimination.cpp:44-105).  std::sort on the
@@ -280,5 +281,101 @@ extern "C" int fd_nms_iou(const fd_box* in, int n, double overlap_threshold, int
         out[nout++] = r;
     }
     *count = nout;
+    return FD_OK;
+}
+
+// Scale limits of the feature pyramid of an extraction::AggregatedFeaturesExtractor (AggregatedFeaturesExtractor.cpp:30-31,
+// 47-77): computed with the incremental scale factor of the octaveLayerCount pyramid, exact or approximated.
+void fd_host_aggregated_limits(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width, int height,
+                               double& minScale, double& maxScale) {
+    const int patchWpx = window_w * cell_size, patchHpx = window_h * cell_size;
+    const double inc = std::pow(0.5, 1. / octave_layer_count);
+    maxScale = 1.0;
+    if (min_window_width > patchWpx) {
+        const double m = (double)patchWpx / min_window_width;
+        const int minLayerIndex = (int)std::ceil(std::log(m) / std::log(inc));
+        maxScale = std::pow(inc, minLayerIndex);
+    }
+    const double aspectRatio = (double)patchHpx / (double)patchWpx, imageAspectRatio = (double)height / (double)width;
+    const int maxWidth = aspectRatio > imageAspectRatio ? (int)(height / aspectRatio) : width;
+    const double m = (double)patchWpx / maxWidth;
+    const int maxLayerIndex = (int)(std::log(m) / std::log(inc));
+    minScale = std::pow(inc, maxLayerIndex);
+}
+
+// Layers of ImagePyramid::createApproximated(octaveLayerCount, min, max) (ImagePyramid.cpp:51-63): the source pyramid has one
+// layer per octave (createLayers(const Mat&), :170-198: scale 1, then pyrDown while scale *= 0.5 stays >= min), FHOG turns each
+// kept one into an exact feature layer, and createLayers(const ImagePyramid&) (:200-235) emits every exact layer followed by its
+// approximations.  Whether a layer exists is decided by the double rounding of these very expressions (libm pow, repeated
+// *= 0.5, exact.scale * pow(inc, i)), so none of them is rewritten.
+void fd_host_plan_aggregated(int cell_size, int octave_layer_count, double minScale, double maxScale, int width, int height,
+                             FdAggregatedPlan& plan) {
+    plan.minScale = minScale;
+    plan.maxScale = maxScale;
+    plan.layers.clear();
+    plan.exactPx.clear();
+    const int n = octave_layer_count;
+    const double inc = std::pow(0.5, 1. / n);
+    struct Src { int index; double scale; int w, h; };
+    std::vector<Src> src;
+    {
+        double scaleFactor = 1.0;   // pow(incrementalScaleFactor, 0) of the one-layer pyramid
+        int pw = fd_cvRound(width * scaleFactor), ph = fd_cvRound(height * scaleFactor);
+        if (scaleFactor <= maxScale && scaleFactor >= minScale) src.push_back(Src{0, scaleFactor, pw, ph});
+        scaleFactor *= 0.5;
+        for (int j = 1; scaleFactor >= minScale && pw > 1; ++j, scaleFactor *= 0.5) {
+            pw = (pw + 1) / 2;
+            ph = (ph + 1) / 2;
+            if (scaleFactor <= maxScale) src.push_back(Src{j, scaleFactor, pw, ph});
+        }
+    }
+    for (const Src& s : src) {
+        if (s.scale < minScale) break;
+        fd_aggregated_layer e;
+        std::memset(&e, 0, sizeof(e));
+        e.index = s.index * n;
+        e.parent = -1;
+        e.rows = s.h / cell_size;
+        e.cols = s.w / cell_size;
+        e.scale = s.scale;
+        e.scale_x = (double)s.w / (double)width;     // ImagePyramid.cpp:178-179,187-188
+        e.scale_y = (double)s.h / (double)height;
+        const int parent = (int)plan.layers.size();
+        if (s.scale <= maxScale) {
+            plan.layers.push_back(e);
+            plan.exactPx.emplace_back(s.w, s.h);
+        }
+        for (int i = 1; i < n; ++i) {
+            const double scaleFactor = std::pow(inc, i);
+            const double overallScale = e.scale * scaleFactor;
+            if (overallScale >= minScale && overallScale <= maxScale) {
+                fd_aggregated_layer a;
+                std::memset(&a, 0, sizeof(a));
+                a.index = e.index + i;
+                a.approximated = 1;
+                a.parent = parent;
+                a.cols = fd_cvRound(e.cols * scaleFactor);   // ImagePyramid::resize :278
+                a.rows = fd_cvRound(e.rows * scaleFactor);
+                a.scale = overallScale;
+                a.scale_x = e.scale_x * scaleFactor;
+                a.scale_y = e.scale_y * scaleFactor;
+                plan.layers.push_back(a);
+            }
+        }
+    }
+}
+
+extern "C" int fd_aggregated_plan_layers(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width,
+                                         int height, fd_aggregated_layer* out, int cap, int* n) {
+    if (!n || window_w < 1 || window_h < 1 || cell_size < 1 || octave_layer_count < 1 || width < 1 || height < 1 || cap < 0 || (cap > 0 && !out))
+        return FD_ERR_INVALID_ARGUMENT;
+    double minScale, maxScale;
+    fd_host_aggregated_limits(window_w, window_h, cell_size, octave_layer_count, min_window_width, width, height, minScale, maxScale);
+    FdAggregatedPlan plan;
+    fd_host_plan_aggregated(cell_size, octave_layer_count, minScale, maxScale, width, height, plan);
+    *n = (int)plan.layers.size();
+    if (plan.exactPx.size() < 2) return FD_ERR_RUNTIME;   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:238-239)
+    if (*n > cap) return FD_ERR_CAPACITY;
+    for (int i = 0; i < *n; ++i) out[i] = plan.layers[i];
     return FD_OK;
 }

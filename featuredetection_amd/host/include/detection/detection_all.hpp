@@ -84,7 +84,12 @@ public:
                                int cellSize, cv::Size windowSize, int octaveLayerCount, std::shared_ptr<classification::SvmClassifier> svm,
                                std::shared_ptr<NonMaximumSuppression> nonMaximumSuppression, float widthScale = 1.0f, float heightScale = 1.0f,
                                int minWindowWidth = 0);
+    // AggregatedFeaturesDetector.cpp:61-67: on an extractor over an approximated feature pyramid (createApproximateDetector)
+    AggregatedFeaturesDetector(std::shared_ptr<imageprocessing::extraction::AggregatedFeaturesExtractor> featureExtractor,
+                               std::shared_ptr<classification::SvmClassifier> svm, std::shared_ptr<NonMaximumSuppression> nonMaximumSuppression,
+                               float widthScale = 1.0f, float heightScale = 1.0f);
     ~AggregatedFeaturesDetector();
+    std::vector<double> getLambdas() const;   // the lambdas of the last detect (approximated feature pyramid)
     std::vector<cv::Rect> detect(std::shared_ptr<imageprocessing::VersionedImage> image);
     std::vector<std::pair<cv::Rect, float>> detectWithScores(std::shared_ptr<imageprocessing::VersionedImage> image);
     std::vector<cv::Rect> detect(const cv::Mat& image) { return detect(std::make_shared<imageprocessing::VersionedImage>(image)); }
@@ -93,6 +98,8 @@ public:
     }
     float getScoreThreshold() const { return scoreThreshold; }
 private:
+    void create(const imageprocessing::filtering::FhogFilter& fhog, cv::Size windowSize, int octaveLayerCount, const classification::SvmClassifier& svm,
+                const NonMaximumSuppression& nms, float widthScale, float heightScale, int minWindowWidth, const std::vector<double>* lambdas);
     fd_aggregated* handle = nullptr;
     float scoreThreshold;
 };

@@ -252,6 +252,23 @@ public:
     // the layers of the source (and its device arena) are shared (createLayers(const ImagePyramid&), :200-235, without the
     // approximated in-between layers of createApproximated)
     ImagePyramid(std::shared_ptr<ImagePyramid> pyramid, double minScaleFactor, double maxScaleFactor = 1);
+    // ImagePyramid.cpp:51-63: a feature pyramid whose layers are computed on one layer per octave only and approximated (resized,
+    // scaled by pow(s, -lambda) per channel) in between.  On this backend such a pyramid is the recipe of an
+    // extraction::AggregatedFeaturesExtractor behind an AggregatedFeaturesDetector (image filter GrayscaleFilter, layer filter
+    // filtering::FhogFilter); the device builds its layers inside fd_aggregated_detect.  Using it for anything else -- updating it
+    // directly, extractors over its layers, other filters -- throws logic_error, and so does approximating an arbitrary source pyramid.
+    static std::shared_ptr<ImagePyramid> createApproximated(int octaveLayerCount, double minScaleFactor, double maxScaleFactor,
+                                                            std::vector<double> lambdas = {});
+    static std::shared_ptr<ImagePyramid> createApproximated(std::shared_ptr<ImagePyramid> pyramid, int octaveLayerCount,
+                                                            std::vector<double> lambdas = {});
+    // empty: estimated per image.  An AggregatedFeaturesDetector reads the lambdas, the layer filter and the image filter when it is
+    // constructed on the extractor: later changes to the pyramid do not reach a detector that already exists.
+    void setLambdas(const std::vector<double>& lambdas) { this->lambdas = lambdas; }
+    const std::vector<double>& getLambdas() const { return lambdas; }
+    bool isApproximated() const { return approximated; }
+    size_t getOctaveLayerCount() const { return ctorOctaveLayers; }
+    std::shared_ptr<ImageFilter> getApproximatedLayerFilter() const { return approxLayerFilter; }
+    bool hasGrayscaleImageFilter() const { return imageChain.size() == 1 && imageChain[0] == FD_IMAGE_GRAY; }
     ~ImagePyramid();
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
@@ -272,7 +289,7 @@ public:
     cv::Size getImageSize() const { return imageSize; }
     std::vector<std::pair<int, double>> getLayerScales() const;
     std::vector<cv::Size> getLayerSizes() const;
-    fd_pyramid* native() const { return sourcePyramid ? sourcePyramid->native() : handle; }
+    fd_pyramid* native() const { return sourcePyramid ? sourcePyramid->native() : (requireExact(), handle); }
     std::shared_ptr<ImagePyramid> getSourcePyramid() const { return sourcePyramid; }
     // a second native pyramid with this pyramid's parameters that holds `frames` equally sized frames at once (backend extension
     // behind FiveStageSlidingWindowDetector::detectFrames); NULL for pyramids on a source pyramid or with layer filters
@@ -292,6 +309,9 @@ public:
     Selection select(int firstLayer = -1, int lastLayer = -1, int stepLayer = 1, const cv::Rect* roi = nullptr) const;
     static long buildCount();   // pyramids actually (re)built so far: the VersionedImage mechanism at work (tests)
 private:
+    struct Approximated {};
+    ImagePyramid(Approximated, size_t octaveLayerCount, double minScaleFactor, double maxScaleFactor, std::vector<double> lambdas);
+    void requireExact() const;   // logic_error on an approximated pyramid
     void applyLayerFilterConfig();
     void viewRange(int& first, int& last) const;   // layer indices of the source inside [minScaleFactor, maxScaleFactor]
     fd_pyramid* handle;
@@ -308,6 +328,9 @@ private:
     std::vector<int> imageChain;          // addImageFilter: FD_IMAGE_GREYWORLD_GRAY for a GreyWorldNormalizationFilter, FD_IMAGE_GRAY for a GrayscaleFilter
     mutable std::vector<std::shared_ptr<ImagePyramidLayer>> layers;
     mutable bool layersValid;
+    bool approximated = false;            // createApproximated: no native pyramid; lambdas and layer filter are recorded
+    std::vector<double> lambdas;
+    std::shared_ptr<ImageFilter> approxLayerFilter;
 };
 
 // Patch.hpp:28-243
@@ -477,5 +500,25 @@ public:
     float alpha;
 };
 }  // namespace filtering
+
+// extraction/AggregatedFeaturesExtractor.hpp:27-146 / AggregatedFeaturesExtractor.cpp:23-32: the feature-pyramid form.  On this
+// backend the feature pyramid must be an approximated one (ImagePyramid::createApproximated) with a GrayscaleFilter image filter
+// and a filtering::FhogFilter layer filter, and the minimum scale factor must be adjusted per image; the extractor is then the
+// argument of AggregatedFeaturesDetector's extractor constructor, which runs it on the device.
+namespace extraction {
+class AggregatedFeaturesExtractor {
+public:
+    AggregatedFeaturesExtractor(std::shared_ptr<ImagePyramid> featurePyramid, cv::Size patchSizeInCells, int cellSizeInPixels,
+                                bool adjustMinScaleFactor, int minPatchWidthInPixels = 0);
+    std::shared_ptr<ImagePyramid> getFeaturePyramid() { return featurePyramid; }
+    cv::Size getPatchSizeInCells() const { return patchSizeInCells; }
+    int getCellSizeInPixels() const { return cellSizeInPixels; }
+    int getMinPatchWidthInPixels() const { return minPatchWidthInPixels; }
+private:
+    std::shared_ptr<ImagePyramid> featurePyramid;
+    cv::Size patchSizeInCells;
+    int cellSizeInPixels, minPatchWidthInPixels;
+};
+}  // namespace extraction
 
 }  // namespace imageprocessing

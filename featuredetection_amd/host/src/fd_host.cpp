@@ -277,8 +277,31 @@ ImagePyramid::ImagePyramid(shared_ptr<ImagePyramid> pyramid, double minS, double
     : handle(nullptr), sourcePyramid(pyramid), minScaleFactor(minS), maxScaleFactor(maxS), layersValid(false) {
     if (!pyramid) throw std::invalid_argument("ImagePyramid: the source pyramid must not be null");
 }
+// ImagePyramid.cpp:51-63.  The approximated pyramid holds no native pyramid: it records what fd_aggregated_create_approximated needs.
+ImagePyramid::ImagePyramid(Approximated, size_t octaveLayerCount, double minS, double maxS, vector<double> lambdas)
+    : handle(nullptr), minScaleFactor(minS), maxScaleFactor(maxS), ctorOctaveLayers(octaveLayerCount), layersValid(false), approximated(true),
+      lambdas(std::move(lambdas)) {
+    if (octaveLayerCount == 0) throw std::invalid_argument("ImagePyramid: the number of layers per octave must be greater than zero");
+    if (minS <= 0) throw std::invalid_argument("ImagePyramid: the minimum scale factor must be greater than zero");
+    if (maxS > 1) throw std::invalid_argument("ImagePyramid: the maximum scale factor must not exceed one");
+}
+shared_ptr<ImagePyramid> ImagePyramid::createApproximated(int octaveLayerCount, double minS, double maxS, vector<double> lambdas) {
+    return shared_ptr<ImagePyramid>(new ImagePyramid(Approximated{}, (size_t)std::max(octaveLayerCount, 0), minS, maxS, std::move(lambdas)));
+}
+shared_ptr<ImagePyramid> ImagePyramid::createApproximated(shared_ptr<ImagePyramid>, int, vector<double>) {
+    throw std::logic_error("ImagePyramid: approximating the layers of an arbitrary source pyramid is not available on this backend "
+                           "(createApproximated(octaveLayerCount, min, max, lambdas) is)");
+}
+void ImagePyramid::requireExact() const {
+    if (approximated)
+        throw std::logic_error("ImagePyramid: an approximated pyramid is available as the feature pyramid of an AggregatedFeaturesExtractor "
+                               "behind an AggregatedFeaturesDetector only");
+}
 ImagePyramid::~ImagePyramid() { if (handle) fd_pyramid_destroy(handle); }
-double ImagePyramid::getIncrementalScaleFactor() const { return fd_pyramid_incremental_scale(native()); }
+double ImagePyramid::getIncrementalScaleFactor() const {
+    if (approximated) return std::pow(0.5, 1. / ctorOctaveLayers);
+    return fd_pyramid_incremental_scale(native());
+}
 static long g_pyramidBuilds = 0;
 long ImagePyramid::buildCount() { return g_pyramidBuilds; }
 
@@ -296,6 +319,7 @@ void ImagePyramid::addImageFilter(const shared_ptr<ImageFilter>& filter) {
     if (sourcePyramid) sourcePyramid->addImageFilter(filter);   // ImagePyramid.cpp:108-110
 }
 void ImagePyramid::setSource(const shared_ptr<VersionedImage>& image) {
+    requireExact();
     if (sourcePyramid && !handle)
         throw std::logic_error("ImagePyramid: a pyramid that was constructed on another pyramid has no layer parameters of its own to build from an image");
     sourcePyramid.reset();
@@ -303,6 +327,7 @@ void ImagePyramid::setSource(const shared_ptr<VersionedImage>& image) {
 }
 void ImagePyramid::setSource(const shared_ptr<ImagePyramid>& pyramid) {
     if (!pyramid) throw std::invalid_argument("ImagePyramid: the source pyramid must not be null");
+    requireExact();
     if (gradient || binning || lbp) throw std::logic_error("ImagePyramid: layer filters on top of a source pyramid are not available on this backend");
     sourceImage.reset();
     sourcePyramid = pyramid;
@@ -310,6 +335,7 @@ void ImagePyramid::setSource(const shared_ptr<ImagePyramid>& pyramid) {
     layersValid = false;
 }
 void ImagePyramid::update() {   // ImagePyramid.cpp:146-168
+    requireExact();
     if (sourcePyramid) {
         if (version != sourcePyramid->version) { version = sourcePyramid->version; imageSize = sourcePyramid->imageSize; layersValid = false; }
     } else if (sourceImage) {
@@ -350,6 +376,12 @@ ImagePyramid::Selection ImagePyramid::select(int firstLayer, int lastLayer, int 
     return Selection(native(), firstLayer, lastLayer, stepLayer, r, view ? vf : -1, view ? vl : -1);
 }
 void ImagePyramid::addLayerFilter(const shared_ptr<ImageFilter>& filter) {
+    if (approximated) {
+        if (approxLayerFilter || !std::dynamic_pointer_cast<filtering::FhogFilter>(filter))
+            throw std::logic_error("ImagePyramid: the layer filter of an approximated pyramid is one filtering::FhogFilter on this backend");
+        approxLayerFilter = filter;
+        return;
+    }
     if (sourcePyramid) throw std::logic_error("ImagePyramid: layer filters on top of a source pyramid are not available on this backend");
     if (auto g = std::dynamic_pointer_cast<GradientFilter>(filter)) gradient = g;
     else if (auto b = std::dynamic_pointer_cast<GradientBinningFilter>(filter)) binning = b;
@@ -370,6 +402,7 @@ void ImagePyramid::applyLayerFilterConfig() {
 }
 void ImagePyramid::update(const Mat& image) { update(make_shared<VersionedImage>(image)); }
 void ImagePyramid::update(const shared_ptr<VersionedImage>& image) {
+    requireExact();
     if (sourcePyramid) {   // ImagePyramid.cpp:121-124: the source pyramid is updated (once per image version), this one follows
         sourcePyramid->update(image);
         update();
@@ -389,6 +422,7 @@ void ImagePyramid::update(const shared_ptr<VersionedImage>& image) {
     layersValid = false;
 }
 const vector<shared_ptr<ImagePyramidLayer>>& ImagePyramid::getLayers() const {
+    requireExact();
     if (sourcePyramid) {
         if (!layersValid) {
             layers.clear();
@@ -421,6 +455,7 @@ const shared_ptr<ImagePyramidLayer> ImagePyramid::getLayer(int index) const {
     return ls[real];
 }
 vector<std::pair<int, double>> ImagePyramid::getLayerScales() const {
+    requireExact();
     vector<std::pair<int, double>> out;
     if (sourcePyramid) {
         for (const auto& sc : sourcePyramid->getLayerScales())
@@ -435,6 +470,7 @@ vector<std::pair<int, double>> ImagePyramid::getLayerScales() const {
     return out;
 }
 vector<cv::Size> ImagePyramid::getLayerSizes() const {
+    requireExact();
     vector<cv::Size> out;
     if (sourcePyramid) {
         auto scales = sourcePyramid->getLayerScales();
@@ -1142,6 +1178,23 @@ vector<Detection> NonMaximumSuppression::eliminateRedundantDetections(vector<Det
     return res;
 }
 
+}  // namespace detection
+namespace imageprocessing { namespace extraction {
+AggregatedFeaturesExtractor::AggregatedFeaturesExtractor(shared_ptr<ImagePyramid> featurePyramid, cv::Size patchSizeInCells, int cellSizeInPixels,
+                                                         bool adjustMinScaleFactor, int minPatchWidthInPixels)
+    : featurePyramid(featurePyramid), patchSizeInCells(patchSizeInCells), cellSizeInPixels(cellSizeInPixels),
+      minPatchWidthInPixels(minPatchWidthInPixels) {
+    if (!featurePyramid) throw std::invalid_argument("AggregatedFeaturesExtractor: the feature pyramid must not be null");
+    if (!featurePyramid->isApproximated())
+        throw std::logic_error("AggregatedFeaturesExtractor: on this backend the feature pyramid must come from ImagePyramid::createApproximated "
+                               "(exact feature pyramids: AggregatedFeaturesDetector's filter constructors)");
+    if (!adjustMinScaleFactor)
+        throw std::logic_error("AggregatedFeaturesExtractor: a fixed minimum scale factor is not available on this backend (adjustMinScaleFactor)");
+    if (patchSizeInCells.width < 1 || patchSizeInCells.height < 1 || cellSizeInPixels < 1)
+        throw std::invalid_argument("AggregatedFeaturesExtractor: patch and cell sizes must be positive");
+}
+}}  // namespace imageprocessing::extraction
+namespace detection {
 AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessing::ImageFilter> imageFilter, shared_ptr<imageprocessing::ImageFilter> layerFilter,
                                                        int cellSize, cv::Size windowSize, int octaveLayerCount,
                                                        shared_ptr<classification::SvmClassifier> svm, shared_ptr<NonMaximumSuppression> nms,
@@ -1153,6 +1206,30 @@ AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessin
     if (!std::dynamic_pointer_cast<imageprocessing::GrayscaleFilter>(imageFilter) || !fhog)
         throw std::logic_error("AggregatedFeaturesDetector: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter");
     if (fhog->cellSize != cellSize) throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the FhogFilter's");
+    create(*fhog, windowSize, octaveLayerCount, *svm, *nms, widthScale, heightScale, minWindowWidth, nullptr);
+}
+AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessing::extraction::AggregatedFeaturesExtractor> featureExtractor,
+                                                       shared_ptr<classification::SvmClassifier> svm, shared_ptr<NonMaximumSuppression> nms,
+                                                       float widthScale, float heightScale)
+    : scoreThreshold(svm->getThreshold()) {
+    if (!featureExtractor) throw std::invalid_argument("AggregatedFeaturesDetector: the feature extractor must not be null");
+    if (!dynamic_cast<classification::LinearKernel*>(svm->getKernel().get()))
+        throw std::invalid_argument("AggregatedFeaturesDetector: the SVM must use a LinearKernel");
+    auto pyramid = featureExtractor->getFeaturePyramid();
+    auto fhog = std::dynamic_pointer_cast<imageprocessing::filtering::FhogFilter>(pyramid->getApproximatedLayerFilter());
+    if (!pyramid->hasGrayscaleImageFilter() || !fhog)
+        throw std::logic_error("AggregatedFeaturesDetector: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter");
+    if (fhog->cellSize != featureExtractor->getCellSizeInPixels())
+        throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the FhogFilter's");
+    create(*fhog, featureExtractor->getPatchSizeInCells(), (int)pyramid->getOctaveLayerCount(), *svm, *nms, widthScale, heightScale,
+           featureExtractor->getMinPatchWidthInPixels(), &pyramid->getLambdas());
+}
+void AggregatedFeaturesDetector::create(const imageprocessing::filtering::FhogFilter& fhogFilter, cv::Size windowSize, int octaveLayerCount,
+                                        const classification::SvmClassifier& svmRef, const NonMaximumSuppression& nmsRef, float widthScale,
+                                        float heightScale, int minWindowWidth, const vector<double>* lambdas) {
+    const imageprocessing::filtering::FhogFilter* fhog = &fhogFilter;
+    const classification::SvmClassifier* svm = &svmRef;
+    const NonMaximumSuppression* nms = &nmsRef;
     const int D = 3 * fhog->unsignedBinCount + 4;
     if (svm->getSupportVectors().size() != 1) throw std::invalid_argument("AggregatedFeaturesDetector: a linear SVM with one support vector is needed");
     Mat sv = contiguous(svm->getSupportVectors()[0]);
@@ -1167,7 +1244,15 @@ AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessin
     prm.svm_weights = sv.ptr<float>(0);
     prm.svm_bias = svm->getBias(); prm.score_threshold = svm->getThreshold();
     prm.nms_overlap_threshold = nms->getOverlapThreshold(); prm.nms_maximum_type = (int)nms->getMaximumType();
-    check(fd_aggregated_create(context(), &prm, &handle));
+    if (lambdas) check(fd_aggregated_create_approximated(context(), &prm, lambdas->data(), (int)lambdas->size(), &handle));
+    else check(fd_aggregated_create(context(), &prm, &handle));
+}
+vector<double> AggregatedFeaturesDetector::getLambdas() const {
+    vector<double> out(64);
+    int n = 0;
+    check(fd_aggregated_get_lambdas(handle, out.data(), (int)out.size(), &n));
+    out.resize((size_t)n);
+    return out;
 }
 AggregatedFeaturesDetector::~AggregatedFeaturesDetector() { fd_aggregated_destroy(handle); }
 vector<std::pair<cv::Rect, float>> AggregatedFeaturesDetector::detectWithScores(shared_ptr<imageprocessing::VersionedImage> image) {

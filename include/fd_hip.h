@@ -345,6 +345,36 @@ void fd_aggregated_destroy(fd_aggregated* a);
 int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
                          fd_box* out, int cap, int* count, fd_box* candidates, int cand_cap, int* cand_count);
 
+/* The same detector on an approximated feature pyramid: createApproximateDetector (DetectorTrainingApp.cpp:168-191),
+ * ImagePyramid::createApproximated (ImagePyramid.cpp:51-63,200-289).  FHOG runs on one gray layer per octave only (a source
+ * pyramid with one layer per octave and the limits of the octave_layer_count pyramid); the octave_layer_count - 1 layers
+ * between two of them are per-channel bilinear resizes of the octave's feature layer (cv::resize INTER_LINEAR on CV_32F),
+ * multiplied by (float)pow(s, -lambda[channel]) with s = pow(inc, i).  lambdas: one per channel (3 * unsigned_bins + 4),
+ * or n_lambdas == 0: estimated per image from the channel means of two exact layers (ImagePyramid.cpp:237-275; the means are
+ * double sums of the float cells).  fd_aggregated_detect works unchanged on such a handle.  Estimating needs two exact layers:
+ * with fewer, fd_aggregated_detect returns FD_ERR_RUNTIME (given lambdas work on a single octave, like in the reference). */
+int fd_aggregated_create_approximated(fd_ctx* ctx, const fd_aggregated_params* prm, const double* lambdas, int n_lambdas, fd_aggregated** out);
+/* the lambdas the last fd_aggregated_detect used (approximated handles; n = 0 before the first detect on estimating handles) */
+int fd_aggregated_get_lambdas(fd_aggregated* a, double* out, int cap, int* n);
+typedef struct {
+    int32_t index;            /* ImagePyramidLayer::getIndex() */
+    int32_t approximated;     /* 0: FHOG of a gray layer; 1: resized from the exact layer at position `parent` */
+    int32_t parent;           /* position of that exact layer in this list; -1 for exact layers */
+    int32_t rows, cols;       /* size in cells */
+    int32_t reserved;
+    double scale, scale_x, scale_y;
+} fd_aggregated_layer;
+/* feature layers of the last fd_aggregated_detect, in layer order (handles of either kind) */
+int fd_aggregated_get_layers(fd_aggregated* a, fd_aggregated_layer* out, int cap, int* n);
+/* feature layer `layer` (position in that list) of the last fd_aggregated_detect: rows * cols * channels floats (host).  Valid
+ * until the next FHOG or aggregated call on the context (FD_ERR_INVALID_ARGUMENT afterwards). */
+int fd_aggregated_feature_layer(fd_ctx* ctx, fd_aggregated* a, int layer, float* out);
+/* Host only (no context, no device): the layer list fd_aggregated_detect builds on an approximated handle for an image of
+ * width x height.  FD_ERR_RUNTIME when fewer than two exact layers remain (what a handle that estimates its lambdas reports; *n is
+ * set), FD_ERR_CAPACITY when cap is too small (*n is set). */
+int fd_aggregated_plan_layers(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width,
+                              int height, fd_aggregated_layer* out, int cap, int* n);
+
 /* Generic histogram patch filters on the pyramid's bin-image layers (FD_LAYER_GRADBIN: 2 or 4 channels,
  * FD_LAYER_LBP: 1 channel), all built on HistogramFilter::createCellHistograms (HistogramFilter.cpp:23-197,
  * interpolating and non-interpolating):
