@@ -403,9 +403,8 @@ struct fd_pyramid {
     DevBuf input;                    // staging for host images
     DevBuf lut;                      // gradient binning LUT (65536 * 2|4 bytes)
     DevBuf rtab;                     // cv::resize coordinate / weight tables of the first-octave layers (k_resize_down, pyramid.hip)
-    std::vector<uint32_t> rtab_x;           // per entry of `all` (depth-0 layers with a pyrDown successor): offset of its column table in rtab, ~0u = none
-    std::vector<uint32_t> rtile_off;        // per k_resize_down launch (MAXJ chains): its tile list in rtab (offset in int2 entries) ...
-    std::vector<int> rtile_cnt;             // ... and the number of tiles per frame
+    struct Plan;                     // the launches of an update, built with the layout (pyramid.hip)
+    std::unique_ptr<Plan> plan;
     DevBuf layer_table;              // LayerDesc per kept layer
     std::vector<LayerDesc> h_layer_table;
     uint32_t gray_full_off = 0;
@@ -428,7 +427,7 @@ struct fd_pyramid {
     // batch entry points) wait for it; consumers on the same stream are ordered anyway
     hipEvent_t ready = nullptr;
     hipStream_t readyStream = nullptr;
-    ~fd_pyramid() { if (ready) (void)hipEventDestroy(ready); }
+    ~fd_pyramid();                   // pyramid.hip, where Plan is complete (handles are created and destroyed only there)
 };
 
 // entry points that only know single-frame pyramids

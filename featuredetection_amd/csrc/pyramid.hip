@@ -167,88 +167,24 @@ __global__ void k_bgr2gray(const uint8_t* __restrict__ bgr, uint8_t* __restrict_
     }
 }
 
-// cv::resize INTER_LINEAR 8UC1 -> all first-octave layers from the full-resolution gray image.  A thread owns one destination
-// column of a band of RS_ROWS rows: the horizontal coordinates / fixed-point weights are computed once per thread, the vertical
-// ones are workgroup-uniform (scalar); per pixel that leaves four byte loads and a dozen integer operations.
-constexpr int RS_ROWS = 8;
-__global__ __launch_bounds__(256) void k_resize_linear(const uint8_t* __restrict__ arena, uint8_t* __restrict__ out, uint32_t src_off, int sw,
-                                                       int sh, ResizeJobs jobs, size_t imageStride) {
-    const ResizeJob jb = jobs.j[blockIdx.y];
-    const uint8_t* src = arena + (size_t)blockIdx.z * imageStride + src_off;   // blockIdx.z = frame of a multi-frame pyramid
-    uint8_t* dst = out + (size_t)blockIdx.z * imageStride + jb.dst_off;
-    const int colBlocks = (jb.dw + 255) / 256, rowBands = (jb.dh + RS_ROWS - 1) / RS_ROWS;
-    for (int t = blockIdx.x; t < colBlocks * rowBands; t += gridDim.x) {
-        const int band = t / colBlocks, cb = t - band * colBlocks;
-        const int dx = cb * 256 + threadIdx.x;
-        if (dx >= jb.dw) continue;
-        float fx = (float)((dx + 0.5) * jb.scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        const int a0 = __float2int_rn((1.f - fx) * 2048), a1 = __float2int_rn(fx * 2048);
-        const int sx1 = sx + 1 < sw ? sx + 1 : sx;
-        const int dyEnd = min(jb.dh, (band + 1) * RS_ROWS);
-        for (int dy = band * RS_ROWS; dy < dyEnd; ++dy) {
-            float fy = (float)((dy + 0.5) * jb.scale_y - 0.5);
-            int sy = (int)floorf(fy);
-            fy -= sy;
-            const int b0 = __float2int_rn((1.f - fy) * 2048), b1 = __float2int_rn(fy * 2048);
-            const int y0 = sy < 0 ? 0 : (sy >= sh ? sh - 1 : sy);
-            const int y1 = sy + 1 < 0 ? 0 : (sy + 1 >= sh ? sh - 1 : sy + 1);
-            const uint8_t* S0 = src + (size_t)y0 * sw;
-            const uint8_t* S1 = src + (size_t)y1 * sw;
-            const int r0 = S0[sx] * a0 + S0[sx1] * a1;
-            const int r1 = S1[sx] * a0 + S1[sx1] * a1;
-            dst[(size_t)dy * jb.dw + dx] = (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-        }
-    }
-}
-
-// cv::pyrDown 8UC1: separable [1 4 6 4 1], (sum + 128) >> 8, BORDER_REFLECT_101.  A thread computes PD_ROWS vertically adjacent
-// outputs of one column: the 2 * PD_ROWS + 3 horizontal 5-tap sums it needs are formed once each (55 loads for 4 outputs instead
-// of 100).
-constexpr int PD_ROWS = 4;
-__global__ __launch_bounds__(256) void k_pyrdown(uint8_t* __restrict__ arena, DownJobs jobs, size_t imageStride) {
-    const DownJob jb = jobs.j[blockIdx.y];
-    const int dw = (jb.sw + 1) / 2, dh = (jb.sh + 1) / 2;
-    arena += (size_t)blockIdx.z * imageStride;   // blockIdx.z = frame of a multi-frame pyramid
-    const uint8_t* src = arena + jb.src_off;
-    uint8_t* dst = arena + jb.dst_off;
-    const int bands = (dh + PD_ROWS - 1) / PD_ROWS;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dw * bands; i += gridDim.x * blockDim.x) {
-        const int band = i / dw, x = i - band * dw;
-        const int y0 = band * PD_ROWS;
-        int xs[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) xs[k] = reflect101(2 * x - 2 + k, jb.sw);
-        int h[2 * PD_ROWS + 3];
-#pragma unroll
-        for (int r = 0; r < 2 * PD_ROWS + 3; ++r) {
-            const uint8_t* S = src + (size_t)reflect101(2 * y0 - 2 + r, jb.sh) * jb.sw;
-            h[r] = S[xs[2]] * 6 + (S[xs[1]] + S[xs[3]]) * 4 + S[xs[0]] + S[xs[4]];
-        }
-#pragma unroll
-        for (int j = 0; j < PD_ROWS; ++j) {
-            if (y0 + j < dh) {
-                const int v = h[2 * j + 2] * 6 + (h[2 * j + 1] + h[2 * j + 3]) * 4 + h[2 * j] + h[2 * j + 4];
-                dst[(size_t)(y0 + j) * dw + x] = (uint8_t)((v + 128) >> 8);
-            }
-        }
-    }
-}
-
-// ---- LDS-tiled versions of the two kernels above -------------------------------------------------------------------------
-// The direct kernels issue four (resize) / 14 (pyrDown) byte loads per output pixel and are bound by the number of memory
-// instructions.  Here a workgroup stages the source rectangle of a 64 x 32 output tile in LDS with dword loads (unaligned where
-// the row start is) and every tap is an LDS byte read; the arithmetic is the same, value for value.
+// ---- LDS-tiled cv::resize and cv::pyrDown ----------------------------------------------------------------------------------
+// k_resize_tiled: cv::resize INTER_LINEAR 8UC1 -> all first-octave layers from the full-resolution gray image.  Per destination
+// pixel: fx = (dx + 0.5) * scale_x - 0.5 in double, rounded to float; sx = floor(fx), fx -= sx, clamped to the row (fx = 0 there);
+// weights a0 = rn((1 - fx) * 2048), a1 = rn(fx * 2048); the same for the rows (b0, b1; the row indices clamped, the weights not); the
+// pixel is ((b0 * ((S[y0][sx] * a0 + S[y0][sx + 1] * a1) >> 4) >> 16) + (b1 * ((S[y1][sx] * a0 + S[y1][sx + 1] * a1) >> 4) >> 16) + 2) >> 2.
+// k_pyrdown_tiled: cv::pyrDown 8UC1: separable [1 4 6 4 1], (sum + 128) >> 8, BORDER_REFLECT_101; output (x, y) is centred on
+// source (2 x, 2 y).  A thread computes four vertically adjacent outputs of one column: the 11 horizontal 5-tap sums it needs are
+// formed once each.
+// A workgroup stages the source rectangle of an output tile in LDS with dword loads (unaligned where the row start is) and every
+// tap is an LDS byte read: read straight from memory, a resize issues four and a pyrDown 14 byte loads per output pixel and is
+// bound by the number of memory instructions.
 constexpr int TL_W = 64, TL_H = 32, TL_PITCH = 136;   // 64 x 32 output pixels per tile, 8 rows per thread: the per-thread column set-up is the
                                                         // larger part of the work of a row
 constexpr int PD_TH = 16;                               // pyrDown: 64 x 16 tiles (its layers are small: 32-row tiles leave CUs idle)
 constexpr int TL_ROWS = 72;                             // resize: 31 * 2.05 + 3 source rows; pyrDown: 2 * 32 + 3
 
 // resize: valid while a tile's source rectangle fits the stage from its conservative origin, i.e. 1 <= scale_x, scale_y <= 2.05
-// (first-octave layers: 1 <= scale < 2)
+// (first-octave layers: 1 <= scale <= 2, checked where the launch plan is built)
 __global__ __launch_bounds__(256) void k_resize_tiled(const uint8_t* __restrict__ arena, uint8_t* __restrict__ out, uint32_t src_off, int sw,
                                                       int sh, ResizeJobs jobs, size_t imageStride) {
     __shared__ __attribute__((aligned(16))) uint8_t tile[TL_ROWS * TL_PITCH];
@@ -977,79 +913,186 @@ void build_gradient_lut(int bins, bool signedGradients, bool interpolate, std::v
     }
 }
 
-// cv::resize column tables of the first-octave layers that feed a pyrDown chain (k_resize_down): the kernel's own float
-// expressions (k_resize_tiled's srcX), evaluated once per geometry on the host (this file is built with -ffp-contract=off)
-void build_resize_tables(fd_pyramid* p, int W, int H) {
-    p->rtab_x.assign(p->all.size(), ~0u);
+int grid_for(int npix) { return std::max(1, std::min(1024, (npix + 255) / 256)); }
+int tile_grid_for(int ntiles) { return std::max(1, std::min(1024, ntiles)); }
+
+// ---- the launch plan: what an update enqueues behind the gray image ----------------------------------------------------------
+// All of it depends only on what build_layout fixes (frame size, pyramid parameters, layer filter, number of frames), so it is
+// built once with the layout and an update only walks it.  Offsets and sizes only, never a device pointer: a DevBuf may move.
+struct ResizeLaunch {   // k_resize_tiled
+    ResizeJobs jobs;
+    int grid;
+};
+struct FusedLaunch {    // k_resize_down
+    FusedJobs jobs;
+    uint32_t tileTab;   // its tile list in rtab (offset in int2 entries) ...
+    int tilesPerFrame;  // ... and the number of tiles per frame
+    int grid;
+};
+struct DownLaunch {     // k_pyrdown_tiled; the grid follows from the launch's tile count, jobs.tile0[jobs.n]
+    DownJobs jobs;
+};
+struct FilterLaunch {   // k_gradbin / k_lbp, behind k_box_blur where GradientFilter blurs (blur.n == jobs.n then, 0 otherwise)
+    FilterJobs jobs, blur;
+    int grid;
+};
+
+}  // namespace
+
+struct fd_pyramid::Plan {   // in launch order
+    std::vector<ResizeLaunch> resize;   // depth 0: resize from the full-resolution gray image
+    std::vector<FusedLaunch> fused;     // first-octave layers with a pyrDown chain: resize + first pyrDown, the resized pixels stay in LDS
+    std::vector<DownLaunch> down;       // generation 1 of the chains k_resize_down does not cover, then generation 2, 3, ...
+    std::vector<FilterLaunch> filter;   // the layer filter over the kept layers
+};
+fd_pyramid::~fd_pyramid() { if (ready) (void)hipEventDestroy(ready); }
+
+namespace {
+
+// The slot of a stage's next job.  A launch takes MAXJ jobs (they travel by value); a stage's launches begin at `first`, so that a
+// generation of pyrDowns never tops up the last launch of the generation it reads.
+template <class Launch>
+auto& next_job(std::vector<Launch>& launches, size_t first = 0) {
+    if (launches.size() == first || launches.back().jobs.n == MAXJ) launches.emplace_back();   // value-initialised: no jobs yet
+    auto& jobs = launches.back().jobs;
+    return jobs.j[jobs.n++];
+}
+
+void build_plan(fd_pyramid* p, int W, int H) {
+    p->plan.reset(new fd_pyramid::Plan());
+    fd_pyramid::Plan& plan = *p->plan;
+    const std::vector<HostLayer>& all = p->all;
+    const int NI = p->nimg;
     static const int mode = [] { const char* e = getenv("FD_PYR_FUSED"); return e ? atoi(e) : 1; }();   // 0: never, 1: default, 2: kept layers too
-    if (mode == 0) return;
+    std::vector<char> fused(all.size(), 0);   // the depth-0 layers that k_resize_down resizes, together with their pyrDown
+    // rtab: the cv::resize column tables of the fused layers -- the kernel's own float expressions (k_resize_tiled's srcX), evaluated
+    // once per geometry on the host (this file is built with -ffp-contract=off) --, behind them one tile list per k_resize_down launch
     std::vector<int2> tab;
-    // tiles of k_resize_down, one list per launch (MAXJ chains): {X0, ncol, tx | ty << 16, chain of the launch}
-    std::vector<std::vector<int4>> tiles;
-    p->rtile_off.clear();
-    p->rtile_cnt.clear();
-    int nfused = 0;
-    for (size_t k = 0; k + 1 < p->all.size(); ++k) {
-        const HostLayer& L = p->all[k];
-        const HostLayer& D = p->all[k + 1];
-        if (L.depth != 0 || D.depth != 1 || D.chain != L.chain) continue;
-        // the scale-1 layer IS the gray image: its pyrDown stays with k_pyrdown_tiled (through this kernel with identity tables it
-        // costs +35 us per 64-frame call against 15 us saved: the resize arithmetic is not free)
+    std::vector<std::vector<int4>> tiles;     // {X0, ncol, tx | ty << 16, chain of the launch}
+    for (size_t k = 0; k < all.size(); ++k) {
+        const HostLayer& L = all[k];
+        if (L.depth != 0) continue;
+        // the scale-1 layer IS the gray image (build_layout): nothing to resize, and its pyrDown stays with k_pyrdown_tiled (through
+        // k_resize_down with identity tables it costs +35 us per 64-frame call against 15 us saved: the resize arithmetic is not free)
         if (L.w == W && L.h == H && L.gray_off == p->gray_full_off) continue;
-        if (L.w < 3 || L.h < 3 || W > 65535 || H > 65535) continue;
+        const double scale_x = 1. / ((double)L.w / W), scale_y = 1. / ((double)L.h / H);
+        // k_resize_tiled stages at most TL_ROWS x TL_PITCH source bytes per 64 x 32 tile: 1 <= scale <= 2.05.  build_layout only makes
+        // depth-0 layers of w = cvRound(W * s) with s = inc^i, i < octl, inc = 0.5^(1 / octl), so 0.5 < s <= 1.  s <= 1 gives W / w >= 1.
+        // Odd W = 2 k + 1: W * s > k + 0.5, so w >= k + 1 and W / w < 2; even W = 2 k: W * s > k, so w >= k and W / w <= 2 (reached at
+        // W = 2).  The same holds for H.
+        if (!(scale_x >= 1.0 && scale_x <= 2.05 && scale_y >= 1.0 && scale_y <= 2.05))
+            FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: first-octave layer %d x %d of a %d x %d image is outside the resize kernel's range", L.w, L.h, W, H);
         // A first-octave layer that is itself a kept layer (config 2's pyramid: scales up to 1) has to be written anyway: the fusion saves
         // nothing there and the fused kernel is the slower resize (round 3: 699 us per 640x480 frame; k_resize_tiled + k_pyrdown_tiled:
         // 101 + 4 x 68 us, round 4).  FD_PYR_FUSED=2 fuses those too (A/B).  Also measured in round 4 and dropped: persistent
         // k_pyrdown_tiled workgroups with the next tile's loads in flight (69 vs 63 us per 64-frame headline call).
-        if (L.kept && mode != 2) continue;
-        const double scale_x = 1. / ((double)L.w / W);
-        std::vector<int2> xt((size_t)L.w);
-        for (int dx = 0; dx < L.w; ++dx) {
-            float fx = (float)((dx + 0.5) * scale_x - 0.5);
-            int sx = (int)floorf(fx);
-            fx -= sx;
-            if (sx < 0) { fx = 0; sx = 0; }
-            if (sx >= W - 1) { fx = 0; sx = W - 1; }
-            const int a0 = (int)nearbyintf((1.f - fx) * 2048), a1 = (int)nearbyintf(fx * 2048);
-            xt[(size_t)dx] = make_int2(sx, a0 | (a1 << 16));
+        const bool chain = k + 1 < all.size() && all[k + 1].depth == 1 && all[k + 1].chain == L.chain;
+        if (chain && mode != 0 && (!L.kept || mode == 2) && L.w >= 3 && L.h >= 3 && W <= 65535 && H <= 65535) {
+            const HostLayer& D = all[k + 1];
+            std::vector<int2> xt((size_t)L.w);
+            for (int dx = 0; dx < L.w; ++dx) {
+                float fx = (float)((dx + 0.5) * scale_x - 0.5);
+                int sx = (int)floorf(fx);
+                fx -= sx;
+                if (sx < 0) { fx = 0; sx = 0; }
+                if (sx >= W - 1) { fx = 0; sx = W - 1; }
+                const int a0 = (int)nearbyintf((1.f - fx) * 2048), a1 = (int)nearbyintf(fx * 2048);
+                xt[(size_t)dx] = make_int2(sx, a0 | (a1 << 16));
+            }
+            // every tile's source columns must fit the kernel's stage (its rows are staged per resized row: no limit there)
+            bool fits = true;
+            for (int x1 = 0; x1 < D.w && fits; x1 += FT_W1) {
+                const int cLo = std::max(0, 2 * x1 - 2), cHi = std::min(L.w - 1, 2 * x1 - 2 + G0_W - 1);
+                fits = std::min(W - 1, xt[(size_t)cHi].x + 1) - xt[(size_t)cLo].x + 1 <= FS_PITCH;
+            }
+            if (fits) {
+                FusedJob& j = next_job(plan.fused);
+                j.dw0 = L.w; j.dh0 = L.h; j.dw1 = D.w; j.dh1 = D.h;
+                j.dst0_off = L.kept ? L.gray_off : 0xffffffffu;
+                j.dst1_off = D.gray_off;
+                j.xtab = (uint32_t)tab.size();
+                j.scale_y = scale_y;
+                tab.insert(tab.end(), xt.begin(), xt.end());
+                // the source columns of every tile, exactly as the kernel's addressing expects them
+                tiles.resize(plan.fused.size());
+                for (int ty = 0; ty * FT_H1 < D.h; ++ty)
+                    for (int tx = 0; tx * FT_W1 < D.w; ++tx) {
+                        const int gx0 = 2 * tx * FT_W1 - 2;
+                        const int cLo = std::max(0, gx0), cHi = std::min(L.w - 1, gx0 + G0_W - 1);
+                        const int X0 = xt[(size_t)cLo].x, ncol = std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1;
+                        tiles.back().push_back(make_int4(X0, ncol, (int)((uint32_t)tx | (uint32_t)ty << 16), plan.fused.back().jobs.n - 1));
+                    }
+                fused[k] = 1;
+                continue;
+            }
         }
-        // every tile's source columns must fit the kernel's stage (its rows are staged per resized row: no limit there)
-        bool fits = true;
-        for (int x1 = 0; x1 < D.w && fits; x1 += FT_W1) {
-            const int cLo = std::max(0, 2 * x1 - 2), cHi = std::min(L.w - 1, 2 * x1 - 2 + G0_W - 1);
-            fits = std::min(W - 1, xt[(size_t)cHi].x + 1) - xt[(size_t)cLo].x + 1 <= FS_PITCH;
-        }
-        if (!fits) continue;
-        {   // the source columns of every tile, exactly as the kernel's addressing expects them
-            if (nfused % MAXJ == 0) tiles.emplace_back();
-            std::vector<int4>& tl = tiles.back();
-            for (int ty = 0; ty * FT_H1 < D.h; ++ty)
-                for (int tx = 0; tx * FT_W1 < D.w; ++tx) {
-                    const int gx0 = 2 * tx * FT_W1 - 2;
-                    const int cLo = std::max(0, gx0), cHi = std::min(L.w - 1, gx0 + G0_W - 1);
-                    const int X0 = xt[(size_t)cLo].x, ncol = std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1;
-                    tl.push_back(make_int4(X0, ncol, (int)((uint32_t)tx | (uint32_t)ty << 16), nfused % MAXJ));
-                }
-            ++nfused;
-        }
-        p->rtab_x[k] = (uint32_t)tab.size();
-        tab.insert(tab.end(), xt.begin(), xt.end());
+        ResizeJob& j = next_job(plan.resize);
+        j.dw = L.w; j.dh = L.h; j.dst_off = L.gray_off;
+        j.scale_x = scale_x;
+        j.scale_y = scale_y;
+        ResizeLaunch& R = plan.resize.back();
+        R.grid = std::max(R.grid, tile_grid_for(((L.w + TL_W - 1) / TL_W) * ((L.h + TL_H - 1) / TL_H)));
     }
-    if (tab.empty()) return;
-    for (const std::vector<int4>& tl : tiles) {   // 16-byte entries behind the 8-byte ones, 16-byte aligned
-        if (tab.size() & 1) tab.push_back(make_int2(0, 0));
-        p->rtile_off.push_back((uint32_t)tab.size());
-        p->rtile_cnt.push_back((int)tl.size());
-        for (const int4& t : tl) { tab.push_back(make_int2(t.x, t.y)); tab.push_back(make_int2(t.z, t.w)); }
+    if (!plan.fused.empty()) {
+        int perCu = 0;   // workgroups of k_resize_down a CU holds
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_resize_down, 256, 0) != hipSuccess || perCu < 1) perCu = 4;
+        for (size_t g = 0; g < plan.fused.size(); ++g) {   // 16-byte entries behind the 8-byte ones, 16-byte aligned
+            FusedLaunch& F = plan.fused[g];
+            if (tab.size() & 1) tab.push_back(make_int2(0, 0));
+            F.tileTab = (uint32_t)tab.size();
+            F.tilesPerFrame = (int)tiles[g].size();
+            for (const int4& t : tiles[g]) { tab.push_back(make_int2(t.x, t.y)); tab.push_back(make_int2(t.z, t.w)); }
+            // persistent workgroups; a multiple of the 8 XCDs for a multi-frame pyramid (every frame is then resized on one XCD)
+            F.grid = (int)std::min<int64_t>((int64_t)F.tilesPerFrame * NI, (int64_t)p->ctx->num_cus * perCu);
+            if (NI >= 8 && F.grid >= 64) F.grid &= ~7;
+        }
+        p->rtab.reserve(sizeof(int2) * tab.size());
+        HIP_CHECK(hipMemcpy(p->rtab.p, tab.data(), sizeof(int2) * tab.size(), hipMemcpyHostToDevice));
     }
-    p->rtab.reserve(sizeof(int2) * tab.size());
-    HIP_CHECK(hipMemcpy(p->rtab.p, tab.data(), sizeof(int2) * tab.size(), hipMemcpyHostToDevice));
+    // (Measured and dropped, twice.  Round 3: one workgroup walking all deeper generations of a chain tile by tile -- 160 us per 64-frame
+    // call against 57 us for the per-generation launches, 32 serial tiles per workgroup.  Round 5: k_pyrdown_chain, a workgroup owning a
+    // 16 x 16 tile of the deepest generation and computing the 35 / 73 / 149-pixel boxes above it in LDS (halo recomputed, reflected
+    // borders materialised; bit-exact on every pyramid test) -- ONE launch of 121 us instead of three of 11.4 us, headline 3270 -> 2690
+    // Mpatches/s: 1.8x the outputs (halo) at ~60 instructions each, against ~12 per output of the column walk of k_pyrdown_tiled, which
+    // shares the row dot products between vertically adjacent outputs.  The per-generation launches are latency-bound but cheap.)
+    int maxDepth = 0;
+    for (const HostLayer& L : all) maxDepth = std::max(maxDepth, L.depth);
+    for (int d = 1; d <= maxDepth; ++d) {
+        const size_t first = plan.down.size();
+        for (size_t k = 1; k < all.size(); ++k) {
+            const HostLayer& L = all[k];
+            if (L.depth != d || fused[k - 1]) continue;
+            const HostLayer& S = all[k - 1];   // previous entry of the same chain
+            DownJob& j = next_job(plan.down, first);
+            j.sw = S.w; j.sh = S.h; j.src_off = S.gray_off; j.dst_off = L.gray_off;
+            DownJobs& jobs = plan.down.back().jobs;
+            jobs.tile0[jobs.n] = jobs.tile0[jobs.n - 1] + ((L.w + PD_W - 1) / PD_W) * ((L.h + PD_TH - 1) / PD_TH);
+        }
+    }
+    if (p->filter_kind != FD_LAYER_NONE) {
+        const bool blur = p->filter_kind == FD_LAYER_GRADBIN && p->grad_blur > 0;
+        for (int k : p->kept) {
+            const HostLayer& L = all[k];
+            FilterJob& j = next_job(plan.filter);
+            j.w = L.w; j.h = L.h; j.src_off = blur ? L.blur_off : L.gray_off; j.dst_off = L.filt_off;
+            FilterLaunch& F = plan.filter.back();
+            if (blur) {   // GradientFilter's blur: gray layer -> blurred copy; the gradients are then taken of the copy
+                FilterJob& b = F.blur.j[F.blur.n++];
+                b.w = L.w; b.h = L.h; b.src_off = L.gray_off; b.dst_off = L.blur_off;
+            }
+            F.grid = std::max(F.grid, grid_for(L.w * L.h));
+        }
+    }
+}
+
+// the settings a layout depends on have changed: the next update builds a new one, and with it a new launch plan
+void invalidate_layout(fd_pyramid* p) {
+    p->all.clear();
+    p->img_w = p->img_h = 0;
 }
 
 void build_layout(fd_pyramid* p, int W, int H) {
-    p->img_w = W;
-    p->img_h = H;
-    p->all.clear();
+    invalidate_layout(p);   // until the layout and its plan are complete: a throw below leaves nothing half-built to be used
     p->kept.clear();
     size_t off = 0;
     p->gray_full_off = 0;
@@ -1107,11 +1150,10 @@ void build_layout(fd_pyramid* p, int W, int H) {
     if (!p->h_layer_table.empty())
         HIP_CHECK(hipMemcpyAsync(p->layer_table.p, p->h_layer_table.data(), sizeof(LayerDesc) * p->h_layer_table.size(),
                                  hipMemcpyHostToDevice, p->ctx->stream));
-    build_resize_tables(p, W, H);
+    build_plan(p, W, H);
+    p->img_w = W;
+    p->img_h = H;
 }
-
-int grid_for(int npix) { return std::max(1, std::min(1024, (npix + 255) / 256)); }
-int tile_grid_for(int ntiles) { return std::max(1, std::min(1024, ntiles)); }
 
 // (Measured and dropped in round 5: single-image updates replayed as a hipGraph -- captured with hipStreamBeginCapture around the launch
 // code below on the second update with the same layout, the image address patched into the k_bgr2gray node with
@@ -1130,161 +1172,22 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
     if (greyworld && (size_t)W * H > 0x7fffffffull) FD_THROW(FD_ERR_INVALID_ARGUMENT, "GreyWorldNormalizationFilter: image too large");
     if (W != p->img_w || H != p->img_h || p->all.empty()) build_layout(p, W, H);
     uint8_t* arena = p->arena.as<uint8_t>();
-    const size_t npix = (size_t)W * H;
-    const int NI = frames ? p->nimg : 1;
+    uint8_t* gray = arena + p->gray_full_off;
+    const size_t npix = (size_t)W * H, bytes = npix * ch;
+    const int NI = p->nimg;   // a single image is one frame: without `frames` the pyramid holds one (checked above)
     const size_t IS = p->image_stride;
-    // everything behind the gray image: the resizes, the pyrDown chains, the layer filters
-    auto enqueue_rest = [&]() {
-    // depth 0: resize from the full-resolution gray image
-    int maxDepth = 0;
-    for (const HostLayer& L : p->all) maxDepth = std::max(maxDepth, L.depth);
-    {
-        ResizeJobs jobs;
-        jobs.n = 0;
-        int maxpix = 0, maxtiles = 0;
-        auto flush = [&]() {
-            if (!jobs.n) return;
-            bool fits = true;   // the tiled kernel stages at most TL_ROWS x TL_PITCH source bytes per 64 x 32 tile
-            for (int q = 0; q < jobs.n; ++q)
-                fits = fits && jobs.j[q].scale_x >= 1.0 && jobs.j[q].scale_x <= 2.05 && jobs.j[q].scale_y >= 1.0 && jobs.j[q].scale_y <= 2.05;
-            if (fits)
-                hipLaunchKernelGGL(k_resize_tiled, dim3(tile_grid_for(maxtiles), jobs.n, NI), dim3(256), 0, st, arena, arena, p->gray_full_off, W, H, jobs, IS);
-            else
-                hipLaunchKernelGGL(k_resize_linear, dim3(grid_for(maxpix), jobs.n, NI), dim3(256), 0, st, arena, arena, p->gray_full_off, W, H, jobs, IS);
-            jobs.n = 0;
-            maxpix = 0;
-            maxtiles = 0;
-        };
-        for (size_t k = 0; k < p->all.size(); ++k) {
-            const HostLayer& L = p->all[k];
-            if (L.depth != 0) continue;
-            if (L.w == W && L.h == H && L.gray_off == p->gray_full_off) continue;   // the gray image itself (build_layout)
-            if (p->rtab_x[k] != ~0u) continue;   // resized and pyrDown'ed by k_resize_down below
-            ResizeJob& j = jobs.j[jobs.n++];
-            j.dw = L.w; j.dh = L.h; j.dst_off = L.gray_off;
-            j.scale_x = 1. / ((double)L.w / W);
-            j.scale_y = 1. / ((double)L.h / H);
-            maxpix = std::max(maxpix, L.w * L.h);
-            maxtiles = std::max(maxtiles, ((L.w + TL_W - 1) / TL_W) * ((L.h + TL_H - 1) / TL_H));
-            if (jobs.n == MAXJ) flush();
+    // the caller's image(s) as device addresses: host images pass through the staging buffer
+    FramePtrs fp{};
+    if (!is_device) p->input.reserve(bytes * NI);
+    for (int f = 0; f < NI; ++f) {
+        fp.p[f] = frames ? frames[f] : image;
+        if (!is_device) {
+            uint8_t* staged = p->input.as<uint8_t>() + (size_t)f * bytes;
+            HIP_CHECK(hipMemcpyAsync(staged, fp.p[f], bytes, hipMemcpyHostToDevice, st));
+            fp.p[f] = staged;
         }
-        flush();
     }
-    {   // first-octave layers with a pyrDown chain: resize + first pyrDown in one kernel, the resized pixels stay in LDS
-        FusedJobs jobs;
-        jobs.n = 0;
-        size_t group = 0;
-        auto flush = [&]() {
-            if (!jobs.n) return;
-            static int perCu = 0;
-            if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_resize_down, 256, 0) != hipSuccess || perCu < 1)) perCu = 4;
-            const int tilesPerFrame = p->rtile_cnt[group];
-            // persistent workgroups; a multiple of the 8 XCDs for a multi-frame pyramid (every frame is then resized on one XCD)
-            int grid = (int)std::min<int64_t>((int64_t)tilesPerFrame * NI, (int64_t)p->ctx->num_cus * perCu);
-            if (NI >= 8 && grid >= 64) grid &= ~7;
-            hipLaunchKernelGGL(k_resize_down, dim3(grid), dim3(256), 0, st, arena, p->gray_full_off, W, H, p->rtab.as<int2>(), jobs, p->rtile_off[group], tilesPerFrame, NI, IS);
-            jobs.n = 0;
-            ++group;
-        };
-        for (size_t k = 0; k + 1 < p->all.size(); ++k) {
-            if (p->rtab_x[k] == ~0u) continue;
-            const HostLayer& L = p->all[k];
-            const HostLayer& D = p->all[k + 1];
-            FusedJob& j = jobs.j[jobs.n++];
-            j.dw0 = L.w; j.dh0 = L.h; j.dw1 = D.w; j.dh1 = D.h;
-            j.dst0_off = (L.kept && L.gray_off != p->gray_full_off) ? L.gray_off : 0xffffffffu;   // the scale-1 layer IS the gray image
-            j.dst1_off = D.gray_off;
-            j.xtab = p->rtab_x[k];
-            j.scale_y = 1. / ((double)L.h / H);
-            if (jobs.n == MAXJ) flush();
-        }
-        flush();
-    }
-    {   // generation 1 of the chains k_resize_down does not cover (the scale-1 chain: pyrDown of the gray image itself)
-        DownJobs dj;
-        dj.n = 0;
-        dj.tile0[0] = 0;
-        auto flush1 = [&]() {
-            if (!dj.n) return;
-            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(dj.tile0[dj.n]), 1, NI), dim3(256), 0, st, arena, dj, IS);
-            dj.n = 0;
-        };
-        for (size_t k = 1; k < p->all.size(); ++k) {
-            const HostLayer& L = p->all[k];
-            if (L.depth != 1 || p->rtab_x[k - 1] != ~0u) continue;
-            const HostLayer& S = p->all[k - 1];
-            DownJob& j = dj.j[dj.n++];
-            j.sw = S.w; j.sh = S.h; j.src_off = S.gray_off; j.dst_off = L.gray_off;
-            dj.tile0[dj.n] = dj.tile0[dj.n - 1] + ((L.w + PD_W - 1) / PD_W) * ((L.h + PD_TH - 1) / PD_TH);
-            if (dj.n == MAXJ) flush1();
-        }
-        flush1();
-    }
-    // (Measured and dropped, twice.  Round 3: one workgroup walking all deeper generations of a chain tile by tile -- 160 us per 64-frame
-    // call against 57 us for the per-generation launches, 32 serial tiles per workgroup.  Round 5: k_pyrdown_chain, a workgroup owning a
-    // 16 x 16 tile of the deepest generation and computing the 35 / 73 / 149-pixel boxes above it in LDS (halo recomputed, reflected
-    // borders materialised; bit-exact on every pyramid test) -- ONE launch of 121 us instead of three of 11.4 us, headline 3270 -> 2690
-    // Mpatches/s: 1.8x the outputs (halo) at ~60 instructions each, against ~12 per output of the column walk below, which shares
-    // the row dot products between vertically adjacent outputs.  The per-generation launches are latency-bound but cheap.)
-    for (int d = 2; d <= maxDepth; ++d) {
-        DownJobs jobs;
-        jobs.n = 0;
-        jobs.tile0[0] = 0;
-        auto flush = [&]() {
-            if (!jobs.n) return;
-            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(jobs.tile0[jobs.n]), 1, NI), dim3(256), 0, st, arena, jobs, IS);
-            jobs.n = 0;
-        };
-        for (size_t k = 0; k < p->all.size(); ++k) {
-            const HostLayer& L = p->all[k];
-            if (L.depth != d) continue;
-            const HostLayer& S = p->all[k - 1];  // previous entry of the same chain
-            DownJob& j = jobs.j[jobs.n++];
-            j.sw = S.w; j.sh = S.h; j.src_off = S.gray_off; j.dst_off = L.gray_off;
-            jobs.tile0[jobs.n] = jobs.tile0[jobs.n - 1] + ((L.w + PD_W - 1) / PD_W) * ((L.h + PD_TH - 1) / PD_TH);
-            if (jobs.n == MAXJ) flush();
-        }
-        flush();
-    }
-    if (p->filter_kind != FD_LAYER_NONE) {
-        FilterJobs jobs, bjobs;
-        jobs.n = 0;
-        bjobs.n = 0;
-        int maxpix = 0;
-        const bool blur = p->filter_kind == FD_LAYER_GRADBIN && p->grad_blur > 0;
-        auto flush = [&]() {
-            if (!jobs.n) return;
-            dim3 g(grid_for(maxpix), jobs.n);
-            // GradientFilter's blur: gray layer -> blurred copy; the gradients are then taken of the copy
-            if (blur) hipLaunchKernelGGL(k_box_blur, g, dim3(256), 0, st, arena, p->grad_blur, bjobs);
-            bjobs.n = 0;
-            if (p->filter_kind == FD_LAYER_GRADBIN) {
-                if (p->interpolate)
-                    hipLaunchKernelGGL(k_gradbin<4>, g, dim3(256), 0, st, arena, p->lut.as<uint8_t>(), p->grad_kernel, jobs);
-                else
-                    hipLaunchKernelGGL(k_gradbin<2>, g, dim3(256), 0, st, arena, p->lut.as<uint8_t>(), p->grad_kernel, jobs);
-            } else {
-                hipLaunchKernelGGL(k_lbp, g, dim3(256), 0, st, arena, p->lbp_type, jobs);
-            }
-            jobs.n = 0;
-            maxpix = 0;
-        };
-        for (int k : p->kept) {
-            const HostLayer& L = p->all[k];
-            FilterJob& j = jobs.j[jobs.n++];
-            j.w = L.w; j.h = L.h; j.src_off = blur ? L.blur_off : L.gray_off; j.dst_off = L.filt_off;
-            if (blur) {
-                FilterJob& b = bjobs.j[bjobs.n++];
-                b.w = L.w; b.h = L.h; b.src_off = L.gray_off; b.dst_off = L.blur_off;
-            }
-            maxpix = std::max(maxpix, L.w * L.h);
-            if (jobs.n == MAXJ) flush();
-        }
-        flush();
-    }
-    };   // enqueue_rest
-    // FD_IMAGE_GREYWORLD_GRAY: the statistics of every frame, then normalisation + gray conversion in one pass
-    auto enqueue_greyworld_gray = [&](const FramePtrs& fp) {
+    if (greyworld) {   // FD_IMAGE_GREYWORLD_GRAY: the statistics of every frame, then normalisation + gray conversion in one pass
         GwStats* stats = p->gw_stats.as<GwStats>();
         HIP_CHECK(hipMemsetAsync(stats, 0, sizeof(GwStats) * (size_t)NI, st));
         // persistent workgroups, one pass of 1024 quads each where the frame is small.  At most one workgroup per CU and frame (a
@@ -1294,40 +1197,32 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
         const int perFrame = std::max(1, std::min(cus, 4 * cus / NI));
         const int gx = std::max(1, std::min((int)((npix / 4 + 1023) / 1024), perFrame));
         hipLaunchKernelGGL(k_gw_stats, dim3(gx, NI), dim3(256), 0, st, fp, stats, (int)npix);
-        hipLaunchKernelGGL(k_gw_gray, dim3(gx, NI), dim3(256), 0, st, fp, stats, arena + p->gray_full_off, IS, (int)npix);
-    };
-    if (frames) {   // one launch converts / copies all frames into their arenas
-        FramePtrs fp;
-        if (!is_device) {
-            p->input.reserve(npix * ch * (size_t)NI);
-            for (int f = 0; f < NI; ++f) {
-                HIP_CHECK(hipMemcpyAsync(p->input.as<uint8_t>() + (size_t)f * npix * ch, frames[f], npix * ch, hipMemcpyHostToDevice, st));
-                fp.p[f] = p->input.as<uint8_t>() + (size_t)f * npix * ch;
-            }
-        } else {
-            for (int f = 0; f < NI; ++f) fp.p[f] = frames[f];
-        }
-        if (greyworld) enqueue_greyworld_gray(fp);
-        else
-            hipLaunchKernelGGL(k_frames_to_gray, dim3(grid_for((int)(npix / 16 + 1)), NI), dim3(256), 0, st, fp, arena + p->gray_full_off, IS, (int)npix, ch);   // four quads per thread
+        hipLaunchKernelGGL(k_gw_gray, dim3(gx, NI), dim3(256), 0, st, fp, stats, gray, IS, (int)npix);
+    } else if (frames) {   // one launch converts / copies all frames into their arenas, four quads per thread
+        hipLaunchKernelGGL(k_frames_to_gray, dim3(grid_for((int)(npix / 16 + 1)), NI), dim3(256), 0, st, fp, gray, IS, (int)npix, ch);
+    } else if (ch == 3) {
+        hipLaunchKernelGGL(k_bgr2gray, dim3(grid_for((int)npix)), dim3(256), 0, st, fp.p[0], gray, (int)npix);
     } else {
-        const uint8_t* dimg = image;
-        if (!is_device) {
-            p->input.reserve(npix * ch);
-            HIP_CHECK(hipMemcpyAsync(p->input.p, image, npix * ch, hipMemcpyHostToDevice, st));
-            dimg = p->input.as<uint8_t>();
-        }
-        if (greyworld) {   // the same two kernels with one frame
-            FramePtrs fp{};
-            fp.p[0] = dimg;
-            enqueue_greyworld_gray(fp);
-        } else if (ch == 3) {
-            hipLaunchKernelGGL(k_bgr2gray, dim3(grid_for((int)npix)), dim3(256), 0, st, dimg, arena + p->gray_full_off, (int)npix);
-        } else {
-            HIP_CHECK(hipMemcpyAsync(arena + p->gray_full_off, dimg, npix, hipMemcpyDeviceToDevice, st));
-        }
+        HIP_CHECK(hipMemcpyAsync(gray, fp.p[0], npix, hipMemcpyDeviceToDevice, st));
     }
-    enqueue_rest();
+    // everything behind the gray image: the resizes, the pyrDown chains, the layer filters
+    const fd_pyramid::Plan& plan = *p->plan;
+    for (const ResizeLaunch& R : plan.resize)
+        hipLaunchKernelGGL(k_resize_tiled, dim3(R.grid, R.jobs.n, NI), dim3(256), 0, st, arena, arena, p->gray_full_off, W, H, R.jobs, IS);
+    for (const FusedLaunch& F : plan.fused)
+        hipLaunchKernelGGL(k_resize_down, dim3(F.grid), dim3(256), 0, st, arena, p->gray_full_off, W, H, p->rtab.as<int2>(), F.jobs, F.tileTab, F.tilesPerFrame, NI, IS);
+    for (const DownLaunch& D : plan.down)
+        hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(D.jobs.tile0[D.jobs.n]), 1, NI), dim3(256), 0, st, arena, D.jobs, IS);
+    for (const FilterLaunch& F : plan.filter) {
+        const dim3 g(F.grid, F.jobs.n);
+        if (F.blur.n) hipLaunchKernelGGL(k_box_blur, g, dim3(256), 0, st, arena, p->grad_blur, F.blur);
+        if (p->filter_kind != FD_LAYER_GRADBIN)
+            hipLaunchKernelGGL(k_lbp, g, dim3(256), 0, st, arena, p->lbp_type, F.jobs);
+        else if (p->interpolate)
+            hipLaunchKernelGGL(k_gradbin<4>, g, dim3(256), 0, st, arena, p->lut.as<uint8_t>(), p->grad_kernel, F.jobs);
+        else
+            hipLaunchKernelGGL(k_gradbin<2>, g, dim3(256), 0, st, arena, p->lut.as<uint8_t>(), p->grad_kernel, F.jobs);
+    }
     HIP_CHECK(hipGetLastError());
     if (!p->ready) HIP_CHECK(hipEventCreateWithFlags(&p->ready, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(p->ready, st));
@@ -1455,8 +1350,7 @@ int fd_pyramid_set_layer_filter(fd_pyramid* p, int kind, int bins, int signed_gr
         p->interpolate = interpolate;
         p->grad_kernel = grad_kernel;
         p->lbp_type = lbp_type;
-        p->all.clear();  // force a new layout
-        p->img_w = p->img_h = 0;
+        invalidate_layout(p);
     });
 }
 
@@ -1488,7 +1382,7 @@ int fd_pyramid_set_frames(fd_pyramid* p, int frames) {
         if (!p) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_set_frames: NULL pyramid");
         if (frames < 1 || frames > FD_MAX_FRAMES) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_set_frames: 1..%d frames", FD_MAX_FRAMES);
         if (frames > 1 && p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "multi-frame pyramids have no layer filters");
-        if (frames != p->nimg) { p->nimg = frames; p->all.clear(); p->img_w = p->img_h = 0; }   // new layout at the next update
+        if (frames != p->nimg) { p->nimg = frames; invalidate_layout(p); }
     });
 }
 
@@ -1521,8 +1415,7 @@ int fd_pyramid_set_gradient_blur(fd_pyramid* p, int blur_kernel) {
         if (blur_kernel < 0 || blur_kernel > 31) FD_THROW(FD_ERR_INVALID_ARGUMENT, "GradientFilter: the blur kernel size must be in 0..31");
         if (blur_kernel != p->grad_blur) {
             p->grad_blur = blur_kernel;
-            p->all.clear();  // force a new layout
-            p->img_w = p->img_h = 0;
+            invalidate_layout(p);
         }
     });
 }
