@@ -83,6 +83,11 @@ class fd_fhog_params(C.Structure):
                 ("alpha", C.c_float)]
 
 
+class fd_fpdw_params(C.Structure):
+    _fields_ = [("cell_size", C.c_int32), ("fast_gradient", C.c_int32), ("interpolate", C.c_int32), ("normalization_radius", C.c_int32),
+                ("normalization_constant", C.c_float)]
+
+
 class fd_aggregated_params(C.Structure):
     _fields_ = [("fhog", fd_fhog_params), ("window_w", C.c_int32), ("window_h", C.c_int32), ("octave_layer_count", C.c_int32),
                 ("min_window_width", C.c_int32), ("width_scale", C.c_float), ("height_scale", C.c_float), ("svm_weights", C.c_void_p),
@@ -199,6 +204,12 @@ _SIGS = {
     "fd_aggregated_get_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "fd_aggregated_feature_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fd_aggregated_plan_layers": (C.c_int, [C.c_int] * 7 + [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_fpdw_size": (C.c_int, [C.POINTER(fd_fpdw_params), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_fpdw_gradient_lut": (C.c_int, [C.POINTER(fd_fpdw_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_fpdw_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_fpdw_params), C.c_void_p]),
+    "fd_fpdw_cells_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_fpdw_params), C.c_void_p]),
+    "fd_aggregated_create_fpdw": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(fd_fpdw_params), C.c_int, C.c_void_p, C.c_int,
+                                            C.POINTER(C.c_void_p)]),
     "fd_nms_iou": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "fd_wvm_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_five_stage_batch_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -861,23 +872,85 @@ def aggregated_plan_layers(window_w, window_h, cell_size, octave_layers, min_win
     return out[:n.value].copy()
 
 
+def _fpdw_params(cell_size, fast_gradient, interpolate_bins, normalization_radius, normalization_constant):
+    radius = cell_size if normalization_radius is None else normalization_radius   # DetectorTrainingApp passes the cell size
+    return fd_fpdw_params(cell_size, int(fast_gradient), int(interpolate_bins), radius, normalization_constant)
+
+
+def fpdw_size(width, height, cell_size=8, **kw):
+    """fd_fpdw_size (host only): (rows, cols, channels) of the FPDW cells of a width x height image"""
+    fp = _fpdw_params(cell_size, kw.get("fast_gradient", True), kw.get("interpolate_bins", False), kw.get("normalization_radius"),
+                      kw.get("normalization_constant", 0.01))
+    r, c, d = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fd_fpdw_size(C.byref(fp), width, height, C.byref(r), C.byref(c), C.byref(d))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_fpdw_size: invalid parameters")
+    return r.value, c.value, d.value
+
+
+def fpdw_gradient_lut(interpolate_bins=False):
+    """fd_fpdw_gradient_lut (host only): dict of the 65536-entry arrays bin1, bin2 (int32), w1, w2, magnitude (float32), index
+    gx | gy << 8"""
+    fp = _fpdw_params(8, True, interpolate_bins, None, 0.01)
+    out = dict(bin1=np.zeros(65536, np.int32), bin2=np.zeros(65536, np.int32), w1=np.zeros(65536, np.float32),
+               w2=np.zeros(65536, np.float32), magnitude=np.zeros(65536, np.float32))
+    rc = lib().fd_fpdw_gradient_lut(C.byref(fp), _ptr(out["bin1"]), _ptr(out["bin2"]), _ptr(out["w1"]), _ptr(out["w2"]), _ptr(out["magnitude"]))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_fpdw_gradient_lut failed")
+    return out
+
+
+def _fpdw_call(ctx, fn, bgr, out_shape, fp):
+    bgr = _c(bgr, np.uint8)
+    if bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError("FPDW features need a BGR image (h, w, 3)")
+    h, w = bgr.shape[:2]
+    out = np.zeros(out_shape(h, w), np.float32)
+    ctx.check(fn(ctx.h, _ptr(bgr), w, h, C.byref(fp), _ptr(out)))
+    return out
+
+
+def fpdw_image(ctx, bgr, cell_size=8, fast_gradient=True, interpolate_bins=False, normalization_radius=None, normalization_constant=0.01):
+    """FpdwFeaturesFilter::applyTo on a host BGR image: (h, w, 10) float32"""
+    fp = _fpdw_params(cell_size, fast_gradient, interpolate_bins, normalization_radius, normalization_constant)
+    return _fpdw_call(ctx, lib().fd_fpdw_image, bgr, lambda h, w: (h, w, 10), fp)
+
+
+def fpdw_cells_image(ctx, bgr, cell_size=8, fast_gradient=True, interpolate_bins=False, normalization_radius=None, normalization_constant=0.01):
+    """ChainedFilter(FpdwFeaturesFilter, AggregationFilter(cell_size, true, false)) on a host BGR image: (h / cell, w / cell, 10) float32"""
+    fp = _fpdw_params(cell_size, fast_gradient, interpolate_bins, normalization_radius, normalization_constant)
+    cs = max(cell_size, 1)   # invalid parameters are reported by the library
+    return _fpdw_call(ctx, lib().fd_fpdw_cells_image, bgr, lambda h, w: (h // cs, w // cs, 10), fp)
+
+
 class Aggregated:
     """fd_aggregated handle: AggregatedFeaturesDetector with GrayscaleFilter + FhogFilter; weights (window_h, window_w, 3B+4).
     approximate=True: the approximated feature pyramid (ImagePyramid::createApproximated) with the given per-channel lambdas,
-    or lambdas estimated per image when lambdas is None."""
+    or lambdas estimated per image when lambdas is None.
+    features="fpdw": no image filter and FpdwFeaturesFilter + AggregationFilter as layer filter instead (BGR images only; weights
+    (window_h, window_w, 10); normalization_radius None: the cell size)."""
     def __init__(self, ctx, weights, bias, threshold, cell_size=8, unsigned_bins=9, interpolate_bins=False, interpolate_cells=True, alpha=0.2,
                  octave_layers=5, min_window_width=0, width_scale=1.0, height_scale=1.0, nms_overlap=0.3, nms_type=0, approximate=False,
-                 lambdas=None):
+                 lambdas=None, features="fhog", fast_gradient=True, normalization_radius=None, normalization_constant=0.01):
+        if features not in ("fhog", "fpdw"):
+            raise ValueError("features must be 'fhog' or 'fpdw'")
         self.ctx = ctx
         self._w = _c(weights, np.float32)
         wh, ww, d = self._w.shape
-        assert d == 3 * unsigned_bins + 4
+        assert d == (10 if features == "fpdw" else 3 * unsigned_bins + 4)
         prm = fd_aggregated_params(fd_fhog_params(cell_size, unsigned_bins, int(interpolate_bins), int(interpolate_cells), alpha), ww, wh,
                                    octave_layers, min_window_width, width_scale, height_scale, self._w.ctypes.data, bias, threshold,
                                    nms_overlap, nms_type)
         self.h = C.c_void_p()
         self.channels = d
-        if approximate:
+        if features == "fpdw":
+            if lambdas is not None and not approximate:
+                raise ValueError("lambdas belong to the approximated feature pyramid (approximate=True)")
+            fp = _fpdw_params(cell_size, fast_gradient, interpolate_bins, normalization_radius, normalization_constant)
+            lam = _c(lambdas, np.float64) if lambdas is not None else None
+            ctx.check(lib().fd_aggregated_create_fpdw(ctx.h, C.byref(prm), C.byref(fp), int(approximate), _ptr(lam) if lam is not None else None,
+                                                      len(lam) if lam is not None else 0, C.byref(self.h)))
+        elif approximate:
             lam = _c(lambdas, np.float64) if lambdas is not None else None
             ctx.check(lib().fd_aggregated_create_approximated(ctx.h, C.byref(prm), _ptr(lam) if lam is not None else None,
                                                               len(lam) if lam is not None else 0, C.byref(self.h)))

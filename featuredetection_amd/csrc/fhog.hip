@@ -80,6 +80,12 @@ struct fd_aggregated {
     DevBuf dapprox, dresize, dfactors, dsums;
     std::vector<float> factors;
     std::vector<double> sums;
+    // feature type: FHOG on a gray pyramid, or FPDW channel features (fd_aggregated_create_fpdw, fpdw.hpp) on a pyramid of three
+    // frames, the B, G and R planes of the image
+    int D = 0;                                   // channels per cell
+    bool fpdw = false;
+    fd_fpdw_params fpp{};
+    int fpdwTiles = 0;                           // k_fpdw workgroups over the exact layers
     ~fd_aggregated() { if (pyr) fd_pyramid_destroy(pyr); }
 };
 
@@ -551,6 +557,8 @@ void resize_tab(int sn, int dn, bool horizontal, std::vector<FhogResizeTab>& out
 
 }  // namespace
 
+#include "fpdw.hpp"
+
 extern "C" {
 
 int fd_fhog_size(const fd_fhog_params* fp, int width, int height, int* rows, int* cols, int* channels) {
@@ -600,18 +608,28 @@ int fd_pyramid_fhog_layer(fd_ctx* ctx, fd_pyramid* p, int layer, const fd_fhog_p
     });
 }
 
-static int aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, bool approx, const double* lambdas, int n_lambdas, fd_aggregated** out) {
+static int aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, bool approx, const double* lambdas, int n_lambdas, fd_aggregated** out,
+                             const fd_fpdw_params* fpdw = nullptr) {
     return fd_guard(ctx, [&] {
         if (!ctx || !prm || !out || !prm->svm_weights) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create: NULL argument");
         if (prm->window_w < 1 || prm->window_h < 1 || prm->octave_layer_count < 1)
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "AggregatedFeaturesDetector: window size and octave layer count must be positive");
-        if (prm->fhog.cell_size < 1 || prm->fhog.unsigned_bins < 1 || 2 * prm->fhog.unsigned_bins > FHOG_MAX_SBINS || !(prm->fhog.alpha > 0))
+        if (fpdw) {
+            check_fpdw_params(*fpdw);
+            if (prm->fhog.cell_size != fpdw->cell_size)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "AggregatedFeaturesDetector: the detector's cell size (%d) and the aggregation filter's (%d) differ",
+                         prm->fhog.cell_size, fpdw->cell_size);
+            fpdw_tile_cells(*fpdw);   // throws when the working set of one cell exceeds the tile memory
+        } else if (prm->fhog.cell_size < 1 || prm->fhog.unsigned_bins < 1 || 2 * prm->fhog.unsigned_bins > FHOG_MAX_SBINS || !(prm->fhog.alpha > 0))
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "AggregatedFeaturesDetector: invalid FhogFilter parameters");
         HIP_CHECK(hipSetDevice(ctx->device));
         std::unique_ptr<fd_aggregated> a(new fd_aggregated());
         a->ctx = ctx;
         a->prm = *prm;
-        const size_t nw = (size_t)prm->window_w * prm->window_h * (3 * prm->fhog.unsigned_bins + 4);
+        a->fpdw = fpdw != nullptr;
+        if (fpdw) a->fpp = *fpdw;
+        a->D = fpdw ? FPDW_CHANNELS : 3 * prm->fhog.unsigned_bins + 4;
+        const size_t nw = (size_t)prm->window_w * prm->window_h * a->D;
         a->weights.assign(prm->svm_weights, prm->svm_weights + nw);
         a->prm.svm_weights = nullptr;
         a->dweights.reserve(sizeof(float) * nw);
@@ -619,7 +637,7 @@ static int aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, bool 
         a->approx = approx;
         if (approx && n_lambdas != 0) {   // ImagePyramid.cpp:212-213
             if (n_lambdas < 0 || !lambdas) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create_approximated: bad lambdas");
-            if (n_lambdas != 3 * prm->fhog.unsigned_bins + 4)
+            if (n_lambdas != a->D)
                 FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: the number of lambdas does not match the number of channels");
             a->givenLambdas.assign(lambdas, lambdas + n_lambdas);
         }
@@ -633,6 +651,14 @@ int fd_aggregated_create(fd_ctx* ctx, const fd_aggregated_params* prm, fd_aggreg
 
 int fd_aggregated_create_approximated(fd_ctx* ctx, const fd_aggregated_params* prm, const double* lambdas, int n_lambdas, fd_aggregated** out) {
     return aggregated_create(ctx, prm, true, lambdas, n_lambdas, out);
+}
+
+int fd_aggregated_create_fpdw(fd_ctx* ctx, const fd_aggregated_params* prm, const fd_fpdw_params* fp, int approximated, const double* lambdas,
+                              int n_lambdas, fd_aggregated** out) {
+    if (!fp) return fd_guard(ctx, [&] { FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create_fpdw: NULL argument"); });
+    if (!approximated && n_lambdas != 0)
+        return fd_guard(ctx, [&] { FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_create_fpdw: lambdas belong to the approximated feature pyramid"); });
+    return aggregated_create(ctx, prm, approximated != 0, lambdas, n_lambdas, out, fp);
 }
 
 int fd_aggregated_get_lambdas(fd_aggregated* a, double* out, int cap, int* n) {
@@ -660,7 +686,7 @@ int fd_aggregated_feature_layer(fd_ctx* ctx, fd_aggregated* a, int layer, float*
         if (layer < 0 || layer >= (int)a->layers.size()) FD_THROW(FD_ERR_INVALID_ARGUMENT, "no such feature layer: %d", layer);
         HIP_CHECK(hipSetDevice(ctx->device));
         const FhogLayerDev& T = a->layerTable[a->tableOf[layer]];
-        const int D = 3 * a->prm.fhog.unsigned_bins + 4;
+        const int D = a->D;
         const size_t n = (size_t)T.rows * T.cols * D;
         if (n) HIP_CHECK(hipMemcpyAsync(out, S.desc.as<float>() + (size_t)T.cellBase * D, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -672,7 +698,7 @@ void fd_aggregated_destroy(fd_aggregated* a) { delete a; }
 // score maps of every layer of the handle's layer table (exact and approximated alike) from the descriptors in S.desc
 static void launch_scores(fd_ctx* ctx, fd_aggregated* a, FhogScratch& S) {
     const fd_aggregated_params& P = a->prm;
-    const int D = 3 * P.fhog.unsigned_bins + 4, nLayers = (int)a->layerTable.size();
+    const int D = a->D, nLayers = (int)a->layerTable.size();
     if (a->layout.positions <= 0) return;
     if (D <= 32) {
         hipLaunchKernelGGL(k_fhog_score, dim3(a->layout.posBlocks), dim3(256), 0, ctx->stream, a->dlayers.as<FhogLayerDev>(), nLayers,
@@ -697,6 +723,52 @@ static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float s
     return fd_box{score, cx - rw / 2, cy - rh / 2, rw, rh};
 }
 
+// the detector's image pyramid: gray layers, or, for FPDW features, a pyramid of three frames -- the B, G and R planes of the image,
+// each scaled exactly as a gray image is (cv::resize and cv::pyrDown treat the channels of a CV_8UC3 image independently)
+static void aggregated_new_pyramid(fd_ctx* ctx, fd_aggregated* a, int octaveLayers, double minScale, double maxScale) {
+    int rc = fd_pyramid_create(ctx, octaveLayers, minScale, maxScale, &a->pyr);
+    if (rc == FD_OK && a->fpdw) rc = fd_pyramid_set_frames(a->pyr, 3);
+    if (rc != FD_OK) throw FdError{rc, ctx->error};
+}
+
+static void aggregated_update_pyramid(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device) {
+    int rc;
+    if (a->fpdw) {
+        const size_t planeStride = fpdw_planes(ctx, fpdw_scratch(ctx), image, width, height, is_device);
+        const uint8_t* planes[3];
+        for (int k = 0; k < 3; ++k) planes[k] = fpdw_scratch(ctx).planes.as<uint8_t>() + k * planeStride;
+        rc = fd_pyramid_update_frames(a->pyr, planes, 3, width, height, 1, 1);
+    } else {
+        rc = fd_pyramid_update(a->pyr, image, width, height, channels, is_device);
+    }
+    if (rc != FD_OK) throw FdError{rc, ctx->error};
+}
+
+// what an FPDW handle checks before anything is built: the image type (FpdwFeaturesFilter.cpp:67-69)
+static void aggregated_check_image(const fd_aggregated* a, int width, int height, int channels) {
+    if (!a->fpdw) return;
+    if (width < 1 || height < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_update: empty image");
+    if (channels != 3)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "FpdwFeaturesFilter: the gradient image type must be CV_8UC3 or CV_32FC3, but was %d", (channels - 1) * 8);
+}
+
+// cell descriptors of the first nLayers entries of the handle's layer table (its exact layers) into S.desc
+static void aggregated_features(fd_ctx* ctx, fd_aggregated* a, FhogScratch& S, int nLayers, const FhogLayoutTotals& t) {
+    if (!a->fpdw) {
+        run_fhog(ctx, S, a->dlayers.as<FhogLayerDev>(), nLayers, t, a->prm.fhog);
+        return;
+    }
+    for (int i = 0; i < nLayers; ++i) check_fpdw_image_size(a->fpp, a->layerTable[i].w, a->layerTable[i].h, true);   // the filters see every layer
+    S.descOwner = nullptr;
+    S.desc.reserve(sizeof(float) * (size_t)std::max(t.cells, 1) * a->D);
+    run_fpdw(ctx, a->dlayers.as<FhogLayerDev>(), nLayers, a->fpdwTiles, a->pyr->image_stride, a->fpp, false, S.desc.as<float>());
+}
+
+// after layout_layers: k_fpdw's tiles over the exact layers (the first nExact entries of the layer table)
+static void aggregated_finish_layout(fd_aggregated* a, int nExact) {
+    if (a->fpdw) a->fpdwTiles = fpdw_assign_tiles(a->layerTable, nExact, a->fpp.cell_size, fpdw_tile_cells(a->fpp), false);
+}
+
 // Feature pyramid and score maps of an approximated handle.  Per image size: the layer plan, the one-layer-per-octave gray
 // pyramid, the layer table (exact layers first, so that run_fhog's launches see exactly them; the approximated ones follow in
 // the same descriptor buffer), the resize tables and, with given lambdas, the factors.  Per image: pyramid, FHOG of the exact
@@ -704,7 +776,7 @@ static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float s
 static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
                                      std::vector<fd_box>& cand) {
     const fd_aggregated_params& P = a->prm;
-    const int D = 3 * P.fhog.unsigned_bins + 4, cs = P.fhog.cell_size, n = P.octave_layer_count;
+    const int D = a->D, cs = P.fhog.cell_size, n = P.octave_layer_count;
     if (!a->pyr || a->pyrW != width || a->pyrH != height) {
         if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
         a->layerTable.clear();
@@ -712,14 +784,10 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
         double minScale, maxScale;
         fd_host_aggregated_limits(P.window_w, P.window_h, cs, n, P.min_window_width, width, height, minScale, maxScale);
         // both setters forward to the source pyramid (ImagePyramid.hpp:241-263), which has one layer per octave
-        const int rc = fd_pyramid_create(ctx, 1, minScale, maxScale, &a->pyr);
-        if (rc != FD_OK) throw FdError{rc, ctx->error};
+        aggregated_new_pyramid(ctx, a, 1, minScale, maxScale);
         a->pyrW = width; a->pyrH = height;
     }
-    {
-        const int rc = fd_pyramid_update(a->pyr, image, width, height, channels, is_device);
-        if (rc != FD_OK) throw FdError{rc, ctx->error};
-    }
+    aggregated_update_pyramid(ctx, a, image, width, height, channels, is_device);
     fd_pyramid* p = a->pyr;
     const bool estimate = a->givenLambdas.empty();
     if (estimate && p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:238-239); given lambdas need no second layer (:209-213)
@@ -748,7 +816,7 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
             std::memset(&T, 0, sizeof(T));
             if (!L.approximated) {
                 const HostLayer& H = p->all[p->kept[ti]];
-                T.img = p->arena.as<uint8_t>() + H.gray_off; T.w = H.w; T.h = H.h; T.stride = H.w; T.channels = 1;
+                T.img = p->arena.as<uint8_t>() + H.gray_off; T.w = H.w; T.h = H.h; T.stride = H.w; T.channels = a->fpdw ? 3 : 1;
             } else {   // no pixels: layout_layers derives rows / cols from w / h
                 const fd_aggregated_layer& X = plan.layers[L.parent];
                 const bool empty = X.rows < 1 || X.cols < 1;
@@ -763,6 +831,7 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
             a->exactLayout = layout_layers(exact, P.fhog);
         }
         a->layout = layout_layers(a->layerTable, P.fhog);
+        aggregated_finish_layout(a, (int)E);
         // approximated layers: launch table, cv::resize tables, factors
         a->approxTable.clear();
         a->approxScale.clear();
@@ -812,8 +881,8 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
     }
     const int nExact = (int)p->kept.size(), nApprox = (int)a->approxTable.size();
     a->scores.reserve(sizeof(float) * std::max<size_t>((size_t)a->layout.positions, 1));
-    S.desc.reserve(sizeof(float) * (size_t)std::max(a->layout.cells, 1) * D);   // before run_fhog: room for the approximated layers too
-    run_fhog(ctx, S, a->dlayers.as<FhogLayerDev>(), nExact, a->exactLayout, P.fhog);
+    S.desc.reserve(sizeof(float) * (size_t)std::max(a->layout.cells, 1) * D);   // before the features: room for the approximated layers too
+    aggregated_features(ctx, a, S, nExact, a->exactLayout);
     // factors (float)pow(s, -lambda[c]) (ImagePyramid.cpp:284; Mat *= double on CV_32F multiplies by the float)
     auto set_factors = [&](const std::vector<double>& lambdas) {
         for (int k = 0; k < nApprox; ++k)
@@ -876,6 +945,7 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         const fd_aggregated_params& P = a->prm;
         HIP_CHECK(hipSetDevice(ctx->device));
         std::vector<fd_box> cand;
+        aggregated_check_image(a, width, height, channels);
         if (a->approx) aggregated_detect_approx(ctx, a, image, width, height, channels, is_device, cand);
         else {
         // feature pyramid limits (AggregatedFeaturesExtractor.cpp:30-31,47-52,58-77), recomputed when the image size changes
@@ -884,14 +954,10 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
             a->layerTable.clear();
             double minScale, maxScale;
             fd_host_aggregated_limits(P.window_w, P.window_h, P.fhog.cell_size, P.octave_layer_count, P.min_window_width, width, height, minScale, maxScale);
-            const int rc = fd_pyramid_create(ctx, P.octave_layer_count, minScale, maxScale, &a->pyr);
-            if (rc != FD_OK) throw FdError{rc, ctx->error};
+            aggregated_new_pyramid(ctx, a, P.octave_layer_count, minScale, maxScale);
             a->pyrW = width; a->pyrH = height;
         }
-        {
-            const int rc = fd_pyramid_update(a->pyr, image, width, height, channels, is_device);
-            if (rc != FD_OK) throw FdError{rc, ctx->error};
-        }
+        aggregated_update_pyramid(ctx, a, image, width, height, channels, is_device);
         fd_pyramid* p = a->pyr;
         if (p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:240-242) of the score pyramid
             FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
@@ -904,12 +970,13 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
                 const HostLayer& L = p->all[p->kept[li]];
                 FhogLayerDev& T = a->layerTable[li];
                 std::memset(&T, 0, sizeof(T));
-                T.img = p->arena.as<uint8_t>() + L.gray_off; T.w = L.w; T.h = L.h; T.stride = L.w; T.channels = 1;
+                T.img = p->arena.as<uint8_t>() + L.gray_off; T.w = L.w; T.h = L.h; T.stride = L.w; T.channels = a->fpdw ? 3 : 1;
                 T.vh = std::max(L.h / P.fhog.cell_size - P.window_h + 1, 0);
                 T.vw = std::max(L.w / P.fhog.cell_size - P.window_w + 1, 0);
                 if (T.vw == 0 || T.vh == 0) T.vw = T.vh = 0;
             }
             a->layout = layout_layers(a->layerTable, P.fhog);
+            aggregated_finish_layout(a, (int)a->layerTable.size());
             a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
             HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
             a->arenaAt = p->arena.p;
@@ -931,7 +998,7 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         }
         off[p->kept.size()] = (size_t)a->layout.positions;
         a->scores.reserve(sizeof(float) * std::max<size_t>(off.back(), 1));
-        run_fhog(ctx, S, a->dlayers.as<FhogLayerDev>(), nLayers, a->layout, P.fhog);
+        aggregated_features(ctx, a, S, nLayers, a->layout);
         launch_scores(ctx, a, S);
         std::vector<float> hs(off.back());
         if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));

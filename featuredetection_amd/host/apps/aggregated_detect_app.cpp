@@ -6,10 +6,12 @@
 //   aggregated_detect_app <config.cfg> <svm file> <image.pgm|ppm>...
 //
 // config (INFO format):
-//   features  { type fhog[N]  windowWidthInCells .. windowHeightInCells .. cellSizeInPixels .. widthScaleFactor .. heightScaleFactor ..
+//   features  { type fhog[N] | fpdw  windowWidthInCells .. windowHeightInCells .. cellSizeInPixels .. widthScaleFactor .. heightScaleFactor ..
 //               lambdas "l0 l1 ..." (optional, this app: the lambdas of the approximated pyramid; absent = estimated per image) }
 //   detection { minWindowWidthInPixels .. minWindowHeightInPixels .. octaveLayerCount .. approximatePyramid true|false
 //               nmsOverlapThreshold ..  threshold .. (optional, this app: the SVM's threshold, default 0) }
+// type fpdw: no image filter, layer filter ChainedFilter(FpdwFeaturesFilter(true, false, cell, 0.01), AggregationFilter(cell, true, false))
+// (DetectorTrainingApp.cpp:99-113), ten lambdas, BGR images only.
 // The SVM is read from the text format of SvmClassifier::store.  Output: one line per detection, "<image index> x y width height score".
 #include <cstdio>
 #include <fstream>
@@ -17,7 +19,9 @@
 #include <sstream>
 #include "detection/detection_all.hpp"
 #include "imageprocessing/extraction/AggregatedFeaturesExtractor.hpp"
+#include "imageprocessing/filtering/AggregationFilter.hpp"
 #include "imageprocessing/filtering/FhogFilter.hpp"
+#include "imageprocessing/filtering/FpdwFeaturesFilter.hpp"
 #include "fdcompat/ptree.hpp"
 
 using namespace detection;
@@ -25,7 +29,9 @@ using namespace imageprocessing;
 using classification::SvmClassifier;
 using boost::property_tree::ptree;
 using imageprocessing::extraction::AggregatedFeaturesExtractor;
+using imageprocessing::filtering::AggregationFilter;
 using imageprocessing::filtering::FhogFilter;
+using imageprocessing::filtering::FpdwFeaturesFilter;
 using std::make_shared;
 using std::shared_ptr;
 using std::string;
@@ -65,10 +71,11 @@ int main(int argc, char** argv) {
         boost::property_tree::read_info(string(argv[1]), config);
         const ptree& fcfg = config.get_child("features");
         const ptree& dcfg = config.get_child("detection");
-        // features: FHOG cells, fhog or fhog<unsigned bin count>
+        // features: FHOG cells, fhog or fhog<unsigned bin count>, or FPDW channel features
         const string type = fcfg.get<string>("type");
-        if (type.compare(0, 4, "fhog") != 0) throw std::invalid_argument("features.type: expected fhog[N], but was '" + type + "' (fpdw is not available on this backend)");
-        const int bins = type.size() > 4 ? std::stoi(type.substr(4)) : 9;
+        const bool fpdw = type == "fpdw";
+        if (!fpdw && type.compare(0, 4, "fhog") != 0) throw std::invalid_argument("features.type: expected fhog[N] or fpdw, but was '" + type + "'");
+        const int bins = !fpdw && type.size() > 4 ? std::stoi(type.substr(4)) : 9;
         const int cell = fcfg.get<int>("cellSizeInPixels");
         const cv::Size window(fcfg.get<int>("windowWidthInCells"), fcfg.get<int>("windowHeightInCells"));
         const float widthScale = 1.0f / fcfg.get<float>("widthScaleFactor"), heightScale = 1.0f / fcfg.get<float>("heightScaleFactor");
@@ -89,18 +96,27 @@ int main(int argc, char** argv) {
         svm->setThreshold(dcfg.get<float>("threshold", 0.0f));
 
         auto gray = make_shared<GrayscaleFilter>();
-        auto fhog = make_shared<FhogFilter>(cell, bins, false, true, 0.2f);
+        shared_ptr<ImageFilter> layerFilter;
+        if (fpdw) {
+            auto chain = make_shared<ChainedFilter>();
+            chain->add(make_shared<FpdwFeaturesFilter>(true, false, cell, 0.01));
+            chain->add(make_shared<AggregationFilter>(cell, true, false));
+            layerFilter = chain;
+        } else {
+            layerFilter = make_shared<FhogFilter>(cell, bins, false, true, 0.2f);
+        }
         auto nms = make_shared<NonMaximumSuppression>(dcfg.get<double>("nmsOverlapThreshold"), NonMaximumSuppression::MaximumType::MAX_SCORE);
         shared_ptr<AggregatedFeaturesDetector> detector;
         if (approximate) {
             auto pyramid = ImagePyramid::createApproximated(octaveLayers, 0.5, 1.0, lambdas);
-            pyramid->addImageFilter(gray);
-            pyramid->addLayerFilter(fhog);
+            if (!fpdw) pyramid->addImageFilter(gray);
+            pyramid->addLayerFilter(layerFilter);
             detector = make_shared<AggregatedFeaturesDetector>(make_shared<AggregatedFeaturesExtractor>(pyramid, window, cell, true, minWidth), svm, nms,
                                                                widthScale, heightScale);
         } else {
             if (!lambdas.empty()) throw std::invalid_argument("features.lambdas belong to approximatePyramid true");
-            detector = make_shared<AggregatedFeaturesDetector>(gray, fhog, cell, window, octaveLayers, svm, nms, widthScale, heightScale, minWidth);
+            if (fpdw) detector = make_shared<AggregatedFeaturesDetector>(layerFilter, cell, window, octaveLayers, svm, nms, widthScale, heightScale, minWidth);
+            else detector = make_shared<AggregatedFeaturesDetector>(gray, layerFilter, cell, window, octaveLayers, svm, nms, widthScale, heightScale, minWidth);
         }
         for (int a = 3; a < argc; ++a) {
             const cv::Mat image = read_pnm(argv[a]);

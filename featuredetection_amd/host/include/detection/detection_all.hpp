@@ -84,6 +84,11 @@ public:
                                int cellSize, cv::Size windowSize, int octaveLayerCount, std::shared_ptr<classification::SvmClassifier> svm,
                                std::shared_ptr<NonMaximumSuppression> nonMaximumSuppression, float widthScale = 1.0f, float heightScale = 1.0f,
                                int minWindowWidth = 0);
+    // AggregatedFeaturesDetector.hpp:60: one filter applied to the layers of the unfiltered image's pyramid; on this backend
+    // ChainedFilter(filtering::FpdwFeaturesFilter, filtering::AggregationFilter(cellSize, true, false))
+    AggregatedFeaturesDetector(std::shared_ptr<imageprocessing::ImageFilter> filter, int cellSize, cv::Size windowSize, int octaveLayerCount,
+                               std::shared_ptr<classification::SvmClassifier> svm, std::shared_ptr<NonMaximumSuppression> nonMaximumSuppression,
+                               float widthScale = 1.0f, float heightScale = 1.0f, int minWindowWidth = 0);
     // AggregatedFeaturesDetector.cpp:61-67: on an extractor over an approximated feature pyramid (createApproximateDetector)
     AggregatedFeaturesDetector(std::shared_ptr<imageprocessing::extraction::AggregatedFeaturesExtractor> featureExtractor,
                                std::shared_ptr<classification::SvmClassifier> svm, std::shared_ptr<NonMaximumSuppression> nonMaximumSuppression,
@@ -98,7 +103,7 @@ public:
     }
     float getScoreThreshold() const { return scoreThreshold; }
 private:
-    void create(const imageprocessing::filtering::FhogFilter& fhog, cv::Size windowSize, int octaveLayerCount, const classification::SvmClassifier& svm,
+    void create(const imageprocessing::filtering::FhogFilter* fhog, const fd_fpdw_params* fpdw, cv::Size windowSize, int octaveLayerCount, const classification::SvmClassifier& svm,
                 const NonMaximumSuppression& nms, float widthScale, float heightScale, int minWindowWidth, const std::vector<double>* lambdas);
     fd_aggregated* handle = nullptr;
     float scoreThreshold;

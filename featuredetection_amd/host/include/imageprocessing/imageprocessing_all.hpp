@@ -57,12 +57,9 @@ public:
     using ImageFilter::applyTo;
     void add(std::shared_ptr<ImageFilter> filter) { filters.push_back(filter); }
     const std::vector<std::shared_ptr<ImageFilter>>& getFilters() const { return filters; }
-    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override {
-        if (filters.empty()) { image.copyTo(filtered); return filtered; }
-        filtered = image;
-        for (const auto& f : filters) { cv::Mat tmp; f->applyTo(filtered, tmp); filtered = tmp; }
-        return filtered;
-    }
+    // the filters in turn.  Only the chain of exactly the two filters [filtering::FpdwFeaturesFilter, filtering::AggregationFilter] is
+    // fused into one device call; inside any other chain AggregationFilter::applyTo is reached on its own and throws logic_error
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
 private:
     std::vector<std::shared_ptr<ImageFilter>> filters;
 };
@@ -269,6 +266,7 @@ public:
     size_t getOctaveLayerCount() const { return ctorOctaveLayers; }
     std::shared_ptr<ImageFilter> getApproximatedLayerFilter() const { return approxLayerFilter; }
     bool hasGrayscaleImageFilter() const { return imageChain.size() == 1 && imageChain[0] == FD_IMAGE_GRAY; }
+    bool hasNoImageFilter() const { return imageChain.empty(); }
     ~ImagePyramid();
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
@@ -498,6 +496,29 @@ public:
     int cellSize, unsignedBinCount;
     bool interpolateBins, interpolateCells;
     float alpha;
+};
+
+// filtering/FpdwFeaturesFilter.hpp:44 / FpdwFeaturesFilter.cpp:21-205: ten channels per pixel of a CV_8UC3 image -- six unsigned
+// gradient-orientation bins, the normalised gradient magnitude, L*u*v* (fd_fpdw_image)
+class FpdwFeaturesFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    FpdwFeaturesFilter(bool fastGradient, bool interpolate, int normalizationRadius = 5, double normalizationConstant = 0.01);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;   // CV_8UC3 -> rows x cols x 10 CV_32F (stored as rows x cols*10)
+    bool fastGradient, interpolate;
+    int normalizationRadius;
+    double normalizationConstant;
+};
+
+// filtering/AggregationFilter.hpp:38 / AggregationFilter.cpp:20-36.  On this backend: the triangular form without normalisation
+// (cellSize, true, false), as the second filter of a ChainedFilter behind a FpdwFeaturesFilter (fd_fpdw_cells_image) or in the layer
+// filter of an AggregatedFeaturesDetector; box aggregation, normalize = true and applyTo on its own throw logic_error.
+class AggregationFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    explicit AggregationFilter(int cellSize, bool interpolate = false, bool normalize = false);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    int cellSize;
 };
 }  // namespace filtering
 

@@ -52,6 +52,40 @@ Mat GrayscaleFilter::applyTo(const Mat& image, Mat& filtered) const {
     return filtered;
 }
 
+// the FPDW chain a ChainedFilter may hold: [filtering::FpdwFeaturesFilter, filtering::AggregationFilter] as fd_fpdw_params
+static bool fpdw_chain(const ImageFilter* filter, fd_fpdw_params& fp) {
+    auto chain = dynamic_cast<const ChainedFilter*>(filter);
+    if (!chain || chain->getFilters().size() != 2) return false;
+    auto fpdw = std::dynamic_pointer_cast<filtering::FpdwFeaturesFilter>(chain->getFilters()[0]);
+    auto agg = std::dynamic_pointer_cast<filtering::AggregationFilter>(chain->getFilters()[1]);
+    if (!fpdw || !agg) return false;
+    fp = fd_fpdw_params{agg->cellSize, fpdw->fastGradient, fpdw->interpolate, fpdw->normalizationRadius, (float)fpdw->normalizationConstant};
+    return true;
+}
+
+static Mat fpdw_apply(const Mat& image, const fd_fpdw_params& fp, bool cells, Mat& descriptors) {
+    if (image.type() != CV_8UC3)
+        throw std::invalid_argument("FpdwFeaturesFilter: the gradient image type must be CV_8UC3 or CV_32FC3, but was " + std::to_string(image.type()) +
+                                    " (this backend: CV_8UC3)");
+    Mat src = contiguous(image);
+    const int rows = cells ? src.rows / fp.cell_size : src.rows, cols = cells ? src.cols / fp.cell_size : src.cols;
+    descriptors.create(rows, cols * 10, CV_32FC1);   // the compat Mat has no CV_32FC(n) with n > 4: channels are interleaved in the row
+    // an image below one cell has no cells to write, but the call is made all the same: it reports the filters' limits as the reference does
+    float none = 0.f;
+    float* out = rows > 0 && cols > 0 ? descriptors.ptr<float>(0) : &none;
+    check((cells ? fd_fpdw_cells_image : fd_fpdw_image)(context(), src.ptr<uchar>(0), src.cols, src.rows, &fp, out));
+    return descriptors;
+}
+
+Mat ChainedFilter::applyTo(const Mat& image, Mat& filtered) const {
+    fd_fpdw_params fp;
+    if (fpdw_chain(this, fp)) return fpdw_apply(image, fp, true, filtered);
+    if (filters.empty()) { image.copyTo(filtered); return filtered; }
+    filtered = image;
+    for (const auto& f : filters) { Mat tmp; f->applyTo(filtered, tmp); filtered = tmp; }
+    return filtered;
+}
+
 Mat HistEq64Filter::applyTo(const Mat& image, Mat& filtered) const {
     if (image.type() != CV_8UC1) throw std::invalid_argument("HistEq64Filter: the image must be of type CV_8UC1");
     Mat src = contiguous(image);
@@ -377,8 +411,10 @@ ImagePyramid::Selection ImagePyramid::select(int firstLayer, int lastLayer, int 
 }
 void ImagePyramid::addLayerFilter(const shared_ptr<ImageFilter>& filter) {
     if (approximated) {
-        if (approxLayerFilter || !std::dynamic_pointer_cast<filtering::FhogFilter>(filter))
-            throw std::logic_error("ImagePyramid: the layer filter of an approximated pyramid is one filtering::FhogFilter on this backend");
+        fd_fpdw_params fp;
+        if (approxLayerFilter || (!std::dynamic_pointer_cast<filtering::FhogFilter>(filter) && !fpdw_chain(filter.get(), fp)))
+            throw std::logic_error("ImagePyramid: the layer filter of an approximated pyramid is one filtering::FhogFilter or one "
+                                   "ChainedFilter(filtering::FpdwFeaturesFilter, filtering::AggregationFilter) on this backend");
         approxLayerFilter = filter;
         return;
     }
@@ -503,6 +539,27 @@ Mat FhogFilter::applyTo(const Mat& image, Mat& descriptors) const {
     if (rows > 0 && cols > 0)
         check(fd_fhog_image_channels(context(), src.ptr<uchar>(0), src.cols, src.rows, src.channels(), &fp, descriptors.ptr<float>(0)));
     return descriptors;
+}
+
+FpdwFeaturesFilter::FpdwFeaturesFilter(bool fastGradient, bool interpolate, int normalizationRadius, double normalizationConstant)
+    : fastGradient(fastGradient), interpolate(interpolate), normalizationRadius(normalizationRadius), normalizationConstant(normalizationConstant) {
+    if (normalizationRadius < 0)
+        throw std::invalid_argument("TriangularConvolutionFilter: size must be greater than zero, but was " + std::to_string(2 * normalizationRadius + 1));
+    if (normalizationConstant <= 0)
+        throw std::invalid_argument("GradientMagnitudeFilter: normalizationConstant must be bigger than zero, but was " + std::to_string(normalizationConstant));
+}
+Mat FpdwFeaturesFilter::applyTo(const Mat& image, Mat& descriptors) const {
+    const fd_fpdw_params fp = {1, fastGradient, interpolate, normalizationRadius, (float)normalizationConstant};
+    return fpdw_apply(image, fp, false, descriptors);
+}
+AggregationFilter::AggregationFilter(int cellSize, bool interpolate, bool normalize) : cellSize(cellSize) {
+    if (cellSize < 1) throw std::invalid_argument("AggregationFilter: cellSize must be bigger than zero, but was " + std::to_string(cellSize));
+    if (!interpolate) throw std::logic_error("AggregationFilter: box aggregation (interpolate = false) is not available on this backend");
+    if (normalize) throw std::logic_error("AggregationFilter: normalize = true is not available on this backend");
+}
+Mat AggregationFilter::applyTo(const Mat&, Mat&) const {
+    throw std::logic_error("AggregationFilter: on this backend the filter runs fused behind a filtering::FpdwFeaturesFilter "
+                           "(ChainedFilter(FpdwFeaturesFilter, AggregationFilter)), not on an image of its own");
 }
 }  // namespace filtering
 
@@ -1206,7 +1263,21 @@ AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessin
     if (!std::dynamic_pointer_cast<imageprocessing::GrayscaleFilter>(imageFilter) || !fhog)
         throw std::logic_error("AggregatedFeaturesDetector: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter");
     if (fhog->cellSize != cellSize) throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the FhogFilter's");
-    create(*fhog, windowSize, octaveLayerCount, *svm, *nms, widthScale, heightScale, minWindowWidth, nullptr);
+    create(fhog.get(), nullptr, windowSize, octaveLayerCount, *svm, *nms, widthScale, heightScale, minWindowWidth, nullptr);
+}
+static const char* const kAggregatedFilters =
+    "AggregatedFeaturesDetector: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter, or no image "
+    "filter and ChainedFilter(filtering::FpdwFeaturesFilter, filtering::AggregationFilter) as the only filter";
+AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessing::ImageFilter> filter, int cellSize, cv::Size windowSize,
+                                                       int octaveLayerCount, shared_ptr<classification::SvmClassifier> svm,
+                                                       shared_ptr<NonMaximumSuppression> nms, float widthScale, float heightScale, int minWindowWidth)
+    : scoreThreshold(svm->getThreshold()) {
+    if (!dynamic_cast<classification::LinearKernel*>(svm->getKernel().get()))
+        throw std::invalid_argument("AggregatedFeaturesDetector: the SVM must use a LinearKernel");
+    fd_fpdw_params fp;
+    if (!imageprocessing::fpdw_chain(filter.get(), fp)) throw std::logic_error(kAggregatedFilters);
+    if (fp.cell_size != cellSize) throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the AggregationFilter's");
+    create(nullptr, &fp, windowSize, octaveLayerCount, *svm, *nms, widthScale, heightScale, minWindowWidth, nullptr);
 }
 AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessing::extraction::AggregatedFeaturesExtractor> featureExtractor,
                                                        shared_ptr<classification::SvmClassifier> svm, shared_ptr<NonMaximumSuppression> nms,
@@ -1217,34 +1288,38 @@ AggregatedFeaturesDetector::AggregatedFeaturesDetector(shared_ptr<imageprocessin
         throw std::invalid_argument("AggregatedFeaturesDetector: the SVM must use a LinearKernel");
     auto pyramid = featureExtractor->getFeaturePyramid();
     auto fhog = std::dynamic_pointer_cast<imageprocessing::filtering::FhogFilter>(pyramid->getApproximatedLayerFilter());
-    if (!pyramid->hasGrayscaleImageFilter() || !fhog)
-        throw std::logic_error("AggregatedFeaturesDetector: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter");
-    if (fhog->cellSize != featureExtractor->getCellSizeInPixels())
-        throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the FhogFilter's");
-    create(*fhog, featureExtractor->getPatchSizeInCells(), (int)pyramid->getOctaveLayerCount(), *svm, *nms, widthScale, heightScale,
+    fd_fpdw_params fp;
+    const bool fpdw = pyramid->hasNoImageFilter() && imageprocessing::fpdw_chain(pyramid->getApproximatedLayerFilter().get(), fp);
+    if (!fpdw && (!pyramid->hasGrayscaleImageFilter() || !fhog)) throw std::logic_error(kAggregatedFilters);
+    if ((fpdw ? fp.cell_size : fhog->cellSize) != featureExtractor->getCellSizeInPixels())
+        throw std::invalid_argument("AggregatedFeaturesDetector: cellSize differs from the layer filter's");
+    create(fpdw ? nullptr : fhog.get(), fpdw ? &fp : nullptr, featureExtractor->getPatchSizeInCells(), (int)pyramid->getOctaveLayerCount(), *svm, *nms, widthScale, heightScale,
            featureExtractor->getMinPatchWidthInPixels(), &pyramid->getLambdas());
 }
-void AggregatedFeaturesDetector::create(const imageprocessing::filtering::FhogFilter& fhogFilter, cv::Size windowSize, int octaveLayerCount,
-                                        const classification::SvmClassifier& svmRef, const NonMaximumSuppression& nmsRef, float widthScale,
-                                        float heightScale, int minWindowWidth, const vector<double>* lambdas) {
-    const imageprocessing::filtering::FhogFilter* fhog = &fhogFilter;
+void AggregatedFeaturesDetector::create(const imageprocessing::filtering::FhogFilter* fhog, const fd_fpdw_params* fpdw, cv::Size windowSize,
+                                        int octaveLayerCount, const classification::SvmClassifier& svmRef, const NonMaximumSuppression& nmsRef,
+                                        float widthScale, float heightScale, int minWindowWidth, const vector<double>* lambdas) {
     const classification::SvmClassifier* svm = &svmRef;
     const NonMaximumSuppression* nms = &nmsRef;
-    const int D = 3 * fhog->unsignedBinCount + 4;
+    const int D = fpdw ? 10 : 3 * fhog->unsignedBinCount + 4;
     if (svm->getSupportVectors().size() != 1) throw std::invalid_argument("AggregatedFeaturesDetector: a linear SVM with one support vector is needed");
     Mat sv = contiguous(svm->getSupportVectors()[0]);
     if (sv.depth() != CV_32F || (int)(sv.total() * sv.channels()) != windowSize.width * windowSize.height * D)
-        throw std::invalid_argument("AggregatedFeaturesDetector: the support vector must hold windowSize x (3 * unsignedBinCount + 4) floats");
+        throw std::invalid_argument(fpdw ? "AggregatedFeaturesDetector: the support vector must hold windowSize x 10 floats"
+                                         : "AggregatedFeaturesDetector: the support vector must hold windowSize x (3 * unsignedBinCount + 4) floats");
     fd_aggregated_params prm;
     std::memset(&prm, 0, sizeof(prm));
-    prm.fhog = fd_fhog_params{fhog->cellSize, fhog->unsignedBinCount, fhog->interpolateBins, fhog->interpolateCells, fhog->alpha};
+    if (fpdw) prm.fhog.cell_size = fpdw->cell_size;
+    else prm.fhog = fd_fhog_params{fhog->cellSize, fhog->unsignedBinCount, fhog->interpolateBins, fhog->interpolateCells, fhog->alpha};
     prm.window_w = windowSize.width; prm.window_h = windowSize.height; prm.octave_layer_count = octaveLayerCount;
     prm.min_window_width = minWindowWidth; prm.width_scale = widthScale; prm.height_scale = heightScale;
     // SvmClassifier: distance = -bias + coefficient * <sv, x>; the reference convolves the raw support vector (coefficients are 1)
     prm.svm_weights = sv.ptr<float>(0);
     prm.svm_bias = svm->getBias(); prm.score_threshold = svm->getThreshold();
     prm.nms_overlap_threshold = nms->getOverlapThreshold(); prm.nms_maximum_type = (int)nms->getMaximumType();
-    if (lambdas) check(fd_aggregated_create_approximated(context(), &prm, lambdas->data(), (int)lambdas->size(), &handle));
+    if (fpdw) check(fd_aggregated_create_fpdw(context(), &prm, fpdw, lambdas != nullptr, lambdas ? lambdas->data() : nullptr,
+                                              lambdas ? (int)lambdas->size() : 0, &handle));
+    else if (lambdas) check(fd_aggregated_create_approximated(context(), &prm, lambdas->data(), (int)lambdas->size(), &handle));
     else check(fd_aggregated_create(context(), &prm, &handle));
 }
 vector<double> AggregatedFeaturesDetector::getLambdas() const {

@@ -375,6 +375,38 @@ int fd_aggregated_feature_layer(fd_ctx* ctx, fd_aggregated* a, int layer, float*
 int fd_aggregated_plan_layers(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width,
                               int height, fd_aggregated_layer* out, int cap, int* n);
 
+/* FPDW channel features: ChainedFilter(FpdwFeaturesFilter(fastGradient, interpolate, normalizationRadius, normalizationConstant),
+ * AggregationFilter(cellSize, true, false)) on CV_8UC3 images (FpdwFeaturesFilter.cpp:21-205, AggregationFilter.cpp:20-36,
+ * TriangularConvolutionFilter.cpp:20-241): ten floats per pixel / cell -- six unsigned gradient-orientation bins, the gradient
+ * magnitude normalised by its (2 radius + 1)-tap triangular mean + constant (radius 0: not normalised), L / 354, (u + 134) / 354,
+ * (v + 140) / 354 -- and the cells the triangular aggregation filter (2 cell_size or 2 cell_size - 1 taps, sampled every cell_size
+ * pixels, alpha = cell_size^2) makes of them.  The sums are fp32 sums of the taps (not the reference's running differences) and
+ * L*u*v* is evaluated per pixel from OpenCV's documented formula: parity is by tolerance, DESIGN.md 4.3.  DetectorTrainingApp
+ * uses (true, false, cellSize, 0.01). */
+typedef struct {
+    int32_t cell_size, fast_gradient, interpolate, normalization_radius;
+    float normalization_constant;
+} fd_fpdw_params;
+/* host only: rows = height / cell_size, cols = width / cell_size, channels = 10 */
+int fd_fpdw_size(const fd_fpdw_params* fp, int width, int height, int* rows, int* cols, int* channels);
+/* host only (no context, no device): the gradient look-up table, 65536 entries each, index gx | gy << 8 (createGradientLut,
+ * FpdwFeaturesFilter.cpp:34-64, with the orientation taken as (float)atan2((double)gY, (double)gX)).  Without interpolation
+ * bin2 = 0, w1 = 1, w2 = 0.  Any output may be NULL. */
+int fd_fpdw_gradient_lut(const fd_fpdw_params* fp, int32_t* bin1, int32_t* bin2, float* w1, float* w2, float* magnitude);
+/* FpdwFeaturesFilter::applyTo: bgr host image (width * height * 3 bytes) -> width * height * 10 floats (host).  FD_ERR_INVALID_ARGUMENT
+ * with TriangularConvolutionFilter's text when the image is smaller than the normaliser allows (rows <= radius, cols < 2 radius + 2) */
+int fd_fpdw_image(fd_ctx* ctx, const uint8_t* bgr, int width, int height, const fd_fpdw_params* fp, float* out);
+/* the whole chain: (height / cell_size) * (width / cell_size) * 10 floats (host); the aggregation filter's limits (rows < cell_size,
+ * cols < 2 cell_size) are reported in the same way */
+int fd_fpdw_cells_image(fd_ctx* ctx, const uint8_t* bgr, int width, int height, const fd_fpdw_params* fp, float* out);
+/* AggregatedFeaturesDetector with no image filter and that chain as layer filter (DetectorTrainingApp.cpp:99-113,252-254): the
+ * pyramid scales the B, G and R planes, each exactly as the gray pyramid scales a gray image.  prm->fhog.cell_size must equal
+ * fp->cell_size (the other fhog fields are ignored); svm_weights is [window_h][window_w][10].  approximated != 0: the
+ * approximated feature pyramid with n_lambdas = 10 given lambdas, or 0: estimated per image.  fd_aggregated_detect (3-channel
+ * images only), _get_lambdas, _get_layers, _feature_layer and _destroy work unchanged on such a handle. */
+int fd_aggregated_create_fpdw(fd_ctx* ctx, const fd_aggregated_params* prm, const fd_fpdw_params* fp, int approximated, const double* lambdas,
+                              int n_lambdas, fd_aggregated** out);
+
 /* Generic histogram patch filters on the pyramid's bin-image layers (FD_LAYER_GRADBIN: 2 or 4 channels,
  * FD_LAYER_LBP: 1 channel), all built on HistogramFilter::createCellHistograms (HistogramFilter.cpp:23-197,
  * interpolating and non-interpolating):
