@@ -113,6 +113,20 @@ class fd_rvm_detect_params(C.Structure):
                 ("step_y", C.c_int32)]
 
 
+class fd_haar_params(C.Structure):
+    _fields_ = [("sizes", C.POINTER(C.c_float)), ("num_sizes", C.c_int32), ("xs", C.POINTER(C.c_float)), ("num_xs", C.c_int32),
+                ("ys", C.POINTER(C.c_float)), ("num_ys", C.c_int32), ("types", C.c_int32)]
+
+
+class fd_surf_params(C.Structure):
+    _fields_ = [("gradient_count", C.c_int32), ("cell_count", C.c_int32)]
+
+
+HAAR_FEATURE_DTYPE = np.dtype([("rects", np.float32, (4, 4)), ("weights", np.float32, (4,)), ("num_rects", np.int32), ("factor", np.float32),
+                               ("area", np.float32)])
+HAAR_2RECTANGLE, HAAR_3RECTANGLE, HAAR_4RECTANGLE, HAAR_CENTER_SURROUND, HAAR_ALL = 1, 2, 4, 8, 15
+INTEGRAL_HAAR, INTEGRAL_SURF = 0, 1
+
 FEATURE_GRAY, FEATURE_HQ64, FEATURE_HISTEQ = 0, 1, 2
 HIST_HOG, HIST_SPATIAL, HIST_PYRAMID_HOG, HIST_SPATIAL_PYRAMID = 0, 1, 2, 3
 
@@ -245,6 +259,26 @@ _SIGS = {
     "fd_sdm_fit_batch_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "fd_sdm_fit_batch_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_sdm_optimize_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_integral_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "fd_integral_destroy": (None, [C.c_void_p]),
+    "fd_integral_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fd_integral_set_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "fd_integral_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_integral_download": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fd_integral_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "fd_haar_grid": (C.c_int, [C.c_int, C.c_void_p]),
+    "fd_haar_feature_count": (C.c_int, [C.POINTER(fd_haar_params)]),
+    "fd_haar_features": (C.c_int, [C.POINTER(fd_haar_params), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_integral_extract_haar": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_haar_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_integral_gradient_patches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_gradient_sum_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "fd_integral_extract_surf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_integral_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "fd_integral_image_length": (C.c_int, [C.c_int, C.c_int]),
+    "fd_integral_gradient_length": (C.c_int, [C.c_int, C.c_int]),
+    "fd_gradient_sum_length": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fd_surf_feature_length": (C.c_int, [C.c_int, C.c_int]),
 }
 
 # include/fd_hip_bench.h: measurement hooks (not part of the drop-in boundary)
@@ -1298,6 +1332,163 @@ def unit_norm_batch(ctx, vecs, norm_type=4):
     out = np.empty(v.shape, np.float32)
     ctx.check(lib().fd_unit_norm_batch(ctx.h, _ptr(v), v.shape[0], int(np.prod(v.shape[1:])), norm_type, _ptr(out)))
     return out
+
+
+# ---- integral-image features on sampled windows (HaarFeatureFilter, IntegralGradientFilter, GradientSumFilter, the SURF-like chain)
+class _HaarParams:
+    """fd_haar_params with the arrays it points to; grid: the (sizes, xCount, yCount, types) constructors' equidistant grid"""
+
+    def __init__(self, sizes=(0.2, 0.4), xs=None, ys=None, types=HAAR_ALL, grid=(5, 5)):
+        self.sizes = _c(sizes, np.float32).ravel()
+        self.xs = haar_grid(grid[0]) if xs is None else _c(xs, np.float32).ravel()
+        self.ys = (haar_grid(grid[1]) if xs is None else self.xs) if ys is None else _c(ys, np.float32).ravel()
+        fp = C.POINTER(C.c_float)
+        self.c = fd_haar_params(self.sizes.ctypes.data_as(fp), len(self.sizes), self.xs.ctypes.data_as(fp), len(self.xs),
+                                self.ys.ctypes.data_as(fp), len(self.ys), int(types))
+
+
+def haar_params(sizes=(0.2, 0.4), xs=None, ys=None, types=HAAR_ALL, grid=(5, 5)):
+    """HaarFeatureFilter's constructors: explicit centre coordinates xs (ys defaults to xs), or an equidistant grid of grid = (xCount,
+    yCount) points; the defaults are the default constructor's"""
+    return _HaarParams(sizes, xs, ys, types, grid)
+
+
+def haar_grid(count):
+    out = np.empty(max(count, 0), np.float32)
+    if lib().fd_haar_grid(count, _ptr(out)) != FD_OK:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "fd_haar_grid: invalid count %d" % count)
+    return out
+
+
+def haar_feature_count(hp):
+    n = lib().fd_haar_feature_count(C.byref(hp.c) if hp is not None else None)
+    if n < 0:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "HaarFeatureFilter: invalid parameters")
+    return n
+
+
+def haar_features(hp):
+    """the feature table of HaarFeatureFilter::buildFeatures as a HAAR_FEATURE_DTYPE array"""
+    out = np.zeros(haar_feature_count(hp), HAAR_FEATURE_DTYPE)
+    cnt = C.c_int()
+    rc = lib().fd_haar_features(C.byref(hp.c), _ptr(out), len(out), C.byref(cnt))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_haar_features")
+    return out[:cnt.value]
+
+
+def surf_feature_length(gradient_count, cell_count):
+    """length of the fused SURF descriptor, 4 * cell_count^2 (host only); FdError where fd_integral_extract_surf rejects the pair"""
+    n = lib().fd_surf_feature_length(gradient_count, cell_count)
+    if n < 0:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "fd_integral_extract_surf: invalid gradient count %d / cell count %d" % (gradient_count, cell_count))
+    return n
+
+
+def integral_image(ctx, gray):
+    g = _c(gray, np.uint8)
+    out = np.empty((g.shape[0] + 1, g.shape[1] + 1), np.int32)
+    ctx.check(lib().fd_integral_image(ctx.h, _ptr(g), g.shape[1], g.shape[0], _ptr(out)))
+    return out
+
+
+def gradient_sum_batch(ctx, grad2ch, cell_rows, cell_cols=None):
+    """GradientSumFilter on [n, rows, cols, 2] u8 gradient patches -> [n, cell_rows * cell_cols * 4] f32"""
+    g = _c(grad2ch, np.uint8)
+    cell_cols = cell_rows if cell_cols is None else cell_cols
+    n, rows, cols = g.shape[:3]
+    out = np.empty((n, max(cell_rows, 0) * max(cell_cols, 0) * 4), np.float32)
+    ctx.check(lib().fd_gradient_sum_batch(ctx.h, _ptr(g), n, rows, cols, cell_rows, cell_cols, _ptr(out)))
+    return out
+
+
+class Integral:
+    """fd_integral: the integral image of a frame and the patch filters of a DirectImageFeatureExtractor on sampled windows.
+    samples: (n, 4) {x, y, width, height}; every extraction returns (rows, valid bool[n])."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        ctx.check(lib().fd_integral_create(ctx.h, C.byref(self.h)))
+
+    def _check(self, rc):   # fd_integral_update / _download report through the handle's context
+        self.ctx.check(rc)
+
+    def update(self, image):
+        img = _c(image, np.uint8)
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        self._check(lib().fd_integral_update(self.h, _ptr(img), img.shape[1], img.shape[0], ch, 0))
+
+    def update_device(self, dev_ptr, w, h, ch):
+        self._check(lib().fd_integral_update(self.h, C.c_void_p(dev_ptr), w, h, ch, 1))
+
+    def set_image(self, integral):
+        """an integral image made elsewhere ((h + 1) x (w + 1) int32) instead of an update"""
+        I = _c(integral, np.int32)
+        self._check(lib().fd_integral_set_image(self.h, _ptr(I), I.shape[1], I.shape[0]))
+
+    def size(self):
+        w, h = C.c_int(), C.c_int()
+        lib().fd_integral_size(self.h, C.byref(w), C.byref(h))
+        return w.value, h.value
+
+    def download(self):
+        w, h = self.size()
+        out = np.empty((h, w), np.int32)
+        self._check(lib().fd_integral_download(self.h, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _samples(samples):
+        return _c(samples, np.int32).reshape(-1, 4)
+
+    def extract_haar(self, hp, samples, download=True):
+        s = self._samples(samples)
+        feats = np.empty((len(s), haar_feature_count(hp)), np.float32) if download else None
+        valid = np.zeros(len(s), np.uint8) if download else None
+        self.ctx.check(lib().fd_integral_extract_haar(self.ctx.h, self.h, C.byref(hp.c), len(s), _ptr(s), _ptr(feats), _ptr(valid)))
+        return (feats, valid.astype(bool)) if download else None
+
+    def gradient_patches(self, rows, cols, samples):
+        s = self._samples(samples)
+        out = np.empty((len(s), max(rows, 0), max(cols, 0), 2), np.uint8)
+        valid = np.zeros(len(s), np.uint8)
+        self.ctx.check(lib().fd_integral_gradient_patches(self.ctx.h, self.h, rows, cols, len(s), _ptr(s), _ptr(out), _ptr(valid)))
+        return out, valid.astype(bool)
+
+    def extract_surf(self, gradient_count, cell_count, samples, download=True):
+        s = self._samples(samples)
+        feats = np.empty((len(s), 4 * max(cell_count, 0) ** 2), np.float32) if download else None
+        valid = np.zeros(len(s), np.uint8) if download else None
+        self.ctx.check(lib().fd_integral_extract_surf(self.ctx.h, self.h, gradient_count, cell_count, len(s), _ptr(s), _ptr(feats), _ptr(valid)))
+        return (feats, valid.astype(bool)) if download else None
+
+    def svm_evaluate_samples(self, svm, samples, haar=None, surf=None):
+        """condensation::SingleClassifierModel::evaluate: haar = haar_params(...) or surf = (gradient_count, cell_count)
+        -> (target bool[n], weight f64[n])"""
+        s = self._samples(samples)
+        target = np.zeros(len(s), np.uint8)
+        weight = np.zeros(len(s), np.float64)
+        if (haar is None) == (surf is None):
+            raise ValueError("exactly one of haar and surf")
+        if haar is not None:
+            kind, prm = INTEGRAL_HAAR, C.byref(haar.c)
+        else:
+            sp = fd_surf_params(int(surf[0]), int(surf[1]))
+            kind, prm = INTEGRAL_SURF, C.byref(sp)
+        self.ctx.check(lib().fd_integral_svm_evaluate_samples(self.ctx.h, self.h, kind, prm, svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight)))
+        return target.astype(bool), weight
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().fd_integral_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):   # a handle nobody holds any more gives its device memory back (hipFree waits for the device)
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HogSvmRun:

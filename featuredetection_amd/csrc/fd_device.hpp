@@ -1,6 +1,7 @@
 // featuredetection_amd/csrc/fd_device.hpp -- small wave-level device helpers shared by the patch-filter kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 
 namespace fd_dev {
 
@@ -77,6 +78,35 @@ __device__ __forceinline__ void histeq64_wave(const unsigned char* px, unsigned 
     wave_sync();
     for (int i = lane; i < n; i += 64) out[i] = (unsigned char)hist[px[i] >> 2];
     wave_sync();
+}
+
+// cv::cvtColor(BGR2GRAY), 8U: (B*1868 + G*9617 + R*4899 + 8192) >> 14 (GrayscaleFilter.cpp:18-24)
+__device__ __forceinline__ uint32_t gray_of(uint32_t b, uint32_t g, uint32_t r) { return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14; }
+
+// four bytes at any address as one little-endian word
+__device__ __forceinline__ uint32_t ld_u32_unaligned(const uint8_t* p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
+// UnitNormFilter::applyTo (UnitNormFilter.cpp:24-43) of one vector by one wave: s / (cv::norm(s, normType) + 1e-4f); the norm is
+// accumulated in double over the float values like cv::norm.  s may be LDS or global memory, d likewise.
+__device__ __forceinline__ void unit_norm_wave(const float* s, float* d, int len, int normType, int lane) {
+    double part = 0;
+    for (int i = lane; i < len; i += 64) {
+        const double v = (double)s[i];
+        if (normType == 4) part += v * v;             // cv::NORM_L2
+        else if (normType == 2) part += fabs(v);      // cv::NORM_L1
+        else part = fmax(part, fabs(v));              // cv::NORM_INF
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_xor(part, o, 64);
+        part = (normType == 4 || normType == 2) ? part + other : fmax(part, other);
+    }
+    const double norm = normType == 4 ? sqrt(part) : part;
+    const float inv = (float)(1.0 / (norm + (double)1e-4f));   // image / (norm + eps): MatExpr scale 1/d, applied in float
+    for (int i = lane; i < len; i += 64) d[i] = s[i] * inv;
 }
 
 }  // namespace fd_dev

@@ -459,3 +459,11 @@ void fd_host_aggregated_limits(int window_w, int window_h, int cell_size, int oc
                                double& minScale, double& maxScale);
 void fd_host_plan_aggregated(int cell_size, int octave_layer_count, double minScale, double maxScale, int width, int height,
                              FdAggregatedPlan& plan);
+// HaarFeatureFilter's feature table (HaarFeatureFilter.cpp:41-136); false on invalid parameters
+bool fd_host_haar_features(const fd_haar_params* hp, std::vector<fd_haar_feature>& features);
+// limits of the integral-image calls (fd_integral_gradient_length, fd_gradient_sum_length, fd_surf_feature_length in hostalgo.cpp)
+constexpr int FD_GRADIENT_MAX_GRID = 16384;           // rows / cols of a gradient patch: 2 * rows * cols stays an int
+constexpr int FD_SURF_MAX_GRID = 64;                  // gradient_count of the fused SURF kernel
+constexpr size_t FD_SURF_LDS_BUDGET = 160 * 1024;     // LDS of one gfx950 workgroup
+// dynamic LDS of one workgroup of the fused SURF kernel (four wavefronts)
+size_t fd_host_surf_lds_bytes(int gradient_count, int cell_count);

@@ -379,3 +379,132 @@ extern "C" int fd_aggregated_plan_layers(int window_w, int window_h, int cell_si
     for (int i = 0; i < *n; ++i) out[i] = plan.layers[i];
     return FD_OK;
 }
+
+// ---- HaarFeatureFilter's feature table (HaarFeatureFilter.cpp:41-136), host only ---------------------------------------------------
+// Everything is float arithmetic written as the reference writes it (this file is built with -ffp-contract=off): 0.5f * base.width,
+// base.width / 3 (a float division), base.x + 2 * base.width / 3, 255 * 2.f / 3.
+static bool haar_params_ok(const fd_haar_params* hp) {
+    if (!hp || hp->num_sizes < 0 || hp->num_xs < 0 || hp->num_ys < 0 || (hp->types & ~FD_HAAR_ALL)) return false;
+    return (hp->num_sizes == 0 || hp->sizes) && (hp->num_xs == 0 || hp->xs) && (hp->num_ys == 0 || hp->ys);
+}
+
+bool fd_host_haar_features(const fd_haar_params* hp, std::vector<fd_haar_feature>& features) {
+    features.clear();
+    if (!haar_params_ok(hp)) return false;
+    const int types = hp->types;
+    fd_haar_feature feature;
+    std::memset(&feature, 0, sizeof(feature));
+    auto rect = [&](int j, float x, float y, float w, float h, float weight) {
+        feature.rects[j][0] = x; feature.rects[j][1] = y; feature.rects[j][2] = w; feature.rects[j][3] = h;
+        feature.weights[j] = weight;
+    };
+    auto push = [&](int n, float factor) {
+        feature.num_rects = n;
+        feature.factor = factor;
+        for (int j = n; j < 4; ++j) rect(j, 0.f, 0.f, 0.f, 0.f, 0.f);
+        features.push_back(feature);
+    };
+    for (int si = 0; si < hp->num_sizes; ++si) {
+        const float size = hp->sizes[si];
+        for (int yi = 0; yi < hp->num_ys; ++yi) {
+            const float y = hp->ys[yi];
+            for (int xi = 0; xi < hp->num_xs; ++xi) {
+                const float x = hp->xs[xi];
+                struct { float x, y, width, height; } base = {x - size / 2, y - size / 2, size, size};
+                if (base.x < 0.f || base.x + base.width > 1.f || base.y < 0.f || base.y + base.height > 1.f) continue;
+                feature.area = base.width * base.height;
+                if (types & FD_HAAR_2RECTANGLE) {
+                    rect(0, base.x, base.y, 0.5f * base.width, base.height, 1.f);
+                    rect(1, base.x + 0.5f * base.width, base.y, 0.5f * base.width, base.height, -1.f);
+                    push(2, 255 * 1.f / 2);
+                    rect(0, base.x, base.y, base.width, 0.5f * base.height, 1.f);
+                    rect(1, base.x, base.y + 0.5f * base.height, base.width, 0.5f * base.height, -1.f);
+                    push(2, 255 * 1.f / 2);
+                }
+                if (types & FD_HAAR_3RECTANGLE) {
+                    rect(0, base.x, base.y, base.width / 3, base.height, 1.f);
+                    rect(1, base.x + base.width / 3, base.y, base.width / 3, base.height, -2.f);
+                    rect(2, base.x + 2 * base.width / 3, base.y, base.width / 3, base.height, 1.f);
+                    push(3, 255 * 2.f / 3);
+                    rect(0, base.x, base.y, base.width, base.height / 3, 1.f);
+                    rect(1, base.x, base.y + base.height / 3, base.width, base.height / 3, -2.f);
+                    rect(2, base.x, base.y + 2 * base.height / 3, base.width, base.height / 3, 1.f);
+                    push(3, 255 * 2.f / 3);
+                }
+                if (types & FD_HAAR_4RECTANGLE) {
+                    rect(0, base.x, base.y, base.width / 2, base.height / 2, 1.f);
+                    rect(1, base.x + base.width / 2, base.y + base.height / 2, base.width / 2, base.height / 2, 1.f);
+                    rect(2, base.x + base.width / 2, base.y, base.width / 2, base.height / 2, -1.f);
+                    rect(3, base.x, base.y + base.height / 2, base.width / 2, base.height / 2, -1.f);
+                    push(4, 255 * 1.f / 2);
+                }
+                if (types & FD_HAAR_CENTER_SURROUND) {
+                    rect(0, base.x, base.y, base.width, base.height, 1.f);
+                    rect(1, base.x + base.width / 4, base.y + base.height / 4, base.width / 2, base.height / 2, -4.f);
+                    push(2, 255 * 3.f / 4);
+                }
+            }
+        }
+    }
+    // every rectangle edge inside [0, 1] (and finite): what bounds the reads of HaarFeatureFilter::applyTo to the patch plus one row / column
+    for (const fd_haar_feature& f : features)
+        for (int j = 0; j < f.num_rects; ++j) {
+            const float e[4] = {f.rects[j][0], f.rects[j][0] + f.rects[j][2], f.rects[j][1], f.rects[j][1] + f.rects[j][3]};
+            for (float v : e)
+                if (!(v >= 0.f && v <= 1.f)) return false;
+        }
+    return true;
+}
+
+extern "C" int fd_haar_grid(int count, float* coords) {
+    if (count < 0 || (count > 0 && !coords)) return FD_ERR_INVALID_ARGUMENT;
+    const float step = 1.f / (float)((unsigned int)count + 1);
+    for (unsigned int i = 0; i < (unsigned int)count; ++i) coords[i] = (float)(i + 1) * step;
+    return FD_OK;
+}
+
+extern "C" int fd_haar_feature_count(const fd_haar_params* hp) {
+    std::vector<fd_haar_feature> features;
+    return fd_host_haar_features(hp, features) ? (int)features.size() : -1;
+}
+
+extern "C" int fd_haar_features(const fd_haar_params* hp, fd_haar_feature* out, int cap, int* count) {
+    std::vector<fd_haar_feature> features;
+    if (!count || cap < 0 || (cap > 0 && !out) || !fd_host_haar_features(hp, features)) return FD_ERR_INVALID_ARGUMENT;
+    *count = (int)features.size();
+    if (*count > cap) return FD_ERR_CAPACITY;
+    for (int i = 0; i < *count; ++i) out[i] = features[i];
+    return FD_OK;
+}
+
+// ---- argument rules of the integral-image calls (integral.hip), host only: the length of one output, or -1 where the call is an error ----
+// Written with divisions, not products, so that no argument can overflow the rule itself.
+extern "C" int fd_integral_image_length(int width, int height) {
+    if (width < 1 || height < 1) return -1;
+    if (width > (2147483647 / 255) / height) return -1;   // 255 * width * height > 2^31 - 1 (integer: the same as width * height > 8421504)
+    return (width + 1) * (height + 1);
+}
+
+extern "C" int fd_integral_gradient_length(int rows, int cols) {
+    if (rows < 2 || cols < 2 || rows > FD_GRADIENT_MAX_GRID || cols > FD_GRADIENT_MAX_GRID) return -1;
+    return 2 * rows * cols;
+}
+
+extern "C" int fd_gradient_sum_length(int rows, int cols, int cell_rows, int cell_cols) {
+    if (rows < 1 || cols < 1 || cell_rows < 1 || cell_cols < 1 || rows > FD_GRADIENT_MAX_GRID || cols > FD_GRADIENT_MAX_GRID) return -1;
+    if (rows % cell_rows != 0 || cols % cell_cols != 0) return -1;
+    return 4 * cell_rows * cell_cols;
+}
+
+// LDS of one workgroup (four wavefronts) of the fused SURF kernel: per wavefront the gradient patch, G * G uchar2 padded to 16 bytes,
+// and the unnormalised descriptor, 4 C C floats
+size_t fd_host_surf_lds_bytes(int gradient_count, int cell_count) {
+    const size_t grad = ((size_t)gradient_count * gradient_count * 2 + 15) & ~(size_t)15;
+    return 4 * (grad + sizeof(float) * 4 * (size_t)cell_count * cell_count);
+}
+
+extern "C" int fd_surf_feature_length(int gradient_count, int cell_count) {
+    if (gradient_count < 2 || gradient_count > FD_SURF_MAX_GRID || cell_count < 1 || gradient_count % cell_count != 0) return -1;
+    if (fd_host_surf_lds_bytes(gradient_count, cell_count) > FD_SURF_LDS_BUDGET) return -1;
+    return 4 * cell_count * cell_count;
+}

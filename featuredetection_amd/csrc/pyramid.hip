@@ -12,6 +12,7 @@
 // HBM-bound stage: algorithmic bytes = 3WH (BGR read) + WH (gray write) + per layer (src read +
 // dst write); see DESIGN.md.  One launch covers all chains of a pyramid depth (blockIdx.y = chain).
 #include "fd_internal.hpp"
+#include "fd_device.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -100,12 +101,8 @@ __device__ __forceinline__ unsigned int mulhi24(unsigned int a, unsigned int b) 
     return r;
 }
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t ld_u32_unaligned(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__device__ __forceinline__ uint32_t gray_of(uint32_t b, uint32_t g, uint32_t r) { return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14; }
+using fd_dev::gray_of;            // both shared with the integral image (integral.hip)
+using fd_dev::ld_u32_unaligned;
 
 // the frames of a multi-frame pyramid: BGR -> gray (ch == 3) or copy (ch == 1) into frame blockIdx.y's arena.  Four pixels per
 // thread: three dword loads, one dword store (the stage is bound by the number of memory instructions, not by their bytes).

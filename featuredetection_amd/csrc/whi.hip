@@ -260,27 +260,11 @@ __global__ void k_convert(const void* __restrict__ src, int srcF32, void* __rest
     }
 }
 
-// UnitNormFilter::applyTo (UnitNormFilter.cpp:24-43): image / (cv::norm(image, normType) + 1e-4f) per image, one wavefront each;
-// the norm is accumulated in double over the float values like cv::norm
+// UnitNormFilter::applyTo (UnitNormFilter.cpp:24-43): image / (cv::norm(image, normType) + 1e-4f) per image, one wavefront each
+// (fd_dev::unit_norm_wave, shared with the fused SURF kernel of integral.hip)
 __global__ __launch_bounds__(64) void k_unit_norm(const float* __restrict__ src, float* __restrict__ dst, int64_t nimg, int len, int normType) {
     const int lane = threadIdx.x;
-    for (int64_t im = blockIdx.x; im < nimg; im += gridDim.x) {
-        const float* s = src + (size_t)im * len;
-        double part = 0;
-        for (int i = lane; i < len; i += 64) {
-            const double v = (double)s[i];
-            if (normType == 4) part += v * v;             // cv::NORM_L2
-            else if (normType == 2) part += fabs(v);      // cv::NORM_L1
-            else part = fmax(part, fabs(v));              // cv::NORM_INF
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const double other = __shfl_xor(part, o, 64);
-            part = (normType == 4 || normType == 2) ? part + other : fmax(part, other);
-        }
-        const double norm = normType == 4 ? sqrt(part) : part;
-        const float inv = (float)(1.0 / (norm + (double)1e-4f));   // image / (norm + eps): MatExpr scale 1/d, applied in float
-        for (int i = lane; i < len; i += 64) dst[(size_t)im * len + i] = s[i] * inv;
-    }
+    for (int64_t im = blockIdx.x; im < nimg; im += gridDim.x) unit_norm_wave(src + (size_t)im * len, dst + (size_t)im * len, len, normType, lane);
 }
 
 void build_table(const fd_pyramid* p, const fd_whi_params* wp, WhiWinTable& wt, std::vector<WindowLayer>& wls) {

@@ -67,4 +67,25 @@ private:
     std::shared_ptr<classification::ProbabilisticSvmClassifier> svm;
 };
 
+// SingleClassifierModel.hpp:30-69 / SingleClassifierModel.cpp:22-63: one feature extractor, one probabilistic classifier.  The
+// batched evaluate(image, samples) scores all samples with one fd_integral_svm_evaluate_samples when the extractor is a
+// DirectImageFeatureExtractor with the chain of createHaarExtractor or createSurfExtractor (BenchmarkRunner.cpp:202-233,278-286) and
+// the classifier a ProbabilisticSvmClassifier on f32 vectors; any other combination runs the per-sample loop.  (The reference's
+// result cache per patch is not kept: the results are the same.)  getFusedEvaluationCount / getLoopEvaluationCount (not in the
+// reference) tell which of the two ran: the results do not.
+class SingleClassifierModel : public MeasurementModel {
+public:
+    SingleClassifierModel(std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor, std::shared_ptr<classification::ProbabilisticClassifier> classifier);
+    void update(std::shared_ptr<imageprocessing::VersionedImage> image) override;
+    void evaluate(Sample& sample) const override;
+    void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override;
+    // calls of evaluate(image, samples) that scored their samples with one fd_integral_svm_evaluate_samples / with the per-sample loop
+    int getFusedEvaluationCount() const { return fusedEvaluations; }
+    int getLoopEvaluationCount() const { return loopEvaluations; }
+private:
+    std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
+    std::shared_ptr<classification::ProbabilisticClassifier> classifier;
+    int fusedEvaluations = 0, loopEvaluations = 0;
+};
+
 }  // namespace condensation

@@ -25,11 +25,17 @@
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
+#define CV_32SC1 CV_MAKETYPE(CV_32S, 1)
 
 namespace cv {
 enum { NORM_INF = 1, NORM_L1 = 2, NORM_L2 = 4 };
 
 typedef unsigned char uchar;
+struct Vec2b {
+    uchar val[2];
+    uchar& operator[](int i) { return val[i]; }
+    const uchar& operator[](int i) const { return val[i]; }
+};
 
 template <class T> struct Point_ {
     T x, y;

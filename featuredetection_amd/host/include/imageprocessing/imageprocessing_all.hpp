@@ -486,6 +486,116 @@ private:
     std::shared_ptr<ChainedFilter> patchFilter;
 };
 
+// ---- the integral-image family: image filters GrayscaleFilter -> IntegralImageFilter of a DirectImageFeatureExtractor, patch filters
+// that are a handful of rectangle sums (the "haar" and "surf" feature types of BenchmarkRunner.cpp:202-233,278-286)
+// IntegralImageFilter.hpp / IntegralImageFilter.cpp:16-21 (cv::integral): CV_8UC1 -> CV_32SC1, one row and column larger
+// (fd_integral_image).  type: -1 or CV_32S; any other depth throws invalid_argument.
+class IntegralImageFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    explicit IntegralImageFilter(int type = -1);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+private:
+    int type;
+};
+
+// A patch filter that reads a window of an integral image.  applyTo(const Mat&) takes the matrix it is given for the whole integral
+// image (fd_integral_set_image) -- reads past it, such as a Haar rectangle edge at 1.0, throw invalid_argument; a
+// DirectImageFeatureExtractor calls applyToSample with its device-resident integral image instead, where a window's reads may
+// leave the window as long as they stay inside the image (like the reference's ROI header on the parent's memory).
+class IntegralPatchFilter : public ImageFilter {
+public:
+    // false: the sample has no patch, or one of the filter's reads lies outside the integral image
+    virtual bool applyToSample(fd_integral* integral, int x, int y, int width, int height, cv::Mat& filtered) const = 0;
+protected:
+    cv::Mat applyToWhole(const cv::Mat& image, cv::Mat& filtered, const char* name) const;
+};
+
+// HaarFeatureFilter.hpp:22-115 / HaarFeatureFilter.cpp:18-158 (fd_integral_extract_haar on one sample)
+class HaarFeatureFilter : public IntegralPatchFilter {
+public:
+    using ImageFilter::applyTo;
+    static const int TYPE_2RECTANGLE = 1;
+    static const int TYPE_3RECTANGLE = 2;
+    static const int TYPE_4RECTANGLE = 4;
+    static const int TYPE_CENTER_SURROUND = 8;
+    static const int TYPES_ALL = TYPE_2RECTANGLE | TYPE_3RECTANGLE | TYPE_4RECTANGLE | TYPE_CENTER_SURROUND;
+    HaarFeatureFilter();   // all types, sizes 0.2 and 0.4, 5 x 5 grid
+    HaarFeatureFilter(std::vector<float> sizes, unsigned int count, int types = TYPES_ALL);
+    HaarFeatureFilter(std::vector<float> sizes, unsigned int xCount, unsigned int yCount, int types = TYPES_ALL);
+    HaarFeatureFilter(std::vector<float> sizes, std::vector<float> coords, int types = TYPES_ALL);
+    HaarFeatureFilter(std::vector<float> sizes, std::vector<float> xs, std::vector<float> ys, int types = TYPES_ALL);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    bool applyToSample(fd_integral* integral, int x, int y, int width, int height, cv::Mat& filtered) const override;
+    fd_haar_params params() const;   // points into this object
+    int getFeatureCount() const { return featureCount; }
+private:
+    void buildFeatures(std::vector<float> sizes, unsigned int xCount, unsigned int yCount, int types);
+    void buildFeatures(std::vector<float> sizes, std::vector<float> xs, std::vector<float> ys, int types);
+    std::vector<float> sizes, xs, ys;
+    int types = TYPES_ALL, featureCount = 0;
+};
+
+// IntegralGradientFilter.hpp / IntegralGradientFilter.cpp:19-85 (fd_integral_gradient_patches on one sample): CV_32SC1 -> CV_8UC2
+class IntegralGradientFilter : public IntegralPatchFilter {
+public:
+    using ImageFilter::applyTo;
+    IntegralGradientFilter(int rows, int cols) : rows(rows), cols(cols) {}
+    explicit IntegralGradientFilter(int count) : rows(count), cols(count) {}
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    bool applyToSample(fd_integral* integral, int x, int y, int width, int height, cv::Mat& filtered) const override;
+    int getRows() const { return rows; }
+    int getCols() const { return cols; }
+private:
+    int rows, cols;
+};
+
+// GradientSumFilter.hpp / GradientSumFilter.cpp:18-60 (fd_gradient_sum_batch on one patch): CV_8UC2 -> 1 x rows * cols * 4 CV_32FC1
+class GradientSumFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    GradientSumFilter(int rows, int cols) : rows(rows), cols(cols) {}
+    explicit GradientSumFilter(int count) : rows(count), cols(count) {}
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    int getRows() const { return rows; }
+    int getCols() const { return cols; }
+private:
+    int rows, cols;
+};
+
+// DirectImageFeatureExtractor.hpp:25-77 / DirectImageFeatureExtractor.cpp:21-52: patches are windows of the filtered image itself (no
+// pyramid).  With the image filters [GrayscaleFilter, IntegralImageFilter] (or [IntegralImageFilter] on gray images) the integral
+// image is built and kept on the device (fd_integral_update); an IntegralPatchFilter as first patch filter then reads it there,
+// and condensation::SingleClassifierModel scores all samples of a frame in one call for the chains of createHaarExtractor and
+// createSurfExtractor.  Any other filter combination runs per Mat on the host copies, like the reference.  A sample whose patch
+// exists but whose first filter would read outside the integral image has no patch.
+class DirectImageFeatureExtractor : public FeatureExtractor {
+public:
+    using FeatureExtractor::update;
+    DirectImageFeatureExtractor();
+    ~DirectImageFeatureExtractor();
+    DirectImageFeatureExtractor(const DirectImageFeatureExtractor&) = delete;
+    DirectImageFeatureExtractor& operator=(const DirectImageFeatureExtractor&) = delete;
+    void addImageFilter(std::shared_ptr<ImageFilter> filter);
+    void addPatchFilter(std::shared_ptr<ImageFilter> filter) { patchFilter->add(filter); }
+    void update(std::shared_ptr<VersionedImage> image) override;
+    std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override;
+    // the device-resident integral image of the last update; null when the image filters are another chain
+    fd_integral* native() const { return integralChain ? integral : nullptr; }
+    // patch filters == [HaarFeatureFilter]
+    std::shared_ptr<HaarFeatureFilter> getHaarChain() const;
+    // patch filters == [IntegralGradientFilter(g), GradientSumFilter(c), UnitNormFilter(NORM_L2)], both square
+    bool getSurfChain(int& gradientCount, int& cellCount) const;
+private:
+    const cv::Mat& hostImage() const;
+    Version version;
+    mutable cv::Mat image;       // the filtered image (for a device-resident integral image: downloaded when first needed)
+    mutable bool imageOnHost = true;
+    std::shared_ptr<ChainedFilter> imageFilter, patchFilter;
+    bool integralChain = false;
+    fd_integral* integral = nullptr;
+};
+
 // filtering/FhogFilter.hpp:55-56 / FhogFilter.cpp:20-72 (the cell descriptors of the AggregatedFeaturesDetector family)
 namespace filtering {
 class FhogFilter : public ImageFilter {

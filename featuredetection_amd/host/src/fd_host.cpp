@@ -523,6 +523,166 @@ vector<cv::Size> ImagePyramid::getLayerSizes() const {
     return out;
 }
 
+// ---- the integral-image family ---------------------------------------------------------------------------------------------------
+IntegralImageFilter::IntegralImageFilter(int type) : type(type) {
+    if (type != -1 && (type & 7) != CV_32S) throw std::invalid_argument("IntegralImageFilter: this backend computes CV_32S integral images only (type -1 or CV_32S)");
+}
+Mat IntegralImageFilter::applyTo(const Mat& image, Mat& filtered) const {   // cv::integral(image, filtered, CV_32S)
+    if (image.type() != CV_8UC1) throw std::invalid_argument("IntegralImageFilter: the image must be of type CV_8UC1");
+    Mat src = contiguous(image);
+    Mat dst(src.rows + 1, src.cols + 1, CV_32SC1);
+    check(fd_integral_image(context(), src.data, src.cols, src.rows, dst.ptr<int32_t>(0)));
+    filtered = dst;
+    return filtered;
+}
+
+namespace {
+struct IntegralHandle {   // owns a fd_integral for the duration of one stand-alone applyTo
+    fd_integral* g = nullptr;
+    IntegralHandle() { check(fd_integral_create(context(), &g)); }
+    ~IntegralHandle() { fd_integral_destroy(g); }
+};
+}  // namespace
+
+Mat IntegralPatchFilter::applyToWhole(const Mat& image, Mat& filtered, const char* name) const {
+    if (image.type() != CV_32SC1) throw std::invalid_argument(string(name) + ": the image must be of type CV_32SC1");
+    Mat src = contiguous(image);
+    IntegralHandle h;
+    check(fd_integral_set_image(h.g, src.ptr<int32_t>(0), src.cols, src.rows));
+    if (!applyToSample(h.g, src.cols / 2, src.rows / 2, src.cols, src.rows, filtered))
+        throw std::invalid_argument(string(name) + ": the filter reads outside of the given matrix (a window of a larger integral image goes through DirectImageFeatureExtractor)");
+    return filtered;
+}
+
+HaarFeatureFilter::HaarFeatureFilter() {
+    vector<float> s;
+    s.push_back(0.2f);
+    s.push_back(0.4f);
+    buildFeatures(s, 5, 5, TYPES_ALL);
+}
+HaarFeatureFilter::HaarFeatureFilter(vector<float> sizes, unsigned int count, int types) { buildFeatures(sizes, count, count, types); }
+HaarFeatureFilter::HaarFeatureFilter(vector<float> sizes, unsigned int xCount, unsigned int yCount, int types) { buildFeatures(sizes, xCount, yCount, types); }
+HaarFeatureFilter::HaarFeatureFilter(vector<float> sizes, vector<float> coords, int types) { buildFeatures(sizes, coords, coords, types); }
+HaarFeatureFilter::HaarFeatureFilter(vector<float> sizes, vector<float> xs, vector<float> ys, int types) { buildFeatures(sizes, xs, ys, types); }
+void HaarFeatureFilter::buildFeatures(vector<float> sizes, unsigned int xCount, unsigned int yCount, int types) {   // HaarFeatureFilter.cpp:41-51
+    vector<float> gx(xCount), gy(yCount);
+    if (fd_haar_grid((int)xCount, gx.data()) != FD_OK || fd_haar_grid((int)yCount, gy.data()) != FD_OK) throw std::invalid_argument("HaarFeatureFilter: invalid grid size");
+    buildFeatures(sizes, gx, gy, types);
+}
+void HaarFeatureFilter::buildFeatures(vector<float> sizes_, vector<float> xs_, vector<float> ys_, int types_) {
+    sizes = sizes_; xs = xs_; ys = ys_; types = types_;
+    const fd_haar_params hp = params();
+    featureCount = fd_haar_feature_count(&hp);
+    if (featureCount < 0) throw std::invalid_argument("HaarFeatureFilter: invalid parameters (types outside 1|2|4|8, or a rectangle edge outside [0, 1])");
+}
+fd_haar_params HaarFeatureFilter::params() const {
+    fd_haar_params hp;
+    hp.sizes = sizes.data(); hp.num_sizes = (int32_t)sizes.size();
+    hp.xs = xs.data(); hp.num_xs = (int32_t)xs.size();
+    hp.ys = ys.data(); hp.num_ys = (int32_t)ys.size();
+    hp.types = types;
+    return hp;
+}
+Mat HaarFeatureFilter::applyTo(const Mat& image, Mat& filtered) const { return applyToWhole(image, filtered, "HaarFeatureFilter"); }
+bool HaarFeatureFilter::applyToSample(fd_integral* integral, int x, int y, int width, int height, Mat& filtered) const {
+    const int32_t xywh[4] = {x, y, width, height};
+    const fd_haar_params hp = params();
+    Mat dst(1, featureCount, CV_32FC1);
+    uint8_t valid = 0;
+    check(fd_integral_extract_haar(context(), integral, &hp, 1, xywh, dst.ptr<float>(0), &valid));
+    filtered = dst;
+    return valid != 0;
+}
+
+Mat IntegralGradientFilter::applyTo(const Mat& image, Mat& filtered) const { return applyToWhole(image, filtered, "IntegralGradientFilter"); }
+bool IntegralGradientFilter::applyToSample(fd_integral* integral, int x, int y, int width, int height, Mat& filtered) const {
+    const int32_t xywh[4] = {x, y, width, height};
+    Mat dst(std::max(rows, 1), std::max(cols, 1), CV_8UC2);
+    uint8_t valid = 0;
+    check(fd_integral_gradient_patches(context(), integral, rows, cols, 1, xywh, dst.data, &valid));
+    filtered = dst;
+    return valid != 0;
+}
+
+Mat GradientSumFilter::applyTo(const Mat& image, Mat& filtered) const {
+    if (image.type() != CV_8UC2) throw std::invalid_argument("GradientSumFilter: the image must be of type CV_8UC2");
+    Mat src = contiguous(image);
+    Mat dst(1, std::max(rows, 1) * std::max(cols, 1) * 4, CV_32FC1);
+    check(fd_gradient_sum_batch(context(), src.data, 1, src.rows, src.cols, rows, cols, dst.ptr<float>(0)));
+    filtered = dst;
+    return filtered;
+}
+
+DirectImageFeatureExtractor::DirectImageFeatureExtractor() : version(), image(), imageFilter(make_shared<ChainedFilter>()), patchFilter(make_shared<ChainedFilter>()) {}
+DirectImageFeatureExtractor::~DirectImageFeatureExtractor() { if (integral) fd_integral_destroy(integral); }
+void DirectImageFeatureExtractor::addImageFilter(shared_ptr<ImageFilter> filter) {
+    imageFilter->add(filter);
+    const auto& f = imageFilter->getFilters();
+    integralChain = (f.size() == 1 && dynamic_cast<IntegralImageFilter*>(f[0].get())) ||
+                    (f.size() == 2 && dynamic_cast<GrayscaleFilter*>(f[0].get()) && dynamic_cast<IntegralImageFilter*>(f[1].get()));
+    version = Version();   // the filtered image belongs to the previous chain
+}
+void DirectImageFeatureExtractor::update(shared_ptr<VersionedImage> img) {   // DirectImageFeatureExtractor.cpp:35-40
+    if (version == img->getVersion()) return;
+    const Mat& data = img->getData();
+    const bool gray = imageFilter->getFilters().size() == 2;
+    if (integralChain && data.depth() == CV_8U && (data.channels() == 1 || (gray && data.channels() == 3))) {
+        if (!integral) check(fd_integral_create(context(), &integral));
+        Mat src = contiguous(data);
+        check(fd_integral_update(integral, src.data, src.cols, src.rows, src.channels(), 0));
+        image = Mat();
+        imageOnHost = false;
+    } else {
+        if (integralChain) throw std::invalid_argument("IntegralImageFilter: the image must be of type CV_8UC1");
+        imageFilter->applyTo(data, image);
+        imageOnHost = true;
+    }
+    version = img->getVersion();
+}
+const Mat& DirectImageFeatureExtractor::hostImage() const {
+    if (!imageOnHost) {
+        int w = 0, h = 0;
+        check(fd_integral_size(integral, &w, &h));
+        Mat dst(h, w, CV_32SC1);
+        check(fd_integral_download(integral, dst.ptr<int32_t>(0)));
+        image = dst;
+        imageOnHost = true;
+    }
+    return image;
+}
+shared_ptr<Patch> DirectImageFeatureExtractor::extract(int x, int y, int width, int height) const {   // DirectImageFeatureExtractor.cpp:42-52
+    int cols = image.cols, rows = image.rows;
+    if (native()) check(fd_integral_size(integral, &cols, &rows));
+    const int patchBeginX = x - width / 2, patchBeginY = y - height / 2;
+    const int patchEndX = patchBeginX + width, patchEndY = patchBeginY + height;
+    if (width < 1 || height < 1 || patchBeginX < 0 || patchEndX > cols || patchBeginY < 0 || patchEndY > rows) return shared_ptr<Patch>();
+    const auto& filters = patchFilter->getFilters();
+    const IntegralPatchFilter* first = native() && !filters.empty() ? dynamic_cast<const IntegralPatchFilter*>(filters[0].get()) : nullptr;
+    if (first) {
+        Mat data;
+        if (!first->applyToSample(integral, x, y, width, height, data)) return shared_ptr<Patch>();
+        for (size_t i = 1; i < filters.size(); ++i) { Mat tmp; filters[i]->applyTo(data, tmp); data = tmp; }
+        return make_shared<Patch>(x, y, width, height, data);
+    }
+    const Mat data(hostImage(), cv::Rect(patchBeginX, patchBeginY, width, height));
+    return make_shared<Patch>(x, y, width, height, patchFilter->applyTo(data));
+}
+shared_ptr<HaarFeatureFilter> DirectImageFeatureExtractor::getHaarChain() const {
+    const auto& f = patchFilter->getFilters();
+    return f.size() == 1 ? std::dynamic_pointer_cast<HaarFeatureFilter>(f[0]) : nullptr;
+}
+bool DirectImageFeatureExtractor::getSurfChain(int& gradientCount, int& cellCount) const {
+    const auto& f = patchFilter->getFilters();
+    if (f.size() != 3) return false;
+    const auto* g = dynamic_cast<const IntegralGradientFilter*>(f[0].get());
+    const auto* s = dynamic_cast<const GradientSumFilter*>(f[1].get());
+    const auto* u = dynamic_cast<const UnitNormFilter*>(f[2].get());
+    if (!g || !s || !u || u->normType != cv::NORM_L2 || g->getRows() != g->getCols() || s->getRows() != s->getCols()) return false;
+    gradientCount = g->getRows();
+    cellCount = s->getRows();
+    return true;
+}
+
 namespace filtering {
 FhogFilter::FhogFilter(int cellSize, int unsignedBinCount, bool interpolateBins, bool interpolateCells, float alpha)
     : cellSize(cellSize), unsignedBinCount(unsignedBinCount), interpolateBins(interpolateBins), interpolateCells(interpolateCells), alpha(alpha) {
@@ -1906,6 +2066,61 @@ void WvmSvmModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, ve
     vector<double> weight((size_t)n);
     check(fd_wvm_svm_evaluate_samples(context(), direct->getPyramid()->native(), wvm->getWvm()->native(wvm->getLogisticA(), wvm->getLogisticB()),
                                       svm->getSvm()->native(svm->getLogisticA(), svm->getLogisticB()), n, xywh.data(), target.data(), weight.data()));
+    for (int i = 0; i < n; ++i) {
+        samples[i]->setTarget(target[i] != 0);
+        samples[i]->setWeight(weight[i]);
+    }
+}
+
+// SingleClassifierModel.cpp:22-63
+SingleClassifierModel::SingleClassifierModel(shared_ptr<imageprocessing::FeatureExtractor> featureExtractor, shared_ptr<classification::ProbabilisticClassifier> classifier)
+    : featureExtractor(featureExtractor), classifier(classifier) {}
+void SingleClassifierModel::update(shared_ptr<imageprocessing::VersionedImage> image) { featureExtractor->update(image); }
+void SingleClassifierModel::evaluate(Sample& sample) const {
+    auto patch = featureExtractor->extract(sample.getX(), sample.getY(), sample.getWidth(), sample.getHeight());
+    if (patch) {
+        std::pair<bool, double> result = classifier->getProbability(patch->getData());
+        sample.setTarget(result.first);
+        sample.setWeight(result.second);
+    } else {
+        sample.setTarget(false);
+        sample.setWeight(0);
+    }
+}
+void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
+    update(image);
+    auto* direct = dynamic_cast<imageprocessing::DirectImageFeatureExtractor*>(featureExtractor.get());
+    auto* psvm = dynamic_cast<classification::ProbabilisticSvmClassifier*>(classifier.get());
+    shared_ptr<imageprocessing::HaarFeatureFilter> haar;
+    fd_surf_params surf = {0, 0};
+    bool fused = direct && direct->native() && psvm && !psvm->getSvm()->getSupportVectors().empty() &&
+                 psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+    if (fused) {
+        haar = direct->getHaarChain();
+        int g = 0, c = 0;
+        if (!haar && direct->getSurfChain(g, c)) { surf.gradient_count = g; surf.cell_count = c; }
+        fused = haar || surf.gradient_count > 0;
+    }
+    if (!fused) {   // MeasurementModel.hpp: the per-sample loop
+        ++loopEvaluations;
+        for (shared_ptr<Sample> sample : samples) evaluate(*sample);
+        return;
+    }
+    ++fusedEvaluations;
+    const int n = (int)samples.size();
+    if (n == 0) return;
+    vector<int32_t> xywh((size_t)4 * n);
+    for (int i = 0; i < n; ++i) {
+        xywh[4 * i] = samples[i]->getX(); xywh[4 * i + 1] = samples[i]->getY();
+        xywh[4 * i + 2] = samples[i]->getWidth(); xywh[4 * i + 3] = samples[i]->getHeight();
+    }
+    vector<uint8_t> target((size_t)n);
+    vector<double> weight((size_t)n);
+    const fd_svm* svm = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
+    fd_haar_params hp;
+    if (haar) hp = haar->params();
+    check(fd_integral_svm_evaluate_samples(context(), direct->native(), haar ? FD_INTEGRAL_HAAR : FD_INTEGRAL_SURF, haar ? (const void*)&hp : (const void*)&surf, svm, n,
+                                           xywh.data(), target.data(), weight.data()));
     for (int i = 0; i < n; ++i) {
         samples[i]->setTarget(target[i] != 0);
         samples[i]->setWeight(weight[i]);

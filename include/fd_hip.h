@@ -466,6 +466,108 @@ int fd_extract_whi(fd_ctx* ctx, fd_pyramid* p, const fd_whi_params* wp, float* f
 int fd_detect_whi_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_whi_params* wp, fd_detection* out, int64_t cap,
                       int64_t* count, double* all_distance);
 
+/* ---- integral-image features on sampled windows: the "haar" and "surf" feature types of benchmarkApp (BenchmarkRunner.cpp:225-233,
+ * 278-286) and the measurement model of the tracking apps ---------------------------------------------------------------------------
+ * Image filters GrayscaleFilter -> IntegralImageFilter (IntegralImageFilter.cpp:18-21: cv::integral, sdepth CV_32S) of a
+ * DirectImageFeatureExtractor: (height + 1) x (width + 1) int32, first row and column zero, I[y+1][x+1] = sum of gray[v][u] over
+ * v <= y, u <= x.  There is no pyramid: rectangle sums are scale-free.  An image with 255 * width * height > 2^31 - 1 is rejected
+ * with FD_ERR_INVALID_ARGUMENT before its data is touched (the reference's sums would wrap silently). */
+typedef struct fd_integral fd_integral;
+int fd_integral_create(fd_ctx* ctx, fd_integral** out);
+void fd_integral_destroy(fd_integral* g);
+/* DirectImageFeatureExtractor::update (DirectImageFeatureExtractor.cpp:35-40).  channels 1 (gray) or 3 (BGR, interleaved; the
+ * pyramid's BGR -> gray arithmetic); is_device != 0: image already resident in HBM. */
+int fd_integral_update(fd_integral* g, const uint8_t* image, int width, int height, int channels, int is_device);
+/* an integral image made elsewhere (host, width x height int32, CV_32SC1) instead of an update: what the stand-alone
+ * HaarFeatureFilter / IntegralGradientFilter::applyTo(const Mat&) of the host layer are given */
+int fd_integral_set_image(fd_integral* g, const int32_t* integral, int width, int height);
+/* size of the integral image (image width + 1, image height + 1); 0, 0 before the first update */
+int fd_integral_size(const fd_integral* g, int* width, int* height);
+/* copy the integral image to host: (height + 1) * (width + 1) int32 */
+int fd_integral_download(fd_integral* g, int32_t* host_dst);
+/* IntegralImageFilter::applyTo on a CV_8UC1 host image: (height + 1) * (width + 1) int32 to host */
+int fd_integral_image(fd_ctx* ctx, const uint8_t* gray, int width, int height, int32_t* dst);
+
+/* Sample windows.  Every extraction call below takes n samples xywh[n][4] = {x, y, width, height} (Sample::getX / getY / getWidth /
+ * getHeight) and follows DirectImageFeatureExtractor::extract (DirectImageFeatureExtractor.cpp:42-52) on the integral image: the
+ * patch origin is (x - width / 2, y - height / 2) (integer division), and the patch exists iff it lies inside the integral image
+ * (and width, height >= 1).  valid[n] receives 1 for every sample whose patch exists and whose filter reads all lie inside the
+ * integral image, else 0; the output rows of the other samples are zero.  features / dst2ch and valid may be NULL: the results
+ * then stay on the device only (what fd_integral_svm_evaluate_samples consumes). */
+
+/* HaarFeatureFilter (HaarFeatureFilter.hpp:24-32, HaarFeatureFilter.cpp:18-158).  types: bit mask of FD_HAAR_*. */
+enum { FD_HAAR_2RECTANGLE = 1, FD_HAAR_3RECTANGLE = 2, FD_HAAR_4RECTANGLE = 4, FD_HAAR_CENTER_SURROUND = 8, FD_HAAR_ALL = 15 };
+typedef struct {
+    const float* sizes;   /* feature sizes relative to the patch */
+    int32_t num_sizes;
+    const float* xs;      /* grid coordinates of the feature centres, relative to the patch */
+    int32_t num_xs;
+    const float* ys;
+    int32_t num_ys;
+    int32_t types;
+} fd_haar_params;
+typedef struct {
+    float rects[4][4];    /* cv::Rect_<float>: x, y, width, height, relative to the patch */
+    float weights[4];
+    int32_t num_rects;
+    float factor, area;
+} fd_haar_feature;
+/* Host only (no context, no device).  fd_haar_grid: the equidistant grid of the (sizes, count, types) constructors, coords[i] =
+ * (i + 1) * (1.f / (count + 1)) (HaarFeatureFilter.cpp:41-51).  fd_haar_feature_count: number of features buildFeatures
+ * (:53-136) makes, -1 on invalid parameters (NULL, a negative count, types outside the mask, a rectangle edge outside [0, 1] or not
+ * finite).  fd_haar_features: that feature table, built in float with the reference's expressions and order; FD_ERR_CAPACITY when
+ * cap is too small (*count is set). */
+int fd_haar_grid(int count, float* coords);
+int fd_haar_feature_count(const fd_haar_params* hp);
+int fd_haar_features(const fd_haar_params* hp, fd_haar_feature* out, int cap, int* count);
+/* HaarFeatureFilter::applyTo (:138-158) per sample: n x fd_haar_feature_count floats.  Corners are cvRound(float product) of the
+ * relative coordinates and the patch size, sums are int32, value += weight * (float)sum per rectangle, then
+ * value / (factor * area * cols * rows), all in float.  One deviation: a rectangle edge at 1.0 reads column `cols` / row `rows` of
+ * the patch, one past the ROI; where that leaves the integral image (a patch flush with its last column or row; the reference
+ * reads out of the row there) the sample is invalid. */
+int fd_integral_extract_haar(fd_ctx* ctx, fd_integral* g, const fd_haar_params* hp, int n, const int32_t* xywh, float* features,
+                             uint8_t* valid);
+/* IntegralGradientFilter(rows, cols)::applyTo (IntegralGradientFilter.cpp:23-85) per sample: rows x cols CV_8UC2 (dx + 127,
+ * dy + 127) from twelve reads around each grid point; radii, spacings and offsets in double with cvRound, integer divisions
+ * truncating.  2 <= rows, cols <= 16384 (below 2 the reference divides by zero).  With patch width and height >= 4 all reads stay inside
+ * the patch; for smaller patches they may leave it, and the rule above decides. */
+int fd_integral_gradient_patches(fd_ctx* ctx, fd_integral* g, int rows, int cols, int n, const int32_t* xywh, uint8_t* dst2ch,
+                                 uint8_t* valid);
+/* GradientSumFilter(cell_rows, cell_cols)::applyTo (GradientSumFilter.cpp:22-60) on n contiguous CV_8UC2 host patches of rows x
+ * cols pixels: per cell (sum dx, sum dy, sum |dx|, sum |dy|) with dx = (1.f / 127.f) * (g - 127), summed in the reference's
+ * order; n x cell_rows * cell_cols * 4 floats to host.  rows % cell_rows != 0 or cols % cell_cols != 0: FD_ERR_INVALID_ARGUMENT. */
+int fd_gradient_sum_batch(fd_ctx* ctx, const uint8_t* grad2ch, int64_t n, int rows, int cols, int cell_rows, int cell_cols, float* dst);
+/* The SURF-like descriptor of createSurfExtractor (BenchmarkRunner.cpp:278-286): IntegralGradientFilter(gradient_count) ->
+ * GradientSumFilter(cell_count) -> UnitNormFilter(NORM_L2) in one launch (the gradient patch never goes to memory):
+ * n x 4 * cell_count^2 floats, identical to the three stand-alone calls in a row.  2 <= gradient_count <= 64, divisible by
+ * cell_count, and the patch and the descriptor of four samples must fit the 160 KB of LDS of a workgroup:
+ * 4 * (2 * gradient_count^2 rounded up to 16 + 16 * cell_count^2) <= 163840 bytes.  That admits every cell_count <= 32 and, with
+ * cell_count == gradient_count, up to 47; (48, 48), (56, 56) and (64, 64) are FD_ERR_INVALID_ARGUMENT (the stand-alone calls have
+ * no such limit). */
+int fd_integral_extract_surf(fd_ctx* ctx, fd_integral* g, int gradient_count, int cell_count, int n, const int32_t* xywh,
+                             float* features, uint8_t* valid);
+/* condensation::SingleClassifierModel::evaluate (SingleClassifierModel.cpp:32-52) with a ProbabilisticSvmClassifier on f32 vectors:
+ * kind FD_INTEGRAL_HAAR (params: const fd_haar_params*) or FD_INTEGRAL_SURF (params: const fd_surf_params*).  The features stay on
+ * the device and are scored by the kernel of fd_svm_distance_batch; target = distance >= threshold, weight = the logistic
+ * probability; samples without a (valid) patch get target 0, weight 0.  FD_ERR_INVALID_ARGUMENT when the feature length differs
+ * from the SVM's dimension. */
+enum { FD_INTEGRAL_HAAR = 0, FD_INTEGRAL_SURF = 1 };
+typedef struct {
+    int32_t gradient_count, cell_count;
+} fd_surf_params;
+int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, const void* params, const fd_svm* svm, int n,
+                                     const int32_t* xywh, uint8_t* target, double* weight);
+/* Host only (no context, no device): the argument rules of the calls above, which use these very functions.  Each returns the
+ * length of one output, or -1 where the call returns FD_ERR_INVALID_ARGUMENT.  fd_integral_image_length: (width + 1) * (height + 1)
+ * ints; -1 for a size below 1 or 255 * width * height > 2^31 - 1.  fd_integral_gradient_length: 2 * rows * cols bytes per sample;
+ * -1 unless 2 <= rows, cols <= 16384.  fd_gradient_sum_length: 4 * cell_rows * cell_cols floats per patch; -1 for the two
+ * divisibility errors of GradientSumFilter.cpp:25-28, a count below 1 or rows, cols > 16384.  fd_surf_feature_length:
+ * 4 * cell_count^2 floats per sample; -1 by the rules of fd_integral_extract_surf. */
+int fd_integral_image_length(int width, int height);
+int fd_integral_gradient_length(int rows, int cols);
+int fd_gradient_sum_length(int rows, int cols, int cell_rows, int cell_cols);
+int fd_surf_feature_length(int gradient_count, int cell_count);
+
 /* ---- classification::RvmClassifier / ProbabilisticRvmClassifier -----------------
  * Cascaded reduced-vector machine (RvmClassifier.cpp:75-126): level k evaluates kernel(x, rsv_k) on the whole
  * vector; through the reference's cached path the running distance is d_0 = -bias + c[0][0] K_0,
