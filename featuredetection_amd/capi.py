@@ -83,6 +83,21 @@ class fd_fhog_params(C.Structure):
                 ("alpha", C.c_float)]
 
 
+class fd_cehog_params(C.Structure):
+    _fields_ = [("cell_size", C.c_int32), ("bin_count", C.c_int32), ("signed_gradients", C.c_int32), ("unsigned_gradients", C.c_int32),
+                ("interpolate_bins", C.c_int32), ("interpolate_cells", C.c_int32), ("alpha", C.c_float)]
+
+
+class fd_ehog_tracker_params(C.Structure):
+    _fields_ = [("filter", fd_cehog_params), ("cell_cols", C.c_int32), ("cell_rows", C.c_int32), ("octave_layer_count", C.c_int32),
+                ("min_width", C.c_int32), ("max_width", C.c_int32)]
+
+
+class fd_ehog_patch_params(C.Structure):
+    _fields_ = [("patch_w", C.c_int32), ("patch_h", C.c_int32), ("bins", C.c_int32), ("cell_w", C.c_int32), ("cell_h", C.c_int32),
+                ("interpolate", C.c_int32), ("signed_and_unsigned", C.c_int32), ("alpha", C.c_float)]
+
+
 class fd_fpdw_params(C.Structure):
     _fields_ = [("cell_size", C.c_int32), ("fast_gradient", C.c_int32), ("interpolate", C.c_int32), ("normalization_radius", C.c_int32),
                 ("normalization_constant", C.c_float)]
@@ -209,6 +224,26 @@ _SIGS = {
     "fd_fhog_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_fhog_params), C.c_void_p]),
     "fd_fhog_image_channels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fd_fhog_params), C.c_void_p]),
     "fd_pyramid_fhog_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_fhog_params), C.c_void_p]),
+    "fd_cehog_size": (C.c_int, [C.POINTER(fd_cehog_params), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_cehog_gradient_lut": (C.c_int, [C.POINTER(fd_cehog_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_cehog_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_cehog_params), C.c_void_p]),
+    "fd_pyramid_cehog_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_cehog_params), C.c_void_p]),
+    "fd_ehog_feature_length": (C.c_int, [C.POINTER(fd_ehog_patch_params), C.c_int]),
+    "fd_ehog_patch_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(fd_ehog_patch_params), C.c_void_p]),
+    "fd_ehog_tracker_plan_layers": (C.c_int, [C.POINTER(fd_ehog_tracker_params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_ehog_tracker_create": (C.c_int, [C.c_void_p, C.POINTER(fd_ehog_tracker_params), C.POINTER(C.c_void_p)]),
+    "fd_ehog_tracker_destroy": (None, [C.c_void_p]),
+    "fd_ehog_tracker_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fd_ehog_tracker_set_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
+    "fd_ehog_tracker_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_ehog_tracker_extract_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_ehog_tracker_extract_patches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_ehog_tracker_patch_lds_bytes": (C.c_int, [C.POINTER(fd_ehog_tracker_params)]),
+    "fd_ehog_tracker_heat_peak": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "fd_ehog_tracker_heat_maxima": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_ehog_tracker_get_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_ehog_tracker_feature_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fd_ehog_tracker_heat_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -887,6 +922,198 @@ def fhog(ctx, gray=None, pyramid=None, layer=0, cell_size=8, unsigned_bins=9, in
     else:
         ctx.check(lib().fd_pyramid_fhog_layer(ctx.h, pyramid.h, layer, C.byref(fp), _ptr(out)))
     return out
+
+
+def cehog_params(cell_size=8, bin_count=18, signed_gradients=True, unsigned_gradients=True, interpolate_bins=False, interpolate_cells=True,
+                 alpha=0.2):
+    """fd_cehog_params with CompleteExtendedHogFilter's defaults"""
+    return fd_cehog_params(cell_size, bin_count, int(signed_gradients), int(unsigned_gradients), int(interpolate_bins), int(interpolate_cells),
+                           alpha)
+
+
+def cehog_size(fp, width, height):
+    """fd_cehog_size (host only): (rows, cols, channels); FdError for invalid parameters"""
+    r, c, d = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fd_cehog_size(C.byref(fp), width, height, C.byref(r), C.byref(c), C.byref(d))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_cehog_size: invalid CompleteExtendedHogFilter parameters or image size")
+    return r.value, c.value, d.value
+
+
+def cehog_gradient_lut(fp):
+    """fd_cehog_gradient_lut (host only): index1, index2 (int32), weight1, weight2 (float32), each (512, 512) indexed [dx + 256, dy + 256]"""
+    i1, i2 = np.zeros((512, 512), np.int32), np.zeros((512, 512), np.int32)
+    w1, w2 = np.zeros((512, 512), np.float32), np.zeros((512, 512), np.float32)
+    rc = lib().fd_cehog_gradient_lut(C.byref(fp), _ptr(i1), _ptr(i2), _ptr(w1), _ptr(w2))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_cehog_gradient_lut: invalid CompleteExtendedHogFilter parameters")
+    return i1, i2, w1, w2
+
+
+def cehog_image(ctx, fp, gray=None, pyramid=None, layer=0):
+    """CompleteExtendedHogFilter::applyTo on a host gray (h, w) image or on a layer of a gray pyramid: (rows, cols, channels) float32"""
+    if gray is not None:
+        gray = _c(gray, np.uint8)
+        h, w = gray.shape[:2]
+    else:
+        info = pyramid.layers()[layer]
+        h, w = info["h"], info["w"]
+    cs = max(fp.cell_size, 1)   # invalid parameters are reported by the library
+    both = fp.signed_gradients and fp.unsigned_gradients
+    out = np.zeros((h // cs, w // cs, max(fp.bin_count + (fp.bin_count // 2 if both else 0) + 4, 0)), np.float32)
+    if gray is not None:
+        ctx.check(lib().fd_cehog_image(ctx.h, _ptr(gray), w, h, C.byref(fp), _ptr(out)))
+    else:
+        ctx.check(lib().fd_pyramid_cehog_layer(ctx.h, pyramid.h, layer, C.byref(fp), _ptr(out)))
+    return out
+
+
+def ehog_patch_params(pw, ph, bins=9, cell_w=5, cell_h=0, interpolate=False, signed_and_unsigned=False, alpha=0.2):
+    return fd_ehog_patch_params(pw, ph, bins, cell_w, cell_h, int(interpolate), int(signed_and_unsigned), alpha)
+
+
+def ehog_feature_length(ep, channels):
+    return lib().fd_ehog_feature_length(C.byref(ep), channels)
+
+
+def ehog_patch_batch(ctx, bin_patches, ep):
+    """ExtendedHogFilter on bin_patches [n, ph, pw, channels] u8 (or [n, ph, pw]): [n, rows, cols, bins (+ bins / 2) + 4] f32"""
+    b = _c(bin_patches, np.uint8)
+    ch = b.shape[3] if b.ndim == 4 else 1
+    F = lib().fd_ehog_feature_length(C.byref(ep), ch)
+    if F < 0:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "invalid extended HOG parameters")
+    D = ep.bins + (ep.bins // 2 if ep.signed_and_unsigned else 0) + 4
+    cells = F // D
+    out = np.zeros((b.shape[0], F), np.float32)
+    ctx.check(lib().fd_ehog_patch_batch(ctx.h, _ptr(b), b.shape[0], ch, C.byref(ep), _ptr(out)))
+    return out.reshape(b.shape[0], cells, D)
+
+
+# fd_ehog_layer: one layer of an extended-HOG tracker
+EHOG_LAYER_DTYPE = np.dtype([("index", "<i4"), ("width", "<i4"), ("height", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("reserved", "<i4"),
+                             ("scale", "<f8")], align=True)
+
+
+def ehog_tracker_params(fp, cell_cols, cell_rows, octave_layers, min_width, max_width):
+    return fd_ehog_tracker_params(fp, cell_cols, cell_rows, octave_layers, min_width, max_width)
+
+
+def ehog_tracker_plan_layers(prm, width, height):
+    """fd_ehog_tracker_plan_layers (host only): the layers of a tracker on a width x height image as an EHOG_LAYER_DTYPE array;
+    FdError (FD_ERR_RUNTIME) when fewer than two layers remain"""
+    out = np.zeros(256, EHOG_LAYER_DTYPE)
+    n = C.c_int()
+    rc = lib().fd_ehog_tracker_plan_layers(C.byref(prm), width, height, _ptr(out), len(out), C.byref(n))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_ehog_tracker_plan_layers: %d layers" % n.value)
+    return out[:n.value].copy()
+
+
+def ehog_tracker_patch_lds_bytes(prm):
+    return lib().fd_ehog_tracker_patch_lds_bytes(C.byref(prm))
+
+
+class EhogTracker:
+    """fd_ehog_tracker: feature pyramid, heat pyramid, samples, patches, peak and maxima of ExtendedHogBasedMeasurementModel"""
+
+    def __init__(self, ctx, prm):
+        self.ctx = ctx
+        self.prm = prm
+        both = prm.filter.signed_gradients and prm.filter.unsigned_gradients
+        self.channels = prm.filter.bin_count + (prm.filter.bin_count // 2 if both else 0) + 4
+        self.h = C.c_void_p()
+        ctx.check(lib().fd_ehog_tracker_create(ctx.h, C.byref(prm), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().fd_ehog_tracker_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, image):
+        image = _c(image, np.uint8)
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        self.ctx.check(lib().fd_ehog_tracker_update(self.ctx.h, self.h, _ptr(image), w, h, ch, 0))
+
+    def update_device(self, dev_ptr, w, h, ch):
+        self.ctx.check(lib().fd_ehog_tracker_update(self.ctx.h, self.h, C.c_void_p(dev_ptr), w, h, ch, 1))
+
+    def set_svm(self, weights, bias):
+        weights = _c(weights, np.float32)
+        if weights.size != self.prm.cell_rows * self.prm.cell_cols * self.channels:
+            raise ValueError("weights must be [cell_rows][cell_cols][channels]")
+        self.ctx.check(lib().fd_ehog_tracker_set_svm(self.ctx.h, self.h, _ptr(weights), bias))
+
+    def layers(self):
+        out = np.zeros(256, EHOG_LAYER_DTYPE)
+        n = C.c_int()
+        self.ctx.check(lib().fd_ehog_tracker_get_layers(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def feature_layer(self, layer):
+        ls = self.layers()   # a layer that does not exist is reported by the library
+        shape = (ls[layer]["rows"], ls[layer]["cols"], self.channels) if 0 <= layer < len(ls) else (1, 1, self.channels)
+        out = np.zeros(shape, np.float32)
+        self.ctx.check(lib().fd_ehog_tracker_feature_layer(self.ctx.h, self.h, layer, _ptr(out)))
+        return out
+
+    def heat_layer(self, layer):
+        n = len(self.layers())
+        shape = (self.layers()[layer]["rows"], self.layers()[layer]["cols"]) if 0 <= layer < n else (1, 1)
+        out = np.zeros(shape, np.float32)
+        self.ctx.check(lib().fd_ehog_tracker_heat_layer(self.ctx.h, self.h, layer, _ptr(out)))
+        return out
+
+    def _samples(self, xywh):
+        xywh = _c(np.asarray(xywh, np.int32).reshape(-1, 4), np.int32)
+        return xywh, np.zeros(len(xywh), np.uint8)
+
+    def evaluate_samples(self, xywh):
+        """(valid uint8 (n,), score float32 (n,)) of samples {x, y, width, height}"""
+        xywh, valid = self._samples(xywh)
+        score = np.zeros(len(xywh), np.float32)
+        self.ctx.check(lib().fd_ehog_tracker_evaluate_samples(self.ctx.h, self.h, len(xywh), _ptr(xywh), _ptr(valid), _ptr(score)))
+        return valid, score
+
+    def extract_cells(self, xywh):
+        """(valid, features float32 (n, cell_rows, cell_cols, channels))"""
+        xywh, valid = self._samples(xywh)
+        feat = np.zeros((len(xywh), self.prm.cell_rows, self.prm.cell_cols, self.channels), np.float32)
+        self.ctx.check(lib().fd_ehog_tracker_extract_cells(self.ctx.h, self.h, len(xywh), _ptr(xywh), _ptr(valid), _ptr(feat)))
+        return valid, feat
+
+    def extract_patches(self, xywh, want_score=False):
+        """(valid, features) or (valid, features, score float64 (n,))"""
+        xywh, valid = self._samples(xywh)
+        feat = np.zeros((len(xywh), self.prm.cell_rows, self.prm.cell_cols, self.channels), np.float32)
+        score = np.zeros(len(xywh), np.float64) if want_score else None
+        self.ctx.check(lib().fd_ehog_tracker_extract_patches(self.ctx.h, self.h, len(xywh), _ptr(xywh), _ptr(valid), _ptr(feat), _ptr(score)))
+        return (valid, feat, score) if want_score else (valid, feat)
+
+    def heat_peak(self):
+        """(found, BOX_DTYPE record): getHeatPeak"""
+        box = np.zeros(1, BOX_DTYPE)
+        found = C.c_int()
+        self.ctx.check(lib().fd_ehog_tracker_heat_peak(self.ctx.h, self.h, _ptr(box), C.byref(found)))
+        return bool(found.value), box[0]
+
+    def heat_maxima(self, threshold, cap=4096):
+        """BOX_DTYPE array of the local maxima above threshold, scan order; FdError FD_ERR_CAPACITY (with .count) when cap is too small"""
+        out = np.zeros(max(cap, 1), BOX_DTYPE)
+        n = C.c_int()
+        rc = lib().fd_ehog_tracker_heat_maxima(self.ctx.h, self.h, threshold, _ptr(out), cap, C.byref(n))
+        if rc != FD_OK:
+            e = FdError(rc, lib().fd_last_error(self.ctx.h).decode())
+            e.count = n.value
+            raise e
+        return out[:n.value].copy()
 
 
 # fd_aggregated_layer: one feature layer of an aggregated-features detector

@@ -13,6 +13,7 @@
 #include "fd_internal.hpp"
 #include "fd_device.hpp"
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -30,6 +31,7 @@ struct FhogCoeffDev { int32_t index1, index2; float weight1, weight2; };
 
 struct FhogParamsDev {
     int32_t cell, ubins, sbins, D, interpBins, interpCells;
+    int32_t plainEnergy;           // k_fhog_hist: energy over the sbins bins themselves (CompleteExtendedHogFilter, unsigned only)
     float alpha;
     const FhogLutEntry* lut;       // [512 * 512], index dy * 512 + dx
     const FhogCoeffDev* coeff;     // all layers: rows of layer 0, columns of layer 0, rows of layer 1, ...
@@ -232,9 +234,13 @@ __global__ __launch_bounds__(64) void k_fhog_hist(const FhogLayerDev* __restrict
             }
         }
         float energy = 0.f;   // computeGradientEnergy, FhogAggregationFilter.cpp:53-61
-        for (int b = 0; b < d.ubins; ++b) {
-            const float u = hist[b][lane] + hist[b + d.ubins][lane];
-            energy = energy + u * u;
+        if (d.plainEnergy) {  // CompleteExtendedHogFilter.cpp:181-190
+            for (int b = 0; b < d.sbins; ++b) energy = energy + hist[b][lane] * hist[b][lane];
+        } else {
+            for (int b = 0; b < d.ubins; ++b) {
+                const float u = hist[b][lane] + hist[b + d.ubins][lane];
+                energy = energy + u * u;
+            }
         }
         energies[L.cellBase + cellId] = energy;
     }
@@ -1029,3 +1035,6 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
 }
 
 }  // extern "C"
+
+#include "cehog.hpp"
+#include "ehog_tracker.hpp"

@@ -1118,3 +1118,5 @@ int fd_detect_hist_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_h
 }
 
 }  // extern "C"
+
+#include "ehog_patch.hpp"

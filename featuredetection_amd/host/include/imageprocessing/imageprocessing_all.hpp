@@ -190,6 +190,38 @@ public:
     bool interpolate, signedAndUnsigned;
 };
 
+// ExtendedHogFilter.hpp:45-57 / ExtendedHogFilter.cpp:14-209 (fd_ehog_patch_batch on one patch): bin image -> rows x cols cells of
+// binCount (+ binCount / 2 with signedAndUnsigned) + 4 floats, stored as rows x cols * channels CV_32F.  Per patch only (applyTo, a
+// FilteringFeatureExtractor): it is not part of a fused pyramid chain.
+class ExtendedHogFilter : public HistogramFilter {
+public:
+    using ImageFilter::applyTo;
+    ExtendedHogFilter(int binCount, int cellSize, bool interpolate, bool signedAndUnsigned, float alpha = 0.2f);
+    ExtendedHogFilter(int binCount, int cellWidth, int cellHeight, bool interpolate, bool signedAndUnsigned, float alpha = 0.2f);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    int getCellWidth() { return cellWidth; }
+    int getCellHeight() { return cellHeight; }
+    int binCount, cellWidth, cellHeight;
+    bool interpolate, signedAndUnsigned;
+    float alpha;
+};
+
+// CompleteExtendedHogFilter.hpp:35-117 / CompleteExtendedHogFilter.cpp:19-303 (fd_cehog_image): CV_8UC1 -> rows x cols cells of
+// binCount (+ binCount / 2 when both gradient kinds are set) + 4 floats, stored as rows x cols * channels CV_32F
+class CompleteExtendedHogFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    explicit CompleteExtendedHogFilter(size_t cellSize = 8, size_t binCount = 18, bool signedGradients = true, bool unsignedGradients = true,
+                                       bool interpolateBins = false, bool interpolateCells = true, float alpha = 0.2f);
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+    size_t getCellSize() { return cellSize; }
+    fd_cehog_params params() const;
+    size_t getDescriptorSize() const { return binCount + (signedGradients && unsignedGradients ? binCount / 2 : 0) + 4; }
+    size_t cellSize, binCount;
+    bool signedGradients, unsignedGradients, interpolateBins, interpolateCells;
+    float alpha;
+};
+
 // SpatialHistogramFilter.hpp:38-54 / SpatialHistogramFilter.cpp:16-54
 class SpatialHistogramFilter : public HistogramFilter {
 public:
@@ -345,6 +377,10 @@ public:
     int getY() const { return center.y; }
     int getWidth() const { return size.width; }
     int getHeight() const { return size.height; }
+    void setX(int x) { center.x = x; }
+    void setY(int y) { center.y = y; }
+    void setWidth(int width) { size.width = width; }
+    void setHeight(int height) { size.height = height; }
     cv::Mat& getData() { return data; }
     const cv::Mat& getData() const { return data; }
 private:
@@ -484,6 +520,71 @@ public:
 private:
     std::shared_ptr<FeatureExtractor> extractor;
     std::shared_ptr<ChainedFilter> patchFilter;
+};
+
+// ExtendedHogFeatureExtractor.hpp / ExtendedHogFeatureExtractor.cpp:32-143 in its stand-alone form (:76-84: a CompleteExtendedHogFilter on a
+// gray pyramid of its own, createPyramid) on one fd_ehog_tracker.  extract() is ExtendedHogFeatureExtractor::extract (:95-130): the patch
+// widened by (cells + 2) / cells, up to one cell outside the layer (mirrored), the inner cells returned (rows x cols * channels CV_32F).
+class ExtendedHogFeatureExtractor : public FeatureExtractor {
+public:
+    using FeatureExtractor::update;
+    ExtendedHogFeatureExtractor(std::shared_ptr<CompleteExtendedHogFilter> ehogFilter, int cols, int rows, int minWidth, int maxWidth,
+                                int octaveLayerCount = 5);
+    ~ExtendedHogFeatureExtractor();
+    ExtendedHogFeatureExtractor(const ExtendedHogFeatureExtractor&) = delete;
+    ExtendedHogFeatureExtractor& operator=(const ExtendedHogFeatureExtractor&) = delete;
+    void update(std::shared_ptr<VersionedImage> image) override;
+    std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override;
+    int getPatchWidth() const { return patchWidth; }
+    int getPatchHeight() const { return patchHeight; }
+    int getCols() const { return cols; }
+    int getRows() const { return rows; }
+    int getCellSize() const { return cellSize; }
+    int getChannels() const { return channels; }
+    int getOctaveLayerCount() const { return octaveLayerCount; }
+    fd_ehog_tracker* native() const { return tracker; }   // feature pyramid, heat pyramid and sample calls of the same frame
+private:
+    fd_ehog_tracker* tracker;
+    int cols, rows, cellSize, channels, patchWidth, patchHeight, octaveLayerCount;
+    double widthFactor, heightFactor;
+};
+
+// CellBasedPyramidFeatureExtractor.hpp / CellBasedPyramidFeatureExtractor.cpp:37-78 on the feature pyramid an ExtendedHogFeatureExtractor's
+// handle builds (on this backend the pyramid with the CompleteExtendedHogFilter layer filter lives inside the handle, so the extractor is
+// constructed from the ExtendedHogFeatureExtractor it shares the gray pyramid with, as the measurement model wires them, instead of
+// from an ImagePyramid): extract() returns windows of cols x rows cells (DirectPyramidFeatureExtractor.cpp:67-73,133-143).
+class CellBasedPyramidFeatureExtractor : public FeatureExtractor {
+public:
+    using FeatureExtractor::update;
+    explicit CellBasedPyramidFeatureExtractor(std::shared_ptr<ExtendedHogFeatureExtractor> base);
+    void update(std::shared_ptr<VersionedImage> image) override { base->update(image); }
+    std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override;
+private:
+    std::shared_ptr<ExtendedHogFeatureExtractor> base;
+};
+
+// PatchResizingFeatureExtractor.hpp:21-60 (the `scale` key of createFeatureExtractor): asks the underlying extractor for a patch of
+// another size and position and reports the patch with the size and position that were asked for
+class PatchResizingFeatureExtractor : public FeatureExtractor {
+public:
+    using FeatureExtractor::update;
+    PatchResizingFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor, double factor, double yOffset = 0, double xOffset = 0)
+        : extractor(extractor), factor(factor), yOffset(yOffset), xOffset(xOffset) {}
+    void update(std::shared_ptr<VersionedImage> image) override { extractor->update(image); }
+    std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override {
+        std::shared_ptr<Patch> patch = extractor->extract(cv::cvRound(x + xOffset * width), cv::cvRound(y + yOffset * height), cv::cvRound(factor * width),
+                                                          cv::cvRound(factor * height));
+        if (patch) {
+            patch->setWidth(cv::cvRound(patch->getWidth() / factor));
+            patch->setHeight(cv::cvRound(patch->getHeight() / factor));
+            patch->setX(cv::cvRound(patch->getX() - xOffset * patch->getWidth()));
+            patch->setY(cv::cvRound(patch->getY() - yOffset * patch->getHeight()));
+        }
+        return patch;
+    }
+private:
+    std::shared_ptr<FeatureExtractor> extractor;
+    double factor, yOffset, xOffset;
 };
 
 // ---- the integral-image family: image filters GrayscaleFilter -> IntegralImageFilter of a DirectImageFeatureExtractor, patch filters

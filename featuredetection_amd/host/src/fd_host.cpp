@@ -284,6 +284,63 @@ static Mat hist_apply(const HistogramFilter& f, const Mat& image, Mat& filtered)
 }
 Mat HogFilter::applyTo(const Mat& image, Mat& filtered) const { return hist_apply(*this, image, filtered); }
 
+// ---- ExtendedHogFilter (ExtendedHogFilter.cpp:14-61), CompleteExtendedHogFilter (CompleteExtendedHogFilter.cpp:19-70) -----------------
+ExtendedHogFilter::ExtendedHogFilter(int binCount, int cellSize, bool interpolate, bool signedAndUnsigned, float alpha)
+    : HistogramFilter(Normalization::L2HYS), binCount(binCount), cellWidth(cellSize), cellHeight(cellSize), interpolate(interpolate),
+      signedAndUnsigned(signedAndUnsigned), alpha(alpha) {
+    if (binCount <= 0) throw std::invalid_argument("ExtendedHogFilter: binCount must be greater than zero");
+    if (cellSize <= 0) throw std::invalid_argument("ExtendedHogFilter: cellSize must be greater than zero");
+    if (signedAndUnsigned && binCount % 2 != 0)
+        throw std::invalid_argument("ExtendedHogFilter: the bin size must be even for signed and unsigned gradients to be combined");
+    if (alpha <= 0) throw std::invalid_argument("ExtendedHogFilter: alpha must be greater than zero");
+}
+ExtendedHogFilter::ExtendedHogFilter(int binCount, int cellWidth, int cellHeight, bool interpolate, bool signedAndUnsigned, float alpha)
+    : HistogramFilter(Normalization::L2HYS), binCount(binCount), cellWidth(cellWidth), cellHeight(cellHeight), interpolate(interpolate),
+      signedAndUnsigned(signedAndUnsigned), alpha(alpha) {
+    if (binCount <= 0) throw std::invalid_argument("ExtendedHogFilter: binCount must be greater than zero");
+    if (cellWidth <= 0) throw std::invalid_argument("ExtendedHogFilter: cellWidth must be greater than zero");
+    if (cellHeight <= 0) throw std::invalid_argument("ExtendedHogFilter: cellHeight must be greater than zero");
+    if (signedAndUnsigned && binCount % 2 != 0)
+        throw std::invalid_argument("ExtendedHogFilter: the bin size must be even for signed and unsigned gradients to be combined");
+    if (alpha <= 0) throw std::invalid_argument("ExtendedHogFilter: alpha must be greater than zero");
+}
+Mat ExtendedHogFilter::applyTo(const Mat& image, Mat& filtered) const {
+    if (image.depth() != CV_8U || (image.channels() != 1 && image.channels() != 2 && image.channels() != 4))
+        throw std::invalid_argument("HistogramFilter: The image must have one, two or four channels and be of depth CV_8U");
+    Mat src = contiguous(image);
+    fd_ehog_patch_params ep = {src.cols, src.rows, binCount, cellWidth, cellHeight, interpolate, signedAndUnsigned, alpha};
+    const int F = fd_ehog_feature_length(&ep, src.channels());
+    if (F < 0) throw std::invalid_argument("ExtendedHogFilter: the patch is smaller than one cell");
+    const int rows = cv::cvRound(static_cast<double>(src.rows) / static_cast<double>(cellHeight));
+    Mat dst(rows, F / rows, CV_32FC1);   // the compat Mat has no CV_32FC(n) with n > 4: channels are interleaved in the row
+    check(fd_ehog_patch_batch(context(), src.data, 1, src.channels(), &ep, dst.ptr<float>(0)));
+    filtered = dst;
+    return filtered;
+}
+
+CompleteExtendedHogFilter::CompleteExtendedHogFilter(size_t cellSize, size_t binCount, bool signedGradients, bool unsignedGradients,
+                                                     bool interpolateBins, bool interpolateCells, float alpha)
+    : cellSize(cellSize), binCount(binCount), signedGradients(signedGradients), unsignedGradients(unsignedGradients),
+      interpolateBins(interpolateBins), interpolateCells(interpolateCells), alpha(alpha) {
+    if (!signedGradients && !unsignedGradients)
+        throw std::invalid_argument("CompleteExtendedHogFilter: signedGradients or unsignedGradients has to be true");
+    if (signedGradients && unsignedGradients && binCount % 2 != 0)
+        throw std::invalid_argument("CompleteExtendedHogFilter: if both signed and unsigned gradients should be used, the bin count has to be even");
+    if (cellSize < 1 || binCount < 1) throw std::invalid_argument("CompleteExtendedHogFilter: cellSize and binCount must be greater than zero");
+}
+fd_cehog_params CompleteExtendedHogFilter::params() const {
+    return fd_cehog_params{(int32_t)cellSize, (int32_t)binCount, signedGradients, unsignedGradients, interpolateBins, interpolateCells, alpha};
+}
+Mat CompleteExtendedHogFilter::applyTo(const Mat& image, Mat& filtered) const {
+    if (image.type() != CV_8UC1) throw std::invalid_argument("CompleteExtendedHogFilter: image must be of type CV_8UC1");
+    Mat src = contiguous(image);
+    const fd_cehog_params fp = params();
+    const int rows = src.rows / (int)cellSize, cols = src.cols / (int)cellSize, D = (int)getDescriptorSize();
+    filtered.create(rows, cols * D, CV_32FC1);   // channels interleaved in the row, as for FhogFilter
+    if (rows > 0 && cols > 0) check(fd_cehog_image(context(), src.ptr<uchar>(0), src.cols, src.rows, &fp, filtered.ptr<float>(0)));
+    return filtered;
+}
+
 // ---- ImagePyramid -------------------------------------------------------------------------------
 static const char* const kImageFilterChains =
     "ImagePyramid: the image filter chains available on this backend are [GrayscaleFilter] and "
@@ -755,6 +812,8 @@ void DirectPyramidFeatureExtractor::addPatchFilter(shared_ptr<ImageFilter> filte
         if (whiStage != 3 || uf->normType != cv::NORM_L2)
             throw std::logic_error("DirectPyramidFeatureExtractor: UnitNormFilter is available as UnitNormFilter(cv::NORM_L2) at the end of the whi chain only");
         whiStage = 4;
+    } else if (std::dynamic_pointer_cast<ExtendedHogFilter>(filter)) {
+        throw std::logic_error("DirectPyramidFeatureExtractor: ExtendedHogFilter is available per patch (applyTo, FilteringFeatureExtractor), not in a fused chain");
     } else if (auto hf = std::dynamic_pointer_cast<HistogramFilter>(filter)) {
         hist = hf;
         auto g = std::dynamic_pointer_cast<HogFilter>(filter);
@@ -912,6 +971,73 @@ shared_ptr<Patch> FilteringPyramidFeatureExtractor::extract(int layer, int x, in
     shared_ptr<Patch> patch = extractor->extract(layer, x, y);
     if (patch) patchFilter->applyInPlace(patch->getData());
     return patch;
+}
+
+
+// ---- ExtendedHogFeatureExtractor, CellBasedPyramidFeatureExtractor on one fd_ehog_tracker ---------------------------------------------
+static shared_ptr<VersionedImage> ehog_update(fd_ehog_tracker* tracker, const shared_ptr<VersionedImage>& image) {
+    Mat src = contiguous(image->getData());
+    if (src.depth() != CV_8U || (src.channels() != 1 && src.channels() != 3)) throw std::invalid_argument("GrayscaleFilter: the image must be CV_8UC1 or CV_8UC3");
+    check(fd_ehog_tracker_update(context(), tracker, src.ptr<uchar>(0), src.cols, src.rows, src.channels(), 0));
+    return image;
+}
+// the layer ImagePyramid::getLayer(scaleFactor) picks (ImagePyramid.cpp:300-310); false when there is none
+static bool ehog_layer_of(fd_ehog_tracker* tracker, double scaleFactor, int octaveLayerCount, fd_ehog_layer& layer) {
+    fd_ehog_layer layers[256];
+    int n = 0;
+    if (fd_ehog_tracker_get_layers(tracker, layers, 256, &n) != FD_OK || n == 0) return false;
+    const double power = std::log(scaleFactor) / std::log(std::pow(0.5, 1. / octaveLayerCount));
+    const long realIndex = std::lround(power) - layers[0].index;
+    if (realIndex < 0 || realIndex >= n) return false;
+    layer = layers[realIndex];
+    return true;
+}
+ExtendedHogFeatureExtractor::ExtendedHogFeatureExtractor(shared_ptr<CompleteExtendedHogFilter> ehogFilter, int cols, int rows, int minWidth, int maxWidth,
+                                                         int octaveLayerCount)
+    : tracker(nullptr), cols(cols), rows(rows), cellSize((int)ehogFilter->getCellSize()), channels((int)ehogFilter->getDescriptorSize()),
+      patchWidth((cols + 2) * (int)ehogFilter->getCellSize()), patchHeight((rows + 2) * (int)ehogFilter->getCellSize()), octaveLayerCount(octaveLayerCount),
+      widthFactor(static_cast<double>(cols + 2) / cols), heightFactor(static_cast<double>(rows + 2) / rows) {
+    if (cols <= 0 || rows <= 0) throw std::invalid_argument("ExtendedHogFeatureExtractor: the amount of columns and rows must be greater than zero");
+    fd_ehog_tracker_params prm = {ehogFilter->params(), cols, rows, octaveLayerCount, minWidth, maxWidth};
+    check(fd_ehog_tracker_create(context(), &prm, &tracker));
+}
+ExtendedHogFeatureExtractor::~ExtendedHogFeatureExtractor() { fd_ehog_tracker_destroy(tracker); }
+void ExtendedHogFeatureExtractor::update(shared_ptr<VersionedImage> image) { ehog_update(tracker, image); }
+shared_ptr<Patch> ExtendedHogFeatureExtractor::extract(int x, int y, int width, int height) const {
+    const int32_t xywh[4] = {x, y, width, height};
+    uint8_t valid = 0;
+    Mat data(rows, cols * channels, CV_32FC1);
+    check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, data.ptr<float>(0), nullptr));
+    if (!valid) return shared_ptr<Patch>();
+    // the patch's place in the image (:96-104,125-129)
+    width = static_cast<int>(std::round(widthFactor * width));
+    height = static_cast<int>(std::round(heightFactor * height));
+    fd_ehog_layer layer;
+    if (!ehog_layer_of(tracker, static_cast<double>(patchWidth) / static_cast<double>(width), octaveLayerCount, layer)) return shared_ptr<Patch>();
+    auto scaled = [&](int v) { return cv::cvRound(v * layer.scale); };
+    auto original = [&](int v) { return cv::cvRound(v / layer.scale); };
+    const int bx = scaled(x - width / 2), by = scaled(y - height / 2);
+    const int originalWidth = original(patchWidth - 2 * cellSize), originalHeight = original(patchHeight - 2 * cellSize);
+    return make_shared<Patch>(original(bx + cellSize) + originalWidth / 2, original(by + cellSize) + originalHeight / 2, originalWidth, originalHeight, data);
+}
+CellBasedPyramidFeatureExtractor::CellBasedPyramidFeatureExtractor(shared_ptr<ExtendedHogFeatureExtractor> base) : base(base) {
+    if (!base) throw std::invalid_argument("CellBasedPyramidFeatureExtractor: the underlying extractor must not be null");
+}
+shared_ptr<Patch> CellBasedPyramidFeatureExtractor::extract(int x, int y, int width, int height) const {
+    const int32_t xywh[4] = {x, y, width, height};
+    uint8_t valid = 0;
+    const int cols = base->getCols(), rows = base->getRows(), cellSize = base->getCellSize();
+    Mat data(rows, cols * base->getChannels(), CV_32FC1);
+    check(fd_ehog_tracker_extract_cells(context(), base->native(), 1, xywh, &valid, data.ptr<float>(0)));
+    if (!valid) return shared_ptr<Patch>();
+    fd_ehog_layer layer;   // getLayer(width) and getScaled / getOriginal in cells (CellBasedPyramidFeatureExtractor.cpp:58-69)
+    if (!ehog_layer_of(base->native(), static_cast<double>(cols * cellSize) / static_cast<double>(width), base->getOctaveLayerCount(), layer))
+        return shared_ptr<Patch>();
+    auto scaled = [&](int v) { return cv::cvRound(v * layer.scale / cellSize); };
+    auto original = [&](int v) { return cv::cvRound(v * cellSize / layer.scale); };
+    const int bx = scaled(x - width / 2), by = scaled(y - height / 2);
+    const int originalWidth = original(cols), originalHeight = original(rows);
+    return make_shared<Patch>(original(bx) + originalWidth / 2, original(by) + originalHeight / 2, originalWidth, originalHeight, data);
 }
 
 }  // namespace imageprocessing
@@ -2020,6 +2146,7 @@ Mat SdmLandmarkModelFitting::optimize(Mat modelShape, Mat image) {
 }  // namespace superviseddescent
 
 // =================================================================================================
+#include <limits>
 #include "condensation/condensation_all.hpp"
 namespace condensation {
 
@@ -2125,6 +2252,300 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
         samples[i]->setTarget(target[i] != 0);
         samples[i]->setWeight(weight[i]);
     }
+}
+
+
+// ---- ExtendedHogBasedMeasurementModel, the evaluation half (ExtendedHogBasedMeasurementModel.cpp) -----------------------------------
+int Sample::nextClusterId = 0;
+
+ExtendedHogBasedMeasurementModel::ExtendedHogBasedMeasurementModel(shared_ptr<classification::ProbabilisticSvmClassifier> classifier)
+    : cellSize(5), cellCount(35), signedAndUnsigned(false), interpolateBins(false), interpolateCells(true), octaveLayerCount(5),
+      rejectionThreshold(-1.5), useSlidingWindow(true), conservativeReInit(false), negativeExampleCount(10), initialNegativeExampleCount(50),
+      randomExampleCount(50), negativeScoreThreshold(-1.0f), positiveOverlapThreshold(0.5), negativeOverlapThreshold(0.5),
+      adaptation(Adaptation::POSITION), adaptationThreshold(0.75), exclusionThreshold(0.0), classifier(classifier) {
+    if (!classifier || !dynamic_cast<classification::LinearKernel*>(classifier->getSvm()->getKernel().get()))   // :74-75
+        throw std::invalid_argument("ExtendedHogBasedMeasurementKernel: the SVM must use a LinearKernel");
+}
+ExtendedHogBasedMeasurementModel::~ExtendedHogBasedMeasurementModel() { if (tracker) fd_ehog_tracker_destroy(tracker); }
+
+void ExtendedHogBasedMeasurementModel::setHogParams(size_t cellSize, size_t cellCount, bool signedAndUnsigned, bool interpolateBins, bool interpolateCells,
+                                                    int octaveLayerCount) {
+    this->cellSize = cellSize; this->cellCount = cellCount; this->signedAndUnsigned = signedAndUnsigned;
+    this->interpolateBins = interpolateBins; this->interpolateCells = interpolateCells; this->octaveLayerCount = octaveLayerCount;
+}
+void ExtendedHogBasedMeasurementModel::setNegativeExampleParams(size_t negativeExampleCount, size_t initialNegativeExampleCount, size_t randomExampleCount,
+                                                                float negativeScoreThreshold) {
+    this->negativeExampleCount = negativeExampleCount; this->initialNegativeExampleCount = initialNegativeExampleCount;
+    this->randomExampleCount = randomExampleCount; this->negativeScoreThreshold = negativeScoreThreshold;
+}
+void ExtendedHogBasedMeasurementModel::setOverlapThresholds(double positiveOverlapThreshold, double negativeOverlapThreshold) {
+    this->positiveOverlapThreshold = positiveOverlapThreshold; this->negativeOverlapThreshold = negativeOverlapThreshold;
+}
+void ExtendedHogBasedMeasurementModel::setAdaptation(Adaptation adaptation, double adaptationThreshold, double exclusionThreshold) {
+    this->adaptation = adaptation; this->adaptationThreshold = adaptationThreshold; this->exclusionThreshold = exclusionThreshold;
+}
+
+void ExtendedHogBasedMeasurementModel::computeCellGrid(int width, int height, size_t cellCount, size_t& cellColumnCount, size_t& cellRowCount) {   // :221-228
+    const double aspectRatio = static_cast<double>(height) / static_cast<double>(width);
+    if (aspectRatio < 1) {   // height is less than width, so determine height first
+        cellRowCount = cv::cvRound(std::sqrt(aspectRatio * cellCount));
+        cellColumnCount = cv::cvRound(cellRowCount / aspectRatio);
+    } else {                 // width is less than or equal to height, so determine width first
+        cellColumnCount = cv::cvRound(std::sqrt(cellCount / aspectRatio));
+        cellRowCount = cv::cvRound(aspectRatio * cellColumnCount);
+    }
+}
+
+static void model_update(fd_ehog_tracker* tracker, const shared_ptr<imageprocessing::VersionedImage>& image) {
+    Mat src = contiguous(image->getData());
+    if (src.depth() != CV_8U || (src.channels() != 1 && src.channels() != 3)) throw std::invalid_argument("GrayscaleFilter: the image must be CV_8UC1 or CV_8UC3");
+    check(fd_ehog_tracker_update(context(), tracker, src.ptr<uchar>(0), src.cols, src.rows, src.channels(), 0));
+}
+
+void ExtendedHogBasedMeasurementModel::update(shared_ptr<imageprocessing::VersionedImage> image) {   // :97-105: one handle holds the three pyramids
+    if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    model_update(tracker, image);
+}
+
+void ExtendedHogBasedMeasurementModel::takeClassifierWeights() {   // in place of retrain + :336-340
+    const auto svm = classifier->getSvm();
+    if (svm->getSupportVectors().size() != 1)
+        throw std::runtime_error("ExtendedHogBasedMeasurementModel: the amount of support vectors has to be one (w)");
+    const int D = signedAndUnsigned ? 18 + 9 + 4 : 9 + 4;
+    Mat w = contiguous(svm->getSupportVectors()[0]);
+    if (w.depth() != CV_32F || (size_t)w.total() * w.channels() != cellRowCount * cellColumnCount * D)
+        throw std::invalid_argument("ExtendedHogBasedMeasurementModel: the support vector must hold cellRowCount x cellColumnCount x channels floats");
+    vector<float> scaled(w.ptr<float>(0), w.ptr<float>(0) + cellRowCount * cellColumnCount * D);
+    const float c = svm->getCoefficients().empty() ? 1.f : svm->getCoefficients()[0];   // computeHyperplaneDistance: coefficient * dot - bias
+    if (c != 1.f) throw std::invalid_argument("ExtendedHogBasedMeasurementModel: the coefficient of the one support vector (w) has to be one");
+    check(fd_ehog_tracker_set_svm(context(), tracker, scaled.data(), svm->getBias()));
+}
+
+void ExtendedHogBasedMeasurementModel::scored(Sample& sample, bool valid, double score) const {   // :173-205
+    if (!valid) {
+        sample.setTarget(false);
+        sample.setWeight(0);
+        sample.setScore(0);
+        return;
+    }
+    std::pair<bool, double> result = classifier->getProbability(score);
+    sample.setWeight(sample.getWeight() * result.second);
+    sample.setScore(score);
+    if (targetLost) sample.setTarget(result.first);
+    else sample.setTarget(useSlidingWindow ? score > rejectionThreshold : true);
+}
+
+void ExtendedHogBasedMeasurementModel::evaluate(Sample& sample) const {
+    if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    const int32_t xywh[4] = {sample.getX(), sample.getY(), sample.getWidth(), sample.getHeight()};
+    uint8_t valid = 0;
+    if (useSlidingWindow) {
+        float score = 0;
+        check(fd_ehog_tracker_evaluate_samples(context(), tracker, 1, xywh, &valid, &score));
+        scored(sample, valid != 0, score);
+    } else {
+        vector<float> features(cellRowCount * cellColumnCount * (signedAndUnsigned ? 31 : 13));
+        double score = 0;
+        check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, features.data(), &score));
+        scored(sample, valid != 0, score);
+    }
+}
+
+// every sample of a frame in one device call; bestScore as :138-142 keeps it
+void ExtendedHogBasedMeasurementModel::evaluateAll(vector<shared_ptr<Sample>>& samples, double* bestScore) {
+    const int n = (int)samples.size();
+    vector<int32_t> xywh((size_t)4 * n);
+    for (int i = 0; i < n; ++i) {
+        xywh[4 * i] = samples[i]->getX(); xywh[4 * i + 1] = samples[i]->getY();
+        xywh[4 * i + 2] = samples[i]->getWidth(); xywh[4 * i + 3] = samples[i]->getHeight();
+    }
+    vector<uint8_t> valid((size_t)n);
+    vector<double> score((size_t)n);
+    if (useSlidingWindow) {
+        vector<float> s((size_t)n);
+        check(fd_ehog_tracker_evaluate_samples(context(), tracker, n, xywh.data(), valid.data(), s.data()));
+        for (int i = 0; i < n; ++i) score[i] = s[i];
+    } else {
+        vector<float> features((size_t)n * cellRowCount * cellColumnCount * (signedAndUnsigned ? 31 : 13));
+        check(fd_ehog_tracker_extract_patches(context(), tracker, n, xywh.data(), valid.data(), features.data(), score.data()));
+    }
+    ++fusedEvaluations;
+    for (int i = 0; i < n; ++i) {
+        scored(*samples[i], valid[i] != 0, score[i]);
+        if (bestScore) *bestScore = std::max(*bestScore, samples[i]->getScore());
+    }
+}
+
+void ExtendedHogBasedMeasurementModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {   // :107-168
+    update(image);
+    if (!useSlidingWindow) {
+        evaluateAll(samples, nullptr);
+        return;
+    }
+    std::pair<double, cv::Rect> peak = getHeatPeak();
+    auto reinitialize = [&]() {   // :118-129,153-164: the draws in the reference's order, then one evaluation of all samples
+        int clusterId = Sample::getNextClusterId();
+        for (shared_ptr<Sample>& sample : samples) {
+            sample->setX(peak.second.x + peak.second.width / 2 + 0.2 * peak.second.width * normalDistribution(generator));
+            sample->setY(peak.second.y + peak.second.height / 2 + 0.2 * peak.second.width * normalDistribution(generator));
+            sample->setSize(peak.second.width * (1 + 0.2 * normalDistribution(generator)));
+            sample->setVx(0.1 * peak.second.width * normalDistribution(generator));
+            sample->setVy(0.1 * peak.second.width * normalDistribution(generator));
+            sample->setVSize(1 + 0.1 * normalDistribution(generator));
+            sample->setClusterId(clusterId);
+            sample->resetAncestor();
+        }
+        evaluateAll(samples, nullptr);
+    };
+    if (targetLost) {
+        double peakScore = peak.first;
+        if (classifier->getSvm()->classify(peakScore) && (!conservativeReInit || peakScore > adaptationThreshold)) {
+            reinitialize();
+        } else {   // target was lost and could not be re-initialized
+            for (shared_ptr<Sample>& sample : samples) {
+                sample->setWeight(0);
+                sample->setScore(0);
+                sample->setTarget(false);
+            }
+        }
+    } else {
+        double bestScore = std::numeric_limits<double>::lowest();
+        evaluateAll(samples, &bestScore);
+        double peakScore = peak.first;
+        double initialFeaturesScore = classifier->getSvm()->computeHyperplaneDistance(initialFeatures);
+        double scoreThreshold = 0.5 * (bestScore + initialFeaturesScore);
+        if (conservativeReInit) scoreThreshold = std::max(scoreThreshold, adaptationThreshold);
+        if (bestScore < initialFeaturesScore && classifier->getSvm()->classify(peakScore) && peakScore > scoreThreshold) reinitialize();
+    }
+}
+
+bool ExtendedHogBasedMeasurementModel::isValid(const Sample& target, const vector<shared_ptr<Sample>>&, shared_ptr<imageprocessing::VersionedImage>) {   // :209-213
+    if (!tracker) return false;
+    const int32_t xywh[4] = {target.getX(), target.getY(), target.getWidth(), target.getHeight()};
+    uint8_t valid = 0;
+    double score = 0;
+    vector<float> features(cellRowCount * cellColumnCount * (signedAndUnsigned ? 31 : 13));
+    check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, features.data(), &score));
+    return valid && score > rejectionThreshold;
+}
+
+bool ExtendedHogBasedMeasurementModel::initialize(shared_ptr<imageprocessing::VersionedImage> image, Sample& target) {   // :219-384 without retraining
+    if (!initialized) {
+        const double aspectRatio = static_cast<double>(target.getHeight()) / static_cast<double>(target.getWidth());
+        computeCellGrid(target.getWidth(), target.getHeight(), cellCount, cellColumnCount, cellRowCount);
+        if (cellColumnCount < 1 || cellRowCount < 1) throw std::invalid_argument("ExtendedHogFeatureExtractor: the amount of columns and rows must be greater than zero");
+        const double newAspectRatio = static_cast<double>(cellRowCount) / static_cast<double>(cellColumnCount);
+        if (newAspectRatio < aspectRatio) target.setSize(cv::cvRound(aspectRatio * target.getSize() / newAspectRatio));
+        Sample::setAspectRatio((int)cellColumnCount, (int)cellRowCount);
+        const Mat& data = image->getData();
+        const double imageAspectRatio = static_cast<double>(data.rows) / static_cast<double>(data.cols);
+        minWidth = cellSize * cellColumnCount;
+        if (aspectRatio > imageAspectRatio) maxWidth = static_cast<size_t>(static_cast<size_t>(data.rows) / aspectRatio);
+        else maxWidth = data.cols;
+        fd_cehog_params filter = signedAndUnsigned ? fd_cehog_params{(int32_t)cellSize, 18, 1, 1, interpolateBins, interpolateCells, 0.2f}
+                                                   : fd_cehog_params{(int32_t)cellSize, 9, 0, 1, interpolateBins, interpolateCells, 0.48f};
+        fd_ehog_tracker_params prm = {filter, (int32_t)cellColumnCount, (int32_t)cellRowCount, octaveLayerCount, (int32_t)minWidth, (int32_t)maxWidth};
+        if (tracker) { fd_ehog_tracker_destroy(tracker); tracker = nullptr; }
+        check(fd_ehog_tracker_create(context(), &prm, &tracker));
+        initialized = true;
+    }
+    model_update(tracker, image);
+    const int32_t xywh[4] = {target.getX(), target.getY(), target.getWidth(), target.getHeight()};
+    uint8_t valid = 0;
+    const int D = signedAndUnsigned ? 31 : 13;
+    Mat features((int)cellRowCount, (int)cellColumnCount * D, CV_32FC1);
+    check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, features.ptr<float>(0), nullptr));
+    if (!valid) {
+        reset();
+        return false;
+    }
+    initialFeatures = features;
+    takeClassifierWeights();   // builds the heat pyramid of this frame as well (:339-341)
+    usable = true;
+    targetLost = false;
+    return usable;
+}
+
+bool ExtendedHogBasedMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage>, const vector<shared_ptr<Sample>>&, const Sample&) {   // :386-404
+    if (!usable) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    targetLost = false;
+    takeClassifierWeights();
+    return true;
+}
+bool ExtendedHogBasedMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage>, const vector<shared_ptr<Sample>>&) {   // :406-419
+    if (!usable) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    takeClassifierWeights();
+    targetLost = true;
+    return false;
+}
+void ExtendedHogBasedMeasurementModel::reset() {   // :421-432
+    initialized = false;
+    usable = false;
+    targetLost = false;
+    initialFeatures = Mat();
+}
+
+std::pair<double, cv::Rect> ExtendedHogBasedMeasurementModel::getHeatPeak() const {   // :434-456
+    if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    fd_box peak;
+    int found = 0;
+    check(fd_ehog_tracker_heat_peak(context(), tracker, &peak, &found));
+    if (!found) return std::make_pair(std::numeric_limits<double>::lowest(), cv::Rect());
+    return std::make_pair((double)peak.score, cv::Rect(peak.x, peak.y, peak.w, peak.h));
+}
+
+double ExtendedHogBasedMeasurementModel::computeOverlap(cv::Rect a, cv::Rect b) const {   // :694-698
+    const int x0 = std::max(a.x, b.x), y0 = std::max(a.y, b.y);
+    const int x1 = std::min(a.x + a.width, b.x + b.width), y1 = std::min(a.y + a.height, b.y + b.height);
+    const double intersectionArea = x1 > x0 && y1 > y0 ? (double)(x1 - x0) * (y1 - y0) : 0.0;
+    const double unionArea = (double)a.width * a.height + (double)b.width * b.height - intersectionArea;
+    return intersectionArea / unionArea;
+}
+
+vector<Mat> ExtendedHogBasedMeasurementModel::createGoodNegativeExamples(cv::Rect targetBounds, vector<cv::Rect>* chosen) const {   // :621-669
+    if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    int count = 0;
+    vector<fd_box> maxima(4096);
+    int rc = fd_ehog_tracker_heat_maxima(context(), tracker, negativeScoreThreshold, maxima.data(), (int)maxima.size(), &count);
+    if (rc == FD_ERR_CAPACITY) {
+        maxima.resize(count);
+        rc = fd_ehog_tracker_heat_maxima(context(), tracker, negativeScoreThreshold, maxima.data(), (int)maxima.size(), &count);
+    }
+    check(rc);
+    vector<std::pair<float, cv::Rect>> candidates;
+    for (int i = 0; i < count; ++i) {
+        cv::Rect bounds(maxima[i].x, maxima[i].y, maxima[i].w, maxima[i].h);
+        if (computeOverlap(targetBounds, bounds) < positiveOverlapThreshold) candidates.emplace_back(maxima[i].score, bounds);
+    }
+    // reduce overlapping candidates using non-maximum suppression
+    std::sort(candidates.begin(), candidates.end(), [](const std::pair<float, cv::Rect>& a, const std::pair<float, cv::Rect>& b) { return a.first < b.first; });
+    vector<cv::Rect> boxes;
+    while (!candidates.empty()) {
+        const cv::Rect box = candidates.back().second;
+        candidates.pop_back();
+        boxes.push_back(box);
+        candidates.erase(std::remove_if(candidates.begin(), candidates.end(),
+                                        [&](const std::pair<float, cv::Rect>& elem) { return computeOverlap(box, elem.second) > negativeOverlapThreshold; }),
+                         candidates.end());
+    }
+    const int D = signedAndUnsigned ? 31 : 13;
+    const size_t per = cellRowCount * cellColumnCount * D;
+    vector<int32_t> xywh;
+    for (const cv::Rect& box : boxes) {
+        xywh.push_back(box.x + box.width / 2); xywh.push_back(box.y + box.height / 2); xywh.push_back(box.width); xywh.push_back(box.height);
+    }
+    vector<uint8_t> valid(boxes.size());
+    vector<float> features(boxes.size() * per);
+    if (!boxes.empty()) check(fd_ehog_tracker_extract_cells(context(), tracker, (int)boxes.size(), xywh.data(), valid.data(), features.data()));
+    vector<Mat> examples;
+    examples.reserve(boxes.size());
+    for (size_t i = 0; i < boxes.size(); ++i) {
+        Mat m((int)cellRowCount, (int)cellColumnCount * D, CV_32FC1);
+        std::memcpy(m.ptr<float>(0), features.data() + i * per, sizeof(float) * per);
+        examples.push_back(m);
+    }
+    if (chosen) *chosen = boxes;
+    return examples;
 }
 
 }  // namespace condensation

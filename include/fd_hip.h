@@ -323,6 +323,87 @@ int fd_fhog_image_channels(fd_ctx* ctx, const uint8_t* image, int width, int hei
 /* the same on kept layer `layer` of an updated gray pyramid (the layer filter of AggregatedFeaturesExtractor's feature pyramid) */
 int fd_pyramid_fhog_layer(fd_ctx* ctx, fd_pyramid* p, int layer, const fd_fhog_params* fp, float* out);
 
+/* imageprocessing::CompleteExtendedHogFilter(cellSize, binCount, signedGradients, unsignedGradients, interpolateBins,
+ * interpolateCells, alpha) (CompleteExtendedHogFilter.cpp:19-303) on CV_8UC1 images: rows = height / cell_size,
+ * cols = width / cell_size cells of bin_count (+ bin_count / 2 when both gradient kinds are set) + 4 floats, in the order
+ * [bins][unsigned halves][4 energy features].  The central differences clamp at the area the cells cover, not at the image
+ * edge.  Reference defaults: 8, 18, true, true, false, true, 0.2 (CompleteExtendedHogFilter.hpp:49-50).  Invalid: neither
+ * gradient kind, both kinds with an odd bin_count, cell_size < 1, bin_count < 1 (this backend: bin_count <= 36). */
+typedef struct {
+    int32_t cell_size, bin_count, signed_gradients, unsigned_gradients, interpolate_bins, interpolate_cells;
+    float alpha;
+} fd_cehog_params;
+/* host only; an image smaller than a cell gives rows or cols 0 */
+int fd_cehog_size(const fd_cehog_params* fp, int width, int height, int* rows, int* cols, int* channels);
+/* host only (no context, no device): the gradient look-up table of the constructor (:31-58), 512 * 512 entries each, index
+ * dx * 512 + dy with dx, dy the central differences + 256.  Without bin interpolation index2 = index1, weight2 = 0.  Any output
+ * may be NULL. */
+int fd_cehog_gradient_lut(const fd_cehog_params* fp, int32_t* index1, int32_t* index2, float* weight1, float* weight2);
+/* applyTo: gray host image (width * height bytes) -> rows * cols * channels floats (host).  FD_ERR_INVALID_ARGUMENT for an image
+ * smaller than a cell. */
+int fd_cehog_image(fd_ctx* ctx, const uint8_t* gray, int width, int height, const fd_cehog_params* fp, float* out);
+/* the same on kept layer `layer` of an updated gray pyramid (the layer filter of ExtendedHogBasedMeasurementModel's feature pyramid) */
+int fd_pyramid_cehog_layer(fd_ctx* ctx, fd_pyramid* p, int layer, const fd_cehog_params* fp, float* out);
+
+/* The per-frame work of condensation::ExtendedHogBasedMeasurementModel with a CompleteExtendedHogFilter
+ * (ExtendedHogBasedMeasurementModel.cpp:97-213,243-265,434-456,621-652): the gray pyramid of
+ * ExtendedHogFeatureExtractor::createPyramid((cell_cols + 2) * cell, (cell_cols + 2) * min_width / cell_cols,
+ * (cell_cols + 2) * max_width / cell_cols, octave_layer_count) (ExtendedHogFeatureExtractor.cpp:32-41,76-84), the filter on every
+ * layer (feature pyramid), and, once an SVM is set, the heat pyramid: ConvolutionFilter.cpp:27-43 with the weight vector as kernel,
+ * anchor at the kernel centre (cell_cols / 2, cell_rows / 2), BORDER_CONSTANT 0, delta = -bias; heat layers have the size of their
+ * feature layers.  Training stays with the caller, who supplies the linear SVM's weight vector and bias. */
+typedef struct fd_ehog_tracker fd_ehog_tracker;
+typedef struct {
+    fd_cehog_params filter;
+    int32_t cell_cols, cell_rows;        /* window size in cells */
+    int32_t octave_layer_count;
+    int32_t min_width, max_width;        /* target widths in pixels the pyramid has to cover */
+} fd_ehog_tracker_params;
+typedef struct {
+    int32_t index;            /* ImagePyramidLayer::getIndex() */
+    int32_t width, height;    /* gray layer in pixels */
+    int32_t rows, cols;       /* feature / heat layer in cells */
+    int32_t reserved;
+    double scale;             /* getScaleFactor() */
+} fd_ehog_layer;
+/* Host only (no context, no device): the layers a handle with these parameters builds for a width x height image.
+ * FD_ERR_RUNTIME when fewer than two layers remain (fd_ehog_tracker_update reports the same: the feature pyramid is an
+ * ImagePyramid built on another, ImagePyramid.cpp:238-239; *n is set), FD_ERR_CAPACITY when cap is too small (*n is set). */
+int fd_ehog_tracker_plan_layers(const fd_ehog_tracker_params* prm, int width, int height, fd_ehog_layer* out, int cap, int* n);
+int fd_ehog_tracker_create(fd_ctx* ctx, const fd_ehog_tracker_params* prm, fd_ehog_tracker** out);
+void fd_ehog_tracker_destroy(fd_ehog_tracker* t);
+/* update(image): gray pyramid, feature layers and, once an SVM is set, heat layers.  image as fd_pyramid_update. */
+int fd_ehog_tracker_update(fd_ctx* ctx, fd_ehog_tracker* t, const uint8_t* image, int width, int height, int channels, int is_device);
+/* the single support vector, [cell_rows][cell_cols][channels], and the bias (:339-340).  On an updated handle the heat layers
+ * of the current frame are rebuilt with it. */
+int fd_ehog_tracker_set_svm(fd_ctx* ctx, fd_ehog_tracker* t, const float* weights, float bias);
+/* evaluate(Sample&) with the sliding window (:189-205) for n samples {x, y, width, height}: the window is that of
+ * CellBasedPyramidFeatureExtractor (.cpp:58-69; DirectPyramidFeatureExtractor.cpp:67-73,133-143), the score the heat value at
+ * (by + cell_rows / 2, bx + cell_cols / 2).  Samples without a patch: valid 0, score 0.  FD_ERR_RUNTIME before an update or
+ * before an SVM is set (also _heat_peak, _heat_maxima, _heat_layer). */
+int fd_ehog_tracker_evaluate_samples(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* xywh, uint8_t* valid, float* score);
+/* the same windows: cell_rows * cell_cols * channels floats each (zeros without a patch) */
+int fd_ehog_tracker_extract_cells(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* xywh, uint8_t* valid, float* features);
+/* ExtendedHogFeatureExtractor::extract (ExtendedHogFeatureExtractor.cpp:95-143): the size widened by (cells + 2) / cells, the
+ * layer by patchWidth / width, bounds up to one cell outside the layer (mirrored), the filter on the (cell_cols + 2) * cell x
+ * (cell_rows + 2) * cell patch, the inner cells returned.  score (may be NULL; needs an SVM): -bias + dot(features, weights), the
+ * double sum in element order of SvmClassifier::computeHyperplaneDistance with a LinearKernel.  One wavefront per sample with the
+ * patch in LDS: FD_ERR_INVALID_ARGUMENT when fd_ehog_tracker_patch_lds_bytes exceeds 65536. */
+int fd_ehog_tracker_extract_patches(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* xywh, uint8_t* valid, float* features, double* score);
+/* host only: LDS bytes fd_ehog_tracker_extract_patches needs per sample; -1 on invalid parameters */
+int fd_ehog_tracker_patch_lds_bytes(const fd_ehog_tracker_params* prm);
+/* getHeatPeak (:434-456): the reference's loop bounds (the last full position is excluded), strict > in layer / row / column
+ * order.  peak: score and the getOriginal bounds; without any position *found = 0, score -FLT_MAX, bounds 0. */
+int fd_ehog_tracker_heat_peak(fd_ctx* ctx, fd_ehog_tracker* t, fd_box* peak, int* found);
+/* the scan of createGoodNegativeExamples (:621-652): positions with score > threshold and >= all eight neighbours, in scan
+ * order.  FD_ERR_CAPACITY with *count set when cap is too small; windows of one cell row or column are FD_ERR_INVALID_ARGUMENT
+ * (the reference's scan reads outside the heat map). */
+int fd_ehog_tracker_heat_maxima(fd_ctx* ctx, fd_ehog_tracker* t, float threshold, fd_box* out, int cap, int* count);
+/* layers of the last update (0 before), and their feature (rows * cols * channels floats) / heat (rows * cols floats) maps */
+int fd_ehog_tracker_get_layers(fd_ehog_tracker* t, fd_ehog_layer* out, int cap, int* n);
+int fd_ehog_tracker_feature_layer(fd_ctx* ctx, fd_ehog_tracker* t, int layer, float* out);
+int fd_ehog_tracker_heat_layer(fd_ctx* ctx, fd_ehog_tracker* t, int layer, float* out);
+
 /* detection::AggregatedFeaturesDetector (AggregatedFeaturesDetector.cpp:37-128) with imageFilter = GrayscaleFilter,
  * layerFilter = FhogFilter on an extraction::AggregatedFeaturesExtractor (AggregatedFeaturesExtractor.cpp:34-130): a linear
  * SVM convolved over the FHOG cell pyramid (ConvolutionFilter.cpp:27-43), windows with score > threshold, bounds through
@@ -436,6 +517,19 @@ int fd_extract_hist(fd_ctx* ctx, fd_pyramid* p, const fd_hist_params* hp, float*
  * pixels, `channels` bytes per pixel: 1 bin, 2 bin + weight, 4 two bins + weights; hp->step_x / step_y are ignored).
  * out: n x fd_hist_feature_length(hp, channels) floats. */
 int fd_hist_patch_batch(fd_ctx* ctx, const uint8_t* bin_patches, int64_t n, int channels, const fd_hist_params* hp, float* out);
+/* imageprocessing::ExtendedHogFilter(binCount, cellWidth, cellHeight, interpolate, signedAndUnsigned, alpha)
+ * (ExtendedHogFilter.cpp:54-209) on n contiguous bin-image patches (patch_w x patch_h pixels, `channels` bytes per pixel as above):
+ * cvRound(patch_h / cell_h) x cvRound(patch_w / cell_w) cell histograms by HistogramFilter::createCellHistograms, then per cell
+ * bins (+ bins / 2 with signed_and_unsigned) + 4 floats in the order [bins][unsigned halves][4 energy features], normalised and
+ * truncated as CompleteExtendedHogFilter's.  cell_h 0: same as cell_w.  The "ehog" feature type of createEHogExtractor is
+ * GradientFilter -> GradientBinningFilter -> this filter. */
+typedef struct {
+    int32_t patch_w, patch_h, bins, cell_w, cell_h, interpolate, signed_and_unsigned;
+    float alpha;
+} fd_ehog_patch_params;
+/* host only: floats per patch; -1 where fd_ehog_patch_batch returns FD_ERR_INVALID_ARGUMENT (a grid with zero rows or columns included) */
+int fd_ehog_feature_length(const fd_ehog_patch_params* ep, int channels);
+int fd_ehog_patch_batch(fd_ctx* ctx, const uint8_t* bin_patches, int64_t n, int channels, const fd_ehog_patch_params* ep, float* out);
 /* SlidingWindowDetector::detect with the histogram patch filter + ProbabilisticSvmClassifier on the f32
  * vectors (any kernel; wiring of BenchmarkRunner.cpp:185-263) */
 int fd_detect_hist_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hist_params* hp, fd_detection* out,
