@@ -6,7 +6,7 @@
 //     so k_fhog_grad's dy * 512 + dx finds the same entry;
 //   - the central differences clamp at the area the cells cover (:126-127), so a layer enters the table with w = cols * cell,
 //     h = rows * cell and its real stride;
-//   - the cell interpolation table is computed in double (createLut, :72-103): k_cehog_coeff instead of k_fhog_coeff;
+//   - the cell interpolation table is computed in double (createLut, :72-103): k_fhog_coeff<double> instead of <float>;
 //   - signed-only / unsigned-only histograms have no unsigned section (D = binCount + 4), and the energy of an unsigned-only
 //     histogram runs over its bins (:181-190): FhogParamsDev::plainEnergy.
 // The normalisers and the 0.5 / 0.2357 factors are read as k_fhog_desc reads them (fp32 1.f / sqrtf, double factors).  DESIGN.md 4.5.
@@ -67,36 +67,6 @@ void cehog_build_lut(const fd_cehog_params& fp, std::vector<CehogBin>& lut) {
     }
 }
 
-// createLut (:72-103) for every pixel row / column the cells of every layer cover, in k_fhog_coeff's storage order (rows in
-// pixel order, columns phase-major).  The index is computed in double and the weights are rounded to float once, as the
-// reference's BinInformation assignment does; double add / divide / floor are correctly rounded on the device.
-__global__ __launch_bounds__(256) void k_cehog_coeff(const FhogLayerDev* __restrict__ layers, int nLayers, int total, FhogParamsDev d,
-                                                     FhogCoeffDev* __restrict__ coeff) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int l = 0;
-    for (int k = 1; k < nLayers; ++k)
-        if (i >= layers[k].coeffBase) l = k;
-    const FhogLayerDev L = layers[l];
-    const int j = i - L.coeffBase, rowPixels = L.rows * d.cell;
-    const int pixel = j < rowPixels ? j : j - rowPixels;
-    const int count = j < rowPixels ? L.rows : L.cols;
-    FhogCoeffDev c;
-    if (d.interpCells) {
-        const double realIndex = ((double)pixel + 0.5) / (double)d.cell - 0.5;
-        int index1 = (int)floor(realIndex);
-        int index2 = index1 + 1;
-        float weight2 = (float)(realIndex - index1);
-        float weight1 = 1.f - weight2;
-        if (index1 < 0) { index1 = index2; weight1 = 0; }
-        else if (index2 >= count) { index2 = index1; weight2 = 0; }
-        c = FhogCoeffDev{index1, index2, weight1, weight2};
-    } else {
-        c = FhogCoeffDev{pixel / d.cell, -1, 1.f, 0.f};
-    }
-    coeff[j < rowPixels ? i : L.coeffBase + rowPixels + (pixel % d.cell) * L.cols + pixel / d.cell] = c;
-}
-
 struct CehogScratch {
     DevBuf lut;
     fd_cehog_params lutFor;
@@ -131,74 +101,39 @@ void cehog_upload_lut(fd_ctx* ctx, CehogScratch& C, const fd_cehog_params& fp) {
 
 // a gray image / layer as an entry of the layer table: the filter never looks past the pixels its cells cover (:111-127)
 FhogLayerDev cehog_layer(const uint8_t* dimg, int w, int h, int stride, int cell) {
-    FhogLayerDev L;
-    std::memset(&L, 0, sizeof(L));
-    L.img = dimg; L.w = (w / cell) * cell; L.h = (h / cell) * cell; L.stride = stride; L.channels = 1;
-    return L;
-}
-
-fd_fhog_params cehog_layout_params(const fd_cehog_params& fp) {   // what layout_layers reads: the cell size
-    fd_fhog_params f;
-    std::memset(&f, 0, sizeof(f));
-    f.cell_size = fp.cell_size;
-    return f;
+    return layer_entry(dimg, (w / cell) * cell, (h / cell) * cell, stride, 1);
 }
 
 // descriptors of every layer of the table at dlayers (entries made by cehog_layer, laid out by layout_layers) into descOut
 // (t.cells * channels floats on the device; NULL: S.desc)
-void run_cehog(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayout& t, const fd_cehog_params& fp,
+void run_cehog(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayoutTotals& t, const fd_cehog_params& fp,
                float* descOut = nullptr) {
     check_cehog_params(fp);
     CehogScratch& C = fd_scratch<CehogScratch>(ctx);
     cehog_upload_lut(ctx, C, fp);
-    if (!descOut) S.descOwner = nullptr;
-    if (t.cells == 0) return;
     const bool both = fp.signed_gradients && fp.unsigned_gradients;
     FhogParamsDev d;
     std::memset(&d, 0, sizeof(d));
     d.cell = fp.cell_size; d.sbins = fp.bin_count; d.D = cehog_channels(fp);
     d.interpBins = fp.interpolate_bins != 0; d.interpCells = fp.interpolate_cells != 0; d.alpha = fp.alpha;
-    S.coeff.reserve(sizeof(FhogCoeffDev) * (size_t)t.coeffs);
-    if (!descOut) {
-        S.desc.reserve(sizeof(float) * (size_t)t.cells * d.D);
-        descOut = S.desc.as<float>();
-    }
-    S.energies.reserve(sizeof(float) * (size_t)t.cells);
-    S.grad.reserve(sizeof(FhogLut) * (size_t)t.pixels);
-    S.hist.reserve(sizeof(float) * (size_t)t.cells * d.sbins);
-    d.lut = C.lut.as<FhogLutEntry>();
-    d.coeff = S.coeff.as<FhogCoeffDev>();
-    hipLaunchKernelGGL(k_cehog_coeff, dim3((t.coeffs + 255) / 256), dim3(256), 0, ctx->stream, dlayers, nLayers, t.coeffs, d, S.coeff.as<FhogCoeffDev>());
-    hipLaunchKernelGGL(k_fhog_grad, dim3(t.pixBlocks), dim3(256), 0, ctx->stream, dlayers, nLayers, d, S.grad.as<FhogLut>());
     // energy (:168-191): over the unsigned halves when the gradients are signed, over the bins otherwise
     FhogParamsDev dh = d;
     dh.ubins = fp.bin_count / 2;
     dh.plainEnergy = fp.signed_gradients ? 0 : 1;
-    hipLaunchKernelGGL(k_fhog_hist, dim3(t.cellBlocks), dim3(64), 0, ctx->stream, dlayers, nLayers, dh, S.grad.as<FhogLut>(), S.hist.as<float>(),
-                       S.energies.as<float>());
     // descriptor (:194-302): [bins][unsigned halves, when both][4 energies]
     FhogParamsDev dd = d;
     dd.ubins = both ? fp.bin_count / 2 : 0;
-    if (d.D <= 32)
-        hipLaunchKernelGGL(k_fhog_desc<32>, dim3((unsigned)(((int64_t)t.cells * 32 + 255) / 256)), dim3(256), 0, ctx->stream, dlayers, nLayers, t.cells, dd,
-                           S.energies.as<float>(), S.hist.as<float>(), descOut);
-    else
-        hipLaunchKernelGGL(k_fhog_desc<64>, dim3((unsigned)(((int64_t)t.cells * 64 + 255) / 256)), dim3(256), 0, ctx->stream, dlayers, nLayers, t.cells, dd,
-                           S.energies.as<float>(), S.hist.as<float>(), descOut);
-    HIP_CHECK(hipGetLastError());
+    run_cell_filter(ctx, S, dlayers, nLayers, t, FhogRun{C.lut.as<FhogLutEntry>(), true, dh, dd}, descOut);
 }
 
-// one gray image already on the device; rows == 0 or cols == 0: nothing is launched
+// one gray image already on the device; an image smaller than a cell is an error
 void run_cehog_single(fd_ctx* ctx, FhogScratch& S, const uint8_t* dimg, int w, int h, int stride, const fd_cehog_params& fp, int& rows, int& cols) {
     check_cehog_params(fp);
-    std::vector<FhogLayerDev> layers(1, cehog_layer(dimg, w, h, stride, fp.cell_size));
-    const FhogLayout t = layout_layers(layers, cehog_layout_params(fp));
-    rows = layers[0].rows; cols = layers[0].cols;
+    FhogLayerDev L = cehog_layer(dimg, w, h, stride, fp.cell_size);
+    const FhogLayoutTotals t = single_layer_table(ctx, S.layers, L, fp.cell_size);
+    rows = L.rows; cols = L.cols;
     if (rows == 0 || cols == 0)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "CompleteExtendedHogFilter: the image (%d x %d) is smaller than a cell (%d)", w, h, fp.cell_size);
-    S.layers.reserve(sizeof(FhogLayerDev));
-    HIP_CHECK(hipMemcpyAsync(S.layers.p, layers.data(), sizeof(FhogLayerDev), hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // `layers` is pageable host memory
     run_cehog(ctx, S, S.layers.as<FhogLayerDev>(), 1, t, fp);
 }
 

@@ -62,10 +62,7 @@ __global__ __launch_bounds__(256) void k_ehog_heat(const FhogLayerDev* __restric
     const bool valid = g < totalCells;
     float sacc = 0.f;
     if (valid && c < D) {
-        int l = 0;
-        for (int i = 1; i < nLayers; ++i)
-            if (g >= layers[i].cellBase) l = i;
-        const FhogLayerDev L = layers[l];
+        const FhogLayerDev L = layers[layer_of<&FhogLayerDev::cellBase>(layers, nLayers, g)];
         const int cellId = g - L.cellBase;
         const int y = cellId / L.cols, x = cellId - y * L.cols;
         const int ay = kh / 2, ax = kw / 2;
@@ -163,10 +160,7 @@ __global__ __launch_bounds__(256) void k_ehog_maxima(const FhogLayerDev* __restr
                                                      const float* __restrict__ heat, EhogMaxDev* __restrict__ out, unsigned int* __restrict__ count) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= totalPos) return;
-    int l = 0;
-    for (int i = 1; i < nLayers; ++i)
-        if (p >= layers[i].posBase) l = i;
-    const FhogLayerDev L = layers[l];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::posBase>(layers, nLayers, p)];
     const int i = p - L.posBase;
     const int y = i / L.vw + cr, x = i - (i / L.vw) * L.vw + cc;
     const float* row = heat + (size_t)L.cellBase + (size_t)y * L.cols;
@@ -221,6 +215,7 @@ __global__ __launch_bounds__(64) void k_ehog_patch(const FhogLayerDev* __restric
     const int off = G.interpCells ? (cs + 1) / 2 + 1 : 0, box = cs + 2 * off;
     for (int cell = lane; cell < nCells; cell += 64) {
         const int r = cell / G.PC, c = cell - r * G.PC;
+        auto bin = [&](int b) -> float& { return hist[b * nCells + cell]; };
         for (int ii = 0; ii < box; ++ii) {
             const int y = r * cs - off + ii;
             if (y < 0 || y >= G.PH) continue;
@@ -240,26 +235,10 @@ __global__ __launch_bounds__(64) void k_ehog_patch(const FhogLayerDev* __restric
                 const int dx = (int)mid[min(x + 1, G.PW - 1)] - (int)mid[max(x - 1, 0)] + 256;
                 const int dy = (int)dn[x] - (int)up[x] + 256;
                 const FhogLut e = lut[dy * 512 + dx].bins;
-                if (G.interpCells) {
-                    const float wc = (c1 ? cc.weight1 : 0.f) + (c2 ? cc.weight2 : 0.f);
-                    hist[e.index1 * nCells + cell] = hist[e.index1 * nCells + cell] + e.weight1 * wr * wc;
-                    if (G.interpBins) hist[e.index2 * nCells + cell] = hist[e.index2 * nCells + cell] + e.weight2 * wr * wc;
-                } else {
-                    hist[e.index1 * nCells + cell] = hist[e.index1 * nCells + cell] + e.weight1;
-                    if (G.interpBins) hist[e.index2 * nCells + cell] = hist[e.index2 * nCells + cell] + e.weight2;
-                }
+                fhog_vote(bin, e, wr, cc, c1, c2, G.interpCells, G.interpBins);
             }
         }
-        float en = 0.f;
-        if (G.plainEnergy) {
-            for (int b = 0; b < G.bins; ++b) en = en + hist[b * nCells + cell] * hist[b * nCells + cell];
-        } else {
-            for (int b = 0; b < G.half; ++b) {
-                const float u = hist[b * nCells + cell] + hist[(b + G.half) * nCells + cell];
-                en = en + u * u;
-            }
-        }
-        energy[cell] = en;
+        energy[cell] = fhog_energy(bin, G.bins, G.half, G.plainEnergy);
     }
     __syncthreads();
     const int ub = G.both ? G.half : 0;
@@ -267,30 +246,9 @@ __global__ __launch_bounds__(64) void k_ehog_patch(const FhogLayerDev* __restric
         const int ic = e / G.D, f = e - ic * G.D;
         const int r = ic / G.cols + 1, c = ic - (ic / G.cols) * G.cols + 1;
         const int cell = r * G.PC + c;
-        const int pr = max(r - 1, 0), nr = min(r + 1, G.PR - 1), pc = max(c - 1, 0), nc = min(c + 1, G.PC - 1);
-        auto E = [&](int rr, int cc) { return energy[rr * G.PC + cc]; };
-        const float eps = 1e-4f;
         float n[4];
-        n[0] = 1.f / sqrtf(E(pr, pc) + E(pr, c) + E(r, pc) + E(r, c) + eps);
-        n[1] = 1.f / sqrtf(E(pr, c) + E(pr, nc) + E(r, c) + E(r, nc) + eps);
-        n[2] = 1.f / sqrtf(E(r, pc) + E(r, c) + E(nr, pc) + E(nr, c) + eps);
-        n[3] = 1.f / sqrtf(E(r, c) + E(r, nc) + E(nr, c) + E(nr, nc) + eps);
-        float out;
-        if (f < G.bins) {
-            const float v = hist[f * nCells + cell];
-            const float v0 = fminf(G.alpha, n[0] * v), v1 = fminf(G.alpha, n[1] * v), v2 = fminf(G.alpha, n[2] * v), v3 = fminf(G.alpha, n[3] * v);
-            out = (float)(0.5 * (double)(v0 + v1 + v2 + v3));
-        } else if (f < G.bins + ub) {
-            const int b = f - G.bins;
-            const float v = hist[b * nCells + cell] + hist[(b + G.half) * nCells + cell];
-            const float s = fminf(G.alpha, n[0] * v) + fminf(G.alpha, n[1] * v) + fminf(G.alpha, n[2] * v) + fminf(G.alpha, n[3] * v);
-            out = (float)(0.5 * (double)s);
-        } else {
-            const float ni = n[f - G.bins - ub];
-            float t = 0.f;
-            for (int b = 0; b < G.bins; ++b) t = t + fminf(G.alpha, ni * hist[b * nCells + cell]);
-            out = (float)(0.2357 * (double)t);
-        }
+        fhog_normalizers([&](int rr, int cc) { return energy[rr * G.PC + cc]; }, r, c, G.PR, G.PC, n);
+        const float out = fhog_feature([&](int b) { return hist[b * nCells + cell]; }, n, f, G.bins, ub, G.alpha);
         desc[e] = out;
         features[(size_t)i * nInner + e] = out;
     }
@@ -453,19 +411,10 @@ int fd_ehog_tracker_create(fd_ctx* ctx, const fd_ehog_tracker_params* prm, fd_eh
         ehog_pyramid_limits(*prm, t->minScale, t->maxScale);
         t->geom = ehog_patch_geom(*prm);
         if ((size_t)t->geom.bytes <= EHOG_PATCH_LDS_BUDGET) {   // createLut (CompleteExtendedHogFilter.cpp:72-103) of the patch's rows and columns
-            const EhogPatchGeom& G = t->geom;                   // in k_cehog_coeff's storage order: it depends on the geometry alone
+            const EhogPatchGeom& G = t->geom;                   // in k_fhog_coeff's storage order: it depends on the geometry alone
             std::vector<FhogCoeffDev> coeff((size_t)G.PH + G.PW);
-            auto entry = [&](int pixel, int count) {
-                if (!G.interpCells) return FhogCoeffDev{pixel / G.cell, -1, 1.f, 0.f};
-                const double realIndex = ((double)pixel + 0.5) / (double)G.cell - 0.5;
-                int index1 = (int)std::floor(realIndex), index2 = index1 + 1;
-                float weight2 = (float)(realIndex - index1), weight1 = 1.f - weight2;
-                if (index1 < 0) { index1 = index2; weight1 = 0; }
-                else if (index2 >= count) { index2 = index1; weight2 = 0; }
-                return FhogCoeffDev{index1, index2, weight1, weight2};
-            };
-            for (int y = 0; y < G.PH; ++y) coeff[y] = entry(y, G.PR);
-            for (int x = 0; x < G.PW; ++x) coeff[(size_t)G.PH + (x % G.cell) * G.PC + x / G.cell] = entry(x, G.PC);
+            for (int y = 0; y < G.PH; ++y) coeff[y] = cell_coeff<double>(y, G.cell, G.PR, G.interpCells);
+            for (int x = 0; x < G.PW; ++x) coeff[(size_t)G.PH + (x % G.cell) * G.PC + x / G.cell] = cell_coeff<double>(x, G.cell, G.PC, G.interpCells);
             t->patchCoeff.reserve(sizeof(FhogCoeffDev) * coeff.size());
             HIP_CHECK(hipMemcpy(t->patchCoeff.p, coeff.data(), sizeof(FhogCoeffDev) * coeff.size(), hipMemcpyHostToDevice));
         }
@@ -512,7 +461,7 @@ int fd_ehog_tracker_update(fd_ctx* ctx, fd_ehog_tracker* t, const uint8_t* image
                 t->layerTable.push_back(T);
                 t->layerPx.push_back(EhogLayerPx{H.w, H.h});
             }
-            t->layout = layout_layers(t->layerTable, cehog_layout_params(P.filter));
+            t->layout = layout_layers(t->layerTable, P.filter.cell_size);
             t->dlayers.reserve(sizeof(FhogLayerDev) * t->layerTable.size());
             HIP_CHECK(hipMemcpy(t->dlayers.p, t->layerTable.data(), sizeof(FhogLayerDev) * t->layerTable.size(), hipMemcpyHostToDevice));
             t->dlayerPx.reserve(sizeof(EhogLayerPx) * t->layerPx.size());

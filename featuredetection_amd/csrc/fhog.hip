@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 struct FhogLut {   // (bin, weight) of a gradient: what k_fhog_hist consumes per pixel
     uint8_t index1, index2;
@@ -98,11 +99,97 @@ using namespace fd_dev;
 constexpr int FHOG_MAX_SBINS = 36;
 constexpr int FHOG_CH = 6;         // pixels whose loads are in flight together in k_fhog_hist
 
-__device__ __forceinline__ int layer_of_block(const FhogLayerDev* __restrict__ layers, int nLayers, int block, bool cells) {
+// the layer of a launch-wide index (a block, cell, coefficient, pixel block or position): the last one whose Base is not above it
+template <int32_t FhogLayerDev::*Base>
+__device__ __forceinline__ int layer_of(const FhogLayerDev* __restrict__ layers, int nLayers, int key) {
     int l = 0;
     for (int i = 1; i < nLayers; ++i)
-        if (block >= (cells ? layers[i].cellBlockBase : layers[i].posBlockBase)) l = i;
+        if (key >= layers[i].*Base) l = i;
     return l;
+}
+
+// createInterpolationCoefficients (FhogFilter.cpp:74-98, Real = float) and createLut (CompleteExtendedHogFilter.cpp:72-103,
+// Real = double: the index in double, the weights rounded to float once) for one pixel row / column of sizeInCells cells.
+// Add / divide / floor of both types are correctly rounded on the device (no fast-math), so a device table equals the host's.
+template <typename Real>
+__host__ __device__ inline FhogCoeffDev cell_coeff(int pixel, int cell, int sizeInCells, bool interpCells) {
+    if (!interpCells) return FhogCoeffDev{pixel / cell, -1, 1.f, 0.f};
+    const Real realCellIndex = ((Real)pixel + (Real)0.5) / (Real)cell - (Real)0.5;
+    int index1 = (int)std::floor(realCellIndex);
+    int index2 = index1 + 1;
+    float weight2 = (float)(realCellIndex - index1);
+    float weight1;   // the one place the two filters differ
+    if constexpr (std::is_same<Real, float>::value) weight1 = index2 - realCellIndex;
+    else weight1 = 1.f - weight2;
+    if (index1 < 0) { index1 = index2; weight1 = 0; }
+    else if (index2 >= sizeInCells) { index2 = index1; weight2 = 0; }
+    return FhogCoeffDev{index1, index2, weight1, weight2};
+}
+
+// ---- the arithmetic k_fhog_hist / k_fhog_desc share with k_ehog_patch (ehog_tracker.hpp); `hist(b)` is bin b of the cell's
+// histogram ([bin][lane] in LDS, [bin * nCells + cell] in LDS, or the cell's run of the raw histograms) ----
+
+// one pixel's vote into a cell it reaches through row weight wr and column coefficients cc (c1 / c2: which of its two indices
+// is the cell): FhogFilter.hpp:174-207
+template <class Hist>
+__device__ __forceinline__ void fhog_vote(Hist&& hist, const FhogLut& e, float wr, const FhogCoeffDev& cc, bool c1, bool c2, bool interpCells,
+                                          bool interpBins) {
+    if (interpCells) {
+        const float wc = (c1 ? cc.weight1 : 0.f) + (c2 ? cc.weight2 : 0.f);
+        hist(e.index1) = hist(e.index1) + e.weight1 * wr * wc;
+        if (interpBins) hist(e.index2) = hist(e.index2) + e.weight2 * wr * wc;
+    } else {
+        hist(e.index1) = hist(e.index1) + e.weight1;
+        if (interpBins) hist(e.index2) = hist(e.index2) + e.weight2;
+    }
+}
+
+// computeGradientEnergy (FhogAggregationFilter.cpp:53-61): over the unsigned halves; plainEnergy: over the sbins bins themselves
+// (CompleteExtendedHogFilter.cpp:181-190, unsigned-only histograms)
+template <class Hist>
+__device__ __forceinline__ float fhog_energy(Hist&& hist, int sbins, int ubins, bool plainEnergy) {
+    float energy = 0.f;
+    if (plainEnergy) {
+        for (int b = 0; b < sbins; ++b) energy = energy + hist(b) * hist(b);
+    } else {
+        for (int b = 0; b < ubins; ++b) {
+            const float u = hist(b) + hist(b + ubins);
+            energy = energy + u * u;
+        }
+    }
+    return energy;
+}
+
+// computeNormalizers (FhogAggregationFilter.cpp:77-99) of cell (r, c) of a rows x cols map; E(r, c) is a cell's energy
+template <class Energy>
+__device__ __forceinline__ void fhog_normalizers(Energy&& E, int r, int c, int rows, int cols, float n[4]) {
+    const int pr = max(r - 1, 0), nr = min(r + 1, rows - 1), pc = max(c - 1, 0), nc = min(c + 1, cols - 1);
+    const float eps = 1e-4f;
+    n[0] = 1.f / sqrtf(E(pr, pc) + E(pr, c) + E(r, pc) + E(r, c) + eps);
+    n[1] = 1.f / sqrtf(E(pr, c) + E(pr, nc) + E(r, c) + E(r, nc) + eps);
+    n[2] = 1.f / sqrtf(E(r, pc) + E(r, c) + E(nr, pc) + E(nr, c) + eps);
+    n[3] = 1.f / sqrtf(E(r, c) + E(r, nc) + E(nr, c) + E(nr, nc) + eps);
+}
+
+// computeDescriptor (FhogAggregationFilter.cpp:101-148), feature f of [sbins bins][ubins unsigned sums][4 energies]; 0.5 and
+// 0.2357 are double literals
+template <class Hist>
+__device__ __forceinline__ float fhog_feature(Hist&& hist, const float n[4], int f, int sbins, int ubins, float alpha) {
+    if (f < sbins) {
+        const float v = hist(f);
+        const float v0 = fminf(alpha, n[0] * v), v1 = fminf(alpha, n[1] * v), v2 = fminf(alpha, n[2] * v), v3 = fminf(alpha, n[3] * v);
+        return (float)(0.5 * (double)(v0 + v1 + v2 + v3));
+    }
+    if (f < sbins + ubins) {
+        const int b = f - sbins;
+        const float v = hist(b) + hist(b + ubins);
+        const float s = fminf(alpha, n[0] * v) + fminf(alpha, n[1] * v) + fminf(alpha, n[2] * v) + fminf(alpha, n[3] * v);
+        return (float)(0.5 * (double)s);
+    }
+    const float ni = n[f - sbins - ubins];
+    float energy = 0.f;
+    for (int b = 0; b < sbins; ++b) energy = energy + fminf(alpha, ni * hist(b));
+    return (float)(0.2357 * (double)energy);
 }
 
 // (bin, weight) entries of every pixel the cells cover: the gradient of FhogFilter.hpp:120-160 (central differences,
@@ -112,10 +199,7 @@ __device__ __forceinline__ int layer_of_block(const FhogLayerDev* __restrict__ l
 // same in-cell offset of consecutive cells, read consecutive entries (a lane-per-cell walk over a row-major map touches 64
 // cache lines per load and is bound by the L1 tag rate).  Thread order == storage order: coalesced writes.
 __global__ __launch_bounds__(256) void k_fhog_grad(const FhogLayerDev* __restrict__ layers, int nLayers, FhogParamsDev d, FhogLut* __restrict__ grad) {
-    int l = 0;
-    for (int i = 1; i < nLayers; ++i)
-        if ((int)blockIdx.x >= layers[i].pixBlockBase) l = i;
-    const FhogLayerDev L = layers[l];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::pixBlockBase>(layers, nLayers, blockIdx.x)];
     const int W = L.cols * d.cell, H = L.rows * d.cell;
     const int i = (blockIdx.x - L.pixBlockBase) * 256 + threadIdx.x;
     if (i >= W * H) return;
@@ -143,46 +227,31 @@ __global__ __launch_bounds__(256) void k_fhog_grad(const FhogLayerDev* __restric
     grad[(size_t)L.pixBase + i] = e;
 }
 
-// createInterpolationCoefficients (FhogFilter.cpp:74-98), one thread per pixel row / column of every layer.
-// fp32 add / divide / floor are correctly rounded on the device (no fast-math), so the table equals the host's.
+// cell_coeff<Real> for every pixel row / column the cells of every layer cover, one thread each
+template <typename Real>
 __global__ __launch_bounds__(256) void k_fhog_coeff(const FhogLayerDev* __restrict__ layers, int nLayers, int total, FhogParamsDev d,
                                                     FhogCoeffDev* __restrict__ coeff) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    int l = 0;
-    for (int k = 1; k < nLayers; ++k)
-        if (i >= layers[k].coeffBase) l = k;
-    const FhogLayerDev L = layers[l];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::coeffBase>(layers, nLayers, i)];
     const int j = i - L.coeffBase, rowPixels = L.rows * d.cell;
     const int pixel = j < rowPixels ? j : j - rowPixels;
-    const int sizeInCells = j < rowPixels ? L.rows : L.cols;
-    FhogCoeffDev c;
-    if (d.interpCells) {
-        const float realCellIndex = (pixel + 0.5f) / d.cell - 0.5f;
-        int index1 = (int)floorf(realCellIndex);
-        int index2 = index1 + 1;
-        float weight2 = realCellIndex - index1;
-        float weight1 = index2 - realCellIndex;
-        if (index1 < 0) { index1 = index2; weight1 = 0; }
-        else if (index2 >= sizeInCells) { index2 = index1; weight2 = 0; }
-        c = FhogCoeffDev{index1, index2, weight1, weight2};
-    } else {
-        c = FhogCoeffDev{pixel / d.cell, -1, 1.f, 0.f};
-    }
     // rows in pixel order; columns phase-major ([x % cell][x / cell]) like the gradient map
-    coeff[j < rowPixels ? i : L.coeffBase + rowPixels + (pixel % d.cell) * L.cols + pixel / d.cell] = c;
+    coeff[j < rowPixels ? i : L.coeffBase + rowPixels + (pixel % d.cell) * L.cols + pixel / d.cell] =
+        cell_coeff<Real>(pixel, d.cell, j < rowPixels ? L.rows : L.cols, d.interpCells);
 }
 
 __global__ __launch_bounds__(64) void k_fhog_hist(const FhogLayerDev* __restrict__ layers, int nLayers, FhogParamsDev d,
                                                   const FhogLut* __restrict__ gradAll, float* __restrict__ rawHist, float* __restrict__ energies) {
     __shared__ float hist[FHOG_MAX_SBINS][64];
-    const FhogLayerDev L = layers[layer_of_block(layers, nLayers, blockIdx.x, true)];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::cellBlockBase>(layers, nLayers, blockIdx.x)];
     const int lane = threadIdx.x;
     const int cellId = (blockIdx.x - L.cellBlockBase) * 64 + lane;
     const bool valid = cellId < L.rows * L.cols;
     const int r = valid ? cellId / L.cols : 0, c = valid ? cellId - r * L.cols : 0;
     for (int b = 0; b < d.sbins; ++b) hist[b][lane] = 0.f;
     if (valid) {
+        auto bin = [&](int b) -> float& { return hist[b][lane]; };
         const FhogCoeffDev* __restrict__ rowCoeff = d.coeff + L.coeffBase;
         const FhogCoeffDev* __restrict__ colCoeff = rowCoeff + L.rows * d.cell;
         // pixel box feeding this cell: non-interpolated [r*cell, (r+1)*cell); interpolated: every pixel whose index1 or index2
@@ -222,27 +291,11 @@ __global__ __launch_bounds__(64) void k_fhog_hist(const FhogLayerDev* __restrict
                 for (int j = 0; j < FHOG_CH; ++j) {
                     const bool c1 = cc[j].index1 == c, c2 = d.interpCells && cc[j].index2 == c;
                     if (!in[j] || (!c1 && !c2)) continue;
-                    if (d.interpCells) {
-                        const float wc = (c1 ? cc[j].weight1 : 0.f) + (c2 ? cc[j].weight2 : 0.f);
-                        hist[e[j].index1][lane] = hist[e[j].index1][lane] + e[j].weight1 * wr * wc;
-                        if (d.interpBins) hist[e[j].index2][lane] = hist[e[j].index2][lane] + e[j].weight2 * wr * wc;
-                    } else {
-                        hist[e[j].index1][lane] = hist[e[j].index1][lane] + e[j].weight1;
-                        if (d.interpBins) hist[e[j].index2][lane] = hist[e[j].index2][lane] + e[j].weight2;
-                    }
+                    fhog_vote(bin, e[j], wr, cc[j], c1, c2, d.interpCells, d.interpBins);
                 }
             }
         }
-        float energy = 0.f;   // computeGradientEnergy, FhogAggregationFilter.cpp:53-61
-        if (d.plainEnergy) {  // CompleteExtendedHogFilter.cpp:181-190
-            for (int b = 0; b < d.sbins; ++b) energy = energy + hist[b][lane] * hist[b][lane];
-        } else {
-            for (int b = 0; b < d.ubins; ++b) {
-                const float u = hist[b][lane] + hist[b + d.ubins][lane];
-                energy = energy + u * u;
-            }
-        }
-        energies[L.cellBase + cellId] = energy;
+        energies[L.cellBase + cellId] = fhog_energy(bin, d.sbins, d.ubins, d.plainEnergy);
     }
     // raw histograms [cell][2B] of the block's 64 consecutive cells, written as one contiguous run
     wave_sync();
@@ -262,39 +315,14 @@ __global__ __launch_bounds__(256) void k_fhog_desc(const FhogLayerDev* __restric
                                                    const float* __restrict__ energiesAll, const float* __restrict__ rawHist, float* __restrict__ descAll) {
     const int g = (blockIdx.x * 256 + threadIdx.x) / LPC, f = threadIdx.x & (LPC - 1);
     if (g >= totalCells || f >= d.D) return;
-    int l = 0;
-    for (int i = 1; i < nLayers; ++i)
-        if (g >= layers[i].cellBase) l = i;
-    const FhogLayerDev L = layers[l];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::cellBase>(layers, nLayers, g)];
     const int cellId = g - L.cellBase;
     const float* energies = energiesAll + L.cellBase;
-    const int r = cellId / L.cols, c = cellId - r * L.cols;
-    const int pr = max(r - 1, 0), nr = min(r + 1, L.rows - 1), pc = max(c - 1, 0), nc = min(c + 1, L.cols - 1);
-    auto E = [&](int rr, int cc) { return energies[rr * L.cols + cc]; };
-    const float eps = 1e-4f;
-    float n[4];   // computeNormalizers, FhogAggregationFilter.cpp:77-99
-    n[0] = 1.f / sqrtf(E(pr, pc) + E(pr, c) + E(r, pc) + E(r, c) + eps);
-    n[1] = 1.f / sqrtf(E(pr, c) + E(pr, nc) + E(r, c) + E(r, nc) + eps);
-    n[2] = 1.f / sqrtf(E(r, pc) + E(r, c) + E(nr, pc) + E(nr, c) + eps);
-    n[3] = 1.f / sqrtf(E(r, c) + E(r, nc) + E(nr, c) + E(nr, nc) + eps);
     const float* h = rawHist + (size_t)g * d.sbins;
-    float out;   // computeDescriptor, :101-148 (0.5 and 0.2357 are double literals)
-    if (f < d.sbins) {
-        const float v = h[f];
-        const float v0 = fminf(d.alpha, n[0] * v), v1 = fminf(d.alpha, n[1] * v), v2 = fminf(d.alpha, n[2] * v), v3 = fminf(d.alpha, n[3] * v);
-        out = (float)(0.5 * (double)(v0 + v1 + v2 + v3));
-    } else if (f < d.sbins + d.ubins) {
-        const int b = f - d.sbins;
-        const float v = h[b] + h[b + d.ubins];
-        const float s = fminf(d.alpha, n[0] * v) + fminf(d.alpha, n[1] * v) + fminf(d.alpha, n[2] * v) + fminf(d.alpha, n[3] * v);
-        out = (float)(0.5 * (double)s);
-    } else {
-        const float ni = n[f - d.sbins - d.ubins];
-        float energy = 0.f;
-        for (int b = 0; b < d.sbins; ++b) energy = energy + fminf(d.alpha, ni * h[b]);
-        out = (float)(0.2357 * (double)energy);
-    }
-    descAll[(size_t)g * d.D + f] = out;
+    const int r = cellId / L.cols, c = cellId - r * L.cols;
+    float n[4];
+    fhog_normalizers([&](int rr, int cc) { return energies[rr * L.cols + cc]; }, r, c, L.rows, L.cols, n);
+    descAll[(size_t)g * d.D + f] = fhog_feature([&](int b) { return h[b]; }, n, f, d.sbins, d.ubins, d.alpha);
 }
 
 struct FhogScratch {
@@ -351,21 +379,28 @@ void check_fhog_params(const fd_fhog_params& fp) {
     if (!(fp.alpha > 0)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "FhogAggregationFilter: alpha must be bigger than zero, but was: %g", (double)fp.alpha);
 }
 
-// fills the launch-wide offsets of a layer list (img, w, h, stride, vw, vh set by the caller); returns total cells
-using FhogLayout = FhogLayoutTotals;
-FhogLayout layout_layers(std::vector<FhogLayerDev>& layers, const fd_fhog_params& fp) {
-    FhogLayout t;
+// a gray / interleaved / planar image on the device as an entry of a layer list
+FhogLayerDev layer_entry(const uint8_t* dimg, int w, int h, int stride, int channels) {
+    FhogLayerDev L;
+    std::memset(&L, 0, sizeof(L));
+    L.img = dimg; L.w = w; L.h = h; L.stride = stride; L.channels = channels;
+    return L;
+}
+
+// fills the launch-wide offsets of a layer list (img, w, h, stride, vw, vh set by the caller); returns the launch-wide totals
+FhogLayoutTotals layout_layers(std::vector<FhogLayerDev>& layers, int cell) {
+    FhogLayoutTotals t;
     for (FhogLayerDev& L : layers) {
-        L.rows = L.h / fp.cell_size;
-        L.cols = L.w / fp.cell_size;
+        L.rows = L.h / cell;
+        L.cols = L.w / cell;
         L.cellBase = t.cells; L.coeffBase = t.coeffs; L.cellBlockBase = t.cellBlocks; L.posBase = t.positions; L.posBlockBase = t.posBlocks;
         L.pixBase = t.pixels; L.pixBlockBase = t.pixBlocks;
-        const int64_t npix = (int64_t)L.rows * L.cols * fp.cell_size * fp.cell_size;
+        const int64_t npix = (int64_t)L.rows * L.cols * cell * cell;
         if (t.pixels + npix > (int64_t)0x7fffff00) FD_THROW(FD_ERR_INVALID_ARGUMENT, "FhogFilter: the layers of one launch exceed 2^31 pixels");
         t.pixels += (int)npix;
         t.pixBlocks += (int)((npix + 255) / 256);
         t.cells += L.rows * L.cols;
-        t.coeffs += (L.rows + L.cols) * fp.cell_size;
+        t.coeffs += (L.rows + L.cols) * cell;
         t.cellBlocks += (L.rows * L.cols + 63) / 64;
         t.positions += L.vw * L.vh;
         t.posBlocks += (((L.vw + 3) / 4) * L.vh + 7) / 8;   // k_fhog_score: 8 groups of FHOG_SP = 4 positions per block
@@ -373,50 +408,72 @@ FhogLayout layout_layers(std::vector<FhogLayerDev>& layers, const fd_fhog_params
     return t;
 }
 
-// descriptors of every layer of the table at dlayers (device copy of `layers`, laid out by layout_layers) into S.desc
-FhogParamsDev run_fhog(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayout& t, const fd_fhog_params& fp) {
+// one image already on the device as a one-entry layer table: L (made by layer_entry) laid out and uploaded to dtable
+FhogLayoutTotals single_layer_table(fd_ctx* ctx, DevBuf& dtable, FhogLayerDev& L, int cell) {
+    std::vector<FhogLayerDev> layers(1, L);
+    const FhogLayoutTotals t = layout_layers(layers, cell);
+    L = layers[0];
+    dtable.reserve(sizeof(FhogLayerDev));
+    HIP_CHECK(hipMemcpyAsync(dtable.p, &L, sizeof(FhogLayerDev), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // L is pageable host memory
+    return t;
+}
+
+// What a filter of the family hands run_cell_filter: its gradient look-up table on the device, whether its cell interpolation
+// table is computed in double, and the parameters of k_fhog_hist and of k_fhog_desc (their lut and coeff are filled in by the
+// runner; the coefficient and gradient kernels read cell, interpCells and lut, which the two blocks share).
+struct FhogRun {
+    const FhogLutEntry* lut;
+    bool doubleCoeff;
+    FhogParamsDev hist, desc;
+};
+
+// descriptors of every layer of the table at dlayers (device copy of a list laid out by layout_layers) into descOut
+// (t.cells * channels floats on the device; NULL: S.desc)
+void run_cell_filter(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayoutTotals& t, FhogRun f, float* descOut) {
+    if (!descOut) S.descOwner = nullptr;
+    if (t.cells == 0) return;
+    S.coeff.reserve(sizeof(FhogCoeffDev) * (size_t)t.coeffs);
+    if (!descOut) {
+        S.desc.reserve(sizeof(float) * (size_t)t.cells * f.desc.D);
+        descOut = S.desc.as<float>();
+    }
+    S.energies.reserve(sizeof(float) * (size_t)t.cells);
+    S.grad.reserve(sizeof(FhogLut) * (size_t)t.pixels);
+    S.hist.reserve(sizeof(float) * (size_t)t.cells * f.hist.sbins);
+    f.hist.lut = f.desc.lut = f.lut;
+    f.hist.coeff = f.desc.coeff = S.coeff.as<FhogCoeffDev>();
+    const auto coeffKernel = f.doubleCoeff ? k_fhog_coeff<double> : k_fhog_coeff<float>;
+    hipLaunchKernelGGL(coeffKernel, dim3((t.coeffs + 255) / 256), dim3(256), 0, ctx->stream, dlayers, nLayers, t.coeffs, f.hist, S.coeff.as<FhogCoeffDev>());
+    hipLaunchKernelGGL(k_fhog_grad, dim3(t.pixBlocks), dim3(256), 0, ctx->stream, dlayers, nLayers, f.hist, S.grad.as<FhogLut>());
+    hipLaunchKernelGGL(k_fhog_hist, dim3(t.cellBlocks), dim3(64), 0, ctx->stream, dlayers, nLayers, f.hist, S.grad.as<FhogLut>(), S.hist.as<float>(),
+                       S.energies.as<float>());
+    const int LPC = f.desc.D <= 32 ? 32 : 64;   // lanes per cell of k_fhog_desc
+    const auto descKernel = LPC == 32 ? k_fhog_desc<32> : k_fhog_desc<64>;
+    hipLaunchKernelGGL(descKernel, dim3((unsigned)(((int64_t)t.cells * LPC + 255) / 256)), dim3(256), 0, ctx->stream, dlayers, nLayers, t.cells, f.desc,
+                       S.energies.as<float>(), S.hist.as<float>(), descOut);
+    HIP_CHECK(hipGetLastError());
+}
+
+// FhogFilter descriptors of every layer of the table at dlayers into S.desc
+void run_fhog(fd_ctx* ctx, FhogScratch& S, const FhogLayerDev* dlayers, int nLayers, const FhogLayoutTotals& t, const fd_fhog_params& fp) {
     check_fhog_params(fp);
     build_lut(ctx, S, fp);
-    S.descOwner = nullptr;
     FhogParamsDev d;
     std::memset(&d, 0, sizeof(d));
     d.cell = fp.cell_size; d.ubins = fp.unsigned_bins; d.sbins = 2 * fp.unsigned_bins; d.D = 3 * fp.unsigned_bins + 4;
     d.interpBins = fp.interpolate_bins != 0; d.interpCells = fp.interpolate_cells != 0; d.alpha = fp.alpha;
-    if (t.cells == 0) return d;
-    S.coeff.reserve(sizeof(FhogCoeffDev) * (size_t)t.coeffs);
-    S.desc.reserve(sizeof(float) * (size_t)t.cells * d.D);
-    S.energies.reserve(sizeof(float) * (size_t)t.cells);
-    S.grad.reserve(sizeof(FhogLut) * (size_t)t.pixels);
-    S.hist.reserve(sizeof(float) * (size_t)t.cells * d.sbins);
-    d.lut = S.lut.as<FhogLutEntry>();
-    d.coeff = S.coeff.as<FhogCoeffDev>();
-    hipLaunchKernelGGL(k_fhog_coeff, dim3((t.coeffs + 255) / 256), dim3(256), 0, ctx->stream, dlayers, nLayers, t.coeffs, d, S.coeff.as<FhogCoeffDev>());
-    hipLaunchKernelGGL(k_fhog_grad, dim3(t.pixBlocks), dim3(256), 0, ctx->stream, dlayers, nLayers, d, S.grad.as<FhogLut>());
-    hipLaunchKernelGGL(k_fhog_hist, dim3(t.cellBlocks), dim3(64), 0, ctx->stream, dlayers, nLayers, d, S.grad.as<FhogLut>(), S.hist.as<float>(),
-                       S.energies.as<float>());
-    if (d.D <= 32)
-        hipLaunchKernelGGL(k_fhog_desc<32>, dim3((unsigned)(((int64_t)t.cells * 32 + 255) / 256)), dim3(256), 0, ctx->stream, dlayers, nLayers, t.cells, d,
-                           S.energies.as<float>(), S.hist.as<float>(), S.desc.as<float>());
-    else
-        hipLaunchKernelGGL(k_fhog_desc<64>, dim3((unsigned)(((int64_t)t.cells * 64 + 255) / 256)), dim3(256), 0, ctx->stream, dlayers, nLayers, t.cells, d,
-                           S.energies.as<float>(), S.hist.as<float>(), S.desc.as<float>());
-    HIP_CHECK(hipGetLastError());
-    return d;
+    run_cell_filter(ctx, S, dlayers, nLayers, t, FhogRun{S.lut.as<FhogLutEntry>(), false, d, d}, nullptr);
 }
 
-// one gray image already on the device
+// one gray or BGR image already on the device; an image smaller than a cell has an empty map: nothing is launched
 void run_fhog_single(fd_ctx* ctx, FhogScratch& S, const uint8_t* dimg, int w, int h, int stride, const fd_fhog_params& fp, int& rows, int& cols,
                      int channels = 1) {
     check_fhog_params(fp);
-    std::vector<FhogLayerDev> layers(1);
-    std::memset(&layers[0], 0, sizeof(FhogLayerDev));
-    layers[0].img = dimg; layers[0].w = w; layers[0].h = h; layers[0].stride = stride; layers[0].channels = channels;
-    const FhogLayout t = layout_layers(layers, fp);
-    rows = layers[0].rows; cols = layers[0].cols;
+    FhogLayerDev L = layer_entry(dimg, w, h, stride, channels);
+    const FhogLayoutTotals t = single_layer_table(ctx, S.layers, L, fp.cell_size);
+    rows = L.rows; cols = L.cols;
     if (rows == 0 || cols == 0) return;
-    S.layers.reserve(sizeof(FhogLayerDev));
-    HIP_CHECK(hipMemcpyAsync(S.layers.p, layers.data(), sizeof(FhogLayerDev), hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // `layers` is pageable host memory
     run_fhog(ctx, S, S.layers.as<FhogLayerDev>(), 1, t, fp);
 }
 
@@ -431,7 +488,7 @@ constexpr int FHOG_SP = 4;
 __global__ __launch_bounds__(256) void k_fhog_score(const FhogLayerDev* __restrict__ layers, int nLayers, const float* __restrict__ descAll, int D,
                                                     const float* __restrict__ K, int kh, int kw, float delta, float* __restrict__ scores) {
     __shared__ float part[8][FHOG_SP][33];
-    const FhogLayerDev L = layers[layer_of_block(layers, nLayers, blockIdx.x, false)];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::posBlockBase>(layers, nLayers, blockIdx.x)];
     const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int gpr = (L.vw + FHOG_SP - 1) / FHOG_SP;   // groups per score row
     const int g = (blockIdx.x - L.posBlockBase) * 8 + grp;
@@ -729,14 +786,8 @@ static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float s
     return fd_box{score, cx - rw / 2, cy - rh / 2, rw, rh};
 }
 
-// the detector's image pyramid: gray layers, or, for FPDW features, a pyramid of three frames -- the B, G and R planes of the image,
-// each scaled exactly as a gray image is (cv::resize and cv::pyrDown treat the channels of a CV_8UC3 image independently)
-static void aggregated_new_pyramid(fd_ctx* ctx, fd_aggregated* a, int octaveLayers, double minScale, double maxScale) {
-    int rc = fd_pyramid_create(ctx, octaveLayers, minScale, maxScale, &a->pyr);
-    if (rc == FD_OK && a->fpdw) rc = fd_pyramid_set_frames(a->pyr, 3);
-    if (rc != FD_OK) throw FdError{rc, ctx->error};
-}
-
+// the image into the detector's pyramid: gray layers, or, for FPDW features, a pyramid of three frames -- the B, G and R planes of
+// the image, each scaled exactly as a gray image is (cv::resize and cv::pyrDown treat the channels of a CV_8UC3 image independently)
 static void aggregated_update_pyramid(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device) {
     int rc;
     if (a->fpdw) {
@@ -766,125 +817,139 @@ static void aggregated_features(fd_ctx* ctx, fd_aggregated* a, FhogScratch& S, i
     }
     for (int i = 0; i < nLayers; ++i) check_fpdw_image_size(a->fpp, a->layerTable[i].w, a->layerTable[i].h, true);   // the filters see every layer
     S.descOwner = nullptr;
-    S.desc.reserve(sizeof(float) * (size_t)std::max(t.cells, 1) * a->D);
     run_fpdw(ctx, a->dlayers.as<FhogLayerDev>(), nLayers, a->fpdwTiles, a->pyr->image_stride, a->fpp, false, S.desc.as<float>());
 }
 
-// after layout_layers: k_fpdw's tiles over the exact layers (the first nExact entries of the layer table)
-static void aggregated_finish_layout(fd_aggregated* a, int nExact) {
-    if (a->fpdw) a->fpdwTiles = fpdw_assign_tiles(a->layerTable, nExact, a->fpp.cell_size, fpdw_tile_cells(a->fpp), false);
-}
-
-// Feature pyramid and score maps of an approximated handle.  Per image size: the layer plan, the one-layer-per-octave gray
-// pyramid, the layer table (exact layers first, so that run_fhog's launches see exactly them; the approximated ones follow in
-// the same descriptor buffer), the resize tables and, with given lambdas, the factors.  Per image: pyramid, FHOG of the exact
-// layers, [channel sums -> host: lambdas and factors], k_fhog_approx, the score kernel over all layers.
-static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
-                                     std::vector<fd_box>& cand) {
+// The geometry of a handle's feature pyramid, rebuilt when the image size or the pyramid's arena has changed: the layer list, the
+// layer table (exact layers first, so that the feature launches see exactly them, with the launch geometry of an exact run; the
+// approximated ones follow in the same descriptor buffer), layouts, tiles, uploads and, for the approximated layers, the launch
+// table of k_fhog_approx with its resize tables.  An exact handle is the approximated one without approximated layers: its
+// layer list is the pyramid's kept layers (octave_layer_count per octave, where the approximated handle's pyramid has one).
+static void aggregated_geometry(fd_ctx* ctx, fd_aggregated* a, int width, int height) {
     const fd_aggregated_params& P = a->prm;
     const int D = a->D, cs = P.fhog.cell_size, n = P.octave_layer_count;
-    if (!a->pyr || a->pyrW != width || a->pyrH != height) {
-        if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
-        a->layerTable.clear();
-        a->layers.clear();
-        double minScale, maxScale;
-        fd_host_aggregated_limits(P.window_w, P.window_h, cs, n, P.min_window_width, width, height, minScale, maxScale);
-        // both setters forward to the source pyramid (ImagePyramid.hpp:241-263), which has one layer per octave
-        aggregated_new_pyramid(ctx, a, 1, minScale, maxScale);
-        a->pyrW = width; a->pyrH = height;
-    }
-    aggregated_update_pyramid(ctx, a, image, width, height, channels, is_device);
-    fd_pyramid* p = a->pyr;
-    const bool estimate = a->givenLambdas.empty();
-    if (estimate && p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:238-239); given lambdas need no second layer (:209-213)
-        FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
-    FhogScratch& S = scratch(ctx);
-    if (a->layerTable.empty() || a->arenaAt != p->arena.p) {
+    const fd_pyramid* p = a->pyr;
+    const size_t E = p->kept.size();
+    a->layers.clear();
+    if (a->approx) {
         FdAggregatedPlan plan;
         fd_host_plan_aggregated(cs, n, p->minS, p->maxS, width, height, plan);
-        const size_t E = p->kept.size();
         bool same = plan.exactPx.size() == E;
         for (size_t li = 0; same && li < E; ++li)
             same = plan.exactPx[li].first == p->all[p->kept[li]].w && plan.exactPx[li].second == p->all[p->kept[li]].h;
         if (!same) FD_THROW(FD_ERR_RUNTIME, "fd_aggregated_detect: the layer plan and the gray pyramid disagree");
         a->layers = plan.layers;
-        a->tableOf.assign(plan.layers.size(), -1);
-        a->layerTable.assign(plan.layers.size(), FhogLayerDev{});
-        std::vector<int> exactPos;   // position in the layer list of the exact layers
-        for (size_t i = 0; i < plan.layers.size(); ++i)
-            if (!plan.layers[i].approximated) exactPos.push_back((int)i);
-        size_t nextApprox = E;
-        for (size_t i = 0, e = 0; i < plan.layers.size(); ++i) {
-            const fd_aggregated_layer& L = plan.layers[i];
-            const int ti = L.approximated ? (int)nextApprox++ : (int)e++;
-            a->tableOf[i] = ti;
-            FhogLayerDev& T = a->layerTable[ti];
-            std::memset(&T, 0, sizeof(T));
-            if (!L.approximated) {
-                const HostLayer& H = p->all[p->kept[ti]];
-                T.img = p->arena.as<uint8_t>() + H.gray_off; T.w = H.w; T.h = H.h; T.stride = H.w; T.channels = a->fpdw ? 3 : 1;
-            } else {   // no pixels: layout_layers derives rows / cols from w / h
-                const fd_aggregated_layer& X = plan.layers[L.parent];
-                const bool empty = X.rows < 1 || X.cols < 1;
-                T.w = empty ? 0 : L.cols * cs; T.h = empty ? 0 : L.rows * cs;
-            }
-            T.vh = std::max(T.h / cs - P.window_h + 1, 0);
-            T.vw = std::max(T.w / cs - P.window_w + 1, 0);
-            if (T.vw == 0 || T.vh == 0) T.vw = T.vh = 0;
+    } else {
+        for (size_t li = 0; li < E; ++li) {
+            const HostLayer& H = p->all[p->kept[li]];   // scales: ImagePyramid.cpp:178-179,187-188
+            a->layers.push_back(fd_aggregated_layer{H.index, 0, -1, H.h / cs, H.w / cs, 0, H.scale, (double)H.w / (double)width, (double)H.h / (double)height});
         }
-        {
-            std::vector<FhogLayerDev> exact(a->layerTable.begin(), a->layerTable.begin() + E);
-            a->exactLayout = layout_layers(exact, P.fhog);
-        }
-        a->layout = layout_layers(a->layerTable, P.fhog);
-        aggregated_finish_layout(a, (int)E);
-        // approximated layers: launch table, cv::resize tables, factors
-        a->approxTable.clear();
-        a->approxScale.clear();
-        std::vector<FhogResizeTab> tabs;
-        int blocks = 0;
-        const double inc = std::pow(0.5, 1. / n);
-        for (size_t i = 0; i < plan.layers.size(); ++i) {
-            const fd_aggregated_layer& L = plan.layers[i];
-            if (!L.approximated) continue;
-            const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
-            const FhogLayerDev& X = a->layerTable[a->tableOf[L.parent]];
-            if (T.rows < 1 || T.cols < 1) continue;
-            FhogApproxDev A;
-            A.layer = a->tableOf[i]; A.parent = a->tableOf[L.parent];
-            A.blockBase = blocks;
-            A.xtab = (int)tabs.size();
-            resize_tab(X.cols, T.cols, true, tabs);
-            A.ytab = (int)tabs.size();
-            resize_tab(X.rows, T.rows, false, tabs);
-            A.factorBase = (int)a->approxTable.size() * D;
-            blocks += (int)(((int64_t)T.rows * T.cols * D + 255) / 256);
-            a->approxTable.push_back(A);
-            a->approxScale.push_back(std::pow(inc, L.index - plan.layers[L.parent].index));
-        }
-        a->approxBlocks = blocks;
-        a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
-        HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
-        if (!a->approxTable.empty()) {
-            a->dapprox.reserve(sizeof(FhogApproxDev) * a->approxTable.size());
-            HIP_CHECK(hipMemcpy(a->dapprox.p, a->approxTable.data(), sizeof(FhogApproxDev) * a->approxTable.size(), hipMemcpyHostToDevice));
-            a->dresize.reserve(sizeof(FhogResizeTab) * tabs.size());
-            HIP_CHECK(hipMemcpy(a->dresize.p, tabs.data(), sizeof(FhogResizeTab) * tabs.size(), hipMemcpyHostToDevice));
-            a->dfactors.reserve(sizeof(float) * a->approxTable.size() * D);
-        }
-        a->factors.assign(a->approxTable.size() * D, 0.f);
-        // the two exact layers the lambdas are estimated from (ImagePyramid.cpp:240-243)
-        if (estimate) {
-            a->sumLayer[0] = E > 2 ? 1 : 0;
-            a->sumLayer[1] = a->sumLayer[0] + 1;
-            const FhogLayerDev& SA = a->layerTable[a->sumLayer[0]];
-            a->sumChunks = std::max(1, (SA.rows * SA.cols + FHOG_SUM_CELLS - 1) / FHOG_SUM_CELLS);   // the larger of the two
-            a->dsums.reserve(sizeof(double) * 2 * a->sumChunks * D);
-            a->sums.assign((size_t)2 * a->sumChunks * D, 0.0);
-        }
-        a->lambdas.clear();
-        a->arenaAt = p->arena.p;
     }
+    const std::vector<fd_aggregated_layer>& list = a->layers;
+    a->tableOf.assign(list.size(), -1);
+    a->layerTable.assign(list.size(), FhogLayerDev{});
+    size_t nextApprox = E;
+    for (size_t i = 0, e = 0; i < list.size(); ++i) {
+        const fd_aggregated_layer& L = list[i];
+        const int ti = L.approximated ? (int)nextApprox++ : (int)e++;
+        a->tableOf[i] = ti;
+        FhogLayerDev& T = a->layerTable[ti];
+        if (!L.approximated) {
+            const HostLayer& H = p->all[p->kept[ti]];
+            T = layer_entry(p->arena.as<uint8_t>() + H.gray_off, H.w, H.h, H.w, a->fpdw ? 3 : 1);
+        } else {   // no pixels: layout_layers derives rows / cols from w / h
+            const fd_aggregated_layer& X = list[L.parent];
+            const bool empty = X.rows < 1 || X.cols < 1;
+            T = layer_entry(nullptr, empty ? 0 : L.cols * cs, empty ? 0 : L.rows * cs, 0, 0);
+        }
+        T.vh = std::max(T.h / cs - P.window_h + 1, 0);
+        T.vw = std::max(T.w / cs - P.window_w + 1, 0);
+        if (T.vw == 0 || T.vh == 0) T.vw = T.vh = 0;
+    }
+    {
+        std::vector<FhogLayerDev> exact(a->layerTable.begin(), a->layerTable.begin() + E);
+        a->exactLayout = layout_layers(exact, cs);
+    }
+    a->layout = layout_layers(a->layerTable, cs);
+    // k_fpdw's tiles over the exact layers
+    if (a->fpdw) a->fpdwTiles = fpdw_assign_tiles(a->layerTable, (int)E, a->fpp.cell_size, fpdw_tile_cells(a->fpp), false);
+    // approximated layers: launch table, cv::resize tables, factors
+    a->approxTable.clear();
+    a->approxScale.clear();
+    std::vector<FhogResizeTab> tabs;
+    int blocks = 0;
+    const double inc = std::pow(0.5, 1. / n);
+    for (size_t i = 0; i < list.size(); ++i) {
+        const fd_aggregated_layer& L = list[i];
+        if (!L.approximated) continue;
+        const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
+        const FhogLayerDev& X = a->layerTable[a->tableOf[L.parent]];
+        if (T.rows < 1 || T.cols < 1) continue;
+        FhogApproxDev A;
+        A.layer = a->tableOf[i]; A.parent = a->tableOf[L.parent];
+        A.blockBase = blocks;
+        A.xtab = (int)tabs.size();
+        resize_tab(X.cols, T.cols, true, tabs);
+        A.ytab = (int)tabs.size();
+        resize_tab(X.rows, T.rows, false, tabs);
+        A.factorBase = (int)a->approxTable.size() * D;
+        blocks += (int)(((int64_t)T.rows * T.cols * D + 255) / 256);
+        a->approxTable.push_back(A);
+        a->approxScale.push_back(std::pow(inc, L.index - list[L.parent].index));
+    }
+    a->approxBlocks = blocks;
+    a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
+    HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
+    if (!a->approxTable.empty()) {
+        a->dapprox.reserve(sizeof(FhogApproxDev) * a->approxTable.size());
+        HIP_CHECK(hipMemcpy(a->dapprox.p, a->approxTable.data(), sizeof(FhogApproxDev) * a->approxTable.size(), hipMemcpyHostToDevice));
+        a->dresize.reserve(sizeof(FhogResizeTab) * tabs.size());
+        HIP_CHECK(hipMemcpy(a->dresize.p, tabs.data(), sizeof(FhogResizeTab) * tabs.size(), hipMemcpyHostToDevice));
+        a->dfactors.reserve(sizeof(float) * a->approxTable.size() * D);
+    }
+    a->factors.assign(a->approxTable.size() * D, 0.f);
+    // the two exact layers the lambdas are estimated from (ImagePyramid.cpp:240-243)
+    if (a->approx && a->givenLambdas.empty()) {
+        a->sumLayer[0] = E > 2 ? 1 : 0;
+        a->sumLayer[1] = a->sumLayer[0] + 1;
+        const FhogLayerDev& SA = a->layerTable[a->sumLayer[0]];
+        a->sumChunks = std::max(1, (SA.rows * SA.cols + FHOG_SUM_CELLS - 1) / FHOG_SUM_CELLS);   // the larger of the two
+        a->dsums.reserve(sizeof(double) * 2 * a->sumChunks * D);
+        a->sums.assign((size_t)2 * a->sumChunks * D, 0.0);
+    }
+    a->lambdas.clear();
+    a->arenaAt = p->arena.p;
+}
+
+// One image through a handle: the pyramid (created anew when the image size changes; an approximated handle's has one layer per
+// octave), the geometry when it is stale, the features of the exact layers, for an approximated handle [channel sums -> host:
+// lambdas and factors] and k_fhog_approx, the score kernel over all layers, and the candidates.
+static void aggregated_candidates(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
+                                  std::vector<fd_box>& cand) {
+    const fd_aggregated_params& P = a->prm;
+    const int D = a->D;
+    // feature pyramid limits (AggregatedFeaturesExtractor.cpp:30-31,47-52,58-77), recomputed when the image size changes
+    if (!a->pyr || a->pyrW != width || a->pyrH != height) {
+        if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
+        a->layerTable.clear();
+        a->layers.clear();
+        double minScale, maxScale;
+        fd_host_aggregated_limits(P.window_w, P.window_h, P.fhog.cell_size, P.octave_layer_count, P.min_window_width, width, height, minScale, maxScale);
+        // approximated: both setters forward to the source pyramid (ImagePyramid.hpp:241-263), which has one layer per octave
+        int rc = fd_pyramid_create(ctx, a->approx ? 1 : P.octave_layer_count, minScale, maxScale, &a->pyr);
+        if (rc == FD_OK && a->fpdw) rc = fd_pyramid_set_frames(a->pyr, 3);
+        if (rc != FD_OK) throw FdError{rc, ctx->error};
+        a->pyrW = width; a->pyrH = height;
+    }
+    aggregated_update_pyramid(ctx, a, image, width, height, channels, is_device);
+    fd_pyramid* p = a->pyr;
+    // ImagePyramid::estimateLambdas (ImagePyramid.cpp:238-242): of the score pyramid of an exact handle, of the feature pyramid of an
+    // approximated one unless its lambdas are given, which need no second layer (:209-213)
+    const bool estimate = a->approx && a->givenLambdas.empty();
+    if ((!a->approx || estimate) && p->kept.size() < 2)
+        FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
+    FhogScratch& S = scratch(ctx);
+    if (a->layerTable.empty() || a->arenaAt != p->arena.p) aggregated_geometry(ctx, a, width, height);
     const int nExact = (int)p->kept.size(), nApprox = (int)a->approxTable.size();
     a->scores.reserve(sizeof(float) * std::max<size_t>((size_t)a->layout.positions, 1));
     S.desc.reserve(sizeof(float) * (size_t)std::max(a->layout.cells, 1) * D);   // before the features: room for the approximated layers too
@@ -917,7 +982,7 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
         }
         a->lambdas = lambdas;
         set_factors(a->lambdas);
-    } else if (a->lambdas.empty()) {   // given lambdas: once per geometry
+    } else if (a->approx && a->lambdas.empty()) {   // given lambdas: once per geometry
         a->lambdas = a->givenLambdas;
         set_factors(a->lambdas);
     }
@@ -931,7 +996,7 @@ static void aggregated_detect_approx(fd_ctx* ctx, fd_aggregated* a, const uint8_
     if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     S.descOwner = a;
-    // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106) over the layers in layer order
+    // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106) over the layers in layer order: layer, row, column
     for (size_t i = 0; i < a->layers.size(); ++i) {
         const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
         const fd_aggregated_layer& L = a->layers[i];
@@ -952,75 +1017,7 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         HIP_CHECK(hipSetDevice(ctx->device));
         std::vector<fd_box> cand;
         aggregated_check_image(a, width, height, channels);
-        if (a->approx) aggregated_detect_approx(ctx, a, image, width, height, channels, is_device, cand);
-        else {
-        // feature pyramid limits (AggregatedFeaturesExtractor.cpp:30-31,47-52,58-77), recomputed when the image size changes
-        if (!a->pyr || a->pyrW != width || a->pyrH != height) {
-            if (a->pyr) { fd_pyramid_destroy(a->pyr); a->pyr = nullptr; }
-            a->layerTable.clear();
-            double minScale, maxScale;
-            fd_host_aggregated_limits(P.window_w, P.window_h, P.fhog.cell_size, P.octave_layer_count, P.min_window_width, width, height, minScale, maxScale);
-            aggregated_new_pyramid(ctx, a, P.octave_layer_count, minScale, maxScale);
-            a->pyrW = width; a->pyrH = height;
-        }
-        aggregated_update_pyramid(ctx, a, image, width, height, channels, is_device);
-        fd_pyramid* p = a->pyr;
-        if (p->kept.size() < 2)   // ImagePyramid::estimateLambdas (ImagePyramid.cpp:240-242) of the score pyramid
-            FD_THROW(FD_ERR_RUNTIME, "ImagePyramid: at least two pyramid layers are needed to estimate the lambdas");
-        FhogScratch& S = scratch(ctx);
-        // layer table of this pyramid geometry (rebuilt with the pyramid): descriptors and score maps of all layers run as
-        // single launches over the table
-        if (a->layerTable.empty() || a->arenaAt != p->arena.p) {
-            a->layerTable.resize(p->kept.size());
-            for (size_t li = 0; li < p->kept.size(); ++li) {
-                const HostLayer& L = p->all[p->kept[li]];
-                FhogLayerDev& T = a->layerTable[li];
-                std::memset(&T, 0, sizeof(T));
-                T.img = p->arena.as<uint8_t>() + L.gray_off; T.w = L.w; T.h = L.h; T.stride = L.w; T.channels = a->fpdw ? 3 : 1;
-                T.vh = std::max(L.h / P.fhog.cell_size - P.window_h + 1, 0);
-                T.vw = std::max(L.w / P.fhog.cell_size - P.window_w + 1, 0);
-                if (T.vw == 0 || T.vh == 0) T.vw = T.vh = 0;
-            }
-            a->layout = layout_layers(a->layerTable, P.fhog);
-            aggregated_finish_layout(a, (int)a->layerTable.size());
-            a->dlayers.reserve(sizeof(FhogLayerDev) * a->layerTable.size());
-            HIP_CHECK(hipMemcpy(a->dlayers.p, a->layerTable.data(), sizeof(FhogLayerDev) * a->layerTable.size(), hipMemcpyHostToDevice));
-            a->arenaAt = p->arena.p;
-            a->layers.resize(p->kept.size());
-            a->tableOf.resize(p->kept.size());
-            for (size_t li = 0; li < p->kept.size(); ++li) {
-                const HostLayer& L = p->all[p->kept[li]];
-                a->layers[li] = fd_aggregated_layer{L.index, 0, -1, a->layerTable[li].rows, a->layerTable[li].cols, 0, L.scale,
-                                                    (double)L.w / (double)width, (double)L.h / (double)height};
-                a->tableOf[li] = (int)li;
-            }
-        }
-        const int nLayers = (int)a->layerTable.size();
-        std::vector<size_t> off(p->kept.size() + 1, 0);
-        std::vector<int> vw(p->kept.size()), vh(p->kept.size());
-        for (size_t li = 0; li < p->kept.size(); ++li) {
-            vw[li] = a->layerTable[li].vw; vh[li] = a->layerTable[li].vh;
-            off[li] = (size_t)a->layerTable[li].posBase;
-        }
-        off[p->kept.size()] = (size_t)a->layout.positions;
-        a->scores.reserve(sizeof(float) * std::max<size_t>(off.back(), 1));
-        aggregated_features(ctx, a, S, nLayers, a->layout);
-        launch_scores(ctx, a, S);
-        std::vector<float> hs(off.back());
-        if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        S.descOwner = a;
-        // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106): layer, row, column order
-        for (size_t li = 0; li < p->kept.size(); ++li) {
-            const HostLayer& L = p->all[p->kept[li]];
-            const double scaleX = (double)L.w / (double)width, scaleY = (double)L.h / (double)height;   // ImagePyramid.cpp:178-179,187-188
-            for (int y = 0; y < vh[li]; ++y)
-                for (int x = 0; x < vw[li]; ++x) {
-                    const float score = hs[off[li] + (size_t)y * vw[li] + x];
-                    if (score > P.score_threshold) cand.push_back(aggregated_candidate(P, score, x, y, scaleX, scaleY));
-                }
-        }
-        }
+        aggregated_candidates(ctx, a, image, width, height, channels, is_device, cand);
         if (cand_count) *cand_count = (int)cand.size();
         if (candidates)
             for (size_t i = 0; i < cand.size() && (int)i < cand_cap; ++i) candidates[i] = cand[i];

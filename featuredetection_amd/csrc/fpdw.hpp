@@ -102,7 +102,7 @@ __device__ __forceinline__ float fpdw_agg_tap(int t, int cell) {
 
 __global__ __launch_bounds__(256) void k_fpdw(const FhogLayerDev* __restrict__ layers, int nLayers, FpdwParamsDev d, float* __restrict__ out) {
     extern __shared__ __align__(16) unsigned char fpdw_lds[];
-    const FhogLayerDev L = layers[layer_of_block(layers, nLayers, blockIdx.x, true)];
+    const FhogLayerDev L = layers[layer_of<&FhogLayerDev::cellBlockBase>(layers, nLayers, blockIdx.x)];
     const int cell = d.cell, r = d.radius, TC = d.TC;
     const FpdwTile T = fpdw_tile(cell, r, TC, d.perPixel != 0);
     const int TP = T.TP, WF = T.WF, WM = T.WM, WS = T.WS;
@@ -436,20 +436,14 @@ void fpdw_image(fd_ctx* ctx, const uint8_t* bgr, int w, int h, const fd_fpdw_par
     FpdwScratch& F = fpdw_scratch(ctx);
     FhogScratch& S = scratch(ctx);
     const size_t planeStride = fpdw_planes(ctx, F, bgr, w, h, 0);
-    std::vector<FhogLayerDev> layers(1);
-    std::memset(&layers[0], 0, sizeof(FhogLayerDev));
-    layers[0].img = F.planes.as<uint8_t>(); layers[0].w = w; layers[0].h = h; layers[0].stride = w; layers[0].channels = 3;
-    fd_fhog_params cellOnly{};
-    cellOnly.cell_size = fp->cell_size;
-    layout_layers(layers, cellOnly);
+    // the one layer's table: its first tile is tile 0, as layout_layers leaves cellBlockBase
+    std::vector<FhogLayerDev> layers(1, layer_entry(F.planes.as<uint8_t>(), w, h, w, 3));
+    single_layer_table(ctx, F.layers, layers[0], fp->cell_size);
     const int tiles = fpdw_assign_tiles(layers, 1, fpdw_tile_unit(*fp, perPixel), fpdw_tile_cells(*fp, perPixel), perPixel);
     const size_t n = perPixel ? (size_t)w * h * FPDW_CHANNELS : (size_t)layers[0].rows * layers[0].cols * FPDW_CHANNELS;
-    if (n == 0) { HIP_CHECK(hipStreamSynchronize(ctx->stream)); return; }
+    if (n == 0) return;
     S.descOwner = nullptr;
     S.desc.reserve(sizeof(float) * n);
-    F.layers.reserve(sizeof(FhogLayerDev));
-    HIP_CHECK(hipMemcpyAsync(F.layers.p, layers.data(), sizeof(FhogLayerDev), hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // `layers` is pageable host memory
     run_fpdw(ctx, F.layers.as<FhogLayerDev>(), 1, tiles, planeStride, *fp, perPixel, S.desc.as<float>());
     HIP_CHECK(hipMemcpyAsync(out, S.desc.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -689,6 +689,37 @@ def test_aggregated_features_detector(oracle, capi, ctx, synth, cfg):
     det.close()
 
 
+def test_aggregated_features_detector_image_size_changes(oracle, capi, ctx, synth):
+    """an exact FHOG handle fed images of different sizes: first, second, first again.  Every call rebuilds the pyramid and the
+    layer geometry (the code an approximated handle shares) and must give the oracle's candidates (scores and boxes) and final
+    detections; the third call's bytes equal the first's; no layer is approximated.  A handle's threshold is fixed when it is
+    created, so the sequence runs on two handles, one per image's threshold (the float32 0.9-quantile of that image's scores at all
+    positions): each image is checked at its own threshold, where the oracle alone gives 46 of 453 and 18 of 172 positions as
+    candidates and 18 and 7 detections, and at the other image's."""
+    images = [synth.make_frame(176, 144, seed=77), synth.make_frame(131, 97, seed=77)]
+    weights = np.random.default_rng(5).normal(0, 0.05, (4, 4, 31)).astype(np.float32)
+    kw = dict(cell_size=8, octave_layers=2, min_window_width=0)
+    thresholds = [float(np.float32(np.quantile(oracle.aggregated_candidates(img, weights, 0.1, -1e30, **kw)[0], 0.9))) for img in images]
+    for own, thr in enumerate(thresholds):
+        det = capi.Aggregated(ctx, weights, 0.1, thr, nms_overlap=0.3, nms_type=0, **kw)
+        first = None
+        for which in (0, 1, 0):
+            so, bo = oracle.aggregated_candidates(images[which], weights, 0.1, thr, **kw)
+            fs, fb = oracle.nms_iou(so, bo, 0.3, 0)
+            fin, cand = det.detect(images[which])
+            assert len(cand) == len(so) and (which != own or len(so) > 5)
+            assert np.array_equal(cand["score"], so)
+            assert np.array_equal(np.stack([cand["x"], cand["y"], cand["w"], cand["h"]], 1), bo)
+            assert len(fin) == len(fs) and (which != own or len(fs) > 0)
+            assert np.array_equal(fin["score"], fs) and np.array_equal(np.stack([fin["x"], fin["y"], fin["w"], fin["h"]], 1), fb)
+            layers = det.layers()
+            assert len(layers) >= 2 and not layers["approximated"].any()
+            if first is None:
+                first = (fin.tobytes(), cand.tobytes())
+        assert (fin.tobytes(), cand.tobytes()) == first
+        det.close()
+
+
 def test_hog_rbf_svm_detector_config2(oracle, capi, ctx, synth):
     """BASELINE config 2 shape on a reduced frame: HOG-324 + RBF SVM (MFMA path).  Scores within
     1e-4 relative (of the natural scale sum|coeff_i| K_i), positives identical away from the threshold."""
