@@ -93,6 +93,21 @@ class fd_ehog_tracker_params(C.Structure):
                 ("min_width", C.c_int32), ("max_width", C.c_int32)]
 
 
+class fd_svm_train_params(C.Structure):
+    _fields_ = [("C", C.c_double), ("weight_pos", C.c_double), ("weight_neg", C.c_double), ("eps", C.c_double),
+                ("max_iterations", C.c_int32), ("launch_iterations", C.c_int32)]
+
+
+class fd_svm_train_info(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("n_sv", C.c_int32), ("n_bounded", C.c_int32), ("launches", C.c_int32),
+                ("rho", C.c_double), ("objective", C.c_double)]
+
+
+class fd_svm_train_problem(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
+                ("weights", C.c_void_p), ("bias", C.c_void_p), ("alpha", C.c_void_p)]
+
+
 class fd_ehog_patch_params(C.Structure):
     _fields_ = [("patch_w", C.c_int32), ("patch_h", C.c_int32), ("bins", C.c_int32), ("cell_w", C.c_int32), ("cell_h", C.c_int32),
                 ("interpolate", C.c_int32), ("signed_and_unsigned", C.c_int32), ("alpha", C.c_float)]
@@ -244,6 +259,14 @@ _SIGS = {
     "fd_ehog_tracker_get_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "fd_ehog_tracker_feature_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fd_ehog_tracker_heat_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fd_linear_svm_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_linear_svm_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_train_params), C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(fd_svm_train_info)]),
+    "fd_linear_svm_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fd_svm_train_params), C.c_void_p]),
+    "fd_ehog_tracker_train_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_svm_train_params),
+                                            C.POINTER(fd_svm_train_info)]),
+    "fd_ehog_tracker_get_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "fd_linear_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1051,6 +1074,22 @@ class EhogTracker:
             raise ValueError("weights must be [cell_rows][cell_cols][channels]")
         self.ctx.check(lib().fd_ehog_tracker_set_svm(self.ctx.h, self.h, _ptr(weights), bias))
 
+    def train_svm(self, x, n_pos, **kw):
+        """fd_ehog_tracker_train_svm on n_pos positive rows followed by the negative rows of x; keywords as svm_train_params.
+        Returns the training info (a dict)."""
+        x = _c(x, np.float32).reshape(len(x), -1)
+        if x.shape[1] != self.prm.cell_rows * self.prm.cell_cols * self.channels:
+            raise ValueError("examples must be [cell_rows][cell_cols][channels]")
+        prm, info = svm_train_params(**kw), fd_svm_train_info()
+        self.ctx.check(lib().fd_ehog_tracker_train_svm(self.ctx.h, self.h, _ptr(x), n_pos, len(x) - n_pos, C.byref(prm), C.byref(info)))
+        return _svm_info(info)
+
+    def get_svm(self):
+        """(weights float32 (cell_rows, cell_cols, channels), bias) of the installed model"""
+        w, bias = np.zeros((self.prm.cell_rows, self.prm.cell_cols, self.channels), np.float32), C.c_float()
+        self.ctx.check(lib().fd_ehog_tracker_get_svm(self.ctx.h, self.h, _ptr(w), C.byref(bias)))
+        return w, bias.value
+
     def layers(self):
         out = np.zeros(256, EHOG_LAYER_DTYPE)
         n = C.c_int()
@@ -1114,6 +1153,61 @@ class EhogTracker:
             e.count = n.value
             raise e
         return out[:n.value].copy()
+
+
+def svm_train_params(C_=1.0, weight_pos=1.0, weight_neg=1.0, eps=0.0, max_iterations=0, launch_iterations=0, **kw):
+    """fd_svm_train_params; the bound may be given as C_ or C"""
+    return fd_svm_train_params(kw.pop("C", C_), weight_pos, weight_neg, eps, max_iterations, launch_iterations, **kw)
+
+
+def _svm_info(info):
+    return {name: getattr(info, name) for name, _ in fd_svm_train_info._fields_}
+
+
+def linear_svm_train_limits(n_pos, n_neg, d):
+    """fd_linear_svm_train_limits (host only): (q_in_lds, max_iterations); FdError for sizes the trainer refuses"""
+    q, m = C.c_int(), C.c_int()
+    rc = lib().fd_linear_svm_train_limits(n_pos, n_neg, d, C.byref(q), C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_linear_svm_train_limits: invalid sizes (%d, %d, %d)" % (n_pos, n_neg, d))
+    return bool(q.value), m.value
+
+
+def linear_svm_gram(ctx, x, n_pos):
+    """(Q float32 (n, n), QD float64 (n,)) of n_pos positive rows followed by the negative rows of x"""
+    x = _c(x, np.float32)
+    n, d = x.shape
+    q, qd = np.zeros((n, n), np.float32), np.zeros(n, np.float64)
+    ctx.check(lib().fd_linear_svm_gram(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, _ptr(q), _ptr(qd)))
+    return q, qd
+
+
+def linear_svm_train(ctx, x, n_pos, **kw):
+    """fd_linear_svm_train: (weights float32 (d,), bias, alpha float64 (n,), info dict); keywords as svm_train_params"""
+    x = _c(x, np.float32)
+    n, d = x.shape
+    w, bias, alpha = np.zeros(d, np.float32), C.c_float(), np.zeros(n, np.float64)
+    prm, info = svm_train_params(**kw), fd_svm_train_info()
+    ctx.check(lib().fd_linear_svm_train(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, C.byref(prm), _ptr(w), C.byref(bias), _ptr(alpha),
+                                        C.byref(info)))
+    return w, bias.value, alpha, _svm_info(info)
+
+
+def linear_svm_train_batch(ctx, problems, **kw):
+    """fd_linear_svm_train_batch over [(x, n_pos), ...]: a list of (weights, bias, alpha, info) like linear_svm_train's"""
+    count = len(problems)
+    xs = [_c(x, np.float32) for x, _ in problems]
+    ws = [np.zeros(x.shape[1], np.float32) for x in xs]
+    alphas = [np.zeros(x.shape[0], np.float64) for x in xs]
+    biases = np.zeros(max(count, 1), np.float32)
+    arr = (fd_svm_train_problem * max(count, 1))()
+    for c, (x, (_, n_pos)) in enumerate(zip(xs, problems)):
+        arr[c] = fd_svm_train_problem(x.ctypes.data, n_pos, x.shape[0] - n_pos, x.shape[1], 0, ws[c].ctypes.data,
+                                      biases.ctypes.data + 4 * c, alphas[c].ctypes.data)
+    infos = (fd_svm_train_info * max(count, 1))()
+    prm = svm_train_params(**kw)
+    ctx.check(lib().fd_linear_svm_train_batch(ctx.h, count, arr, C.byref(prm), infos))
+    return [(ws[c], float(biases[c]), alphas[c], _svm_info(infos[c])) for c in range(count)]
 
 
 # fd_aggregated_layer: one feature layer of an aggregated-features detector

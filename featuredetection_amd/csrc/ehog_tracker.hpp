@@ -492,6 +492,37 @@ int fd_ehog_tracker_set_svm(fd_ctx* ctx, fd_ehog_tracker* t, const float* weight
     });
 }
 
+int fd_ehog_tracker_train_svm(fd_ctx* ctx, fd_ehog_tracker* t, const float* x, int n_pos, int n_neg, const fd_svm_train_params* params,
+                              fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        ehog_checked(ctx, t, "fd_ehog_tracker_train_svm", false, false);
+        if (!x || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_ehog_tracker_train_svm: NULL argument");
+        const size_t nw = (size_t)t->prm.cell_rows * t->prm.cell_cols * t->D;
+        t->dweights.reserve(sizeof(float) * nw);
+        fd_svm_train_problem pr = {};
+        pr.x = x;
+        pr.n_pos = n_pos;
+        pr.n_neg = n_neg;
+        pr.d = (int)nw;
+        fd_svm_train_run(ctx, "fd_ehog_tracker_train_svm", 1, &pr, params, t->dweights.as<float>(), info);   // k_svm_finish writes dweights
+        t->bias = (float)info->rho;
+        t->hasSvm = true;
+        if (t->updated) ehog_launch_heat(ctx, t);
+        t->weights.resize(nw);
+        HIP_CHECK(hipMemcpyAsync(t->weights.data(), t->dweights.p, sizeof(float) * nw, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_ehog_tracker_get_svm(fd_ctx* ctx, fd_ehog_tracker* t, float* weights, float* bias) {
+    return fd_guard(ctx, [&] {
+        ehog_checked(ctx, t, "fd_ehog_tracker_get_svm", false, true);
+        if (!weights || !bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_ehog_tracker_get_svm: NULL argument");
+        std::copy(t->weights.begin(), t->weights.end(), weights);
+        *bias = t->bias;
+    });
+}
+
 int fd_ehog_tracker_get_layers(fd_ehog_tracker* t, fd_ehog_layer* out, int cap, int* n) {
     if (!t || !n || cap < 0 || (cap > 0 && !out)) return FD_ERR_INVALID_ARGUMENT;
     *n = t->updated ? (int)t->layers.size() : 0;

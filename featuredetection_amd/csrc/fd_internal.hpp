@@ -445,6 +445,12 @@ constexpr int FD_MAX_FRAMES = 64;
 void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, const int* roi,
                          std::vector<WindowLayer>& out, int64_t& total);
 
+// ---------------- linear SVM training (svm_train.hip) ----------------
+// trains `count` problems in one set of launches; problem 0's weights go to wOverride (device memory) when given, in place of
+// its host buffer.  Throws FdError; leaves ctx->stream synchronised.
+void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+                      fd_svm_train_info* infos);
+
 // ---------------- host-side detection logic (hostalgo.cpp) ----------------
 void fd_host_overlap_elimination(const fd_detection* in, int n, float dist, float ratio, std::vector<int>& keep);
 void fd_host_block_nms_sparse(const std::vector<fd_detection>& pos, int imgW, int imgH, int sz, bool masked,

@@ -1,0 +1,552 @@
+// featuredetection_amd/csrc/svm_train.hip -- linear C-SVC training on the device, libsvm's model bit for bit on a given Q
+// (DESIGN.md section 4.6).  What ExtendedHogBasedMeasurementModel's adaptation needs of libsvm::LibSvmClassifier::train
+// (LibSvmClassifier.cpp:156-189, libSvm/src/svm.cpp Solver::Solve :551-830 without shrinking, select_working_set :833-930,
+// calculate_rho :1013-1049, LibSvmUtils::extractSupportVectors LibSvmUtils.cpp:105-118).
+//
+//   k_svm_gram    K = X X^T on the f64 MFMA pipe (f32 products are exact in f64), Q_ij = (float)(y_i y_j K_ij), QD_i = K_ii;
+//                 also the start state alpha = 0, G = -1
+//   k_svm_smo     one workgroup per problem: a counted loop of SMO iterations over a per-launch budget; alpha, G, the iteration
+//                 count and the converged flag persist in global memory between launches (the host relaunches)
+//   k_svm_finish  rho, the objective and the support-vector counts (one thread, libsvm's summation order), and the single
+//                 weight vector, one thread per dimension
+//
+// A problem is n_pos positive rows followed by n_neg negative rows, so y_i = +1 for i < n_pos and libsvm's class grouping is the
+// identity; the bound status is alpha compared with 0 and C as update_alpha_status does.
+#include "fd_internal.hpp"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int SVM_MAX_N = 1024;
+constexpr int SVM_SMO_THREADS = 256;
+constexpr int SVM_SMO_WAVES = SVM_SMO_THREADS / 64;
+constexpr size_t SVM_LDS_BUDGET = 160 * 1024;     // LDS of one gfx950 workgroup
+constexpr int SVM_SLOT_BYTES = 512;               // the reduction slots of k_svm_smo
+constexpr int SVM_DEFAULT_LAUNCH_ITERATIONS = 16384;
+constexpr double SVM_TAU = 1e-12;
+
+struct SvmProbDev {
+    const float* x;            // n x d, row-major
+    float* Q;                  // n_pad x n_pad
+    double* QD;                // n_pad
+    double* alpha;             // n_pad
+    double* G;                 // n_pad
+    float* w;                  // d
+    fd_svm_train_info* info;
+    int32_t* state;            // [0] iterations, [1] converged
+    double Cp, Cn, eps;
+    int32_t n_pos, n, n_pad, d, q_in_lds, max_iter;
+};
+
+inline int svm_pad(int n) { return (n + 15) / 16 * 16; }
+inline size_t svm_smo_lds(int n, bool withQ) {
+    const size_t np = (size_t)svm_pad(n);
+    return 3 * sizeof(double) * np + SVM_SLOT_BYTES + (withQ ? sizeof(float) * np * np : 0);
+}
+inline bool svm_q_in_lds(int n) { return svm_smo_lds(n, true) <= SVM_LDS_BUDGET; }
+
+// One wavefront per 16 x 16 tile of K, the whole feature length: lane (r, kq) feeds row r of both operand tiles at feature
+// k + kq.  Rows from n up to n_pad read as zero, so the padding of Q is zero.
+__global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ P) {
+    const SvmProbDev p = P[blockIdx.z];
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
+    const int lane = threadIdx.x, r = lane & 15, kq = lane >> 4;
+    const int i = ti * 16 + r, j = tj * 16 + r;
+    const bool iok = i < p.n, jok = j < p.n;
+    const float* __restrict__ xi = p.x + (size_t)(iok ? i : 0) * p.d;
+    const float* __restrict__ xj = p.x + (size_t)(jok ? j : 0) * p.d;
+    f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
+    constexpr int U = 4;   // k-steps whose loads are issued together
+    for (int k = 0; k < p.d; k += 4 * U) {
+        float a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = k + 4 * u + kq;
+            const bool kok = kk < p.d;
+            const int kc = kok ? kk : 0;   // in-range address for the masked lanes
+            a[u] = xi[kc];
+            b[u] = xj[kc];
+            a[u] = (iok && kok) ? a[u] : 0.f;
+            b[u] = (jok && kok) ? b[u] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[u], (double)b[u], acc, 0, 0, 0);
+    }
+    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
+    const int col = tj * 16 + r;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = ti * 16 + kq + 4 * q;
+        const double K = acc[q];
+        const bool same = (row < p.n_pos) == (col < p.n_pos);
+        p.Q[(size_t)row * p.n_pad + col] = (float)(same ? K : -K);
+        if (row == col) {
+            p.QD[row] = K;
+            p.alpha[row] = 0.0;
+            p.G[row] = -1.0;
+        }
+    }
+}
+
+// (value, index) of the larger value, ties to the higher index: what a scan in index order with >= leaves
+__device__ __forceinline__ void svm_take_max(double& v, int& i, double ov, int oi) {
+    if (ov > v || (ov == v && oi > i)) { v = ov; i = oi; }
+}
+// the smaller value, ties to the higher index (a scan with <=)
+__device__ __forceinline__ void svm_take_min(double& v, int& i, double ov, int oi) {
+    if (ov < v || (ov == v && oi > i)) { v = ov; i = oi; }
+}
+
+// Solver::Solve's loop.  Every thread owns the elements tid, tid + 256, ...; the two selections are reduced over the
+// wavefront by shuffles and over the four wavefronts through LDS slots, after which every thread holds i, j and performs the
+// two-variable update redundantly.  Three barriers per iteration: behind either selection, and between reading alpha / G of
+// (i, j) and their owners' writes.
+__global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* __restrict__ P, int budget) {
+    extern __shared__ double svm_lds[];
+    const SvmProbDev p = P[blockIdx.x];
+    if (p.state[1] || p.state[0] >= p.max_iter) return;   // done in an earlier launch (a batch relaunches until its last problem is done)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = p.n, np = p.n_pad, n_pos = p.n_pos;
+    double* sAlpha = svm_lds;
+    double* sG = sAlpha + np;
+    double* sQD = sG + np;
+    double* slotAv = sQD + np;                        // [4] Gmax of a wavefront
+    double* slotBv = slotAv + SVM_SMO_WAVES;          // [4] its smallest obj_diff
+    double* slotBg = slotBv + SVM_SMO_WAVES;          // [4] its Gmax2
+    int* slotAi = (int*)(slotBg + SVM_SMO_WAVES);     // [4]
+    int* slotBi = slotAi + SVM_SMO_WAVES;             // [4]
+    float* sQ = (float*)((char*)(sQD + np) + SVM_SLOT_BYTES);
+    for (int k = tid; k < np; k += SVM_SMO_THREADS) {
+        sAlpha[k] = p.alpha[k];
+        sG[k] = p.G[k];
+        sQD[k] = p.QD[k];
+    }
+    if (p.q_in_lds)
+        for (int k = tid; k < np * np; k += SVM_SMO_THREADS) sQ[k] = p.Q[k];
+    const float* __restrict__ Qbase = p.q_in_lds ? sQ : p.Q;
+    __syncthreads();
+    const double Cp = p.Cp, Cn = p.Cn, eps = p.eps;
+    int iter = p.state[0];
+    int converged = 0;
+    for (int it = 0; it < budget; ++it) {
+        if (iter >= p.max_iter) break;
+        // i: maximises -y_t G_t over I_up, the highest index among equals (:847-865)
+        double gmax = -INFINITY;
+        int gi = -1;
+        for (int k = tid; k < n; k += SVM_SMO_THREADS) {
+            const double a = sAlpha[k], g = sG[k];
+            if (k < n_pos) {
+                if (a < Cp && -g >= gmax) { gmax = -g; gi = k; }
+            } else {
+                if (a > 0.0 && g >= gmax) { gmax = g; gi = k; }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) svm_take_max(gmax, gi, __shfl_xor(gmax, o, 64), __shfl_xor(gi, o, 64));
+        if (lane == 0) { slotAv[wave] = gmax; slotAi[wave] = gi; }
+        __syncthreads();
+        gmax = slotAv[0];
+        gi = slotAi[0];
+#pragma unroll
+        for (int w = 1; w < SVM_SMO_WAVES; ++w) svm_take_max(gmax, gi, slotAv[w], slotAi[w]);
+        const int i = gi;
+        // j: minimises obj_diff over I_low with grad_diff > 0, the highest index among equals; Gmax2 on the way (:872-922)
+        double gmax2 = -INFINITY, omin = INFINITY;
+        int gj = -1;
+        if (i >= 0) {
+            const double yi = i < n_pos ? 1.0 : -1.0, QDi = sQD[i];
+            const float* __restrict__ Qi = Qbase + (size_t)i * np;
+            for (int k = tid; k < n; k += SVM_SMO_THREADS) {
+                const double a = sAlpha[k], g = sG[k];
+                if (k < n_pos) {
+                    if (a > 0.0) {
+                        const double gd = gmax + g;
+                        if (g >= gmax2) gmax2 = g;
+                        if (gd > 0.0) {
+                            const double quad = QDi + sQD[k] - 2.0 * yi * Qi[k];
+                            const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
+                            if (od <= omin) { gj = k; omin = od; }
+                        }
+                    }
+                } else {
+                    if (a < Cn) {
+                        const double gd = gmax - g;
+                        if (-g >= gmax2) gmax2 = -g;
+                        if (gd > 0.0) {
+                            const double quad = QDi + sQD[k] + 2.0 * yi * Qi[k];
+                            const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
+                            if (od <= omin) { gj = k; omin = od; }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            svm_take_min(omin, gj, __shfl_xor(omin, o, 64), __shfl_xor(gj, o, 64));
+            gmax2 = fmax(gmax2, __shfl_xor(gmax2, o, 64));
+        }
+        if (lane == 0) { slotBv[wave] = omin; slotBi[wave] = gj; slotBg[wave] = gmax2; }
+        __syncthreads();
+        omin = slotBv[0];
+        gj = slotBi[0];
+        gmax2 = slotBg[0];
+#pragma unroll
+        for (int w = 1; w < SVM_SMO_WAVES; ++w) {
+            svm_take_min(omin, gj, slotBv[w], slotBi[w]);
+            gmax2 = fmax(gmax2, slotBg[w]);
+        }
+        const int j = gj;
+        if (gmax + gmax2 < eps || i < 0 || j < 0) {   // optimal (without a pair only when the Gram holds a NaN)
+            converged = 1;
+            break;
+        }
+        ++iter;
+        // the two-variable update with its clipping (:640-734)
+        const float* __restrict__ Qi = Qbase + (size_t)i * np;
+        const float* __restrict__ Qj = Qbase + (size_t)j * np;
+        const bool ipos = i < n_pos, jpos = j < n_pos;
+        const double Ci = ipos ? Cp : Cn, Cj = jpos ? Cp : Cn;
+        const double oldAi = sAlpha[i], oldAj = sAlpha[j], Gi = sG[i], Gj = sG[j];
+        double ai = oldAi, aj = oldAj;
+        if (ipos != jpos) {
+            double quad = sQD[i] + sQD[j] + (double)(2.f * Qi[j]);
+            if (quad <= 0.0) quad = SVM_TAU;
+            const double delta = (-Gi - Gj) / quad;
+            const double diff = ai - aj;
+            ai += delta;
+            aj += delta;
+            if (diff > 0.0) {
+                if (aj < 0.0) { aj = 0.0; ai = diff; }
+            } else {
+                if (ai < 0.0) { ai = 0.0; aj = -diff; }
+            }
+            if (diff > Ci - Cj) {
+                if (ai > Ci) { ai = Ci; aj = Ci - diff; }
+            } else {
+                if (aj > Cj) { aj = Cj; ai = Cj + diff; }
+            }
+        } else {
+            double quad = sQD[i] + sQD[j] - (double)(2.f * Qi[j]);
+            if (quad <= 0.0) quad = SVM_TAU;
+            const double delta = (Gi - Gj) / quad;
+            const double sum = ai + aj;
+            ai -= delta;
+            aj += delta;
+            if (sum > Ci) {
+                if (ai > Ci) { ai = Ci; aj = sum - Ci; }
+            } else {
+                if (aj < 0.0) { aj = 0.0; ai = sum; }
+            }
+            if (sum > Cj) {
+                if (aj > Cj) { aj = Cj; ai = sum - Cj; }
+            } else {
+                if (ai < 0.0) { ai = 0.0; aj = sum; }
+            }
+        }
+        const double dai = ai - oldAi, daj = aj - oldAj;
+        __syncthreads();   // every thread has read alpha and G of (i, j)
+        if (tid == (i & (SVM_SMO_THREADS - 1))) sAlpha[i] = ai;
+        if (tid == (j & (SVM_SMO_THREADS - 1))) sAlpha[j] = aj;
+        for (int k = tid; k < n; k += SVM_SMO_THREADS) sG[k] += (double)Qi[k] * dai + (double)Qj[k] * daj;   // (:741-744)
+    }
+    // the loop's last writes are their owners' own elements: no barrier needed before the owners store them
+    for (int k = tid; k < n; k += SVM_SMO_THREADS) {
+        p.alpha[k] = sAlpha[k];
+        p.G[k] = sG[k];
+    }
+    if (tid == 0) {
+        p.state[0] = iter;
+        p.state[1] = converged;
+    }
+}
+
+// rho, objective and counts by thread 0 of a problem's first block (alpha and G staged in LDS; the sums run in index order as
+// calculate_rho's and Solve's do), and w_k = sum over the support vectors, in index order, of (float)(alpha_i y_i * (double)x_ik)
+// accumulated in float (extractSupportVectors, CV_32F).  Only for a problem that is done (converged or at max_iterations).
+__global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict__ P) {
+    __shared__ double sA[SVM_MAX_N], sGf[SVM_MAX_N];
+    const SvmProbDev p = P[blockIdx.y];
+    const int tid = threadIdx.x, n = p.n, n_pos = p.n_pos;
+    const int k = blockIdx.x * 256 + tid;
+    if (!p.state[1] && p.state[0] < p.max_iter) {   // the solver goes on in the next launch: the host needs the progress only
+        if (blockIdx.x == 0 && tid == 0) {
+            fd_svm_train_info out = {};
+            out.iterations = p.state[0];
+            *p.info = out;
+        }
+        return;
+    }
+    if (k < p.d) {
+        float w = 0.f;
+        const float* __restrict__ xk = p.x + k;
+        for (int i = 0; i < n; ++i) {
+            const double a = p.alpha[i];
+            if (a > 0.0) {
+                const double coef = i < n_pos ? a : -a;
+                w += (float)(coef * (double)xk[(size_t)i * p.d]);
+            }
+        }
+        p.w[k] = w;
+    }
+    if (blockIdx.x != 0) return;
+    for (int i = tid; i < n; i += 256) {
+        sA[i] = p.alpha[i];
+        sGf[i] = p.G[i];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double ub = INFINITY, lb = -INFINITY, sumFree = 0.0, obj = 0.0;
+    int nFree = 0, nSv = 0, nBounded = 0;
+    for (int i = 0; i < n; ++i) {
+        const bool pos = i < n_pos;
+        const double a = sA[i], g = sGf[i], C = pos ? p.Cp : p.Cn;
+        const double yG = pos ? g : -g;
+        if (a >= C) {
+            if (!pos) ub = fmin(ub, yG);
+            else lb = fmax(lb, yG);
+        } else if (a <= 0.0) {
+            if (pos) ub = fmin(ub, yG);
+            else lb = fmax(lb, yG);
+        } else {
+            ++nFree;
+            sumFree += yG;
+        }
+        obj += a * (g + -1.0);
+        if (a > 0.0) {
+            ++nSv;
+            if (a >= C) ++nBounded;
+        }
+    }
+    fd_svm_train_info out;
+    out.iterations = p.state[0];
+    out.converged = p.state[1];
+    out.n_sv = nSv;
+    out.n_bounded = nBounded;
+    out.launches = 0;   // the host's count
+    out.rho = nFree > 0 ? sumFree / nFree : (ub + lb) / 2;
+    out.objective = obj / 2;
+    *p.info = out;
+}
+
+struct SvmTrainScratch {
+    DevBuf x, q, dbl, w, desc, info, state;
+};
+
+void svm_check_shape(const char* who, int n_pos, int n_neg, int d) {
+    if (n_pos < 1 || n_neg < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
+    if ((int64_t)n_pos + n_neg > SVM_MAX_N) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, SVM_MAX_N);
+    if (d < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the feature length must be positive (%d)", who, d);
+}
+
+fd_svm_train_params svm_checked_params(const char* who, const fd_svm_train_params* prm) {
+    if (!prm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    fd_svm_train_params p = *prm;
+    if (!(p.C > 0.0) || !(p.weight_pos > 0.0) || !(p.weight_neg > 0.0))
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: C and the class weights must be positive (%g, %g, %g)", who, p.C, p.weight_pos, p.weight_neg);
+    if (!(p.eps >= 0.0)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: eps must not be negative (%g)", who, p.eps);
+    if (p.max_iterations < 0 || p.launch_iterations < 0)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: max_iterations and launch_iterations must not be negative", who);
+    if (p.eps == 0.0) p.eps = 1e-4;
+    if (p.launch_iterations == 0) p.launch_iterations = SVM_DEFAULT_LAUNCH_ITERATIONS;
+    return p;
+}
+
+inline size_t svm_align(size_t v) { return (v + 255) / 256 * 256; }
+
+// What one call works on: the problems' descriptors, and the layout of the context's pinned staging area (pageable copies
+// cost about a millisecond each on this stack): descriptors, infos, the host callers' X, and the weights / alpha to return.
+struct SvmRun {
+    std::vector<SvmProbDev> h;
+    std::vector<size_t> outW, outA;   // offsets into the pinned area
+    char* pinned = nullptr;
+    size_t infoOff = 0;
+    int maxPad = 0, maxD = 0;
+    size_t smoLds = 0;
+};
+
+// wOverride: device buffer that receives problem 0's weights in place of the scratch (the tracker's dweights)
+void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params& prm, float* wOverride,
+                 SvmRun& run) {
+    SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
+    size_t xBytes = 0, qBytes = 0, dblBytes = 0, wBytes = 0, outBytes = 0;
+    for (int c = 0; c < count; ++c) {
+        const fd_svm_train_problem& pr = probs[c];
+        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d);
+        if (!pr.x) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+        const size_t n = (size_t)pr.n_pos + pr.n_neg, np = (size_t)svm_pad((int)n);
+        if (!pr.is_device) xBytes += svm_align(sizeof(float) * n * pr.d);
+        qBytes += svm_align(sizeof(float) * np * np);
+        dblBytes += svm_align(sizeof(double) * np * 3);
+        wBytes += svm_align(sizeof(float) * pr.d);
+        outBytes += svm_align(sizeof(float) * pr.d) + svm_align(sizeof(double) * np);
+    }
+    sc.x.reserve(xBytes);
+    sc.q.reserve(qBytes);
+    sc.dbl.reserve(dblBytes);
+    sc.w.reserve(wBytes);
+    sc.desc.reserve(sizeof(SvmProbDev) * count);
+    sc.info.reserve(sizeof(fd_svm_train_info) * count);
+    sc.state.reserve(sizeof(int32_t) * 2 * count);
+    run.infoOff = svm_align(sizeof(SvmProbDev) * count);
+    const size_t xOff = run.infoOff + svm_align(sizeof(fd_svm_train_info) * count);
+    size_t outOff = xOff + xBytes;
+    run.pinned = (char*)fd_pinned(ctx, outOff + outBytes);
+    SvmProbDev* hd = (SvmProbDev*)run.pinned;
+    run.h.resize(count);
+    run.outW.resize(count);
+    run.outA.resize(count);
+    size_t xo = 0, qo = 0, dblo = 0, wo = 0;
+    for (int c = 0; c < count; ++c) {
+        const fd_svm_train_problem& pr = probs[c];
+        const int n = pr.n_pos + pr.n_neg, np = svm_pad(n);
+        SvmProbDev& D = run.h[c];
+        if (pr.is_device) {
+            D.x = pr.x;
+        } else {
+            D.x = (const float*)((char*)sc.x.p + xo);
+            std::memcpy(run.pinned + xOff + xo, pr.x, sizeof(float) * (size_t)n * pr.d);
+            xo += svm_align(sizeof(float) * (size_t)n * pr.d);
+        }
+        D.Q = (float*)((char*)sc.q.p + qo);
+        qo += svm_align(sizeof(float) * (size_t)np * np);
+        D.QD = (double*)((char*)sc.dbl.p + dblo);
+        D.alpha = D.QD + np;
+        D.G = D.alpha + np;
+        dblo += svm_align(sizeof(double) * (size_t)np * 3);
+        D.w = (c == 0 && wOverride) ? wOverride : (float*)((char*)sc.w.p + wo);
+        wo += svm_align(sizeof(float) * pr.d);
+        run.outW[c] = outOff;
+        outOff += svm_align(sizeof(float) * pr.d);
+        run.outA[c] = outOff;
+        outOff += svm_align(sizeof(double) * (size_t)np);
+        D.info = sc.info.as<fd_svm_train_info>() + c;
+        D.state = sc.state.as<int32_t>() + 2 * c;
+        D.Cp = prm.C * prm.weight_pos;
+        D.Cn = prm.C * prm.weight_neg;
+        D.eps = prm.eps;
+        D.n_pos = pr.n_pos;
+        D.n = n;
+        D.n_pad = np;
+        D.d = pr.d;
+        D.q_in_lds = svm_q_in_lds(n) ? 1 : 0;
+        D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : std::max(10000000, 100 * n);
+        hd[c] = D;
+        run.maxPad = std::max(run.maxPad, np);
+        run.maxD = std::max(run.maxD, pr.d);
+        run.smoLds = std::max(run.smoLds, svm_smo_lds(n, D.q_in_lds != 0));
+    }
+    if (xBytes) HIP_CHECK(hipMemcpyAsync(sc.x.p, run.pinned + xOff, xBytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(sc.desc.p, hd, sizeof(SvmProbDev) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(sc.state.p, 0, sizeof(int32_t) * 2 * count, ctx->stream));
+    hipLaunchKernelGGL(k_svm_gram, dim3(run.maxPad / 16, run.maxPad / 16, count), dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+// Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Problem 0's weights go to wOverride
+// (device) when given.  Leaves ctx->stream synchronised.
+void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+                      fd_svm_train_info* infos) {
+    const fd_svm_train_params prm = svm_checked_params(who, params);
+    if (count < 1 || !probs || !infos) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument or no problem", who);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    SvmRun run;
+    svm_prepare(ctx, who, count, probs, prm, wOverride, run);
+    SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
+    static uint64_t ldsAllowed = 0;
+    fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
+    const fd_svm_train_info* hinfo = (const fd_svm_train_info*)(run.pinned + run.infoOff);
+    int launches = 0;
+    for (;;) {
+        hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
+        HIP_CHECK(hipGetLastError());
+        ++launches;
+        hipLaunchKernelGGL(k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(run.pinned + run.infoOff, sc.info.p, sizeof(fd_svm_train_info) * count, hipMemcpyDeviceToHost, ctx->stream));
+        // the results ride along: in the usual case the first launch converges and this is the only wait
+        for (int c = 0; c < count; ++c) {
+            const SvmProbDev& D = run.h[c];
+            if (probs[c].weights && !(c == 0 && wOverride))
+                HIP_CHECK(hipMemcpyAsync(run.pinned + run.outW[c], D.w, sizeof(float) * D.d, hipMemcpyDeviceToHost, ctx->stream));
+            if (probs[c].alpha) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outA[c], D.alpha, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        bool done = true;
+        for (int c = 0; c < count; ++c) done = done && (hinfo[c].converged || hinfo[c].iterations >= run.h[c].max_iter);
+        if (done) break;
+    }
+    for (int c = 0; c < count; ++c) {
+        infos[c] = hinfo[c];
+        infos[c].launches = launches;
+        const fd_svm_train_problem& pr = probs[c];
+        if (pr.weights && !(c == 0 && wOverride)) std::memcpy(pr.weights, run.pinned + run.outW[c], sizeof(float) * pr.d);
+        if (pr.alpha) std::memcpy(pr.alpha, run.pinned + run.outA[c], sizeof(double) * run.h[c].n);
+        if (pr.bias) *pr.bias = (float)infos[c].rho;
+    }
+}
+
+extern "C" {
+
+int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations) {
+    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    const int n = n_pos + n_neg;
+    if (q_in_lds) *q_in_lds = svm_q_in_lds(n) ? 1 : 0;
+    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    return FD_OK;
+}
+
+int fd_linear_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_gram: NULL argument");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        fd_svm_train_problem pr = {};
+        pr.x = x;
+        pr.n_pos = n_pos;
+        pr.n_neg = n_neg;
+        pr.d = d;
+        pr.is_device = is_device;
+        fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
+        SvmRun run;
+        svm_prepare(ctx, "fd_linear_svm_gram", 1, &pr, prm, nullptr, run);
+        const SvmProbDev& D = run.h[0];
+        HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_linear_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params, float* weights,
+                        float* bias, double* alpha, fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train: NULL argument");
+        fd_svm_train_problem pr = {};
+        pr.x = x;
+        pr.n_pos = n_pos;
+        pr.n_neg = n_neg;
+        pr.d = d;
+        pr.is_device = is_device;
+        pr.weights = weights;
+        pr.bias = bias;
+        pr.alpha = alpha;
+        fd_svm_train_run(ctx, "fd_linear_svm_train", 1, &pr, params, nullptr, info);
+    });
+}
+
+int fd_linear_svm_train_batch(fd_ctx* ctx, int count, const fd_svm_train_problem* problems, const fd_svm_train_params* params, fd_svm_train_info* infos) {
+    return fd_guard(ctx, [&] {
+        if (!ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: NULL argument");
+        if (count > 65535) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: %d problems, at most 65535", count);
+        for (int c = 0; c < count && problems; ++c)
+            if (!problems[c].weights || !problems[c].bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: NULL argument in problem %d", c);
+        fd_svm_train_run(ctx, "fd_linear_svm_train_batch", count, problems, params, nullptr, infos);
+    });
+}
+
+}  // extern "C"

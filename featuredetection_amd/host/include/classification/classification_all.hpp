@@ -2,6 +2,7 @@
 #pragma once
 #include <fstream>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -238,4 +239,262 @@ private:
     double logisticA, logisticB;
 };
 
+// ---------------- training: example stores and trainable classifiers ----------------
+
+// ExampleManagement.hpp:22-81
+class ExampleManagement {
+public:
+    class ExampleIterator {
+    public:
+        virtual ~ExampleIterator() {}
+        virtual bool hasNext() const = 0;
+        virtual const cv::Mat& next() = 0;
+    };
+    virtual ~ExampleManagement() {}
+    virtual void add(const std::vector<cv::Mat>& newExamples) = 0;
+    virtual void clear() = 0;
+    virtual size_t size() const = 0;
+    virtual bool hasRequiredSize() const = 0;
+    virtual std::unique_ptr<ExampleIterator> iterator() const = 0;
+};
+
+// EmptyExampleManagement.hpp:20-55
+class EmptyExampleManagement : public ExampleManagement {
+public:
+    void add(const std::vector<cv::Mat>&) override {}
+    void clear() override {}
+    size_t size() const override { return 0; }
+    bool hasRequiredSize() const override { return true; }
+    std::unique_ptr<ExampleIterator> iterator() const override { return std::unique_ptr<ExampleIterator>(new EmptyIterator()); }
+private:
+    class EmptyIterator : public ExampleIterator {
+    public:
+        bool hasNext() const override { return false; }
+        const cv::Mat& next() override { throw std::runtime_error("EmptyExampleManagement::EmptyIterator::next: there is no element to iterate over"); }
+    };
+};
+
+// VectorBasedExampleManagement.hpp / .cpp:16-47.  The reference's capacity is that of the reserved vector; it is a member here.
+class VectorBasedExampleManagement : public ExampleManagement {
+public:
+    explicit VectorBasedExampleManagement(size_t capacity, size_t requiredSize = 1) : requiredSize(requiredSize), capacity(capacity) {
+        examples.reserve(capacity);
+    }
+    void clear() override { examples.clear(); }
+    size_t size() const override { return examples.size(); }
+    bool hasRequiredSize() const override { return examples.size() >= requiredSize; }
+    std::unique_ptr<ExampleIterator> iterator() const override { return std::unique_ptr<ExampleIterator>(new VectorIterator(examples)); }
+protected:
+    std::vector<cv::Mat> examples;
+    size_t requiredSize, capacity;
+private:
+    class VectorIterator : public ExampleIterator {
+    public:
+        explicit VectorIterator(const std::vector<cv::Mat>& examples) : current(examples.cbegin()), end(examples.cend()) {}
+        bool hasNext() const override { return current != end; }
+        const cv::Mat& next() override { return *current++; }
+    private:
+        std::vector<cv::Mat>::const_iterator current, end;
+    };
+};
+
+// UnlimitedExampleManagement.cpp:15-20
+class UnlimitedExampleManagement : public VectorBasedExampleManagement {
+public:
+    explicit UnlimitedExampleManagement(size_t requiredSize = 1) : VectorBasedExampleManagement(10, requiredSize) {}
+    void add(const std::vector<cv::Mat>& newExamples) override { examples.insert(examples.end(), newExamples.begin(), newExamples.end()); }
+};
+
+// AgeBasedExampleManagement.cpp:15-30: fill up, then overwrite the oldest (a ring over the stored examples)
+class AgeBasedExampleManagement : public VectorBasedExampleManagement {
+public:
+    explicit AgeBasedExampleManagement(size_t capacity, size_t requiredSize = 1) : VectorBasedExampleManagement(capacity, requiredSize), insertPosition(0) {}
+    void add(const std::vector<cv::Mat>& newExamples) override {
+        for (const cv::Mat& example : newExamples) {
+            if (examples.size() < capacity) {
+                examples.push_back(example);
+            } else {
+                examples[insertPosition] = example;
+                if (++insertPosition == examples.size()) insertPosition = 0;
+            }
+        }
+    }
+private:
+    size_t insertPosition;
+};
+
+// ConfidenceBasedExampleManagement.cpp:19-68: new examples fill the free space, least confident first; then the new example of
+// least confidence replaces the stored one of highest confidence (the first `keep` stored examples are never replaced) for as
+// long as it is the less confident of the two.  The confidence is that of the example's own class.
+class ConfidenceBasedExampleManagement : public VectorBasedExampleManagement {
+public:
+    ConfidenceBasedExampleManagement(const std::shared_ptr<BinaryClassifier>& classifier, bool positive, size_t capacity, size_t requiredSize = 1)
+        : VectorBasedExampleManagement(capacity, requiredSize), classifier(classifier), positive(positive), keep(1) {}
+    void setFirstExamplesToKeep(size_t keep) { this->keep = keep; }
+    void add(const std::vector<cv::Mat>& newExamples) override;
+private:
+    double confidence(const cv::Mat& example) const {
+        const std::pair<bool, double> result = classifier->getConfidence(example);
+        return (positive != result.first) ? -result.second : result.second;
+    }
+    const std::shared_ptr<BinaryClassifier> classifier;
+    bool positive;
+    size_t keep;
+};
+
+// TrainableClassifier.hpp:21-52
+class TrainableClassifier {
+public:
+    virtual ~TrainableClassifier() {}
+    virtual bool isUsable() const = 0;
+    virtual bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples) = 0;
+    virtual void reset() = 0;
+};
+class TrainableBinaryClassifier : public TrainableClassifier, public BinaryClassifier {};   // TrainableBinaryClassifier.hpp:19-24
+// TrainableProbabilisticClassifier.hpp:19-48
+class TrainableProbabilisticClassifier : public TrainableClassifier, public ProbabilisticClassifier {
+public:
+    bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples) override = 0;
+    virtual bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples,
+                         const std::vector<cv::Mat>& newPositiveTestExamples, const std::vector<cv::Mat>& newNegativeTestExamples) = 0;
+};
+
+// TrainableSvmClassifier.hpp / .cpp:18-48
+class TrainableSvmClassifier : public TrainableBinaryClassifier {
+public:
+    explicit TrainableSvmClassifier(std::shared_ptr<SvmClassifier> svm) : svm(svm), usable(false) {}
+    explicit TrainableSvmClassifier(std::shared_ptr<Kernel> kernel) : svm(std::make_shared<SvmClassifier>(kernel)), usable(false) {}
+    bool classify(const cv::Mat& featureVector) const override { return svm->classify(featureVector); }
+    std::pair<bool, double> getConfidence(const cv::Mat& featureVector) const override { return svm->getConfidence(featureVector); }
+    bool isUsable() const override { return usable; }
+    std::shared_ptr<SvmClassifier> getSvm() { return svm; }
+    const std::shared_ptr<SvmClassifier> getSvm() const { return svm; }
+protected:
+    std::shared_ptr<SvmClassifier> svm;
+    bool usable;
+};
+
+// TrainableProbabilisticSvmClassifier.hpp / .cpp:22-110: rings of test examples; after a successful retraining the logistic
+// parameters follow from the SVM's mean output on them, and the threshold optionally from a target probability
+class TrainableProbabilisticSvmClassifier : public TrainableProbabilisticClassifier {
+public:
+    TrainableProbabilisticSvmClassifier(std::shared_ptr<TrainableSvmClassifier> trainableSvm, int positiveCount, int negativeCount,
+                                        double highProb = 0.99, double lowProb = 0.01);
+    bool classify(const cv::Mat& featureVector) const override { return probabilisticSvm->classify(featureVector); }
+    std::pair<bool, double> getConfidence(const cv::Mat& featureVector) const override { return probabilisticSvm->getConfidence(featureVector); }
+    std::pair<bool, double> getProbability(const cv::Mat& featureVector) const override { return probabilisticSvm->getProbability(featureVector); }
+    bool isUsable() const override { return trainableSvm->isUsable(); }
+    bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples) override {
+        return retrain(newPositiveExamples, newNegativeExamples, newPositiveExamples, newNegativeExamples);
+    }
+    bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples,
+                 const std::vector<cv::Mat>& newPositiveTestExamples, const std::vector<cv::Mat>& newNegativeTestExamples) override;
+    void reset() override;
+    std::shared_ptr<ProbabilisticSvmClassifier> getProbabilisticSvm() { return probabilisticSvm; }
+    const std::shared_ptr<ProbabilisticSvmClassifier> getProbabilisticSvm() const { return probabilisticSvm; }
+    std::shared_ptr<TrainableSvmClassifier> getTrainableSvm() { return trainableSvm; }   // not in the reference
+    void setAdjustThreshold(double targetProbability) {
+        adjustThreshold = true;
+        this->targetProbability = targetProbability;
+    }
+protected:
+    virtual std::pair<double, double> computeLogisticParameters(std::shared_ptr<SvmClassifier> svm) const;
+    double computeMeanOutput(std::shared_ptr<SvmClassifier> svm, const std::vector<cv::Mat>& examples) const;
+    std::pair<double, double> computeLogisticParameters(double meanPosOutput, double meanNegOutput) const;
+private:
+    void updateLogisticParameters();   // after a successful retraining: logistic parameters and, when asked for, the threshold
+    void addTestExamples(const std::vector<cv::Mat>& newPositiveTestExamples, const std::vector<cv::Mat>& newNegativeTestExamples);
+    static void addTestExamples(std::vector<cv::Mat>& examples, size_t capacity, const std::vector<cv::Mat>& newExamples, size_t& insertPosition);
+    std::shared_ptr<ProbabilisticSvmClassifier> probabilisticSvm;
+    std::shared_ptr<TrainableSvmClassifier> trainableSvm;
+    std::vector<cv::Mat> positiveTestExamples, negativeTestExamples;
+    size_t positiveCapacity, negativeCapacity, positiveInsertPosition, negativeInsertPosition;
+    double highProb, lowProb;
+    bool adjustThreshold;
+    double targetProbability;
+};
+
+// FixedTrainableProbabilisticSvmClassifier.hpp:20-66
+class FixedTrainableProbabilisticSvmClassifier : public TrainableProbabilisticSvmClassifier {
+public:
+    FixedTrainableProbabilisticSvmClassifier(std::shared_ptr<TrainableSvmClassifier> trainableSvm, double logisticA, double logisticB)
+        : TrainableProbabilisticSvmClassifier(trainableSvm, 0, 0), logisticA(logisticA), logisticB(logisticB) {}
+    FixedTrainableProbabilisticSvmClassifier(std::shared_ptr<TrainableSvmClassifier> trainableSvm, double highProb, double lowProb,
+                                             double meanPosOutput, double meanNegOutput)
+        : TrainableProbabilisticSvmClassifier(trainableSvm, 0, 0, highProb, lowProb) {
+        const std::pair<double, double> ab = computeLogisticParameters(meanPosOutput, meanNegOutput);
+        logisticA = ab.first;
+        logisticB = ab.second;
+    }
+protected:
+    using TrainableProbabilisticSvmClassifier::computeLogisticParameters;
+    std::pair<double, double> computeLogisticParameters(std::shared_ptr<SvmClassifier>) const override { return std::make_pair(logisticA, logisticB); }
+private:
+    double logisticA, logisticB;
+};
+
 }  // namespace classification
+
+// libsvm/LibSvmClassifier.hpp / .cpp:33-224 -- the binary C-SVC with a LinearKernel on continuous CV_32F examples, trained on the
+// device by fd_linear_svm_train (include/fd_hip.h): the model libsvm's svm_train gives.  Any other kernel or example depth,
+// one-class SVMs, probabilistic output (libsvm's own sigmoid fit) and static negatives throw std::invalid_argument.
+namespace libsvm {
+
+class LibSvmClassifier : public classification::TrainableSvmClassifier {
+public:
+    static std::shared_ptr<LibSvmClassifier> createOneClassSvm(std::shared_ptr<classification::Kernel> kernel, double nu = 1) {
+        return std::make_shared<LibSvmClassifier>(kernel, nu, true, false);
+    }
+    static std::shared_ptr<LibSvmClassifier> createOneClassSvm(std::shared_ptr<classification::SvmClassifier> svm, double nu = 1) {
+        return std::make_shared<LibSvmClassifier>(svm, nu, true, false);
+    }
+    static std::shared_ptr<LibSvmClassifier> createBinarySvm(std::shared_ptr<classification::Kernel> kernel, double c = 1,
+                                                             bool compensateImbalance = false, bool probabilistic = false) {
+        return std::make_shared<LibSvmClassifier>(kernel, c, false, compensateImbalance, probabilistic);
+    }
+    static std::shared_ptr<LibSvmClassifier> createBinarySvm(std::shared_ptr<classification::SvmClassifier> svm, double c = 1,
+                                                             bool compensateImbalance = false, bool probabilistic = false) {
+        return std::make_shared<LibSvmClassifier>(svm, c, false, compensateImbalance, probabilistic);
+    }
+    LibSvmClassifier(std::shared_ptr<classification::Kernel> kernel, double cnu, bool oneClass, bool compensateImbalance = false,
+                     bool probabilistic = false);
+    LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double cnu, bool oneClass, bool compensateImbalance = false,
+                     bool probabilistic = false);
+    void loadStaticNegatives(const std::string& negativesFilename, int maxNegatives, double scale = 1);   // throws: not supported
+    bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples) override;
+    void reset() override;
+    void setPositiveExampleManagement(std::unique_ptr<classification::ExampleManagement> positiveExamples) {
+        this->positiveExamples = std::move(positiveExamples);
+    }
+    void setNegativeExampleManagement(std::unique_ptr<classification::ExampleManagement> negativeExamples) {
+        this->negativeExamples = std::move(negativeExamples);
+    }
+    std::shared_ptr<classification::ProbabilisticSvmClassifier> getProbabilisticSvm() { return probabilisticSvm; }
+    const std::shared_ptr<classification::ProbabilisticSvmClassifier> getProbabilisticSvm() const { return probabilisticSvm; }
+    // not in the reference: what the last training ran with and returned (weights of compensateImbalance, iterations, rho, ...)
+    const fd_svm_train_params& getLastTrainingParameters() const { return lastParams; }
+    const fd_svm_train_info& getLastTrainingInfo() const { return lastInfo; }
+    // not in the reference: train on this tracker handle (fd_ehog_tracker_train_svm) -- the weight vector is written into the handle's
+    // device weights and its heat pyramid follows; the classifier object receives w and rho from the handle's host copy.  nullptr:
+    // back to fd_linear_svm_train.  The handle must outlive its use here (ExtendedHogBasedMeasurementModel sets and clears it).
+    // dimensions: the handle's cell_rows * cell_cols * channels; examples of another length are std::invalid_argument
+    void setTrainingTarget(fd_ehog_tracker* tracker, int dimensions = 0) { trainingTarget = tracker; targetDimensions = dimensions; }
+    fd_ehog_tracker* getTrainingTarget() const { return trainingTarget; }
+private:
+    // retrain's two halves: add the examples and, when both stores have their required size, gather them (positives first) with
+    // the parameters; install the trained model
+    bool addAndGather(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples, std::vector<float>& x,
+                      int& positiveCount, int& negativeCount, int& dimensions, fd_svm_train_params& params);
+    void setTrained(const std::vector<float>& weights, const fd_svm_train_params& params, const fd_svm_train_info& info);
+    bool compensateImbalance;
+    double c;
+    std::shared_ptr<classification::ProbabilisticSvmClassifier> probabilisticSvm;
+    std::unique_ptr<classification::ExampleManagement> positiveExamples, negativeExamples;
+    int rows = 0, cols = 0, type = 0;   // shape of the examples, for the weight vector (LibSvmUtils::createNode)
+    fd_ehog_tracker* trainingTarget = nullptr;
+    int targetDimensions = 0;
+    fd_svm_train_params lastParams = {};
+    fd_svm_train_info lastInfo = {};
+};
+
+}  // namespace libsvm

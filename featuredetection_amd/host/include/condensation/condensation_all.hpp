@@ -105,14 +105,17 @@ private:
 
 // ExtendedHogBasedMeasurementModel.hpp / .cpp:60-742, the evaluation half, on one fd_ehog_tracker: update, evaluate(image, samples) with
 // the re-initialisation branches and targetLost, evaluate(Sample&), isValid, getHeatPeak, createGoodNegativeExamples, the setters and
-// the cell-grid rule of initialize.  The one deviation: initialize / adapt do not retrain; they take the weight vector
-// and the bias from the ProbabilisticSvmClassifier, which must hold a LinearKernel and one support vector of
-// cellRowCount * cellColumnCount * channels values.  The batched evaluate scores all samples with one fd_ehog_tracker_evaluate_samples
+// the cell-grid rule of initialize.  With the constructor that takes a ProbabilisticSvmClassifier initialize / adapt do not retrain (the one
+// deviation); they take the weight vector and the bias from the classifier, which must hold a LinearKernel and one support
+// vector of cellRowCount * cellColumnCount * channels values.  With the reference's constructor (a TrainableProbabilisticSvmClassifier)
+// initialize is :321-384 and adapt :386-419 with adaptation NONE, POSITION and TRAJECTORY; CORRECTED_TRAJECTORY throws std::runtime_error.  The batched evaluate scores all samples with one fd_ehog_tracker_evaluate_samples
 // (sliding window) or one fd_ehog_tracker_extract_patches (no sliding window); getFusedEvaluationCount (not in the reference) counts them.
 class ExtendedHogBasedMeasurementModel : public MeasurementModel {
 public:
     enum class Adaptation { NONE, POSITION, TRAJECTORY, CORRECTED_TRAJECTORY };
     explicit ExtendedHogBasedMeasurementModel(std::shared_ptr<classification::ProbabilisticSvmClassifier> classifier);
+    // the reference's constructor (:60-75): initialize / adapt create training examples and retrain the classifier (see below)
+    explicit ExtendedHogBasedMeasurementModel(std::shared_ptr<classification::TrainableProbabilisticSvmClassifier> trainable);
     ~ExtendedHogBasedMeasurementModel();
     ExtendedHogBasedMeasurementModel(const ExtendedHogBasedMeasurementModel&) = delete;
     ExtendedHogBasedMeasurementModel& operator=(const ExtendedHogBasedMeasurementModel&) = delete;
@@ -128,6 +131,15 @@ public:
     std::pair<double, cv::Rect> getHeatPeak() const;
     // the examples (cellRowCount x cellColumnCount * channels CV_32F each) and, optionally, their bounds in the order they were chosen
     std::vector<cv::Mat> createGoodNegativeExamples(cv::Rect targetBounds, std::vector<cv::Rect>* bounds = nullptr) const;
+    // :671-692: windows of random width and position that overlap the target by less than positiveOverlapThreshold, drawn from the
+    // model's std::mt19937 (default seed); extracted like the model's negatives (cells with the sliding window, patches without)
+    std::vector<cv::Mat> createRandomNegativeExamples(size_t count, const cv::Mat& image, cv::Rect targetBounds, std::vector<cv::Rect>* bounds = nullptr) const;
+    // not in the reference: what every retraining of initialize / adapt was given, in order -- the positive samples {x, y, width,
+    // height} (centre form, extracted as patches) and the bounds of the negative examples -- so that a caller can follow it
+    struct TrainingRecord {
+        std::vector<cv::Rect> positives, negatives;
+    };
+    const std::vector<TrainingRecord>& getTrainingLog() const { return trainingLog; }
     void setHogParams(size_t cellSize, size_t cellCount, bool signedAndUnsigned, bool interpolateBins, bool interpolateCells, int octaveLayerCount);
     void setRejectionThreshold(double rejectionThreshold) { this->rejectionThreshold = rejectionThreshold; }
     void setUseSlidingWindow(bool useSlidingWindow, bool conservativeReInit) { this->useSlidingWindow = useSlidingWindow; this->conservativeReInit = conservativeReInit; }
@@ -143,6 +155,13 @@ public:
     fd_ehog_tracker* native() const { return tracker; }
 private:
     void takeClassifierWeights();
+    void setTrainingTarget(fd_ehog_tracker* target);
+    bool retrain(const std::vector<cv::Mat>& positives, const std::vector<cv::Mat>& negatives, const std::vector<cv::Rect>& positiveSamples,
+                 const std::vector<cv::Rect>& negativeBounds);
+    std::vector<cv::Mat> createPositiveTrainingExamples(const Sample& target, std::vector<cv::Rect>& samplesUsed);
+    std::vector<cv::Mat> createNegativeTrainingExamples(const cv::Mat& image, cv::Rect targetBounds, std::vector<cv::Rect>& bounds) const;
+    cv::Rect createRandomBounds(const cv::Mat& image) const;
+    bool extractPositive(const Sample& target, cv::Mat& features, double* score) const;
     void evaluateAll(std::vector<std::shared_ptr<Sample>>& samples, double* bestScore);
     void scored(Sample& sample, bool valid, double score) const;
     double computeOverlap(cv::Rect a, cv::Rect b) const;
@@ -157,6 +176,11 @@ private:
     Adaptation adaptation;
     double adaptationThreshold, exclusionThreshold;
     std::shared_ptr<classification::ProbabilisticSvmClassifier> classifier;
+    std::shared_ptr<classification::TrainableProbabilisticSvmClassifier> trainable;   // null with the first constructor
+    std::vector<cv::Mat> trajectoryFeatures;
+    std::vector<cv::Rect> trajectorySamples;
+    std::vector<TrainingRecord> trainingLog;
+    bool trainsOnHandle = false;   // the trainable's SVM is a LibSvmClassifier that trains on `tracker` (fd_ehog_tracker_train_svm)
     fd_ehog_tracker* tracker = nullptr;
     size_t cellRowCount = 0, cellColumnCount = 0, minWidth = 0, maxWidth = 0;
     bool initialized = false, usable = false, targetLost = false;

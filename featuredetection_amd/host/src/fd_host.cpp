@@ -1475,7 +1475,164 @@ shared_ptr<ProbabilisticWvmClassifier> ProbabilisticWvmClassifier::load(const bo
     return pwvm;
 }
 
+// ---------------- training ----------------
+void ConfidenceBasedExampleManagement::add(const vector<Mat>& newExamples) {   // ConfidenceBasedExampleManagement.cpp:28-68
+    typedef std::pair<size_t, double> Scored;
+    vector<Scored> existing, incoming;
+    for (size_t i = keep; i < examples.size(); ++i) existing.push_back(Scored(i, confidence(examples[i])));
+    for (size_t i = 0; i < newExamples.size(); ++i) incoming.push_back(Scored(i, confidence(newExamples[i])));
+    std::sort(existing.begin(), existing.end(), [](Scored a, Scored b) { return a.second > b.second; });   // most confident first
+    std::sort(incoming.begin(), incoming.end(), [](Scored a, Scored b) { return a.second < b.second; });   // least confident first
+    size_t in = 0, ex = 0;
+    for (; examples.size() < capacity && in < incoming.size(); ++in) examples.push_back(newExamples[incoming[in].first]);
+    for (; ex < existing.size() && in < incoming.size() && incoming[in].second < existing[ex].second; ++ex, ++in)
+        examples[existing[ex].first] = newExamples[incoming[in].first];
+}
+
+TrainableProbabilisticSvmClassifier::TrainableProbabilisticSvmClassifier(shared_ptr<TrainableSvmClassifier> trainableSvm, int positiveCount,
+                                                                         int negativeCount, double highProb, double lowProb)
+    : probabilisticSvm(make_shared<ProbabilisticSvmClassifier>(trainableSvm->getSvm())), trainableSvm(trainableSvm),
+      positiveCapacity(positiveCount > 0 ? positiveCount : 0), negativeCapacity(negativeCount > 0 ? negativeCount : 0), positiveInsertPosition(0),
+      negativeInsertPosition(0), highProb(highProb), lowProb(lowProb), adjustThreshold(false), targetProbability(0.5) {}
+
+void TrainableProbabilisticSvmClassifier::addTestExamples(vector<Mat>& examples, size_t capacity, const vector<Mat>& newExamples, size_t& insertPosition) {
+    for (const Mat& example : newExamples) {   // .cpp:69-81: fill up, then overwrite the oldest
+        if (examples.size() < capacity) {
+            examples.push_back(example);
+        } else {
+            examples[insertPosition] = example;
+            if (++insertPosition == examples.size()) insertPosition = 0;
+        }
+    }
+}
+void TrainableProbabilisticSvmClassifier::addTestExamples(const vector<Mat>& newPositiveTestExamples, const vector<Mat>& newNegativeTestExamples) {
+    if (positiveCapacity > 0 && negativeCapacity > 0) {   // .cpp:52-55
+        addTestExamples(positiveTestExamples, positiveCapacity, newPositiveTestExamples, positiveInsertPosition);
+        addTestExamples(negativeTestExamples, negativeCapacity, newNegativeTestExamples, negativeInsertPosition);
+    }
+}
+void TrainableProbabilisticSvmClassifier::updateLogisticParameters() {   // .cpp:57-63
+    const std::pair<double, double> ab = computeLogisticParameters(probabilisticSvm->getSvm());
+    probabilisticSvm->setLogisticParameters(ab.first, ab.second);
+    if (adjustThreshold) probabilisticSvm->getSvm()->setThreshold((std::log(1.0 / targetProbability - 1.0) - ab.first) / ab.second);   // setThreshold takes a float, as the reference's
+}
+bool TrainableProbabilisticSvmClassifier::retrain(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples,
+                                                  const vector<Mat>& newPositiveTestExamples, const vector<Mat>& newNegativeTestExamples) {
+    addTestExamples(newPositiveTestExamples, newNegativeTestExamples);
+    if (!trainableSvm->retrain(newPositiveExamples, newNegativeExamples)) return false;
+    updateLogisticParameters();
+    return true;
+}
+void TrainableProbabilisticSvmClassifier::reset() {
+    positiveTestExamples.clear();
+    negativeTestExamples.clear();
+    trainableSvm->reset();
+}
+std::pair<double, double> TrainableProbabilisticSvmClassifier::computeLogisticParameters(double meanPosOutput, double meanNegOutput) const {
+    const double logisticB = (std::log((1 - lowProb) / lowProb) - std::log((1 - highProb) / highProb)) / (meanNegOutput - meanPosOutput);   // .cpp:93-97
+    const double logisticA = std::log((1 - highProb) / highProb) - logisticB * meanPosOutput;
+    return std::make_pair(logisticA, logisticB);
+}
+std::pair<double, double> TrainableProbabilisticSvmClassifier::computeLogisticParameters(shared_ptr<SvmClassifier> svm) const {
+    const double meanPosOutput = computeMeanOutput(svm, positiveTestExamples);
+    return computeLogisticParameters(meanPosOutput, computeMeanOutput(svm, negativeTestExamples));
+}
+double TrainableProbabilisticSvmClassifier::computeMeanOutput(shared_ptr<SvmClassifier> svm, const vector<Mat>& examples) const {
+    double sum = 0;
+    for (const Mat& example : examples) sum += svm->computeHyperplaneDistance(example);
+    return sum / examples.size();
+}
+
 }  // namespace classification
+
+// =================================================================================================
+namespace libsvm {
+using classification::ExampleManagement;
+using classification::Kernel;
+using classification::SvmClassifier;
+
+LibSvmClassifier::LibSvmClassifier(shared_ptr<Kernel> kernel, double cnu, bool oneClass, bool compensateImbalance, bool probabilistic)
+    : LibSvmClassifier(make_shared<SvmClassifier>(kernel), cnu, oneClass, compensateImbalance, probabilistic) {}
+LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double cnu, bool oneClass, bool compensateImbalance, bool probabilistic)
+    : TrainableSvmClassifier(svm), compensateImbalance(compensateImbalance), c(cnu),
+      probabilisticSvm(make_shared<classification::ProbabilisticSvmClassifier>(svm)),
+      positiveExamples(new classification::UnlimitedExampleManagement()), negativeExamples(new classification::UnlimitedExampleManagement()) {
+    if (oneClass) throw std::invalid_argument("LibSvmClassifier: one-class SVMs are not trained on this backend");
+    if (probabilistic) throw std::invalid_argument("LibSvmClassifier: probabilistic output (libsvm's sigmoid fit) is not available on this backend");
+    if (!svm->getKernel() || svm->getKernel()->abiKernel() != FD_KERNEL_LINEAR)
+        throw std::invalid_argument("LibSvmClassifier: only a LinearKernel is trained on this backend");
+}
+void LibSvmClassifier::loadStaticNegatives(const string&, int, double) {
+    throw std::invalid_argument("LibSvmClassifier: static negatives are not supported on this backend");
+}
+bool LibSvmClassifier::addAndGather(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples, vector<float>& x, int& positiveCount,
+                                    int& negativeCount, int& dimensions, fd_svm_train_params& params) {
+    positiveExamples->add(newPositiveExamples);   // LibSvmClassifier.cpp:122-125
+    negativeExamples->add(newNegativeExamples);
+    if (!positiveExamples->hasRequiredSize() || !negativeExamples->hasRequiredSize()) return false;
+    x.clear();
+    dimensions = -1;
+    ExampleManagement* stores[2] = {positiveExamples.get(), negativeExamples.get()};
+    for (ExampleManagement* store : stores)   // createProblem (:164-189): the positives, then the negatives, in the stores' order
+        for (auto it = store->iterator(); it->hasNext();) {
+            const Mat& example = it->next();
+            if (example.depth() != CV_32F) throw std::invalid_argument("LibSvmClassifier: examples have to be of depth CV_32F on this backend");
+            if (!example.isContinuous()) throw std::invalid_argument("LibSvmUtils: vector has to be continuous");
+            const int dim = (int)(example.total() * example.channels());
+            if (dimensions < 0) {
+                dimensions = dim;
+                rows = example.rows;
+                cols = example.cols;
+                type = example.type();
+            } else if (dim != dimensions) {
+                throw std::invalid_argument("LibSvmClassifier: examples have to have the same length");
+            }
+            x.insert(x.end(), example.ptr<float>(), example.ptr<float>() + dim);
+        }
+    positiveCount = (int)positiveExamples->size();
+    negativeCount = (int)negativeExamples->size();
+    params = fd_svm_train_params{c, 1.0, 1.0, 1e-4, 0, 0};   // createParameters (:56-85)
+    if (compensateImbalance) {   // :141-146
+        params.weight_pos = (double)negativeCount / (double)positiveCount;
+        params.weight_neg = (double)positiveCount / (double)negativeCount;
+    }
+    return true;
+}
+void LibSvmClassifier::setTrained(const vector<float>& weights, const fd_svm_train_params& params, const fd_svm_train_info& info) {
+    Mat w(rows, cols, type);   // extractSupportVectors: one vector of the examples' shape, coefficient 1, bias rho
+    std::memcpy(w.data, weights.data(), sizeof(float) * weights.size());
+    svm->setSvmParameters(vector<Mat>{w}, vector<float>{1.f}, info.rho);
+    lastParams = params;
+    lastInfo = info;
+    usable = true;
+}
+bool LibSvmClassifier::retrain(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples) {
+    if (newPositiveExamples.empty() && newNegativeExamples.empty()) return usable;   // :119-121
+    vector<float> x;
+    int positiveCount = 0, negativeCount = 0, dimensions = 0;
+    fd_svm_train_params params;
+    if (!addAndGather(newPositiveExamples, newNegativeExamples, x, positiveCount, negativeCount, dimensions, params)) return usable;
+    vector<float> weights(dimensions);
+    float bias = 0;
+    fd_svm_train_info info;
+    if (trainingTarget) {
+        if (dimensions != targetDimensions) throw std::invalid_argument("LibSvmClassifier: the examples do not have the length of the tracker's weight vector");
+        check(fd_ehog_tracker_train_svm(context(), trainingTarget, x.data(), positiveCount, negativeCount, &params, &info));
+        check(fd_ehog_tracker_get_svm(context(), trainingTarget, weights.data(), &bias));
+    } else {
+        check(fd_linear_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &params, weights.data(), &bias, nullptr, &info));
+    }
+    setTrained(weights, params, info);
+    return usable;
+}
+void LibSvmClassifier::reset() {   // :218-223
+    usable = false;
+    svm->setSvmParameters(vector<Mat>(), vector<float>(), 0.0);
+    positiveExamples->clear();
+    negativeExamples->clear();
+}
+
+}  // namespace libsvm
 
 // =================================================================================================
 namespace detection {
@@ -2266,7 +2423,21 @@ ExtendedHogBasedMeasurementModel::ExtendedHogBasedMeasurementModel(shared_ptr<cl
     if (!classifier || !dynamic_cast<classification::LinearKernel*>(classifier->getSvm()->getKernel().get()))   // :74-75
         throw std::invalid_argument("ExtendedHogBasedMeasurementKernel: the SVM must use a LinearKernel");
 }
-ExtendedHogBasedMeasurementModel::~ExtendedHogBasedMeasurementModel() { if (tracker) fd_ehog_tracker_destroy(tracker); }
+ExtendedHogBasedMeasurementModel::ExtendedHogBasedMeasurementModel(shared_ptr<classification::TrainableProbabilisticSvmClassifier> trainable)
+    : ExtendedHogBasedMeasurementModel(trainable ? trainable->getProbabilisticSvm() : shared_ptr<classification::ProbabilisticSvmClassifier>()) {
+    this->trainable = trainable;
+}
+ExtendedHogBasedMeasurementModel::~ExtendedHogBasedMeasurementModel() {
+    setTrainingTarget(nullptr);
+    if (tracker) fd_ehog_tracker_destroy(tracker);
+}
+// a LibSvmClassifier behind the trainable trains on the model's tracker handle: the weights stay on the device
+void ExtendedHogBasedMeasurementModel::setTrainingTarget(fd_ehog_tracker* target) {
+    if (!trainable) return;
+    auto svm = std::dynamic_pointer_cast<libsvm::LibSvmClassifier>(trainable->getTrainableSvm());
+    if (svm) svm->setTrainingTarget(target, (int)(cellRowCount * cellColumnCount * (signedAndUnsigned ? 31 : 13)));
+    trainsOnHandle = svm && target;
+}
 
 void ExtendedHogBasedMeasurementModel::setHogParams(size_t cellSize, size_t cellCount, bool signedAndUnsigned, bool interpolateBins, bool interpolateCells,
                                                     int octaveLayerCount) {
@@ -2445,8 +2616,10 @@ bool ExtendedHogBasedMeasurementModel::initialize(shared_ptr<imageprocessing::Ve
         fd_cehog_params filter = signedAndUnsigned ? fd_cehog_params{(int32_t)cellSize, 18, 1, 1, interpolateBins, interpolateCells, 0.2f}
                                                    : fd_cehog_params{(int32_t)cellSize, 9, 0, 1, interpolateBins, interpolateCells, 0.48f};
         fd_ehog_tracker_params prm = {filter, (int32_t)cellColumnCount, (int32_t)cellRowCount, octaveLayerCount, (int32_t)minWidth, (int32_t)maxWidth};
+        setTrainingTarget(nullptr);
         if (tracker) { fd_ehog_tracker_destroy(tracker); tracker = nullptr; }
         check(fd_ehog_tracker_create(context(), &prm, &tracker));
+        setTrainingTarget(tracker);
         initialized = true;
     }
     model_update(tracker, image);
@@ -2460,29 +2633,167 @@ bool ExtendedHogBasedMeasurementModel::initialize(shared_ptr<imageprocessing::Ve
         return false;
     }
     initialFeatures = features;
-    takeClassifierWeights();   // builds the heat pyramid of this frame as well (:339-341)
-    usable = true;
+    if (!trainable) {
+        takeClassifierWeights();   // builds the heat pyramid of this frame as well (:339-341)
+        usable = true;
+        targetLost = false;
+        return usable;
+    }
+    // :329-384: the target against random windows, then against the windows the first model scores best
+    const cv::Rect targetBounds = target.getBounds();
+    const vector<cv::Rect> targetSample{cv::Rect(target.getX(), target.getY(), target.getWidth(), target.getHeight())};
+    vector<cv::Rect> bounds;
+    vector<Mat> negatives = createRandomNegativeExamples(initialNegativeExampleCount, image->getData(), targetBounds, &bounds);
+    usable = retrain(vector<Mat>{initialFeatures}, negatives, targetSample, bounds);
+    if (usable) {
+        negatives = createNegativeTrainingExamples(image->getData(), targetBounds, bounds);
+        if (useSlidingWindow || !negatives.empty()) usable = retrain(vector<Mat>(), negatives, vector<cv::Rect>(), bounds);
+    }
     targetLost = false;
     return usable;
 }
 
-bool ExtendedHogBasedMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage>, const vector<shared_ptr<Sample>>&, const Sample&) {   // :386-404
+// trainable->retrain and, when the classifier is usable, its one support vector and bias as the heat pyramid's kernel (:334-340)
+bool ExtendedHogBasedMeasurementModel::retrain(const vector<Mat>& positives, const vector<Mat>& negatives, const vector<cv::Rect>& positiveSamples,
+                                               const vector<cv::Rect>& negativeBounds) {
+    trainingLog.push_back(TrainingRecord{positiveSamples, negativeBounds});
+    const bool ok = trainable->retrain(positives, negatives);
+    if (!ok) return false;
+    if (!trainsOnHandle) {
+        takeClassifierWeights();
+    } else if (classifier->getSvm()->getSupportVectors().size() != 1) {   // the handle already holds the weights and this frame's heat pyramid
+        throw std::runtime_error("ExtendedHogBasedMeasurementModel: the amount of support vectors has to be one (w)");
+    }
+    return true;
+}
+
+bool ExtendedHogBasedMeasurementModel::extractPositive(const Sample& target, Mat& features, double* score) const {
+    const int32_t xywh[4] = {target.getX(), target.getY(), target.getWidth(), target.getHeight()};
+    uint8_t valid = 0;
+    features = Mat((int)cellRowCount, (int)cellColumnCount * (signedAndUnsigned ? 31 : 13), CV_32FC1);
+    check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, features.ptr<float>(0), score));
+    return valid != 0;
+}
+
+vector<Mat> ExtendedHogBasedMeasurementModel::createPositiveTrainingExamples(const Sample& target, vector<cv::Rect>& samplesUsed) {   // :492-533
+    samplesUsed.clear();
+    if (adaptation == Adaptation::NONE) return vector<Mat>();
+    if (adaptation == Adaptation::CORRECTED_TRAJECTORY)
+        throw std::runtime_error("ExtendedHogBasedMeasurementModel: the corrected trajectory needs the feature extractors of past frames, which this backend does not keep");
+    Mat features;
+    double score = 0;
+    if (!extractPositive(target, features, &score)) return vector<Mat>();
+    const cv::Rect sample(target.getX(), target.getY(), target.getWidth(), target.getHeight());
+    if (adaptation == Adaptation::POSITION) {
+        if (score <= adaptationThreshold) return vector<Mat>();
+        samplesUsed.push_back(sample);
+        return vector<Mat>{features};
+    }
+    // TRAJECTORY: collect the patches above the exclusion threshold, learn them all once the target scores above the adaptation threshold
+    if (score > exclusionThreshold) {
+        trajectoryFeatures.push_back(features);
+        trajectorySamples.push_back(sample);
+    }
+    if (score <= adaptationThreshold) return vector<Mat>();
+    vector<Mat> examples = trajectoryFeatures;
+    samplesUsed = trajectorySamples;
+    trajectoryFeatures.clear();
+    trajectorySamples.clear();
+    return examples;
+}
+
+vector<Mat> ExtendedHogBasedMeasurementModel::createNegativeTrainingExamples(const Mat& image, cv::Rect targetBounds, vector<cv::Rect>& bounds) const {   // :593-619
+    bounds.clear();
+    if (useSlidingWindow) {
+        vector<Mat> examples = createGoodNegativeExamples(targetBounds, &bounds);
+        if (examples.size() > negativeExampleCount) {
+            examples.resize(negativeExampleCount);
+            bounds.resize(negativeExampleCount);
+        }
+        return examples;
+    }
+    vector<cv::Rect> candidateBounds;
+    vector<Mat> candidates = createRandomNegativeExamples(randomExampleCount, image, targetBounds, &candidateBounds);
+    vector<std::pair<float, size_t>> classified(candidates.size());
+    for (size_t i = 0; i < candidates.size(); ++i) classified[i] = std::make_pair((float)classifier->getSvm()->computeHyperplaneDistance(candidates[i]), i);
+    const size_t top = std::min(negativeExampleCount, classified.size());
+    std::partial_sort(classified.begin(), classified.begin() + top, classified.end(),
+                      [](const std::pair<float, size_t>& a, const std::pair<float, size_t>& b) { return a.first > b.first; });
+    size_t count = top;
+    while (count > 0 && classified[count - 1].first <= negativeScoreThreshold) count--;
+    vector<Mat> examples;
+    for (size_t i = 0; i < count; ++i) {
+        examples.push_back(candidates[classified[i].second]);
+        bounds.push_back(candidateBounds[classified[i].second]);
+    }
+    return examples;
+}
+
+cv::Rect ExtendedHogBasedMeasurementModel::createRandomBounds(const Mat& image) const {   // :685-692; a range of n values is [0, n)
+    auto below = [this](long n) { return n > 1 ? std::uniform_int_distribution<int>(0, (int)n - 1)(generator) : 0; };
+    const int width = below((long)maxWidth - (long)minWidth) + (int)minWidth;
+    const int height = (int)(width * cellRowCount / cellColumnCount);
+    const int x = below(image.cols - width);
+    const int y = below(image.rows - height);
+    return cv::Rect(x, y, width, height);
+}
+
+vector<Mat> ExtendedHogBasedMeasurementModel::createRandomNegativeExamples(size_t count, const Mat& image, cv::Rect targetBounds, vector<cv::Rect>* chosen) const {
+    if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
+    const int D = signedAndUnsigned ? 31 : 13;
+    vector<Mat> examples;
+    vector<cv::Rect> boxes;
+    size_t draws = 0;
+    while (examples.size() < count) {
+        if (++draws > 1000 * (count + 1)) throw std::runtime_error("ExtendedHogBasedMeasurementModel: no random negative example has a patch in this image");
+        const cv::Rect bounds = createRandomBounds(image);
+        if (!(computeOverlap(targetBounds, bounds) < positiveOverlapThreshold)) continue;
+        const int32_t xywh[4] = {bounds.x + bounds.width / 2, bounds.y + bounds.height / 2, bounds.width, bounds.height};
+        uint8_t valid = 0;
+        Mat m((int)cellRowCount, (int)cellColumnCount * D, CV_32FC1);
+        if (useSlidingWindow) check(fd_ehog_tracker_extract_cells(context(), tracker, 1, xywh, &valid, m.ptr<float>(0)));
+        else check(fd_ehog_tracker_extract_patches(context(), tracker, 1, xywh, &valid, m.ptr<float>(0), nullptr));
+        if (!valid) continue;
+        examples.push_back(m);
+        boxes.push_back(bounds);
+    }
+    if (chosen) *chosen = boxes;
+    return examples;
+}
+
+bool ExtendedHogBasedMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage> image, const vector<shared_ptr<Sample>>&, const Sample& target) {   // :386-404
     if (!usable) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
     targetLost = false;
-    takeClassifierWeights();
+    if (!trainable) {
+        takeClassifierWeights();
+        return true;
+    }
+    vector<cv::Rect> positiveSamples, negativeBounds;
+    const vector<Mat> positives = createPositiveTrainingExamples(target, positiveSamples);
+    if (positives.empty()) return false;
+    const vector<Mat> negatives = createNegativeTrainingExamples(image->getData(), target.getBounds(), negativeBounds);
+    usable = retrain(positives, negatives, positiveSamples, negativeBounds);
     return true;
 }
 bool ExtendedHogBasedMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage>, const vector<shared_ptr<Sample>>&) {   // :406-419
     if (!usable) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
-    takeClassifierWeights();
+    if (trainable) {
+        usable = trainable->retrain(vector<Mat>(), vector<Mat>());   // nothing new: the classifier's state
+        if (usable) takeClassifierWeights();
+    } else {
+        takeClassifierWeights();
+    }
     targetLost = true;
     return false;
 }
 void ExtendedHogBasedMeasurementModel::reset() {   // :421-432
+    if (trainable) trainable->reset();
     initialized = false;
     usable = false;
     targetLost = false;
     initialFeatures = Mat();
+    trajectoryFeatures.clear();
+    trajectorySamples.clear();
 }
 
 std::pair<double, cv::Rect> ExtendedHogBasedMeasurementModel::getHeatPeak() const {   // :434-456

@@ -351,7 +351,8 @@ int fd_pyramid_cehog_layer(fd_ctx* ctx, fd_pyramid* p, int layer, const fd_cehog
  * (cell_cols + 2) * max_width / cell_cols, octave_layer_count) (ExtendedHogFeatureExtractor.cpp:32-41,76-84), the filter on every
  * layer (feature pyramid), and, once an SVM is set, the heat pyramid: ConvolutionFilter.cpp:27-43 with the weight vector as kernel,
  * anchor at the kernel centre (cell_cols / 2, cell_rows / 2), BORDER_CONSTANT 0, delta = -bias; heat layers have the size of their
- * feature layers.  Training stays with the caller, who supplies the linear SVM's weight vector and bias. */
+ * feature layers.  The caller supplies the linear SVM's weight vector and bias (fd_ehog_tracker_set_svm) or trains them on the
+ * device (fd_ehog_tracker_train_svm). */
 typedef struct fd_ehog_tracker fd_ehog_tracker;
 typedef struct {
     fd_cehog_params filter;
@@ -403,6 +404,51 @@ int fd_ehog_tracker_heat_maxima(fd_ctx* ctx, fd_ehog_tracker* t, float threshold
 int fd_ehog_tracker_get_layers(fd_ehog_tracker* t, fd_ehog_layer* out, int cap, int* n);
 int fd_ehog_tracker_feature_layer(fd_ctx* ctx, fd_ehog_tracker* t, int layer, float* out);
 int fd_ehog_tracker_heat_layer(fd_ctx* ctx, fd_ehog_tracker* t, int layer, float* out);
+
+/* Linear C-SVC training on the device: the model libsvm::LibSvmClassifier::train obtains from svm_train (libsvm 3.17, C_SVC,
+ * LINEAR, no shrinking; LibSvmClassifier.cpp:56-85,156-189) and LibSvmUtils::extractSupportVectors turns into one weight vector
+ * (LibSvmUtils.cpp:105-118).  A problem is n_pos positive rows followed by n_neg negative rows of an n x d float row-major matrix
+ * (n = n_pos + n_neg <= 1024), the order of createProblem.  The solver repeats libsvm's Solver::Solve operation for operation in
+ * double on Q_ij = (float)(y_i y_j K_ij); K = X X^T is summed on the f64 matrix pipe, in another order than libsvm's dot, so that
+ * single entries of Q may differ from libsvm's by one float ulp.  On the Q that fd_linear_svm_gram returns the result is libsvm's
+ * bit for bit. */
+typedef struct {
+    double C, weight_pos, weight_neg;   /* per-class bound C * weight (libsvm's weighted_C) */
+    double eps;                         /* stopping tolerance; 0 -> 1e-4 */
+    int32_t max_iterations;             /* 0 -> libsvm's max(10000000, 100 n) */
+    int32_t launch_iterations;          /* SMO iterations per kernel launch; 0 -> the default budget */
+} fd_svm_train_params;
+typedef struct {
+    int32_t iterations, converged;      /* converged 0: max_iterations reached, the current model is returned (not an error) */
+    int32_t n_sv, n_bounded, launches;  /* alpha > 0; alpha at its bound; launches of the solver kernel */
+    double rho, objective;
+} fd_svm_train_info;
+typedef struct {
+    const float* x;                     /* n x d */
+    int32_t n_pos, n_neg, d, is_device; /* is_device: x is device memory */
+    float* weights;                     /* out, d floats (host) */
+    float* bias;                        /* out: (float)rho; the decision value is dot(w, x) - bias */
+    double* alpha;                      /* out, n doubles (host); may be NULL */
+} fd_svm_train_problem;
+/* FD_ERR_INVALID_ARGUMENT for n_pos < 1, n_neg < 1, n > 1024, d < 1, C or a class weight <= 0, eps < 0, negative iteration
+ * counts, or a required pointer that is NULL. */
+/* Q (n x n floats) and QD (n doubles, K_ii) to host */
+int fd_linear_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD);
+int fd_linear_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params,
+                        float* weights, float* bias, double* alpha /* n, may be NULL */, fd_svm_train_info* info);
+/* count independent problems (one per tracked target) in one set of launches, one workgroup per problem; infos: count entries */
+int fd_linear_svm_train_batch(fd_ctx* ctx, int count, const fd_svm_train_problem* problems, const fd_svm_train_params* params,
+                              fd_svm_train_info* infos);
+/* Trains on n_pos + n_neg host feature vectors of d = cell_rows * cell_cols * channels floats and installs the model in the
+ * tracker: the weight vector is written by the training kernel into the tracker's device weights, then what
+ * fd_ehog_tracker_set_svm does (the heat pyramid of the current frame); the handle's host copy of the weights is refreshed. */
+int fd_ehog_tracker_train_svm(fd_ctx* ctx, fd_ehog_tracker* t, const float* x, int n_pos, int n_neg, const fd_svm_train_params* params,
+                              fd_svm_train_info* info);
+/* the handle's host copy of the installed model (fd_ehog_tracker_set_svm / _train_svm): cell_rows * cell_cols * channels floats and the
+ * bias; FD_ERR_RUNTIME before an SVM is set */
+int fd_ehog_tracker_get_svm(fd_ctx* ctx, fd_ehog_tracker* t, float* weights, float* bias);
+/* host only, no context: whether the solver keeps Q in LDS for this size, and the default max_iterations; either may be NULL */
+int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations);
 
 /* detection::AggregatedFeaturesDetector (AggregatedFeaturesDetector.cpp:37-128) with imageFilter = GrayscaleFilter,
  * layerFilter = FhogFilter on an extraction::AggregatedFeaturesExtractor (AggregatedFeaturesExtractor.cpp:34-130): a linear
