@@ -103,6 +103,16 @@ class fd_svm_train_info(C.Structure):
                 ("rho", C.c_double), ("objective", C.c_double)]
 
 
+class fd_particles_arrays(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("x", "y", "size", "vx", "vy", "vsize", "weight", "score", "target", "cluster_id")]
+
+
+class fd_particles_info(C.Structure):
+    _fields_ = [("found", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("size", C.c_int32), ("vx", C.c_int32), ("vy", C.c_int32),
+                ("vsize", C.c_float), ("cluster_id", C.c_int32), ("count", C.c_int32), ("n_valid", C.c_int32), ("n_target", C.c_int32),
+                ("bad_weight", C.c_int32), ("best_score", C.c_double), ("weight_sum", C.c_double)]
+
+
 class fd_svm_train_problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
                 ("weights", C.c_void_p), ("bias", C.c_void_p), ("alpha", C.c_void_p)]
@@ -267,6 +277,17 @@ _SIGS = {
                                             C.POINTER(fd_svm_train_info)]),
     "fd_ehog_tracker_get_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "fd_linear_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_particles_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fd_particles_destroy": (None, [C.c_void_p]),
+    "fd_particles_capacity": (C.c_int, [C.c_void_p]),
+    "fd_particles_route_enabled": (C.c_int, []),
+    "fd_particles_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_particles_arrays)]),
+    "fd_particles_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(fd_particles_arrays)]),
+    "fd_particles_get_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_particles_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]),
+    "fd_particles_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "fd_particles_weigh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double]),
+    "fd_particles_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_particles_info)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1153,6 +1174,97 @@ class EhogTracker:
             e.count = n.value
             raise e
         return out[:n.value].copy()
+
+
+FD_PARTICLES_MAX = 8192
+FD_PARTICLES_TARGET_LOST, FD_PARTICLES_SLIDING_WINDOW, FD_PARTICLES_ALL_TARGETS = 0, 1, 2
+# the fields of a generation of particles, in the order of fd_particles_arrays
+PARTICLE_FIELDS = (("x", np.int32), ("y", np.int32), ("size", np.int32), ("vx", np.int32), ("vy", np.int32), ("vsize", np.float32),
+                   ("weight", np.float64), ("score", np.float64), ("target", np.uint8), ("cluster_id", np.int32))
+
+
+class Particles:
+    """fd_particles: the particle set of the Condensation tracker resident on the device, bound to one EhogTracker.  A generation is a
+    dict of arrays keyed like PARTICLE_FIELDS."""
+
+    def __init__(self, ctx, tracker, capacity):
+        self.ctx = ctx
+        self.tracker = tracker   # must outlive the set
+        self.h = C.c_void_p()
+        ctx.check(lib().fd_particles_create(ctx.h, tracker.h, capacity, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().fd_particles_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def capacity(self):
+        return lib().fd_particles_capacity(self.h)
+
+    def set(self, x, y, size, vx=None, vy=None, vsize=None, weight=None, score=None, target=None, cluster_id=None):
+        """fills the current generation; defaults: velocity 0, size factor 1, weight 1, score 0, no target flag, cluster ids 0"""
+        n = len(x)
+        given = dict(x=x, y=y, size=size, vx=vx, vy=vy, vsize=vsize, weight=weight, score=score, target=target, cluster_id=cluster_id)
+        default = dict(vx=0, vy=0, vsize=1, weight=1, score=0, target=0, cluster_id=0)
+        keep = [_c(np.full(n, default[name]) if given[name] is None else given[name], dtype) for name, dtype in PARTICLE_FIELDS]
+        if any(len(a) != n for a in keep):
+            raise ValueError("the fields of a generation have one length")
+        arrays = fd_particles_arrays(*[_ptr(a) for a in keep])
+        self.ctx.check(lib().fd_particles_set(self.ctx.h, self.h, n, C.byref(arrays)))
+
+    def get(self):
+        """the current generation as a dict of arrays"""
+        keep = {name: np.zeros(self.capacity, dtype) for name, dtype in PARTICLE_FIELDS}
+        arrays = fd_particles_arrays(*[_ptr(keep[name]) for name, _ in PARTICLE_FIELDS])
+        n = C.c_int()
+        self.ctx.check(lib().fd_particles_get(self.ctx.h, self.h, self.capacity, C.byref(n), C.byref(arrays)))
+        return {name: a[:n.value].copy() for name, a in keep.items()}
+
+    def trace(self, windows=True):
+        """(source int32 (n,), windows int32 (n, 4) {layer, bx, by, valid} or None, valid uint8 (n,)) of the last sample / evaluate"""
+        source, valid = np.zeros(self.capacity, np.int32), np.zeros(self.capacity, np.uint8)
+        win = np.zeros((self.capacity, 4), np.int32) if windows else None
+        self.ctx.check(lib().fd_particles_get_trace(self.ctx.h, self.h, _ptr(source), _ptr(win), _ptr(valid)))
+        n = len(self)
+        return source[:n].copy(), (win[:n].copy() if windows else None), valid[:n].copy()
+
+    def __len__(self):
+        n = C.c_int()
+        rc = lib().fd_particles_get(self.ctx.h, self.h, FD_PARTICLES_MAX, C.byref(n), None)
+        self.ctx.check(rc)
+        return n.value
+
+    def sample(self, count, n_resampled, u, diffusion, fresh, first_fresh_cluster_id):
+        """fd_particles_sample: diffusion float64 (n_resampled, 3) {dx, dy, size factor}, fresh int32 (count - n_resampled, 3) {x, y, size}"""
+        diffusion = _c(np.asarray(diffusion, np.float64).reshape(-1, 3), np.float64)
+        fresh = _c(np.asarray(fresh, np.int32).reshape(-1, 3), np.int32)
+        if len(diffusion) < n_resampled or len(fresh) < count - n_resampled:
+            raise ValueError("too few draws")
+        self.ctx.check(lib().fd_particles_sample(self.ctx.h, self.h, count, n_resampled, u, _ptr(diffusion), _ptr(fresh), first_fresh_cluster_id))
+
+    def evaluate(self, use_patches, aspect_ratio):
+        self.ctx.check(lib().fd_particles_evaluate(self.ctx.h, self.h, int(use_patches), aspect_ratio))
+
+    def weigh(self, logistic_a, logistic_b, svm_threshold, mode, rejection_threshold):
+        self.ctx.check(lib().fd_particles_weigh(self.ctx.h, self.h, logistic_a, logistic_b, svm_threshold, mode, rejection_threshold))
+
+    def state(self):
+        """fd_particles_state: the info as a dict; FdError (with .info) when a weight is negative or not finite"""
+        info = fd_particles_info()
+        rc = lib().fd_particles_state(self.ctx.h, self.h, C.byref(info))
+        out = {name: getattr(info, name) for name, _ in fd_particles_info._fields_}
+        if rc != FD_OK:
+            e = FdError(rc, lib().fd_last_error(self.ctx.h).decode())
+            e.info = out
+            raise e
+        return out
 
 
 def svm_train_params(C_=1.0, weight_pos=1.0, weight_neg=1.0, eps=0.0, max_iterations=0, launch_iterations=0, **kw):

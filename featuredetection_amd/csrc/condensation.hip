@@ -1,0 +1,495 @@
+// featuredetection_amd/csrc/condensation.hip -- the particle set of the Condensation tracker resident on the device: two generations of
+// samples as structure-of-arrays and the per-frame steps of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel)
+// (ResamplingSampler.cpp:50-59, LowVarianceSampling.cpp:20-46, SimpleTransitionModel.cpp:25-44), of
+// ExtendedHogBasedMeasurementModel's weighting (.cpp:173-205) and of FilteringStateExtractor(WeightedMeanStateExtractor)
+// (WeightedMeanStateExtractor.cpp:23-62).  The scoring of the samples is the tracker's (ehog_tracker.hpp).  DESIGN.md 4.7.
+//
+// Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
+// needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
+// against them, so another association would select other samples); they are walked by single lanes in LDS, everything around them
+// is parallel.  All loops are counted; nothing waits on another workgroup.
+#include "fd_internal.hpp"
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+namespace {
+
+constexpr int PT = 256;                        // threads of the three kernels
+constexpr int32_t PARTICLE_NO_CLUSTER = INT32_MIN;   // the empty key of the cluster table
+
+struct ParticleGen {
+    int32_t *x, *y, *size, *vx, *vy;
+    float* vsize;
+    double *weight, *score;
+    uint8_t* target;
+    int32_t* cluster;
+};
+
+__host__ __device__ inline bool particle_weight_ok(double w) { return w >= 0.0 && w <= DBL_MAX; }   // not negative, not infinite, not NaN
+
+// LowVarianceSampling::resample + SimpleTransitionModel::predict + the fresh samples of ResamplingSampler::sample.
+// cum[k]: the weights added up in index order, by one lane.  The forward walk of the reference (advance while pointer > sum) ends at
+// the smallest k with pointer <= cum[k] (weights are not negative, so cum does not decrease): every copy finds its k by bisection.
+// Where rounding leaves the last pointers above the total the walk stops at the last sample (the reference walks off the end).
+__global__ __launch_bounds__(PT) void k_particles_sample(ParticleGen src, ParticleGen dst, int nOld, int nCopies, int nFresh, double step, double start,
+                                                         const double* __restrict__ diffusion, const int32_t* __restrict__ fresh, int32_t firstFreshId,
+                                                         int32_t* __restrict__ source, fd_particles_info* __restrict__ info) {
+    extern __shared__ double cum[];
+    const int tid = threadIdx.x;
+    if (nCopies > 0) {
+        for (int i = tid; i < nOld; i += PT) cum[i] = src.weight[i];
+        __syncthreads();
+        if (tid == 0) {
+            double running = 0.0;
+            for (int i = 0; i < nOld; ++i) {
+                running = running + cum[i];
+                cum[i] = running;
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < nCopies; i += PT) {
+        const double weightPointer = start + (double)(unsigned int)i * step;
+        int lo = 0, hi = nOld - 1;
+        for (int it = 0; it < 14 && lo < hi; ++it) {   // 2^13 = FD_PARTICLES_MAX
+            const int mid = (lo + hi) >> 1;
+            if (weightPointer > cum[mid]) lo = mid + 1;
+            else hi = mid;
+        }
+        const int k = lo;
+        double vx = src.vx[k], vy = src.vy[k], vs = src.vsize[k];
+        vx = vx + diffusion[3 * i];
+        vy = vy + diffusion[3 * i + 1];
+        vs = vs * diffusion[3 * i + 2];
+        const int nvx = static_cast<int>(round(vx)), nvy = static_cast<int>(round(vy));
+        const float nvs = (float)vs;
+        dst.vx[i] = nvx; dst.vy[i] = nvy; dst.vsize[i] = nvs;
+        dst.x[i] = src.x[k] + nvx;
+        dst.y[i] = src.y[k] + nvy;
+        dst.size[i] = static_cast<int>(roundf((float)src.size[k] * nvs));   // int * float: the product and its rounding are float
+        dst.weight[i] = 1.0; dst.score[i] = 0.0; dst.target[i] = 0;
+        dst.cluster[i] = src.cluster[k];
+        source[i] = k;
+    }
+    for (int j = tid; j < nFresh; j += PT) {
+        const int i = nCopies + j;
+        dst.x[i] = fresh[3 * j]; dst.y[i] = fresh[3 * j + 1]; dst.size[i] = fresh[3 * j + 2];
+        dst.vx[i] = 0; dst.vy[i] = 0; dst.vsize[i] = 1.f;
+        dst.weight[i] = 1.0; dst.score[i] = 0.0; dst.target[i] = 0;
+        dst.cluster[i] = firstFreshId + j;
+        source[i] = -1;
+    }
+    if (tid == 0) {
+        info->count = nCopies + nFresh;
+        info->n_valid = 0;
+        info->bad_weight = 0;
+        info->best_score = -DBL_MAX;
+    }
+}
+
+// ExtendedHogBasedMeasurementModel::scored for every sample, ProbabilisticSvmClassifier::getProbability (.cpp:54-58) in double.  Two
+// passes: the first only looks for a product that is negative or not finite; with one, nothing is written but the flag.
+__global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, const uint8_t* __restrict__ valid, double logisticA, double logisticB,
+                                                        double svmThreshold, int mode, double rejectionThreshold, fd_particles_info* __restrict__ info) {
+    __shared__ double sBest[PT];
+    __shared__ int sValid[PT];
+    const int tid = threadIdx.x;
+    auto weighed = [&](int i) {
+        const double fABp = logisticA + logisticB * g.score[i];
+        const double p = fABp >= 0 ? exp(-fABp) / (1.0 + exp(-fABp)) : 1.0 / (1.0 + exp(fABp));
+        return g.weight[i] * p;
+    };
+    int bad = 0;
+    for (int i = tid; i < n; i += PT)
+        if (valid[i] && !particle_weight_ok(weighed(i))) bad = 1;
+    if (__syncthreads_or(bad)) {
+        if (tid == 0) info->bad_weight = 1;
+        return;
+    }
+    double best = -DBL_MAX;   // bestScore = lowest(); std::max(bestScore, score) never takes a NaN
+    int nValid = 0;
+    for (int i = tid; i < n; i += PT) {
+        double score = 0.0;
+        if (!valid[i]) {
+            g.target[i] = 0;
+            g.weight[i] = 0.0;
+            g.score[i] = 0.0;
+        } else {
+            score = g.score[i];
+            g.weight[i] = weighed(i);
+            g.target[i] = mode == FD_PARTICLES_TARGET_LOST ? score >= svmThreshold : (mode == FD_PARTICLES_SLIDING_WINDOW ? score > rejectionThreshold : 1);
+            ++nValid;
+        }
+        if (best < score) best = score;
+    }
+    sBest[tid] = best;
+    sValid[tid] = nValid;
+    __syncthreads();
+    for (int s = PT / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            if (sBest[tid] < sBest[tid + s]) sBest[tid] = sBest[tid + s];
+            sValid[tid] += sValid[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        info->best_score = sBest[0];
+        info->n_valid = sValid[0];
+    }
+}
+
+__device__ inline unsigned int particle_hash(int32_t id) { return (unsigned int)id * 2654435761u; }
+
+// FilteringStateExtractor + WeightedMeanStateExtractor.  The cluster sizes are counted in an LDS hash table (`slots` a power of two
+// >= 2 n: linear probing, integer atomics, so the counts do not depend on the order of arrival); one 64-bit atomic max over
+// (size, -index) of every target sample then names the first member of the largest cluster, of equally large clusters the one whose
+// first member comes first.  The sums: per chunk of 256 samples every thread forms its sample's seven products (0 for a sample
+// outside the cluster: the sums start at +0 and never become -0, so adding +0 changes no bit), and eight lanes add one column each
+// in index order.  The eighth column adds up all weights of the generation.
+__global__ __launch_bounds__(PT) void k_particles_state(ParticleGen g, int n, int slots, fd_particles_info* __restrict__ info) {
+    extern __shared__ __align__(8) unsigned char stateLds[];
+    __shared__ unsigned long long sWinner;
+    __shared__ double sSums[8];
+    __shared__ int sTargets[PT];
+    const int tid = threadIdx.x;
+    int32_t* keys = (int32_t*)stateLds;
+    int* counts = (int*)(stateLds + sizeof(int32_t) * (size_t)slots);
+    for (int s = tid; s < slots; s += PT) { keys[s] = PARTICLE_NO_CLUSTER; counts[s] = 0; }
+    if (tid == 0) sWinner = 0ull;
+    __syncthreads();
+    int bad = tid == 0 && info->bad_weight, nTarget = 0;   // raised by k_particles_weigh: the generation was left unweighted
+    for (int i = tid; i < n; i += PT) {
+        if (!particle_weight_ok(g.weight[i])) bad = 1;
+        if (!g.target[i]) continue;
+        ++nTarget;
+        const int32_t id = g.cluster[i];
+        unsigned int slot = particle_hash(id) & (unsigned int)(slots - 1);
+        for (int probe = 0; probe < slots; ++probe) {   // slots > number of distinct ids: a free slot exists
+            const int32_t old = atomicCAS(&keys[slot], PARTICLE_NO_CLUSTER, id);
+            if (old == PARTICLE_NO_CLUSTER || old == id) { atomicAdd(&counts[slot], 1); break; }
+            slot = (slot + 1) & (unsigned int)(slots - 1);
+        }
+    }
+    bad = __syncthreads_or(bad);
+    for (int i = tid; i < n; i += PT) {
+        if (!g.target[i]) continue;
+        const int32_t id = g.cluster[i];
+        unsigned int slot = particle_hash(id) & (unsigned int)(slots - 1);
+        for (int probe = 0; probe < slots && keys[slot] != id; ++probe) slot = (slot + 1) & (unsigned int)(slots - 1);
+        atomicMax(&sWinner, ((unsigned long long)(unsigned int)counts[slot] << 32) | (unsigned int)(INT32_MAX - i));
+    }
+    sTargets[tid] = nTarget;
+    __syncthreads();
+    for (int s = PT / 2; s > 0; s >>= 1) {
+        if (tid < s) sTargets[tid] += sTargets[tid + s];
+        __syncthreads();
+    }
+    const unsigned long long winner = sWinner;
+    const bool any = winner != 0ull && !bad;
+    const int32_t winnerId = winner != 0ull ? g.cluster[INT32_MAX - (int)(unsigned int)(winner & 0xffffffffull)] : 0;
+    __syncthreads();   // the table has been read: its memory now holds the products
+    double* terms = (double*)stateLds;   // [8][PT]
+    double acc = 0.0;
+    for (int base = 0; base < n; base += PT) {
+        const int i = base + tid;
+        double t[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (i < n) {
+            const double w = g.weight[i];
+            t[7] = w;
+            if (any && g.target[i] && g.cluster[i] == winnerId) {
+                t[0] = w * g.x[i]; t[1] = w * g.y[i]; t[2] = w * g.size[i]; t[3] = w * g.vx[i]; t[4] = w * g.vy[i]; t[5] = w * g.vsize[i];
+                t[6] = w;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) terms[c * PT + tid] = t[c];
+        __syncthreads();
+        if (tid < 8) {
+            const int m = min(PT, n - base);
+            const double* column = terms + tid * PT;
+            for (int j = 0; j < m; ++j) acc = acc + column[j];
+        }
+        __syncthreads();
+    }
+    if (tid < 8) sSums[tid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        const double weightSum = sSums[6];
+        info->count = n;
+        info->n_target = sTargets[0];
+        info->weight_sum = sSums[7];
+        if (bad) info->bad_weight = 1;
+        info->found = 0;
+        info->x = info->y = info->size = info->vx = info->vy = 0;
+        info->vsize = 0.f;
+        info->cluster_id = winnerId;
+        if (any && weightSum != 0) {   // if (weightSum == 0) return shared_ptr<Sample>()
+            info->found = 1;
+            info->x = (int)(sSums[0] / weightSum + 0.5);
+            info->y = (int)(sSums[1] / weightSum + 0.5);
+            info->size = (int)(sSums[2] / weightSum + 0.5);
+            info->vx = (int)(sSums[3] / weightSum + 0.5);
+            info->vy = (int)(sSums[4] / weightSum + 0.5);
+            info->vsize = (float)(int)(sSums[5] / weightSum + 0.5);   // the reference truncates the size factor as well
+        }
+    }
+}
+
+int particle_state_slots(int n) {
+    int slots = 2048;   // 16 KB: the eight columns of products fit
+    while (slots < 2 * n) slots *= 2;
+    return slots;
+}
+
+}  // namespace
+
+struct fd_particles {
+    fd_ctx* ctx = nullptr;
+    fd_ehog_tracker* tracker = nullptr;
+    int capacity = 0, n = 0, cur = 0;
+    bool sumKnown = true, bad = false, evaluated = false;
+    double sum = 0.0;   // the weights of the current generation added in index order, when sumKnown
+    DevBuf arena, staging, dinfo;
+    ParticleGen gen[2];
+    int32_t* source = nullptr;
+    int32_t* windows = nullptr;   // {layer, bx, by, valid} per sample, written by fd_particles_evaluate
+    uint8_t* valid = nullptr;
+    HostBuf pinned;   // the draws of one fd_particles_sample on their way to the device
+    hipEvent_t uploaded = nullptr;
+    ~fd_particles() { if (uploaded) (void)hipEventDestroy(uploaded); }
+};
+
+namespace {
+
+fd_particles* particles_checked(fd_ctx* ctx, fd_particles* p, const char* what) {
+    if (!ctx || !p) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", what);
+    if (p->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    return p;
+}
+
+// state kernel + the read-back of the info; refreshes what the host knows about the generation
+void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out) {
+    static uint64_t allowed = 0;
+    const int slots = particle_state_slots(p->n);
+    const size_t lds = sizeof(int32_t) * 2 * (size_t)slots;
+    fd_allow_lds(ctx, (const void*)k_particles_state, (int)(sizeof(int32_t) * 2 * (size_t)particle_state_slots(FD_PARTICLES_MAX)), allowed);
+    hipLaunchKernelGGL(k_particles_state, dim3(1), dim3(PT), lds, ctx->stream, p->gen[p->cur], p->n, slots, p->dinfo.as<fd_particles_info>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, p->dinfo.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    p->sum = out->weight_sum;
+    p->sumKnown = true;
+    p->bad = out->bad_weight != 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fd_particles_create(fd_ctx* ctx, fd_ehog_tracker* t, int capacity, fd_particles** out) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !t || !out) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create: NULL argument");
+        if (capacity < 1 || capacity > FD_PARTICLES_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create: the capacity must be 1 .. %d", FD_PARTICLES_MAX);
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::unique_ptr<fd_particles> p(new fd_particles());
+        p->ctx = ctx;
+        p->tracker = t;
+        p->capacity = capacity;
+        const size_t N = (size_t)capacity;
+        // per generation: weight, score (8 N each), x, y, size, vx, vy, vsize, cluster (4 N each), target (N); then the window list (16 N), source (4 N) and valid (N)
+        const size_t perGen = (16 * N + 28 * N + N + 63) & ~(size_t)63;   // the doubles of the second generation stay aligned
+        p->arena.reserve(2 * perGen + 20 * N + N);
+        HIP_CHECK(hipMemset(p->arena.p, 0, 2 * perGen + 20 * N + N));
+        unsigned char* base = p->arena.as<unsigned char>();
+        for (int gi = 0; gi < 2; ++gi) {
+            unsigned char* b = base + perGen * gi;
+            ParticleGen& G = p->gen[gi];
+            G.weight = (double*)b; G.score = (double*)(b + 8 * N);
+            int32_t* q = (int32_t*)(b + 16 * N);
+            G.x = q; G.y = q + N; G.size = q + 2 * N; G.vx = q + 3 * N; G.vy = q + 4 * N; G.vsize = (float*)(q + 5 * N); G.cluster = q + 6 * N;
+            G.target = (uint8_t*)(q + 7 * N);
+        }
+        p->windows = (int32_t*)(base + 2 * perGen);   // 16-byte elements at a 64-byte boundary
+        p->source = (int32_t*)(base + 2 * perGen + 16 * N);
+        p->valid = (uint8_t*)(base + 2 * perGen + 20 * N);
+        p->staging.reserve(36 * N);
+        p->pinned.reserve(36 * N);
+        p->dinfo.reserve(sizeof(fd_particles_info));
+        fd_particles_info zero;
+        std::memset(&zero, 0, sizeof(zero));
+        zero.best_score = -DBL_MAX;
+        HIP_CHECK(hipMemcpy(p->dinfo.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        HIP_CHECK(hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming));
+        *out = p.release();
+    });
+}
+
+void fd_particles_destroy(fd_particles* p) { delete p; }
+
+int fd_particles_capacity(const fd_particles* p) { return p ? p->capacity : 0; }
+
+int fd_particles_route_enabled(void) { return fd_knob_cond_device() ? 1 : 0; }
+
+int fd_particles_set(fd_ctx* ctx, fd_particles* p, int n, const fd_particles_arrays* in) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_set");
+        if (n < 0 || n > p->capacity) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_set: %d samples, the capacity is %d", n, p->capacity);
+        if (n > 0 && (!in || !in->x || !in->y || !in->size || !in->vx || !in->vy || !in->vsize || !in->weight || !in->cluster_id))
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_set: NULL argument");
+        double sum = 0.0;
+        bool bad = false;
+        for (int i = 0; i < n; ++i) {
+            if (in->cluster_id[i] == PARTICLE_NO_CLUSTER) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_set: cluster id %d is reserved", PARTICLE_NO_CLUSTER);
+            sum = sum + in->weight[i];
+            bad = bad || !particle_weight_ok(in->weight[i]);
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        const ParticleGen& G = p->gen[p->cur];
+        const size_t N = (size_t)n;
+        if (n > 0) {
+            HIP_CHECK(hipMemcpy(G.x, in->x, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.y, in->y, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.size, in->size, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.vx, in->vx, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.vy, in->vy, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.vsize, in->vsize, 4 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.weight, in->weight, 8 * N, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(G.cluster, in->cluster_id, 4 * N, hipMemcpyHostToDevice));
+            if (in->score) HIP_CHECK(hipMemcpy(G.score, in->score, 8 * N, hipMemcpyHostToDevice));
+            else HIP_CHECK(hipMemset(G.score, 0, 8 * N));
+            if (in->target) HIP_CHECK(hipMemcpy(G.target, in->target, N, hipMemcpyHostToDevice));
+            else HIP_CHECK(hipMemset(G.target, 0, N));
+            HIP_CHECK(hipMemset(p->source, 0xff, 4 * N));
+            HIP_CHECK(hipMemset(p->valid, 0, N));
+        }
+        fd_particles_info zero;
+        std::memset(&zero, 0, sizeof(zero));
+        zero.count = n;
+        zero.best_score = -DBL_MAX;
+        zero.bad_weight = bad;
+        HIP_CHECK(hipMemcpy(p->dinfo.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
+        p->n = n;
+        p->sum = sum;
+        p->sumKnown = true;
+        p->bad = bad;
+        p->evaluated = false;
+    });
+}
+
+int fd_particles_get(fd_ctx* ctx, fd_particles* p, int cap, int* n, const fd_particles_arrays* out) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_get");
+        if (!n || cap < 0) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_get: bad argument");
+        *n = p->n;
+        if (p->n > cap) FD_THROW(FD_ERR_CAPACITY, "fd_particles_get: %d samples, capacity %d", p->n, cap);
+        const ParticleGen& G = p->gen[p->cur];
+        const size_t N = (size_t)p->n;
+        auto fetch = [&](void* dst, const void* src, size_t bytes) {
+            if (dst && bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        };
+        if (out) {
+            fetch(out->x, G.x, 4 * N); fetch(out->y, G.y, 4 * N); fetch(out->size, G.size, 4 * N); fetch(out->vx, G.vx, 4 * N); fetch(out->vy, G.vy, 4 * N);
+            fetch(out->vsize, G.vsize, 4 * N); fetch(out->weight, G.weight, 8 * N); fetch(out->score, G.score, 8 * N); fetch(out->target, G.target, N);
+            fetch(out->cluster_id, G.cluster, 4 * N);
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_particles_get_trace(fd_ctx* ctx, fd_particles* p, int32_t* source, int32_t* windows, uint8_t* valid) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_get_trace");
+        const size_t N = (size_t)p->n;
+        if (windows && !p->evaluated) FD_THROW(FD_ERR_RUNTIME, "fd_particles_get_trace: the generation has not been evaluated");
+        if (source && N) HIP_CHECK(hipMemcpyAsync(source, p->source, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+        if (valid && N) HIP_CHECK(hipMemcpyAsync(valid, p->valid, N, hipMemcpyDeviceToHost, ctx->stream));
+        if (windows && N) HIP_CHECK(hipMemcpyAsync(windows, p->windows, 16 * N, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_particles_sample(fd_ctx* ctx, fd_particles* p, int count, int n_resampled, double u, const double* diffusion, const int32_t* fresh,
+                        int32_t first_fresh_cluster_id) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_sample");
+        if (count < 0 || count > p->capacity) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: %d samples, the capacity is %d", count, p->capacity);
+        if (n_resampled < 0 || n_resampled > count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: %d of %d samples resampled", n_resampled, count);
+        const int nFresh = count - n_resampled;
+        if ((n_resampled > 0 && !diffusion) || (nFresh > 0 && !fresh)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: NULL argument");
+        if (nFresh > 0 && ((int64_t)first_fresh_cluster_id + nFresh - 1 > INT32_MAX || first_fresh_cluster_id == PARTICLE_NO_CLUSTER))
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: the fresh cluster ids leave the int range");
+        if (!p->sumKnown) {   // weighed since the last read-back: ask the device for the sum the step is made of
+            fd_particles_info info;
+            particles_read_state(ctx, p, &info);
+        }
+        if (p->bad) FD_THROW(FD_ERR_RUNTIME, "fd_particles_sample: the generation holds a weight that is negative or not finite");
+        // LowVarianceSampling.cpp:22-26
+        int nCopies = 0;
+        double step = 0.0, start = 0.0;
+        if (p->n > 0 && n_resampled > 0) {
+            step = p->sum / (size_t)n_resampled;
+            if (step > 0) {
+                start = step * u;
+                nCopies = n_resampled;
+            }
+        }
+        // the draws: one pinned block, one copy
+        HIP_CHECK(hipEventSynchronize(p->uploaded));
+        unsigned char* pin = p->pinned.as<unsigned char>();
+        const size_t diffBytes = sizeof(double) * 3 * (size_t)nCopies, freshBytes = sizeof(int32_t) * 3 * (size_t)nFresh;
+        if (diffBytes) std::memcpy(pin, diffusion, diffBytes);
+        if (freshBytes) std::memcpy(pin + diffBytes, fresh, freshBytes);
+        if (diffBytes + freshBytes) {
+            HIP_CHECK(hipMemcpyAsync(p->staging.p, pin, diffBytes + freshBytes, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipEventRecord(p->uploaded, ctx->stream));
+        }
+        const int next = p->cur ^ 1;
+        hipLaunchKernelGGL(k_particles_sample, dim3(1), dim3(PT), nCopies > 0 ? sizeof(double) * (size_t)p->n : 0, ctx->stream, p->gen[p->cur], p->gen[next],
+                           p->n, nCopies, nFresh, step, start, p->staging.as<double>(), (const int32_t*)(p->staging.as<unsigned char>() + diffBytes),
+                           first_fresh_cluster_id, p->source, p->dinfo.as<fd_particles_info>());
+        HIP_CHECK(hipGetLastError());
+        p->cur = next;
+        p->n = nCopies + nFresh;
+        p->sum = (double)p->n;   // every new sample has weight 1: n times 1 added up is exact
+        p->sumKnown = true;
+        p->evaluated = false;
+    });
+}
+
+int fd_particles_evaluate(fd_ctx* ctx, fd_particles* p, int use_patches, double aspect_ratio) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_evaluate");
+        const ParticleGen& G = p->gen[p->cur];
+        fd_ehog_tracker_score_particles(ctx, p->tracker, p->n, G.x, G.y, G.size, aspect_ratio, use_patches != 0, p->windows, p->valid, G.score);
+        p->evaluated = true;
+    });
+}
+
+int fd_particles_weigh(fd_ctx* ctx, fd_particles* p, double logistic_a, double logistic_b, double svm_threshold, int mode, double rejection_threshold) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_weigh");
+        if (mode != FD_PARTICLES_TARGET_LOST && mode != FD_PARTICLES_SLIDING_WINDOW && mode != FD_PARTICLES_ALL_TARGETS)
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_weigh: unknown mode %d", mode);
+        if (!p->evaluated) FD_THROW(FD_ERR_RUNTIME, "fd_particles_weigh: the generation has not been evaluated (fd_particles_evaluate)");
+        hipLaunchKernelGGL(k_particles_weigh, dim3(1), dim3(PT), 0, ctx->stream, p->gen[p->cur], p->n, p->valid, logistic_a, logistic_b, svm_threshold, mode,
+                           rejection_threshold, p->dinfo.as<fd_particles_info>());
+        HIP_CHECK(hipGetLastError());
+        p->sumKnown = false;
+    });
+}
+
+int fd_particles_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_state");
+        if (!out) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_state: NULL argument");
+        particles_read_state(ctx, p, out);
+        if (out->bad_weight) FD_THROW(FD_ERR_RUNTIME, "fd_particles_state: the generation holds a weight that is negative or not finite");
+    });
+}
+
+}  // extern "C"

@@ -7,8 +7,9 @@
 //
 // Kernels: k_ehog_heat (all layers, LPC lanes per cell, lane == channel), k_ehog_gather_scores / k_ehog_gather_cells (samples),
 // k_ehog_patch (one wavefront per sample, patch and histograms in LDS), k_ehog_peak (one workgroup), k_ehog_maxima.
-// The sample -> (layer, position) arithmetic is double log / round / cvRound and runs on the host with libm, like the
-// reference; the device receives the window list.
+// The sample -> (layer, position) arithmetic is double log / round / cvRound: ehog_cell_window / ehog_patch_window below hold it once
+// for the host entry points (libm's log per sample, the window list uploaded) and for the resident particle set of condensation.hip
+// (k_ehog_resolve: the layer of a width read from a table the host built with the same libm expression).
 #pragma once
 
 struct EhogLayerPx { int32_t w, h; };   // real size of a gray layer (the layer table holds the area its cells cover)
@@ -37,6 +38,8 @@ struct fd_ehog_tracker {
     FhogLayoutTotals layout;
     void* arenaAt = nullptr;
     DevBuf dlayers, dlayerPx, desc, heat, dweights, list, outScore, outFeat, outValid, peak, maxima, counter, patchCoeff;
+    DevBuf dplan, dcellLayerOf, dpatchLayerOf;   // the layer plan and the width -> layer tables of k_ehog_resolve (rebuilt with the plan)
+    int cellLayerOfLen = 0, patchLayerOfLen = 0;
     std::vector<float> weights;
     float bias = 0.f;
     bool hasSvm = false, updated = false;
@@ -47,6 +50,77 @@ struct fd_ehog_tracker {
 namespace {
 
 constexpr size_t EHOG_PATCH_LDS_BUDGET = 64 * 1024;
+
+// what turns a sample into a window, apart from the layers
+struct EhogWindowRule {
+    int32_t cellCols, cellRows, cell, PW, PH, nLayers, firstLayer, octaveLayers;
+    double widthFactor, heightFactor;
+};
+
+__host__ __device__ inline int ehog_cvround(double v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int)rint(v);   // half to even, like lrint in the default rounding mode
+#else
+    return fd_cvRound(v);
+#endif
+}
+
+// the position in the layer list a width maps to: lround(log(patchWidth / width) / log(inc)) - first index (ImagePyramid.cpp:300-310)
+inline long ehog_layer_of_width(const EhogWindowRule& R, int patchWidth, int width) {
+    const double inc = std::pow(0.5, 1. / R.octaveLayers);
+    const double scaleFactor = static_cast<double>(patchWidth) / static_cast<double>(width);
+    return std::lround(std::log(scaleFactor) / std::log(inc)) - R.firstLayer;
+}
+
+// samples -> windows in cells (CellBasedPyramidFeatureExtractor.cpp:58-69, DirectPyramidFeatureExtractor.cpp:67-73,133-143):
+// {layer, bx, by, valid}.  layerOf(width) is ehog_layer_of_width or a table of it.
+template <class LayerOf>
+__host__ __device__ inline int4 ehog_cell_window(const EhogWindowRule& R, const fd_ehog_layer* layers, int x, int y, int width, int height, LayerOf layerOf) {
+    if (width <= 0 || height <= 0) return make_int4(0, 0, 0, 0);
+    const long realIndex = layerOf(width);
+    if (realIndex < 0 || realIndex >= (long)R.nLayers) return make_int4(0, 0, 0, 0);
+    const fd_ehog_layer& L = layers[realIndex];
+    const int bx = ehog_cvround((x - width / 2) * L.scale / R.cell), by = ehog_cvround((y - height / 2) * L.scale / R.cell);
+    if (bx < 0 || by < 0 || bx + R.cellCols > L.cols || by + R.cellRows > L.rows) return make_int4(0, 0, 0, 0);
+    return make_int4((int)realIndex, bx, by, 1);
+}
+
+// ExtendedHogFeatureExtractor::extract (:95-107): widened size, layer, bounds in the layer's pixels.  layerOf takes the widened width.
+template <class LayerOf>
+__host__ __device__ inline int4 ehog_patch_window(const EhogWindowRule& R, const fd_ehog_layer* layers, int x, int y, int sampleWidth, int sampleHeight,
+                                                  LayerOf layerOf) {
+    if (sampleWidth <= 0 || sampleHeight <= 0) return make_int4(0, 0, 0, 0);
+    const int width = static_cast<int>(round(R.widthFactor * sampleWidth));
+    const int height = static_cast<int>(round(R.heightFactor * sampleHeight));
+    const long realIndex = layerOf(width);
+    if (realIndex < 0 || realIndex >= (long)R.nLayers) return make_int4(0, 0, 0, 0);
+    const fd_ehog_layer& L = layers[realIndex];
+    const int bx = ehog_cvround((x - width / 2) * L.scale), by = ehog_cvround((y - height / 2) * L.scale);
+    if (bx < -R.cell || bx + R.PW > L.width + R.cell || by < -R.cell || by + R.PH > L.height + R.cell) return make_int4(0, 0, 0, 0);
+    return make_int4((int)realIndex, bx, by, 1);
+}
+
+// the samples of a resident particle set (x, y, size; height = cvRound(aspect * size), Sample.hpp:127-129) -> the window list of
+// k_ehog_gather_scores (patches 0) or k_ehog_patch (patches 1).  layerOf[w]: the layer position of width w, -1 for none; widths from
+// tableLen on have none.
+__global__ __launch_bounds__(256) void k_ehog_resolve(EhogWindowRule R, const fd_ehog_layer* __restrict__ layers, const int16_t* __restrict__ layerOf,
+                                                      int tableLen, const int32_t* __restrict__ x, const int32_t* __restrict__ y,
+                                                      const int32_t* __restrict__ size, int n, double aspect, int patches, int4* __restrict__ list,
+                                                      uint8_t* __restrict__ valid) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int width = size[i], height = ehog_cvround(aspect * width);
+    auto look = [&](int w) -> long { return w > 0 && w < tableLen ? (long)layerOf[w] : -1L; };
+    const int4 w = patches ? ehog_patch_window(R, layers, x[i], y[i], width, height, look) : ehog_cell_window(R, layers, x[i], y[i], width, height, look);
+    list[i] = w;
+    valid[i] = (uint8_t)w.w;
+}
+
+// the float scores of k_ehog_gather_scores as the doubles a Sample keeps
+__global__ __launch_bounds__(256) void k_ehog_widen_scores(const float* __restrict__ in, int n, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (double)in[i];
+}
 
 // ConvolutionFilter::applyTo (ConvolutionFilter.cpp:27-43) with anchor (-1, -1) = the kernel centre (kw / 2, kh / 2),
 // BORDER_CONSTANT 0 and delta = -bias, on every feature layer of the table: heat(y, x) = delta + sum over channels c of
@@ -356,30 +430,54 @@ fd_ehog_tracker* ehog_checked(fd_ctx* ctx, fd_ehog_tracker* t, const char* what,
 }
 
 // samples -> windows in cells (CellBasedPyramidFeatureExtractor.cpp:58-69, DirectPyramidFeatureExtractor.cpp:67-73,133-143,
-// ImagePyramid.cpp:300-310); uploads the list, fills valid
-void ehog_sample_windows(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* xywh, uint8_t* valid) {
+// ImagePyramid.cpp:300-310) through ehog_cell_window; uploads the list, fills valid
+EhogWindowRule ehog_window_rule(const fd_ehog_tracker* t) {
     const fd_ehog_tracker_params& P = t->prm;
-    const int cell = P.filter.cell_size;
-    const double inc = std::pow(0.5, 1. / P.octave_layer_count);
-    const int firstLayer = t->layers.empty() ? 0 : t->layers[0].index;
+    EhogWindowRule R;
+    R.cellCols = P.cell_cols; R.cellRows = P.cell_rows; R.cell = P.filter.cell_size; R.PW = t->geom.PW; R.PH = t->geom.PH;
+    R.nLayers = (int32_t)t->layers.size(); R.firstLayer = t->layers.empty() ? 0 : t->layers[0].index; R.octaveLayers = P.octave_layer_count;
+    R.widthFactor = static_cast<double>(P.cell_cols + 2) / P.cell_cols; R.heightFactor = static_cast<double>(P.cell_rows + 2) / P.cell_rows;
+    return R;
+}
+
+void ehog_sample_windows(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* xywh, uint8_t* valid) {
+    const EhogWindowRule R = ehog_window_rule(t);
     int4* pin = (int4*)fd_pinned(ctx, sizeof(int4) * (size_t)std::max(n, 1));
     for (int i = 0; i < n; ++i) {
-        const int x = xywh[4 * i], y = xywh[4 * i + 1], width = xywh[4 * i + 2], height = xywh[4 * i + 3];
-        pin[i] = make_int4(0, 0, 0, 0);
-        valid[i] = 0;
-        if (width <= 0 || height <= 0) continue;
-        const double scaleFactor = static_cast<double>(P.cell_cols * cell) / static_cast<double>(width);
-        const double power = std::log(scaleFactor) / std::log(inc);
-        const long realIndex = std::lround(power) - firstLayer;
-        if (realIndex < 0 || realIndex >= (long)t->layers.size()) continue;
-        const fd_ehog_layer& L = t->layers[realIndex];
-        const int bx = fd_cvRound((x - width / 2) * L.scale / cell), by = fd_cvRound((y - height / 2) * L.scale / cell);
-        if (bx < 0 || by < 0 || bx + P.cell_cols > L.cols || by + P.cell_rows > L.rows) continue;
-        pin[i] = make_int4((int)realIndex, bx, by, 1);
-        valid[i] = 1;
+        pin[i] = ehog_cell_window(R, t->layers.data(), xywh[4 * i], xywh[4 * i + 1], xywh[4 * i + 2], xywh[4 * i + 3],
+                                  [&](int width) { return ehog_layer_of_width(R, R.cellCols * R.cell, width); });
+        valid[i] = (uint8_t)pin[i].w;
     }
     t->list.reserve(sizeof(int4) * (size_t)std::max(n, 1));
     if (n) HIP_CHECK(hipMemcpyAsync(t->list.p, pin, sizeof(int4) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+}
+
+// width -> layer for every width that can have one: a width twice the one that maps onto the last layer is an octave past it
+void ehog_build_layer_tables(fd_ehog_tracker* t) {
+    const EhogWindowRule R = ehog_window_rule(t);
+    auto build = [&](int patchWidth, DevBuf& dev, int& len) {
+        const double last = t->layers.empty() ? 1.0 : t->layers.back().scale;
+        len = (int)std::min<double>(2.0 * patchWidth / last + 2.0, (double)(1 << 20));
+        std::vector<int16_t> table((size_t)len, (int16_t)-1);
+        for (int w = 1; w < len; ++w) {
+            const long realIndex = ehog_layer_of_width(R, patchWidth, w);
+            if (realIndex >= 0 && realIndex < (long)R.nLayers) table[w] = (int16_t)realIndex;
+        }
+        dev.reserve(sizeof(int16_t) * table.size());
+        HIP_CHECK(hipMemcpy(dev.p, table.data(), sizeof(int16_t) * table.size(), hipMemcpyHostToDevice));
+    };
+    build(R.cellCols * R.cell, t->dcellLayerOf, t->cellLayerOfLen);
+    build(R.PW, t->dpatchLayerOf, t->patchLayerOfLen);
+    t->dplan.reserve(sizeof(fd_ehog_layer) * std::max<size_t>(t->layers.size(), 1));
+    if (!t->layers.empty()) HIP_CHECK(hipMemcpy(t->dplan.p, t->layers.data(), sizeof(fd_ehog_layer) * t->layers.size(), hipMemcpyHostToDevice));
+}
+
+void ehog_check_patch_lds(const fd_ehog_tracker* t, const char* what) {
+    const fd_ehog_tracker_params& P = t->prm;
+    const int ldsBytes = fd_ehog_tracker_patch_lds_bytes(&P);
+    if (ldsBytes < 0 || (size_t)ldsBytes > EHOG_PATCH_LDS_BUDGET)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: a patch of %d x %d cells of %d pixels with %d bins needs %d bytes of LDS, a workgroup has %zu", what,
+                 P.cell_cols + 2, P.cell_rows + 2, P.filter.cell_size, P.filter.bin_count, ldsBytes, EHOG_PATCH_LDS_BUDGET);
 }
 
 }  // namespace
@@ -466,6 +564,7 @@ int fd_ehog_tracker_update(fd_ctx* ctx, fd_ehog_tracker* t, const uint8_t* image
             HIP_CHECK(hipMemcpy(t->dlayers.p, t->layerTable.data(), sizeof(FhogLayerDev) * t->layerTable.size(), hipMemcpyHostToDevice));
             t->dlayerPx.reserve(sizeof(EhogLayerPx) * t->layerPx.size());
             HIP_CHECK(hipMemcpy(t->dlayerPx.p, t->layerPx.data(), sizeof(EhogLayerPx) * t->layerPx.size(), hipMemcpyHostToDevice));
+            ehog_build_layer_tables(t);
             t->arenaAt = p->arena.p;
             t->pyrW = width; t->pyrH = height;
         }
@@ -598,32 +697,14 @@ int fd_ehog_tracker_extract_patches(fd_ctx* ctx, fd_ehog_tracker* t, int n, cons
         if (score && !t->hasSvm) FD_THROW(FD_ERR_RUNTIME, "fd_ehog_tracker_extract_patches: no SVM has been set (fd_ehog_tracker_set_svm)");
         const fd_ehog_tracker_params& P = t->prm;
         const EhogPatchGeom& G = t->geom;
-        const int ldsBytes = fd_ehog_tracker_patch_lds_bytes(&P);
-        if (ldsBytes < 0 || (size_t)ldsBytes > EHOG_PATCH_LDS_BUDGET)
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_ehog_tracker_extract_patches: a patch of %d x %d cells of %d pixels with %d bins needs %d bytes of LDS, a workgroup has %zu",
-                     P.cell_cols + 2, P.cell_rows + 2, P.filter.cell_size, P.filter.bin_count, ldsBytes, EHOG_PATCH_LDS_BUDGET);
+        ehog_check_patch_lds(t, "fd_ehog_tracker_extract_patches");
         if (n == 0) return;
-        // ExtendedHogFeatureExtractor::extract (:95-107): widened size, layer, bounds in the layer's pixels
-        const int cell = P.filter.cell_size;
-        const double widthFactor = static_cast<double>(P.cell_cols + 2) / P.cell_cols, heightFactor = static_cast<double>(P.cell_rows + 2) / P.cell_rows;
-        const double inc = std::pow(0.5, 1. / P.octave_layer_count);
-        const int firstLayer = t->layers.empty() ? 0 : t->layers[0].index;
+        const EhogWindowRule R = ehog_window_rule(t);
         int4* pin = (int4*)fd_pinned(ctx, sizeof(int4) * (size_t)n);
         for (int i = 0; i < n; ++i) {
-            const int x = xywh[4 * i], y = xywh[4 * i + 1];
-            pin[i] = make_int4(0, 0, 0, 0);
-            valid[i] = 0;
-            if (xywh[4 * i + 2] <= 0 || xywh[4 * i + 3] <= 0) continue;
-            const int width = static_cast<int>(std::round(widthFactor * xywh[4 * i + 2]));
-            const int height = static_cast<int>(std::round(heightFactor * xywh[4 * i + 3]));
-            const double scaleFactor = static_cast<double>(G.PW) / static_cast<double>(width);
-            const long realIndex = std::lround(std::log(scaleFactor) / std::log(inc)) - firstLayer;
-            if (realIndex < 0 || realIndex >= (long)t->layers.size()) continue;
-            const fd_ehog_layer& L = t->layers[realIndex];
-            const int bx = fd_cvRound((x - width / 2) * L.scale), by = fd_cvRound((y - height / 2) * L.scale);
-            if (bx < -cell || bx + G.PW > L.width + cell || by < -cell || by + G.PH > L.height + cell) continue;
-            pin[i] = make_int4((int)realIndex, bx, by, 1);
-            valid[i] = 1;
+            pin[i] = ehog_patch_window(R, t->layers.data(), xywh[4 * i], xywh[4 * i + 1], xywh[4 * i + 2], xywh[4 * i + 3],
+                                       [&](int width) { return ehog_layer_of_width(R, R.PW, width); });
+            valid[i] = (uint8_t)pin[i].w;
         }
         t->list.reserve(sizeof(int4) * (size_t)n);
         HIP_CHECK(hipMemcpyAsync(t->list.p, pin, sizeof(int4) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -705,3 +786,38 @@ int fd_ehog_tracker_heat_maxima(fd_ctx* ctx, fd_ehog_tracker* t, float threshold
 }
 
 }  // extern "C"
+
+// fd_particles_evaluate (condensation.hip): the samples of a resident particle set, all in device memory, resolved to windows by
+// k_ehog_resolve and scored by the kernels of fd_ehog_tracker_evaluate_samples (use_patches 0) or _extract_patches (1).  Queued on
+// the context's stream; nothing is copied back.  The window list {layer, bx, by, valid} goes to `windows` (the caller's, 4 n ints: the
+// tracker's own list belongs to its host entry points); the features of the patch form stay in t->outFeat.
+void fd_ehog_tracker_score_particles(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* x, const int32_t* y, const int32_t* size, double aspect,
+                                     int use_patches, int32_t* windows, uint8_t* valid, double* score) {
+    ehog_checked(ctx, t, "fd_particles_evaluate", true, true);
+    if (use_patches) ehog_check_patch_lds(t, "fd_particles_evaluate");
+    if (n <= 0) return;
+    const EhogWindowRule R = ehog_window_rule(t);
+    int4* list = (int4*)windows;
+    hipLaunchKernelGGL(k_ehog_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, R, t->dplan.as<fd_ehog_layer>(),
+                       use_patches ? t->dpatchLayerOf.as<int16_t>() : t->dcellLayerOf.as<int16_t>(), use_patches ? t->patchLayerOfLen : t->cellLayerOfLen,
+                       x, y, size, n, aspect, use_patches, list, valid);
+    HIP_CHECK(hipGetLastError());
+    if (!use_patches) {
+        t->outScore.reserve(sizeof(float) * (size_t)n);
+        hipLaunchKernelGGL(k_ehog_gather_scores, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, t->dlayers.as<FhogLayerDev>(), list, n,
+                           t->prm.cell_rows / 2, t->prm.cell_cols / 2, t->heat.as<float>(), t->outScore.as<float>());
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_ehog_widen_scores, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, t->outScore.as<float>(), n, score);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    const fd_ehog_tracker_params& P = t->prm;
+    const EhogPatchGeom& G = t->geom;
+    CehogScratch& C = fd_scratch<CehogScratch>(ctx);
+    cehog_upload_lut(ctx, C, P.filter);
+    t->outFeat.reserve(sizeof(float) * (size_t)P.cell_rows * P.cell_cols * t->D * (size_t)n);
+    hipLaunchKernelGGL(k_ehog_patch, dim3(n), dim3(64), (size_t)G.bytes, ctx->stream, t->dlayers.as<FhogLayerDev>(), t->dlayerPx.as<EhogLayerPx>(),
+                       list, G, C.lut.as<FhogLutEntry>(), t->patchCoeff.as<FhogCoeffDev>(), t->dweights.as<float>(), -(double)t->bias,
+                       t->outFeat.as<float>(), score);
+    HIP_CHECK(hipGetLastError());
+}

@@ -312,6 +312,8 @@ static inline int fd_knob_fs_tail() { const char* e = getenv("FD_FS_TAIL"); retu
 // single-frame five-stage calls: the second stage over all first-stage positives behind the cascade (one host wait); 0: two waits.
 // Read per call: the tests compare both orders.
 static inline bool fd_knob_fs_spec() { const char* e = getenv("FD_FS_SPEC"); return !(e && atoi(e) == 0); }
+// the trackers of the host layer keep their particle set on the device: 1 on, anything else (and unset) off.  Read per call.
+static inline bool fd_knob_cond_device() { const char* e = getenv("FD_COND_DEVICE"); return e && atoi(e) == 1; }
 
 // FD_TRACE's stopwatch: lap_ns() is the time since the start (or the previous lap) and starts the next lap; off: no clock is read.
 struct FdStopwatch {
@@ -450,6 +452,12 @@ void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, co
 // its host buffer.  Throws FdError; leaves ctx->stream synchronised.
 void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
                       fd_svm_train_info* infos);
+
+// ---------------- resident particle set (condensation.hip) on an extended-HOG tracker (ehog_tracker.hpp) ----------------
+// scores n samples held in device memory (x, y, size; height = cvRound(aspect * size)): the window list (4 n ints), valid and score are
+// the caller's device buffers.  Queued on ctx->stream, no host wait.  Throws FdError.
+void fd_ehog_tracker_score_particles(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* x, const int32_t* y, const int32_t* size, double aspect,
+                                     int use_patches, int32_t* windows, uint8_t* valid, double* score);
 
 // ---------------- host-side detection logic (hostalgo.cpp) ----------------
 void fd_host_overlap_elimination(const fd_detection* in, int n, float dist, float ratio, std::vector<int>& keep);

@@ -1,0 +1,190 @@
+// tracker_app -- the frame loop of the reference's adaptiveTrackingApp / headTrackingApp / trackingBenchmarkApp (TrackingBenchmark.cpp:489-510,553):
+// a condensation::AdaptiveCondensationTracker on ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) or GridSampler, an
+// ExtendedHogBasedMeasurementModel and FilteringStateExtractor(WeightedMeanStateExtractor).
+//   usage: tracker_app [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
+// config (boost info format), the `tracking` block of algorithm.cfg:
+//   tracking {
+//     transition simple { positionDeviation 10  sizeDeviation 0.1 }            (optical flow is not supported)
+//     adaptive { resampling { particleCount 800  randomRate 0.35  minSize 40  maxSize 200 } }
+//     grid { minSize 20 maxSize 80 sizeScale 1.2 stepSize 0.1 }                (optional: a GridSampler in place of the resampling sampler)
+//     initialCount 800   seed 1                                                (seed: the samplers' generators get seed, seed + 1, seed + 2)
+//     measurement ehog { cellSize 5 cellCount 35 signedAndUnsigned 0 interpolateBins 0 interpolateCells 1 octaveLayerCount 5
+//                        rejectionThreshold -1.5 useSlidingWindow 1 conservativeReInit 0 negativeExampleCount 10 initialNegativeExampleCount 50
+//                        randomExampleCount 50 negativeScoreThreshold -1.0 positiveOverlapThreshold 0.5 negativeOverlapThreshold 0.5
+//                        adaptation position adaptationThreshold 0.75 exclusionThreshold 0.0
+//                        classifier { training { c 1  compensateImbalance 0  negativeCapacity 100 }  logisticA 0.00556  logisticB -2.95  threshold 0 } }
+//   }
+// the box is the target's bounding box (top left corner) in frame 0.  Prints "init <0|1> [x y w h]", then per further frame
+//   "frame <f> found <0|1> <x> <y> <w> <h> adapted <0|1> route <generic|device> ms <wall time of process()>"
+// With --dump every frame is followed by "draws u <0|1> <u> copies <n> fresh <m>", one "d <dx> <dy> <factor>" per copy, one "f <x> <y>
+// <size>" per random sample, "samples <n>" and one "s <x> <y> <size> <vx> <vy> <vsize> <weight> <score> <target> <clusterId>" per sample
+// (%.17g / %.9g: the values round-trip), so that tests/condensation_model.py can replay the run.
+//   tracker_app --selftest <seed> <frames> <count> <randomRate>
+// runs the samplers, the transition model and the extractors without a device: a CondensationTracker on a stub measurement model that
+// weighs a sample by its distance to a moving point, on 64 x 48 frames; it dumps every frame as above, and the GridSampler's samples.
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include "condensation/AdaptiveCondensationTracker.hpp"
+#include "condensation/CondensationTracker.hpp"
+#include "libsvm/LibSvmClassifier.hpp"
+#include "fdcompat/ptree.hpp"
+
+using namespace imageprocessing;
+using namespace classification;
+using namespace condensation;
+using boost::property_tree::ptree;
+using std::make_shared;
+using std::shared_ptr;
+using std::string;
+
+static cv::Mat read_pnm(const string& path) {
+    std::ifstream f(path.c_str(), std::ios::binary);
+    if (!f.is_open()) throw std::runtime_error("cannot open image " + path);
+    string magic;
+    int w, h, maxv;
+    f >> magic >> w >> h >> maxv;
+    f.get();
+    if ((magic != "P5" && magic != "P6") || maxv != 255) throw std::runtime_error("only binary PGM/PPM with maxval 255 are supported");
+    const int ch = magic == "P6" ? 3 : 1;
+    cv::Mat img(h, w, CV_MAKETYPE(CV_8U, ch));
+    f.read((char*)img.data, (size_t)w * h * ch);
+    if (ch == 3)
+        for (size_t i = 0; i < (size_t)w * h; ++i) std::swap(img.data[3 * i], img.data[3 * i + 2]);
+    return img;
+}
+
+static void dump(const shared_ptr<Sampler>& sampler, const std::vector<shared_ptr<Sample>>& samples) {
+    if (auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler)) {
+        const ResamplingSampler::Draws& d = resampling->getLastDraws();
+        std::printf("draws u %d %.17g copies %zu fresh %zu\n", d.hasU ? 1 : 0, d.u, d.diffusion.size() / 3, d.fresh.size() / 3);
+        for (size_t i = 0; i + 2 < d.diffusion.size(); i += 3) std::printf("d %.17g %.17g %.17g\n", d.diffusion[i], d.diffusion[i + 1], d.diffusion[i + 2]);
+        for (size_t i = 0; i + 2 < d.fresh.size(); i += 3) std::printf("f %d %d %d\n", d.fresh[i], d.fresh[i + 1], d.fresh[i + 2]);
+    }
+    std::printf("samples %zu\n", samples.size());
+    for (const auto& s : samples)
+        std::printf("s %d %d %d %d %d %.9g %.17g %.17g %d %d\n", s->getX(), s->getY(), s->getSize(), s->getVx(), s->getVy(), s->getVSize(), s->getWeight(),
+                    s->getScore(), s->isTarget() ? 1 : 0, s->getClusterId());
+}
+
+// weight = 1 / (1 + squared distance to a point that moves with the frames), target when closer than 12 pixels; no device involved
+struct StubModel : public MeasurementModel {
+    using MeasurementModel::evaluate;
+    int frame = 0;
+    void update(shared_ptr<VersionedImage>) override { ++frame; }
+    void evaluate(Sample& sample) const override {
+        const double dx = sample.getX() - (20 + 2 * frame), dy = sample.getY() - (16 + frame);
+        const double d2 = dx * dx + dy * dy;
+        sample.setScore(-d2);
+        sample.setWeight(sample.getWeight() * (1.0 / (1.0 + d2)));
+        sample.setTarget(d2 < 144);
+    }
+};
+
+static int selftest(int argc, char** argv) {
+    if (argc < 6) return 2;
+    const unsigned seed = (unsigned)std::atoi(argv[2]);
+    const int frames = std::atoi(argv[3]), count = std::atoi(argv[4]);
+    const double randomRate = std::atof(argv[5]);
+    cv::Mat image(48, 64, CV_8UC1);
+    std::memset(image.data, 0, 48 * 64);
+    Sample::setAspectRatio(1.0);
+    auto sampler = make_shared<ResamplingSampler>(count, randomRate, make_shared<LowVarianceSampling>(seed), make_shared<SimpleTransitionModel>(3.0, 0.1, seed + 1),
+                                                  8, 80, seed + 2);
+    sampler->init(image);
+    CondensationTracker tracker(sampler, make_shared<StubModel>(), make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()));
+    MaxWeightStateExtractor maxWeight;
+    for (int f = 0; f < frames; ++f) {
+        boost::optional<cv::Rect> box = tracker.process(image);
+        shared_ptr<Sample> s = tracker.getState();
+        if (s) std::printf("frame %d found 1 %d %d %d %d %d %.9g route generic\n", f, s->getX(), s->getY(), s->getSize(), s->getVx(), s->getVy(), s->getVSize());
+        else std::printf("frame %d found 0 route generic\n", f);
+        shared_ptr<Sample> m = maxWeight.extract(tracker.getSamples());
+        if (m) std::printf("max 1 %d %d %d\n", m->getX(), m->getY(), m->getSize());
+        else std::printf("max 0\n");
+        dump(sampler, tracker.getSamples());
+        if (box && s && (box->width != s->getWidth() || box->x != s->getX() - s->getWidth() / 2)) return 1;
+    }
+    GridSampler grid(10, 40, 1.5f, 0.25f);
+    std::vector<shared_ptr<Sample>> none, cells;
+    grid.sample(none, cells, image, shared_ptr<Sample>());
+    std::printf("grid %zu\n", cells.size());
+    for (const auto& s : cells) std::printf("g %d %d %d\n", s->getX(), s->getY(), s->getSize());
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    try {
+        if (argc > 1 && string(argv[1]) == "--selftest") return selftest(argc, argv);
+        const bool dumping = argc > 1 && string(argv[1]) == "--dump";
+        const int a = dumping ? 2 : 1;
+        if (argc < a + 6) {
+            std::fprintf(stderr, "usage: %s [--dump] <config.cfg> <x> <y> <width> <height> <frame0> [<frame1> ...]\n", argv[0]);
+            return 2;
+        }
+        ptree all;
+        boost::property_tree::read_info(string(argv[a]), all);
+        const ptree& pt = all.get_child("tracking");
+        if (pt.get("transition", string("simple")) != "simple") throw std::invalid_argument("tracker_app: only `transition simple` is supported");
+        const unsigned seed = (unsigned)pt.get("seed", 1);
+        shared_ptr<Sampler> sampler;
+        if (pt.count("grid"))
+            sampler = make_shared<GridSampler>(pt.get("grid.minSize", 20), pt.get("grid.maxSize", 80), (float)pt.get("grid.sizeScale", 1.2), (float)pt.get("grid.stepSize", 0.1));
+        else
+            sampler = make_shared<ResamplingSampler>(pt.get("adaptive.resampling.particleCount", 800), pt.get("adaptive.resampling.randomRate", 0.35),
+                                                     make_shared<LowVarianceSampling>(seed),
+                                                     make_shared<SimpleTransitionModel>(pt.get("transition.positionDeviation", 10.0), pt.get("transition.sizeDeviation", 0.1), seed + 1),
+                                                     pt.get("adaptive.resampling.minSize", 40), pt.get("adaptive.resampling.maxSize", 200), seed + 2);
+        const ptree& mt = pt.get_child("measurement");
+        if (pt.get("measurement", string("ehog")) != "ehog") throw std::invalid_argument("tracker_app: only `measurement ehog` is supported");
+        const ptree& ct = mt.get_child("classifier");
+        shared_ptr<ExtendedHogBasedMeasurementModel> model;
+        if (ct.count("training")) {
+            const ptree& tr = ct.get_child("training");
+            auto svm = libsvm::LibSvmClassifier::createBinarySvm(make_shared<LinearKernel>(), tr.get("c", 1.0), tr.get("compensateImbalance", 0) != 0);
+            svm->setNegativeExampleManagement(std::unique_ptr<ExampleManagement>(new AgeBasedExampleManagement(tr.get("negativeCapacity", 100))));
+            svm->getSvm()->setThreshold(ct.get("threshold", 0.0f));   // as ProbabilisticSvmClassifier::load reads it
+            model = make_shared<ExtendedHogBasedMeasurementModel>(
+                make_shared<FixedTrainableProbabilisticSvmClassifier>(svm, ct.get("logisticA", 0.00556), ct.get("logisticB", -2.95)));
+        } else {
+            model = make_shared<ExtendedHogBasedMeasurementModel>(ProbabilisticSvmClassifier::load(ct));
+        }
+        model->setHogParams(mt.get("cellSize", 5), mt.get("cellCount", 35), mt.get("signedAndUnsigned", 0) != 0, mt.get("interpolateBins", 0) != 0,
+                            mt.get("interpolateCells", 1) != 0, mt.get("octaveLayerCount", 5));
+        model->setRejectionThreshold(mt.get("rejectionThreshold", -1.5));
+        model->setUseSlidingWindow(mt.get("useSlidingWindow", 1) != 0, mt.get("conservativeReInit", 0) != 0);
+        model->setNegativeExampleParams(mt.get("negativeExampleCount", 10), mt.get("initialNegativeExampleCount", 50), mt.get("randomExampleCount", 50),
+                                        (float)mt.get("negativeScoreThreshold", -1.0));
+        model->setOverlapThresholds(mt.get("positiveOverlapThreshold", 0.5), mt.get("negativeOverlapThreshold", 0.5));
+        const string adaptation = mt.get("adaptation", string("position"));
+        model->setAdaptation(adaptation == "none" ? ExtendedHogBasedMeasurementModel::Adaptation::NONE
+                             : adaptation == "trajectory" ? ExtendedHogBasedMeasurementModel::Adaptation::TRAJECTORY
+                                                          : ExtendedHogBasedMeasurementModel::Adaptation::POSITION,
+                             mt.get("adaptationThreshold", 0.75), mt.get("exclusionThreshold", 0.0));
+        AdaptiveCondensationTracker tracker(sampler, model, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()),
+                                            pt.get("initialCount", 800));
+        const cv::Rect box(std::atoi(argv[a + 1]), std::atoi(argv[a + 2]), std::atoi(argv[a + 3]), std::atoi(argv[a + 4]));
+        boost::optional<cv::Rect> start = tracker.initialize(read_pnm(argv[a + 5]), box);
+        if (!start) {
+            std::printf("init 0\n");
+            return 1;
+        }
+        std::printf("init 1 %d %d %d %d\n", start->x, start->y, start->width, start->height);
+        for (int f = a + 6; f < argc; ++f) {
+            const cv::Mat frame = read_pnm(argv[f]);
+            const auto t0 = std::chrono::steady_clock::now();
+            boost::optional<cv::Rect> found = tracker.process(frame);
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            const cv::Rect r = found ? *found : cv::Rect();
+            std::printf("frame %d found %d %d %d %d %d adapted %d route %s ms %.3f\n", f - a - 5, found ? 1 : 0, r.x, r.y, r.width, r.height,
+                        tracker.hasAdapted() ? 1 : 0, tracker.getLastRoute() == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
+            if (dumping) dump(tracker.getSampler(), tracker.getSamples());
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "tracker_app: %s\n", e.what());
+        return 1;
+    }
+}

@@ -2,10 +2,13 @@
 // the tracking-side caller of the WVM -> SVM path.
 #pragma once
 #include <memory>
+#include <optional>
 #include <random>
 #include <vector>
 #include "classification/classification_all.hpp"
 #include "imageprocessing/imageprocessing_all.hpp"
+
+namespace boost { using std::optional; }   // the trackers return boost::optional<cv::Rect>; std::optional reads the same
 
 namespace condensation {
 
@@ -16,6 +19,10 @@ public:
     Sample(int x, int y, int size) : x(x), y(y), size(size), vx(0), vy(0), vsize(1), weight(1), target(false), clusterId(getNextClusterId()) {}
     Sample(int x, int y, int size, int vx, int vy, float vsize)
         : x(x), y(y), size(size), vx(vx), vy(vy), vsize(vsize), weight(1), target(false), clusterId(getNextClusterId()) {}
+    // a descendant (Sample.hpp:64-66): the parent's values and cluster, score 0, no target flag
+    explicit Sample(std::shared_ptr<Sample> other, double weight = 1)
+        : x(other->x), y(other->y), size(other->size), vx(other->vx), vy(other->vy), vsize(other->vsize), weight(weight), target(false),
+          clusterId(other->clusterId), ancestor(other) {}
     cv::Rect getBounds() const { return cv::Rect(x - getWidth() / 2, y - getHeight() / 2, getWidth(), getHeight()); }
     int getX() const { return x; }
     void setX(int v) { x = v; }
@@ -35,7 +42,9 @@ public:
     void setScore(double s) { score = s; }
     int getClusterId() const { return clusterId; }
     void setClusterId(int id) { clusterId = id; }
-    void resetAncestor() {}   // ancestors belong to the adaptation half (Sample.hpp:256-258), which is not kept here
+    const std::shared_ptr<Sample> getAncestor() const { return ancestor; }
+    void setAncestor(std::shared_ptr<Sample> a) { ancestor = a; }
+    void resetAncestor() { ancestor.reset(); }
     double getWeight() const { return weight; }
     void setWeight(double w) { weight = w; }
     bool isTarget() const { return target; }
@@ -53,6 +62,7 @@ private:
     bool target;
     double score = 0;
     int clusterId;
+    std::shared_ptr<Sample> ancestor;
 };
 
 // MeasurementModel.hpp:25-56
@@ -65,6 +75,25 @@ public:
         update(image);
         for (std::shared_ptr<Sample> sample : samples) evaluate(*sample);
     }
+};
+
+// AdaptiveMeasurementModel.hpp:25-83
+class AdaptiveMeasurementModel : public MeasurementModel {
+public:
+    using MeasurementModel::evaluate;
+    virtual ~AdaptiveMeasurementModel() {}
+    virtual bool isUsable() const = 0;
+    virtual bool initialize(std::shared_ptr<imageprocessing::VersionedImage> image, Sample& target) = 0;
+    virtual bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples, const Sample& target) = 0;
+    virtual bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples) = 0;
+    virtual void reset() = 0;
+};
+
+// StateValidator.hpp:24-40
+class StateValidator {
+public:
+    virtual ~StateValidator() {}
+    virtual bool isValid(const Sample& target, const std::vector<std::shared_ptr<Sample>>& samples, std::shared_ptr<imageprocessing::VersionedImage> image) = 0;
 };
 
 // WvmSvmModel.hpp / WvmSvmModel.cpp:36-118.  With a DirectPyramidFeatureExtractor + HistEq64Filter all samples are
@@ -110,7 +139,7 @@ private:
 // vector of cellRowCount * cellColumnCount * channels values.  With the reference's constructor (a TrainableProbabilisticSvmClassifier)
 // initialize is :321-384 and adapt :386-419 with adaptation NONE, POSITION and TRAJECTORY; CORRECTED_TRAJECTORY throws std::runtime_error.  The batched evaluate scores all samples with one fd_ehog_tracker_evaluate_samples
 // (sliding window) or one fd_ehog_tracker_extract_patches (no sliding window); getFusedEvaluationCount (not in the reference) counts them.
-class ExtendedHogBasedMeasurementModel : public MeasurementModel {
+class ExtendedHogBasedMeasurementModel : public AdaptiveMeasurementModel, public StateValidator {
 public:
     enum class Adaptation { NONE, POSITION, TRAJECTORY, CORRECTED_TRAJECTORY };
     explicit ExtendedHogBasedMeasurementModel(std::shared_ptr<classification::ProbabilisticSvmClassifier> classifier);
@@ -122,12 +151,17 @@ public:
     void update(std::shared_ptr<imageprocessing::VersionedImage> image) override;
     void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override;
     void evaluate(Sample& sample) const override;
-    bool isValid(const Sample& target, const std::vector<std::shared_ptr<Sample>>& samples, std::shared_ptr<imageprocessing::VersionedImage> image);
-    bool isUsable() const { return usable; }
-    bool initialize(std::shared_ptr<imageprocessing::VersionedImage> image, Sample& target);
-    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples, const Sample& target);
-    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples);
-    void reset();
+    bool isValid(const Sample& target, const std::vector<std::shared_ptr<Sample>>& samples, std::shared_ptr<imageprocessing::VersionedImage> image) override;
+    bool isUsable() const override { return usable; }
+    bool initialize(std::shared_ptr<imageprocessing::VersionedImage> image, Sample& target) override;
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples, const Sample& target) override;
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples) override;
+    void reset() override;
+    // not in the reference: evaluate(image, samples) for a particle set that lives on the device (fd_particles, bound to native()) -- the
+    // same branches, re-initialisation draws and weights; the samples never visit the host unless a re-initialisation rewrites them.
+    // Fills info with the extracted state (FilteringStateExtractor(WeightedMeanStateExtractor)); throws when a weight is not finite.
+    void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles, fd_particles_info& info);
+    Adaptation getAdaptation() const { return adaptation; }
     std::pair<double, cv::Rect> getHeatPeak() const;
     // the examples (cellRowCount x cellColumnCount * channels CV_32F each) and, optionally, their bounds in the order they were chosen
     std::vector<cv::Mat> createGoodNegativeExamples(cv::Rect targetBounds, std::vector<cv::Rect>* bounds = nullptr) const;
@@ -188,6 +222,230 @@ private:
     mutable std::normal_distribution<> normalDistribution;
     cv::Mat initialFeatures;
     int fusedEvaluations = 0;
+};
+
+// Sampler.hpp:24-48
+class Sampler {
+public:
+    virtual ~Sampler() {}
+    virtual void init(const cv::Mat& image) = 0;
+    virtual void sample(const std::vector<std::shared_ptr<Sample>>& samples, std::vector<std::shared_ptr<Sample>>& newSamples, const cv::Mat& image,
+                        const std::shared_ptr<Sample> target) = 0;
+};
+
+// ResamplingAlgorithm.hpp:22-38
+class ResamplingAlgorithm {
+public:
+    virtual ~ResamplingAlgorithm() {}
+    virtual void resample(const std::vector<std::shared_ptr<Sample>>& samples, size_t count, std::vector<std::shared_ptr<Sample>>& newSamples) = 0;
+};
+
+// LowVarianceSampling.hpp / .cpp:17-46.  The reference seeds a boost::mt19937 with time(0); here a std::mt19937 with `seed` and a
+// std::uniform_real_distribution<> on [0, 1): one draw per resample call that has samples and a positive step.  Where rounding leaves
+// the last pointers above the total weight the walk stops at the last sample (the reference increments its iterator past the end).
+class LowVarianceSampling : public ResamplingAlgorithm {
+public:
+    explicit LowVarianceSampling(unsigned int seed = std::mt19937::default_seed);
+    void resample(const std::vector<std::shared_ptr<Sample>>& samples, size_t count, std::vector<std::shared_ptr<Sample>>& newSamples) override;
+    double computeWeightSum(const std::vector<std::shared_ptr<Sample>>& samples);
+    // the next uniform number, as resample takes it; the last one is kept for replaying a run
+    double draw() { lastDraw = distribution(generator); drew = true; return lastDraw; }
+    bool hasLastDraw() const { return drew; }
+    double getLastDraw() const { return lastDraw; }
+    void forgetLastDraw() { drew = false; }
+private:
+    std::mt19937 generator;
+    std::uniform_real_distribution<> distribution;
+    double lastDraw = 0;
+    bool drew = false;
+};
+
+// TransitionModel.hpp:24-49
+class TransitionModel {
+public:
+    virtual ~TransitionModel() {}
+    virtual void init(const cv::Mat& image) = 0;
+    virtual void predict(std::vector<std::shared_ptr<Sample>>& samples, const cv::Mat& image, const std::shared_ptr<Sample> target) = 0;
+};
+
+// SimpleTransitionModel.hpp / .cpp:19-44.  std::mt19937(seed) + std::normal_distribution<>: three draws per sample, in the order x
+// velocity, y velocity, size factor.
+class SimpleTransitionModel : public TransitionModel {
+public:
+    explicit SimpleTransitionModel(double positionDeviation, double sizeDeviation, unsigned int seed = std::mt19937::default_seed);
+    void init(const cv::Mat& image) override;
+    void predict(std::vector<std::shared_ptr<Sample>>& samples, const cv::Mat& image, const std::shared_ptr<Sample> target) override;
+    double getPositionDeviation() const { return positionDeviation; }
+    void setPositionDeviation(double deviation) { positionDeviation = deviation; }
+    double getSizeDeviation() const { return sizeDeviation; }
+    void setSizeDeviation(double deviation) { sizeDeviation = deviation; }
+    // the three draws of one sample as predict applies them: {positionDeviation * z, positionDeviation * z, pow(2, sizeDeviation * z)}
+    void drawDiffusion(double out[3]);
+    // predict for one sample with its draws (the arithmetic of k_particles_sample)
+    static void apply(Sample& sample, const double diffusion[3]);
+    const std::vector<double>& getLastDiffusion() const { return lastDiffusion; }   // the draws of the last predict, 3 per sample
+private:
+    std::vector<double> lastDiffusion;
+    double positionDeviation, sizeDeviation;
+    std::mt19937 generator;
+    std::normal_distribution<> distribution;
+};
+
+// ResamplingSampler.hpp / .cpp:24-71.  std::mt19937(seed): per random sample one std::uniform_real_distribution<> draw (the size), then
+// std::uniform_int_distribution<int>(0, cols - size) and (0, rows - size).
+class ResamplingSampler : public Sampler {
+public:
+    ResamplingSampler(unsigned int count, double randomRate, std::shared_ptr<ResamplingAlgorithm> resamplingAlgorithm,
+                      std::shared_ptr<TransitionModel> transitionModel, int minSize, int maxSize, unsigned int seed = std::mt19937::default_seed);
+    void init(const cv::Mat& image) override;
+    void sample(const std::vector<std::shared_ptr<Sample>>& samples, std::vector<std::shared_ptr<Sample>>& newSamples, const cv::Mat& image,
+                const std::shared_ptr<Sample> target) override;
+    int getCount() { return count; }
+    void setCount(unsigned int count) { this->count = count; }
+    double getRandomRate() { return randomRate; }
+    void setRandomRate(double randomRate) { this->randomRate = std::max(0.0, std::min(1.0, randomRate)); }
+    std::shared_ptr<ResamplingAlgorithm> getResamplingAlgorithm() const { return resamplingAlgorithm; }
+    std::shared_ptr<TransitionModel> getTransitionModel() const { return transitionModel; }
+    // the values of one random sample {x, y, size} for an image of cols x rows (sampleValues, .cpp:61-71)
+    void drawValues(int cols, int rows, int32_t out[3]);
+    // not in the reference: what the last frame drew, in the order it was drawn (u, then three numbers per copy, then the values of the
+    // random samples), for replaying a run
+    struct Draws {
+        bool hasU = false;
+        double u = 0;
+        std::vector<double> diffusion;   // 3 per copy
+        std::vector<int32_t> fresh;      // 3 per random sample
+    };
+    const Draws& getLastDraws() const { return lastDraws; }
+    // the draws of one frame without the Sample objects, in sample()'s order: for an old generation of oldCount samples whose weights
+    // add up (in index order) to oldWeightSum.  Needs LowVarianceSampling and SimpleTransitionModel.
+    const Draws& drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows);
+private:
+    Draws lastDraws;
+    void sampleValues(Sample& sample, const cv::Mat& image);
+    unsigned int count;
+    double randomRate;
+    std::shared_ptr<ResamplingAlgorithm> resamplingAlgorithm;
+    std::shared_ptr<TransitionModel> transitionModel;
+    int minSize, maxSize;
+    std::mt19937 generator;
+    std::uniform_real_distribution<> realDistribution;
+};
+
+// GridSampler.hpp / .cpp:23-53
+class GridSampler : public Sampler {
+public:
+    GridSampler(int minSize, int maxSize, float sizeScale, float stepSize);
+    void init(const cv::Mat& image) override;
+    void sample(const std::vector<std::shared_ptr<Sample>>& samples, std::vector<std::shared_ptr<Sample>>& newSamples, const cv::Mat& image,
+                const std::shared_ptr<Sample> target) override;
+private:
+    int minSize, maxSize;
+    float sizeScale, stepSize;
+};
+
+// StateExtractor.hpp:22-38
+class StateExtractor {
+public:
+    virtual ~StateExtractor() {}
+    virtual std::shared_ptr<Sample> extract(const std::vector<std::shared_ptr<Sample>>& samples) = 0;
+};
+
+// FilteringStateExtractor.hpp / .cpp:16-25: the samples with the target flag go to the wrapped extractor
+class FilteringStateExtractor : public StateExtractor {
+public:
+    explicit FilteringStateExtractor(std::shared_ptr<StateExtractor> extractor);
+    std::shared_ptr<Sample> extract(const std::vector<std::shared_ptr<Sample>>& samples) override;
+    std::shared_ptr<StateExtractor> getExtractor() const { return extractor; }
+private:
+    std::shared_ptr<StateExtractor> extractor;
+};
+
+// WeightedMeanStateExtractor.hpp / .cpp:21-62.  The reference picks the largest cluster with max_element over an unordered_map, so
+// equally large clusters are decided by the hash order; here the one whose first member has the lowest sample index wins.
+class WeightedMeanStateExtractor : public StateExtractor {
+public:
+    WeightedMeanStateExtractor();
+    std::shared_ptr<Sample> extract(const std::vector<std::shared_ptr<Sample>>& samples) override;
+};
+
+// MaxWeightStateExtractor.hpp / .cpp:16-30
+class MaxWeightStateExtractor : public StateExtractor {
+public:
+    MaxWeightStateExtractor();
+    std::shared_ptr<Sample> extract(const std::vector<std::shared_ptr<Sample>>& samples) override;
+};
+
+// The two trackers share the frame loop: sample -> evaluate -> extract (CondensationTracker.cpp:35-47), and for the adaptive one
+// validators and adapt (AdaptiveCondensationTracker.cpp:67-95).  Not in the reference: the device route.  With
+// FD_COND_DEVICE=1 a frame whose sampler is a ResamplingSampler on LowVarianceSampling + SimpleTransitionModel, whose model is an
+// ExtendedHogBasedMeasurementModel with adaptation NONE or POSITION and whose extractor is
+// FilteringStateExtractor(WeightedMeanStateExtractor) -- these classes exactly: a subclass of any of them may override what the route
+// restates and therefore keeps the generic route -- runs on a particle set that stays on the device (fd_particles): the host draws the
+// same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample objects on demand;
+// they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
+class ParticleFrameLoop {
+public:
+    enum class Route { NONE, GENERIC, DEVICE };
+    Route getLastRoute() const { return lastRoute; }
+protected:
+    ParticleFrameLoop(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
+    ~ParticleFrameLoop();
+    ParticleFrameLoop(const ParticleFrameLoop&) = delete;
+    ParticleFrameLoop& operator=(const ParticleFrameLoop&) = delete;
+    void step(const cv::Mat& imageData);   // one frame up to the extracted state
+    const std::vector<std::shared_ptr<Sample>>& currentSamples() const;
+    void replaceSamples(const std::vector<std::shared_ptr<Sample>>& newSamples);
+    mutable std::vector<std::shared_ptr<Sample>> samples;
+    std::vector<std::shared_ptr<Sample>> oldSamples;
+    std::shared_ptr<Sample> state;
+    std::shared_ptr<imageprocessing::VersionedImage> image;
+    std::shared_ptr<Sampler> sampler;
+    std::shared_ptr<MeasurementModel> measurementModel;
+    std::shared_ptr<StateExtractor> extractor;
+private:
+    bool deviceRoutePossible() const;
+    void deviceStep();
+    void releaseParticles();
+    fd_particles* particles = nullptr;
+    fd_ehog_tracker* particlesOn = nullptr;   // the tracker handle `particles` is bound to
+    bool resident = false;                    // the current generation lives in `particles`
+    mutable bool materialized = true;         // `samples` holds it as well
+    int residentCount = 0;
+    double residentWeightSum = 0;
+    Route lastRoute = Route::NONE;
+};
+
+// CondensationTracker.hpp / .cpp:25-47
+class CondensationTracker : public ParticleFrameLoop {
+public:
+    CondensationTracker(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
+    boost::optional<cv::Rect> process(const cv::Mat& image);
+    std::shared_ptr<Sample> getState() { return state; }
+    const std::vector<std::shared_ptr<Sample>>& getSamples() const { return currentSamples(); }
+    std::shared_ptr<Sampler> getSampler() { return sampler; }
+    void setSampler(std::shared_ptr<Sampler> sampler) { this->sampler = sampler; }
+};
+
+// AdaptiveCondensationTracker.hpp / .cpp:29-119
+class AdaptiveCondensationTracker : public ParticleFrameLoop {
+public:
+    AdaptiveCondensationTracker(std::shared_ptr<Sampler> sampler, std::shared_ptr<AdaptiveMeasurementModel> measurementModel,
+                                std::shared_ptr<StateExtractor> extractor, int initialCount);
+    boost::optional<cv::Rect> initialize(const cv::Mat& image, const cv::Rect& position);
+    boost::optional<cv::Rect> process(const cv::Mat& image);
+    void reset();
+    bool hasAdapted();
+    std::shared_ptr<Sample> getState();
+    const std::vector<std::shared_ptr<Sample>>& getSamples() const;
+    std::shared_ptr<Sampler> getSampler();
+    void setSampler(std::shared_ptr<Sampler> sampler);
+    void addValidator(std::shared_ptr<StateValidator> validator);
+private:
+    int initialCount;
+    bool adapted;
+    std::shared_ptr<AdaptiveMeasurementModel> adaptiveModel;
+    std::vector<std::shared_ptr<StateValidator>> validators;
 };
 
 }  // namespace condensation

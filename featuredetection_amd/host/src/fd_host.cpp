@@ -2303,7 +2303,10 @@ Mat SdmLandmarkModelFitting::optimize(Mat modelShape, Mat image) {
 }  // namespace superviseddescent
 
 // =================================================================================================
+#include <functional>
 #include <limits>
+#include <typeinfo>
+#include <unordered_map>
 #include "condensation/condensation_all.hpp"
 namespace condensation {
 
@@ -2858,5 +2861,503 @@ vector<Mat> ExtendedHogBasedMeasurementModel::createGoodNegativeExamples(cv::Rec
     if (chosen) *chosen = boxes;
     return examples;
 }
+
+// ---- the rest of the Condensation tracker: samplers, transition model, state extractors, trackers -----------------------
+
+LowVarianceSampling::LowVarianceSampling(unsigned int seed) : generator(seed), distribution(0.0, 1.0) {}
+
+void LowVarianceSampling::resample(const vector<shared_ptr<Sample>>& samples, size_t count, vector<shared_ptr<Sample>>& newSamples) {   // .cpp:20-39
+    newSamples.reserve(count);
+    if (samples.size() > 0) {
+        double weightSum = computeWeightSum(samples);
+        double step = weightSum / count;
+        if (step > 0) {
+            double start = step * draw();
+            size_t sample = 0;
+            double runningSum = samples[0]->getWeight();
+            for (unsigned int i = 0; i < count; ++i) {
+                double weightPointer = start + i * step;
+                while (weightPointer > runningSum && sample + 1 < samples.size()) {   // the second condition is not the reference's
+                    ++sample;
+                    runningSum += samples[sample]->getWeight();
+                }
+                newSamples.emplace_back(new Sample(samples[sample]));
+            }
+        }
+    }
+}
+
+double LowVarianceSampling::computeWeightSum(const vector<shared_ptr<Sample>>& samples) {   // .cpp:41-46
+    double weightSum = 0;
+    for (const shared_ptr<Sample>& sample : samples) weightSum += sample->getWeight();
+    return weightSum;
+}
+
+SimpleTransitionModel::SimpleTransitionModel(double positionDeviation, double sizeDeviation, unsigned int seed)
+    : positionDeviation(positionDeviation), sizeDeviation(sizeDeviation), generator(seed), distribution() {}
+
+void SimpleTransitionModel::init(const Mat&) {}
+
+void SimpleTransitionModel::drawDiffusion(double out[3]) {
+    out[0] = positionDeviation * distribution(generator);
+    out[1] = positionDeviation * distribution(generator);
+    out[2] = pow(2, sizeDeviation * distribution(generator));
+}
+
+void SimpleTransitionModel::apply(Sample& sample, const double diffusion[3]) {   // .cpp:27-42
+    double vx = sample.getVx();
+    double vy = sample.getVy();
+    double vs = sample.getVSize();
+    vx += diffusion[0];
+    vy += diffusion[1];
+    vs *= diffusion[2];
+    sample.setVx(static_cast<int>(std::round(vx)));
+    sample.setVy(static_cast<int>(std::round(vy)));
+    sample.setVSize(vs);
+    sample.setX(sample.getX() + sample.getVx());
+    sample.setY(sample.getY() + sample.getVy());
+    sample.setSize(static_cast<int>(std::round(sample.getSize() * sample.getVSize())));   // int * float: a float product
+}
+
+void SimpleTransitionModel::predict(vector<shared_ptr<Sample>>& samples, const Mat&, const shared_ptr<Sample>) {
+    lastDiffusion.clear();
+    for (shared_ptr<Sample>& sample : samples) {
+        double diffusion[3];
+        drawDiffusion(diffusion);
+        lastDiffusion.insert(lastDiffusion.end(), diffusion, diffusion + 3);
+        apply(*sample, diffusion);
+    }
+}
+
+ResamplingSampler::ResamplingSampler(unsigned int count, double randomRate, shared_ptr<ResamplingAlgorithm> resamplingAlgorithm,
+                                     shared_ptr<TransitionModel> transitionModel, int minSize, int maxSize, unsigned int seed)
+    : count(count), randomRate(randomRate), resamplingAlgorithm(resamplingAlgorithm), transitionModel(transitionModel), minSize(minSize), maxSize(maxSize),
+      generator(seed), realDistribution(0.0, 1.0) {
+    if (minSize < 1) throw std::invalid_argument("ResamplingSampler: the minimum size must be greater than zero");
+    if (maxSize < minSize) throw std::invalid_argument("ResamplingSampler: the maximum size must not be smaller than the minimum size");
+    setRandomRate(randomRate);
+}
+
+void ResamplingSampler::init(const Mat& image) {   // .cpp:42-48
+    if (minSize > image.cols || minSize > image.rows)
+        throw std::invalid_argument("ResamplingSampler: the minimum size must not be greater than the width and height of the image");
+    if (maxSize > image.cols || maxSize > image.rows) maxSize = std::min(image.cols, image.rows);
+    transitionModel->init(image);
+}
+
+void ResamplingSampler::drawValues(int cols, int rows, int32_t out[3]) {   // .cpp:61-71
+    auto upTo = [this](int n) { return n > 0 ? std::uniform_int_distribution<int>(0, n)(generator) : 0; };
+    double sizeFactor = realDistribution(generator) * (static_cast<double>(maxSize) / static_cast<double>(minSize) - 1.0) + 1.0;
+    int size = cv::cvRound(sizeFactor * minSize);
+    int halfSize = size / 2;
+    out[2] = size;
+    out[0] = upTo(cols - size) + halfSize;
+    out[1] = upTo(rows - size) + halfSize;
+}
+
+void ResamplingSampler::sampleValues(Sample& sample, const Mat& image) {
+    int32_t v[3];
+    drawValues(image.cols, image.rows, v);
+    lastDraws.fresh.insert(lastDraws.fresh.end(), v, v + 3);
+    sample.setSize(v[2]);
+    sample.setX(v[0]);
+    sample.setY(v[1]);
+    sample.setVx(0);
+    sample.setVy(0);
+    sample.setVSize(1);
+}
+
+void ResamplingSampler::sample(const vector<shared_ptr<Sample>>& samples, vector<shared_ptr<Sample>>& newSamples, const Mat& image,
+                               const shared_ptr<Sample> target) {   // .cpp:50-59
+    lastDraws = Draws();
+    auto lowVariance = std::dynamic_pointer_cast<LowVarianceSampling>(resamplingAlgorithm);
+    auto simple = std::dynamic_pointer_cast<SimpleTransitionModel>(transitionModel);
+    if (lowVariance) lowVariance->forgetLastDraw();
+    resamplingAlgorithm->resample(samples, (int)((1 - randomRate) * count), newSamples);
+    transitionModel->predict(newSamples, image, target);
+    if (lowVariance && lowVariance->hasLastDraw()) { lastDraws.hasU = true; lastDraws.u = lowVariance->getLastDraw(); }
+    if (simple) lastDraws.diffusion = simple->getLastDiffusion();
+    while (newSamples.size() < count) {
+        shared_ptr<Sample> newSample = make_shared<Sample>();
+        sampleValues(*newSample, image);
+        newSamples.push_back(newSample);
+    }
+}
+
+const ResamplingSampler::Draws& ResamplingSampler::drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows) {
+    lastDraws = Draws();
+    auto lowVariance = std::dynamic_pointer_cast<LowVarianceSampling>(resamplingAlgorithm);
+    auto simple = std::dynamic_pointer_cast<SimpleTransitionModel>(transitionModel);
+    if (!lowVariance || !simple) throw std::logic_error("ResamplingSampler::drawFrame needs LowVarianceSampling and SimpleTransitionModel");
+    const size_t resampled = (size_t)(int)((1 - randomRate) * count);
+    size_t copies = 0;
+    if (oldCount > 0 && oldWeightSum / resampled > 0) {   // LowVarianceSampling.cpp:22-26: the draw is taken even for zero copies
+        lastDraws.hasU = true;
+        lastDraws.u = lowVariance->draw();
+        copies = resampled;
+    }
+    lastDraws.diffusion.resize(3 * copies);
+    for (size_t i = 0; i < copies; ++i) simple->drawDiffusion(&lastDraws.diffusion[3 * i]);
+    for (size_t i = copies; i < count; ++i) {
+        int32_t v[3];
+        drawValues(cols, rows, v);
+        lastDraws.fresh.insert(lastDraws.fresh.end(), v, v + 3);
+    }
+    return lastDraws;
+}
+
+GridSampler::GridSampler(int minSize, int maxSize, float sizeScale, float stepSize) : minSize(minSize), maxSize(maxSize), sizeScale(sizeScale), stepSize(stepSize) {
+    if (minSize < 1) throw std::invalid_argument("GridSampler: the minimum size must be greater than zero");
+    if (maxSize < minSize) throw std::invalid_argument("GridSampler: the maximum size must not be smaller than the minimum size");
+    if (sizeScale <= 1) throw std::invalid_argument("GridSampler: The scale factor of the size must be greater than one");
+    if (stepSize <= 0) throw std::invalid_argument("GridSampler: The step size must be greater than zero");
+}
+
+void GridSampler::init(const Mat&) {}
+
+void GridSampler::sample(const vector<shared_ptr<Sample>>&, vector<shared_ptr<Sample>>& newSamples, const Mat& image, const shared_ptr<Sample>) {   // .cpp:37-53
+    newSamples.clear();
+    for (int size = minSize; size <= maxSize; size *= sizeScale) {
+        int halfSize = size / 2;
+        int minX = halfSize;
+        int minY = halfSize;
+        int maxX = image.cols - size + halfSize;
+        int maxY = image.rows - size + halfSize;
+        int step = (int)(stepSize * size + 0.5f);
+        if (step < 1) throw std::invalid_argument("GridSampler: the step size rounds to zero pixels");   // the reference would not return
+        for (int x = minX; x < maxX; x += step) {
+            for (int y = minY; y < maxY; y += step) newSamples.push_back(make_shared<Sample>(x, y, size));
+        }
+    }
+}
+
+FilteringStateExtractor::FilteringStateExtractor(shared_ptr<StateExtractor> extractor) : extractor(extractor) {}
+
+shared_ptr<Sample> FilteringStateExtractor::extract(const vector<shared_ptr<Sample>>& samples) {
+    vector<shared_ptr<Sample>> objects;
+    for (const shared_ptr<Sample>& sample : samples) {
+        if (sample->isTarget()) objects.push_back(sample);
+    }
+    return extractor->extract(objects);
+}
+
+WeightedMeanStateExtractor::WeightedMeanStateExtractor() {}
+
+shared_ptr<Sample> WeightedMeanStateExtractor::extract(const vector<shared_ptr<Sample>>& samples) {   // .cpp:23-62
+    std::unordered_map<int, std::pair<size_t, size_t>> clusters;   // id -> (members, index of the first member)
+    for (size_t i = 0; i < samples.size(); ++i) {
+        auto it = clusters.emplace(samples[i]->getClusterId(), std::make_pair((size_t)0, i)).first;
+        ++it->second.first;
+    }
+    if (clusters.empty()) return shared_ptr<Sample>();
+    auto best = clusters.begin();
+    for (auto it = clusters.begin(); it != clusters.end(); ++it) {
+        if (it->second.first > best->second.first || (it->second.first == best->second.first && it->second.second < best->second.second)) best = it;
+    }
+    const int clusterId = best->first;
+    double weightedSumX = 0;
+    double weightedSumY = 0;
+    double weightedSumSize = 0;
+    double weightedSumVx = 0;
+    double weightedSumVy = 0;
+    double weightedSumVSize = 0;
+    double weightSum = 0;
+    for (const shared_ptr<Sample>& sample : samples) {
+        if (sample->getClusterId() != clusterId) continue;
+        weightedSumX += sample->getWeight() * sample->getX();
+        weightedSumY += sample->getWeight() * sample->getY();
+        weightedSumSize += sample->getWeight() * sample->getSize();
+        weightedSumVx += sample->getWeight() * sample->getVx();
+        weightedSumVy += sample->getWeight() * sample->getVy();
+        weightedSumVSize += sample->getWeight() * sample->getVSize();
+        weightSum += sample->getWeight();
+    }
+    if (weightSum == 0) return shared_ptr<Sample>();
+    double weightedMeanX = weightedSumX / weightSum;
+    double weightedMeanY = weightedSumY / weightSum;
+    double weightedMeanSize = weightedSumSize / weightSum;
+    double weightedMeanVx = weightedSumVx / weightSum;
+    double weightedMeanVy = weightedSumVy / weightSum;
+    double weightedMeanVSize = weightedSumVSize / weightSum;
+    return make_shared<Sample>((int)(weightedMeanX + 0.5), (int)(weightedMeanY + 0.5), (int)(weightedMeanSize + 0.5), (int)(weightedMeanVx + 0.5),
+                               (int)(weightedMeanVy + 0.5), (int)(weightedMeanVSize + 0.5));
+}
+
+MaxWeightStateExtractor::MaxWeightStateExtractor() {}
+
+shared_ptr<Sample> MaxWeightStateExtractor::extract(const vector<shared_ptr<Sample>>& samples) {   // .cpp:18-30
+    shared_ptr<Sample> best;
+    double maxWeight = 0;
+    for (const shared_ptr<Sample>& sample : samples) {
+        if (sample->getWeight() > maxWeight) {
+            maxWeight = sample->getWeight();
+            best = sample;
+        }
+    }
+    if (maxWeight > 0 && best->isTarget()) return best;
+    return shared_ptr<Sample>();
+}
+
+// evaluate(image, samples) (:107-168) on a resident particle set.  The heat peak is read before the samples are scored only where
+// the branch needs it first (target lost); a re-initialisation downloads the generation, rewrites it with the draws of the generic
+// route and scores it again.
+void ExtendedHogBasedMeasurementModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles, fd_particles_info& info) {
+    update(image);
+    const double a = classifier->getLogisticA(), b = classifier->getLogisticB(), threshold = classifier->getSvm()->getThreshold();
+    auto score = [&](int mode) {
+        check(fd_particles_evaluate(context(), particles, useSlidingWindow ? 0 : 1, Sample::getAspectRatio()));
+        check(fd_particles_weigh(context(), particles, a, b, threshold, mode, rejectionThreshold));
+        ++fusedEvaluations;
+    };
+    const int mode = targetLost ? FD_PARTICLES_TARGET_LOST : (useSlidingWindow ? FD_PARTICLES_SLIDING_WINDOW : FD_PARTICLES_ALL_TARGETS);
+    if (!useSlidingWindow) {
+        score(mode);
+        check(fd_particles_state(context(), particles, &info));
+        return;
+    }
+    // the generation on the host, rewritten by f, and back
+    auto rewrite = [&](const std::function<void(int, fd_particles_arrays&)>& f) {
+        int n = 0;
+        check(fd_particles_get(context(), particles, FD_PARTICLES_MAX, &n, nullptr));
+        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
+        vector<float> vsize(n);
+        vector<double> weight(n), sc(n);
+        vector<uint8_t> target(n);
+        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), sc.data(), target.data(), cluster.data()};
+        check(fd_particles_get(context(), particles, n, &n, &arrays));
+        f(n, arrays);
+        check(fd_particles_set(context(), particles, n, &arrays));
+    };
+    std::pair<double, cv::Rect> peak;
+    auto reinitialize = [&]() {
+        int clusterId = Sample::getNextClusterId();
+        rewrite([&](int n, fd_particles_arrays& s) {
+            for (int i = 0; i < n; ++i) {   // the draws and the double -> int conversions of the setters, as evaluate(image, samples) has them
+                s.x[i] = peak.second.x + peak.second.width / 2 + 0.2 * peak.second.width * normalDistribution(generator);
+                s.y[i] = peak.second.y + peak.second.height / 2 + 0.2 * peak.second.width * normalDistribution(generator);
+                s.size[i] = peak.second.width * (1 + 0.2 * normalDistribution(generator));
+                s.vx[i] = 0.1 * peak.second.width * normalDistribution(generator);
+                s.vy[i] = 0.1 * peak.second.width * normalDistribution(generator);
+                s.vsize[i] = 1 + 0.1 * normalDistribution(generator);
+                s.cluster_id[i] = clusterId;
+            }
+        });
+        score(mode);
+    };
+    if (targetLost) {
+        peak = getHeatPeak();
+        double peakScore = peak.first;
+        if (classifier->getSvm()->classify(peakScore) && (!conservativeReInit || peakScore > adaptationThreshold)) {
+            reinitialize();
+        } else {
+            rewrite([&](int n, fd_particles_arrays& s) {
+                for (int i = 0; i < n; ++i) { s.weight[i] = 0; s.score[i] = 0; s.target[i] = 0; }
+            });
+        }
+        check(fd_particles_state(context(), particles, &info));
+        return;
+    }
+    score(mode);
+    check(fd_particles_state(context(), particles, &info));
+    peak = getHeatPeak();
+    double bestScore = info.best_score;
+    double peakScore = peak.first;
+    double initialFeaturesScore = classifier->getSvm()->computeHyperplaneDistance(initialFeatures);
+    double scoreThreshold = 0.5 * (bestScore + initialFeaturesScore);
+    if (conservativeReInit) scoreThreshold = std::max(scoreThreshold, adaptationThreshold);
+    if (bestScore < initialFeaturesScore && classifier->getSvm()->classify(peakScore) && peakScore > scoreThreshold) {
+        reinitialize();
+        check(fd_particles_state(context(), particles, &info));
+    }
+}
+
+ParticleFrameLoop::ParticleFrameLoop(shared_ptr<Sampler> sampler, shared_ptr<MeasurementModel> measurementModel, shared_ptr<StateExtractor> extractor)
+    : samples(), oldSamples(), state(), image(make_shared<imageprocessing::VersionedImage>()), sampler(sampler), measurementModel(measurementModel),
+      extractor(extractor) {}
+
+ParticleFrameLoop::~ParticleFrameLoop() { releaseParticles(); }
+
+void ParticleFrameLoop::releaseParticles() {
+    if (particles) fd_particles_destroy(particles);
+    particles = nullptr;
+    particlesOn = nullptr;
+}
+
+// exactly that class: a subclass may override what the device route restates, and keeps the generic route
+template <class T, class U>
+static bool is_exactly(const shared_ptr<U>& p) { return p && typeid(*p) == typeid(T); }
+
+bool ParticleFrameLoop::deviceRoutePossible() const {
+    if (!fd_particles_route_enabled()) return false;
+    if (!is_exactly<ResamplingSampler>(sampler)) return false;
+    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
+    if (!is_exactly<LowVarianceSampling>(resampling->getResamplingAlgorithm()) || !is_exactly<SimpleTransitionModel>(resampling->getTransitionModel())) return false;
+    if (!is_exactly<ExtendedHogBasedMeasurementModel>(measurementModel)) return false;
+    auto model = std::static_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
+    if (!model->native() || !model->isUsable()) return false;
+    if (model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::NONE && model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::POSITION)
+        return false;
+    if (!is_exactly<FilteringStateExtractor>(extractor)) return false;
+    if (!is_exactly<WeightedMeanStateExtractor>(std::static_pointer_cast<FilteringStateExtractor>(extractor)->getExtractor())) return false;
+    const size_t old = resident ? (size_t)residentCount : samples.size();
+    return old <= FD_PARTICLES_MAX && resampling->getCount() >= 0 && resampling->getCount() <= FD_PARTICLES_MAX;
+}
+
+const vector<shared_ptr<Sample>>& ParticleFrameLoop::currentSamples() const {
+    if (resident && !materialized) {   // the Sample objects of the resident generation: no ancestors on this route
+        int n = 0;
+        check(fd_particles_get(context(), particles, FD_PARTICLES_MAX, &n, nullptr));
+        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
+        vector<float> vsize(n);
+        vector<double> weight(n), score(n);
+        vector<uint8_t> target(n);
+        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
+        check(fd_particles_get(context(), particles, n, &n, &arrays));
+        samples.clear();
+        const int nextId = Sample::nextClusterId;
+        for (int i = 0; i < n; ++i) {
+            auto sample = make_shared<Sample>(x[i], y[i], size[i], vx[i], vy[i], vsize[i]);
+            sample->setWeight(weight[i]);
+            sample->setScore(score[i]);
+            sample->setTarget(target[i] != 0);
+            sample->setClusterId(cluster[i]);
+            samples.push_back(sample);
+        }
+        Sample::nextClusterId = nextId;   // building the objects draws no cluster ids
+        materialized = true;
+    }
+    return samples;
+}
+
+void ParticleFrameLoop::replaceSamples(const vector<shared_ptr<Sample>>& newSamples) {
+    samples = newSamples;
+    resident = false;
+    materialized = true;
+}
+
+void ParticleFrameLoop::deviceStep() {
+    auto model = std::dynamic_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
+    auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
+    if (particles && particlesOn != model->native()) releaseParticles();   // the model was initialised again: another tracker handle
+    if (!particles) {
+        check(fd_particles_create(context(), model->native(), FD_PARTICLES_MAX, &particles));
+        particlesOn = model->native();
+        if (resident) throw std::logic_error("ParticleFrameLoop: the resident generation was lost with its tracker");
+    }
+    if (!resident) {   // the generation of the generic route (or of initialize) moves to the device
+        const int n = (int)samples.size();
+        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
+        vector<float> vsize(n);
+        vector<double> weight(n), score(n);
+        vector<uint8_t> target(n);
+        residentWeightSum = 0;
+        for (int i = 0; i < n; ++i) {
+            const Sample& s = *samples[i];
+            x[i] = s.getX(); y[i] = s.getY(); size[i] = s.getSize(); vx[i] = s.getVx(); vy[i] = s.getVy(); vsize[i] = s.getVSize();
+            weight[i] = s.getWeight(); score[i] = s.getScore(); target[i] = s.isTarget(); cluster[i] = s.getClusterId();
+            residentWeightSum += weight[i];
+        }
+        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
+        check(fd_particles_set(context(), particles, n, &arrays));
+        residentCount = n;
+        resident = true;
+    }
+    const Mat& data = image->getData();
+    const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows);
+    const int copies = (int)(draws.diffusion.size() / 3), fresh = (int)(draws.fresh.size() / 3);
+    const int firstFreshId = Sample::nextClusterId;
+    Sample::nextClusterId += fresh;   // the ids the random samples of the generic route would have drawn, in order
+    check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
+    fd_particles_info info;
+    model->evaluateResident(image, particles, info);
+    residentCount = info.count;
+    residentWeightSum = info.weight_sum;
+    materialized = false;
+    samples.clear();
+    oldSamples.clear();
+    state = info.found ? make_shared<Sample>(info.x, info.y, info.size, info.vx, info.vy, info.vsize) : shared_ptr<Sample>();
+}
+
+void ParticleFrameLoop::step(const Mat& imageData) {
+    image->setData(imageData);
+    if (deviceRoutePossible()) {
+        lastRoute = Route::DEVICE;
+        deviceStep();
+        return;
+    }
+    lastRoute = Route::GENERIC;
+    currentSamples();   // a generation that lived on the device comes back as Sample objects
+    resident = false;
+    samples.swap(oldSamples);
+    samples.clear();
+    sampler->sample(oldSamples, samples, image->getData(), state);
+    measurementModel->evaluate(image, samples);
+    state = extractor->extract(samples);
+}
+
+CondensationTracker::CondensationTracker(shared_ptr<Sampler> sampler, shared_ptr<MeasurementModel> measurementModel, shared_ptr<StateExtractor> extractor)
+    : ParticleFrameLoop(sampler, measurementModel, extractor) {}
+
+boost::optional<cv::Rect> CondensationTracker::process(const Mat& imageData) {   // .cpp:35-47
+    step(imageData);
+    if (state) return boost::optional<cv::Rect>(state->getBounds());
+    return boost::optional<cv::Rect>();
+}
+
+AdaptiveCondensationTracker::AdaptiveCondensationTracker(shared_ptr<Sampler> sampler, shared_ptr<AdaptiveMeasurementModel> measurementModel,
+                                                         shared_ptr<StateExtractor> extractor, int initialCount)
+    : ParticleFrameLoop(sampler, measurementModel, extractor), initialCount(initialCount), adapted(false), adaptiveModel(measurementModel), validators() {
+    shared_ptr<StateValidator> validator = std::dynamic_pointer_cast<StateValidator>(measurementModel);
+    if (validator) addValidator(validator);
+}
+
+void AdaptiveCondensationTracker::reset() { adaptiveModel->reset(); }
+
+boost::optional<cv::Rect> AdaptiveCondensationTracker::initialize(const Mat& imageData, const cv::Rect& positionData) {   // .cpp:50-65
+    image->setData(imageData);
+    replaceSamples(vector<shared_ptr<Sample>>());
+    Sample::setAspectRatio(positionData.width, positionData.height);
+    state = make_shared<Sample>(positionData.x + positionData.width / 2, positionData.y + positionData.height / 2, positionData.width);
+    sampler->init(imageData);
+    adaptiveModel->initialize(image, *state);
+    if (adaptiveModel->isUsable()) {
+        vector<shared_ptr<Sample>> initial;
+        for (int i = 0; i < initialCount; ++i) initial.push_back(state);
+        replaceSamples(initial);
+    }
+    if (adaptiveModel->isUsable()) return boost::optional<cv::Rect>(state->getBounds());
+    return boost::optional<cv::Rect>();
+}
+
+boost::optional<cv::Rect> AdaptiveCondensationTracker::process(const Mat& imageData) {   // .cpp:67-95
+    if (!adaptiveModel->isUsable()) throw std::runtime_error("AdaptiveCondensationTracker: Is not usable (was not initialized or was resetted)");
+    step(imageData);
+    // validate target state; the measurement model looks at the state alone, any other validator gets the samples
+    if (state) {
+        for (shared_ptr<StateValidator>& validator : validators) {
+            const bool isModel = std::dynamic_pointer_cast<StateValidator>(measurementModel) == validator;
+            static const vector<shared_ptr<Sample>> none;
+            const bool onDevice = getLastRoute() == Route::DEVICE && isModel;
+            if (!validator->isValid(*state, onDevice ? none : currentSamples(), image)) {
+                state.reset();
+                break;
+            }
+        }
+    }
+    // update model: ExtendedHogBasedMeasurementModel::adapt does not read the samples
+    static const vector<shared_ptr<Sample>> unread;
+    const vector<shared_ptr<Sample>>& forAdapt = getLastRoute() == Route::DEVICE ? unread : currentSamples();
+    if (state) adapted = adaptiveModel->adapt(image, forAdapt, *state);
+    else adapted = adaptiveModel->adapt(image, forAdapt);
+    if (state) return boost::optional<cv::Rect>(state->getBounds());
+    return boost::optional<cv::Rect>();
+}
+
+bool AdaptiveCondensationTracker::hasAdapted() { return adapted; }
+shared_ptr<Sample> AdaptiveCondensationTracker::getState() { return state; }
+const vector<shared_ptr<Sample>>& AdaptiveCondensationTracker::getSamples() const { return currentSamples(); }
+shared_ptr<Sampler> AdaptiveCondensationTracker::getSampler() { return sampler; }
+void AdaptiveCondensationTracker::setSampler(shared_ptr<Sampler> sampler) { this->sampler = sampler; }
+void AdaptiveCondensationTracker::addValidator(shared_ptr<StateValidator> validator) { validators.push_back(validator); }
 
 }  // namespace condensation

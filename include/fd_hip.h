@@ -450,6 +450,72 @@ int fd_ehog_tracker_get_svm(fd_ctx* ctx, fd_ehog_tracker* t, float* weights, flo
 /* host only, no context: whether the solver keeps Q in LDS for this size, and the default max_iterations; either may be NULL */
 int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations);
 
+/* A particle set of the Condensation tracker resident on the device: two generations of up to `capacity` samples
+ * as structure-of-arrays, bound to one fd_ehog_tracker.  A frame of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) +
+ * ExtendedHogBasedMeasurementModel + FilteringStateExtractor(WeightedMeanStateExtractor) is fd_ehog_tracker_update,
+ * fd_particles_sample, _evaluate, _weigh and _state: one chain of kernels on the context's stream and one read-back of
+ * fd_particles_info.  The host draws every random number; the device adds, multiplies, rounds and compares, so that every integer it
+ * produces is reproducible bit for bit. */
+typedef struct fd_particles fd_particles;
+#define FD_PARTICLES_MAX 8192
+typedef struct {
+    int32_t *x, *y, *size, *vx, *vy;   /* centre, width, velocity */
+    float* vsize;                      /* size factor per frame */
+    double *weight, *score;
+    uint8_t* target;
+    int32_t* cluster_id;               /* any int but INT32_MIN */
+} fd_particles_arrays;
+typedef struct {
+    int32_t found;                     /* a state was extracted: x .. vsize hold it */
+    int32_t x, y, size, vx, vy;
+    float vsize;
+    int32_t cluster_id;                /* the cluster the state was taken from */
+    int32_t count, n_valid, n_target;  /* samples of the generation; with a window at the last _evaluate; with the target flag */
+    int32_t bad_weight;                /* a weight is negative, infinite or NaN */
+    double best_score;                 /* the largest score after _weigh (samples without a window count with 0); -DBL_MAX before */
+    double weight_sum;                 /* all weights added in index order: the sum LowVarianceSampling::computeWeightSum returns */
+} fd_particles_info;
+/* capacity 1 .. FD_PARTICLES_MAX, otherwise FD_ERR_INVALID_ARGUMENT.  The tracker must outlive the set. */
+int fd_particles_create(fd_ctx* ctx, fd_ehog_tracker* t, int capacity, fd_particles** out);
+void fd_particles_destroy(fd_particles* p);
+int fd_particles_capacity(const fd_particles* p);
+/* host only: whether FD_COND_DEVICE asks the trackers of the host layer to keep their particles on the device (read at every call) */
+int fd_particles_route_enabled(void);
+/* fills the current generation with n <= capacity samples from host arrays; score and target may be NULL (0) */
+int fd_particles_set(fd_ctx* ctx, fd_particles* p, int n, const fd_particles_arrays* in);
+/* downloads the current generation (*n samples, FD_ERR_CAPACITY with *n set when cap is smaller); NULL members, or a NULL out, are
+ * skipped */
+int fd_particles_get(fd_ctx* ctx, fd_particles* p, int cap, int* n, const fd_particles_arrays* out);
+/* what the last _sample and _evaluate left besides the samples: the index in the old generation each sample was copied from (-1: a
+ * fresh one), the window {layer, bx, by, valid} and the valid flag of each sample.  Any pointer may be NULL. */
+int fd_particles_get_trace(fd_ctx* ctx, fd_particles* p, int32_t* source, int32_t* windows, uint8_t* valid);
+/* ResamplingSampler::sample (ResamplingSampler.cpp:50-59): the current generation becomes the old one; the new one is n_resampled
+ * copies chosen by LowVarianceSampling::resample (.cpp:20-39) with the uniform draw u in [0, 1), each moved as
+ * SimpleTransitionModel::predict (.cpp:25-44) moves it with diffusion[3 i .. 3 i + 2] = {positionDeviation * z, positionDeviation * z,
+ * pow(2, sizeDeviation * z)}, followed by count - n_resampled samples {x, y, size} from `fresh` with the cluster ids
+ * first_fresh_cluster_id, + 1, ...  Copies have weight 1, score 0, no target flag and their parent's cluster id.  When the old
+ * generation is empty or its weight sum / n_resampled is not positive no copy is made (the new generation holds the fresh samples
+ * only).  count 0: an empty generation.  FD_ERR_INVALID_ARGUMENT for count > capacity or n_resampled outside [0, count];
+ * FD_ERR_RUNTIME when the old generation holds a weight that is negative or not finite (nothing is launched). */
+int fd_particles_sample(fd_ctx* ctx, fd_particles* p, int count, int n_resampled, double u, const double* diffusion, const int32_t* fresh,
+                        int32_t first_fresh_cluster_id);
+/* scores the current generation on the tracker's current frame: each sample {x, y, size, cvRound(aspect_ratio * size)} is resolved to
+ * its window on the device and scored by the kernels of fd_ehog_tracker_evaluate_samples (use_patches 0: the heat value) or of
+ * fd_ehog_tracker_extract_patches (1).  Nothing is copied back. */
+int fd_particles_evaluate(fd_ctx* ctx, fd_particles* p, int use_patches, double aspect_ratio);
+#define FD_PARTICLES_TARGET_LOST 0     /* target: score >= svm_threshold */
+#define FD_PARTICLES_SLIDING_WINDOW 1  /* target: score > rejection_threshold */
+#define FD_PARTICLES_ALL_TARGETS 2
+/* ExtendedHogBasedMeasurementModel.cpp:173-205 on the scores of _evaluate: a sample without a window gets weight 0, score 0 and no
+ * target flag; any other weight *= p(score) with ProbabilisticSvmClassifier's logistic (a, b).  When a product is negative or not
+ * finite no weight is changed and bad_weight is raised. */
+int fd_particles_weigh(fd_ctx* ctx, fd_particles* p, double logistic_a, double logistic_b, double svm_threshold, int mode, double rejection_threshold);
+/* FilteringStateExtractor(WeightedMeanStateExtractor) on the current generation (WeightedMeanStateExtractor.cpp:23-62): the samples
+ * with the target flag, their largest cluster (of equally large ones the cluster whose first member has the lowest index), seven
+ * double sums in index order, (int)(mean + 0.5) for all six values.  Fills *out and waits for it: the one read-back of a frame.
+ * With bad_weight set no state is reported and FD_ERR_RUNTIME is returned (*out is filled). */
+int fd_particles_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out);
+
 /* detection::AggregatedFeaturesDetector (AggregatedFeaturesDetector.cpp:37-128) with imageFilter = GrayscaleFilter,
  * layerFilter = FhogFilter on an extraction::AggregatedFeaturesExtractor (AggregatedFeaturesExtractor.cpp:34-130): a linear
  * SVM convolved over the FHOG cell pyramid (ConvolutionFilter.cpp:27-43), windows with score > threshold, bounds through
