@@ -372,6 +372,8 @@ _BENCH_SIGS = {
     "fd_wvm_last_spec_state": (C.c_int, [C.c_void_p]),
     "fd_wvm_last_stage_b_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fd_debug_wvd_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "fd_debug_wvd_packed_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p]),
 }
 
 
@@ -709,6 +711,23 @@ def wvd_plan(nx, ny, frames, sy, ph, slots):
     if k < 1:
         raise FdError(k, "fd_debug_wvd_plan")
     return k, first
+
+
+def wvd_packed_plan(nx, ny, frames, sy, ph, slots, tasks=None):
+    """Test hook (no GPU): the pre-filter's packed plan -> (K, tiles per frame, tasks per frame, decoded), decoded[i] = (layer, column,
+    first window row, windows) of tasks[i]; tasks=None decodes every task of a frame"""
+    nx, ny = _c(nx, np.int32), _c(ny, np.int32)
+    tiles, ntask = C.c_int32(), C.c_int32()
+    k = lib().fd_debug_wvd_packed_plan(_ptr(nx), _ptr(ny), len(nx), frames, sy, ph, slots, C.byref(tiles), C.byref(ntask), None, 0, None)
+    if k < 1:
+        raise FdError(k, "fd_debug_wvd_packed_plan")
+    tasks = np.arange(ntask.value, dtype=np.int32) if tasks is None else _c(tasks, np.int32)
+    dec = np.zeros((len(tasks), 4), np.int32)
+    if len(tasks):
+        k = lib().fd_debug_wvd_packed_plan(_ptr(nx), _ptr(ny), len(nx), frames, sy, ph, slots, None, None, _ptr(tasks), len(tasks), _ptr(dec))
+        if k < 1:
+            raise FdError(k, "fd_debug_wvd_packed_plan")
+    return k, tiles.value, ntask.value, dec
 
 
 def wvb_rect_sums(model, patches_eq):

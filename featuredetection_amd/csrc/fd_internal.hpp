@@ -314,6 +314,12 @@ static inline int fd_knob_fs_tail() { const char* e = getenv("FD_FS_TAIL"); retu
 static inline bool fd_knob_fs_spec() { const char* e = getenv("FD_FS_SPEC"); return !(e && atoi(e) == 0); }
 // the trackers of the host layer keep their particle set on the device: 1 on, anything else (and unset) off.  Read per call.
 static inline bool fd_knob_cond_device() { const char* e = getenv("FD_COND_DEVICE"); return e && atoi(e) == 1; }
+// k_wvm_prefilter's plan: tasks packed 64 to a wavefront across the layers of a frame, balanced row groups; 0: the per-layer plan.
+// Read per call: the tests compare both plans in one process.
+static inline bool fd_knob_wvd_pack() { const char* e = getenv("FD_WVD_PACK"); return !(e && atoi(e) == 0); }
+// k_pyrdown_tiled of a multi-frame pyramid (frames a multiple of 8): frame f's tiles on XCD f % 8; 0: the (tiles, 1, frames) grid.
+// Read where the launch is queued.
+static inline bool fd_knob_pyr_xcd() { const char* e = getenv("FD_PYR_XCD"); return !(e && atoi(e) == 0); }
 
 // FD_TRACE's stopwatch: lap_ns() is the time since the start (or the previous lap) and starts the next lap; off: no clock is read.
 struct FdStopwatch {

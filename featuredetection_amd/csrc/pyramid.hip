@@ -467,13 +467,22 @@ __device__ __forceinline__ int reflect_cf(int p, int len) {
     return min(max(q, 0), len - 1);
 }
 constexpr int PD_W = 62;   // pyrDown tile: 62 x 16 outputs = 127 x 35 source bytes = 32 dwords per row: two rows per wavefront load
-__global__ __launch_bounds__(256) void k_pyrdown_tiled(uint8_t* __restrict__ arena, DownJobs jobs, size_t imageStride) {
+// xcdFrames > 0 (a multiple of 8; 1-D grid, a multiple of 8): workgroup b runs on XCD b % 8 (observed dispatch order; only speed depends
+// on it) and takes tiles of the frames (b & 7) + 8 i, like k_resize_down before and k_wvm_prefilter behind this kernel: a frame's
+// generations stay in one L2 instead of going round-robin over all eight.  0: grid (tiles, 1, frames), blockIdx.z = frame.
+__global__ __launch_bounds__(256) void k_pyrdown_tiled(uint8_t* __restrict__ arena0, DownJobs jobs, size_t imageStride, int xcdFrames) {
     __shared__ __attribute__((aligned(16))) uint8_t tile[TL_ROWS * TL_PITCH];
-    arena += (size_t)blockIdx.z * imageStride;   // blockIdx.z = frame of a multi-frame pyramid
     const int c = threadIdx.x & 63, rq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // rq scalar: row offsets on the scalar unit
     constexpr int NROWS = 2 * PD_TH + 3, PD_LD = (NROWS + 7) / 8;   // 35 source rows; a wavefront stages rows 2 (rq + 4 k) and the next
     static_assert(2 * (3 + 4 * (PD_LD - 1)) + 1 < TL_ROWS && 128 <= TL_PITCH && 2 * PD_W + 3 <= 128, "pyrDown stage");
-    for (int g = blockIdx.x; g < jobs.tile0[jobs.n]; g += gridDim.x) {   // flat list of the tiles of all jobs
+    const bool byXcd = xcdFrames > 0;
+    const int ntile = jobs.tile0[jobs.n];
+    const int first = byXcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, stride = byXcd ? (int)(gridDim.x >> 3) : (int)gridDim.x;
+    const int items = byXcd ? (xcdFrames >> 3) * ntile : ntile;   // (frame, tile) items of this XCD, frame-major / the tiles of frame blockIdx.z
+    for (int item = first; item < items; item += stride) {   // flat list of the tiles of all jobs
+        const int fi = byXcd ? item / ntile : 0;
+        const int g = item - fi * ntile;
+        uint8_t* __restrict__ arena = arena0 + (size_t)(byXcd ? (int)(blockIdx.x & 7u) + 8 * fi : (int)blockIdx.z) * imageStride;
         int ji = 0;
         while (ji + 1 < jobs.n && g >= jobs.tile0[ji + 1]) ++ji;
         const DownJob jb = jobs.j[ji];
@@ -1208,8 +1217,14 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
         hipLaunchKernelGGL(k_resize_tiled, dim3(R.grid, R.jobs.n, NI), dim3(256), 0, st, arena, arena, p->gray_full_off, W, H, R.jobs, IS);
     for (const FusedLaunch& F : plan.fused)
         hipLaunchKernelGGL(k_resize_down, dim3(F.grid), dim3(256), 0, st, arena, p->gray_full_off, W, H, p->rtab.as<int2>(), F.jobs, F.tileTab, F.tilesPerFrame, NI, IS);
-    for (const DownLaunch& D : plan.down)
-        hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(D.jobs.tile0[D.jobs.n]), 1, NI), dim3(256), 0, st, arena, D.jobs, IS);
+    const bool downByXcd = NI >= 8 && NI % 8 == 0 && fd_knob_pyr_xcd();   // multi-frame: frame f's tiles on XCD f % 8
+    for (const DownLaunch& D : plan.down) {
+        const int ntile = D.jobs.tile0[D.jobs.n];
+        if (downByXcd)   // one tile per workgroup (up to 8 x 8192 workgroups; beyond that they loop)
+            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(8 * (int)std::min<int64_t>((int64_t)(NI / 8) * ntile, 8192)), dim3(256), 0, st, arena, D.jobs, IS, NI);
+        else
+            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(ntile), 1, NI), dim3(256), 0, st, arena, D.jobs, IS, 0);
+    }
     for (const FilterLaunch& F : plan.filter) {
         const dim3 g(F.grid, F.jobs.n);
         if (F.blur.n) hipLaunchKernelGGL(k_box_blur, g, dim3(256), 0, st, arena, p->grad_blur, F.blur);

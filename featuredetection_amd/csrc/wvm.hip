@@ -1331,6 +1331,7 @@ static void wvb_reserve(fd_wvm* m, int64_t total, int64_t minCap = 0) {
 // k_wvm_prefilter's tiles for K windows per lane: 64 (column, row group of K) tasks of a layer each
 static int wvd_plan_sliding(WvdTable& t, int K) {
     t.K = K;
+    t.packed = 0;
     int tiles = 0;
     for (int i = 0; i < t.n; ++i) {
         WvdLayer& l = t.l[i];
@@ -1344,8 +1345,12 @@ static int wvd_plan_sliding(WvdTable& t, int K) {
 // How many windows a lane walks down.  More is cheaper per window (the first window of a lane pays the full histogram, ~0.45 of a
 // window's other work; each later one a slide of 2 sy rows, ~0.04 each) but makes the tiles longer: the launch takes
 // rounds(K) x (first + K x step) with rounds = tiles / wavefront slots rounded up.  FD_WVD_K fixes it.
-static int wvd_choose_k(WvdTable t, int slots, int ph) {
+static int wvd_forced_k() {
     static const int forced = [] { const char* e = getenv("FD_WVD_K"); const int v = e ? atoi(e) : 0; return v < 1 ? 0 : (v > WVD_KMAX ? WVD_KMAX : v); }();
+    return forced;
+}
+static int wvd_choose_k(WvdTable t, int slots, int ph) {
+    const int forced = wvd_forced_k();
     if (2 * t.sy > ph) return 1;   // windows of a column barely overlap: nothing to slide
     if (forced) return forced;
     int best = 1;
@@ -1359,12 +1364,82 @@ static int wvd_choose_k(WvdTable t, int slots, int ph) {
     return best;
 }
 
+// The packed plan of k_wvm_prefilter (wvm_dense.hpp, wvd_packed_task): tiles of 64 consecutive tasks of the frame's flat task list.
+// The list is piecewise constant in the windows a task walks -- per layer ny % G groups of nx tasks with ny / G + 1 windows, then the
+// groups with ny / G -- so the tiles' lengths (a tile runs as many steps as its longest task) follow from the pieces: `area` is the
+// sum over a frame's tiles of first + steps x step in wvd_choose_k's units, `longest` the largest of them.
+static int wvd_plan_packed(WvdTable& t, int K, double* area = nullptr, double* longest = nullptr) {
+    t.K = K;
+    t.packed = 1;
+    const double step = 1.0 + (K > 1 ? 0.04 * t.sy : 0.0);
+    int64_t pos = 0, tiles = 0;
+    int cur = 0, top = 0;   // longest task of the tile being filled / of all tiles
+    double a = 0;
+    auto piece = [&](int rows, int64_t count) {
+        if (count <= 0) return;
+        top = std::max(top, rows);
+        if (pos & 63) {
+            const int64_t fill = std::min<int64_t>(count, 64 - (pos & 63));
+            cur = std::max(cur, rows);
+            pos += fill; count -= fill;
+            if ((pos & 63) == 0) { a += 0.45 + cur * step; ++tiles; cur = 0; }
+        }
+        const int64_t full = count >> 6;
+        a += (double)full * (0.45 + rows * step); tiles += full;
+        pos += count;
+        if (count & 63) cur = rows;
+    };
+    for (int i = 0; i < t.n; ++i) {
+        WvdLayer& l = t.l[i];
+        l.G = (l.ny + K - 1) / K;
+        l.sTileFirst = 0;
+        l.pFirst = (int32_t)pos;
+        const int q = l.ny / l.G, r = l.ny % l.G;
+        piece(q + 1, (int64_t)l.nx * r);
+        piece(q, (int64_t)l.nx * (l.G - r));
+    }
+    if (pos & 63) { a += 0.45 + cur * step; ++tiles; }
+    t.pTasks = (int32_t)pos;
+    t.sTilesPerImage = (int)tiles;
+    if (area) *area = a;
+    if (longest) *longest = 0.45 + top * step;
+    return (int)tiles;
+}
+// K of the packed plan, from wvd_choose_k's constants: the tiles of the whole rounds cost their area (slots x the mean tile per round),
+// a last partial round takes as long as the longest tile.
+static int wvd_choose_k_packed(WvdTable t, int slots, int ph) {
+    const int forced = wvd_forced_k();
+    if (2 * t.sy > ph) return 1;
+    if (forced) return forced;
+    int best = 1;
+    double bestCost = 0;
+    for (int K = 1; K <= WVD_KMAX; ++K) {
+        double area, longest;
+        const int perFrame = wvd_plan_packed(t, K, &area, &longest);
+        const int64_t tiles = (int64_t)perFrame * t.nimg;
+        const double cost = (double)(tiles / slots) * (area / perFrame) + (tiles % slots ? longest : 0.0);
+        if (K == 1 || cost < bestCost * 0.999) { best = K; bestCost = cost; }
+    }
+    return best;
+}
+// the packed plan needs the tasks of a frame to fit 32 bits (the per-layer plan needs that of a layer's)
+static bool wvd_pack_ok(const WvdTable& t) {
+    int64_t tasks = 0;
+    for (int i = 0; i < t.n; ++i) tasks += t.l[i].nwin;
+    return tasks <= (int64_t)INT32_MAX - 64;
+}
+// plans the launch (FD_WVD_PACK=0: the per-layer plan); returns the tiles of all frames
+static int64_t wvd_plan(WvdTable& wt, int slots, int ph) {
+    if (fd_knob_wvd_pack() && wvd_pack_ok(wt)) return (int64_t)wvd_plan_packed(wt, wvd_choose_k_packed(wt, slots, ph)) * wt.nimg;
+    return (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, ph)) * wt.nimg;
+}
+
 template <int PW_, int PH_>
 static void launch_prefilter_sized(fd_ctx* ctx, hipStream_t st, const uint8_t* arena, WvdTable wt, const WvdDev& dv) {
     static int perCu = 0;
     if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_wvm_prefilter<PW_, PH_>, 256, 0) != hipSuccess || perCu < 1)) perCu = 2;
     const int slots = ctx->num_cus * perCu * 4;
-    const int64_t tiles = (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, PH_)) * wt.nimg;
+    const int64_t tiles = wvd_plan(wt, slots, PH_);
     int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
     if (wt.nimg >= 8 && grid >= 64) grid &= ~7;   // a multiple of the 8 XCDs: the kernel then keeps every frame on one XCD
     hipLaunchKernelGGL((k_wvm_prefilter<PW_, PH_>), dim3(grid), dim3(256), 0, st, arena, wt, dv);
@@ -1412,6 +1487,12 @@ static bool launch_prefilter(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const uint8
     if (m->denseL == 0) return false;
     WvdTable t;
     if (!wvd_table_from(wt, t)) return false;
+    // the kernel's lanes address their rows as a 32-bit offset into the frame's arena, advanced by 24-bit multiplies of the row length
+    for (int i = 0; i < t.n; ++i) {
+        const WvdLayer& l = t.l[i];
+        const int64_t rowsBelow = (int64_t)l.by + (int64_t)(l.ny - 1) * t.sy + m->dev.fh;
+        if ((int64_t)l.lw * std::max(t.sy, m->dev.fh) >= (1 << 24) || (int64_t)l.off + (rowsBelow + 1) * l.lw > (int64_t)UINT32_MAX) return false;
+    }
     WvdDev dv;
     wvd_dev_from(m, q, qcount, dv);
 #define FD_WVM_CASE(W, H) \
@@ -2208,6 +2289,33 @@ int fd_debug_wvd_plan(const int32_t* nx, const int32_t* ny, int n_layers, int fr
     if (tile_first) {
         for (int i = 0; i < n_layers; ++i) tile_first[i] = t.l[i].sTileFirst;
         tile_first[n_layers] = tiles;
+    }
+    return K;
+}
+
+// Test hook (include/fd_hip_bench.h; needs no GPU): the packed plan of the pre-filter, and the kernel's decode of given tasks
+int fd_debug_wvd_packed_plan(const int32_t* nx, const int32_t* ny, int n_layers, int frames, int sy, int ph, int slots, int32_t* tiles_per_frame,
+                             int32_t* tasks_per_frame, const int32_t* tasks, int64_t n_tasks, int32_t* decoded) {
+    if (!nx || !ny || n_layers < 1 || n_layers > WVM_MAX_LAYERS || frames < 1 || sy < 1 || ph < 1 || slots < 1 || n_tasks < 0) return FD_ERR_INVALID_ARGUMENT;
+    if (n_tasks > 0 && (!tasks || !decoded)) return FD_ERR_INVALID_ARGUMENT;
+    WvdTable t;
+    std::memset(&t, 0, sizeof(t));
+    t.n = n_layers; t.sx = 1; t.sy = sy; t.nimg = frames;
+    for (int i = 0; i < n_layers; ++i) {
+        if (nx[i] < 1 || ny[i] < 1) return FD_ERR_INVALID_ARGUMENT;
+        t.l[i].nx = nx[i]; t.l[i].ny = ny[i]; t.l[i].nwin = (int32_t)std::min<int64_t>((int64_t)nx[i] * ny[i], INT32_MAX);
+        t.l[i].magic = (uint32_t)std::min<uint64_t>((1ull << 32) / (uint64_t)nx[i], 0xffffffffull);   // as fd_wvm_build_table
+    }
+    if (!wvd_pack_ok(t)) return FD_ERR_INVALID_ARGUMENT;
+    const int K = wvd_choose_k_packed(t, slots, ph);
+    const int tiles = wvd_plan_packed(t, K);
+    if (tiles_per_frame) *tiles_per_frame = tiles;
+    if (tasks_per_frame) *tasks_per_frame = t.pTasks;
+    for (int64_t i = 0; i < n_tasks; ++i) {
+        if (tasks[i] < 0 || tasks[i] >= t.pTasks) return FD_ERR_INVALID_ARGUMENT;
+        const WvdTask d = wvd_packed_task((unsigned int)tasks[i], t.n, [&](int l) { return t.l[l].pFirst; },
+                                          [&](int l) { const WvdLayer& L = t.l[l]; return make_int4(L.nx, (int)L.magic, L.ny / L.G, L.ny % L.G); });
+        decoded[4 * i] = d.li; decoded[4 * i + 1] = (int32_t)d.ix; decoded[4 * i + 2] = d.iy0; decoded[4 * i + 3] = d.rows;
     }
     return K;
 }

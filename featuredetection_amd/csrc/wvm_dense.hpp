@@ -36,13 +36,13 @@ typedef __attribute__((address_space(3))) unsigned short wvd_lds_u16;
 struct WvdLayer {
     int32_t bx, by, nx, lw;
     uint32_t off, magic;
-    int32_t nwin, pad0;
+    int32_t nwin, pFirst;                // packed plan: first task of the layer in the frame's flat task list
     int64_t first;
-    int32_t ny, G, sTileFirst, pad;      // G = ceil(ny / K) row groups; tiles of 64 (column, row group) tasks
+    int32_t ny, G, sTileFirst, pad;      // G = ceil(ny / K) row groups; per-layer plan: tiles of 64 (column, row group) tasks of ONE layer
 };
 struct WvdTable {
-    int32_t n, sx, sy, pad0;
-    int32_t nimg, pad1;                  // multi-frame pyramid: tile -> (frame, tile inside the frame)
+    int32_t n, sx, sy, packed;           // packed: the plan of wvd_plan_packed (k_wvm_prefilter only), else wvd_plan_sliding's
+    int32_t nimg, pTasks;                // multi-frame pyramid: tile -> (frame, tile inside the frame); packed plan: tasks per frame
     int32_t K, sTilesPerImage;           // windows a lane walks down (WVD_KMAX at most), tiles per frame
     int64_t perImage;                    // windows per frame
     uint64_t imageStride;                // bytes between the frames' arenas
@@ -194,8 +194,8 @@ __device__ __forceinline__ unsigned int wvd_lshl_or(unsigned int a, int sh, unsi
     return r;
 }
 
-// One wavefront = 64 (column, row group) tasks of a layer: lane == task, and a lane walks DOWN its column through up to K windows
-// (wt.K, WVD_KMAX at most).  Windows one step apart share all but `sy` rows, so after the first window a lane takes the rows that
+// One wavefront = 64 (column, row group) tasks of a frame (packed plan: consecutive tasks of the frame's flat list, whatever their
+// layers; per-layer plan: of one layer): lane == task, and a lane walks DOWN its column through up to K windows (wt.K, WVD_KMAX at most).  Windows one step apart share all but `sy` rows, so after the first window a lane takes the rows that
 // left its window out of its private histogram and adds the ones that entered: 2 * sy * PW_ LDS atomics per window instead of
 // PW_ * PH_ (the histogram pass was a third of the kernel, bound by the LDS pipe).
 // The contraction runs with the roles swapped against k_wvm_prefilter_multi -- A = the digit matrix, B = the pixels -- so that the
@@ -204,6 +204,34 @@ __device__ __forceinline__ unsigned int wvd_lshl_or(unsigned int a, int sh, unsi
 // N-tiles want) and, after the digits are folded into exact doubles, brings the two halves of a window's filters together:
 // lane == window again without the LDS round trips (pixel staging, 8 KB transpose) of the other formulation.
 constexpr int WVD_KMAX = 16;
+
+// ---- the packed plan: the (column, row group) tasks of ALL layers of a frame as one flat list -- layer-major, group-major,
+// column-minor -- cut into tiles of 64, so that only a frame's last tile has lanes without a task (the per-layer plan ends every layer
+// in a partly empty tile), with the rows of a column dealt evenly over its G = ceil(ny / K) groups: the first ny % G groups walk
+// ny / G + 1 windows, the others ny / G (the per-layer plan ends every column in a short group that the whole wavefront waits for).
+// One decode for the kernel and the host hook (fd_debug_wvd_packed_plan): task -> layer, column, first window row, windows.
+//   firstOf(l): first task of layer l (l >= 1; ascending);  layerOf(l): {nx, magic = 2^32 / nx, ny / G, ny % G} of layer l
+__host__ __device__ __forceinline__ unsigned int wvd_mulhi(unsigned int a, unsigned int b) { return (unsigned int)(((unsigned long long)a * b) >> 32); }
+struct WvdTask { int li; unsigned int ix; int iy0, rows; };
+template <class FirstOf, class LayerOf>
+__host__ __device__ __forceinline__ WvdTask wvd_packed_task(unsigned int task, int n, FirstOf firstOf, LayerOf layerOf) {
+    WvdTask t;
+    t.li = 0;
+    unsigned int base = 0;
+    for (int l = 1; l < n; ++l) {   // layer starts: scalar operands on the device
+        const unsigned int f = (unsigned int)firstOf(l);
+        t.li += task >= f ? 1 : 0;
+        base = task >= f ? f : base;
+    }
+    const int4 L = layerOf(t.li);
+    const unsigned int local = task - base;
+    unsigned int g = wvd_mulhi(local, (unsigned int)L.y);   // floor(local / nx) or one less
+    t.ix = local - g * (unsigned int)L.x;
+    if (t.ix >= (unsigned int)L.x) { t.ix -= (unsigned int)L.x; ++g; }
+    t.iy0 = (int)g * L.z + ((int)g < L.w ? (int)g : L.w);
+    t.rows = L.z + ((int)g < L.w ? 1 : 0);
+    return t;
+}
 
 // one patch row into (ADD_) or out of the lane's histogram
 template <int NW_, bool ADD_>
@@ -284,8 +312,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     static_assert(D4 % 4 == 0, "the equalise blocks take 4 dwords");
     constexpr int KS = (D4 + 7) / 8;
     __shared__ __attribute__((aligned(16384))) WvdLds S;
+    // what a LANE needs of its layer (a wavefront of the packed plan spans layers): {nx, magic, ny / G, ny % G}, {lw, byte offset of
+    // the layer's first window in the frame's arena, ny, 0}, {first window id (lo, hi), 0, 0}
+    __shared__ int4 SL[WVM_MAX_LAYERS][3];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if ((int)threadIdx.x < wt.n) {
+        const WvdLayer& l = wt.l[threadIdx.x];
+        SL[threadIdx.x][0] = make_int4(l.nx, (int)l.magic, l.ny / l.G, l.ny % l.G);
+        SL[threadIdx.x][1] = make_int4(l.lw, (int)(l.off + (unsigned int)(l.by * l.lw + l.bx)), l.ny, 0);
+        SL[threadIdx.x][2] = make_int4((int)(unsigned int)l.first, (int)(l.first >> 32), 0, 0);
+    }
+    __syncthreads();
     // constant address space: scalar loads (SMEM) even though the kernel also stores to global memory
     const __attribute__((address_space(4))) WvdConst& C = *(const __attribute__((address_space(4))) WvdConst*)(uintptr_t)dv.c;
     const int L = dv.L;
@@ -317,23 +355,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         const int fi = wt.nimg > 1 ? v / wt.sTilesPerImage : 0;
         const int img = byXcd ? xcd + 8 * fi : fi;   // frame of a multi-frame pyramid
         const int tile = v - fi * wt.sTilesPerImage;
-        if (img != lastImg) { li = 0; lastImg = img; }
-        while (li + 1 < wt.n && tile >= wt.l[li + 1].sTileFirst) ++li;   // tiles ascend per wavefront inside a frame
-        const WvdLayer& wl = wt.l[li];
-        const int ntask = wl.nx * wl.G;
-        const int task0 = (tile - wl.sTileFirst) * 64 + lane;
-        const unsigned int task = (unsigned int)(task0 < ntask ? task0 : ntask - 1);
-        unsigned int g = __umulhi(task, wl.magic);   // floor(task / nx) or one less
-        unsigned int ix = task - g * (unsigned int)wl.nx;
-        if (ix >= (unsigned int)wl.nx) { ix -= wl.nx; ++g; }
-        const int iy0 = (int)g * K;
-        const int rows = task0 < ntask ? min(K, wl.ny - iy0) : 0;   // windows of this lane; 0: a lane past the layer's last task (it repeats that task, unseen)
-        const int lw = wl.lw;
-        const unsigned int rowStep = (unsigned int)(wt.sy * lw);   // bytes between the windows of a column
-        // addresses = a wave-uniform base (scalar registers) + a 32-bit lane offset
-        const uint8_t* ubase = arena + (size_t)img * wt.imageStride + wl.off;
-        const unsigned int lo0 = (unsigned int)((wl.by + iy0 * wt.sy) * lw + (wl.bx + (int)ix * wt.sx));
-        const int64_t wid0 = (int64_t)img * wt.perImage + wl.first + (int64_t)iy0 * wl.nx + ix;
+        // the lane's task: layer, column, first window row, windows (0: a lane past the last task; it repeats that task, unseen)
+        int myLi, iy0, rows;
+        unsigned int ix;
+        if (wt.packed) {
+            const int task0 = tile * 64 + lane;
+            const WvdTask t = wvd_packed_task((unsigned int)min(task0, wt.pTasks - 1), wt.n, [&](int l) { return wt.l[l].pFirst; }, [&](int l) { return SL[l][0]; });
+            myLi = t.li; ix = t.ix; iy0 = t.iy0;
+            rows = task0 < wt.pTasks ? t.rows : 0;
+        } else {   // the per-layer plan: 64 (column, row group of K) tasks of one layer
+            if (img != lastImg) { li = 0; lastImg = img; }
+            while (li + 1 < wt.n && tile >= wt.l[li + 1].sTileFirst) ++li;   // tiles ascend per wavefront inside a frame
+            const WvdLayer& wl = wt.l[li];
+            const int ntask = wl.nx * wl.G;
+            const int task0 = (tile - wl.sTileFirst) * 64 + lane;
+            const unsigned int task = (unsigned int)(task0 < ntask ? task0 : ntask - 1);
+            unsigned int g = __umulhi(task, wl.magic);   // floor(task / nx) or one less
+            ix = task - g * (unsigned int)wl.nx;
+            if (ix >= (unsigned int)wl.nx) { ix -= wl.nx; ++g; }
+            myLi = li;
+            iy0 = (int)g * K;
+            rows = task0 < ntask ? min(K, wl.ny - iy0) : 0;
+        }
+        const int4 la = SL[myLi][1], lb = SL[myLi][2];
+        const unsigned int nxl = (unsigned int)SL[myLi][0].x;
+        const unsigned int lw = (unsigned int)la.x;                       // per lane from here on
+        const unsigned int rowStep = wvd_mul24((unsigned int)wt.sy, lw);   // bytes between the windows of a column (the host checks sy * lw < 2^24)
+        // addresses = a wave-uniform base (scalar registers: the frame's arena) + a 32-bit lane offset
+        const uint8_t* ubase = arena + (size_t)img * wt.imageStride;
+        const unsigned int lo0 = (unsigned int)la.y + (unsigned int)(iy0 * wt.sy) * lw + ix * (unsigned int)wt.sx;
+        const int64_t wid0 = (int64_t)img * wt.perImage + (int64_t)(((unsigned long long)(unsigned int)lb.y << 32) | (unsigned int)lb.x) + (int64_t)iy0 * nxl + ix;
 
         WVD_T(pa);
         // ---- 1. histogram of the lane's first window: 64 bins x 64 lanes of u16 counters
@@ -344,17 +395,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         }
         __builtin_amdgcn_wave_barrier();
         {
-            unsigned int wn[NW];
+            unsigned int wn[NW], ra = lo0;   // ra: the lane's offset of the row in flight (a running add: the row length is per lane)
 #pragma unroll
-            for (int j = 0; j < NW; ++j) wn[j] = wvd_load_u32(ubase + 4 * j, lo0);
+            for (int j = 0; j < NW; ++j) wn[j] = wvd_load_u32(ubase + 4 * j, ra);
 #pragma unroll 2
             for (int r = 0; r < PH_; ++r) {   // one patch row per iteration, the next row's loads in flight
                 unsigned int w4[NW];
 #pragma unroll
                 for (int j = 0; j < NW; ++j) w4[j] = wn[j];
-                const uint8_t* nsrc = ubase + (size_t)(r + 1 < PH_ ? r + 1 : r) * lw;
+                if (r + 1 < PH_) ra += lw;
 #pragma unroll
-                for (int j = 0; j < NW; ++j) wn[j] = wvd_load_u32(nsrc + 4 * j, lo0);
+                for (int j = 0; j < NW; ++j) wn[j] = wvd_load_u32(ubase + 4 * j, ra);
                 wvd_hist_row<NW, true>(w4, blkH4, laneOff32, inc);
             }
         }
@@ -369,17 +420,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         if (__ballot(active) == 0) break;
         WVD_T(ps);
         if (step > 0 && active) {   // ---- 1'. slide the histogram down by one window: rows leave at the top, rows enter at the bottom
-            const uint8_t* out0 = ubase + (size_t)(step - 1) * rowStep;
-            for (int q = 0; q < wt.sy; ++q) {
+            unsigned int ro = wvd_mad24((unsigned int)(step - 1), rowStep, lo0);   // the row that leaves; the one that enters is PH_ rows below
+            for (int q = 0; q < wt.sy; ++q, ro += lw) {
+                const unsigned int ri = wvd_mad24((unsigned int)PH_, lw, ro);
                 unsigned int wo[NW], wi[NW];
 #pragma unroll
-                for (int j = 0; j < NW; ++j) { wo[j] = wvd_load_u32(out0 + (size_t)q * lw + 4 * j, lo0); wi[j] = wvd_load_u32(out0 + (size_t)(q + PH_) * lw + 4 * j, lo0); }
+                for (int j = 0; j < NW; ++j) { wo[j] = wvd_load_u32(ubase + 4 * j, ro); wi[j] = wvd_load_u32(ubase + 4 * j, ri); }
                 wvd_hist_row<NW, false>(wo, blkH4, laneOff32, inc);
                 wvd_hist_row<NW, true>(wi, blkH4, laneOff32, inc);
             }
         }
         // the window this lane evaluates now (a lane that has run out of windows repeats its last one, unseen)
-        const unsigned int lo = lo0 + (unsigned int)(active ? step : (rows > 0 ? rows - 1 : 0)) * rowStep;
+        const unsigned int lo = wvd_mad24((unsigned int)(active ? step : (rows > 0 ? rows - 1 : 0)), rowStep, lo0);
         wave_sync();
         WVD_T(pb);
         // ---- 2. the fp32 cdf, the LUT, and the exact integer sum / sum of squares of the equalised patch
@@ -398,11 +450,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             const char* Bb = reinterpret_cast<const char*>(dv.B);   // uniform base + lane * 16
             unsigned int lane16 = (unsigned int)lane * 16u;
             asm volatile("" : "+v"(lane16));   // stays an offset register (hoisted out of the loops as 2 KS address pairs, the fragment addresses spill)
+            unsigned int rowOff = lo;   // the lane's offset of patch row `pr`: the fetches walk the rows in order, one add per row
+            int pr = 0;
             auto fetchPx = [&](int ks) {   // pixel dwords of k-step ks
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int q = 8 * ks + j;
-                    if (q < D4) nxq[ks % PF][j] = wvd_load_u32(ubase + (size_t)(q / NW) * lw + 4 * (q % NW), lo);
+                    if (q < D4) {
+                        if (pr < q / NW) { rowOff += lw; ++pr; }
+                        nxq[ks % PF][j] = wvd_load_u32(ubase + 4 * (q % NW), rowOff);
+                    }
                 }
             };
             auto fetch = [&](int ks) {   // digit fragments of k-step ks
@@ -516,7 +573,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             for (int st = 0; st < K; ++st) {
                 const bool mine = (survBits >> st) & 1u;
                 const unsigned long long mask = __ballot(mine);
-                if (mine) dv.q[base + __popcll(mask & ((1ull << lane) - 1ull))] = wid0 + (int64_t)st * wl.nx;
+                if (mine) dv.q[base + __popcll(mask & ((1ull << lane) - 1ull))] = wid0 + (int64_t)((unsigned long long)(unsigned int)st * nxl);
                 base += (unsigned int)__popcll(mask);
             }
         }

@@ -50,6 +50,15 @@ int64_t fd_debug_wvb_rect_sums(const fd_wvm_model* md, const uint8_t* patches, i
  * per frame. */
 int fd_debug_wvd_plan(const int32_t* nx, const int32_t* ny, int n_layers, int frames, int sy, int ph, int slots, int32_t* tile_first);
 
+/* Test hook, needs no GPU: the packed plan k_wvm_prefilter runs by default (FD_WVD_PACK=0 selects the plan above) for the same
+ * arguments.  The (column, row group) tasks of all layers of a frame form ONE flat list -- layer-major, group-major, column-minor --
+ * cut into tiles of 64; the ny rows of a column are dealt evenly over G = ceil(ny / K) groups (the first ny % G walk ny / G + 1
+ * windows, the others ny / G).  Returns K (FD_WVD_K pins it; 1 when 2 sy > ph); *tiles_per_frame = ceil(*tasks_per_frame / 64).
+ * decoded[4 i ..] = {layer, column, first window row, windows} of task tasks[i] (0 <= tasks[i] < *tasks_per_frame), from the function
+ * the kernel decodes its lanes with.  The outputs may be NULL (tasks / decoded with n_tasks = 0). */
+int fd_debug_wvd_packed_plan(const int32_t* nx, const int32_t* ny, int n_layers, int frames, int sy, int ph, int slots, int32_t* tiles_per_frame,
+                             int32_t* tasks_per_frame, const int32_t* tasks, int64_t n_tasks, int32_t* decoded);
+
 /* Test hook: hyperplane distances of n u8 vectors through both instantiations of the u8 RBF MFMA kernel (8 and 16 wavefronts per
  * workgroup).  fd_detect_five_stage scores one frame's positives with either, depending on how many the previous frame had, and
  * relies on bit-identical sums; tests/test_gpu_cascade_hardening.py compares them.  (fd_detect_five_stage keeps per-call state in
