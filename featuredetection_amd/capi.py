@@ -374,6 +374,7 @@ _BENCH_SIGS = {
     "fd_debug_wvd_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "fd_debug_wvd_packed_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int64, C.c_void_p]),
+    "fd_debug_pyrdown_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -728,6 +729,23 @@ def wvd_packed_plan(nx, ny, frames, sy, ph, slots, tasks=None):
         if k < 1:
             raise FdError(k, "fd_debug_wvd_packed_plan")
     return k, tiles.value, ntask.value, dec
+
+
+def pyrdown_stage(image, tile):
+    """Test hook (no GPU): tile `tile` of the pyrDown of a 2-D uint8 image as k_pyrdown_tiled stages it -> (tiles of the layer,
+    staged [35, 128] uint8, entry dict); tile=None only counts the tiles"""
+    image = _c(image, np.uint8)
+    sh, sw = image.shape
+    if tile is None:
+        nt = lib().fd_debug_pyrdown_stage(None, sw, sh, 0, None, None)
+        if nt < 1:
+            raise FdError(1, "fd_debug_pyrdown_stage: no such tile")
+        return nt
+    staged, entry = np.zeros((35, 128), np.uint8), np.zeros(8, np.int32)
+    nt = lib().fd_debug_pyrdown_stage(_ptr(image), sw, sh, tile, _ptr(staged), _ptr(entry))
+    if nt < 1:
+        raise FdError(1, "fd_debug_pyrdown_stage: no such tile")
+    return nt, staged, dict(zip(("src_off", "dst_off", "sw", "sh", "dx0", "dy0", "nx", "ny"), entry.tolist()))
 
 
 def wvb_rect_sums(model, patches_eq):

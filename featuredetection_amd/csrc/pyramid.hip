@@ -29,10 +29,6 @@ struct ResizeJobs {
     int n;
     ResizeJob j[MAXJ];
 };
-struct DownJob {
-    int sw, sh;
-    uint32_t src_off, dst_off;
-};
 // one first-octave chain of k_resize_down: cv::resize of the frame to dw0 x dh0 and its pyrDown to dw1 x dh1
 struct FusedJob {
     int dw0, dh0, dw1, dh1;
@@ -45,11 +41,16 @@ struct FusedJobs {
     int n;
     FusedJob j[MAXJ];
 };
-struct DownJobs {
-    int n;
-    int tile0[MAXJ + 1];   // k_pyrdown_tiled: first tile of every job in the launch's flat tile list (exact grids: no empty workgroups)
-    DownJob j[MAXJ];
+// one tile of k_pyrdown_tiled (62 x 16 outputs): everything a workgroup needs, built on the host with the launch plan and read with
+// one scalar load (pd_tile_entry)
+struct PdTile {
+    uint32_t src_off;   // source layer
+    uint32_t dst_off;   // output (dx0, dy0) of the destination layer
+    int sw, sh;         // source layer
+    int dx0, dy0;       // first output of the tile
+    int nx, ny;         // outputs the tile stores: min(62, dw - dx0) x min(16, dh - dy0)
 };
+static_assert(sizeof(PdTile) == 32, "a tile entry is eight dwords");
 struct FilterJob {
     int w, h;
     uint32_t src_off, dst_off;
@@ -178,7 +179,29 @@ __global__ void k_bgr2gray(const uint8_t* __restrict__ bgr, uint8_t* __restrict_
 constexpr int TL_W = 64, TL_H = 32, TL_PITCH = 136;   // 64 x 32 output pixels per tile, 8 rows per thread: the per-thread column set-up is the
                                                         // larger part of the work of a row
 constexpr int PD_TH = 16;                               // pyrDown: 64 x 16 tiles (its layers are small: 32-row tiles leave CUs idle)
-constexpr int TL_ROWS = 72;                             // resize: 31 * 2.05 + 3 source rows; pyrDown: 2 * 32 + 3
+constexpr int TL_ROWS = 72;                             // resize: 31 * 2.05 + 3 source rows
+
+// cv::pyrDown of four vertically adjacent outputs of one column from a staged tile (k_pyrdown_tiled, and the tail of k_resize_down):
+// T points at the byte of the column's first tap in the first of the 11 rows the outputs reach; PITCH bytes between rows.
+// The row sums [1 4 6 4] . (s0 s1 s2 s3) + s4 are one byte dot product each (v_dot4_u32_u8: exact integers, a third of the
+// instructions); h <= 16 * 255, so h * 6 is a 24-bit multiply-add (v_mul_lo_u32 runs at a quarter of the rate).
+// T is an LDS pointer by type: through a generic one the compiler joins the two 16-bit reads of a row into one 32-bit read before it
+// knows the address space, and that read is only 2-byte aligned in every other lane.
+typedef const __attribute__((address_space(3))) uint8_t* lds_bytes;
+template <int PITCH>
+__device__ __forceinline__ void pyrdown_col4(lds_bytes T, uint32_t out[4]) {
+    uint32_t h[11];
+#pragma unroll
+    for (int r = 0; r < 11; ++r) {
+        lds_bytes S = T + r * PITCH;
+        typedef const __attribute__((address_space(3))) uint16_t* lds_u16;
+        const uint32_t p01 = *(lds_u16)S, p23 = *(lds_u16)(S + 2);
+        h[r] = __builtin_amdgcn_udot4(p01 | (p23 << 16), 0x04060401u, (uint32_t)S[4], false);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        out[j] = (mad24(h[2 * j + 2], 6u, ((h[2 * j + 1] + h[2 * j + 3]) << 2) + h[2 * j]) + h[2 * j + 4] + 128u) >> 8;
+}
 
 // resize: valid while a tile's source rectangle fits the stage from its conservative origin, i.e. 1 <= scale_x, scale_y <= 2.05
 // (first-octave layers: 1 <= scale <= 2, checked where the launch plan is built)
@@ -415,22 +438,13 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
             const int x = x1 + c1;
             if (c1 < FT_W1 && x < jb.dw1) {
                 constexpr int PR = FT_H1 / 4;   // output rows per thread
-                const uint8_t* T = g0 + (2 * wave * PR) * G0_PITCH + 2 * c1;
-                int h[2 * PR + 3];
-#pragma unroll
-                for (int r = 0; r < 2 * PR + 3; ++r) {
-                    const uint8_t* S = T + r * G0_PITCH;
-                    const uint32_t p01 = *reinterpret_cast<const uint16_t*>(S), p23 = *reinterpret_cast<const uint16_t*>(S + 2);
-                    h[r] = (int)__builtin_amdgcn_udot4(p01 | (p23 << 16), 0x04060401u, (uint32_t)S[4], false);
-                }
+                static_assert(PR == 4, "pyrdown_col4");
+                uint32_t v[PR];
+                pyrdown_col4<G0_PITCH>((lds_bytes)g0 + (2 * wave * PR) * G0_PITCH + 2 * c1, v);
                 uint8_t* dp = arena + jb.dst1_off + (uint32_t)((y1 + wave * PR) * jb.dw1) + x;
 #pragma unroll
-                for (int j = 0; j < PR; ++j, dp += jb.dw1) {
-                    if (y1 + wave * PR + j < jb.dh1) {
-                        const int v = h[2 * j + 2] * 6 + (h[2 * j + 1] + h[2 * j + 3]) * 4 + h[2 * j] + h[2 * j + 4];
-                        *dp = (uint8_t)((v + 128) >> 8);
-                    }
-                }
+                for (int j = 0; j < PR; ++j, dp += jb.dw1)
+                    if (y1 + wave * PR + j < jb.dh1) *dp = (uint8_t)v[j];
             }
         }
         if (jb.dst0_off != 0xffffffffu) {   // the resized layer is a kept layer: the tile's own 124 x 32 pixels of it
@@ -458,96 +472,127 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
 #endif
 }
 
+// ---- k_pyrdown_tiled ------------------------------------------------------------------------------------------------------
+// A workgroup takes one 62 x 16 tile of a destination layer: its 127 x 35 source bytes (5-tap halo included) go to LDS as 32 dwords
+// per row, then every thread computes four vertically adjacent outputs of one column (pyrdown_col4).  What a tile is comes from a
+// host-built entry (PdTile, one scalar load); the functions below are __host__ __device__ so that the host hook
+// fd_debug_pyrdown_stage stages a tile with the kernel's own code.
+constexpr int PD_W = 62;                 // 62 x 16 outputs = 127 x 35 source bytes = 32 dwords per row: two rows per wavefront load
+constexpr int PD_LD = 5;                 // wavefront rq stages rows 2 (rq + 4 k) and 2 (rq + 4 k) + 1 (its lanes 0..31 / 32..63), k < PD_LD
+constexpr int PD_ROWS = 8 * PD_LD;       // 40 staged rows; the outputs read 35
+constexpr int PD_PITCH = 136;
+static_assert(2 * PD_TH + 3 <= PD_ROWS && 2 * PD_W + 3 <= 128 && 128 <= PD_PITCH, "pyrDown stage");
+
 // BORDER_REFLECT_101 without branches for the coordinates a 5-tap pyrDown USES (two pixels out on either side): |p|, one reflection
 // at the far end, then a clamp.  Exact for every len >= 1 there (len 1: everything is 0; len 2: -2 -> 0, -1 -> 1, 2 -> 0); coordinates
 // further out only feed outputs outside the layer and may be anything valid.
-__device__ __forceinline__ int reflect_cf(int p, int len) {
+__host__ __device__ inline int reflect_cf(int p, int len) {
     int q = p < 0 ? -p : p;
     q = q >= len ? 2 * len - 2 - q : q;
-    return min(max(q, 0), len - 1);
+    q = q < 0 ? 0 : q;
+    return q > len - 1 ? len - 1 : q;
 }
-constexpr int PD_W = 62;   // pyrDown tile: 62 x 16 outputs = 127 x 35 source bytes = 32 dwords per row: two rows per wavefront load
-// xcdFrames > 0 (a multiple of 8; 1-D grid, a multiple of 8): workgroup b runs on XCD b % 8 (observed dispatch order; only speed depends
-// on it) and takes tiles of the frames (b & 7) + 8 i, like k_resize_down before and k_wvm_prefilter behind this kernel: a frame's
-// generations stay in one L2 instead of going round-robin over all eight.  0: grid (tiles, 1, frames), blockIdx.z = frame.
-__global__ __launch_bounds__(256) void k_pyrdown_tiled(uint8_t* __restrict__ arena0, DownJobs jobs, size_t imageStride, int xcdFrames) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[TL_ROWS * TL_PITCH];
+__host__ __device__ inline int pd_tiles(int sw, int sh) { return (((sw + 1) / 2 + PD_W - 1) / PD_W) * (((sh + 1) / 2 + PD_TH - 1) / PD_TH); }
+// tile t (row-major over the destination layer) of the pyrDown of a sw x sh layer
+__host__ __device__ inline PdTile pd_tile_entry(int sw, int sh, uint32_t src_off, uint32_t dst_off, int t) {
+    const int dw = (sw + 1) / 2, dh = (sh + 1) / 2, tilesX = (dw + PD_W - 1) / PD_W;
+    const int ty = t / tilesX, tx = t - ty * tilesX;
+    PdTile e;
+    e.src_off = src_off;
+    e.sw = sw; e.sh = sh;
+    e.dx0 = tx * PD_W; e.dy0 = ty * PD_TH;
+    e.dst_off = dst_off + (uint32_t)(e.dy0 * dw + e.dx0);
+    e.nx = dw - e.dx0 < PD_W ? dw - e.dx0 : PD_W;
+    e.ny = dh - e.dy0 < PD_TH ? dh - e.dy0 : PD_TH;
+    return e;
+}
+// The dword of source columns xs .. xs + 3 of a row of sw >= 8 pixels, xs even and >= -2: the dword to load (clamped into the row) and
+// the byte selector that makes it the wanted one.  Inside the row the two coincide (identity).  Left of it (xs == -2, tile column 0
+// only) columns -2 .. 1 are bytes {2, 1, 0, 1} of the dword at 0.  Over the right end the dword at sw - 4 is loaded, d = xs - (sw - 4)
+// columns too far left: column sw - 4 + i is byte i for i <= 3, sw reflects to sw - 2 (byte 2), sw + 1 to sw - 3 (byte 1); no stored
+// output reads beyond sw + 1, those bytes may be anything.  Byte i of the constant is that map, so the selector is the constant
+// shifted down by d bytes.  sw >= 8: the two overhangs never meet in one dword.
+struct PdCol {
+    int xc;
+    uint32_t sel;
+};
+__host__ __device__ inline PdCol pd_col(int xs, int sw) {
+    PdCol pc;
+    pc.xc = xs < 0 ? 0 : (xs > sw - 4 ? sw - 4 : xs);
+    const int d = xs - pc.xc;
+    const uint32_t right = (uint32_t)(0x0000010203020100ull >> (8 * ((d > 5 ? 5 : d) & 7)));
+    pc.sel = d < 0 ? 0x01000102u : right;
+    return pc;
+}
+__host__ __device__ inline uint32_t pd_perm(uint32_t v, uint32_t sel) {   // byte i of the result = byte (sel >> 8 i) & 3 of v
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_perm(v, v, sel);   // v_perm_b32
+#else
+    uint32_t r = 0;
+    for (int i = 0; i < 4; ++i) r |= ((v >> (8 * ((sel >> (8 * i)) & 3u))) & 0xffu) << (8 * i);
+    return r;
+#endif
+}
+// What lane `lane` of wavefront rq stages: v[k] = source columns X0 + 4 (lane & 31) .. + 3 of tile row 2 (rq + 4 k) + (lane >> 5), border
+// reflected.  One clamped dword load and one byte permute per row, no tests, nothing per row but the address: rq is wave-uniform in
+// the kernel, so the reflected row offsets of both halves are scalar and a lane picks its own with an AND.
+// Layers narrower than 8 pixels (one tile column, a handful of bytes per row) gather reflected bytes instead.
+__host__ __device__ inline void pd_stage(const uint8_t* __restrict__ src, const PdTile& e, int rq, int lane, uint32_t v[PD_LD]) {
+    const int sw = e.sw, sh = e.sh;
+    const int xs = 2 * e.dx0 - 2 + 4 * (lane & 31), Y0 = 2 * e.dy0 - 2 + 2 * rq;
+    const uint32_t odd = 0u - (uint32_t)(lane >> 5);
+    if (sw >= 8) {
+        const PdCol pc = pd_col(xs, sw);
+#pragma unroll
+        for (int k = 0; k < PD_LD; ++k) {
+            const uint32_t o0 = (uint32_t)(reflect_cf(Y0 + 8 * k, sh) * sw), o1 = (uint32_t)(reflect_cf(Y0 + 8 * k + 1, sh) * sw);
+            uint32_t w;
+            __builtin_memcpy(&w, src + (o0 + ((o1 - o0) & odd) + (uint32_t)pc.xc), 4);
+            v[k] = pd_perm(w, pc.sel);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < PD_LD; ++k) {
+            const uint8_t* row = src + (uint32_t)(reflect_cf(Y0 + 8 * k + (int)(odd & 1u), sh) * sw);
+            uint32_t w = 0;
+            for (int b = 0; b < 4; ++b) w |= (uint32_t)row[reflect_cf(xs + b, sw)] << (8 * b);
+            v[k] = w;
+        }
+    }
+}
+
+// grid (tiles << xcdShift, frames >> xcdShift, 1) with xcdShift = 3, or (tiles, 1, frames) with xcdShift = 0.  With 3, workgroup
+// (b, y) runs on XCD b % 8 (observed dispatch order, the grid's x extent being a multiple of 8; only speed depends on it) and takes
+// tile b >> 3 of frame (b & 7) + 8 y, like k_resize_down before and k_wvm_prefilter behind this kernel: a frame's generations stay
+// in one L2 instead of going round-robin over all eight.
+__global__ __launch_bounds__(256) void k_pyrdown_tiled(uint8_t* __restrict__ arena0, const PdTile* __restrict__ tiles, size_t imageStride, int xcdShift) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[PD_ROWS * PD_PITCH];
     const int c = threadIdx.x & 63, rq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // rq scalar: row offsets on the scalar unit
-    constexpr int NROWS = 2 * PD_TH + 3, PD_LD = (NROWS + 7) / 8;   // 35 source rows; a wavefront stages rows 2 (rq + 4 k) and the next
-    static_assert(2 * (3 + 4 * (PD_LD - 1)) + 1 < TL_ROWS && 128 <= TL_PITCH && 2 * PD_W + 3 <= 128, "pyrDown stage");
-    const bool byXcd = xcdFrames > 0;
-    const int ntile = jobs.tile0[jobs.n];
-    const int first = byXcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, stride = byXcd ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    const int items = byXcd ? (xcdFrames >> 3) * ntile : ntile;   // (frame, tile) items of this XCD, frame-major / the tiles of frame blockIdx.z
-    for (int item = first; item < items; item += stride) {   // flat list of the tiles of all jobs
-        const int fi = byXcd ? item / ntile : 0;
-        const int g = item - fi * ntile;
-        uint8_t* __restrict__ arena = arena0 + (size_t)(byXcd ? (int)(blockIdx.x & 7u) + 8 * fi : (int)blockIdx.z) * imageStride;
-        int ji = 0;
-        while (ji + 1 < jobs.n && g >= jobs.tile0[ji + 1]) ++ji;
-        const DownJob jb = jobs.j[ji];
-        const int t = g - jobs.tile0[ji];
-        const int sw = jb.sw, sh = jb.sh;
-        const int dw = (sw + 1) / 2, dh = (sh + 1) / 2;
-        const uint8_t* src = arena + jb.src_off;
-        uint8_t* dst = arena + jb.dst_off;
-        const int tilesX = (dw + PD_W - 1) / PD_W;
-        const int ty = t / tilesX, tx = t - ty * tilesX;
-        const int dx0 = tx * PD_W, dy0 = ty * PD_TH;
-        const int X0 = 2 * dx0 - 2, Y0 = 2 * dy0 - 2;
-        {   // stage the source rectangle: lane = dword j of row 2 (rq + 4 k) + (lane >> 5).  No tests in the common path: the row is
-            // reflected in closed form, the column clamped into the row; only tiles on the left / right edge of the layer rebuild the
-            // dwords that hang over it from reflected bytes.  (Round 3 staged a flat element list -- a division by 33, two range
-            // tests and a loop-form reflection per element: 170 branches in the kernel, the staging was most of a tile's time.)
-            const int j4 = 4 * (c & 31), half = c >> 5;
-            const int xs = X0 + j4;
-            const int xc = min(max(xs, 0), max(sw - 4, 0));
-            const uint32_t lastDw = (uint32_t)max(sw * sh - 4, 0);
-            uint32_t v[PD_LD];
+    const uint32_t frame = (blockIdx.x & ((1u << xcdShift) - 1u)) + 8u * blockIdx.y + blockIdx.z;
+    const PdTile e = tiles[blockIdx.x >> xcdShift];
+    uint8_t* __restrict__ arena = arena0 + (size_t)frame * imageStride;
+    {
+        uint32_t v[PD_LD];
+        pd_stage(arena + e.src_off, e, rq, c, v);
+        uint8_t* sp = tile + 2 * rq * PD_PITCH + ((0u - (uint32_t)(c >> 5)) & (uint32_t)PD_PITCH) + 4 * (c & 31);
 #pragma unroll
-            for (int k = 0; k < PD_LD; ++k) {
-                const int r = 2 * (rq + 4 * k) + half;
-                v[k] = ld_u32_unaligned(src + min((uint32_t)(reflect_cf(Y0 + r, sh) * sw + xc), lastDw));
+        for (int k = 0; k < PD_LD; ++k) *reinterpret_cast<uint32_t*>(sp + 8 * k * PD_PITCH) = v[k];
+    }
+    __syncthreads();
+    if (c < e.nx) {
+        constexpr int PR = PD_TH / 4;   // output rows per thread
+        static_assert(PR == 4, "pyrdown_col4");
+        uint32_t v[PR];
+        pyrdown_col4<PD_PITCH>((lds_bytes)tile + (2 * rq * PR) * PD_PITCH + 2 * c, v);
+        const int dw = (e.sw + 1) >> 1;
+        uint8_t* dst = arena + e.dst_off + (uint32_t)(rq * PR * dw);   // scalar row pointers, the column as the lane's offset
+#pragma unroll
+        for (int j = 0; j < PR; ++j, dst += dw)
+            if (rq * PR + j < e.ny) {
+                uint32_t col = (uint32_t)c;
+                asm("" : "+v"(col));   // the offset's zero extension inside the block of its store: global_store with a scalar base
+                dst[col] = (uint8_t)v[j];
             }
-            if (X0 < 0 || X0 + 128 > sw) {   // wave-uniform: an edge tile
-                if (!(xs >= 0 && xs + 3 < sw)) {
-#pragma unroll
-                    for (int k = 0; k < PD_LD; ++k) {
-                        const int r = 2 * (rq + 4 * k) + half;
-                        const uint8_t* row = src + (uint32_t)(reflect_cf(Y0 + r, sh) * sw);
-                        uint32_t w = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) w |= (uint32_t)row[reflect_cf(xs + b, sw)] << (8 * b);
-                        v[k] = w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < PD_LD; ++k) *reinterpret_cast<uint32_t*>(&tile[(2 * (rq + 4 * k) + half) * TL_PITCH + j4]) = v[k];
-        }
-        __syncthreads();
-        const int x = dx0 + c;
-        if (c < PD_W && x < dw) {
-            constexpr int PR = PD_TH / 4;   // output rows per thread
-            const uint8_t* T = tile + (2 * rq * PR) * TL_PITCH + 2 * c;
-            int h[2 * PR + 3];
-#pragma unroll
-            for (int r = 0; r < 2 * PR + 3; ++r) {
-                const uint8_t* S = T + r * TL_PITCH;
-                // [1 4 6 4] . (s0 s1 s2 s3) + s4 as one byte dot product (v_dot4_u32_u8): exact integers, a third of the instructions
-                const uint32_t p01 = *reinterpret_cast<const uint16_t*>(S), p23 = *reinterpret_cast<const uint16_t*>(S + 2);
-                h[r] = (int)__builtin_amdgcn_udot4(p01 | (p23 << 16), 0x04060401u, (uint32_t)S[4], false);
-            }
-            uint8_t* dp = dst + (uint32_t)((dy0 + rq * PR) * dw) + x;
-#pragma unroll
-            for (int j = 0; j < PR; ++j, dp += dw) {
-                if (dy0 + rq * PR + j < dh) {
-                    const int v = h[2 * j + 2] * 6 + (h[2 * j + 1] + h[2 * j + 3]) * 4 + h[2 * j] + h[2 * j + 4];
-                    *dp = (uint8_t)((v + 128) >> 8);
-                }
-            }
-        }
-        __syncthreads();
     }
 }
 
@@ -935,8 +980,10 @@ struct FusedLaunch {    // k_resize_down
     int tilesPerFrame;  // ... and the number of tiles per frame
     int grid;
 };
-struct DownLaunch {     // k_pyrdown_tiled; the grid follows from the launch's tile count, jobs.tile0[jobs.n]
-    DownJobs jobs;
+struct DownLaunch {     // k_pyrdown_tiled: the pyrDowns of up to MAXJ layers of one generation
+    int njobs;
+    int ntile;          // tiles per frame: the grid
+    uint32_t tileTab;   // its PdTile list in rtab (offset in int2 entries)
 };
 struct FilterLaunch {   // k_gradbin / k_lbp, behind k_box_blur where GradientFilter blurs (blur.n == jobs.n then, 0 otherwise)
     FilterJobs jobs, blur;
@@ -955,11 +1002,10 @@ fd_pyramid::~fd_pyramid() { if (ready) (void)hipEventDestroy(ready); }
 
 namespace {
 
-// The slot of a stage's next job.  A launch takes MAXJ jobs (they travel by value); a stage's launches begin at `first`, so that a
-// generation of pyrDowns never tops up the last launch of the generation it reads.
+// The slot of a stage's next job.  A launch takes MAXJ jobs (they travel by value).
 template <class Launch>
-auto& next_job(std::vector<Launch>& launches, size_t first = 0) {
-    if (launches.size() == first || launches.back().jobs.n == MAXJ) launches.emplace_back();   // value-initialised: no jobs yet
+auto& next_job(std::vector<Launch>& launches) {
+    if (launches.empty() || launches.back().jobs.n == MAXJ) launches.emplace_back();   // value-initialised: no jobs yet
     auto& jobs = launches.back().jobs;
     return jobs.j[jobs.n++];
 }
@@ -972,7 +1018,8 @@ void build_plan(fd_pyramid* p, int W, int H) {
     static const int mode = [] { const char* e = getenv("FD_PYR_FUSED"); return e ? atoi(e) : 1; }();   // 0: never, 1: default, 2: kept layers too
     std::vector<char> fused(all.size(), 0);   // the depth-0 layers that k_resize_down resizes, together with their pyrDown
     // rtab: the cv::resize column tables of the fused layers -- the kernel's own float expressions (k_resize_tiled's srcX), evaluated
-    // once per geometry on the host (this file is built with -ffp-contract=off) --, behind them one tile list per k_resize_down launch
+    // once per geometry on the host (this file is built with -ffp-contract=off) --, behind them one tile list per k_resize_down
+    // launch, then one per k_pyrdown_tiled launch
     std::vector<int2> tab;
     std::vector<std::vector<int4>> tiles;     // {X0, ncol, tx | ty << 16, chain of the launch}
     for (size_t k = 0; k < all.size(); ++k) {
@@ -1052,8 +1099,6 @@ void build_plan(fd_pyramid* p, int W, int H) {
             F.grid = (int)std::min<int64_t>((int64_t)F.tilesPerFrame * NI, (int64_t)p->ctx->num_cus * perCu);
             if (NI >= 8 && F.grid >= 64) F.grid &= ~7;
         }
-        p->rtab.reserve(sizeof(int2) * tab.size());
-        HIP_CHECK(hipMemcpy(p->rtab.p, tab.data(), sizeof(int2) * tab.size(), hipMemcpyHostToDevice));
     }
     // (Measured and dropped, twice.  Round 3: one workgroup walking all deeper generations of a chain tile by tile -- 160 us per 64-frame
     // call against 57 us for the per-generation launches, 32 serial tiles per workgroup.  Round 5: k_pyrdown_chain, a workgroup owning a
@@ -1063,17 +1108,34 @@ void build_plan(fd_pyramid* p, int W, int H) {
     // shares the row dot products between vertically adjacent outputs.  The per-generation launches are latency-bound but cheap.)
     int maxDepth = 0;
     for (const HostLayer& L : all) maxDepth = std::max(maxDepth, L.depth);
+    // One flat tile list per launch, layer after layer (exact grids: no empty workgroups).  A launch takes MAXJ layers, and a
+    // generation never tops up the last launch of the generation it reads.
+    static_assert(sizeof(PdTile) == 4 * sizeof(int2), "PdTile entries in rtab");
     for (int d = 1; d <= maxDepth; ++d) {
         const size_t first = plan.down.size();
         for (size_t k = 1; k < all.size(); ++k) {
             const HostLayer& L = all[k];
             if (L.depth != d || fused[k - 1]) continue;
             const HostLayer& S = all[k - 1];   // previous entry of the same chain
-            DownJob& j = next_job(plan.down, first);
-            j.sw = S.w; j.sh = S.h; j.src_off = S.gray_off; j.dst_off = L.gray_off;
-            DownJobs& jobs = plan.down.back().jobs;
-            jobs.tile0[jobs.n] = jobs.tile0[jobs.n - 1] + ((L.w + PD_W - 1) / PD_W) * ((L.h + PD_TH - 1) / PD_TH);
+            if (plan.down.size() == first || plan.down.back().njobs == MAXJ) {
+                if (tab.size() & 1) tab.push_back(make_int2(0, 0));
+                plan.down.push_back(DownLaunch{0, 0, (uint32_t)tab.size()});
+            }
+            DownLaunch& D = plan.down.back();
+            const int nt = pd_tiles(S.w, S.h);
+            for (int t = 0; t < nt; ++t) {
+                const PdTile e = pd_tile_entry(S.w, S.h, S.gray_off, L.gray_off, t);
+                int2 q[4];
+                std::memcpy(q, &e, sizeof(e));
+                tab.insert(tab.end(), q, q + 4);
+            }
+            D.njobs++;
+            D.ntile += nt;
         }
+    }
+    if (!tab.empty()) {
+        p->rtab.reserve(sizeof(int2) * tab.size());
+        HIP_CHECK(hipMemcpy(p->rtab.p, tab.data(), sizeof(int2) * tab.size(), hipMemcpyHostToDevice));
     }
     if (p->filter_kind != FD_LAYER_NONE) {
         const bool blur = p->filter_kind == FD_LAYER_GRADBIN && p->grad_blur > 0;
@@ -1218,12 +1280,12 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
     for (const FusedLaunch& F : plan.fused)
         hipLaunchKernelGGL(k_resize_down, dim3(F.grid), dim3(256), 0, st, arena, p->gray_full_off, W, H, p->rtab.as<int2>(), F.jobs, F.tileTab, F.tilesPerFrame, NI, IS);
     const bool downByXcd = NI >= 8 && NI % 8 == 0 && fd_knob_pyr_xcd();   // multi-frame: frame f's tiles on XCD f % 8
-    for (const DownLaunch& D : plan.down) {
-        const int ntile = D.jobs.tile0[D.jobs.n];
-        if (downByXcd)   // one tile per workgroup (up to 8 x 8192 workgroups; beyond that they loop)
-            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(8 * (int)std::min<int64_t>((int64_t)(NI / 8) * ntile, 8192)), dim3(256), 0, st, arena, D.jobs, IS, NI);
+    for (const DownLaunch& D : plan.down) {   // one tile per workgroup
+        const PdTile* tiles = reinterpret_cast<const PdTile*>(p->rtab.as<int2>() + D.tileTab);
+        if (downByXcd)
+            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(8 * D.ntile, NI / 8), dim3(256), 0, st, arena, tiles, IS, 3);
         else
-            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(tile_grid_for(ntile), 1, NI), dim3(256), 0, st, arena, D.jobs, IS, 0);
+            hipLaunchKernelGGL(k_pyrdown_tiled, dim3(D.ntile, 1, NI), dim3(256), 0, st, arena, tiles, IS, 0);
     }
     for (const FilterLaunch& F : plan.filter) {
         const dim3 g(F.grid, F.jobs.n);
@@ -1622,6 +1684,29 @@ int fd_lbp_image(fd_ctx* ctx, const uint8_t* gray, int w, int h, int lbp_type, u
         HIP_CHECK(hipMemcpyAsync(dst, buf.as<uint8_t>() + doff, n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
+}
+
+// Test hook (include/fd_hip_bench.h; needs no GPU): tile `tile` of the pyrDown of a sw x sh image as k_pyrdown_tiled stages it, by
+// the kernel's own entry builder and staging function, lane by lane
+int fd_debug_pyrdown_stage(const uint8_t* image, int sw, int sh, int tile, uint8_t* staged, int32_t* entry) {
+    if (sw < 1 || sh < 1 || (int64_t)sw * sh > 0x7fffffff) return -1;
+    const int nt = pd_tiles(sw, sh);
+    if (!image && !staged && !entry) return nt;
+    if (!image || tile < 0 || tile >= nt) return -1;
+    const PdTile e = pd_tile_entry(sw, sh, 0, 0, tile);
+    if (entry) std::memcpy(entry, &e, sizeof(e));
+    if (staged) {
+        for (int rq = 0; rq < 4; ++rq)
+            for (int lane = 0; lane < 64; ++lane) {
+                uint32_t v[PD_LD];
+                pd_stage(image, e, rq, lane, v);
+                for (int k = 0; k < PD_LD; ++k) {
+                    const int r = 2 * (rq + 4 * k) + (lane >> 5);
+                    if (r < 2 * PD_TH + 3) std::memcpy(staged + r * 128 + 4 * (lane & 31), &v[k], 4);
+                }
+            }
+    }
+    return nt;
 }
 
 }  // extern "C"

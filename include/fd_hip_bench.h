@@ -59,6 +59,14 @@ int fd_debug_wvd_plan(const int32_t* nx, const int32_t* ny, int n_layers, int fr
 int fd_debug_wvd_packed_plan(const int32_t* nx, const int32_t* ny, int n_layers, int frames, int sy, int ph, int slots, int32_t* tiles_per_frame,
                              int32_t* tasks_per_frame, const int32_t* tasks, int64_t n_tasks, int32_t* decoded);
 
+/* Test hook, needs no GPU: tile `tile` (row-major over the 62 x 16 output tiles) of cv::pyrDown of the sw x sh 8-bit image as
+ * k_pyrdown_tiled stages it in LDS, made by the kernel's own tile-entry builder and per-lane staging function.  staged[r * 128 + c],
+ * 35 x 128 bytes: source pixel (2 dy0 - 2 + r, 2 dx0 - 2 + c), BORDER_REFLECT_101, wherever a stored output of the tile reads it.
+ * entry[8] = {src_off, dst_off, sw, sh, dx0, dy0, nx, ny} with the layer offsets 0 (dst_off: the tile's first output inside its
+ * layer); nx x ny outputs are stored.  Returns the number of tiles of the layer (image, staged, entry all NULL: only that), or -1 when
+ * there is no such tile. */
+int fd_debug_pyrdown_stage(const uint8_t* image, int sw, int sh, int tile, uint8_t* staged, int32_t* entry);
+
 /* Test hook: hyperplane distances of n u8 vectors through both instantiations of the u8 RBF MFMA kernel (8 and 16 wavefronts per
  * workgroup).  fd_detect_five_stage scores one frame's positives with either, depending on how many the previous frame had, and
  * relies on bit-identical sums; tests/test_gpu_cascade_hardening.py compares them.  (fd_detect_five_stage keeps per-call state in
