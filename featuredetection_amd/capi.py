@@ -375,6 +375,7 @@ _BENCH_SIGS = {
     "fd_debug_wvd_packed_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int64, C.c_void_p]),
     "fd_debug_pyrdown_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_debug_resize_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -746,6 +747,23 @@ def pyrdown_stage(image, tile):
     if nt < 1:
         raise FdError(1, "fd_debug_pyrdown_stage: no such tile")
     return nt, staged, dict(zip(("src_off", "dst_off", "sw", "sh", "dx0", "dy0", "nx", "ny"), entry.tolist()))
+
+
+def resize_stage(image, dw0, dh0, tile):
+    """Test hook (no GPU): tile `tile` of the fused resize (2-D uint8 image -> dw0 x dh0) + pyrDown as k_resize_down stages it ->
+    (tiles of the layer, staged [36, 512] uint8, read offsets [35, 127] int32, entry dict); tile=None only counts the tiles"""
+    image = _c(image, np.uint8)
+    sh, sw = image.shape
+    if tile is None:
+        nt = lib().fd_debug_resize_stage(None, sw, sh, dw0, dh0, 0, None, None, None)
+        if nt < 1:
+            raise FdError(1, "fd_debug_resize_stage: not a layer of k_resize_down")
+        return nt
+    staged, off, entry = np.zeros((36, 512), np.uint8), np.zeros((35, 127), np.int32), np.zeros(8, np.int32)
+    nt = lib().fd_debug_resize_stage(_ptr(image), sw, sh, dw0, dh0, tile, _ptr(staged), _ptr(off), _ptr(entry))
+    if nt < 1:
+        raise FdError(1, "fd_debug_resize_stage: no such tile")
+    return nt, staged, off, dict(zip(("X0", "ncol", "tx", "ty", "gx0", "gy0", "dw1", "dh1"), entry.tolist()))
 
 
 def wvb_rect_sums(model, patches_eq):

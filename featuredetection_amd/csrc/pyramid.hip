@@ -303,8 +303,9 @@ __global__ __launch_bounds__(256) void k_resize_tiled(const uint8_t* __restrict_
 //   * the cv::resize column coordinates and fixed-point weights come from a per-layer table built on the host with the kernel's own
 //     float expressions (xtab[dx] = {left source column, a0 | a1 << 16}); the rows' (k_resize_tiled's srcY) are worked out with the
 //     next tile's loads, one resized row per lane;
-//   * the stage holds the two source rows of every resized row of the tile in slots of their own (y0 in slot 2 i, y1 in slot 2 i + 1),
-//     so a resized row reads its four bytes at fixed offsets: no row record, scalar unpacking or address arithmetic per row.
+//   * the stage holds the two source rows of every resized row of the tile in a slot of their own, interleaved byte-wise (y0 at the
+//     even bytes, y1 at the odd ones), so a resized row reads its four bytes as two aligned 16-bit words at fixed offsets: no row
+//     record, scalar unpacking or address arithmetic per row.
 // -DFD_PYR_PROF (tools/build_prof_lib.sh, tools/pyr_phases.py): ticks thread 0 of every workgroup spends in the phases of k_resize_down
 #ifdef FD_PYR_PROF
 constexpr int PYR_PROF_WGS = 65536;
@@ -315,48 +316,116 @@ __device__ unsigned long long fd_pyr_prof[PYR_PROF_WGS * 8];   // one record per
 #endif
 constexpr int FT_W1 = 62, FT_H1 = 16;                    // pyrDown tile
 constexpr int G0_W = 2 * FT_W1 + 3, G0_H = 2 * FT_H1 + 3, G0_PITCH = 128;   // resized pixels under it: 127 x 35
-constexpr int FS_PITCH = 256;                           // source stage: 126 * 2.0 + 3 columns (64 dwords: one per lane) ...
-constexpr int FS_LOADS = (2 * G0_H + 3) / 4;            // ... in 2 * 35 slots: wavefront w holds slots w, w + 4, ..., a lane one dword of each
+constexpr int FS_PITCH = 256;                           // source stage: 126 * 2.0 + 3 columns (64 dwords: one per lane) of a source row
+constexpr int FS_LOADS = (2 * G0_H + 3) / 4;            // 18 dwords per lane: rows y0 and y1 of the FS_ROWS resized rows of its wavefront
+constexpr int FS_ROWS = FS_LOADS / 2;                   // wavefront w fetches and stages the resized rows 9 w .. 9 w + 8
+constexpr int FS_SLOT = 2 * FS_PITCH;                   // pair slot of a resized row: byte 2 x = row y0, byte 2 x + 1 = row y1 of source column X0 + x
+constexpr int FS_SLOTS = 2 * FS_LOADS;                  // 36 slots; the tile has 35 rows, slot 35 repeats row 34
+static_assert(FS_SLOTS >= G0_H + 1, "the last column's neighbour read of the tile's last row lands in the next slot");
 // Persistent workgroups walk a host-built list of tiles ({source columns, tile position, chain} per entry: the layout is static) and keep
 // the NEXT tile's global loads -- 18 source dwords and the column's xtab entry per thread -- in flight in registers while they resize the
 // current one: a tile used to spend 45 % of its 7.6 us waiting for them (in-kernel timestamps, tools/pyr_phases.py).
 // Multi-frame pyramids: workgroup b runs on XCD b % 8 and takes the frames b % 8, b % 8 + 8, ...: a frame's gray image is read by one L2.
+//
+// The row arithmetic and the stage addressing are __host__ __device__ functions: the host hook fd_debug_resize_stage stages a tile
+// with the kernel's own code.
+struct FusedRow {
+    int y0, y1;      // the two source rows of a resized row, clamped into the image
+    uint32_t taps;   // its vertical weights b0 | b1 << 16
+};
+__host__ __device__ inline int fused_rn(float v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __float2int_rn(v);
+#else
+    return (int)nearbyintf(v);
+#endif
+}
+// Row i of the tile whose first resized row (before the reflection) is gy0: BORDER_REFLECT_101 of the resized rows the kept pyrDown
+// rows reach (one reflection; rows further out only feed pyrDown rows past the layer's end, any valid row will do for them), then
+// k_resize_tiled's srcY / clampY
+__host__ __device__ inline FusedRow fused_row(int i, int gy0, int dh0, double scale_y, int sh) {
+    const int py = gy0 + (i < G0_H - 1 ? i : G0_H - 1), pr = py < 0 ? -py : (py >= dh0 ? 2 * dh0 - 2 - py : py);
+    const int pc = pr < 0 ? 0 : (pr > dh0 - 1 ? dh0 - 1 : pr);
+    float fy = (float)((pc + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy -= sy;
+    FusedRow r;
+    r.taps = (uint32_t)fused_rn((1.f - fy) * 2048) | (uint32_t)fused_rn(fy * 2048) << 16;
+    r.y0 = sy < 0 ? 0 : (sy > sh - 1 ? sh - 1 : sy);
+    r.y1 = sy + 1 < 0 ? 0 : (sy + 1 > sh - 1 ? sh - 1 : sy + 1);
+    return r;
+}
+// the first of the four source columns lane `lane` fetches of every row: lanes right of the tile's ncol columns take its last dword again
+__host__ __device__ inline uint32_t fs_fetch_col(int lane, int X0, int ncol) {
+    const int last = (ncol - 1) >> 2;
+    return (uint32_t)(4 * (lane < last ? lane : last) + X0);
+}
+__host__ __device__ inline uint32_t fs_perm(uint32_t hi, uint32_t lo, uint32_t sel) {   // v_perm_b32: selector byte 0..3 = byte of lo, 4..7 = of hi, 12 = 0
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    uint32_t r = 0;
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t b = (sel >> (8 * i)) & 255u;
+        const uint32_t v = b < 4 ? lo >> (8 * b) : (b < 8 ? hi >> (8 * (b - 4)) : 0u);
+        r |= (v & 255u) << (8 * i);
+    }
+    return r;
+#endif
+}
+// what a lane stores into the slot of a resized row: its dword a of row y0 and b of row y1 as {a0 b0 a1 b1 | a2 b2 a3 b3} ...
+__host__ __device__ inline uint2 fs_pair(uint32_t a, uint32_t b) {
+    uint2 r;
+    r.x = fs_perm(b, a, 0x05010400u);
+    r.y = fs_perm(b, a, 0x07030602u);
+    return r;
+}
+// ... at this byte of the stage (8-byte aligned)
+__host__ __device__ inline int fs_store_off(int row, int lane) { return row * FS_SLOT + 8 * lane; }
+// The byte of the stage where the thread of left source column sx reads rows y0 | y1 << 8 of that column for resized row `row` of the
+// tile; the right neighbour's pair is the 16-bit word behind it (+ 2).  Both are even: the LDS serves an odd 16-bit read slowly.
+// A column that the reflection on a layer's right edge takes back left of the tile's first source column (e.g. 374 against 494 on
+// the last tile of a 498-wide layer) only feeds pyrDown outputs past the layer's end: the clamp keeps its reads inside its slot.
+// Columns the tile keeps lie in 0 .. FS_PITCH - 1 already; 255 is the image's last column there, whose neighbour -- the first word
+// of the next slot, and slot 35 exists -- weighs 0.
+__host__ __device__ inline int fs_read_off(int sx, int X0, int row) {
+    const int x = sx - X0;
+    return 2 * (x < 0 ? 0 : (x > FS_PITCH - 1 ? FS_PITCH - 1 : x)) + row * FS_SLOT;
+}
+
 struct FusedFetch {   // what a thread holds for a tile before it is in LDS
-    uint32_t v[FS_LOADS];
+    uint32_t v[FS_LOADS];   // v[2 q], v[2 q + 1]: its dword of rows y0, y1 of the resized row FS_ROWS w + q
     int2 ex;         // thread = column of the tile: its xtab entry
-    uint32_t taps;   // lane q = resized row (w >> 1) + 2 q of the tile: its vertical weights b0 | b1 << 16
+    uint32_t taps;   // lane q < FS_ROWS = resized row FS_ROWS w + q of the tile: its vertical weights b0 | b1 << 16
 };
 __device__ __forceinline__ void fused_issue(FusedFetch& f, const uint8_t* __restrict__ src, int sw, int sh, const int2* __restrict__ tabs,
                                             const FusedJob& jb, const int4 d) {
     const int X0 = d.x, ncol = d.y;
     const int gx0 = 2 * (d.z & 0xffff) * FT_W1 - 2, gy0 = 2 * (int)((uint32_t)d.z >> 16) * FT_H1 - 2;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t rowOff;
-    {   // slot w + 4 q holds source row y0 (even w) or y1 (odd w) of the tile's resized row (w >> 1) + 2 q, and lane q works that row out:
-        // BORDER_REFLECT_101 of the resized rows the kept pyrDown rows reach (one reflection; rows further out only feed pyrDown rows past
-        // the layer's end, any valid row will do for them), then k_resize_tiled's srcY / clampY
-        const int py = gy0 + min((wave >> 1) + 2 * lane, G0_H - 1), pr = py < 0 ? -py : (py >= jb.dh0 ? 2 * jb.dh0 - 2 - py : py);
-        float fy = (float)((min(max(pr, 0), jb.dh0 - 1) + 0.5) * jb.scale_y - 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= sy;
-        f.taps = (uint32_t)__float2int_rn((1.f - fy) * 2048) | (uint32_t)__float2int_rn(fy * 2048) << 16;
-        rowOff = mul24((uint32_t)min(max(sy + (wave & 1), 0), sh - 1), (uint32_t)sw);
-    }
+    // wavefront w fetches both source rows of the resized rows FS_ROWS w + q, and lane q works that row out (the lanes from FS_ROWS on
+    // work out rows nobody asks them for)
+    const FusedRow r = fused_row(FS_ROWS * wave + lane, gy0, jb.dh0, jb.scale_y, sh);
+    f.taps = r.taps;
+    const uint32_t rowOff0 = mul24((uint32_t)r.y0, (uint32_t)sw), rowOff1 = mul24((uint32_t)r.y1, (uint32_t)sw);
     // A dword that hangs over the right edge of the image takes its last bytes from the next row (or, in the last row, from the arena
     // behind the gray image): they stand for columns >= sw, which no tap reads (the last column's right neighbour has weight 0).
     // No predication: lanes right of the rectangle load its last dword again (valid addresses, values nobody reads) -- with a test per
     // load the loads were as many basic blocks of exec-mask bookkeeping, 400 instructions per tile.
-    const uint32_t voff = (uint32_t)(4 * min(lane, (ncol - 1) >> 2) + X0);
+    const uint32_t voff = fs_fetch_col(lane, X0, ncol);
 #pragma unroll
-    for (int q = 0; q < FS_LOADS; ++q) f.v[q] = ld_u32_unaligned(src + ((uint32_t)__builtin_amdgcn_readlane((int)rowOff, q) + voff));
+    for (int q = 0; q < FS_ROWS; ++q) {
+        f.v[2 * q] = ld_u32_unaligned(src + ((uint32_t)__builtin_amdgcn_readlane((int)rowOff0, q) + voff));
+        f.v[2 * q + 1] = ld_u32_unaligned(src + ((uint32_t)__builtin_amdgcn_readlane((int)rowOff1, q) + voff));
+    }
     f.ex = tabs[jb.xtab + reflect101(gx0 + (int)(threadIdx.x & 127), jb.dw0)];
 }
 
 __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena0, uint32_t src_off, int sw, int sh, const int2* __restrict__ tabs,
                                                      FusedJobs jobs, uint32_t tileTab, int tilesPerFrame, int nimg, size_t imageStride) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[4 * FS_LOADS * FS_PITCH];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[FS_SLOTS * FS_SLOT];
     __shared__ __attribute__((aligned(16))) uint8_t g0[G0_H * G0_PITCH];
-    __shared__ uint2 taps[G0_H];   // per resized row of the tile: b0 << 12, b1 << 12 (read as a broadcast beside the row's bytes)
+    __shared__ __attribute__((aligned(16))) uint2 taps[G0_H];   // per resized row of the tile: b0 << 12, b1 << 12 (read as a broadcast beside the row's bytes)
     const int4* tiles = reinterpret_cast<const int4*>(tabs + tileTab);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool byXcd = nimg >= 8 && (gridDim.x & 7u) == 0;
@@ -385,12 +454,14 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
         const int x1 = (d.z & 0xffff) * FT_W1, y1 = (int)((uint32_t)d.z >> 16) * FT_H1;   // first pyrDown pixel of the tile
         const int gx0 = 2 * x1 - 2, gy0 = 2 * y1 - 2;                      // resized pixel of tile entry (0, 0), before the border reflection
         {   // the fetched source rows and vertical taps -> LDS
-            // every lane stores its dword of every slot (a dword per lane; what lies right of the rectangle is never read)
-            static_assert(2 * G0_H <= 4 * FS_LOADS && FS_PITCH == 256, "stage holds a dword per lane for slots wave + 4 q");
+            // every lane stores its two dwords of every row, interleaved (what lies right of the rectangle is never read); a row's taps
+            // come from the lane that worked the row out: nine adjacent entries per wavefront, no two on one bank
+            static_assert(FS_LOADS % 2 == 0 && 4 * FS_ROWS >= G0_H && FS_PITCH == 256, "stage holds a dword pair per lane for rows FS_ROWS wave + q");
 #pragma unroll
-            for (int q = 0; q < FS_LOADS; ++q) *reinterpret_cast<uint32_t*>(&stage[(wave + 4 * q) * FS_PITCH + 4 * lane]) = f.v[q];
-            const int i = (wave >> 1) + 2 * lane;
-            if ((wave & 1) == 0 && i < G0_H) taps[i] = make_uint2((f.taps & 0xffffu) << 12, (f.taps >> 16) << 12);
+            for (int q = 0; q < FS_ROWS; ++q)
+                *reinterpret_cast<uint2*>(&stage[fs_store_off(FS_ROWS * wave + q, lane)]) = fs_pair(f.v[2 * q], f.v[2 * q + 1]);
+            const int i = FS_ROWS * wave + lane;
+            if (lane < FS_ROWS && i < G0_H) taps[i] = make_uint2((f.taps & 0xffffu) << 12, (f.taps >> 16) << 12);
         }
         const int2 ex = f.ex;
         PYR_T(p1);
@@ -399,35 +470,41 @@ __global__ __launch_bounds__(256) void k_resize_down(uint8_t* __restrict__ arena
         if (itemN < items)   // the next tile's loads fly while this one is resized
             fused_issue(f, arena0 + (size_t)frame_of(itemN) * imageStride + src_off, sw, sh, tabs, jobs.j[dN.w], dN);
         PYR_T(p3);
-        {   // ---- resize: thread = one column of the tile, half of its rows (0..17 / 17..34: row 17 is computed by both halves, the same
-            //      value stored twice, and nothing is predicated).  A row: its two byte pairs at fixed offsets (each read as s0 | s1 << 16
-            //      for v_dot2_u32_u16 against a0 | a1 << 16) and its taps as an LDS broadcast that no address waits for
+        {   // ---- resize: thread = one column of the tile, half of its rows (0..17 / 18..34).  A row: the pairs y0 | y1 << 8 of its column
+            //      and of the right neighbour at fixed offsets (two permutes make s0 | s1 << 16 of either row for v_dot2_u32_u16 against
+            //      a0 | a1 << 16) and its taps as an LDS broadcast that no address waits for, two rows per 16-byte read
             const int c = threadIdx.x & 127, half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7);
             if (c < G0_W) {
-                const int rBase = half * (G0_H - 18);
-                // the right neighbour is the next byte except in the image's last column, where its weight a1 is 0.  A column that the
-                // reflection on a layer's right edge takes back left of the tile's first source column (e.g. 374 against 494 on the last
-                // tile of a 498-wide layer) only feeds pyrDown outputs past the layer's end: the clamp keeps its reads inside its slot
-                // (columns the tile keeps lie in 0 .. FS_PITCH - 1 already; 255 is the image's last column, whose neighbour weighs 0)
-                const int lx = min(max(ex.x - X0, 0), FS_PITCH - 1) + 2 * rBase * FS_PITCH;
-                // the right neighbour through an offset the compiler cannot relate to lx: it would otherwise merge the two byte reads into
-                // one ds_read_u16 at an odd address, which the LDS serves so slowly that the kernel took 4x as long (363 against 85 us)
-                int lx1 = lx + 1;
+                constexpr int HR = (G0_H + 1) / 2;   // 18 rows for the first half, 17 for the second
+                static_assert(HR % 2 == 0 && (HR * sizeof(uint2)) % 16 == 0 && 2 * HR - 1 == G0_H, "either half reads its taps as aligned row pairs");
+                const int rBase = half * HR;
+                const int lx = fs_read_off(ex.x, X0, rBase);
+                // the right neighbour through an offset the compiler cannot relate to lx: it would otherwise merge the two 16-bit reads
+                // into one ds_read_b32 that is only 2-byte aligned in the odd columns (an odd-address ds_read_u16 once made this kernel
+                // 4x as slow: 363 against 85 us)
+                int lx1 = lx + 2;
                 asm("" : "+v"(lx1));
-                const uint8_t *sp = stage + lx, *sp1 = stage + lx1;
+                typedef const __attribute__((address_space(3))) uint16_t* lds_u16;
+                lds_bytes sp = (lds_bytes)stage + lx, sp1 = (lds_bytes)stage + lx1;
                 const uint2* tp = taps + rBase;
                 const u16x2 aw = __builtin_bit_cast(u16x2, ex.y);
                 uint8_t* gp = g0 + rBase * G0_PITCH + c;
-#pragma unroll
-                for (int i = 0; i < 18; ++i) {
-                    const uint8_t *s = sp + 2 * i * FS_PITCH, *s1 = sp1 + 2 * i * FS_PITCH;
-                    const u16x2 p0 = {s[0], s1[0]}, p1 = {s[FS_PITCH], s1[FS_PITCH]};
-                    const uint2 t = tp[i];
+                auto row = [&](int i, const uint2 t) {
+                    const uint32_t P = *(lds_u16)(sp + i * FS_SLOT), Q = *(lds_u16)(sp1 + i * FS_SLOT);
+                    const u16x2 p0 = __builtin_bit_cast(u16x2, fs_perm(Q, P, 0x0c040c00u)), p1 = __builtin_bit_cast(u16x2, fs_perm(Q, P, 0x0c050c01u));
                     const unsigned int h0 = __builtin_amdgcn_udot2(p0, aw, 0u, false) & ~15u;   // cv::resize's horizontal intermediate, times 16
                     const unsigned int h1 = __builtin_amdgcn_udot2(p1, aw, 0u, false) & ~15u;
                     // b << 12 (<= 2^23): (b << 12) * (h & ~15) >> 32 == (b * (h >> 4)) >> 16
                     gp[i * G0_PITCH] = (uint8_t)((mulhi24(t.x, h0) + mulhi24(t.y, h1) + 2) >> 2);
+                };
+#pragma unroll
+                for (int i = 0; i < HR - 2; i += 2) {
+                    const uint4 t2 = *reinterpret_cast<const uint4*>(tp + i);
+                    row(i, make_uint2(t2.x, t2.y));
+                    row(i + 1, make_uint2(t2.z, t2.w));
                 }
+                row(HR - 2, tp[HR - 2]);
+                if (half == 0) row(HR - 1, tp[HR - 1]);   // row 35 does not exist
             }
         }
         PYR_T(p4);
@@ -1010,6 +1087,35 @@ auto& next_job(std::vector<Launch>& launches) {
     return jobs.j[jobs.n++];
 }
 
+// The cv::resize column table of a fused layer of width dw0 from a frame of width W: the kernel's own float expressions
+// (k_resize_tiled's srcX), evaluated once per geometry on the host (this file is built with -ffp-contract=off)
+std::vector<int2> fused_xtab(int dw0, int W, double scale_x) {
+    std::vector<int2> xt((size_t)dw0);
+    for (int dx = 0; dx < dw0; ++dx) {
+        float fx = (float)((dx + 0.5) * scale_x - 0.5);
+        int sx = (int)floorf(fx);
+        fx -= sx;
+        if (sx < 0) { fx = 0; sx = 0; }
+        if (sx >= W - 1) { fx = 0; sx = W - 1; }
+        const int a0 = (int)nearbyintf((1.f - fx) * 2048), a1 = (int)nearbyintf(fx * 2048);
+        xt[(size_t)dx] = make_int2(sx, a0 | (a1 << 16));
+    }
+    return xt;
+}
+// the source columns of tile column tx, exactly as the kernel's addressing expects them: {X0, ncol}
+int2 fused_tile_cols(const std::vector<int2>& xt, int W, int tx) {
+    const int dw0 = (int)xt.size(), gx0 = 2 * tx * FT_W1 - 2;
+    const int cLo = std::max(0, gx0), cHi = std::min(dw0 - 1, gx0 + G0_W - 1);
+    const int X0 = xt[(size_t)cLo].x;
+    return make_int2(X0, std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1);
+}
+// every tile's source columns must fit the kernel's stage (its rows are staged per resized row: no limit there)
+bool fused_fits(const std::vector<int2>& xt, int W, int dw1) {
+    for (int tx = 0; tx * FT_W1 < dw1; ++tx)
+        if (fused_tile_cols(xt, W, tx).y > FS_PITCH) return false;
+    return true;
+}
+
 void build_plan(fd_pyramid* p, int W, int H) {
     p->plan.reset(new fd_pyramid::Plan());
     fd_pyramid::Plan& plan = *p->plan;
@@ -1042,22 +1148,8 @@ void build_plan(fd_pyramid* p, int W, int H) {
         const bool chain = k + 1 < all.size() && all[k + 1].depth == 1 && all[k + 1].chain == L.chain;
         if (chain && mode != 0 && (!L.kept || mode == 2) && L.w >= 3 && L.h >= 3 && W <= 65535 && H <= 65535) {
             const HostLayer& D = all[k + 1];
-            std::vector<int2> xt((size_t)L.w);
-            for (int dx = 0; dx < L.w; ++dx) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)floorf(fx);
-                fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx >= W - 1) { fx = 0; sx = W - 1; }
-                const int a0 = (int)nearbyintf((1.f - fx) * 2048), a1 = (int)nearbyintf(fx * 2048);
-                xt[(size_t)dx] = make_int2(sx, a0 | (a1 << 16));
-            }
-            // every tile's source columns must fit the kernel's stage (its rows are staged per resized row: no limit there)
-            bool fits = true;
-            for (int x1 = 0; x1 < D.w && fits; x1 += FT_W1) {
-                const int cLo = std::max(0, 2 * x1 - 2), cHi = std::min(L.w - 1, 2 * x1 - 2 + G0_W - 1);
-                fits = std::min(W - 1, xt[(size_t)cHi].x + 1) - xt[(size_t)cLo].x + 1 <= FS_PITCH;
-            }
+            const std::vector<int2> xt = fused_xtab(L.w, W, scale_x);
+            const bool fits = fused_fits(xt, W, D.w);
             if (fits) {
                 FusedJob& j = next_job(plan.fused);
                 j.dw0 = L.w; j.dh0 = L.h; j.dw1 = D.w; j.dh1 = D.h;
@@ -1066,14 +1158,11 @@ void build_plan(fd_pyramid* p, int W, int H) {
                 j.xtab = (uint32_t)tab.size();
                 j.scale_y = scale_y;
                 tab.insert(tab.end(), xt.begin(), xt.end());
-                // the source columns of every tile, exactly as the kernel's addressing expects them
                 tiles.resize(plan.fused.size());
                 for (int ty = 0; ty * FT_H1 < D.h; ++ty)
                     for (int tx = 0; tx * FT_W1 < D.w; ++tx) {
-                        const int gx0 = 2 * tx * FT_W1 - 2;
-                        const int cLo = std::max(0, gx0), cHi = std::min(L.w - 1, gx0 + G0_W - 1);
-                        const int X0 = xt[(size_t)cLo].x, ncol = std::min(W - 1, xt[(size_t)cHi].x + 1) - X0 + 1;
-                        tiles.back().push_back(make_int4(X0, ncol, (int)((uint32_t)tx | (uint32_t)ty << 16), plan.fused.back().jobs.n - 1));
+                        const int2 cols = fused_tile_cols(xt, W, tx);
+                        tiles.back().push_back(make_int4(cols.x, cols.y, (int)((uint32_t)tx | (uint32_t)ty << 16), plan.fused.back().jobs.n - 1));
                     }
                 fused[k] = 1;
                 continue;
@@ -1704,6 +1793,58 @@ int fd_debug_pyrdown_stage(const uint8_t* image, int sw, int sh, int tile, uint8
                     const int r = 2 * (rq + 4 * k) + (lane >> 5);
                     if (r < 2 * PD_TH + 3) std::memcpy(staged + r * 128 + 4 * (lane & 31), &v[k], 4);
                 }
+            }
+    }
+    return nt;
+}
+
+// Test hook (include/fd_hip_bench.h; needs no GPU): tile `tile` of the fused resize + pyrDown of a sw x sh image to a dw0 x dh0
+// first-octave layer as k_resize_down stages it, by the plan's own column table and tile columns and the kernel's own row, fetch,
+// interleave and addressing functions, wavefront by wavefront and lane by lane
+int fd_debug_resize_stage(const uint8_t* image, int sw, int sh, int dw0, int dh0, int tile, uint8_t* staged, int32_t* read_off, int32_t* entry) {
+    if (sw < 1 || sh < 1 || sw > 65535 || sh > 65535 || dw0 < 3 || dh0 < 3 || dw0 > sw || dh0 > sh) return -1;
+    const double scale_x = 1. / ((double)dw0 / sw), scale_y = 1. / ((double)dh0 / sh);
+    if (!(scale_x >= 1.0 && scale_x <= 2.05 && scale_y >= 1.0 && scale_y <= 2.05)) return -1;
+    const int dw1 = (dw0 + 1) / 2, dh1 = (dh0 + 1) / 2;
+    const int tilesX = (dw1 + FT_W1 - 1) / FT_W1, nt = tilesX * ((dh1 + FT_H1 - 1) / FT_H1);
+    const std::vector<int2> xt = fused_xtab(dw0, sw, scale_x);
+    if (!fused_fits(xt, sw, dw1)) return -1;
+    if (!image && !staged && !read_off && !entry) return nt;
+    if (tile < 0 || tile >= nt) return -1;
+    const int ty = tile / tilesX, tx = tile - ty * tilesX;
+    const int2 cols = fused_tile_cols(xt, sw, tx);
+    const int X0 = cols.x, ncol = cols.y, gx0 = 2 * tx * FT_W1 - 2, gy0 = 2 * ty * FT_H1 - 2;
+    if (entry) {
+        const int32_t e[8] = {X0, ncol, tx, ty, gx0, gy0, dw1, dh1};
+        std::memcpy(entry, e, sizeof(e));
+    }
+    if (staged) {
+        if (!image) return -1;
+        const size_t n = (size_t)sw * sh;
+        auto dword_at = [&](uint32_t off) {   // the kernel's unaligned dword load; what hangs over the image's end reads as 0 here
+            uint32_t w = 0;
+            for (uint32_t b = 0; b < 4; ++b)
+                if ((size_t)off + b < n) w |= (uint32_t)image[off + b] << (8 * b);
+            return w;
+        };
+        std::memset(staged, 0, (size_t)FS_SLOTS * FS_SLOT);
+        for (int wave = 0; wave < 4; ++wave)
+            for (int q = 0; q < FS_ROWS; ++q) {
+                const FusedRow r = fused_row(FS_ROWS * wave + q, gy0, dh0, scale_y, sh);   // lane q of the wavefront works the row out
+                for (int lane = 0; lane < 64; ++lane) {
+                    const uint32_t voff = fs_fetch_col(lane, X0, ncol);
+                    const uint2 pr = fs_pair(dword_at((uint32_t)r.y0 * (uint32_t)sw + voff), dword_at((uint32_t)r.y1 * (uint32_t)sw + voff));
+                    std::memcpy(staged + fs_store_off(FS_ROWS * wave + q, lane), &pr, 8);
+                }
+            }
+    }
+    if (read_off) {   // thread = column c of the tile, rows 0 .. 34 (two halves in the kernel, at the same offsets)
+        for (int r = 0; r < G0_H; ++r)
+            for (int c = 0; c < G0_W; ++c) {
+                int gx = gx0 + c;   // the kernel's reflect101
+                if (dw0 == 1) gx = 0;
+                else while (gx < 0 || gx >= dw0) gx = gx < 0 ? -gx : 2 * dw0 - 2 - gx;
+                read_off[r * G0_W + c] = fs_read_off(xt[(size_t)gx].x, X0, r);
             }
     }
     return nt;

@@ -67,6 +67,17 @@ int fd_debug_wvd_packed_plan(const int32_t* nx, const int32_t* ny, int n_layers,
  * there is no such tile. */
 int fd_debug_pyrdown_stage(const uint8_t* image, int sw, int sh, int tile, uint8_t* staged, int32_t* entry);
 
+/* Test hook, needs no GPU: tile `tile` (row-major over the 62 x 16 tiles of the pyrDown layer) of the fused cv::resize of the sw x sh
+ * 8-bit image to a dw0 x dh0 first-octave layer and its cv::pyrDown, as k_resize_down stages it in LDS, made by the launch plan's own
+ * column table and tile columns and the kernel's own row, fetch, interleave and addressing functions.  staged: 36 pair slots of 512
+ * bytes, one per resized row of the tile (slot 35 repeats row 34): byte 2 x = source column X0 + x of the row's upper source row y0,
+ * byte 2 x + 1 = the same column of its lower source row y1.  read_off[r * 127 + c], 35 x 127: the byte of the stage where the thread
+ * of tile column c reads the 16-bit pair {y0, y1} of its left source column for tile row r (resized pixel (gy0 + r, gx0 + c),
+ * BORDER_REFLECT_101); the right neighbour's pair is the next 16-bit word.  entry[8] = {X0, ncol, tx, ty, gx0, gy0, dw1, dh1}.
+ * Returns the number of tiles of the layer (image, staged, read_off, entry all NULL: only that), or -1 when there is no such tile or
+ * k_resize_down does not take such a layer. */
+int fd_debug_resize_stage(const uint8_t* image, int sw, int sh, int dw0, int dh0, int tile, uint8_t* staged, int32_t* read_off, int32_t* entry);
+
 /* Test hook: hyperplane distances of n u8 vectors through both instantiations of the u8 RBF MFMA kernel (8 and 16 wavefronts per
  * workgroup).  fd_detect_five_stage scores one frame's positives with either, depending on how many the previous frame had, and
  * relies on bit-identical sums; tests/test_gpu_cascade_hardening.py compares them.  (fd_detect_five_stage keeps per-call state in
