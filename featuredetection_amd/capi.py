@@ -277,6 +277,13 @@ _SIGS = {
                                             C.POINTER(fd_svm_train_info)]),
     "fd_ehog_tracker_get_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "fd_linear_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_linear_svm_gram_large": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_linear_svm_train_large": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_train_params), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(fd_svm_train_info)]),
+    "fd_linear_svm_train_large_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_aggregated_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "fd_aggregated_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_aggregated_set_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
     "fd_particles_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "fd_particles_destroy": (None, [C.c_void_p]),
     "fd_particles_capacity": (C.c_int, [C.c_void_p]),
@@ -1360,6 +1367,38 @@ def linear_svm_train(ctx, x, n_pos, **kw):
     return w, bias.value, alpha, _svm_info(info)
 
 
+SVM_LARGE_MAX_N = 16384   # FD_SVM_LARGE_MAX_N
+
+
+def linear_svm_train_large_limits(n_pos, n_neg, d):
+    """fd_linear_svm_train_large_limits (host only): (lds_bytes, max_iterations); FdError for sizes the large trainer refuses"""
+    b, m = C.c_int(), C.c_int()
+    rc = lib().fd_linear_svm_train_large_limits(n_pos, n_neg, d, C.byref(b), C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_linear_svm_train_large_limits: invalid sizes (%d, %d, %d)" % (n_pos, n_neg, d))
+    return b.value, m.value
+
+
+def linear_svm_gram_large(ctx, x, n_pos):
+    """linear_svm_gram for up to SVM_LARGE_MAX_N rows (fd_linear_svm_gram_large)"""
+    x = _c(x, np.float32)
+    n, d = x.shape
+    q, qd = np.zeros((n, n), np.float32), np.zeros(n, np.float64)
+    ctx.check(lib().fd_linear_svm_gram_large(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, _ptr(q), _ptr(qd)))
+    return q, qd
+
+
+def linear_svm_train_large(ctx, x, n_pos, **kw):
+    """linear_svm_train for up to SVM_LARGE_MAX_N rows (fd_linear_svm_train_large)"""
+    x = _c(x, np.float32)
+    n, d = x.shape
+    w, bias, alpha = np.zeros(d, np.float32), C.c_float(), np.zeros(n, np.float64)
+    prm, info = svm_train_params(**kw), fd_svm_train_info()
+    ctx.check(lib().fd_linear_svm_train_large(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, C.byref(prm), _ptr(w), C.byref(bias), _ptr(alpha),
+                                              C.byref(info)))
+    return w, bias.value, alpha, _svm_info(info)
+
+
 def linear_svm_train_batch(ctx, problems, **kw):
     """fd_linear_svm_train_batch over [(x, n_pos), ...]: a list of (weights, bias, alpha, info) like linear_svm_train's"""
     count = len(problems)
@@ -1501,6 +1540,34 @@ class Aggregated:
         out = np.empty((int(L["rows"]), int(L["cols"]), self.channels), np.float32)
         self.ctx.check(lib().fd_aggregated_feature_layer(self.ctx.h, self.h, int(i), _ptr(out)))
         return out
+
+    def update(self, image):
+        """AggregatedFeaturesExtractor::update: the feature layers of the image, no scores (layers(), feature_layer(), extract())"""
+        image = _c(image, np.uint8)
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        self.ctx.check(lib().fd_aggregated_update(self.ctx.h, self.h, _ptr(image), w, h, ch, 0))
+
+    def extract(self, boxes, out=None):
+        """AggregatedFeaturesExtractor::extract(Rect) for n boxes (x, y, w, h) in image pixels: (features float32 (n, window_h *
+        window_w * channels), bounds BOX_DTYPE (n,), valid bool (n,)).  Rows and bounds of invalid boxes keep what `out` (or
+        zeros) held."""
+        boxes = _c(np.asarray(boxes, np.int32).reshape(-1, 4), np.int32)
+        n = len(boxes)
+        d = self._w.size
+        feats = np.zeros((n, d), np.float32) if out is None else out
+        assert feats.dtype == np.float32 and feats.shape == (n, d) and feats.flags.c_contiguous
+        bounds, valid = np.zeros(n, BOX_DTYPE), np.zeros(n, np.uint8)
+        self.ctx.check(lib().fd_aggregated_extract(self.ctx.h, self.h, n, _ptr(boxes), _ptr(feats), 0, _ptr(bounds), _ptr(valid)))
+        return feats, bounds, valid.astype(bool)
+
+    def set_svm(self, weights, bias, threshold):
+        """replaces the linear SVM and the threshold of the handle (fd_aggregated_set_svm)"""
+        w = _c(weights, np.float32)
+        if w.shape != self._w.shape:
+            raise ValueError("weights must have shape %r" % (self._w.shape,))
+        self.ctx.check(lib().fd_aggregated_set_svm(self.ctx.h, self.h, _ptr(w), bias, threshold))
+        self._w = w
 
     def detect(self, image, cap=1 << 16, candidates=True):
         """(final detections, candidates) as BOX_DTYPE arrays (candidates None when not asked for)"""

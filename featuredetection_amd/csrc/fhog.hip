@@ -89,6 +89,7 @@ struct fd_aggregated {
     bool fpdw = false;
     fd_fpdw_params fpp{};
     int fpdwTiles = 0;                           // k_fpdw workgroups over the exact layers
+    uint64_t featureStamp = 0;                   // of its last update (0: none): a new handle at a destroyed owner's address owns nothing
     ~fd_aggregated() { if (pyr) fd_pyramid_destroy(pyr); }
 };
 
@@ -325,11 +326,30 @@ __global__ __launch_bounds__(256) void k_fhog_desc(const FhogLayerDev* __restric
     descAll[(size_t)g * d.D + f] = fhog_feature([&](int b) { return h[b]; }, n, f, d.sbins, d.ubins, d.alpha);
 }
 
+// AggregatedFeaturesExtractor::extract for a list of windows: the window_h x window_w cells of window v, D floats each, from
+// the descriptor buffer into row `row` of an n x (cells * D) matrix.  A thread per float; consecutive threads are the channels of
+// a cell, then the cells of a window row, so that reads are runs of window_w * D floats and the writes of a window are one run.
+struct AggWindowDev { int32_t cell, cols, row; };   // first cell in the descriptor buffer, cells per layer row, output row
+__global__ __launch_bounds__(256) void k_agg_gather(const AggWindowDev* __restrict__ windows, int nWindows, const float* __restrict__ desc, int D,
+                                                   int windowW, int windowCells, float* __restrict__ out) {
+    const int64_t d = (int64_t)windowCells * D;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= d * nWindows) return;
+    const int v = (int)(idx / d);
+    const int f = (int)(idx - (int64_t)v * d);
+    const int cell = f / D, c = f - cell * D;
+    const int wy = cell / windowW, wx = cell - wy * windowW;
+    const AggWindowDev W = windows[v];
+    out[(int64_t)W.row * d + f] = desc[((int64_t)W.cell + (int64_t)wy * W.cols + wx) * D + c];
+}
+
 struct FhogScratch {
     DevBuf lut, coeff, img, desc, energies, layers, grad, hist;
+    DevBuf windows, gathered;          // fd_aggregated_extract: its window list, and the rows of a call that returns them to the host
     fd_fhog_params lutFor;
     bool lutValid = false;
     const void* descOwner = nullptr;   // the fd_aggregated whose last detect's feature layers `desc` still holds
+    uint64_t descStamp = 0;            // the count of such updates on this context, as the owner recorded it
 };
 FhogScratch& scratch(fd_ctx* ctx) { return fd_scratch<FhogScratch>(ctx); }
 
@@ -775,15 +795,48 @@ static void launch_scores(fd_ctx* ctx, fd_aggregated* a, FhogScratch& S) {
     HIP_CHECK(hipGetLastError());
 }
 
-// a window with score > threshold as a candidate: computeBoundsInImagePixels (AggregatedFeaturesExtractor.cpp:121-128) through
-// the layer's x / y scales, Patch::computeCenter, rescaleWindow (AggregatedFeaturesDetector.cpp:108-112)
-static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float score, int x, int y, double scaleX, double scaleY) {
+// bounds in image pixels of the window at cell (x, y) of a layer: computeBoundsInImagePixels
+// (AggregatedFeaturesExtractor.cpp:121-128) through the layer's x / y scales
+static inline fd_box aggregated_bounds(const fd_aggregated_params& P, int x, int y, double scaleX, double scaleY) {
     const int cs = P.fhog.cell_size;
     const int bx = (int)std::round((x * cs) / scaleX), by = (int)std::round((y * cs) / scaleY);
     const int bw = (int)std::round((P.window_w * cs) / scaleX), bh = (int)std::round((P.window_h * cs) / scaleY);
-    const int cx = bx + bw / 2, cy = by + bh / 2;
-    const int rw = (int)(P.width_scale * bw), rh = (int)(P.height_scale * bh);
+    return fd_box{0.f, bx, by, bw, bh};
+}
+
+// a window with score > threshold as a candidate: its bounds, Patch::computeCenter, rescaleWindow
+// (AggregatedFeaturesDetector.cpp:108-112)
+static inline fd_box aggregated_candidate(const fd_aggregated_params& P, float score, int x, int y, double scaleX, double scaleY) {
+    const fd_box b = aggregated_bounds(P, x, y, scaleX, scaleY);
+    const int cx = b.x + b.w / 2, cy = b.y + b.h / 2;
+    const int rw = (int)(P.width_scale * b.w), rh = (int)(P.height_scale * b.h);
     return fd_box{score, cx - rw / 2, cy - rh / 2, rw, rh};
+}
+
+// AggregatedFeaturesExtractor::extract(Rect) (AggregatedFeaturesExtractor.cpp:83-119) up to the copy, in double as written: the
+// layer round(log(patchWidthPx / width) / log(inc)) (ImagePyramid::getLayer(double), ImagePyramid.cpp:307-310), the centre
+// through the layer's actual scales, truncated to cells (computePointInLayerCells), Patch::computeBounds, isPatchWithinImage.
+// false where the reference returns a null patch (and for a width < 1, whose scale factor the reference does not define).
+// layer: position in a->layers; (x, y): the window's first cell.
+static bool aggregated_resolve(const fd_aggregated* a, const int32_t* box, int& layer, int& x, int& y) {
+    const fd_aggregated_params& P = a->prm;
+    const int cs = P.fhog.cell_size;
+    if (box[2] < 1) return false;
+    const double inc = std::pow(0.5, 1. / P.octave_layer_count);
+    const double scaleFactor = (double)(P.window_w * cs) / (double)box[2];
+    const double power = std::log(scaleFactor) / std::log(inc);
+    const int index = (int)std::round(power);
+    layer = -1;
+    for (size_t i = 0; i < a->layers.size(); ++i)
+        if (a->layers[i].index == index) layer = (int)i;
+    if (layer < 0) return false;
+    const fd_aggregated_layer& L = a->layers[layer];
+    const FhogLayerDev& T = a->layerTable[a->tableOf[layer]];
+    const double cxImage = box[0] + 0.5 * box[2], cyImage = box[1] + 0.5 * box[3];
+    const int cxCells = (int)((cxImage * L.scale_x) / cs), cyCells = (int)((cyImage * L.scale_y) / cs);
+    x = cxCells - P.window_w / 2;
+    y = cyCells - P.window_h / 2;
+    return x >= 0 && y >= 0 && x + P.window_w <= T.cols && y + P.window_h <= T.rows;
 }
 
 // the image into the detector's pyramid: gray layers, or, for FPDW features, a pyramid of three frames -- the B, G and R planes of
@@ -921,11 +974,11 @@ static void aggregated_geometry(fd_ctx* ctx, fd_aggregated* a, int width, int he
     a->arenaAt = p->arena.p;
 }
 
-// One image through a handle: the pyramid (created anew when the image size changes; an approximated handle's has one layer per
-// octave), the geometry when it is stale, the features of the exact layers, for an approximated handle [channel sums -> host:
-// lambdas and factors] and k_fhog_approx, the score kernel over all layers, and the candidates.
-static void aggregated_candidates(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
-                                  std::vector<fd_box>& cand) {
+// One image into a handle's feature layers (AggregatedFeaturesExtractor::update): the pyramid (created anew when the image size
+// changes; an approximated handle's has one layer per octave), the geometry when it is stale, the features of the exact layers,
+// for an approximated handle [channel sums -> host: lambdas and factors] and k_fhog_approx.  Queued on ctx->stream; the context's
+// descriptor buffer is this handle's from here on.
+static void aggregated_update(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device) {
     const fd_aggregated_params& P = a->prm;
     const int D = a->D;
     // feature pyramid limits (AggregatedFeaturesExtractor.cpp:30-31,47-52,58-77), recomputed when the image size changes
@@ -951,7 +1004,6 @@ static void aggregated_candidates(fd_ctx* ctx, fd_aggregated* a, const uint8_t* 
     FhogScratch& S = scratch(ctx);
     if (a->layerTable.empty() || a->arenaAt != p->arena.p) aggregated_geometry(ctx, a, width, height);
     const int nExact = (int)p->kept.size(), nApprox = (int)a->approxTable.size();
-    a->scores.reserve(sizeof(float) * std::max<size_t>((size_t)a->layout.positions, 1));
     S.desc.reserve(sizeof(float) * (size_t)std::max(a->layout.cells, 1) * D);   // before the features: room for the approximated layers too
     aggregated_features(ctx, a, S, nExact, a->exactLayout);
     // factors (float)pow(s, -lambda[c]) (ImagePyramid.cpp:284; Mat *= double on CV_32F multiplies by the float)
@@ -991,11 +1043,21 @@ static void aggregated_candidates(fd_ctx* ctx, fd_aggregated* a, const uint8_t* 
                            a->dapprox.as<FhogApproxDev>(), nApprox, a->dresize.as<FhogResizeTab>(), a->dfactors.as<float>(), D, S.desc.as<float>());
         HIP_CHECK(hipGetLastError());
     }
+    S.descOwner = a;
+    a->featureStamp = ++S.descStamp;
+}
+
+// One image through a handle: its feature layers, the score kernel over all of them, and the candidates.
+static void aggregated_candidates(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device,
+                                  std::vector<fd_box>& cand) {
+    const fd_aggregated_params& P = a->prm;
+    aggregated_update(ctx, a, image, width, height, channels, is_device);
+    FhogScratch& S = scratch(ctx);
+    a->scores.reserve(sizeof(float) * std::max<size_t>((size_t)a->layout.positions, 1));
     launch_scores(ctx, a, S);
     std::vector<float> hs((size_t)a->layout.positions);
     if (!hs.empty()) HIP_CHECK(hipMemcpyAsync(hs.data(), a->scores.p, sizeof(float) * hs.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    S.descOwner = a;
     // getPositiveWindows (AggregatedFeaturesDetector.cpp:87-106) over the layers in layer order: layer, row, column
     for (size_t i = 0; i < a->layers.size(); ++i) {
         const FhogLayerDev& T = a->layerTable[a->tableOf[i]];
@@ -1028,6 +1090,78 @@ int fd_aggregated_detect(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, in
         *count = nfin;
         for (int i = 0; i < nfin && i < cap && out; ++i) out[i] = fin[i];
         if (out && nfin > cap) FD_THROW(FD_ERR_CAPACITY, "fd_aggregated_detect: %d detections, capacity %d", nfin, cap);
+    });
+}
+
+int fd_aggregated_update(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !a || !image) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_update: NULL argument");
+        if (a->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        aggregated_check_image(a, width, height, channels);
+        aggregated_update(ctx, a, image, width, height, channels, is_device);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_aggregated_extract(fd_ctx* ctx, fd_aggregated* a, int n, const int32_t* boxes, float* features, int features_on_device, fd_box* bounds,
+                          uint8_t* valid) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !a || n < 0 || (n > 0 && (!boxes || !features || !valid))) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_extract: NULL argument");
+        if (a->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+        FhogScratch& S = scratch(ctx);
+        if (S.descOwner != a || a->featureStamp != S.descStamp || a->featureStamp == 0)
+            FD_THROW(FD_ERR_RUNTIME, "fd_aggregated_extract: the feature layers of this detector's last update are gone");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        const fd_aggregated_params& P = a->prm;
+        const int D = a->D, cells = P.window_w * P.window_h;
+        const size_t d = (size_t)cells * D;
+        std::vector<AggWindowDev> wins;
+        std::vector<int> rowOf;   // output row of a gathered window
+        for (int k = 0; k < n; ++k) {
+            int layer, x, y;
+            valid[k] = aggregated_resolve(a, boxes + 4 * (size_t)k, layer, x, y) ? 1 : 0;
+            if (!valid[k]) continue;
+            const fd_aggregated_layer& L = a->layers[layer];
+            const FhogLayerDev& T = a->layerTable[a->tableOf[layer]];
+            if (bounds) bounds[k] = aggregated_bounds(P, x, y, L.scale_x, L.scale_y);
+            wins.push_back(AggWindowDev{T.cellBase + y * T.cols + x, T.cols, features_on_device ? k : (int)wins.size()});
+            rowOf.push_back(k);
+        }
+        if (wins.empty()) return;
+        const int nv = (int)wins.size();
+        S.windows.reserve(sizeof(AggWindowDev) * wins.size());
+        HIP_CHECK(hipMemcpyAsync(S.windows.p, wins.data(), sizeof(AggWindowDev) * wins.size(), hipMemcpyHostToDevice, ctx->stream));
+        float* out = features;
+        if (!features_on_device) {
+            S.gathered.reserve(sizeof(float) * d * nv);
+            out = S.gathered.as<float>();
+        }
+        const int64_t total = (int64_t)d * nv;
+        hipLaunchKernelGGL(k_agg_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, S.windows.as<AggWindowDev>(), nv,
+                           S.desc.as<float>(), D, P.window_w, cells, out);
+        HIP_CHECK(hipGetLastError());
+        if (!features_on_device) {
+            std::vector<float> rows(d * nv);
+            HIP_CHECK(hipMemcpyAsync(rows.data(), out, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            for (int v = 0; v < nv; ++v) std::memcpy(features + (size_t)rowOf[v] * d, rows.data() + (size_t)v * d, sizeof(float) * d);
+        } else {
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));   // wins is pageable host memory
+        }
+    });
+}
+
+int fd_aggregated_set_svm(fd_ctx* ctx, fd_aggregated* a, const float* weights, float bias, float threshold) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !a || !weights) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_aggregated_set_svm: NULL argument");
+        if (a->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        a->weights.assign(weights, weights + a->weights.size());
+        HIP_CHECK(hipMemcpyAsync(a->dweights.p, a->weights.data(), sizeof(float) * a->weights.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        a->prm.svm_bias = bias;
+        a->prm.score_threshold = threshold;
     });
 }
 

@@ -9,6 +9,8 @@
 //                 count and the converged flag persist in global memory between launches (the host relaunches)
 //   k_svm_finish  rho, the objective and the support-vector counts (one thread, libsvm's summation order), and the single
 //                 weight vector, one thread per dimension
+//   k_svm_smo_large, k_svm_finish_large   the same for up to 16384 examples: 1024 threads, G and a status
+//                 byte per element in LDS, alpha in memory; the arithmetic is shared with the two kernels above
 //
 // A problem is n_pos positive rows followed by n_neg negative rows, so y_i = +1 for i < n_pos and libsvm's class grouping is the
 // identity; the bound status is alpha compared with 0 and C as update_alpha_status does.
@@ -27,6 +29,12 @@ constexpr size_t SVM_LDS_BUDGET = 160 * 1024;     // LDS of one gfx950 workgroup
 constexpr int SVM_SLOT_BYTES = 512;               // the reduction slots of k_svm_smo
 constexpr int SVM_DEFAULT_LAUNCH_ITERATIONS = 16384;
 constexpr double SVM_TAU = 1e-12;
+// the large solver (fd_linear_svm_train_large)
+constexpr int SVM_LARGE_MAX_N = FD_SVM_LARGE_MAX_N;
+constexpr int SVM_LARGE_THREADS = 1024;
+constexpr int SVM_LARGE_WAVES = SVM_LARGE_THREADS / 64;
+constexpr int SVM_LARGE_U = 4;                // elements of a thread whose loads are issued together
+constexpr int SVM_LARGE_SLOT_BYTES = 1024;
 
 struct SvmProbDev {
     const float* x;            // n x d, row-major
@@ -46,6 +54,7 @@ inline size_t svm_smo_lds(int n, bool withQ) {
     const size_t np = (size_t)svm_pad(n);
     return 3 * sizeof(double) * np + SVM_SLOT_BYTES + (withQ ? sizeof(float) * np * np : 0);
 }
+inline size_t svm_large_lds(int n) { return (sizeof(double) + 1) * (size_t)svm_pad(n) + SVM_LARGE_SLOT_BYTES; }   // G, status, slots
 inline bool svm_q_in_lds(int n) { return svm_smo_lds(n, true) <= SVM_LDS_BUDGET; }
 
 // One wavefront per 16 x 16 tile of K, the whole feature length: lane (r, kq) feeds row r of both operand tiles at feature
@@ -101,6 +110,84 @@ __device__ __forceinline__ void svm_take_min(double& v, int& i, double ov, int o
     if (ov < v || (ov == v && oi > i)) { v = ov; i = oi; }
 }
 
+// The element-wise steps of Solver::Solve, shared by k_svm_smo and k_svm_smo_large.
+// i: element k in the scan that maximises -y_t G_t over I_up, the highest index among equals (:847-865); inUp: alpha_k below its
+// bound (positives) / above zero (negatives)
+__device__ __forceinline__ void svm_scan_i(int k, bool pos, bool inUp, double g, double& gmax, int& gi) {
+    if (pos) {
+        if (inUp && -g >= gmax) { gmax = -g; gi = k; }
+    } else {
+        if (inUp && g >= gmax) { gmax = g; gi = k; }
+    }
+}
+// j: element k in the scan that minimises obj_diff over I_low with grad_diff > 0, the highest index among equals; Gmax2 on the
+// way (:872-922).  inLow: alpha_k above zero (positives) / below its bound (negatives).  Qik is read only for the elements that
+// need it.
+template <typename QikF>
+__device__ __forceinline__ void svm_scan_j(int k, bool pos, bool inLow, double g, double gmax, double yi, double QDi, double QDk, QikF Qik,
+                                           double& gmax2, double& omin, int& gj) {
+    if (pos) {
+        if (inLow) {
+            const double gd = gmax + g;
+            if (g >= gmax2) gmax2 = g;
+            if (gd > 0.0) {
+                const double quad = QDi + QDk - 2.0 * yi * Qik();
+                const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
+                if (od <= omin) { gj = k; omin = od; }
+            }
+        }
+    } else {
+        if (inLow) {
+            const double gd = gmax - g;
+            if (-g >= gmax2) gmax2 = -g;
+            if (gd > 0.0) {
+                const double quad = QDi + QDk + 2.0 * yi * Qik();
+                const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
+                if (od <= omin) { gj = k; omin = od; }
+            }
+        }
+    }
+}
+// the two-variable update with its clipping (:640-734): the new alpha_i, alpha_j in ai, aj
+__device__ __forceinline__ void svm_pair_update(bool ipos, bool jpos, double Ci, double Cj, double QDi, double QDj, float Qij, double Gi, double Gj,
+                                                double& ai, double& aj) {
+    if (ipos != jpos) {
+        double quad = QDi + QDj + (double)(2.f * Qij);
+        if (quad <= 0.0) quad = SVM_TAU;
+        const double delta = (-Gi - Gj) / quad;
+        const double diff = ai - aj;
+        ai += delta;
+        aj += delta;
+        if (diff > 0.0) {
+            if (aj < 0.0) { aj = 0.0; ai = diff; }
+        } else {
+            if (ai < 0.0) { ai = 0.0; aj = -diff; }
+        }
+        if (diff > Ci - Cj) {
+            if (ai > Ci) { ai = Ci; aj = Ci - diff; }
+        } else {
+            if (aj > Cj) { aj = Cj; ai = Cj + diff; }
+        }
+    } else {
+        double quad = QDi + QDj - (double)(2.f * Qij);
+        if (quad <= 0.0) quad = SVM_TAU;
+        const double delta = (Gi - Gj) / quad;
+        const double sum = ai + aj;
+        ai -= delta;
+        aj += delta;
+        if (sum > Ci) {
+            if (ai > Ci) { ai = Ci; aj = sum - Ci; }
+        } else {
+            if (aj < 0.0) { aj = 0.0; ai = sum; }
+        }
+        if (sum > Cj) {
+            if (aj > Cj) { aj = Cj; ai = sum - Cj; }
+        } else {
+            if (ai < 0.0) { ai = 0.0; aj = sum; }
+        }
+    }
+}
+
 // Solver::Solve's loop.  Every thread owns the elements tid, tid + 256, ...; the two selections are reduced over the
 // wavefront by shuffles and over the four wavefronts through LDS slots, after which every thread holds i, j and performs the
 // two-variable update redundantly.  Three barriers per iteration: behind either selection, and between reading alpha / G of
@@ -137,14 +224,8 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
         // i: maximises -y_t G_t over I_up, the highest index among equals (:847-865)
         double gmax = -INFINITY;
         int gi = -1;
-        for (int k = tid; k < n; k += SVM_SMO_THREADS) {
-            const double a = sAlpha[k], g = sG[k];
-            if (k < n_pos) {
-                if (a < Cp && -g >= gmax) { gmax = -g; gi = k; }
-            } else {
-                if (a > 0.0 && g >= gmax) { gmax = g; gi = k; }
-            }
-        }
+        for (int k = tid; k < n; k += SVM_SMO_THREADS)
+            svm_scan_i(k, k < n_pos, k < n_pos ? sAlpha[k] < Cp : sAlpha[k] > 0.0, sG[k], gmax, gi);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) svm_take_max(gmax, gi, __shfl_xor(gmax, o, 64), __shfl_xor(gi, o, 64));
         if (lane == 0) { slotAv[wave] = gmax; slotAi[wave] = gi; }
@@ -160,30 +241,8 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
         if (i >= 0) {
             const double yi = i < n_pos ? 1.0 : -1.0, QDi = sQD[i];
             const float* __restrict__ Qi = Qbase + (size_t)i * np;
-            for (int k = tid; k < n; k += SVM_SMO_THREADS) {
-                const double a = sAlpha[k], g = sG[k];
-                if (k < n_pos) {
-                    if (a > 0.0) {
-                        const double gd = gmax + g;
-                        if (g >= gmax2) gmax2 = g;
-                        if (gd > 0.0) {
-                            const double quad = QDi + sQD[k] - 2.0 * yi * Qi[k];
-                            const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
-                            if (od <= omin) { gj = k; omin = od; }
-                        }
-                    }
-                } else {
-                    if (a < Cn) {
-                        const double gd = gmax - g;
-                        if (-g >= gmax2) gmax2 = -g;
-                        if (gd > 0.0) {
-                            const double quad = QDi + sQD[k] + 2.0 * yi * Qi[k];
-                            const double od = quad > 0.0 ? -(gd * gd) / quad : -(gd * gd) / SVM_TAU;
-                            if (od <= omin) { gj = k; omin = od; }
-                        }
-                    }
-                }
-            }
+            for (int k = tid; k < n; k += SVM_SMO_THREADS)
+                svm_scan_j(k, k < n_pos, k < n_pos ? sAlpha[k] > 0.0 : sAlpha[k] < Cn, sG[k], gmax, yi, QDi, sQD[k], [&] { return Qi[k]; }, gmax2, omin, gj);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -206,48 +265,13 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
             break;
         }
         ++iter;
-        // the two-variable update with its clipping (:640-734)
         const float* __restrict__ Qi = Qbase + (size_t)i * np;
         const float* __restrict__ Qj = Qbase + (size_t)j * np;
         const bool ipos = i < n_pos, jpos = j < n_pos;
         const double Ci = ipos ? Cp : Cn, Cj = jpos ? Cp : Cn;
         const double oldAi = sAlpha[i], oldAj = sAlpha[j], Gi = sG[i], Gj = sG[j];
         double ai = oldAi, aj = oldAj;
-        if (ipos != jpos) {
-            double quad = sQD[i] + sQD[j] + (double)(2.f * Qi[j]);
-            if (quad <= 0.0) quad = SVM_TAU;
-            const double delta = (-Gi - Gj) / quad;
-            const double diff = ai - aj;
-            ai += delta;
-            aj += delta;
-            if (diff > 0.0) {
-                if (aj < 0.0) { aj = 0.0; ai = diff; }
-            } else {
-                if (ai < 0.0) { ai = 0.0; aj = -diff; }
-            }
-            if (diff > Ci - Cj) {
-                if (ai > Ci) { ai = Ci; aj = Ci - diff; }
-            } else {
-                if (aj > Cj) { aj = Cj; ai = Cj + diff; }
-            }
-        } else {
-            double quad = sQD[i] + sQD[j] - (double)(2.f * Qi[j]);
-            if (quad <= 0.0) quad = SVM_TAU;
-            const double delta = (Gi - Gj) / quad;
-            const double sum = ai + aj;
-            ai -= delta;
-            aj += delta;
-            if (sum > Ci) {
-                if (ai > Ci) { ai = Ci; aj = sum - Ci; }
-            } else {
-                if (aj < 0.0) { aj = 0.0; ai = sum; }
-            }
-            if (sum > Cj) {
-                if (aj > Cj) { aj = Cj; ai = sum - Cj; }
-            } else {
-                if (ai < 0.0) { ai = 0.0; aj = sum; }
-            }
-        }
+        svm_pair_update(ipos, jpos, Ci, Cj, sQD[i], sQD[j], Qi[j], Gi, Gj, ai, aj);
         const double dai = ai - oldAi, daj = aj - oldAj;
         __syncthreads();   // every thread has read alpha and G of (i, j)
         if (tid == (i & (SVM_SMO_THREADS - 1))) sAlpha[i] = ai;
@@ -265,41 +289,160 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
     }
 }
 
-// rho, objective and counts by thread 0 of a problem's first block (alpha and G staged in LDS; the sums run in index order as
-// calculate_rho's and Solve's do), and w_k = sum over the support vectors, in index order, of (float)(alpha_i y_i * (double)x_ik)
-// accumulated in float (extractSupportVectors, CV_32F).  Only for a problem that is done (converged or at max_iterations).
-__global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict__ P) {
-    __shared__ double sA[SVM_MAX_N], sGf[SVM_MAX_N];
-    const SvmProbDev p = P[blockIdx.y];
-    const int tid = threadIdx.x, n = p.n, n_pos = p.n_pos;
-    const int k = blockIdx.x * 256 + tid;
-    if (!p.state[1] && p.state[0] < p.max_iter) {   // the solver goes on in the next launch: the host needs the progress only
-        if (blockIdx.x == 0 && tid == 0) {
-            fd_svm_train_info out = {};
-            out.iterations = p.state[0];
-            *p.info = out;
-        }
-        return;
-    }
-    if (k < p.d) {
-        float w = 0.f;
-        const float* __restrict__ xk = p.x + k;
-        for (int i = 0; i < n; ++i) {
-            const double a = p.alpha[i];
-            if (a > 0.0) {
-                const double coef = i < n_pos ? a : -a;
-                w += (float)(coef * (double)xk[(size_t)i * p.d]);
-            }
-        }
-        p.w[k] = w;
-    }
-    if (blockIdx.x != 0) return;
-    for (int i = tid; i < n; i += 256) {
-        sA[i] = p.alpha[i];
-        sGf[i] = p.G[i];
+// k_svm_smo for up to SVM_LARGE_MAX_N examples: one workgroup of 1024 threads per problem, thread t owns the elements t,
+// t + 1024, ... (at most 16).  G lives in LDS (8 n bytes, 128 KB at the limit) next to one status byte per element, the two set
+// memberships the selections ask of alpha (libsvm's alpha_status; 16 KB).  alpha itself stays in global memory and is touched by
+// the owners of i and j only; QD and the rows of Q are read through the cache.  The owners of i and j publish alpha and G of the
+// pair through LDS slots, so that an iteration has three barriers as in k_svm_smo: behind either selection and behind the
+// publication.  The arithmetic is k_svm_smo's.
+__global__ __launch_bounds__(SVM_LARGE_THREADS) void k_svm_smo_large(const SvmProbDev* __restrict__ P, int budget) {
+    extern __shared__ double svm_lds[];
+    const SvmProbDev p = P[blockIdx.x];
+    if (p.state[1] || p.state[0] >= p.max_iter) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = p.n, np = p.n_pad, n_pos = p.n_pos;
+    double* sG = svm_lds;
+    double* slotAv = sG + np;                          // [16] Gmax of a wavefront
+    double* slotBv = slotAv + SVM_LARGE_WAVES;         // [16] its smallest obj_diff
+    double* slotBg = slotBv + SVM_LARGE_WAVES;         // [16] its Gmax2
+    double* pub = slotBg + SVM_LARGE_WAVES;            // alpha_i, G_i, alpha_j, G_j
+    int* slotAi = (int*)(pub + 4);                     // [16]
+    int* slotBi = slotAi + SVM_LARGE_WAVES;            // [16]
+    uint8_t* sStatus = (uint8_t*)(sG + np) + SVM_LARGE_SLOT_BYTES;   // [np] bit 0: in I_up, bit 1: in I_low
+    const float* __restrict__ Q = p.Q;
+    const double* __restrict__ QD = p.QD;
+    const double Cp = p.Cp, Cn = p.Cn, eps = p.eps;
+    auto status_of = [&](int k, double a) { return (uint8_t)(k < n_pos ? (a < Cp ? 1 : 0) | (a > 0.0 ? 2 : 0) : (a > 0.0 ? 1 : 0) | (a < Cn ? 2 : 0)); };
+    for (int k = tid; k < n; k += SVM_LARGE_THREADS) {
+        sG[k] = p.G[k];
+        sStatus[k] = status_of(k, p.alpha[k]);
     }
     __syncthreads();
-    if (tid != 0) return;
+    int iter = p.state[0];
+    int converged = 0;
+    for (int it = 0; it < budget; ++it) {
+        if (iter >= p.max_iter) break;
+        double gmax = -INFINITY;
+        int gi = -1;
+        for (int k = tid; k < n; k += SVM_LARGE_THREADS) svm_scan_i(k, k < n_pos, (sStatus[k] & 1) != 0, sG[k], gmax, gi);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) svm_take_max(gmax, gi, __shfl_xor(gmax, o, 64), __shfl_xor(gi, o, 64));
+        if (lane == 0) { slotAv[wave] = gmax; slotAi[wave] = gi; }
+        __syncthreads();
+        gmax = slotAv[0];
+        gi = slotAi[0];
+#pragma unroll
+        for (int w = 1; w < SVM_LARGE_WAVES; ++w) svm_take_max(gmax, gi, slotAv[w], slotAi[w]);
+        const int i = gi;
+        double gmax2 = -INFINITY, omin = INFINITY;
+        int gj = -1;
+        if (i >= 0) {
+            const double yi = i < n_pos ? 1.0 : -1.0, QDi = QD[i];
+            const float* __restrict__ Qi = Q + (size_t)i * np;
+            if ((i & (SVM_LARGE_THREADS - 1)) == tid) { pub[0] = p.alpha[i]; pub[1] = sG[i]; }
+            for (int k0 = tid; k0 < n; k0 += SVM_LARGE_U * SVM_LARGE_THREADS) {
+                float qi[SVM_LARGE_U];
+                double qd[SVM_LARGE_U];
+#pragma unroll
+                for (int u = 0; u < SVM_LARGE_U; ++u) {   // the loads of a step, in flight together (in-range address for the masked lanes)
+                    const int k = k0 + u * SVM_LARGE_THREADS, kc = k < n ? k : 0;
+                    qi[u] = Qi[kc];
+                    qd[u] = QD[kc];
+                }
+#pragma unroll
+                for (int u = 0; u < SVM_LARGE_U; ++u) {
+                    const int k = k0 + u * SVM_LARGE_THREADS;
+                    if (k < n) svm_scan_j(k, k < n_pos, (sStatus[k] & 2) != 0, sG[k], gmax, yi, QDi, qd[u], [&] { return qi[u]; }, gmax2, omin, gj);
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            svm_take_min(omin, gj, __shfl_xor(omin, o, 64), __shfl_xor(gj, o, 64));
+            gmax2 = fmax(gmax2, __shfl_xor(gmax2, o, 64));
+        }
+        if (lane == 0) { slotBv[wave] = omin; slotBi[wave] = gj; slotBg[wave] = gmax2; }
+        __syncthreads();
+        omin = slotBv[0];
+        gj = slotBi[0];
+        gmax2 = slotBg[0];
+#pragma unroll
+        for (int w = 1; w < SVM_LARGE_WAVES; ++w) {
+            svm_take_min(omin, gj, slotBv[w], slotBi[w]);
+            gmax2 = fmax(gmax2, slotBg[w]);
+        }
+        const int j = gj;
+        if (gmax + gmax2 < eps || i < 0 || j < 0) {
+            converged = 1;
+            break;
+        }
+        ++iter;
+        const float* __restrict__ Qi = Q + (size_t)i * np;
+        const float* __restrict__ Qj = Q + (size_t)j * np;
+        const float Qij = Qi[j];
+        const double QDi = QD[i], QDj = QD[j];
+        if ((j & (SVM_LARGE_THREADS - 1)) == tid) { pub[2] = p.alpha[j]; pub[3] = sG[j]; }
+        __syncthreads();   // the pair's alpha and G are published; nobody writes G before everybody holds them
+        const bool ipos = i < n_pos, jpos = j < n_pos;
+        const double Ci = ipos ? Cp : Cn, Cj = jpos ? Cp : Cn;
+        const double oldAi = pub[0], Gi = pub[1], oldAj = pub[2], Gj = pub[3];
+        double ai = oldAi, aj = oldAj;
+        svm_pair_update(ipos, jpos, Ci, Cj, QDi, QDj, Qij, Gi, Gj, ai, aj);
+        const double dai = ai - oldAi, daj = aj - oldAj;
+        if ((i & (SVM_LARGE_THREADS - 1)) == tid) { p.alpha[i] = ai; sStatus[i] = status_of(i, ai); }
+        if ((j & (SVM_LARGE_THREADS - 1)) == tid) { p.alpha[j] = aj; sStatus[j] = status_of(j, aj); }
+        for (int k0 = tid; k0 < n; k0 += SVM_LARGE_U * SVM_LARGE_THREADS) {
+            float qi[SVM_LARGE_U], qj[SVM_LARGE_U];
+#pragma unroll
+            for (int u = 0; u < SVM_LARGE_U; ++u) {
+                const int k = k0 + u * SVM_LARGE_THREADS, kc = k < n ? k : 0;
+                qi[u] = Qi[kc];
+                qj[u] = Qj[kc];
+            }
+#pragma unroll
+            for (int u = 0; u < SVM_LARGE_U; ++u) {
+                const int k = k0 + u * SVM_LARGE_THREADS;
+                if (k < n) sG[k] += (double)qi[u] * dai + (double)qj[u] * daj;   // (:741-744)
+            }
+        }
+    }
+    // a thread's last writes to G are its own elements; alpha is in memory already
+    for (int k = tid; k < n; k += SVM_LARGE_THREADS) p.G[k] = sG[k];
+    if (tid == 0) {
+        p.state[0] = iter;
+        p.state[1] = converged;
+    }
+}
+
+// The pieces of k_svm_finish and k_svm_finish_large.  Only for a problem that is done (converged or at max_iterations); for one
+// that the solver goes on with in the next launch the host needs the progress only.
+__device__ __forceinline__ bool svm_finish_pending(const SvmProbDev& p, bool first) {
+    if (p.state[1] || p.state[0] >= p.max_iter) return false;
+    if (first) {
+        fd_svm_train_info out = {};
+        out.iterations = p.state[0];
+        *p.info = out;
+    }
+    return true;
+}
+// w_k = sum over the support vectors, in index order, of (float)(alpha_i y_i * (double)x_ik) accumulated in float
+// (extractSupportVectors, CV_32F)
+__device__ __forceinline__ void svm_finish_weight(const SvmProbDev& p, int k) {
+    if (k >= p.d) return;
+    float w = 0.f;
+    const float* __restrict__ xk = p.x + k;
+    for (int i = 0; i < p.n; ++i) {
+        const double a = p.alpha[i];
+        if (a > 0.0) {
+            const double coef = i < p.n_pos ? a : -a;
+            w += (float)(coef * (double)xk[(size_t)i * p.d]);
+        }
+    }
+    p.w[k] = w;
+}
+// rho, the objective and the counts by one thread; the sums run in index order as calculate_rho's and Solve's do
+__device__ __forceinline__ void svm_finish_info(const SvmProbDev& p, const double* sA, const double* sGf) {
+    const int n = p.n, n_pos = p.n_pos;
     double ub = INFINITY, lb = -INFINITY, sumFree = 0.0, obj = 0.0;
     int nFree = 0, nSv = 0, nBounded = 0;
     for (int i = 0; i < n; ++i) {
@@ -333,13 +476,40 @@ __global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict
     *p.info = out;
 }
 
+// rho, objective and counts by thread 0 of a problem's first block (alpha and G staged in LDS), and the single weight vector,
+// one thread per dimension
+__global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict__ P) {
+    __shared__ double sA[SVM_MAX_N], sGf[SVM_MAX_N];
+    const SvmProbDev p = P[blockIdx.y];
+    const int tid = threadIdx.x, n = p.n;
+    if (svm_finish_pending(p, blockIdx.x == 0 && tid == 0)) return;
+    svm_finish_weight(p, blockIdx.x * 256 + tid);
+    if (blockIdx.x != 0) return;
+    for (int i = tid; i < n; i += 256) {
+        sA[i] = p.alpha[i];
+        sGf[i] = p.G[i];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    svm_finish_info(p, sA, sGf);
+}
+
+// the same for a problem of k_svm_smo_large: the one thread reads alpha and G from memory
+__global__ __launch_bounds__(256) void k_svm_finish_large(const SvmProbDev* __restrict__ P) {
+    const SvmProbDev p = P[blockIdx.y];
+    const int tid = threadIdx.x;
+    if (svm_finish_pending(p, blockIdx.x == 0 && tid == 0)) return;
+    svm_finish_weight(p, blockIdx.x * 256 + tid);
+    if (blockIdx.x == 0 && tid == 0) svm_finish_info(p, p.alpha, p.G);
+}
+
 struct SvmTrainScratch {
     DevBuf x, q, dbl, w, desc, info, state;
 };
 
-void svm_check_shape(const char* who, int n_pos, int n_neg, int d) {
+void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN = SVM_MAX_N) {
     if (n_pos < 1 || n_neg < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
-    if ((int64_t)n_pos + n_neg > SVM_MAX_N) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, SVM_MAX_N);
+    if ((int64_t)n_pos + n_neg > maxN) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, maxN);
     if (d < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the feature length must be positive (%d)", who, d);
 }
 
@@ -370,13 +540,14 @@ struct SvmRun {
 };
 
 // wOverride: device buffer that receives problem 0's weights in place of the scratch (the tracker's dweights)
+// large: the problems of fd_linear_svm_train_large (up to SVM_LARGE_MAX_N examples, Q always in memory)
 void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params& prm, float* wOverride,
-                 SvmRun& run) {
+                 SvmRun& run, bool large = false) {
     SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
     size_t xBytes = 0, qBytes = 0, dblBytes = 0, wBytes = 0, outBytes = 0;
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
-        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d);
+        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, large ? SVM_LARGE_MAX_N : SVM_MAX_N);
         if (!pr.x) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
         const size_t n = (size_t)pr.n_pos + pr.n_neg, np = (size_t)svm_pad((int)n);
         if (!pr.is_device) xBytes += svm_align(sizeof(float) * n * pr.d);
@@ -386,7 +557,11 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
         outBytes += svm_align(sizeof(float) * pr.d) + svm_align(sizeof(double) * np);
     }
     sc.x.reserve(xBytes);
-    sc.q.reserve(qBytes);
+    try {
+        sc.q.reserve(qBytes);
+    } catch (const FdError& e) {   // up to 1 GiB for a large problem: the caller learns what did not fit
+        FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for Q (%zu bytes): %s", who, qBytes, e.msg.c_str());
+    }
     sc.dbl.reserve(dblBytes);
     sc.w.reserve(wBytes);
     sc.desc.reserve(sizeof(SvmProbDev) * count);
@@ -433,12 +608,12 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
         D.n = n;
         D.n_pad = np;
         D.d = pr.d;
-        D.q_in_lds = svm_q_in_lds(n) ? 1 : 0;
+        D.q_in_lds = !large && svm_q_in_lds(n) ? 1 : 0;
         D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : std::max(10000000, 100 * n);
         hd[c] = D;
         run.maxPad = std::max(run.maxPad, np);
         run.maxD = std::max(run.maxD, pr.d);
-        run.smoLds = std::max(run.smoLds, svm_smo_lds(n, D.q_in_lds != 0));
+        run.smoLds = std::max(run.smoLds, large ? svm_large_lds(n) : svm_smo_lds(n, D.q_in_lds != 0));
     }
     if (xBytes) HIP_CHECK(hipMemcpyAsync(sc.x.p, run.pinned + xOff, xBytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(sc.desc.p, hd, sizeof(SvmProbDev) * count, hipMemcpyHostToDevice, ctx->stream));
@@ -447,27 +622,30 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
     HIP_CHECK(hipGetLastError());
 }
 
-}  // namespace
-
 // Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Problem 0's weights go to wOverride
-// (device) when given.  Leaves ctx->stream synchronised.
-void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
-                      fd_svm_train_info* infos) {
+// (device) when given.  Leaves ctx->stream synchronised.  large: one problem of up to SVM_LARGE_MAX_N examples on k_svm_smo_large.
+void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+                   fd_svm_train_info* infos, bool large) {
     const fd_svm_train_params prm = svm_checked_params(who, params);
     if (count < 1 || !probs || !infos) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument or no problem", who);
     HIP_CHECK(hipSetDevice(ctx->device));
     SvmRun run;
-    svm_prepare(ctx, who, count, probs, prm, wOverride, run);
+    svm_prepare(ctx, who, count, probs, prm, wOverride, run, large);
     SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
-    static uint64_t ldsAllowed = 0;
-    fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
+    static uint64_t ldsAllowed = 0, ldsAllowedLarge = 0;
+    if (large) fd_allow_lds(ctx, (const void*)k_svm_smo_large, (int)SVM_LDS_BUDGET, ldsAllowedLarge);
+    else fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
     const fd_svm_train_info* hinfo = (const fd_svm_train_info*)(run.pinned + run.infoOff);
     int launches = 0;
     for (;;) {
-        hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
+        if (large)
+            hipLaunchKernelGGL(k_svm_smo_large, dim3(count), dim3(SVM_LARGE_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
+        else
+            hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
         HIP_CHECK(hipGetLastError());
         ++launches;
-        hipLaunchKernelGGL(k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        hipLaunchKernelGGL(large ? k_svm_finish_large : k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream,
+                           sc.desc.as<SvmProbDev>());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(run.pinned + run.infoOff, sc.info.p, sizeof(fd_svm_train_info) * count, hipMemcpyDeviceToHost, ctx->stream));
         // the results ride along: in the usual case the first launch converges and this is the only wait
@@ -492,6 +670,42 @@ void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_trai
     }
 }
 
+void svm_gram(fd_ctx* ctx, const char* who, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD, bool large) {
+    HIP_CHECK(hipSetDevice(ctx->device));
+    fd_svm_train_problem pr = {};
+    pr.x = x;
+    pr.n_pos = n_pos;
+    pr.n_neg = n_neg;
+    pr.d = d;
+    pr.is_device = is_device;
+    fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
+    SvmRun run;
+    svm_prepare(ctx, who, 1, &pr, prm, nullptr, run, large);
+    const SvmProbDev& D = run.h[0];
+    HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+fd_svm_train_problem svm_single_problem(const float* x, int n_pos, int n_neg, int d, int is_device, float* weights, float* bias, double* alpha) {
+    fd_svm_train_problem pr = {};
+    pr.x = x;
+    pr.n_pos = n_pos;
+    pr.n_neg = n_neg;
+    pr.d = d;
+    pr.is_device = is_device;
+    pr.weights = weights;
+    pr.bias = bias;
+    pr.alpha = alpha;
+    return pr;
+}
+}  // namespace
+
+void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+                      fd_svm_train_info* infos) {
+    svm_train_run(ctx, who, count, probs, params, wOverride, infos, false);
+}
+
 extern "C" {
 
 int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations) {
@@ -502,23 +716,25 @@ int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* 
     return FD_OK;
 }
 
+int fd_linear_svm_train_large_limits(int n_pos, int n_neg, int d, int* lds_bytes, int* max_iterations) {
+    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_LARGE_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    const int n = n_pos + n_neg;
+    if (lds_bytes) *lds_bytes = (int)svm_large_lds(n);
+    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    return FD_OK;
+}
+
 int fd_linear_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
     return fd_guard(ctx, [&] {
         if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_gram: NULL argument");
-        HIP_CHECK(hipSetDevice(ctx->device));
-        fd_svm_train_problem pr = {};
-        pr.x = x;
-        pr.n_pos = n_pos;
-        pr.n_neg = n_neg;
-        pr.d = d;
-        pr.is_device = is_device;
-        fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
-        SvmRun run;
-        svm_prepare(ctx, "fd_linear_svm_gram", 1, &pr, prm, nullptr, run);
-        const SvmProbDev& D = run.h[0];
-        HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        svm_gram(ctx, "fd_linear_svm_gram", x, n_pos, n_neg, d, is_device, Q, QD, false);
+    });
+}
+
+int fd_linear_svm_gram_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_gram_large: NULL argument");
+        svm_gram(ctx, "fd_linear_svm_gram_large", x, n_pos, n_neg, d, is_device, Q, QD, true);
     });
 }
 
@@ -526,16 +742,17 @@ int fd_linear_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d
                         float* bias, double* alpha, fd_svm_train_info* info) {
     return fd_guard(ctx, [&] {
         if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train: NULL argument");
-        fd_svm_train_problem pr = {};
-        pr.x = x;
-        pr.n_pos = n_pos;
-        pr.n_neg = n_neg;
-        pr.d = d;
-        pr.is_device = is_device;
-        pr.weights = weights;
-        pr.bias = bias;
-        pr.alpha = alpha;
-        fd_svm_train_run(ctx, "fd_linear_svm_train", 1, &pr, params, nullptr, info);
+        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, weights, bias, alpha);
+        svm_train_run(ctx, "fd_linear_svm_train", 1, &pr, params, nullptr, info, false);
+    });
+}
+
+int fd_linear_svm_train_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params,
+                              float* weights, float* bias, double* alpha, fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_large: NULL argument");
+        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, weights, bias, alpha);
+        svm_train_run(ctx, "fd_linear_svm_train_large", 1, &pr, params, nullptr, info, true);
     });
 }
 

@@ -436,7 +436,8 @@ private:
 }  // namespace classification
 
 // libsvm/LibSvmClassifier.hpp / .cpp:33-224 -- the binary C-SVC with a LinearKernel on continuous CV_32F examples, trained on the
-// device by fd_linear_svm_train (include/fd_hip.h): the model libsvm's svm_train gives.  Any other kernel or example depth,
+// device by fd_linear_svm_train (include/fd_hip.h; more than 1024 examples: fd_linear_svm_train_large, up to 16384, beyond that
+// std::runtime_error): the model libsvm's svm_train gives.  Any other kernel or example depth,
 // one-class SVMs, probabilistic output (libsvm's own sigmoid fit) and static negatives throw std::invalid_argument.
 namespace libsvm {
 
@@ -474,6 +475,8 @@ public:
     // not in the reference: what the last training ran with and returned (weights of compensateImbalance, iterations, rho, ...)
     const fd_svm_train_params& getLastTrainingParameters() const { return lastParams; }
     const fd_svm_train_info& getLastTrainingInfo() const { return lastInfo; }
+    int getLastPositiveCount() const { return lastPositiveCount; }   // examples of the last training
+    int getLastNegativeCount() const { return lastNegativeCount; }
     // not in the reference: train on this tracker handle (fd_ehog_tracker_train_svm) -- the weight vector is written into the handle's
     // device weights and its heat pyramid follows; the classifier object receives w and rho from the handle's host copy.  nullptr:
     // back to fd_linear_svm_train.  The handle must outlive its use here (ExtendedHogBasedMeasurementModel sets and clears it).
@@ -495,6 +498,7 @@ private:
     int targetDimensions = 0;
     fd_svm_train_params lastParams = {};
     fd_svm_train_info lastInfo = {};
+    int lastPositiveCount = 0, lastNegativeCount = 0;
 };
 
 }  // namespace libsvm

@@ -25,6 +25,7 @@
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
 #define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
+#define CV_32FC(n) CV_MAKETYPE(CV_32F, (n))
 #define CV_32SC1 CV_MAKETYPE(CV_32S, 1)
 
 namespace cv {
@@ -61,6 +62,12 @@ template <class T> struct Rect_ {
     T area() const { return width * height; }
 };
 typedef Rect_<int> Rect;
+// intersection; empty rectangles are all zero
+template <class T> static inline Rect_<T> operator&(const Rect_<T>& a, const Rect_<T>& b) {
+    const T x1 = a.x > b.x ? a.x : b.x, y1 = a.y > b.y ? a.y : b.y;
+    const T x2 = a.x + a.width < b.x + b.width ? a.x + a.width : b.x + b.width, y2 = a.y + a.height < b.y + b.height ? a.y + a.height : b.y + b.height;
+    return x2 > x1 && y2 > y1 ? Rect_<T>(x1, y1, x2 - x1, y2 - y1) : Rect_<T>();
+}
 
 static inline int cvRound(double v);
 
@@ -121,6 +128,19 @@ private:
 };
 
 static inline int cvRound(double v) { return (int)__builtin_lrint(v); }
+
+// cv::flip with flipCode 1: around the vertical axis (the columns in reverse order); any element size
+static inline void flip(const Mat& src, Mat& dst, int flipCode) {
+    if (flipCode != 1) throw std::invalid_argument("cv::flip: only flipCode 1 (horizontal) is available");
+    Mat out(src.rows, src.cols, src.type());
+    const size_t es = src.elemSize();
+    for (int r = 0; r < src.rows; ++r) {
+        const uchar* in = src.ptr<uchar>(r);
+        uchar* o = out.ptr<uchar>(r);
+        for (int c = 0; c < src.cols; ++c) std::memcpy(o + (size_t)c * es, in + (size_t)(src.cols - 1 - c) * es, es);
+    }
+    dst = out;
+}
 
 }  // namespace cv
 #endif

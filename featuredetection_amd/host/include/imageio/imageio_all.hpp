@@ -37,6 +37,22 @@ private:
     float x, y, z;
 };
 
+// RectLandmark.hpp / RectLandmark.cpp:22-40: a rectangle given by its centre and size in float (Landmark::getRect, Landmark.hpp:76-78)
+class RectLandmark : public Landmark {
+public:
+    explicit RectLandmark(const std::string& name) : Landmark(name, false), x(0), y(0), width(0), height(0) {}
+    RectLandmark(const std::string& name, float x, float y, float width, float height) : Landmark(name, true), x(x), y(y), width(width), height(height) {}
+    RectLandmark(const std::string& name, const cv::Rect& rect)
+        : Landmark(name, true), x(rect.x + 0.5f * rect.width), y(rect.y + 0.5f * rect.height), width((float)rect.width), height((float)rect.height) {}
+    float getX() const override { return x; }
+    float getY() const override { return y; }
+    float getWidth() const { return width; }
+    float getHeight() const { return height; }
+    cv::Rect_<float> getRect() const { return cv::Rect_<float>(x - 0.5f * width, y - 0.5f * height, width, height); }
+private:
+    float x, y, width, height;
+};
+
 // LandmarkCollection.hpp:30-90
 class LandmarkCollection {
 public:

@@ -13,6 +13,8 @@
 #include "fdcompat/cv.hpp"
 #include "fdcompat/runtime.hpp"
 
+namespace classification { class SvmClassifier; }
+
 namespace imageprocessing {
 
 // Version.hpp:18-46 -- (instance id, counter) pair used to avoid rebuilding pyramids
@@ -733,23 +735,54 @@ public:
 };
 }  // namespace filtering
 
-// extraction/AggregatedFeaturesExtractor.hpp:27-146 / AggregatedFeaturesExtractor.cpp:23-32: the feature-pyramid form.  On this
-// backend the feature pyramid must be an approximated one (ImagePyramid::createApproximated) with a GrayscaleFilter image filter
-// and a filtering::FhogFilter layer filter, and the minimum scale factor must be adjusted per image; the extractor is then the
-// argument of AggregatedFeaturesDetector's extractor constructor, which runs it on the device.
+// extraction/AggregatedFeaturesExtractor.hpp:27-146 / AggregatedFeaturesExtractor.cpp:23-130.  The feature pyramid lives on the
+// device in an fd_aggregated handle (include/fd_hip.h) the extractor creates with its first update.  Feature-pyramid form: the
+// pyramid must be an approximated one (ImagePyramid::createApproximated) with a GrayscaleFilter image filter and a
+// filtering::FhogFilter layer filter, or no image filter and the FPDW chain, and the minimum scale factor must be adjusted per
+// image; such an extractor is also the argument of AggregatedFeaturesDetector's extractor constructor.  Filter forms (.cpp:34-46):
+// an exact feature pyramid with octaveLayerCount layers per octave, for the layer filters this backend runs on the device --
+// (GrayscaleFilter, filtering::FhogFilter), a filtering::FhogFilter alone (gray images only), or
+// ChainedFilter(filtering::FpdwFeaturesFilter, filtering::AggregationFilter) alone; anything else is a logic_error.
 namespace extraction {
 class AggregatedFeaturesExtractor {
 public:
     AggregatedFeaturesExtractor(std::shared_ptr<ImagePyramid> featurePyramid, cv::Size patchSizeInCells, int cellSizeInPixels,
                                 bool adjustMinScaleFactor, int minPatchWidthInPixels = 0);
-    std::shared_ptr<ImagePyramid> getFeaturePyramid() { return featurePyramid; }
+    AggregatedFeaturesExtractor(std::shared_ptr<ImageFilter> layerFilter, cv::Size patchSizeInCells, int cellSizeInPixels, int octaveLayerCount,
+                                int minPatchWidthInPixels = 0);
+    AggregatedFeaturesExtractor(std::shared_ptr<ImageFilter> imageFilter, std::shared_ptr<ImageFilter> layerFilter, cv::Size patchSizeInCells,
+                                int cellSizeInPixels, int octaveLayerCount, int minPatchWidthInPixels = 0);
+    ~AggregatedFeaturesExtractor();
+    AggregatedFeaturesExtractor(const AggregatedFeaturesExtractor&) = delete;
+    AggregatedFeaturesExtractor& operator=(const AggregatedFeaturesExtractor&) = delete;
+    std::shared_ptr<ImagePyramid> getFeaturePyramid() { return featurePyramid; }   // null for the filter forms
     cv::Size getPatchSizeInCells() const { return patchSizeInCells; }
     int getCellSizeInPixels() const { return cellSizeInPixels; }
     int getMinPatchWidthInPixels() const { return minPatchWidthInPixels; }
+    int getOctaveLayerCount() const { return octaveLayerCount; }
+    int getChannelCount() const { return channels; }
+    // the feature layers of the image (fd_aggregated_update)
+    void update(const cv::Mat& image) { update(std::make_shared<VersionedImage>(image)); }
+    void update(std::shared_ptr<VersionedImage> image);
+    // the patch of a box in image pixels: data is a patchSizeInCells CV_32FC(channels) Mat, the bounds are those of the cells in
+    // image pixels; null where the reference returns null (fd_aggregated_extract)
+    std::shared_ptr<Patch> extract(int centerX, int centerY, int width, int height) const;
+    std::shared_ptr<Patch> extract(cv::Rect bounds) const;
+    // not in the reference: all boxes of an image in one launch; result k is extract(bounds[k])
+    std::vector<std::shared_ptr<Patch>> extract(const std::vector<cv::Rect>& bounds) const;
+    // not in the reference: the windows of the current image whose score under the SVM exceeds `threshold`, before any non-maximum
+    // suppression, in layer / row / column order -- what AggregatedFeaturesDetector(extractor, svm, NonMaximumSuppression(1.0))
+    // ::detect(image) returns.  Installs the model in the extractor's handle (fd_aggregated_set_svm); its feature layers stay valid.
+    std::vector<std::pair<cv::Rect, float>> detectWindows(const classification::SvmClassifier& svm, float threshold);
+    fd_aggregated* native() const { return handle; }
 private:
+    void init(const ImageFilter* imageFilter, const ImageFilter* layerFilter);
     std::shared_ptr<ImagePyramid> featurePyramid;
     cv::Size patchSizeInCells;
-    int cellSizeInPixels, minPatchWidthInPixels;
+    int cellSizeInPixels, minPatchWidthInPixels, octaveLayerCount = 0, channels = 0;
+    bool grayOnly = false, colorOnly = false;   // image types the filters accept
+    fd_aggregated* handle = nullptr;
+    cv::Mat image;                              // of the last update
 };
 }  // namespace extraction
 

@@ -1620,8 +1620,17 @@ bool LibSvmClassifier::retrain(const vector<Mat>& newPositiveExamples, const vec
         check(fd_ehog_tracker_train_svm(context(), trainingTarget, x.data(), positiveCount, negativeCount, &params, &info));
         check(fd_ehog_tracker_get_svm(context(), trainingTarget, weights.data(), &bias));
     } else {
-        check(fd_linear_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &params, weights.data(), &bias, nullptr, &info));
+        const int64_t count = (int64_t)positiveCount + negativeCount;
+        if (count > FD_SVM_LARGE_MAX_N)
+            throw std::runtime_error("LibSvmClassifier: " + std::to_string(count) + " training examples, at most " + std::to_string(FD_SVM_LARGE_MAX_N) +
+                                     " are trained on this backend (DetectorTrainer: bound the negatives with TrainingParams::maxNegatives)");
+        if (count > 1024)   // beyond the tracker-sized trainer: the large entry point, the same model
+            check(fd_linear_svm_train_large(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &params, weights.data(), &bias, nullptr, &info));
+        else
+            check(fd_linear_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &params, weights.data(), &bias, nullptr, &info));
     }
+    lastPositiveCount = positiveCount;
+    lastNegativeCount = negativeCount;
     setTrained(weights, params, info);
     return usable;
 }
@@ -1680,6 +1689,9 @@ vector<Detection> NonMaximumSuppression::eliminateRedundantDetections(vector<Det
 
 }  // namespace detection
 namespace imageprocessing { namespace extraction {
+static const char* const kExtractorFilters =
+    "AggregatedFeaturesExtractor: this backend needs a GrayscaleFilter image filter and a filtering::FhogFilter layer filter, a "
+    "filtering::FhogFilter alone (gray images), or ChainedFilter(filtering::FpdwFeaturesFilter, filtering::AggregationFilter) alone";
 AggregatedFeaturesExtractor::AggregatedFeaturesExtractor(shared_ptr<ImagePyramid> featurePyramid, cv::Size patchSizeInCells, int cellSizeInPixels,
                                                          bool adjustMinScaleFactor, int minPatchWidthInPixels)
     : featurePyramid(featurePyramid), patchSizeInCells(patchSizeInCells), cellSizeInPixels(cellSizeInPixels),
@@ -1687,11 +1699,130 @@ AggregatedFeaturesExtractor::AggregatedFeaturesExtractor(shared_ptr<ImagePyramid
     if (!featurePyramid) throw std::invalid_argument("AggregatedFeaturesExtractor: the feature pyramid must not be null");
     if (!featurePyramid->isApproximated())
         throw std::logic_error("AggregatedFeaturesExtractor: on this backend the feature pyramid must come from ImagePyramid::createApproximated "
-                               "(exact feature pyramids: AggregatedFeaturesDetector's filter constructors)");
+                               "(exact feature pyramids: the filter constructors)");
     if (!adjustMinScaleFactor)
         throw std::logic_error("AggregatedFeaturesExtractor: a fixed minimum scale factor is not available on this backend (adjustMinScaleFactor)");
     if (patchSizeInCells.width < 1 || patchSizeInCells.height < 1 || cellSizeInPixels < 1)
         throw std::invalid_argument("AggregatedFeaturesExtractor: patch and cell sizes must be positive");
+    octaveLayerCount = (int)featurePyramid->getOctaveLayerCount();
+}
+AggregatedFeaturesExtractor::AggregatedFeaturesExtractor(shared_ptr<ImageFilter> layerFilter, cv::Size patchSizeInCells, int cellSizeInPixels,
+                                                         int octaveLayerCount, int minPatchWidthInPixels)
+    : patchSizeInCells(patchSizeInCells), cellSizeInPixels(cellSizeInPixels), minPatchWidthInPixels(minPatchWidthInPixels),
+      octaveLayerCount(octaveLayerCount) {
+    init(nullptr, layerFilter.get());
+}
+AggregatedFeaturesExtractor::AggregatedFeaturesExtractor(shared_ptr<ImageFilter> imageFilter, shared_ptr<ImageFilter> layerFilter,
+                                                         cv::Size patchSizeInCells, int cellSizeInPixels, int octaveLayerCount,
+                                                         int minPatchWidthInPixels)
+    : patchSizeInCells(patchSizeInCells), cellSizeInPixels(cellSizeInPixels), minPatchWidthInPixels(minPatchWidthInPixels),
+      octaveLayerCount(octaveLayerCount) {
+    if (!imageFilter) throw std::invalid_argument("AggregatedFeaturesExtractor: the image filter must not be null");
+    init(imageFilter.get(), layerFilter.get());
+}
+AggregatedFeaturesExtractor::~AggregatedFeaturesExtractor() { if (handle) fd_aggregated_destroy(handle); }
+
+// the handle of the filter forms (an exact feature pyramid); the model is a placeholder until detectWindows installs one
+static fd_aggregated* create_extractor_handle(const filtering::FhogFilter* fhog, const fd_fpdw_params* fpdw, cv::Size patch, int cell, int octaveLayers,
+                                              int minPatchWidth, const vector<double>* lambdas, int channels) {
+    fd_aggregated_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    if (fpdw) prm.fhog.cell_size = fpdw->cell_size;
+    else prm.fhog = fd_fhog_params{fhog->cellSize, fhog->unsignedBinCount, fhog->interpolateBins, fhog->interpolateCells, fhog->alpha};
+    if (prm.fhog.cell_size != cell) throw std::invalid_argument("AggregatedFeaturesExtractor: cellSizeInPixels differs from the layer filter's");
+    prm.window_w = patch.width; prm.window_h = patch.height; prm.octave_layer_count = octaveLayers;
+    prm.min_window_width = minPatchWidth; prm.width_scale = 1.f; prm.height_scale = 1.f;
+    const vector<float> zeros((size_t)patch.width * patch.height * channels, 0.f);
+    prm.svm_weights = zeros.data();
+    prm.nms_overlap_threshold = 1.0;   // NonMaximumSuppression(1.0): no suppression
+    fd_aggregated* handle = nullptr;
+    if (fpdw) check(fd_aggregated_create_fpdw(context(), &prm, fpdw, lambdas != nullptr, lambdas ? lambdas->data() : nullptr,
+                                              lambdas ? (int)lambdas->size() : 0, &handle));
+    else if (lambdas) check(fd_aggregated_create_approximated(context(), &prm, lambdas->data(), (int)lambdas->size(), &handle));
+    else check(fd_aggregated_create(context(), &prm, &handle));
+    return handle;
+}
+void AggregatedFeaturesExtractor::init(const ImageFilter* imageFilter, const ImageFilter* layerFilter) {
+    if (patchSizeInCells.width < 1 || patchSizeInCells.height < 1 || cellSizeInPixels < 1 || octaveLayerCount < 1)
+        throw std::invalid_argument("AggregatedFeaturesExtractor: patch and cell sizes and the octave layer count must be positive");
+    auto fhog = dynamic_cast<const filtering::FhogFilter*>(layerFilter);
+    fd_fpdw_params fp;
+    if (fhog && (!imageFilter || dynamic_cast<const GrayscaleFilter*>(imageFilter))) {
+        channels = 3 * fhog->unsignedBinCount + 4;
+        grayOnly = imageFilter == nullptr;
+        handle = create_extractor_handle(fhog, nullptr, patchSizeInCells, cellSizeInPixels, octaveLayerCount, minPatchWidthInPixels, nullptr, channels);
+    } else if (!imageFilter && fpdw_chain(layerFilter, fp)) {
+        channels = 10;
+        colorOnly = true;
+        handle = create_extractor_handle(nullptr, &fp, patchSizeInCells, cellSizeInPixels, octaveLayerCount, minPatchWidthInPixels, nullptr, channels);
+    } else {
+        throw std::logic_error(kExtractorFilters);
+    }
+}
+void AggregatedFeaturesExtractor::update(shared_ptr<VersionedImage> versioned) {
+    if (!handle) {   // the feature-pyramid form: what AggregatedFeaturesDetector's extractor constructor reads from the pyramid
+        auto fhog = std::dynamic_pointer_cast<filtering::FhogFilter>(featurePyramid->getApproximatedLayerFilter());
+        fd_fpdw_params fp;
+        const bool fpdw = featurePyramid->hasNoImageFilter() && fpdw_chain(featurePyramid->getApproximatedLayerFilter().get(), fp);
+        if (!fpdw && (!featurePyramid->hasGrayscaleImageFilter() || !fhog)) throw std::logic_error(kExtractorFilters);
+        channels = fpdw ? 10 : 3 * fhog->unsignedBinCount + 4;
+        colorOnly = fpdw;
+        handle = create_extractor_handle(fpdw ? nullptr : fhog.get(), fpdw ? &fp : nullptr, patchSizeInCells, cellSizeInPixels, octaveLayerCount,
+                                         minPatchWidthInPixels, &featurePyramid->getLambdas(), channels);
+    }
+    Mat img = contiguous(versioned->getData());
+    if (img.depth() != CV_8U) throw std::invalid_argument("AggregatedFeaturesExtractor: the image must be of depth CV_8U");
+    if (grayOnly && img.channels() != 1) throw std::invalid_argument("FhogFilter: the image must be of type CV_8UC1 (add a GrayscaleFilter as image filter)");
+    if (colorOnly && img.channels() != 3) throw std::invalid_argument("FpdwFeaturesFilter: the image must be of type CV_8UC3");
+    check(fd_aggregated_update(context(), handle, img.data, img.cols, img.rows, img.channels(), 0));
+    image = img;
+}
+shared_ptr<Patch> AggregatedFeaturesExtractor::extract(int centerX, int centerY, int width, int height) const {
+    return extract(cv::Rect(centerX - width / 2, centerY - height / 2, width, height));   // Patch::computeBounds
+}
+shared_ptr<Patch> AggregatedFeaturesExtractor::extract(cv::Rect bounds) const { return extract(vector<cv::Rect>{bounds})[0]; }
+vector<shared_ptr<Patch>> AggregatedFeaturesExtractor::extract(const vector<cv::Rect>& boxes) const {
+    if (!handle) throw std::runtime_error("AggregatedFeaturesExtractor: update has to be called before extract");
+    const int n = (int)boxes.size();
+    vector<shared_ptr<Patch>> patches((size_t)n);
+    if (n == 0) return patches;
+    const size_t d = (size_t)patchSizeInCells.width * patchSizeInCells.height * channels;
+    vector<int32_t> in((size_t)4 * n);
+    for (int k = 0; k < n; ++k) {
+        in[4 * k] = boxes[k].x; in[4 * k + 1] = boxes[k].y; in[4 * k + 2] = boxes[k].width; in[4 * k + 3] = boxes[k].height;
+    }
+    vector<float> features(d * n);
+    vector<fd_box> bounds((size_t)n);
+    vector<uint8_t> valid((size_t)n);
+    check(fd_aggregated_extract(context(), handle, n, in.data(), features.data(), 0, bounds.data(), valid.data()));
+    for (int k = 0; k < n; ++k) {
+        if (!valid[k]) continue;
+        Mat data(patchSizeInCells.height, patchSizeInCells.width, CV_32FC(channels));
+        std::memcpy(data.data, features.data() + d * k, sizeof(float) * d);
+        const fd_box& b = bounds[k];   // Patch(bounds, data): Patch::computeCenter
+        patches[k] = make_shared<Patch>(b.x + b.w / 2, b.y + b.h / 2, b.w, b.h, data);
+    }
+    return patches;
+}
+vector<std::pair<cv::Rect, float>> AggregatedFeaturesExtractor::detectWindows(const classification::SvmClassifier& svm, float threshold) {
+    if (!handle || image.empty()) throw std::runtime_error("AggregatedFeaturesExtractor: update has to be called before detectWindows");
+    if (svm.getSupportVectors().size() != 1) throw std::invalid_argument("AggregatedFeaturesExtractor: a linear SVM with one support vector is needed");
+    Mat sv = contiguous(svm.getSupportVectors()[0]);
+    if (sv.depth() != CV_32F || (int)(sv.total() * sv.channels()) != patchSizeInCells.width * patchSizeInCells.height * channels)
+        throw std::invalid_argument("AggregatedFeaturesExtractor: the support vector must hold patchSizeInCells x channels floats");
+    check(fd_aggregated_set_svm(context(), handle, sv.ptr<float>(0), svm.getBias(), threshold));
+    vector<fd_box> fin(1), cand(1 << 14);
+    int n = 0, nc = 0;
+    // the candidates are the windows before suppression; the final detections are not asked for (a capacity of 0 reports their count only)
+    int rc = fd_aggregated_detect(context(), handle, image.data, image.cols, image.rows, image.channels(), 0, nullptr, 0, &n, cand.data(), (int)cand.size(), &nc);
+    check(rc);
+    if (nc > (int)cand.size()) {
+        cand.resize((size_t)nc);
+        check(fd_aggregated_detect(context(), handle, image.data, image.cols, image.rows, image.channels(), 0, nullptr, 0, &n, cand.data(), nc, &nc));
+    }
+    vector<std::pair<cv::Rect, float>> res;
+    for (int i = 0; i < nc; ++i) res.emplace_back(cv::Rect(cand[i].x, cand[i].y, cand[i].w, cand[i].h), cand[i].score);
+    return res;
 }
 }}  // namespace imageprocessing::extraction
 namespace detection {

@@ -450,6 +450,19 @@ int fd_ehog_tracker_get_svm(fd_ctx* ctx, fd_ehog_tracker* t, float* weights, flo
 /* host only, no context: whether the solver keeps Q in LDS for this size, and the default max_iterations; either may be NULL */
 int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations);
 
+/* The same trainer for up to FD_SVM_LARGE_MAX_N examples (detector training with hard negatives): same parameter
+ * and info structs, same row order (positives first), same guarantee -- on the Q that fd_linear_svm_gram_large returns the
+ * result is libsvm's bit for bit.  Q (n_pad x n_pad floats, 1 GiB at the limit) lives in the context's training scratch;
+ * FD_ERR_RUNTIME with a message when it cannot be allocated.  One problem per call, one workgroup of 1024 threads.  The
+ * entry points above keep their limit of 1024 examples. */
+#define FD_SVM_LARGE_MAX_N 16384
+int fd_linear_svm_gram_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD);
+int fd_linear_svm_train_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params,
+                              float* weights, float* bias, double* alpha /* n, may be NULL */, fd_svm_train_info* info);
+/* host only, no context: the solver's LDS bytes for this size (G and the reduction slots) and the default max_iterations; either
+ * may be NULL.  FD_ERR_INVALID_ARGUMENT for n_pos < 1, n_neg < 1, n > FD_SVM_LARGE_MAX_N or d < 1. */
+int fd_linear_svm_train_large_limits(int n_pos, int n_neg, int d, int* lds_bytes, int* max_iterations);
+
 /* A particle set of the Condensation tracker resident on the device: two generations of up to `capacity` samples
  * as structure-of-arrays, bound to one fd_ehog_tracker.  A frame of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) +
  * ExtendedHogBasedMeasurementModel + FilteringStateExtractor(WeightedMeanStateExtractor) is fd_ehog_tracker_update,
@@ -567,6 +580,21 @@ int fd_aggregated_feature_layer(fd_ctx* ctx, fd_aggregated* a, int layer, float*
  * set), FD_ERR_CAPACITY when cap is too small (*n is set). */
 int fd_aggregated_plan_layers(int window_w, int window_h, int cell_size, int octave_layer_count, int min_window_width, int width,
                               int height, fd_aggregated_layer* out, int cap, int* n);
+
+/* extraction::AggregatedFeaturesExtractor::update and extract(Rect) on a handle of any kind (AggregatedFeaturesExtractor.cpp:55-60,
+ * 83-128).  fd_aggregated_update does what fd_aggregated_detect does up to and including the feature layers (the
+ * pyramid, the geometry, the features, the approximated layers) and produces no scores.  fd_aggregated_extract resolves n boxes
+ * {x, y, w, h} in image pixels on the host, in double, exactly as the reference does -- layer round(log(patchWidthPx / w) /
+ * log(inc)), centre through the layer's actual scales and truncated to cells, Patch::computeBounds, the within-image test -- and
+ * copies the window_h x window_w x channels cells of every valid window k into row k of `features` (n x d floats, host or
+ * device memory) in one launch.  bounds[k] (may be NULL; score 0) is computeBoundsInImagePixels of the window.  valid[k] = 0
+ * where the reference returns a null patch or w < 1: row k and bounds[k] are left untouched.  FD_ERR_RUNTIME when the handle's
+ * feature layers are not the context's current ones (another FHOG or aggregated call came in between). */
+int fd_aggregated_update(fd_ctx* ctx, fd_aggregated* a, const uint8_t* image, int width, int height, int channels, int is_device);
+int fd_aggregated_extract(fd_ctx* ctx, fd_aggregated* a, int n, const int32_t* boxes /* n x {x, y, w, h} */, float* features,
+                          int features_on_device, fd_box* bounds, uint8_t* valid);
+/* replaces the linear SVM of a handle (weights as in fd_aggregated_params) and its threshold; the feature layers stay */
+int fd_aggregated_set_svm(fd_ctx* ctx, fd_aggregated* a, const float* weights, float bias, float threshold);
 
 /* FPDW channel features: ChainedFilter(FpdwFeaturesFilter(fastGradient, interpolate, normalizationRadius, normalizationConstant),
  * AggregationFilter(cellSize, true, false)) on CV_8UC3 images (FpdwFeaturesFilter.cpp:21-205, AggregationFilter.cpp:20-36,
