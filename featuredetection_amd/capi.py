@@ -56,6 +56,22 @@ class fd_sdm_model(C.Structure):
                 ("desc_params", C.POINTER(C.c_int32))]
 
 
+class fd_sdm_train_params(C.Structure):
+    _fields_ = [("num_landmarks", C.c_int32), ("num_steps", C.c_int32), ("hog_variant", C.c_int32), ("desc_params", C.POINTER(C.c_int32)),
+                ("regularisation", C.c_int32), ("lambda_", C.c_double), ("regularise_affine", C.c_int32)]
+
+
+class fd_sdm_train_group(C.Structure):
+    _fields_ = [("images", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("count", C.c_int32), ("on_device", C.c_int32)]
+
+
+class fd_sdm_train_step_info(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("err_l1", C.c_double), ("err_fro", C.c_double), ("rows", C.c_int32), ("dim", C.c_int32),
+                ("pivot_flag", C.c_int32)]
+
+
+SDM_REG_MANUAL, SDM_REG_AUTOMATIC, SDM_REG_EIGENVALUE_THRESHOLD = 0, 1, 2
+
 DET_DTYPE = np.dtype([("cx", "<i4"), ("cy", "<i4"), ("w", "<i4"), ("h", "<i4"), ("layer", "<i4"), ("lx", "<i4"),
                       ("ly", "<i4"), ("level", "<i4"), ("positive", "<i4"), ("score", "<f4"), ("probability", "<f8")],
                      align=True)
@@ -345,6 +361,12 @@ _SIGS = {
     "fd_sdm_fit_batch_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "fd_sdm_fit_batch_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_sdm_optimize_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_sdm_train": (C.c_int, [C.c_void_p, C.POINTER(fd_sdm_train_params), C.POINTER(fd_sdm_train_group), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(fd_sdm_train_step_info)]),
+    "fd_sdm_linear_regression": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                           C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "fd_sdm_train_step_dims": (C.c_int, [C.POINTER(fd_sdm_train_params), C.c_void_p]),
+    "fd_sdm_train_limits": (C.c_int, [C.POINTER(fd_sdm_train_params), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "fd_integral_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "fd_integral_destroy": (None, [C.c_void_p]),
     "fd_integral_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -372,6 +394,8 @@ _BENCH_SIGS = {
     "fd_debug_svm_u8_both": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fd_ctx_set_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "fd_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]),
+    "fd_sdm_train_last_phase_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "fd_debug_sdm_linear_regression_solution": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fd_last_group_prefilter_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "fd_debug_wvb_rect_sums": (C.c_int64, [C.POINTER(fd_wvm_model), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "fd_wvm_last_queue_length": (C.c_int64, [C.c_void_p]),
@@ -2126,6 +2150,15 @@ class Sdm:
         self.ctx.check(lib().fd_sdm_fit_batch_end(self.ctx.h, t, _ptr(out), _ptr(st)))
         return out, st
 
+    def optimize(self, gray_images, shapes):
+        """fd_sdm_optimize_batch: gray_images [B,H,W] u8, shapes [B,2L] start shapes.  Returns (shapes [B,2L], status [B])."""
+        imgs = _c(gray_images, np.uint8)
+        B, H, W = imgs.shape
+        out = _c(shapes, np.float32).reshape(B, 2 * self.L).copy()
+        st = np.zeros(B, np.int32)
+        self.ctx.check(lib().fd_sdm_optimize_batch(self.ctx.h, self.h, _ptr(imgs), W, H, B, 0, _ptr(out), _ptr(st)))
+        return out, st
+
     def close(self):
         if getattr(self, "h", None):
             lib().fd_sdm_destroy(self.h)
@@ -2149,3 +2182,89 @@ def sdm_descriptors(ctx, gray, px, py, wsh, variant=1, num_cells=3, cell_size=10
     ctx.check(lib().fd_sdm_descriptors(ctx.h, _ptr(gray), gray.shape[1], gray.shape[0], _ptr(px), _ptr(py), n, wsh, variant, num_cells,
                                        cell_size, num_bins, _ptr(out), C.byref(ln)))
     return out
+
+
+def _sdm_train_params(L, desc_params, variant, regularisation, lam, regularise_affine):
+    dp = _c(desc_params, np.int32).reshape(-1)
+    assert dp.size % 3 == 0 and dp.size > 0
+    p = fd_sdm_train_params()
+    p.num_landmarks, p.num_steps, p.hog_variant = int(L), dp.size // 3, int(variant)
+    p.desc_params = dp.ctypes.data_as(C.POINTER(C.c_int32))
+    p.regularisation, p.lambda_, p.regularise_affine = int(regularisation), float(lam), int(bool(regularise_affine))
+    return p, dp
+
+
+def sdm_train_limits(L, desc_params, rows, variant=1):
+    """fd_sdm_train_limits (host only): (device bytes the trainer keeps resident, largest D of the steps)"""
+    p, _keep = _sdm_train_params(L, desc_params, variant, SDM_REG_AUTOMATIC, 0.5, True)
+    b, m = C.c_int64(), C.c_int()
+    rc = lib().fd_sdm_train_limits(C.byref(p), int(rows), C.byref(b), C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_sdm_train_limits: invalid parameters")
+    return b.value, m.value
+
+
+def sdm_linear_regression(ctx, A, b, regularisation=SDM_REG_AUTOMATIC, lam=0.5, regularise_affine=True, want_normal_equations=False):
+    """fd_sdm_linear_regression: x [D,N] float32 and lambda; with want_normal_equations also AtA [D,D] and Atb [D,N] (float64)"""
+    A, b = _c(A, np.float32), _c(b, np.float32)
+    M, D = A.shape
+    N = b.shape[1]
+    assert b.shape[0] == M
+    x, lo = np.zeros((D, N), np.float32), C.c_double()
+    ata = np.zeros((D, D), np.float64) if want_normal_equations else None
+    atb = np.zeros((D, N), np.float64) if want_normal_equations else None
+    ctx.check(lib().fd_sdm_linear_regression(ctx.h, _ptr(A), _ptr(b), M, D, N, int(regularisation), float(lam), int(bool(regularise_affine)),
+                                             _ptr(x), C.byref(lo), _ptr(ata), _ptr(atb)))
+    return (x, lo.value, ata, atb) if want_normal_equations else (x, lo.value)
+
+
+def sdm_linear_regression_solution(ctx, D, N):
+    """the double solution the last sdm_linear_regression on this context rounded to float"""
+    x = np.zeros((D, N), np.float64)
+    ctx.check(lib().fd_debug_sdm_linear_regression_solution(ctx.h, int(D), int(N), _ptr(x)))
+    return x
+
+
+def sdm_train_last_phase_ms(ctx):
+    """fd_sdm_train_last_phase_ms: dict of the six phase times (ms) of the last timed step"""
+    ms = np.zeros(6, np.float32)
+    ctx.check(lib().fd_sdm_train_last_phase_ms(ctx.h, _ptr(ms)))
+    return dict(zip(("descriptors", "gram", "norm", "cholesky", "substitution", "update"), ms.tolist()))
+
+
+def sdm_train(ctx, groups, samples_per_image, initial_shapes, groundtruth, desc_params, variant=1, regularisation=SDM_REG_AUTOMATIC,
+              lam=0.5, regularise_affine=True):
+    """fd_sdm_train.  groups: list of [count,H,W] u8 arrays (images numbered through the groups in order); both shape arrays
+    [images * samples_per_image, 2L], image-major.  Returns a dict: R (list of [D_s,2L]), shapes_steps [S+1,M,2L], row_status [M],
+    info (list of S+1 dicts).  On FdError the exception carries row_status as .row_status."""
+    x0, gt = _c(initial_shapes, np.float32), _c(groundtruth, np.float32)
+    M, N = x0.shape
+    L = N // 2
+    assert gt.shape == x0.shape
+    p, dp = _sdm_train_params(L, desc_params, variant, regularisation, lam, regularise_affine)
+    S = p.num_steps
+    # a group is a [count,H,W] u8 array, or (device pointer, count, H, W) for images resident in HBM
+    imgs = [g if isinstance(g, tuple) else _c(g, np.uint8) for g in groups]
+    arr = (fd_sdm_train_group * len(imgs))()
+    for a, g in zip(arr, imgs):
+        if isinstance(g, tuple):
+            a.images, a.count, a.height, a.width, a.on_device = int(g[0]), int(g[1]), int(g[2]), int(g[3]), 1
+        else:
+            a.images, a.count, a.height, a.width, a.on_device = g.ctypes.data, g.shape[0], g.shape[1], g.shape[2], 0
+    assert sum(a.count for a in arr) * samples_per_image == M
+    dims = np.zeros(S, np.int32)
+    rc = lib().fd_sdm_train_step_dims(C.byref(p), _ptr(dims))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_sdm_train_step_dims: invalid parameters")
+    R = [np.zeros((d, N), np.float32) for d in dims]
+    ptrs = (C.c_void_p * S)(*[r.ctypes.data for r in R])
+    steps = np.zeros((S + 1, M, N), np.float32)
+    status = np.zeros(M, np.int32)
+    info = (fd_sdm_train_step_info * (S + 1))()
+    rc = lib().fd_sdm_train(ctx.h, C.byref(p), arr, len(imgs), int(samples_per_image), _ptr(x0), _ptr(gt), ptrs, _ptr(steps), _ptr(status), info)
+    if rc != FD_OK:
+        e = FdError(rc, lib().fd_last_error(ctx.h).decode())
+        e.row_status, e.R = status, R
+        raise e
+    return dict(R=R, shapes_steps=steps, row_status=status,
+                info=[dict(lam=i.lambda_, err_l1=i.err_l1, err_fro=i.err_fro, rows=i.rows, dim=i.dim, pivot_flag=i.pivot_flag) for i in info])

@@ -763,6 +763,13 @@ int descriptor_blocks_per_cu(const DescParams& p) {
     return e == hipSuccess && nb > 0 ? nb : 4;
 }
 
+// persistent grid of the descriptor kernel: the resident workgroups, a multiple of the 8 XCDs so that the kernel keeps every face on one XCD
+int descriptor_grid(fd_ctx* ctx, const DescParams& p, int64_t nitems) {
+    int grid = (int)std::min<int64_t>((nitems + 1) / 2, (int64_t)ctx->num_cus * descriptor_blocks_per_cu(p));
+    if (grid >= 16) grid &= ~7;
+    return grid;
+}
+
 void launch_descriptors(dim3 grid, hipStream_t st, const uint8_t* dimg, const int32_t* origin, const DescParams& p, int64_t nitems, float* out,
                         int64_t out_stride) {
     if (desc_small(p.iw, p.ih))
@@ -772,6 +779,8 @@ void launch_descriptors(dim3 grid, hipStream_t st, const uint8_t* dimg, const in
 }
 
 }  // namespace
+
+#include "sdm_train.hpp"   // the trainer: fd_sdm_train, fd_sdm_linear_regression (uses the kernels and launch helpers above)
 
 extern "C" {
 
@@ -909,8 +918,7 @@ static void sdm_launch(fd_ctx* ctx, fd_sdm* m, SdmScratch& sc, hipStream_t st, c
         hipLaunchKernelGGL(k_sdm_prepare, dim3((B * L + 255) / 256), dim3(256), 0, st, sc.shapes.as<float>(), B, L, W, H, adaptive ? 1 : 0,
                            adaptive ? 0 : half[step], adaptive ? (1 << 20) : SDM_IMG, stepFactor,
                            sc.origin.as<int32_t>(), sc.dist.as<float>(), sc.status.as<int32_t>());
-        int grid = (int)std::min<int64_t>((nitems + 1) / 2, (int64_t)ctx->num_cus * descriptor_blocks_per_cu(p));
-        if (grid >= 16) grid &= ~7;   // a multiple of the 8 XCDs: the kernel then keeps every face on one XCD
+        const int grid = descriptor_grid(ctx, p, nitems);
         const bool timeThis = timeIt && step + 1 == m->S;   // fd_hip_bench.h: the last step's descriptor launch
         if (timeThis) HIP_CHECK(hipEventRecord(ctx->ev0, st));
         launch_descriptors(dim3(grid), st, dimg, sc.origin.as<int32_t>(), p, nitems, sc.desc.as<float>(), (int64_t)F);

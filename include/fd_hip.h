@@ -898,6 +898,69 @@ int fd_sdm_fit_batch_begin(fd_ctx* ctx, const fd_sdm* model, const uint8_t* gray
                            const int32_t* face_boxes, int images_on_device, fd_sdm_ticket** ticket);
 int fd_sdm_fit_batch_end(fd_ctx* ctx, fd_sdm_ticket* ticket, float* shapes_out, int32_t* status_out);
 
+/* ---- supervised descent training: LandmarkBasedSupervisedDescentTraining::train's cascade loop (.cpp:297-365) and linearRegression
+ * (.cpp:439-518) on the device (csrc/sdm_train.hpp).  Per cascade step: the feature matrix A (row r: the L VlHog
+ * descriptors of row r's shape on row r's image, landmark-major, then a 1; the non-adaptive geometry of fd_sdm_model.desc_params, the
+ * descriptor floats are fd_sdm_descriptors'), AtA and Atb = A^T (groundtruth - shapes) accumulated in double in a fixed order (two
+ * calls give the same bits, AtA is exactly symmetric), lambda, Mreg = AtA + lambda I, R = Mreg^-1 Atb by Cholesky factorisation and
+ * two triangular solves in double, rounded to float once, and shapes += A R through the kernels fd_sdm_optimize_batch runs: the shapes
+ * after step s are bit for bit what fd_sdm_optimize_batch gives on the model of the first s regressors from the same start shapes.
+ * Reference quirks and what became of them:
+ *  - train() calls linearRegression(A, b, RegularizationType::Automatic) with the defaults of the HEADER (.hpp:187: lambda = 0.5f,
+ *    regularizeAffineComponent = true; the .cpp's comment says false) and never reads the member setRegularisation sets.  This ABI
+ *    takes the three values as parameters; the host class decides which to pass.
+ *  - the reference's solve is a float A.t()*A and Eigen's float full-pivoting LU INVERSE; here double and Cholesky, so the contract
+ *    is a tolerance against a float64 model, not bits.  A pivot <= 0 or NaN is FD_ERR_RUNTIME ("the regularised AtA is not positive
+ *    definite (pivot k); increase lambda"), the reference's "not invertible ... increase lambda".
+ *  - EigenvalueThreshold needs Eigen's FullPivLU::maxPivot() * threshold() and is not built: FD_ERR_INVALID_ARGUMENT naming it.
+ *  - the reference draws landmarks and boxes into the training images before it takes features from them (.cpp:263-264,273: debug
+ *    output).  Not reproduced: features come from the images as given.
+ *  - the reference trains with the extractors' fixed windows, but its compiled optimize() fits with face-size adaptive ones: a trained
+ *    model is for fd_sdm_model.desc_params (SdmLandmarkModelFitting(model, adaptive = false), sdm_fit_app --non-adaptive).
+ *  - getPerturbedShape seeds a fresh mt19937 from random_device per sample and passes rndN_t_x(engine), rndN_t_y(engine) as two arguments
+ *    of one call (unspecified evaluation order).  The start shapes are an INPUT of this ABI; the host class
+ *    (superviseddescent/LandmarkBasedSupervisedDescentTraining.hpp) draws them from one seeded std::mt19937 in the order scale, tx, ty. */
+enum { FD_SDM_REG_MANUAL = 0, FD_SDM_REG_AUTOMATIC = 1, FD_SDM_REG_EIGENVALUE_THRESHOLD = 2 };
+typedef struct {                /* zero-initialise before setting fields */
+    int32_t num_landmarks;      /* L */
+    int32_t num_steps;          /* S */
+    int32_t hog_variant;        /* 0 DalalTriggs, 1 UoCTTI */
+    const int32_t* desc_params; /* 3 per step {numCells, cellSize, numBins}, validated as fd_sdm_model.desc_params */
+    int32_t regularisation;     /* FD_SDM_REG_MANUAL: lambda as given; FD_SDM_REG_AUTOMATIC: lambda * ||AtA||_F / rows */
+    double lambda;
+    int32_t regularise_affine;  /* 0: the last diagonal element (the bias) gets no lambda */
+} fd_sdm_train_params;
+typedef struct {
+    const uint8_t* images;      /* count contiguous gray images of width x height, host or device */
+    int32_t width, height, count, on_device;
+} fd_sdm_train_group;           /* images are numbered through the groups in order */
+typedef struct {
+    double lambda;              /* the lambda added to the diagonal (entry 0: 0) */
+    double err_l1;              /* ||groundtruth - shapes||_1 / (rows * 2L), the number the reference logs (.cpp:293,363) */
+    double err_fro;             /* ||groundtruth - shapes||_F */
+    int32_t rows, dim;          /* M and D = L * len + 1 of the step (entry 0: dim 0) */
+    int32_t pivot_flag;         /* 0, or 1 + the index of the pivot that was not positive */
+} fd_sdm_train_step_info;
+/* rows = images * samples_per_image (the reference's K + 1 per image); both shape arrays are image-major as the reference lays
+ * them out (row = image * samples_per_image + sample, 2L floats x0..xL-1, y0..yL-1).  R_out[s]: (L * len_s + 1) x 2L floats in
+ * fd_sdm_model.R's layout, bias row last.  shapes_steps_out (may be NULL): (S + 1) x rows x 2L floats, entry 0 the start shapes.
+ * row_status_out (may be NULL): per row 0 ok / 1 a patch window left the image in some step; such a row makes the call fail with
+ * FD_ERR_RUNTIME, and R_out is not written.  info_out (may be NULL): S + 1 entries, entry 0 carries the start errors. */
+int fd_sdm_train(fd_ctx* ctx, const fd_sdm_train_params* params, const fd_sdm_train_group* groups, int num_groups, int samples_per_image,
+                 const float* initial_shapes, const float* groundtruth, float* const* R_out, float* shapes_steps_out,
+                 int32_t* row_status_out, fd_sdm_train_step_info* info_out);
+/* The reference's free function linearRegression on host matrices: A is M x D (its last column is whatever the caller put there; it
+ * is the one regularise_affine == 0 leaves alone), b is M x N, x_out D x N.  lambda_out, ata_out (D x D), atb_out (D x N) may be NULL. */
+int fd_sdm_linear_regression(fd_ctx* ctx, const float* A, const float* b, int M, int D, int N, int type, double lambda,
+                             int regularise_affine, float* x_out, double* lambda_out, double* ata_out, double* atb_out);
+/* host only: device bytes the trainer keeps resident for `rows` rows (A, AtA with the right-hand sides, the update's partial sums, R,
+ * shapes, patch origins, row status) and the largest D of the steps.  NOT counted: the images of host groups, which the call uploads
+ * (width x height x count bytes per group), and a few hundred bytes of scalars.  An allocation that fails in fd_sdm_train is
+ * FD_ERR_RUNTIME naming its byte count.  Either output may be NULL. */
+int fd_sdm_train_limits(const fd_sdm_train_params* params, int rows, int64_t* bytes, int* max_dim);
+/* host only: dims[s] = L * len_s + 1, the rows of R_out[s], for every step */
+int fd_sdm_train_step_dims(const fd_sdm_train_params* params, int32_t* dims);
+
 /* ---- image-shard data parallelism (north_star: "images shard embarrassingly across the 8 GPUs of one node with a single RCCL gather
  * of detections over xGMI").  One process per GPU; image i belongs to rank i mod world; models are replicated; no data-path
  * collective.  The reference has no counterpart (it is single-threaded, ffpDetectApp.cpp:548-659 loops over the images of a

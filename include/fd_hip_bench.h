@@ -19,6 +19,13 @@ int fd_last_kernel_ms(fd_ctx* ctx, const char** kernel_name, float* ms);
  * (HIP events on the stream it was launched on) and the number of detectors it served; members = 0: no group launch was timed.  Meant
  * for a batch that holds ONE group (several groups of a batch are queued by different host threads: the last writer wins). */
 int fd_last_group_prefilter_ms(fd_ctx* ctx, float* ms, int* members);
+/* With kernel timing on: the phases (ms, HIP events on the context's stream) of the last cascade step of the last fd_sdm_train, or of the
+ * last fd_sdm_linear_regression, on this context: {descriptors and deltas, Gram, norm + lambda + diagonal, Cholesky (with the forward
+ * substitution it carries), backward substitution + rounding, update + errors}.  fd_sdm_linear_regression: entries 0 and 5 are empty. */
+int fd_sdm_train_last_phase_ms(fd_ctx* ctx, float* ms6);
+/* the unrounded (double) D x N solution of the last successful fd_sdm_linear_regression on this context, of which x_out is the rounding to
+ * float: what the backward-error bound of a Cholesky solve is stated for (FD_ERR_LOGIC when there is none of that size) */
+int fd_debug_sdm_linear_regression_solution(fd_ctx* ctx, int D, int N, double* x64_out);
 
 /* Windows the last finished cascade run of this handle handed to stage B (the pre-filter's queue; all frames of a multi-frame call
  * together); -1 before the first run.  bench.py reports the spread over the calls of a run. */
