@@ -144,6 +144,16 @@ class fd_fpdw_params(C.Structure):
                 ("normalization_constant", C.c_float)]
 
 
+class fd_svm_kernel(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+
+
+class fd_kernel_svm_train_problem(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
+                ("sv_index", C.c_void_p), ("coefficients", C.c_void_p), ("support_vectors", C.c_void_p), ("bias", C.c_void_p),
+                ("alpha", C.c_void_p)]
+
+
 class fd_aggregated_params(C.Structure):
     _fields_ = [("fhog", fd_fhog_params), ("window_w", C.c_int32), ("window_h", C.c_int32), ("octave_layer_count", C.c_int32),
                 ("min_window_width", C.c_int32), ("width_scale", C.c_float), ("height_scale", C.c_float), ("svm_weights", C.c_void_p),
@@ -297,6 +307,15 @@ _SIGS = {
     "fd_linear_svm_train_large": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_train_params), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(fd_svm_train_info)]),
     "fd_linear_svm_train_large_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_kernel_svm_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel), C.c_void_p, C.c_void_p]),
+    "fd_kernel_svm_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
+                                      C.POINTER(fd_svm_train_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(fd_svm_train_info)]),
+    "fd_kernel_svm_train_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
+                                            C.POINTER(fd_svm_train_params), C.c_float, C.c_double, C.c_double, C.POINTER(C.c_void_p),
+                                            C.POINTER(fd_svm_train_info)]),
+    "fd_kernel_svm_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fd_svm_kernel), C.POINTER(fd_svm_train_params), C.c_void_p]),
+    "fd_kernel_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fd_aggregated_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fd_aggregated_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "fd_aggregated_set_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
@@ -842,6 +861,13 @@ class Svm:
         ctx.check(lib().fd_svm_create(ctx.h, C.byref(s), C.byref(self.h)))
         self.dim = s.dim
         self.np_dtype = dtype
+
+    @classmethod
+    def from_handle(cls, ctx, handle, dim):
+        """an f32 model the library created itself (fd_kernel_svm_train_model); the object owns the handle"""
+        self = cls.__new__(cls)
+        self.ctx, self.model, self.h, self.dim, self.np_dtype = ctx, None, handle, dim, np.float32
+        return self
 
     def distance(self, feats):
         feats = _c(feats, self.np_dtype).reshape(-1, self.dim)
@@ -1438,6 +1464,92 @@ def linear_svm_train_batch(ctx, problems, **kw):
     prm = svm_train_params(**kw)
     ctx.check(lib().fd_linear_svm_train_batch(ctx.h, count, arr, C.byref(prm), infos))
     return [(ws[c], float(biases[c]), alphas[c], _svm_info(infos[c])) for c in range(count)]
+
+
+def svm_kernel(kernel, p0=0.0, p1=0.0, p2=0.0):
+    """fd_svm_kernel: FD_KERNEL_* and its parameters as in fd_svm_model (rbf: gamma; poly: alpha, constant, degree)"""
+    return fd_svm_kernel(int(kernel), float(p0), float(p1), float(p2))
+
+
+def _svm_kernel(kernel):
+    return kernel if isinstance(kernel, fd_svm_kernel) else svm_kernel(*kernel)
+
+
+def _x_and_pointer(x):
+    """(keep-alive, pointer, n, d, is_device) of a host array or a torch tensor on the device (float32, contiguous)"""
+    if hasattr(x, "data_ptr"):
+        if str(x.dtype) != "torch.float32" or not x.is_contiguous() or x.dim() != 2 or not x.is_cuda:
+            raise ValueError("a device input is a contiguous float32 n x d tensor on the GPU")
+        return x, C.c_void_p(x.data_ptr()), int(x.shape[0]), int(x.shape[1]), 1
+    x = _c(x, np.float32)
+    if x.ndim != 2:
+        raise ValueError("x is n x d")
+    return x, _ptr(x), x.shape[0], x.shape[1], 0
+
+
+def kernel_svm_train_limits(n_pos, n_neg, d):
+    """fd_kernel_svm_train_limits (host only): (q_in_lds, large, max_iterations); FdError for sizes the trainer refuses"""
+    q, l, m = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fd_kernel_svm_train_limits(n_pos, n_neg, d, C.byref(q), C.byref(l), C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_kernel_svm_train_limits: invalid sizes (%d, %d, %d)" % (n_pos, n_neg, d))
+    return bool(q.value), bool(l.value), m.value
+
+
+def kernel_svm_gram(ctx, x, n_pos, kernel):
+    """fd_kernel_svm_gram: (Q float32 (n, n), QD float64 (n,)); kernel: svm_kernel(...) or its argument tuple"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    q, qd = np.zeros((n, n), np.float32), np.zeros(n, np.float64)
+    ctx.check(lib().fd_kernel_svm_gram(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(k), _ptr(q), _ptr(qd)))
+    return q, qd
+
+
+def kernel_svm_train(ctx, x, n_pos, kernel, want_support_vectors=True, **kw):
+    """fd_kernel_svm_train: (sv_index int32 (n_sv,), coefficients float32 (n_sv,), support_vectors float32 (n_sv, d) or None, bias,
+    alpha float64 (n,), info dict); x: host array or device tensor; keywords as svm_train_params"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    svi, coef, alpha, bias = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float64), C.c_float()
+    sv = np.zeros((n, d), np.float32) if want_support_vectors else None
+    prm, info = svm_train_params(**kw), fd_svm_train_info()
+    ctx.check(lib().fd_kernel_svm_train(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(k), C.byref(prm), _ptr(svi), _ptr(coef), _ptr(sv),
+                                        C.byref(bias), _ptr(alpha), C.byref(info)))
+    m = info.n_sv
+    return svi[:m].copy(), coef[:m].copy(), (sv[:m].copy() if sv is not None else None), bias.value, alpha, _svm_info(info)
+
+
+def kernel_svm_train_model(ctx, x, n_pos, kernel, threshold=0.0, logistic_a=0.00556, logistic_b=-2.95, **kw):
+    """fd_kernel_svm_train_model: (Svm, info dict) -- the trained f32 model, ready for Svm.distance"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    prm, info, h = svm_train_params(**kw), fd_svm_train_info(), C.c_void_p()
+    ctx.check(lib().fd_kernel_svm_train_model(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(k), C.byref(prm), threshold, logistic_a, logistic_b,
+                                              C.byref(h), C.byref(info)))
+    return Svm.from_handle(ctx, h, d), _svm_info(info)
+
+
+def kernel_svm_train_batch(ctx, problems, kernel, **kw):
+    """fd_kernel_svm_train_batch over [(x, n_pos), ...] (host arrays): a list of tuples like kernel_svm_train's"""
+    count = len(problems)
+    xs = [_c(x, np.float32) for x, _ in problems]
+    svis = [np.zeros(x.shape[0], np.int32) for x in xs]
+    coefs = [np.zeros(x.shape[0], np.float32) for x in xs]
+    svs = [np.zeros(x.shape, np.float32) for x in xs]
+    alphas = [np.zeros(x.shape[0], np.float64) for x in xs]
+    biases = np.zeros(max(count, 1), np.float32)
+    arr = (fd_kernel_svm_train_problem * max(count, 1))()
+    for c, (x, (_, n_pos)) in enumerate(zip(xs, problems)):
+        arr[c] = fd_kernel_svm_train_problem(x.ctypes.data, n_pos, x.shape[0] - n_pos, x.shape[1], 0, svis[c].ctypes.data, coefs[c].ctypes.data,
+                                             svs[c].ctypes.data, biases.ctypes.data + 4 * c, alphas[c].ctypes.data)
+    infos = (fd_svm_train_info * max(count, 1))()
+    k, prm = _svm_kernel(kernel), svm_train_params(**kw)
+    ctx.check(lib().fd_kernel_svm_train_batch(ctx.h, count, arr, C.byref(k), C.byref(prm), infos))
+    out = []
+    for c in range(count):
+        m = infos[c].n_sv
+        out.append((svis[c][:m].copy(), coefs[c][:m].copy(), svs[c][:m].copy(), float(biases[c]), alphas[c], _svm_info(infos[c])))
+    return out
 
 
 # fd_aggregated_layer: one feature layer of an aggregated-features detector

@@ -12,10 +12,23 @@
 //   k_svm_smo_large, k_svm_finish_large   the same for up to 16384 examples: 1024 threads, G and a status
 //                 byte per element in LDS, alpha in memory; the arithmetic is shared with the two kernels above
 //
+//
+// The same solver on the Q of a polynomial, RBF or histogram-intersection kernel, with the model returned as support vectors and
+// coefficients (fd_kernel_svm_*; Kernel::kernel_poly / kernel_rbf / kernel_hik svm.cpp:235-273, svm_train's
+// two-class model, LibSvmUtils::extractCoefficients):
+//   k_svm_gram_kernel   k_svm_gram's dot tile with an epilogue in double: powi(gamma dot + coef0, degree) or
+//                       exp(-gamma ((xs_i + xs_j) - 2 dot)); xs comes from a first launch over the diagonal tiles, so that the
+//                       diagonal of the second launch subtracts the very same sum and K_ii = 1 exactly
+//   k_svm_gram_hik      sum_k min(x_ik, x_jk) in double with k ascending (libsvm's order: Q and QD are libsvm's bits), the operand
+//                       tiles staged through LDS
+//   k_svm_finish_sv     rho, objective, counts as above, and in the same pass the support-vector indices and (float)(alpha_i y_i)
+//   k_svm_gather_sv     the support vectors' rows into a dense [n_sv][d] buffer
+//
 // A problem is n_pos positive rows followed by n_neg negative rows, so y_i = +1 for i < n_pos and libsvm's class grouping is the
 // identity; the bound status is alpha compared with 0 and C as update_alpha_status does.
 #include "fd_internal.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -47,6 +60,13 @@ struct SvmProbDev {
     int32_t* state;            // [0] iterations, [1] converged
     double Cp, Cn, eps;
     int32_t n_pos, n, n_pad, d, q_in_lds, max_iter;
+    // the support-vector form (fd_kernel_svm_*) only
+    double* xs;                // n_pad: x_i . x_i of the RBF kernel
+    int32_t* sv_index;         // n: the examples with alpha > 0, ascending
+    float* coef;               // n: (float)(alpha_i y_i) of these
+    float* sv;                 // n x d: their rows; NULL when not asked for
+    double gamma, coef0;
+    int32_t kernel, degree;    // FD_KERNEL_*
 };
 
 inline int svm_pad(int n) { return (n + 15) / 16 * 16; }
@@ -58,11 +78,9 @@ inline size_t svm_large_lds(int n) { return (sizeof(double) + 1) * (size_t)svm_p
 inline bool svm_q_in_lds(int n) { return svm_smo_lds(n, true) <= SVM_LDS_BUDGET; }
 
 // One wavefront per 16 x 16 tile of K, the whole feature length: lane (r, kq) feeds row r of both operand tiles at feature
-// k + kq.  Rows from n up to n_pad read as zero, so the padding of Q is zero.
-__global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ P) {
-    const SvmProbDev p = P[blockIdx.z];
-    const int ti = blockIdx.y, tj = blockIdx.x;
-    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
+// k + kq.  Rows from n up to n_pad read as zero.  The result is in the C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15,
+// row = (lane >> 4) + 4 * reg.
+__device__ __forceinline__ f64x4 svm_dot_tile(const SvmProbDev& p, int ti, int tj) {
     const int lane = threadIdx.x, r = lane & 15, kq = lane >> 4;
     const int i = ti * 16 + r, j = tj * 16 + r;
     const bool iok = i < p.n, jok = j < p.n;
@@ -85,20 +103,112 @@ __global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ 
 #pragma unroll
         for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[u], (double)b[u], acc, 0, 0, 0);
     }
-    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
-    const int col = tj * 16 + r;
+    return acc;
+}
+
+// Q_ij = (float)(y_i y_j K_ij) of a tile, QD and the start state on the diagonal
+__device__ __forceinline__ void svm_store_tile(const SvmProbDev& p, int ti, int tj, const double (&K)[4]) {
+    const int lane = threadIdx.x, col = tj * 16 + (lane & 15);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const int row = ti * 16 + kq + 4 * q;
-        const double K = acc[q];
+        const int row = ti * 16 + (lane >> 4) + 4 * q;
         const bool same = (row < p.n_pos) == (col < p.n_pos);
-        p.Q[(size_t)row * p.n_pad + col] = (float)(same ? K : -K);
+        p.Q[(size_t)row * p.n_pad + col] = (float)(same ? K[q] : -K[q]);
         if (row == col) {
-            p.QD[row] = K;
+            p.QD[row] = K[q];
             p.alpha[row] = 0.0;
             p.G[row] = -1.0;
         }
     }
+}
+
+// the linear kernel: the zero rows make the padding of Q zero
+__global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ P) {
+    const SvmProbDev p = P[blockIdx.z];
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
+    const f64x4 acc = svm_dot_tile(p, ti, tj);
+    const double K[4] = {acc[0], acc[1], acc[2], acc[3]};
+    svm_store_tile(p, ti, tj, K);
+}
+
+// powi of svm.cpp:26
+__device__ __forceinline__ double svm_powi(double base, int times) {
+    double tmp = base, ret = 1.0;
+    for (int t = times; t > 0; t /= 2) {
+        if (t % 2 == 1) ret *= tmp;
+        tmp = tmp * tmp;
+    }
+    return ret;
+}
+
+// Linear, polynomial and RBF kernel on the dot tile.  xsPass: the diagonal tiles only (blockIdx.x), which write xs_i = x_i . x_i
+// and nothing else; the launch over all tiles that follows accumulates its diagonal in the same order, so that
+// (xs_i + xs_i) - 2 dot_ii = 0 and K_ii = exp(-0) = 1 exactly, as where x_square and dot are one function.  The padding is
+// written as zero (a kernel of the zero rows is not).
+__global__ __launch_bounds__(64) void k_svm_gram_kernel(const SvmProbDev* __restrict__ P, int xsPass) {
+    const SvmProbDev p = P[blockIdx.z];
+    const int ti = xsPass ? blockIdx.x : blockIdx.y, tj = blockIdx.x;
+    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
+    const f64x4 acc = svm_dot_tile(p, ti, tj);
+    const int lane = threadIdx.x, col = tj * 16 + (lane & 15);
+    if (xsPass) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (ti * 16 + (lane >> 4) + 4 * q == col) p.xs[col] = acc[q];
+        return;
+    }
+    double K[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = ti * 16 + (lane >> 4) + 4 * q;
+        double v = acc[q];
+        if (p.kernel == FD_KERNEL_POLY) v = svm_powi(p.gamma * v + p.coef0, p.degree);
+        else if (p.kernel == FD_KERNEL_RBF) v = exp(-p.gamma * ((p.xs[row] + p.xs[col]) - 2.0 * v));
+        K[q] = (row < p.n && col < p.n) ? v : 0.0;
+    }
+    svm_store_tile(p, ti, tj, K);
+}
+
+// The histogram-intersection kernel: one wavefront per 16 x 16 tile, lane (c, kq) owns the entries (kq + 4 q, c) as in the MFMA
+// layout.  Chunks of SVM_HIK_KC features of the two operand tiles go through LDS (rows padded by one word: the 16 columns of a
+// read fall into 16 banks); per feature a lane takes the minimum (exact), converts and adds in double, k ascending as
+// kernel_hik does.  Rows from n up to n_pad read row 0 and are written as zero.
+constexpr int SVM_HIK_KC = 64;
+__global__ __launch_bounds__(64) void k_svm_gram_hik(const SvmProbDev* __restrict__ P) {
+    __shared__ float sA[16][SVM_HIK_KC + 1], sB[16][SVM_HIK_KC + 1];
+    const SvmProbDev p = P[blockIdx.z];
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
+    const int lane = threadIdx.x, c = lane & 15, kq = lane >> 4;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < p.d; k0 += SVM_HIK_KC) {
+        const int kn = min(SVM_HIK_KC, p.d - k0);
+        const int kc = k0 + (lane < kn ? lane : 0);   // in-range address for the masked lanes
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = ti * 16 + r, j = tj * 16 + r;
+            sA[r][lane] = p.x[(size_t)(i < p.n ? i : 0) * p.d + kc];
+            sB[r][lane] = p.x[(size_t)(j < p.n ? j : 0) * p.d + kc];
+        }
+        __syncthreads();
+        for (int k = 0; k < kn; ++k) {
+            const float b = sB[c][k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float a = sA[kq + 4 * q][k];
+                acc[q] += (double)(b < a ? b : a);   // min<double>(x_ik, x_jk)
+            }
+        }
+        __syncthreads();
+    }
+    const int col = tj * 16 + c;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = ti * 16 + kq + 4 * q;
+        if (row >= p.n || col >= p.n) acc[q] = 0.0;
+    }
+    svm_store_tile(p, ti, tj, acc);
 }
 
 // (value, index) of the larger value, ties to the higher index: what a scan in index order with >= leaves
@@ -440,7 +550,10 @@ __device__ __forceinline__ void svm_finish_weight(const SvmProbDev& p, int k) {
     }
     p.w[k] = w;
 }
-// rho, the objective and the counts by one thread; the sums run in index order as calculate_rho's and Solve's do
+// rho, the objective and the counts by one thread; the sums run in index order as calculate_rho's and Solve's do.  EmitSv: the
+// pass also lists the support vectors, ascending, with their coefficients (float)(alpha_i y_i) (svm_train's model for two classes,
+// extractCoefficients)
+template <bool EmitSv>
 __device__ __forceinline__ void svm_finish_info(const SvmProbDev& p, const double* sA, const double* sGf) {
     const int n = p.n, n_pos = p.n_pos;
     double ub = INFINITY, lb = -INFINITY, sumFree = 0.0, obj = 0.0;
@@ -461,6 +574,10 @@ __device__ __forceinline__ void svm_finish_info(const SvmProbDev& p, const doubl
         }
         obj += a * (g + -1.0);
         if (a > 0.0) {
+            if (EmitSv) {
+                p.sv_index[nSv] = i;
+                p.coef[nSv] = (float)(pos ? a : -a);
+            }
             ++nSv;
             if (a >= C) ++nBounded;
         }
@@ -491,7 +608,7 @@ __global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict
     }
     __syncthreads();
     if (tid != 0) return;
-    svm_finish_info(p, sA, sGf);
+    svm_finish_info<false>(p, sA, sGf);
 }
 
 // the same for a problem of k_svm_smo_large: the one thread reads alpha and G from memory
@@ -500,12 +617,77 @@ __global__ __launch_bounds__(256) void k_svm_finish_large(const SvmProbDev* __re
     const int tid = threadIdx.x;
     if (svm_finish_pending(p, blockIdx.x == 0 && tid == 0)) return;
     svm_finish_weight(p, blockIdx.x * 256 + tid);
-    if (blockIdx.x == 0 && tid == 0) svm_finish_info(p, p.alpha, p.G);
+    if (blockIdx.x == 0 && tid == 0) svm_finish_info<false>(p, p.alpha, p.G);
+}
+
+// The finish of the support-vector form, one block per problem: no weight vector; the sequential pass also writes sv_index and
+// coef.  Large: alpha and G are read from memory as in k_svm_finish_large.
+template <bool Large>
+__global__ __launch_bounds__(256) void k_svm_finish_sv(const SvmProbDev* __restrict__ P) {
+    __shared__ double sA[Large ? 1 : SVM_MAX_N], sGf[Large ? 1 : SVM_MAX_N];
+    const SvmProbDev p = P[blockIdx.x];
+    const int tid = threadIdx.x, n = p.n;
+    if (svm_finish_pending(p, tid == 0)) return;
+    if (Large) {
+        if (tid == 0) svm_finish_info<true>(p, p.alpha, p.G);
+        return;
+    }
+    for (int i = tid; i < n; i += 256) {
+        sA[i] = p.alpha[i];
+        sGf[i] = p.G[i];
+    }
+    __syncthreads();
+    if (tid == 0) svm_finish_info<true>(p, sA, sGf);
+}
+
+// sv[q][k] = x[sv_index[q]][k] for the n_sv support vectors that k_svm_finish_sv listed (none while the problem is pending): one
+// thread per element, consecutive threads along d
+__global__ __launch_bounds__(256) void k_svm_gather_sv(const SvmProbDev* __restrict__ P) {
+    const SvmProbDev p = P[blockIdx.y];
+    if (!p.sv) return;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)p.info->n_sv * p.d) return;
+    const size_t q = e / p.d;
+    p.sv[e] = p.x[(size_t)p.sv_index[q] * p.d + (e - q * p.d)];
 }
 
 struct SvmTrainScratch {
     DevBuf x, q, dbl, w, desc, info, state;
+    DevBuf xs, svList, sv;   // the support-vector form: xs; sv_index and coef; the gathered rows
 };
+
+// The support-vector form of a run (fd_kernel_svm_*): the checked kernel and, per problem, where the model goes (host).  The
+// first n_sv entries of sv_index / coefficients and the first n_sv rows of support_vectors are written.
+struct SvmSvOut {
+    int32_t* sv_index;
+    float* coefficients;
+    float* support_vectors;           // n x d, or NULL
+    std::vector<float>* sv_store;     // in place of support_vectors: resized to n_sv x d
+};
+struct SvmSvForm {
+    int32_t kernel, degree;
+    double gamma, coef0;
+    const SvmSvOut* outs;             // count entries, or NULL (the Gram alone)
+};
+
+SvmSvForm svm_checked_kernel(const char* who, const fd_svm_kernel* k) {
+    if (!k) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    SvmSvForm f = {k->kernel, 0, 0.0, 0.0, nullptr};
+    if (k->kernel == FD_KERNEL_POLY || k->kernel == FD_KERNEL_RBF) {
+        if (!(k->p0 >= 0.0) || std::isinf(k->p0)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: gamma must be finite and not negative (%g)", who, k->p0);
+        f.gamma = k->p0;
+    }
+    if (k->kernel == FD_KERNEL_POLY) {
+        if (!std::isfinite(k->p1)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the polynomial kernel's constant must be finite (%g)", who, k->p1);
+        if (!(k->p2 >= 0.0) || k->p2 > 2147483647.0 || k->p2 != std::floor(k->p2))
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the polynomial kernel's degree must be a non-negative integer (%g)", who, k->p2);
+        f.coef0 = k->p1;
+        f.degree = (int32_t)k->p2;
+    } else if (k->kernel != FD_KERNEL_LINEAR && k->kernel != FD_KERNEL_RBF && k->kernel != FD_KERNEL_HIK) {
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown kernel %d", who, k->kernel);
+    }
+    return f;
+}
 
 void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN = SVM_MAX_N) {
     if (n_pos < 1 || n_neg < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
@@ -532,7 +714,7 @@ inline size_t svm_align(size_t v) { return (v + 255) / 256 * 256; }
 // cost about a millisecond each on this stack): descriptors, infos, the host callers' X, and the weights / alpha to return.
 struct SvmRun {
     std::vector<SvmProbDev> h;
-    std::vector<size_t> outW, outA;   // offsets into the pinned area
+    std::vector<size_t> outW, outA, outS;   // offsets into the pinned area (outS: sv_index, then coef, n entries each)
     char* pinned = nullptr;
     size_t infoOff = 0;
     int maxPad = 0, maxD = 0;
@@ -541,10 +723,12 @@ struct SvmRun {
 
 // wOverride: device buffer that receives problem 0's weights in place of the scratch (the tracker's dweights)
 // large: the problems of fd_linear_svm_train_large (up to SVM_LARGE_MAX_N examples, Q always in memory)
+// form: the support-vector form with its kernel; NULL: the linear weight-vector form
 void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params& prm, float* wOverride,
-                 SvmRun& run, bool large = false) {
+                 SvmRun& run, bool large = false, const SvmSvForm* form = nullptr) {
     SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
-    size_t xBytes = 0, qBytes = 0, dblBytes = 0, wBytes = 0, outBytes = 0;
+    size_t xBytes = 0, qBytes = 0, dblBytes = 0, wBytes = 0, outBytes = 0, xsBytes = 0, listBytes = 0, svBytes = 0;
+    auto wantsRows = [&](int c) { return form && form->outs && (form->outs[c].support_vectors || form->outs[c].sv_store); };
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
         svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, large ? SVM_LARGE_MAX_N : SVM_MAX_N);
@@ -555,6 +739,12 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
         dblBytes += svm_align(sizeof(double) * np * 3);
         wBytes += svm_align(sizeof(float) * pr.d);
         outBytes += svm_align(sizeof(float) * pr.d) + svm_align(sizeof(double) * np);
+        if (form) {
+            xsBytes += svm_align(sizeof(double) * np);
+            listBytes += svm_align(2 * sizeof(int32_t) * np);
+            outBytes += svm_align(2 * sizeof(int32_t) * np);
+            if (wantsRows(c)) svBytes += svm_align(sizeof(float) * n * pr.d);
+        }
     }
     sc.x.reserve(xBytes);
     try {
@@ -567,6 +757,15 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
     sc.desc.reserve(sizeof(SvmProbDev) * count);
     sc.info.reserve(sizeof(fd_svm_train_info) * count);
     sc.state.reserve(sizeof(int32_t) * 2 * count);
+    if (form) {
+        sc.xs.reserve(xsBytes);
+        sc.svList.reserve(listBytes);
+        try {
+            sc.sv.reserve(svBytes);
+        } catch (const FdError& e) {
+            FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for the support vectors (%zu bytes): %s", who, svBytes, e.msg.c_str());
+        }
+    }
     run.infoOff = svm_align(sizeof(SvmProbDev) * count);
     const size_t xOff = run.infoOff + svm_align(sizeof(fd_svm_train_info) * count);
     size_t outOff = xOff + xBytes;
@@ -575,7 +774,8 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
     run.h.resize(count);
     run.outW.resize(count);
     run.outA.resize(count);
-    size_t xo = 0, qo = 0, dblo = 0, wo = 0;
+    run.outS.resize(count);
+    size_t xo = 0, qo = 0, dblo = 0, wo = 0, xso = 0, listo = 0, svo = 0;
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
         const int n = pr.n_pos + pr.n_neg, np = svm_pad(n);
@@ -610,6 +810,30 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
         D.d = pr.d;
         D.q_in_lds = !large && svm_q_in_lds(n) ? 1 : 0;
         D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : std::max(10000000, 100 * n);
+        D.xs = nullptr;
+        D.sv_index = nullptr;
+        D.coef = nullptr;
+        D.sv = nullptr;
+        D.gamma = D.coef0 = 0.0;
+        D.kernel = FD_KERNEL_LINEAR;
+        D.degree = 0;
+        if (form) {
+            D.xs = (double*)((char*)sc.xs.p + xso);
+            xso += svm_align(sizeof(double) * (size_t)np);
+            D.sv_index = (int32_t*)((char*)sc.svList.p + listo);
+            D.coef = (float*)(D.sv_index + np);
+            listo += svm_align(2 * sizeof(int32_t) * (size_t)np);
+            if (wantsRows(c)) {
+                D.sv = (float*)((char*)sc.sv.p + svo);
+                svo += svm_align(sizeof(float) * (size_t)n * pr.d);
+            }
+            run.outS[c] = outOff;
+            outOff += svm_align(2 * sizeof(int32_t) * (size_t)np);
+            D.gamma = form->gamma;
+            D.coef0 = form->coef0;
+            D.kernel = form->kernel;
+            D.degree = form->degree;
+        }
         hd[c] = D;
         run.maxPad = std::max(run.maxPad, np);
         run.maxD = std::max(run.maxD, pr.d);
@@ -618,20 +842,35 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
     if (xBytes) HIP_CHECK(hipMemcpyAsync(sc.x.p, run.pinned + xOff, xBytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(sc.desc.p, hd, sizeof(SvmProbDev) * count, hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemsetAsync(sc.state.p, 0, sizeof(int32_t) * 2 * count, ctx->stream));
-    hipLaunchKernelGGL(k_svm_gram, dim3(run.maxPad / 16, run.maxPad / 16, count), dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+    const dim3 tiles(run.maxPad / 16, run.maxPad / 16, count);
+    if (!form) {
+        hipLaunchKernelGGL(k_svm_gram, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+    } else if (form->kernel == FD_KERNEL_HIK) {
+        hipLaunchKernelGGL(k_svm_gram_hik, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+    } else {
+        if (form->kernel == FD_KERNEL_RBF) {   // xs first, from the diagonal tiles
+            hipLaunchKernelGGL(k_svm_gram_kernel, dim3(run.maxPad / 16, 1, count), dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>(), 1);
+            HIP_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_svm_gram_kernel, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>(), 0);
+    }
     HIP_CHECK(hipGetLastError());
 }
 
 // Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Problem 0's weights go to wOverride
 // (device) when given.  Leaves ctx->stream synchronised.  large: one problem of up to SVM_LARGE_MAX_N examples on k_svm_smo_large.
+// form: the support-vector form (the problems' weights are NULL; form->outs receives the model).
 void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
-                   fd_svm_train_info* infos, bool large) {
+                   fd_svm_train_info* infos, bool large, const SvmSvForm* form = nullptr) {
     const fd_svm_train_params prm = svm_checked_params(who, params);
     if (count < 1 || !probs || !infos) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument or no problem", who);
     HIP_CHECK(hipSetDevice(ctx->device));
     SvmRun run;
-    svm_prepare(ctx, who, count, probs, prm, wOverride, run, large);
+    svm_prepare(ctx, who, count, probs, prm, wOverride, run, large, form);
     SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
+    size_t rowElements = 0;   // the gather's grid: the largest n x d among the problems that want their support vectors' rows
+    for (int c = 0; c < count; ++c)
+        if (run.h[c].sv) rowElements = std::max(rowElements, (size_t)run.h[c].n * run.h[c].d);
     static uint64_t ldsAllowed = 0, ldsAllowedLarge = 0;
     if (large) fd_allow_lds(ctx, (const void*)k_svm_smo_large, (int)SVM_LDS_BUDGET, ldsAllowedLarge);
     else fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
@@ -644,8 +883,18 @@ void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_p
             hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
         HIP_CHECK(hipGetLastError());
         ++launches;
-        hipLaunchKernelGGL(large ? k_svm_finish_large : k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream,
-                           sc.desc.as<SvmProbDev>());
+        if (form) {
+            hipLaunchKernelGGL(large ? k_svm_finish_sv<true> : k_svm_finish_sv<false>, dim3(count), dim3(large ? 64 : 256), 0, ctx->stream,
+                               sc.desc.as<SvmProbDev>());
+            if (rowElements) {
+                HIP_CHECK(hipGetLastError());
+                hipLaunchKernelGGL(k_svm_gather_sv, dim3((unsigned)((rowElements + 255) / 256), count), dim3(256), 0, ctx->stream,
+                                   sc.desc.as<SvmProbDev>());
+            }
+        } else {
+            hipLaunchKernelGGL(large ? k_svm_finish_large : k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream,
+                               sc.desc.as<SvmProbDev>());
+        }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(run.pinned + run.infoOff, sc.info.p, sizeof(fd_svm_train_info) * count, hipMemcpyDeviceToHost, ctx->stream));
         // the results ride along: in the usual case the first launch converges and this is the only wait
@@ -654,6 +903,7 @@ void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_p
             if (probs[c].weights && !(c == 0 && wOverride))
                 HIP_CHECK(hipMemcpyAsync(run.pinned + run.outW[c], D.w, sizeof(float) * D.d, hipMemcpyDeviceToHost, ctx->stream));
             if (probs[c].alpha) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outA[c], D.alpha, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+            if (form) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outS[c], D.sv_index, 2 * sizeof(int32_t) * D.n_pad, hipMemcpyDeviceToHost, ctx->stream));
         }
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         bool done = true;
@@ -668,9 +918,26 @@ void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_p
         if (pr.alpha) std::memcpy(pr.alpha, run.pinned + run.outA[c], sizeof(double) * run.h[c].n);
         if (pr.bias) *pr.bias = (float)infos[c].rho;
     }
+    if (!form) return;
+    bool rows = false;
+    for (int c = 0; c < count; ++c) {   // the lists from the staging area; the rows, whose number is known only now, straight from the device
+        const SvmProbDev& D = run.h[c];
+        const SvmSvOut& o = form->outs[c];
+        const size_t nsv = (size_t)infos[c].n_sv;
+        std::memcpy(o.sv_index, run.pinned + run.outS[c], sizeof(int32_t) * nsv);
+        std::memcpy(o.coefficients, run.pinned + run.outS[c] + sizeof(int32_t) * D.n_pad, sizeof(float) * nsv);
+        if (o.sv_store) o.sv_store->resize(nsv * D.d);
+        float* dst = o.sv_store ? o.sv_store->data() : o.support_vectors;
+        if (D.sv && nsv) {
+            HIP_CHECK(hipMemcpyAsync(dst, D.sv, sizeof(float) * nsv * D.d, hipMemcpyDeviceToHost, ctx->stream));
+            rows = true;
+        }
+    }
+    if (rows) HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
-void svm_gram(fd_ctx* ctx, const char* who, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD, bool large) {
+void svm_gram(fd_ctx* ctx, const char* who, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD, bool large,
+              const SvmSvForm* form = nullptr) {
     HIP_CHECK(hipSetDevice(ctx->device));
     fd_svm_train_problem pr = {};
     pr.x = x;
@@ -680,7 +947,7 @@ void svm_gram(fd_ctx* ctx, const char* who, const float* x, int n_pos, int n_neg
     pr.is_device = is_device;
     fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
     SvmRun run;
-    svm_prepare(ctx, who, 1, &pr, prm, nullptr, run, large);
+    svm_prepare(ctx, who, 1, &pr, prm, nullptr, run, large, form);
     const SvmProbDev& D = run.h[0];
     HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
@@ -763,6 +1030,93 @@ int fd_linear_svm_train_batch(fd_ctx* ctx, int count, const fd_svm_train_problem
         for (int c = 0; c < count && problems; ++c)
             if (!problems[c].weights || !problems[c].bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: NULL argument in problem %d", c);
         fd_svm_train_run(ctx, "fd_linear_svm_train_batch", count, problems, params, nullptr, infos);
+    });
+}
+
+/* ---- the support-vector form: any kernel of fd_svm_model ---- */
+int fd_kernel_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* large, int* max_iterations) {
+    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_LARGE_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    const int n = n_pos + n_neg;
+    if (q_in_lds) *q_in_lds = n <= SVM_MAX_N && svm_q_in_lds(n) ? 1 : 0;
+    if (large) *large = n > SVM_MAX_N ? 1 : 0;
+    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    return FD_OK;
+}
+
+int fd_kernel_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel, float* Q, double* QD) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_gram: NULL argument");
+        const SvmSvForm form = svm_checked_kernel("fd_kernel_svm_gram", kernel);
+        svm_gram(ctx, "fd_kernel_svm_gram", x, n_pos, n_neg, d, is_device, Q, QD, (int64_t)n_pos + n_neg > SVM_MAX_N, &form);
+    });
+}
+
+int fd_kernel_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                        const fd_svm_train_params* params, int32_t* sv_index, float* coefficients, float* support_vectors, float* bias, double* alpha,
+                        fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !sv_index || !coefficients || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train: NULL argument");
+        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train", kernel);
+        const SvmSvOut out = {sv_index, coefficients, support_vectors, nullptr};
+        form.outs = &out;
+        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, bias, alpha);
+        svm_train_run(ctx, "fd_kernel_svm_train", 1, &pr, params, nullptr, info, (int64_t)n_pos + n_neg > SVM_MAX_N, &form);
+    });
+}
+
+int fd_kernel_svm_train_model(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                              const fd_svm_train_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out,
+                              fd_svm_train_info* info) {
+    int rc = fd_guard(ctx, [&] {
+        if (!ctx || !x || !out || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_model: NULL argument");
+        *out = nullptr;
+        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train_model", kernel);
+        svm_check_shape("fd_kernel_svm_train_model", n_pos, n_neg, d, SVM_LARGE_MAX_N);   // before the lists are sized by n
+        const int n = n_pos + n_neg;
+        std::vector<int32_t> svIndex(n);
+        std::vector<float> coef(n), rows;
+        float bias = 0.f;
+        const SvmSvOut o = {svIndex.data(), coef.data(), nullptr, &rows};
+        form.outs = &o;
+        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, &bias, nullptr);
+        svm_train_run(ctx, "fd_kernel_svm_train_model", 1, &pr, params, nullptr, info, n > SVM_MAX_N, &form);
+        if (info->n_sv < 1) FD_THROW(FD_ERR_RUNTIME, "fd_kernel_svm_train_model: the trained model has no support vector");
+        fd_svm_model md = {};
+        md.kernel = kernel->kernel;
+        md.p0 = kernel->p0;
+        md.p1 = kernel->p1;
+        md.p2 = kernel->p2;
+        md.num_sv = info->n_sv;
+        md.dim = d;
+        md.dtype = FD_DTYPE_F32;
+        md.support_vectors = rows.data();
+        md.coefficients = coef.data();
+        md.bias = bias;
+        md.threshold = threshold;
+        md.logistic_a = logistic_a;
+        md.logistic_b = logistic_b;
+        const int created = fd_svm_create(ctx, &md, out);
+        if (created != FD_OK) throw FdError{created, ctx->error};
+    });
+    return rc;
+}
+
+int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_problem* problems, const fd_svm_kernel* kernel,
+                              const fd_svm_train_params* params, fd_svm_train_info* infos) {
+    return fd_guard(ctx, [&] {
+        if (!ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: NULL argument");
+        if (count > 65535) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: %d problems, at most 65535", count);
+        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train_batch", kernel);
+        std::vector<fd_svm_train_problem> probs;
+        std::vector<SvmSvOut> outs;
+        for (int c = 0; c < count && problems; ++c) {
+            const fd_kernel_svm_train_problem& pr = problems[c];
+            if (!pr.sv_index || !pr.coefficients || !pr.bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: NULL argument in problem %d", c);
+            probs.push_back(svm_single_problem(pr.x, pr.n_pos, pr.n_neg, pr.d, pr.is_device, nullptr, pr.bias, pr.alpha));
+            outs.push_back(SvmSvOut{pr.sv_index, pr.coefficients, pr.support_vectors, nullptr});
+        }
+        form.outs = outs.data();
+        svm_train_run(ctx, "fd_kernel_svm_train_batch", count, problems ? probs.data() : nullptr, params, nullptr, infos, false, &form);
     });
 }
 

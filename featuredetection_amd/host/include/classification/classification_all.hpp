@@ -439,6 +439,8 @@ private:
 // device by fd_linear_svm_train (include/fd_hip.h; more than 1024 examples: fd_linear_svm_train_large, up to 16384, beyond that
 // std::runtime_error): the model libsvm's svm_train gives.  Any other kernel or example depth,
 // one-class SVMs, probabilistic output (libsvm's own sigmoid fit) and static negatives throw std::invalid_argument.
+// createBinaryKernelSvm (not in the reference) is the same classifier with any kernel, trained by fd_kernel_svm_train and holding
+// the support vectors and coefficients of libsvm's model (LibSvmClassifier.cpp:144-147) in place of one weight vector.
 namespace libsvm {
 
 class LibSvmClassifier : public classification::TrainableSvmClassifier {
@@ -457,6 +459,20 @@ public:
                                                              bool compensateImbalance = false, bool probabilistic = false) {
         return std::make_shared<LibSvmClassifier>(svm, c, false, compensateImbalance, probabilistic);
     }
+    // not in the reference: the binary C-SVC with a LinearKernel, PolynomialKernel, RbfKernel or HistogramIntersectionKernel whose
+    // retrain installs setSvmParameters(the examples that are support vectors, coefficients, rho).  createBinarySvm keeps throwing
+    // for the kernels it does not train, so the kernel form has a factory of its own.
+    static std::shared_ptr<LibSvmClassifier> createBinaryKernelSvm(std::shared_ptr<classification::Kernel> kernel, double c = 1,
+                                                                   bool compensateImbalance = false) {
+        return std::make_shared<LibSvmClassifier>(std::make_shared<classification::SvmClassifier>(kernel), c, compensateImbalance, KernelForm());
+    }
+    static std::shared_ptr<LibSvmClassifier> createBinaryKernelSvm(std::shared_ptr<classification::SvmClassifier> svm, double c = 1,
+                                                                   bool compensateImbalance = false) {
+        return std::make_shared<LibSvmClassifier>(svm, c, compensateImbalance, KernelForm());
+    }
+    struct KernelForm {};   // selects the constructor behind createBinaryKernelSvm
+    LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double c, bool compensateImbalance, KernelForm);
+    bool trainsSupportVectors() const { return kernelForm; }
     LibSvmClassifier(std::shared_ptr<classification::Kernel> kernel, double cnu, bool oneClass, bool compensateImbalance = false,
                      bool probabilistic = false);
     LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double cnu, bool oneClass, bool compensateImbalance = false,
@@ -486,10 +502,14 @@ public:
 private:
     // retrain's two halves: add the examples and, when both stores have their required size, gather them (positives first) with
     // the parameters; install the trained model
+    // examples: receives the gathered Mats in the order of x's rows (the kernel form installs some of them as support vectors)
     bool addAndGather(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples, std::vector<float>& x,
-                      int& positiveCount, int& negativeCount, int& dimensions, fd_svm_train_params& params);
+                      int& positiveCount, int& negativeCount, int& dimensions, fd_svm_train_params& params,
+                      std::vector<cv::Mat>* examples = nullptr);
+    bool retrainKernelForm(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples);
     void setTrained(const std::vector<float>& weights, const fd_svm_train_params& params, const fd_svm_train_info& info);
     bool compensateImbalance;
+    bool kernelForm = false;
     double c;
     std::shared_ptr<classification::ProbabilisticSvmClassifier> probabilisticSvm;
     std::unique_ptr<classification::ExampleManagement> positiveExamples, negativeExamples;

@@ -1562,11 +1562,17 @@ LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double cnu, bo
     if (!svm->getKernel() || svm->getKernel()->abiKernel() != FD_KERNEL_LINEAR)
         throw std::invalid_argument("LibSvmClassifier: only a LinearKernel is trained on this backend");
 }
+LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double c, bool compensateImbalance, KernelForm)
+    : TrainableSvmClassifier(svm), compensateImbalance(compensateImbalance), kernelForm(true), c(c),
+      probabilisticSvm(make_shared<classification::ProbabilisticSvmClassifier>(svm)),
+      positiveExamples(new classification::UnlimitedExampleManagement()), negativeExamples(new classification::UnlimitedExampleManagement()) {
+    if (!svm->getKernel()) throw std::invalid_argument("LibSvmClassifier: the SVM has no kernel");
+}
 void LibSvmClassifier::loadStaticNegatives(const string&, int, double) {
     throw std::invalid_argument("LibSvmClassifier: static negatives are not supported on this backend");
 }
 bool LibSvmClassifier::addAndGather(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples, vector<float>& x, int& positiveCount,
-                                    int& negativeCount, int& dimensions, fd_svm_train_params& params) {
+                                    int& negativeCount, int& dimensions, fd_svm_train_params& params, vector<Mat>* examples) {
     positiveExamples->add(newPositiveExamples);   // LibSvmClassifier.cpp:122-125
     negativeExamples->add(newNegativeExamples);
     if (!positiveExamples->hasRequiredSize() || !negativeExamples->hasRequiredSize()) return false;
@@ -1588,6 +1594,7 @@ bool LibSvmClassifier::addAndGather(const vector<Mat>& newPositiveExamples, cons
                 throw std::invalid_argument("LibSvmClassifier: examples have to have the same length");
             }
             x.insert(x.end(), example.ptr<float>(), example.ptr<float>() + dim);
+            if (examples) examples->push_back(example);
         }
     positiveCount = (int)positiveExamples->size();
     negativeCount = (int)negativeExamples->size();
@@ -1606,8 +1613,40 @@ void LibSvmClassifier::setTrained(const vector<float>& weights, const fd_svm_tra
     lastInfo = info;
     usable = true;
 }
+// the kernel form: libsvm's model as it is, the support vectors being the stored example Mats (:144-147)
+bool LibSvmClassifier::retrainKernelForm(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples) {
+    if (trainingTarget) throw std::invalid_argument("LibSvmClassifier: a tracker handle takes one weight vector (createBinarySvm), not support vectors");
+    vector<float> x;
+    vector<Mat> examples;
+    int positiveCount = 0, negativeCount = 0, dimensions = 0;
+    fd_svm_train_params params;
+    if (!addAndGather(newPositiveExamples, newNegativeExamples, x, positiveCount, negativeCount, dimensions, params, &examples)) return usable;
+    if (examples.size() > (size_t)FD_SVM_LARGE_MAX_N)
+        throw std::runtime_error("LibSvmClassifier: " + std::to_string(examples.size()) + " training examples, at most " +
+                                 std::to_string(FD_SVM_LARGE_MAX_N) + " are trained on this backend");
+    fd_svm_kernel kernel;
+    kernel.kernel = svm->getKernel()->abiKernel();
+    svm->getKernel()->abiParams(kernel.p0, kernel.p1, kernel.p2);
+    vector<int32_t> svIndex(examples.size());
+    vector<float> coefficients(examples.size());
+    float bias = 0;
+    fd_svm_train_info info;
+    check(fd_kernel_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &kernel, &params, svIndex.data(), coefficients.data(),
+                              nullptr, &bias, nullptr, &info));
+    vector<Mat> supportVectors;
+    for (int q = 0; q < info.n_sv; ++q) supportVectors.push_back(examples[svIndex[q]]);
+    coefficients.resize(info.n_sv);
+    svm->setSvmParameters(supportVectors, coefficients, info.rho);
+    lastPositiveCount = positiveCount;
+    lastNegativeCount = negativeCount;
+    lastParams = params;
+    lastInfo = info;
+    usable = true;
+    return usable;
+}
 bool LibSvmClassifier::retrain(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples) {
     if (newPositiveExamples.empty() && newNegativeExamples.empty()) return usable;   // :119-121
+    if (kernelForm) return retrainKernelForm(newPositiveExamples, newNegativeExamples);
     vector<float> x;
     int positiveCount = 0, negativeCount = 0, dimensions = 0;
     fd_svm_train_params params;

@@ -463,6 +463,48 @@ int fd_linear_svm_train_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg,
  * may be NULL.  FD_ERR_INVALID_ARGUMENT for n_pos < 1, n_neg < 1, n > FD_SVM_LARGE_MAX_N or d < 1. */
 int fd_linear_svm_train_large_limits(int n_pos, int n_neg, int d, int* lds_bytes, int* max_iterations);
 
+/* C-SVC training with any kernel of fd_svm_model: what libsvm::LibSvmClassifier::createBinarySvm(kernel, C) trains
+ * in the reference with an RbfKernel, a PolynomialKernel or a HistogramIntersectionKernel.  Problems, parameters and info as
+ * above; K is Kernel::kernel_linear / kernel_poly / kernel_rbf / kernel_hik of libsvm (svm.cpp:231-273), Q_ij = (float)(y_i y_j
+ * K_ij), QD_i = K_ii, and the solver is the one above.  The model is svm_train's for two classes: the examples with alpha > 0 in
+ * ascending index (positives first) as support vectors, the coefficients (float)(alpha_i y_i), the bias rho; the decision value is
+ * sum_i coefficient_i K(sv_i, x) - bias.  On the Q that fd_kernel_svm_gram returns the result is libsvm's bit for bit; for the
+ * histogram-intersection kernel that Q is libsvm's own, for the others single entries may differ from it by one float ulp.  For
+ * the RBF kernel QD is exactly 1.  The linear kernel is accepted (the same Q, alpha and rho as fd_linear_svm_train). */
+typedef struct {
+    int32_t kernel;       /* FD_KERNEL_* */
+    double p0, p1, p2;    /* as in fd_svm_model -- rbf: gamma; poly: alpha (libsvm's gamma), constant (coef0), degree */
+} fd_svm_kernel;
+typedef struct {
+    const float* x;                     /* n x d */
+    int32_t n_pos, n_neg, d, is_device; /* is_device: x is device memory */
+    int32_t* sv_index;                  /* out, n ints (host): the first n_sv are written */
+    float* coefficients;                /* out, n floats (host): the first n_sv are written */
+    float* support_vectors;             /* out, n x d floats (host): the first n_sv rows are written; may be NULL */
+    float* bias;                        /* out: (float)rho */
+    double* alpha;                      /* out, n doubles (host); may be NULL */
+} fd_kernel_svm_train_problem;
+/* FD_ERR_INVALID_ARGUMENT for what fd_linear_svm_train rejects (n up to FD_SVM_LARGE_MAX_N here, 1024 in the batch), an unknown
+ * kernel, gamma < 0 (rbf, poly), a polynomial degree that is negative or not integral, a NULL kernel or required output.
+ * One entry point for every size: up to 1024 examples on the solver of fd_linear_svm_train, beyond on that of
+ * fd_linear_svm_train_large. */
+int fd_kernel_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel, float* Q, double* QD);
+int fd_kernel_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                        const fd_svm_train_params* params, int32_t* sv_index /* n */, float* coefficients /* n */,
+                        float* support_vectors /* n x d, may be NULL */, float* bias, double* alpha /* n, may be NULL */, fd_svm_train_info* info);
+/* trains and creates the f32 model with fd_svm_create (the support vectors, coefficients, (float)rho, the kernel; threshold and
+ * logistic parameters as given): *out is scored with fd_svm_distance_batch and freed with fd_svm_destroy.  FD_ERR_RUNTIME when no
+ * alpha is positive (eps > 2). */
+int fd_kernel_svm_train_model(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                              const fd_svm_train_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out,
+                              fd_svm_train_info* info);
+/* count independent problems of at most 1024 examples with one kernel in one set of launches; infos: count entries */
+int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_problem* problems, const fd_svm_kernel* kernel,
+                              const fd_svm_train_params* params, fd_svm_train_info* infos);
+/* host only, no context: whether the solver keeps Q in LDS, whether the size takes the large solver, and the default
+ * max_iterations; each may be NULL */
+int fd_kernel_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* large, int* max_iterations);
+
 /* A particle set of the Condensation tracker resident on the device: two generations of up to `capacity` samples
  * as structure-of-arrays, bound to one fd_ehog_tracker.  A frame of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) +
  * ExtendedHogBasedMeasurementModel + FilteringStateExtractor(WeightedMeanStateExtractor) is fd_ehog_tracker_update,
