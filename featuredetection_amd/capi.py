@@ -1388,33 +1388,46 @@ def _svm_info(info):
     return {name: getattr(info, name) for name, _ in fd_svm_train_info._fields_}
 
 
-def linear_svm_train_limits(n_pos, n_neg, d):
-    """fd_linear_svm_train_limits (host only): (q_in_lds, max_iterations); FdError for sizes the trainer refuses"""
-    q, m = C.c_int(), C.c_int()
-    rc = lib().fd_linear_svm_train_limits(n_pos, n_neg, d, C.byref(q), C.byref(m))
+def _linear_svm_limits(name, n_pos, n_neg, d):
+    """the two results of the host-only fd_linear_svm_train_limits / _large_limits (`name`)"""
+    a, m = C.c_int(), C.c_int()
+    rc = getattr(lib(), name)(n_pos, n_neg, d, C.byref(a), C.byref(m))
     if rc != FD_OK:
-        raise FdError(rc, "fd_linear_svm_train_limits: invalid sizes (%d, %d, %d)" % (n_pos, n_neg, d))
-    return bool(q.value), m.value
+        raise FdError(rc, "%s: invalid sizes (%d, %d, %d)" % (name, n_pos, n_neg, d))
+    return a.value, m.value
 
 
-def linear_svm_gram(ctx, x, n_pos):
-    """(Q float32 (n, n), QD float64 (n,)) of n_pos positive rows followed by the negative rows of x"""
+def _linear_svm_gram(fn, ctx, x, n_pos):
     x = _c(x, np.float32)
     n, d = x.shape
     q, qd = np.zeros((n, n), np.float32), np.zeros(n, np.float64)
-    ctx.check(lib().fd_linear_svm_gram(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, _ptr(q), _ptr(qd)))
+    ctx.check(fn(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, _ptr(q), _ptr(qd)))
     return q, qd
 
 
-def linear_svm_train(ctx, x, n_pos, **kw):
-    """fd_linear_svm_train: (weights float32 (d,), bias, alpha float64 (n,), info dict); keywords as svm_train_params"""
+def _linear_svm_train(fn, ctx, x, n_pos, kw):
     x = _c(x, np.float32)
     n, d = x.shape
     w, bias, alpha = np.zeros(d, np.float32), C.c_float(), np.zeros(n, np.float64)
     prm, info = svm_train_params(**kw), fd_svm_train_info()
-    ctx.check(lib().fd_linear_svm_train(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, C.byref(prm), _ptr(w), C.byref(bias), _ptr(alpha),
-                                        C.byref(info)))
+    ctx.check(fn(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, C.byref(prm), _ptr(w), C.byref(bias), _ptr(alpha), C.byref(info)))
     return w, bias.value, alpha, _svm_info(info)
+
+
+def linear_svm_train_limits(n_pos, n_neg, d):
+    """fd_linear_svm_train_limits (host only): (q_in_lds, max_iterations); FdError for sizes the trainer refuses"""
+    q, m = _linear_svm_limits("fd_linear_svm_train_limits", n_pos, n_neg, d)
+    return bool(q), m
+
+
+def linear_svm_gram(ctx, x, n_pos):
+    """(Q float32 (n, n), QD float64 (n,)) of n_pos positive rows followed by the negative rows of x"""
+    return _linear_svm_gram(lib().fd_linear_svm_gram, ctx, x, n_pos)
+
+
+def linear_svm_train(ctx, x, n_pos, **kw):
+    """fd_linear_svm_train: (weights float32 (d,), bias, alpha float64 (n,), info dict); keywords as svm_train_params"""
+    return _linear_svm_train(lib().fd_linear_svm_train, ctx, x, n_pos, kw)
 
 
 SVM_LARGE_MAX_N = 16384   # FD_SVM_LARGE_MAX_N
@@ -1422,31 +1435,17 @@ SVM_LARGE_MAX_N = 16384   # FD_SVM_LARGE_MAX_N
 
 def linear_svm_train_large_limits(n_pos, n_neg, d):
     """fd_linear_svm_train_large_limits (host only): (lds_bytes, max_iterations); FdError for sizes the large trainer refuses"""
-    b, m = C.c_int(), C.c_int()
-    rc = lib().fd_linear_svm_train_large_limits(n_pos, n_neg, d, C.byref(b), C.byref(m))
-    if rc != FD_OK:
-        raise FdError(rc, "fd_linear_svm_train_large_limits: invalid sizes (%d, %d, %d)" % (n_pos, n_neg, d))
-    return b.value, m.value
+    return _linear_svm_limits("fd_linear_svm_train_large_limits", n_pos, n_neg, d)
 
 
 def linear_svm_gram_large(ctx, x, n_pos):
     """linear_svm_gram for up to SVM_LARGE_MAX_N rows (fd_linear_svm_gram_large)"""
-    x = _c(x, np.float32)
-    n, d = x.shape
-    q, qd = np.zeros((n, n), np.float32), np.zeros(n, np.float64)
-    ctx.check(lib().fd_linear_svm_gram_large(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, _ptr(q), _ptr(qd)))
-    return q, qd
+    return _linear_svm_gram(lib().fd_linear_svm_gram_large, ctx, x, n_pos)
 
 
 def linear_svm_train_large(ctx, x, n_pos, **kw):
     """linear_svm_train for up to SVM_LARGE_MAX_N rows (fd_linear_svm_train_large)"""
-    x = _c(x, np.float32)
-    n, d = x.shape
-    w, bias, alpha = np.zeros(d, np.float32), C.c_float(), np.zeros(n, np.float64)
-    prm, info = svm_train_params(**kw), fd_svm_train_info()
-    ctx.check(lib().fd_linear_svm_train_large(ctx.h, _ptr(x), n_pos, n - n_pos, d, 0, C.byref(prm), _ptr(w), C.byref(bias), _ptr(alpha),
-                                              C.byref(info)))
-    return w, bias.value, alpha, _svm_info(info)
+    return _linear_svm_train(lib().fd_linear_svm_train_large, ctx, x, n_pos, kw)
 
 
 def linear_svm_train_batch(ctx, problems, **kw):

@@ -603,7 +603,7 @@ int fd_ehog_tracker_train_svm(fd_ctx* ctx, fd_ehog_tracker* t, const float* x, i
         pr.n_pos = n_pos;
         pr.n_neg = n_neg;
         pr.d = (int)nw;
-        fd_svm_train_run(ctx, "fd_ehog_tracker_train_svm", 1, &pr, params, t->dweights.as<float>(), info);   // k_svm_finish writes dweights
+        fd_svm_train_run(ctx, {"fd_ehog_tracker_train_svm", false, t->dweights.as<float>()}, 1, &pr, params, info);   // k_svm_finish writes dweights
         t->bias = (float)info->rho;
         t->hasSvm = true;
         if (t->updated) ehog_launch_heat(ctx, t);

@@ -453,10 +453,27 @@ constexpr int FD_MAX_FRAMES = 64;
 void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, const int* roi,
                          std::vector<WindowLayer>& out, int64_t& total);
 
-// ---------------- linear SVM training (svm_train.hip) ----------------
-// trains `count` problems in one set of launches; problem 0's weights go to wOverride (device memory) when given, in place of
-// its host buffer.  Throws FdError; leaves ctx->stream synchronised.
-void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+// ---------------- SVM training (svm_train.hip) ----------------
+// Where the support-vector form (fd_kernel_svm_*) leaves one problem's model (host).  The first n_sv entries of sv_index /
+// coefficients and the first n_sv rows of support_vectors are written.
+struct FdSvmSvOut {
+    int32_t* sv_index;
+    float* coefficients;
+    float* support_vectors;           // n x d, or NULL
+    std::vector<float>* sv_store;     // in place of support_vectors: resized to n_sv x d
+};
+// One run of the trainer
+struct FdSvmRunSpec {
+    const char* who;                  // the entry point, for the messages
+    bool large = false;               // the solver for up to FD_SVM_LARGE_MAX_N examples (one problem, Q always in memory); else up to 1024
+    float* wOverride = nullptr;       // device memory that receives problem 0's weights in place of its host buffer (the tracker's dweights)
+    bool svForm = false;              // the model as support vectors and coefficients of `kernel` (checked); else one linear weight vector
+    int32_t kernel = FD_KERNEL_LINEAR, degree = 0;
+    double gamma = 0.0, coef0 = 0.0;
+    const FdSvmSvOut* outs = nullptr; // svForm: one entry per problem, or NULL (the Gram alone)
+};
+// trains `count` problems in one set of launches.  Throws FdError; leaves ctx->stream synchronised.
+void fd_svm_train_run(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params,
                       fd_svm_train_info* infos);
 
 // ---------------- resident particle set (condensation.hip) on an extended-HOG tracker (ehog_tracker.hpp) ----------------

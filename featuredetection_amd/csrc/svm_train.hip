@@ -3,25 +3,28 @@
 // (LibSvmClassifier.cpp:156-189, libSvm/src/svm.cpp Solver::Solve :551-830 without shrinking, select_working_set :833-930,
 // calculate_rho :1013-1049, LibSvmUtils::extractSupportVectors LibSvmUtils.cpp:105-118).
 //
-//   k_svm_gram    K = X X^T on the f64 MFMA pipe (f32 products are exact in f64), Q_ij = (float)(y_i y_j K_ij), QD_i = K_ii;
+//   k_svm_gram<LINEAR>   K = X X^T on the f64 MFMA pipe (f32 products are exact in f64), Q_ij = (float)(y_i y_j K_ij), QD_i = K_ii;
 //                 also the start state alpha = 0, G = -1
 //   k_svm_smo     one workgroup per problem: a counted loop of SMO iterations over a per-launch budget; alpha, G, the iteration
 //                 count and the converged flag persist in global memory between launches (the host relaunches)
-//   k_svm_finish  rho, the objective and the support-vector counts (one thread, libsvm's summation order), and the single
-//                 weight vector, one thread per dimension
-//   k_svm_smo_large, k_svm_finish_large   the same for up to 16384 examples: 1024 threads, G and a status
-//                 byte per element in LDS, alpha in memory; the arithmetic is shared with the two kernels above
+//   k_svm_smo_large   the same for up to 16384 examples: 1024 threads, G and a status byte per element
+//                 in LDS, alpha in memory; the arithmetic, the block reductions and the slot layout are shared with k_svm_smo
+//   k_svm_finish<Staged, false>   rho, the objective and the support-vector counts (one thread, libsvm's summation order), and
+//                 the single weight vector, one thread per dimension.  Staged: alpha and G of a problem of k_svm_smo go through
+//                 LDS; one of k_svm_smo_large is read from memory
 //
 //
 // The same solver on the Q of a polynomial, RBF or histogram-intersection kernel, with the model returned as support vectors and
 // coefficients (fd_kernel_svm_*; Kernel::kernel_poly / kernel_rbf / kernel_hik svm.cpp:235-273, svm_train's
 // two-class model, LibSvmUtils::extractCoefficients):
-//   k_svm_gram_kernel   k_svm_gram's dot tile with an epilogue in double: powi(gamma dot + coef0, degree) or
-//                       exp(-gamma ((xs_i + xs_j) - 2 dot)); xs comes from a first launch over the diagonal tiles, so that the
-//                       diagonal of the second launch subtracts the very same sum and K_ii = 1 exactly
+//   k_svm_gram<POLY>, <RBF>   the same dot tile with an epilogue in double: powi(gamma dot + coef0, degree) or
+//                       exp(-gamma ((xs_i + xs_j) - 2 dot)); xs comes from a first launch over the diagonal tiles
+//                       (k_svm_gram<SVM_GRAM_XS>), so that the diagonal of the second launch subtracts the very same sum and
+//                       K_ii = 1 exactly
 //   k_svm_gram_hik      sum_k min(x_ik, x_jk) in double with k ascending (libsvm's order: Q and QD are libsvm's bits), the operand
 //                       tiles staged through LDS
-//   k_svm_finish_sv     rho, objective, counts as above, and in the same pass the support-vector indices and (float)(alpha_i y_i)
+//   k_svm_finish<Staged, true>   rho, objective, counts as above, and in the same pass the support-vector indices and
+//                       (float)(alpha_i y_i); no weight vector
 //   k_svm_gather_sv     the support vectors' rows into a dense [n_sv][d] buffer
 //
 // A problem is n_pos positive rows followed by n_neg negative rows, so y_i = +1 for i < n_pos and libsvm's class grouping is the
@@ -65,9 +68,23 @@ struct SvmProbDev {
     int32_t* sv_index;         // n: the examples with alpha > 0, ascending
     float* coef;               // n: (float)(alpha_i y_i) of these
     float* sv;                 // n x d: their rows; NULL when not asked for
-    double gamma, coef0;
-    int32_t kernel, degree;    // FD_KERNEL_*
+    double gamma, coef0;       // of the polynomial and RBF kernels; the host picks the kernel's instantiation of k_svm_gram
+    int32_t degree;
 };
+
+// The LDS slots of a solver: per wavefront what either block reduction leaves, and for k_svm_smo_large (Pub = 4) the pair's
+// alpha_i, G_i, alpha_j, G_j that their owners publish.  The LDS formulas below reserve SVM_SLOT_BYTES / SVM_LARGE_SLOT_BYTES.
+template <int Waves, int Pub>
+struct SvmSlots {
+    double av[Waves];    // Gmax of a wavefront
+    double bv[Waves];    // its smallest obj_diff
+    double bg[Waves];    // its Gmax2
+    double pub[Pub];
+    int ai[Waves], bi[Waves];
+};
+typedef SvmSlots<SVM_SMO_WAVES, 0> SvmSmoSlots;
+typedef SvmSlots<SVM_LARGE_WAVES, 4> SvmLargeSlots;
+static_assert(sizeof(SvmSmoSlots) <= SVM_SLOT_BYTES && sizeof(SvmLargeSlots) <= SVM_LARGE_SLOT_BYTES, "the slots outgrow their LDS reserve");
 
 inline int svm_pad(int n) { return (n + 15) / 16 * 16; }
 inline size_t svm_smo_lds(int n, bool withQ) {
@@ -122,16 +139,6 @@ __device__ __forceinline__ void svm_store_tile(const SvmProbDev& p, int ti, int 
     }
 }
 
-// the linear kernel: the zero rows make the padding of Q zero
-__global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ P) {
-    const SvmProbDev p = P[blockIdx.z];
-    const int ti = blockIdx.y, tj = blockIdx.x;
-    if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
-    const f64x4 acc = svm_dot_tile(p, ti, tj);
-    const double K[4] = {acc[0], acc[1], acc[2], acc[3]};
-    svm_store_tile(p, ti, tj, K);
-}
-
 // powi of svm.cpp:26
 __device__ __forceinline__ double svm_powi(double base, int times) {
     double tmp = base, ret = 1.0;
@@ -142,17 +149,20 @@ __device__ __forceinline__ double svm_powi(double base, int times) {
     return ret;
 }
 
-// Linear, polynomial and RBF kernel on the dot tile.  xsPass: the diagonal tiles only (blockIdx.x), which write xs_i = x_i . x_i
-// and nothing else; the launch over all tiles that follows accumulates its diagonal in the same order, so that
-// (xs_i + xs_i) - 2 dot_ii = 0 and K_ii = exp(-0) = 1 exactly, as where x_square and dot are one function.  The padding is
-// written as zero (a kernel of the zero rows is not).
-__global__ __launch_bounds__(64) void k_svm_gram_kernel(const SvmProbDev* __restrict__ P, int xsPass) {
+// Linear, polynomial and RBF kernel on the dot tile, one instantiation each (the host picks it), and the xs pass of the RBF
+// kernel.  SVM_GRAM_XS: the diagonal tiles only (blockIdx.x), which write xs_i = x_i . x_i and nothing else; the launch over all
+// tiles that follows accumulates its diagonal in the same order, so that (xs_i + xs_i) - 2 dot_ii = 0 and K_ii = exp(-0) = 1
+// exactly, as where x_square and dot are one function.  The padding is written as zero: the zero rows make it so for the linear
+// kernel, which neither loads xs nor masks; a polynomial or RBF kernel of the zero rows is not zero.
+constexpr int SVM_GRAM_XS = -1;
+template <int Kernel>   // FD_KERNEL_LINEAR, FD_KERNEL_POLY, FD_KERNEL_RBF or SVM_GRAM_XS
+__global__ __launch_bounds__(64) void k_svm_gram(const SvmProbDev* __restrict__ P) {
     const SvmProbDev p = P[blockIdx.z];
-    const int ti = xsPass ? blockIdx.x : blockIdx.y, tj = blockIdx.x;
+    const int ti = Kernel == SVM_GRAM_XS ? blockIdx.x : blockIdx.y, tj = blockIdx.x;
     if (ti * 16 >= p.n_pad || tj * 16 >= p.n_pad) return;
     const f64x4 acc = svm_dot_tile(p, ti, tj);
     const int lane = threadIdx.x, col = tj * 16 + (lane & 15);
-    if (xsPass) {
+    if (Kernel == SVM_GRAM_XS) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (ti * 16 + (lane >> 4) + 4 * q == col) p.xs[col] = acc[q];
@@ -163,9 +173,9 @@ __global__ __launch_bounds__(64) void k_svm_gram_kernel(const SvmProbDev* __rest
     for (int q = 0; q < 4; ++q) {
         const int row = ti * 16 + (lane >> 4) + 4 * q;
         double v = acc[q];
-        if (p.kernel == FD_KERNEL_POLY) v = svm_powi(p.gamma * v + p.coef0, p.degree);
-        else if (p.kernel == FD_KERNEL_RBF) v = exp(-p.gamma * ((p.xs[row] + p.xs[col]) - 2.0 * v));
-        K[q] = (row < p.n && col < p.n) ? v : 0.0;
+        if (Kernel == FD_KERNEL_POLY) v = svm_powi(p.gamma * v + p.coef0, p.degree);
+        if (Kernel == FD_KERNEL_RBF) v = exp(-p.gamma * ((p.xs[row] + p.xs[col]) - 2.0 * v));
+        K[q] = (Kernel == FD_KERNEL_LINEAR || (row < p.n && col < p.n)) ? v : 0.0;
     }
     svm_store_tile(p, ti, tj, K);
 }
@@ -219,6 +229,55 @@ __device__ __forceinline__ void svm_take_max(double& v, int& i, double ov, int o
 __device__ __forceinline__ void svm_take_min(double& v, int& i, double ov, int oi) {
     if (ov < v || (ov == v && oi > i)) { v = ov; i = oi; }
 }
+
+// The two block reductions of a solver: over the wavefront by shuffles, over the wavefronts through the LDS slots, after which
+// every thread holds the result.  One barrier each.
+// the larger (v, i), ties to the higher index
+template <int Waves, int Pub>
+__device__ __forceinline__ void svm_block_argmax(SvmSlots<Waves, Pub>& s, double& v, int& i) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) svm_take_max(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
+    if (lane == 0) { s.av[wave] = v; s.ai[wave] = i; }
+    __syncthreads();
+    v = s.av[0];
+    i = s.ai[0];
+#pragma unroll
+    for (int w = 1; w < Waves; ++w) svm_take_max(v, i, s.av[w], s.ai[w]);
+}
+// the smaller (v, i), ties to the higher index, and the maximum of g
+template <int Waves, int Pub>
+__device__ __forceinline__ void svm_block_argmin_max(SvmSlots<Waves, Pub>& s, double& v, int& i, double& g) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        svm_take_min(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
+        g = fmax(g, __shfl_xor(g, o, 64));
+    }
+    if (lane == 0) { s.bv[wave] = v; s.bi[wave] = i; s.bg[wave] = g; }
+    __syncthreads();
+    v = s.bv[0];
+    i = s.bi[0];
+    g = s.bg[0];
+#pragma unroll
+    for (int w = 1; w < Waves; ++w) {
+        svm_take_min(v, i, s.bv[w], s.bi[w]);
+        g = fmax(g, s.bg[w]);
+    }
+}
+
+// A problem that is done, converged or at max_iterations, in an earlier launch (a batch relaunches until its last problem is
+// done): the solvers leave it alone, the finish reports it
+__device__ __forceinline__ bool svm_done(const SvmProbDev& p) { return p.state[1] || p.state[0] >= p.max_iter; }
+// what a solver leaves for the next launch and the finish, besides alpha and G
+__device__ __forceinline__ void svm_store_state(const SvmProbDev& p, int iter, int converged) {
+    if (threadIdx.x == 0) {
+        p.state[0] = iter;
+        p.state[1] = converged;
+    }
+}
+// the stopping test of Solve: optimal (without a pair only when the Gram holds a NaN)
+__device__ __forceinline__ bool svm_optimal(double gmax, double gmax2, double eps, int i, int j) { return gmax + gmax2 < eps || i < 0 || j < 0; }
 
 // The element-wise steps of Solver::Solve, shared by k_svm_smo and k_svm_smo_large.
 // i: element k in the scan that maximises -y_t G_t over I_up, the highest index among equals (:847-865); inUp: alpha_k below its
@@ -298,24 +357,19 @@ __device__ __forceinline__ void svm_pair_update(bool ipos, bool jpos, double Ci,
     }
 }
 
-// Solver::Solve's loop.  Every thread owns the elements tid, tid + 256, ...; the two selections are reduced over the
-// wavefront by shuffles and over the four wavefronts through LDS slots, after which every thread holds i, j and performs the
-// two-variable update redundantly.  Three barriers per iteration: behind either selection, and between reading alpha / G of
+// Solver::Solve's loop.  Every thread owns the elements tid, tid + 256, ...; the two selections are reduced over the block
+// (svm_block_argmax, svm_block_argmin_max), after which every thread holds i, j and performs the two-variable update redundantly.  Three barriers per iteration: behind either selection, and between reading alpha / G of
 // (i, j) and their owners' writes.
 __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* __restrict__ P, int budget) {
     extern __shared__ double svm_lds[];
     const SvmProbDev p = P[blockIdx.x];
-    if (p.state[1] || p.state[0] >= p.max_iter) return;   // done in an earlier launch (a batch relaunches until its last problem is done)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (svm_done(p)) return;
+    const int tid = threadIdx.x;
     const int n = p.n, np = p.n_pad, n_pos = p.n_pos;
     double* sAlpha = svm_lds;
     double* sG = sAlpha + np;
     double* sQD = sG + np;
-    double* slotAv = sQD + np;                        // [4] Gmax of a wavefront
-    double* slotBv = slotAv + SVM_SMO_WAVES;          // [4] its smallest obj_diff
-    double* slotBg = slotBv + SVM_SMO_WAVES;          // [4] its Gmax2
-    int* slotAi = (int*)(slotBg + SVM_SMO_WAVES);     // [4]
-    int* slotBi = slotAi + SVM_SMO_WAVES;             // [4]
+    SvmSmoSlots& slots = *(SvmSmoSlots*)(sQD + np);
     float* sQ = (float*)((char*)(sQD + np) + SVM_SLOT_BYTES);
     for (int k = tid; k < np; k += SVM_SMO_THREADS) {
         sAlpha[k] = p.alpha[k];
@@ -336,14 +390,7 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
         int gi = -1;
         for (int k = tid; k < n; k += SVM_SMO_THREADS)
             svm_scan_i(k, k < n_pos, k < n_pos ? sAlpha[k] < Cp : sAlpha[k] > 0.0, sG[k], gmax, gi);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) svm_take_max(gmax, gi, __shfl_xor(gmax, o, 64), __shfl_xor(gi, o, 64));
-        if (lane == 0) { slotAv[wave] = gmax; slotAi[wave] = gi; }
-        __syncthreads();
-        gmax = slotAv[0];
-        gi = slotAi[0];
-#pragma unroll
-        for (int w = 1; w < SVM_SMO_WAVES; ++w) svm_take_max(gmax, gi, slotAv[w], slotAi[w]);
+        svm_block_argmax(slots, gmax, gi);
         const int i = gi;
         // j: minimises obj_diff over I_low with grad_diff > 0, the highest index among equals; Gmax2 on the way (:872-922)
         double gmax2 = -INFINITY, omin = INFINITY;
@@ -354,23 +401,9 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
             for (int k = tid; k < n; k += SVM_SMO_THREADS)
                 svm_scan_j(k, k < n_pos, k < n_pos ? sAlpha[k] > 0.0 : sAlpha[k] < Cn, sG[k], gmax, yi, QDi, sQD[k], [&] { return Qi[k]; }, gmax2, omin, gj);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            svm_take_min(omin, gj, __shfl_xor(omin, o, 64), __shfl_xor(gj, o, 64));
-            gmax2 = fmax(gmax2, __shfl_xor(gmax2, o, 64));
-        }
-        if (lane == 0) { slotBv[wave] = omin; slotBi[wave] = gj; slotBg[wave] = gmax2; }
-        __syncthreads();
-        omin = slotBv[0];
-        gj = slotBi[0];
-        gmax2 = slotBg[0];
-#pragma unroll
-        for (int w = 1; w < SVM_SMO_WAVES; ++w) {
-            svm_take_min(omin, gj, slotBv[w], slotBi[w]);
-            gmax2 = fmax(gmax2, slotBg[w]);
-        }
+        svm_block_argmin_max(slots, omin, gj, gmax2);
         const int j = gj;
-        if (gmax + gmax2 < eps || i < 0 || j < 0) {   // optimal (without a pair only when the Gram holds a NaN)
+        if (svm_optimal(gmax, gmax2, eps, i, j)) {
             converged = 1;
             break;
         }
@@ -393,10 +426,7 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
         p.alpha[k] = sAlpha[k];
         p.G[k] = sG[k];
     }
-    if (tid == 0) {
-        p.state[0] = iter;
-        p.state[1] = converged;
-    }
+    svm_store_state(p, iter, converged);
 }
 
 // k_svm_smo for up to SVM_LARGE_MAX_N examples: one workgroup of 1024 threads per problem, thread t owns the elements t,
@@ -404,20 +434,18 @@ __global__ __launch_bounds__(SVM_SMO_THREADS) void k_svm_smo(const SvmProbDev* _
 // memberships the selections ask of alpha (libsvm's alpha_status; 16 KB).  alpha itself stays in global memory and is touched by
 // the owners of i and j only; QD and the rows of Q are read through the cache.  The owners of i and j publish alpha and G of the
 // pair through LDS slots, so that an iteration has three barriers as in k_svm_smo: behind either selection and behind the
-// publication.  The arithmetic is k_svm_smo's.
+// publication.  The arithmetic, the reductions and the slots are k_svm_smo's.
+// The iteration loop is written out a second time on purpose: where alpha, G, QD and Q live, how the pair is fetched around the
+// third barrier, and eager loads four at a time against the lazy Qik are the design; a hook for each would outweigh the lines saved.
 __global__ __launch_bounds__(SVM_LARGE_THREADS) void k_svm_smo_large(const SvmProbDev* __restrict__ P, int budget) {
     extern __shared__ double svm_lds[];
     const SvmProbDev p = P[blockIdx.x];
-    if (p.state[1] || p.state[0] >= p.max_iter) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (svm_done(p)) return;
+    const int tid = threadIdx.x;
     const int n = p.n, np = p.n_pad, n_pos = p.n_pos;
     double* sG = svm_lds;
-    double* slotAv = sG + np;                          // [16] Gmax of a wavefront
-    double* slotBv = slotAv + SVM_LARGE_WAVES;         // [16] its smallest obj_diff
-    double* slotBg = slotBv + SVM_LARGE_WAVES;         // [16] its Gmax2
-    double* pub = slotBg + SVM_LARGE_WAVES;            // alpha_i, G_i, alpha_j, G_j
-    int* slotAi = (int*)(pub + 4);                     // [16]
-    int* slotBi = slotAi + SVM_LARGE_WAVES;            // [16]
+    SvmLargeSlots& slots = *(SvmLargeSlots*)(sG + np);
+    double* pub = slots.pub;   // alpha_i, G_i, alpha_j, G_j
     uint8_t* sStatus = (uint8_t*)(sG + np) + SVM_LARGE_SLOT_BYTES;   // [np] bit 0: in I_up, bit 1: in I_low
     const float* __restrict__ Q = p.Q;
     const double* __restrict__ QD = p.QD;
@@ -435,14 +463,7 @@ __global__ __launch_bounds__(SVM_LARGE_THREADS) void k_svm_smo_large(const SvmPr
         double gmax = -INFINITY;
         int gi = -1;
         for (int k = tid; k < n; k += SVM_LARGE_THREADS) svm_scan_i(k, k < n_pos, (sStatus[k] & 1) != 0, sG[k], gmax, gi);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) svm_take_max(gmax, gi, __shfl_xor(gmax, o, 64), __shfl_xor(gi, o, 64));
-        if (lane == 0) { slotAv[wave] = gmax; slotAi[wave] = gi; }
-        __syncthreads();
-        gmax = slotAv[0];
-        gi = slotAi[0];
-#pragma unroll
-        for (int w = 1; w < SVM_LARGE_WAVES; ++w) svm_take_max(gmax, gi, slotAv[w], slotAi[w]);
+        svm_block_argmax(slots, gmax, gi);
         const int i = gi;
         double gmax2 = -INFINITY, omin = INFINITY;
         int gj = -1;
@@ -466,23 +487,9 @@ __global__ __launch_bounds__(SVM_LARGE_THREADS) void k_svm_smo_large(const SvmPr
                 }
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            svm_take_min(omin, gj, __shfl_xor(omin, o, 64), __shfl_xor(gj, o, 64));
-            gmax2 = fmax(gmax2, __shfl_xor(gmax2, o, 64));
-        }
-        if (lane == 0) { slotBv[wave] = omin; slotBi[wave] = gj; slotBg[wave] = gmax2; }
-        __syncthreads();
-        omin = slotBv[0];
-        gj = slotBi[0];
-        gmax2 = slotBg[0];
-#pragma unroll
-        for (int w = 1; w < SVM_LARGE_WAVES; ++w) {
-            svm_take_min(omin, gj, slotBv[w], slotBi[w]);
-            gmax2 = fmax(gmax2, slotBg[w]);
-        }
+        svm_block_argmin_max(slots, omin, gj, gmax2);
         const int j = gj;
-        if (gmax + gmax2 < eps || i < 0 || j < 0) {
+        if (svm_optimal(gmax, gmax2, eps, i, j)) {
             converged = 1;
             break;
         }
@@ -518,16 +525,13 @@ __global__ __launch_bounds__(SVM_LARGE_THREADS) void k_svm_smo_large(const SvmPr
     }
     // a thread's last writes to G are its own elements; alpha is in memory already
     for (int k = tid; k < n; k += SVM_LARGE_THREADS) p.G[k] = sG[k];
-    if (tid == 0) {
-        p.state[0] = iter;
-        p.state[1] = converged;
-    }
+    svm_store_state(p, iter, converged);
 }
 
-// The pieces of k_svm_finish and k_svm_finish_large.  Only for a problem that is done (converged or at max_iterations); for one
-// that the solver goes on with in the next launch the host needs the progress only.
+// The pieces of k_svm_finish.  Only for a problem that is done (converged or at max_iterations); for one that the solver goes on
+// with in the next launch the host needs the progress only.
 __device__ __forceinline__ bool svm_finish_pending(const SvmProbDev& p, bool first) {
-    if (p.state[1] || p.state[0] >= p.max_iter) return false;
+    if (svm_done(p)) return false;
     if (first) {
         fd_svm_train_info out = {};
         out.iterations = p.state[0];
@@ -593,54 +597,29 @@ __device__ __forceinline__ void svm_finish_info(const SvmProbDev& p, const doubl
     *p.info = out;
 }
 
-// rho, objective and counts by thread 0 of a problem's first block (alpha and G staged in LDS), and the single weight vector,
-// one thread per dimension
+// The finish of a problem (blockIdx.y).  The weight-vector form: the single weight vector, one thread per dimension over the
+// blocks along x, and rho, objective and counts by thread 0 of the first block.  SvForm: one block, no weight vector; the
+// sequential pass also writes sv_index and coef.  Staged: alpha and G go through LDS for the one thread (a problem of k_svm_smo,
+// at most SVM_MAX_N examples); one of k_svm_smo_large is read from memory.
+template <bool Staged, bool SvForm>
 __global__ __launch_bounds__(256) void k_svm_finish(const SvmProbDev* __restrict__ P) {
-    __shared__ double sA[SVM_MAX_N], sGf[SVM_MAX_N];
+    __shared__ double sA[Staged ? SVM_MAX_N : 1], sGf[Staged ? SVM_MAX_N : 1];
     const SvmProbDev p = P[blockIdx.y];
     const int tid = threadIdx.x, n = p.n;
     if (svm_finish_pending(p, blockIdx.x == 0 && tid == 0)) return;
-    svm_finish_weight(p, blockIdx.x * 256 + tid);
+    if (!SvForm) svm_finish_weight(p, blockIdx.x * 256 + tid);
     if (blockIdx.x != 0) return;
-    for (int i = tid; i < n; i += 256) {
-        sA[i] = p.alpha[i];
-        sGf[i] = p.G[i];
+    if (Staged) {
+        for (int i = tid; i < n; i += 256) {
+            sA[i] = p.alpha[i];
+            sGf[i] = p.G[i];
+        }
+        __syncthreads();
     }
-    __syncthreads();
-    if (tid != 0) return;
-    svm_finish_info<false>(p, sA, sGf);
+    if (tid == 0) svm_finish_info<SvForm>(p, Staged ? sA : p.alpha, Staged ? sGf : p.G);
 }
 
-// the same for a problem of k_svm_smo_large: the one thread reads alpha and G from memory
-__global__ __launch_bounds__(256) void k_svm_finish_large(const SvmProbDev* __restrict__ P) {
-    const SvmProbDev p = P[blockIdx.y];
-    const int tid = threadIdx.x;
-    if (svm_finish_pending(p, blockIdx.x == 0 && tid == 0)) return;
-    svm_finish_weight(p, blockIdx.x * 256 + tid);
-    if (blockIdx.x == 0 && tid == 0) svm_finish_info<false>(p, p.alpha, p.G);
-}
-
-// The finish of the support-vector form, one block per problem: no weight vector; the sequential pass also writes sv_index and
-// coef.  Large: alpha and G are read from memory as in k_svm_finish_large.
-template <bool Large>
-__global__ __launch_bounds__(256) void k_svm_finish_sv(const SvmProbDev* __restrict__ P) {
-    __shared__ double sA[Large ? 1 : SVM_MAX_N], sGf[Large ? 1 : SVM_MAX_N];
-    const SvmProbDev p = P[blockIdx.x];
-    const int tid = threadIdx.x, n = p.n;
-    if (svm_finish_pending(p, tid == 0)) return;
-    if (Large) {
-        if (tid == 0) svm_finish_info<true>(p, p.alpha, p.G);
-        return;
-    }
-    for (int i = tid; i < n; i += 256) {
-        sA[i] = p.alpha[i];
-        sGf[i] = p.G[i];
-    }
-    __syncthreads();
-    if (tid == 0) svm_finish_info<true>(p, sA, sGf);
-}
-
-// sv[q][k] = x[sv_index[q]][k] for the n_sv support vectors that k_svm_finish_sv listed (none while the problem is pending): one
+// sv[q][k] = x[sv_index[q]][k] for the n_sv support vectors that k_svm_finish listed (none while the problem is pending): one
 // thread per element, consecutive threads along d
 __global__ __launch_bounds__(256) void k_svm_gather_sv(const SvmProbDev* __restrict__ P) {
     const SvmProbDev p = P[blockIdx.y];
@@ -656,23 +635,12 @@ struct SvmTrainScratch {
     DevBuf xs, svList, sv;   // the support-vector form: xs; sv_index and coef; the gathered rows
 };
 
-// The support-vector form of a run (fd_kernel_svm_*): the checked kernel and, per problem, where the model goes (host).  The
-// first n_sv entries of sv_index / coefficients and the first n_sv rows of support_vectors are written.
-struct SvmSvOut {
-    int32_t* sv_index;
-    float* coefficients;
-    float* support_vectors;           // n x d, or NULL
-    std::vector<float>* sv_store;     // in place of support_vectors: resized to n_sv x d
-};
-struct SvmSvForm {
-    int32_t kernel, degree;
-    double gamma, coef0;
-    const SvmSvOut* outs;             // count entries, or NULL (the Gram alone)
-};
-
-SvmSvForm svm_checked_kernel(const char* who, const fd_svm_kernel* k) {
+// the run of a support-vector form (fd_kernel_svm_*) with its checked kernel; the solver follows from the number of examples
+FdSvmRunSpec svm_sv_spec(const char* who, const fd_svm_kernel* k, int64_t n) {
     if (!k) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
-    SvmSvForm f = {k->kernel, 0, 0.0, 0.0, nullptr};
+    FdSvmRunSpec f = {who, n > SVM_MAX_N};
+    f.svForm = true;
+    f.kernel = k->kernel;
     if (k->kernel == FD_KERNEL_POLY || k->kernel == FD_KERNEL_RBF) {
         if (!(k->p0 >= 0.0) || std::isinf(k->p0)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: gamma must be finite and not negative (%g)", who, k->p0);
         f.gamma = k->p0;
@@ -689,11 +657,22 @@ SvmSvForm svm_checked_kernel(const char* who, const fd_svm_kernel* k) {
     return f;
 }
 
-void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN = SVM_MAX_N) {
-    if (n_pos < 1 || n_neg < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
-    if ((int64_t)n_pos + n_neg > maxN) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, maxN);
-    if (d < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the feature length must be positive (%d)", who, d);
+// 0 for a shape the trainer takes, else which of svm_check_shape's messages applies
+int svm_shape_fault(int n_pos, int n_neg, int d, int maxN) {
+    if (n_pos < 1 || n_neg < 1) return 1;
+    if ((int64_t)n_pos + n_neg > maxN) return 2;
+    return d < 1 ? 3 : 0;
 }
+
+void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN) {
+    const int fault = svm_shape_fault(n_pos, n_neg, d, maxN);
+    if (fault == 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
+    if (fault == 2) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, maxN);
+    if (fault == 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the feature length must be positive (%d)", who, d);
+}
+
+// max_iterations = 0: libsvm's own cap
+inline int svm_default_max_iter(int n) { return std::max(10000000, 100 * n); }
 
 fd_svm_train_params svm_checked_params(const char* who, const fd_svm_train_params* prm) {
     if (!prm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
@@ -710,6 +689,30 @@ fd_svm_train_params svm_checked_params(const char* who, const fd_svm_train_param
 
 inline size_t svm_align(size_t v) { return (v + 255) / 256 * 256; }
 
+// The aligned byte counts of one problem's buffers, each written here and nowhere else: summed they size the reserves, one after
+// the other they place the problem.  SZ_X: the rows of a host caller; SZ_AOUT: alpha in the pinned area; SZ_XS, SZ_LIST (sv_index,
+// then coef, n_pad entries each) and SZ_SV (the gathered rows, where asked for): the support-vector form only.  The weights and
+// the list have the same size on the device and in the pinned area.
+enum { SZ_X, SZ_Q, SZ_DBL, SZ_W, SZ_AOUT, SZ_XS, SZ_LIST, SZ_SV, SZ_COUNT };
+struct SvmSizes {
+    size_t b[SZ_COUNT] = {};
+};
+SvmSizes svm_sizes(const fd_svm_train_problem& pr, const FdSvmRunSpec& spec, int c) {
+    const size_t n = (size_t)pr.n_pos + pr.n_neg, np = (size_t)svm_pad((int)n);
+    SvmSizes z;
+    if (!pr.is_device) z.b[SZ_X] = svm_align(sizeof(float) * n * pr.d);
+    z.b[SZ_Q] = svm_align(sizeof(float) * np * np);
+    z.b[SZ_DBL] = svm_align(sizeof(double) * np * 3);   // QD, alpha, G
+    z.b[SZ_W] = svm_align(sizeof(float) * pr.d);
+    z.b[SZ_AOUT] = svm_align(sizeof(double) * np);
+    if (spec.svForm) {
+        z.b[SZ_XS] = svm_align(sizeof(double) * np);
+        z.b[SZ_LIST] = svm_align(2 * sizeof(int32_t) * np);
+        if (spec.outs && (spec.outs[c].support_vectors || spec.outs[c].sv_store)) z.b[SZ_SV] = svm_align(sizeof(float) * n * pr.d);
+    }
+    return z;
+}
+
 // What one call works on: the problems' descriptors, and the layout of the context's pinned staging area (pageable copies
 // cost about a millisecond each on this stack): descriptors, infos, the host callers' X, and the weights / alpha to return.
 struct SvmRun {
@@ -721,84 +724,74 @@ struct SvmRun {
     size_t smoLds = 0;
 };
 
-// wOverride: device buffer that receives problem 0's weights in place of the scratch (the tracker's dweights)
-// large: the problems of fd_linear_svm_train_large (up to SVM_LARGE_MAX_N examples, Q always in memory)
-// form: the support-vector form with its kernel; NULL: the linear weight-vector form
-void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params& prm, float* wOverride,
-                 SvmRun& run, bool large = false, const SvmSvForm* form = nullptr) {
+void svm_prepare(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_train_problem* probs, const fd_svm_train_params& prm, SvmRun& run) {
     SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
-    size_t xBytes = 0, qBytes = 0, dblBytes = 0, wBytes = 0, outBytes = 0, xsBytes = 0, listBytes = 0, svBytes = 0;
-    auto wantsRows = [&](int c) { return form && form->outs && (form->outs[c].support_vectors || form->outs[c].sv_store); };
+    const char* who = spec.who;
+    std::vector<SvmSizes> sizes(count);
+    SvmSizes total;
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
-        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, large ? SVM_LARGE_MAX_N : SVM_MAX_N);
+        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, spec.large ? SVM_LARGE_MAX_N : SVM_MAX_N);
         if (!pr.x) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
-        const size_t n = (size_t)pr.n_pos + pr.n_neg, np = (size_t)svm_pad((int)n);
-        if (!pr.is_device) xBytes += svm_align(sizeof(float) * n * pr.d);
-        qBytes += svm_align(sizeof(float) * np * np);
-        dblBytes += svm_align(sizeof(double) * np * 3);
-        wBytes += svm_align(sizeof(float) * pr.d);
-        outBytes += svm_align(sizeof(float) * pr.d) + svm_align(sizeof(double) * np);
-        if (form) {
-            xsBytes += svm_align(sizeof(double) * np);
-            listBytes += svm_align(2 * sizeof(int32_t) * np);
-            outBytes += svm_align(2 * sizeof(int32_t) * np);
-            if (wantsRows(c)) svBytes += svm_align(sizeof(float) * n * pr.d);
-        }
+        sizes[c] = svm_sizes(pr, spec, c);
+        for (int k = 0; k < SZ_COUNT; ++k) total.b[k] += sizes[c].b[k];
     }
-    sc.x.reserve(xBytes);
+    sc.x.reserve(total.b[SZ_X]);
     try {
-        sc.q.reserve(qBytes);
+        sc.q.reserve(total.b[SZ_Q]);
     } catch (const FdError& e) {   // up to 1 GiB for a large problem: the caller learns what did not fit
-        FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for Q (%zu bytes): %s", who, qBytes, e.msg.c_str());
+        FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for Q (%zu bytes): %s", who, total.b[SZ_Q], e.msg.c_str());
     }
-    sc.dbl.reserve(dblBytes);
-    sc.w.reserve(wBytes);
+    sc.dbl.reserve(total.b[SZ_DBL]);
+    sc.w.reserve(total.b[SZ_W]);
     sc.desc.reserve(sizeof(SvmProbDev) * count);
     sc.info.reserve(sizeof(fd_svm_train_info) * count);
     sc.state.reserve(sizeof(int32_t) * 2 * count);
-    if (form) {
-        sc.xs.reserve(xsBytes);
-        sc.svList.reserve(listBytes);
+    if (spec.svForm) {
+        sc.xs.reserve(total.b[SZ_XS]);
+        sc.svList.reserve(total.b[SZ_LIST]);
         try {
-            sc.sv.reserve(svBytes);
+            sc.sv.reserve(total.b[SZ_SV]);
         } catch (const FdError& e) {
-            FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for the support vectors (%zu bytes): %s", who, svBytes, e.msg.c_str());
+            FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for the support vectors (%zu bytes): %s", who, total.b[SZ_SV], e.msg.c_str());
         }
     }
     run.infoOff = svm_align(sizeof(SvmProbDev) * count);
     const size_t xOff = run.infoOff + svm_align(sizeof(fd_svm_train_info) * count);
-    size_t outOff = xOff + xBytes;
-    run.pinned = (char*)fd_pinned(ctx, outOff + outBytes);
+    size_t outOff = xOff + total.b[SZ_X];
+    run.pinned = (char*)fd_pinned(ctx, outOff + total.b[SZ_W] + total.b[SZ_AOUT] + total.b[SZ_LIST]);
     SvmProbDev* hd = (SvmProbDev*)run.pinned;
     run.h.resize(count);
     run.outW.resize(count);
     run.outA.resize(count);
     run.outS.resize(count);
-    size_t xo = 0, qo = 0, dblo = 0, wo = 0, xso = 0, listo = 0, svo = 0;
+    SvmSizes at;   // where the next problem's share of each buffer begins
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
+        const SvmSizes& z = sizes[c];
         const int n = pr.n_pos + pr.n_neg, np = svm_pad(n);
-        SvmProbDev& D = run.h[c];
+        auto take = [&](const DevBuf& buf, int k) {
+            char* at_k = (char*)buf.p + at.b[k];
+            at.b[k] += z.b[k];
+            return at_k;
+        };
+        SvmProbDev D = {};
         if (pr.is_device) {
             D.x = pr.x;
         } else {
-            D.x = (const float*)((char*)sc.x.p + xo);
-            std::memcpy(run.pinned + xOff + xo, pr.x, sizeof(float) * (size_t)n * pr.d);
-            xo += svm_align(sizeof(float) * (size_t)n * pr.d);
+            std::memcpy(run.pinned + xOff + at.b[SZ_X], pr.x, sizeof(float) * (size_t)n * pr.d);
+            D.x = (const float*)take(sc.x, SZ_X);
         }
-        D.Q = (float*)((char*)sc.q.p + qo);
-        qo += svm_align(sizeof(float) * (size_t)np * np);
-        D.QD = (double*)((char*)sc.dbl.p + dblo);
+        D.Q = (float*)take(sc.q, SZ_Q);
+        D.QD = (double*)take(sc.dbl, SZ_DBL);
         D.alpha = D.QD + np;
         D.G = D.alpha + np;
-        dblo += svm_align(sizeof(double) * (size_t)np * 3);
-        D.w = (c == 0 && wOverride) ? wOverride : (float*)((char*)sc.w.p + wo);
-        wo += svm_align(sizeof(float) * pr.d);
+        D.w = (float*)take(sc.w, SZ_W);
+        if (c == 0 && spec.wOverride) D.w = spec.wOverride;
         run.outW[c] = outOff;
-        outOff += svm_align(sizeof(float) * pr.d);
+        outOff += z.b[SZ_W];
         run.outA[c] = outOff;
-        outOff += svm_align(sizeof(double) * (size_t)np);
+        outOff += z.b[SZ_AOUT];
         D.info = sc.info.as<fd_svm_train_info>() + c;
         D.state = sc.state.as<int32_t>() + 2 * c;
         D.Cp = prm.C * prm.weight_pos;
@@ -808,150 +801,39 @@ void svm_prepare(fd_ctx* ctx, const char* who, int count, const fd_svm_train_pro
         D.n = n;
         D.n_pad = np;
         D.d = pr.d;
-        D.q_in_lds = !large && svm_q_in_lds(n) ? 1 : 0;
-        D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : std::max(10000000, 100 * n);
-        D.xs = nullptr;
-        D.sv_index = nullptr;
-        D.coef = nullptr;
-        D.sv = nullptr;
-        D.gamma = D.coef0 = 0.0;
-        D.kernel = FD_KERNEL_LINEAR;
-        D.degree = 0;
-        if (form) {
-            D.xs = (double*)((char*)sc.xs.p + xso);
-            xso += svm_align(sizeof(double) * (size_t)np);
-            D.sv_index = (int32_t*)((char*)sc.svList.p + listo);
+        D.q_in_lds = !spec.large && svm_q_in_lds(n) ? 1 : 0;
+        D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : svm_default_max_iter(n);
+        if (spec.svForm) {
+            D.xs = (double*)take(sc.xs, SZ_XS);
+            D.sv_index = (int32_t*)take(sc.svList, SZ_LIST);
             D.coef = (float*)(D.sv_index + np);
-            listo += svm_align(2 * sizeof(int32_t) * (size_t)np);
-            if (wantsRows(c)) {
-                D.sv = (float*)((char*)sc.sv.p + svo);
-                svo += svm_align(sizeof(float) * (size_t)n * pr.d);
-            }
+            if (z.b[SZ_SV]) D.sv = (float*)take(sc.sv, SZ_SV);
             run.outS[c] = outOff;
-            outOff += svm_align(2 * sizeof(int32_t) * (size_t)np);
-            D.gamma = form->gamma;
-            D.coef0 = form->coef0;
-            D.kernel = form->kernel;
-            D.degree = form->degree;
+            outOff += z.b[SZ_LIST];
+            D.gamma = spec.gamma;
+            D.coef0 = spec.coef0;
+            D.degree = spec.degree;
         }
+        run.h[c] = D;
         hd[c] = D;
         run.maxPad = std::max(run.maxPad, np);
         run.maxD = std::max(run.maxD, pr.d);
-        run.smoLds = std::max(run.smoLds, large ? svm_large_lds(n) : svm_smo_lds(n, D.q_in_lds != 0));
+        run.smoLds = std::max(run.smoLds, spec.large ? svm_large_lds(n) : svm_smo_lds(n, D.q_in_lds != 0));
     }
-    if (xBytes) HIP_CHECK(hipMemcpyAsync(sc.x.p, run.pinned + xOff, xBytes, hipMemcpyHostToDevice, ctx->stream));
+    if (total.b[SZ_X]) HIP_CHECK(hipMemcpyAsync(sc.x.p, run.pinned + xOff, total.b[SZ_X], hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(sc.desc.p, hd, sizeof(SvmProbDev) * count, hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemsetAsync(sc.state.p, 0, sizeof(int32_t) * 2 * count, ctx->stream));
     const dim3 tiles(run.maxPad / 16, run.maxPad / 16, count);
-    if (!form) {
-        hipLaunchKernelGGL(k_svm_gram, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
-    } else if (form->kernel == FD_KERNEL_HIK) {
-        hipLaunchKernelGGL(k_svm_gram_hik, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
-    } else {
-        if (form->kernel == FD_KERNEL_RBF) {   // xs first, from the diagonal tiles
-            hipLaunchKernelGGL(k_svm_gram_kernel, dim3(run.maxPad / 16, 1, count), dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>(), 1);
-            HIP_CHECK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_svm_gram_kernel, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>(), 0);
+    void (*gram)(const SvmProbDev*) = k_svm_gram<FD_KERNEL_LINEAR>;
+    if (spec.kernel == FD_KERNEL_HIK) gram = k_svm_gram_hik;
+    if (spec.kernel == FD_KERNEL_POLY) gram = k_svm_gram<FD_KERNEL_POLY>;
+    if (spec.kernel == FD_KERNEL_RBF) {   // xs first, from the diagonal tiles
+        gram = k_svm_gram<FD_KERNEL_RBF>;
+        hipLaunchKernelGGL(k_svm_gram<SVM_GRAM_XS>, dim3(run.maxPad / 16, 1, count), dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        HIP_CHECK(hipGetLastError());
     }
+    hipLaunchKernelGGL(gram, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
     HIP_CHECK(hipGetLastError());
-}
-
-// Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Problem 0's weights go to wOverride
-// (device) when given.  Leaves ctx->stream synchronised.  large: one problem of up to SVM_LARGE_MAX_N examples on k_svm_smo_large.
-// form: the support-vector form (the problems' weights are NULL; form->outs receives the model).
-void svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
-                   fd_svm_train_info* infos, bool large, const SvmSvForm* form = nullptr) {
-    const fd_svm_train_params prm = svm_checked_params(who, params);
-    if (count < 1 || !probs || !infos) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument or no problem", who);
-    HIP_CHECK(hipSetDevice(ctx->device));
-    SvmRun run;
-    svm_prepare(ctx, who, count, probs, prm, wOverride, run, large, form);
-    SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
-    size_t rowElements = 0;   // the gather's grid: the largest n x d among the problems that want their support vectors' rows
-    for (int c = 0; c < count; ++c)
-        if (run.h[c].sv) rowElements = std::max(rowElements, (size_t)run.h[c].n * run.h[c].d);
-    static uint64_t ldsAllowed = 0, ldsAllowedLarge = 0;
-    if (large) fd_allow_lds(ctx, (const void*)k_svm_smo_large, (int)SVM_LDS_BUDGET, ldsAllowedLarge);
-    else fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
-    const fd_svm_train_info* hinfo = (const fd_svm_train_info*)(run.pinned + run.infoOff);
-    int launches = 0;
-    for (;;) {
-        if (large)
-            hipLaunchKernelGGL(k_svm_smo_large, dim3(count), dim3(SVM_LARGE_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
-        else
-            hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
-        HIP_CHECK(hipGetLastError());
-        ++launches;
-        if (form) {
-            hipLaunchKernelGGL(large ? k_svm_finish_sv<true> : k_svm_finish_sv<false>, dim3(count), dim3(large ? 64 : 256), 0, ctx->stream,
-                               sc.desc.as<SvmProbDev>());
-            if (rowElements) {
-                HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_svm_gather_sv, dim3((unsigned)((rowElements + 255) / 256), count), dim3(256), 0, ctx->stream,
-                                   sc.desc.as<SvmProbDev>());
-            }
-        } else {
-            hipLaunchKernelGGL(large ? k_svm_finish_large : k_svm_finish, dim3((run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream,
-                               sc.desc.as<SvmProbDev>());
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(run.pinned + run.infoOff, sc.info.p, sizeof(fd_svm_train_info) * count, hipMemcpyDeviceToHost, ctx->stream));
-        // the results ride along: in the usual case the first launch converges and this is the only wait
-        for (int c = 0; c < count; ++c) {
-            const SvmProbDev& D = run.h[c];
-            if (probs[c].weights && !(c == 0 && wOverride))
-                HIP_CHECK(hipMemcpyAsync(run.pinned + run.outW[c], D.w, sizeof(float) * D.d, hipMemcpyDeviceToHost, ctx->stream));
-            if (probs[c].alpha) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outA[c], D.alpha, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
-            if (form) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outS[c], D.sv_index, 2 * sizeof(int32_t) * D.n_pad, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        bool done = true;
-        for (int c = 0; c < count; ++c) done = done && (hinfo[c].converged || hinfo[c].iterations >= run.h[c].max_iter);
-        if (done) break;
-    }
-    for (int c = 0; c < count; ++c) {
-        infos[c] = hinfo[c];
-        infos[c].launches = launches;
-        const fd_svm_train_problem& pr = probs[c];
-        if (pr.weights && !(c == 0 && wOverride)) std::memcpy(pr.weights, run.pinned + run.outW[c], sizeof(float) * pr.d);
-        if (pr.alpha) std::memcpy(pr.alpha, run.pinned + run.outA[c], sizeof(double) * run.h[c].n);
-        if (pr.bias) *pr.bias = (float)infos[c].rho;
-    }
-    if (!form) return;
-    bool rows = false;
-    for (int c = 0; c < count; ++c) {   // the lists from the staging area; the rows, whose number is known only now, straight from the device
-        const SvmProbDev& D = run.h[c];
-        const SvmSvOut& o = form->outs[c];
-        const size_t nsv = (size_t)infos[c].n_sv;
-        std::memcpy(o.sv_index, run.pinned + run.outS[c], sizeof(int32_t) * nsv);
-        std::memcpy(o.coefficients, run.pinned + run.outS[c] + sizeof(int32_t) * D.n_pad, sizeof(float) * nsv);
-        if (o.sv_store) o.sv_store->resize(nsv * D.d);
-        float* dst = o.sv_store ? o.sv_store->data() : o.support_vectors;
-        if (D.sv && nsv) {
-            HIP_CHECK(hipMemcpyAsync(dst, D.sv, sizeof(float) * nsv * D.d, hipMemcpyDeviceToHost, ctx->stream));
-            rows = true;
-        }
-    }
-    if (rows) HIP_CHECK(hipStreamSynchronize(ctx->stream));
-}
-
-void svm_gram(fd_ctx* ctx, const char* who, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD, bool large,
-              const SvmSvForm* form = nullptr) {
-    HIP_CHECK(hipSetDevice(ctx->device));
-    fd_svm_train_problem pr = {};
-    pr.x = x;
-    pr.n_pos = n_pos;
-    pr.n_neg = n_neg;
-    pr.d = d;
-    pr.is_device = is_device;
-    fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
-    SvmRun run;
-    svm_prepare(ctx, who, 1, &pr, prm, nullptr, run, large, form);
-    const SvmProbDev& D = run.h[0];
-    HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
 fd_svm_train_problem svm_single_problem(const float* x, int n_pos, int n_neg, int d, int is_device, float* weights, float* bias, double* alpha) {
@@ -966,61 +848,147 @@ fd_svm_train_problem svm_single_problem(const float* x, int n_pos, int n_neg, in
     pr.alpha = alpha;
     return pr;
 }
+
+void svm_gram(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, nullptr, nullptr);
+    fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
+    SvmRun run;
+    svm_prepare(ctx, spec, 1, &pr, prm, run);
+    const SvmProbDev& D = run.h[0];
+    HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+// the two linear Gram entry points and the two single-problem linear trainers: `spec` names the one that was called
+int svm_linear_gram(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", spec.who);
+        svm_gram(ctx, spec, x, n_pos, n_neg, d, is_device, Q, QD);
+    });
+}
+int svm_linear_train(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params,
+                     float* weights, float* bias, double* alpha, fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", spec.who);
+        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, weights, bias, alpha);
+        fd_svm_train_run(ctx, spec, 1, &pr, params, info);
+    });
+}
 }  // namespace
 
-void fd_svm_train_run(fd_ctx* ctx, const char* who, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params, float* wOverride,
+// Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Leaves ctx->stream synchronised.
+// spec.large: one problem of up to SVM_LARGE_MAX_N examples on k_svm_smo_large.  spec.svForm: the problems' weights are NULL;
+// spec.outs receives the model.
+void fd_svm_train_run(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params,
                       fd_svm_train_info* infos) {
-    svm_train_run(ctx, who, count, probs, params, wOverride, infos, false);
+    const char* who = spec.who;
+    const bool large = spec.large, svForm = spec.svForm;
+    float* const wOverride = spec.wOverride;
+    const fd_svm_train_params prm = svm_checked_params(who, params);
+    if (count < 1 || !probs || !infos) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument or no problem", who);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    SvmRun run;
+    svm_prepare(ctx, spec, count, probs, prm, run);
+    SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
+    size_t rowElements = 0;   // the gather's grid: the largest n x d among the problems that want their support vectors' rows
+    for (int c = 0; c < count; ++c)
+        if (run.h[c].sv) rowElements = std::max(rowElements, (size_t)run.h[c].n * run.h[c].d);
+    static uint64_t ldsAllowed = 0, ldsAllowedLarge = 0;
+    if (large) fd_allow_lds(ctx, (const void*)k_svm_smo_large, (int)SVM_LDS_BUDGET, ldsAllowedLarge);
+    else fd_allow_lds(ctx, (const void*)k_svm_smo, (int)SVM_LDS_BUDGET, ldsAllowed);
+    const auto finish = large ? (svForm ? k_svm_finish<false, true> : k_svm_finish<false, false>)
+                              : (svForm ? k_svm_finish<true, true> : k_svm_finish<true, false>);
+    const fd_svm_train_info* hinfo = (const fd_svm_train_info*)(run.pinned + run.infoOff);
+    int launches = 0;
+    for (;;) {
+        if (large)
+            hipLaunchKernelGGL(k_svm_smo_large, dim3(count), dim3(SVM_LARGE_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
+        else
+            hipLaunchKernelGGL(k_svm_smo, dim3(count), dim3(SVM_SMO_THREADS), run.smoLds, ctx->stream, sc.desc.as<SvmProbDev>(), prm.launch_iterations);
+        HIP_CHECK(hipGetLastError());
+        ++launches;
+        hipLaunchKernelGGL(finish, dim3(svForm ? 1 : (run.maxD + 255) / 256, count), dim3(256), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        if (rowElements) {
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_svm_gather_sv, dim3((unsigned)((rowElements + 255) / 256), count), dim3(256), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(run.pinned + run.infoOff, sc.info.p, sizeof(fd_svm_train_info) * count, hipMemcpyDeviceToHost, ctx->stream));
+        // the results ride along: in the usual case the first launch converges and this is the only wait
+        for (int c = 0; c < count; ++c) {
+            const SvmProbDev& D = run.h[c];
+            if (probs[c].weights && !(c == 0 && wOverride))
+                HIP_CHECK(hipMemcpyAsync(run.pinned + run.outW[c], D.w, sizeof(float) * D.d, hipMemcpyDeviceToHost, ctx->stream));
+            if (probs[c].alpha) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outA[c], D.alpha, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+            if (svForm) HIP_CHECK(hipMemcpyAsync(run.pinned + run.outS[c], D.sv_index, 2 * sizeof(int32_t) * D.n_pad, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        bool done = true;
+        for (int c = 0; c < count; ++c) done = done && (hinfo[c].converged || hinfo[c].iterations >= run.h[c].max_iter);
+        if (done) break;
+    }
+    for (int c = 0; c < count; ++c) {
+        infos[c] = hinfo[c];
+        infos[c].launches = launches;
+        const fd_svm_train_problem& pr = probs[c];
+        if (pr.weights && !(c == 0 && wOverride)) std::memcpy(pr.weights, run.pinned + run.outW[c], sizeof(float) * pr.d);
+        if (pr.alpha) std::memcpy(pr.alpha, run.pinned + run.outA[c], sizeof(double) * run.h[c].n);
+        if (pr.bias) *pr.bias = (float)infos[c].rho;
+    }
+    if (!svForm) return;
+    bool rows = false;
+    for (int c = 0; c < count; ++c) {   // the lists from the staging area; the rows, whose number is known only now, straight from the device
+        const SvmProbDev& D = run.h[c];
+        const FdSvmSvOut& o = spec.outs[c];
+        const size_t nsv = (size_t)infos[c].n_sv;
+        std::memcpy(o.sv_index, run.pinned + run.outS[c], sizeof(int32_t) * nsv);
+        std::memcpy(o.coefficients, run.pinned + run.outS[c] + sizeof(int32_t) * D.n_pad, sizeof(float) * nsv);
+        if (o.sv_store) o.sv_store->resize(nsv * D.d);
+        float* dst = o.sv_store ? o.sv_store->data() : o.support_vectors;
+        if (D.sv && nsv) {
+            HIP_CHECK(hipMemcpyAsync(dst, D.sv, sizeof(float) * nsv * D.d, hipMemcpyDeviceToHost, ctx->stream));
+            rows = true;
+        }
+    }
+    if (rows) HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
 extern "C" {
 
 int fd_linear_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* max_iterations) {
-    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    if (svm_shape_fault(n_pos, n_neg, d, SVM_MAX_N)) return FD_ERR_INVALID_ARGUMENT;
     const int n = n_pos + n_neg;
     if (q_in_lds) *q_in_lds = svm_q_in_lds(n) ? 1 : 0;
-    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    if (max_iterations) *max_iterations = svm_default_max_iter(n);
     return FD_OK;
 }
 
 int fd_linear_svm_train_large_limits(int n_pos, int n_neg, int d, int* lds_bytes, int* max_iterations) {
-    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_LARGE_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    if (svm_shape_fault(n_pos, n_neg, d, SVM_LARGE_MAX_N)) return FD_ERR_INVALID_ARGUMENT;
     const int n = n_pos + n_neg;
     if (lds_bytes) *lds_bytes = (int)svm_large_lds(n);
-    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    if (max_iterations) *max_iterations = svm_default_max_iter(n);
     return FD_OK;
 }
 
 int fd_linear_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
-    return fd_guard(ctx, [&] {
-        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_gram: NULL argument");
-        svm_gram(ctx, "fd_linear_svm_gram", x, n_pos, n_neg, d, is_device, Q, QD, false);
-    });
+    return svm_linear_gram(ctx, {"fd_linear_svm_gram", false}, x, n_pos, n_neg, d, is_device, Q, QD);
 }
 
 int fd_linear_svm_gram_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
-    return fd_guard(ctx, [&] {
-        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_gram_large: NULL argument");
-        svm_gram(ctx, "fd_linear_svm_gram_large", x, n_pos, n_neg, d, is_device, Q, QD, true);
-    });
+    return svm_linear_gram(ctx, {"fd_linear_svm_gram_large", true}, x, n_pos, n_neg, d, is_device, Q, QD);
 }
 
 int fd_linear_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params, float* weights,
                         float* bias, double* alpha, fd_svm_train_info* info) {
-    return fd_guard(ctx, [&] {
-        if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train: NULL argument");
-        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, weights, bias, alpha);
-        svm_train_run(ctx, "fd_linear_svm_train", 1, &pr, params, nullptr, info, false);
-    });
+    return svm_linear_train(ctx, {"fd_linear_svm_train", false}, x, n_pos, n_neg, d, is_device, params, weights, bias, alpha, info);
 }
 
 int fd_linear_svm_train_large(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_train_params* params,
                               float* weights, float* bias, double* alpha, fd_svm_train_info* info) {
-    return fd_guard(ctx, [&] {
-        if (!ctx || !x || !weights || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_large: NULL argument");
-        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, weights, bias, alpha);
-        svm_train_run(ctx, "fd_linear_svm_train_large", 1, &pr, params, nullptr, info, true);
-    });
+    return svm_linear_train(ctx, {"fd_linear_svm_train_large", true}, x, n_pos, n_neg, d, is_device, params, weights, bias, alpha, info);
 }
 
 int fd_linear_svm_train_batch(fd_ctx* ctx, int count, const fd_svm_train_problem* problems, const fd_svm_train_params* params, fd_svm_train_info* infos) {
@@ -1029,25 +997,24 @@ int fd_linear_svm_train_batch(fd_ctx* ctx, int count, const fd_svm_train_problem
         if (count > 65535) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: %d problems, at most 65535", count);
         for (int c = 0; c < count && problems; ++c)
             if (!problems[c].weights || !problems[c].bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_linear_svm_train_batch: NULL argument in problem %d", c);
-        fd_svm_train_run(ctx, "fd_linear_svm_train_batch", count, problems, params, nullptr, infos);
+        fd_svm_train_run(ctx, {"fd_linear_svm_train_batch"}, count, problems, params, infos);
     });
 }
 
 /* ---- the support-vector form: any kernel of fd_svm_model ---- */
 int fd_kernel_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* large, int* max_iterations) {
-    if (n_pos < 1 || n_neg < 1 || (int64_t)n_pos + n_neg > SVM_LARGE_MAX_N || d < 1) return FD_ERR_INVALID_ARGUMENT;
+    if (svm_shape_fault(n_pos, n_neg, d, SVM_LARGE_MAX_N)) return FD_ERR_INVALID_ARGUMENT;
     const int n = n_pos + n_neg;
     if (q_in_lds) *q_in_lds = n <= SVM_MAX_N && svm_q_in_lds(n) ? 1 : 0;
     if (large) *large = n > SVM_MAX_N ? 1 : 0;
-    if (max_iterations) *max_iterations = std::max(10000000, 100 * n);
+    if (max_iterations) *max_iterations = svm_default_max_iter(n);
     return FD_OK;
 }
 
 int fd_kernel_svm_gram(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel, float* Q, double* QD) {
     return fd_guard(ctx, [&] {
         if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_gram: NULL argument");
-        const SvmSvForm form = svm_checked_kernel("fd_kernel_svm_gram", kernel);
-        svm_gram(ctx, "fd_kernel_svm_gram", x, n_pos, n_neg, d, is_device, Q, QD, (int64_t)n_pos + n_neg > SVM_MAX_N, &form);
+        svm_gram(ctx, svm_sv_spec("fd_kernel_svm_gram", kernel, (int64_t)n_pos + n_neg), x, n_pos, n_neg, d, is_device, Q, QD);
     });
 }
 
@@ -1056,11 +1023,11 @@ int fd_kernel_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d
                         fd_svm_train_info* info) {
     return fd_guard(ctx, [&] {
         if (!ctx || !x || !sv_index || !coefficients || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train: NULL argument");
-        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train", kernel);
-        const SvmSvOut out = {sv_index, coefficients, support_vectors, nullptr};
-        form.outs = &out;
+        FdSvmRunSpec spec = svm_sv_spec("fd_kernel_svm_train", kernel, (int64_t)n_pos + n_neg);
+        const FdSvmSvOut out = {sv_index, coefficients, support_vectors, nullptr};
+        spec.outs = &out;
         const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, bias, alpha);
-        svm_train_run(ctx, "fd_kernel_svm_train", 1, &pr, params, nullptr, info, (int64_t)n_pos + n_neg > SVM_MAX_N, &form);
+        fd_svm_train_run(ctx, spec, 1, &pr, params, info);
     });
 }
 
@@ -1070,16 +1037,16 @@ int fd_kernel_svm_train_model(fd_ctx* ctx, const float* x, int n_pos, int n_neg,
     int rc = fd_guard(ctx, [&] {
         if (!ctx || !x || !out || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_model: NULL argument");
         *out = nullptr;
-        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train_model", kernel);
+        FdSvmRunSpec spec = svm_sv_spec("fd_kernel_svm_train_model", kernel, (int64_t)n_pos + n_neg);
         svm_check_shape("fd_kernel_svm_train_model", n_pos, n_neg, d, SVM_LARGE_MAX_N);   // before the lists are sized by n
         const int n = n_pos + n_neg;
         std::vector<int32_t> svIndex(n);
         std::vector<float> coef(n), rows;
         float bias = 0.f;
-        const SvmSvOut o = {svIndex.data(), coef.data(), nullptr, &rows};
-        form.outs = &o;
+        const FdSvmSvOut o = {svIndex.data(), coef.data(), nullptr, &rows};
+        spec.outs = &o;
         const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, &bias, nullptr);
-        svm_train_run(ctx, "fd_kernel_svm_train_model", 1, &pr, params, nullptr, info, n > SVM_MAX_N, &form);
+        fd_svm_train_run(ctx, spec, 1, &pr, params, info);
         if (info->n_sv < 1) FD_THROW(FD_ERR_RUNTIME, "fd_kernel_svm_train_model: the trained model has no support vector");
         fd_svm_model md = {};
         md.kernel = kernel->kernel;
@@ -1106,17 +1073,17 @@ int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_
     return fd_guard(ctx, [&] {
         if (!ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: NULL argument");
         if (count > 65535) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: %d problems, at most 65535", count);
-        SvmSvForm form = svm_checked_kernel("fd_kernel_svm_train_batch", kernel);
+        FdSvmRunSpec spec = svm_sv_spec("fd_kernel_svm_train_batch", kernel, 0);   // the batch runs on the small solver
         std::vector<fd_svm_train_problem> probs;
-        std::vector<SvmSvOut> outs;
+        std::vector<FdSvmSvOut> outs;
         for (int c = 0; c < count && problems; ++c) {
             const fd_kernel_svm_train_problem& pr = problems[c];
             if (!pr.sv_index || !pr.coefficients || !pr.bias) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_batch: NULL argument in problem %d", c);
             probs.push_back(svm_single_problem(pr.x, pr.n_pos, pr.n_neg, pr.d, pr.is_device, nullptr, pr.bias, pr.alpha));
-            outs.push_back(SvmSvOut{pr.sv_index, pr.coefficients, pr.support_vectors, nullptr});
+            outs.push_back(FdSvmSvOut{pr.sv_index, pr.coefficients, pr.support_vectors, nullptr});
         }
-        form.outs = outs.data();
-        svm_train_run(ctx, "fd_kernel_svm_train_batch", count, problems ? probs.data() : nullptr, params, nullptr, infos, false, &form);
+        spec.outs = outs.data();
+        fd_svm_train_run(ctx, spec, count, problems ? probs.data() : nullptr, params, infos);
     });
 }
 

@@ -219,7 +219,7 @@ def test_trained_model_scores_its_examples(capi, ctx, name, kernel):
 
 
 # ---------------- relaunch, iteration limit ----------------
-@pytest.mark.parametrize("name,kernel", [("b", RBF), ("c", K.KERNELS[3]), ("e", HIK)], ids=lambda v: v if isinstance(v, str) else K.kernel_id(v))
+@pytest.mark.parametrize("name,kernel", [("b", RBF), ("c", K.KERNELS[3]), ("e", HIK), ("large", RBF)], ids=lambda v: v if isinstance(v, str) else K.kernel_id(v))
 def test_relaunch_gives_the_same_bits(capi, ctx, name, kernel):
     prm = (1.0, 1.0, 1.0)
     want = _model_on_device_q(capi, ctx, name, kernel, prm)
