@@ -154,6 +154,19 @@ class fd_kernel_svm_train_problem(C.Structure):
                 ("alpha", C.c_void_p)]
 
 
+class fd_svm_one_class_params(C.Structure):
+    _fields_ = [("nu", C.c_double), ("eps", C.c_double), ("max_iterations", C.c_int32), ("launch_iterations", C.c_int32)]
+
+
+FD_SVM_CV_FOLDS = 5
+FD_SVM_SIGMOID_CONVERGED, FD_SVM_SIGMOID_MAX_ITERATIONS, FD_SVM_SIGMOID_LINE_SEARCH_FAILED = 0, 1, 2
+
+
+class fd_svm_cv_info(C.Structure):
+    _fields_ = [("fold", fd_svm_train_info * FD_SVM_CV_FOLDS), ("fold_trained", C.c_int32 * FD_SVM_CV_FOLDS),
+                ("fold_constant", C.c_double * FD_SVM_CV_FOLDS), ("newton_iterations", C.c_int32), ("status", C.c_int32)]
+
+
 class fd_aggregated_params(C.Structure):
     _fields_ = [("fhog", fd_fhog_params), ("window_w", C.c_int32), ("window_h", C.c_int32), ("octave_layer_count", C.c_int32),
                 ("min_window_width", C.c_int32), ("width_scale", C.c_float), ("height_scale", C.c_float), ("svm_weights", C.c_void_p),
@@ -316,6 +329,20 @@ _SIGS = {
                                             C.POINTER(fd_svm_train_info)]),
     "fd_kernel_svm_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fd_svm_kernel), C.POINTER(fd_svm_train_params), C.c_void_p]),
     "fd_kernel_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_one_class_svm_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel), C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "fd_one_class_svm_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
+                                         C.POINTER(fd_svm_one_class_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(fd_svm_train_info)]),
+    "fd_one_class_svm_train_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
+                                               C.POINTER(fd_svm_one_class_params), C.c_float, C.c_double, C.c_double, C.POINTER(C.c_void_p),
+                                               C.POINTER(fd_svm_train_info)]),
+    "fd_one_class_svm_train_limits": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_kernel_svm_cv_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
+                                           C.POINTER(fd_svm_train_params), C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                           C.c_void_p, C.POINTER(fd_svm_cv_info)]),
+    "fd_svm_sigmoid_train": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int)]),
     "fd_aggregated_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fd_aggregated_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "fd_aggregated_set_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
@@ -1549,6 +1576,80 @@ def kernel_svm_train_batch(ctx, problems, kernel, **kw):
         m = infos[c].n_sv
         out.append((svis[c][:m].copy(), coefs[c][:m].copy(), svs[c][:m].copy(), float(biases[c]), alphas[c], _svm_info(infos[c])))
     return out
+
+
+def svm_one_class_params(nu=0.5, eps=0.0, max_iterations=0, launch_iterations=0):
+    """fd_svm_one_class_params"""
+    return fd_svm_one_class_params(float(nu), float(eps), int(max_iterations), int(launch_iterations))
+
+
+def one_class_svm_train_limits(n, d):
+    """fd_one_class_svm_train_limits (host only): (q_in_lds, large, max_iterations); FdError for sizes the trainer refuses"""
+    q, l, m = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fd_one_class_svm_train_limits(n, d, C.byref(q), C.byref(l), C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_one_class_svm_train_limits: invalid sizes (%d, %d)" % (n, d))
+    return bool(q.value), bool(l.value), m.value
+
+
+def one_class_svm_gram(ctx, x, kernel, nu):
+    """fd_one_class_svm_gram: (Q float32 (n, n), QD float64 (n,), G0 float64 (n,) -- the start gradient of this nu)"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    q, qd, g0 = np.zeros((n, n), np.float32), np.zeros(n, np.float64), np.zeros(n, np.float64)
+    ctx.check(lib().fd_one_class_svm_gram(ctx.h, xp, n, d, dev, C.byref(k), nu, _ptr(q), _ptr(qd), _ptr(g0)))
+    return q, qd, g0
+
+
+def one_class_svm_train(ctx, x, kernel, want_support_vectors=True, **kw):
+    """fd_one_class_svm_train: (sv_index, coefficients, support_vectors or None, bias, alpha, info dict) like kernel_svm_train's;
+    keywords as svm_one_class_params"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    svi, coef, alpha, bias = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float64), C.c_float()
+    sv = np.zeros((n, d), np.float32) if want_support_vectors else None
+    prm, info = svm_one_class_params(**kw), fd_svm_train_info()
+    ctx.check(lib().fd_one_class_svm_train(ctx.h, xp, n, d, dev, C.byref(k), C.byref(prm), _ptr(svi), _ptr(coef), _ptr(sv), C.byref(bias),
+                                           _ptr(alpha), C.byref(info)))
+    m = info.n_sv
+    return svi[:m].copy(), coef[:m].copy(), (sv[:m].copy() if sv is not None else None), bias.value, alpha, _svm_info(info)
+
+
+def one_class_svm_train_model(ctx, x, kernel, threshold=0.0, logistic_a=0.00556, logistic_b=-2.95, **kw):
+    """fd_one_class_svm_train_model: (Svm, info dict); FdError (FD_ERR_RUNTIME) when rho is not finite (nu = 1)"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    prm, info, h = svm_one_class_params(**kw), fd_svm_train_info(), C.c_void_p()
+    ctx.check(lib().fd_one_class_svm_train_model(ctx.h, xp, n, d, dev, C.byref(k), C.byref(prm), threshold, logistic_a, logistic_b, C.byref(h),
+                                                 C.byref(info)))
+    return Svm.from_handle(ctx, h, d), _svm_info(info)
+
+
+def svm_sigmoid_train(dec_values, n_pos):
+    """fd_svm_sigmoid_train (host only): (probA, probB, iterations, status) of libsvm's sigmoid_train on decision values whose
+    first n_pos belong to positive examples"""
+    dec = _c(dec_values, np.float64).reshape(-1)
+    a, b, it, st = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    rc = lib().fd_svm_sigmoid_train(len(dec), _ptr(dec) if len(dec) else None, n_pos, C.byref(a), C.byref(b), C.byref(it), C.byref(st))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_svm_sigmoid_train: invalid arguments (%d, %d)" % (len(dec), n_pos))
+    return a.value, b.value, it.value, st.value
+
+
+def kernel_svm_cv_sigmoid(ctx, x, n_pos, kernel, perm, **kw):
+    """fd_kernel_svm_cv_sigmoid: (probA, probB, dec_values float64 (n,), info) -- info: folds (a list of five dicts: the fold's
+    train info, trained, constant), newton_iterations, status; perm: n ints; keywords as svm_train_params"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    k = _svm_kernel(kernel)
+    perm = _c(perm, np.int32).reshape(-1)
+    if len(perm) != n:
+        raise ValueError("perm has n entries")
+    dec, a, b = np.zeros(n, np.float64), C.c_double(), C.c_double()
+    prm, ci = svm_train_params(**kw), fd_svm_cv_info()
+    ctx.check(lib().fd_kernel_svm_cv_sigmoid(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(k), C.byref(prm), _ptr(perm), C.byref(a), C.byref(b),
+                                             _ptr(dec), C.byref(ci)))
+    folds = [dict(_svm_info(ci.fold[f]), trained=bool(ci.fold_trained[f]), constant=ci.fold_constant[f]) for f in range(FD_SVM_CV_FOLDS)]
+    return a.value, b.value, dec, dict(folds=folds, newton_iterations=ci.newton_iterations, status=ci.status)
 
 
 # fd_aggregated_layer: one feature layer of an aggregated-features detector

@@ -465,12 +465,13 @@ struct FdSvmSvOut {
 // One run of the trainer
 struct FdSvmRunSpec {
     const char* who;                  // the entry point, for the messages
-    bool large = false;               // the solver for up to FD_SVM_LARGE_MAX_N examples (one problem, Q always in memory); else up to 1024
+    bool large = false;               // the solver for up to FD_SVM_LARGE_MAX_N examples (Q always in memory); else up to 1024
     float* wOverride = nullptr;       // device memory that receives problem 0's weights in place of its host buffer (the tracker's dweights)
     bool svForm = false;              // the model as support vectors and coefficients of `kernel` (checked); else one linear weight vector
     int32_t kernel = FD_KERNEL_LINEAR, degree = 0;
     double gamma = 0.0, coef0 = 0.0;
     const FdSvmSvOut* outs = nullptr; // svForm: one entry per problem, or NULL (the Gram alone)
+    double nu = 0.0;                  // > 0: one-class problems (n_neg = 0, linear term 0, libsvm's start state for this nu); svForm only
 };
 // trains `count` problems in one set of launches.  Throws FdError; leaves ctx->stream synchronised.
 void fd_svm_train_run(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params,

@@ -27,6 +27,14 @@
 //                       (float)(alpha_i y_i); no weight vector
 //   k_svm_gather_sv     the support vectors' rows into a dense [n_sv][d] buffer
 //
+// One-class models and libsvm's sigmoid fit for a C-SVC (fd_one_class_svm_*, fd_kernel_svm_cv_sigmoid, DESIGN.md section 4.11;
+// solve_one_class svm.cpp:1577-1607, svm_binary_svc_probability :1940-2024, k_function :342-420, sigmoid_train :1752-1863):
+//   k_svm_one_class_start   behind the Gram of a problem of positives: libsvm's start state for nu and its gradient, summed as
+//                       Solver::Solve does; the solvers and the finish follow unchanged (the linear term is in the descriptor)
+//   k_svm_gather_rows   a cross-validation fold's rows into the fold's block; the five folds then train as one batch
+//   k_svm_cv_decision<Kernel>   the held-out examples' decision values in double, k_function's and svm_predict_values' order
+// The Newton fit on the decision values is host code (svm_sigmoid_train, libm's exp and log).
+//
 // A problem is n_pos positive rows followed by n_neg negative rows, so y_i = +1 for i < n_pos and libsvm's class grouping is the
 // identity; the bound status is alpha compared with 0 and C as update_alpha_status does.
 #include "fd_internal.hpp"
@@ -70,6 +78,11 @@ struct SvmProbDev {
     float* sv;                 // n x d: their rows; NULL when not asked for
     double gamma, coef0;       // of the polynomial and RBF kernels; the host picks the kernel's instantiation of k_svm_gram
     int32_t degree;
+    // the linear term p of the dual, the same for every example: -1 (C-SVC), 0 (one-class)
+    double lin;
+    // one-class only (solve_one_class): alpha_i = 1 for i < oc_full, alpha_oc_full = oc_frac, 0 behind
+    int32_t oc_full;
+    double oc_frac;
 };
 
 // The LDS slots of a solver: per wavefront what either block reduction leaves, and for k_svm_smo_large (Pub = 4) the pair's
@@ -219,6 +232,25 @@ __global__ __launch_bounds__(64) void k_svm_gram_hik(const SvmProbDev* __restric
         if (row >= p.n || col >= p.n) acc[q] = 0.0;
     }
     svm_store_tile(p, ti, tj, acc);
+}
+
+// The start state of a one-class problem (solve_one_class svm.cpp:1586-1593 and the gradient Solver::Solve builds from it
+// :571-588), behind the Gram launch, which ran as for n_pos = n: alpha_i = 1 for i < oc_full, oc_frac at oc_full, 0 behind, and
+// G_j = 0 + sum over the i with alpha_i > 0, ascending, of alpha_i * (double)Q_ij -- a product, then a sum, as G[j] += alpha_i *
+// Q_i[j] is.  One thread per j: consecutive threads read consecutive floats of row i.
+__global__ __launch_bounds__(256) void k_svm_one_class_start(const SvmProbDev* __restrict__ P) {
+    const SvmProbDev p = P[blockIdx.y];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= p.n) return;
+    const double aj = j < p.oc_full ? 1.0 : (j == p.oc_full ? p.oc_frac : 0.0);
+    double g = p.lin;
+    const int last = min(p.oc_full, p.n - 1);   // the last i whose alpha can be positive
+    for (int i = 0; i <= last; ++i) {
+        const double ai = i < p.oc_full ? 1.0 : p.oc_frac;
+        if (ai > 0.0) g += ai * (double)p.Q[(size_t)i * p.n_pad + j];
+    }
+    p.alpha[j] = aj;
+    p.G[j] = g;
 }
 
 // (value, index) of the larger value, ties to the higher index: what a scan in index order with >= leaves
@@ -576,7 +608,7 @@ __device__ __forceinline__ void svm_finish_info(const SvmProbDev& p, const doubl
             ++nFree;
             sumFree += yG;
         }
-        obj += a * (g + -1.0);
+        obj += a * (g + p.lin);
         if (a > 0.0) {
             if (EmitSv) {
                 p.sv_index[nSv] = i;
@@ -630,9 +662,100 @@ __global__ __launch_bounds__(256) void k_svm_gather_sv(const SvmProbDev* __restr
     p.sv[e] = p.x[(size_t)p.sv_index[q] * p.d + (e - q * p.d)];
 }
 
+// out[q][k] = x[idx[q]][k]: the rows of a cross-validation fold's training part, positives first, into the fold's block
+__global__ __launch_bounds__(256) void k_svm_gather_rows(const float* __restrict__ x, const int32_t* __restrict__ idx, float* __restrict__ out,
+                                                         size_t elements, int d) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= elements) return;
+    const size_t q = e / d;
+    out[e] = x[(size_t)idx[q] * d + (e - q * d)];
+}
+
+// The decision values of the held-out examples of the (at most five) folds of fd_kernel_svm_cv_sigmoid: what svm_predict_values
+// (svm.cpp:2506-2562) gives for a two-class model, sum_s (alpha_s y_s) k_function(x, sv_s) - rho in double, s in the model's
+// order, k_function (:342-420) summing in feature order: x y, (x - y)^2, min.  The rows are addressed through index lists into
+// the examples: sv lists a fold's support vectors in ascending fold index (positives first), held its held-out examples.
+struct SvmCvFoldDev {
+    const int32_t* sv;
+    const double* coef;     // alpha_s y_s, double
+    const int32_t* held;
+    int32_t n_sv, n_held;   // n_held = 0: a fold that trained nothing
+    double rho;
+};
+struct SvmCvDev {
+    const float* x;         // n x d
+    double* dec;            // n, in example order
+    int32_t d, degree;
+    double gamma, coef0;
+    SvmCvFoldDev fold[FD_SVM_CV_FOLDS];
+};
+// One wavefront per 16 held-out rows (blockIdx.x) of a fold (blockIdx.y), k_svm_gram_hik's pattern: 16 support vectors at a
+// time, feature chunks of both operand tiles through padded LDS, lane (c, kq) accumulating the pairs (held kq + 4 q, sv c) in
+// double with k ascending.  After a tile the 16 x 16 kernel values go through LDS and lane h < 16 adds coef_s K_hs to its row's
+// sum, s ascending; the tiles are walked in ascending order, - rho comes last.  Rows past the lists read the lists' first row.
+constexpr int SVM_CV_KC = 64;
+template <int Kernel>
+__global__ __launch_bounds__(64) void k_svm_cv_decision(const SvmCvDev P) {
+    __shared__ float sA[16][SVM_CV_KC + 1], sB[16][SVM_CV_KC + 1];
+    __shared__ double sK[16][17];
+    __shared__ int32_t sHeld[16], sSv[16];
+    const SvmCvFoldDev f = P.fold[blockIdx.y];
+    const int h0 = blockIdx.x * 16;
+    if (h0 >= f.n_held) return;
+    const int lane = threadIdx.x, c = lane & 15, kq = lane >> 4, d = P.d;
+    if (lane < 16) sHeld[lane] = f.held[h0 + lane < f.n_held ? h0 + lane : 0];
+    double sum = 0.0;
+    for (int s0 = 0; s0 < f.n_sv; s0 += 16) {
+        if (lane < 16) sSv[lane] = f.sv[s0 + lane < f.n_sv ? s0 + lane : 0];
+        __syncthreads();
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k0 = 0; k0 < d; k0 += SVM_CV_KC) {
+            const int kn = min(SVM_CV_KC, d - k0);
+            const int kc = k0 + (lane < kn ? lane : 0);   // in-range address for the masked lanes
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sA[r][lane] = P.x[(size_t)sHeld[r] * d + kc];
+                sB[r][lane] = P.x[(size_t)sSv[r] * d + kc];
+            }
+            __syncthreads();
+            for (int k = 0; k < kn; ++k) {
+                const float b = sB[c][k];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float a = sA[kq + 4 * q][k];
+                    if (Kernel == FD_KERNEL_HIK) {
+                        acc[q] += (double)(b < a ? b : a);   // min<double>(x_k, sv_k)
+                    } else if (Kernel == FD_KERNEL_RBF) {
+                        const double diff = (double)a - (double)b;
+                        acc[q] += diff * diff;
+                    } else {
+                        acc[q] += (double)a * (double)b;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            double v = acc[q];
+            if (Kernel == FD_KERNEL_POLY) v = svm_powi(P.gamma * v + P.coef0, P.degree);
+            if (Kernel == FD_KERNEL_RBF) v = exp(-P.gamma * v);
+            sK[kq + 4 * q][c] = v;
+        }
+        __syncthreads();
+        if (lane < 16) {
+            const int ns = min(16, f.n_sv - s0);
+            for (int s = 0; s < ns; ++s) sum += f.coef[s0 + s] * sK[lane][s];
+        }
+        __syncthreads();   // sK and sSv are rewritten by the next tile
+    }
+    if (lane < 16 && h0 + lane < f.n_held) P.dec[sHeld[lane]] = sum - f.rho;
+}
+
 struct SvmTrainScratch {
     DevBuf x, q, dbl, w, desc, info, state;
     DevBuf xs, svList, sv;   // the support-vector form: xs; sv_index and coef; the gathered rows
+    DevBuf cvX, cvRows, cvIdx, cvCoef, cvDec;   // fd_kernel_svm_cv_sigmoid: a host caller's x; the folds' rows; index lists; coef; dec
 };
 
 // the run of a support-vector form (fd_kernel_svm_*) with its checked kernel; the solver follows from the number of examples
@@ -658,15 +781,17 @@ FdSvmRunSpec svm_sv_spec(const char* who, const fd_svm_kernel* k, int64_t n) {
 }
 
 // 0 for a shape the trainer takes, else which of svm_check_shape's messages applies
-int svm_shape_fault(int n_pos, int n_neg, int d, int maxN) {
-    if (n_pos < 1 || n_neg < 1) return 1;
+// oneClass: n_pos examples and no negative one
+int svm_shape_fault(int n_pos, int n_neg, int d, int maxN, bool oneClass = false) {
+    if (n_pos < 1 || (oneClass ? n_neg != 0 : n_neg < 1)) return oneClass ? 4 : 1;
     if ((int64_t)n_pos + n_neg > maxN) return 2;
     return d < 1 ? 3 : 0;
 }
 
-void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN) {
-    const int fault = svm_shape_fault(n_pos, n_neg, d, maxN);
+void svm_check_shape(const char* who, int n_pos, int n_neg, int d, int maxN, bool oneClass = false) {
+    const int fault = svm_shape_fault(n_pos, n_neg, d, maxN, oneClass);
     if (fault == 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one positive and one negative example (%d, %d)", who, n_pos, n_neg);
+    if (fault == 4) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: needs at least one example (%d)", who, n_pos);
     if (fault == 2) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %lld examples, at most %d", who, (long long)n_pos + n_neg, maxN);
     if (fault == 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the feature length must be positive (%d)", who, d);
 }
@@ -731,7 +856,7 @@ void svm_prepare(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_
     SvmSizes total;
     for (int c = 0; c < count; ++c) {
         const fd_svm_train_problem& pr = probs[c];
-        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, spec.large ? SVM_LARGE_MAX_N : SVM_MAX_N);
+        svm_check_shape(who, pr.n_pos, pr.n_neg, pr.d, spec.large ? SVM_LARGE_MAX_N : SVM_MAX_N, spec.nu > 0.0);
         if (!pr.x) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
         sizes[c] = svm_sizes(pr, spec, c);
         for (int k = 0; k < SZ_COUNT; ++k) total.b[k] += sizes[c].b[k];
@@ -803,6 +928,12 @@ void svm_prepare(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_
         D.d = pr.d;
         D.q_in_lds = !spec.large && svm_q_in_lds(n) ? 1 : 0;
         D.max_iter = prm.max_iterations > 0 ? prm.max_iterations : svm_default_max_iter(n);
+        D.lin = -1.0;
+        if (spec.nu > 0.0) {   // solve_one_class: p = 0, (int)(nu l) alphas at the bound 1 and the remainder behind them
+            D.lin = 0.0;
+            D.oc_full = (int)(spec.nu * n);
+            D.oc_frac = spec.nu * n - D.oc_full;
+        }
         if (spec.svForm) {
             D.xs = (double*)take(sc.xs, SZ_XS);
             D.sv_index = (int32_t*)take(sc.svList, SZ_LIST);
@@ -834,6 +965,10 @@ void svm_prepare(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_
     }
     hipLaunchKernelGGL(gram, tiles, dim3(64), 0, ctx->stream, sc.desc.as<SvmProbDev>());
     HIP_CHECK(hipGetLastError());
+    if (spec.nu > 0.0) {   // in place of alpha = 0, G = -1
+        hipLaunchKernelGGL(k_svm_one_class_start, dim3((run.maxPad + 255) / 256, count), dim3(256), 0, ctx->stream, sc.desc.as<SvmProbDev>());
+        HIP_CHECK(hipGetLastError());
+    }
 }
 
 fd_svm_train_problem svm_single_problem(const float* x, int n_pos, int n_neg, int d, int is_device, float* weights, float* bias, double* alpha) {
@@ -849,7 +984,8 @@ fd_svm_train_problem svm_single_problem(const float* x, int n_pos, int n_neg, in
     return pr;
 }
 
-void svm_gram(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD) {
+void svm_gram(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, int n_neg, int d, int is_device, float* Q, double* QD,
+              double* G0 = nullptr) {
     HIP_CHECK(hipSetDevice(ctx->device));
     const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, nullptr, nullptr);
     fd_svm_train_params prm = {1.0, 1.0, 1.0, 1e-4, 0, SVM_DEFAULT_LAUNCH_ITERATIONS};
@@ -858,6 +994,7 @@ void svm_gram(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int n_pos, 
     const SvmProbDev& D = run.h[0];
     HIP_CHECK(hipMemcpy2DAsync(Q, sizeof(float) * D.n, D.Q, sizeof(float) * D.n_pad, sizeof(float) * D.n, D.n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(QD, D.QD, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));
+    if (G0) HIP_CHECK(hipMemcpyAsync(G0, D.G, sizeof(double) * D.n, hipMemcpyDeviceToHost, ctx->stream));   // the start gradient
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
@@ -876,11 +1013,282 @@ int svm_linear_train(fd_ctx* ctx, const FdSvmRunSpec& spec, const float* x, int 
         fd_svm_train_run(ctx, spec, 1, &pr, params, info);
     });
 }
+
+// trains one problem of a support-vector form and creates the f32 model with fd_svm_create; one-class when spec.nu > 0
+void svm_train_model(fd_ctx* ctx, FdSvmRunSpec spec, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel& kernel,
+                     const fd_svm_train_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out, fd_svm_train_info* info) {
+    svm_check_shape(spec.who, n_pos, n_neg, d, SVM_LARGE_MAX_N, spec.nu > 0.0);   // before the lists are sized by n
+    const int n = n_pos + n_neg;
+    std::vector<int32_t> svIndex(n);
+    std::vector<float> coef(n), rows;
+    float bias = 0.f;
+    const FdSvmSvOut o = {svIndex.data(), coef.data(), nullptr, &rows};
+    spec.outs = &o;
+    const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, &bias, nullptr);
+    fd_svm_train_run(ctx, spec, 1, &pr, params, info);
+    if (info->n_sv < 1) FD_THROW(FD_ERR_RUNTIME, "%s: the trained model has no support vector", spec.who);
+    if (spec.nu > 0.0 && !std::isfinite(info->rho))   // nu = 1: every alpha at its bound, rho = +inf
+        FD_THROW(FD_ERR_RUNTIME, "%s: the trained model's rho is not finite (%g)", spec.who, info->rho);
+    fd_svm_model md = {};
+    md.kernel = kernel.kernel;
+    md.p0 = kernel.p0;
+    md.p1 = kernel.p1;
+    md.p2 = kernel.p2;
+    md.num_sv = info->n_sv;
+    md.dim = d;
+    md.dtype = FD_DTYPE_F32;
+    md.support_vectors = rows.data();
+    md.coefficients = coef.data();
+    md.bias = bias;
+    md.threshold = threshold;
+    md.logistic_a = logistic_a;
+    md.logistic_b = logistic_b;
+    const int created = fd_svm_create(ctx, &md, out);
+    if (created != FD_OK) throw FdError{created, ctx->error};
+}
+
+// svm_check_parameter's rule for ONE_CLASS (svm.cpp:3056-3060)
+double svm_checked_nu(const char* who, double nu) {
+    if (!(nu > 0.0) || nu > 1.0) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: nu <= 0 or nu > 1 (%g)", who, nu);
+    return nu;
+}
+// a one-class run: nu into the spec, and the solver's parameters with both bounds 1
+fd_svm_train_params svm_one_class_params(FdSvmRunSpec& spec, const fd_svm_one_class_params& p) {
+    spec.nu = svm_checked_nu(spec.who, p.nu);
+    return fd_svm_train_params{1.0, 1.0, 1.0, p.eps, p.max_iterations, p.launch_iterations};
+}
+
+// sigmoid_train (svm.cpp:1752-1863), operation for operation; labels_i > 0 for i < n_pos
+void svm_sigmoid_train(int l, const double* dec, int n_pos, double& A, double& B, int* iterations, int* status) {
+    const double prior1 = n_pos, prior0 = l - n_pos;
+    const int max_iter = 100;
+    const double min_step = 1e-10, sigma = 1e-12, eps = 1e-5;
+    const double hiTarget = (prior1 + 1.0) / (prior1 + 2.0), loTarget = 1 / (prior0 + 2.0);
+    std::vector<double> t(l);
+    A = 0.0;
+    B = std::log((prior0 + 1.0) / (prior1 + 1.0));
+    double fval = 0.0;
+    for (int i = 0; i < l; ++i) {
+        t[i] = i < n_pos ? hiTarget : loTarget;
+        const double fApB = dec[i] * A + B;
+        if (fApB >= 0) fval += t[i] * fApB + std::log(1 + std::exp(-fApB));
+        else fval += (t[i] - 1) * fApB + std::log(1 + std::exp(fApB));
+    }
+    int iter, st = FD_SVM_SIGMOID_CONVERGED;
+    for (iter = 0; iter < max_iter; ++iter) {
+        double h11 = sigma, h22 = sigma, h21 = 0.0, g1 = 0.0, g2 = 0.0;
+        for (int i = 0; i < l; ++i) {
+            const double fApB = dec[i] * A + B;
+            double p, q;
+            if (fApB >= 0) {
+                p = std::exp(-fApB) / (1.0 + std::exp(-fApB));
+                q = 1.0 / (1.0 + std::exp(-fApB));
+            } else {
+                p = 1.0 / (1.0 + std::exp(fApB));
+                q = std::exp(fApB) / (1.0 + std::exp(fApB));
+            }
+            const double d2 = p * q;
+            h11 += dec[i] * dec[i] * d2;
+            h22 += d2;
+            h21 += dec[i] * d2;
+            const double d1 = t[i] - p;
+            g1 += dec[i] * d1;
+            g2 += d1;
+        }
+        if (std::fabs(g1) < eps && std::fabs(g2) < eps) break;
+        const double det = h11 * h22 - h21 * h21;
+        const double dA = -(h22 * g1 - h21 * g2) / det;
+        const double dB = -(-h21 * g1 + h11 * g2) / det;
+        const double gd = g1 * dA + g2 * dB;
+        double stepsize = 1;
+        while (stepsize >= min_step) {
+            const double newA = A + stepsize * dA, newB = B + stepsize * dB;
+            double newf = 0.0;
+            for (int i = 0; i < l; ++i) {
+                const double fApB = dec[i] * newA + newB;
+                if (fApB >= 0) newf += t[i] * fApB + std::log(1 + std::exp(-fApB));
+                else newf += (t[i] - 1) * fApB + std::log(1 + std::exp(fApB));
+            }
+            if (newf < fval + 0.0001 * stepsize * gd) {
+                A = newA;
+                B = newB;
+                fval = newf;
+                break;
+            } else {
+                stepsize = stepsize / 2.0;
+            }
+        }
+        if (stepsize < min_step) {
+            st = FD_SVM_SIGMOID_LINE_SEARCH_FAILED;
+            break;
+        }
+    }
+    if (iter >= max_iter) st = FD_SVM_SIGMOID_MAX_ITERATIONS;
+    if (iterations) *iterations = iter;
+    if (status) *status = st;
+}
+
+// fd_kernel_svm_cv_sigmoid: the folds' index lists on the host, their rows gathered on the device, the trainer over the
+// folds (those of up to 1024 rows in one run, the larger ones in another), k_svm_cv_decision over the held-out rows, the fit.
+void svm_cv_sigmoid(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                    const fd_svm_train_params* params, const int32_t* perm, double* prob_a, double* prob_b, double* dec_values,
+                    fd_svm_cv_info* cv_info) {
+    const char* who = "fd_kernel_svm_cv_sigmoid";
+    const FdSvmRunSpec kspec = svm_sv_spec(who, kernel, 0);
+    svm_check_shape(who, n_pos, n_neg, d, SVM_LARGE_MAX_N);
+    const fd_svm_train_params prm = svm_checked_params(who, params);
+    const int n = n_pos + n_neg;
+    {
+        std::vector<char> seen(n, 0);
+        for (int i = 0; i < n; ++i) {
+            if (perm[i] < 0 || perm[i] >= n || seen[perm[i]]) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: perm is not a permutation of 0..%d (entry %d)", who, n - 1, i);
+            seen[perm[i]] = 1;
+        }
+    }
+    // the folds train with C = 1 and the weighted bounds as class weights (svm.cpp:1998-2007)
+    const fd_svm_train_params foldPrm = {1.0, prm.C * prm.weight_pos, prm.C * prm.weight_neg, prm.eps, prm.max_iterations, prm.launch_iterations};
+    constexpr int F = FD_SVM_CV_FOLDS;
+    fd_svm_cv_info ci = {};
+    std::vector<int32_t> train[F], held[F];
+    int nPosOf[F];
+    size_t rowsOff[F], rowsTotal = 0, idxTotal = 0;
+    for (int f = 0; f < F; ++f) {
+        const int begin = (int)((int64_t)f * n / F), end = (int)((int64_t)(f + 1) * n / F);
+        std::vector<int32_t> neg;
+        for (int j = 0; j < n; ++j) {   // svm_group_classes: the positives in permuted order, then the negatives
+            if (j >= begin && j < end) continue;
+            (perm[j] < n_pos ? train[f] : neg).push_back(perm[j]);
+        }
+        nPosOf[f] = (int)train[f].size();
+        const int nNegOf = (int)neg.size();
+        train[f].insert(train[f].end(), neg.begin(), neg.end());
+        held[f].assign(perm + begin, perm + end);
+        ci.fold_trained[f] = nPosOf[f] > 0 && nNegOf > 0 ? 1 : 0;
+        ci.fold_constant[f] = ci.fold_trained[f] ? 0.0 : (nPosOf[f] > 0 ? 1.0 : (nNegOf > 0 ? -1.0 : 0.0));
+        if (!ci.fold_trained[f]) {
+            train[f].clear();
+            held[f].clear();   // no decision values from the device
+        }
+        rowsOff[f] = rowsTotal;
+        rowsTotal += svm_align(sizeof(float) * train[f].size() * d);
+        idxTotal += 2 * (size_t)n;   // a fold's lists: train, later its support vectors in their place; held
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    SvmTrainScratch& sc = fd_scratch<SvmTrainScratch>(ctx);
+    const float* dx = x;
+    if (!is_device) {
+        sc.cvX.reserve(sizeof(float) * (size_t)n * d);
+        HIP_CHECK(hipMemcpyAsync(sc.cvX.p, x, sizeof(float) * (size_t)n * d, hipMemcpyHostToDevice, ctx->stream));
+        dx = sc.cvX.as<float>();
+    }
+    try {
+        sc.cvRows.reserve(rowsTotal);
+    } catch (const FdError& e) {
+        FD_THROW(FD_ERR_RUNTIME, "%s: no device memory for the folds' rows (%zu bytes): %s", who, rowsTotal, e.msg.c_str());
+    }
+    sc.cvIdx.reserve(sizeof(int32_t) * idxTotal);
+    sc.cvCoef.reserve(sizeof(double) * (size_t)n * F);
+    sc.cvDec.reserve(sizeof(double) * n);
+    std::vector<int32_t> hIdx(idxTotal, 0);
+    for (int f = 0; f < F; ++f) {
+        std::copy(train[f].begin(), train[f].end(), hIdx.begin() + 2 * (size_t)n * f);
+        std::copy(held[f].begin(), held[f].end(), hIdx.begin() + 2 * (size_t)n * f + n);
+    }
+    HIP_CHECK(hipMemcpyAsync(sc.cvIdx.p, hIdx.data(), sizeof(int32_t) * idxTotal, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<double> alpha[F];
+    std::vector<int32_t> svIndex[F];
+    std::vector<float> coefF[F];
+    float bias[F];
+    fd_svm_train_problem prob[F];
+    FdSvmSvOut outs[F];
+    for (int f = 0; f < F; ++f) {
+        if (!ci.fold_trained[f]) continue;
+        const size_t rows = train[f].size(), elements = rows * d;
+        float* block = (float*)((char*)sc.cvRows.p + rowsOff[f]);
+        hipLaunchKernelGGL(k_svm_gather_rows, dim3((unsigned)((elements + 255) / 256)), dim3(256), 0, ctx->stream, dx,
+                           sc.cvIdx.as<int32_t>() + 2 * (size_t)n * f, block, elements, d);
+        HIP_CHECK(hipGetLastError());
+        alpha[f].resize(rows);
+        svIndex[f].resize(rows);
+        coefF[f].resize(rows);
+        prob[f] = svm_single_problem(block, nPosOf[f], (int)rows - nPosOf[f], d, 1, nullptr, &bias[f], alpha[f].data());
+        outs[f] = FdSvmSvOut{svIndex[f].data(), coefF[f].data(), nullptr, nullptr};
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // hIdx and a pageable x are read
+    for (int large = 0; large < 2; ++large) {   // the folds of either solver in one run
+        std::vector<int> which;
+        std::vector<fd_svm_train_problem> probs;
+        std::vector<FdSvmSvOut> os;
+        for (int f = 0; f < F; ++f)
+            if (ci.fold_trained[f] && ((int)train[f].size() > SVM_MAX_N) == (large != 0)) {
+                which.push_back(f);
+                probs.push_back(prob[f]);
+                os.push_back(outs[f]);
+            }
+        if (which.empty()) continue;
+        FdSvmRunSpec spec = kspec;
+        spec.large = large != 0;
+        spec.outs = os.data();
+        std::vector<fd_svm_train_info> infos(which.size());
+        fd_svm_train_run(ctx, spec, (int)which.size(), probs.data(), &foldPrm, infos.data());
+        for (size_t c = 0; c < which.size(); ++c) ci.fold[which[c]] = infos[c];
+    }
+    // the models' support vectors as example indices, and alpha_s y_s in double
+    SvmCvDev cv = {};
+    cv.x = dx;
+    cv.dec = sc.cvDec.as<double>();
+    cv.d = d;
+    cv.degree = kspec.degree;
+    cv.gamma = kspec.gamma;
+    cv.coef0 = kspec.coef0;
+    std::vector<double> hCoef((size_t)n * F, 0.0);
+    int maxHeld = 0;
+    for (int f = 0; f < F; ++f) {
+        if (!ci.fold_trained[f]) continue;
+        const int nsv = ci.fold[f].n_sv;
+        int32_t* sv = hIdx.data() + 2 * (size_t)n * f;
+        for (int s = 0; s < nsv; ++s) {
+            const int q = svIndex[f][s];
+            hCoef[(size_t)n * f + s] = q < nPosOf[f] ? alpha[f][q] : -alpha[f][q];
+            sv[s] = train[f][q];
+        }
+        SvmCvFoldDev& fd = cv.fold[f];
+        fd.sv = sc.cvIdx.as<int32_t>() + 2 * (size_t)n * f;
+        fd.held = fd.sv + n;
+        fd.coef = sc.cvCoef.as<double>() + (size_t)n * f;
+        fd.n_sv = nsv;
+        fd.n_held = (int)held[f].size();
+        fd.rho = ci.fold[f].rho;
+        maxHeld = std::max(maxHeld, fd.n_held);
+    }
+    std::vector<double> dec(n, 0.0);
+    if (maxHeld > 0) {
+        HIP_CHECK(hipMemcpyAsync(sc.cvIdx.p, hIdx.data(), sizeof(int32_t) * idxTotal, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(sc.cvCoef.p, hCoef.data(), sizeof(double) * hCoef.size(), hipMemcpyHostToDevice, ctx->stream));
+        void (*decision)(const SvmCvDev) = k_svm_cv_decision<FD_KERNEL_LINEAR>;
+        if (kspec.kernel == FD_KERNEL_POLY) decision = k_svm_cv_decision<FD_KERNEL_POLY>;
+        if (kspec.kernel == FD_KERNEL_RBF) decision = k_svm_cv_decision<FD_KERNEL_RBF>;
+        if (kspec.kernel == FD_KERNEL_HIK) decision = k_svm_cv_decision<FD_KERNEL_HIK>;
+        hipLaunchKernelGGL(decision, dim3((maxHeld + 15) / 16, F), dim3(64), 0, ctx->stream, cv);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(dec.data(), sc.cvDec.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    for (int f = 0; f < F; ++f) {
+        if (ci.fold_trained[f]) continue;
+        const int begin = (int)((int64_t)f * n / F), end = (int)((int64_t)(f + 1) * n / F);
+        for (int j = begin; j < end; ++j) dec[perm[j]] = ci.fold_constant[f];
+    }
+    svm_sigmoid_train(n, dec.data(), n_pos, *prob_a, *prob_b, &ci.newton_iterations, &ci.status);
+    if (dec_values) std::memcpy(dec_values, dec.data(), sizeof(double) * n);
+    if (cv_info) *cv_info = ci;
+}
 }  // namespace
 
 // Trains `count` problems in one set of launches; infos[c] is filled for every problem.  Leaves ctx->stream synchronised.
-// spec.large: one problem of up to SVM_LARGE_MAX_N examples on k_svm_smo_large.  spec.svForm: the problems' weights are NULL;
-// spec.outs receives the model.
+// spec.large: problems of up to SVM_LARGE_MAX_N examples on k_svm_smo_large, one workgroup each (the public entry points pass one;
+// the sigmoid fit's folds up to five).  spec.svForm: the problems' weights are NULL; spec.outs receives the model.  spec.nu > 0:
+// one-class problems.
 void fd_svm_train_run(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd_svm_train_problem* probs, const fd_svm_train_params* params,
                       fd_svm_train_info* infos) {
     const char* who = spec.who;
@@ -1034,38 +1442,12 @@ int fd_kernel_svm_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d
 int fd_kernel_svm_train_model(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
                               const fd_svm_train_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out,
                               fd_svm_train_info* info) {
-    int rc = fd_guard(ctx, [&] {
+    return fd_guard(ctx, [&] {
         if (!ctx || !x || !out || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_train_model: NULL argument");
         *out = nullptr;
-        FdSvmRunSpec spec = svm_sv_spec("fd_kernel_svm_train_model", kernel, (int64_t)n_pos + n_neg);
-        svm_check_shape("fd_kernel_svm_train_model", n_pos, n_neg, d, SVM_LARGE_MAX_N);   // before the lists are sized by n
-        const int n = n_pos + n_neg;
-        std::vector<int32_t> svIndex(n);
-        std::vector<float> coef(n), rows;
-        float bias = 0.f;
-        const FdSvmSvOut o = {svIndex.data(), coef.data(), nullptr, &rows};
-        spec.outs = &o;
-        const fd_svm_train_problem pr = svm_single_problem(x, n_pos, n_neg, d, is_device, nullptr, &bias, nullptr);
-        fd_svm_train_run(ctx, spec, 1, &pr, params, info);
-        if (info->n_sv < 1) FD_THROW(FD_ERR_RUNTIME, "fd_kernel_svm_train_model: the trained model has no support vector");
-        fd_svm_model md = {};
-        md.kernel = kernel->kernel;
-        md.p0 = kernel->p0;
-        md.p1 = kernel->p1;
-        md.p2 = kernel->p2;
-        md.num_sv = info->n_sv;
-        md.dim = d;
-        md.dtype = FD_DTYPE_F32;
-        md.support_vectors = rows.data();
-        md.coefficients = coef.data();
-        md.bias = bias;
-        md.threshold = threshold;
-        md.logistic_a = logistic_a;
-        md.logistic_b = logistic_b;
-        const int created = fd_svm_create(ctx, &md, out);
-        if (created != FD_OK) throw FdError{created, ctx->error};
+        const FdSvmRunSpec spec = svm_sv_spec("fd_kernel_svm_train_model", kernel, (int64_t)n_pos + n_neg);
+        svm_train_model(ctx, spec, x, n_pos, n_neg, d, is_device, *kernel, params, threshold, logistic_a, logistic_b, out, info);
     });
-    return rc;
 }
 
 int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_problem* problems, const fd_svm_kernel* kernel,
@@ -1084,6 +1466,67 @@ int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_
         }
         spec.outs = outs.data();
         fd_svm_train_run(ctx, spec, count, problems ? probs.data() : nullptr, params, infos);
+    });
+}
+
+/* ---- one-class models ---- */
+int fd_one_class_svm_train_limits(int n, int d, int* q_in_lds, int* large, int* max_iterations) {
+    if (svm_shape_fault(n, 0, d, SVM_LARGE_MAX_N, true)) return FD_ERR_INVALID_ARGUMENT;
+    if (q_in_lds) *q_in_lds = n <= SVM_MAX_N && svm_q_in_lds(n) ? 1 : 0;
+    if (large) *large = n > SVM_MAX_N ? 1 : 0;
+    if (max_iterations) *max_iterations = svm_default_max_iter(n);
+    return FD_OK;
+}
+
+int fd_one_class_svm_gram(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel, double nu, float* Q, double* QD,
+                          double* G0) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !Q || !QD) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_one_class_svm_gram: NULL argument");
+        FdSvmRunSpec spec = svm_sv_spec("fd_one_class_svm_gram", kernel, n);
+        spec.nu = svm_checked_nu(spec.who, nu);
+        svm_gram(ctx, spec, x, n, 0, d, is_device, Q, QD, G0);
+    });
+}
+
+int fd_one_class_svm_train(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel,
+                           const fd_svm_one_class_params* params, int32_t* sv_index, float* coefficients, float* support_vectors, float* bias,
+                           double* alpha, fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !params || !sv_index || !coefficients || !bias || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_one_class_svm_train: NULL argument");
+        FdSvmRunSpec spec = svm_sv_spec("fd_one_class_svm_train", kernel, n);
+        const fd_svm_train_params prm = svm_one_class_params(spec, *params);
+        const FdSvmSvOut out = {sv_index, coefficients, support_vectors, nullptr};
+        spec.outs = &out;
+        const fd_svm_train_problem pr = svm_single_problem(x, n, 0, d, is_device, nullptr, bias, alpha);
+        fd_svm_train_run(ctx, spec, 1, &pr, &prm, info);
+    });
+}
+
+int fd_one_class_svm_train_model(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel,
+                                 const fd_svm_one_class_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out,
+                                 fd_svm_train_info* info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !params || !out || !info) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_one_class_svm_train_model: NULL argument");
+        *out = nullptr;
+        FdSvmRunSpec spec = svm_sv_spec("fd_one_class_svm_train_model", kernel, n);
+        const fd_svm_train_params prm = svm_one_class_params(spec, *params);
+        svm_train_model(ctx, spec, x, n, 0, d, is_device, *kernel, &prm, threshold, logistic_a, logistic_b, out, info);
+    });
+}
+
+/* ---- libsvm's sigmoid fit ---- */
+int fd_svm_sigmoid_train(int n, const double* dec_values, int n_pos, double* prob_a, double* prob_b, int* iterations, int* status) {
+    if (n < 1 || n_pos < 0 || n_pos > n || !dec_values || !prob_a || !prob_b) return FD_ERR_INVALID_ARGUMENT;
+    svm_sigmoid_train(n, dec_values, n_pos, *prob_a, *prob_b, iterations, status);
+    return FD_OK;
+}
+
+int fd_kernel_svm_cv_sigmoid(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                             const fd_svm_train_params* params, const int32_t* perm, double* prob_a, double* prob_b, double* dec_values,
+                             fd_svm_cv_info* cv_info) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !x || !perm || !prob_a || !prob_b) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_kernel_svm_cv_sigmoid: NULL argument");
+        svm_cv_sigmoid(ctx, x, n_pos, n_neg, d, is_device, kernel, params, perm, prob_a, prob_b, dec_values, cv_info);
     });
 }
 

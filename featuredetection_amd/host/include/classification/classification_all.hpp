@@ -440,7 +440,10 @@ private:
 // std::runtime_error): the model libsvm's svm_train gives.  Any other kernel or example depth,
 // one-class SVMs, probabilistic output (libsvm's own sigmoid fit) and static negatives throw std::invalid_argument.
 // createBinaryKernelSvm (not in the reference) is the same classifier with any kernel, trained by fd_kernel_svm_train and holding
-// the support vectors and coefficients of libsvm's model (LibSvmClassifier.cpp:144-147) in place of one weight vector.
+// the support vectors and coefficients of libsvm's model (LibSvmClassifier.cpp:144-147) in place of one weight vector; with
+// `probabilistic` it also runs libsvm's sigmoid fit (fd_kernel_svm_cv_sigmoid) and installs the logistic parameters as
+// LibSvmClassifier.cpp:148-152 does.  createOneClassKernelSvm (not in the reference) trains libsvm's one-class model from the
+// positives alone (fd_one_class_svm_train).  The reference-named factories keep throwing for what they did not train before.
 namespace libsvm {
 
 class LibSvmClassifier : public classification::TrainableSvmClassifier {
@@ -462,16 +465,34 @@ public:
     // not in the reference: the binary C-SVC with a LinearKernel, PolynomialKernel, RbfKernel or HistogramIntersectionKernel whose
     // retrain installs setSvmParameters(the examples that are support vectors, coefficients, rho).  createBinarySvm keeps throwing
     // for the kernels it does not train, so the kernel form has a factory of its own.
+    // probabilistic: train() first draws libsvm's permutation with std::rand (j = i + rand() % (l - i), in libsvm's place in the
+    // sequence: before the final training), runs the five-fold sigmoid fit with the weighted C and installs
+    // getProbabilisticSvm()->setLogisticParameters(probB, probA)
     static std::shared_ptr<LibSvmClassifier> createBinaryKernelSvm(std::shared_ptr<classification::Kernel> kernel, double c = 1,
-                                                                   bool compensateImbalance = false) {
-        return std::make_shared<LibSvmClassifier>(std::make_shared<classification::SvmClassifier>(kernel), c, compensateImbalance, KernelForm());
+                                                                   bool compensateImbalance = false, bool probabilistic = false) {
+        return std::make_shared<LibSvmClassifier>(std::make_shared<classification::SvmClassifier>(kernel), c, compensateImbalance, KernelForm(),
+                                                  probabilistic);
     }
     static std::shared_ptr<LibSvmClassifier> createBinaryKernelSvm(std::shared_ptr<classification::SvmClassifier> svm, double c = 1,
-                                                                   bool compensateImbalance = false) {
-        return std::make_shared<LibSvmClassifier>(svm, c, compensateImbalance, KernelForm());
+                                                                   bool compensateImbalance = false, bool probabilistic = false) {
+        return std::make_shared<LibSvmClassifier>(svm, c, compensateImbalance, KernelForm(), probabilistic);
     }
-    struct KernelForm {};   // selects the constructor behind createBinaryKernelSvm
-    LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double c, bool compensateImbalance, KernelForm);
+    // not in the reference: what createOneClassSvm stands for there.  The negatives are an EmptyExampleManagement; retrain trains
+    // from the positives alone and installs setSvmParameters(the examples that are support vectors, alpha, rho).  nu = 1, the
+    // reference's default, puts every alpha at its bound and gives rho = +inf, as libsvm does.
+    static std::shared_ptr<LibSvmClassifier> createOneClassKernelSvm(std::shared_ptr<classification::Kernel> kernel, double nu = 1) {
+        return std::make_shared<LibSvmClassifier>(std::make_shared<classification::SvmClassifier>(kernel), nu, OneClassForm());
+    }
+    static std::shared_ptr<LibSvmClassifier> createOneClassKernelSvm(std::shared_ptr<classification::SvmClassifier> svm, double nu = 1) {
+        return std::make_shared<LibSvmClassifier>(svm, nu, OneClassForm());
+    }
+    struct KernelForm {};     // selects the constructor behind createBinaryKernelSvm
+    struct OneClassForm {};   // and the one behind createOneClassKernelSvm
+    LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double c, bool compensateImbalance, KernelForm, bool probabilistic = false);
+    LibSvmClassifier(std::shared_ptr<classification::SvmClassifier> svm, double nu, OneClassForm);
+    // libsvm's probA, probB of the last probabilistic training (the logistic parameters are installed swapped)
+    double getLastProbA() const { return lastProbA; }
+    double getLastProbB() const { return lastProbB; }
     bool trainsSupportVectors() const { return kernelForm; }
     LibSvmClassifier(std::shared_ptr<classification::Kernel> kernel, double cnu, bool oneClass, bool compensateImbalance = false,
                      bool probabilistic = false);
@@ -509,8 +530,9 @@ private:
     bool retrainKernelForm(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples);
     void setTrained(const std::vector<float>& weights, const fd_svm_train_params& params, const fd_svm_train_info& info);
     bool compensateImbalance;
-    bool kernelForm = false;
-    double c;
+    bool kernelForm = false, oneClassForm = false, probabilistic = false;
+    double c;   // C, or nu of the one-class form
+    double lastProbA = 0, lastProbB = 0;
     std::shared_ptr<classification::ProbabilisticSvmClassifier> probabilisticSvm;
     std::unique_ptr<classification::ExampleManagement> positiveExamples, negativeExamples;
     int rows = 0, cols = 0, type = 0;   // shape of the examples, for the weight vector (LibSvmUtils::createNode)

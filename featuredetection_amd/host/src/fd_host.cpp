@@ -1562,10 +1562,16 @@ LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double cnu, bo
     if (!svm->getKernel() || svm->getKernel()->abiKernel() != FD_KERNEL_LINEAR)
         throw std::invalid_argument("LibSvmClassifier: only a LinearKernel is trained on this backend");
 }
-LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double c, bool compensateImbalance, KernelForm)
-    : TrainableSvmClassifier(svm), compensateImbalance(compensateImbalance), kernelForm(true), c(c),
+LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double c, bool compensateImbalance, KernelForm, bool probabilistic)
+    : TrainableSvmClassifier(svm), compensateImbalance(compensateImbalance), kernelForm(true), probabilistic(probabilistic), c(c),
       probabilisticSvm(make_shared<classification::ProbabilisticSvmClassifier>(svm)),
       positiveExamples(new classification::UnlimitedExampleManagement()), negativeExamples(new classification::UnlimitedExampleManagement()) {
+    if (!svm->getKernel()) throw std::invalid_argument("LibSvmClassifier: the SVM has no kernel");
+}
+LibSvmClassifier::LibSvmClassifier(shared_ptr<SvmClassifier> svm, double nu, OneClassForm)   // LibSvmClassifier.cpp:42-44: no negatives are kept
+    : TrainableSvmClassifier(svm), compensateImbalance(false), kernelForm(true), oneClassForm(true), c(nu),
+      probabilisticSvm(make_shared<classification::ProbabilisticSvmClassifier>(svm)),
+      positiveExamples(new classification::UnlimitedExampleManagement()), negativeExamples(new classification::EmptyExampleManagement()) {
     if (!svm->getKernel()) throw std::invalid_argument("LibSvmClassifier: the SVM has no kernel");
 }
 void LibSvmClassifier::loadStaticNegatives(const string&, int, double) {
@@ -1631,12 +1637,28 @@ bool LibSvmClassifier::retrainKernelForm(const vector<Mat>& newPositiveExamples,
     vector<float> coefficients(examples.size());
     float bias = 0;
     fd_svm_train_info info;
-    check(fd_kernel_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &kernel, &params, svIndex.data(), coefficients.data(),
-                              nullptr, &bias, nullptr, &info));
+    if (oneClassForm) {   // svm_type ONE_CLASS with nu (createParameters :63-65), from the positives alone
+        const fd_svm_one_class_params oneClass = {c, params.eps, 0, 0};
+        check(fd_one_class_svm_train(context(), x.data(), positiveCount, dimensions, 0, &kernel, &oneClass, svIndex.data(), coefficients.data(), nullptr,
+                                     &bias, nullptr, &info));
+    } else {
+        if (probabilistic) {   // svm_train runs svm_binary_svc_probability, which draws its shuffle from rand(), before the final training
+            const int count = positiveCount + negativeCount;
+            vector<int32_t> perm(count);
+            for (int i = 0; i < count; ++i) perm[i] = i;
+            for (int i = 0; i < count; ++i) std::swap(perm[i], perm[i + std::rand() % (count - i)]);
+            check(fd_kernel_svm_cv_sigmoid(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &kernel, &params, perm.data(), &lastProbA,
+                                           &lastProbB, nullptr, nullptr));
+        }
+        check(fd_kernel_svm_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &kernel, &params, svIndex.data(),
+                                  coefficients.data(), nullptr, &bias, nullptr, &info));
+    }
     vector<Mat> supportVectors;
     for (int q = 0; q < info.n_sv; ++q) supportVectors.push_back(examples[svIndex[q]]);
     coefficients.resize(info.n_sv);
     svm->setSvmParameters(supportVectors, coefficients, info.rho);
+    // libsvm's A and B are ProbabilisticSvmClassifier's B and A (LibSvmClassifier.cpp:148-152)
+    if (probabilistic) probabilisticSvm->setLogisticParameters(lastProbB, lastProbA);
     lastPositiveCount = positiveCount;
     lastNegativeCount = negativeCount;
     lastParams = params;

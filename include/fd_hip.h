@@ -505,6 +505,63 @@ int fd_kernel_svm_train_batch(fd_ctx* ctx, int count, const fd_kernel_svm_train_
  * max_iterations; each may be NULL */
 int fd_kernel_svm_train_limits(int n_pos, int n_neg, int d, int* q_in_lds, int* large, int* max_iterations);
 
+/* One-class SVM training: what libsvm::LibSvmClassifier trains with oneClass set (svm_type ONE_CLASS;
+ * solve_one_class svm.cpp:1577-1607).  n rows, every label +1, the dual's linear term 0, both bounds 1, the start state alpha_i = 1
+ * for i < (int)(nu n), alpha_(int)(nu n) = nu n - (int)(nu n), 0 behind, and the start gradient G_j = sum_i alpha_i Q_ij summed as
+ * Solver::Solve does (i ascending, in double on the float Q).  Q_ij = (float)K_ij, QD_i = K_ii with the kernels and the solver of
+ * fd_kernel_svm_train; the model is the examples with alpha > 0, ascending, with the coefficients (float)alpha_i, and rho; the
+ * decision value is sum_i coefficient_i K(sv_i, x) - bias.  On the Q that fd_one_class_svm_gram returns the result is libsvm's bit
+ * for bit.  nu = 1 puts every alpha at its bound and gives rho = +inf, as libsvm does. */
+typedef struct {
+    double nu;                          /* in (0, 1] */
+    double eps;                         /* stopping tolerance; 0 -> 1e-4 */
+    int32_t max_iterations;             /* 0 -> libsvm's max(10000000, 100 n) */
+    int32_t launch_iterations;          /* as in fd_svm_train_params */
+} fd_svm_one_class_params;
+/* FD_ERR_INVALID_ARGUMENT for n < 1, n > FD_SVM_LARGE_MAX_N, d < 1, nu <= 0 or nu > 1 (svm_check_parameter), eps < 0, negative
+ * iteration counts, what fd_kernel_svm_train rejects of a kernel, or a required pointer that is NULL.  Up to 1024 examples run on
+ * the solver of fd_linear_svm_train, more on that of fd_linear_svm_train_large. */
+/* Q (n x n floats), QD (n doubles) and the start gradient G0 (n doubles, may be NULL) of this nu to host */
+int fd_one_class_svm_gram(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel, double nu, float* Q, double* QD,
+                          double* G0);
+int fd_one_class_svm_train(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel,
+                           const fd_svm_one_class_params* params, int32_t* sv_index /* n */, float* coefficients /* n */,
+                           float* support_vectors /* n x d, may be NULL */, float* bias, double* alpha /* n, may be NULL */, fd_svm_train_info* info);
+/* trains and creates the f32 model as fd_kernel_svm_train_model does.  FD_ERR_RUNTIME when rho is not finite (nu = 1). */
+int fd_one_class_svm_train_model(fd_ctx* ctx, const float* x, int n, int d, int is_device, const fd_svm_kernel* kernel,
+                                 const fd_svm_one_class_params* params, float threshold, double logistic_a, double logistic_b, fd_svm** out,
+                                 fd_svm_train_info* info);
+/* host only, no context: as fd_kernel_svm_train_limits for n examples */
+int fd_one_class_svm_train_limits(int n, int d, int* q_in_lds, int* large, int* max_iterations);
+
+/* libsvm's sigmoid fit for a C-SVC (`probabilistic`): svm_binary_svc_probability (svm.cpp:1940-2024) with the
+ * permutation supplied by the caller.  The five folds [i n / 5, (i + 1) n / 5) of the permuted order are held out in turn; a
+ * fold's C-SVC is trained on the remaining examples, its positives in permuted order, then its negatives, with C = 1 and the
+ * class weights C weight_pos, C weight_neg of `params` -- all folds in one set of launches, each with the alpha, rho and iteration
+ * count fd_kernel_svm_train returns for these rows.  The held-out examples get sum_s (alpha_s y_s) k_function(x, sv_s) - rho in
+ * double, in libsvm's summation order; a fold whose training part has no positive, no negative or no example gives its examples
+ * -1, +1 or 0 and trains nothing.  sigmoid_train (svm.cpp:1752-1863) on these decision values returns libsvm's probA, probB
+ * (LibSvmClassifier installs them as logisticB, logisticA).  The final model is not trained here. */
+#define FD_SVM_CV_FOLDS 5
+#define FD_SVM_SIGMOID_CONVERGED 0            /* both gradient components below 1e-5 */
+#define FD_SVM_SIGMOID_MAX_ITERATIONS 1       /* 100 Newton iterations */
+#define FD_SVM_SIGMOID_LINE_SEARCH_FAILED 2
+typedef struct {
+    fd_svm_train_info fold[FD_SVM_CV_FOLDS];  /* of the trained folds; zero for the others */
+    int32_t fold_trained[FD_SVM_CV_FOLDS];    /* 1: trained; 0: constant decision values */
+    double fold_constant[FD_SVM_CV_FOLDS];    /* the constant of a fold that was not trained: -1, +1 or 0 */
+    int32_t newton_iterations, status;        /* of the fit; FD_SVM_SIGMOID_* */
+} fd_svm_cv_info;
+/* perm: n = n_pos + n_neg ints, a permutation of 0..n-1 (else FD_ERR_INVALID_ARGUMENT); dec_values: n doubles in example order,
+ * may be NULL; cv_info may be NULL.  Otherwise the errors of fd_kernel_svm_train. */
+int fd_kernel_svm_cv_sigmoid(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_svm_kernel* kernel,
+                             const fd_svm_train_params* params, const int32_t* perm, double* prob_a, double* prob_b, double* dec_values,
+                             fd_svm_cv_info* cv_info);
+/* host only, no context: sigmoid_train operation for operation in double with libm's exp and log, on n decision values of which
+ * the first n_pos belong to positive examples.  iterations and status may be NULL.  FD_ERR_INVALID_ARGUMENT for n < 1, n_pos
+ * outside 0..n or a NULL array or result. */
+int fd_svm_sigmoid_train(int n, const double* dec_values, int n_pos, double* prob_a, double* prob_b, int* iterations, int* status);
+
 /* A particle set of the Condensation tracker resident on the device: two generations of up to `capacity` samples
  * as structure-of-arrays, bound to one fd_ehog_tracker.  A frame of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) +
  * ExtendedHogBasedMeasurementModel + FilteringStateExtractor(WeightedMeanStateExtractor) is fd_ehog_tracker_update,
