@@ -438,6 +438,7 @@ _SIGS = {
 # include/fd_hip_bench.h: measurement hooks (not part of the drop-in boundary)
 _BENCH_SIGS = {
     "fd_debug_svm_u8_both": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "fd_debug_svm_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "fd_ctx_set_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "fd_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]),
     "fd_sdm_train_last_phase_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -780,6 +781,30 @@ def svm_u8_both(ctx, svm, feats):
     o8, o16 = np.empty(len(feats), np.float64), np.empty(len(feats), np.float64)
     ctx.check(lib().fd_debug_svm_u8_both(ctx.h, svm.h, _ptr(feats), len(feats), _ptr(o8), _ptr(o16)))
     return o8, o16
+
+
+# fd_debug_svm_launch: the kernel bodies of svm.hip by name (include/fd_hip_bench.h)
+(SVM_PRODUCTION, SVM_U8_MFMA_8, SVM_U8_MFMA_16, SVM_U8_LANES_2, SVM_U8_LANES_4, SVM_U8_LANES_8, SVM_GENERIC, SVM_RBF_MFMA, SVM_RBF_MFMA_SVS,
+ SVM_RBF_MFMA_PRODUCTION) = range(10)
+
+
+def svm_launch(ctx, svm, feats, variant, idx=None, dcount=-1, n=None):
+    """Test hook: distances through one named kernel body.  feats: 2-D array of the model's dtype whose rows may be longer than svm.dim
+    (the row stride is feats.strides[0]; only the first svm.dim elements of a row belong to the vector); n: score only the first n
+    rows; idx: slots into those rows (the launch scores len(idx) gathered rows); dcount >= 0: a device-side count.  Returns float64
+    [len(idx) or n]; entries the kernel did not write are NaN with all bits set (SVM_SENTINEL_BITS)."""
+    assert feats.ndim == 2 and feats.dtype == svm.np_dtype and feats.shape[1] >= svm.dim and feats.strides[1] == feats.itemsize
+    n = feats.shape[0] if n is None else n
+    assert 1 <= n <= feats.shape[0]
+    if idx is not None:
+        idx = _c(idx, np.uint32)
+    out = np.zeros(len(idx) if idx is not None else n, np.float64)
+    ctx.check(lib().fd_debug_svm_launch(ctx.h, svm.h, C.c_void_p(feats.ctypes.data), n, feats.strides[0], _ptr(idx), len(idx) if idx is not None else 0,
+                                        int(dcount), int(variant), _ptr(out)))
+    return out
+
+
+SVM_SENTINEL_BITS = 0xFFFFFFFFFFFFFFFF
 
 
 def wvd_plan(nx, ny, frames, sy, ph, slots):

@@ -3,9 +3,10 @@
 // PolynomialKernel.hpp:35-37,73-81).
 //
 // Two paths:
-//  * k_svm_generic: one workgroup per feature vector, one wavefront per support vector, all four
-//    kernels, u8 (exact integer SSD / min-sum / dot via v_dot4) or f32 features.  Used for the
-//    second cascade stage (a few hundred survivors per image) and for fd_svm_distance_batch.
+//  * k_svm_generic: one workgroup per f32 feature vector, one wavefront per support vector, all four
+//    kernels.  u8 vectors (the second cascade stage, a few hundred survivors per image) go to
+//    k_svm_u8_lanes (exact integer SSD / min-sum / dot via v_dot4) or, RBF, to k_svm_u8_rbf_mfma;
+//    fd_svm_distance_batch takes whichever fd_svm_generic_launch_on picks.
 //  * k_svm_rbf_mfma: the dense stage of config 2 -- N patches x 1024 support vectors x 324 dims
 //    as a patch x support-vector contraction on the f32 MFMA pipe (v_mfma_f32_32x32x2_f32), with
 //    the RBF epilogue exp(-gamma (|x|^2 + |s|^2 - 2 x.s)) * coeff fused and the sum over support
@@ -33,13 +34,12 @@ static inline size_t frag_index(int64_t row, int k, int KP) {
 
 struct SvmDev {
     int32_t kernel, nsv, dim, dtype;
-    int32_t dpad;            // generic path: row stride in elements (u8: multiple of 16, f32: == dim)
+    int32_t dpad;            // u8: vector length padded to a multiple of 16 (k_svm_u8_lanes); f32: == dim
     double p0, p1;
     int32_t degree;
     float bias;
-    const void* sv;          // [nsv][dpad]
+    const void* sv;          // f32: [nsv][dim] (k_svm_generic); u8 models keep only the transposed and the MFMA tables below
     const float* coeff;      // [nsv]
-    const uint32_t* ss_u32;  // u8 rbf: sum of squares per SV
     int32_t nsvp;            // u8: nsv padded to a multiple of 64
     const uint32_t* svT;     // u8: [dpad/16][nsvp][4]: words 4q..4q+3 of support vector s at svT[(q*nsvp + s)*4 ..] (one 16-byte load per lane)
     const float* coeffP;     // u8: [nsvp], zero padded
@@ -63,7 +63,7 @@ struct fd_svm {
     SvmDev dev;
     float threshold;
     double logisticA, logisticB;
-    DevBuf sv, coeff, ss, svFrag, ssF, coeffPad, svT, coeffP, ssP, svA, ssShift, coeffD;
+    DevBuf sv, coeff, svFrag, ssF, coeffPad, svT, coeffP, ssP, svA, ssShift, coeffD;
     DevBuf feat, dist, idx;  // scratch for batch calls
 };
 
@@ -91,8 +91,13 @@ __device__ __forceinline__ double powi(double base, int exponent) {  // Polynomi
     return ret;
 }
 
-// One workgroup (256 threads) per feature vector; wave w handles support vectors w, w+4, ...
-// features: [n][dpad] (u8 or f32), optionally gathered through idx (slot indices).
+// The DYNAMIC LDS a launch gets without opting in (hipFuncAttributeMaxDynamicSharedMemorySize); the launchers refuse what needs more with
+// the library's own error.  The small static arrays of k_svm_generic and k_svm_u8_lanes do not count against it: the CU has 160 KiB, and
+// vectors that fill the 64 KiB exactly (f32 dim 16384, u8 dim 32768 two per workgroup) are scored (tests/test_gpu_svm_score.py).
+constexpr size_t SVM_LDS_LIMIT = 64 * 1024;
+
+// One workgroup (256 threads) per f32 feature vector; wave w handles support vectors w, w+4, ...
+// features: [n] rows of dim floats, feat_stride_bytes apart, optionally gathered through idx (slot indices).
 // dcount (may be NULL): the number of vectors lives on the device and the grid was sized for a capacity; workgroups past it leave at once.
 __global__ __launch_bounds__(256) void k_svm_generic(SvmDev m, const void* __restrict__ features, const uint32_t* __restrict__ idx,
                                                      int64_t feat_stride_bytes, double* __restrict__ out, const unsigned int* __restrict__ dcount) {
@@ -103,65 +108,29 @@ __global__ __launch_bounds__(256) void k_svm_generic(SvmDev m, const void* __res
     const int64_t item = blockIdx.x;
     const int64_t slot = idx ? (int64_t)idx[item] : item;
     const unsigned char* x = (const unsigned char*)features + slot * feat_stride_bytes;
-    const int nbytes = m.dtype == FD_DTYPE_U8 ? m.dpad : m.dim * 4;
-    for (int i = threadIdx.x; i < nbytes; i += 256) smem[i] = i < (m.dtype == FD_DTYPE_U8 ? m.dim : nbytes) ? x[i] : 0;
+    const int nbytes = m.dim * 4;
+    for (int i = threadIdx.x; i < nbytes; i += 256) smem[i] = x[i];
     __syncthreads();
     double acc = 0.0;
-    if (m.dtype == FD_DTYPE_U8) {
-        const uint32_t* xs = (const uint32_t*)smem;
-        const int nd = m.dpad >> 2;
-        int xxp = 0;
-        for (int i = lane; i < nd; i += 64) xxp = __builtin_amdgcn_udot4(xs[i], xs[i], xxp, false);
-        const int xx = __builtin_amdgcn_readfirstlane(wave_sum_i(xxp));
-        for (int s = wave; s < m.nsv; s += 4) {
-            const uint32_t* sv = (const uint32_t*)((const unsigned char*)m.sv + (size_t)s * m.dpad);
-            int part = 0;
-            if (m.kernel == FD_KERNEL_HIK) {
-                for (int i = lane; i < nd; i += 64) {
-                    uint32_t a = xs[i], b = sv[i];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) part += min((a >> (8 * q)) & 255u, (b >> (8 * q)) & 255u);
-                }
-            } else {
-                for (int i = lane; i < nd; i += 64) part = __builtin_amdgcn_udot4(xs[i], sv[i], part, false);
-            }
-            const int tot = wave_sum_i(part);
-            if (lane == 0) {
-                double kv;
-                if (m.kernel == FD_KERNEL_RBF) {
-                    const int ssd = xx + (int)m.ss_u32[s] - 2 * tot;  // exact integer SSD (RbfKernel.hpp:78-88)
-                    kv = exp(-m.p0 * (double)ssd);
-                } else if (m.kernel == FD_KERNEL_HIK) {
-                    kv = (double)tot;
-                } else if (m.kernel == FD_KERNEL_LINEAR) {
-                    kv = (double)tot;
-                } else {
-                    kv = powi(m.p0 * (double)tot + m.p1, m.degree);
-                }
-                acc += (double)m.coeff[s] * kv;
-            }
+    const float* xs = (const float*)smem;
+    for (int s = wave; s < m.nsv; s += 4) {
+        const float* sv = (const float*)m.sv + (size_t)s * m.dim;
+        double kv;
+        if (m.kernel == FD_KERNEL_RBF) {
+            float part = 0.f;
+            for (int i = lane; i < m.dim; i += 64) { float df = xs[i] - sv[i]; part += df * df; }
+            kv = exp(-m.p0 * (double)wave_sum_f(part));
+        } else if (m.kernel == FD_KERNEL_HIK) {
+            float part = 0.f;
+            for (int i = lane; i < m.dim; i += 64) part += fminf(xs[i], sv[i]);
+            kv = (double)wave_sum_f(part);
+        } else {
+            double part = 0.0;
+            for (int i = lane; i < m.dim; i += 64) part += (double)xs[i] * (double)sv[i];
+            part = wave_sum_d(part);
+            kv = m.kernel == FD_KERNEL_LINEAR ? part : powi(m.p0 * part + m.p1, m.degree);
         }
-    } else {
-        const float* xs = (const float*)smem;
-        for (int s = wave; s < m.nsv; s += 4) {
-            const float* sv = (const float*)m.sv + (size_t)s * m.dim;
-            double kv;
-            if (m.kernel == FD_KERNEL_RBF) {
-                float part = 0.f;
-                for (int i = lane; i < m.dim; i += 64) { float df = xs[i] - sv[i]; part += df * df; }
-                kv = exp(-m.p0 * (double)wave_sum_f(part));
-            } else if (m.kernel == FD_KERNEL_HIK) {
-                float part = 0.f;
-                for (int i = lane; i < m.dim; i += 64) part += fminf(xs[i], sv[i]);
-                kv = (double)wave_sum_f(part);
-            } else {
-                double part = 0.0;
-                for (int i = lane; i < m.dim; i += 64) part += (double)xs[i] * (double)sv[i];
-                part = wave_sum_d(part);
-                kv = m.kernel == FD_KERNEL_LINEAR ? part : powi(m.p0 * part + m.p1, m.degree);
-            }
-            if (lane == 0) acc += (double)m.coeff[s] * kv;
-        }
+        if (lane == 0) acc += (double)m.coeff[s] * kv;
     }
     if (lane == 0) red[wave] = acc;
     __syncthreads();
@@ -676,11 +645,10 @@ size_t fd_svm_rbf_lds_bytes(int KP) { return (size_t)2 * (KP / 8) * 256 * 4 + 64
 
 // dense MFMA scoring of npatches feature vectors already on the device in fragment-major layout
 // (rows padded to a multiple of 64, pad rows zero).  partial: scratch for the SV-stationary kernel.
-void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out) {
+// variant: 2 = the support-vector-stationary kernel where it is instantiated, anything else = the A-resident kernel
+static void svm_rbf_mfma_launch_variant(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out, int variant) {
     if (!m->dev.svFrag) FD_THROW(FD_ERR_INVALID_ARGUMENT, "SVM has no MFMA path (needs an RBF kernel on f32 vectors)");
     const int KP = m->dev.KP;
-    static int variant = -1;
-    if (variant < 0) { const char* e = getenv("FD_SVM_KERNEL"); variant = e ? atoi(e) : 2; }
     if (variant == 2 && (KP == 328 || KP == 336)) {   // instantiated sizes (HOG-324 -> 328); others use the A-resident kernel
         fd_svm* mm = const_cast<fd_svm*>(m);
         const int64_t ntiles = (npatches + 31) / 32;
@@ -712,8 +680,49 @@ void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, co
                        (float)(-m->dev.p0), npatches, out);
     HIP_CHECK(hipGetLastError());
 }
+void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out) {
+    static const int variant = [] { const char* e = getenv("FD_SVM_KERNEL"); return e ? atoi(e) : 2; }();
+    svm_rbf_mfma_launch_variant(ctx, m, xFrag, xx, npatches, out, variant);
+}
 
 bool fd_svm_u8_mfma_available(const fd_svm* m);
+
+// ---- one launch function per kernel body: the launchers below and the test hook (fd_debug_svm_launch) share the geometry and the checks
+static size_t svm_u8_mfma_lds_bytes(const fd_svm* m) {   // 32 patches + one partial sum per (tile of 32 support vectors, patch)
+    return (size_t)32 * (m->dev.KS * 32 + 16) + 384 + sizeof(double) * (size_t)(m->dev.nsv32 >> 5) * 32;
+}
+template <int SU_W>
+static void svm_launch_u8_mfma(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n,
+                               const unsigned int* dcount, double* dout) {
+    hipLaunchKernelGGL(k_svm_u8_rbf_mfma<SU_W>, dim3((unsigned)((n + 31) / 32)), dim3(64 * SU_W), svm_u8_mfma_lds_bytes(m), st, m->dev, dfeat, didx,
+                       stride_bytes, n, dout, dcount);
+    HIP_CHECK(hipGetLastError());
+}
+static bool svm_u8_lanes_fits(const fd_svm* m, int pb) { return (size_t)pb * m->dev.dpad <= SVM_LDS_LIMIT; }
+// k_svm_u8_lanes with pb (2, 4 or 8) vectors per workgroup
+static void svm_launch_u8_lanes(hipStream_t st, const fd_svm* m, int pb, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n,
+                                double* dout) {
+    if (!svm_u8_lanes_fits(m, pb)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
+    const size_t lb = (size_t)pb * m->dev.dpad;
+    const unsigned grid = (unsigned)((n + pb - 1) / pb);
+#define FD_SVM_U8(H, P) hipLaunchKernelGGL((k_svm_u8_lanes<H, P>), dim3(grid), dim3(256), lb, st, m->dev, dfeat, didx, stride_bytes, n, dout)
+    if (m->dev.kernel == FD_KERNEL_HIK) {
+        if (pb == 8) FD_SVM_U8(true, 8); else if (pb == 4) FD_SVM_U8(true, 4); else FD_SVM_U8(true, 2);
+    } else {
+        if (pb == 8) FD_SVM_U8(false, 8); else if (pb == 4) FD_SVM_U8(false, 4); else FD_SVM_U8(false, 2);
+    }
+#undef FD_SVM_U8
+    HIP_CHECK(hipGetLastError());
+}
+static bool svm_generic_fits(const fd_svm* m) { return (size_t)m->dev.dim * 4 <= SVM_LDS_LIMIT; }
+// k_svm_generic (f32 rows): one workgroup per row, n of them; dcount may be NULL
+static void svm_launch_generic(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n,
+                               const unsigned int* dcount, double* dout) {
+    if (!svm_generic_fits(m)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
+    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)n), dim3(256), (size_t)m->dev.dim * 4, st, m->dev, dfeat, didx, stride_bytes, dout, dcount);
+    HIP_CHECK(hipGetLastError());
+}
+
 // generic scoring of n device-resident feature vectors (optionally gathered by slot index)
 void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes,
                               int64_t n, double* dout);
@@ -731,30 +740,16 @@ void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat
     // thousands of support vectors -- the lane-per-support-vector kernel takes over.  A 16-wavefront variant made a lone small launch
     // faster, 25 -> 21 us, and cost config 3 a third of its throughput: whole CUs taken from the other calls' kernels; removed.)
     if (fd_svm_u8_mfma_available(m)) {
-        const size_t lb = (size_t)32 * (m->dev.KS * 32 + 16) + 384 + sizeof(double) * (size_t)(m->dev.nsv32 >> 5) * 32;
-        const unsigned grid = (unsigned)((n + 31) / 32);
-        hipLaunchKernelGGL(k_svm_u8_rbf_mfma<8>, dim3(grid), dim3(64 * 8), lb, st, m->dev, dfeat, didx, stride_bytes, n, dout, (const unsigned int*)nullptr);
-        HIP_CHECK(hipGetLastError());
+        svm_launch_u8_mfma<8>(st, m, dfeat, didx, stride_bytes, n, nullptr, dout);
         return;
     }
     if (m->dev.dtype == FD_DTYPE_U8) {
-        const int pb = n >= 16384 ? 8 : (n >= 8192 ? 4 : 2);   // measured: 4 per workgroup at n ~ 2000-4000 is slower than 2 (fewer workgroups)
-        const size_t lb = (size_t)pb * m->dev.dpad;
-        if (lb > 64 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
-        const unsigned grid = (unsigned)((n + pb - 1) / pb);
-#define FD_SVM_U8(H, P) hipLaunchKernelGGL((k_svm_u8_lanes<H, P>), dim3(grid), dim3(256), lb, st, m->dev, dfeat, didx, stride_bytes, n, dout)
-        if (m->dev.kernel == FD_KERNEL_HIK) {
-            if (pb == 8) FD_SVM_U8(true, 8); else if (pb == 4) FD_SVM_U8(true, 4); else FD_SVM_U8(true, 2);
-        } else {
-            if (pb == 8) FD_SVM_U8(false, 8); else if (pb == 4) FD_SVM_U8(false, 4); else FD_SVM_U8(false, 2);
-        }
-#undef FD_SVM_U8
+        int pb = n >= 16384 ? 8 : (n >= 8192 ? 4 : 2);   // measured: 4 per workgroup at n ~ 2000-4000 is slower than 2 (fewer workgroups)
+        while (pb > 2 && !svm_u8_lanes_fits(m, pb)) pb >>= 1;   // long vectors: as many per workgroup as the LDS holds (two must fit)
+        svm_launch_u8_lanes(st, m, pb, dfeat, didx, stride_bytes, n, dout);
         return;
     }
-    const size_t ldsBytes = m->dev.dtype == FD_DTYPE_U8 ? (size_t)m->dev.dpad : (size_t)m->dev.dim * 4;
-    if (ldsBytes > 64 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
-    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)n), dim3(256), ldsBytes, st, m->dev, dfeat, didx, stride_bytes, dout, (const unsigned int*)nullptr);
-    HIP_CHECK(hipGetLastError());
+    svm_launch_generic(st, m, dfeat, didx, stride_bytes, n, nullptr, dout);
 }
 
 // k_svm_generic on f32 rows with the row count on the device (the five-stage detector with an RVM first stage, rvm_five_stage.hpp: the
@@ -764,30 +759,24 @@ void fd_svm_f32_launch_counted(hipStream_t st, const fd_svm* m, const void* dfea
                                double* dout) {
     if (nmax <= 0) return;
     if (m->dev.dtype != FD_DTYPE_F32) FD_THROW(FD_ERR_LOGIC, "fd_svm_f32_launch_counted: f32 support vectors only");
-    const size_t ldsBytes = (size_t)m->dev.dim * 4;
-    if (ldsBytes > 64 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", m->dev.dim);
-    hipLaunchKernelGGL(k_svm_generic, dim3((unsigned)nmax), dim3(256), ldsBytes, st, m->dev, dfeat, (const uint32_t*)nullptr, stride_bytes, dout, dcount);
-    HIP_CHECK(hipGetLastError());
+    svm_launch_generic(st, m, dfeat, nullptr, stride_bytes, nmax, dcount, dout);
 }
 
 // The u8 RBF stage with the vector count on the device (the five-stage tail: overlap elimination and this launch are queued behind the
 // cascade without a host round trip).  The launch covers nmax vectors; min(*dcount, nmax) are scored.  false: this model has no
 // k_svm_u8_rbf_mfma tables (the caller keeps the host-driven path).
 bool fd_svm_u8_mfma_available(const fd_svm* m) {
-    const size_t lb = (size_t)32 * (m->dev.KS * 32 + 16) + 384 + sizeof(double) * (size_t)(m->dev.nsv32 >> 5) * 32;
-    return m->dev.dtype == FD_DTYPE_U8 && m->dev.kernel == FD_KERNEL_RBF && m->dev.svA && lb <= 64 * 1024;
+    return m->dev.dtype == FD_DTYPE_U8 && m->dev.kernel == FD_KERNEL_RBF && m->dev.svA && svm_u8_mfma_lds_bytes(m) <= SVM_LDS_LIMIT;
 }
 void fd_svm_u8_mfma_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t nmax,
                                    const unsigned int* dcount, double* dout) {
     if (nmax <= 0) return;
-    const size_t lb = (size_t)32 * (m->dev.KS * 32 + 16) + 384 + sizeof(double) * (size_t)(m->dev.nsv32 >> 5) * 32;
     // a frame's worth of vectors (a handful of workgroups: the launch is a chain of latencies) takes sixteen wavefronts per workgroup,
     // half the support-vector tiles per wavefront and a tile's operands requested at once; the sums are the same (fixed pairwise order)
     if (nmax <= 32 * 64)
-        hipLaunchKernelGGL(k_svm_u8_rbf_mfma<16>, dim3((unsigned)((nmax + 31) / 32)), dim3(64 * 16), lb, st, m->dev, dfeat, didx, stride_bytes, nmax, dout, dcount);
+        svm_launch_u8_mfma<16>(st, m, dfeat, didx, stride_bytes, nmax, dcount, dout);
     else
-        hipLaunchKernelGGL(k_svm_u8_rbf_mfma<8>, dim3((unsigned)((nmax + 31) / 32)), dim3(64 * 8), lb, st, m->dev, dfeat, didx, stride_bytes, nmax, dout, dcount);
-    HIP_CHECK(hipGetLastError());
+        svm_launch_u8_mfma<8>(st, m, dfeat, didx, stride_bytes, nmax, dcount, dout);
 }
 
 extern "C" {
@@ -827,10 +816,6 @@ int fd_svm_create(fd_ctx* ctx, const fd_svm_model* md, fd_svm** out) {
                     sv[(size_t)s * d.dpad + k] = v;
                     ss[s] += (uint32_t)v * v;
                 }
-            up(m->sv, sv.data(), sv.size());
-            up(m->ss, ss.data(), sizeof(uint32_t) * ss.size());
-            d.sv = m->sv.p;
-            d.ss_u32 = m->ss.as<uint32_t>();
             {   // word-transposed copy for the lane == support-vector kernel
                 d.nsvp = (d.nsv + 63) & ~63;
                 const int nd = d.dpad >> 2;
@@ -945,6 +930,123 @@ int fd_debug_svm_u8_both(fd_ctx* ctx, const fd_svm* m_, const uint8_t* features,
         HIP_CHECK(hipMemcpyAsync(out8, m->dist.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(out16, m->dist.as<double>() + n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+// Test hook (include/fd_hip_bench.h): ONE named kernel body, through the launch function the launchers above use, on host rows staged
+// at the caller's stride.  Every refusal happens before anything is queued.
+int fd_debug_svm_launch(fd_ctx* ctx, const fd_svm* m, const void* features, int64_t n, int64_t row_stride_bytes, const uint32_t* idx,
+                        int64_t n_idx, int64_t dcount, int variant, double* out) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !m || !features || !out || n < 1 || (idx && n_idx < 1)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: bad argument");
+        const SvmDev& d = m->dev;
+        const bool u8 = d.dtype == FD_DTYPE_U8;
+        const int64_t rowBytes = (int64_t)d.dim * (u8 ? 1 : 4);
+        if (row_stride_bytes < rowBytes || (!u8 && (row_stride_bytes & 3)))
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: row stride %lld for rows of %lld bytes", (long long)row_stride_bytes, (long long)rowBytes);
+        const int64_t items = idx ? n_idx : n;
+        for (int64_t i = 0; idx && i < n_idx; ++i)
+            if ((int64_t)idx[i] >= n) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: slot %u of %lld rows", idx[i], (long long)n);
+        if (dcount > 0xffffffffll) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: count beyond 32 bits");
+        const bool counted = dcount >= 0;
+        const bool f32Mfma = variant == FD_SVM_VARIANT_RBF_MFMA || variant == FD_SVM_VARIANT_RBF_MFMA_SVS || variant == FD_SVM_VARIANT_RBF_MFMA_PRODUCTION;
+        switch (variant) {   // what the model cannot run, or the kernel has no argument for, is refused here
+        case FD_SVM_VARIANT_PRODUCTION:
+            if (counted && u8 && !fd_svm_u8_mfma_available(m)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: no counted launcher for this u8 model");
+            if (counted && !u8 && idx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: the counted f32 launcher takes no slot list");
+            if (!counted && u8 && !fd_svm_u8_mfma_available(m) && !svm_u8_lanes_fits(m, 2)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", d.dim);
+            if (!u8 && !svm_generic_fits(m)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", d.dim);
+            break;
+        case FD_SVM_VARIANT_U8_MFMA_8:
+        case FD_SVM_VARIANT_U8_MFMA_16:
+            if (!fd_svm_u8_mfma_available(m)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: the model has no u8 RBF MFMA path");
+            break;
+        case FD_SVM_VARIANT_U8_LANES_2:
+        case FD_SVM_VARIANT_U8_LANES_4:
+        case FD_SVM_VARIANT_U8_LANES_8: {
+            const int pb = variant == FD_SVM_VARIANT_U8_LANES_2 ? 2 : variant == FD_SVM_VARIANT_U8_LANES_4 ? 4 : 8;
+            if (!u8) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: k_svm_u8_lanes needs a u8 model");
+            if (counted) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: k_svm_u8_lanes takes no device count");
+            if (!svm_u8_lanes_fits(m, pb)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", d.dim);
+            break;
+        }
+        case FD_SVM_VARIANT_GENERIC:
+            if (u8) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: k_svm_generic needs an f32 model");
+            if (!svm_generic_fits(m)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature vector too long (%d)", d.dim);
+            break;
+        case FD_SVM_VARIANT_RBF_MFMA:
+        case FD_SVM_VARIANT_RBF_MFMA_SVS:
+        case FD_SVM_VARIANT_RBF_MFMA_PRODUCTION:
+            if (!d.svFrag) FD_THROW(FD_ERR_INVALID_ARGUMENT, "SVM has no MFMA path (needs an RBF kernel on f32 vectors)");
+            if (idx || counted) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: the f32 MFMA kernels take neither a slot list nor a device count");
+            if (variant == FD_SVM_VARIANT_RBF_MFMA_SVS && d.KP != 328 && d.KP != 336)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: k_svm_rbf_mfma_svs is instantiated for padded lengths 328 and 336, not %d", d.KP);
+            if (!(d.KP == 328 || d.KP == 336) || variant == FD_SVM_VARIANT_RBF_MFMA)
+                if (fd_svm_rbf_lds_bytes(d.KP) > 160 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature length %d too large for the MFMA SVM kernel", d.dim);
+            break;
+        default:
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_svm_launch: no variant %d", variant);
+        }
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        DevBuf dfeat, didx, dcnt, dout;
+        dout.reserve(sizeof(double) * (size_t)items);
+        HIP_CHECK(hipMemsetAsync(dout.p, 0xff, sizeof(double) * (size_t)items, st));   // the sentinel: a NaN of all-one bits
+        double* o = dout.as<double>();
+        const unsigned int hcount = counted ? (unsigned int)dcount : 0u;   // copied from here: lives until the final synchronize
+        if (f32Mfma) {   // fragment-major rows padded to 64 (pad rows zero), |x|^2 in float: what hog.hip hands to fd_svm_rbf_mfma_launch
+            const int64_t npad = ((n + 63) / 64) * 64;
+            std::vector<float> frag((size_t)npad * d.KP, 0.f), xx((size_t)npad, 0.f);
+            for (int64_t r = 0; r < n; ++r) {
+                const float* x = reinterpret_cast<const float*>((const unsigned char*)features + r * row_stride_bytes);
+                float acc = 0.f;
+                for (int k = 0; k < d.dim; ++k) {
+                    frag[frag_index(r, k, d.KP)] = x[k];
+                    acc += x[k] * x[k];
+                }
+                xx[(size_t)r] = acc;
+            }
+            dfeat.reserve(sizeof(float) * frag.size());
+            dcnt.reserve(sizeof(float) * xx.size());   // no count here: the buffer carries |x|^2
+            HIP_CHECK(hipMemcpyAsync(dfeat.p, frag.data(), sizeof(float) * frag.size(), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(dcnt.p, xx.data(), sizeof(float) * xx.size(), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));   // frag and xx are pageable and leave scope below
+            if (variant == FD_SVM_VARIANT_RBF_MFMA_PRODUCTION)
+                fd_svm_rbf_mfma_launch(ctx, m, dfeat.as<float>(), dcnt.as<float>(), n, o);
+            else
+                svm_rbf_mfma_launch_variant(ctx, m, dfeat.as<float>(), dcnt.as<float>(), n, o, variant == FD_SVM_VARIANT_RBF_MFMA_SVS ? 2 : 1);
+        } else {
+            const size_t featBytes = (size_t)(n - 1) * (size_t)row_stride_bytes + (size_t)rowBytes;   // the last row ends with its last element
+            dfeat.reserve(featBytes + 16);
+            HIP_CHECK(hipMemcpyAsync(dfeat.p, features, featBytes, hipMemcpyHostToDevice, st));
+            const uint32_t* di = nullptr;
+            if (idx) {
+                didx.reserve(sizeof(uint32_t) * (size_t)n_idx);
+                HIP_CHECK(hipMemcpyAsync(didx.p, idx, sizeof(uint32_t) * (size_t)n_idx, hipMemcpyHostToDevice, st));
+                di = didx.as<uint32_t>();
+            }
+            const unsigned int* dc = nullptr;
+            if (counted) {
+                dcnt.reserve(sizeof(unsigned int));
+                HIP_CHECK(hipMemcpyAsync(dcnt.p, &hcount, sizeof(unsigned int), hipMemcpyHostToDevice, st));
+                dc = dcnt.as<unsigned int>();
+            }
+            switch (variant) {
+            case FD_SVM_VARIANT_PRODUCTION:
+                if (!counted) fd_svm_generic_launch_on(st, m, dfeat.p, di, row_stride_bytes, items, o);
+                else if (u8) fd_svm_u8_mfma_launch_counted(st, m, dfeat.p, di, row_stride_bytes, items, dc, o);
+                else fd_svm_f32_launch_counted(st, m, dfeat.p, row_stride_bytes, items, dc, o);
+                break;
+            case FD_SVM_VARIANT_U8_MFMA_8: svm_launch_u8_mfma<8>(st, m, dfeat.p, di, row_stride_bytes, items, dc, o); break;
+            case FD_SVM_VARIANT_U8_MFMA_16: svm_launch_u8_mfma<16>(st, m, dfeat.p, di, row_stride_bytes, items, dc, o); break;
+            case FD_SVM_VARIANT_U8_LANES_2: svm_launch_u8_lanes(st, m, 2, dfeat.p, di, row_stride_bytes, items, o); break;
+            case FD_SVM_VARIANT_U8_LANES_4: svm_launch_u8_lanes(st, m, 4, dfeat.p, di, row_stride_bytes, items, o); break;
+            case FD_SVM_VARIANT_U8_LANES_8: svm_launch_u8_lanes(st, m, 8, dfeat.p, di, row_stride_bytes, items, o); break;
+            default: svm_launch_generic(st, m, dfeat.p, di, row_stride_bytes, items, dc, o); break;
+            }
+        }
+        HIP_CHECK(hipMemcpyAsync(out, dout.p, sizeof(double) * (size_t)items, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
     });
 }
 

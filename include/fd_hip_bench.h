@@ -91,6 +91,30 @@ int fd_debug_resize_stage(const uint8_t* image, int sw, int sh, int dw0, int dh0
  * the fd_wvm handle: one handle must not be used from two threads at a time.) */
 int fd_debug_svm_u8_both(fd_ctx* ctx, const fd_svm* svm, const uint8_t* features, int64_t n, double* out8, double* out16);
 
+/* Test hook: hyperplane distances through ONE named kernel body of svm.hip, launched with the geometry and the checks the library's
+ * launchers use (tests/test_gpu_svm_score.py).  `features`: n host rows (u8 or f32, as the model), row_stride_bytes apart (f32: a
+ * multiple of 4), staged on the device at that stride.  `idx` (may be NULL): n_idx slots into the rows; the launch then scores the
+ * n_idx gathered rows, otherwise the n rows in order.  dcount < 0: no device-side count; otherwise the value is written to a device word
+ * the kernel reads, and min(dcount, launch size) entries are scored.  `out` (one double per scored entry) is filled on the device with
+ * a sentinel of all-one bits (a NaN) before the launch, so entries the kernel did not write can be told apart.
+ * FD_ERR_INVALID_ARGUMENT, before anything is launched, for a variant the model cannot run (wrong dtype or kernel type, no tables,
+ * padded length other than 328 / 336 for _SVS, LDS over budget) or that has no such argument: only the u8 MFMA kernels and
+ * k_svm_generic read a count, the f32 MFMA kernels take no slot list. */
+enum {
+    FD_SVM_VARIANT_PRODUCTION = 0,         /* fd_svm_generic_launch_on; with a count fd_svm_u8_mfma_launch_counted (u8) / fd_svm_f32_launch_counted (f32) */
+    FD_SVM_VARIANT_U8_MFMA_8 = 1,          /* k_svm_u8_rbf_mfma<8> */
+    FD_SVM_VARIANT_U8_MFMA_16 = 2,         /* k_svm_u8_rbf_mfma<16> */
+    FD_SVM_VARIANT_U8_LANES_2 = 3,         /* k_svm_u8_lanes<*, 2>: HIK or not as the model says */
+    FD_SVM_VARIANT_U8_LANES_4 = 4,
+    FD_SVM_VARIANT_U8_LANES_8 = 5,
+    FD_SVM_VARIANT_GENERIC = 6,            /* k_svm_generic (f32 rows) */
+    FD_SVM_VARIANT_RBF_MFMA = 7,           /* k_svm_rbf_mfma (A-resident); rows packed fragment-major, padded to 64, |x|^2 summed in float on the host */
+    FD_SVM_VARIANT_RBF_MFMA_SVS = 8,       /* k_svm_rbf_mfma_svs<41 | 42> + k_sum_partials, same packing */
+    FD_SVM_VARIANT_RBF_MFMA_PRODUCTION = 9 /* fd_svm_rbf_mfma_launch (what fd_detect_hog_svm calls; FD_SVM_KERNEL is read there), same packing */
+};
+int fd_debug_svm_launch(fd_ctx* ctx, const fd_svm* svm, const void* features, int64_t n, int64_t row_stride_bytes, const uint32_t* idx,
+                        int64_t n_idx, int64_t dcount, int variant, double* out);
+
 #ifdef __cplusplus
 }
 #endif
