@@ -100,11 +100,8 @@ int fd_ehog_patch_batch(fd_ctx* ctx, const uint8_t* bin_patches, int64_t n, int 
         const size_t bytes = (size_t)n * hp.patch_w * hp.patch_h * channels;
         S.patchIn.reserve(bytes);
         HIP_CHECK(hipMemcpyAsync(S.patchIn.p, bin_patches, bytes, hipMemcpyHostToDevice, ctx->stream));
-        HogWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.n = 1; wt.sx = 1; wt.sy = hp.patch_h; wt.total = n;
-        wt.l[0].bx = 0; wt.l[0].by = 0; wt.l[0].nx = 1; wt.l[0].ny = (int32_t)n; wt.l[0].lw = hp.patch_w; wt.l[0].off = 0; wt.l[0].first = 0;
-        launch_hist_features(ctx, S.patchIn.as<uint8_t>(), wt, hd, S);   // S.feat: n x rows * cols * bins raw cell histograms
+        // S.feat: n x rows * cols * bins raw cell histograms
+        launch_hist_features(ctx, S.patchIn.as<uint8_t>(), fd_win_table_column(n, hp.patch_w, hp.patch_h), hd, S);
         const int D = ep->bins + (ep->signed_and_unsigned ? ep->bins / 2 : 0) + 4;
         const int64_t total = n * hd.rows * hd.cols * D;
         S.xx.reserve(sizeof(float) * (size_t)total);

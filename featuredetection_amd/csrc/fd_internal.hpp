@@ -350,16 +350,6 @@ static inline void fd_allow_lds(fd_ctx* ctx, const void* kernel, int bytes, uint
     done |= bit;
 }
 
-// what the fused HOG + SVM kernel (hog_svm_fused.hpp, launched from hog.hip) needs of an f32 RBF model (svm.hip)
-struct FdSvmFusedView {
-    const float* svFrag;   // fragment-major support vectors [nsv_pad][KP]
-    const float* ss;       // |s|^2, [nsv_pad]
-    const float* coeff;    // [nsv_pad], zero padded
-    int nsv_pad, KP;
-    float bias;
-    double gamma;
-};
-
 struct FdStreamSwap {   // temporarily redirects everything that launches on ctx->stream
     fd_ctx* c;
     hipStream_t keep;
@@ -443,6 +433,10 @@ static inline void fd_pyramid_require_single(const fd_pyramid* p, const char* wh
     if (p->nimg > 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the pyramid holds %d frames (fd_pyramid_set_frames); use fd_detect_five_stage_frames", who, p->nimg);
 }
 
+static inline void fd_pyramid_require_image(const fd_pyramid* p) {
+    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+}
+
 // makes `consumer` wait for the pyramid's last update when that ran on another stream
 static inline void fd_pyramid_wait(const fd_pyramid* p, hipStream_t consumer) {
     if (p->ready && consumer != p->readyStream) HIP_CHECK(hipStreamWaitEvent(consumer, p->ready, 0));
@@ -452,6 +446,40 @@ void fd_pyramid_update_on(fd_pyramid* p, const uint8_t* image, int w, int h, int
 constexpr int FD_MAX_FRAMES = 64;
 void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, const int* roi,
                          std::vector<WindowLayer>& out, int64_t& total);
+
+// window id -> detection record geometry (wvm.hip)
+void fd_window_to_detection(const fd_pyramid* p, const std::vector<WindowLayer>& wls, int sx, int sy, int64_t wid, fd_detection& d);
+
+// ---------------- SVM scoring: what the detectors use of a model (svm.hip) ----------------
+// what the fused HOG + SVM kernel (hog_svm_fused.hpp, launched from hog.hip) needs of an f32 RBF model (svm.hip)
+struct FdSvmFusedView {
+    const float* svFrag;   // fragment-major support vectors [nsv_pad][KP]
+    const float* ss;       // |s|^2, [nsv_pad]
+    const float* coeff;    // [nsv_pad], zero padded
+    int nsv_pad, KP;
+    float bias;
+    double gamma;
+};
+bool fd_svm_fused_view(const fd_svm* m, FdSvmFusedView* v);
+bool fd_svm_has_mfma_path(const fd_svm* m);
+int fd_svm_KP(const fd_svm* m);
+float fd_svm_threshold(const fd_svm* m);
+int fd_svm_dim(const fd_svm* m);
+bool fd_svm_is_u8(const fd_svm* m);
+double fd_svm_probability(const fd_svm* m, double d);
+void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out);
+// generic scoring of n device-resident feature vectors (optionally gathered by slot index); _on: explicit stream, touches no context state
+void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
+void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
+// the row count on the device: the launch covers nmax rows, min(*dcount, nmax) are scored
+void fd_svm_f32_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, int64_t stride_bytes, int64_t nmax, const unsigned int* dcount,
+                               double* dout);
+bool fd_svm_u8_mfma_available(const fd_svm* m);
+void fd_svm_u8_mfma_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t nmax,
+                                   const unsigned int* dcount, double* dout);
+// classifier positives of N scored windows -> detection records in extraction order (hog.hip)
+void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_svm* svm, const std::vector<WindowLayer>& wls, int sx, int sy,
+                                    const double* ddist, int64_t N, fd_detection* out, int64_t cap, int64_t* count, double* all_distance);
 
 // ---------------- SVM training (svm_train.hip) ----------------
 // Where the support-vector form (fd_kernel_svm_*) leaves one problem's model (host).  The first n_sv entries of sv_index /

@@ -10,23 +10,12 @@
 // MFMA SVM kernel consumes (svm.hip), together with |x|^2.
 // Algorithmic HBM bytes per window: 2*pw*ph (layer read, mostly L2 hits) + 4*F (feature write).
 #include "fd_internal.hpp"
+#include "fd_device.hpp"
+#include "win_table.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
 
-constexpr int HOG_MAX_LAYERS = 64;
-
-struct HogWinLayer {
-    int32_t bx, by, nx, ny;
-    int32_t lw;          // layer width in pixels
-    uint32_t off;        // byte offset of the filtered (bin, weight) layer
-    int64_t first;
-};
-struct HogWinTable {
-    int32_t n, sx, sy, pad;
-    int64_t total;
-    HogWinLayer l[HOG_MAX_LAYERS];
-};
 struct HogDev {
     int32_t pw, ph, bins, cell, block, sau;
     int32_t rows, cols;      // cell grid
@@ -36,28 +25,14 @@ struct HogDev {
     int32_t KP;              // padded length for the fragment layout
 };
 
-// from svm.hip
-struct fd_svm;
-bool fd_svm_has_mfma_path(const fd_svm* m);
-int fd_svm_KP(const fd_svm* m);
-float fd_svm_threshold(const fd_svm* m);
-int fd_svm_dim(const fd_svm* m);
-bool fd_svm_is_u8(const fd_svm* m);
-double fd_svm_probability(const fd_svm* m, double d);
-void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out);
-void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-bool fd_svm_fused_view(const fd_svm* m, FdSvmFusedView* v);
-
 namespace {
+
+using fd_dev::wave_sync;
+using fd_dev::win_locate;
 
 constexpr int HOG_MAX_HIST = 1024;   // cells * bins
 constexpr int HOG_MAX_CELLS = 64;
 constexpr int HOG_MAX_BLOCKS = 64;
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // fp32 add executed by the LDS unit (ds_add_f32, no return value): fire-and-forget, in program order per wave
 __device__ __forceinline__ void lds_fadd(float* p, float v) {
@@ -87,7 +62,7 @@ struct HogTables {
 // tile of the MFMA SVM kernel; the WPW windows of a pass fill WPW*16 contiguous bytes per slot.
 // Only ~3 KB of LDS per wave, so occupancy (and with it latency hiding) is register-bound.
 template <bool FRAG>
-__global__ __launch_bounds__(256) void k_hog_tile(const uint8_t* __restrict__ arena, HogWinTable wt, HogDev hp, HogTables tab,
+__global__ __launch_bounds__(256) void k_hog_tile(const uint8_t* __restrict__ arena, FdWinTable wt, HogDev hp, HogTables tab,
                                                   int64_t npad, float* __restrict__ feat, float* __restrict__ xx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -129,12 +104,9 @@ __global__ __launch_bounds__(256) void k_hog_tile(const uint8_t* __restrict__ ar
         for (int b = 0; b < B; ++b) hist[b * 64 + lane] = 0.f;
         if (valid) {
             // window geometry per lane (windows of one pass may straddle rows / layers)
-            int li = 0;
-            for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
-            const HogWinLayer wl = wt.l[li];
-            const int local = (int)(wid - wl.first);
-            const int iy = local / wl.nx, ix = local - iy * wl.nx;
-            const unsigned short* src = (const unsigned short*)(arena + wl.off) + (size_t)(wl.by + iy * wt.sy) * wl.lw + (wl.bx + ix * wt.sx);
+            int x0, y0;
+            const FdWinLayer wl = win_locate(wt, wid, x0, y0);
+            const unsigned short* src = (const unsigned short*)(arena + wl.off) + (size_t)y0 * wl.lw + x0;
             // cell histograms (HistogramFilter.cpp:150-163)
             for (int y = cr0; y < cr1; ++y) {
                 const unsigned short* rowp = src + (size_t)y * wl.lw;
@@ -211,18 +183,13 @@ float* hp_ = &hist[(v & 255u) * 64 + lane];
     }
 }
 
-struct HogPos {
-    uint32_t wid_lo, wid_hi;
-    double dist;
-};
-
-__global__ void k_select_positives(const double* __restrict__ dist, int64_t n, float threshold, HogPos* __restrict__ pos,
+__global__ void k_select_positives(const double* __restrict__ dist, int64_t n, float threshold, FdPosRec* __restrict__ pos,
                                    unsigned int* __restrict__ count, unsigned int cap) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double dv = dist[i];
         if (dv >= (double)threshold) {  // SvmClassifier.cpp:44-46
             unsigned int s = atomicAdd(count, 1u);
-            if (s < cap) pos[s] = HogPos{(uint32_t)i, (uint32_t)(i >> 32), dv};
+            if (s < cap) pos[s] = FdPosRec{(uint32_t)i, (uint32_t)(i >> 32), dv};
         }
     }
 }
@@ -306,7 +273,7 @@ size_t hog_lds_bytes(const HogDev& d, bool /*frag*/) {
 }
 
 template <bool FRAG>
-void launch_hog(fd_ctx* ctx, const fd_pyramid* p, const HogWinTable& wt, const HogDev& hd, HogScratch& S, int64_t npad, float* feat, float* xx) {
+void launch_hog(fd_ctx* ctx, const fd_pyramid* p, const FdWinTable& wt, const HogDev& hd, HogScratch& S, int64_t npad, float* feat, float* xx) {
     const HogTables tb = hog_tables(ctx, S, hd);
     const size_t lds = hog_lds_bytes(hd, FRAG);
     if (lds > 160 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "HOG feature vector too long for the LDS tile (%d floats)", hd.F);
@@ -319,41 +286,11 @@ void launch_hog(fd_ctx* ctx, const fd_pyramid* p, const HogWinTable& wt, const H
     HIP_CHECK(hipGetLastError());
 }
 
-void build_table(const fd_pyramid* p, const fd_hog_params* hp, HogWinTable& wt, std::vector<WindowLayer>& wls, bool any_bin_image = false) {
-    if (!any_bin_image) {
-        if (p->filter_kind != FD_LAYER_GRADBIN || p->interpolate)
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "HOG extraction needs a pyramid with the FD_LAYER_GRADBIN layer filter (no bin interpolation)");
-        if (p->bins != hp->bins) FD_THROW(FD_ERR_INVALID_ARGUMENT, "HogFilter bins (%d) differ from the layer filter bins (%d)", hp->bins, p->bins);
-    }
-    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
-    int64_t total;
-    fd_enumerate_layers(p, hp->patch_w, hp->patch_h, hp->step_x, hp->step_y, nullptr, wls, total);
-    if (wls.size() > (size_t)HOG_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", wls.size());
-    std::memset(&wt, 0, sizeof(wt));
-    wt.sx = hp->step_x; wt.sy = hp->step_y; wt.total = total;
-    for (const WindowLayer& w : wls) {
-        if (w.nx == 0 || w.ny == 0) continue;
-        const HostLayer& L = p->all[p->kept[w.layer]];
-        HogWinLayer& dl = wt.l[wt.n++];
-        dl.bx = w.bx; dl.by = w.by; dl.nx = w.nx; dl.ny = w.ny; dl.lw = L.w; dl.off = L.filt_off; dl.first = w.first;
-    }
-}
-
-void window_geometry(const fd_pyramid* p, const std::vector<WindowLayer>& wls, int sx, int sy, int64_t wid, fd_detection& d) {
-    size_t i = 0;
-    while (i + 1 < wls.size() && (wls[i + 1].first <= wid)) ++i;
-    while (wls[i].nx == 0 || wls[i].ny == 0) --i;
-    const WindowLayer& w = wls[i];
-    const HostLayer& L = p->all[p->kept[w.layer]];
-    int64_t local = wid - w.first;
-    int iy = (int)(local / w.nx), ix = (int)(local % w.nx);
-    d.layer = w.layer;
-    d.lx = w.bx + ix * sx;
-    d.ly = w.by + iy * sy;
-    d.w = w.ow;
-    d.h = w.oh;
-    d.cx = fd_cvRound(d.lx / L.scale) + w.ow / 2;
-    d.cy = fd_cvRound(d.ly / L.scale) + w.oh / 2;
+void build_table(const fd_pyramid* p, const fd_hog_params* hp, FdWinTable& wt, std::vector<WindowLayer>& wls) {
+    if (p->filter_kind != FD_LAYER_GRADBIN || p->interpolate)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "HOG extraction needs a pyramid with the FD_LAYER_GRADBIN layer filter (no bin interpolation)");
+    if (p->bins != hp->bins) FD_THROW(FD_ERR_INVALID_ARGUMENT, "HogFilter bins (%d) differ from the layer filter bins (%d)", hp->bins, p->bins);
+    fd_win_table_build(p, hp->patch_w, hp->patch_h, hp->step_x, hp->step_y, nullptr, /*filtered=*/true, wt, wls);
 }
 
 // features for all windows (fragment-major + |x|^2) then the MFMA SVM; returns window count
@@ -365,7 +302,7 @@ int64_t run_hog_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hog_
     if (!fd_svm_has_mfma_path(svm)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "the HOG detector needs an RBF SVM on f32 feature vectors");
     HogDev hd = make_hogdev(hp, fd_svm_KP(svm));
     if (((hd.F + 7) & ~7) != hd.KP) FD_THROW(FD_ERR_INVALID_ARGUMENT, "SVM dimension does not match the HOG feature length %d", hd.F);
-    HogWinTable wt;
+    FdWinTable wt;
     build_table(p, hp, wt, wls);
     const int64_t N = wt.total;
     if (N == 0) return 0;
@@ -396,8 +333,8 @@ int64_t run_hog_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hog_
         o.dist = S.dist.as<double>(); o.part = S.part.as<double>();
         o.cap = (unsigned int)std::min<int64_t>(N, 1 << 22);
         o.threshold = fd_svm_threshold(svm);
-        S.hcount.reserve(sizeof(HogPos) * ((size_t)o.cap + 1));
-        o.pos = S.hcount.as<HogPos>();          // pinned host memory is device-accessible under the same address
+        S.hcount.reserve(sizeof(FdPosRec) * ((size_t)o.cap + 1));
+        o.pos = S.hcount.as<FdPosRec>();        // pinned host memory is device-accessible under the same address
         if (!S.header.p) { S.header.reserve(64); S.headerClean = false; }
         if (!S.headerClean) HIP_CHECK(hipMemsetAsync(S.header.p, 0, 64, st));
         S.headerClean = true;                   // k_hsf_finish leaves it zero
@@ -443,7 +380,7 @@ int fd_extract_hog(fd_ctx* ctx, fd_pyramid* p, const fd_hog_params* hp, float* f
         if (!ctx || !p || !hp || !count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_extract_hog: NULL argument");
         fd_pyramid_require_single(p, "fd_extract_hog");
         HogDev hd = make_hogdev(hp, 0);
-        HogWinTable wt;
+        FdWinTable wt;
         std::vector<WindowLayer> wls;
         build_table(p, hp, wt, wls);
         *count = wt.total;
@@ -486,14 +423,14 @@ static void hog_svm_begin(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const f
     if (!t.zerocopy) {
         t.pcap = (unsigned int)std::min<int64_t>(t.N, 1 << 22);
         // record 0 of the positive buffer is the header (counter), so that counter + first positives come back in one copy
-        S.pos.reserve(sizeof(HogPos) * ((size_t)t.pcap + 1));
-        S.hcount.reserve(sizeof(HogPos) * ((size_t)t.pcap + 1));
-        HIP_CHECK(hipMemsetAsync(S.pos.p, 0, sizeof(HogPos), st));
+        S.pos.reserve(sizeof(FdPosRec) * ((size_t)t.pcap + 1));
+        S.hcount.reserve(sizeof(FdPosRec) * ((size_t)t.pcap + 1));
+        HIP_CHECK(hipMemsetAsync(S.pos.p, 0, sizeof(FdPosRec), st));
         hipLaunchKernelGGL(k_select_positives, dim3((unsigned)std::min<int64_t>((t.N + 255) / 256, 2048)), dim3(256), 0, st,
-                           S.dist.as<double>(), t.N, fd_svm_threshold(svm), S.pos.as<HogPos>() + 1, S.pos.as<unsigned int>(), t.pcap);
+                           S.dist.as<double>(), t.N, fd_svm_threshold(svm), S.pos.as<FdPosRec>() + 1, S.pos.as<unsigned int>(), t.pcap);
         HIP_CHECK(hipGetLastError());
         const size_t first = std::min<size_t>(t.pcap, HOG_FIRST_CHUNK);
-        HIP_CHECK(hipMemcpyAsync(S.hcount.p, S.pos.p, sizeof(HogPos) * (first + 1), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(S.hcount.p, S.pos.p, sizeof(FdPosRec) * (first + 1), hipMemcpyDeviceToHost, st));
     }
     if (!t.done) HIP_CHECK(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(t.done, st));
@@ -509,27 +446,18 @@ static void hog_svm_end(fd_ctx* ctx, fd_hog_svm_ticket& t, fd_detection* out, in
         HIP_CHECK(hipEventElapsedTime(&ctx->last_kernel_ms, ctx->ev0, ctx->ev1));
         ctx->last_kernel = t.zerocopy ? "k_hog_svm_fused" : "k_svm_rbf_mfma";
     }
-    HogPos* h = S.hcount.as<HogPos>();
+    FdPosRec* h = S.hcount.as<FdPosRec>();
     const unsigned int cnt = h[0].wid_lo;
     if (cnt > t.pcap) FD_THROW(FD_ERR_DEVICE_CAPACITY, "fd_detect_hog_svm: %u positives exceed the device buffer", cnt);
     const size_t first = t.zerocopy ? (size_t)t.pcap : std::min<size_t>(t.pcap, HOG_FIRST_CHUNK);
-    if (cnt > first) HIP_CHECK(hipMemcpyAsync(h + 1 + first, S.pos.as<HogPos>() + 1 + first, sizeof(HogPos) * (cnt - first), hipMemcpyDeviceToHost, st));
+    if (cnt > first) HIP_CHECK(hipMemcpyAsync(h + 1 + first, S.pos.as<FdPosRec>() + 1 + first, sizeof(FdPosRec) * (cnt - first), hipMemcpyDeviceToHost, st));
     if (all_distance) HIP_CHECK(hipMemcpyAsync(all_distance, S.dist.p, sizeof(double) * (size_t)t.N, hipMemcpyDeviceToHost, st));
     if (cnt > first || all_distance) HIP_CHECK(hipStreamSynchronize(st));
-    HogPos* raw = h + 1;
-    auto widof = [](const HogPos& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; };
-    std::sort(raw, raw + cnt, [&](const HogPos& a, const HogPos& b) { return widof(a) < widof(b); });   // extraction order
+    FdPosRec* raw = h + 1;
+    fd_pos_sort(raw, cnt);
     *count = cnt;
-    for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i) {
-        fd_detection d;
-        std::memset(&d, 0, sizeof(d));
-        window_geometry(t.p, t.wls, t.hp.step_x, t.hp.step_y, (int64_t)widof(raw[i]), d);
-        d.level = -1;
-        d.positive = 1;
-        d.score = (float)raw[i].dist;
-        d.probability = fd_svm_probability(t.svm, raw[i].dist);
-        out[i] = d;
-    }
+    for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i)
+        out[i] = fd_pos_detection(t.p, t.wls, t.hp.step_x, t.hp.step_y, raw[i], -1, fd_svm_probability(t.svm, raw[i].d));
     if (out && (int64_t)cnt > cap) FD_THROW(FD_ERR_CAPACITY, "fd_detect_hog_svm: %u positives, capacity %lld", cnt, (long long)cap);
 }
 
@@ -664,7 +592,7 @@ __device__ __forceinline__ void hist_normalize_wave(float* v, int n, int normali
     }
 }
 
-__global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict__ arena, HogWinTable wt, HistDev hd, HistTables tab,
+__global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict__ arena, FdWinTable wt, HistDev hd, HistTables tab,
                                                       float* __restrict__ feat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -689,12 +617,9 @@ __global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict_
 
     for (int64_t wid = blockIdx.x; wid < wt.total; wid += gridDim.x) {
         // ---- window -> layer position (DirectPyramidFeatureExtractor.cpp:75-123 order)
-        int li = 0;
-        for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
-        const HogWinLayer& wl = wt.l[li];
-        const int local = (int)(wid - wl.first);
-        const int iy = local / wl.nx, ix = local - iy * wl.nx;
-        const uint8_t* src = arena + wl.off + ((size_t)(wl.by + iy * wt.sy) * wl.lw + (wl.bx + ix * wt.sx)) * ch;
+        int x0, y0;
+        const FdWinLayer& wl = win_locate(wt, wid, x0, y0);
+        const uint8_t* src = arena + wl.off + ((size_t)y0 * wl.lw + x0) * ch;
         const size_t srcStride = (size_t)wl.lw * ch;
         for (int i = lane; i < ph * rowBytes; i += 64) {
             const int y = i / rowBytes, xb = i - y * rowBytes;
@@ -964,7 +889,7 @@ void hist_tables(fd_ctx* ctx, HogScratch& S, const HistDev& d, HistTables& tb) {
 }
 
 // k_hist_features over the windows of `wt` inside `arena` -> S.feat ([N][F] floats)
-void launch_hist_features(fd_ctx* ctx, const uint8_t* arena, const HogWinTable& wt, const HistDev& hd, HogScratch& S) {
+void launch_hist_features(fd_ctx* ctx, const uint8_t* arena, const FdWinTable& wt, const HistDev& hd, HogScratch& S) {
     HIP_CHECK(hipSetDevice(ctx->device));
     const size_t lds = hist_lds_bytes(hd);
     if (lds > 160 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram feature vector too long for the LDS (%d floats)", hd.F);
@@ -983,18 +908,15 @@ int64_t run_hist_features(fd_ctx* ctx, fd_pyramid* p, const fd_hist_params* hp, 
     if (!hp) FD_THROW(FD_ERR_INVALID_ARGUMENT, "NULL histogram parameters");
     if (p->filter_kind != FD_LAYER_GRADBIN && p->filter_kind != FD_LAYER_LBP)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram features need a pyramid whose layers are bin images (FD_LAYER_GRADBIN or FD_LAYER_LBP)");
-    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+    fd_pyramid_require_image(p);   // before kept[0] is read
     const int ch = p->all[p->kept[0]].ch;
     if ((hp->kind == FD_HIST_HOG || hp->kind == FD_HIST_PYRAMID_HOG) && ch == 1)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "HOG features need a gradient bin image (FD_LAYER_GRADBIN)");
     if (p->filter_kind == FD_LAYER_GRADBIN && p->bins != hp->bins)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram bins (%d) differ from the layer filter bins (%d)", hp->bins, p->bins);
     hd = make_histdev(hp, ch);
-    fd_hog_params g;
-    std::memset(&g, 0, sizeof(g));
-    g.patch_w = hp->patch_w; g.patch_h = hp->patch_h; g.step_x = hp->step_x; g.step_y = hp->step_y; g.bins = hp->bins;
-    HogWinTable wt;
-    build_table(p, &g, wt, wls, /*any_bin_image=*/true);
+    FdWinTable wt;
+    fd_win_table_build(p, hp->patch_w, hp->patch_h, hp->step_x, hp->step_y, nullptr, /*filtered=*/true, wt, wls);
     const int64_t N = wt.total;
     if (N == 0) return 0;
     launch_hist_features(ctx, p->arena.as<uint8_t>(), wt, hd, S);
@@ -1010,11 +932,11 @@ void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_s
     HogScratch& S = scratch(ctx);
     hipStream_t st = ctx->stream;
     const unsigned int pcap = (unsigned int)std::min<int64_t>(N, 1 << 22);
-    S.pos.reserve(sizeof(HogPos) * (size_t)pcap);
+    S.pos.reserve(sizeof(FdPosRec) * (size_t)pcap);
     S.counter.reserve(256);
     HIP_CHECK(hipMemsetAsync(S.counter.p, 0, 4, st));
     hipLaunchKernelGGL(k_select_positives, dim3((unsigned)std::min<int64_t>((N + 255) / 256, 2048)), dim3(256), 0, st, ddist, N,
-                       fd_svm_threshold(svm), S.pos.as<HogPos>(), S.counter.as<unsigned int>(), pcap);
+                       fd_svm_threshold(svm), S.pos.as<FdPosRec>(), S.counter.as<unsigned int>(), pcap);
     HIP_CHECK(hipGetLastError());
     unsigned int* hcnt = (unsigned int*)fd_pinned(ctx, 64);
     HIP_CHECK(hipMemcpyAsync(hcnt, S.counter.p, 4, hipMemcpyDeviceToHost, st));
@@ -1022,21 +944,12 @@ void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_s
     HIP_CHECK(hipStreamSynchronize(st));
     const unsigned int cnt = *hcnt;
     if (cnt > pcap) FD_THROW(FD_ERR_DEVICE_CAPACITY, "%u positives exceed the device buffer", cnt);
-    std::vector<HogPos> raw(cnt);
-    if (cnt) HIP_CHECK(hipMemcpy(raw.data(), S.pos.p, sizeof(HogPos) * cnt, hipMemcpyDeviceToHost));
-    auto widof = [](const HogPos& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; };
-    std::sort(raw.begin(), raw.end(), [&](const HogPos& a, const HogPos& b) { return widof(a) < widof(b); });
+    std::vector<FdPosRec> raw(cnt);
+    if (cnt) HIP_CHECK(hipMemcpy(raw.data(), S.pos.p, sizeof(FdPosRec) * cnt, hipMemcpyDeviceToHost));
+    fd_pos_sort(raw.data(), cnt);
     *count = cnt;
-    for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i) {
-        fd_detection d;
-        std::memset(&d, 0, sizeof(d));
-        window_geometry(p, wls, sx, sy, (int64_t)widof(raw[i]), d);
-        d.level = -1;
-        d.positive = 1;
-        d.score = (float)raw[i].dist;
-        d.probability = fd_svm_probability(svm, raw[i].dist);
-        out[i] = d;
-    }
+    for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i)
+        out[i] = fd_pos_detection(p, wls, sx, sy, raw[i], -1, fd_svm_probability(svm, raw[i].d));
     if (out && (int64_t)cnt > cap) FD_THROW(FD_ERR_CAPACITY, "%u positives, capacity %lld", cnt, (long long)cap);
 }
 
@@ -1088,11 +1001,7 @@ int fd_hist_patch_batch(fd_ctx* ctx, const uint8_t* bin_patches, int64_t n, int 
         const size_t bytes = (size_t)n * hp->patch_w * hp->patch_h * channels;
         S.patchIn.reserve(bytes);
         HIP_CHECK(hipMemcpyAsync(S.patchIn.p, bin_patches, bytes, hipMemcpyHostToDevice, ctx->stream));
-        HogWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.n = 1; wt.sx = 1; wt.sy = hp->patch_h; wt.total = n;
-        wt.l[0].bx = 0; wt.l[0].by = 0; wt.l[0].nx = 1; wt.l[0].ny = (int32_t)n; wt.l[0].lw = hp->patch_w; wt.l[0].off = 0; wt.l[0].first = 0;
-        launch_hist_features(ctx, S.patchIn.as<uint8_t>(), wt, hd, S);
+        launch_hist_features(ctx, S.patchIn.as<uint8_t>(), fd_win_table_column(n, hp->patch_w, hp->patch_h), hd, S);
         HIP_CHECK(hipMemcpyAsync(out, S.feat.p, sizeof(float) * (size_t)n * hd.F, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });

@@ -44,7 +44,7 @@ struct HsfPlan {
 struct HsfOut {
     double* dist;          // every window's hyperplane distance (device)
     double* part;          // partial sums of the remainder round
-    HogPos* pos;           // pinned, host-mapped
+    FdPosRec* pos;         // pinned, host-mapped
     unsigned int* header;  // device: [0] positives so far, [1] retired workgroups of k_hsf_finish
     unsigned int cap;
     float threshold;
@@ -60,7 +60,7 @@ __device__ __forceinline__ void hsf_append(const HsfOut& o, bool positive, int64
     base = __shfl(base, __ffsll((long long)mask) - 1, 64);
     if (positive) {
         const unsigned int slot = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-        if (slot < o.cap) o.pos[1 + slot] = HogPos{(uint32_t)w, (uint32_t)(w >> 32), d};
+        if (slot < o.cap) o.pos[1 + slot] = FdPosRec{(uint32_t)w, (uint32_t)(w >> 32), d};
     }
 }
 
@@ -80,23 +80,15 @@ __host__ __device__ constexpr int hsf_off(int k) {
 }
 __host__ __device__ constexpr int hsf_block(int k) { return k / 36; }
 
-__device__ __forceinline__ void hsf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // HOG vectors of the 32 windows of `tile` -> B (this lane's 41 float4 fragment slots) and |x|^2 of window lane & 31
-__device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, const HogWinTable& wt, int64_t tile, float* hist,
+__device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, const FdWinTable& wt, int64_t tile, float* hist,
                                              hsf_f32x4 (&B)[HSF_Q], float& xxOut) {
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     int64_t wid = tile * 32 + r;
     wid = wid < wt.total ? wid : wt.total - 1;   // rows behind the last window repeat it (their results are never written)
-    int li = 0;
-    for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
-    const HogWinLayer wl = wt.l[li];
-    const int local = (int)(wid - wl.first);
-    const int iy = local / wl.nx, ix = local - iy * wl.nx;
-    const uint8_t* src = arena + wl.off + 2 * ((size_t)(wl.by + iy * wt.sy + 10 * h) * wl.lw + (wl.bx + ix * wt.sx));
+    int x0, y0;
+    const FdWinLayer wl = win_locate(wt, wid, x0, y0);
+    const uint8_t* src = arena + wl.off + 2 * ((size_t)(y0 + 10 * h) * wl.lw + x0);
     const size_t rowBytes = (size_t)wl.lw * 2;
     // the lane's ten pixel rows: 20 (bin, weight) pairs = 10 dwords each
     uint32_t px[10][10];
@@ -145,7 +137,7 @@ __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, 
             for (int c = 0; c < 8; ++c) *a[c] = v[c] + w[c];
         }
     }
-    hsf_wave_sync();
+    wave_sync();
     // cell energies (HogFilter.cpp:102-122, no signed / unsigned combination): own eight, the partner's eight through the crossbar
     float own[8], oth[8];
 #pragma unroll
@@ -209,13 +201,13 @@ __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, 
         sqd += ((double)nrm[bl] * (double)nrm[bl]) * e;
     }
     xxOut = (float)sqd;
-    hsf_wave_sync();
+    wave_sync();
 }
 
 // SUBS: groups the eight wavefronts prepare their tiles in (2: four at a time, 92 KB of LDS; 1: all at once, 157 KB; 0: no HOG at
 // all -- a timing experiment, results meaningless)
 template <int SUBS>
-__global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restrict__ arena, HogWinTable wt, HsfSvm m, HsfPlan plan, HsfOut out) {
+__global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restrict__ arena, FdWinTable wt, HsfSvm m, HsfPlan plan, HsfOut out) {
     extern __shared__ __attribute__((aligned(16))) float hsf_lds[];
     float* const buf0 = hsf_lds;
     float* const buf1 = hsf_lds + HSF_TILE_FLOATS;

@@ -22,13 +22,6 @@
 #include <algorithm>
 #include <cstring>
 
-// svm.hip
-float fd_svm_threshold(const fd_svm* m);
-int fd_svm_dim(const fd_svm* m);
-bool fd_svm_is_u8(const fd_svm* m);
-double fd_svm_probability(const fd_svm* m, double d);
-void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-
 struct fd_integral {
     fd_ctx* ctx = nullptr;
     int w = 0, h = 0;            // size of the source image; the integral image is (h + 1) x (w + 1)

@@ -16,27 +16,13 @@
 // which is applied on the fly (x = float(u8) * scale + shift, like cv::Mat::convertTo).
 #include "fd_internal.hpp"
 #include "fd_device.hpp"
+#include "win_table.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
 
-void fd_window_to_detection(const fd_pyramid* p, const std::vector<WindowLayer>& wls, int sx, int sy, int64_t wid, fd_detection& d);
-
-constexpr int RVM_MAX_LAYERS = 64;
 constexpr int RVM_DEEP_FROM = 16;    // levels from here on are evaluated 64 at a time per surviving window
 constexpr int RVM_MAX_DIM = 32;       // patch width/height limit of the window feature kernel
-
-struct RvmWinLayer {
-    int32_t bx, by, nx, ny;
-    int32_t lw;
-    uint32_t off;
-    int64_t first;
-};
-struct RvmWinTable {
-    int32_t n, sx, sy, pad;
-    int64_t total;
-    RvmWinLayer l[RVM_MAX_LAYERS];
-};
 
 struct RvmDev {
     int32_t kernel, dim, numFilters, numUse;
@@ -47,11 +33,6 @@ struct RvmDev {
     const float* svT;     // [dim][numFilters]: element i of every reduced set vector (lane == level reads are coalesced)
     const float* diag;    // [numFilters]: coefficients[k][k]
     const float* thr;     // [numFilters]
-};
-
-struct RvmRec {   // survivor between passes / positive record
-    uint32_t wid_lo, wid_hi;
-    double d;
 };
 
 struct fd_rvm {
@@ -80,7 +61,7 @@ __device__ __forceinline__ double powi_d(double base, int exponent) {  // Polyno
 }
 
 // u8 patch features of every window: gray (copy), HistEq64Filter, cv::equalizeHist.  One wave per window.
-__global__ __launch_bounds__(64) void k_window_patches(const uint8_t* __restrict__ arena, RvmWinTable wt, int pw, int ph, int mode,
+__global__ __launch_bounds__(64) void k_window_patches(const uint8_t* __restrict__ arena, FdWinTable wt, int pw, int ph, int mode,
                                                        uint8_t* __restrict__ out) {
     __shared__ unsigned char px[RVM_MAX_DIM * RVM_MAX_DIM];
     __shared__ unsigned char eq[RVM_MAX_DIM * RVM_MAX_DIM];
@@ -89,12 +70,9 @@ __global__ __launch_bounds__(64) void k_window_patches(const uint8_t* __restrict
     const int lane = threadIdx.x;
     const int n = pw * ph;
     for (int64_t wid = blockIdx.x; wid < wt.total; wid += gridDim.x) {
-        int li = 0;
-        for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
-        const RvmWinLayer& wl = wt.l[li];
-        const int local = (int)(wid - wl.first);
-        const int iy = local / wl.nx, ix = local - iy * wl.nx;
-        const uint8_t* src = arena + wl.off + (size_t)(wl.by + iy * wt.sy) * wl.lw + (wl.bx + ix * wt.sx);
+        int x0, y0;
+        const FdWinLayer& wl = win_locate(wt, wid, x0, y0);
+        const uint8_t* src = arena + wl.off + (size_t)y0 * wl.lw + x0;
         for (int i = lane; i < n; i += 64) {
             const int y = i / pw, x = i - y * pw;
             px[i] = src[(size_t)y * wl.lw + x];
@@ -173,10 +151,10 @@ __device__ __forceinline__ double rvm_kernel_value(const RvmDev& m, const void* 
 // One pass over the levels [k0, k1).  inq == NULL: the items are the windows 0..n0-1 (first pass).
 template <bool U8IN>
 __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restrict__ feats, int64_t rowBytes, float scale, float shift,
-                                                  int64_t n0, const RvmRec* __restrict__ inq, const unsigned int* __restrict__ in_count,
-                                                  int k0, int k1, RvmRec* __restrict__ outq, unsigned int* __restrict__ out_count,
+                                                  int64_t n0, const FdPosRec* __restrict__ inq, const unsigned int* __restrict__ in_count,
+                                                  int k0, int k1, FdPosRec* __restrict__ outq, unsigned int* __restrict__ out_count,
                                                   int32_t* __restrict__ all_level, double* __restrict__ all_dist,
-                                                  RvmRec* __restrict__ pos, unsigned int* __restrict__ pos_count, unsigned int pos_cap) {
+                                                  FdPosRec* __restrict__ pos, unsigned int* __restrict__ pos_count, unsigned int pos_cap) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int64_t n = inq ? (int64_t)*in_count : n0;
@@ -186,7 +164,7 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
         int64_t wid = item;
         double d = 0.0;
         if (alive && inq) {
-            wid = (int64_t)(((uint64_t)inq[item].wid_hi << 32) | inq[item].wid_lo);
+            wid = (int64_t)fd_pos_wid(inq[item]);
             d = inq[item].d;
         }
         const void* x = (const char*)feats + (size_t)(alive ? wid : 0) * rowBytes;
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
                     if (all_dist) all_dist[wid] = d;
                     if (k + 1 == m.numUse && d >= (double)thr) {         // classify, :68-73
                         const unsigned int slot = atomicAdd(pos_count, 1u);
-                        if (slot < pos_cap) pos[slot] = RvmRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
+                        if (slot < pos_cap) pos[slot] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
                     }
                     alive = false;
                 }
@@ -216,7 +194,7 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
             base = __builtin_amdgcn_readfirstlane(base);
             if (alive) {
                 const unsigned int idx = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-                outq[idx] = RvmRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
+                outq[idx] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
             }
         }
     }
@@ -229,9 +207,9 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
 // in level order and stops at the first missed threshold.
 template <bool U8IN>
 __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restrict__ feats, int64_t rowBytes, float scale, float shift,
-                                                  const RvmRec* __restrict__ inq, const unsigned int* __restrict__ in_count, int k0,
+                                                  const FdPosRec* __restrict__ inq, const unsigned int* __restrict__ in_count, int k0,
                                                   int32_t* __restrict__ all_level, double* __restrict__ all_dist,
-                                                  RvmRec* __restrict__ pos, unsigned int* __restrict__ pos_count, unsigned int pos_cap) {
+                                                  FdPosRec* __restrict__ pos, unsigned int* __restrict__ pos_count, unsigned int pos_cap) {
     __shared__ float xs[4][RVM_MAX_DIM * RVM_MAX_DIM];   // the window's vector, converted once
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -239,7 +217,7 @@ __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restri
     const int dim = m.dim, F = m.numFilters;
     float* x = xs[wave];
     for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < n; item += (int64_t)gridDim.x * 4) {
-        const int64_t wid = (int64_t)(((uint64_t)inq[item].wid_hi << 32) | inq[item].wid_lo);
+        const int64_t wid = (int64_t)fd_pos_wid(inq[item]);
         double d = inq[item].d;
         const char* row = (const char*)feats + (size_t)wid * rowBytes;
         for (int i = lane; i < dim; i += 64)
@@ -288,7 +266,7 @@ __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restri
                     if (all_dist) all_dist[wid] = mine;
                     if (level + 1 == m.numUse && mine >= (double)thr) {
                         const unsigned int slot = atomicAdd(pos_count, 1u);
-                        if (slot < pos_cap) pos[slot] = RvmRec{(uint32_t)wid, (uint32_t)(wid >> 32), mine};
+                        if (slot < pos_cap) pos[slot] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), mine};
                     }
                 }
             }
@@ -318,10 +296,10 @@ void run_cascade(fd_ctx* ctx, fd_rvm* m, const void* dfeats, int64_t rowBytes, f
     hipStream_t st = ctx->stream;
     int b[16];
     const int np = pass_bounds(m->dev.numUse, b);
-    m->q0.reserve(sizeof(RvmRec) * (size_t)n);
-    m->q1.reserve(sizeof(RvmRec) * (size_t)n);
+    m->q0.reserve(sizeof(FdPosRec) * (size_t)n);
+    m->q1.reserve(sizeof(FdPosRec) * (size_t)n);
     m->counters.reserve(256);
-    m->pos.reserve(sizeof(RvmRec) * (size_t)std::max<unsigned int>(pos_cap, 1));
+    m->pos.reserve(sizeof(FdPosRec) * (size_t)std::max<unsigned int>(pos_cap, 1));
     if (want_all) {
         m->level.reserve(sizeof(int32_t) * (size_t)n);
         m->dist.reserve(sizeof(double) * (size_t)n);
@@ -329,20 +307,20 @@ void run_cascade(fd_ctx* ctx, fd_rvm* m, const void* dfeats, int64_t rowBytes, f
     HIP_CHECK(hipMemsetAsync(m->counters.p, 0, 256, st));
     unsigned int* cnt = m->counters.as<unsigned int>();   // [0] positives, [1 + p] survivors of pass p
     for (int p = 0; p < np; ++p) {
-        const RvmRec* inq = p == 0 ? nullptr : (p % 2 ? m->q0.as<RvmRec>() : m->q1.as<RvmRec>());
-        RvmRec* outq = p % 2 ? m->q1.as<RvmRec>() : m->q0.as<RvmRec>();
+        const FdPosRec* inq = p == 0 ? nullptr : (p % 2 ? m->q0.as<FdPosRec>() : m->q1.as<FdPosRec>());
+        FdPosRec* outq = p % 2 ? m->q1.as<FdPosRec>() : m->q0.as<FdPosRec>();
         const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cus * 8);
         hipLaunchKernelGGL(k_rvm_pass<U8IN>, dim3(grid), dim3(256), 0, st, m->dev, dfeats, rowBytes, scale, shift, n, inq,
                            p == 0 ? nullptr : cnt + p, b[p], b[p + 1], outq, cnt + 1 + p, want_all ? m->level.as<int32_t>() : nullptr,
-                           want_all ? m->dist.as<double>() : nullptr, m->pos.as<RvmRec>(), cnt, pos_cap);
+                           want_all ? m->dist.as<double>() : nullptr, m->pos.as<FdPosRec>(), cnt, pos_cap);
         HIP_CHECK(hipGetLastError());
     }
     if (m->dev.numUse > b[np]) {
         if (m->dev.dim > RVM_MAX_DIM * RVM_MAX_DIM) FD_THROW(FD_ERR_INVALID_ARGUMENT, "RvmClassifier: vectors longer than %d are not supported", RVM_MAX_DIM * RVM_MAX_DIM);
-        const RvmRec* inq = np % 2 ? m->q0.as<RvmRec>() : m->q1.as<RvmRec>();
+        const FdPosRec* inq = np % 2 ? m->q0.as<FdPosRec>() : m->q1.as<FdPosRec>();
         const int grid = (int)std::min<int64_t>((n + 3) / 4, (int64_t)ctx->num_cus * 8);
         hipLaunchKernelGGL(k_rvm_deep<U8IN>, dim3(grid), dim3(256), 0, st, m->dev, dfeats, rowBytes, scale, shift, inq, cnt + np, b[np],
-                           want_all ? m->level.as<int32_t>() : nullptr, want_all ? m->dist.as<double>() : nullptr, m->pos.as<RvmRec>(), cnt,
+                           want_all ? m->level.as<int32_t>() : nullptr, want_all ? m->dist.as<double>() : nullptr, m->pos.as<FdPosRec>(), cnt,
                            pos_cap);
         HIP_CHECK(hipGetLastError());
     }
@@ -359,7 +337,7 @@ void rvm_scan_check(fd_ctx* ctx, const fd_pyramid* p, const fd_rvm* m, const fd_
     if (p->ctx != ctx || m->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
     if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "RVM detection needs a gray pyramid (no layer filter)");
     fd_pyramid_require_single(p, who);
-    if (needImage && p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+    if (needImage) fd_pyramid_require_image(p);
     if (dp->feature_space < FD_FEATURE_GRAY || dp->feature_space > FD_FEATURE_HISTEQ)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "unknown feature space %d", dp->feature_space);
     if (m->filter_w > RVM_MAX_DIM || m->filter_h > RVM_MAX_DIM) FD_THROW(FD_ERR_INVALID_ARGUMENT, "patch size must be within %d x %d", RVM_MAX_DIM, RVM_MAX_DIM);
@@ -369,19 +347,10 @@ void rvm_scan_check(fd_ctx* ctx, const fd_pyramid* p, const fd_rvm* m, const fd_
 bool rvm_scan_windows(fd_ctx* ctx, fd_pyramid* p, fd_rvm* m, const fd_rvm_detect_params* dp, const int* roi, RvmScan& sc) {
     const int pw = m->filter_w, ph = m->filter_h, dim = pw * ph;
     HIP_CHECK(hipSetDevice(ctx->device));
-    fd_enumerate_layers(p, pw, ph, dp->step_x, dp->step_y, roi, sc.wls, sc.total);
-    const int64_t total = sc.total;
+    FdWinTable wt;
+    fd_win_table_build(p, pw, ph, dp->step_x, dp->step_y, roi, /*filtered=*/false, wt, sc.wls);
+    const int64_t total = sc.total = wt.total;
     if (total == 0) return false;
-    if (sc.wls.size() > (size_t)RVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", sc.wls.size());
-    RvmWinTable wt;
-    std::memset(&wt, 0, sizeof(wt));
-    wt.sx = dp->step_x; wt.sy = dp->step_y; wt.total = total;
-    for (const WindowLayer& w : sc.wls) {
-        if (w.nx == 0 || w.ny == 0) continue;
-        const HostLayer& L = p->all[p->kept[w.layer]];
-        RvmWinLayer& dl = wt.l[wt.n++];
-        dl.bx = w.bx; dl.by = w.by; dl.nx = w.nx; dl.ny = w.ny; dl.lw = L.w; dl.off = L.gray_off; dl.first = w.first;
-    }
     m->feats.reserve((size_t)total * dim + 16);
     hipLaunchKernelGGL(k_window_patches, dim3((unsigned)std::min<int64_t>(total, (int64_t)ctx->num_cus * 32)), dim3(64), 0, ctx->stream,
                        p->arena.as<uint8_t>(), wt, pw, ph, dp->feature_space, m->feats.as<uint8_t>());
@@ -394,18 +363,10 @@ void rvm_scan_cascade(fd_ctx* ctx, fd_rvm* m, const fd_rvm_detect_params* dp, co
     run_cascade<true>(ctx, m, m->feats.p, (int64_t)m->dev.dim, dp->conv_scale, dp->conv_shift, sc.total, want_all, sc.pos_cap);
 }
 
-inline uint64_t rvm_wid(const RvmRec& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; }
-
 // a positive record -> the ClassifiedPatch of SlidingWindowDetector::detect
-fd_detection rvm_detection(const fd_pyramid* p, const fd_rvm* m, const std::vector<WindowLayer>& wls, const fd_rvm_detect_params* dp, const RvmRec& r) {
-    fd_detection d;
-    std::memset(&d, 0, sizeof(d));
-    fd_window_to_detection(p, wls, dp->step_x, dp->step_y, (int64_t)rvm_wid(r), d);
-    d.level = m->dev.numUse - 1;
-    d.positive = 1;
-    d.score = (float)r.d;
-    d.probability = 1.0f / (1.0f + std::exp(m->logisticA + m->logisticB * r.d));   // ProbabilisticRvmClassifier.cpp:62
-    return d;
+fd_detection rvm_detection(const fd_pyramid* p, const fd_rvm* m, const std::vector<WindowLayer>& wls, const fd_rvm_detect_params* dp, const FdPosRec& r) {
+    return fd_pos_detection(p, wls, dp->step_x, dp->step_y, r, m->dev.numUse - 1,
+                            1.0f / (1.0f + std::exp(m->logisticA + m->logisticB * r.d)));   // ProbabilisticRvmClassifier.cpp:62
 }
 
 }  // namespace
@@ -492,9 +453,9 @@ int fd_detect_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* rvm_, const fd_rvm_d
         HIP_CHECK(hipStreamSynchronize(st));
         const unsigned int cnt = *hcnt;
         if (cnt > pos_cap) FD_THROW(FD_ERR_DEVICE_CAPACITY, "fd_detect_rvm: %u positives exceed the device buffer", cnt);
-        std::vector<RvmRec> raw(cnt);
-        if (cnt) HIP_CHECK(hipMemcpy(raw.data(), m->pos.p, sizeof(RvmRec) * cnt, hipMemcpyDeviceToHost));
-        std::sort(raw.begin(), raw.end(), [](const RvmRec& a, const RvmRec& b) { return rvm_wid(a) < rvm_wid(b); });
+        std::vector<FdPosRec> raw(cnt);
+        if (cnt) HIP_CHECK(hipMemcpy(raw.data(), m->pos.p, sizeof(FdPosRec) * cnt, hipMemcpyDeviceToHost));
+        fd_pos_sort(raw.data(), cnt);
         *count = cnt;
         for (unsigned int i = 0; i < cnt && out && (int64_t)i < cap; ++i) out[i] = rvm_detection(p, m, wls, dp, raw[i]);
         if (out && (int64_t)cnt > cap) FD_THROW(FD_ERR_CAPACITY, "fd_detect_rvm: %u positives, capacity %lld", cnt, (long long)cap);

@@ -17,13 +17,6 @@
 #pragma once
 #include "five_stage_stages.hpp"
 
-float fd_svm_threshold(const fd_svm* m);
-int fd_svm_dim(const fd_svm* m);
-bool fd_svm_is_u8(const fd_svm* m);
-void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-void fd_svm_f32_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, int64_t stride_bytes, int64_t nmax, const unsigned int* dcount,
-                               double* dout);
-
 namespace {
 
 constexpr int RVM_FS_SPEC_CAP = 4096;   // rows the one-wait order's launches cover
@@ -38,9 +31,9 @@ constexpr int RVM_FS_SPEC_CAP = 4096;   // rows the one-wait order's launches co
 // as the WVM path's tail does: the host reads them after the stream's wait.
 static_assert((RVM_MAX_DIM * RVM_MAX_DIM + 8) % 4 == 0, "k_rvm_rows_f32: every wavefront's LDS slab must start dword-aligned");
 __global__ __launch_bounds__(256) void k_rvm_rows_f32(const uint8_t* __restrict__ feats, int dim, float scale, float shift,
-                                                      const RvmRec* __restrict__ recs, const uint32_t* __restrict__ wids,
+                                                      const FdPosRec* __restrict__ recs, const uint32_t* __restrict__ wids,
                                                       const unsigned int* __restrict__ dcount, unsigned int n, float* __restrict__ rows,
-                                                      RvmRec* __restrict__ recs_out) {
+                                                      FdPosRec* __restrict__ recs_out) {
     __shared__ __attribute__((aligned(16))) unsigned char stage[4][RVM_MAX_DIM * RVM_MAX_DIM + 8];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -50,8 +43,8 @@ __global__ __launch_bounds__(256) void k_rvm_rows_f32(const uint8_t* __restrict_
     if (row >= cnt) return;   // (no workgroup barrier below: the wavefronts of a workgroup are independent)
     uint64_t wid;
     if (recs) {
-        const RvmRec r = recs[row];
-        wid = ((uint64_t)r.wid_hi << 32) | r.wid_lo;
+        const FdPosRec r = recs[row];
+        wid = fd_pos_wid(r);
         if (recs_out && lane == 0) recs_out[row] = r;
     } else {
         wid = wids[row];
@@ -74,8 +67,8 @@ __global__ __launch_bounds__(256) void k_rvm_rows_f32(const uint8_t* __restrict_
     for (int i = lane; i < dim; i += 64) o[i] = (float)s[head + i] * scale + shift;   // cv::Mat::convertTo(CV_32F, scale, shift)
 }
 
-void rvm_rows_launch(hipStream_t st, const fd_rvm* m, const fd_rvm_detect_params* dp, const RvmRec* recs, const uint32_t* wids,
-                     const unsigned int* dcount, unsigned int n, float* rows, RvmRec* recs_out) {
+void rvm_rows_launch(hipStream_t st, const fd_rvm* m, const fd_rvm_detect_params* dp, const FdPosRec* recs, const uint32_t* wids,
+                     const unsigned int* dcount, unsigned int n, float* rows, FdPosRec* recs_out) {
     hipLaunchKernelGGL(k_rvm_rows_f32, dim3((n + 3) / 4), dim3(256), 0, st, m->feats.as<uint8_t>(), m->dev.dim, dp->conv_scale, dp->conv_shift, recs,
                        wids, dcount, n, rows, recs_out);
     HIP_CHECK(hipGetLastError());
@@ -120,7 +113,7 @@ void rvm_five_stage(fd_ctx* ctx, fd_pyramid* p, fd_rvm* m, const fd_rvm_detect_p
     // pinned staging: [count (64 bytes) | records | distances | levels]
     auto layout = [&](size_t n, bool withRecs, size_t& recOff, size_t& distOff, size_t& levelOff) {
         recOff = 64;
-        distOff = recOff + (withRecs ? sizeof(RvmRec) * n : ((sizeof(uint32_t) * n + 15) & ~(size_t)15));
+        distOff = recOff + (withRecs ? sizeof(FdPosRec) * n : ((sizeof(uint32_t) * n + 15) & ~(size_t)15));
         levelOff = distOff + sizeof(double) * n;
         return levelOff + sizeof(int32_t) * n;
     };
@@ -131,19 +124,19 @@ void rvm_five_stage(fd_ctx* ctx, fd_pyramid* p, fd_rvm* m, const fd_rvm_detect_p
     HIP_CHECK(hipMemcpyAsync(hb, dcnt, 4, hipMemcpyDeviceToHost, st));
     if (spec) {   // the SVM on every positive, by record slot, straight behind the cascade
         m->rows.reserve((size_t)RVM_FS_SPEC_CAP * rowBytes);
-        rvm_rows_launch(st, m, dp, m->pos.as<RvmRec>(), nullptr, dcnt, RVM_FS_SPEC_CAP, m->rows.as<float>(), reinterpret_cast<RvmRec*>(hb + recOff));
+        rvm_rows_launch(st, m, dp, m->pos.as<FdPosRec>(), nullptr, dcnt, RVM_FS_SPEC_CAP, m->rows.as<float>(), reinterpret_cast<FdPosRec*>(hb + recOff));
         fd_svm_f32_launch_counted(st, svm, m->rows.p, rowBytes, RVM_FS_SPEC_CAP, dcnt, reinterpret_cast<double*>(hb + distOff));
     }
     HIP_CHECK(hipStreamSynchronize(st));
     const unsigned int cnt = *reinterpret_cast<const unsigned int*>(hb);
     if (cnt > sc.pos_cap) FD_THROW(FD_ERR_DEVICE_CAPACITY, "five-stage (RVM): %u positives exceed the device buffer", cnt);
     const bool scored = spec && cnt <= (unsigned int)RVM_FS_SPEC_CAP;
-    std::vector<RvmRec> raw(cnt);
-    if (scored) std::memcpy(raw.data(), hb + recOff, sizeof(RvmRec) * cnt);
-    else if (cnt) HIP_CHECK(hipMemcpy(raw.data(), m->pos.p, sizeof(RvmRec) * cnt, hipMemcpyDeviceToHost));
+    std::vector<FdPosRec> raw(cnt);
+    if (scored) std::memcpy(raw.data(), hb + recOff, sizeof(FdPosRec) * cnt);
+    else if (cnt) HIP_CHECK(hipMemcpy(raw.data(), m->pos.p, sizeof(FdPosRec) * cnt, hipMemcpyDeviceToHost));
     std::vector<uint32_t> order(cnt);   // record slots in window order, as fd_detect_rvm returns its positives
     for (unsigned int i = 0; i < cnt; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rvm_wid(raw[a]) < rvm_wid(raw[b]); });
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return fd_pos_before(raw[a], raw[b]); });
     std::vector<fd_detection> dets(cnt);
     for (unsigned int i = 0; i < cnt; ++i) dets[i] = rvm_detection(p, m, sc.wls, dp, raw[order[i]]);
     if (stage_counts) stage_counts[0] = (int)cnt;
@@ -165,7 +158,7 @@ void rvm_five_stage(fd_ctx* ctx, fd_pyramid* p, fd_rvm* m, const fd_rvm_detect_p
         m->h_fs.reserve(layout(n, false, recOff, distOff, levelOff));
         hb = m->h_fs.as<char>();
         uint32_t* wids = reinterpret_cast<uint32_t*>(hb + recOff);
-        for (size_t i = 0; i < n; ++i) wids[i] = (uint32_t)rvm_wid(raw[order[(size_t)keep[i]]]);
+        for (size_t i = 0; i < n; ++i) wids[i] = (uint32_t)fd_pos_wid(raw[order[(size_t)keep[i]]]);
         m->rows.reserve(n * (size_t)rowBytes);
         rvm_rows_launch(st, m, dp, nullptr, wids, nullptr, (unsigned int)n, m->rows.as<float>(), nullptr);
         const double* dist = reinterpret_cast<const double*>(hb + distOff);

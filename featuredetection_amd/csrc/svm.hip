@@ -685,8 +685,6 @@ void fd_svm_rbf_mfma_launch(fd_ctx* ctx, const fd_svm* m, const float* xFrag, co
     svm_rbf_mfma_launch_variant(ctx, m, xFrag, xx, npatches, out, variant);
 }
 
-bool fd_svm_u8_mfma_available(const fd_svm* m);
-
 // ---- one launch function per kernel body: the launchers below and the test hook (fd_debug_svm_launch) share the geometry and the checks
 static size_t svm_u8_mfma_lds_bytes(const fd_svm* m) {   // 32 patches + one partial sum per (tile of 32 support vectors, patch)
     return (size_t)32 * (m->dev.KS * 32 + 16) + 384 + sizeof(double) * (size_t)(m->dev.nsv32 >> 5) * 32;
@@ -724,8 +722,6 @@ static void svm_launch_generic(hipStream_t st, const fd_svm* m, const void* dfea
 }
 
 // generic scoring of n device-resident feature vectors (optionally gathered by slot index)
-void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes,
-                              int64_t n, double* dout);
 void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes,
                            int64_t n, double* dout) {
     fd_svm_generic_launch_on(ctx->stream, m, dfeat, didx, stride_bytes, n, dout);

@@ -11,33 +11,14 @@
 // is the patch read (L2 hits for overlapping windows) and the 4*w*h-byte feature write.
 #include "fd_internal.hpp"
 #include "fd_device.hpp"
+#include "win_table.hpp"
 #include <algorithm>
 #include <complex>
 #include <cstring>
 #include <memory>
 
-struct fd_svm;
-float fd_svm_threshold(const fd_svm* m);
-int fd_svm_dim(const fd_svm* m);
-bool fd_svm_is_u8(const fd_svm* m);
-void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_svm* svm, const std::vector<WindowLayer>& wls, int sx, int sy,
-                                    const double* ddist, int64_t N, fd_detection* out, int64_t cap, int64_t* count, double* all_distance);
-
-constexpr int WHI_MAX_LAYERS = 64;
 constexpr int WHI_MAX_DIM = 32;
 
-struct WhiWinLayer {
-    int32_t bx, by, nx, ny;
-    int32_t lw;
-    uint32_t off;
-    int64_t first;
-};
-struct WhiWinTable {
-    int32_t n, sx, sy, raw;   // raw != 0: `total` contiguous w x h patches
-    int64_t total;
-    WhiWinLayer l[WHI_MAX_LAYERS];
-};
 struct WhiDev {
     int32_t w, h;
     const double* twRow;   // [w][w] (re, im) = polar(1, -2 pi x k / w)
@@ -49,24 +30,21 @@ namespace {
 
 using namespace fd_dev;
 
-__device__ __forceinline__ const uint8_t* locate(const uint8_t* arena, const WhiWinTable& wt, int64_t wid, int w, int h, int& stride) {
+__device__ __forceinline__ const uint8_t* locate(const uint8_t* arena, const FdWinTable& wt, int64_t wid, int w, int h, int& stride) {
     if (wt.raw) {
         stride = w;
         return arena + (size_t)wid * w * h;
     }
-    int li = 0;
-    for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
-    const WhiWinLayer& wl = wt.l[li];
-    const int local = (int)(wid - wl.first);
-    const int iy = local / wl.nx, ix = local - iy * wl.nx;
+    int x0, y0;
+    const FdWinLayer& wl = win_locate(wt, wid, x0, y0);
     stride = wl.lw;
-    return arena + wl.off + (size_t)(wl.by + iy * wt.sy) * wl.lw + (wl.bx + ix * wt.sx);
+    return arena + wl.off + (size_t)y0 * wl.lw + x0;
 }
 
 // EQ_ONLY: HistogramEqualizationFilter alone, u8 output
 // MODE 0: the whole whi chain -> unit-norm floats; 1: cv::equalizeHist only -> u8; 2: WhiteningFilter only -> u8
 template <int MODE>
-__global__ __launch_bounds__(64) void k_whi(const uint8_t* __restrict__ arena, WhiWinTable wt, WhiDev d, float* __restrict__ feat,
+__global__ __launch_bounds__(64) void k_whi(const uint8_t* __restrict__ arena, FdWinTable wt, WhiDev d, float* __restrict__ feat,
                                             uint8_t* __restrict__ eqOut) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -237,7 +215,7 @@ size_t lds_bytes(int w, int h) {
 }
 
 template <int MODE>
-void launch(fd_ctx* ctx, const uint8_t* arena, const WhiWinTable& wt, const WhiDev& d, float* feat, uint8_t* eqOut) {
+void launch(fd_ctx* ctx, const uint8_t* arena, const FdWinTable& wt, const WhiDev& d, float* feat, uint8_t* eqOut) {
     const size_t lds = lds_bytes(d.w, d.h);
     static uint64_t lds_allowed = 0;   // per instantiation
     fd_allow_lds(ctx, (const void*)k_whi<MODE>, 64 * 1024, lds_allowed);
@@ -267,21 +245,10 @@ __global__ __launch_bounds__(64) void k_unit_norm(const float* __restrict__ src,
     for (int64_t im = blockIdx.x; im < nimg; im += gridDim.x) unit_norm_wave(src + (size_t)im * len, dst + (size_t)im * len, len, normType, lane);
 }
 
-void build_table(const fd_pyramid* p, const fd_whi_params* wp, WhiWinTable& wt, std::vector<WindowLayer>& wls) {
+void build_table(const fd_pyramid* p, const fd_whi_params* wp, FdWinTable& wt, std::vector<WindowLayer>& wls) {
     if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "the whi chain needs a gray pyramid (no layer filter)");
     fd_pyramid_require_single(p, "the whi chain");
-    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
-    int64_t total;
-    fd_enumerate_layers(p, wp->patch_w, wp->patch_h, wp->step_x, wp->step_y, nullptr, wls, total);
-    if (wls.size() > (size_t)WHI_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", wls.size());
-    std::memset(&wt, 0, sizeof(wt));
-    wt.sx = wp->step_x; wt.sy = wp->step_y; wt.total = total;
-    for (const WindowLayer& w : wls) {
-        if (w.nx == 0 || w.ny == 0) continue;
-        const HostLayer& L = p->all[p->kept[w.layer]];
-        WhiWinLayer& dl = wt.l[wt.n++];
-        dl.bx = w.bx; dl.by = w.by; dl.nx = w.nx; dl.ny = w.ny; dl.lw = L.w; dl.off = L.gray_off; dl.first = w.first;
-    }
+    fd_win_table_build(p, wp->patch_w, wp->patch_h, wp->step_x, wp->step_y, nullptr, /*filtered=*/false, wt, wls);
 }
 
 // whi features of every window into S.feat ([N][w*h] floats); returns N
@@ -289,12 +256,23 @@ int64_t run_whi(fd_ctx* ctx, fd_pyramid* p, const fd_whi_params* wp, std::vector
     if (p->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
     HIP_CHECK(hipSetDevice(ctx->device));
     const WhiDev& d = tables(ctx, S, wp->patch_w, wp->patch_h, wp->alpha, wp->cutoff);
-    WhiWinTable wt;
+    FdWinTable wt;
     build_table(p, wp, wt, wls);
     if (wt.total == 0) return 0;
     S.feat.reserve(sizeof(float) * (size_t)wt.total * d.w * d.h);
     launch<0>(ctx, p->arena.as<uint8_t>(), wt, d, S.feat.as<float>(), nullptr);
     return wt.total;
+}
+
+// a per-Mat patch call: src (host) -> S.in, the kernel that `queue` puts on the stream (S.in -> S.feat), S.feat -> dst (host), the wait
+template <class Q>
+void patch_call(fd_ctx* ctx, WhiScratch& S, const void* src, size_t inBytes, void* dst, size_t outBytes, Q&& queue) {
+    S.in.reserve(inBytes);
+    S.feat.reserve(outBytes);
+    HIP_CHECK(hipMemcpyAsync(S.in.p, src, inBytes, hipMemcpyHostToDevice, ctx->stream));
+    queue();
+    HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
 }
 
 }  // namespace
@@ -309,16 +287,8 @@ int fd_whi_batch(fd_ctx* ctx, const uint8_t* patches, int64_t n, int w, int h, f
         WhiScratch& S = scratch(ctx);
         const WhiDev& d = tables(ctx, S, w, h, alpha, cutoff);
         const size_t bytes = (size_t)n * w * h;
-        S.in.reserve(bytes);
-        S.feat.reserve(bytes * sizeof(float));
-        HIP_CHECK(hipMemcpyAsync(S.in.p, patches, bytes, hipMemcpyHostToDevice, ctx->stream));
-        WhiWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.raw = 1;
-        wt.total = n;
-        launch<0>(ctx, S.in.as<uint8_t>(), wt, d, S.feat.as<float>(), nullptr);
-        HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, bytes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        patch_call(ctx, S, patches, bytes, dst, bytes * sizeof(float),
+                   [&] { launch<0>(ctx, S.in.as<uint8_t>(), fd_win_table_raw(n), d, S.feat.as<float>(), nullptr); });
     });
 }
 
@@ -330,19 +300,10 @@ int fd_equalize_hist_batch(fd_ctx* ctx, const uint8_t* patches, int64_t n, int w
         HIP_CHECK(hipSetDevice(ctx->device));
         WhiScratch& S = scratch(ctx);
         const size_t bytes = (size_t)n * w * h;
-        S.in.reserve(bytes);
-        S.feat.reserve(bytes);
-        HIP_CHECK(hipMemcpyAsync(S.in.p, patches, bytes, hipMemcpyHostToDevice, ctx->stream));
-        WhiWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.raw = 1;
-        wt.total = n;
         WhiDev d;
         std::memset(&d, 0, sizeof(d));
         d.w = w; d.h = h;
-        launch<1>(ctx, S.in.as<uint8_t>(), wt, d, nullptr, S.feat.as<uint8_t>());
-        HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        patch_call(ctx, S, patches, bytes, dst, bytes, [&] { launch<1>(ctx, S.in.as<uint8_t>(), fd_win_table_raw(n), d, nullptr, S.feat.as<uint8_t>()); });
     });
 }
 
@@ -355,16 +316,7 @@ int fd_whitening_batch(fd_ctx* ctx, const uint8_t* patches, int64_t n, int w, in
         WhiScratch& S = scratch(ctx);
         const WhiDev& d = tables(ctx, S, w, h, alpha, cutoff);
         const size_t bytes = (size_t)n * w * h;
-        S.in.reserve(bytes);
-        S.feat.reserve(bytes);
-        HIP_CHECK(hipMemcpyAsync(S.in.p, patches, bytes, hipMemcpyHostToDevice, ctx->stream));
-        WhiWinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.raw = 1;
-        wt.total = n;
-        launch<2>(ctx, S.in.as<uint8_t>(), wt, d, nullptr, S.feat.as<uint8_t>());
-        HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        patch_call(ctx, S, patches, bytes, dst, bytes, [&] { launch<2>(ctx, S.in.as<uint8_t>(), fd_win_table_raw(n), d, nullptr, S.feat.as<uint8_t>()); });
     });
 }
 
@@ -377,14 +329,11 @@ int fd_convert_batch(fd_ctx* ctx, const void* src, int src_dtype, int64_t count,
         HIP_CHECK(hipSetDevice(ctx->device));
         WhiScratch& S = scratch(ctx);
         const size_t sb = (size_t)count * (src_dtype == FD_DTYPE_F32 ? 4 : 1), db = (size_t)count * (dst_dtype == FD_DTYPE_F32 ? 4 : 1);
-        S.in.reserve(sb);
-        S.feat.reserve(db);
-        HIP_CHECK(hipMemcpyAsync(S.in.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_convert, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, ctx->stream, S.in.p,
-                           src_dtype == FD_DTYPE_F32, S.feat.p, dst_dtype == FD_DTYPE_F32, count, alpha, beta);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, db, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        patch_call(ctx, S, src, sb, dst, db, [&] {
+            hipLaunchKernelGGL(k_convert, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, ctx->stream, S.in.p,
+                               src_dtype == FD_DTYPE_F32, S.feat.p, dst_dtype == FD_DTYPE_F32, count, alpha, beta);
+            HIP_CHECK(hipGetLastError());
+        });
     });
 }
 
@@ -396,13 +345,10 @@ int fd_unit_norm_batch(fd_ctx* ctx, const float* src, int64_t n, int len, int no
         HIP_CHECK(hipSetDevice(ctx->device));
         WhiScratch& S = scratch(ctx);
         const size_t bytes = sizeof(float) * (size_t)n * len;
-        S.in.reserve(bytes);
-        S.feat.reserve(bytes);
-        HIP_CHECK(hipMemcpyAsync(S.in.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_unit_norm, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(64), 0, ctx->stream, S.in.as<float>(), S.feat.as<float>(), n, len, norm_type);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(dst, S.feat.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        patch_call(ctx, S, src, bytes, dst, bytes, [&] {
+            hipLaunchKernelGGL(k_unit_norm, dim3((unsigned)std::min<int64_t>(n, 65535)), dim3(64), 0, ctx->stream, S.in.as<float>(), S.feat.as<float>(), n, len, norm_type);
+            HIP_CHECK(hipGetLastError());
+        });
     });
 }
 

@@ -26,19 +26,6 @@
 #include <mutex>
 #include <atomic>
 
-
-// from svm.hip
-struct fd_svm;
-int fd_svm_dim(const fd_svm* m);
-bool fd_svm_is_u8(const fd_svm* m);
-float fd_svm_threshold(const fd_svm* m);
-double fd_svm_probability(const fd_svm* m, double d);
-void fd_svm_generic_launch(fd_ctx* ctx, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-void fd_svm_generic_launch_on(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t n, double* dout);
-bool fd_svm_u8_mfma_available(const fd_svm* m);
-void fd_svm_u8_mfma_launch_counted(hipStream_t st, const fd_svm* m, const void* dfeat, const uint32_t* didx, int64_t stride_bytes, int64_t nmax,
-                                   const unsigned int* dcount, double* dout);
-
 constexpr int WVM_MAX_LAYERS = 64;
 constexpr int WVM_MAX_DIM = 32;      // patch width/height limit of this kernel
 constexpr int WVM_MAX_VALS = 16;     // grey values per filter
@@ -1601,7 +1588,7 @@ void fd_wvm_launch_on(fd_ctx* ctx, hipStream_t st, fd_pyramid* p, fd_wvm* m, int
     if (p->ctx != ctx || m->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
     if (p->filter_kind != FD_LAYER_NONE)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "WVM detection needs a gray pyramid (no layer filter)");
-    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+    fd_pyramid_require_image(p);
     HIP_CHECK(hipSetDevice(ctx->device));
     fd_pyramid_wait(p, st);   // the batch entry points launch on pool streams, the caller may have updated on the context's
     WinTable wt;
@@ -1756,7 +1743,7 @@ void fd_wvm_launch_group(fd_ctx* ctx, const hipStream_t* sts, fd_pyramid* p, fd_
     for (int i = 0; i < n; ++i)
         if (p->ctx != ctx || ms[i]->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
     if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "WVM detection needs a gray pyramid (no layer filter)");
-    if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+    fd_pyramid_require_image(p);
     HIP_CHECK(hipSetDevice(ctx->device));
     fd_pyramid_wait(p, sts[0]);
     WinTable wt;
@@ -2152,7 +2139,7 @@ int fd_wvm_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, 
         five_stage_check(m, svm);
         if (p->ctx != ctx || m->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "objects belong to different contexts");
         if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "WVM evaluation needs a gray pyramid (no layer filter)");
-        if (p->all.empty()) FD_THROW(FD_ERR_RUNTIME, "pyramid has not been updated with an image");
+        fd_pyramid_require_image(p);
         if (p->kept.size() > (size_t)WVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "pyramid has %zu layers, this backend supports %d", p->kept.size(), WVM_MAX_LAYERS);
         HIP_CHECK(hipSetDevice(ctx->device));
         const int pw = m->dev.fw, ph = m->dev.fh;

@@ -800,6 +800,54 @@ def test_hog_svm_fused_kernel_equals_the_two_kernel_path(oracle, capi, ctx, synt
     sg.close(); pg.close()
 
 
+def test_every_window_of_every_scan_family_lands_where_the_oracle_enumerates_it(oracle, capi, ctx, synth, monkeypatch):
+    """The numbering rule the window-scan families share (windows layer by layer in extraction order, a layer without windows
+    shares its successor's first index, a tile's tail repeats the last window), for EVERY window: with thresholds no window can
+    miss, the detections of the HOG (fused and two-kernel), histogram, whi and RVM detectors are the oracle's window list, row by
+    row.  96 x 72 at two layers per octave: layers 96x72, 68x51, 48x36, 34x26, 24x18 hold 988 / 384 / 112 / 21 / 0 windows of
+    20 x 20 at step 2 -- a trailing empty layer, and 32-window tiles that straddle every layer boundary (988 % 32 = 28); the RVM
+    with a roi sees 50 / 4 / 0 / 0 / 0."""
+    frame = synth.make_frame(96, 72, seed=11)
+    kw = dict(octave_layers=2, min_scale=0.25, max_scale=1.0)
+    po, pg = _pyr_pair(oracle, capi, ctx, frame, **kw)
+    assert [(L["w"], L["h"]) for L in po.layers()] == [(96, 72), (68, 51), (48, 36), (34, 26), (24, 18)]
+    wins = po.windows(20, 20, 2, 2)
+    assert np.bincount(wins[:, 0], minlength=5).tolist() == [988, 384, 112, 21, 0]
+    pb = capi.Pyramid(ctx, **kw)   # the gradient-bin pyramid of the HOG and histogram runs
+    pb.set_layer_filter(capi.FD_LAYER_GRADBIN, bins=9)
+    pb.update(frame)
+
+    def rows(dets):   # the oracle's columns
+        return np.stack([dets[f] for f in ("layer", "lx", "ly", "cx", "cy", "w", "h")], 1).astype(np.int32)
+
+    def same(dets, expect):
+        assert len(dets) == len(expect)
+        assert np.array_equal(rows(dets), expect)
+
+    rng = np.random.default_rng(17)
+
+    def svm_all_positive(dim):   # an RBF distance is bounded by sum|coeff| + |bias|: -1e30 lies below every one
+        return capi.Svm(ctx, dict(kernel=2, dtype=1, sv=rng.random((64, dim)).astype(np.float32), coeff=rng.normal(0, 1, 64).astype(np.float32),
+                                  bias=np.float32(0.1), p0=0.5, p1=0.0, p2=0.0, threshold=-1e30, logistic_a=0.0, logistic_b=-1.0))
+
+    s324, s400 = svm_all_positive(324), svm_all_positive(400)
+    same(capi.detect_hog_svm(ctx, pb, s324, capi.hog_params())[0], wins)            # the fused 20/5/2/9 shape
+    monkeypatch.setenv("FD_HOG_FUSED", "0")
+    same(capi.detect_hog_svm(ctx, pb, s324, capi.hog_params())[0], wins)            # k_hog_tile + the selection kernel
+    monkeypatch.delenv("FD_HOG_FUSED")
+    same(capi.detect_hist_svm(ctx, pb, s324, capi.hist_params(kind=0, block=2))[0], wins)
+    same(capi.detect_whi_svm(ctx, pg, s400, capi.whi_params())[0], wins)
+    m = synth.make_rvm(3, rng.integers(0, 256, (64, 400)).astype(np.float32), 20, 20, n_filters=20)   # 20 levels: the passes and the deep kernel
+    m["thresholds"][:] = -1e30
+    rg = capi.Rvm(ctx, m)
+    same(capi.detect_rvm(ctx, pg, rg, sx=2, sy=2)[0], wins)
+    roi = (30, 20, 40, 30)
+    wroi = po.windows(20, 20, 2, 2, roi)
+    assert np.bincount(wroi[:, 0], minlength=5).tolist() == [50, 4, 0, 0, 0]
+    same(capi.detect_rvm(ctx, pg, rg, sx=2, sy=2, roi=roi)[0], wroi)
+    rg.close(); s324.close(); s400.close(); pb.close(); pg.close(); po.close()
+
+
 def test_sdm_descriptors_bit_exact(oracle, capi, ctx, synth):
     gray = synth.make_frame(256, 256, seed=21, channels=1)
     rng = np.random.default_rng(1)
