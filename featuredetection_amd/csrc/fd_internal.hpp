@@ -451,14 +451,13 @@ void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, co
 void fd_window_to_detection(const fd_pyramid* p, const std::vector<WindowLayer>& wls, int sx, int sy, int64_t wid, fd_detection& d);
 
 // ---------------- SVM scoring: what the detectors use of a model (svm.hip) ----------------
-// what the fused HOG + SVM kernel (hog_svm_fused.hpp, launched from hog.hip) needs of an f32 RBF model (svm.hip)
+// what the fused HOG + SVM kernel (hog_svm_fused.hpp, launched from hog.hip) needs of an f32 RBF model (svm.hip): its kernel argument
 struct FdSvmFusedView {
-    const float* svFrag;   // fragment-major support vectors [nsv_pad][KP]
-    const float* ss;       // |s|^2, [nsv_pad]
-    const float* coeff;    // [nsv_pad], zero padded
-    int nsv_pad, KP;
-    float bias;
-    double gamma;
+    const float* svFrag;   // fragment-major support vectors [nsvt][KP * 32]
+    const float* ss;       // |s|^2 per support vector (padded ones 0)
+    const float* coeff;    // coefficients (padded ones 0)
+    int32_t nsvt, KP;      // tiles of 32 support vectors, padded vector length
+    float bias, negGamma;
 };
 bool fd_svm_fused_view(const fd_svm* m, FdSvmFusedView* v);
 bool fd_svm_has_mfma_path(const fd_svm* m);

@@ -12,6 +12,7 @@
 #include "fd_internal.hpp"
 #include "fd_device.hpp"
 #include "win_table.hpp"
+#include "rbf_mfma.hpp"   // at file scope: hog_svm_fused.hpp is included inside the anonymous namespace below
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -185,12 +186,10 @@ float* hp_ = &hist[(v & 255u) * 64 + lane];
 
 __global__ void k_select_positives(const double* __restrict__ dist, int64_t n, float threshold, FdPosRec* __restrict__ pos,
                                    unsigned int* __restrict__ count, unsigned int cap) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double dv = dist[i];
-        if (dv >= (double)threshold) {  // SvmClassifier.cpp:44-46
-            unsigned int s = atomicAdd(count, 1u);
-            if (s < cap) pos[s] = FdPosRec{(uint32_t)i, (uint32_t)(i >> 32), dv};
-        }
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < n; i0 += (int64_t)gridDim.x * blockDim.x) {   // whole wavefronts reach the append
+        const int64_t i = i0 + threadIdx.x;
+        const double dv = i < n ? dist[i] : 0.0;
+        fd_dev::pos_append(pos, count, cap, i < n && dv >= (double)threshold, i, dv);  // SvmClassifier.cpp:44-46
     }
 }
 
@@ -316,19 +315,12 @@ int64_t run_hog_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hog_
     const char* fusedEnv = getenv("FD_HOG_FUSED");   // read per call: the tests switch between the two paths inside one process
     const bool fusedOn = !(fusedEnv && atoi(fusedEnv) == 0);
     if (fusedOn && hd.pw == 20 && hd.ph == 20 && hd.cell == 5 && hd.block == 2 && hd.bins == 9 && !hd.sau && hd.KP == 8 * HSF_Q &&
-        fd_svm_fused_view(svm, &fv) && fv.KP == hd.KP && fv.nsv_pad / 32 <= 64) {
-        HsfSvm hm;
-        hm.svFrag = fv.svFrag; hm.ss = fv.ss; hm.coeff = fv.coeff; hm.nsvt = fv.nsv_pad / 32; hm.bias = fv.bias; hm.negGamma = (float)(-fv.gamma);
-        const HsfPlan pl = hsf_plan(N, ctx->num_cus, hm.nsvt);
+        fd_svm_fused_view(svm, &fv) && fv.KP == hd.KP && fv.nsvt <= 64) {
+        const HsfPlan pl = hsf_plan(N, ctx->num_cus, fv.nsvt);
         S.dist.reserve(sizeof(double) * (size_t)pl.npadRows);
         if (pl.rem > 0) S.part.reserve(sizeof(double) * (size_t)pl.S * pl.npadRows);
-        const char* me = getenv("FD_HSF_SUBS");
-        const int subs = me ? atoi(me) : 1;
-        const size_t lds = hsf_lds_bytes(subs, hm.nsvt);
-        static uint64_t a0 = 0, a1 = 0, a2 = 0;
-        fd_allow_lds(ctx, (const void*)k_hog_svm_fused<0>, 160 * 1024, a0);
-        fd_allow_lds(ctx, (const void*)k_hog_svm_fused<1>, 160 * 1024, a1);
-        fd_allow_lds(ctx, (const void*)k_hog_svm_fused<2>, 160 * 1024, a2);
+        static uint64_t lds_allowed = 0;
+        fd_allow_lds(ctx, (const void*)k_hog_svm_fused, 160 * 1024, lds_allowed);
         HsfOut o;
         o.dist = S.dist.as<double>(); o.part = S.part.as<double>();
         o.cap = (unsigned int)std::min<int64_t>(N, 1 << 22);
@@ -342,16 +334,11 @@ int64_t run_hog_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hog_
         o.pos[0].wid_lo = 0xffffffffu;          // overwritten by the last workgroup of k_hsf_finish
         const int grid = pl.R > 0 ? pl.G : pl.rem * pl.S;
         if (time_kernel) HIP_CHECK(hipEventRecord(ctx->ev0, st));
-        if (subs == 0)
-            hipLaunchKernelGGL(k_hog_svm_fused<0>, dim3(grid), dim3(512), lds, st, p->arena.as<uint8_t>(), wt, hm, pl, o);
-        else if (subs == 2)
-            hipLaunchKernelGGL(k_hog_svm_fused<2>, dim3(grid), dim3(512), lds, st, p->arena.as<uint8_t>(), wt, hm, pl, o);
-        else
-            hipLaunchKernelGGL(k_hog_svm_fused<1>, dim3(grid), dim3(512), lds, st, p->arena.as<uint8_t>(), wt, hm, pl, o);
+        hipLaunchKernelGGL(k_hog_svm_fused, dim3(grid), dim3(512), hsf_lds_bytes(fv.nsvt), st, p->arena.as<uint8_t>(), wt, fv, pl, o);
         if (time_kernel) HIP_CHECK(hipEventRecord(ctx->ev1, st));
         const int64_t first = pl.rem > 0 ? (int64_t)pl.R * pl.G * 256 : N;   // first window of the remainder round
         hipLaunchKernelGGL(k_hsf_finish, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((N - first + 255) / 256, 1024))), dim3(256), 0, st,
-                           o, pl.S, pl.npadRows, first, N, hm.bias);
+                           o, pl.S, pl.npadRows, first, N, fv.bias);
         if (selected) *selected = true;
         if (pcapOut) *pcapOut = o.cap;
         HIP_CHECK(hipGetLastError());

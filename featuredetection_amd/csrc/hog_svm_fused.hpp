@@ -8,8 +8,9 @@
 // compute units.  Here the roles are swapped: a wavefront computes the HOG vectors of 32 windows straight into the 164 VGPRs of
 // its MFMA B operand (lane (h, r) holds elements 8q + 4h .. + 3 of window r for q = 0 .. 40: the fragment layout of svm.hip), and
 // the support-vector tiles (1.3 MB, L2 resident) stream through a double-buffered LDS image filled by global_load_lds -- the
-// inner loop, its barrier per tile and its epilogue are those of k_svm_rbf_mfma_svs with A and B exchanged.  The sum over support
-// vectors stays in the lane (fp64, tile after tile), so there are no partial sums to add in a second kernel.
+// tile load, the K loop and the epilogue are the ones k_svm_rbf_mfma_svs uses (rbf_mfma.hpp), with the register operand on the
+// other side of the MFMA.  The sum over support vectors stays in the lane (fp64, tile after tile), so there are no partial sums
+// to add in a second kernel.
 //
 // HOG of a tile, lane == (window r, half h): the lane loads ITS window's pixel rows 10h .. 10h + 9 of the (bin, weight) layer
 // (unaligned dwordx4 / x2 loads, 100 dwords), owns the eight cells of those rows and accumulates their histograms in LDS
@@ -18,22 +19,16 @@
 // reference's row-major order (HistogramFilter.cpp:150-163), so the fp32 histograms, energies, block norms and block vectors are
 // bit-identical to k_hog_tile's and the CPU path's.  Cell energies stay in registers (the partner half arrives through one
 // ds_bpermute each), both lanes of a window compute its nine block norms, and each lane multiplies out the 164 elements it owns.
-// The histograms alias the support-vector buffers (they are idle while a round's windows are prepared); the eight wavefronts
-// prepare their tiles in two groups of four so that the kernel needs 92 KB of LDS, not 160: the other streams' pyramid kernels can
-// still be resident on the same compute units.
+// The histograms alias the support-vector buffers (they are idle while a round's windows are prepared).  All eight wavefronts
+// prepare their tiles at once: 8 x 18,432 B of histograms + 256 B per support-vector tile (hsf_lds_bytes: 155,648 B for 1024
+// support vectors, 160 KiB for the 2048 the launcher accepts), so the kernel runs one workgroup per compute unit and no other
+// kernel shares it.
 //
 // Work: a round = 8 tiles (one per wavefront) x all support-vector tiles; workgroup g takes tile groups g, g + G, ...  The
 // groups left over after the last full round are split over the support vectors (S parts, S a power of two) so that the tail
 // costs 1 / S of a round instead of a whole one; their partial sums are added by k_hsf_finish.
 #pragma once
 
-struct HsfSvm {
-    const float* svFrag;   // fragment-major support vectors [nsvt][Q * 256]
-    const float* ss;       // |s|^2 per support vector (padded ones 0)
-    const float* coeff;    // coefficients (padded ones 0)
-    int32_t nsvt;          // tiles of 32 support vectors
-    float bias, negGamma;
-};
 struct HsfPlan {
     int32_t G, R, rem, S;  // workgroups, full rounds, tile groups of the remainder round, support-vector parts of a remainder group
     int64_t T, N, npadRows;
@@ -50,28 +45,16 @@ struct HsfOut {
     float threshold;
 };
 
-// appends this wavefront's positive windows: one atomic per wavefront
-__device__ __forceinline__ void hsf_append(const HsfOut& o, bool positive, int64_t w, double d) {
-    const unsigned long long mask = __ballot(positive);
-    if (!mask) return;
-    const int lane = threadIdx.x & 63;
-    unsigned int base = 0;
-    if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(o.header, (unsigned int)__popcll(mask));
-    base = __shfl(base, __ffsll((long long)mask) - 1, 64);
-    if (positive) {
-        const unsigned int slot = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-        if (slot < o.cap) o.pos[1 + slot] = FdPosRec{(uint32_t)w, (uint32_t)(w >> 32), d};
-    }
-}
-
-typedef float hsf_f32x16 __attribute__((ext_vector_type(16)));
-typedef float hsf_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void hsf_lds_void_t;
+using fd_dev::f32x4;
 
 constexpr int HSF_Q = 41;          // 8-wide k groups of the 324-element vector (KP = 328)
 constexpr int HSF_F = 324;
 constexpr int HSF_HS = 144;        // floats per window in the histogram scratch (16 cells x 9 bins)
 constexpr int HSF_TILE_FLOATS = HSF_Q * 256;
+// LDS, in floats: the eight wavefronts' histogram scratch, aliasing the two support-vector buffers; behind it [nsvt][64] floats:
+// |s|^2 of a tile's 32 support vectors, then their coefficients
+constexpr int HSF_SCR = std::max(8 * 32 * HSF_HS, 2 * HSF_TILE_FLOATS);
+static inline size_t hsf_lds_bytes(int nsvt) { return sizeof(float) * ((size_t)HSF_SCR + (size_t)nsvt * 64); }
 
 // element k of the feature vector -> offset of its histogram value inside a window's 144 floats, and its block
 // (HogFilter.cpp:85-97: blocks row-major, the block's 2 x 2 cells row-major, 9 bins each)
@@ -82,7 +65,7 @@ __host__ __device__ constexpr int hsf_block(int k) { return k / 36; }
 
 // HOG vectors of the 32 windows of `tile` -> B (this lane's 41 float4 fragment slots) and |x|^2 of window lane & 31
 __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, const FdWinTable& wt, int64_t tile, float* hist,
-                                             hsf_f32x4 (&B)[HSF_Q], float& xxOut) {
+                                             f32x4 (&B)[HSF_Q], float& xxOut) {
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     int64_t wid = tile * 32 + r;
     wid = wid < wt.total ? wid : wt.total - 1;   // rows behind the last window repeat it (their results are never written)
@@ -171,7 +154,7 @@ __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, 
     if (h == 0) {
 #pragma unroll
         for (int q = 0; q < HSF_Q; ++q) {
-            hsf_f32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int k = 8 * q + t;
@@ -182,7 +165,7 @@ __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, 
     } else {
 #pragma unroll
         for (int q = 0; q < HSF_Q; ++q) {
-            hsf_f32x4 o;
+            f32x4 o;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int k = 8 * q + 4 + t;
@@ -204,37 +187,22 @@ __device__ __forceinline__ void hsf_hog_tile(const uint8_t* __restrict__ arena, 
     wave_sync();
 }
 
-// SUBS: groups the eight wavefronts prepare their tiles in (2: four at a time, 92 KB of LDS; 1: all at once, 157 KB; 0: no HOG at
-// all -- a timing experiment, results meaningless)
-template <int SUBS>
-__global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restrict__ arena, FdWinTable wt, HsfSvm m, HsfPlan plan, HsfOut out) {
+__global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restrict__ arena, FdWinTable wt, FdSvmFusedView m, HsfPlan plan,
+                                                          HsfOut out) {
     extern __shared__ __attribute__((aligned(16))) float hsf_lds[];
     float* const buf0 = hsf_lds;
     float* const buf1 = hsf_lds + HSF_TILE_FLOATS;
-    constexpr int HISTW = SUBS == 1 ? 8 : 4;            // wavefronts whose histogram scratch exists at the same time
-    constexpr int SCR = (HISTW * 32 * HSF_HS > 2 * HSF_TILE_FLOATS) ? HISTW * 32 * HSF_HS : 2 * HSF_TILE_FLOATS;
-    float* const svc = hsf_lds + SCR;   // [nsvt][64]: |s|^2 of the tile's 32 support vectors, then their coefficients
+    float* const svc = hsf_lds + HSF_SCR;   // [nsvt][64]: |s|^2 of the tile's 32 support vectors, then their coefficients
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = threadIdx.x; i < m.nsvt * 64; i += 512) {
         const int t = i >> 6, j = i & 63;
         svc[i] = j < 32 ? m.ss[t * 32 + j] : m.coeff[t * 32 + j - 32];
     }
-    float* const hist = hsf_lds + (wave & (HISTW - 1)) * (32 * HSF_HS);   // aliases buf0 / buf1 (4 x 18,432 B <= 83,968 B)
-    auto issue_tile = [&](int sv, float* dst) {
-        // LDS-DMA, 1 KiB per wave instruction; wave w moves q-groups w, w + 8, ...  (svm.hip: issued through inline asm so that the
-        // compiler does not wait vmcnt(0) before every ds_read of the tile being computed; completion is awaited explicitly)
-        const char* g = (const char*)(m.svFrag + (size_t)sv * HSF_TILE_FLOATS) + (size_t)lane * 16;
-        for (int q = wave; q < HSF_Q; q += 8) {
-            const unsigned ldsDst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(hsf_lds_void_t*)(dst + q * 256));
-            const char* gsrc = g + (size_t)q * 1024;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(ldsDst) : "memory");
-        }
-    };
-    hsf_f32x4 B[HSF_Q];
+    float* const hist = hsf_lds + wave * (32 * HSF_HS);   // aliases buf0 / buf1
+    auto issue_tile = [&](int sv, float* dst) { fd_dev::lds_dma_tile<HSF_Q>(m.svFrag + (size_t)sv * HSF_TILE_FLOATS, dst, lane, wave); };
+    f32x4 B[HSF_Q];
 #pragma unroll
-    for (int q = 0; q < HSF_Q; ++q) B[q] = hsf_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < HSF_Q; ++q) B[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     float xxj = 0.f;
     for (int round = 0; round <= plan.R; ++round) {
         int64_t group;
@@ -251,18 +219,8 @@ __global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restr
         const int64_t tile = group * 8 + wave;
         const bool have = tile < plan.T;
         __syncthreads();   // svc staged; the previous round's last support-vector tile has been read by every wavefront
-        if (SUBS == 2) {
-            for (int sub = 0; sub < 2; ++sub) {
-                if ((wave >> 2) == sub && have) hsf_hog_tile(arena, wt, tile, hist, B, xxj);
-                __syncthreads();
-            }
-        } else if (SUBS == 1) {
-            if (have) hsf_hog_tile(arena, wt, tile, hist, B, xxj);
-            __syncthreads();
-        } else {
-#pragma unroll
-            for (int q = 0; q < HSF_Q; ++q) B[q] = hsf_f32x4{(float)tile, 1.f, 2.f, (float)q};
-        }
+        if (have) hsf_hog_tile(arena, wt, tile, hist, B, xxj);
+        __syncthreads();
         int cur = 0;
         issue_tile(s0, buf0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -270,30 +228,9 @@ __global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restr
         double s = 0.0;
         for (int sv = s0; sv < s1; ++sv) {
             if (sv + 1 < s1) issue_tile(sv + 1, cur ? buf0 : buf1);
-            if (have) {
-                const hsf_f32x4* ap = (const hsf_f32x4*)(cur ? buf1 : buf0) + lane;
-                hsf_f32x16 acc = {0};
-                hsf_f32x4 p = ap[0];
-#pragma unroll
-                for (int q = 0; q < HSF_Q; ++q) {
-                    const hsf_f32x4 pn = ap[(size_t)(q + 1 < HSF_Q ? q + 1 : q) * 64];
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[0], B[q][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[1], B[q][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[2], B[q][2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p[3], B[q][3], acc, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    p = pn;
-                }
-                // RBF values of the tile's 32 support vectors for this lane's window, added to its fp64 sum (C[i = SV][j = window]:
-                // accumulator r is support vector (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
-                const float* c = svc + sv * 64;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    const float d2 = (xxj + c[row]) - 2.f * acc[r];
-                    s += (double)c[32 + row] * (double)__expf(m.negGamma * fmaxf(d2, 0.f));
-                }
+            if (have) {   // the tile's 32 support vectors for this lane's window, added to its fp64 sum
+                const fd_dev::f32x16 acc = fd_dev::mfma32_tile<HSF_Q, false>((const f32x4*)(cur ? buf1 : buf0) + lane, B);
+                fd_dev::rbf_accumulate(s, acc, xxj, svc + sv * 64, m.negGamma, lane);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next tile has landed in LDS
             __syncthreads();
@@ -302,12 +239,12 @@ __global__ __launch_bounds__(512, 2) void k_hog_svm_fused(const uint8_t* __restr
         s += __shfl_xor(s, 32, 64);   // the two halves of the support-vector rows
         const int64_t w = tile * 32 + lane;
         if (prt < 0) {
-            const double d = SUBS == 0 ? -1e30 + 1e-30 * s : -(double)m.bias + s;
+            const double d = -(double)m.bias + s;
             const bool mine = have && lane < 32 && w < plan.N;
             if (mine) out.dist[w] = d;
-            hsf_append(out, mine && d >= (double)out.threshold, w, d);
+            fd_dev::pos_append(out.pos + 1, out.header, out.cap, mine && d >= (double)out.threshold, w, d);
         } else if (have && lane < 32) {
-            out.part[(size_t)prt * plan.npadRows + w] = SUBS == 0 ? -1e30 + 1e-30 * s : s;
+            out.part[(size_t)prt * plan.npadRows + w] = s;
         }
     }
 }
@@ -319,12 +256,10 @@ __global__ __launch_bounds__(256) void k_hsf_finish(HsfOut o, int S, int64_t npa
         const int64_t i = i0 + threadIdx.x;
         double d = 0.0;
         if (i < n) {
-            double s = 0.0;
-            for (int p = 0; p < S; ++p) s += o.part[(size_t)p * npadRows + i];
-            d = -(double)bias + s;
+            d = -(double)bias + fd_dev::sum_rows(o.part, S, npadRows, i);
             o.dist[i] = d;
         }
-        hsf_append(o, i < n && d >= (double)o.threshold, i, d);
+        fd_dev::pos_append(o.pos + 1, o.header, o.cap, i < n && d >= (double)o.threshold, i, d);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -338,11 +273,6 @@ __global__ __launch_bounds__(256) void k_hsf_finish(HsfOut o, int S, int64_t npa
             __hip_atomic_store(o.header + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-}
-
-static inline size_t hsf_lds_bytes(int subs, int nsvt) {
-    const size_t scr = std::max<size_t>((size_t)(subs == 1 ? 8 : 4) * 32 * HSF_HS, (size_t)2 * HSF_TILE_FLOATS);
-    return sizeof(float) * (scr + (size_t)nsvt * 64);
 }
 
 static inline HsfPlan hsf_plan(int64_t N, int G, int nsvt) {

@@ -186,17 +186,8 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
                 }
             }
         }
-        // survivors of this pass: wave-aggregated append
-        const unsigned long long mask = __ballot(alive);
-        if (mask) {
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(out_count, (unsigned int)__popcll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (alive) {
-                const unsigned int idx = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-                outq[idx] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
-            }
-        }
+        // survivors of this pass (the queue holds every window: no cap)
+        fd_dev::pos_append(outq, out_count, 0xffffffffu, alive, wid, d);
     }
 }
 

@@ -16,6 +16,7 @@
 //    workgroup in LDS, B (support vectors, L2-resident) streams straight into registers.
 // MFMA-bound: 2*d*n_sv flop per patch; peak 157.3 TFLOP/s dense f32 MFMA.
 #include "fd_internal.hpp"
+#include "rbf_mfma.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -25,7 +26,8 @@
 // stored as tiles of 32 rows; within a tile, for each group q of 8 consecutive k there are 64
 // float4 slots: slot (h*32 + r) holds row r, k = 8q + 4h .. 8q + 4h + 3.  Lane l of a wave reads
 // slot l: that is exactly its operand for four consecutive v_mfma_f32_32x32x2_f32 issues (lanes
-// 0-31 supply k = 8q+t, lanes 32-63 supply k = 8q+4+t, t = 0..3).
+// 0-31 supply k = 8q+t, lanes 32-63 supply k = 8q+4+t, t = 0..3).  The device side of the layout (tile
+// load, K loop, accumulator row map, RBF epilogue) is rbf_mfma.hpp.
 static inline size_t frag_index(int64_t row, int k, int KP) {
     const int64_t tile = row >> 5;
     const int r = (int)(row & 31), q = k >> 3, h = (k >> 2) & 1, t = k & 3;
@@ -68,6 +70,10 @@ struct fd_svm {
 };
 
 namespace {
+
+using fd_dev::f32x16;
+using fd_dev::f32x4;
+using fd_dev::mfma32_row;
 
 __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -366,7 +372,7 @@ __global__ __launch_bounds__(64 * SU_W) void k_svm_u8_rbf_mfma(SvmDev m, const v
         double sum = 0.0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int sv = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int sv = t * 32 + mfma32_row(r, lane);
             const int ssd = xxv + m.ssShift[sv] - 2 * acc[r];
             sum += m.coeffD[sv] * exp(-m.p0 * (double)ssd);   // padded support vectors have coefficient 0
         }
@@ -383,9 +389,6 @@ __global__ __launch_bounds__(64 * SU_W) void k_svm_u8_rbf_mfma(SvmDev m, const v
 }
 
 // ---- dense RBF stage on the f32 MFMA pipe --------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int RB_THREADS = 512;   // 8 waves: 2 per SIMD (one can run its exp epilogue while the other issues MFMAs)
 constexpr int RB_BM = 64;         // patches per workgroup (2 row tiles), A resident in LDS
 constexpr int RB_DEPTH = 4;       // B prefetch ring (q-groups in flight per wave)
@@ -465,13 +468,13 @@ __global__ __launch_bounds__(RB_THREADS, 2) void k_svm_rbf_mfma(const float* __r
         if (q + 1 < Q) RB_STEP(1, false)
         if (q + 2 < Q) RB_STEP(2, false)
 #undef RB_STEP
-        // epilogue: C/D layout col = lane & 31 (support vector), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (patch)
+        // epilogue: C/D layout col = lane & 31 (support vector), row = mfma32_row(r, lane) (patch)
         const int j = nt * 32 + (lane & 31);
         const float ssj = m.ss_f32[j];
         const double cj = (double)m.coeffPad[j];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = mfma32_row(r, lane);
             const float d0 = (ldsXX[row] + ssj) - 2.f * acc0[r];
             const float d1 = (ldsXX[32 + row] + ssj) - 2.f * acc1[r];
             rs0[r] += cj * (double)__expf(negGamma * fmaxf(d0, 0.f));
@@ -487,7 +490,7 @@ __global__ __launch_bounds__(RB_THREADS, 2) void k_svm_rbf_mfma(const float* __r
             b += __shfl_xor(b, o, 64);
         }
         if ((lane & 31) == 0) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = mfma32_row(r, lane);
             ldsRed[wave * 64 + row] = a;
             ldsRed[wave * 64 + 32 + row] = b;
         }
@@ -515,9 +518,6 @@ __global__ __launch_bounds__(RB_THREADS, 2) void k_svm_rbf_mfma(const float* __r
 // phase (deferred epilogue) was measured to change nothing: the matrix pipe is already 95 % busy at
 // the ~2.1 GHz the part sustains under this load (PMC: SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE).
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
 template <int Q>   // exact number of 8-wide k groups (KP / 8): keeps the K loop free of branches
 __global__ __launch_bounds__(512, 2) void k_svm_rbf_mfma_svs(const float* __restrict__ xFrag, const float* __restrict__ xx, SvmDev m,
                                                              float negGamma, int64_t ntiles, double* __restrict__ partial,
@@ -541,34 +541,10 @@ __global__ __launch_bounds__(512, 2) void k_svm_rbf_mfma_svs(const float* __rest
     // stationary operand): svc[wave][0..31] = |s|^2, svc[wave][32..63] = coefficient
     float* svc = red + wave * 64;
     svc[lane] = lane < 32 ? m.ss_f32[nt * 32 + lane] : m.coeffPad[nt * 32 + lane - 32];
-    auto issue_tile = [&](int64_t tile, float* dst) {
-        // LDS-DMA, 1 KiB per wave instruction; wave w moves q-groups w, w+8, ...  Issued through inline asm so
-        // that the compiler does not see a pending LDS write (it would wait vmcnt(0) before every ds_read of
-        // the tile being computed); completion is awaited explicitly (vmcnt(0) + barrier) before the buffer
-        // is read.  Recipe: cdna_hip_programming.md section 5.7 (M0 = wave-uniform LDS destination).
-        const char* g = (const char*)(xFrag + (size_t)tile * 32 * KP) + (size_t)lane * 16;
-        for (int q = wave; q < Q; q += 8) {
-            const unsigned ldsDst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void_t*)(dst + q * 256));
-            const char* gsrc = g + (size_t)q * 1024;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(ldsDst) : "memory");
-        }
-    };
-    // epilogue of one tile: RBF values of this wave's 32 support vectors for the 32 patches, summed over the support
-    // vectors in fp64 and written as this wave's partial sum (k_sum_partials adds the 8 * ngroups partials)
+    auto issue_tile = [&](int64_t tile, float* dst) { fd_dev::lds_dma_tile<Q>(xFrag + (size_t)tile * 32 * KP, dst, lane, wave); };
+    // this wave's partial sums: RBF values of its 32 support vectors for a tile's 32 patches, summed over the support vectors in
+    // fp64 (k_sum_partials adds the 8 * ngroups partials)
     double* const myPartial = partial + ((size_t)blockIdx.y * 8 + wave) * npadRows;
-    auto epilogue = [&](const f32x16& a, float xxv, int64_t t) {
-        double s = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);   // support vector of accumulator r
-            const float d2 = (xxv + svc[row]) - 2.f * a[r];
-            s += (double)svc[32 + row] * (double)__expf(negGamma * fmaxf(d2, 0.f));
-        }
-        s += __shfl_xor(s, 32, 64);
-        if (lane < 32) myPartial[t * 32 + lane] = s;
-    };
     int cur = 0;
     int64_t tile = blockIdx.x;
     float xxj = tile < ntiles ? xx[tile * 32 + (lane & 31)] : 0.f;
@@ -581,21 +557,11 @@ __global__ __launch_bounds__(512, 2) void k_svm_rbf_mfma_svs(const float* __rest
         // compiler-inserted vmcnt wait for it can land behind the DMA inside this iteration's compute
         const float xxn = next < ntiles ? xx[next * 32 + (lane & 31)] : 0.f;
         if (next < ntiles) issue_tile(next, cur ? buf0 : buf1);
-        const f32x4* ap = (const f32x4*)(cur ? buf1 : buf0) + lane;
-        f32x16 acc = {0};
-        f32x4 p = ap[0];
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const f32x4 pn = ap[(size_t)(q + 1 < Q ? q + 1 : q) * 64];
-            __builtin_amdgcn_sched_barrier(0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[q][0], p[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[q][1], p[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[q][2], p[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[q][3], p[3], acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            p = pn;
-        }
-        epilogue(acc, xxj, tile);
+        const f32x16 acc = fd_dev::mfma32_tile<Q, true>((const f32x4*)(cur ? buf1 : buf0) + lane, sv);
+        double s = 0.0;
+        fd_dev::rbf_accumulate(s, acc, xxj, svc, negGamma, lane);
+        s += __shfl_xor(s, 32, 64);   // the two halves of the support-vector rows
+        if (lane < 32) myPartial[tile * 32 + lane] = s;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next tile has landed in LDS (and the partial sums are out)
         __syncthreads();
         xxj = xxn;
@@ -606,19 +572,8 @@ __global__ __launch_bounds__(512, 2) void k_svm_rbf_mfma_svs(const float* __rest
 // out[i] = -bias + sum over SV groups
 __global__ void k_sum_partials(const double* __restrict__ partial, int ngroups, int64_t npadRows, int64_t n, float bias,
                                double* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double s = 0.0;
-        int g = 0;
-        for (; g + 8 <= ngroups; g += 8) {   // eight loads in flight, added in group order
-            double v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = partial[(size_t)(g + k) * npadRows + i];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; g < ngroups; ++g) s += partial[(size_t)g * npadRows + i];
-        out[i] = -(double)bias + s;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = -(double)bias + fd_dev::sum_rows(partial, ngroups, npadRows, i);
 }
 
 }  // namespace
@@ -637,39 +592,41 @@ double fd_svm_probability(const fd_svm* m, double d) {  // ProbabilisticSvmClass
 bool fd_svm_fused_view(const fd_svm* m, FdSvmFusedView* v) {
     if (!m->dev.svFrag || m->dev.kernel != FD_KERNEL_RBF) return false;
     v->svFrag = m->dev.svFrag; v->ss = m->dev.ss_f32; v->coeff = m->dev.coeffPad;
-    v->nsv_pad = m->dev.nsv_pad; v->KP = m->dev.KP; v->bias = m->dev.bias; v->gamma = m->dev.p0;
+    v->nsvt = m->dev.nsv_pad / 32; v->KP = m->dev.KP; v->bias = m->dev.bias; v->negGamma = (float)(-m->dev.p0);
     return true;
 }
 
 size_t fd_svm_rbf_lds_bytes(int KP) { return (size_t)2 * (KP / 8) * 256 * 4 + 64 * 4 + 8 * 64 * 8; }
+// k_svm_rbf_mfma_svs: two patch tiles + |s|^2 and coefficients of the eight wavefronts' support-vector tiles
+static size_t svs_lds_bytes(int KP) { return (size_t)2 * (KP / 8) * 256 * 4 + 8 * 64 * 4; }
+
+// k_svm_rbf_mfma_svs<Q> + k_sum_partials
+template <int Q>
+static void launch_svs(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out) {
+    fd_svm* mm = const_cast<fd_svm*>(m);
+    const int64_t ntiles = (npatches + 31) / 32;
+    const int64_t npadRows = ((npatches + 63) / 64) * 64;
+    const int ngroups = m->dev.nsv_pad / 256;
+    mm->dist.reserve(sizeof(double) * (size_t)ngroups * 8 * npadRows);
+    static uint64_t lds_allowed = 0;   // per instantiation
+    fd_allow_lds(ctx, (const void*)k_svm_rbf_mfma_svs<Q>, 160 * 1024, lds_allowed);
+    const int gx = (int)std::min<int64_t>(ntiles, std::max(1, ctx->num_cus / ngroups));
+    hipLaunchKernelGGL(k_svm_rbf_mfma_svs<Q>, dim3(gx, ngroups), dim3(512), svs_lds_bytes(8 * Q), ctx->stream, xFrag, xx, m->dev,
+                       (float)(-m->dev.p0), ntiles, mm->dist.as<double>(), npadRows);
+    hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)std::min<int64_t>((npatches + 255) / 256, 2048)), dim3(256), 0, ctx->stream,
+                       mm->dist.as<double>(), ngroups * 8, npadRows, npatches, m->dev.bias, out);
+    HIP_CHECK(hipGetLastError());
+}
 
 // dense MFMA scoring of npatches feature vectors already on the device in fragment-major layout
-// (rows padded to a multiple of 64, pad rows zero).  partial: scratch for the SV-stationary kernel.
+// (rows padded to a multiple of 64, pad rows zero).
 // variant: 2 = the support-vector-stationary kernel where it is instantiated, anything else = the A-resident kernel
 static void svm_rbf_mfma_launch_variant(fd_ctx* ctx, const fd_svm* m, const float* xFrag, const float* xx, int64_t npatches, double* out, int variant) {
     if (!m->dev.svFrag) FD_THROW(FD_ERR_INVALID_ARGUMENT, "SVM has no MFMA path (needs an RBF kernel on f32 vectors)");
     const int KP = m->dev.KP;
-    if (variant == 2 && (KP == 328 || KP == 336)) {   // instantiated sizes (HOG-324 -> 328); others use the A-resident kernel
-        fd_svm* mm = const_cast<fd_svm*>(m);
-        const int64_t ntiles = (npatches + 31) / 32;
-        const int64_t npadRows = ((npatches + 63) / 64) * 64;
-        const int ngroups = m->dev.nsv_pad / 256;
-        mm->dist.reserve(sizeof(double) * (size_t)ngroups * 8 * npadRows);
-        const size_t ldsBytes = (size_t)2 * (KP / 8) * 256 * 4 + 8 * 64 * 4;
-        static uint64_t lds41 = 0, lds42 = 0;
-        fd_allow_lds(ctx, (const void*)k_svm_rbf_mfma_svs<41>, 160 * 1024, lds41);
-        fd_allow_lds(ctx, (const void*)k_svm_rbf_mfma_svs<42>, 160 * 1024, lds42);
-        const int gx = (int)std::min<int64_t>(ntiles, std::max(1, ctx->num_cus / ngroups));
-        if (KP == 328)
-            hipLaunchKernelGGL(k_svm_rbf_mfma_svs<41>, dim3(gx, ngroups), dim3(512), ldsBytes, ctx->stream, xFrag, xx, m->dev,
-                               (float)(-m->dev.p0), ntiles, mm->dist.as<double>(), npadRows);
-        else
-            hipLaunchKernelGGL(k_svm_rbf_mfma_svs<42>, dim3(gx, ngroups), dim3(512), ldsBytes, ctx->stream, xFrag, xx, m->dev,
-                               (float)(-m->dev.p0), ntiles, mm->dist.as<double>(), npadRows);
-        hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)std::min<int64_t>((npatches + 255) / 256, 2048)), dim3(256), 0, ctx->stream,
-                           mm->dist.as<double>(), ngroups * 8, npadRows, npatches, m->dev.bias, out);
-        HIP_CHECK(hipGetLastError());
-        return;
+    if (variant == 2) {   // instantiated sizes (HOG-324 -> 328); others use the A-resident kernel
+        if (KP == 328) return launch_svs<41>(ctx, m, xFrag, xx, npatches, out);
+        if (KP == 336) return launch_svs<42>(ctx, m, xFrag, xx, npatches, out);
     }
     const size_t ldsBytes = fd_svm_rbf_lds_bytes(KP);
     if (ldsBytes > 160 * 1024) FD_THROW(FD_ERR_INVALID_ARGUMENT, "feature length %d too large for the MFMA SVM kernel", m->dev.dim);

@@ -1,6 +1,6 @@
 // featuredetection_amd/csrc/win_table.hpp -- what every "scan all windows of the pyramid" family beside the WVM cascade shares (HOG,
 // the histogram filters, the whi chain, the RVM detector): the device window table and its host builders, the device window id ->
-// position search, and the host tail that turns positive records into fd_detections.
+// position search, the device append of positive records, and the host tail that turns them into fd_detections.
 //
 // One numbering rule, the one of fd_enumerate_layers and fd_window_to_detection: windows are numbered layer by layer in extraction
 // order (DirectPyramidFeatureExtractor.cpp:75-123), row-major inside a layer.  Layers without windows are left out of the table
@@ -81,6 +81,26 @@ struct FdPosRec {
     double d;   // hyperplane distance (RVM: also the running distance of a survivor between passes)
 };
 __host__ __device__ inline uint64_t fd_pos_wid(const FdPosRec& r) { return ((uint64_t)r.wid_hi << 32) | r.wid_lo; }
+
+namespace fd_dev {
+
+// appends the records of this wavefront's `positive` lanes to recs (one atomic on *counter per wavefront; records from slot cap on
+// are counted, not written).  Every lane of the wavefront must reach the call: wavefront-uniform control flow around it.  The order
+// of the records in the buffer is not defined (the hosts sort by window id)
+__device__ __forceinline__ void pos_append(FdPosRec* recs, unsigned int* counter, unsigned int cap, bool positive, int64_t wid, double d) {
+    const unsigned long long mask = __ballot(positive);
+    if (!mask) return;
+    const int lane = threadIdx.x & 63;
+    unsigned int base = 0;
+    if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(counter, (unsigned int)__popcll(mask));
+    base = __shfl(base, __ffsll((long long)mask) - 1, 64);
+    if (positive) {
+        const unsigned int slot = base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+        if (slot < cap) recs[slot] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), d};
+    }
+}
+
+}  // namespace fd_dev
 
 // extraction order
 static inline bool fd_pos_before(const FdPosRec& a, const FdPosRec& b) { return fd_pos_wid(a) < fd_pos_wid(b); }

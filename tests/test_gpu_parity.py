@@ -755,13 +755,9 @@ def test_hog_rbf_svm_detector_config2(oracle, capi, ctx, synth):
     sg.close(); pg.close()
 
 
-@pytest.mark.parametrize("size,nsv", [((160, 120), 100), ((320, 240), 300), ((333, 251), 1024), ((640, 480), 64), ((45, 37), 33), ((97, 22), 256)])
-def test_hog_svm_fused_kernel_equals_the_two_kernel_path(oracle, capi, ctx, synth, size, nsv, monkeypatch):
-    """config 2's shape runs as ONE kernel (hog_svm_fused.hpp: HOG vectors produced in the registers of the MFMA operand, support
-    vectors streamed).  Against the two-kernel path (k_hog_tile -> features in HBM -> k_svm_rbf_mfma_svs, FD_HOG_FUSED=0) the HOG
-    values are the same bits; |x|^2 (fp32) and the fp64 sum over support vectors are added in another order: distances within 2e-7 of sum|coeff|,
-    the same positives away from the threshold.  The sizes cover a launch without a full round (the tail split over 2..32
-    support-vector parts), full rounds + a tail, window counts that are not multiples of 32, and 2 / 16 / 32 support-vector tiles."""
+def _fused_case(capi, ctx, synth, size, nsv):
+    """a frame of that size in a gradient-bin pyramid and an RBF SVM of nsv support vectors on config 2's HOG shape:
+    (frame, pyramid arguments, pyramid, model, model on the device)"""
     W, H = size
     frame = synth.make_frame(W, H, seed=31)
     kw = dict(octave_layers=5, min_scale=1 / 16, max_scale=1.0)
@@ -777,7 +773,17 @@ def test_hog_svm_fused_kernel_equals_the_two_kernel_path(oracle, capi, ctx, synt
         pb.close()
     m = synth.make_svm_f32(7, feats2[:: max(1, len(feats2) // 4000)], nsv=nsv, gamma=0.5, positive_fraction=0.05)
     pg.update(frame)
-    sg = capi.Svm(ctx, m)
+    return frame, kw, pg, m, capi.Svm(ctx, m)
+
+
+@pytest.mark.parametrize("size,nsv", [((160, 120), 100), ((320, 240), 300), ((333, 251), 1024), ((640, 480), 64), ((45, 37), 33), ((97, 22), 256)])
+def test_hog_svm_fused_kernel_equals_the_two_kernel_path(oracle, capi, ctx, synth, size, nsv, monkeypatch):
+    """config 2's shape runs as ONE kernel (hog_svm_fused.hpp: HOG vectors produced in the registers of the MFMA operand, support
+    vectors streamed).  Against the two-kernel path (k_hog_tile -> features in HBM -> k_svm_rbf_mfma_svs, FD_HOG_FUSED=0) the HOG
+    values are the same bits; |x|^2 (fp32) and the fp64 sum over support vectors are added in another order: distances within 2e-7 of sum|coeff|,
+    the same positives away from the threshold.  The sizes cover a launch without a full round (the tail split over 2..32
+    support-vector parts), full rounds + a tail, window counts that are not multiples of 32, and 2 / 16 / 32 support-vector tiles."""
+    frame, kw, pg, m, sg = _fused_case(capi, ctx, synth, size, nsv)
     monkeypatch.setenv("FD_HOG_FUSED", "0")
     dets_2, dist_2 = capi.detect_hog_svm(ctx, pg, sg, capi.hog_params())
     monkeypatch.setenv("FD_HOG_FUSED", "1")
@@ -846,6 +852,71 @@ def test_every_window_of_every_scan_family_lands_where_the_oracle_enumerates_it(
     assert np.bincount(wroi[:, 0], minlength=5).tolist() == [50, 4, 0, 0, 0]
     same(capi.detect_rvm(ctx, pg, rg, sx=2, sy=2, roi=roi)[0], wroi)
     rg.close(); s324.close(); s400.close(); pb.close(); pg.close(); po.close()
+
+
+@pytest.mark.parametrize("size,nsv", [((45, 37), 33), ((97, 22), 256)])
+def test_hsf_subs_is_gone(capi, ctx, synth, size, nsv, monkeypatch):
+    """k_hog_svm_fused has one body.  FD_HSF_SUBS used to pick one of three per call, unvalidated: 0 returned garbage, 2 a variant no
+    test ran, anything else the default body with the LDS sized for another.  Whatever it is set to, distances and detections are
+    now the bytes of a run without it."""
+    monkeypatch.delenv("FD_HOG_FUSED", raising=False)
+    monkeypatch.delenv("FD_HSF_SUBS", raising=False)
+    _, _, pg, _, sg = _fused_case(capi, ctx, synth, size, nsv)
+    dets, dist = capi.detect_hog_svm(ctx, pg, sg, capi.hog_params())
+    assert len(dist) > 0
+    for value in ("0", "2", "7"):
+        monkeypatch.setenv("FD_HSF_SUBS", value)
+        dets_v, dist_v = capi.detect_hog_svm(ctx, pg, sg, capi.hog_params())
+        assert dist_v.tobytes() == dist.tobytes() and dets_v.tobytes() == dets.tobytes(), value
+    sg.close(); pg.close()
+
+
+def test_selected_positives_are_exactly_the_windows_at_or_above_the_threshold(oracle, capi, ctx, synth, monkeypatch):
+    """k_select_positives (the two-kernel HOG path, the histogram and the whi detectors) appends a wavefront's positives with one
+    atomic: every lane of a wavefront has to reach the ballot, with the windows behind the last one voting no.  The 96 x 72 frame of
+    the scan-family test has 1505 windows: 23 full wavefronts and one of 33 lanes.  Thresholds come from a run's own distances -- the
+    largest float below or at the minimum, the median rounded to float, the smallest float above the maximum -- and the decision is
+    re-derived from the distances the same run returned, so there is no tolerance: the detections are the oracle's window rows at
+    nonzero(distance >= threshold), every window once, none twice, all of them / half of them / none (an empty ballot in every
+    wavefront).  "Half": the 753 distances from the median up, or 752 when the float threshold lies just above the median; the
+    models' gamma is 1 / (median squared distance between feature vectors), so neighbouring distances are many float steps apart."""
+    frame = synth.make_frame(96, 72, seed=11)
+    kw = dict(octave_layers=2, min_scale=0.25, max_scale=1.0)
+    po, pg = _pyr_pair(oracle, capi, ctx, frame, **kw)
+    wins = po.windows(20, 20, 2, 2)
+    n = len(wins)
+    assert n == 1505 and n % 64 == 33
+    pb = capi.Pyramid(ctx, **kw)
+    pb.set_layer_filter(capi.FD_LAYER_GRADBIN, bins=9)
+    pb.update(frame)
+    monkeypatch.setenv("FD_HOG_FUSED", "0")
+    hist = capi.hist_params(kind=0, block=2)
+    families = [(capi.extract_hog(ctx, pb, capi.hog_params()), lambda s: capi.detect_hog_svm(ctx, pb, s, capi.hog_params(), want_all=True)),
+                (capi.extract_hist(ctx, pb, hist), lambda s: capi.detect_hist_svm(ctx, pb, s, hist, want_all=True)),
+                (capi.extract_whi(ctx, pg, capi.whi_params()), lambda s: capi.detect_whi_svm(ctx, pg, s, capi.whi_params(), want_all=True))]
+    for which, (feats, detect) in enumerate(families):
+        assert len(feats) == n
+        sub = feats[::16].astype(np.float64)
+        d2 = (sub ** 2).sum(1)[:, None] + (sub ** 2).sum(1)[None, :] - 2 * sub @ sub.T
+        m = synth.make_svm_f32(41 + which, feats, nsv=64, gamma=1.0 / np.median(d2[d2 > 0]))
+
+        def run(threshold):
+            s = capi.Svm(ctx, dict(m, threshold=threshold))
+            dets, dist = detect(s)
+            s.close()
+            rows = np.stack([dets[f] for f in ("layer", "lx", "ly", "cx", "cy", "w", "h")], 1).astype(np.int32)
+            return rows, dist
+
+        _, dist0 = run(np.float32(-1e30))
+        lo, mid, hi = np.float32(dist0.min()), np.float32(np.median(dist0)), np.float32(dist0.max())
+        lo = lo if lo <= dist0.min() else np.nextafter(lo, np.float32(-np.inf))
+        hi = np.nextafter(hi, np.float32(np.inf)) if hi <= dist0.max() else hi
+        for thr, counts in ((lo, (n,)), (mid, (n // 2, n // 2 + 1)), (hi, (0,))):
+            rows, dist = run(thr)
+            pos = np.nonzero(dist >= np.float64(thr))[0]
+            assert len(pos) in counts, (which, thr, len(pos))
+            assert np.array_equal(rows, wins[pos]), (which, thr)
+    pb.close(); pg.close(); po.close()
 
 
 def test_sdm_descriptors_bit_exact(oracle, capi, ctx, synth):
