@@ -119,6 +119,21 @@ class fd_svm_train_info(C.Structure):
                 ("rho", C.c_double), ("objective", C.c_double)]
 
 
+class fd_liblinear_params(C.Structure):
+    _fields_ = [("C", C.c_double), ("weight_pos", C.c_double), ("weight_neg", C.c_double), ("eps", C.c_double), ("solver_tol", C.c_double),
+                ("bias", C.c_int32), ("max_iterations", C.c_int32), ("max_cg_steps", C.c_int32), ("launch_steps", C.c_int32)]
+
+
+class fd_liblinear_info(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("cg_steps", C.c_int32), ("converged", C.c_int32), ("stop", C.c_int32), ("n_active", C.c_int32),
+                ("trace_len", C.c_int32), ("objective", C.c_double), ("gnorm", C.c_double), ("gnorm0", C.c_double), ("delta", C.c_double)]
+
+
+class fd_liblinear_problem(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
+                ("weights", C.c_void_p), ("bias", C.c_void_p), ("w", C.c_void_p)]
+
+
 class fd_particles_arrays(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("x", "y", "size", "vx", "vy", "vsize", "weight", "score", "target", "cluster_id")]
 
@@ -320,6 +335,13 @@ _SIGS = {
     "fd_linear_svm_train_large": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_train_params), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.POINTER(fd_svm_train_info)]),
     "fd_linear_svm_train_large_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_liblinear_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_liblinear_params), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_liblinear_info)]),
+    "fd_liblinear_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fd_liblinear_params), C.c_void_p]),
+    "fd_liblinear_objective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_liblinear_params), C.c_void_p,
+                                         C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "fd_liblinear_train_limits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int)]),
     "fd_kernel_svm_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel), C.c_void_p, C.c_void_p]),
     "fd_kernel_svm_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(fd_svm_kernel),
                                       C.POINTER(fd_svm_train_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1515,6 +1537,78 @@ def linear_svm_train_batch(ctx, problems, **kw):
     prm = svm_train_params(**kw)
     ctx.check(lib().fd_linear_svm_train_batch(ctx.h, count, arr, C.byref(prm), infos))
     return [(ws[c], float(biases[c]), alphas[c], _svm_info(infos[c])) for c in range(count)]
+
+
+LIBLINEAR_MAX_N, LIBLINEAR_MAX_D, LIBLINEAR_SMALL_MAX_N = 1048576, 8192, 2048   # FD_LIBLINEAR_*
+FD_LL_STOP_GRADIENT, FD_LL_STOP_MAX_ITER, FD_LL_STOP_ACTRED_ZERO, FD_LL_STOP_ACTRED_SMALL, FD_LL_STOP_CG_CAP, FD_LL_STOP_NONFINITE = 1, 2, 3, 4, 5, 6
+
+
+def liblinear_params(C_=1.0, weight_pos=1.0, weight_neg=1.0, eps=0.0, solver_tol=0.0, bias=False, max_iterations=0, max_cg_steps=0,
+                     launch_steps=0, **kw):
+    """fd_liblinear_params; the bound may be given as C_ or C"""
+    return fd_liblinear_params(kw.pop("C", C_), weight_pos, weight_neg, eps, solver_tol, int(bias), max_iterations, max_cg_steps, launch_steps, **kw)
+
+
+def _liblinear_info(info):
+    return {name: getattr(info, name) for name, _ in fd_liblinear_info._fields_}
+
+
+def liblinear_train_limits(n_pos, n_neg, d, bias=False):
+    """fd_liblinear_train_limits (host only): (single_workgroup, slab_rows, scratch_bytes, lds_bytes); FdError for sizes the trainer
+    refuses.  FD_LIBLINEAR_SMALL_ROWS in the environment moves the rule (0: the multi-workgroup form for every size)."""
+    single, rows, scratch, lds = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+    rc = lib().fd_liblinear_train_limits(n_pos, n_neg, d, int(bias), C.byref(single), C.byref(rows), C.byref(scratch), C.byref(lds))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_liblinear_train_limits: invalid sizes (%d, %d, %d, %d)" % (n_pos, n_neg, d, int(bias)))
+    return bool(single.value), rows.value, scratch.value, lds.value
+
+
+def liblinear_train(ctx, x, n_pos, trace_cap=1024, **kw):
+    """fd_liblinear_train: (weights float32 (d,), bias, w float64 (d + bias,), trace int32 (k, 3), info dict); x: host array or
+    device tensor; keywords as liblinear_params"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    prm, info = liblinear_params(**kw), fd_liblinear_info()
+    weights, bias, w = np.zeros(d, np.float32), C.c_float(), np.zeros(d + prm.bias, np.float64)
+    trace = np.zeros((max(trace_cap, 1), 3), np.int32)
+    ctx.check(lib().fd_liblinear_train(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(prm), _ptr(weights), C.byref(bias), _ptr(w), _ptr(trace),
+                                       trace_cap, C.byref(info)))
+    return weights, bias.value, w, trace[:min(info.trace_len, trace_cap)], _liblinear_info(info)
+
+
+def liblinear_train_batch(ctx, problems, **kw):
+    """fd_liblinear_train_batch over [(x, n_pos), ...] (host arrays): a list of (weights, bias, w, info)"""
+    count = len(problems)
+    prm = liblinear_params(**kw)
+    xs = [_c(x, np.float32) for x, _ in problems]
+    ws = [np.zeros(x.shape[1], np.float32) for x in xs]
+    wds = [np.zeros(x.shape[1] + prm.bias, np.float64) for x in xs]
+    biases = np.zeros(max(count, 1), np.float32)
+    arr = (fd_liblinear_problem * max(count, 1))()
+    for c, (x, (_, n_pos)) in enumerate(zip(xs, problems)):
+        arr[c] = fd_liblinear_problem(x.ctypes.data, n_pos, x.shape[0] - n_pos, x.shape[1], 0, ws[c].ctypes.data, biases.ctypes.data + 4 * c,
+                                      wds[c].ctypes.data)
+    infos = (fd_liblinear_info * max(count, 1))()
+    ctx.check(lib().fd_liblinear_train_batch(ctx.h, count, arr, C.byref(prm), infos))
+    return [(ws[c], float(biases[c]), wds[c], _liblinear_info(infos[c])) for c in range(count)]
+
+
+def liblinear_objective(ctx, x, n_pos, w, s=None, **kw):
+    """fd_liblinear_objective: (f, g float64 (d + bias,), Hs or None) at the float64 point w; keywords as liblinear_params"""
+    keep, xp, n, d, dev = _x_and_pointer(x)
+    prm = liblinear_params(**kw)
+    w = _c(w, np.float64)
+    if w.shape != (d + prm.bias,):
+        raise ValueError("w has d + bias entries")
+    f, g = C.c_double(), np.zeros(d + prm.bias, np.float64)
+    hs = None
+    if s is not None:
+        s = _c(s, np.float64)
+        if s.shape != w.shape:
+            raise ValueError("s has d + bias entries")
+        hs = np.zeros_like(g)
+    ctx.check(lib().fd_liblinear_objective(ctx.h, xp, n_pos, n - n_pos, d, dev, C.byref(prm), _ptr(w), _ptr(s) if s is not None else None,
+                                           C.byref(f), _ptr(g), _ptr(hs) if hs is not None else None))
+    return f.value, g, hs
 
 
 def svm_kernel(kernel, p0=0.0, p1=0.0, p2=0.0):

@@ -6,8 +6,11 @@
 // classifier.cfg: the reference's INFO format with headTrackingApp's keys:
 //   kernel rbf        ; rbf | poly | hik | linear
 //   { gamma 0.1  alpha 0.05  constant 0  degree 2 }
-//   training binary   ; binary | one-class
+//   training binary   ; binary | one-class | liblinear
 //   { C 1  nu 0.5  compensateImbalance false  probabilistic false }
+// `training liblinear { C 1  bias false  staticNegativeExamples true { filename f  amount n  scale s } }` trains a
+// liblinear::LibLinearClassifier the way headTrackingApp's `classifier libLinear` does (HeadTracking.cpp:368-385); the kernel has
+// to be linear.  It prints the bias, the iterations and the CG steps.
 // --seed: std::srand's seed (default 1, the C library's own), which decides the shuffle of the sigmoid fit's five folds.
 // Writes the SvmClassifier text format, followed by the `Logistic a b` line when probabilistic (a = libsvm's probB, b = probA), and
 // prints rho, the number of support vectors and, when probabilistic, probA and probB with 17 digits.
@@ -15,6 +18,7 @@
 #include <cstdlib>
 #include <fstream>
 #include "fdcompat/ptree.hpp"
+#include "liblinear/LibLinearClassifier.hpp"
 #include "libsvm/LibSvmClassifier.hpp"
 
 using namespace classification;
@@ -52,7 +56,9 @@ int main(int argc, char** argv) {
         const string trainingType = pt.get<string>("training");
         const boost::property_tree::ptree& tp = pt.get_child("training");
         const bool oneClass = trainingType == "one-class";
-        if (!oneClass && trainingType != "binary") throw std::invalid_argument("invalid training type: " + trainingType);
+        const bool libLinear = trainingType == "liblinear";
+        if (libLinear && kernelType != "linear") throw std::invalid_argument("training liblinear needs kernel linear, not " + kernelType);
+        if (!oneClass && !libLinear && trainingType != "binary") throw std::invalid_argument("invalid training type: " + trainingType);
         const bool probabilistic = !oneClass && flag(tp, "probabilistic");
 
         std::ifstream in(pos[0]);
@@ -68,6 +74,21 @@ int main(int argc, char** argv) {
         }
         if (!in) throw std::runtime_error("truncated feature matrix: " + pos[0]);
 
+        if (libLinear) {
+            liblinear::LibLinearClassifier trainer(tp.get<double>("C", 1.0), flag(tp, "bias"));
+            if (tp.count("staticNegativeExamples") && flag(tp, "staticNegativeExamples")) {
+                const boost::property_tree::ptree& np = tp.get_child("staticNegativeExamples");
+                trainer.loadStaticNegatives(np.get<string>("filename"), np.get<int>("amount"), np.get<double>("scale"));
+            }
+            if (!trainer.retrain(positiveExamples, negativeExamples)) throw std::runtime_error("the classifier is not usable after the training");
+            const fd_liblinear_info& info = trainer.getLastTrainingInfo();
+            std::printf("bias %.9g\niterations %d\ncg_steps %d\nnegatives %d\n", trainer.getSvm()->getBias(), info.iterations, info.cg_steps,
+                        trainer.getLastNegativeCount());
+            std::ofstream out(pos[2]);
+            if (!out.is_open()) throw std::runtime_error("cannot write " + pos[2]);
+            trainer.getSvm()->store(out);
+            return 0;
+        }
         std::shared_ptr<libsvm::LibSvmClassifier> trainer =
             oneClass ? libsvm::LibSvmClassifier::createOneClassKernelSvm(kernel, tp.get<double>("nu", 0.5))
                      : libsvm::LibSvmClassifier::createBinaryKernelSvm(kernel, tp.get<double>("C", 1.0), flag(tp, "compensateImbalance"), probabilistic);

@@ -13,6 +13,7 @@
 //                        randomExampleCount 50 negativeScoreThreshold -1.0 positiveOverlapThreshold 0.5 negativeOverlapThreshold 0.5
 //                        adaptation position adaptationThreshold 0.75 exclusionThreshold 0.0
 //                        classifier { training { c 1  compensateImbalance 0  negativeCapacity 100 }  logisticA 0.00556  logisticB -2.95  threshold 0 } }
+//                        (training { type libLinear  c 1  bias 0  negativeCapacity 100 }: a liblinear::LibLinearClassifier; type libSvm is the default)
 //   }
 // the box is the target's bounding box (top left corner) in frame 0.  Prints "init <0|1> [x y w h]", then per further frame
 //   "frame <f> found <0|1> <x> <y> <w> <h> adapted <0|1> route <generic|device> ms <wall time of process()>"
@@ -29,6 +30,7 @@
 #include <iostream>
 #include "condensation/AdaptiveCondensationTracker.hpp"
 #include "condensation/CondensationTracker.hpp"
+#include "liblinear/LibLinearClassifier.hpp"
 #include "libsvm/LibSvmClassifier.hpp"
 #include "fdcompat/ptree.hpp"
 
@@ -143,8 +145,20 @@ int main(int argc, char** argv) {
         shared_ptr<ExtendedHogBasedMeasurementModel> model;
         if (ct.count("training")) {
             const ptree& tr = ct.get_child("training");
-            auto svm = libsvm::LibSvmClassifier::createBinarySvm(make_shared<LinearKernel>(), tr.get("c", 1.0), tr.get("compensateImbalance", 0) != 0);
-            svm->setNegativeExampleManagement(std::unique_ptr<ExampleManagement>(new AgeBasedExampleManagement(tr.get("negativeCapacity", 100))));
+            const string trainingType = tr.get("type", string("libSvm"));
+            shared_ptr<TrainableSvmClassifier> svm;
+            std::unique_ptr<ExampleManagement> negatives(new AgeBasedExampleManagement(tr.get("negativeCapacity", 100)));
+            if (trainingType == "libLinear") {
+                auto linear = make_shared<liblinear::LibLinearClassifier>(tr.get("c", 1.0), tr.get("bias", 0) != 0);
+                linear->setNegativeExampleManagement(std::move(negatives));
+                svm = linear;
+            } else if (trainingType == "libSvm") {
+                auto dual = libsvm::LibSvmClassifier::createBinarySvm(make_shared<LinearKernel>(), tr.get("c", 1.0), tr.get("compensateImbalance", 0) != 0);
+                dual->setNegativeExampleManagement(std::move(negatives));
+                svm = dual;
+            } else {
+                throw std::invalid_argument("tracker_app: invalid training type: " + trainingType);
+            }
             svm->getSvm()->setThreshold(ct.get("threshold", 0.0f));   // as ProbabilisticSvmClassifier::load reads it
             model = make_shared<ExtendedHogBasedMeasurementModel>(
                 make_shared<FixedTrainableProbabilisticSvmClassifier>(svm, ct.get("logisticA", 0.00556), ct.get("logisticB", -2.95)));

@@ -544,3 +544,47 @@ private:
 };
 
 }  // namespace libsvm
+
+// liblinear/LibLinearClassifier.hpp / .cpp:32-157: liblinear's L2R_L2LOSS_SVC (eps 0.01, no class weights) trained on the device
+// (fd_liblinear_train) on the positives, the negatives and the static negatives, in this order; the model is one
+// weight vector of the examples' shape with coefficient 1 and bias -w[d] (0 without the bias term), as LibLinearUtils extracts it.
+// Examples have to be continuous CV_32F Mats (std::invalid_argument otherwise), and a static negative is (float)(scale * value)
+// where the reference keeps the double.  loadStaticNegatives reads the reference's format -- one example per line, `value
+// separator value ...`, a separator being one character that is not white space -- with one difference: a character that can
+// begin a number (digit, sign, point) is not taken as a separator, so that values separated by spaces alone are read as they
+// stand (the reference's `>> separator` swallows the first character of the next value there).  A line whose length differs from
+// the examples' is std::invalid_argument at the training (the reference indexes out of range).
+namespace liblinear {
+
+class LibLinearClassifier : public classification::TrainableSvmClassifier {
+public:
+    explicit LibLinearClassifier(double c = 1, bool bias = false);
+    // at most maxNegatives lines of the file, each value multiplied by scale; a file that cannot be opened yields nothing
+    void loadStaticNegatives(const std::string& negativesFilename, int maxNegatives, double scale = 1);
+    bool retrain(const std::vector<cv::Mat>& newPositiveExamples, const std::vector<cv::Mat>& newNegativeExamples) override;
+    void reset() override;
+    void setPositiveExampleManagement(std::unique_ptr<classification::ExampleManagement> positiveExamples) {
+        this->positiveExamples = std::move(positiveExamples);
+    }
+    void setNegativeExampleManagement(std::unique_ptr<classification::ExampleManagement> negativeExamples) {
+        this->negativeExamples = std::move(negativeExamples);
+    }
+    // not in the reference: what the last training ran with and returned; the negatives include the static ones
+    const fd_liblinear_params& getLastTrainingParameters() const { return lastParams; }
+    const fd_liblinear_info& getLastTrainingInfo() const { return lastInfo; }
+    int getLastPositiveCount() const { return lastPositiveCount; }
+    int getLastNegativeCount() const { return lastNegativeCount; }
+    const std::vector<std::vector<float>>& getStaticNegatives() const { return staticNegativeExamples; }
+    // the values of one line of a static-negatives file, each times scale
+    static std::vector<float> parseStaticNegative(const std::string& line, double scale);
+private:
+    double c;
+    bool bias;
+    std::vector<std::vector<float>> staticNegativeExamples;
+    std::unique_ptr<classification::ExampleManagement> positiveExamples, negativeExamples;
+    fd_liblinear_params lastParams = {};
+    fd_liblinear_info lastInfo = {};
+    int lastPositiveCount = 0, lastNegativeCount = 0;
+};
+
+}  // namespace liblinear

@@ -4,7 +4,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cctype>
 #include <cstring>
+#include <fstream>
 #include <iomanip>
 #include <sstream>
 #include "detection/detection_all.hpp"
@@ -1703,6 +1705,98 @@ void LibSvmClassifier::reset() {   // :218-223
 }
 
 }  // namespace libsvm
+
+// =================================================================================================
+namespace liblinear {
+using classification::ExampleManagement;
+
+LibLinearClassifier::LibLinearClassifier(double c, bool bias)
+    : TrainableSvmClassifier(make_shared<classification::LinearKernel>()), c(c), bias(bias),
+      positiveExamples(new classification::UnlimitedExampleManagement()), negativeExamples(new classification::UnlimitedExampleManagement()) {}
+
+vector<float> LibLinearClassifier::parseStaticNegative(const string& line, double scale) {
+    vector<float> values;
+    std::istringstream in(line);
+    while (in.good()) {
+        double value = 0;   // what a failed read leaves behind, and the reference stores
+        in >> value;
+        values.push_back((float)(scale * value));
+        in >> std::ws;
+        if (!in.good()) break;
+        const int next = in.peek();
+        if (!(std::isdigit(next) || next == '+' || next == '-' || next == '.')) in.get();   // the separator
+    }
+    return values;
+}
+
+void LibLinearClassifier::loadStaticNegatives(const string& negativesFilename, int maxNegatives, double scale) {   // :48-84
+    std::ifstream file(negativesFilename.c_str());
+    if (!file.is_open()) return;
+    string line;
+    for (int negatives = 0; file.good() && negatives < maxNegatives && std::getline(file, line); ++negatives)
+        staticNegativeExamples.push_back(parseStaticNegative(line, scale));
+}
+
+bool LibLinearClassifier::retrain(const vector<Mat>& newPositiveExamples, const vector<Mat>& newNegativeExamples) {   // :86-110
+    if (newPositiveExamples.empty() && newNegativeExamples.empty()) return usable;
+    positiveExamples->add(newPositiveExamples);
+    negativeExamples->add(newNegativeExamples);
+    if (!positiveExamples->hasRequiredSize() || !negativeExamples->hasRequiredSize()) return usable;
+    vector<float> x;
+    int dimensions = -1, rows = 0, cols = 0, type = 0;
+    ExampleManagement* stores[2] = {positiveExamples.get(), negativeExamples.get()};
+    for (ExampleManagement* store : stores)   // createProblem (:120-148): positives, negatives, static negatives
+        for (auto it = store->iterator(); it->hasNext();) {
+            const Mat& example = it->next();
+            if (example.depth() != CV_32F) throw std::invalid_argument("LibLinearClassifier: examples have to be of depth CV_32F on this backend");
+            if (!example.isContinuous()) throw std::invalid_argument("LibLinearUtils: vector has to be continuous");
+            const int dim = (int)(example.total() * example.channels());
+            if (dimensions < 0) {
+                dimensions = dim;
+                rows = example.rows;
+                cols = example.cols;
+                type = example.type();
+            } else if (dim != dimensions) {
+                throw std::invalid_argument("LibLinearClassifier: examples have to have the same length");
+            }
+            x.insert(x.end(), example.ptr<float>(), example.ptr<float>() + dim);
+        }
+    for (const vector<float>& example : staticNegativeExamples) {
+        if (dimensions < 0 || (int)example.size() != dimensions)
+            throw std::invalid_argument("LibLinearClassifier: a static negative example has " + std::to_string(example.size()) + " values, the examples " +
+                                        std::to_string(std::max(dimensions, 0)));
+        x.insert(x.end(), example.begin(), example.end());
+    }
+    const int positiveCount = (int)positiveExamples->size();
+    const int negativeCount = (int)(negativeExamples->size() + staticNegativeExamples.size());
+    fd_liblinear_params params = {};   // the constructor's parameter (:32-46): L2R_L2LOSS_SVC, eps 0.01, no weights
+    params.C = c;
+    params.weight_pos = params.weight_neg = 1.0;
+    params.eps = 0.01;
+    params.bias = bias ? 1 : 0;
+    vector<float> weights(std::max(dimensions, 0));
+    float b = 0;
+    fd_liblinear_info info;
+    check(fd_liblinear_train(context(), x.data(), positiveCount, negativeCount, dimensions, 0, &params, weights.data(), &b, nullptr, nullptr, 0, &info));
+    Mat w(rows, cols, type);   // LibLinearUtils::extractSupportVectors: one vector of the examples' shape, coefficient 1
+    std::memcpy(w.data, weights.data(), sizeof(float) * weights.size());
+    svm->setSvmParameters(vector<Mat>{w}, vector<float>{1.f}, b);
+    lastParams = params;
+    lastInfo = info;
+    lastPositiveCount = positiveCount;
+    lastNegativeCount = negativeCount;
+    usable = true;
+    return usable;
+}
+
+void LibLinearClassifier::reset() {   // :150-155
+    usable = false;
+    svm->setSvmParameters(vector<Mat>(), vector<float>(), 0.0);
+    positiveExamples->clear();
+    negativeExamples->clear();
+}
+
+}  // namespace liblinear
 
 // =================================================================================================
 namespace detection {

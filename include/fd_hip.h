@@ -562,6 +562,66 @@ int fd_kernel_svm_cv_sigmoid(fd_ctx* ctx, const float* x, int n_pos, int n_neg, 
  * outside 0..n or a NULL array or result. */
 int fd_svm_sigmoid_train(int n, const double* dec_values, int n_pos, double* prob_a, double* prob_b, int* iterations, int* status);
 
+/* Primal L2-regularised L2-loss SVC training on the device: the model liblinear::LibLinearClassifier::train
+ * obtains from liblinear's train with L2R_L2LOSS_SVC (LibLinearClassifier.cpp:32-46,96-148; linear.cpp l2r_l2_svc_fun :191-340,
+ * train_one :2181-2230; tron.cpp TRON::tron / trcg :56-221) and LibLinearUtils turns into one weight vector
+ * (LibLinearUtils.cpp:70-105).  f(w) = 1/2 w.w + sum_i C_i max(0, 1 - y_i w.x_i)^2 is minimised by the trust-region Newton
+ * method, all in double; the state is one weight vector of d + bias doubles and the work is passes over the n x d float matrix,
+ * so there is no n x n term.  Rows are positives first; with bias a constant-1 feature is appended (never stored) and regularised
+ * like any weight.  TRON's scalar state machine is tron.cpp's, comparison for comparison; sums run in a fixed order that depends
+ * on (n, d, bias) only and differs from liblinear's sequential one, so the result is liblinear's up to rounding as long as no
+ * comparison of the run is closer than that rounding. */
+#define FD_LIBLINEAR_MAX_N 1048576
+#define FD_LIBLINEAR_MAX_D 8192          /* d + bias */
+#define FD_LIBLINEAR_SMALL_MAX_N 2048    /* rows the single-workgroup form (and a problem of a batch) takes */
+enum { FD_LL_STOP_NONE = 0, FD_LL_STOP_GRADIENT = 1, FD_LL_STOP_MAX_ITER = 2, FD_LL_STOP_ACTRED_ZERO = 3, FD_LL_STOP_ACTRED_SMALL = 4,
+       FD_LL_STOP_CG_CAP = 5, FD_LL_STOP_NONFINITE = 6 };
+typedef struct {
+    double C, weight_pos, weight_neg;  /* per-class C * weight; the reference passes 1, 1 */
+    double eps;                        /* liblinear's param->eps; 0 -> 0.01.  The solver runs with eps * max(min(pos, neg), 1) / n */
+    double solver_tol;                 /* > 0: TRON's eps directly (overrides eps) */
+    int32_t bias;                      /* 1: append the constant-1 feature, regularised */
+    int32_t max_iterations;            /* 0 -> 1000 (TRON's max_iter) */
+    int32_t max_cg_steps;              /* cap on the total number of CG steps (trcg has none); 0 -> 100 (d + bias) + 1000 */
+    int32_t launch_steps;              /* (pass, step) pairs per budget; 0 -> default */
+} fd_liblinear_params;
+typedef struct {
+    int32_t iterations, cg_steps, converged, stop;   /* accepted steps; CG steps in all; 1 for FD_LL_STOP_GRADIENT only; FD_LL_STOP_* */
+    int32_t n_active;                                 /* |I| at the returned w */
+    int32_t trace_len;                                /* outer iterations (trcg calls) run; min(trace_len, trace_cap) triples are written */
+    double objective, gnorm, gnorm0, delta;
+} fd_liblinear_info;
+typedef struct {
+    const float* x;                     /* n x d */
+    int32_t n_pos, n_neg, d, is_device; /* is_device: x is device memory */
+    float* weights;                     /* out, d floats (host) */
+    float* bias;                        /* out: (float)(-w[d]), 0 without the bias term; the decision value is dot(w, x) - bias */
+    double* w;                          /* out, d + bias doubles (host); may be NULL */
+} fd_liblinear_problem;
+/* weights: d floats (float)w; *bias_out as above; w (d + bias doubles), trace ({cg_steps, hit_boundary, accepted} per outer
+ * iteration, at most trace_cap int32 triples) and info may be NULL.  A run that stops for another reason than the gradient test
+ * (the iteration or CG cap, TRON's warnings, a non-finite f or |g|) returns the last accepted w with converged = 0 and is not an
+ * error.  FD_ERR_INVALID_ARGUMENT for what fd_linear_svm_train rejects (n up to FD_LIBLINEAR_MAX_N, d + bias up to
+ * FD_LIBLINEAR_MAX_D), eps < 0, solver_tol < 0, a bias other than 0 or 1, negative caps, or a required pointer that is NULL;
+ * FD_ERR_RUNTIME with a message when the scratch cannot be allocated. */
+int fd_liblinear_train(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_liblinear_params* params,
+                       float* weights, float* bias_out, double* w, int32_t* trace, int trace_cap, fd_liblinear_info* info);
+/* count independent problems (one per tracked target) of at most FD_LIBLINEAR_SMALL_MAX_N rows in one set of launches, one
+ * workgroup per problem; infos: count entries.  A problem's result is that of fd_liblinear_train in its single-workgroup form. */
+int fd_liblinear_train_batch(fd_ctx* ctx, int count, const fd_liblinear_problem* problems, const fd_liblinear_params* params,
+                             fd_liblinear_info* infos);
+/* fun, grad and -- when s is given -- Hv of l2r_l2_svc_fun at the caller's w (d + bias doubles), through the pass and reduction
+ * code of the trainer: *f, g (d + bias doubles), Hs (d + bias doubles; the active set is that of grad at w).  Hs may be NULL
+ * when s is. */
+int fd_liblinear_objective(fd_ctx* ctx, const float* x, int n_pos, int n_neg, int d, int is_device, const fd_liblinear_params* params,
+                           const double* w, const double* s, double* f, double* g, double* Hs);
+/* host only, no context: whether fd_liblinear_train takes the single-workgroup form for this size, the rows of a slab, the bytes
+ * of training scratch (without a host caller's x) and the LDS bytes of a workgroup; each may be NULL.  The rule:
+ * single workgroup for n <= FD_LIBLINEAR_SMALL_MAX_N and n (d + bias) <= 40960; FD_LIBLINEAR_SMALL_ROWS in the environment
+ * (0 .. FD_LIBLINEAR_SMALL_MAX_N) replaces the first limit, 0 selecting the multi-workgroup form for every size. */
+int fd_liblinear_train_limits(int n_pos, int n_neg, int d, int bias, int* single_workgroup, int* slab_rows, int64_t* scratch_bytes,
+                              int* lds_bytes);
+
 /* A particle set of the Condensation tracker resident on the device: two generations of up to `capacity` samples
  * as structure-of-arrays, bound to one fd_ehog_tracker.  A frame of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) +
  * ExtendedHogBasedMeasurementModel + FilteringStateExtractor(WeightedMeanStateExtractor) is fd_ehog_tracker_update,
