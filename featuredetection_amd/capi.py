@@ -144,6 +144,16 @@ class fd_particles_info(C.Structure):
                 ("bad_weight", C.c_int32), ("best_score", C.c_double), ("weight_sum", C.c_double)]
 
 
+class fd_flow_params(C.Structure):
+    _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double),
+                ("min_eig_threshold", C.c_double)]
+
+
+class fd_flow_motion(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("n_valid", C.c_int32), ("n_correct", C.c_int32), ("median_x", C.c_float), ("median_y", C.c_float),
+                ("median_ratio", C.c_float), ("order", C.c_void_p)]
+
+
 class fd_svm_train_problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
                 ("weights", C.c_void_p), ("bias", C.c_void_p), ("alpha", C.c_void_p)]
@@ -379,6 +389,17 @@ _SIGS = {
     "fd_particles_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
     "fd_particles_weigh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double]),
     "fd_particles_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_particles_info)]),
+    "fd_flow_default_params": (C.c_int, [C.POINTER(fd_flow_params)]),
+    "fd_flow_limits": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_flow_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(fd_flow_params), C.POINTER(C.c_void_p)]),
+    "fd_flow_destroy": (None, [C.c_void_p]),
+    "fd_flow_levels": (C.c_int, [C.c_void_p]),
+    "fd_flow_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "fd_flow_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_flow_track_fb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_debug_flow_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_flow_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_flow_median": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_flow_motion)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1451,6 +1472,122 @@ class Particles:
             e.info = out
             raise e
         return out
+
+
+FD_FLOW_MAX_POINTS, FD_FLOW_MAX_LEVELS = 16384, 8
+(FD_FLOW_EXIT_NONE, FD_FLOW_EXIT_SKIP_RANGE, FD_FLOW_EXIT_SKIP_EIGEN, FD_FLOW_EXIT_EPS, FD_FLOW_EXIT_OSCILLATION, FD_FLOW_EXIT_COUNT,
+ FD_FLOW_EXIT_LEFT_RANGE) = range(7)
+
+
+def flow_params(**kw):
+    """fd_flow_params: fd_flow_default_params (15 x 15 window, max_level 2, 30 iterations, epsilon 0.01, min_eig_threshold 1e-4) with overrides"""
+    p = fd_flow_params()
+    lib().fd_flow_default_params(C.byref(p))
+    for name, value in kw.items():
+        if name not in dict(fd_flow_params._fields_):
+            raise TypeError("fd_flow_params has no field %r" % name)
+        setattr(p, name, value)
+    return p
+
+
+def flow_limits():
+    """fd_flow_limits: (max points per call, smallest window side, largest window side)"""
+    a, b, c = C.c_int(), C.c_int(), C.c_int()
+    lib().fd_flow_limits(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def flow_grid(grid_w, grid_h, circle=True):
+    """fd_flow_grid: OpticalFlowTransitionModel's template points, float32 (n, 2)"""
+    n = C.c_int()
+    out = np.zeros((max(grid_w, 0) * max(grid_h, 0), 2), np.float32)
+    rc = lib().fd_flow_grid(grid_w, grid_h, int(bool(circle)), _ptr(out), len(out), C.byref(n))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_flow_grid(%d, %d)" % (grid_w, grid_h))
+    return out[:n.value].copy()
+
+
+def flow_median(points, fwd, bwd, fstatus, bstatus):
+    """fd_flow_median: dict(ok, n_valid, n_correct, median_x, median_y, median_ratio (np.float32 each), order int32 (n_valid,))"""
+    points, fwd, bwd = (_c(np.asarray(a, np.float32).reshape(-1, 2), np.float32) for a in (points, fwd, bwd))
+    fstatus, bstatus = _c(fstatus, np.uint8).ravel(), _c(bstatus, np.uint8).ravel()
+    n = len(points)
+    if not (len(fwd) == len(bwd) == len(fstatus) == len(bstatus) == n):
+        raise ValueError("the arrays of the tracked points have one length")
+    order = np.zeros(max(n, 1), np.int32)
+    m = fd_flow_motion()
+    m.order = order.ctypes.data
+    rc = lib().fd_flow_median(_ptr(points), _ptr(fwd), _ptr(bwd), _ptr(fstatus), _ptr(bstatus), n, C.byref(m))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_flow_median")
+    return dict(ok=bool(m.ok), n_valid=m.n_valid, n_correct=m.n_correct, median_x=np.float32(m.median_x), median_y=np.float32(m.median_y),
+                median_ratio=np.float32(m.median_ratio), order=order[:m.n_valid].copy())
+
+
+class Flow:
+    """fd_flow: the flow pyramids of the current and the previous frame (width x height) and pyramidal Lucas-Kanade between them"""
+
+    def __init__(self, ctx, width, height, params=None, **kw):
+        self.ctx = ctx
+        self.width, self.height = width, height
+        self.params = params if params is not None else flow_params(**kw)
+        self.h = C.c_void_p()
+        ctx.check(lib().fd_flow_create(ctx.h, width, height, C.byref(self.params), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().fd_flow_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def levels(self):
+        return lib().fd_flow_levels(self.h)
+
+    def update(self, image):
+        """the next frame: a uint8 array (h, w) or (h, w, 3) BGR on the host, or a torch uint8 tensor of that shape on the device"""
+        if hasattr(image, "data_ptr"):
+            if str(image.dtype) != "torch.uint8" or image.stride(-1) != 1 or (image.dim() == 3 and image.stride(1) != image.shape[2]):
+                raise ValueError("a device image is a uint8 tensor with dense rows")
+            shape, ptr, stride, dev = tuple(image.shape), C.c_void_p(image.data_ptr()), int(image.stride(0)), 1
+        else:
+            image = _c(image, np.uint8)
+            shape, ptr, stride, dev = image.shape, _ptr(image), int(image.strides[0]), 0
+        ch = 1 if len(shape) == 2 else shape[2]
+        if shape[:2] != (self.height, self.width):
+            raise ValueError("the image is %s, the flow was created for %d x %d" % (shape, self.width, self.height))
+        self.ctx.check(lib().fd_flow_update(self.ctx.h, self.h, ptr, ch, stride, dev))
+
+    def track(self, points, backward=False, trace=False):
+        """fd_flow_track: (out float32 (n, 2), status uint8 (n,)[, trace uint8 (n, FD_FLOW_MAX_LEVELS, 2) {steps, exit reason}])"""
+        points = _c(np.asarray(points, np.float32).reshape(-1, 2), np.float32)
+        n = len(points)
+        out, status = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        tr = np.zeros((n, FD_FLOW_MAX_LEVELS, 2), np.uint8) if trace else None
+        self.ctx.check(lib().fd_flow_track(self.ctx.h, self.h, int(bool(backward)), _ptr(points), n, _ptr(out), _ptr(status), _ptr(tr)))
+        return (out, status, tr) if trace else (out, status)
+
+    def track_fb(self, points):
+        """fd_flow_track_fb: (fwd, bwd float32 (n, 2), fstatus, bstatus uint8 (n,))"""
+        points = _c(np.asarray(points, np.float32).reshape(-1, 2), np.float32)
+        n = len(points)
+        fwd, bwd = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        fst, bst = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self.ctx.check(lib().fd_flow_track_fb(self.ctx.h, self.h, _ptr(points), n, _ptr(fwd), _ptr(bwd), _ptr(fst), _ptr(bst)))
+        return fwd, bwd, fst, bst
+
+    def level(self, level, previous=False):
+        """fd_debug_flow_level: (image uint8 (ph, pw), derivatives int16 (ph, pw, 2)) of a stored level, border included"""
+        w, h = C.c_int(), C.c_int()
+        self.ctx.check(lib().fd_debug_flow_level(self.ctx.h, self.h, int(bool(previous)), level, None, None, C.byref(w), C.byref(h)))
+        img, der = np.zeros((h.value, w.value), np.uint8), np.zeros((h.value, w.value, 2), np.int16)
+        self.ctx.check(lib().fd_debug_flow_level(self.ctx.h, self.h, int(bool(previous)), level, _ptr(img), _ptr(der), C.byref(w), C.byref(h)))
+        return img, der
 
 
 def svm_train_params(C_=1.0, weight_pos=1.0, weight_neg=1.0, eps=0.0, max_iterations=0, launch_iterations=0, **kw):

@@ -508,3 +508,88 @@ extern "C" int fd_surf_feature_length(int gradient_count, int cell_count) {
     if (fd_host_surf_lds_bytes(gradient_count, cell_count) > FD_SURF_LDS_BUDGET) return -1;
     return 4 * cell_count * cell_count;
 }
+
+// ---- OpticalFlowTransitionModel's host arithmetic; the tracking itself is optflow.hip ----
+
+// OpticalFlowTransitionModel.cpp:63-75, operation for operation: gridPoint's first value is formed in double (0.5 * gridX is a double
+// product) and stored as float, the value a row starts from afterwards in float
+extern "C" int fd_flow_grid(int grid_w, int grid_h, int circle, float* out_xy, int cap, int* n) {
+    if (grid_w < 1 || grid_h < 1 || grid_w > 1024 || grid_h > 1024 || cap < 0 || !n || (cap > 0 && !out_xy)) return FD_ERR_INVALID_ARGUMENT;
+    const float gridY = 1.f / static_cast<float>(grid_h + 2);
+    const float gridX = 1.f / static_cast<float>(grid_w + 2);
+    const float r = 0.5f - 0.5f * (gridX + gridY);
+    float px = (float)(-0.5f + 0.5 * gridX + gridX), py = (float)(-0.5f + 0.5 * gridY + gridY);
+    int count = 0;
+    for (int y = 0; y < grid_h; ++y) {
+        for (int x = 0; x < grid_w; ++x) {
+            if (!circle || px * px + py * py < r * r) {
+                if (count < cap) { out_xy[2 * count] = px; out_xy[2 * count + 1] = py; }
+                ++count;
+            }
+            px += gridX;
+        }
+        px = -0.5f + gridX / 2 + gridX;
+        py += gridY;
+    }
+    *n = count;
+    return count > cap ? FD_ERR_CAPACITY : FD_OK;
+}
+
+// OpticalFlowTransitionModel.cpp:114-170.  Not the reference's: pairs are ordered by (distance, index) -- its std::sort on the distance
+// alone leaves ties to the implementation; a pair whose distance is NaN counts as not tracked; with fewer than two correct pairs there
+// is no ratio to take a median of (the reference indexes an empty vector) and the result is not ok; a NaN ratio (two points that
+// coincide) sorts behind every number.
+extern "C" int fd_flow_median(const float* points, const float* fwd, const float* bwd, const uint8_t* fstatus, const uint8_t* bstatus, int n,
+                              fd_flow_motion* out) {
+    if (!out || n < 0 || (n > 0 && (!points || !fwd || !bwd || !fstatus || !bstatus))) return FD_ERR_INVALID_ARGUMENT;
+    out->ok = 0;
+    out->n_valid = out->n_correct = 0;
+    out->median_x = out->median_y = 0.f;
+    out->median_ratio = 1.f;
+    struct Pair { float d; int i; };
+    std::vector<Pair> pairs;
+    pairs.reserve(n);
+    for (int i = 0; i < n; ++i) {
+        if (!fstatus[i] || !bstatus[i]) continue;
+        const float dx = bwd[2 * i] - points[2 * i], dy = bwd[2 * i + 1] - points[2 * i + 1];
+        const float d = dx * dx + dy * dy;
+        if (d == d) pairs.push_back(Pair{d, i});
+    }
+    std::sort(pairs.begin(), pairs.end(), [](const Pair& a, const Pair& b) { return a.d < b.d || (a.d == b.d && a.i < b.i); });
+    out->n_valid = (int)pairs.size();
+    if (out->order)
+        for (size_t k = 0; k < pairs.size(); ++k) out->order[k] = pairs[k].i;
+    const size_t half = (size_t)n / 2;
+    if (pairs.size() < half) return FD_OK;
+    const float maxError = 1 * 0.5f;
+    size_t correct = 0;
+    while (correct < pairs.size() && !(pairs[correct].d > maxError)) ++correct;
+    out->n_correct = (int)correct;
+    if (correct < half || correct < 2) return FD_OK;
+    std::vector<float> xs(correct), ys(correct);
+    for (size_t k = 0; k < correct; ++k) {
+        const int i = pairs[k].i;
+        xs[k] = fwd[2 * i] - points[2 * i];
+        ys[k] = fwd[2 * i + 1] - points[2 * i + 1];
+    }
+    auto nanLast = [](float a, float b) { return a < b || (a == a && b != b); };
+    std::sort(xs.begin(), xs.end(), nanLast);
+    std::sort(ys.begin(), ys.end(), nanLast);
+    out->median_x = xs[correct / 2];
+    out->median_y = ys[correct / 2];
+    std::vector<float> ratios;
+    ratios.reserve(correct * (correct - 1) / 2);
+    for (size_t a = 0; a < correct; ++a) {
+        const int i = pairs[a].i;
+        for (size_t b = a + 1; b < correct; ++b) {
+            const int j = pairs[b].i;
+            const float bx = points[2 * i] - points[2 * j], by = points[2 * i + 1] - points[2 * j + 1];
+            const float ax = fwd[2 * i] - fwd[2 * j], ay = fwd[2 * i + 1] - fwd[2 * j + 1];
+            ratios.push_back((ax * ax + ay * ay) / (bx * bx + by * by));
+        }
+    }
+    std::nth_element(ratios.begin(), ratios.begin() + ratios.size() / 2, ratios.end(), nanLast);   // the element a full sort puts there
+    out->median_ratio = std::sqrt(ratios[ratios.size() / 2]);
+    out->ok = 1;
+    return FD_OK;
+}

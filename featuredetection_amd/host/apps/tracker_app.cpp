@@ -1,13 +1,17 @@
 // tracker_app -- the frame loop of the reference's adaptiveTrackingApp / headTrackingApp / trackingBenchmarkApp (TrackingBenchmark.cpp:489-510,553):
-// a condensation::AdaptiveCondensationTracker on ResamplingSampler(LowVarianceSampling, SimpleTransitionModel) or GridSampler, an
+// a condensation::AdaptiveCondensationTracker on ResamplingSampler(LowVarianceSampling, SimpleTransitionModel or OpticalFlowTransitionModel)
+// or GridSampler, an
 // ExtendedHogBasedMeasurementModel and FilteringStateExtractor(WeightedMeanStateExtractor).
 //   usage: tracker_app [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
 // config (boost info format), the `tracking` block of algorithm.cfg:
 //   tracking {
-//     transition simple { positionDeviation 10  sizeDeviation 0.1 }            (optical flow is not supported)
+//     transition simple { positionDeviation 10  sizeDeviation 0.1 }
+//     transition opticalFlow { positionDeviation 10  sizeDeviation 0.08  fallback simple { positionDeviation 12.8  sizeDeviation 0.1 } }
+//                                                                              (headTrackingApp/default.cfg:16-27; in place of the line above)
 //     adaptive { resampling { particleCount 800  randomRate 0.35  minSize 40  maxSize 200 } }
 //     grid { minSize 20 maxSize 80 sizeScale 1.2 stepSize 0.1 }                (optional: a GridSampler in place of the resampling sampler)
-//     initialCount 800   seed 1                                                (seed: the samplers' generators get seed, seed + 1, seed + 2)
+//     initialCount 800   seed 1                                                (seed: the samplers' generators get seed, seed + 1, seed + 2;
+//                                                                               seed + 1 is the simple model's, also as the fallback; the flow model's seed + 3)
 //     measurement ehog { cellSize 5 cellCount 35 signedAndUnsigned 0 interpolateBins 0 interpolateCells 1 octaveLayerCount 5
 //                        rejectionThreshold -1.5 useSlidingWindow 1 conservativeReInit 0 negativeExampleCount 10 initialNegativeExampleCount 50
 //                        randomExampleCount 50 negativeScoreThreshold -1.0 positiveOverlapThreshold 0.5 negativeOverlapThreshold 0.5
@@ -17,6 +21,10 @@
 //   }
 // the box is the target's bounding box (top left corner) in frame 0.  Prints "init <0|1> [x y w h]", then per further frame
 //   "frame <f> found <0|1> <x> <y> <w> <h> adapted <0|1> route <generic|device> ms <wall time of process()>"
+// With `transition opticalFlow` every frame line is followed by "flow <0|1> tracked <0|1> valid <n> correct <m> motion <x> <y> <ratio>": whether
+// the flow (1) or the fallback (0) predicted the frame, whether points were tracked at all, the pairs tracked both ways, those of them
+// that count as correct, and the median flow (%.9g).  With --dump the draws of the transition model follow it: "z <zx> <zy> <zsize>" per
+// resampled sample on a flow frame (the normal draws), "d ..." as below on a fallback frame.
 // With --dump every frame is followed by "draws u <0|1> <u> copies <n> fresh <m>", one "d <dx> <dy> <factor>" per copy, one "f <x> <y>
 // <size>" per random sample, "samples <n>" and one "s <x> <y> <size> <vx> <vy> <vsize> <weight> <score> <target> <clusterId>" per sample
 // (%.17g / %.9g: the values round-trip), so that tests/condensation_model.py can replay the run.
@@ -30,6 +38,7 @@
 #include <iostream>
 #include "condensation/AdaptiveCondensationTracker.hpp"
 #include "condensation/CondensationTracker.hpp"
+#include "condensation/OpticalFlowTransitionModel.hpp"
 #include "liblinear/LibLinearClassifier.hpp"
 #include "libsvm/LibSvmClassifier.hpp"
 #include "fdcompat/ptree.hpp"
@@ -58,11 +67,31 @@ static cv::Mat read_pnm(const string& path) {
     return img;
 }
 
+// the optical-flow transition model of a sampler, if it has one
+static shared_ptr<OpticalFlowTransitionModel> flow_model(const shared_ptr<Sampler>& sampler) {
+    auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
+    return resampling ? std::dynamic_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel()) : nullptr;
+}
+
+static void print_flow(const OpticalFlowTransitionModel& flow) {
+    const fd_flow_motion& m = flow.getLastMotion();
+    std::printf("flow %d tracked %d valid %d correct %d motion %.9g %.9g %.9g\n", flow.usedFlow() ? 1 : 0, flow.getPoints().empty() ? 0 : 1, m.n_valid, m.n_correct,
+                m.median_x, m.median_y, m.median_ratio);
+}
+
 static void dump(const shared_ptr<Sampler>& sampler, const std::vector<shared_ptr<Sample>>& samples) {
     if (auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler)) {
         const ResamplingSampler::Draws& d = resampling->getLastDraws();
-        std::printf("draws u %d %.17g copies %zu fresh %zu\n", d.hasU ? 1 : 0, d.u, d.diffusion.size() / 3, d.fresh.size() / 3);
-        for (size_t i = 0; i + 2 < d.diffusion.size(); i += 3) std::printf("d %.17g %.17g %.17g\n", d.diffusion[i], d.diffusion[i + 1], d.diffusion[i + 2]);
+        if (auto flow = flow_model(sampler)) {   // the sampler does not know this model's draws: the copies are what is not fresh
+            auto simple = std::dynamic_pointer_cast<SimpleTransitionModel>(flow->getFallback());
+            const std::vector<double> none;
+            const std::vector<double>& t = flow->usedFlow() ? flow->getLastDraws() : (simple ? simple->getLastDiffusion() : none);
+            std::printf("draws u %d %.17g copies %zu fresh %zu\n", d.hasU ? 1 : 0, d.u, samples.size() - d.fresh.size() / 3, d.fresh.size() / 3);
+            for (size_t i = 0; i + 2 < t.size(); i += 3) std::printf("%s %.17g %.17g %.17g\n", flow->usedFlow() ? "z" : "d", t[i], t[i + 1], t[i + 2]);
+        } else {
+            std::printf("draws u %d %.17g copies %zu fresh %zu\n", d.hasU ? 1 : 0, d.u, d.diffusion.size() / 3, d.fresh.size() / 3);
+            for (size_t i = 0; i + 2 < d.diffusion.size(); i += 3) std::printf("d %.17g %.17g %.17g\n", d.diffusion[i], d.diffusion[i + 1], d.diffusion[i + 2]);
+        }
         for (size_t i = 0; i + 2 < d.fresh.size(); i += 3) std::printf("f %d %d %d\n", d.fresh[i], d.fresh[i + 1], d.fresh[i + 2]);
     }
     std::printf("samples %zu\n", samples.size());
@@ -129,15 +158,25 @@ int main(int argc, char** argv) {
         ptree all;
         boost::property_tree::read_info(string(argv[a]), all);
         const ptree& pt = all.get_child("tracking");
-        if (pt.get("transition", string("simple")) != "simple") throw std::invalid_argument("tracker_app: only `transition simple` is supported");
         const unsigned seed = (unsigned)pt.get("seed", 1);
+        const string transition = pt.get("transition", string("simple"));
+        shared_ptr<TransitionModel> transitionModel;
+        if (transition == "simple") {
+            transitionModel = make_shared<SimpleTransitionModel>(pt.get("transition.positionDeviation", 10.0), pt.get("transition.sizeDeviation", 0.1), seed + 1);
+        } else if (transition == "opticalFlow") {   // HeadTracking.cpp:545-550
+            if (pt.get("transition.fallback", string("simple")) != "simple") throw std::invalid_argument("tracker_app: only `fallback simple` is supported");
+            auto fallback = make_shared<SimpleTransitionModel>(pt.get("transition.fallback.positionDeviation", 12.8), pt.get("transition.fallback.sizeDeviation", 0.1), seed + 1);
+            transitionModel = make_shared<OpticalFlowTransitionModel>(fallback, pt.get("transition.positionDeviation", 10.0), pt.get("transition.sizeDeviation", 0.08),
+                                                                      cv::Size(10, 10), true, cv::Size(15, 15), 2, seed + 3);
+        } else {
+            throw std::invalid_argument("tracker_app: invalid transition model type: " + transition);
+        }
         shared_ptr<Sampler> sampler;
         if (pt.count("grid"))
             sampler = make_shared<GridSampler>(pt.get("grid.minSize", 20), pt.get("grid.maxSize", 80), (float)pt.get("grid.sizeScale", 1.2), (float)pt.get("grid.stepSize", 0.1));
         else
             sampler = make_shared<ResamplingSampler>(pt.get("adaptive.resampling.particleCount", 800), pt.get("adaptive.resampling.randomRate", 0.35),
-                                                     make_shared<LowVarianceSampling>(seed),
-                                                     make_shared<SimpleTransitionModel>(pt.get("transition.positionDeviation", 10.0), pt.get("transition.sizeDeviation", 0.1), seed + 1),
+                                                     make_shared<LowVarianceSampling>(seed), transitionModel,
                                                      pt.get("adaptive.resampling.minSize", 40), pt.get("adaptive.resampling.maxSize", 200), seed + 2);
         const ptree& mt = pt.get_child("measurement");
         if (pt.get("measurement", string("ehog")) != "ehog") throw std::invalid_argument("tracker_app: only `measurement ehog` is supported");
@@ -194,6 +233,7 @@ int main(int argc, char** argv) {
             const cv::Rect r = found ? *found : cv::Rect();
             std::printf("frame %d found %d %d %d %d %d adapted %d route %s ms %.3f\n", f - a - 5, found ? 1 : 0, r.x, r.y, r.width, r.height,
                         tracker.hasAdapted() ? 1 : 0, tracker.getLastRoute() == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
+            if (auto flow = flow_model(tracker.getSampler())) print_flow(*flow);
             if (dumping) dump(tracker.getSampler(), tracker.getSamples());
         }
         return 0;

@@ -291,6 +291,66 @@ private:
     std::normal_distribution<> distribution;
 };
 
+// OpticalFlowTransitionModel.hpp / .cpp:27-191 on one fd_flow: the pyramids of the previous and the current frame
+// live on the device, predict is fd_flow_update, fd_flow_track_fb (forward, then backward from the forward results) and
+// fd_flow_median, then the motion of every sample on the host.  The fallback predicts exactly where the reference's does: no previous
+// frame, no target, fewer than points / 2 pairs tracked both ways, fewer than points / 2 of them with a squared forward-backward
+// distance of at most 0.5; the frame becomes the previous one before either of the late fallbacks, as in the reference.
+// Not the reference's: std::mt19937(seed) + std::normal_distribution<> in place of boost::mt19937(time(0)) -- three draws per sample in
+// the order x, y, size; pairs of equal forward-backward distance are ordered by point index (the reference's std::sort on the
+// distance alone leaves them to the implementation); with fewer than two correct pairs (a grid of fewer than four points) the
+// fallback predicts, where the reference indexes an empty vector; the flow handle is rebuilt when the frame size changes; drawFlow
+// is left out (fdcompat has no drawing).  usedFlow / getLastMotion / getLastDraws tell what the last predict did.
+class OpticalFlowTransitionModel : public TransitionModel {
+public:
+    explicit OpticalFlowTransitionModel(std::shared_ptr<TransitionModel> fallback, double positionDeviation, double sizeDeviation,
+                                        cv::Size gridSize = cv::Size(10, 10), bool circle = true, cv::Size windowSize = cv::Size(15, 15), int maxLevel = 2,
+                                        unsigned int seed = std::mt19937::default_seed);
+    ~OpticalFlowTransitionModel();
+    OpticalFlowTransitionModel(const OpticalFlowTransitionModel&) = delete;
+    OpticalFlowTransitionModel& operator=(const OpticalFlowTransitionModel&) = delete;
+    void init(const cv::Mat& image) override;
+    void predict(std::vector<std::shared_ptr<Sample>>& samples, const cv::Mat& image, const std::shared_ptr<Sample> target) override;
+    double getPositionDeviation() const { return positionDeviation; }
+    void setPositionDeviation(double deviation) { positionDeviation = deviation; }
+    double getSizeDeviation() const { return sizeDeviation; }
+    void setSizeDeviation(double deviation) { sizeDeviation = deviation; }
+    std::shared_ptr<TransitionModel> getFallback() const { return fallback; }
+    const std::vector<cv::Point2f>& getTemplatePoints() const { return templatePoints; }
+    const std::vector<cv::Point2f>& getPoints() const { return points; }                 // of the last predict; empty when it did not track
+    const std::vector<cv::Point2f>& getForwardPoints() const { return forwardPoints; }
+    const std::vector<cv::Point2f>& getBackwardPoints() const { return backwardPoints; }
+    // the point indices of the correct flows, ordered by forward-backward distance (squaredDistances[0 .. correctFlowCount) of the reference)
+    const std::vector<int>& getCorrectFlowIndices() const { return correctFlowIndices; }
+    bool usedFlow() const { return flowUsed; }                                           // the last predict moved the samples by the flow
+    const fd_flow_motion& getLastMotion() const { return lastMotion; }                   // of the last predict; all zero when it did not track (order is not set)
+    const std::vector<double>& getLastDraws() const { return lastDraws; }                // the normal draws of the last flow prediction, 3 per sample
+    // predict for one sample with its three normal draws
+    static void apply(Sample& sample, float medianX, float medianY, float medianRatio, double positionDeviation, double sizeDeviation, const double z[3]);
+protected:
+    // the frame becomes the current one (fd_flow_update); tracks `points` forward and the results backward (fd_flow_track_fb)
+    virtual void updatePyramid(const cv::Mat& image);
+    virtual void trackPoints(const std::vector<cv::Point2f>& points, std::vector<cv::Point2f>& forwardPoints, std::vector<cv::Point2f>& backwardPoints,
+                             std::vector<cv::uchar>& forwardStatus, std::vector<cv::uchar>& backwardStatus);
+private:
+    std::shared_ptr<TransitionModel> fallback;
+    std::vector<cv::Point2f> templatePoints;
+    cv::Size gridSize, windowSize;
+    int maxLevel;
+    fd_flow* flow = nullptr;
+    int flowWidth = 0, flowHeight = 0;
+    bool hasPrevious = false;
+    std::vector<cv::Point2f> points, forwardPoints, backwardPoints;
+    std::vector<cv::uchar> forwardStatus, backwardStatus;
+    std::vector<int> correctFlowIndices;
+    fd_flow_motion lastMotion{};
+    bool flowUsed = false;
+    std::vector<double> lastDraws;
+    double positionDeviation, sizeDeviation;
+    std::mt19937 generator;
+    std::normal_distribution<> distribution;
+};
+
 // ResamplingSampler.hpp / .cpp:24-71.  std::mt19937(seed): per random sample one std::uniform_real_distribution<> draw (the size), then
 // std::uniform_int_distribution<int>(0, cols - size) and (0, rows - size).
 class ResamplingSampler : public Sampler {

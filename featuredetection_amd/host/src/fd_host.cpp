@@ -3215,6 +3215,132 @@ void SimpleTransitionModel::predict(vector<shared_ptr<Sample>>& samples, const M
     }
 }
 
+OpticalFlowTransitionModel::OpticalFlowTransitionModel(shared_ptr<TransitionModel> fallback, double positionDeviation, double sizeDeviation,
+                                                       cv::Size gridSize, bool circle, cv::Size windowSize, int maxLevel, unsigned int seed)
+    : fallback(fallback), gridSize(gridSize), windowSize(windowSize), maxLevel(maxLevel), positionDeviation(positionDeviation),
+      sizeDeviation(sizeDeviation), generator(seed), distribution() {
+    if (!fallback) throw std::invalid_argument("OpticalFlowTransitionModel: the fallback model is missing");
+    int minWindow = 0, maxWindow = 0;
+    fd_flow_limits(nullptr, &minWindow, &maxWindow);   // host only, like the grid and the median below: no context, nothing to check() against
+    if (windowSize.width < minWindow || windowSize.width > maxWindow || windowSize.height < minWindow || windowSize.height > maxWindow)
+        throw std::invalid_argument("OpticalFlowTransitionModel: the window size must be " + std::to_string(minWindow) + " .. " + std::to_string(maxWindow) + " per side");
+    if (maxLevel < 0 || maxLevel >= FD_FLOW_MAX_LEVELS) throw std::invalid_argument("OpticalFlowTransitionModel: the maximal level must be 0 .. " + std::to_string(FD_FLOW_MAX_LEVELS - 1));
+    int n = 0;
+    if (gridSize.width < 1 || gridSize.height < 1 || fd_flow_grid(gridSize.width, gridSize.height, circle ? 1 : 0, nullptr, 0, &n) == FD_ERR_INVALID_ARGUMENT ||
+        n > FD_FLOW_MAX_POINTS)
+        throw std::invalid_argument("OpticalFlowTransitionModel: invalid grid size");
+    vector<float> xy(2 * (size_t)n);
+    if (n > 0 && fd_flow_grid(gridSize.width, gridSize.height, circle ? 1 : 0, xy.data(), n, &n) != FD_OK) throw std::logic_error("OpticalFlowTransitionModel: fd_flow_grid failed");
+    for (int i = 0; i < n; ++i) templatePoints.push_back(cv::Point2f(xy[2 * i], xy[2 * i + 1]));
+    lastMotion.median_ratio = 1.f;
+}
+
+OpticalFlowTransitionModel::~OpticalFlowTransitionModel() { fd_flow_destroy(flow); }
+
+void OpticalFlowTransitionModel::updatePyramid(const Mat& image) {
+    if (image.empty() || image.depth() != CV_8U || (image.channels() != 1 && image.channels() != 3))
+        throw std::invalid_argument("OpticalFlowTransitionModel: the image must be CV_8UC1 or CV_8UC3");
+    if (!flow || flowWidth != image.cols || flowHeight != image.rows) {   // another frame size: nothing of the previous frame can be used
+        fd_flow_destroy(flow);
+        flow = nullptr;
+        hasPrevious = false;
+        fd_flow_params params;
+        check(fd_flow_default_params(&params));
+        params.win_w = windowSize.width;
+        params.win_h = windowSize.height;
+        params.max_level = maxLevel;
+        check(fd_flow_create(context(), image.cols, image.rows, &params, &flow));
+        flowWidth = image.cols;
+        flowHeight = image.rows;
+    }
+    check(fd_flow_update(context(), flow, image.data, image.channels(), (int)image.step, 0));
+}
+
+void OpticalFlowTransitionModel::trackPoints(const vector<cv::Point2f>& points, vector<cv::Point2f>& forwardPoints, vector<cv::Point2f>& backwardPoints,
+                                             vector<uchar>& forwardStatus, vector<uchar>& backwardStatus) {
+    static_assert(sizeof(cv::Point2f) == 2 * sizeof(float), "Point2f is two floats");
+    const size_t n = points.size();
+    forwardPoints.resize(n);
+    backwardPoints.resize(n);
+    forwardStatus.resize(n);
+    backwardStatus.resize(n);
+    if (n == 0) return;
+    check(fd_flow_track_fb(context(), flow, &points[0].x, (int)n, &forwardPoints[0].x, &backwardPoints[0].x, forwardStatus.data(), backwardStatus.data()));
+}
+
+void OpticalFlowTransitionModel::init(const Mat& image) {   // .cpp:86-88
+    updatePyramid(image);
+    hasPrevious = true;
+}
+
+void OpticalFlowTransitionModel::apply(Sample& sample, float medianX, float medianY, float medianRatio, double positionDeviation, double sizeDeviation,
+                                       const double z[3]) {   // .cpp:174-189
+    double vx = medianX;
+    double vy = medianY;
+    double vs = medianRatio;
+    vx += positionDeviation * z[0];
+    vy += positionDeviation * z[1];
+    vs *= pow(2, sizeDeviation * z[2]);
+    sample.setVx(static_cast<int>(std::round(vx)));
+    sample.setVy(static_cast<int>(std::round(vy)));
+    sample.setVSize(vs);
+    sample.setX(sample.getX() + sample.getVx());
+    sample.setY(sample.getY() + sample.getVy());
+    sample.setSize(static_cast<int>(std::round(sample.getSize() * sample.getVSize())));   // int * float: a float product
+}
+
+void OpticalFlowTransitionModel::predict(vector<shared_ptr<Sample>>& samples, const Mat& image, const shared_ptr<Sample> target) {   // .cpp:90-191
+    points.clear();
+    forwardPoints.clear();
+    backwardPoints.clear();
+    forwardStatus.clear();
+    backwardStatus.clear();
+    correctFlowIndices.clear();
+    lastDraws.clear();
+    flowUsed = false;
+    lastMotion = fd_flow_motion{};
+    lastMotion.median_ratio = 1.f;
+
+    const bool hadPrevious = hasPrevious;
+    updatePyramid(image);   // may reset hasPrevious (another frame size)
+    if (!(hadPrevious && hasPrevious) || !target) {   // no previous pyramid or no current target
+        hasPrevious = true;
+        return fallback->predict(samples, image, target);
+    }
+
+    for (const cv::Point2f& point : templatePoints)
+        points.push_back(cv::Point2f(target->getWidth() * point.x + target->getX(), target->getHeight() * point.y + target->getY()));
+    trackPoints(points, forwardPoints, backwardPoints, forwardStatus, backwardStatus);
+    if (forwardPoints.size() != points.size() || backwardPoints.size() != points.size() || forwardStatus.size() != points.size() ||
+        backwardStatus.size() != points.size())
+        throw std::logic_error("OpticalFlowTransitionModel: trackPoints must fill one entry per point");
+
+    const int n = (int)points.size();
+    vector<int32_t> order(std::max(n, 1));
+    fd_flow_motion motion{};
+    motion.order = order.data();
+    static const float none[2] = {0.f, 0.f};
+    static const uchar noStatus[1] = {0};
+    if (fd_flow_median(n ? &points[0].x : none, n ? &forwardPoints[0].x : none, n ? &backwardPoints[0].x : none, n ? forwardStatus.data() : noStatus,
+                       n ? backwardStatus.data() : noStatus, n, &motion) != FD_OK)
+        throw std::logic_error("OpticalFlowTransitionModel: fd_flow_median failed");
+    lastMotion = motion;
+    lastMotion.order = nullptr;
+    correctFlowIndices.assign(order.begin(), order.begin() + motion.n_correct);
+    if (!motion.ok) return fallback->predict(samples, image, target);   // too few points tracked, or too few correct correspondences
+
+    flowUsed = true;
+    lastDraws.reserve(3 * samples.size());
+    for (shared_ptr<Sample>& sample : samples) {
+        double z[3];
+        z[0] = distribution(generator);
+        z[1] = distribution(generator);
+        z[2] = distribution(generator);
+        lastDraws.insert(lastDraws.end(), z, z + 3);
+        apply(*sample, motion.median_x, motion.median_y, motion.median_ratio, positionDeviation, sizeDeviation, z);
+    }
+}
+
 ResamplingSampler::ResamplingSampler(unsigned int count, double randomRate, shared_ptr<ResamplingAlgorithm> resamplingAlgorithm,
                                      shared_ptr<TransitionModel> transitionModel, int minSize, int maxSize, unsigned int seed)
     : count(count), randomRate(randomRate), resamplingAlgorithm(resamplingAlgorithm), transitionModel(transitionModel), minSize(minSize), maxSize(maxSize),

@@ -688,6 +688,69 @@ int fd_particles_weigh(fd_ctx* ctx, fd_particles* p, double logistic_a, double l
  * With bad_weight set no state is reported and FD_ERR_RUNTIME is returned (*out is filled). */
 int fd_particles_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out);
 
+/* Pyramidal Lucas-Kanade optical flow for condensation::OpticalFlowTransitionModel (OpticalFlowTransitionModel.cpp:86-111):
+ * cv::buildOpticalFlowPyramid(gray, pyramid, winSize, maxLevel, true, BORDER_REPLICATE, BORDER_REPLICATE) and
+ * cv::calcOpticalFlowPyrLK(previous, current, points, ..., winSize, maxLevel) with OpenCV's default criteria, as DESIGN.md 4.14
+ * defines their arithmetic.  A handle holds the padded levels and padded Scharr derivatives of two frames of one size (current and
+ * previous); one wavefront tracks one point through all levels. */
+typedef struct fd_flow fd_flow;
+#define FD_FLOW_MAX_POINTS 16384
+#define FD_FLOW_MIN_WINDOW 3
+#define FD_FLOW_MAX_WINDOW 31
+#define FD_FLOW_MAX_LEVELS 8            /* max_level 0 .. 7 */
+typedef struct {
+    int32_t win_w, win_h;               /* search window, FD_FLOW_MIN_WINDOW .. FD_FLOW_MAX_WINDOW per side */
+    int32_t max_level;                  /* 0-based top level asked for; fewer are built when a level would not exceed the window */
+    int32_t max_count;                  /* iterations per level, clamped to 0 .. 100 */
+    double epsilon;                     /* clamped to 0 .. 10, squared before use */
+    double min_eig_threshold;
+} fd_flow_params;
+/* host only: 15, 15, 2, 30, 0.01, 1e-4 (OpticalFlowTransitionModel's and calcOpticalFlowPyrLK's defaults) */
+int fd_flow_default_params(fd_flow_params* out);
+/* host only: the largest n of fd_flow_track / _track_fb and the window bounds; each may be NULL */
+int fd_flow_limits(int* max_points, int* min_window, int* max_window);
+/* FD_ERR_INVALID_ARGUMENT for a window outside the bounds, max_level outside 0 .. FD_FLOW_MAX_LEVELS - 1 or an empty image */
+int fd_flow_create(fd_ctx* ctx, int width, int height, const fd_flow_params* params, fd_flow** out);
+void fd_flow_destroy(fd_flow* flow);
+int fd_flow_levels(const fd_flow* flow);   /* levels built: level l + 1 exists while its width > win_w and its height > win_h */
+/* The current pyramid becomes the previous one and the image's pyramid the current one.  image: width x height, channels 1 (gray) or
+ * 3 (BGR, converted as the image pyramid converts), rows `stride` bytes apart (0: width * channels), host or device memory.  Queued
+ * on the context's stream. */
+int fd_flow_update(fd_ctx* ctx, fd_flow* flow, const uint8_t* image, int channels, int stride, int on_device);
+/* what ended a level of a point (trace) */
+enum {
+    FD_FLOW_EXIT_NONE = 0,          /* the level does not exist */
+    FD_FLOW_EXIT_SKIP_RANGE = 1,    /* the window of the point lies outside the level: skipped (status 0 at level 0) */
+    FD_FLOW_EXIT_SKIP_EIGEN = 2,    /* smallest eigenvalue under the threshold or determinant under FLT_EPSILON: skipped (status 0 at level 0) */
+    FD_FLOW_EXIT_EPS = 3,           /* a step of squared length <= epsilon^2 */
+    FD_FLOW_EXIT_OSCILLATION = 4,   /* two steps that cancel: half of the last one is taken back */
+    FD_FLOW_EXIT_COUNT = 5,         /* max_count steps */
+    FD_FLOW_EXIT_LEFT_RANGE = 6     /* the window left the level during the iterations (status 0 at level 0) */
+};
+/* Tracks n <= FD_FLOW_MAX_POINTS points {x, y} from the previous frame to the current one (backward 0) or from the current to the
+ * previous (backward 1).  out_xy: 2 n floats; status: n bytes; trace (may be NULL): per point and level l < FD_FLOW_MAX_LEVELS
+ * the two bytes {steps taken, exit reason}.  Waits for the results.  FD_ERR_RUNTIME before the second fd_flow_update. */
+int fd_flow_track(fd_ctx* ctx, fd_flow* flow, int backward, const float* pts_xy, int n, float* out_xy, uint8_t* status, uint8_t* trace);
+/* forward, then backward from the forward results (all of them, as OpticalFlowTransitionModel.cpp:110-111 does): one submission, one
+ * wait.  fwd, bwd: 2 n floats each. */
+int fd_flow_track_fb(fd_ctx* ctx, fd_flow* flow, const float* pts_xy, int n, float* fwd, float* bwd, uint8_t* fstatus, uint8_t* bstatus);
+/* test hook: level `level` of the current (which 0) or previous (1) frame as it is stored, with its border: *w x *h bytes into
+ * image_out and 2 * *w * *h int16 {dx, dy} into deriv_out (either may be NULL) */
+int fd_debug_flow_level(fd_ctx* ctx, fd_flow* flow, int which, int level, uint8_t* image_out, int16_t* deriv_out, int* w, int* h);
+/* host only: the template grid of OpticalFlowTransitionModel (.cpp:63-75) for grid_w x grid_h points, relative to the target's centre
+ * in units of its size.  out_xy: up to cap points; *n the number of points (FD_ERR_CAPACITY when cap is smaller). */
+int fd_flow_grid(int grid_w, int grid_h, int circle, float* out_xy, int cap, int* n);
+typedef struct {
+    int32_t ok;                        /* the median flow is usable: enough valid and enough correct pairs */
+    int32_t n_valid, n_correct;        /* pairs with both status flags; of those, with squared forward-backward distance <= 0.5f */
+    float median_x, median_y;          /* medians of the correct flows */
+    float median_ratio;                /* sqrt of the median ratio of squared point distances after / before */
+    int32_t* order;                    /* caller's buffer of n entries or NULL: the valid indices by (distance, index); the first n_correct are the correct ones */
+} fd_flow_motion;
+/* host only: OpticalFlowTransitionModel.cpp:114-170 on n tracked points */
+int fd_flow_median(const float* points, const float* fwd, const float* bwd, const uint8_t* fstatus, const uint8_t* bstatus, int n,
+                   fd_flow_motion* out);
+
 /* detection::AggregatedFeaturesDetector (AggregatedFeaturesDetector.cpp:37-128) with imageFilter = GrayscaleFilter,
  * layerFilter = FhogFilter on an extraction::AggregatedFeaturesExtractor (AggregatedFeaturesExtractor.cpp:34-130): a linear
  * SVM convolved over the FHOG cell pyramid (ConvolutionFilter.cpp:27-43), windows with score > threshold, bounds through
