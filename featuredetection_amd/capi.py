@@ -12,7 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FD_HIP_LIB", os.path.join(_HERE, "libfd_hip.so"))   # FD_HIP_LIB: a differently built libfd_hip.so (A/B runs of kernel variants)
 
 FD_OK, FD_ERR_INVALID_ARGUMENT, FD_ERR_RUNTIME, FD_ERR_LOGIC, FD_ERR_HIP, FD_ERR_CAPACITY, FD_ERR_DEVICE_CAPACITY = range(7)
-FD_LAYER_NONE, FD_LAYER_GRADBIN, FD_LAYER_LBP = 0, 1, 2
+FD_LAYER_NONE, FD_LAYER_GRADBIN, FD_LAYER_LBP, FD_LAYER_GRADMAG_LBP = 0, 1, 2, 3
+FD_SAMPLES_HIST, FD_SAMPLES_EHOG = 0, 1
+FD_HIST_SAMPLES_MAX = 1 << 20
 IMAGE_GRAY, IMAGE_GREYWORLD_GRAY = 0, 1   # fd_pyramid_set_image_filter
 FD_KERNEL_LINEAR, FD_KERNEL_POLY, FD_KERNEL_RBF, FD_KERNEL_HIK = 0, 1, 2, 3
 FD_DTYPE_U8, FD_DTYPE_F32 = 0, 1
@@ -476,6 +478,17 @@ _SIGS = {
     "fd_integral_gradient_length": (C.c_int, [C.c_int, C.c_int]),
     "fd_gradient_sum_length": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "fd_surf_feature_length": (C.c_int, [C.c_int, C.c_int]),
+    "fd_gradient_magnitude_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "fd_sample_windows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
+    "fd_pyramid_sample_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_hist_samples_limits": (C.c_int, [C.POINTER(C.c_int)]),
+    "fd_hist_extract_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_hist_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_ehog_extract_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_ehog_patch_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_hist_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "fd_hist_svm_evaluate_samples_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p]),
 }
 
 # include/fd_hip_bench.h: measurement hooks (not part of the drop-in boundary)
@@ -665,6 +678,13 @@ class Pyramid:
         r = _c(roi, np.int32) if roi is not None else None
         self.ctx.check(lib().fd_pyramid_window_count(self.h, pw, ph, sx, sy, _ptr(r), C.byref(n)))
         return n.value
+
+    def sample_windows(self, pw, ph, samples):
+        """samples (n, 4) {x, y, width, height} -> (n, 4) int32 {layer position, bx, by, valid} by the sample -> window rule"""
+        s = _c(samples, np.int32).reshape(-1, 4)
+        out = np.zeros((len(s), 4), np.int32)
+        self.ctx.check(lib().fd_pyramid_sample_windows(self.h, pw, ph, len(s), _ptr(s), _ptr(out)))
+        return out
 
     def windows(self, pw, ph, sx, sy, roi=None):
         n = self.window_count(pw, ph, sx, sy, roi)
@@ -2343,6 +2363,80 @@ def lbp_image(ctx, gray, lbp_type=0):
     out = np.empty(g.shape, np.uint8)
     ctx.check(lib().fd_lbp_image(ctx.h, _ptr(g), g.shape[1], g.shape[0], lbp_type, _ptr(out)))
     return out
+
+
+def gradient_magnitude_image(ctx, grad2ch):
+    """imageprocessing::GradientMagnitudeFilter on a CV_8UC2 gradient image [h, w, 2] -> [h, w] u8"""
+    g = _c(grad2ch, np.uint8)
+    if g.ndim != 3 or g.shape[2] != 2:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "GradientMagnitudeFilter: the image must have two channels")
+    out = np.empty(g.shape[:2], np.uint8)
+    ctx.check(lib().fd_gradient_magnitude_image(ctx.h, _ptr(g), g.shape[1], g.shape[0], _ptr(out)))
+    return out
+
+
+def sample_windows(layers, inc, pw, ph, samples):
+    """host only: layers as Pyramid.layers() (dicts with index, scale, w, h); samples (n, 4) {x, y, width, height} ->
+    (n, 4) int32 {layer position, bx, by, valid}"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    idx = _c([l["index"] for l in layers], np.int32)
+    sc = _c([l["scale"] for l in layers], np.float64)
+    lw = _c([l["w"] for l in layers], np.int32)
+    lh = _c([l["h"] for l in layers], np.int32)
+    out = np.zeros((len(s), 4), np.int32)
+    rc = lib().fd_sample_windows(len(layers), _ptr(idx), _ptr(sc), _ptr(lw), _ptr(lh), inc, pw, ph, len(s), _ptr(s), _ptr(out))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_sample_windows: invalid arguments")
+    return out
+
+
+def hist_samples_limits():
+    n = C.c_int()
+    if lib().fd_hist_samples_limits(C.byref(n)) != FD_OK:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "fd_hist_samples_limits")
+    return n.value
+
+
+def hist_extract_samples(ctx, pyr, hp, samples):
+    """the FD_HIST_* patch filter hp on the sampled windows of pyr: (features (n, F) f32, valid bool[n]); rows without a window are zero"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    layers = pyr.layers()
+    F = lib().fd_hist_feature_length(C.byref(hp), layers[0]["ch"] if layers else 1)
+    if F < 0:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "invalid histogram parameters")
+    feats = np.zeros((len(s), F), np.float32)
+    valid = np.zeros(len(s), np.uint8)
+    ctx.check(lib().fd_hist_extract_samples(ctx.h, pyr.h, C.byref(hp), len(s), _ptr(s), _ptr(valid), _ptr(feats)))
+    return feats, valid.astype(bool)
+
+
+def ehog_extract_samples(ctx, pyr, ep, samples):
+    """ExtendedHogFilter on the sampled windows of a FD_LAYER_GRADBIN pyramid: (features (n, F) f32, valid bool[n])"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    layers = pyr.layers()
+    F = lib().fd_ehog_feature_length(C.byref(ep), layers[0]["ch"] if layers else 2)
+    if F < 0:
+        raise FdError(FD_ERR_INVALID_ARGUMENT, "invalid extended HOG parameters")
+    feats = np.zeros((len(s), F), np.float32)
+    valid = np.zeros(len(s), np.uint8)
+    ctx.check(lib().fd_ehog_extract_samples(ctx.h, pyr.h, C.byref(ep), len(s), _ptr(s), _ptr(valid), _ptr(feats)))
+    return feats, valid.astype(bool)
+
+
+def hist_svm_evaluate_samples(ctx, pyr, params, svm, samples, want_distance=False):
+    """condensation::SingleClassifierModel::evaluate on sampled pyramid windows: params is a fd_hist_params or a fd_ehog_patch_params;
+    -> (target bool[n], weight f64[n]) and, with want_distance, the hyperplane distances f64[n]"""
+    kind = FD_SAMPLES_EHOG if isinstance(params, fd_ehog_patch_params) else FD_SAMPLES_HIST
+    s = _c(samples, np.int32).reshape(-1, 4)
+    target = np.zeros(len(s), np.uint8)
+    weight = np.zeros(len(s), np.float64)
+    if want_distance:
+        dist = np.zeros(len(s), np.float64)
+        ctx.check(lib().fd_hist_svm_evaluate_samples_distance(ctx.h, pyr.h, kind, C.byref(params), svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight),
+                                                              _ptr(dist)))
+        return target.astype(bool), weight, dist
+    ctx.check(lib().fd_hist_svm_evaluate_samples(ctx.h, pyr.h, kind, C.byref(params), svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight)))
+    return target.astype(bool), weight
 
 
 def hist_patch_batch(ctx, bin_patches, hp):

@@ -442,6 +442,31 @@ static inline void fd_pyramid_wait(const fd_pyramid* p, hipStream_t consumer) {
     if (p->ready && consumer != p->readyStream) HIP_CHECK(hipStreamWaitEvent(consumer, p->ready, 0));
 }
 
+// The sample -> window rule of DirectPyramidFeatureExtractor::extract(x, y, width, height) (DirectPyramidFeatureExtractor.cpp:67-73,
+// 134-153; ImagePyramid::getLayer(double), ImagePyramid.hpp:307-310), stated once: the layer with pyramid index
+// lround(log(patch_w / width) / log(inc)) must be a kept one (the kept layers have consecutive indices from first_index on);
+// layer(pos, scale, w, h) reports the kept layer at list position pos.  Returns false for a sample without a window.
+struct FdSampleWindow { int32_t layer, bx, by; };
+template <class LayerAt>
+static inline bool fd_sample_window(int n_layers, int first_index, double inc, int pw, int ph, int x, int y, int width, int height, LayerAt&& layer,
+                                    FdSampleWindow& out) {
+    if (width <= 0 || n_layers <= 0) return false;
+    const double power = std::log((double)pw / (double)width) / std::log(inc);
+    if (!(std::fabs(power) < 1e9)) return false;   // not a finite, representable index
+    const long index = std::lround(power);   // std::round, then the int cast of the reference
+    const long realIndex = index - first_index;
+    if (realIndex < 0 || realIndex >= (long)n_layers) return false;
+    double scale;
+    int lw, lh;
+    layer((int)realIndex, scale, lw, lh);
+    const double fx = (double)((int64_t)x - width / 2) * scale, fy = (double)((int64_t)y - height / 2) * scale;
+    if (!(fx >= -1.0 && fx <= (double)lw && fy >= -1.0 && fy <= (double)lh)) return false;   // far outside (and nothing the int cast could wrap)
+    const int bx = fd_cvRound(fx), by = fd_cvRound(fy);
+    if (bx < 0 || by < 0 || (int64_t)bx + pw > lw || (int64_t)by + ph > lh) return false;
+    out.layer = (int32_t)realIndex; out.bx = bx; out.by = by;
+    return true;
+}
+
 void fd_pyramid_update_on(fd_pyramid* p, const uint8_t* image, int w, int h, int ch, int is_device, hipStream_t st);
 constexpr int FD_MAX_FRAMES = 64;
 void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, const int* roi,

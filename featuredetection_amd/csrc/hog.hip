@@ -197,11 +197,14 @@ __global__ void k_select_positives(const double* __restrict__ dist, int64_t n, f
 
 struct HogScratch {
     DevBuf feat, xx, dist, pos, counter, tables, histTables, patchIn, part;
+    DevBuf list;          // the {layer, bx, by} triples of a sampled call (FdWinTable::list)
     DevBuf header;        // fused path: {positives, retired workgroups}, left zero by every run
     bool headerClean = false;
     HostBuf hcount;       // pinned read-back slot
     HogDev tabFor;        // parameters the tables were built for
     bool tabValid = false;
+    unsigned char histFor[128] = {};   // the HistDev (zero-filled, then set field by field) histTables was built for
+    bool histValid = false;
 };
 HogScratch& scratch(fd_ctx* ctx) { return fd_scratch<HogScratch>(ctx); }
 
@@ -835,8 +838,20 @@ size_t hist_lds_bytes(const HistDev& d) {
            sizeof(float) * (size_t)d.ldsFloats;
 }
 
-// HistogramFilter::createCache (HistogramFilter.cpp:199-220) + the pixel range each cell row/column receives
+// HistogramFilter::createCache (HistogramFilter.cpp:199-220) + the pixel range each cell row/column receives.  Built and uploaded
+// (one wait: the blob is a stack-lifetime host buffer) when the parameters change; a call with the parameters of the call before
+// queues nothing and waits for nothing
 void hist_tables(fd_ctx* ctx, HogScratch& S, const HistDev& d, HistTables& tb) {
+    static_assert(sizeof(HistDev) <= sizeof(S.histFor), "HogScratch::histFor holds a HistDev");
+    const size_t t1 = sizeof(HistCache) * (size_t)d.ph, t2 = t1 + sizeof(HistCache) * (size_t)d.pw, t3 = t2 + 4 * (size_t)d.rows;
+    if (S.histValid && std::memcmp(S.histFor, &d, sizeof(HistDev)) == 0) {
+        tb.rowCache = (const HistCache*)S.histTables.p;
+        tb.colCache = (const HistCache*)((const char*)S.histTables.p + t1);
+        tb.rowRange = (const int32_t*)((const char*)S.histTables.p + t2);
+        tb.colRange = (const int32_t*)((const char*)S.histTables.p + t3);
+        return;
+    }
+    S.histValid = false;
     std::vector<unsigned char> blob;
     auto cache = [](int size, int count, std::vector<HistCache>& c, std::vector<int32_t>& range) {
         c.resize(size);
@@ -873,6 +888,8 @@ void hist_tables(fd_ctx* ctx, HogScratch& S, const HistDev& d, HistTables& tb) {
     tb.colCache = (const HistCache*)((const char*)S.histTables.p + o1);
     tb.rowRange = (const int32_t*)((const char*)S.histTables.p + o2);
     tb.colRange = (const int32_t*)((const char*)S.histTables.p + o3);
+    std::memcpy(S.histFor, &d, sizeof(HistDev));
+    S.histValid = true;
 }
 
 // k_hist_features over the windows of `wt` inside `arena` -> S.feat ([N][F] floats)
@@ -890,17 +907,23 @@ void launch_hist_features(fd_ctx* ctx, const uint8_t* arena, const FdWinTable& w
     HIP_CHECK(hipGetLastError());
 }
 
-// features of every window, plain [N][F] layout, into S.feat; returns N
-int64_t run_hist_features(fd_ctx* ctx, fd_pyramid* p, const fd_hist_params* hp, std::vector<WindowLayer>& wls, HogScratch& S, HistDev& hd) {
+// what the histogram filters ask of the pyramid's layer filter; returns the channels of a layer
+int hist_check_layers(const fd_pyramid* p, const fd_hist_params* hp) {
     if (!hp) FD_THROW(FD_ERR_INVALID_ARGUMENT, "NULL histogram parameters");
-    if (p->filter_kind != FD_LAYER_GRADBIN && p->filter_kind != FD_LAYER_LBP)
-        FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram features need a pyramid whose layers are bin images (FD_LAYER_GRADBIN or FD_LAYER_LBP)");
+    if (p->filter_kind != FD_LAYER_GRADBIN && p->filter_kind != FD_LAYER_LBP && p->filter_kind != FD_LAYER_GRADMAG_LBP)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram features need a pyramid whose layers are bin images (FD_LAYER_GRADBIN, FD_LAYER_LBP or FD_LAYER_GRADMAG_LBP)");
     fd_pyramid_require_image(p);   // before kept[0] is read
-    const int ch = p->all[p->kept[0]].ch;
+    const int ch = p->kept.empty() ? (p->filter_kind == FD_LAYER_GRADBIN ? (p->interpolate ? 4 : 2) : 1) : p->all[p->kept[0]].ch;
     if ((hp->kind == FD_HIST_HOG || hp->kind == FD_HIST_PYRAMID_HOG) && ch == 1)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "HOG features need a gradient bin image (FD_LAYER_GRADBIN)");
     if (p->filter_kind == FD_LAYER_GRADBIN && p->bins != hp->bins)
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "histogram bins (%d) differ from the layer filter bins (%d)", hp->bins, p->bins);
+    return ch;
+}
+
+// features of every window, plain [N][F] layout, into S.feat; returns N
+int64_t run_hist_features(fd_ctx* ctx, fd_pyramid* p, const fd_hist_params* hp, std::vector<WindowLayer>& wls, HogScratch& S, HistDev& hd) {
+    const int ch = hist_check_layers(p, hp);
     hd = make_histdev(hp, ch);
     FdWinTable wt;
     fd_win_table_build(p, hp->patch_w, hp->patch_h, hp->step_x, hp->step_y, nullptr, /*filtered=*/true, wt, wls);
@@ -1016,3 +1039,4 @@ int fd_detect_hist_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_h
 }  // extern "C"
 
 #include "ehog_patch.hpp"
+#include "hist_samples.hpp"

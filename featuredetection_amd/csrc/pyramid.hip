@@ -780,6 +780,48 @@ __global__ void k_binning_image(const uint8_t* __restrict__ grad, const uint8_t*
     }
 }
 
+// LbpFilter.cpp:20-44: uniform patterns (<= 2 circular transitions) get indices 1..58 in increasing code order, all others 0.
+// index = 1 + #uniform codes below this one.
+__device__ __forceinline__ int lbp_uniform_index(int code) {
+    int rot = ((code << 1) | (code >> 7)) & 0xff;  // bit pos compared with bit pos-1 (pos 0 with 7)
+    int transitions = __popc((code ^ rot) & 0xff);
+    if (transitions > 2) return 0;
+    int cnt = 0;
+    for (int q = 0; q < code; ++q) {
+        int rq = ((q << 1) | (q >> 7)) & 0xff;
+        cnt += __popc((q ^ rq) & 0xff) <= 2;
+    }
+    return 1 + cnt;
+}
+
+// one LBP code (LbpFilter.hpp:88-180) from the rows P (y - 1), C (y), N (y + 1) at the columns xm, x, xp; the caller resolves the
+// border.  FD_LBP8_UNIFORM: the raw 8-bit code (the callers map it: lbp_uniform_index, or a table of it)
+__device__ __forceinline__ int lbp_raw_code(const uint8_t* P, const uint8_t* C, const uint8_t* N, int xm, int x, int xp, int type) {
+    const int c = C[x];
+    int code = 0;
+    if (type == FD_LBP8 || type == FD_LBP8_UNIFORM) {
+        code |= (P[xm] > c) << 7;
+        code |= (P[x] > c) << 6;
+        code |= (P[xp] > c) << 5;
+        code |= (C[xp] > c) << 4;
+        code |= (N[xp] > c) << 3;
+        code |= (N[x] > c) << 2;
+        code |= (N[xm] > c) << 1;
+        code |= (C[xm] > c) << 0;
+    } else if (type == FD_LBP4) {
+        code |= (P[x] > c) << 3;
+        code |= (C[xp] > c) << 2;
+        code |= (N[x] > c) << 1;
+        code |= (C[xm] > c) << 0;
+    } else {
+        code |= (P[xm] > c) << 3;
+        code |= (P[xp] > c) << 2;
+        code |= (N[xp] > c) << 1;
+        code |= (N[xm] > c) << 0;
+    }
+    return code;
+}
+
 // LbpFilter 3x3 codes with BORDER_REPLICATE (LbpFilter.hpp:88-180), optional uniform map
 __global__ void k_lbp(uint8_t* __restrict__ arena, int type, FilterJobs jobs) {
     const FilterJob jb = jobs.j[blockIdx.y];
@@ -789,45 +831,72 @@ __global__ void k_lbp(uint8_t* __restrict__ arena, int type, FilterJobs jobs) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < w * h; i += gridDim.x * blockDim.x) {
         int y = i / w, x = i - y * w;
         int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
-        const uint8_t *P = src + (size_t)ym * w, *C = src + (size_t)y * w, *N = src + (size_t)yp * w;
-        int c = C[x];
-        int code = 0;
-        if (type == FD_LBP8 || type == FD_LBP8_UNIFORM) {
-            code |= (P[xm] > c) << 7;
-            code |= (P[x] > c) << 6;
-            code |= (P[xp] > c) << 5;
-            code |= (C[xp] > c) << 4;
-            code |= (N[xp] > c) << 3;
-            code |= (N[x] > c) << 2;
-            code |= (N[xm] > c) << 1;
-            code |= (C[xm] > c) << 0;
-            if (type == FD_LBP8_UNIFORM) {
-                // LbpFilter.cpp:20-44: uniform patterns (<= 2 circular transitions) get indices 1..58 in
-                // increasing code order, all others 0.  index = 1 + #uniform codes below this one.
-                int rot = ((code << 1) | (code >> 7)) & 0xff;  // bit pos compared with bit pos-1 (pos 0 with 7)
-                int transitions = __popc((code ^ rot) & 0xff);
-                if (transitions > 2) code = 0;
-                else {
-                    int cnt = 0;
-                    for (int q = 0; q < code; ++q) {
-                        int rq = ((q << 1) | (q >> 7)) & 0xff;
-                        cnt += __popc((q ^ rq) & 0xff) <= 2;
-                    }
-                    code = 1 + cnt;
-                }
-            }
-        } else if (type == FD_LBP4) {
-            code |= (P[x] > c) << 3;
-            code |= (C[xp] > c) << 2;
-            code |= (N[x] > c) << 1;
-            code |= (C[xm] > c) << 0;
-        } else {
-            code |= (P[xm] > c) << 3;
-            code |= (P[xp] > c) << 2;
-            code |= (N[xp] > c) << 1;
-            code |= (N[xm] > c) << 0;
-        }
+        int code = lbp_raw_code(src + (size_t)ym * w, src + (size_t)y * w, src + (size_t)yp * w, xm, x, xp, type);
+        if (type == FD_LBP8_UNIFORM) code = lbp_uniform_index(code);
         dst[i] = (uint8_t)code;
+    }
+}
+
+// imageprocessing::GradientMagnitudeFilter (GradientMagnitudeFilter.hpp:39-50, CV_8U branch) of one GradientFilter pixel (vx, vy):
+// saturate_cast<uchar>(sqrt(x^2 + y^2)) with x = vx - 127, y = vy - 127.  s = x^2 + y^2 <= 32768 is an integer, its root is never
+// k + 1/2, so the rounded root is the r with r^2 - r < s <= r^2 + r (at most 181): the largest r with r (r - 1) < s, bit by bit
+__device__ __forceinline__ int grad_magnitude(int vx, int vy) {
+    const int x = vx - 127, y = vy - 127;
+    const int s = x * x + y * y;
+    int r = 0;
+#pragma unroll
+    for (int b = 128; b > 0; b >>= 1) {
+        const int t = r + b;
+        r = t * t - t < s ? t : r;
+    }
+    return r;
+}
+
+// GradientMagnitudeFilter::applyTo alone: CV_8UC2 gradient image -> CV_8UC1 magnitudes
+__global__ void k_gradient_magnitude_image(const uint8_t* __restrict__ grad, uint8_t* __restrict__ dst, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        dst[i] = (uint8_t)grad_magnitude(grad[2 * (size_t)i], grad[2 * (size_t)i + 1]);
+}
+
+// FD_LAYER_GRADMAG_LBP: GradientFilter -> GradientMagnitudeFilter -> LbpFilter in one pass, no magnitude plane in memory.  A
+// workgroup takes GL_TW x GL_TH pixel tiles of a layer: it stages the magnitudes of the tile and of a one-pixel halo in LDS (a halo
+// position outside the layer holds the magnitude AT THE CLAMPED COORDINATE: LbpFilter's BORDER_REPLICATE replicates its own input,
+// the magnitude image, not the gray layer under it) and writes the LBP codes of the tile's pixels from there.
+// LDS: mag[(GL_TH + 2) * GL_PITCH] bytes, then the 256 uniform-map entries (FD_LBP8_UNIFORM only; one entry per thread).
+constexpr int GL_TW = 64, GL_TH = 16, GL_PITCH = GL_TW + 4;
+__global__ __launch_bounds__(256) void k_gradmag_lbp(uint8_t* __restrict__ arena, int ksize, int type, FilterJobs jobs) {
+    __shared__ uint8_t mag[(GL_TH + 2) * GL_PITCH];
+    __shared__ uint8_t utab[256];
+    const FilterJob jb = jobs.j[blockIdx.y];
+    const uint8_t* src = arena + jb.src_off;
+    uint8_t* dst = arena + jb.dst_off;
+    const int w = jb.w, h = jb.h;
+    const int tilesX = (w + GL_TW - 1) / GL_TW, ntiles = tilesX * ((h + GL_TH - 1) / GL_TH);
+    if ((int)blockIdx.x >= ntiles) return;   // the grid is sized for the layer with the most tiles
+    if (type == FD_LBP8_UNIFORM) utab[threadIdx.x] = (uint8_t)lbp_uniform_index(threadIdx.x);   // visible behind the first barrier below
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {   // the same trip count for every thread of the workgroup
+        const int ty = tile / tilesX, tx = tile - ty * tilesX;
+        const int x0 = tx * GL_TW, y0 = ty * GL_TH;
+        for (int i = threadIdx.x; i < (GL_TW + 2) * (GL_TH + 2); i += 256) {
+            const int hy = i / (GL_TW + 2), hx = i - hy * (GL_TW + 2);
+            const int x = min(max(x0 + hx - 1, 0), w - 1), y = min(max(y0 + hy - 1, 0), h - 1);
+            int gx, gy;
+            const float scale = grad_pair(src, w, h, x, y, ksize, gx, gy);
+            const int vx = min(255, max(0, __float2int_rn(127.f + scale * gx))), vy = min(255, max(0, __float2int_rn(127.f + scale * gy)));
+            mag[hy * GL_PITCH + hx] = (uint8_t)grad_magnitude(vx, vy);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < GL_TW * GL_TH; i += 256) {
+            const int ly = i / GL_TW, lx = i - ly * GL_TW;
+            const int x = x0 + lx, y = y0 + ly;
+            if (x < w && y < h) {
+                const uint8_t* C = mag + (ly + 1) * GL_PITCH + 1;   // the halo resolves the border
+                int code = lbp_raw_code(C - GL_PITCH, C, C + GL_PITCH, lx - 1, lx, lx + 1, type);
+                if (type == FD_LBP8_UNIFORM) code = utab[code];
+                dst[(size_t)y * w + x] = (uint8_t)code;
+            }
+        }
+        __syncthreads();   // the next tile overwrites mag
     }
 }
 
@@ -1041,8 +1110,11 @@ void build_gradient_lut(int bins, bool signedGradients, bool interpolate, std::v
     }
 }
 
+// layer filters that start with GradientFilter (and so with its optional blur)
+bool layer_takes_gradients(int kind) { return kind == FD_LAYER_GRADBIN || kind == FD_LAYER_GRADMAG_LBP; }
 int grid_for(int npix) { return std::max(1, std::min(1024, (npix + 255) / 256)); }
 int tile_grid_for(int ntiles) { return std::max(1, std::min(1024, ntiles)); }
+int gradmag_lbp_tiles(int w, int h) { return ((w + GL_TW - 1) / GL_TW) * ((h + GL_TH - 1) / GL_TH); }
 
 // ---- the launch plan: what an update enqueues behind the gray image ----------------------------------------------------------
 // All of it depends only on what build_layout fixes (frame size, pyramid parameters, layer filter, number of frames), so it is
@@ -1062,9 +1134,10 @@ struct DownLaunch {     // k_pyrdown_tiled: the pyrDowns of up to MAXJ layers of
     int ntile;          // tiles per frame: the grid
     uint32_t tileTab;   // its PdTile list in rtab (offset in int2 entries)
 };
-struct FilterLaunch {   // k_gradbin / k_lbp, behind k_box_blur where GradientFilter blurs (blur.n == jobs.n then, 0 otherwise)
+struct FilterLaunch {   // k_gradbin / k_lbp / k_gradmag_lbp, behind k_box_blur where GradientFilter blurs (blur.n == jobs.n then, 0 otherwise)
     FilterJobs jobs, blur;
-    int grid;
+    int grid;       // workgroups per job of the per-pixel kernels
+    int tileGrid;   // ... of k_gradmag_lbp: the tiles of the job with the most
 };
 
 }  // namespace
@@ -1227,7 +1300,7 @@ void build_plan(fd_pyramid* p, int W, int H) {
         HIP_CHECK(hipMemcpy(p->rtab.p, tab.data(), sizeof(int2) * tab.size(), hipMemcpyHostToDevice));
     }
     if (p->filter_kind != FD_LAYER_NONE) {
-        const bool blur = p->filter_kind == FD_LAYER_GRADBIN && p->grad_blur > 0;
+        const bool blur = layer_takes_gradients(p->filter_kind) && p->grad_blur > 0;
         for (int k : p->kept) {
             const HostLayer& L = all[k];
             FilterJob& j = next_job(plan.filter);
@@ -1238,6 +1311,7 @@ void build_plan(fd_pyramid* p, int W, int H) {
                 b.w = L.w; b.h = L.h; b.src_off = L.gray_off; b.dst_off = L.blur_off;
             }
             F.grid = std::max(F.grid, grid_for(L.w * L.h));
+            F.tileGrid = std::max(F.tileGrid, tile_grid_for(gradmag_lbp_tiles(L.w, L.h)));
         }
     }
 }
@@ -1285,7 +1359,7 @@ void build_layout(fd_pyramid* p, int W, int H) {
         else {
             L.filt_off = (uint32_t)off;
             off = align256(off + (size_t)L.w * L.h * fch);
-            if (p->filter_kind == FD_LAYER_GRADBIN && p->grad_blur > 0) {
+            if (layer_takes_gradients(p->filter_kind) && p->grad_blur > 0) {
                 L.blur_off = (uint32_t)off;
                 off = align256(off + (size_t)L.w * L.h);
             }
@@ -1379,7 +1453,9 @@ void pyramid_update(fd_pyramid* p, const uint8_t* image, int W, int H, int ch, i
     for (const FilterLaunch& F : plan.filter) {
         const dim3 g(F.grid, F.jobs.n);
         if (F.blur.n) hipLaunchKernelGGL(k_box_blur, g, dim3(256), 0, st, arena, p->grad_blur, F.blur);
-        if (p->filter_kind != FD_LAYER_GRADBIN)
+        if (p->filter_kind == FD_LAYER_GRADMAG_LBP)
+            hipLaunchKernelGGL(k_gradmag_lbp, dim3(F.tileGrid, F.jobs.n), dim3(256), 0, st, arena, p->grad_kernel, p->lbp_type, F.jobs);
+        else if (p->filter_kind != FD_LAYER_GRADBIN)
             hipLaunchKernelGGL(k_lbp, g, dim3(256), 0, st, arena, p->lbp_type, F.jobs);
         else if (p->interpolate)
             hipLaunchKernelGGL(k_gradbin<4>, g, dim3(256), 0, st, arena, p->lut.as<uint8_t>(), p->grad_kernel, F.jobs);
@@ -1503,6 +1579,10 @@ int fd_pyramid_set_layer_filter(fd_pyramid* p, int kind, int bins, int signed_gr
             HIP_CHECK(hipMemcpyAsync(p->lut.p, lut.data(), lut.size(), hipMemcpyHostToDevice, p->ctx->stream));
             HIP_CHECK(hipStreamSynchronize(p->ctx->stream));
         } else if (kind == FD_LAYER_LBP) {
+            if (lbp_type < 0 || lbp_type > 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "LbpFilter: invalid type");
+        } else if (kind == FD_LAYER_GRADMAG_LBP) {   // bins, signed_gradients and interpolate are not used
+            if (grad_kernel != 1 && grad_kernel != 3 && grad_kernel != 5 && grad_kernel != 7 && grad_kernel != FD_GRAD_SCHARR)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "GradientFilter: the kernel size must be 1, 3, 5, 7 or CV_SCHARR");
             if (lbp_type < 0 || lbp_type > 3) FD_THROW(FD_ERR_INVALID_ARGUMENT, "LbpFilter: invalid type");
         } else if (kind != FD_LAYER_NONE) {
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_pyramid_set_layer_filter: unknown kind %d", kind);
@@ -1752,6 +1832,23 @@ int fd_gradient_binning_image(fd_ctx* ctx, const uint8_t* grad2ch, int w, int h,
         else hipLaunchKernelGGL(k_binning_image<4>, dim3(grid_for((int)n)), dim3(256), 0, ctx->stream, in.as<uint8_t>(), dl.as<uint8_t>(), out.as<uint8_t>(), (int)n);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(dst, out.p, (size_t)E * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_gradient_magnitude_image(fd_ctx* ctx, const uint8_t* grad2ch, int w, int h, uint8_t* dst) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !grad2ch || !dst || w < 1 || h < 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_gradient_magnitude_image: bad argument");
+        if ((size_t)w * h > 0x3fffffffull) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_gradient_magnitude_image: image too large");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        const size_t n = (size_t)w * h;
+        DevBuf in, out;
+        in.reserve(2 * n);
+        out.reserve(n);
+        HIP_CHECK(hipMemcpyAsync(in.p, grad2ch, 2 * n, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_gradient_magnitude_image, dim3(grid_for((int)n)), dim3(256), 0, ctx->stream, in.as<uint8_t>(), out.as<uint8_t>(), (int)n);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(dst, out.p, n, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     });
 }

@@ -21,6 +21,9 @@ struct FdWinLayer {
 struct FdWinTable {
     int32_t n, sx, sy, raw;   // raw != 0 (whi.hip): `total` contiguous patches, no layers
     int64_t total;
+    // list mode (fd_win_table_list): `total` explicit windows, window wid is the triple {layer, bx, by} at list[3 * wid]; l[layer]
+    // names the plane (lw, off).  NULL: the windows of a strided scan, as every other builder leaves it
+    const int32_t* list;
     FdWinLayer l[FD_WIN_MAX_LAYERS];
 };
 
@@ -59,10 +62,28 @@ static inline FdWinTable fd_win_table_column(int64_t n, int patch_w, int patch_h
     return wt;
 }
 
+// `total` explicit windows {layer, bx, by} (device memory, layer = position in the kept-layer list) on the filtered planes of p
+static inline void fd_win_table_list(const fd_pyramid* p, const int32_t* dlist, int64_t total, FdWinTable& wt) {
+    fd_pyramid_require_image(p);
+    if (p->kept.size() > (size_t)FD_WIN_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", p->kept.size());
+    std::memset(&wt, 0, sizeof(wt));
+    wt.n = (int32_t)p->kept.size(); wt.sx = wt.sy = 1; wt.total = total; wt.list = dlist;
+    for (size_t i = 0; i < p->kept.size(); ++i) {
+        const HostLayer& L = p->all[p->kept[i]];
+        wt.l[i].nx = 1; wt.l[i].ny = 1; wt.l[i].lw = L.w; wt.l[i].off = L.filt_off;
+    }
+}
+
 namespace fd_dev {
 
 // window wid < total -> its layer record and the window's pixel origin (x, y) in that layer
 __device__ __forceinline__ const FdWinLayer& win_locate(const FdWinTable& wt, int64_t wid, int& x, int& y) {
+    if (wt.list) {
+        const int32_t* t = wt.list + 3 * wid;
+        x = t[1];
+        y = t[2];
+        return wt.l[t[0]];
+    }
     int li = 0;
     for (int l = 1; l < wt.n; ++l) li = wt.l[l].first <= wid ? l : li;
     const FdWinLayer& wl = wt.l[li];

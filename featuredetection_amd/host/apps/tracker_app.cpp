@@ -18,6 +18,9 @@
 //                        adaptation position adaptationThreshold 0.75 exclusionThreshold 0.0
 //                        classifier { training { c 1  compensateImbalance 0  negativeCapacity 100 }  logisticA 0.00556  logisticB -2.95  threshold 0 } }
 //                        (training { type libLinear  c 1  bias 0  negativeCapacity 100 }: a liblinear::LibLinearClassifier; type libSvm is the default)
+//     measurement positionDependent { feature hog|ehog|lbp|glbp { ... }  filter none  startFrameCount 1 ...  classifier { training { ... } } }
+//                        (in place of `measurement ehog`: a condensation::PositionDependentMeasurementModel, keys in tracking_setup.hpp; the
+//                         AdaptiveCondensationTracker initialises its model once, so startFrameCount must be 1 for it to start; its generator gets seed + 4)
 //   }
 // the box is the target's bounding box (top left corner) in frame 0.  Prints "init <0|1> [x y w h]", then per further frame
 //   "frame <f> found <0|1> <x> <y> <w> <h> adapted <0|1> route <generic|device> ms <wall time of process()>"
@@ -42,6 +45,7 @@
 #include "liblinear/LibLinearClassifier.hpp"
 #include "libsvm/LibSvmClassifier.hpp"
 #include "fdcompat/ptree.hpp"
+#include "tracking_setup.hpp"
 
 using namespace imageprocessing;
 using namespace classification;
@@ -179,44 +183,37 @@ int main(int argc, char** argv) {
                                                      make_shared<LowVarianceSampling>(seed), transitionModel,
                                                      pt.get("adaptive.resampling.minSize", 40), pt.get("adaptive.resampling.maxSize", 200), seed + 2);
         const ptree& mt = pt.get_child("measurement");
-        if (pt.get("measurement", string("ehog")) != "ehog") throw std::invalid_argument("tracker_app: only `measurement ehog` is supported");
+        const string measurement = pt.get("measurement", string("ehog"));
+        if (measurement != "ehog" && measurement != "positionDependent")
+            throw std::invalid_argument("tracker_app: invalid measurement model type: " + measurement + " (ehog and positionDependent are supported)");
         const ptree& ct = mt.get_child("classifier");
+        shared_ptr<AdaptiveMeasurementModel> adaptiveModel;
         shared_ptr<ExtendedHogBasedMeasurementModel> model;
-        if (ct.count("training")) {
-            const ptree& tr = ct.get_child("training");
-            const string trainingType = tr.get("type", string("libSvm"));
-            shared_ptr<TrainableSvmClassifier> svm;
-            std::unique_ptr<ExampleManagement> negatives(new AgeBasedExampleManagement(tr.get("negativeCapacity", 100)));
-            if (trainingType == "libLinear") {
-                auto linear = make_shared<liblinear::LibLinearClassifier>(tr.get("c", 1.0), tr.get("bias", 0) != 0);
-                linear->setNegativeExampleManagement(std::move(negatives));
-                svm = linear;
-            } else if (trainingType == "libSvm") {
-                auto dual = libsvm::LibSvmClassifier::createBinarySvm(make_shared<LinearKernel>(), tr.get("c", 1.0), tr.get("compensateImbalance", 0) != 0);
-                dual->setNegativeExampleManagement(std::move(negatives));
-                svm = dual;
-            } else {
-                throw std::invalid_argument("tracker_app: invalid training type: " + trainingType);
-            }
-            svm->getSvm()->setThreshold(ct.get("threshold", 0.0f));   // as ProbabilisticSvmClassifier::load reads it
+        if (measurement == "positionDependent") {
+            adaptiveModel = tracking_setup::createPositionDependent(mt, seed + 4).model;
+        } else if (ct.count("training")) {
+            shared_ptr<TrainableSvmClassifier> svm = tracking_setup::createTrainableSvm(ct);
             model = make_shared<ExtendedHogBasedMeasurementModel>(
                 make_shared<FixedTrainableProbabilisticSvmClassifier>(svm, ct.get("logisticA", 0.00556), ct.get("logisticB", -2.95)));
         } else {
             model = make_shared<ExtendedHogBasedMeasurementModel>(ProbabilisticSvmClassifier::load(ct));
         }
-        model->setHogParams(mt.get("cellSize", 5), mt.get("cellCount", 35), mt.get("signedAndUnsigned", 0) != 0, mt.get("interpolateBins", 0) != 0,
-                            mt.get("interpolateCells", 1) != 0, mt.get("octaveLayerCount", 5));
-        model->setRejectionThreshold(mt.get("rejectionThreshold", -1.5));
-        model->setUseSlidingWindow(mt.get("useSlidingWindow", 1) != 0, mt.get("conservativeReInit", 0) != 0);
-        model->setNegativeExampleParams(mt.get("negativeExampleCount", 10), mt.get("initialNegativeExampleCount", 50), mt.get("randomExampleCount", 50),
-                                        (float)mt.get("negativeScoreThreshold", -1.0));
-        model->setOverlapThresholds(mt.get("positiveOverlapThreshold", 0.5), mt.get("negativeOverlapThreshold", 0.5));
-        const string adaptation = mt.get("adaptation", string("position"));
-        model->setAdaptation(adaptation == "none" ? ExtendedHogBasedMeasurementModel::Adaptation::NONE
-                             : adaptation == "trajectory" ? ExtendedHogBasedMeasurementModel::Adaptation::TRAJECTORY
-                                                          : ExtendedHogBasedMeasurementModel::Adaptation::POSITION,
-                             mt.get("adaptationThreshold", 0.75), mt.get("exclusionThreshold", 0.0));
-        AdaptiveCondensationTracker tracker(sampler, model, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()),
+        if (model) {
+            adaptiveModel = model;
+            model->setHogParams(mt.get("cellSize", 5), mt.get("cellCount", 35), mt.get("signedAndUnsigned", 0) != 0, mt.get("interpolateBins", 0) != 0,
+                                mt.get("interpolateCells", 1) != 0, mt.get("octaveLayerCount", 5));
+            model->setRejectionThreshold(mt.get("rejectionThreshold", -1.5));
+            model->setUseSlidingWindow(mt.get("useSlidingWindow", 1) != 0, mt.get("conservativeReInit", 0) != 0);
+            model->setNegativeExampleParams(mt.get("negativeExampleCount", 10), mt.get("initialNegativeExampleCount", 50), mt.get("randomExampleCount", 50),
+                                            (float)mt.get("negativeScoreThreshold", -1.0));
+            model->setOverlapThresholds(mt.get("positiveOverlapThreshold", 0.5), mt.get("negativeOverlapThreshold", 0.5));
+            const string adaptation = mt.get("adaptation", string("position"));
+            model->setAdaptation(adaptation == "none" ? ExtendedHogBasedMeasurementModel::Adaptation::NONE
+                                 : adaptation == "trajectory" ? ExtendedHogBasedMeasurementModel::Adaptation::TRAJECTORY
+                                                              : ExtendedHogBasedMeasurementModel::Adaptation::POSITION,
+                                 mt.get("adaptationThreshold", 0.75), mt.get("exclusionThreshold", 0.0));
+        }
+        AdaptiveCondensationTracker tracker(sampler, adaptiveModel, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()),
                                             pt.get("initialCount", 800));
         const cv::Rect box(std::atoi(argv[a + 1]), std::atoi(argv[a + 2]), std::atoi(argv[a + 3]), std::atoi(argv[a + 4]));
         boost::optional<cv::Rect> start = tracker.initialize(read_pnm(argv[a + 5]), box);

@@ -1,0 +1,167 @@
+// tracking_setup.hpp -- what tracker_app and position_dependent_eval_app share: the pyramid feature types of the reference's
+// createFeatureExtractor (HeadTracking.cpp:117-135,199-330: hog, ehog, lbp, glbp on a `pyramid direct` block), the trainable classifier of
+// a `classifier` block, and condensation::PositionDependentMeasurementModel from a `measurement positionDependent` block
+// (HeadTracking.cpp:503-533).
+//   measurement positionDependent {
+//     feature hog|ehog|lbp|glbp { pyramid direct { patch { width 16 height 16 minWidth 16 maxWidth 64 } interval 3 }   scale 1
+//        gradientKernel 1 blurKernel 0 bins 9 signed 0 interpolate 0     (hog, ehog; glbp: gradientKernel, blurKernel)
+//        type lbp8|lbp8uniform|lbp4|lbp4rotated                           (lbp, glbp)
+//        histogram spatial { cellSize 4 blockSize 2 interpolate 0 signedAndUnsigned 0 concatenate 0 normalization l2hys }
+//        histogram pyramid { levels 2 interpolate 0 signedAndUnsigned 0 normalization l2norm }
+//        (ehog: histogram { cellSize 4 interpolate 0 signedAndUnsigned 0 alpha 0.2 }) }
+//     filter none   startFrameCount 3  stopFrameCount 0  targetThreshold 0.7  confidenceThreshold 0.95  positiveOffsetFactor 0.05
+//     negativeOffsetFactor 0.5  sampleNegativesAroundTarget 0  sampleAdditionalNegatives 10  sampleTestNegatives 10  exploitSymmetry 0
+//     classifier { training { type libSvm|libLinear c 1 ... }  logisticA 0.00556  logisticB -2.95  threshold 0 }
+//   }
+// Not built, each an invalid_argument that names it: filter before|after (FilteringClassifierModel), validator rvm, the gray-patch
+// feature types (grayscale, histeq, h, whi) and the integral ones (haar, ihog, iehog, surf) under this key.
+#pragma once
+#include <cmath>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include "condensation/PositionDependentMeasurementModel.hpp"
+#include "imageprocessing/GradientMagnitudeFilter.hpp"
+#include "liblinear/LibLinearClassifier.hpp"
+#include "libsvm/LibSvmClassifier.hpp"
+#include "fdcompat/ptree.hpp"
+
+namespace tracking_setup {
+
+using boost::property_tree::ptree;
+using namespace imageprocessing;
+using namespace classification;
+
+inline bool flag(const ptree& config, const std::string& key, bool dflt = false) { return config.get<int>(key, dflt ? 1 : 0) != 0; }
+
+// createPyramidExtractor, `direct` (DirectPyramidFeatureExtractor.cpp:27-36,41-43)
+inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(const ptree& config) {
+    if (config.get_value<std::string>() != "direct")
+        throw std::invalid_argument("tracking: pyramid type `" + config.get_value<std::string>() + "` is not built (only `pyramid direct`)");
+    const int width = config.get<int>("patch.width"), height = config.get<int>("patch.height");
+    const int minWidth = config.get<int>("patch.minWidth"), maxWidth = config.get<int>("patch.maxWidth"), interval = config.get<int>("interval");
+    const double inc = std::pow(0.5, 1. / interval);
+    double minScale = static_cast<double>(width) / maxWidth, maxScale = static_cast<double>(width) / minWidth;
+    const int maxLayerIndex = cv::cvRound(std::log(minScale) / std::log(inc)), minLayerIndex = cv::cvRound(std::log(maxScale) / std::log(inc));
+    maxScale = std::pow(inc, minLayerIndex);
+    minScale = std::pow(inc, maxLayerIndex);
+    auto extractor = std::make_shared<DirectPyramidFeatureExtractor>(std::make_shared<ImagePyramid>(static_cast<size_t>(interval), minScale, maxScale), width, height);
+    extractor->addImageFilter(std::make_shared<GrayscaleFilter>());
+    return extractor;
+}
+
+inline std::shared_ptr<HistogramFilter> createHistogramFilter(unsigned int bins, const ptree& config) {
+    const std::string name = config.get<std::string>("normalization");
+    HistogramFilter::Normalization normalization;
+    if (name == "none") normalization = HistogramFilter::Normalization::NONE;
+    else if (name == "l2norm") normalization = HistogramFilter::Normalization::L2NORM;
+    else if (name == "l2hys") normalization = HistogramFilter::Normalization::L2HYS;
+    else if (name == "l1norm") normalization = HistogramFilter::Normalization::L1NORM;
+    else if (name == "l1sqrt") normalization = HistogramFilter::Normalization::L1SQRT;
+    else throw std::invalid_argument("tracking: invalid normalization method: " + name);
+    if (config.get_value<std::string>() == "spatial")
+        return std::make_shared<SpatialHistogramFilter>((int)bins, config.get<int>("cellSize"), config.get<int>("blockSize"), flag(config, "interpolate"),
+                                                        flag(config, "concatenate"), normalization);
+    if (config.get_value<std::string>() == "pyramid")
+        return std::make_shared<SpatialPyramidHistogramFilter>((int)bins, config.get<int>("levels"), flag(config, "interpolate"), normalization);
+    throw std::invalid_argument("tracking: invalid histogram type: " + config.get_value<std::string>());
+}
+
+inline std::shared_ptr<HistogramFilter> createHogFilter(int bins, const ptree& config) {
+    if (config.get_value<std::string>() == "spatial") {
+        if (config.get<int>("blockSize") == 1 && !flag(config, "signedAndUnsigned")) return createHistogramFilter(bins, config);
+        return std::make_shared<HogFilter>(bins, config.get<int>("cellSize"), config.get<int>("blockSize"), flag(config, "interpolate"), flag(config, "signedAndUnsigned"));
+    }
+    if (config.get_value<std::string>() == "pyramid")
+        return std::make_shared<PyramidHogFilter>(bins, config.get<int>("levels"), flag(config, "interpolate"), flag(config, "signedAndUnsigned"));
+    throw std::invalid_argument("tracking: invalid histogram type: " + config.get_value<std::string>());
+}
+
+inline std::shared_ptr<LbpFilter> createLbpFilter(const std::string& lbpType) {
+    if (lbpType == "lbp8") return std::make_shared<LbpFilter>(LbpFilter::Type::LBP8);
+    if (lbpType == "lbp8uniform") return std::make_shared<LbpFilter>(LbpFilter::Type::LBP8_UNIFORM);
+    if (lbpType == "lbp4") return std::make_shared<LbpFilter>(LbpFilter::Type::LBP4);
+    if (lbpType == "lbp4rotated") return std::make_shared<LbpFilter>(LbpFilter::Type::LBP4_ROTATED);
+    throw std::invalid_argument("tracking: invalid LBP type: " + lbpType);
+}
+
+inline std::shared_ptr<FeatureExtractor> createFeatureExtractor(const ptree& config) {
+    const std::string type = config.get_value<std::string>();
+    const float scaleFactor = config.get<float>("scale", 1.f);
+    std::shared_ptr<DirectPyramidFeatureExtractor> extractor;
+    if (type == "hog" || type == "ehog") {
+        extractor = createPyramidExtractor(config.get_child("pyramid"));
+        extractor->addLayerFilter(std::make_shared<GradientFilter>(config.get<int>("gradientKernel"), config.get<int>("blurKernel")));
+        extractor->addLayerFilter(std::make_shared<GradientBinningFilter>(config.get<int>("bins"), flag(config, "signed"), flag(config, "interpolate")));
+        if (type == "hog")
+            extractor->addPatchFilter(createHogFilter(config.get<int>("bins"), config.get_child("histogram")));
+        else
+            extractor->addPatchFilter(std::make_shared<ExtendedHogFilter>(config.get<int>("bins"), config.get<int>("histogram.cellSize"), flag(config, "histogram.interpolate"),
+                                                                          flag(config, "histogram.signedAndUnsigned"), config.get<float>("histogram.alpha")));
+    } else if (type == "lbp" || type == "glbp") {
+        extractor = createPyramidExtractor(config.get_child("pyramid"));
+        std::shared_ptr<LbpFilter> lbpFilter = createLbpFilter(config.get<std::string>("type"));
+        if (type == "glbp") {
+            extractor->addLayerFilter(std::make_shared<GradientFilter>(config.get<int>("gradientKernel"), config.get<int>("blurKernel")));
+            extractor->addLayerFilter(std::make_shared<GradientMagnitudeFilter>());
+        }
+        extractor->addLayerFilter(lbpFilter);
+        extractor->addPatchFilter(createHistogramFilter(lbpFilter->getBinCount(), config.get_child("histogram")));
+    } else if (type == "grayscale" || type == "histeq" || type == "h" || type == "whi") {
+        throw std::invalid_argument("tracking: the gray-patch feature type `" + type + "` is not built for measurement positionDependent");
+    } else if (type == "haar" || type == "ihog" || type == "iehog" || type == "surf") {
+        throw std::invalid_argument("tracking: the integral feature type `" + type + "` is not built for measurement positionDependent");
+    } else {
+        throw std::invalid_argument("tracking: invalid feature type: " + type);
+    }
+    if (scaleFactor == 1.0) return extractor;
+    return std::make_shared<PatchResizingFeatureExtractor>(extractor, scaleFactor);
+}
+
+// the trainable SVM of a `classifier { training { ... } }` block
+inline std::shared_ptr<TrainableSvmClassifier> createTrainableSvm(const ptree& ct) {
+    const ptree& tr = ct.get_child("training");
+    const std::string trainingType = tr.get("type", std::string("libSvm"));
+    std::shared_ptr<TrainableSvmClassifier> svm;
+    std::unique_ptr<ExampleManagement> negatives(new AgeBasedExampleManagement(tr.get("negativeCapacity", 100)));
+    if (trainingType == "libLinear") {
+        auto linear = std::make_shared<liblinear::LibLinearClassifier>(tr.get("c", 1.0), tr.get("bias", 0) != 0);
+        linear->setNegativeExampleManagement(std::move(negatives));
+        svm = linear;
+    } else if (trainingType == "libSvm") {
+        auto dual = libsvm::LibSvmClassifier::createBinarySvm(std::make_shared<LinearKernel>(), tr.get("c", 1.0), tr.get("compensateImbalance", 0) != 0);
+        dual->setNegativeExampleManagement(std::move(negatives));
+        svm = dual;
+    } else {
+        throw std::invalid_argument("tracker_app: invalid training type: " + trainingType);
+    }
+    svm->getSvm()->setThreshold(ct.get("threshold", 0.0f));   // as ProbabilisticSvmClassifier::load reads it
+    return svm;
+}
+
+struct PositionDependentSetup {
+    std::shared_ptr<FeatureExtractor> featureExtractor;
+    std::shared_ptr<TrainableProbabilisticSvmClassifier> classifier;
+    std::shared_ptr<condensation::PositionDependentMeasurementModel> model;
+};
+inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned int seed) {
+    const std::string filter = mt.get("filter", std::string("none"));
+    if (filter == "before" || filter == "after")
+        throw std::invalid_argument("tracking: `filter " + filter + "` (condensation::FilteringClassifierModel) is not built; use `filter none`");
+    if (filter != "none") throw std::invalid_argument("tracking: invalid filter type: " + filter);
+    if (mt.count("validator"))
+        throw std::invalid_argument("tracking: `validator " + mt.get("validator", std::string()) + "` (ClassificationBasedStateValidator) is not built");
+    PositionDependentSetup s;
+    s.featureExtractor = createFeatureExtractor(mt.get_child("feature"));
+    const ptree& ct = mt.get_child("classifier");
+    s.classifier = std::make_shared<FixedTrainableProbabilisticSvmClassifier>(createTrainableSvm(ct), ct.get("logisticA", 0.00556), ct.get("logisticB", -2.95));
+    s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.featureExtractor, s.classifier, seed);
+    s.model->setFrameCounts(mt.get("startFrameCount", 3u), mt.get("stopFrameCount", 0u));
+    s.model->setThresholds(mt.get("targetThreshold", 0.7f), mt.get("confidenceThreshold", 0.95f));
+    s.model->setOffsetFactors(mt.get("positiveOffsetFactor", 0.05f), mt.get("negativeOffsetFactor", 0.5f));
+    s.model->setSamplingProperties(mt.get("sampleNegativesAroundTarget", 0u), mt.get("sampleAdditionalNegatives", 10u), mt.get("sampleTestNegatives", 10u),
+                                   flag(mt, "exploitSymmetry"));
+    return s;
+}
+
+}  // namespace tracking_setup

@@ -114,7 +114,10 @@ private:
 // SingleClassifierModel.hpp:30-69 / SingleClassifierModel.cpp:22-63: one feature extractor, one probabilistic classifier.  The
 // batched evaluate(image, samples) scores all samples with one fd_integral_svm_evaluate_samples when the extractor is a
 // DirectImageFeatureExtractor with the chain of createHaarExtractor or createSurfExtractor (BenchmarkRunner.cpp:202-233,278-286) and
-// the classifier a ProbabilisticSvmClassifier on f32 vectors; any other combination runs the per-sample loop.  (The reference's
+// the classifier a ProbabilisticSvmClassifier on f32 vectors, and with one fd_hist_svm_evaluate_samples when the extractor is a
+// DirectPyramidFeatureExtractor (itself, not wrapped in a PatchResizingFeatureExtractor) whose patch filter is one histogram filter or
+// one ExtendedHogFilter on bin-image layers (the hog, lbp, glbp and ehog feature types) and the classifier a ProbabilisticSvmClassifier
+// or a TrainableProbabilisticSvmClassifier on f32 vectors; any other combination runs the per-sample loop.  (The reference's
 // result cache per patch is not kept: the results are the same.)  getFusedEvaluationCount / getLoopEvaluationCount (not in the
 // reference) tell which of the two ran: the results do not.
 class SingleClassifierModel : public MeasurementModel {
@@ -130,6 +133,86 @@ private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticClassifier> classifier;
     int fusedEvaluations = 0, loopEvaluations = 0;
+};
+
+// PositionDependentMeasurementModel.hpp / .cpp:28-274: a measurement model that learns its classifier from the target position --
+// the frame counters, the target-threshold gate, 1 or 5 positives, 6 / 18 / 26 negatives around the target, the weight-ordered
+// additional negatives taken from the particles, random negatives and random test negatives, the confidence-filtered retrain
+// against the unfiltered one, exploitSymmetry (cv::flip(.., 1) of the patch data).
+// Not the reference's: a std::mt19937(seed) constructor argument replaces the default-constructed boost::mt19937, and
+// distribution(generator, n) is (uint64(engine()) * n) >> 32 -- one 32-bit draw per call, the result in [0, n); n <= 0 throws
+// invalid_argument (undefined in the reference).  With a DirectPyramidFeatureExtractor on a histogram or extended-HOG chain every
+// sample set of one adapt (positives, negatives, test negatives) is extracted in one device call, whether a random sample has a
+// window is decided on the host by the extractor's own rule (fd_pyramid_sample_windows), and with a (Trainable)ProbabilisticSvm
+// classifier the confidence predicates score all vectors of a set in one call.  exploitSymmetry mirrors patch data as cv::flip(.., 1)
+// mirrors the reference's Mat: an ExtendedHogFilter descriptor is rows x cols cells of bins (+ bins / 2) + 4 channels there and rows x
+// cols * channels CV_32FC1 here, so for a DirectPyramidFeatureExtractor on an ehog chain (also behind a PatchResizingFeatureExtractor) the
+// cells of a row change places and every cell keeps its channel order; all other patch data is flipped element by element, which is the
+// reference's result for single-channel data (an ExtendedHogFilter reached through any other extractor type is not recognised).
+// getLastAdaptation / getAdaptationCount (not in the reference) tell what the last adapt that reached a retraining chose.
+class PositionDependentMeasurementModel : public AdaptiveMeasurementModel {
+public:
+    PositionDependentMeasurementModel(std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                      std::shared_ptr<classification::TrainableProbabilisticClassifier> classifier,
+                                      unsigned int seed = std::mt19937::default_seed);
+    PositionDependentMeasurementModel(std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                      std::shared_ptr<classification::TrainableProbabilisticClassifier> classifier,
+                                      unsigned int seed = std::mt19937::default_seed);
+    void update(std::shared_ptr<imageprocessing::VersionedImage> image) override;
+    void evaluate(Sample& sample) const override;
+    void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override;
+    bool isUsable() const override { return usable; }
+    void reset() override;
+    bool initialize(std::shared_ptr<imageprocessing::VersionedImage> image, Sample& target) override;
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples, const Sample& target) override;
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples) override;
+    void setFrameCounts(unsigned int startFrameCount = 3, unsigned int stopFrameCount = 0) {
+        this->startFrameCount = startFrameCount;
+        this->stopFrameCount = stopFrameCount;
+    }
+    void setThresholds(float targetThreshold = 0.7f, float confidenceThreshold = 0.95f) {
+        this->targetThreshold = targetThreshold;
+        this->confidenceThreshold = confidenceThreshold;
+    }
+    void setOffsetFactors(float positiveOffsetFactor = 0.05f, float negativeOffsetFactor = 0.5f) {
+        this->positiveOffsetFactor = positiveOffsetFactor;
+        this->negativeOffsetFactor = negativeOffsetFactor;
+    }
+    void setSamplingProperties(unsigned int sampleNegativesAroundTarget = 0, unsigned int sampleAdditionalNegatives = 10,
+                               unsigned int sampleTestNegatives = 10, bool exploitSymmetry = false) {
+        this->sampleNegativesAroundTarget = sampleNegativesAroundTarget;
+        this->sampleAdditionalNegatives = sampleAdditionalNegatives;
+        this->sampleTestNegatives = sampleTestNegatives;
+        this->exploitSymmetry = exploitSymmetry;
+    }
+    // not in the reference: the samples {x, y, size} the last adapt that reached a retraining chose and the vectors it passed on (the
+    // Mats share their buffers with the classifier's examples); one record is kept, getAdaptationCount counts the retrainings
+    struct AdaptationRecord {
+        std::vector<cv::Rect> positives, negatives, testNegatives;   // Rect(x, y, size, size): centre and size, not bounds
+        std::vector<cv::Mat> positiveVectors, negativeVectors;
+    };
+    const AdaptationRecord& getLastAdaptation() const { return lastAdaptation; }
+    size_t getAdaptationCount() const { return adaptationCount; }
+    std::shared_ptr<MeasurementModel> getMeasurementModel() const { return measurementModel; }
+private:
+    int draw(int n);   // distribution(generator, n)
+    Sample createRandomSample(const cv::Mat& image);
+    bool hasWindow(int x, int y, int width, int height) const;
+    // the patch data of every sample that has a patch; square: extracted with (size, size) as the random samples are
+    std::vector<cv::Mat> extractAll(const std::vector<Sample>& samples, bool square) const;
+    std::vector<double> probabilities(const std::vector<cv::Mat>& vectors) const;
+    std::vector<cv::Mat> getFeatureVectors(const std::vector<Sample>& samples, int predicate /* 0 all, 1 positives, 2 negatives */) const;
+    std::mt19937 generator;
+    std::shared_ptr<MeasurementModel> measurementModel;
+    std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
+    std::shared_ptr<classification::TrainableProbabilisticClassifier> classifier;
+    bool usable;
+    unsigned int frameCount, startFrameCount, stopFrameCount;
+    float targetThreshold, confidenceThreshold, positiveOffsetFactor, negativeOffsetFactor;
+    unsigned int sampleNegativesAroundTarget, sampleAdditionalNegatives, sampleTestNegatives;
+    bool exploitSymmetry;
+    AdaptationRecord lastAdaptation;
+    size_t adaptationCount = 0;
 };
 
 // ExtendedHogBasedMeasurementModel.hpp / .cpp:60-742, the evaluation half, on one fd_ehog_tracker: update, evaluate(image, samples) with

@@ -159,6 +159,17 @@ public:
     bool signedGradients, interpolate;
 };
 
+// GradientMagnitudeFilter.hpp:39-50 / GradientMagnitudeFilter.cpp:19-42: the magnitude of a two-channel gradient image.  On this
+// backend CV_8UC2 only (the output of GradientFilter: saturate_cast<uchar>(sqrt(x^2 + y^2)) with x, y = value - 127, via
+// fd_gradient_magnitude_image); other depths throw invalid_argument naming the depth.  As a layer filter it is fused: the chain
+// GradientFilter, GradientMagnitudeFilter, LbpFilter (the "glbp" feature type) runs as FD_LAYER_GRADMAG_LBP
+class GradientMagnitudeFilter : public ImageFilter {
+public:
+    using ImageFilter::applyTo;
+    GradientMagnitudeFilter() {}
+    cv::Mat applyTo(const cv::Mat& image, cv::Mat& filtered) const override;
+};
+
 // LbpFilter.hpp (fused as a layer filter; applyTo via fd_lbp_image)
 class LbpFilter : public ImageFilter {
 public:
@@ -301,12 +312,17 @@ public:
     std::shared_ptr<ImageFilter> getApproximatedLayerFilter() const { return approxLayerFilter; }
     bool hasGrayscaleImageFilter() const { return imageChain.size() == 1 && imageChain[0] == FD_IMAGE_GRAY; }
     bool hasNoImageFilter() const { return imageChain.empty(); }
+    // the FD_LAYER_* kind the layer filter chain maps to
+    int getLayerFilterKind() const {
+        return gradient && binning ? FD_LAYER_GRADBIN : (gradient && magnitude && lbp ? FD_LAYER_GRADMAG_LBP : (lbp && !gradient ? FD_LAYER_LBP : FD_LAYER_NONE));
+    }
     ~ImagePyramid();
     ImagePyramid(const ImagePyramid&) = delete;
     ImagePyramid& operator=(const ImagePyramid&) = delete;
     // chains: [GrayscaleFilter] or [GreyWorldNormalizationFilter, GrayscaleFilter]; anything else throws logic_error
     void addImageFilter(const std::shared_ptr<ImageFilter>& filter);
-    void addLayerFilter(const std::shared_ptr<ImageFilter>& filter);   // GradientFilter, GradientBinningFilter, LbpFilter
+    // the chains [GradientFilter, GradientBinningFilter], [LbpFilter] and [GradientFilter, GradientMagnitudeFilter, LbpFilter]
+    void addLayerFilter(const std::shared_ptr<ImageFilter>& filter);
     void update(const cv::Mat& image);
     void update(const std::shared_ptr<VersionedImage>& image);
     void setSource(const cv::Mat& image) { setSource(std::make_shared<VersionedImage>(image)); }
@@ -357,6 +373,7 @@ private:
     std::shared_ptr<GradientFilter> gradient;
     std::shared_ptr<GradientBinningFilter> binning;
     std::shared_ptr<LbpFilter> lbp;
+    std::shared_ptr<GradientMagnitudeFilter> magnitude;
     std::vector<int> imageChain;          // addImageFilter: FD_IMAGE_GREYWORLD_GRAY for a GreyWorldNormalizationFilter, FD_IMAGE_GRAY for a GrayscaleFilter
     mutable std::vector<std::shared_ptr<ImagePyramidLayer>> layers;
     mutable bool layersValid;
@@ -433,6 +450,13 @@ public:
     std::vector<std::shared_ptr<Patch>> extract(int stepX, int stepY, cv::Rect roi = cv::Rect(), int firstLayer = -1, int lastLayer = -1,
                                                 int stepLayer = 1) const override;
     std::shared_ptr<Patch> extract(int layer, int x, int y) const override;
+    // not in the reference: extract(x, y, width, height) for every sample {x - width / 2, y - height / 2, width, height} at once,
+    // null for a sample without a window.  One device call (fd_hist_extract_samples / fd_ehog_extract_samples) when the patch filter
+    // is one histogram filter or one ExtendedHogFilter (the hog, lbp, glbp and ehog feature types); the per-sample path otherwise.
+    // The patch geometry is the one extractFromLayer computes.
+    std::vector<std::shared_ptr<Patch>> extract(const std::vector<cv::Rect>& samples) const;
+    // the parameters of that device call: kind FD_SAMPLES_HIST (hp) or FD_SAMPLES_EHOG (ep); false: no such chain
+    bool getSampledChain(int& kind, fd_hist_params& hp, fd_ehog_patch_params& ep) const;
     int getLayerIndex(int width, int height) const override;
     double getMinScaleFactor() const override { return pyramid->getMinScaleFactor(); }
     double getMaxScaleFactor() const override { return pyramid->getMaxScaleFactor(); }
@@ -450,13 +474,14 @@ public:
     bool hasHistEq64() const { return (bool)histeq; }
     std::shared_ptr<HogFilter> getHogFilter() const { return hog; }   // non-interpolating square HogFilter: k_hog_tile path
     std::shared_ptr<HistogramFilter> getHistogramFilter() const { return hist; }
+    std::shared_ptr<ExtendedHogFilter> getExtendedHogFilter() const { return ehog; }   // the only patch filter of an ehog chain
     // complete whi chain (WhiteningFilter, HistogramEqualizationFilter, ConversionFilter(CV_32F, 1/127.5, -1), UnitNormFilter(L2))
     std::shared_ptr<WhiteningFilter> getWhiChain() const { return whiStage == 4 ? whitening : nullptr; }
     // u8 feature space (0 gray, 1 hq64 = HistEq64Filter, 2 histeq = HistogramEqualizationFilter) followed by a
     // ConversionFilter(CV_32F, scale, shift): the input of a ProbabilisticRvmClassifier (fd_detect_rvm)
     std::shared_ptr<ConversionFilter> getConversion() const { return whiStage == 0 ? conversion : nullptr; }
     int getU8FeatureSpace() const { return histeq ? 1 : (equalization ? 2 : 0); }
-    bool hasPatchFilters() const { return histeq || hist || whitening || equalization || conversion || reshaping; }
+    bool hasPatchFilters() const { return histeq || hist || ehog || whitening || equalization || conversion || reshaping; }
 private:
     std::shared_ptr<Patch> extractFromLayer(const ImagePyramidLayer& layer, cv::Rect bounds) const;
     std::shared_ptr<ImagePyramid> pyramid;
@@ -464,6 +489,7 @@ private:
     std::shared_ptr<HistEq64Filter> histeq;
     std::shared_ptr<HogFilter> hog;
     std::shared_ptr<HistogramFilter> hist;
+    std::shared_ptr<ExtendedHogFilter> ehog;   // alone in the chain: per Mat, and fused for sampled windows (extract(samples))
     std::shared_ptr<WhiteningFilter> whitening;
     std::shared_ptr<HistogramEqualizationFilter> equalization;
     std::shared_ptr<ConversionFilter> conversion;
@@ -584,6 +610,7 @@ public:
         }
         return patch;
     }
+    std::shared_ptr<FeatureExtractor> getExtractor() const { return extractor; }
 private:
     std::shared_ptr<FeatureExtractor> extractor;
     double factor, yOffset, xOffset;

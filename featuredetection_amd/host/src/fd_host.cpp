@@ -129,6 +129,15 @@ Mat GradientBinningFilter::applyTo(const Mat& image, Mat& filtered) const {
     filtered = dst;
     return filtered;
 }
+Mat GradientMagnitudeFilter::applyTo(const Mat& image, Mat& filtered) const {
+    if (image.channels() != 2) throw std::invalid_argument("GradientMagnitudeFilter: the image must have two channels");   // GradientMagnitudeFilter.cpp:20-21
+    if (image.depth() != CV_8U) throw std::invalid_argument("GradientMagnitudeFilter: unsupported image depth " + std::to_string(image.depth()));
+    Mat src = contiguous(image);
+    Mat dst(src.rows, src.cols, CV_8UC1);
+    check(fd_gradient_magnitude_image(context(), src.data, src.cols, src.rows, dst.data));
+    filtered = dst;
+    return filtered;
+}
 Mat LbpFilter::applyTo(const Mat& image, Mat& filtered) const {
     if (image.type() != CV_8UC1) throw std::invalid_argument("LbpFilter: the image must be of type CV_8UC1");
     Mat src = contiguous(image);
@@ -481,7 +490,11 @@ void ImagePyramid::addLayerFilter(const shared_ptr<ImageFilter>& filter) {
     if (auto g = std::dynamic_pointer_cast<GradientFilter>(filter)) gradient = g;
     else if (auto b = std::dynamic_pointer_cast<GradientBinningFilter>(filter)) binning = b;
     else if (auto l = std::dynamic_pointer_cast<LbpFilter>(filter)) lbp = l;
-    else throw std::logic_error("ImagePyramid: unsupported layer filter (GradientFilter, GradientBinningFilter, LbpFilter are available)");
+    else if (auto m = std::dynamic_pointer_cast<GradientMagnitudeFilter>(filter)) {
+        if (!gradient || binning || lbp) throw std::logic_error("ImagePyramid: GradientMagnitudeFilter is available in the chain GradientFilter, GradientMagnitudeFilter, LbpFilter");
+        magnitude = m;
+    }
+    else throw std::logic_error("ImagePyramid: unsupported layer filter (GradientFilter, GradientBinningFilter, GradientMagnitudeFilter, LbpFilter are available)");
     applyLayerFilterConfig();
 }
 void ImagePyramid::applyLayerFilterConfig() {
@@ -491,7 +504,12 @@ void ImagePyramid::applyLayerFilterConfig() {
                                           gradient->kernelSize, 0));
         check(fd_pyramid_set_gradient_blur(handle, gradient->blurKernelSize > 0 ? gradient->blurKernelSize : 0));
     }
-    else if (lbp)
+    else if (gradient && magnitude && lbp)
+    {
+        check(fd_pyramid_set_layer_filter(handle, FD_LAYER_GRADMAG_LBP, 0, 0, 0, gradient->kernelSize, (int)lbp->type));
+        check(fd_pyramid_set_gradient_blur(handle, gradient->blurKernelSize > 0 ? gradient->blurKernelSize : 0));
+    }
+    else if (lbp && !gradient)
         check(fd_pyramid_set_layer_filter(handle, FD_LAYER_LBP, 0, 0, 0, 1, (int)lbp->type));
     version = Version();
 }
@@ -503,7 +521,7 @@ void ImagePyramid::update(const shared_ptr<VersionedImage>& image) {
         update();
         return;
     }
-    if ((gradient != nullptr) != (binning != nullptr))
+    if (magnitude ? (!gradient || !lbp || binning) : ((gradient != nullptr) != (binning != nullptr)))
         throw std::logic_error("ImagePyramid: GradientFilter and GradientBinningFilter have to be added together");
     // a GreyWorldNormalizationFilter alone would give three-channel layers
     if (!imageChain.empty() && imageChain.back() != FD_IMAGE_GRAY) throw std::logic_error(kImageFilterChains);
@@ -786,6 +804,7 @@ Mat AggregationFilter::applyTo(const Mat&, Mat&) const {
 DirectPyramidFeatureExtractor::DirectPyramidFeatureExtractor(shared_ptr<ImagePyramid> pyramid, int width, int height)
     : pyramid(pyramid), patchWidth(width), patchHeight(height) {}
 void DirectPyramidFeatureExtractor::addPatchFilter(shared_ptr<ImageFilter> filter) {
+    if (ehog) throw std::logic_error("DirectPyramidFeatureExtractor: ExtendedHogFilter is available as the only patch filter (the ehog feature type); nothing may follow it");
     if (auto rf = std::dynamic_pointer_cast<ReshapingFilter>(filter)) {   // the fused kernels work on flat vectors: nothing to do
         if (rf->rows != 1 || rf->channels > 1) throw std::logic_error("DirectPyramidFeatureExtractor: ReshapingFilter(1) (row vectors) is available in a fused chain");
         reshaping = rf;
@@ -814,8 +833,9 @@ void DirectPyramidFeatureExtractor::addPatchFilter(shared_ptr<ImageFilter> filte
         if (whiStage != 3 || uf->normType != cv::NORM_L2)
             throw std::logic_error("DirectPyramidFeatureExtractor: UnitNormFilter is available as UnitNormFilter(cv::NORM_L2) at the end of the whi chain only");
         whiStage = 4;
-    } else if (std::dynamic_pointer_cast<ExtendedHogFilter>(filter)) {
-        throw std::logic_error("DirectPyramidFeatureExtractor: ExtendedHogFilter is available per patch (applyTo, FilteringFeatureExtractor), not in a fused chain");
+    } else if (auto xf = std::dynamic_pointer_cast<ExtendedHogFilter>(filter)) {
+        if (hasPatchFilters()) throw std::logic_error("DirectPyramidFeatureExtractor: ExtendedHogFilter is available as the only patch filter (the ehog feature type)");
+        ehog = xf;   // extract(x, y, width, height) per Mat, extract(samples) fused; no strided scan
     } else if (auto hf = std::dynamic_pointer_cast<HistogramFilter>(filter)) {
         hist = hf;
         auto g = std::dynamic_pointer_cast<HogFilter>(filter);
@@ -850,6 +870,64 @@ shared_ptr<Patch> DirectPyramidFeatureExtractor::extract(int x, int y, int width
     if (!layer) return shared_ptr<Patch>();
     return extractFromLayer(*layer, cv::Rect(layer->getScaled(x - width / 2), layer->getScaled(y - height / 2), patchWidth, patchHeight));
 }
+bool DirectPyramidFeatureExtractor::getSampledChain(int& kind, fd_hist_params& hp, fd_ehog_patch_params& ep) const {
+    if (histeq || whitening || equalization || conversion || pyramid->getSourcePyramid()) return false;
+    const int layerKind = pyramid->getLayerFilterKind();
+    if (layerKind == FD_LAYER_NONE || (ehog && layerKind != FD_LAYER_GRADBIN)) return false;
+    if (ehog) {
+        kind = FD_SAMPLES_EHOG;
+        ep = fd_ehog_patch_params{patchWidth, patchHeight, ehog->binCount, ehog->cellWidth, ehog->cellHeight, ehog->interpolate, ehog->signedAndUnsigned, ehog->alpha};
+        return true;
+    }
+    if (!hist) return false;
+    kind = FD_SAMPLES_HIST;
+    hp = hist_params_of(*hist, patchWidth, patchHeight, 1, 1);
+    return true;
+}
+vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv::Rect>& samples) const {
+    vector<shared_ptr<Patch>> patches(samples.size());
+    int kind = 0;
+    fd_hist_params hp;
+    fd_ehog_patch_params ep;
+    if (!getSampledChain(kind, hp, ep)) {   // the per-sample path
+        for (size_t i = 0; i < samples.size(); ++i)
+            patches[i] = extract(samples[i].x + samples[i].width / 2, samples[i].y + samples[i].height / 2, samples[i].width, samples[i].height);
+        return patches;
+    }
+    const int n = (int)samples.size();
+    if (n == 0) return patches;
+    // the centre form the rule works on: x - width / 2 is the rectangle's x again for every width
+    vector<int32_t> xywh((size_t)4 * n), windows((size_t)4 * n);
+    for (int i = 0; i < n; ++i) {
+        xywh[4 * i] = samples[i].x + samples[i].width / 2; xywh[4 * i + 1] = samples[i].y + samples[i].height / 2;
+        xywh[4 * i + 2] = samples[i].width; xywh[4 * i + 3] = samples[i].height;
+    }
+    int index, lw, lh, ch = 1; double scale;
+    if (fd_pyramid_layer_count(pyramid->native()) > 0) fd_pyramid_layer_info(pyramid->native(), 0, &index, &scale, &lw, &lh, &ch);
+    const int F = kind == FD_SAMPLES_EHOG ? fd_ehog_feature_length(&ep, ch) : fd_hist_feature_length(&hp, ch);
+    if (F < 0) throw std::invalid_argument("DirectPyramidFeatureExtractor: invalid histogram filter parameters for this patch size");
+    Mat all(n, F, CV_32FC1);
+    vector<uint8_t> valid((size_t)n);
+    if (kind == FD_SAMPLES_EHOG) check(fd_ehog_extract_samples(context(), pyramid->native(), &ep, n, xywh.data(), valid.data(), all.ptr<float>(0)));
+    else check(fd_hist_extract_samples(context(), pyramid->native(), &hp, n, xywh.data(), valid.data(), all.ptr<float>(0)));
+    check(fd_pyramid_sample_windows(pyramid->native(), patchWidth, patchHeight, n, xywh.data(), windows.data()));
+    const int ehogRows = kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(patchHeight) / static_cast<double>(ehog->cellHeight)) : 1;
+    for (int i = 0; i < n; ++i) {
+        if (!valid[i]) continue;
+        fd_pyramid_layer_info(pyramid->native(), windows[4 * i], &index, &scale, &lw, &lh, &ch);
+        // extractFromLayer's geometry (ImagePyramidLayer::getOriginal)
+        const int ow = cv::cvRound(patchWidth / scale), oh = cv::cvRound(patchHeight / scale);
+        const int ox = cv::cvRound(windows[4 * i + 1] / scale) + ow / 2, oy = cv::cvRound(windows[4 * i + 2] / scale) + oh / 2;
+        Mat row = Mat(all, cv::Rect(0, i, F, 1)).clone();
+        if (kind == FD_SAMPLES_EHOG) {   // rows x cols * channels, as ExtendedHogFilter::applyTo stores it
+            Mat shaped(ehogRows, F / ehogRows, CV_32FC1);
+            std::memcpy(shaped.data, row.data, sizeof(float) * (size_t)F);
+            row = shaped;
+        }
+        patches[i] = make_shared<Patch>(ox, oy, ow, oh, row);
+    }
+    return patches;
+}
 shared_ptr<Patch> DirectPyramidFeatureExtractor::extract(int layerIndex, int x, int y) const {
     auto layer = pyramid->getLayer(layerIndex);
     if (!layer) return shared_ptr<Patch>();
@@ -879,6 +957,7 @@ vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(int stepX, int 
         return patches;
     }
     if (whiStage != 0 && whiStage != 4) throw std::logic_error("DirectPyramidFeatureExtractor: incomplete whi filter chain");
+    if (ehog) throw std::logic_error("DirectPyramidFeatureExtractor: ExtendedHogFilter is available for sampled windows and per patch, not for a strided scan");
     if (whiStage == 4) {
         fd_whi_params wp = {patchWidth, patchHeight, stepX, stepY, whitening->alpha, whitening->cutoffFrequency};
         const int F = patchWidth * patchHeight;
@@ -2674,6 +2753,19 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
         if (!haar && direct->getSurfChain(g, c)) { surf.gradient_count = g; surf.cell_count = c; }
         fused = haar || surf.gradient_count > 0;
     }
+    // sampled pyramid windows: a native DirectPyramidFeatureExtractor (not wrapped) on a histogram or extended-HOG chain with a
+    // ProbabilisticSvmClassifier or a TrainableProbabilisticSvmClassifier on f32 vectors: one fd_hist_svm_evaluate_samples
+    auto* pyramidDirect = fused ? nullptr : dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
+    int sampledKind = 0;
+    fd_hist_params histParams;
+    fd_ehog_patch_params ehogParams;
+    if (pyramidDirect) {
+        if (!psvm)
+            if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
+        fused = psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F &&
+                pyramidDirect->getSampledChain(sampledKind, histParams, ehogParams);
+        if (!fused) pyramidDirect = nullptr;
+    }
     if (!fused) {   // MeasurementModel.hpp: the per-sample loop
         ++loopEvaluations;
         for (shared_ptr<Sample> sample : samples) evaluate(*sample);
@@ -2690,14 +2782,280 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
     const fd_svm* svm = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-    fd_haar_params hp;
-    if (haar) hp = haar->params();
-    check(fd_integral_svm_evaluate_samples(context(), direct->native(), haar ? FD_INTEGRAL_HAAR : FD_INTEGRAL_SURF, haar ? (const void*)&hp : (const void*)&surf, svm, n,
-                                           xywh.data(), target.data(), weight.data()));
+    if (pyramidDirect) {
+        check(fd_hist_svm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), sampledKind,
+                                           sampledKind == FD_SAMPLES_EHOG ? (const void*)&ehogParams : (const void*)&histParams, svm, n, xywh.data(),
+                                           target.data(), weight.data()));
+    } else {
+        fd_haar_params hp;
+        if (haar) hp = haar->params();
+        check(fd_integral_svm_evaluate_samples(context(), direct->native(), haar ? FD_INTEGRAL_HAAR : FD_INTEGRAL_SURF, haar ? (const void*)&hp : (const void*)&surf, svm, n,
+                                               xywh.data(), target.data(), weight.data()));
+    }
     for (int i = 0; i < n; ++i) {
         samples[i]->setTarget(target[i] != 0);
         samples[i]->setWeight(weight[i]);
     }
+}
+
+// ---- PositionDependentMeasurementModel (PositionDependentMeasurementModel.cpp:28-274) --------------------------------------------------
+PositionDependentMeasurementModel::PositionDependentMeasurementModel(shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                                                     shared_ptr<classification::TrainableProbabilisticClassifier> classifier, unsigned int seed)
+    : PositionDependentMeasurementModel(make_shared<SingleClassifierModel>(featureExtractor, classifier), featureExtractor, classifier, seed) {}
+PositionDependentMeasurementModel::PositionDependentMeasurementModel(shared_ptr<MeasurementModel> measurementModel,
+                                                                     shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                                                     shared_ptr<classification::TrainableProbabilisticClassifier> classifier, unsigned int seed)
+    : generator(seed), measurementModel(measurementModel), featureExtractor(featureExtractor), classifier(classifier), usable(false), frameCount(0),
+      startFrameCount(3), stopFrameCount(0), targetThreshold(0.7f), confidenceThreshold(0.95f), positiveOffsetFactor(0.05f), negativeOffsetFactor(0.5f),
+      sampleNegativesAroundTarget(0), sampleAdditionalNegatives(10), sampleTestNegatives(10), exploitSymmetry(false) {}
+void PositionDependentMeasurementModel::update(shared_ptr<imageprocessing::VersionedImage> image) { measurementModel->update(image); }
+void PositionDependentMeasurementModel::evaluate(Sample& sample) const { measurementModel->evaluate(sample); }
+void PositionDependentMeasurementModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
+    measurementModel->evaluate(image, samples);
+}
+void PositionDependentMeasurementModel::reset() {
+    classifier->reset();
+    usable = false;
+}
+bool PositionDependentMeasurementModel::initialize(shared_ptr<imageprocessing::VersionedImage> image, Sample& target) {
+    vector<shared_ptr<Sample>> empty;
+    return adapt(image, empty, target);
+}
+int PositionDependentMeasurementModel::draw(int n) {
+    if (n <= 0) throw std::invalid_argument("PositionDependentMeasurementModel: the image is too small for random samples (range " + std::to_string(n) + ")");
+    return (int)(((uint64_t)generator() * (uint64_t)n) >> 32);
+}
+Sample PositionDependentMeasurementModel::createRandomSample(const Mat& image) {   // :246-254
+    int minSize = (int)(0.1 * std::min(image.cols, image.rows));
+    int maxSize = (int)(0.9 * std::min(image.cols, image.rows));
+    int size = draw(maxSize - minSize) + minSize;
+    int halfSize = size / 2;
+    int x = draw(image.cols - size) + halfSize;
+    int y = draw(image.rows - size) + halfSize;
+    return Sample(x, y, size);
+}
+bool PositionDependentMeasurementModel::hasWindow(int x, int y, int width, int height) const {
+    auto* direct = dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
+    int kind;
+    fd_hist_params hp;
+    fd_ehog_patch_params ep;
+    if (direct && direct->getSampledChain(kind, hp, ep)) {   // the extractor's rule, on the host
+        const int32_t s[4] = {x, y, width, height};
+        int32_t w[4];
+        check(fd_pyramid_sample_windows(direct->getPyramid()->native(), direct->getPatchWidth(), direct->getPatchHeight(), 1, s, w));
+        return w[3] != 0;
+    }
+    return (bool)featureExtractor->extract(x, y, width, height);
+}
+vector<Mat> PositionDependentMeasurementModel::extractAll(const vector<Sample>& samples, bool square) const {
+    vector<Mat> data;
+    data.reserve(samples.size());
+    auto* direct = dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
+    if (direct) {   // one batched extract for the set (the per-sample path inside when the chain is not a sampled one)
+        vector<cv::Rect> rects;
+        rects.reserve(samples.size());
+        for (const Sample& s : samples) {
+            const int w = s.getWidth(), h = square ? s.getSize() : s.getHeight();
+            rects.push_back(cv::Rect(s.getX() - w / 2, s.getY() - h / 2, w, h));
+        }
+        for (const auto& patch : direct->extract(rects))
+            if (patch) data.push_back(patch->getData());
+        return data;
+    }
+    for (const Sample& s : samples) {
+        auto patch = featureExtractor->extract(s.getX(), s.getY(), s.getWidth(), square ? s.getSize() : s.getHeight());
+        if (patch) data.push_back(patch->getData());
+    }
+    return data;
+}
+vector<double> PositionDependentMeasurementModel::probabilities(const vector<Mat>& vectors) const {
+    vector<double> p(vectors.size());
+    auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get());
+    const classification::ProbabilisticSvmClassifier* psvm = trainable ? trainable->getProbabilisticSvm().get() : nullptr;
+    const bool batch = psvm && !vectors.empty() && !psvm->getSvm()->getSupportVectors().empty() && vectors[0].depth() == CV_32F &&
+                       psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+    if (batch) {   // one scoring call for the set
+        const size_t d = (size_t)vectors[0].rows * vectors[0].cols * vectors[0].channels();
+        vector<float> rows(vectors.size() * d);
+        for (size_t i = 0; i < vectors.size(); ++i) {
+            Mat v = contiguous(vectors[i]);
+            if ((size_t)v.rows * v.cols * v.channels() != d) throw std::invalid_argument("PositionDependentMeasurementModel: feature vectors of different sizes");
+            std::memcpy(rows.data() + i * d, v.data, sizeof(float) * d);
+        }
+        vector<double> dist(vectors.size());
+        check(fd_svm_distance_batch(context(), psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()), rows.data(), (int64_t)vectors.size(), dist.data()));
+        for (size_t i = 0; i < vectors.size(); ++i) p[i] = psvm->getProbability(dist[i]).second;
+        return p;
+    }
+    for (size_t i = 0; i < vectors.size(); ++i) p[i] = classifier->getProbability(vectors[i]).second;
+    return p;
+}
+// floats per cell of an extractor's patch data where the reference's Mat would carry them as channels: the descriptor of the
+// ExtendedHogFilter of an ehog chain (also behind a PatchResizingFeatureExtractor), 1 for everything else
+static int patch_channels(const imageprocessing::FeatureExtractor* extractor) {
+    while (auto* resizing = dynamic_cast<const imageprocessing::PatchResizingFeatureExtractor*>(extractor)) extractor = resizing->getExtractor().get();
+    auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor);
+    if (!direct || !direct->getExtendedHogFilter()) return 1;
+    const auto f = direct->getExtendedHogFilter();
+    return f->binCount + (f->signedAndUnsigned ? f->binCount / 2 : 0) + 4;
+}
+// cv::flip(data, mirrored, 1) of a Mat whose columns are cells of `channels` floats: the cells of a row in reverse order, each as it is
+static Mat flip_cells(const Mat& data, int channels) {
+    if (channels <= 1 || data.type() != CV_32FC1 || data.cols % channels != 0) {
+        Mat mirrored;
+        cv::flip(data, mirrored, 1);
+        return mirrored;
+    }
+    Mat mirrored(data.rows, data.cols, CV_32FC1);
+    const int cells = data.cols / channels;
+    for (int r = 0; r < data.rows; ++r)
+        for (int c = 0; c < cells; ++c)
+            std::memcpy(mirrored.ptr<float>(r) + (size_t)(cells - 1 - c) * channels, data.ptr<float>(r) + (size_t)c * channels, sizeof(float) * (size_t)channels);
+    return mirrored;
+}
+vector<Mat> PositionDependentMeasurementModel::getFeatureVectors(const vector<Sample>& samples, int predicate) const {   // :256-274
+    vector<Mat> patches = extractAll(samples, false);
+    vector<double> p;
+    if (predicate != 0) p = probabilities(patches);
+    vector<Mat> trainingExamples;
+    trainingExamples.reserve(exploitSymmetry ? 2 * patches.size() : patches.size());
+    const int channels = exploitSymmetry ? patch_channels(featureExtractor.get()) : 1;
+    for (size_t i = 0; i < patches.size(); ++i) {
+        if (predicate == 1 && !(p[i] < confidenceThreshold)) continue;
+        if (predicate == 2 && !(p[i] > 1 - confidenceThreshold)) continue;
+        trainingExamples.push_back(patches[i]);
+        if (exploitSymmetry) trainingExamples.push_back(flip_cells(patches[i], channels));
+    }
+    return trainingExamples;
+}
+bool PositionDependentMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage> image, const vector<shared_ptr<Sample>>& samples, const Sample& target) {
+    if (!isUsable()) {
+        frameCount++;
+        if (frameCount < startFrameCount) return false;
+    } else {
+        frameCount = 0;
+    }
+    featureExtractor->update(image);
+    vector<Mat> targetData = extractAll(vector<Sample>{target}, false);
+    if (targetData.empty()) return false;
+    if (isUsable() && classifier->getProbability(targetData[0]).second < targetThreshold) return false;
+
+    vector<Sample> positiveSamples;
+    if (positiveOffsetFactor == 0) {
+        positiveSamples.push_back(target);
+    } else {
+        int offset = std::max(1, (int)(positiveOffsetFactor * target.getSize()));
+        positiveSamples.push_back(target);
+        positiveSamples.push_back(Sample(target.getX() - offset, target.getY(), target.getSize()));
+        positiveSamples.push_back(Sample(target.getX() + offset, target.getY(), target.getSize()));
+        positiveSamples.push_back(Sample(target.getX(), target.getY() - offset, target.getSize()));
+        positiveSamples.push_back(Sample(target.getX(), target.getY() + offset, target.getSize()));
+    }
+
+    vector<Sample> negativeSamples;
+    int boundOffset = (int)(negativeOffsetFactor * target.getSize());
+    int xLowBound = target.getX() - boundOffset;
+    int xHighBound = target.getX() + boundOffset;
+    int yLowBound = target.getY() - boundOffset;
+    int yHighBound = target.getY() + boundOffset;
+    float downScaleBound = (1 - negativeOffsetFactor);
+    float upScaleBound = 1 / downScaleBound;
+    int sizeLowBound = (int)(downScaleBound * target.getSize());
+    int sizeHighBound = (int)(upScaleBound * target.getSize());
+    const int tx = target.getX(), ty = target.getY(), ts = target.getSize();
+    if (sampleNegativesAroundTarget > 0) {
+        negativeSamples.push_back(Sample(xLowBound, ty, ts));
+        negativeSamples.push_back(Sample(xHighBound, ty, ts));
+        negativeSamples.push_back(Sample(tx, yLowBound, ts));
+        negativeSamples.push_back(Sample(tx, yHighBound, ts));
+        negativeSamples.push_back(Sample(tx, ty, sizeLowBound));
+        negativeSamples.push_back(Sample(tx, ty, sizeHighBound));
+        if (sampleNegativesAroundTarget > 1) {
+            negativeSamples.push_back(Sample(xLowBound, yLowBound, ts));
+            negativeSamples.push_back(Sample(xLowBound, yHighBound, ts));
+            negativeSamples.push_back(Sample(xHighBound, yLowBound, ts));
+            negativeSamples.push_back(Sample(xHighBound, yHighBound, ts));
+            negativeSamples.push_back(Sample(xLowBound, ty, sizeLowBound));
+            negativeSamples.push_back(Sample(xLowBound, ty, sizeHighBound));
+            negativeSamples.push_back(Sample(xHighBound, ty, sizeLowBound));
+            negativeSamples.push_back(Sample(xHighBound, ty, sizeHighBound));
+            negativeSamples.push_back(Sample(tx, yLowBound, sizeLowBound));
+            negativeSamples.push_back(Sample(tx, yLowBound, sizeHighBound));
+            negativeSamples.push_back(Sample(tx, yHighBound, sizeLowBound));
+            negativeSamples.push_back(Sample(tx, yHighBound, sizeHighBound));
+            if (sampleNegativesAroundTarget > 2) {
+                negativeSamples.push_back(Sample(xLowBound, yLowBound, sizeLowBound));
+                negativeSamples.push_back(Sample(xLowBound, yLowBound, sizeHighBound));
+                negativeSamples.push_back(Sample(xLowBound, yHighBound, sizeLowBound));
+                negativeSamples.push_back(Sample(xLowBound, yHighBound, sizeHighBound));
+                negativeSamples.push_back(Sample(xHighBound, yLowBound, sizeLowBound));
+                negativeSamples.push_back(Sample(xHighBound, yLowBound, sizeHighBound));
+                negativeSamples.push_back(Sample(xHighBound, yHighBound, sizeLowBound));
+                negativeSamples.push_back(Sample(xHighBound, yHighBound, sizeHighBound));
+            }
+        }
+    }
+    auto outside = [&](const Sample& s) {
+        return s.getX() <= xLowBound || s.getX() >= xHighBound || s.getY() <= yLowBound || s.getY() >= yHighBound || s.getSize() <= sizeLowBound ||
+               s.getSize() >= sizeHighBound;
+    };
+    if (sampleAdditionalNegatives > 0) {
+        vector<Sample> additionalNegatives;
+        additionalNegatives.reserve(sampleAdditionalNegatives);
+        for (const shared_ptr<Sample>& sample : samples) {
+            if (!outside(*sample)) continue;
+            if (additionalNegatives.size() < sampleAdditionalNegatives) {
+                auto low = std::lower_bound(additionalNegatives.begin(), additionalNegatives.end(), *sample,
+                                            [](const Sample& a, const Sample& b) { return a.getWeight() < b.getWeight(); });
+                additionalNegatives.insert(low, *sample);
+            } else if (additionalNegatives.front().getWeight() < sample->getWeight()) {
+                additionalNegatives.front() = *sample;
+                for (unsigned int i = 1; i < additionalNegatives.size() && additionalNegatives[i - 1].getWeight() > additionalNegatives[i].getWeight(); ++i)
+                    std::swap(additionalNegatives[i - 1], additionalNegatives[i]);
+            }
+        }
+        while (additionalNegatives.size() < sampleAdditionalNegatives) {
+            Sample sample = createRandomSample(image->getData());
+            if (outside(sample) && hasWindow(sample.getX(), sample.getY(), sample.getSize(), sample.getSize())) additionalNegatives.push_back(sample);
+        }
+        negativeSamples.insert(negativeSamples.end(), additionalNegatives.begin(), additionalNegatives.end());
+    }
+
+    vector<Mat> positiveTestExamples;
+    positiveTestExamples.push_back(targetData[0]);
+    vector<Sample> testSamples;
+    testSamples.reserve(sampleTestNegatives);
+    while (testSamples.size() < sampleTestNegatives) {
+        Sample sample = createRandomSample(image->getData());
+        if (outside(sample) && hasWindow(sample.getX(), sample.getY(), sample.getSize(), sample.getSize())) testSamples.push_back(sample);
+    }
+    vector<Mat> negativeTestExamples = extractAll(testSamples, true);
+
+    const bool filtered = isUsable() && confidenceThreshold > 0;
+    const vector<Mat> positives = getFeatureVectors(positiveSamples, filtered ? 1 : 0);
+    const vector<Mat> negatives = getFeatureVectors(negativeSamples, filtered ? 2 : 0);
+    AdaptationRecord record;
+    auto asRect = [](const Sample& s) { return cv::Rect(s.getX(), s.getY(), s.getSize(), s.getSize()); };
+    for (const Sample& s : positiveSamples) record.positives.push_back(asRect(s));
+    for (const Sample& s : negativeSamples) record.negatives.push_back(asRect(s));
+    for (const Sample& s : testSamples) record.testNegatives.push_back(asRect(s));
+    record.positiveVectors = positives;
+    record.negativeVectors = negatives;
+    lastAdaptation = record;
+    ++adaptationCount;
+    usable = classifier->retrain(positives, negatives, positiveTestExamples, negativeTestExamples);
+    return true;
+}
+bool PositionDependentMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage>, const vector<shared_ptr<Sample>>&) {   // :233-244
+    if (isUsable()) frameCount++;
+    if (frameCount == stopFrameCount) {
+        reset();
+        frameCount = 0;
+    } else {
+        const vector<Mat> empty;
+        usable = classifier->retrain(empty, empty);
+    }
+    return false;
 }
 
 

@@ -61,8 +61,12 @@ void fd_pyramid_destroy(fd_pyramid* p);
  *                      (GradientFilter.cpp:16-59, GradientBinningFilter.cpp:18-93); 2 or 4 channels.
  *                      grad_kernel: 1, 3, 5, 7 or FD_GRAD_SCHARR (the reference's CV_SCHARR = -1);
  *                      blur: fd_pyramid_set_gradient_blur (blurKernelSize of the reference's constructor, default 0 = none)
- *  FD_LAYER_LBP        LbpFilter(lbp_type) (LbpFilter.cpp:56-85); 1 channel */
-enum { FD_LAYER_NONE = 0, FD_LAYER_GRADBIN = 1, FD_LAYER_LBP = 2 };
+ *  FD_LAYER_LBP        LbpFilter(lbp_type) (LbpFilter.cpp:56-85); 1 channel
+ *  FD_LAYER_GRADMAG_LBP  GradientFilter(grad_kernel, blur) -> imageprocessing::GradientMagnitudeFilter (GradientMagnitudeFilter.hpp:39-50,
+ *                      CV_8U: saturate_cast<uchar>(sqrt(x^2 + y^2)), x = gx - 127, y = gy - 127) -> LbpFilter(lbp_type): the layer
+ *                      filters of the "glbp" feature type (HeadTracking.cpp:199-254); 1 channel, one kernel per update, the
+ *                      magnitudes never reach memory.  bins, signed_gradients and interpolate are ignored. */
+enum { FD_LAYER_NONE = 0, FD_LAYER_GRADBIN = 1, FD_LAYER_LBP = 2, FD_LAYER_GRADMAG_LBP = 3 };
 enum { FD_LBP8 = 0, FD_LBP8_UNIFORM = 1, FD_LBP4 = 2, FD_LBP4_ROTATED = 3 };
 enum { FD_GRAD_SCHARR = -1 };
 int fd_pyramid_set_layer_filter(fd_pyramid* p, int kind, int bins, int signed_gradients, int interpolate,
@@ -125,6 +129,9 @@ int fd_gradient_filter_image(fd_ctx* ctx, const uint8_t* gray, int width, int he
 int fd_gradient_binning_image(fd_ctx* ctx, const uint8_t* grad2ch, int width, int height, int bins, int signed_gradients,
                               int interpolate, uint8_t* dst);
 int fd_lbp_image(fd_ctx* ctx, const uint8_t* gray, int width, int height, int lbp_type, uint8_t* dst);
+/* imageprocessing::GradientMagnitudeFilter::applyTo (GradientMagnitudeFilter.hpp:39-50) on a CV_8UC2 gradient image (the output of
+ * fd_gradient_image): CV_8UC1 magnitudes, the square root rounded to nearest (an exact integer function, at most 181) */
+int fd_gradient_magnitude_image(fd_ctx* ctx, const uint8_t* grad2ch, int width, int height, uint8_t* dst);
 
 /* ---- classification::WvmClassifier / ProbabilisticWvmClassifier --------------------------------
  * Field meaning as in WvmClassifier.hpp / the Matlab loader WvmClassifier.cpp:352-769 (values already
@@ -892,6 +899,43 @@ typedef struct {
 /* host only: floats per patch; -1 where fd_ehog_patch_batch returns FD_ERR_INVALID_ARGUMENT (a grid with zero rows or columns included) */
 int fd_ehog_feature_length(const fd_ehog_patch_params* ep, int channels);
 int fd_ehog_patch_batch(fd_ctx* ctx, const uint8_t* bin_patches, int64_t n, int channels, const fd_ehog_patch_params* ep, float* out);
+/* ---- features of explicit sample windows of a filtered pyramid (DirectPyramidFeatureExtractor::extract(x, y, width, height),
+ *      DirectPyramidFeatureExtractor.cpp:67-73,134-153), all samples of a call in one launch ----
+ * The sample -> window rule (ImagePyramid::getLayer(double) :307-310): index = lround(log(patch_w / width) / log(incremental
+ * scale)); the layer with that pyramid index must be a kept one; bx = cvRound((x - width / 2) * scale), by = cvRound((y - height
+ * / 2) * scale) with C integer division; the sample has a window iff width > 0 and the patch_w x patch_h window at (bx, by) lies
+ * inside the layer.
+ * fd_sample_windows: host only (no context, no device).  The kept layers are given by their pyramid index, scale and size, in
+ * increasing index order without gaps (as fd_pyramid_layer_info reports them).  xywh: n x {x, y, width, height};
+ * windows: n x {layer position, bx, by, valid}; rows of samples without a window are {-1, 0, 0, 0}.
+ * fd_pyramid_sample_windows: the same on the kept layers of an updated pyramid. */
+int fd_sample_windows(int n_layers, const int32_t* layer_index, const double* layer_scale, const int32_t* layer_w, const int32_t* layer_h,
+                      double incremental_scale, int patch_w, int patch_h, int n, const int32_t* xywh, int32_t* windows);
+int fd_pyramid_sample_windows(const fd_pyramid* p, int patch_w, int patch_h, int n, const int32_t* xywh, int32_t* windows);
+/* samples per call of the three entry points below */
+enum { FD_HIST_SAMPLES_MAX = 1 << 20 };
+int fd_hist_samples_limits(int* max_samples);
+/* The four FD_HIST_* patch filters on the sampled windows of a FD_LAYER_GRADBIN, FD_LAYER_LBP or FD_LAYER_GRADMAG_LBP pyramid:
+ * features is n x fd_hist_feature_length floats, valid n bytes (either may be NULL); the rows of samples without a window are zero.
+ * hp->step_x / step_y are ignored.  Bit for bit what fd_hist_patch_batch gives on the patches cut from the layers. */
+int fd_hist_extract_samples(fd_ctx* ctx, fd_pyramid* p, const fd_hist_params* hp, int n, const int32_t* xywh, uint8_t* valid, float* features);
+/* ExtendedHogFilter on the sampled windows of a FD_LAYER_GRADBIN pyramid: n x fd_ehog_feature_length floats, as fd_ehog_patch_batch */
+int fd_ehog_extract_samples(fd_ctx* ctx, fd_pyramid* p, const fd_ehog_patch_params* ep, int n, const int32_t* xywh, uint8_t* valid,
+                            float* features);
+/* condensation::SingleClassifierModel::evaluate (SingleClassifierModel.cpp:32-52) on a DirectPyramidFeatureExtractor with one of
+ * those patch filters and a ProbabilisticSvmClassifier on f32 vectors: kind FD_SAMPLES_HIST (params: const fd_hist_params*) or
+ * FD_SAMPLES_EHOG (params: const fd_ehog_patch_params*).  The features stay on the device and are scored by the kernel of
+ * fd_svm_distance_batch; target = distance >= threshold, weight = the logistic probability; samples without a window get target
+ * 0, weight 0.
+ * FD_ERR_INVALID_ARGUMENT, before anything is launched: a multi-frame pyramid, a pyramid without an image, a layer kind the
+ * filter does not read, a bin count other than the layer filter's, an SVM of another dimension or on u8 vectors, n < 0 or
+ * n > FD_HIST_SAMPLES_MAX.  n == 0 or no sample with a window: FD_OK without a launch. */
+enum { FD_SAMPLES_HIST = 0, FD_SAMPLES_EHOG = 1 };
+int fd_hist_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, int kind, const void* params, const fd_svm* svm, int n, const int32_t* xywh,
+                                 uint8_t* target, double* weight);
+/* ... the same call that also reports the hyperplane distances (n doubles; 0 for samples without a window) */
+int fd_hist_svm_evaluate_samples_distance(fd_ctx* ctx, fd_pyramid* p, int kind, const void* params, const fd_svm* svm, int n,
+                                          const int32_t* xywh, uint8_t* target, double* weight, double* distance);
 /* SlidingWindowDetector::detect with the histogram patch filter + ProbabilisticSvmClassifier on the f32
  * vectors (any kernel; wiring of BenchmarkRunner.cpp:185-263) */
 int fd_detect_hist_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_hist_params* hp, fd_detection* out,
