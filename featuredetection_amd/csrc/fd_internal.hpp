@@ -349,6 +349,18 @@ static inline void fd_allow_lds(fd_ctx* ctx, const void* kernel, int bytes, uint
     HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     done |= bit;
 }
+// Workgroups of KERNEL (`threads` threads, no dynamic LDS) a CU holds, `fallback` when the runtime cannot tell.  Asked once per kernel
+// instance; the batch's worker threads call it concurrently (they may both ask the first time, and store the same answer).
+template <auto KERNEL>
+static inline int fd_blocks_per_cu(int threads, int fallback) {
+    static std::atomic<int> cached{0};
+    int n = cached.load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, threads, 0) != hipSuccess || n < 1) n = fallback;
+        cached.store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
 
 struct FdStreamSwap {   // temporarily redirects everything that launches on ctx->stream
     fd_ctx* c;

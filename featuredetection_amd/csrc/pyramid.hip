@@ -1249,8 +1249,7 @@ void build_plan(fd_pyramid* p, int W, int H) {
         R.grid = std::max(R.grid, tile_grid_for(((L.w + TL_W - 1) / TL_W) * ((L.h + TL_H - 1) / TL_H)));
     }
     if (!plan.fused.empty()) {
-        int perCu = 0;   // workgroups of k_resize_down a CU holds
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_resize_down, 256, 0) != hipSuccess || perCu < 1) perCu = 4;
+        const int perCu = fd_blocks_per_cu<k_resize_down>(256, 4);
         for (size_t g = 0; g < plan.fused.size(); ++g) {   // 16-byte entries behind the 8-byte ones, 16-byte aligned
             FusedLaunch& F = plan.fused[g];
             if (tab.size() & 1) tab.push_back(make_int2(0, 0));

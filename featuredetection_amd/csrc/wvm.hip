@@ -985,17 +985,14 @@ void launch_sized(fd_ctx* ctx, hipStream_t st, int64_t total, fd_wvm* mh, const 
         // four windows per wavefront where four integral images leave enough LDS for the occupancy of the fixed part; only for
         // cascades that continue in stage B (no window turns positive in the first WVM_LCAP filters)
         if (!launched && dev.numPer <= 32 && dev.numUsed > WVM_LCAP) {
-            static int perCu4q = 0;
-            if (perCu4q == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu4q, k_wvm_cascade4<PW_, PH_, RAW>, 64 * WVM_QUAD_WAVES, 0) != hipSuccess || perCu4q < 1))
-                perCu4q = 4;
+            const int perCu4q = fd_blocks_per_cu<k_wvm_cascade4<PW_, PH_, RAW>>(64 * WVM_QUAD_WAVES, 4);
             const int grid4 = (int)std::min<int64_t>((total + 4 * WVM_QUAD_WAVES - 1) / (4 * WVM_QUAD_WAVES), (int64_t)ctx->num_cus * perCu4q * 2);
             hipLaunchKernelGGL((k_wvm_cascade4<PW_, PH_, RAW>), dim3(grid4), dim3(64 * WVM_QUAD_WAVES), 0, st, arena, wt, dev, o);
             launched = true;
         }
     }
     if (!launched) {   // one window per wavefront: any patch size, any filters per level
-        static int perCuA = 0;
-        if (perCuA == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCuA, k_wvm_cascade<PW_, PH_, RAW>, 256, 0) != hipSuccess || perCuA < 1)) perCuA = 4;
+        const int perCuA = fd_blocks_per_cu<k_wvm_cascade<PW_, PH_, RAW>>(256, 4);
         const int gridA = (int)std::min<int64_t>((total + 3) / 4, (int64_t)ctx->num_cus * perCuA * 2);   // two full rounds
         hipLaunchKernelGGL((k_wvm_cascade<PW_, PH_, RAW>), dim3(gridA), dim3(256), 0, st, arena, wt, dev, o);
     }
@@ -1007,8 +1004,7 @@ void launch_sized(fd_ctx* ctx, hipStream_t st, int64_t total, fd_wvm* mh, const 
     }
     // the rect-lookup stage B (k_wvm_deep: one workgroup of eight wavefronts per queued window): models the int8 operand cannot
     // express (more than 127 rects of one grey value on a pixel), FD_WVM_STAGEB=old (the cross-check of the tests)
-    static int perCu8 = 0;
-    if (perCu8 == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu8, k_wvm_deep<PW_, PH_, RAW, 8>, 512, 0) != hipSuccess || perCu8 < 1)) perCu8 = 1;
+    const int perCu8 = fd_blocks_per_cu<k_wvm_deep<PW_, PH_, RAW, 8>>(512, 1);
     const int gridB = (int)std::min<int64_t>(total, (int64_t)ctx->num_cus * perCu8);
     hipLaunchKernelGGL((k_wvm_deep<PW_, PH_, RAW, 8>), dim3(gridB), dim3(512), 0, st, arena, wt, dev, o);
 }
@@ -1047,7 +1043,7 @@ static void wvm_build_dense(fd_wvm* m, const fd_wvm_model* md) {
     const int pw = md->filter_w, ph = md->filter_h, d = pw * ph;
     bool sized = false;
 #define FD_WVM_CASE(W, H) if (pw == W && ph == H) sized = true;
-    FD_WVM_CASE(20, 20) FD_WVM_CASE(24, 24) FD_WVM_CASE(16, 24) FD_WVM_CASE(32, 16) FD_WVM_CASE(32, 24)
+    FD_WVM_SIZES(FD_WVM_CASE)
 #undef FD_WVM_CASE
     const int numUsed = m->dev.numUsed, numPer = m->dev.numPer;
     if (!sized || numUsed <= WVM_LCAP || numPer > 32) return;
@@ -1423,8 +1419,7 @@ static int64_t wvd_plan(WvdTable& wt, int slots, int ph) {
 
 template <int PW_, int PH_>
 static void launch_prefilter_sized(fd_ctx* ctx, hipStream_t st, const uint8_t* arena, WvdTable wt, const WvdDev& dv) {
-    static int perCu = 0;
-    if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_wvm_prefilter<PW_, PH_>, 256, 0) != hipSuccess || perCu < 1)) perCu = 2;
+    const int perCu = fd_blocks_per_cu<k_wvm_prefilter<PW_, PH_>>(256, 2);
     const int slots = ctx->num_cus * perCu * 4;
     const int64_t tiles = wvd_plan(wt, slots, PH_);
     int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
@@ -1484,24 +1479,33 @@ static bool launch_prefilter(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const uint8
     wvd_dev_from(m, q, qcount, dv);
 #define FD_WVM_CASE(W, H) \
     if (m->dev.fw == W && m->dev.fh == H) { launch_prefilter_sized<W, H>(ctx, st, arena, t, dv); return true; }
-    FD_WVM_CASE(20, 20) FD_WVM_CASE(24, 24) FD_WVM_CASE(16, 24) FD_WVM_CASE(32, 16) FD_WVM_CASE(32, 24)
+    FD_WVM_SIZES(FD_WVM_CASE)
 #undef FD_WVM_CASE
     return false;
 }
 
-// the same for a group of detectors with one patch size on one window table (wvm_dense_group.hpp)
+// the same for a group of detectors with one patch size on one window table (wvm_dense_group.hpp); false for a patch size the
+// group kernel does not take (wvd_group_fits)
 template <int PW_, int PH_>
-static void launch_prefilter_group_sized(fd_ctx* ctx, hipStream_t st, const uint8_t* arena, WvdTable wt, const WvdGroup& g) {
-    static int perCu = 0;
-    if (perCu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_wvm_prefilter_group<PW_, PH_>, 256, 0) != hipSuccess || perCu < 1)) perCu = 2;
-    const int slots = ctx->num_cus * perCu * 4;
-    const int64_t tiles = (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, PH_)) * wt.nimg;
-    int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
-    if (wt.nimg >= 8 && grid >= 64) grid &= ~7;
-    hipLaunchKernelGGL((k_wvm_prefilter_group<PW_, PH_>), dim3(grid), dim3(256), 0, st, arena, wt, g);
+static bool launch_prefilter_group_sized(fd_ctx* ctx, hipStream_t st, const uint8_t* arena, WvdTable wt, const WvdGroup& g) {
+    if constexpr (wvd_group_fits(PW_, PH_)) {
+        const int perCu = fd_blocks_per_cu<k_wvm_prefilter_group<PW_, PH_>>(256, 2);
+        const int slots = ctx->num_cus * perCu * 4;
+        const int64_t tiles = (int64_t)wvd_plan_sliding(wt, wvd_choose_k(wt, slots, PH_)) * wt.nimg;
+        int grid = (int)std::min<int64_t>((tiles + 3) / 4, (int64_t)ctx->num_cus * perCu * fd_knob_wvd_rounds());
+        if (wt.nimg >= 8 && grid >= 64) grid &= ~7;
+        hipLaunchKernelGGL((k_wvm_prefilter_group<PW_, PH_>), dim3(grid), dim3(256), 0, st, arena, wt, g);
+        return true;
+    }
+    return false;
 }
-// patch sizes whose equalised patch fits a lane's registers (KS <= 18 k-steps)
-static bool wvd_group_size(int fw, int fh) { return (fw == 20 && fh == 20) || (fw == 24 && fh == 24) || (fw == 16 && fh == 24) || (fw == 32 && fh == 16); }
+// the compile-time patch sizes the group kernel takes
+static bool wvd_group_size(int fw, int fh) {
+#define FD_WVM_CASE(W, H) if (fw == W && fh == H) return wvd_group_fits(W, H);
+    FD_WVM_SIZES(FD_WVM_CASE)
+#undef FD_WVM_CASE
+    return false;
+}
 static bool launch_prefilter_group(fd_ctx* ctx, hipStream_t st, fd_wvm* const* ms, int n, const uint8_t* arena, const WinTable& wt, const CascadeOut* os) {
     if (n < 2 || n > WVD_GMAX) return false;
     WvdTable t;
@@ -1518,8 +1522,8 @@ static bool launch_prefilter_group(fd_ctx* ctx, hipStream_t st, fd_wvm* const* m
         g.m[i].qcount = os[i].deep_count;
     }
 #define FD_WVM_CASE(W, H) \
-    if (ms[0]->dev.fw == W && ms[0]->dev.fh == H) { launch_prefilter_group_sized<W, H>(ctx, st, arena, t, g); return true; }
-    FD_WVM_CASE(20, 20) FD_WVM_CASE(24, 24) FD_WVM_CASE(16, 24) FD_WVM_CASE(32, 16)
+    if (ms[0]->dev.fw == W && ms[0]->dev.fh == H) return launch_prefilter_group_sized<W, H>(ctx, st, arena, t, g);
+    FD_WVM_SIZES(FD_WVM_CASE)
 #undef FD_WVM_CASE
     return false;
 }

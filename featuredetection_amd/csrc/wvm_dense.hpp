@@ -23,6 +23,10 @@
 //        Everything else is appended to a queue and runs the exact stage B (wvm_stageb.hpp) from level 0, so positives, their levels
 //        and their fp32 outputs stay bit-identical to the rectangle-sum formulation.
 //   k_wvb_prepare_lanes: stage B's preparation of long queues with the same per-lane machinery.
+//   k_wvm_prefilter_group (wvm_dense_group.hpp): the pre-filter of several detectors that scan the same windows.
+//   What the kernels share stands once, in front of them: WvdLaneLds and wvd_hist_clear (all three), WvdWaves and wvd_layer_task
+//   (the two pre-filters), and the soundness-critical part -- wvd_fold, wvd_levels (every error-bound constant and its reason) and
+//   wvd_push_survivors -- which both pre-filters call, so that they queue the same windows by construction.
 //   Only used when no per-window outputs are requested (fd_detect_wvm with all_level / all_score takes the exact path for every window).
 #pragma once
 
@@ -50,7 +54,7 @@ struct WvdTable {
 };
 
 // per-level model constants of the dense stage (device memory, read through the scalar cache)
-// the scalars k_wvm_prefilter takes as kernel arguments (WvdDev), for k_wvm_prefilter_group, which reads them per detector
+// the scalars of wvd_levels: k_wvm_prefilter fills them from its kernel arguments (WvdDev), k_wvm_prefilter_group per detector from WvdConst::sc
 struct WvdScal {
     int32_t L;
     float negBasis, negBias, stretch, sxxSlack;
@@ -304,6 +308,156 @@ __device__ __forceinline__ void wvd_cdf_lut(unsigned int cntLds, unsigned int lu
     sumxx = s2;
 }
 
+// ---- the pieces k_wvm_prefilter, k_wvm_prefilter_group (wvm_dense_group.hpp) and k_wvb_prepare_lanes share ----------------------
+
+// A lane's LDS addresses in the blocks of WvdLds / WvdPrepLds (`hist`, `lut`: the workgroup's arrays)
+struct WvdLaneLds {
+    unsigned char* histPtr;    // this wavefront's half rows, 256 B apart
+    unsigned int blkH4;        // block bits of the address byte, for all four pixels
+    unsigned int laneOff32;    // lanes l and l + 32 share a dword of every bin row: they are served in different LDS cycles, so nothing conflicts
+    unsigned int cntLds;       // this lane's u16 counter of bin 0
+    unsigned int inc;          // one count in this lane's half of the dword
+    unsigned int lutLds;       // this lane's LUT byte of bin 0
+    unsigned int blkL4, lutWord;
+    __device__ __forceinline__ WvdLaneLds(unsigned int (&hist)[2][64][2][32], unsigned char (&lut)[64][64][4], int lane, int wave) {
+        histPtr = reinterpret_cast<unsigned char*>(&hist[wave >> 1][0][wave & 1][0]);
+        const unsigned int histLds = (unsigned int)(uintptr_t)(wvd_lds_u16*)histPtr;   // LDS byte address: 16 KB block + (wave & 1) * 128
+        blkH4 = ((histLds >> 8) & 0xC0u) * 0x01010101u;
+        laneOff32 = (histLds & ~0xFF00u) + (unsigned int)(lane & 31) * 4u;
+        cntLds = histLds + (unsigned int)(lane & 31) * 4u + (unsigned int)(lane >> 5) * 2u;
+        inc = 1u << (16 * (lane >> 5));
+        lutLds = (unsigned int)(uintptr_t)(wvd_lds_u8*)&lut[0][lane][wave];
+        blkL4 = ((lutLds >> 8) & 0xC0u) * 0x01010101u;
+        lutWord = lutLds & ~0xFF00u;
+    }
+};
+// zeroes the wavefront's 64 bins x 64 lanes of u16 counters: 8 rows of 128 B per step
+__device__ __forceinline__ void wvd_hist_clear(unsigned char* histPtr, int lane) {
+    unsigned char* z = histPtr + (lane >> 3) * 256 + (lane & 7) * 16;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) *reinterpret_cast<uint4*>(z + i * 2048) = make_uint4(0, 0, 0, 0);
+}
+
+// The tiles a wavefront of the pre-filter kernels takes: v = first, first + stride, ... < end, and v -> (frame, tile inside the frame).
+// Multi-frame pyramids: workgroup b runs on XCD b % 8 (observed dispatch order; only speed depends on it), and every XCD has its own
+// L2.  With the plain round-robin every L2 pulled the layers of ALL frames across the fabric (162 MB per 64-frame call against
+// 2.5 MB of kept layers); here XCD x takes the frames x, x + 8, ...: each frame's layers live in one L2.
+struct WvdWaves {
+    bool byXcd;
+    int xcd, first, stride, end;
+    __device__ __forceinline__ WvdWaves(const WvdTable& wt, int wave) {
+        byXcd = wt.nimg >= 8 && (gridDim.x & 7u) == 0;
+        xcd = blockIdx.x & 7;
+        stride = byXcd ? (int)(gridDim.x >> 3) * 4 : (int)gridDim.x * 4;
+        end = byXcd ? ((wt.nimg - xcd + 7) >> 3) * wt.sTilesPerImage : wt.sTilesPerImage * wt.nimg;
+        first = (byXcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x) * 4 + wave;
+    }
+    __device__ __forceinline__ void locate(const WvdTable& wt, int v, int& img, int& tile) const {
+        const int fi = wt.nimg > 1 ? v / wt.sTilesPerImage : 0;
+        img = byXcd ? xcd + 8 * fi : fi;   // frame of a multi-frame pyramid
+        tile = v - fi * wt.sTilesPerImage;
+    }
+};
+
+// The per-layer plan: tile `tile` of the frame is 64 (column, row group of K) tasks of layer `wl`.  The lane's task: column, first
+// window row, windows (0: a lane past the last task; it repeats that task, unseen)
+__device__ __forceinline__ void wvd_layer_task(int tile, int lane, const WvdLayer& wl, int K, unsigned int& ix, int& iy0, int& rows) {
+    const int ntask = wl.nx * wl.G;
+    const int task0 = (tile - wl.sTileFirst) * 64 + lane;
+    const unsigned int task = (unsigned int)(task0 < ntask ? task0 : ntask - 1);
+    unsigned int g = __umulhi(task, wl.magic);   // floor(task / nx) or one less
+    ix = task - g * (unsigned int)wl.nx;
+    if (ix >= (unsigned int)wl.nx) { ix -= wl.nx; ++g; }
+    iy0 = (int)g * K;
+    rows = task0 < ntask ? min(K, wl.ny - iy0) : 0;
+}
+
+// ---- 4. digits -> exact integer dot products, lane == window.  Register r of acc[M][N] is digit row (r & 3) + 8 (r >> 2) + 4 h
+//         (h = lane >> 5) of tile M: filter fs(i) = (i & 3) + 8 (i >> 2) + 4 h for i = r & 7, digit 2 M + (r >> 3).  After the
+//         swap, xq[0][i] is filter (i & 3) + 8 (i >> 2) of THIS lane's window and xq[1][i] filter (i & 3) + 8 (i >> 2) + 4.
+__device__ __forceinline__ void wvd_fold(const wvd_v16i& acc00, const wvd_v16i& acc01, const wvd_v16i& acc10, const wvd_v16i& acc11, double (&xq)[2][8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        // exact (explicit fma: -ffp-contract=off): |digit sums| < 2^24, every intermediate is an integer below 2^53
+        const double v0 = __builtin_fma(256.0, __builtin_fma(65536.0, (double)acc10[8 + i], (double)acc00[8 + i]), __builtin_fma(65536.0, (double)acc10[i], (double)acc00[i]));
+        const double v1 = __builtin_fma(256.0, __builtin_fma(65536.0, (double)acc11[8 + i], (double)acc01[8 + i]), __builtin_fma(65536.0, (double)acc11[i], (double)acc01[i]));
+        uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
+        wvd_swap32(u0.x, u1.x);
+        wvd_swap32(u0.y, u1.y);
+        xq[0][i] = __builtin_bit_cast(double, u0);
+        xq[1][i] = __builtin_bit_cast(double, u1);
+    }
+}
+
+// ---- 5. the first L cascade levels of this lane's window with error bounds; returns whether the window is still undecided (it goes
+//         to the exact cascade).  `sc`: the detector's scalars, `C`: its level constants (constant address space: scalar loads (SMEM)
+//         even though the kernels also store to global memory).  Branch-free per window (selects became plain
+//         arithmetic: an exponent below the float range gives K = 0 within the absolute slack, one above it makes the sums
+//         inf / NaN, which never compare below a threshold); the level constants are scalar loads the scheduler can issue ahead of
+//         the arithmetic.
+typedef __attribute__((address_space(4))) WvdConst wvd_cconst;
+typedef float wvd_v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool wvd_levels(const wvd_cconst& C, const WvdScal sc, const double (&xq)[2][8], unsigned int sumx, unsigned int sumxx, bool active, int lane) {
+    wvd_v2f KK[WVD_L];   // {K_p, bound of its error}: the level sum and its bound run as ONE v_pk_fma_f32 per term
+    // the reference's fp32 sum of squares: row totals (exact ints) added in fp32, so it IS the integer below 2^24
+    const float sxx = (float)sumxx;
+    // |norm - reference norm|: 2 * quantisation error of xp, the fp32 sum of squares above 2^24, slack for the fp64 roundings on
+    // both sides (the reference's chain and the regrouped one below: < 1e-5)
+    const double dn = sc.scale * (double)sumx + (sumxx >= (1u << 24) ? (double)sc.sxxSlack : 0.0) + 1e-4;
+    const float relDn = (float)(-(double)sc.negBasis * dn) * 1.0001f;
+    constexpr float sumOrder = 4.6e-6f;   // the fp32 summation-order term (4k + 16) 2^-24 of a level sum, relative
+    // relative error of K: exponent error (quantisation; float cast of the exponent and 2^x: 1.69e-7 |log2 K| + 6e-7), the final
+    // rounding, and -- folded in here -- sumOrder
+    const float rho0 = (relDn + 6.0e-7f) * 1.01f + sumOrder;
+    const double e0 = sc.nb2 * (double)sxx;   // log2 K = nb2 (sxx - 2 xp + pp) = e0 + cA[k] + mXq (x' . Q)
+    const wvd_v2f RE0 = {sc.negBias, fabsf(sc.negBias) * sumOrder + 1e-37f};
+    const __attribute__((address_space(4))) wvd_v2f* W2 = (const __attribute__((address_space(4))) wvd_v2f*)&C.w2[0][0][0];
+    unsigned long long und = __ballot(active);
+    // NL levels as ONE basic block (no test of L between levels: the scheduler issues the scalar loads of the level constants
+    // ahead of the arithmetic; with a test per level pair every pair waited for its own loads: 132 -> 127 us per headline launch).
+    // Levels L .. NL - 1 are padding (thr = -inf, weights 0): evaluated, never rejecting.
+    auto levels = [&](auto nl) {
+        constexpr int NL = decltype(nl)::value;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            const double ex = __builtin_fma(xq[(k >> 2) & 1][(k & 3) + 4 * (k >> 3)], sc.mXq, e0 + C.cA[k]);
+            const float lg = (float)ex;
+            const float Kraw = __builtin_amdgcn_exp2f(lg);   // <= 2^-115 where the old form tested arg < -80: inside the 3e-35 below
+            const float rho = __builtin_fmaf(fabsf(lg), 1.69e-7f, rho0);
+            KK[k] = wvd_v2f{Kraw, __builtin_fmaf(Kraw, rho, 3e-35f)};
+            wvd_v2f RE = RE0;
+#pragma unroll
+            for (int p = 0; p <= k; ++p) RE = __builtin_elementwise_fma(W2[k * WVD_L + p], KK[p], RE);   // R += w K_p, E += |w| dK_p
+            // the reference leaves at the first level with res < thr, and res_ref <= R + E
+            und &= ~__ballot(RE.x + RE.y < C.thr[k]);
+        }
+    };
+    if (sc.L > 14) levels(std::integral_constant<int, 16>());
+    else if (sc.L > 12) levels(std::integral_constant<int, 14>());
+    else if (sc.L > 8) levels(std::integral_constant<int, 12>());
+    else levels(std::integral_constant<int, 8>());
+    return (und >> lane) & 1ull;
+}
+
+// ---- 6. survivors (bit s of survBits: the lane's window s of its column, `nx` windows apart in the queue's ids) -> queue of the
+// exact cascade: ONE returning atomic per wavefront and column walk (it was one per window step: with a model that lets a quarter of
+// the windows through, 48 K of them per 64-frame launch and each waited for on the spot -- the launch took 231 instead of 126 us)
+__device__ __forceinline__ void wvd_push_survivors(unsigned int survBits, int K, int64_t* q, unsigned int* qcount, int64_t wid0, unsigned int nx, int lane) {
+    if (__ballot(survBits != 0)) {
+        unsigned int total = 0;
+        for (int st = 0; st < K; ++st) total += (unsigned int)__popcll(__ballot((survBits >> st) & 1u));
+        unsigned int base = 0;
+        if (lane == 0) base = atomicAdd(qcount, total);
+        base = __builtin_amdgcn_readfirstlane(base);
+        for (int st = 0; st < K; ++st) {
+            const bool mine = (survBits >> st) & 1u;
+            const unsigned long long mask = __ballot(mine);
+            if (mine) q[base + __popcll(mask & ((1ull << lane) - 1ull))] = wid0 + (int64_t)((unsigned long long)(unsigned int)st * nx);
+            base += (unsigned int)__popcll(mask);
+        }
+    }
+}
+
 template <int PW_, int PH_>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_wvm_prefilter(const uint8_t* __restrict__ arena, WvdTable wt, WvdDev dv) {
     static_assert(PW_ % 4 == 0 && PW_ >= 16 && PW_ <= 32, "rows are read as dwords");
@@ -324,37 +478,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         SL[threadIdx.x][2] = make_int4((int)(unsigned int)l.first, (int)(l.first >> 32), 0, 0);
     }
     __syncthreads();
-    // constant address space: scalar loads (SMEM) even though the kernel also stores to global memory
-    const __attribute__((address_space(4))) WvdConst& C = *(const __attribute__((address_space(4))) WvdConst*)(uintptr_t)dv.c;
-    const int L = dv.L;
+    const wvd_cconst& C = *(const wvd_cconst*)(uintptr_t)dv.c;
+    const WvdScal sc = {dv.L, dv.negBasis, dv.negBias, dv.stretch, dv.sxxSlack, 0, dv.scale, dv.nb2, dv.mXq};   // kernel arguments: SGPRs
     const int K = wt.K;
     int li = 0;
-    unsigned char* histPtr = reinterpret_cast<unsigned char*>(&S.hist[wave >> 1][0][wave & 1][0]);   // this wavefront's half rows, 256 B apart
-    const unsigned int histLds = (unsigned int)(uintptr_t)(wvd_lds_u16*)histPtr;   // LDS byte address: 16 KB block + (wave & 1) * 128
-    const unsigned int blkH4 = ((histLds >> 8) & 0xC0u) * 0x01010101u;             // block bits of the address byte, for all four pixels
-    // lanes l and l + 32 share a dword of every bin row: they are served in different LDS cycles, so nothing conflicts
-    const unsigned int laneOff32 = (histLds & ~0xFF00u) + (unsigned int)(lane & 31) * 4u;
-    const unsigned int cntLds = histLds + (unsigned int)(lane & 31) * 4u + (unsigned int)(lane >> 5) * 2u;   // this lane's u16 counter of bin 0
-    const unsigned int inc = 1u << (16 * (lane >> 5));
-    const unsigned int lutLds = (unsigned int)(uintptr_t)(wvd_lds_u8*)&S.lut[0][lane][wave];   // this lane's LUT byte of bin 0
-    const unsigned int blkL4 = ((lutLds >> 8) & 0xC0u) * 0x01010101u;
-    const unsigned int lutWord = lutLds & ~0xFF00u;
+    const WvdLaneLds ld(S.hist, S.lut, lane, wave);
 
     int lastImg = -1;
 #ifdef FD_WVB_PROF
     const unsigned long long pT0 = __builtin_amdgcn_s_memtime();
     unsigned long long pAcc[4] = {0, 0, 0, 0}, pTiles = 0;
 #endif
-    // Multi-frame pyramids: workgroup b runs on XCD b % 8 (observed dispatch order; only speed depends on it), and every XCD has its own
-    // L2.  With the plain round-robin every L2 pulled the layers of ALL frames across the fabric (162 MB per 64-frame call against
-    // 2.5 MB of kept layers); here XCD x takes the frames x, x + 8, ...: each frame's layers live in one L2.
-    const bool byXcd = wt.nimg >= 8 && (gridDim.x & 7u) == 0;
-    const int xcd = blockIdx.x & 7, vStride = byXcd ? (int)(gridDim.x >> 3) * 4 : (int)gridDim.x * 4;
-    const int vEnd = byXcd ? ((wt.nimg - xcd + 7) >> 3) * wt.sTilesPerImage : wt.sTilesPerImage * wt.nimg;
-    for (int v = (byXcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x) * 4 + wave; v < vEnd; v += vStride) {
-        const int fi = wt.nimg > 1 ? v / wt.sTilesPerImage : 0;
-        const int img = byXcd ? xcd + 8 * fi : fi;   // frame of a multi-frame pyramid
-        const int tile = v - fi * wt.sTilesPerImage;
+    const WvdWaves W(wt, wave);
+    for (int v = W.first; v < W.end; v += W.stride) {
+        int img, tile;
+        W.locate(wt, v, img, tile);
         // the lane's task: layer, column, first window row, windows (0: a lane past the last task; it repeats that task, unseen)
         int myLi, iy0, rows;
         unsigned int ix;
@@ -366,16 +504,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         } else {   // the per-layer plan: 64 (column, row group of K) tasks of one layer
             if (img != lastImg) { li = 0; lastImg = img; }
             while (li + 1 < wt.n && tile >= wt.l[li + 1].sTileFirst) ++li;   // tiles ascend per wavefront inside a frame
-            const WvdLayer& wl = wt.l[li];
-            const int ntask = wl.nx * wl.G;
-            const int task0 = (tile - wl.sTileFirst) * 64 + lane;
-            const unsigned int task = (unsigned int)(task0 < ntask ? task0 : ntask - 1);
-            unsigned int g = __umulhi(task, wl.magic);   // floor(task / nx) or one less
-            ix = task - g * (unsigned int)wl.nx;
-            if (ix >= (unsigned int)wl.nx) { ix -= wl.nx; ++g; }
+            wvd_layer_task(tile, lane, wt.l[li], K, ix, iy0, rows);
             myLi = li;
-            iy0 = (int)g * K;
-            rows = task0 < ntask ? min(K, wl.ny - iy0) : 0;
         }
         const int4 la = SL[myLi][1], lb = SL[myLi][2];
         const unsigned int nxl = (unsigned int)SL[myLi][0].x;
@@ -388,11 +518,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 
         WVD_T(pa);
         // ---- 1. histogram of the lane's first window: 64 bins x 64 lanes of u16 counters
-        {
-            unsigned char* z = histPtr + (lane >> 3) * 256 + (lane & 7) * 16;   // 8 rows of 128 B per step
-#pragma unroll
-            for (int i = 0; i < 8; ++i) *reinterpret_cast<uint4*>(z + i * 2048) = make_uint4(0, 0, 0, 0);
-        }
+        wvd_hist_clear(ld.histPtr, lane);
         __builtin_amdgcn_wave_barrier();
         {
             unsigned int wn[NW], ra = lo0;   // ra: the lane's offset of the row in flight (a running add: the row length is per lane)
@@ -406,7 +532,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
                 if (r + 1 < PH_) ra += lw;
 #pragma unroll
                 for (int j = 0; j < NW; ++j) wn[j] = wvd_load_u32(ubase + 4 * j, ra);
-                wvd_hist_row<NW, true>(w4, blkH4, laneOff32, inc);
+                wvd_hist_row<NW, true>(w4, ld.blkH4, ld.laneOff32, ld.inc);
             }
         }
         WVD_T(pb0);
@@ -426,8 +552,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
                 unsigned int wo[NW], wi[NW];
 #pragma unroll
                 for (int j = 0; j < NW; ++j) { wo[j] = wvd_load_u32(ubase + 4 * j, ro); wi[j] = wvd_load_u32(ubase + 4 * j, ri); }
-                wvd_hist_row<NW, false>(wo, blkH4, laneOff32, inc);
-                wvd_hist_row<NW, true>(wi, blkH4, laneOff32, inc);
+                wvd_hist_row<NW, false>(wo, ld.blkH4, ld.laneOff32, ld.inc);
+                wvd_hist_row<NW, true>(wi, ld.blkH4, ld.laneOff32, ld.inc);
             }
         }
         // the window this lane evaluates now (a lane that has run out of windows repeats its last one, unseen)
@@ -436,7 +562,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         WVD_T(pb);
         // ---- 2. the fp32 cdf, the LUT, and the exact integer sum / sum of squares of the equalised patch
         unsigned int sumx, sumxx;
-        wvd_cdf_lut<PW_ * PH_>(cntLds, lutLds, dv.stretch, sumx, sumxx);
+        wvd_cdf_lut<PW_ * PH_>(ld.cntLds, ld.lutLds, dv.stretch, sumx, sumxx);
         wave_sync();
         WVD_T(pc);
         // ---- 3. equalise, exact dot products on the matrix pipe.  k-step ks takes the dwords 8 ks .. 8 ks + 7 of the row-major patch
@@ -478,8 +604,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
                 for (int j = 0; j < 8; ++j) cur[j] = nxq[ks % PF][j];
                 if (ks + PF < KS) fetchPx(ks + PF);
                 if (ks + 1 < KS) fetch(ks + 1);
-                wvd_equalise<4>(cur, pk, lutWord, blkL4);
-                if (8 * ks + 4 < D4) wvd_equalise<4>(cur + 4, pk + 4, lutWord, blkL4);
+                wvd_equalise<4>(cur, pk, ld.lutWord, ld.blkL4);
+                if (8 * ks + 4 < D4) wvd_equalise<4>(cur + 4, pk + 4, ld.lutWord, ld.blkL4);
                 else pk[4] = pk[5] = pk[6] = pk[7] = 0;   // k-slots past the patch: zero pixels against zero digits
                 // this lane's 32 bytes -> the k-half each N-tile wants from it: lanes 0..31 give bytes 0..15 of windows 0..31 (tile 0) /
                 // 32..63 (tile 1), lanes 32..63 bytes 16..31
@@ -492,67 +618,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             }
         }
         WVD_T(pd);
-        // ---- 4. digits -> exact integer dot products, lane == window.  Register r of acc[M][N] is digit row (r & 3) + 8 (r >> 2) + 4 h
-        //         (h = lane >> 5) of tile M: filter fs(i) = (i & 3) + 8 (i >> 2) + 4 h for i = r & 7, digit 2 M + (r >> 3).  After the
-        //         swap, xq[0][i] is filter (i & 3) + 8 (i >> 2) of THIS lane's window and xq[1][i] filter (i & 3) + 8 (i >> 2) + 4.
+        // ---- 4. / 5. digits -> exact integer dot products, lane == window; the first L cascade levels with their error bounds
         double xq[2][8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            // exact (explicit fma: -ffp-contract=off): |digit sums| < 2^24, every intermediate is an integer below 2^53
-            const double v0 = __builtin_fma(256.0, __builtin_fma(65536.0, (double)acc10[8 + i], (double)acc00[8 + i]), __builtin_fma(65536.0, (double)acc10[i], (double)acc00[i]));
-            const double v1 = __builtin_fma(256.0, __builtin_fma(65536.0, (double)acc11[8 + i], (double)acc01[8 + i]), __builtin_fma(65536.0, (double)acc11[i], (double)acc01[i]));
-            uint2 u0 = __builtin_bit_cast(uint2, v0), u1 = __builtin_bit_cast(uint2, v1);
-            wvd_swap32(u0.x, u1.x);
-            wvd_swap32(u0.y, u1.y);
-            xq[0][i] = __builtin_bit_cast(double, u0);
-            xq[1][i] = __builtin_bit_cast(double, u1);
-        }
-        // ---- 5. the first L cascade levels of this lane's window with error bounds.  Branch-free per window (selects became plain
-        //         arithmetic: an exponent below the float range gives K = 0 within the absolute slack, one above it makes the sums
-        //         inf / NaN, which never compare below a threshold); levels come in pairs behind one uniform test of L, the level
-        //         constants of a pair are scalar loads the scheduler can issue ahead of the arithmetic.
-        bool undecided = active;
-        {
-            typedef float wvd_v2f __attribute__((ext_vector_type(2)));
-            wvd_v2f KK[WVD_L];   // {K_p, bound of its error}: the level sum and its bound run as ONE v_pk_fma_f32 per term
-            // the reference's fp32 sum of squares: row totals (exact ints) added in fp32, so it IS the integer below 2^24
-            const float sxx = (float)sumxx;
-            // |norm - reference norm|: 2 * quantisation error of xp, the fp32 sum of squares above 2^24, slack for the fp64 roundings on
-            // both sides (the reference's chain and the regrouped one below: < 1e-5)
-            const double dn = dv.scale * (double)sumx + (sumxx >= (1u << 24) ? (double)dv.sxxSlack : 0.0) + 1e-4;
-            const float relDn = (float)(-(double)dv.negBasis * dn) * 1.0001f;
-            // relative error of K: exponent error (quantisation; float cast of the exponent and 2^x: 1.69e-7 |log2 K| + 6e-7), the final
-            // rounding, and -- folded in here -- the fp32 summation-order term (4k + 16) 2^-24 <= 4.6e-6 of the level sums
-            const float rho0 = (relDn + 6.0e-7f) * 1.01f + 4.6e-6f;
-            const double e0 = dv.nb2 * (double)sxx;   // log2 K = nb2 (sxx - 2 xp + pp) = e0 + cA[k] + mXq (x' . Q)
-            const wvd_v2f RE0 = {dv.negBias, fabsf(dv.negBias) * 4.6e-6f + 1e-37f};
-            const __attribute__((address_space(4))) wvd_v2f* W2 = (const __attribute__((address_space(4))) wvd_v2f*)&C.w2[0][0][0];
-            unsigned long long und = __ballot(undecided);
-            // NL levels as ONE basic block (no test of L between levels: the scheduler issues the scalar loads of the level constants
-            // ahead of the arithmetic; with a test per level pair every pair waited for its own loads: 132 -> 127 us per headline launch).
-            // Levels L .. NL - 1 are padding (thr = -inf, weights 0): evaluated, never rejecting.
-            auto levels = [&](auto nl) {
-                constexpr int NL = decltype(nl)::value;
-#pragma unroll
-                for (int k = 0; k < NL; ++k) {
-                    const double ex = __builtin_fma(xq[(k >> 2) & 1][(k & 3) + 4 * (k >> 3)], dv.mXq, e0 + C.cA[k]);
-                    const float lg = (float)ex;
-                    const float Kraw = __builtin_amdgcn_exp2f(lg);   // <= 2^-115 where the old form tested arg < -80: inside the 3e-35 below
-                    const float rho = __builtin_fmaf(fabsf(lg), 1.69e-7f, rho0);
-                    KK[k] = wvd_v2f{Kraw, __builtin_fmaf(Kraw, rho, 3e-35f)};
-                    wvd_v2f RE = RE0;
-#pragma unroll
-                    for (int p = 0; p <= k; ++p) RE = __builtin_elementwise_fma(W2[k * WVD_L + p], KK[p], RE);   // R += w K_p, E += |w| dK_p
-                    // the reference leaves at the first level with res < thr, and res_ref <= R + E
-                    und &= ~__ballot(RE.x + RE.y < C.thr[k]);
-                }
-            };
-            if (L > 14) levels(std::integral_constant<int, 16>());
-            else if (L > 12) levels(std::integral_constant<int, 14>());
-            else if (L > 8) levels(std::integral_constant<int, 12>());
-            else levels(std::integral_constant<int, 8>());
-            undecided = (und >> lane) & 1ull;
-        }
+        wvd_fold(acc00, acc01, acc10, acc11, xq);
+        const bool undecided = wvd_levels(C, sc, xq, sumx, sumxx, active, lane);
         survBits |= undecided ? 1u << step : 0u;
 #ifdef FD_WVB_PROF
         {
@@ -561,22 +630,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         }
 #endif
         }   // windows of the column
-        // ---- 6. survivors -> queue of the exact cascade: ONE returning atomic per wavefront and column walk (it was one per window step:
-        // with a model that lets a quarter of the windows through, 48 K of them per 64-frame launch and each waited for on the spot --
-        // the launch took 231 instead of 126 us)
-        if (__ballot(survBits != 0)) {
-            unsigned int total = 0;
-            for (int st = 0; st < K; ++st) total += (unsigned int)__popcll(__ballot((survBits >> st) & 1u));
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(dv.qcount, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-            for (int st = 0; st < K; ++st) {
-                const bool mine = (survBits >> st) & 1u;
-                const unsigned long long mask = __ballot(mine);
-                if (mine) dv.q[base + __popcll(mask & ((1ull << lane) - 1ull))] = wid0 + (int64_t)((unsigned long long)(unsigned int)st * nxl);
-                base += (unsigned int)__popcll(mask);
-            }
-        }
+        // ---- 6. survivors -> queue of the exact cascade
+        wvd_push_survivors(survBits, K, dv.q, dv.qcount, wid0, nxl, lane);
         wave_sync();
     }
 #ifdef FD_WVB_PROF
@@ -619,15 +674,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         S.layer[threadIdx.x][1] = make_int4((int)l.off, (int)l.magic, (int)l.first, 0);
     }
     __syncthreads();
-    unsigned char* histPtr = reinterpret_cast<unsigned char*>(&S.hist[wave >> 1][0][wave & 1][0]);
-    const unsigned int histLds = (unsigned int)(uintptr_t)(wvd_lds_u16*)histPtr;
-    const unsigned int blkH4 = ((histLds >> 8) & 0xC0u) * 0x01010101u;
-    const unsigned int laneOff32 = (histLds & ~0xFF00u) + (unsigned int)(lane & 31) * 4u;
-    const unsigned int cntLds = histLds + (unsigned int)(lane & 31) * 4u + (unsigned int)(lane >> 5) * 2u;
-    const unsigned int inc = 1u << (16 * (lane >> 5));
-    const unsigned int lutLds = (unsigned int)(uintptr_t)(wvd_lds_u8*)&S.lut[0][lane][wave];
-    const unsigned int blkL4 = ((lutLds >> 8) & 0xC0u) * 0x01010101u;
-    const unsigned int lutWord = lutLds & ~0xFF00u;
+    const WvdLaneLds ld(S.hist, S.lut, lane, wave);
     const unsigned int perImage = (unsigned int)wt.per_image;                          // the launcher checks that all ids fit 32 bits
     const unsigned int magicPI = wt.nimg > 1 ? (unsigned int)(0xffffffffu / perImage) : 0u;   // mulhi(id, magic) = id / perImage or one less
     const unsigned int n = wvb_count(qcount, s);
@@ -654,11 +701,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         const int lw = la.w;
         const uint8_t* src = arena + (size_t)img * wt.image_stride + (unsigned int)lb.x + (size_t)(la.y + (int)iy * wt.sy) * lw + (la.x + (int)ix * wt.sx);
         // ---- histogram, cdf, LUT
-        {
-            unsigned char* z = histPtr + (lane >> 3) * 256 + (lane & 7) * 16;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) *reinterpret_cast<uint4*>(z + i * 2048) = make_uint4(0, 0, 0, 0);
-        }
+        wvd_hist_clear(ld.histPtr, lane);
         __builtin_amdgcn_wave_barrier();
         {
             unsigned int wn[NW];
@@ -669,12 +712,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 #pragma unroll
                 for (int j = 0; j < NW; ++j) w4[j] = wn[j];
                 wvd_load_row<NW>(src + (size_t)(r + 1 < PH_ ? r + 1 : r) * lw, wn);
-                wvd_hist_row<NW, true>(w4, blkH4, laneOff32, inc);
+                wvd_hist_row<NW, true>(w4, ld.blkH4, ld.laneOff32, ld.inc);
             }
         }
         wave_sync();
         unsigned int sumx, sumxx;
-        wvd_cdf_lut<PW_ * PH_>(cntLds, lutLds, stretch, sumx, sumxx);
+        wvd_cdf_lut<PW_ * PH_>(ld.cntLds, ld.lutLds, stretch, sumx, sumxx);
         wave_sync();
         // ---- equalise row by row: the patch as x - 128 bytes, the fp32 sum of squares in row order
         int8_t* xr = s.X[0] + (size_t)pos * mv.dstride;
@@ -697,8 +740,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
 #pragma unroll
                     for (int j = 0; j < NW; ++j) w4[j] = wn[j];
                     wvd_load_row<NW>(src + (size_t)(r + 1 < PH_ ? r + 1 : r) * lw, wn);
-                    if constexpr (NW <= 5) wvd_equalise<NW>(w4, pk, lutWord, blkL4);
-                    else { wvd_equalise<NW / 2>(w4, pk, lutWord, blkL4); wvd_equalise<NW / 2>(w4 + NW / 2, pk + NW / 2, lutWord, blkL4); }
+                    if constexpr (NW <= 5) wvd_equalise<NW>(w4, pk, ld.lutWord, ld.blkL4);
+                    else { wvd_equalise<NW / 2>(w4, pk, ld.lutWord, ld.blkL4); wvd_equalise<NW / 2>(w4 + NW / 2, pk + NW / 2, ld.lutWord, ld.blkL4); }
                     unsigned int rowsq = 0;
 #pragma unroll
                     for (int j = 0; j < NW; ++j) {
