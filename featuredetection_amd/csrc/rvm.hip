@@ -139,7 +139,10 @@ __device__ __forceinline__ double rvm_kernel_value(const RvmDev& m, const void* 
     }
     if (m.kernel == FD_KERNEL_HIK) {
         float sum = 0.f;
-        for (int i = 0; i < dim; ++i) sum = sum + fminf(X(i), s[i]);
+        for (int i = 0; i < dim; ++i) {
+            const float xi = X(i), si = s[i];
+            sum = sum + (si < xi ? si : xi);   // std::min(x, s), HistogramIntersectionKernel.hpp:88-92: a NaN in x stays (fminf drops it)
+        }
         return (double)sum;
     }
     double dot = 0.0;
@@ -229,7 +232,10 @@ __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restri
                 K = exp(-m.p0 * (double)sum);
             } else if (m.kernel == FD_KERNEL_HIK) {
                 float sum = 0.f;
-                for (int i = 0; i < dim; ++i) sum = sum + fminf(x[i], st[(size_t)i * F]);
+                for (int i = 0; i < dim; ++i) {
+                    const float xi = x[i], si = st[(size_t)i * F];
+                    sum = sum + (si < xi ? si : xi);   // std::min(x, s), as in rvm_kernel_value
+                }
                 K = (double)sum;
             } else {
                 double dot = 0.0;
@@ -287,6 +293,9 @@ void run_cascade(fd_ctx* ctx, fd_rvm* m, const void* dfeats, int64_t rowBytes, f
     hipStream_t st = ctx->stream;
     int b[16];
     const int np = pass_bounds(m->dev.numUse, b);
+    // k_rvm_deep keeps the window's vector in an LDS slab of RVM_MAX_DIM^2 floats: refused before anything is queued
+    if (m->dev.numUse > b[np] && m->dev.dim > RVM_MAX_DIM * RVM_MAX_DIM)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "RvmClassifier: vectors longer than %d are not supported with more than %d levels", RVM_MAX_DIM * RVM_MAX_DIM, RVM_DEEP_FROM);
     m->q0.reserve(sizeof(FdPosRec) * (size_t)n);
     m->q1.reserve(sizeof(FdPosRec) * (size_t)n);
     m->counters.reserve(256);
@@ -307,7 +316,6 @@ void run_cascade(fd_ctx* ctx, fd_rvm* m, const void* dfeats, int64_t rowBytes, f
         HIP_CHECK(hipGetLastError());
     }
     if (m->dev.numUse > b[np]) {
-        if (m->dev.dim > RVM_MAX_DIM * RVM_MAX_DIM) FD_THROW(FD_ERR_INVALID_ARGUMENT, "RvmClassifier: vectors longer than %d are not supported", RVM_MAX_DIM * RVM_MAX_DIM);
         const FdPosRec* inq = np % 2 ? m->q0.as<FdPosRec>() : m->q1.as<FdPosRec>();
         const int grid = (int)std::min<int64_t>((n + 3) / 4, (int64_t)ctx->num_cus * 8);
         hipLaunchKernelGGL(k_rvm_deep<U8IN>, dim3(grid), dim3(256), 0, st, m->dev, dfeats, rowBytes, scale, shift, inq, cnt + np, b[np],
