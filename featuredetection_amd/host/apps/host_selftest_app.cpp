@@ -5,6 +5,8 @@
 //   * DirectPyramidFeatureExtractor::extract(stepX, stepY, roi, firstLayer, lastLayer, stepLayer) on a HOG chain
 //   * FilteringPyramidFeatureExtractor: fused chain vs per-Mat composition of the same filters
 //   * the stand-alone ImageFilter::applyTo(const Mat&) of every filter
+//   * fdhost::with_capacity on a scan that does not fit its first buffer, and the logistic pair of a device model that a per-Mat
+//     call built first
 // usage: host_selftest_app <image.pgm> <out-dir>
 #include <cstdio>
 #include <fstream>
@@ -167,6 +169,32 @@ int main(int argc, char** argv) {
         }
         cv::Mat row = ReshapingFilter(1).applyTo(g20);
         std::printf("reshaped %d x %d\n", row.rows, row.cols);
+
+        // ---- 5. the capacity retry and the logistic pair of a classifier's device model, on the HOG chain of 2.
+        {
+            auto windows = hogEx->extract(8, 8);
+            if (windows.size() < 8 || !hogEx->getHogFilter()) throw std::runtime_error("the HOG chain has too few windows");
+            // four of the scanned windows as support vectors, threshold 1: each of them scores exp(0) plus three positive terms
+            std::vector<cv::Mat> vectors;
+            for (size_t k : {(size_t)0, windows.size() / 3, windows.size() / 2, windows.size() - 1}) vectors.push_back(windows[k]->getData());
+            auto psvm = make_shared<classification::ProbabilisticSvmClassifier>(make_shared<classification::RbfKernel>(1.0), 0.3, -1.7);
+            psvm->getSvm()->setSvmParameters(vectors, std::vector<float>(4, 1.f), 0.0);
+            psvm->getSvm()->setThreshold(1.0f);
+            // one Mat first: SvmClassifier::computeHyperplaneDistance builds the device model without knowing the logistic pair
+            psvm->getProbability(windows[1]->getData());
+            auto hog = hogEx->getHogFilter();
+            fd_hog_params hp = {hogEx->getPatchWidth(), hogEx->getPatchHeight(), 8, 8, hog->binCount, hog->cellWidth, hog->blockWidth, hog->signedAndUnsigned};
+            auto scan = [&](int64_t capacity) {
+                return fdhost::with_capacity<fd_detection>(capacity, [&](fd_detection* dets, int64_t cap, int64_t* count) {
+                    return fd_detect_hog_svm(fdhost::context(), hogEx->getPyramid()->native(), psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()),
+                                             &hp, dets, cap, count, nullptr);
+                });
+            };
+            const std::vector<fd_detection> retried = scan(1), fitting = scan((int64_t)1 << 16);
+            const bool equal = retried.size() == fitting.size() && std::memcmp(retried.data(), fitting.data(), sizeof(fd_detection) * fitting.size()) == 0;
+            std::printf("retry count_small %zu count_default %zu equal %d\n", retried.size(), fitting.size(), equal ? 1 : 0);
+            for (const fd_detection& d : fitting) std::printf("sigmoid %.9g %.17g\n", d.score, d.probability);
+        }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;

@@ -80,6 +80,36 @@ protected:
     float bias, threshold;
 };
 
+// not in the reference: the lazily built device model of a vector machine classifier.  It is built again when the classifier
+// changed (invalidate), when there is none yet, or when the logistic pair differs from the one it was built with: the fused scans
+// take fd_detection.probability from the device model's sigmoid.
+template <class Handle, void (*Destroy)(Handle*)>
+class DeviceModel {
+public:
+    DeviceModel() = default;
+    DeviceModel(const DeviceModel&) = delete;
+    DeviceModel& operator=(const DeviceModel&) = delete;
+    ~DeviceModel() { Destroy(handle); }
+    void invalidate() { dirty = true; }
+    // the model as it stands, whatever pair it was built with, or null when it has to be built: for the per-Mat distance calls,
+    // which do not read the sigmoid and so need no rebuild between two fused calls
+    const Handle* current() const { return dirty ? nullptr : handle; }
+    template <class Build>   // build(Handle** out) creates the model with this logistic pair, or throws
+    const Handle* get(double logisticA, double logisticB, Build build) {
+        if (dirty || !handle || logisticA != builtA || logisticB != builtB) {
+            Destroy(handle);
+            handle = nullptr;
+            build(&handle);
+            dirty = false; builtA = logisticA; builtB = logisticB;
+        }
+        return handle;
+    }
+private:
+    Handle* handle = nullptr;
+    bool dirty = true;
+    double builtA = 0, builtB = 0;
+};
+
 // SvmClassifier.hpp / SvmClassifier.cpp:32-159 -- scoring by fd_svm_distance_batch
 class SvmClassifier : public VectorMachineClassifier {
 public:
@@ -90,7 +120,7 @@ public:
     bool classify(double hyperplaneDistance) const { return hyperplaneDistance >= threshold; }
     double computeHyperplaneDistance(const cv::Mat& featureVector) const;
     void setSvmParameters(std::vector<cv::Mat> supportVectors, std::vector<float> coefficients, double bias);
-    void setThreshold(float t) override { threshold = t; dirty = true; }
+    void setThreshold(float t) override { threshold = t; device.invalidate(); }
     void store(std::ofstream& file);                       // SvmClassifier.cpp:68-107 text format
     static std::shared_ptr<SvmClassifier> load(std::ifstream& file);   // :109-159
     static std::shared_ptr<SvmClassifier> loadFromText(const std::string& classifierFilename);   // :161-239 (FullPolynomial text models)
@@ -100,8 +130,8 @@ public:
 private:
     std::vector<cv::Mat> supportVectors;
     std::vector<float> coefficients;
-    mutable fd_svm* handle;
-    mutable bool dirty;
+    const fd_svm* distanceModel() const { const fd_svm* m = device.current(); return m ? m : native(); }
+    mutable DeviceModel<fd_svm, fd_svm_destroy> device;
 };
 
 // ProbabilisticSvmClassifier.hpp / .cpp:36-164
@@ -161,8 +191,8 @@ private:
     Model model;
     std::vector<float> hierarchicalThresholds;
     float limitReliabilityFilter;
-    mutable fd_wvm* handle;
-    mutable bool dirty;
+    const fd_wvm* distanceModel() const { const fd_wvm* m = device.current(); return m ? m : native(); }
+    mutable DeviceModel<fd_wvm, fd_wvm_destroy> device;
 };
 
 // RvmClassifier.hpp / RvmClassifier.cpp:42-126 -- scoring by fd_rvm_eval_batch / fd_detect_rvm
@@ -193,9 +223,8 @@ public:
 private:
     Model model;
     unsigned int numFiltersToUse = 0;
-    mutable fd_rvm* handle = nullptr;
-    mutable bool dirty = true;
-    mutable double builtA = 0, builtB = 0;
+    const fd_rvm* distanceModel() const { const fd_rvm* m = device.current(); return m ? m : native(); }
+    mutable DeviceModel<fd_rvm, fd_rvm_destroy> device;
 };
 
 // ProbabilisticRvmClassifier.hpp / .cpp:32-115

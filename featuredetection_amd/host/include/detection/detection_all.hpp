@@ -109,6 +109,37 @@ private:
     float scoreThreshold;
 };
 
+// ---- Not in the reference: which device path a pair of extractor and classifier takes.  Stated once, for SlidingWindowDetector,
+// FiveStageSlidingWindowDetector and the condensation models.  Pure functions of the objects: they touch neither the pyramid's
+// handle nor the device.
+
+// a ProbabilisticSvmClassifier (null: false) whose SVM holds CV_32F support vectors; one without support vectors has none
+bool hasF32SupportVectors(const classification::ProbabilisticSvmClassifier* psvm);
+// the DirectPyramidFeatureExtractor whose patch filter chain the fused kernels run: the extractor itself, the equivalent of a
+// FilteringPyramidFeatureExtractor (getFusedExtractor(), null for a chain that is not fused), or null
+std::shared_ptr<imageprocessing::DirectPyramidFeatureExtractor> resolveFusedExtractor(
+    const std::shared_ptr<imageprocessing::PyramidFeatureExtractor>& extractor);
+// The sliding-window scan, in this order of precedence:
+enum class FusedScan {
+    Wvm,      // ProbabilisticWvmClassifier on a HistEq64Filter chain: fd_detect_wvm
+    HogSvm,   // ProbabilisticSvmClassifier, f32 vectors, RbfKernel, on getHogFilter(): fd_detect_hog_svm
+    Rvm,      // ProbabilisticRvmClassifier on getConversion() without histogram filter and whi chain: fd_detect_rvm
+    WhiSvm,   // ProbabilisticSvmClassifier, f32 vectors, on getWhiChain(): fd_detect_whi_svm
+    HistSvm,  // ProbabilisticSvmClassifier, f32 vectors, any kernel, on getHistogramFilter(): fd_detect_hist_svm
+    Generic   // everything else, a null fused extractor included: extract all, classify each through the per-Mat interface
+};
+FusedScan fusedScanRoute(const imageprocessing::DirectPyramidFeatureExtractor* fused, const classification::ProbabilisticClassifier* classifier);
+// The five-stage detector:
+enum class FiveStageRoute {
+    WvmSvm,      // ProbabilisticWvmClassifier on HistEq64 patches + a ProbabilisticSvmClassifier whose vectors are not f32 (u8, or none
+                 // yet): fd_detect_five_stage, fd_detect_five_stage_frames
+    RvmSecond,   // FusedScan::Rvm + a second stage that fits its filter size: a ProbabilisticSvmClassifier with f32 vectors of
+                 // filter_w * filter_h values, or a ProbabilisticRvmClassifier on another RvmClassifier: fd_detect_five_stage_rvm
+    Composition  // the reference's own composition, one classify() per survivor
+};
+FiveStageRoute fiveStageRoute(const imageprocessing::DirectPyramidFeatureExtractor* fused, const classification::ProbabilisticClassifier* first,
+                              const classification::ProbabilisticClassifier* second);
+
 // SlidingWindowDetector.hpp:41-93 / SlidingWindowDetector.cpp:40-98
 class SlidingWindowDetector : public Detector {
 public:

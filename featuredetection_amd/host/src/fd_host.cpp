@@ -32,6 +32,7 @@ fd_ctx* context() {
 }  // namespace fdhost
 using fdhost::check;
 using fdhost::context;
+using fdhost::with_capacity;
 
 static Mat contiguous(const Mat& m) { return m.isContinuous() ? m : m.clone(); }
 
@@ -1150,18 +1151,16 @@ double Kernel::compute(const Mat& lhs, const Mat& rhs) const {
     return out;
 }
 
-SvmClassifier::SvmClassifier(shared_ptr<Kernel> kernel) : VectorMachineClassifier(kernel), handle(nullptr), dirty(true) {}
-SvmClassifier::~SvmClassifier() { fd_svm_destroy(handle); }
+SvmClassifier::SvmClassifier(shared_ptr<Kernel> kernel) : VectorMachineClassifier(kernel) {}
+SvmClassifier::~SvmClassifier() {}
 void SvmClassifier::setSvmParameters(vector<Mat> sv, vector<float> coeff, double b) {
     supportVectors = sv;
     coefficients = coeff;
     bias = (float)b;
-    dirty = true;
+    device.invalidate();
 }
 const fd_svm* SvmClassifier::native(double la, double lb) const {
-    if (dirty || !handle) {
-        fd_svm_destroy(handle);
-        handle = nullptr;
+    return device.get(la, lb, [&](fd_svm** handle) {
         if (supportVectors.empty() || supportVectors.size() != coefficients.size())
             throw std::runtime_error("SvmClassifier: no support vectors / coefficient count mismatch");
         const Mat& first = supportVectors.front();
@@ -1188,17 +1187,15 @@ const fd_svm* SvmClassifier::native(double la, double lb) const {
         m.threshold = threshold;
         m.logistic_a = la;
         m.logistic_b = lb;
-        check(fd_svm_create(context(), &m, &handle));
-        dirty = false;
-    }
-    return handle;
+        check(fd_svm_create(context(), &m, handle));
+    });
 }
 double SvmClassifier::computeHyperplaneDistance(const Mat& featureVector) const {
     if (!supportVectors.empty() && featureVector.depth() != supportVectors[0].depth())   // as the reference's kernels (RbfKernel.hpp: lhs.flags != rhs.flags)
         throw std::invalid_argument("SvmClassifier: feature vector and support vectors have to have the same type");
     Mat x = contiguous(featureVector);
     double out = 0;
-    check(fd_svm_distance_batch(context(), native(), x.data, 1, &out));
+    check(fd_svm_distance_batch(context(), distanceModel(), x.data, 1, &out));
     return out;
 }
 bool SvmClassifier::classify(const Mat& featureVector) const { return classify(computeHyperplaneDistance(featureVector)); }
@@ -1259,7 +1256,6 @@ shared_ptr<SvmClassifier> SvmClassifier::load(std::ifstream& file) {   // SvmCla
         svm->supportVectors.push_back(v);
     }
     if (!file) throw std::runtime_error("SvmClassifier: Invalid classifier file");
-    svm->dirty = true;
     return svm;
 }
 
@@ -1364,8 +1360,8 @@ shared_ptr<ProbabilisticSvmClassifier> ProbabilisticSvmClassifier::load(const bo
 }
 
 // ---- WVM ------------------------------------------------------------------------------------------
-WvmClassifier::WvmClassifier() : VectorMachineClassifier(nullptr), limitReliabilityFilter(0.f), handle(nullptr), dirty(true) {}
-WvmClassifier::~WvmClassifier() { fd_wvm_destroy(handle); }
+WvmClassifier::WvmClassifier() : VectorMachineClassifier(nullptr), limitReliabilityFilter(0.f) {}
+WvmClassifier::~WvmClassifier() {}
 void WvmClassifier::setModel(const Model& m) {
     model = m;
     bias = m.bias;
@@ -1374,19 +1370,17 @@ void WvmClassifier::setModel(const Model& m) {
 }
 void WvmClassifier::setNumUsedFilters(int var) {   // WvmClassifier.cpp:151-158
     model.num_used = (var > model.num_filters || var == 0) ? model.num_filters : var;
-    dirty = true;
+    device.invalidate();
 }
 void WvmClassifier::setLimitReliabilityFilter(float var) {   // WvmClassifier.cpp:165-181
     limitReliabilityFilter = var;
     hierarchicalThresholds = model.thresholdsFromFile;
     if (var != 0.0f)
         for (float& t : hierarchicalThresholds) t = t + limitReliabilityFilter;
-    dirty = true;
+    device.invalidate();
 }
 const fd_wvm* WvmClassifier::native(double la, double lb) const {
-    if (dirty || !handle) {
-        fd_wvm_destroy(handle);
-        handle = nullptr;
+    return device.get(la, lb, [&](fd_wvm** handle) {
         fd_wvm_model m;
         std::memset(&m, 0, sizeof(m));
         m.filter_w = model.filter_w; m.filter_h = model.filter_h; m.num_filters = model.num_filters; m.num_used = model.num_used;
@@ -1398,10 +1392,8 @@ const fd_wvm* WvmClassifier::native(double la, double lb) const {
         // a file with too short offset tables would be read out of bounds before the library sees it
         if ((int)model.val_off.size() != model.num_filters + 1 || model.val_off.back() < 0 || (int)model.rec_off.size() != model.val_off.back() + 1)
             throw std::invalid_argument("WvmClassifier: inconsistent offset tables in the model");
-        check(fd_wvm_create(context(), &m, &handle));
-        dirty = false;
-    }
-    return handle;
+        check(fd_wvm_create(context(), &m, handle));
+    });
 }
 std::pair<int, double> WvmClassifier::computeHyperplaneDistance(const Mat& featureVector) const {
     if (featureVector.depth() != CV_8U || (int)(featureVector.total() * featureVector.channels()) != model.filter_w * model.filter_h)
@@ -1409,7 +1401,7 @@ std::pair<int, double> WvmClassifier::computeHyperplaneDistance(const Mat& featu
     Mat x = contiguous(featureVector);
     int32_t level = 0;
     float fout = 0;
-    check(fd_wvm_eval_batch(context(), native(), x.data, 1, &level, &fout));
+    check(fd_wvm_eval_batch(context(), distanceModel(), x.data, 1, &level, &fout));
     return std::make_pair((int)level, (double)fout);
 }
 bool WvmClassifier::classify(std::pair<int, double> lad) const {   // WvmClassifier.cpp:91-98
@@ -1453,25 +1445,21 @@ shared_ptr<WvmClassifier> WvmClassifier::loadFromFile(const string& filename) {
 
 // ---- RVM ------------------------------------------------------------------------------------------
 RvmClassifier::RvmClassifier(shared_ptr<Kernel> kernel, bool) : VectorMachineClassifier(kernel) {}
-RvmClassifier::~RvmClassifier() { fd_rvm_destroy(handle); }
+RvmClassifier::~RvmClassifier() {}
 void RvmClassifier::setNumFiltersToUse(unsigned int numFilters) {   // RvmClassifier.cpp:119-126
     numFiltersToUse = (numFilters == 0 || numFilters > (unsigned int)model.num_filters) ? (unsigned int)model.num_filters : numFilters;
-    dirty = true;
+    device.invalidate();
 }
 const fd_rvm* RvmClassifier::native(double la, double lb) const {
-    if (dirty || !handle || la != builtA || lb != builtB) {
-        fd_rvm_destroy(handle);
-        handle = nullptr;
+    return device.get(la, lb, [&](fd_rvm** handle) {
         fd_rvm_model m;
         std::memset(&m, 0, sizeof(m));
         m.kernel = model.kernel; m.p0 = model.p0; m.p1 = model.p1; m.p2 = model.p2;
         m.num_filters = model.num_filters; m.num_used = (int)numFiltersToUse; m.filter_w = model.filter_w; m.filter_h = model.filter_h;
         m.support_vectors = model.support_vectors.data(); m.coefficients = model.coefficients.data(); m.thresholds = model.thresholds.data();
         m.bias = model.bias; m.logistic_a = la; m.logistic_b = lb;
-        check(fd_rvm_create(context(), &m, &handle));
-        dirty = false; builtA = la; builtB = lb;
-    }
-    return handle;
+        check(fd_rvm_create(context(), &m, handle));
+    });
 }
 std::pair<int, double> RvmClassifier::computeHyperplaneDistance(const Mat& featureVector) const {
     if (featureVector.depth() != CV_32F || (int)(featureVector.total() * featureVector.channels()) != model.filter_w * model.filter_h)
@@ -1479,7 +1467,7 @@ std::pair<int, double> RvmClassifier::computeHyperplaneDistance(const Mat& featu
     Mat x = contiguous(featureVector);
     int32_t level = 0;
     double dist = 0;
-    check(fd_rvm_eval_batch(context(), native(), x.ptr<float>(0), 1, &level, &dist));
+    check(fd_rvm_eval_batch(context(), distanceModel(), x.ptr<float>(0), 1, &level, &dist));
     return std::make_pair((int)level, dist);
 }
 bool RvmClassifier::classify(std::pair<int, double> lad) const {   // RvmClassifier.cpp:66-73
@@ -1879,6 +1867,7 @@ void LibLinearClassifier::reset() {   // :150-155
 
 // =================================================================================================
 namespace detection {
+using classification::ProbabilisticRvmClassifier;
 using classification::ProbabilisticSvmClassifier;
 using classification::ProbabilisticWvmClassifier;
 using imageprocessing::DirectPyramidFeatureExtractor;
@@ -1887,12 +1876,56 @@ using imageprocessing::Patch;
 static shared_ptr<ClassifiedPatch> to_patch(const fd_detection& d) {
     return make_shared<ClassifiedPatch>(make_shared<Patch>(d.cx, d.cy, d.w, d.h, Mat()), d.positive != 0, d.probability);
 }
+static vector<shared_ptr<ClassifiedPatch>> to_patches(const vector<fd_detection>& dets) {
+    vector<shared_ptr<ClassifiedPatch>> out;
+    for (const fd_detection& d : dets) out.push_back(to_patch(d));
+    return out;
+}
 static fd_detection from_patch(const ClassifiedPatch& p) {
     fd_detection d;
     std::memset(&d, 0, sizeof(d));
     d.cx = p.getPatch()->getX(); d.cy = p.getPatch()->getY(); d.w = p.getPatch()->getWidth(); d.h = p.getPatch()->getHeight();
     d.positive = p.isPositive(); d.probability = p.getProbability();
     return d;
+}
+
+// ---- the route decision (not in the reference) ------------------------------------------------------------------------------------
+bool hasF32SupportVectors(const ProbabilisticSvmClassifier* psvm) {
+    return psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+}
+shared_ptr<DirectPyramidFeatureExtractor> resolveFusedExtractor(const shared_ptr<imageprocessing::PyramidFeatureExtractor>& extractor) {
+    if (auto filtering = std::dynamic_pointer_cast<imageprocessing::FilteringPyramidFeatureExtractor>(extractor)) return filtering->getFusedExtractor();
+    return std::dynamic_pointer_cast<DirectPyramidFeatureExtractor>(extractor);
+}
+FusedScan fusedScanRoute(const DirectPyramidFeatureExtractor* fused, const classification::ProbabilisticClassifier* classifier) {
+    if (!fused) return FusedScan::Generic;
+    auto* psvm = dynamic_cast<const ProbabilisticSvmClassifier*>(classifier);
+    const bool f32sv = hasF32SupportVectors(psvm);
+    if (dynamic_cast<const ProbabilisticWvmClassifier*>(classifier) && fused->hasHistEq64()) return FusedScan::Wvm;
+    if (f32sv && fused->getHogFilter() && std::dynamic_pointer_cast<classification::RbfKernel>(psvm->getSvm()->getKernel())) return FusedScan::HogSvm;
+    if (dynamic_cast<const ProbabilisticRvmClassifier*>(classifier) && fused->getConversion() && !fused->getHistogramFilter() && !fused->getWhiChain())
+        return FusedScan::Rvm;
+    if (f32sv && fused->getWhiChain()) return FusedScan::WhiSvm;
+    if (f32sv && fused->getHistogramFilter()) return FusedScan::HistSvm;
+    return FusedScan::Generic;
+}
+FiveStageRoute fiveStageRoute(const DirectPyramidFeatureExtractor* fused, const classification::ProbabilisticClassifier* first,
+                              const classification::ProbabilisticClassifier* second) {
+    auto* psvm = dynamic_cast<const ProbabilisticSvmClassifier*>(second);
+    if (fused && dynamic_cast<const ProbabilisticWvmClassifier*>(first) && psvm && fused->hasHistEq64() && !hasF32SupportVectors(psvm))
+        return FiveStageRoute::WvmSvm;
+    if (fusedScanRoute(fused, first) != FusedScan::Rvm) return FiveStageRoute::Composition;
+    auto* prvm = dynamic_cast<const ProbabilisticRvmClassifier*>(first);
+    const classification::RvmClassifier::Model& m1 = prvm->getRvm()->getModel();
+    bool fits = false;
+    if (hasF32SupportVectors(psvm)) {
+        const Mat& sv = psvm->getSvm()->getSupportVectors()[0];
+        fits = (int)(sv.total() * sv.channels()) == m1.filter_w * m1.filter_h;
+    } else if (auto* prvm2 = dynamic_cast<const ProbabilisticRvmClassifier*>(second)) {
+        const classification::RvmClassifier::Model& m2 = prvm2->getRvm()->getModel();
+        fits = prvm2->getRvm() != prvm->getRvm() && m2.filter_w == m1.filter_w && m2.filter_h == m1.filter_h;
+    }
+    return fits ? FiveStageRoute::RvmSecond : FiveStageRoute::Composition;
 }
 
 vector<shared_ptr<ClassifiedPatch>> OverlapElimination::eliminate(vector<shared_ptr<ClassifiedPatch>>& classifiedPatches) {
@@ -2140,16 +2173,11 @@ vector<double> AggregatedFeaturesDetector::getLambdas() const {
 AggregatedFeaturesDetector::~AggregatedFeaturesDetector() { fd_aggregated_destroy(handle); }
 vector<std::pair<cv::Rect, float>> AggregatedFeaturesDetector::detectWithScores(shared_ptr<imageprocessing::VersionedImage> image) {
     Mat img = contiguous(image->getData());
-    vector<fd_box> out(1 << 14);
-    int n = 0;
-    int rc = fd_aggregated_detect(context(), handle, img.data, img.cols, img.rows, img.channels(), 0, out.data(), (int)out.size(), &n, nullptr, 0, nullptr);
-    if (rc == FD_ERR_CAPACITY) {
-        out.resize((size_t)n);
-        rc = fd_aggregated_detect(context(), handle, img.data, img.cols, img.rows, img.channels(), 0, out.data(), n, &n, nullptr, 0, nullptr);
-    }
-    check(rc);
+    const vector<fd_box> out = with_capacity<fd_box>(1 << 14, [&](fd_box* boxes, int cap, int* n) {
+        return fd_aggregated_detect(context(), handle, img.data, img.cols, img.rows, img.channels(), 0, boxes, cap, n, nullptr, 0, nullptr);
+    });
     vector<std::pair<cv::Rect, float>> res;
-    for (int i = 0; i < n; ++i) res.emplace_back(cv::Rect(out[i].x, out[i].y, out[i].w, out[i].h), out[i].score);
+    for (const fd_box& b : out) res.emplace_back(cv::Rect(b.x, b.y, b.w, b.h), b.score);
     return res;
 }
 vector<cv::Rect> AggregatedFeaturesDetector::detect(shared_ptr<imageprocessing::VersionedImage> image) {
@@ -2176,96 +2204,62 @@ vector<shared_ptr<ClassifiedPatch>> SlidingWindowDetector::detect(const cv::Rect
     return out;
 }
 vector<shared_ptr<ClassifiedPatch>> SlidingWindowDetector::detectWindows(const cv::Rect* roi) const {
-    vector<shared_ptr<ClassifiedPatch>> out;
-    auto direct = std::dynamic_pointer_cast<DirectPyramidFeatureExtractor>(featureExtractor);
-    if (auto filtering = std::dynamic_pointer_cast<imageprocessing::FilteringPyramidFeatureExtractor>(featureExtractor))
-        direct = filtering->getFusedExtractor();   // ffpDetectApp.cpp:445: same pyramid, the chain as patch filters; null = generic composition
+    auto direct = resolveFusedExtractor(featureExtractor);   // ffpDetectApp.cpp:445: same pyramid, the chain as patch filters; null = generic composition
     // the region of interest (SlidingWindowDetector.cpp:53-78) and the scale range of a pyramid built on another pyramid
     // apply to the window enumeration of every fused chain
     std::unique_ptr<imageprocessing::ImagePyramid::Selection> selection;
     if (direct) selection.reset(new imageprocessing::ImagePyramid::Selection(direct->getPyramid()->select(-1, -1, 1, roi)));
-    auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(classifier);
     auto psvm = std::dynamic_pointer_cast<ProbabilisticSvmClassifier>(classifier);
     int r[4] = {0, 0, 0, 0};
     if (roi) { r[0] = roi->x; r[1] = roi->y; r[2] = roi->width; r[3] = roi->height; }
-    if (direct && pwvm && direct->hasHistEq64()) {   // fused extract + HistEq64 + WVM cascade
+    const int64_t cap = 1 << 16;
+    switch (fusedScanRoute(direct.get(), classifier.get())) {
+    case FusedScan::Wvm: {   // fused extract + HistEq64 + WVM cascade
+        auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(classifier);
         const fd_wvm* w = pwvm->getWvm()->native(pwvm->getLogisticA(), pwvm->getLogisticB());
-        int64_t cnt = 0, cap = 1 << 16;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_wvm(context(), direct->getPyramid()->native(), w, stepSizeX, stepSizeY, roi ? r : nullptr, dets.data(), cap, &cnt, nullptr, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_wvm(context(), direct->getPyramid()->native(), w, stepSizeX, stepSizeY, roi ? r : nullptr, dets.data(), cnt, &cnt, nullptr, nullptr);
-        }
-        check(rc);
-        for (int64_t i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-        return out;
+        return to_patches(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int64_t n, int64_t* cnt) {
+            return fd_detect_wvm(context(), direct->getPyramid()->native(), w, stepSizeX, stepSizeY, roi ? r : nullptr, dets, n, cnt, nullptr, nullptr);
+        }));
     }
-    const bool f32sv = psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
-    if (direct && psvm && direct->getHogFilter() && f32sv &&
-        std::dynamic_pointer_cast<classification::RbfKernel>(psvm->getSvm()->getKernel())) {   // fused HOG + MFMA RBF-SVM
+    case FusedScan::HogSvm: {   // fused HOG + MFMA RBF-SVM
         auto hog = direct->getHogFilter();
         fd_hog_params hp = {direct->getPatchWidth(), direct->getPatchHeight(), stepSizeX, stepSizeY, hog->binCount, hog->cellWidth, hog->blockWidth,
                             hog->signedAndUnsigned};
         const fd_svm* s = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-        int64_t cnt = 0, cap = 1 << 16;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_hog_svm(context(), direct->getPyramid()->native(), s, &hp, dets.data(), cap, &cnt, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_hog_svm(context(), direct->getPyramid()->native(), s, &hp, dets.data(), cnt, &cnt, nullptr);
-        }
-        check(rc);
-        for (int64_t i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-        return out;
+        return to_patches(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int64_t n, int64_t* cnt) {
+            return fd_detect_hog_svm(context(), direct->getPyramid()->native(), s, &hp, dets, n, cnt, nullptr);
+        }));
     }
-    auto prvm = std::dynamic_pointer_cast<classification::ProbabilisticRvmClassifier>(classifier);
-    if (direct && prvm && direct->getConversion() && !direct->getHistogramFilter() && !direct->getWhiChain()) {   // fused RVM cascade ("prvm")
+    case FusedScan::Rvm: {   // fused RVM cascade ("prvm")
+        auto prvm = std::dynamic_pointer_cast<ProbabilisticRvmClassifier>(classifier);
         auto cf = direct->getConversion();
         fd_rvm_detect_params dp = {direct->getU8FeatureSpace(), (float)cf->alpha, (float)cf->beta, stepSizeX, stepSizeY};
         const fd_rvm* rv = prvm->getRvm()->native(prvm->getLogisticA(), prvm->getLogisticB());
-        int64_t cnt = 0, cap = 1 << 16;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_rvm(context(), direct->getPyramid()->native(), rv, &dp, roi ? r : nullptr, dets.data(), cap, &cnt, nullptr, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_rvm(context(), direct->getPyramid()->native(), rv, &dp, roi ? r : nullptr, dets.data(), cnt, &cnt, nullptr, nullptr);
-        }
-        check(rc);
-        for (int64_t i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-        return out;
+        return to_patches(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int64_t n, int64_t* cnt) {
+            return fd_detect_rvm(context(), direct->getPyramid()->native(), rv, &dp, roi ? r : nullptr, dets, n, cnt, nullptr, nullptr);
+        }));
     }
-    if (direct && psvm && direct->getWhiChain() && f32sv) {   // fused whi chain + SVM (ffpDetectApp.cpp:449-454, "psvm")
+    case FusedScan::WhiSvm: {   // fused whi chain + SVM (ffpDetectApp.cpp:449-454, "psvm")
         auto wf = direct->getWhiChain();
         fd_whi_params wp = {direct->getPatchWidth(), direct->getPatchHeight(), stepSizeX, stepSizeY, wf->alpha, wf->cutoffFrequency};
         const fd_svm* s = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-        int64_t cnt = 0, cap = 1 << 16;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_whi_svm(context(), direct->getPyramid()->native(), s, &wp, dets.data(), cap, &cnt, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_whi_svm(context(), direct->getPyramid()->native(), s, &wp, dets.data(), cnt, &cnt, nullptr);
-        }
-        check(rc);
-        for (int64_t i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-        return out;
+        return to_patches(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int64_t n, int64_t* cnt) {
+            return fd_detect_whi_svm(context(), direct->getPyramid()->native(), s, &wp, dets, n, cnt, nullptr);
+        }));
     }
-    if (direct && psvm && direct->getHistogramFilter() && f32sv) {   // fused histogram features + SVM (any kernel)
+    case FusedScan::HistSvm: {   // fused histogram features + SVM (any kernel)
         fd_hist_params hp = hist_params_of(*direct->getHistogramFilter(), direct->getPatchWidth(), direct->getPatchHeight(), stepSizeX, stepSizeY);
         const fd_svm* s = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-        int64_t cnt = 0, cap = 1 << 16;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_hist_svm(context(), direct->getPyramid()->native(), s, &hp, dets.data(), cap, &cnt, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_hist_svm(context(), direct->getPyramid()->native(), s, &hp, dets.data(), cnt, &cnt, nullptr);
-        }
-        check(rc);
-        for (int64_t i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-        return out;
+        return to_patches(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int64_t n, int64_t* cnt) {
+            return fd_detect_hist_svm(context(), direct->getPyramid()->native(), s, &hp, dets, n, cnt, nullptr);
+        }));
+    }
+    case FusedScan::Generic:
+        break;
     }
     // generic composition (SlidingWindowDetector.cpp:87-98): extract all, classify each through the per-Mat interface
     selection.reset();
+    vector<shared_ptr<ClassifiedPatch>> out;
     auto patches = roi ? featureExtractor->extract(stepSizeX, stepSizeY, *roi) : featureExtractor->extract(stepSizeX, stepSizeY);
     for (auto& p : patches) {
         auto res = classifier->getProbability(p->getData());
@@ -2290,87 +2284,54 @@ FiveStageSlidingWindowDetector::FiveStageSlidingWindowDetector(shared_ptr<Slidin
                                                                shared_ptr<classification::ProbabilisticClassifier> strong)
     : slidingWindowDetector(swd), overlapElimination(oe), strongClassifier(strong) {}
 
-static bool svm_vectors_are_f32(const shared_ptr<ProbabilisticSvmClassifier>& psvm) {
-    return psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
-}
-// path 1 below, for run and detectFrames alike: what fd_detect_five_stage and fd_detect_five_stage_frames accept
-static bool five_stage_wvm_pair(const shared_ptr<DirectPyramidFeatureExtractor>& direct, const shared_ptr<ProbabilisticWvmClassifier>& pwvm,
-                                const shared_ptr<ProbabilisticSvmClassifier>& psvm) {
-    return direct && pwvm && psvm && direct->hasHistEq64() && !svm_vectors_are_f32(psvm);
-}
-
-// Three paths:
-//  1. ProbabilisticWvmClassifier on HistEq64 patches + ProbabilisticSvmClassifier with u8 support vectors: fd_detect_five_stage
-//  2. the fused RVM case of SlidingWindowDetector::detectWindows ("prvm": a ConversionFilter behind a u8 feature space) + a
+// Three paths, chosen by fiveStageRoute:
+//  WvmSvm: ProbabilisticWvmClassifier on HistEq64 patches + ProbabilisticSvmClassifier with u8 support vectors: fd_detect_five_stage
+//  RvmSecond: the fused RVM case of SlidingWindowDetector::detectWindows ("prvm": a ConversionFilter behind a u8 feature space) + a
 //     ProbabilisticSvmClassifier with f32 support vectors or a ProbabilisticRvmClassifier: fd_detect_five_stage_rvm
-//  3. anything else: the reference's own composition, one classify() per survivor (FiveStageSlidingWindowDetector.cpp:187-320 / :331-380)
+//  Composition: anything else: the reference's own composition, one classify() per survivor (FiveStageSlidingWindowDetector.cpp:187-320 / :331-380)
 vector<shared_ptr<ClassifiedPatch>> FiveStageSlidingWindowDetector::run(const Mat& image, const cv::Rect* roi) {
-    auto direct = std::dynamic_pointer_cast<DirectPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor());
-    if (auto filtering = std::dynamic_pointer_cast<imageprocessing::FilteringPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor()))
-        direct = filtering->getFusedExtractor();
-    auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(slidingWindowDetector->getClassifier());
+    auto direct = resolveFusedExtractor(slidingWindowDetector->getPyramidFeatureExtractor());
+    auto weak = slidingWindowDetector->getClassifier();
     auto psvm = std::dynamic_pointer_cast<ProbabilisticSvmClassifier>(strongClassifier);
-    const bool f32sv = svm_vectors_are_f32(psvm);
     int r[4] = {0, 0, 0, 0};
     if (roi) { r[0] = roi->x; r[1] = roi->y; r[2] = roi->width; r[3] = roi->height; }
-    if (five_stage_wvm_pair(direct, pwvm, psvm)) {
-        direct->update(image);
-        auto selection = direct->getPyramid()->select();   // the scale range of a pyramid built on another pyramid
-        int cnt = 0, cap = 4096;
-        vector<fd_detection> dets((size_t)cap);
-        int rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(pwvm->getLogisticA(), pwvm->getLogisticB()),
-                                      psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()), overlapElimination->getDist(),
-                                      overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(), slidingWindowDetector->getStepSizeY(),
-                                      roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
-        if (rc == FD_ERR_CAPACITY) {
-            dets.resize((size_t)cnt);
-            rc = fd_detect_five_stage(context(), direct->getPyramid()->native(), pwvm->getWvm()->native(), psvm->getSvm()->native(),
-                                      overlapElimination->getDist(), overlapElimination->getRatio(), slidingWindowDetector->getStepSizeX(),
-                                      slidingWindowDetector->getStepSizeY(), roi ? r : nullptr, dets.data(), cnt, &cnt, nullptr);
-        }
-        check(rc);
-        vector<shared_ptr<ClassifiedPatch>> out;
-        for (int i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
+    const int cap = 4096;
+    auto finish = [&](const vector<fd_detection>& dets) {
+        auto out = to_patches(dets);
         if (patchData) fillPatchData(*slidingWindowDetector->getPyramidFeatureExtractor(), out);   // the patches of the shared extractor (FiveStageSlidingWindowDetector.cpp:187-380)
         return out;
+    };
+    switch (fiveStageRoute(direct.get(), weak.get(), strongClassifier.get())) {
+    case FiveStageRoute::WvmSvm: {
+        auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(weak);
+        direct->update(image);
+        auto selection = direct->getPyramid()->select();   // the scale range of a pyramid built on another pyramid
+        const fd_wvm* w = pwvm->getWvm()->native(pwvm->getLogisticA(), pwvm->getLogisticB());
+        const fd_svm* s = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
+        return finish(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int n, int* cnt) {
+            return fd_detect_five_stage(context(), direct->getPyramid()->native(), w, s, overlapElimination->getDist(), overlapElimination->getRatio(),
+                                        slidingWindowDetector->getStepSizeX(), slidingWindowDetector->getStepSizeY(), roi ? r : nullptr, dets, n, cnt, nullptr);
+        }));
     }
-    auto prvm = std::dynamic_pointer_cast<classification::ProbabilisticRvmClassifier>(slidingWindowDetector->getClassifier());
-    auto prvm2 = std::dynamic_pointer_cast<classification::ProbabilisticRvmClassifier>(strongClassifier);
-    if (direct && prvm && direct->getConversion() && !direct->getHistogramFilter() && !direct->getWhiChain()) {
-        const classification::RvmClassifier::Model& m1 = prvm->getRvm()->getModel();
-        bool second = false;
-        if (f32sv) {
-            const Mat& sv = psvm->getSvm()->getSupportVectors()[0];
-            second = (int)(sv.total() * sv.channels()) == m1.filter_w * m1.filter_h;
-        } else if (prvm2 && prvm2->getRvm() != prvm->getRvm()) {
-            const classification::RvmClassifier::Model& m2 = prvm2->getRvm()->getModel();
-            second = m2.filter_w == m1.filter_w && m2.filter_h == m1.filter_h;
-        }
-        if (second) {
-            direct->update(image);
-            auto selection = direct->getPyramid()->select();
-            auto cf = direct->getConversion();
-            fd_rvm_detect_params dp = {direct->getU8FeatureSpace(), (float)cf->alpha, (float)cf->beta, slidingWindowDetector->getStepSizeX(),
-                                       slidingWindowDetector->getStepSizeY()};
-            const fd_rvm* first = prvm->getRvm()->native(prvm->getLogisticA(), prvm->getLogisticB());
-            const fd_svm* s2 = f32sv ? psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()) : nullptr;
-            const fd_rvm* r2 = f32sv ? nullptr : prvm2->getRvm()->native(prvm2->getLogisticA(), prvm2->getLogisticB());
-            int cnt = 0, cap = 4096;
-            vector<fd_detection> dets((size_t)cap);
-            int rc = fd_detect_five_stage_rvm(context(), direct->getPyramid()->native(), first, &dp, s2, r2, overlapElimination->getDist(),
-                                              overlapElimination->getRatio(), roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
-            if (rc == FD_ERR_CAPACITY) {
-                cap = cnt;
-                dets.resize((size_t)cap);
-                rc = fd_detect_five_stage_rvm(context(), direct->getPyramid()->native(), first, &dp, s2, r2, overlapElimination->getDist(),
-                                              overlapElimination->getRatio(), roi ? r : nullptr, dets.data(), cap, &cnt, nullptr);
-            }
-            check(rc);
-            vector<shared_ptr<ClassifiedPatch>> out;
-            for (int i = 0; i < cnt; ++i) out.push_back(to_patch(dets[i]));
-            if (patchData) fillPatchData(*slidingWindowDetector->getPyramidFeatureExtractor(), out);
-            return out;
-        }
+    case FiveStageRoute::RvmSecond: {
+        auto prvm = std::dynamic_pointer_cast<ProbabilisticRvmClassifier>(weak);
+        auto prvm2 = std::dynamic_pointer_cast<ProbabilisticRvmClassifier>(strongClassifier);
+        const bool f32sv = hasF32SupportVectors(psvm.get());
+        direct->update(image);
+        auto selection = direct->getPyramid()->select();
+        auto cf = direct->getConversion();
+        fd_rvm_detect_params dp = {direct->getU8FeatureSpace(), (float)cf->alpha, (float)cf->beta, slidingWindowDetector->getStepSizeX(),
+                                   slidingWindowDetector->getStepSizeY()};
+        const fd_rvm* first = prvm->getRvm()->native(prvm->getLogisticA(), prvm->getLogisticB());
+        const fd_svm* s2 = f32sv ? psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB()) : nullptr;
+        const fd_rvm* r2 = f32sv ? nullptr : prvm2->getRvm()->native(prvm2->getLogisticA(), prvm2->getLogisticB());
+        return finish(with_capacity<fd_detection>(cap, [&](fd_detection* dets, int n, int* cnt) {
+            return fd_detect_five_stage_rvm(context(), direct->getPyramid()->native(), first, &dp, s2, r2, overlapElimination->getDist(),
+                                            overlapElimination->getRatio(), roi ? r : nullptr, dets, n, cnt, nullptr);
+        }));
+    }
+    case FiveStageRoute::Composition:
+        break;
     }
     // the reference's composition: the first detector's positives with their patch data, overlap elimination, one classify() per survivor
     vector<shared_ptr<ClassifiedPatch>> first;
@@ -2412,9 +2373,8 @@ FiveStageSlidingWindowDetector::~FiveStageSlidingWindowDetector() { if (framesPy
 
 vector<vector<shared_ptr<ClassifiedPatch>>> FiveStageSlidingWindowDetector::detectFrames(const vector<Mat>& images) {
     vector<vector<shared_ptr<ClassifiedPatch>>> out(images.size());
-    auto direct = std::dynamic_pointer_cast<DirectPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor());
-    if (auto filtering = std::dynamic_pointer_cast<imageprocessing::FilteringPyramidFeatureExtractor>(slidingWindowDetector->getPyramidFeatureExtractor()))
-        direct = filtering->getFusedExtractor();
+    auto direct = resolveFusedExtractor(slidingWindowDetector->getPyramidFeatureExtractor());
+    const bool wvmSvm = fiveStageRoute(direct.get(), slidingWindowDetector->getClassifier().get(), strongClassifier.get()) == FiveStageRoute::WvmSvm;
     auto pwvm = std::dynamic_pointer_cast<ProbabilisticWvmClassifier>(slidingWindowDetector->getClassifier());
     auto psvm = std::dynamic_pointer_cast<ProbabilisticSvmClassifier>(strongClassifier);
     size_t i = 0;
@@ -2425,7 +2385,7 @@ vector<vector<shared_ptr<ClassifiedPatch>>> FiveStageSlidingWindowDetector::dete
         const int n = (int)(j - i);
         const int ch = images[i].channels();
         // (keepPatchData: the patches are cut from the extractor's own pyramid, which the multi-frame path never fills: one image at a time)
-        bool fused = !patchData && five_stage_wvm_pair(direct, pwvm, psvm) && n > 1 && images[i].depth() == CV_8U && (ch == 1 || ch == 3);
+        bool fused = !patchData && wvmSvm && n > 1 && images[i].depth() == CV_8U && (ch == 1 || ch == 3);
         if (fused && (!framesPyramid || framesCount != n)) {
             if (framesPyramid) { fd_pyramid_destroy(framesPyramid); framesPyramid = nullptr; }
             framesPyramid = direct->getPyramid()->createFramesPyramid(n);
@@ -2677,6 +2637,21 @@ namespace condensation {
 
 double Sample::aspectRatio = 1;
 
+// the samples as the C ABI takes them: {x, y, width, height} each (Sample::getX / getY / getWidth / getHeight)
+static vector<int32_t> pack_samples(const vector<shared_ptr<Sample>>& samples) {
+    vector<int32_t> xywh;
+    xywh.reserve(4 * samples.size());
+    for (const auto& s : samples) xywh.insert(xywh.end(), {s->getX(), s->getY(), s->getWidth(), s->getHeight()});
+    return xywh;
+}
+// what an fd_*_evaluate_samples call returned, back into the samples
+static void unpack_samples(const vector<uint8_t>& target, const vector<double>& weight, vector<shared_ptr<Sample>>& samples) {
+    for (size_t i = 0; i < samples.size(); ++i) {
+        samples[i]->setTarget(target[i] != 0);
+        samples[i]->setWeight(weight[i]);
+    }
+}
+
 WvmSvmModel::WvmSvmModel(shared_ptr<imageprocessing::FeatureExtractor> featureExtractor, shared_ptr<classification::ProbabilisticWvmClassifier> wvm,
                          shared_ptr<classification::ProbabilisticSvmClassifier> svm)
     : featureExtractor(featureExtractor), wvm(wvm), svm(svm) {}
@@ -2709,19 +2684,12 @@ void WvmSvmModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, ve
     auto* direct = fused_extractor(featureExtractor);
     const int n = (int)samples.size();
     if (n == 0) return;
-    vector<int32_t> xywh((size_t)4 * n);
-    for (int i = 0; i < n; ++i) {
-        xywh[4 * i] = samples[i]->getX(); xywh[4 * i + 1] = samples[i]->getY();
-        xywh[4 * i + 2] = samples[i]->getWidth(); xywh[4 * i + 3] = samples[i]->getHeight();
-    }
+    const vector<int32_t> xywh = pack_samples(samples);
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
     check(fd_wvm_svm_evaluate_samples(context(), direct->getPyramid()->native(), wvm->getWvm()->native(wvm->getLogisticA(), wvm->getLogisticB()),
                                       svm->getSvm()->native(svm->getLogisticA(), svm->getLogisticB()), n, xywh.data(), target.data(), weight.data()));
-    for (int i = 0; i < n; ++i) {
-        samples[i]->setTarget(target[i] != 0);
-        samples[i]->setWeight(weight[i]);
-    }
+    unpack_samples(target, weight, samples);
 }
 
 // SingleClassifierModel.cpp:22-63
@@ -2745,8 +2713,7 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     auto* psvm = dynamic_cast<classification::ProbabilisticSvmClassifier*>(classifier.get());
     shared_ptr<imageprocessing::HaarFeatureFilter> haar;
     fd_surf_params surf = {0, 0};
-    bool fused = direct && direct->native() && psvm && !psvm->getSvm()->getSupportVectors().empty() &&
-                 psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+    bool fused = direct && direct->native() && detection::hasF32SupportVectors(psvm);
     if (fused) {
         haar = direct->getHaarChain();
         int g = 0, c = 0;
@@ -2762,8 +2729,7 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     if (pyramidDirect) {
         if (!psvm)
             if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
-        fused = psvm && !psvm->getSvm()->getSupportVectors().empty() && psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F &&
-                pyramidDirect->getSampledChain(sampledKind, histParams, ehogParams);
+        fused = detection::hasF32SupportVectors(psvm) && pyramidDirect->getSampledChain(sampledKind, histParams, ehogParams);
         if (!fused) pyramidDirect = nullptr;
     }
     if (!fused) {   // MeasurementModel.hpp: the per-sample loop
@@ -2774,11 +2740,7 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     ++fusedEvaluations;
     const int n = (int)samples.size();
     if (n == 0) return;
-    vector<int32_t> xywh((size_t)4 * n);
-    for (int i = 0; i < n; ++i) {
-        xywh[4 * i] = samples[i]->getX(); xywh[4 * i + 1] = samples[i]->getY();
-        xywh[4 * i + 2] = samples[i]->getWidth(); xywh[4 * i + 3] = samples[i]->getHeight();
-    }
+    const vector<int32_t> xywh = pack_samples(samples);
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
     const fd_svm* svm = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
@@ -2792,10 +2754,7 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
         check(fd_integral_svm_evaluate_samples(context(), direct->native(), haar ? FD_INTEGRAL_HAAR : FD_INTEGRAL_SURF, haar ? (const void*)&hp : (const void*)&surf, svm, n,
                                                xywh.data(), target.data(), weight.data()));
     }
-    for (int i = 0; i < n; ++i) {
-        samples[i]->setTarget(target[i] != 0);
-        samples[i]->setWeight(weight[i]);
-    }
+    unpack_samples(target, weight, samples);
 }
 
 // ---- PositionDependentMeasurementModel (PositionDependentMeasurementModel.cpp:28-274) --------------------------------------------------
@@ -2872,8 +2831,7 @@ vector<double> PositionDependentMeasurementModel::probabilities(const vector<Mat
     vector<double> p(vectors.size());
     auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get());
     const classification::ProbabilisticSvmClassifier* psvm = trainable ? trainable->getProbabilisticSvm().get() : nullptr;
-    const bool batch = psvm && !vectors.empty() && !psvm->getSvm()->getSupportVectors().empty() && vectors[0].depth() == CV_32F &&
-                       psvm->getSvm()->getSupportVectors()[0].depth() == CV_32F;
+    const bool batch = !vectors.empty() && vectors[0].depth() == CV_32F && detection::hasF32SupportVectors(psvm);
     if (batch) {   // one scoring call for the set
         const size_t d = (size_t)vectors[0].rows * vectors[0].cols * vectors[0].channels();
         vector<float> rows(vectors.size() * d);
@@ -3172,11 +3130,7 @@ void ExtendedHogBasedMeasurementModel::evaluate(Sample& sample) const {
 // every sample of a frame in one device call; bestScore as :138-142 keeps it
 void ExtendedHogBasedMeasurementModel::evaluateAll(vector<shared_ptr<Sample>>& samples, double* bestScore) {
     const int n = (int)samples.size();
-    vector<int32_t> xywh((size_t)4 * n);
-    for (int i = 0; i < n; ++i) {
-        xywh[4 * i] = samples[i]->getX(); xywh[4 * i + 1] = samples[i]->getY();
-        xywh[4 * i + 2] = samples[i]->getWidth(); xywh[4 * i + 3] = samples[i]->getHeight();
-    }
+    const vector<int32_t> xywh = pack_samples(samples);
     vector<uint8_t> valid((size_t)n);
     vector<double> score((size_t)n);
     if (useSlidingWindow) {
@@ -3462,18 +3416,13 @@ double ExtendedHogBasedMeasurementModel::computeOverlap(cv::Rect a, cv::Rect b) 
 
 vector<Mat> ExtendedHogBasedMeasurementModel::createGoodNegativeExamples(cv::Rect targetBounds, vector<cv::Rect>* chosen) const {   // :621-669
     if (!tracker) throw std::runtime_error("ExtendedHogBasedMeasurementModel: model is not yet usable (was not initialized)");
-    int count = 0;
-    vector<fd_box> maxima(4096);
-    int rc = fd_ehog_tracker_heat_maxima(context(), tracker, negativeScoreThreshold, maxima.data(), (int)maxima.size(), &count);
-    if (rc == FD_ERR_CAPACITY) {
-        maxima.resize(count);
-        rc = fd_ehog_tracker_heat_maxima(context(), tracker, negativeScoreThreshold, maxima.data(), (int)maxima.size(), &count);
-    }
-    check(rc);
+    const vector<fd_box> maxima = with_capacity<fd_box>(4096, [&](fd_box* boxes, int cap, int* count) {
+        return fd_ehog_tracker_heat_maxima(context(), tracker, negativeScoreThreshold, boxes, cap, count);
+    });
     vector<std::pair<float, cv::Rect>> candidates;
-    for (int i = 0; i < count; ++i) {
-        cv::Rect bounds(maxima[i].x, maxima[i].y, maxima[i].w, maxima[i].h);
-        if (computeOverlap(targetBounds, bounds) < positiveOverlapThreshold) candidates.emplace_back(maxima[i].score, bounds);
+    for (const fd_box& m : maxima) {
+        cv::Rect bounds(m.x, m.y, m.w, m.h);
+        if (computeOverlap(targetBounds, bounds) < positiveOverlapThreshold) candidates.emplace_back(m.score, bounds);
     }
     // reduce overlapping candidates using non-maximum suppression
     std::sort(candidates.begin(), candidates.end(), [](const std::pair<float, cv::Rect>& a, const std::pair<float, cv::Rect>& b) { return a.first < b.first; });

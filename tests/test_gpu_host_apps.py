@@ -566,7 +566,8 @@ def test_condensation_eval_app_matches_oracle(tmp_path, oracle, synth, frame640,
 
 def test_host_selftest_app(tmp_path, oracle, capi, ctx, synth, frame640):
     """Pyramid-on-pyramid views, layer sub-ranges + ROI on a fused chain, FilteringPyramidFeatureExtractor and the stand-alone
-    applyTo of every filter, through the reference-shaped C++ classes (host_selftest_app) against the oracle."""
+    applyTo of every filter, through the reference-shaped C++ classes (host_selftest_app) against the oracle; the capacity retry and
+    the logistic pair of a lazily built device model."""
     app = os.path.join(PKG, "host_selftest_app")
     if not os.path.exists(app):
         pytest.fail("host apps not built (make -C featuredetection_amd/host)")
@@ -641,6 +642,17 @@ def test_host_selftest_app(tmp_path, oracle, capi, ctx, synth, frame640):
     assert np.array_equal(f32("zmuv.bin"), zmuv(g20))
     raw = np.fromfile(str(tmp_path / "ffe_raw.bin"), np.uint8)
     assert len(raw) == 400 and np.array_equal(f32("ffe_patch.bin"), zmuv(raw))
+    # 5. fdhost::with_capacity: a scan that starts with room for one detection is retried once and returns what a fitting call returns
+    rl = [l for l in lines if l.startswith("retry ")][0].split()
+    assert int(rl[2]) > 1 and rl[2] == rl[4] and rl[6] == "1", rl
+    # the fused scan's probabilities come from the classifier's own logistic pair (0.3, -1.7), although a per-Mat getProbability
+    # built the device model first (SvmClassifier::native's default pair is 0.00556, -2.95); the tolerance is the one of
+    # test_ffp_detect_app_single_detector_feature_spaces
+    sig = np.array([[float(v) for v in l.split()[1:]] for l in lines if l.startswith("sigmoid ")], np.float64)
+    assert len(sig) == int(rl[4])
+    exp = 1.0 / (1.0 + np.exp(0.3 + -1.7 * sig[:, 0]))
+    print("stale-sigmoid check: %d detections, max |p - sigmoid(score)| = %.3e" % (len(sig), np.abs(sig[:, 1] - exp).max()))
+    assert np.abs(sig[:, 1] - exp).max() <= 1e-6
 
 
 def test_svm_text_format_fixture(tmp_path, capi, ctx):
