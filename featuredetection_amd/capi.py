@@ -234,6 +234,13 @@ HAAR_2RECTANGLE, HAAR_3RECTANGLE, HAAR_4RECTANGLE, HAAR_CENTER_SURROUND, HAAR_AL
 INTEGRAL_HAAR, INTEGRAL_SURF = 0, 1
 
 FEATURE_GRAY, FEATURE_HQ64, FEATURE_HISTEQ = 0, 1, 2
+FD_FEATURE_GRAY, FD_FEATURE_HQ64, FD_FEATURE_HISTEQ, FD_FEATURE_WHI = 0, 1, 2, 3   # WHI: the sampled gray-patch calls only
+
+
+class fd_patch_samples_params(C.Structure):
+    _fields_ = [("patch_w", C.c_int32), ("patch_h", C.c_int32), ("feature_space", C.c_int32), ("conv_scale", C.c_float),
+                ("conv_shift", C.c_float), ("whi_alpha", C.c_float), ("whi_cutoff", C.c_float)]
+
 HIST_HOG, HIST_SPATIAL, HIST_PYRAMID_HOG, HIST_SPATIAL_PYRAMID = 0, 1, 2, 3
 
 _SIGS = {
@@ -489,6 +496,13 @@ _SIGS = {
                                                C.c_void_p]),
     "fd_hist_svm_evaluate_samples_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p]),
+    "fd_patch_feature_length": (C.c_int, [C.POINTER(fd_patch_samples_params)]),
+    "fd_patch_extract_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_patch_samples_params), C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "fd_patch_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_patch_samples_params), C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_patch_rvm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_patch_samples_params), C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # include/fd_hip_bench.h: measurement hooks (not part of the drop-in boundary)
@@ -2437,6 +2451,45 @@ def hist_svm_evaluate_samples(ctx, pyr, params, svm, samples, want_distance=Fals
         return target.astype(bool), weight, dist
     ctx.check(lib().fd_hist_svm_evaluate_samples(ctx.h, pyr.h, kind, C.byref(params), svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight)))
     return target.astype(bool), weight
+
+
+def patch_samples_params(pw=20, ph=20, feature_space=FD_FEATURE_GRAY, conv_scale=1.0, conv_shift=0.0, whi_alpha=1.0, whi_cutoff=0.390625):
+    return fd_patch_samples_params(pw, ph, feature_space, conv_scale, conv_shift, whi_alpha, whi_cutoff)
+
+
+def patch_extract_samples(ctx, pyr, pp, samples):
+    """the gray-patch feature space pp on the sampled windows of a gray pyramid: (features (n, pw * ph) f32, valid bool[n]); rows without a
+    window are zero"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    F = lib().fd_patch_feature_length(C.byref(pp))
+    feats = np.zeros((len(s), max(F, 0)), np.float32)   # F < 0: the call refuses the parameters, with its message, before it writes
+    valid = np.zeros(len(s), np.uint8)
+    ctx.check(lib().fd_patch_extract_samples(ctx.h, pyr.h, C.byref(pp), len(s), _ptr(s), _ptr(valid), _ptr(feats)))
+    return feats, valid.astype(bool)
+
+
+def patch_svm_evaluate_samples(ctx, pyr, pp, svm, samples, want_distance=False):
+    """condensation::SingleClassifierModel::evaluate on sampled gray patches with an f32 SVM: (target bool[n], weight f64[n]) and, with
+    want_distance, the hyperplane distances f64[n]"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    target = np.zeros(len(s), np.uint8)
+    weight = np.zeros(len(s), np.float64)
+    dist = np.zeros(len(s), np.float64) if want_distance else None
+    ctx.check(lib().fd_patch_svm_evaluate_samples(ctx.h, pyr.h, C.byref(pp), svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight), _ptr(dist)))
+    return (target.astype(bool), weight, dist) if want_distance else (target.astype(bool), weight)
+
+
+def patch_rvm_evaluate_samples(ctx, pyr, pp, rvm, samples):
+    """the RVM cascade on sampled gray patches: (valid bool[n], level i32[n], distance f64[n], target bool[n]); a sample without a window
+    has valid False, level -1, distance 0, target False"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    valid = np.zeros(len(s), np.uint8)
+    level = np.full(len(s), -1, np.int32)
+    dist = np.zeros(len(s), np.float64)
+    target = np.zeros(len(s), np.uint8)
+    ctx.check(lib().fd_patch_rvm_evaluate_samples(ctx.h, pyr.h, C.byref(pp), rvm.h, len(s), _ptr(s), _ptr(valid), _ptr(level), _ptr(dist),
+                                                  _ptr(target)))
+    return valid.astype(bool), level, dist, target.astype(bool)
 
 
 def hist_patch_batch(ctx, bin_patches, hp):

@@ -1,6 +1,7 @@
 // featuredetection_amd/csrc/fd_internal.hpp -- internal declarations of libfd_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -321,6 +322,11 @@ static inline bool fd_knob_wvd_pack() { const char* e = getenv("FD_WVD_PACK"); r
 // Read where the launch is queued.
 static inline bool fd_knob_pyr_xcd() { const char* e = getenv("FD_PYR_XCD"); return !(e && atoi(e) == 0); }
 
+// fd_patch_rvm_evaluate_samples: 1 the fused kernel (k_rvm_samples) at every sample count, 0 the composed route (window patches, then the
+// cascade's passes) at every count, -1 (unset): the size rule of patch_samples.hpp.  WHI takes the composed route whatever this says.
+// Read per call: the tests compare both routes in one process.
+static inline int fd_knob_patch_fused() { const char* e = getenv("FD_PATCH_FUSED"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }
+
 // FD_TRACE's stopwatch: lap_ns() is the time since the start (or the previous lap) and starts the next lap; off: no clock is read.
 struct FdStopwatch {
     bool on = fd_knob_trace();
@@ -479,6 +485,43 @@ static inline bool fd_sample_window(int n_layers, int first_index, double inc, i
     return true;
 }
 
+// sample s = {x, y, width, height} -> window by that rule on the kept layers of p; false: no window
+static inline bool pyramid_sample_window(const fd_pyramid* p, int pw, int ph, const int32_t* s, FdSampleWindow& w) {
+    if (p->kept.empty()) return false;
+    return fd_sample_window((int)p->kept.size(), p->all[p->kept[0]].index, p->inc, pw, ph, s[0], s[1], s[2], s[3],
+                            [&](int pos, double& scale, int& lw, int& lh) {
+                                const HostLayer& L = p->all[p->kept[pos]];
+                                scale = L.scale; lw = L.w; lh = L.h;
+                            }, w);
+}
+
+// Resolves n samples, uploads the windows {layer, bx, by} of those that have one into dlist (pinned staging + one async copy on
+// ctx->stream) and fills sampleOf (list position -> sample); valid (may be NULL): one byte per sample.  `extraPinnedPerValid` bytes per
+// listed window behind the list in the same pinned block are the caller's, at the returned address.  NULL: no sample has a window,
+// nothing was queued.
+static inline void* fd_samples_upload(fd_ctx* ctx, const fd_pyramid* p, int pw, int ph, int n, const int32_t* xywh, uint8_t* valid, DevBuf& dlist,
+                                      std::vector<int>& sampleOf, size_t extraPinnedPerValid) {
+    std::vector<int32_t> list;
+    list.reserve(3 * (size_t)n);
+    sampleOf.clear();
+    for (int i = 0; i < n; ++i) {
+        FdSampleWindow w;
+        const bool ok = pyramid_sample_window(p, pw, ph, xywh + 4 * (size_t)i, w);
+        if (valid) valid[i] = ok ? 1 : 0;
+        if (!ok) continue;
+        list.push_back(w.layer); list.push_back(w.bx); list.push_back(w.by);
+        sampleOf.push_back(i);
+    }
+    if (sampleOf.empty()) return nullptr;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t listBytes = (sizeof(int32_t) * list.size() + 15) & ~(size_t)15;
+    char* pin = (char*)fd_pinned(ctx, listBytes + extraPinnedPerValid * sampleOf.size());
+    std::copy(list.begin(), list.end(), (int32_t*)pin);
+    dlist.reserve(listBytes);
+    HIP_CHECK(hipMemcpyAsync(dlist.p, pin, sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
+    return pin + listBytes;
+}
+
 void fd_pyramid_update_on(fd_pyramid* p, const uint8_t* image, int w, int h, int ch, int is_device, hipStream_t st);
 constexpr int FD_MAX_FRAMES = 64;
 void fd_enumerate_layers(const fd_pyramid* p, int pw, int ph, int sx, int sy, const int* roi,
@@ -516,6 +559,14 @@ void fd_svm_u8_mfma_launch_counted(hipStream_t st, const fd_svm* m, const void* 
 // classifier positives of N scored windows -> detection records in extraction order (hog.hip)
 void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_svm* svm, const std::vector<WindowLayer>& wls, int sx, int sy,
                                     const double* ddist, int64_t N, fd_detection* out, int64_t cap, int64_t* count, double* all_distance);
+
+// ---------------- the whi chain and ConversionFilter on device-resident data (whi.hip), for patch_samples.hpp ----------------
+// the whole whi chain on `total` listed windows {layer, bx, by} (device memory) of the gray planes of p: total x (patch_w * patch_h) floats
+// into dfeat.  Queued on ctx->stream.  Throws FdError (a patch side outside 2..32) before anything is queued
+void fd_whi_list_launch(fd_ctx* ctx, const fd_pyramid* p, const int32_t* dlist, int64_t total, int patch_w, int patch_h, float alpha, float cutoff,
+                        float* dfeat);
+// ConversionFilter(CV_32F, scale, shift) on count u8 values: dst[i] = float(src[i]) * scale + shift.  Queued on ctx->stream
+void fd_convert_u8_f32_launch(fd_ctx* ctx, const uint8_t* dsrc, int64_t count, float scale, float shift, float* ddst);
 
 // ---------------- SVM training (svm_train.hip) ----------------
 // Where the support-vector form (fd_kernel_svm_*) leaves one problem's model (host).  The first n_sv entries of sv_index /

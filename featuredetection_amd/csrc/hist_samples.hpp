@@ -8,16 +8,6 @@
 
 namespace {
 
-// sample i -> window by the one rule (fd_sample_window) on the kept layers of p; false: no window
-bool pyramid_sample_window(const fd_pyramid* p, int pw, int ph, const int32_t* s, FdSampleWindow& w) {
-    if (p->kept.empty()) return false;
-    return fd_sample_window((int)p->kept.size(), p->all[p->kept[0]].index, p->inc, pw, ph, s[0], s[1], s[2], s[3],
-                            [&](int pos, double& scale, int& lw, int& lh) {
-                                const HostLayer& L = p->all[p->kept[pos]];
-                                scale = L.scale; lw = L.w; lh = L.h;
-                            }, w);
-}
-
 // what a sampled call needs to know before it launches anything: every argument rule of the three entry points
 struct SamplesPlan {
     fd_hist_params hp;     // the cell-histogram stage (for ExtendedHogFilter: its SpatialHistogramFilter stand-in)
@@ -54,32 +44,14 @@ SamplesPlan samples_plan(fd_ctx* ctx, const fd_pyramid* p, int kind, const void*
 // in the same pinned block are the caller's, at the returned address) and fills sampleOf; valid (may be NULL): one byte per sample
 void* samples_upload(fd_ctx* ctx, const fd_pyramid* p, const SamplesPlan& pl, int n, const int32_t* xywh, uint8_t* valid, HogScratch& S,
                      std::vector<int>& sampleOf, size_t extraPinnedPerValid) {
-    std::vector<int32_t> list;
-    list.reserve(3 * (size_t)n);
-    sampleOf.clear();
-    for (int i = 0; i < n; ++i) {
-        FdSampleWindow w;
-        const bool ok = pyramid_sample_window(p, pl.hp.patch_w, pl.hp.patch_h, xywh + 4 * (size_t)i, w);
-        if (valid) valid[i] = ok ? 1 : 0;
-        if (!ok) continue;
-        list.push_back(w.layer); list.push_back(w.bx); list.push_back(w.by);
-        sampleOf.push_back(i);
-    }
-    if (sampleOf.empty()) return nullptr;
-    HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t listBytes = (sizeof(int32_t) * list.size() + 15) & ~(size_t)15;
-    char* pin = (char*)fd_pinned(ctx, listBytes + extraPinnedPerValid * sampleOf.size());
-    std::memcpy(pin, list.data(), sizeof(int32_t) * list.size());
-    S.list.reserve(listBytes);
-    HIP_CHECK(hipMemcpyAsync(S.list.p, pin, sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
-    return pin + listBytes;
+    return fd_samples_upload(ctx, p, pl.hp.patch_w, pl.hp.patch_h, n, xywh, valid, S.list, sampleOf, extraPinnedPerValid);
 }
 
 // the features of the nv listed windows, [nv][pl.F] floats on the device: queued on ctx->stream
 const float* samples_features(fd_ctx* ctx, const fd_pyramid* p, const SamplesPlan& pl, int64_t nv, HogScratch& S) {
     fd_pyramid_wait(p, ctx->stream);
     FdWinTable wt;
-    fd_win_table_list(p, S.list.as<int32_t>(), nv, wt);
+    fd_win_table_list(p, S.list.as<int32_t>(), nv, /*filtered=*/true, wt);
     launch_hist_features(ctx, p->arena.as<uint8_t>(), wt, pl.hd, S);
     if (!pl.ehog) return S.feat.as<float>();
     const int64_t total = nv * pl.F;   // S.feat: the raw cell histograms, as in fd_ehog_patch_batch

@@ -194,11 +194,71 @@ __global__ __launch_bounds__(256) void k_rvm_pass(RvmDev m, const void* __restri
     }
 }
 
+// The level blocks [k0, numUse) of the cascade on ONE vector by one wavefront, 64 levels per block: lane == level, the vector x (LDS,
+// f32) is wave-uniform, the reduced set vectors are read transposed.  The kernel values of a block are independent; the running distance is
+// then formed in level order (RvmClassifier.cpp:94-112) and the first lane that misses its threshold is the exit.  d: the distance after
+// level k0 - 1.  Returns the exit level and the lane that holds it (the same on every lane); on that lane, the distance there and
+// classify()'s verdict (:68-73).
+struct RvmExit {
+    int level, lane;
+    double d;        // valid on lane `lane`
+    bool positive;   // valid on lane `lane`
+};
+__device__ __forceinline__ RvmExit rvm_level_blocks(const RvmDev& m, const float* x, int k0, double d, int lane) {
+    const int dim = m.dim, F = m.numFilters;
+    RvmExit ex{-1, 0, 0.0, false};
+    for (int kb = k0; kb < m.numUse && ex.level < 0; kb += 64) {
+        const int k = kb + lane;
+        const bool valid = k < m.numUse;
+        const float* st = m.svT + (valid ? k : kb);
+        double K;
+        if (m.kernel == FD_KERNEL_RBF) {
+            float sum = 0.f;
+            for (int i = 0; i < dim; ++i) {
+                const float diff = x[i] - st[(size_t)i * F];
+                sum = sum + diff * diff;
+            }
+            K = exp(-m.p0 * (double)sum);
+        } else if (m.kernel == FD_KERNEL_HIK) {
+            float sum = 0.f;
+            for (int i = 0; i < dim; ++i) {
+                const float xi = x[i], si = st[(size_t)i * F];
+                sum = sum + (si < xi ? si : xi);   // std::min(x, s), as in rvm_kernel_value
+            }
+            K = (double)sum;
+        } else {
+            double dot = 0.0;
+            for (int i = 0; i < dim; ++i) dot = dot + (double)x[i] * (double)st[(size_t)i * F];
+            K = m.kernel == FD_KERNEL_LINEAR ? dot : powi_d(m.p0 * dot + m.p1, m.degree);
+        }
+        const double term = valid ? (double)m.diag[k] * K : 0.0;
+        // running distance in level order; lane j keeps d_{kb+j}
+        double mine = 0.0;
+        const int cnt = min(64, m.numUse - kb);
+        for (int j = 0; j < cnt; ++j) {
+            const double t = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(term), j),
+                                              __builtin_amdgcn_readlane(__double2loint(term), j));
+            d = (kb + j == 0) ? (-(double)m.bias) + t : d + t;
+            mine = (lane == j) ? d : mine;
+        }
+        const float thr = valid ? m.thr[k] : 0.f;
+        const bool leaves = valid && !(mine >= (double)thr && k + 1 < m.numUse);
+        const unsigned long long lm = __ballot(leaves);
+        if (lm) {
+            ex.lane = __builtin_ctzll(lm);
+            ex.level = kb + ex.lane;
+            ex.d = mine;
+            ex.positive = ex.level + 1 == m.numUse && mine >= (double)thr;
+        }
+        // (d now holds the distance after the last level of the block: the entry value of the next one)
+    }
+    return ex;
+}
+
 // Deep part of the cascade: the few windows that survive the first levels run dozens more, and a lane == window
 // mapping would leave them on a handful of wavefronts, each bound by its 400-step fp32 chains.  The kernel values of
-// different levels are independent, so here a wavefront takes ONE window and evaluates 64 levels at once (lane ==
-// level; the patch is wave-uniform, the reduced set vectors are read transposed), then forms the running distance
-// in level order and stops at the first missed threshold.
+// different levels are independent, so here a wavefront takes ONE window and evaluates 64 levels at once
+// (rvm_level_blocks), and stops at the first missed threshold.
 template <bool U8IN>
 __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restrict__ feats, int64_t rowBytes, float scale, float shift,
                                                   const FdPosRec* __restrict__ inq, const unsigned int* __restrict__ in_count, int k0,
@@ -208,66 +268,22 @@ __global__ __launch_bounds__(256) void k_rvm_deep(RvmDev m, const void* __restri
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int64_t n = (int64_t)*in_count;
-    const int dim = m.dim, F = m.numFilters;
+    const int dim = m.dim;
     float* x = xs[wave];
     for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < n; item += (int64_t)gridDim.x * 4) {
         const int64_t wid = (int64_t)fd_pos_wid(inq[item]);
-        double d = inq[item].d;
         const char* row = (const char*)feats + (size_t)wid * rowBytes;
         for (int i = lane; i < dim; i += 64)
             x[i] = U8IN ? (float)((const unsigned char*)row)[i] * scale + shift : ((const float*)row)[i];
         wave_sync();
-        int level = -1;
-        for (int kb = k0; kb < m.numUse && level < 0; kb += 64) {
-            const int k = kb + lane;
-            const bool valid = k < m.numUse;
-            const float* st = m.svT + (valid ? k : kb);
-            double K;
-            if (m.kernel == FD_KERNEL_RBF) {
-                float sum = 0.f;
-                for (int i = 0; i < dim; ++i) {
-                    const float diff = x[i] - st[(size_t)i * F];
-                    sum = sum + diff * diff;
-                }
-                K = exp(-m.p0 * (double)sum);
-            } else if (m.kernel == FD_KERNEL_HIK) {
-                float sum = 0.f;
-                for (int i = 0; i < dim; ++i) {
-                    const float xi = x[i], si = st[(size_t)i * F];
-                    sum = sum + (si < xi ? si : xi);   // std::min(x, s), as in rvm_kernel_value
-                }
-                K = (double)sum;
-            } else {
-                double dot = 0.0;
-                for (int i = 0; i < dim; ++i) dot = dot + (double)x[i] * (double)st[(size_t)i * F];
-                K = m.kernel == FD_KERNEL_LINEAR ? dot : powi_d(m.p0 * dot + m.p1, m.degree);
+        const RvmExit ex = rvm_level_blocks(m, x, k0, inq[item].d, lane);
+        if (ex.level >= 0 && lane == ex.lane) {
+            if (all_level) all_level[wid] = ex.level;
+            if (all_dist) all_dist[wid] = ex.d;
+            if (ex.positive) {
+                const unsigned int slot = atomicAdd(pos_count, 1u);
+                if (slot < pos_cap) pos[slot] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), ex.d};
             }
-            const double term = valid ? (double)m.diag[k] * K : 0.0;
-            // running distance in level order (RvmClassifier.cpp:94-112); lane j keeps d_{kb+j}
-            double mine = 0.0;
-            const int cnt = min(64, m.numUse - kb);
-            for (int j = 0; j < cnt; ++j) {
-                const double t = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(term), j),
-                                                  __builtin_amdgcn_readlane(__double2loint(term), j));
-                d = (kb + j == 0) ? (-(double)m.bias) + t : d + t;
-                mine = (lane == j) ? d : mine;
-            }
-            const float thr = valid ? m.thr[k] : 0.f;
-            const bool leaves = valid && !(mine >= (double)thr && k + 1 < m.numUse);
-            const unsigned long long lm = __ballot(leaves);
-            if (lm) {
-                const int e = __builtin_ctzll(lm);
-                level = kb + e;
-                if (lane == e) {
-                    if (all_level) all_level[wid] = level;
-                    if (all_dist) all_dist[wid] = mine;
-                    if (level + 1 == m.numUse && mine >= (double)thr) {
-                        const unsigned int slot = atomicAdd(pos_count, 1u);
-                        if (slot < pos_cap) pos[slot] = FdPosRec{(uint32_t)wid, (uint32_t)(wid >> 32), mine};
-                    }
-                }
-            }
-            // (d now holds the distance after the last level of the block: the entry value of the next one)
         }
         wave_sync();
     }
@@ -464,3 +480,4 @@ int fd_detect_rvm(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* rvm_, const fd_rvm_d
 }  // extern "C"
 
 #include "rvm_five_stage.hpp"
+#include "patch_samples.hpp"

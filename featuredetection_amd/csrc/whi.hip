@@ -277,6 +277,20 @@ void patch_call(fd_ctx* ctx, WhiScratch& S, const void* src, size_t inBytes, voi
 
 }  // namespace
 
+void fd_whi_list_launch(fd_ctx* ctx, const fd_pyramid* p, const int32_t* dlist, int64_t total, int patch_w, int patch_h, float alpha, float cutoff,
+                        float* dfeat) {
+    const WhiDev& d = tables(ctx, scratch(ctx), patch_w, patch_h, alpha, cutoff);
+    FdWinTable wt;
+    fd_win_table_list(p, dlist, total, /*filtered=*/false, wt);
+    launch<0>(ctx, p->arena.as<uint8_t>(), wt, d, dfeat, nullptr);
+}
+
+void fd_convert_u8_f32_launch(fd_ctx* ctx, const uint8_t* dsrc, int64_t count, float scale, float shift, float* ddst) {
+    hipLaunchKernelGGL(k_convert, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, ctx->stream, dsrc, 0, ddst, 1, count,
+                       (double)scale, (double)shift);
+    HIP_CHECK(hipGetLastError());
+}
+
 extern "C" {
 
 int fd_whi_batch(fd_ctx* ctx, const uint8_t* patches, int64_t n, int w, int h, float alpha, float cutoff, float* dst) {

@@ -62,15 +62,16 @@ static inline FdWinTable fd_win_table_column(int64_t n, int patch_w, int patch_h
     return wt;
 }
 
-// `total` explicit windows {layer, bx, by} (device memory, layer = position in the kept-layer list) on the filtered planes of p
-static inline void fd_win_table_list(const fd_pyramid* p, const int32_t* dlist, int64_t total, FdWinTable& wt) {
+// `total` explicit windows {layer, bx, by} (device memory, layer = position in the kept-layer list) on the filtered planes of p or on
+// its gray planes
+static inline void fd_win_table_list(const fd_pyramid* p, const int32_t* dlist, int64_t total, bool filtered, FdWinTable& wt) {
     fd_pyramid_require_image(p);
     if (p->kept.size() > (size_t)FD_WIN_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "too many pyramid layers (%zu)", p->kept.size());
     std::memset(&wt, 0, sizeof(wt));
     wt.n = (int32_t)p->kept.size(); wt.sx = wt.sy = 1; wt.total = total; wt.list = dlist;
     for (size_t i = 0; i < p->kept.size(); ++i) {
         const HostLayer& L = p->all[p->kept[i]];
-        wt.l[i].nx = 1; wt.l[i].ny = 1; wt.l[i].lw = L.w; wt.l[i].off = L.filt_off;
+        wt.l[i].nx = 1; wt.l[i].ny = 1; wt.l[i].lw = L.w; wt.l[i].off = filtered ? L.filt_off : L.gray_off;
     }
 }
 

@@ -18,9 +18,12 @@
 //                        adaptation position adaptationThreshold 0.75 exclusionThreshold 0.0
 //                        classifier { training { c 1  compensateImbalance 0  negativeCapacity 100 }  logisticA 0.00556  logisticB -2.95  threshold 0 } }
 //                        (training { type libLinear  c 1  bias 0  negativeCapacity 100 }: a liblinear::LibLinearClassifier; type libSvm is the default)
-//     measurement positionDependent { feature hog|ehog|lbp|glbp { ... }  filter none  startFrameCount 1 ...  classifier { training { ... } } }
+//     measurement positionDependent { feature grayscale|h|whi|hog|ehog|lbp|glbp { ... }  filter none  startFrameCount 1 ...  classifier { training { ... } } }
+//                        (filter before|after { classifierFile .. feature .. { ... } }: an RVM in front of / behind the adaptive classifier)
 //                        (in place of `measurement ehog`: a condensation::PositionDependentMeasurementModel, keys in tracking_setup.hpp; the
 //                         AdaptiveCondensationTracker initialises its model once, so startFrameCount must be 1 for it to start; its generator gets seed + 4)
+//     validator rvm { classifierFile <FDRVM1 file> feature grayscale|h|whi { ... } sizes "0.9 1 1.1" displacements "-0.1 0 0.1" }
+//                        (optional: a ClassificationBasedStateValidator on the tracker; keys in tracking_setup.hpp)
 //   }
 // the box is the target's bounding box (top left corner) in frame 0.  Prints "init <0|1> [x y w h]", then per further frame
 //   "frame <f> found <0|1> <x> <y> <w> <h> adapted <0|1> route <generic|device> ms <wall time of process()>"
@@ -215,6 +218,7 @@ int main(int argc, char** argv) {
         }
         AdaptiveCondensationTracker tracker(sampler, adaptiveModel, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()),
                                             pt.get("initialCount", 800));
+        if (auto validator = tracking_setup::createValidator(pt)) tracker.addValidator(validator);
         const cv::Rect box(std::atoi(argv[a + 1]), std::atoi(argv[a + 2]), std::atoi(argv[a + 3]), std::atoi(argv[a + 4]));
         boost::optional<cv::Rect> start = tracker.initialize(read_pnm(argv[a + 5]), box);
         if (!start) {

@@ -1,25 +1,39 @@
-// tracking_setup.hpp -- what tracker_app and position_dependent_eval_app share: the pyramid feature types of the reference's
-// createFeatureExtractor (HeadTracking.cpp:117-135,199-330: hog, ehog, lbp, glbp on a `pyramid direct` block), the trainable classifier of
-// a `classifier` block, and condensation::PositionDependentMeasurementModel from a `measurement positionDependent` block
-// (HeadTracking.cpp:503-533).
+// tracking_setup.hpp -- what tracker_app, position_dependent_eval_app and filtering_eval_app share: the pyramid feature types of the
+// reference's createFeatureExtractor (HeadTracking.cpp:117-167,199-330: grayscale, h, whi, hog, ehog, lbp, glbp on a `pyramid direct`
+// block), the trainable classifier of a `classifier` block, condensation::PositionDependentMeasurementModel from a `measurement
+// positionDependent` block with its optional RVM filter (HeadTracking.cpp:503-533), and the RVM validator (HeadTracking.cpp:568-577).
 //   measurement positionDependent {
+//     feature grayscale|h|whi { pyramid direct { patch { width 16 height 16 minWidth 16 maxWidth 64 } interval 3 }   scale 1 }
+//                        (grayscale: ConversionFilter(CV_32F, 1/255); h: HistogramEqualizationFilter, ConversionFilter(CV_32F, 1/127.5, -1);
+//                         whi: WhiteningFilter, HistogramEqualizationFilter, that ConversionFilter, UnitNormFilter(NORM_L2))
 //     feature hog|ehog|lbp|glbp { pyramid direct { patch { width 16 height 16 minWidth 16 maxWidth 64 } interval 3 }   scale 1
 //        gradientKernel 1 blurKernel 0 bins 9 signed 0 interpolate 0     (hog, ehog; glbp: gradientKernel, blurKernel)
 //        type lbp8|lbp8uniform|lbp4|lbp4rotated                           (lbp, glbp)
 //        histogram spatial { cellSize 4 blockSize 2 interpolate 0 signedAndUnsigned 0 concatenate 0 normalization l2hys }
 //        histogram pyramid { levels 2 interpolate 0 signedAndUnsigned 0 normalization l2norm }
 //        (ehog: histogram { cellSize 4 interpolate 0 signedAndUnsigned 0 alpha 0.2 }) }
+//     filter before|after { classifierFile <FDRVM1 file>  [numFiltersToUse n]  feature grayscale|h|whi { ... } }
+//                        (condensation::FilteringClassifierModel with an RvmClassifier on features of its own: before = RESET_WEIGHT,
+//                         after = KEEP_WEIGHT; in place of `filter none`)
 //     filter none   startFrameCount 3  stopFrameCount 0  targetThreshold 0.7  confidenceThreshold 0.95  positiveOffsetFactor 0.05
 //     negativeOffsetFactor 0.5  sampleNegativesAroundTarget 0  sampleAdditionalNegatives 10  sampleTestNegatives 10  exploitSymmetry 0
 //     classifier { training { type libSvm|libLinear c 1 ... }  logisticA 0.00556  logisticB -2.95  threshold 0 }
 //   }
-// Not built, each an invalid_argument that names it: filter before|after (FilteringClassifierModel), validator rvm, the gray-patch
-// feature types (grayscale, histeq, h, whi) and the integral ones (haar, ihog, iehog, surf) under this key.
+//   validator rvm { classifierFile <FDRVM1 file>  [numFiltersToUse n]  feature grayscale|h|whi { ... }  sizes "0.9 1 1.1"  displacements "-0.1 0 0.1" }
+//                        (beside `measurement`, in the `tracking` block: a condensation::ClassificationBasedStateValidator on the adaptive tracker)
+// Not built, each an invalid_argument that names it: the feature type histeq (u8 vectors: this host layer's RvmClassifier and the
+// trainers take CV_32F), `pyramid derived`, and the integral feature types (haar, ihog, iehog, surf) under this key.  A bare
+// `filter before` / `filter after` without its block is refused with what the block needs.
 #pragma once
 #include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <sstream>
+#include <vector>
+#include "condensation/AdaptiveCondensationTracker.hpp"
+#include "condensation/ClassificationBasedStateValidator.hpp"
+#include "condensation/FilteringClassifierModel.hpp"
 #include "condensation/PositionDependentMeasurementModel.hpp"
 #include "imageprocessing/GradientMagnitudeFilter.hpp"
 #include "liblinear/LibLinearClassifier.hpp"
@@ -36,6 +50,8 @@ inline bool flag(const ptree& config, const std::string& key, bool dflt = false)
 
 // createPyramidExtractor, `direct` (DirectPyramidFeatureExtractor.cpp:27-36,41-43)
 inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(const ptree& config) {
+    if (config.get_value<std::string>() == "derived")
+        throw std::invalid_argument("tracking: `pyramid derived` (a pyramid on the layers of another extractor's pyramid) is not built; use `pyramid direct`");
     if (config.get_value<std::string>() != "direct")
         throw std::invalid_argument("tracking: pyramid type `" + config.get_value<std::string>() + "` is not built (only `pyramid direct`)");
     const int width = config.get<int>("patch.width"), height = config.get<int>("patch.height");
@@ -107,8 +123,16 @@ inline std::shared_ptr<FeatureExtractor> createFeatureExtractor(const ptree& con
         }
         extractor->addLayerFilter(lbpFilter);
         extractor->addPatchFilter(createHistogramFilter(lbpFilter->getBinCount(), config.get_child("histogram")));
-    } else if (type == "grayscale" || type == "histeq" || type == "h" || type == "whi") {
-        throw std::invalid_argument("tracking: the gray-patch feature type `" + type + "` is not built for measurement positionDependent");
+    } else if (type == "grayscale" || type == "h" || type == "whi") {   // HeadTracking.cpp:144-167
+        extractor = createPyramidExtractor(config.get_child("pyramid"));
+        if (type == "whi") extractor->addPatchFilter(std::make_shared<WhiteningFilter>());
+        if (type != "grayscale") extractor->addPatchFilter(std::make_shared<HistogramEqualizationFilter>());
+        extractor->addPatchFilter(type == "grayscale" ? std::make_shared<ConversionFilter>(CV_32F, 1.0 / 255.0)
+                                                      : std::make_shared<ConversionFilter>(CV_32F, 1.0 / 127.5, -1.0));
+        if (type == "whi") extractor->addPatchFilter(std::make_shared<UnitNormFilter>(cv::NORM_L2));
+    } else if (type == "histeq") {
+        throw std::invalid_argument("tracking: the feature type `histeq` is not built (its vectors are u8; the RvmClassifier and the trainers of this "
+                                    "host layer take CV_32F vectors: use `h`)");
     } else if (type == "haar" || type == "ihog" || type == "iehog" || type == "surf") {
         throw std::invalid_argument("tracking: the integral feature type `" + type + "` is not built for measurement positionDependent");
     } else {
@@ -139,23 +163,72 @@ inline std::shared_ptr<TrainableSvmClassifier> createTrainableSvm(const ptree& c
     return svm;
 }
 
+// the RvmClassifier of a `filter` or `validator` block: classifierFile, optional numFiltersToUse
+inline std::shared_ptr<RvmClassifier> createRvm(const ptree& config) {
+    std::shared_ptr<RvmClassifier> rvm = RvmClassifier::load(config);
+    if (int count = config.get("numFiltersToUse", 0)) rvm->setNumFiltersToUse((unsigned int)count);
+    return rvm;
+}
+
+// "0.9 1 1.1" -> {0.9, 1, 1.1}
+inline std::vector<double> readValues(const std::string& text) {
+    std::vector<double> values;
+    std::istringstream in(text);
+    double value;
+    while (in >> value) values.push_back(value);
+    if (values.empty() || !in.eof()) throw std::invalid_argument("tracking: invalid list of values: `" + text + "`");
+    return values;
+}
+
+// `validator rvm { ... }` of the tracking block (HeadTracking.cpp:568-577); null for `validator none` or no such key
+inline std::shared_ptr<condensation::ClassificationBasedStateValidator> createValidator(const ptree& pt) {
+    const std::string type = pt.get("validator", std::string("none"));
+    if (type == "none") return nullptr;
+    if (type != "rvm") throw std::invalid_argument("tracking: invalid validator type: " + type);
+    const ptree& vt = pt.get_child("validator");
+    if (!vt.count("classifierFile") || !vt.count("feature"))
+        throw std::invalid_argument("tracking: `validator rvm` (condensation::ClassificationBasedStateValidator) needs a block: validator rvm { classifierFile "
+                                    "<FDRVM1 file> [numFiltersToUse n] feature grayscale|h|whi { pyramid direct { .. } } sizes \"0.9 1 1.1\" displacements \"-0.1 0 0.1\" }");
+    return std::make_shared<condensation::ClassificationBasedStateValidator>(createFeatureExtractor(vt.get_child("feature")), createRvm(vt),
+                                                                             readValues(vt.get("sizes", std::string("1"))),
+                                                                             readValues(vt.get("displacements", std::string("0"))));
+}
+
 struct PositionDependentSetup {
     std::shared_ptr<FeatureExtractor> featureExtractor;
     std::shared_ptr<TrainableProbabilisticSvmClassifier> classifier;
     std::shared_ptr<condensation::PositionDependentMeasurementModel> model;
+    std::shared_ptr<FeatureExtractor> filterExtractor;                       // with `filter before|after`
+    std::shared_ptr<RvmClassifier> filter;
+    std::shared_ptr<condensation::FilteringClassifierModel> filteringModel;
 };
-inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned int seed) {
+// the filtering behaviour of a `filter` key: false for `none`
+inline bool filterBehavior(const ptree& mt, condensation::FilteringClassifierModel::Behavior& behavior) {
     const std::string filter = mt.get("filter", std::string("none"));
-    if (filter == "before" || filter == "after")
-        throw std::invalid_argument("tracking: `filter " + filter + "` (condensation::FilteringClassifierModel) is not built; use `filter none`");
-    if (filter != "none") throw std::invalid_argument("tracking: invalid filter type: " + filter);
-    if (mt.count("validator"))
-        throw std::invalid_argument("tracking: `validator " + mt.get("validator", std::string()) + "` (ClassificationBasedStateValidator) is not built");
+    if (filter == "none") return false;
+    if (filter != "before" && filter != "after") throw std::invalid_argument("tracking: invalid filter type: " + filter);
+    const ptree& ft = mt.get_child("filter");
+    if (!ft.count("classifierFile") || !ft.count("feature"))
+        throw std::invalid_argument("tracking: `filter " + filter + "` (condensation::FilteringClassifierModel) needs a block: filter " + filter +
+                                    " { classifierFile <FDRVM1 file> [numFiltersToUse n] feature grayscale|h|whi { pyramid direct { .. } } }");
+    behavior = filter == "before" ? condensation::FilteringClassifierModel::Behavior::RESET_WEIGHT : condensation::FilteringClassifierModel::Behavior::KEEP_WEIGHT;
+    return true;
+}
+inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned int seed) {
     PositionDependentSetup s;
+    condensation::FilteringClassifierModel::Behavior behavior;
+    const bool filtering = filterBehavior(mt, behavior);
     s.featureExtractor = createFeatureExtractor(mt.get_child("feature"));
     const ptree& ct = mt.get_child("classifier");
     s.classifier = std::make_shared<FixedTrainableProbabilisticSvmClassifier>(createTrainableSvm(ct), ct.get("logisticA", 0.00556), ct.get("logisticB", -2.95));
-    s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.featureExtractor, s.classifier, seed);
+    if (filtering) {   // HeadTracking.cpp:507-518
+        s.filterExtractor = createFeatureExtractor(mt.get_child("filter.feature"));
+        s.filter = createRvm(mt.get_child("filter"));
+        s.filteringModel = std::make_shared<condensation::FilteringClassifierModel>(s.filterExtractor, s.filter, s.featureExtractor, s.classifier, behavior);
+        s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.filteringModel, s.featureExtractor, s.classifier, seed);
+    } else {
+        s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.featureExtractor, s.classifier, seed);
+    }
     s.model->setFrameCounts(mt.get("startFrameCount", 3u), mt.get("stopFrameCount", 0u));
     s.model->setThresholds(mt.get("targetThreshold", 0.7f), mt.get("confidenceThreshold", 0.95f));
     s.model->setOffsetFactors(mt.get("positiveOffsetFactor", 0.05f), mt.get("negativeOffsetFactor", 0.5f));

@@ -220,10 +220,11 @@ public:
     static std::shared_ptr<RvmClassifier> loadFromFile(const std::string& classifierFilename);
     const fd_rvm* native(double logisticA = 0.0, double logisticB = -1.0) const;
     const Model& getModel() const { return model; }
+    // the device model the distances come from: the current one whatever its logistic parameters, built when there is none
+    const fd_rvm* distanceModel() const { const fd_rvm* m = device.current(); return m ? m : native(); }
 private:
     Model model;
     unsigned int numFiltersToUse = 0;
-    const fd_rvm* distanceModel() const { const fd_rvm* m = device.current(); return m ? m : native(); }
     mutable DeviceModel<fd_rvm, fd_rvm_destroy> device;
 };
 

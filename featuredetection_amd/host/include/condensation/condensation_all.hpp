@@ -117,7 +117,9 @@ private:
 // the classifier a ProbabilisticSvmClassifier on f32 vectors, and with one fd_hist_svm_evaluate_samples when the extractor is a
 // DirectPyramidFeatureExtractor (itself, not wrapped in a PatchResizingFeatureExtractor) whose patch filter is one histogram filter or
 // one ExtendedHogFilter on bin-image layers (the hog, lbp, glbp and ehog feature types) and the classifier a ProbabilisticSvmClassifier
-// or a TrainableProbabilisticSvmClassifier on f32 vectors; any other combination runs the per-sample loop.  (The reference's
+// or a TrainableProbabilisticSvmClassifier on f32 vectors, and with one fd_patch_svm_evaluate_samples / fd_patch_rvm_evaluate_samples when
+// that extractor has a sampled gray-patch chain (getSampledPatchChain: the grayscale, h and whi feature types) and the classifier is such
+// an SVM classifier / a ProbabilisticRvmClassifier; any other combination runs the per-sample loop.  (The reference's
 // result cache per patch is not kept: the results are the same.)  getFusedEvaluationCount / getLoopEvaluationCount (not in the
 // reference) tell which of the two ran: the results do not.
 class SingleClassifierModel : public MeasurementModel {
@@ -133,6 +135,62 @@ private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticClassifier> classifier;
     int fusedEvaluations = 0, loopEvaluations = 0;
+};
+
+// FilteringClassifierModel.hpp / FilteringClassifierModel.cpp:27-103: a binary classifier on features of its own in front of (RESET_WEIGHT)
+// or behind (KEEP_WEIGHT) a measurement model.  RESET_WEIGHT: a sample that does not pass the filter (no patch included) gets target
+// false and weight 0 and never reaches the model.  KEEP_WEIGHT: the model evaluates every sample; a sample it marked as target loses the
+// flag when it does not pass the filter, and keeps its weight.  The batched evaluate asks the filter once for all samples it concerns
+// (fd_patch_rvm_evaluate_samples) when the filter is an RvmClassifier or a ProbabilisticRvmClassifier and the filter's extractor a
+// DirectPyramidFeatureExtractor (itself, not wrapped) with a sampled gray-patch chain, and hands the model the passing samples in one
+// batched evaluate (RESET_WEIGHT; KEEP_WEIGHT: all samples first); anything else asks per sample.  Targets and weights do not depend on
+// the route.  (The reference's result cache per patch is not kept: the results are the same.)  getFusedFilterCount /
+// getLoopFilterCount (not in the reference) count the batched evaluate calls by the route their filter took.
+class FilteringClassifierModel : public MeasurementModel {
+public:
+    enum class Behavior { RESET_WEIGHT, KEEP_WEIGHT };
+    FilteringClassifierModel(std::shared_ptr<imageprocessing::FeatureExtractor> filterFeatureExtractor, std::shared_ptr<classification::BinaryClassifier> filter,
+                             std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor, std::shared_ptr<classification::ProbabilisticClassifier> classifier,
+                             Behavior behavior);
+    FilteringClassifierModel(std::shared_ptr<imageprocessing::FeatureExtractor> filterFeatureExtractor, std::shared_ptr<classification::BinaryClassifier> filter,
+                             std::shared_ptr<MeasurementModel> measurementModel, Behavior behavior);
+    void update(std::shared_ptr<imageprocessing::VersionedImage> image) override;
+    void evaluate(Sample& sample) const override;
+    void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override;
+    int getFusedFilterCount() const { return fusedFilters; }
+    int getLoopFilterCount() const { return loopFilters; }
+    std::shared_ptr<MeasurementModel> getMeasurementModel() const { return measurementModel; }
+private:
+    bool passesFilter(const Sample& sample) const;
+    // the filter's verdict for every sample of the list: one device call when the route allows it (true), else per sample (false)
+    bool passFilter(const std::vector<std::shared_ptr<Sample>>& samples, std::vector<char>& passes) const;
+    Behavior behavior;
+    std::shared_ptr<MeasurementModel> measurementModel;
+    std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
+    std::shared_ptr<classification::BinaryClassifier> filter;
+    int fusedFilters = 0, loopFilters = 0;
+};
+
+// ClassificationBasedStateValidator.hpp / .cpp:28-45: the state is valid when the classifier accepts one window of a small grid around
+// it -- for every size factor size = round(factor * target size), for every x displacement x = target x + round(displacement * size),
+// for every y displacement likewise (std::round: half-way cases away from zero), in that order.  With an RvmClassifier (or a
+// ProbabilisticRvmClassifier) on a DirectPyramidFeatureExtractor with a sampled gray-patch chain the whole grid is one
+// fd_patch_rvm_evaluate_samples and the verdict is any(target); otherwise the windows are asked one by one up to the first accepted.
+// getLastCandidates (not in the reference) returns the grid of the last call as Rect(x, y, size, size): centre and size, not bounds.
+class ClassificationBasedStateValidator : public StateValidator {
+public:
+    ClassificationBasedStateValidator(std::shared_ptr<imageprocessing::FeatureExtractor> extractor, std::shared_ptr<classification::BinaryClassifier> classifier,
+                                      std::vector<double> sizes = {1}, std::vector<double> displacements = {0});
+    bool isValid(const Sample& target, const std::vector<std::shared_ptr<Sample>>& samples, std::shared_ptr<imageprocessing::VersionedImage> image) override;
+    const std::vector<cv::Rect>& getLastCandidates() const { return lastCandidates; }
+    int getFusedValidationCount() const { return fusedValidations; }
+    int getLoopValidationCount() const { return loopValidations; }
+private:
+    std::shared_ptr<imageprocessing::FeatureExtractor> extractor;
+    std::shared_ptr<classification::BinaryClassifier> classifier;
+    std::vector<double> sizes, displacements;
+    std::vector<cv::Rect> lastCandidates;
+    int fusedValidations = 0, loopValidations = 0;
 };
 
 // PositionDependentMeasurementModel.hpp / .cpp:28-274: a measurement model that learns its classifier from the target position --

@@ -452,11 +452,16 @@ public:
     std::shared_ptr<Patch> extract(int layer, int x, int y) const override;
     // not in the reference: extract(x, y, width, height) for every sample {x - width / 2, y - height / 2, width, height} at once,
     // null for a sample without a window.  One device call (fd_hist_extract_samples / fd_ehog_extract_samples) when the patch filter
-    // is one histogram filter or one ExtendedHogFilter (the hog, lbp, glbp and ehog feature types); the per-sample path otherwise.
+    // is one histogram filter or one ExtendedHogFilter (the hog, lbp, glbp and ehog feature types), one fd_patch_extract_samples for a
+    // sampled gray-patch chain (below: the grayscale, h and whi feature types); the per-sample path otherwise.
     // The patch geometry is the one extractFromLayer computes.
     std::vector<std::shared_ptr<Patch>> extract(const std::vector<cv::Rect>& samples) const;
     // the parameters of that device call: kind FD_SAMPLES_HIST (hp) or FD_SAMPLES_EHOG (ep); false: no such chain
     bool getSampledChain(int& kind, fd_hist_params& hp, fd_ehog_patch_params& ep) const;
+    // the gray-patch chains of the sampled calls (fd_patch_*_samples): on a gray pyramid without layer filters or source pyramid the patch
+    // filters are exactly [ConversionFilter(CV_32F)], [HistEq64Filter, ConversionFilter(CV_32F)], [HistogramEqualizationFilter,
+    // ConversionFilter(CV_32F)] or the complete whi chain; false: any other chain
+    bool getSampledPatchChain(fd_patch_samples_params& pp) const;
     int getLayerIndex(int width, int height) const override;
     double getMinScaleFactor() const override { return pyramid->getMinScaleFactor(); }
     double getMaxScaleFactor() const override { return pyramid->getMaxScaleFactor(); }

@@ -885,12 +885,30 @@ bool DirectPyramidFeatureExtractor::getSampledChain(int& kind, fd_hist_params& h
     hp = hist_params_of(*hist, patchWidth, patchHeight, 1, 1);
     return true;
 }
+bool DirectPyramidFeatureExtractor::getSampledPatchChain(fd_patch_samples_params& pp) const {
+    if (pyramid->getSourcePyramid() || pyramid->getLayerFilterKind() != FD_LAYER_NONE || hist || ehog || reshaping) return false;
+    const auto& filters = chain->getFilters();
+    pp = fd_patch_samples_params{patchWidth, patchHeight, FD_FEATURE_GRAY, 1.f, 0.f, 1.f, 0.390625f};
+    if (whiStage == 4 && filters.size() == 4 && !histeq && !conversion) {
+        pp.feature_space = FD_FEATURE_WHI;
+        pp.whi_alpha = whitening->alpha; pp.whi_cutoff = whitening->cutoffFrequency;
+        return fd_patch_feature_length(&pp) > 0;
+    }
+    if (whiStage != 0 || !conversion || filters.empty() || filters.back() != conversion) return false;
+    if (filters.size() == 2 && histeq && !equalization && filters[0] == histeq) pp.feature_space = FD_FEATURE_HQ64;
+    else if (filters.size() == 2 && equalization && !histeq && filters[0] == equalization) pp.feature_space = FD_FEATURE_HISTEQ;
+    else if (filters.size() != 1 || histeq || equalization) return false;
+    pp.conv_scale = (float)conversion->alpha; pp.conv_shift = (float)conversion->beta;   // cv::Mat::convertTo works in float
+    return fd_patch_feature_length(&pp) > 0;
+}
 vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv::Rect>& samples) const {
     vector<shared_ptr<Patch>> patches(samples.size());
     int kind = 0;
     fd_hist_params hp;
     fd_ehog_patch_params ep;
-    if (!getSampledChain(kind, hp, ep)) {   // the per-sample path
+    fd_patch_samples_params pp;
+    const bool grayPatches = getSampledPatchChain(pp);
+    if (!grayPatches && !getSampledChain(kind, hp, ep)) {   // the per-sample path
         for (size_t i = 0; i < samples.size(); ++i)
             patches[i] = extract(samples[i].x + samples[i].width / 2, samples[i].y + samples[i].height / 2, samples[i].width, samples[i].height);
         return patches;
@@ -905,14 +923,15 @@ vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv
     }
     int index, lw, lh, ch = 1; double scale;
     if (fd_pyramid_layer_count(pyramid->native()) > 0) fd_pyramid_layer_info(pyramid->native(), 0, &index, &scale, &lw, &lh, &ch);
-    const int F = kind == FD_SAMPLES_EHOG ? fd_ehog_feature_length(&ep, ch) : fd_hist_feature_length(&hp, ch);
+    const int F = grayPatches ? fd_patch_feature_length(&pp) : (kind == FD_SAMPLES_EHOG ? fd_ehog_feature_length(&ep, ch) : fd_hist_feature_length(&hp, ch));
     if (F < 0) throw std::invalid_argument("DirectPyramidFeatureExtractor: invalid histogram filter parameters for this patch size");
     Mat all(n, F, CV_32FC1);
     vector<uint8_t> valid((size_t)n);
-    if (kind == FD_SAMPLES_EHOG) check(fd_ehog_extract_samples(context(), pyramid->native(), &ep, n, xywh.data(), valid.data(), all.ptr<float>(0)));
+    if (grayPatches) check(fd_patch_extract_samples(context(), pyramid->native(), &pp, n, xywh.data(), valid.data(), all.ptr<float>(0)));
+    else if (kind == FD_SAMPLES_EHOG) check(fd_ehog_extract_samples(context(), pyramid->native(), &ep, n, xywh.data(), valid.data(), all.ptr<float>(0)));
     else check(fd_hist_extract_samples(context(), pyramid->native(), &hp, n, xywh.data(), valid.data(), all.ptr<float>(0)));
     check(fd_pyramid_sample_windows(pyramid->native(), patchWidth, patchHeight, n, xywh.data(), windows.data()));
-    const int ehogRows = kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(patchHeight) / static_cast<double>(ehog->cellHeight)) : 1;
+    const int ehogRows = grayPatches ? patchHeight : kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(patchHeight) / static_cast<double>(ehog->cellHeight)) : 1;
     for (int i = 0; i < n; ++i) {
         if (!valid[i]) continue;
         fd_pyramid_layer_info(pyramid->native(), windows[4 * i], &index, &scale, &lw, &lh, &ch);
@@ -920,7 +939,7 @@ vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv
         const int ow = cv::cvRound(patchWidth / scale), oh = cv::cvRound(patchHeight / scale);
         const int ox = cv::cvRound(windows[4 * i + 1] / scale) + ow / 2, oy = cv::cvRound(windows[4 * i + 2] / scale) + oh / 2;
         Mat row = Mat(all, cv::Rect(0, i, F, 1)).clone();
-        if (kind == FD_SAMPLES_EHOG) {   // rows x cols * channels, as ExtendedHogFilter::applyTo stores it
+        if (grayPatches || kind == FD_SAMPLES_EHOG) {   // rows x cols * channels, as ExtendedHogFilter::applyTo stores it; a gray patch keeps its shape
             Mat shaped(ehogRows, F / ehogRows, CV_32FC1);
             std::memcpy(shaped.data, row.data, sizeof(float) * (size_t)F);
             row = shaped;
@@ -2726,10 +2745,19 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     int sampledKind = 0;
     fd_hist_params histParams;
     fd_ehog_patch_params ehogParams;
+    fd_patch_samples_params patchParams;
+    bool grayPatches = false;
+    classification::ProbabilisticRvmClassifier* prvm = nullptr;
     if (pyramidDirect) {
         if (!psvm)
             if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
         fused = detection::hasF32SupportVectors(psvm) && pyramidDirect->getSampledChain(sampledKind, histParams, ehogParams);
+        // ... or on a sampled gray-patch chain (the grayscale, h and whi feature types) with such an SVM classifier or a
+        // ProbabilisticRvmClassifier: one fd_patch_svm_evaluate_samples / fd_patch_rvm_evaluate_samples
+        if (!fused && pyramidDirect->getSampledPatchChain(patchParams)) {
+            prvm = dynamic_cast<classification::ProbabilisticRvmClassifier*>(classifier.get());
+            fused = grayPatches = prvm || detection::hasF32SupportVectors(psvm);
+        }
         if (!fused) pyramidDirect = nullptr;
     }
     if (!fused) {   // MeasurementModel.hpp: the per-sample loop
@@ -2743,8 +2771,25 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     const vector<int32_t> xywh = pack_samples(samples);
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
+    if (grayPatches && prvm) {   // level and distance from the device, verdict and probability by the classifier's own getProbability
+        vector<uint8_t> valid((size_t)n);
+        vector<int32_t> level((size_t)n);
+        vector<double> distance((size_t)n);
+        check(fd_patch_rvm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), &patchParams, prvm->getRvm()->distanceModel(), n, xywh.data(),
+                                            valid.data(), level.data(), distance.data(), nullptr));
+        for (int i = 0; i < n; ++i) {
+            const std::pair<bool, double> result = valid[i] ? prvm->getProbability(std::make_pair((int)level[i], distance[i])) : std::make_pair(false, 0.0);
+            target[i] = result.first ? 1 : 0;
+            weight[i] = result.second;
+        }
+        unpack_samples(target, weight, samples);
+        return;
+    }
     const fd_svm* svm = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-    if (pyramidDirect) {
+    if (grayPatches) {
+        check(fd_patch_svm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), &patchParams, svm, n, xywh.data(), target.data(), weight.data(),
+                                            nullptr));
+    } else if (pyramidDirect) {
         check(fd_hist_svm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), sampledKind,
                                            sampledKind == FD_SAMPLES_EHOG ? (const void*)&ehogParams : (const void*)&histParams, svm, n, xywh.data(),
                                            target.data(), weight.data()));
@@ -2755,6 +2800,128 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
                                                xywh.data(), target.data(), weight.data()));
     }
     unpack_samples(target, weight, samples);
+}
+
+// ---- FilteringClassifierModel (FilteringClassifierModel.cpp:27-103) --------------------------------------------------------------------
+// the RVM behind a binary classifier that is an RvmClassifier or a ProbabilisticRvmClassifier; null: another classifier
+static const classification::RvmClassifier* rvm_of(const classification::BinaryClassifier* c) {
+    if (auto* rvm = dynamic_cast<const classification::RvmClassifier*>(c)) return rvm;
+    if (auto* prvm = dynamic_cast<const classification::ProbabilisticRvmClassifier*>(c)) return prvm->getRvm().get();
+    return nullptr;
+}
+// classifier->classify on the patch of every sample {x, y, width, height} in one fd_patch_rvm_evaluate_samples: possible with an RVM on
+// a DirectPyramidFeatureExtractor (itself) with a sampled gray-patch chain; the verdict is the RvmClassifier's own classify(level,
+// distance), false for a sample without a patch.  false: not this combination, nothing was done
+static bool rvm_classify_samples(const imageprocessing::FeatureExtractor* extractor, const classification::BinaryClassifier* classifier,
+                                 const vector<int32_t>& xywh, vector<char>& verdict) {
+    const classification::RvmClassifier* rvm = rvm_of(classifier);
+    auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor);
+    fd_patch_samples_params pp;
+    if (!rvm || !direct || !direct->getSampledPatchChain(pp)) return false;
+    const int n = (int)(xywh.size() / 4);
+    verdict.assign((size_t)n, 0);
+    if (n == 0) return true;
+    vector<uint8_t> valid((size_t)n);
+    vector<int32_t> level((size_t)n);
+    vector<double> distance((size_t)n);
+    check(fd_patch_rvm_evaluate_samples(context(), direct->getPyramid()->native(), &pp, rvm->distanceModel(), n, xywh.data(), valid.data(), level.data(),
+                                        distance.data(), nullptr));
+    for (int i = 0; i < n; ++i) verdict[i] = valid[i] && rvm->classify(std::make_pair((int)level[i], distance[i])) ? 1 : 0;
+    return true;
+}
+
+FilteringClassifierModel::FilteringClassifierModel(shared_ptr<imageprocessing::FeatureExtractor> filterFeatureExtractor, shared_ptr<classification::BinaryClassifier> filter,
+                                                   shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                                   shared_ptr<classification::ProbabilisticClassifier> classifier, Behavior behavior)
+    : FilteringClassifierModel(filterFeatureExtractor, filter, make_shared<SingleClassifierModel>(featureExtractor, classifier), behavior) {}
+FilteringClassifierModel::FilteringClassifierModel(shared_ptr<imageprocessing::FeatureExtractor> filterFeatureExtractor, shared_ptr<classification::BinaryClassifier> filter,
+                                                   shared_ptr<MeasurementModel> measurementModel, Behavior behavior)
+    : behavior(behavior), measurementModel(measurementModel), featureExtractor(filterFeatureExtractor), filter(filter) {}
+void FilteringClassifierModel::update(shared_ptr<imageprocessing::VersionedImage> image) {
+    featureExtractor->update(image);
+    measurementModel->update(image);
+}
+bool FilteringClassifierModel::passesFilter(const Sample& sample) const {
+    auto patch = featureExtractor->extract(sample.getX(), sample.getY(), sample.getWidth(), sample.getHeight());
+    return patch && filter->classify(patch->getData());
+}
+bool FilteringClassifierModel::passFilter(const vector<shared_ptr<Sample>>& samples, vector<char>& passes) const {
+    if (rvm_classify_samples(featureExtractor.get(), filter.get(), pack_samples(samples), passes)) return true;
+    passes.assign(samples.size(), 0);
+    for (size_t i = 0; i < samples.size(); ++i) passes[i] = passesFilter(*samples[i]) ? 1 : 0;
+    return false;
+}
+void FilteringClassifierModel::evaluate(Sample& sample) const {
+    if (behavior == Behavior::RESET_WEIGHT) {
+        if (passesFilter(sample)) {
+            measurementModel->evaluate(sample);
+        } else {
+            sample.setTarget(false);
+            sample.setWeight(0);
+        }
+    } else {
+        measurementModel->evaluate(sample);
+        if (sample.isTarget() && !passesFilter(sample)) sample.setTarget(false);
+    }
+}
+void FilteringClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
+    vector<char> passes;
+    vector<shared_ptr<Sample>> asked;
+    if (behavior == Behavior::RESET_WEIGHT) {   // the filter on every sample, the model on those that pass
+        featureExtractor->update(image);
+        (passFilter(samples, passes) ? fusedFilters : loopFilters)++;
+        for (size_t i = 0; i < samples.size(); ++i) {
+            if (passes[i]) {
+                asked.push_back(samples[i]);
+            } else {
+                samples[i]->setTarget(false);
+                samples[i]->setWeight(0);
+            }
+        }
+        measurementModel->evaluate(image, asked);   // (updates the model on the image, as update() does)
+    } else {   // the model on every sample, the filter on those it marked as target
+        featureExtractor->update(image);
+        measurementModel->evaluate(image, samples);
+        for (const auto& sample : samples)
+            if (sample->isTarget()) asked.push_back(sample);
+        (passFilter(asked, passes) ? fusedFilters : loopFilters)++;
+        for (size_t i = 0; i < asked.size(); ++i)
+            if (!passes[i]) asked[i]->setTarget(false);
+    }
+}
+
+// ---- ClassificationBasedStateValidator (ClassificationBasedStateValidator.cpp:28-45) ---------------------------------------------------
+ClassificationBasedStateValidator::ClassificationBasedStateValidator(shared_ptr<imageprocessing::FeatureExtractor> extractor,
+                                                                     shared_ptr<classification::BinaryClassifier> classifier, vector<double> sizes,
+                                                                     vector<double> displacements)
+    : extractor(extractor), classifier(classifier), sizes(sizes), displacements(displacements) {}
+bool ClassificationBasedStateValidator::isValid(const Sample& target, const vector<shared_ptr<Sample>>&, shared_ptr<imageprocessing::VersionedImage> image) {
+    extractor->update(image);
+    lastCandidates.clear();
+    vector<int32_t> xywh;
+    for (double factor : sizes) {
+        const int size = static_cast<int>(std::round(factor * target.getSize()));
+        for (double dx : displacements) {
+            const int x = target.getX() + static_cast<int>(std::round(dx * size));
+            for (double dy : displacements) {
+                const int y = target.getY() + static_cast<int>(std::round(dy * size));
+                const Sample candidate(x, y, size);
+                lastCandidates.push_back(cv::Rect(x, y, size, size));
+                xywh.insert(xywh.end(), {candidate.getX(), candidate.getY(), candidate.getWidth(), candidate.getHeight()});
+            }
+        }
+    }
+    vector<char> accepted;
+    if (rvm_classify_samples(extractor.get(), classifier.get(), xywh, accepted)) {
+        ++fusedValidations;
+        return std::find(accepted.begin(), accepted.end(), (char)1) != accepted.end();
+    }
+    ++loopValidations;
+    for (size_t i = 0; i < lastCandidates.size(); ++i) {
+        auto patch = extractor->extract(xywh[4 * i], xywh[4 * i + 1], xywh[4 * i + 2], xywh[4 * i + 3]);
+        if (patch && classifier->classify(patch->getData())) return true;
+    }
+    return false;
 }
 
 // ---- PositionDependentMeasurementModel (PositionDependentMeasurementModel.cpp:28-274) --------------------------------------------------
@@ -2798,7 +2965,8 @@ bool PositionDependentMeasurementModel::hasWindow(int x, int y, int width, int h
     int kind;
     fd_hist_params hp;
     fd_ehog_patch_params ep;
-    if (direct && direct->getSampledChain(kind, hp, ep)) {   // the extractor's rule, on the host
+    fd_patch_samples_params pp;
+    if (direct && (direct->getSampledChain(kind, hp, ep) || direct->getSampledPatchChain(pp))) {   // the extractor's rule, on the host
         const int32_t s[4] = {x, y, width, height};
         int32_t w[4];
         check(fd_pyramid_sample_windows(direct->getPyramid()->native(), direct->getPatchWidth(), direct->getPatchHeight(), 1, s, w));

@@ -1115,6 +1115,40 @@ int fd_detect_five_stage_rvm_image(fd_ctx* ctx, fd_pyramid* p, const fd_rvm* fir
                                    const fd_rvm* second_rvm, const uint8_t* image, int width, int height, int channels, int image_is_device,
                                    float oe_dist, float oe_ratio, const int* roi, fd_detection* out, int cap, int* count, int32_t* stage_counts);
 
+/* ---- gray-patch features and the RVM cascade on explicit sample windows of a gray pyramid (no layer filter): what the tracking apps
+ * put on a DirectPyramidFeatureExtractor with the patch filters of HeadTracking.cpp:144-167 -- condensation::SingleClassifierModel,
+ * FilteringClassifierModel (FilteringClassifierModel.cpp:27-103) and ClassificationBasedStateValidator (:28-45) ---------------------
+ * Feature spaces: FD_FEATURE_GRAY / HQ64 / HISTEQ followed by ConversionFilter(CV_32F, conv_scale, conv_shift), x = float(u8) *
+ * scale + shift; FD_FEATURE_WHI: the whole whi chain of fd_whi_params with (whi_alpha, whi_cutoff), which ignores conv_scale and
+ * conv_shift (fd_detect_rvm does not take it).  A feature vector has patch_w * patch_h floats, row-major.
+ * The sample -> window rule is fd_sample_windows'.  Samples without a window: a zero feature row; target 0, weight 0, distance 0 from
+ * the SVM call; valid 0, level -1, distance 0, target 0 from the RVM call.
+ * FD_ERR_INVALID_ARGUMENT, before anything is queued: objects of different contexts, a multi-frame pyramid, a pyramid without an image,
+ * a layer-filtered pyramid, n < 0 or n > FD_HIST_SAMPLES_MAX, a patch side outside 1..32 (whi: 2..32), an unknown feature space, an RVM
+ * whose filter size is not the patch size, an SVM on u8 vectors or of another dimension.  n == 0 or no sample with a window: FD_OK
+ * without a launch. */
+enum { FD_FEATURE_WHI = 3 };
+typedef struct {
+    int32_t patch_w, patch_h, feature_space;
+    float conv_scale, conv_shift, whi_alpha, whi_cutoff;
+} fd_patch_samples_params;
+/* host only: patch_w * patch_h, or -1 where the calls below refuse the parameters */
+int fd_patch_feature_length(const fd_patch_samples_params* pp);
+/* features: n x fd_patch_feature_length floats, valid: n bytes (either may be NULL).  Bit for bit what the per-patch entry points
+ * (fd_histeq64 of the patch, fd_equalize_hist_batch, fd_convert_batch, fd_whi_batch) give on the patches cut from the layers. */
+int fd_patch_extract_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_params* pp, int n, const int32_t* xywh, uint8_t* valid,
+                             float* features);
+/* SingleClassifierModel::evaluate with a ProbabilisticSvmClassifier on f32 vectors, as fd_hist_svm_evaluate_samples_distance:
+ * target = distance >= threshold, weight = the logistic probability; distance may be NULL */
+int fd_patch_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_params* pp, const fd_svm* svm, int n,
+                                  const int32_t* xywh, uint8_t* target, double* weight, double* distance);
+/* RvmClassifier::computeHyperplaneDistance and classify (RvmClassifier.cpp:68-85) per sample: level and distance as fd_rvm_eval_batch
+ * on the extracted row (the same bits), target = the last used level is reached and passed.  valid, level, distance and target may
+ * each be NULL.  Inside a measured range of sample counts one kernel gathers, filters and scores a window without writing its feature
+ * row; outside it (and for FD_FEATURE_WHI) the rows are written and the cascade of fd_rvm_eval_batch runs on them. */
+int fd_patch_rvm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_params* pp, const fd_rvm* rvm, int n,
+                                  const int32_t* xywh, uint8_t* valid, int32_t* level, double* distance, uint8_t* target);
+
 /* ---- supervised descent: superviseddescent::SdmLandmarkModel / SdmLandmarkModelFitting ---------- */
 typedef struct {
     int32_t num_landmarks;      /* L */
