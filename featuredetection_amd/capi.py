@@ -228,10 +228,15 @@ class fd_surf_params(C.Structure):
     _fields_ = [("gradient_count", C.c_int32), ("cell_count", C.c_int32)]
 
 
+class fd_integral_hog_params(C.Structure):
+    _fields_ = [("grad_rows", C.c_int32), ("grad_cols", C.c_int32), ("bins", C.c_int32), ("signed_gradients", C.c_int32),
+                ("interpolate_bins", C.c_int32), ("kind", C.c_int32), ("hist", fd_hist_params), ("ehog", fd_ehog_patch_params)]
+
+
 HAAR_FEATURE_DTYPE = np.dtype([("rects", np.float32, (4, 4)), ("weights", np.float32, (4,)), ("num_rects", np.int32), ("factor", np.float32),
                                ("area", np.float32)])
 HAAR_2RECTANGLE, HAAR_3RECTANGLE, HAAR_4RECTANGLE, HAAR_CENTER_SURROUND, HAAR_ALL = 1, 2, 4, 8, 15
-INTEGRAL_HAAR, INTEGRAL_SURF = 0, 1
+INTEGRAL_HAAR, INTEGRAL_SURF, INTEGRAL_HOG = 0, 1, 2
 
 FEATURE_GRAY, FEATURE_HQ64, FEATURE_HISTEQ = 0, 1, 2
 FD_FEATURE_GRAY, FD_FEATURE_HQ64, FD_FEATURE_HISTEQ, FD_FEATURE_WHI = 0, 1, 2, 3   # WHI: the sampled gray-patch calls only
@@ -481,6 +486,9 @@ _SIGS = {
     "fd_integral_extract_surf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_integral_svm_evaluate_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                    C.c_void_p]),
+    "fd_integral_hog_feature_length": (C.c_int, [C.POINTER(fd_integral_hog_params)]),
+    "fd_integral_gradient_samples_valid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fd_integral_extract_hog": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fd_integral_hog_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fd_integral_image_length": (C.c_int, [C.c_int, C.c_int]),
     "fd_integral_gradient_length": (C.c_int, [C.c_int, C.c_int]),
     "fd_gradient_sum_length": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -2579,6 +2587,36 @@ def surf_feature_length(gradient_count, cell_count):
     return n
 
 
+def integral_hog_params(rows, cols=None, bins=9, signed_gradients=False, interpolate_bins=False, hist=None, ehog=None):
+    """fd_integral_hog_params: IntegralGradientFilter(rows, cols) -> GradientBinningFilter(bins, signed_gradients, interpolate_bins) ->
+    hist (a fd_hist_params: one of the four HIST_* patch filters) or ehog (a fd_ehog_patch_params: ExtendedHogFilter)"""
+    if (hist is None) == (ehog is None):
+        raise ValueError("exactly one of hist and ehog")
+    p = fd_integral_hog_params()
+    p.grad_rows, p.grad_cols = int(rows), int(rows if cols is None else cols)
+    p.bins, p.signed_gradients, p.interpolate_bins = int(bins), int(signed_gradients), int(interpolate_bins)
+    if hist is not None:
+        p.kind, p.hist = FD_SAMPLES_HIST, hist
+    else:
+        p.kind, p.ehog = FD_SAMPLES_EHOG, ehog
+    return p
+
+
+def integral_hog_feature_length(hp):
+    """floats per sample of Integral.extract_hog (host only); -1 where the call is refused"""
+    return lib().fd_integral_hog_feature_length(C.byref(hp) if hp is not None else None)
+
+
+def integral_gradient_samples_valid(width, height, rows, cols, samples):
+    """which samples of a width x height image IntegralGradientFilter(rows, cols) can serve (host only) -> bool[n]"""
+    s = _c(samples, np.int32).reshape(-1, 4)
+    valid = np.zeros(len(s), np.uint8)
+    rc = lib().fd_integral_gradient_samples_valid(width, height, rows, cols, len(s), _ptr(s), _ptr(valid))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_integral_gradient_samples_valid: invalid image size %d x %d or grid %d x %d" % (width, height, rows, cols))
+    return valid.astype(bool)
+
+
 def integral_image(ctx, gray):
     g = _c(gray, np.uint8)
     out = np.empty((g.shape[0] + 1, g.shape[1] + 1), np.int32)
@@ -2657,16 +2695,28 @@ class Integral:
         self.ctx.check(lib().fd_integral_extract_surf(self.ctx.h, self.h, gradient_count, cell_count, len(s), _ptr(s), _ptr(feats), _ptr(valid)))
         return (feats, valid.astype(bool)) if download else None
 
-    def svm_evaluate_samples(self, svm, samples, haar=None, surf=None):
-        """condensation::SingleClassifierModel::evaluate: haar = haar_params(...) or surf = (gradient_count, cell_count)
-        -> (target bool[n], weight f64[n])"""
+    def extract_hog(self, hp, samples, download=True):
+        """the integral HOG family (integral_hog_params) in one launch"""
+        s = self._samples(samples)
+        feats = np.empty((len(s), max(integral_hog_feature_length(hp), 0)), np.float32) if download else None
+        valid = np.zeros(len(s), np.uint8) if download else None
+        self.ctx.check(lib().fd_integral_extract_hog(self.ctx.h, self.h, C.byref(hp), len(s), _ptr(s), _ptr(feats), _ptr(valid)))
+        return (feats, valid.astype(bool)) if download else None
+
+    def svm_evaluate_samples(self, svm, samples, haar=None, surf=None, hog=None, kind=None):
+        """condensation::SingleClassifierModel::evaluate: haar = haar_params(...), surf = (gradient_count, cell_count) or
+        hog = integral_hog_params(...) -> (target bool[n], weight f64[n]).  kind ("haar" | "surf" | "hog"), when given, must name
+        the argument that is set."""
         s = self._samples(samples)
         target = np.zeros(len(s), np.uint8)
         weight = np.zeros(len(s), np.float64)
-        if (haar is None) == (surf is None):
-            raise ValueError("exactly one of haar and surf")
+        given = [k for k, v in (("haar", haar), ("surf", surf), ("hog", hog)) if v is not None]
+        if len(given) != 1 or (kind is not None and kind != given[0]):
+            raise ValueError("exactly one of haar, surf and hog (and kind, when given, names it)")
         if haar is not None:
             kind, prm = INTEGRAL_HAAR, C.byref(haar.c)
+        elif hog is not None:
+            kind, prm = INTEGRAL_HOG, C.byref(hog)
         else:
             sp = fd_surf_params(int(surf[0]), int(surf[1]))
             kind, prm = INTEGRAL_SURF, C.byref(sp)

@@ -620,3 +620,14 @@ constexpr int FD_SURF_MAX_GRID = 64;                  // gradient_count of the f
 constexpr size_t FD_SURF_LDS_BUDGET = 160 * 1024;     // LDS of one gfx950 workgroup
 // dynamic LDS of one workgroup of the fused SURF kernel (four wavefronts)
 size_t fd_host_surf_lds_bytes(int gradient_count, int cell_count);
+
+// ---------------- integral HOG: the ihog / iehog chains on sampled windows (integral_hog.hpp, included by hog.hip) ----------------
+// GradientBinningFilter's 65536-entry look-up table (pyramid.hip): 2 bytes per entry, 4 with bin interpolation
+void fd_build_gradient_lut(int bins, bool signedGradients, bool interpolate, std::vector<uint8_t>& lut);
+// every argument rule of fd_integral_hog_params, with a message for each (FdError); returns the floats per sample
+int fd_integral_hog_check(const fd_integral_hog_params* p);
+// k_integral_hog (and k_ehog_patch_desc for FD_SAMPLES_EHOG) over the n uploaded samples, queued on ctx->stream: `feat` receives
+// n x fd_integral_hog_check(p) floats, `valid` n bytes; `raw` is scratch (the cell histograms of the ehog kind).  img: the
+// (H + 1) x (W + 1) integral image, lut: the table of (p->bins, p->signed_gradients, p->interpolate_bins) on the device
+void fd_integral_hog_launch(fd_ctx* ctx, const fd_integral_hog_params* p, const int32_t* img, int W, int H, const uint8_t* lut, const int32_t* xywh,
+                            int n, DevBuf& raw, DevBuf& feat, uint8_t* valid);

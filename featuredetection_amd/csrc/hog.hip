@@ -582,39 +582,19 @@ __device__ __forceinline__ void hist_normalize_wave(float* v, int n, int normali
     }
 }
 
-__global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict__ arena, FdWinTable wt, HistDev hd, HistTables tab,
-                                                      float* __restrict__ feat) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x;
+// The histogram stage of one window by one wavefront: HistogramFilter::createCellHistograms on the [ph][pw][ch] bin-image patch in
+// LDS, then the HOG / spatial / pyramid stage; the F floats of the window are left at the returned address inside `vec`.  The caller
+// has staged the patch (and, for an interpolating filter, the four tables) in LDS; this function clears `vec` ([ldsFloats]) and
+// synchronises the wavefront before it reads anything.  k_hist_features and k_integral_hog are its callers.
+__device__ __forceinline__ const float* hist_patch_features(const HistDev& hd, const unsigned char* patch, const HistCache* rowCache,
+                                                            const HistCache* colCache, const int32_t* rowRange, const int32_t* colRange,
+                                                            float* vec, int lane) {
     const int pw = hd.pw, ph = hd.ph, ch = hd.ch, B = hd.bins;
     const int R = hd.rows, Cc = hd.cols, ncells = R * Cc;
-    unsigned char* patch = smem;                                           // [ph][pw][ch]
-    HistCache* rowCache = (HistCache*)(smem + hd.patchBytes);               // [ph]
-    HistCache* colCache = rowCache + ph;                                    // [pw]
-    int32_t* rowRange = (int32_t*)(colCache + pw);                          // [R]
-    int32_t* colRange = rowRange + R;                                       // [Cc]
-    float* vec = (float*)(((size_t)(colRange + Cc) + 15) & ~(size_t)15);    // [ldsFloats]: output vector (+ raw cells, scratch)
     float* cells = vec + hd.cellsOff;                                       // [ncells][B]
-    if (hd.interpolate) {
-        for (int i = lane; i < ph; i += 64) rowCache[i] = tab.rowCache[i];
-        for (int i = lane; i < pw; i += 64) colCache[i] = tab.colCache[i];
-        for (int i = lane; i < R; i += 64) rowRange[i] = tab.rowRange[i];
-        for (int i = lane; i < Cc; i += 64) colRange[i] = tab.colRange[i];
-    }
     const float factor = 1.f / 255.f;
     const float eps = 1e-4f;
-    const int rowBytes = pw * ch;
-
-    for (int64_t wid = blockIdx.x; wid < wt.total; wid += gridDim.x) {
-        // ---- window -> layer position (DirectPyramidFeatureExtractor.cpp:75-123 order)
-        int x0, y0;
-        const FdWinLayer& wl = win_locate(wt, wid, x0, y0);
-        const uint8_t* src = arena + wl.off + ((size_t)y0 * wl.lw + x0) * ch;
-        const size_t srcStride = (size_t)wl.lw * ch;
-        for (int i = lane; i < ph * rowBytes; i += 64) {
-            const int y = i / rowBytes, xb = i - y * rowBytes;
-            patch[i] = src[(size_t)y * srcStride + xb];
-        }
+    {
         for (int i = lane; i < hd.ldsFloats; i += 64) vec[i] = 0.f;
         wave_sync();
 
@@ -754,6 +734,41 @@ __global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict_
             }
             wave_sync();
         }
+        return out;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_hist_features(const uint8_t* __restrict__ arena, FdWinTable wt, HistDev hd, HistTables tab,
+                                                      float* __restrict__ feat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const int pw = hd.pw, ph = hd.ph, ch = hd.ch;
+    const int R = hd.rows, Cc = hd.cols;
+    unsigned char* patch = smem;                                           // [ph][pw][ch]
+    HistCache* rowCache = (HistCache*)(smem + hd.patchBytes);               // [ph]
+    HistCache* colCache = rowCache + ph;                                    // [pw]
+    int32_t* rowRange = (int32_t*)(colCache + pw);                          // [R]
+    int32_t* colRange = rowRange + R;                                       // [Cc]
+    float* vec = (float*)(((size_t)(colRange + Cc) + 15) & ~(size_t)15);    // [ldsFloats]: output vector (+ raw cells, scratch)
+    if (hd.interpolate) {
+        for (int i = lane; i < ph; i += 64) rowCache[i] = tab.rowCache[i];
+        for (int i = lane; i < pw; i += 64) colCache[i] = tab.colCache[i];
+        for (int i = lane; i < R; i += 64) rowRange[i] = tab.rowRange[i];
+        for (int i = lane; i < Cc; i += 64) colRange[i] = tab.colRange[i];
+    }
+    const int rowBytes = pw * ch;
+
+    for (int64_t wid = blockIdx.x; wid < wt.total; wid += gridDim.x) {
+        // ---- window -> layer position (DirectPyramidFeatureExtractor.cpp:75-123 order)
+        int x0, y0;
+        const FdWinLayer& wl = win_locate(wt, wid, x0, y0);
+        const uint8_t* src = arena + wl.off + ((size_t)y0 * wl.lw + x0) * ch;
+        const size_t srcStride = (size_t)wl.lw * ch;
+        for (int i = lane; i < ph * rowBytes; i += 64) {
+            const int y = i / rowBytes, xb = i - y * rowBytes;
+            patch[i] = src[(size_t)y * srcStride + xb];
+        }
+        const float* out = hist_patch_features(hd, patch, rowCache, colCache, rowRange, colRange, vec, lane);
         for (int i = lane; i < hd.F; i += 64) feat[(size_t)wid * hd.F + i] = out[i];
         wave_sync();
     }
@@ -1040,3 +1055,4 @@ int fd_detect_hist_svm(fd_ctx* ctx, fd_pyramid* p, const fd_svm* svm, const fd_h
 
 #include "ehog_patch.hpp"
 #include "hist_samples.hpp"
+#include "integral_hog.hpp"

@@ -19,6 +19,7 @@
 // image is gathered through L2 (a 1080p integral image is 8.3 MB), every output row is written with consecutive lanes.
 #include "fd_internal.hpp"
 #include "fd_device.hpp"
+#include "integral_geo.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -34,12 +35,17 @@ struct fd_integral {
     std::vector<float> haarKey;
     int haarTypes = -1, haarCount = 0;
     float haarMaxX = 0.f, haarMaxY = 0.f;
+    // GradientBinningFilter's look-up table of the last integral HOG call (rebuilt when (bins, signed, interpolate) changes)
+    DevBuf hogLut;
+    int hogLutBins = -1, hogLutSigned = 0, hogLutInterpolate = 0;
+    DevBuf hogRaw;               // cell histograms of the ehog kind
     // per-call device buffers
     DevBuf xywh, feat, valid, dist;
 };
 
 namespace {
 using namespace fd_dev;
+using namespace fd_integral_geo;
 
 constexpr int BAND = 32;           // rows per band of the column pass
 
@@ -125,21 +131,8 @@ __global__ __launch_bounds__(64) void k_integral_cols(int32_t* __restrict__ img,
     }
 }
 
-// ---- sample windows: DirectImageFeatureExtractor::extract (DirectImageFeatureExtractor.cpp:42-52) on the integral image ----
-struct SampleGeo {
-    int px0, py0, w, h;   // patch origin and size inside the (H + 1) x (W + 1) integral image
-    bool exists;
-};
-__device__ __forceinline__ SampleGeo sample_geo(const int32_t* __restrict__ xywh, int i, int W, int H) {
-    const int4 s = reinterpret_cast<const int4*>(xywh)[i];
-    SampleGeo g;
-    g.w = s.z; g.h = s.w;
-    g.px0 = s.x - s.z / 2;
-    g.py0 = s.y - s.w / 2;
-    g.exists = s.z >= 1 && s.w >= 1 && g.px0 >= 0 && g.py0 >= 0 && (long long)g.px0 + s.z <= (long long)W + 1 && (long long)g.py0 + s.w <= (long long)H + 1;
-    return g;
-}
-
+// ---- sample windows: DirectImageFeatureExtractor::extract (DirectImageFeatureExtractor.cpp:42-52) on the integral image; sample_geo,
+// grad_geo and grad_point are integral_geo.hpp's ----
 // HaarFeatureFilter: one feature of the device table.  xe / ye hold rect.x + rect.width / rect.y + rect.height (float sums, made
 // on the host exactly as applyTo makes them), fa = factor * area.
 struct HaarDev {
@@ -184,46 +177,6 @@ __global__ __launch_bounds__(256) void k_haar(const int32_t* __restrict__ img, i
             out[f] = value / (t.fa * fc * fr);
         }
     }
-}
-
-// IntegralGradientFilter::applyTo (IntegralGradientFilter.cpp:23-85): the per-patch constants
-struct GradGeo {
-    int rX, rY;
-    double spX, spY;
-    bool ok;   // every read lies inside the integral image
-};
-__device__ __forceinline__ GradGeo grad_geo(const SampleGeo& g, int rows, int cols, int W, int H) {
-    GradGeo q;
-    const int width = g.w - 1, height = g.h - 1;
-    q.rX = max(1, __double2int_rn((double)(width - 1) / (double)(cols + 2)));
-    q.rY = max(1, __double2int_rn((double)(height - 1) / (double)(rows + 2)));
-    q.spX = (double)(width - 3 * q.rX) / (double)(cols - 1);
-    q.spY = (double)(height - 3 * q.rY) / (double)(rows - 1);
-    // the grid coordinates cvRound(radius + i * spacing) are monotonic in i: the first (== radius) and the last bound all reads
-    const int cLast = __double2int_rn((double)q.rX + (double)(cols - 1) * q.spX), rLast = __double2int_rn((double)q.rY + (double)(rows - 1) * q.spY);
-    const long long xmin = (long long)g.px0 + min(q.rX, cLast) - q.rX, xmax = (long long)g.px0 + max(q.rX, cLast) + 2 * q.rX;
-    const long long ymin = (long long)g.py0 + min(q.rY, rLast) - q.rY, ymax = (long long)g.py0 + max(q.rY, rLast) + 2 * q.rY;
-    q.ok = g.exists && xmin >= 0 && ymin >= 0 && xmax <= W && ymax <= H;
-    return q;
-}
-// one grid point: (dx + 127, dy + 127) as uchar
-__device__ __forceinline__ uchar2 grad_point(const int32_t* __restrict__ base, size_t S, const GradGeo& q, int row, int col) {
-    const int r = __double2int_rn((double)q.rY + (double)row * q.spY), c = __double2int_rn((double)q.rX + (double)col * q.spX);
-    const int32_t* __restrict__ p = base + (ptrdiff_t)r * (ptrdiff_t)S + c;
-    const ptrdiff_t oy0 = -(ptrdiff_t)q.rY * (ptrdiff_t)S, oy2 = (ptrdiff_t)q.rY * (ptrdiff_t)S, oy3 = 2 * oy2;
-    const int ox0 = -q.rX, ox2 = q.rX, ox3 = 2 * q.rX;
-    //     p1  p2
-    // p3  p4  p5  p6
-    // p7  p8  p9  p10
-    //     p11 p12
-    const int p1 = p[oy0], p2 = p[oy0 + ox2];
-    const int p3 = p[ox0], p4 = p[0], p5 = p[ox2], p6 = p[ox3];
-    const int p7 = p[oy2 + ox0], p8 = p[oy2], p9 = p[oy2 + ox2], p10 = p[oy2 + ox3];
-    const int p11 = p[oy3], p12 = p[oy3 + ox2];
-    const int top = p1 - p2 - p4 + p5, bottom = p8 - p9 - p11 + p12, left = p3 - p4 - p7 + p8, right = p5 - p6 - p9 + p10;
-    const int half = q.rY * q.rX;
-    const int dx = (right - left) / (2 * half), dy = (bottom - top) / (2 * half);   // truncating, like the reference's int division
-    return make_uchar2((unsigned char)(dx + 127), (unsigned char)(dy + 127));
 }
 
 __global__ __launch_bounds__(256) void k_grad_patches(const int32_t* __restrict__ img, int W, int H, int rows, int cols, const int32_t* __restrict__ xywh,
@@ -393,6 +346,27 @@ void run_haar(fd_ctx* ctx, fd_integral* g, int F, int n) {
     hipLaunchKernelGGL(k_haar, dim3(sample_grid(ctx, n)), dim3(256), 0, ctx->stream, g->img.as<int32_t>(), g->w, g->h, g->haarTab.as<HaarDev>(), F,
                        g->haarMaxX, g->haarMaxY, g->xywh.as<int32_t>(), n, g->feat.as<float>(), g->valid.as<uint8_t>());
     HIP_CHECK(hipGetLastError());
+}
+
+// the look-up table of hp's GradientBinningFilter on the device (kept until (bins, signed, interpolate) changes)
+const uint8_t* prepare_hog_lut(fd_ctx* ctx, fd_integral* g, const fd_integral_hog_params* hp) {
+    const int sg = hp->signed_gradients ? 1 : 0, ib = hp->interpolate_bins ? 1 : 0;
+    if (g->hogLutBins == hp->bins && g->hogLutSigned == sg && g->hogLutInterpolate == ib) return g->hogLut.as<uint8_t>();
+    std::vector<uint8_t> lut;
+    fd_build_gradient_lut(hp->bins, sg != 0, ib != 0, lut);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));   // a kernel still reading the previous table
+    g->hogLutBins = -1;
+    g->hogLut.reserve(lut.size());
+    HIP_CHECK(hipMemcpy(g->hogLut.p, lut.data(), lut.size(), hipMemcpyHostToDevice));
+    g->hogLutBins = hp->bins; g->hogLutSigned = sg; g->hogLutInterpolate = ib;
+    return g->hogLut.as<uint8_t>();
+}
+
+// features of the n uploaded samples into g->feat / g->valid
+void run_hog(fd_ctx* ctx, fd_integral* g, const fd_integral_hog_params* hp, int n) {
+    const uint8_t* lut = prepare_hog_lut(ctx, g, hp);
+    fd_integral_hog_launch(ctx, hp, g->img.as<int32_t>(), g->w, g->h, lut, g->xywh.as<int32_t>(), n, g->hogRaw, g->feat, g->valid.as<uint8_t>());
 }
 
 // the rules of fd_surf_feature_length, with a message for each; returns the descriptor length
@@ -571,16 +545,39 @@ int fd_integral_extract_surf(fd_ctx* ctx, fd_integral* g, int gradient_count, in
     });
 }
 
+int fd_integral_gradient_samples_valid(int width, int height, int rows, int cols, int n, const int32_t* xywh, uint8_t* valid) {
+    if (width < 1 || height < 1 || fd_integral_gradient_length(rows, cols) < 0 || n < 0 || (n > 0 && (!xywh || !valid))) return FD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; ++i) {
+        alignas(16) int32_t s[4];   // sample_geo reads an aligned int4
+        std::memcpy(s, xywh + 4 * (size_t)i, sizeof(s));
+        valid[i] = grad_geo(sample_geo(s, 0, width, height), rows, cols, width, height).ok ? 1 : 0;
+    }
+    return FD_OK;
+}
+
+int fd_integral_extract_hog(fd_ctx* ctx, fd_integral* g, const fd_integral_hog_params* hp, int n, const int32_t* xywh, float* features, uint8_t* valid) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !g || !hp || n < 0 || (n > 0 && !xywh)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_extract_hog: bad argument");
+        const int len = fd_integral_hog_check(hp);
+        require_updated(ctx, g, "fd_integral_extract_hog");
+        if (n == 0) return;
+        upload_samples(ctx, g, n, xywh);
+        run_hog(ctx, g, hp, n);
+        download_rows(ctx, g, n, features, sizeof(float) * (size_t)len, valid);
+    });
+}
+
 int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, const void* params, const fd_svm* svm, int n, const int32_t* xywh,
                                      uint8_t* target, double* weight) {
     return fd_guard(ctx, [&] {
         if (!ctx || !g || !params || !svm || n < 0 || (n > 0 && (!xywh || !target || !weight)))
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: bad argument");
-        if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: unknown feature kind %d", kind);
+        if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF && kind != FD_INTEGRAL_HOG) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: unknown feature kind %d", kind);
         require_updated(ctx, g, "fd_integral_svm_evaluate_samples");
         const fd_surf_params* sp = (const fd_surf_params*)params;
         int len;
         if (kind == FD_INTEGRAL_HAAR) len = prepare_haar(ctx, g, (const fd_haar_params*)params);
+        else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_check((const fd_integral_hog_params*)params);
         else len = check_surf(sp->gradient_count, sp->cell_count);
         if (fd_svm_is_u8(svm) || fd_svm_dim(svm) != len)
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: the SVM must work on f32 vectors of length %d (it has %d %s values)", len,
@@ -588,6 +585,7 @@ int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, cons
         if (n == 0) return;
         upload_samples(ctx, g, n, xywh);
         if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
+        else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
         else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
         g->dist.reserve(sizeof(double) * (size_t)n);
         fd_svm_generic_launch(ctx, svm, g->feat.p, nullptr, (int64_t)len * 4, n, g->dist.as<double>());

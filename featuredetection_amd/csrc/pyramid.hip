@@ -1142,6 +1142,10 @@ struct FilterLaunch {   // k_gradbin / k_lbp / k_gradmag_lbp, behind k_box_blur 
 
 }  // namespace
 
+void fd_build_gradient_lut(int bins, bool signedGradients, bool interpolate, std::vector<uint8_t>& lut) {
+    build_gradient_lut(bins, signedGradients, interpolate, lut);
+}
+
 struct fd_pyramid::Plan {   // in launch order
     std::vector<ResizeLaunch> resize;   // depth 0: resize from the full-resolution gray image
     std::vector<FusedLaunch> fused;     // first-octave layers with a pyrDown chain: resize + first pyrDown, the resized pixels stay in LDS

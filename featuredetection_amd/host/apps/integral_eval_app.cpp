@@ -5,6 +5,11 @@
 // config (boost info format, keys of benchmarkApp):
 //   feature haar { sizes "0.2 0.4"  gridRows 5  gridCols 5  types "2rect 3rect 4rect center-surround" }     (types: also "all")
 //   feature surf { gradientCount 12  cellCount 4 }
+//   feature ihog { gradientCount 30  bins 9  signed false  interpolate true  scale 1.1                      (keys of the tracking apps,
+//                  histogram spatial { cellSize 6 blockSize 1 interpolate false normalization l2norm } }     AdaptiveTracking.cpp:189-213:
+//   feature iehog { gradientCount 30  bins 18  signed true  interpolate false  scale 1.1                    behind an IntegralFeatureExtractor,
+//                   histogram { cellSize 6 interpolate 0 signedAndUnsigned 1 alpha 0.2 } }                  and a PatchResizingFeatureExtractor
+//                                                                                                           when scale != 1)
 //   classifier { classifierFile <SVM text file>  [threshold t] [logisticA a logisticB b] }
 //   aspectRatio r                                                                                           (optional, default 1)
 // samples.txt: one "x y size" per line (width = size, height = cvRound(aspectRatio * size)).  Prints "<target 0|1> <weight>" per sample, and on
@@ -15,6 +20,7 @@
 #include <sstream>
 #include "condensation/condensation_all.hpp"
 #include "fdcompat/ptree.hpp"
+#include "tracking_setup.hpp"
 
 using namespace imageprocessing;
 using namespace classification;
@@ -79,7 +85,8 @@ static shared_ptr<FeatureExtractor> createFeatureExtractor(const ptree& config) 
     const string kind = config.get_value<string>();
     if (kind == "haar") return createHaarExtractor(config);
     if (kind == "surf") return createSurfExtractor(config);
-    throw std::invalid_argument("invalid feature type: " + kind + " (integral_eval_app knows haar and surf)");
+    if (kind == "ihog" || kind == "iehog") return tracking_setup::createFeatureExtractor(config);
+    throw std::invalid_argument("invalid feature type: " + kind + " (integral_eval_app knows haar, surf, ihog and iehog)");
 }
 
 int main(int argc, char** argv) {

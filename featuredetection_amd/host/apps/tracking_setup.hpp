@@ -21,9 +21,15 @@
 //   }
 //   validator rvm { classifierFile <FDRVM1 file>  [numFiltersToUse n]  feature grayscale|h|whi { ... }  sizes "0.9 1 1.1"  displacements "-0.1 0 0.1" }
 //                        (beside `measurement`, in the `tracking` block: a condensation::ClassificationBasedStateValidator on the adaptive tracker)
+//     feature haar { sizes "0.2 0.4" gridRows 5 gridCols 5 types "2rect 3rect 4rect center-surround"   scale 1 }
+//     feature ihog { gradientCount 30 bins 9 signed false interpolate true  histogram spatial|pyramid { ... }   scale 1.1 }
+//     feature iehog { gradientCount 30 bins 18 signed true interpolate false  histogram { cellSize 6 interpolate 0 signedAndUnsigned 1 alpha 0.2 }  scale 1 }
+//     feature surf { gradientCount 12 cellCount 4   scale 1 }
+//                        (the integral feature types of AdaptiveTracking.cpp:152-221: a DirectImageFeatureExtractor on the integral image,
+//                         behind an IntegralFeatureExtractor except for haar, behind a PatchResizingFeatureExtractor when scale != 1)
 // Not built, each an invalid_argument that names it: the feature type histeq (u8 vectors: this host layer's RvmClassifier and the
-// trainers take CV_32F), `pyramid derived`, and the integral feature types (haar, ihog, iehog, surf) under this key.  A bare
-// `filter before` / `filter after` without its block is refused with what the block needs.
+// trainers take CV_32F) and `pyramid derived`.  A bare `filter before` / `filter after` without its block is refused with what the
+// block needs.
 #pragma once
 #include <cmath>
 #include <memory>
@@ -46,7 +52,13 @@ using boost::property_tree::ptree;
 using namespace imageprocessing;
 using namespace classification;
 
-inline bool flag(const ptree& config, const std::string& key, bool dflt = false) { return config.get<int>(key, dflt ? 1 : 0) != 0; }
+// a boolean key: 0 / 1, or true / false as the reference's configuration files write them (boost's get<bool> reads both)
+inline bool flag(const ptree& config, const std::string& key, bool dflt = false) {
+    const std::string word = config.get<std::string>(key, std::string());
+    if (word == "true") return true;
+    if (word == "false") return false;
+    return config.get<int>(key, dflt ? 1 : 0) != 0;
+}
 
 // createPyramidExtractor, `direct` (DirectPyramidFeatureExtractor.cpp:27-36,41-43)
 inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(const ptree& config) {
@@ -101,6 +113,58 @@ inline std::shared_ptr<LbpFilter> createLbpFilter(const std::string& lbpType) {
     throw std::invalid_argument("tracking: invalid LBP type: " + lbpType);
 }
 
+// wrapFeatureExtractor (AdaptiveTracking.cpp:263-267)
+inline std::shared_ptr<FeatureExtractor> wrapFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor, float scaleFactor) {
+    if (scaleFactor == 1.0) return extractor;
+    return std::make_shared<PatchResizingFeatureExtractor>(extractor, scaleFactor);
+}
+
+// "0.2 0.4" -> {0.2f, 0.4f}
+inline std::vector<float> readFloats(const std::string& text) {
+    std::vector<float> values;
+    std::istringstream in(text);
+    float value;
+    while (in >> value) values.push_back(value);
+    return values;
+}
+
+// the integral feature types (AdaptiveTracking.cpp:152-221): a DirectImageFeatureExtractor on [GrayscaleFilter, IntegralImageFilter];
+// ihog, iehog and surf sit behind an IntegralFeatureExtractor, haar does not
+inline std::shared_ptr<FeatureExtractor> createIntegralExtractor(const std::string& type, const ptree& config) {
+    auto extractor = std::make_shared<DirectImageFeatureExtractor>();
+    extractor->addImageFilter(std::make_shared<GrayscaleFilter>());
+    extractor->addImageFilter(std::make_shared<IntegralImageFilter>());
+    if (type == "haar") {
+        int types = 0;
+        std::string name;
+        std::istringstream typesStream(config.get<std::string>("types"));
+        while (typesStream >> name) {
+            if (name == "2rect") types |= HaarFeatureFilter::TYPE_2RECTANGLE;
+            else if (name == "3rect") types |= HaarFeatureFilter::TYPE_3RECTANGLE;
+            else if (name == "4rect") types |= HaarFeatureFilter::TYPE_4RECTANGLE;
+            else if (name == "center-surround") types |= HaarFeatureFilter::TYPE_CENTER_SURROUND;
+            else if (name == "all") types |= HaarFeatureFilter::TYPES_ALL;
+        }
+        // as the reference passes them: gridRows is the constructor's xCount, gridCols its yCount
+        extractor->addPatchFilter(std::make_shared<HaarFeatureFilter>(readFloats(config.get<std::string>("sizes")), (unsigned int)config.get<float>("gridRows"),
+                                                                      (unsigned int)config.get<float>("gridCols"), types));
+        return extractor;
+    }
+    extractor->addPatchFilter(std::make_shared<IntegralGradientFilter>(config.get<int>("gradientCount")));
+    if (type == "surf") {
+        extractor->addPatchFilter(std::make_shared<GradientSumFilter>(config.get<int>("cellCount")));
+        extractor->addPatchFilter(std::make_shared<UnitNormFilter>(cv::NORM_L2));
+    } else {
+        extractor->addPatchFilter(std::make_shared<GradientBinningFilter>(config.get<int>("bins"), flag(config, "signed"), flag(config, "interpolate")));
+        if (type == "ihog")
+            extractor->addPatchFilter(createHogFilter(config.get<int>("bins"), config.get_child("histogram")));
+        else
+            extractor->addPatchFilter(std::make_shared<ExtendedHogFilter>(config.get<int>("bins"), config.get<int>("histogram.cellSize"), flag(config, "histogram.interpolate"),
+                                                                          flag(config, "histogram.signedAndUnsigned"), config.get<float>("histogram.alpha")));
+    }
+    return std::make_shared<IntegralFeatureExtractor>(extractor);
+}
+
 inline std::shared_ptr<FeatureExtractor> createFeatureExtractor(const ptree& config) {
     const std::string type = config.get_value<std::string>();
     const float scaleFactor = config.get<float>("scale", 1.f);
@@ -134,12 +198,11 @@ inline std::shared_ptr<FeatureExtractor> createFeatureExtractor(const ptree& con
         throw std::invalid_argument("tracking: the feature type `histeq` is not built (its vectors are u8; the RvmClassifier and the trainers of this "
                                     "host layer take CV_32F vectors: use `h`)");
     } else if (type == "haar" || type == "ihog" || type == "iehog" || type == "surf") {
-        throw std::invalid_argument("tracking: the integral feature type `" + type + "` is not built for measurement positionDependent");
+        return wrapFeatureExtractor(createIntegralExtractor(type, config), scaleFactor);
     } else {
         throw std::invalid_argument("tracking: invalid feature type: " + type);
     }
-    if (scaleFactor == 1.0) return extractor;
-    return std::make_shared<PatchResizingFeatureExtractor>(extractor, scaleFactor);
+    return wrapFeatureExtractor(extractor, scaleFactor);
 }
 
 // the trainable SVM of a `classifier { training { ... } }` block

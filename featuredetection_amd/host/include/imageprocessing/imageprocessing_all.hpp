@@ -604,9 +604,16 @@ public:
     PatchResizingFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor, double factor, double yOffset = 0, double xOffset = 0)
         : extractor(extractor), factor(factor), yOffset(yOffset), xOffset(xOffset) {}
     void update(std::shared_ptr<VersionedImage> image) override { extractor->update(image); }
+    // what the underlying extractor is asked for (not in the reference: the one copy of these expressions)
+    void mapSample(int& x, int& y, int& width, int& height) const {
+        x = cv::cvRound(x + xOffset * width);
+        y = cv::cvRound(y + yOffset * height);
+        width = cv::cvRound(factor * width);
+        height = cv::cvRound(factor * height);
+    }
     std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override {
-        std::shared_ptr<Patch> patch = extractor->extract(cv::cvRound(x + xOffset * width), cv::cvRound(y + yOffset * height), cv::cvRound(factor * width),
-                                                          cv::cvRound(factor * height));
+        mapSample(x, y, width, height);
+        std::shared_ptr<Patch> patch = extractor->extract(x, y, width, height);
         if (patch) {
             patch->setWidth(cv::cvRound(patch->getWidth() / factor));
             patch->setHeight(cv::cvRound(patch->getHeight() / factor));
@@ -616,9 +623,73 @@ public:
         return patch;
     }
     std::shared_ptr<FeatureExtractor> getExtractor() const { return extractor; }
+    double getFactor() const { return factor; }
+    double getXOffset() const { return xOffset; }
+    double getYOffset() const { return yOffset; }
 private:
     std::shared_ptr<FeatureExtractor> extractor;
     double factor, yOffset, xOffset;
+};
+
+// IntegralFeatureExtractor.hpp:17-55: a feature extractor on an integral image is asked for a patch one pixel wider and higher (the
+// integral image has one row and column more than the image), moved by one where the size is odd
+class IntegralFeatureExtractor : public FeatureExtractor {
+public:
+    using FeatureExtractor::update;
+    explicit IntegralFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor) : extractor(extractor) {}
+    void update(std::shared_ptr<VersionedImage> image) override { extractor->update(image); }
+    // what the underlying extractor is asked for (not in the reference: the one copy of these expressions)
+    void mapSample(int& x, int& y, int& width, int& height) const {
+        x += width % 2 == 0 ? 0 : 1;
+        y += height % 2 == 0 ? 0 : 1;
+        width += 1;
+        height += 1;
+    }
+    std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override {
+        const int offsetX = width % 2 == 0 ? 0 : 1, offsetY = height % 2 == 0 ? 0 : 1;
+        mapSample(x, y, width, height);
+        std::shared_ptr<Patch> patch = extractor->extract(x, y, width, height);
+        if (patch) {
+            patch->setX(patch->getX() - offsetX);
+            patch->setY(patch->getY() - offsetY);
+            patch->setWidth(patch->getWidth() - 1);
+            patch->setHeight(patch->getHeight() - 1);
+        }
+        return patch;
+    }
+    std::shared_ptr<FeatureExtractor> getExtractor() const { return extractor; }
+private:
+    std::shared_ptr<FeatureExtractor> extractor;
+};
+
+// Not in the reference: the chain of PatchResizingFeatureExtractor / IntegralFeatureExtractor wrappers around an extractor, walked
+// once.  inner() is the extractor the wrappers end at; map() applies every wrapper's forward map to a sample {x, y, width, height},
+// outer to inner, so that the batched device calls receive what the innermost extract(x, y, width, height) would.
+class ExtractorWrappers {
+public:
+    explicit ExtractorWrappers(const FeatureExtractor* outer) : innermost(outer) {
+        for (;;) {
+            if (auto* resizing = dynamic_cast<const PatchResizingFeatureExtractor*>(innermost)) { chain.push_back(innermost); innermost = resizing->getExtractor().get(); }
+            else if (auto* integral = dynamic_cast<const IntegralFeatureExtractor*>(innermost)) { chain.push_back(innermost); innermost = integral->getExtractor().get(); }
+            else break;
+        }
+    }
+    const FeatureExtractor* inner() const { return innermost; }
+    bool wrapped() const { return !chain.empty(); }
+    void map(int& x, int& y, int& width, int& height) const {
+        for (const FeatureExtractor* w : chain) {
+            if (auto* resizing = dynamic_cast<const PatchResizingFeatureExtractor*>(w)) resizing->mapSample(x, y, width, height);
+            else static_cast<const IntegralFeatureExtractor*>(w)->mapSample(x, y, width, height);
+        }
+    }
+    void map(int32_t* xywh) const {
+        int x = xywh[0], y = xywh[1], w = xywh[2], h = xywh[3];
+        map(x, y, w, h);
+        xywh[0] = x; xywh[1] = y; xywh[2] = w; xywh[3] = h;
+    }
+private:
+    const FeatureExtractor* innermost;
+    std::vector<const FeatureExtractor*> chain;
 };
 
 // ---- the integral-image family: image filters GrayscaleFilter -> IntegralImageFilter of a DirectImageFeatureExtractor, patch filters
@@ -721,6 +792,17 @@ public:
     std::shared_ptr<HaarFeatureFilter> getHaarChain() const;
     // patch filters == [IntegralGradientFilter(g), GradientSumFilter(c), UnitNormFilter(NORM_L2)], both square
     bool getSurfChain(int& gradientCount, int& cellCount) const;
+    // patch filters == [IntegralGradientFilter, GradientBinningFilter, one of HogFilter | SpatialHistogramFilter | PyramidHogFilter |
+    // SpatialPyramidHistogramFilter | ExtendedHogFilter] (the ihog / iehog feature types) with parameters fd_integral_extract_hog takes
+    bool getIntegralHogChain(fd_integral_hog_params& hp) const;
+    // the last patch filter where it is an ExtendedHogFilter (the iehog feature type); null otherwise
+    std::shared_ptr<ExtendedHogFilter> getExtendedHogFilter() const {
+        const auto& f = patchFilter->getFilters();
+        return f.empty() ? nullptr : std::dynamic_pointer_cast<ExtendedHogFilter>(f.back());
+    }
+    // not in the reference: the patch data of n samples {x, y, width, height} of an integral HOG chain in one fd_integral_extract_hog,
+    // each as extract(x, y, width, height)->getData() gives it; an empty Mat where extract returns null
+    std::vector<cv::Mat> extractIntegralHog(const fd_integral_hog_params& hp, const std::vector<int32_t>& xywh) const;
 private:
     const cv::Mat& hostImage() const;
     Version version;

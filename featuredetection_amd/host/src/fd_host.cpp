@@ -760,6 +760,43 @@ bool DirectImageFeatureExtractor::getSurfChain(int& gradientCount, int& cellCoun
     cellCount = s->getRows();
     return true;
 }
+bool DirectImageFeatureExtractor::getIntegralHogChain(fd_integral_hog_params& hp) const {
+    const auto& f = patchFilter->getFilters();
+    if (f.size() != 3) return false;
+    const auto* g = dynamic_cast<const IntegralGradientFilter*>(f[0].get());
+    const auto* b = dynamic_cast<const GradientBinningFilter*>(f[1].get());
+    const auto* h = dynamic_cast<const HistogramFilter*>(f[2].get());
+    if (!g || !b || !h) return false;
+    std::memset(&hp, 0, sizeof(hp));
+    hp.grad_rows = g->getRows(); hp.grad_cols = g->getCols();
+    hp.bins = (int32_t)b->bins; hp.signed_gradients = b->signedGradients; hp.interpolate_bins = b->interpolate;
+    if (auto* e = dynamic_cast<const ExtendedHogFilter*>(h)) {
+        hp.kind = FD_SAMPLES_EHOG;
+        hp.ehog = fd_ehog_patch_params{hp.grad_cols, hp.grad_rows, e->binCount, e->cellWidth, e->cellHeight, e->interpolate, e->signedAndUnsigned, e->alpha};
+    } else {
+        hp.kind = FD_SAMPLES_HIST;
+        hp.hist = hist_params_of(*h, hp.grad_cols, hp.grad_rows, 1, 1);
+    }
+    return fd_integral_hog_feature_length(&hp) > 0;   // anything the fused call refuses stays on the per-Mat composition
+}
+vector<Mat> DirectImageFeatureExtractor::extractIntegralHog(const fd_integral_hog_params& hp, const vector<int32_t>& xywh) const {
+    const int n = (int)(xywh.size() / 4), F = fd_integral_hog_feature_length(&hp);
+    vector<Mat> data((size_t)n);
+    if (n == 0) return data;
+    if (!native() || F <= 0) throw std::logic_error("DirectImageFeatureExtractor: extractIntegralHog needs an updated integral image and an integral HOG chain");
+    vector<float> rows((size_t)n * F);
+    vector<uint8_t> valid((size_t)n);
+    check(fd_integral_extract_hog(context(), integral, &hp, n, xywh.data(), rows.data(), valid.data()));
+    // ExtendedHogFilter::applyTo gives cell rows x (cell columns * channels), the histogram filters 1 x F
+    const int matRows = hp.kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(hp.grad_rows) / static_cast<double>(hp.ehog.cell_h > 0 ? hp.ehog.cell_h : hp.ehog.cell_w)) : 1;
+    for (int i = 0; i < n; ++i) {
+        if (!valid[i]) continue;
+        Mat m(matRows, F / matRows, CV_32FC1);
+        std::memcpy(m.ptr<float>(0), rows.data() + (size_t)i * F, sizeof(float) * (size_t)F);
+        data[i] = m;
+    }
+    return data;
+}
 
 namespace filtering {
 FhogFilter::FhogFilter(int cellSize, int unsignedBinCount, bool interpolateBins, bool interpolateCells, float alpha)
@@ -2728,16 +2765,24 @@ void SingleClassifierModel::evaluate(Sample& sample) const {
 }
 void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
     update(image);
-    auto* direct = dynamic_cast<imageprocessing::DirectImageFeatureExtractor*>(featureExtractor.get());
+    // the integral chains (haar, surf, ihog / iehog), also behind PatchResizingFeatureExtractor / IntegralFeatureExtractor wrappers: the
+    // wrappers are integer maps of the sample, applied here, and the features of all samples come from one device call
+    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
+    auto* direct = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
     auto* psvm = dynamic_cast<classification::ProbabilisticSvmClassifier*>(classifier.get());
+    if (direct && !psvm)
+        if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
     shared_ptr<imageprocessing::HaarFeatureFilter> haar;
     fd_surf_params surf = {0, 0};
+    fd_integral_hog_params ihog;
+    bool integralHog = false;
     bool fused = direct && direct->native() && detection::hasF32SupportVectors(psvm);
     if (fused) {
         haar = direct->getHaarChain();
         int g = 0, c = 0;
         if (!haar && direct->getSurfChain(g, c)) { surf.gradient_count = g; surf.cell_count = c; }
-        fused = haar || surf.gradient_count > 0;
+        if (!haar && surf.gradient_count == 0) integralHog = direct->getIntegralHogChain(ihog);
+        fused = haar || surf.gradient_count > 0 || integralHog;
     }
     // sampled pyramid windows: a native DirectPyramidFeatureExtractor (not wrapped) on a histogram or extended-HOG chain with a
     // ProbabilisticSvmClassifier or a TrainableProbabilisticSvmClassifier on f32 vectors: one fd_hist_svm_evaluate_samples
@@ -2768,7 +2813,9 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     ++fusedEvaluations;
     const int n = (int)samples.size();
     if (n == 0) return;
-    const vector<int32_t> xywh = pack_samples(samples);
+    vector<int32_t> xywh = pack_samples(samples);
+    if (!pyramidDirect)
+        for (int i = 0; i < n; ++i) wrappers.map(xywh.data() + 4 * (size_t)i);
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
     if (grayPatches && prvm) {   // level and distance from the device, verdict and probability by the classifier's own getProbability
@@ -2796,8 +2843,9 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     } else {
         fd_haar_params hp;
         if (haar) hp = haar->params();
-        check(fd_integral_svm_evaluate_samples(context(), direct->native(), haar ? FD_INTEGRAL_HAAR : FD_INTEGRAL_SURF, haar ? (const void*)&hp : (const void*)&surf, svm, n,
-                                               xywh.data(), target.data(), weight.data()));
+        const int kind = haar ? (int)FD_INTEGRAL_HAAR : (integralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
+        const void* prm = haar ? (const void*)&hp : (integralHog ? (const void*)&ihog : (const void*)&surf);
+        check(fd_integral_svm_evaluate_samples(context(), direct->native(), kind, prm, svm, n, xywh.data(), target.data(), weight.data()));
     }
     unpack_samples(target, weight, samples);
 }
@@ -2972,6 +3020,20 @@ bool PositionDependentMeasurementModel::hasWindow(int x, int y, int width, int h
         check(fd_pyramid_sample_windows(direct->getPyramid()->native(), direct->getPatchWidth(), direct->getPatchHeight(), 1, s, w));
         return w[3] != 0;
     }
+    // an integral HOG chain (ihog / iehog, also behind its wrappers): the rule of the kernels on the mapped sample, on the host
+    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
+    auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
+    fd_integral_hog_params ihog;
+    if (image && image->native() && image->getIntegralHogChain(ihog)) {
+        int32_t s[4] = {x, y, width, height};
+        wrappers.map(s);
+        int iw = 0, ih = 0;
+        check(fd_integral_size(image->native(), &iw, &ih));
+        uint8_t valid = 0;
+        if (fd_integral_gradient_samples_valid(iw - 1, ih - 1, ihog.grad_rows, ihog.grad_cols, 1, s, &valid) != FD_OK)
+            throw std::invalid_argument("PositionDependentMeasurementModel: the integral image has no size");
+        return valid != 0;
+    }
     return (bool)featureExtractor->extract(x, y, width, height);
 }
 vector<Mat> PositionDependentMeasurementModel::extractAll(const vector<Sample>& samples, bool square) const {
@@ -2987,6 +3049,21 @@ vector<Mat> PositionDependentMeasurementModel::extractAll(const vector<Sample>& 
         }
         for (const auto& patch : direct->extract(rects))
             if (patch) data.push_back(patch->getData());
+        return data;
+    }
+    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
+    auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
+    fd_integral_hog_params ihog;
+    if (image && image->native() && image->getIntegralHogChain(ihog)) {   // one fd_integral_extract_hog for the set
+        vector<int32_t> xywh;
+        xywh.reserve(4 * samples.size());
+        for (const Sample& s : samples) {
+            int32_t m[4] = {s.getX(), s.getY(), s.getWidth(), square ? s.getSize() : s.getHeight()};
+            wrappers.map(m);
+            xywh.insert(xywh.end(), m, m + 4);
+        }
+        for (const Mat& m : image->extractIntegralHog(ihog, xywh))
+            if (!m.empty()) data.push_back(m);
         return data;
     }
     for (const Sample& s : samples) {
@@ -3017,12 +3094,13 @@ vector<double> PositionDependentMeasurementModel::probabilities(const vector<Mat
     return p;
 }
 // floats per cell of an extractor's patch data where the reference's Mat would carry them as channels: the descriptor of the
-// ExtendedHogFilter of an ehog chain (also behind a PatchResizingFeatureExtractor), 1 for everything else
+// ExtendedHogFilter of an ehog or iehog chain (also behind its wrapper extractors), 1 for everything else
 static int patch_channels(const imageprocessing::FeatureExtractor* extractor) {
-    while (auto* resizing = dynamic_cast<const imageprocessing::PatchResizingFeatureExtractor*>(extractor)) extractor = resizing->getExtractor().get();
-    auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor);
-    if (!direct || !direct->getExtendedHogFilter()) return 1;
-    const auto f = direct->getExtendedHogFilter();
+    extractor = imageprocessing::ExtractorWrappers(extractor).inner();
+    std::shared_ptr<imageprocessing::ExtendedHogFilter> f;
+    if (auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor)) f = direct->getExtendedHogFilter();
+    else if (auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(extractor)) f = image->getExtendedHogFilter();
+    if (!f) return 1;
     return f->binCount + (f->signedAndUnsigned ? f->binCount / 2 : 0) + 4;
 }
 // cv::flip(data, mirrored, 1) of a Mat whose columns are cells of `channels` floats: the cells of a row in reverse order, each as it is

@@ -1057,6 +1057,32 @@ typedef struct {
 } fd_surf_params;
 int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, const void* params, const fd_svm* svm, int n,
                                      const int32_t* xywh, uint8_t* target, double* weight);
+/* The integral HOG family, the "ihog" and "iehog" feature types of the tracking apps (AdaptiveTracking.cpp:189-213):
+ * IntegralGradientFilter(grad_rows, grad_cols) -> GradientBinningFilter(bins, signed_gradients, interpolate_bins) -> one of the four
+ * FD_HIST_* patch filters (kind FD_SAMPLES_HIST) or ExtendedHogFilter (kind FD_SAMPLES_EHOG), per sample in one launch: the
+ * gradient patch and the bin image stay in LDS.  Bit for bit what fd_integral_gradient_patches -> fd_gradient_binning_image ->
+ * fd_hist_patch_batch / fd_ehog_patch_batch give.  xywh is what the innermost DirectImageFeatureExtractor::extract receives: the
+ * maps of IntegralFeatureExtractor (+1) and PatchResizingFeatureExtractor (scale) are the caller's.
+ * FD_ERR_INVALID_ARGUMENT: a grid side outside 2..64, bins outside 1..255, a filter patch other than grad_cols x grad_rows, filter
+ * bins other than `bins`, whatever fd_hist_feature_length / fd_ehog_feature_length refuse with interpolate_bins ? 4 : 2 channels,
+ * and a configuration whose four samples per workgroup do not fit the 160 KB of LDS (tables + 4 * (2|4 * rows * cols rounded up to
+ * 16 + the vector area of the histogram filter); the three stand-alone calls serve those). */
+typedef struct {
+    int32_t grad_rows, grad_cols;                      /* IntegralGradientFilter(rows, cols): 2..64 each */
+    int32_t bins, signed_gradients, interpolate_bins;  /* GradientBinningFilter(bins, signed, interpolate) */
+    int32_t kind;                                      /* FD_SAMPLES_HIST: `hist` is read; FD_SAMPLES_EHOG: `ehog` is read */
+    fd_hist_params hist;                               /* patch_w == grad_cols, patch_h == grad_rows, bins == bins; step_x / step_y ignored */
+    fd_ehog_patch_params ehog;                         /* same three equalities */
+} fd_integral_hog_params;
+enum { FD_INTEGRAL_HOG = 2 };   /* fd_integral_svm_evaluate_samples: params is a const fd_integral_hog_params* */
+/* host only: floats per sample, or -1 where fd_integral_extract_hog returns FD_ERR_INVALID_ARGUMENT */
+int fd_integral_hog_feature_length(const fd_integral_hog_params* hp);
+/* host only: valid[i] = 1 iff sample i of a width x height image has a patch and every read of IntegralGradientFilter(rows, cols)
+ * lies inside the integral image -- the statements the kernels run.  2 <= rows, cols <= 16384. */
+int fd_integral_gradient_samples_valid(int width, int height, int rows, int cols, int n, const int32_t* xywh, uint8_t* valid);
+/* n x fd_integral_hog_feature_length floats; rows of samples without a valid patch are zero.  features or valid may be NULL. */
+int fd_integral_extract_hog(fd_ctx* ctx, fd_integral* g, const fd_integral_hog_params* hp, int n, const int32_t* xywh, float* features,
+                            uint8_t* valid);
 /* Host only (no context, no device): the argument rules of the calls above, which use these very functions.  Each returns the
  * length of one output, or -1 where the call returns FD_ERR_INVALID_ARGUMENT.  fd_integral_image_length: (width + 1) * (height + 1)
  * ints; -1 for a size below 1 or 255 * width * height > 2^31 - 1.  fd_integral_gradient_length: 2 * rows * cols bytes per sample;

@@ -4,6 +4,15 @@
   python tools/integral_probe.py --size 640x480       one size only
   python tools/integral_probe.py --profile DIR        also one `rocprofv3 --kernel-trace --stats` run per size (a fresh child process;
                                                       CSVs under DIR) and the mean microseconds per launch of every kernel
+  python tools/integral_probe.py --hog                the integral HOG family instead: 1000 samples of a 640x480 frame with the reference's
+                                                      default `feature ihog` configuration (gradientCount 30, 9 bins interpolated, spatial
+                                                      histogram of 6-pixel cells, l2norm), three routes to the same n x 225 floats on the host
+                                                      -- per sample (the three stand-alone calls on one sample at a time, what the host
+                                                      layer's per-Mat loop issues), composed (the three stand-alone calls on all samples,
+                                                      two host round trips between them) and fused (fd_integral_extract_hog) -- and
+                                                      svm_evaluate_samples(hog=...) with a 256-SV RBF SVM
+  python tools/integral_probe.py --hog --root DIR     ... of the tree under DIR (a checkout of another commit with its library built); a
+                                                      tree without the fused call reports the first two routes
 
 Frames are gray and device-resident (fd_integral_update with is_device = 1): `update` is the three launches and nothing else, and
 its achieved fraction of HBM is (W H + 4 (W + 1)(H + 1)) bytes -- what it must read and write -- over the measured time, against the
@@ -93,6 +102,55 @@ def run(size, calls, warmup):
     return out
 
 
+HOG_SAMPLES = 1000
+
+
+def run_hog(calls, warmup):
+    from featuredetection_amd import capi, synth
+    w, h = SIZES[0]
+    stream = torch.cuda.Stream()
+    ctx = capi.Context(0, stream=stream.cuda_stream)
+    g = capi.Integral(ctx)
+    frame = torch.from_numpy(synth.bgr2gray_np(synth.make_frame(w, h, seed=200))).cuda()
+    torch.cuda.synchronize()
+    G, BINS = 30, 9
+    hist = capi.hist_params(kind=capi.HIST_SPATIAL, pw=G, ph=G, sx=1, sy=1, bins=BINS, cell=6, block=1, normalization=1)
+    s = make_samples(w, h, HOG_SAMPLES, seed=3)
+    out = dict(size="%dx%d" % (w, h), samples=HOG_SAMPLES, calls=calls)
+
+    def composed(samples):
+        grad, valid = g.gradient_patches(G, G, samples)
+        bins = capi.gradient_binning_image(ctx, grad.reshape(len(samples) * G, G, 2), BINS, signed_gradients=False, interpolate=True)
+        return capi.hist_patch_batch(ctx, bins.reshape(len(samples), G, G, 4), hist), valid
+
+    def per_sample():
+        return np.concatenate([composed(s[i:i + 1])[0] for i in range(len(s))])
+
+    def entry(t):
+        return dict(ms_median=t[0], ms_p10=t[1], ms_p90=t[2], samples_per_s=HOG_SAMPLES / (t[0] * 1e-3))
+    with torch.cuda.stream(stream):
+        g.update_device(frame.data_ptr(), w, h, 1)
+        want, valid = composed(s)
+        assert valid.all()
+        out["composed"] = entry(timed(stream, lambda: composed(s), calls, warmup))
+        assert np.array_equal(per_sample(), want)
+        out["per_sample"] = entry(timed(stream, per_sample, max(3, calls // 8), 1))
+        svm = capi.Svm(ctx, synth.make_svm_f32(9, want, nsv=256, gamma=0.5, positive_fraction=0.1))
+        # SingleClassifierModel's per-sample loop: extract one patch, classify it
+        out["per_sample_svm_256sv"] = entry(timed(stream, lambda: [svm.distance(composed(s[i:i + 1])[0]) for i in range(len(s))], max(3, calls // 8), 1))
+        if hasattr(capi, "integral_hog_params"):
+            hp = capi.integral_hog_params(G, G, bins=BINS, interpolate_bins=True, hist=hist)
+            got, gvalid = g.extract_hog(hp, s)
+            assert gvalid.all() and np.array_equal(got, want)
+            out["fused"] = entry(timed(stream, lambda: g.extract_hog(hp, s), calls, warmup))
+            out["fused_rows_on_device"] = entry(timed(stream, lambda: g.extract_hog(hp, s, download=False), calls, warmup))
+            out["svm_evaluate_hog_256sv"] = entry(timed(stream, lambda: g.svm_evaluate_samples(svm, s, hog=hp), calls, warmup))
+        svm.close()
+    g.close()
+    ctx.close()
+    return out
+
+
 def kernel_split(outdir):
     """calls and mean microseconds per launch of every kernel in the child's kernel_stats CSV"""
     files = glob.glob(os.path.join(outdir, "**", "*kernel_stats.csv"), recursive=True)
@@ -117,7 +175,14 @@ def main():
     ap.add_argument("--calls", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--profile", default=None, help="directory for the rocprofv3 runs")
+    ap.add_argument("--hog", action="store_true", help="the integral HOG routes on 640x480 instead")
+    ap.add_argument("--root", default=None, help="measure the featuredetection_amd package of this tree")
     a = ap.parse_args()
+    if a.root:
+        sys.path.insert(0, os.path.abspath(a.root))
+    if a.hog:
+        print(json.dumps(dict(probe="integral_hog", results=[run_hog(a.calls, a.warmup)])))
+        return
     sizes = [tuple(int(v) for v in a.size.split("x"))] if a.size else list(SIZES)
     results, kernels = [], {}
     for size in sizes:
