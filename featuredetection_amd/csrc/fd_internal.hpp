@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <map>
 #include <memory>
@@ -559,6 +560,53 @@ void fd_svm_u8_mfma_launch_counted(hipStream_t st, const fd_svm* m, const void* 
 // classifier positives of N scored windows -> detection records in extraction order (hog.hip)
 void fd_svm_positives_to_detections(fd_ctx* ctx, const fd_pyramid* p, const fd_svm* svm, const std::vector<WindowLayer>& wls, int sx, int sy,
                                     const double* ddist, int64_t N, fd_detection* out, int64_t cap, int64_t* count, double* all_distance);
+
+// ---------------- sampled windows: what follows the feature rows (hist_samples.hpp, patch_samples.hpp, integral.hip) ----------------
+// nv rows of F floats at dfeat (device, queued on ctx->stream) -> features[n][F] (host, zeroed by the caller): row k belongs to sample
+// sampleOf[k].  The rows are in place when every sample has a window; otherwise they are downloaded and scattered.  Synchronises.
+static inline void fd_samples_rows_to_host(fd_ctx* ctx, const float* dfeat, int F, int64_t nv, int n, const std::vector<int>& sampleOf, float* features) {
+    const size_t rowBytes = sizeof(float) * (size_t)F;
+    std::vector<float> rows(nv == n ? 0 : (size_t)nv * F);
+    float* dst = nv == n ? features : rows.data();
+    HIP_CHECK(hipMemcpyAsync(dst, dfeat, rowBytes * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (nv == n) return;
+    for (int64_t k = 0; k < nv; ++k) std::memcpy(features + (size_t)sampleOf[k] * F, dst + (size_t)k * F, rowBytes);
+}
+
+static inline void fd_samples_require_f32_svm(const fd_svm* svm, int F, const char* who) {
+    if (fd_svm_is_u8(svm) || fd_svm_dim(svm) != F)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the SVM must work on f32 vectors of length %d (it has %d %s values)", who, F, fd_svm_dim(svm),
+                 fd_svm_is_u8(svm) ? "u8" : "f32");
+}
+
+// what a sample without a window keeps: target 0, weight 0, distance 0 (distance may be NULL)
+static inline void fd_samples_clear(int n, uint8_t* target, double* weight, double* distance) {
+    std::memset(target, 0, (size_t)n);
+    std::fill(weight, weight + n, 0.0);
+    if (distance) std::fill(distance, distance + n, 0.0);
+}
+
+// The SVM on nv feature rows of F floats at dfeat: one launch, the distances into hdist (host, nv doubles) through ddist, one wait, then
+// SvmClassifier::classify (distance >= threshold) and ProbabilisticSvmClassifier::getProbability per row.  With sampleOf (the pyramid
+// families) row k is sample sampleOf[k] and the caller has cleared the outputs; without (the integral family) row k is sample k and the
+// kernels' validity bytes at dvalid come into target with the distances: an invalid sample gets target 0, weight 0.
+static inline void fd_samples_svm_tail(fd_ctx* ctx, const fd_svm* svm, const void* dfeat, int F, int64_t nv, DevBuf& ddist, double* hdist,
+                                       const int* sampleOf, const void* dvalid, uint8_t* target, double* weight, double* distance) {
+    ddist.reserve(sizeof(double) * (size_t)nv);
+    fd_svm_generic_launch(ctx, svm, dfeat, nullptr, (int64_t)F * 4, nv, ddist.as<double>());
+    HIP_CHECK(hipMemcpyAsync(hdist, ddist.p, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
+    if (!sampleOf) HIP_CHECK(hipMemcpyAsync(target, dvalid, (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const double threshold = (double)fd_svm_threshold(svm);
+    for (int64_t k = 0; k < nv; ++k) {
+        const int64_t i = sampleOf ? sampleOf[k] : k;
+        const bool valid = sampleOf || target[i];
+        target[i] = valid && hdist[k] >= threshold ? 1 : 0;
+        weight[i] = valid ? fd_svm_probability(svm, hdist[k]) : 0.0;
+        if (distance) distance[i] = valid ? hdist[k] : 0.0;
+    }
+}
 
 // ---------------- the whi chain and ConversionFilter on device-resident data (whi.hip), for patch_samples.hpp ----------------
 // the whole whi chain on `total` listed windows {layer, bx, by} (device memory) of the gray planes of p: total x (patch_w * patch_h) floats

@@ -73,17 +73,7 @@ void extract_samples(fd_ctx* ctx, fd_pyramid* p, int kind, const void* params, i
     samples_upload(ctx, p, pl, n, xywh, valid, S, sampleOf, 0);
     const int64_t nv = (int64_t)sampleOf.size();
     if (nv == 0 || !features) return;
-    const float* dfeat = samples_features(ctx, p, pl, nv, S);
-    const size_t rowBytes = sizeof(float) * (size_t)pl.F;
-    if (nv == n) {   // every sample has a window: the rows are in place
-        HIP_CHECK(hipMemcpyAsync(features, dfeat, rowBytes * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return;
-    }
-    std::vector<float> rows((size_t)nv * pl.F);
-    HIP_CHECK(hipMemcpyAsync(rows.data(), dfeat, rowBytes * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int64_t k = 0; k < nv; ++k) std::memcpy(features + (size_t)sampleOf[k] * pl.F, rows.data() + (size_t)k * pl.F, rowBytes);
+    fd_samples_rows_to_host(ctx, samples_features(ctx, p, pl, nv, S), pl.F, nv, n, sampleOf, features);
 }
 
 }  // namespace
@@ -142,30 +132,15 @@ int fd_hist_svm_evaluate_samples_distance(fd_ctx* ctx, fd_pyramid* p, int kind, 
         const char* who = "fd_hist_svm_evaluate_samples";
         if (!ctx || !p || !params || !svm || (n > 0 && (!xywh || !target || !weight))) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
         const SamplesPlan pl = samples_plan(ctx, p, kind, params, n, who);
-        if (fd_svm_is_u8(svm) || fd_svm_dim(svm) != pl.F)
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the SVM must work on f32 vectors of length %d (it has %d %s values)", who, pl.F, fd_svm_dim(svm),
-                     fd_svm_is_u8(svm) ? "u8" : "f32");
+        fd_samples_require_f32_svm(svm, pl.F, who);
         if (n == 0) return;
-        std::memset(target, 0, (size_t)n);
-        for (int i = 0; i < n; ++i) weight[i] = 0.0;
-        if (distance) for (int i = 0; i < n; ++i) distance[i] = 0.0;
+        fd_samples_clear(n, target, weight, distance);
         HogScratch& S = scratch(ctx);
         std::vector<int> sampleOf;
         double* hdist = (double*)samples_upload(ctx, p, pl, n, xywh, nullptr, S, sampleOf, sizeof(double));
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0) return;
-        const float* dfeat = samples_features(ctx, p, pl, nv, S);
-        S.dist.reserve(sizeof(double) * (size_t)nv);
-        fd_svm_generic_launch(ctx, svm, dfeat, nullptr, (int64_t)pl.F * 4, nv, S.dist.as<double>());
-        HIP_CHECK(hipMemcpyAsync(hdist, S.dist.p, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        const double threshold = (double)fd_svm_threshold(svm);
-        for (int64_t k = 0; k < nv; ++k) {   // SvmClassifier::classify: distance >= threshold; ProbabilisticSvmClassifier::getProbability
-            const int i = sampleOf[k];
-            target[i] = hdist[k] >= threshold ? 1 : 0;
-            weight[i] = fd_svm_probability(svm, hdist[k]);
-            if (distance) distance[i] = hdist[k];
-        }
+        fd_samples_svm_tail(ctx, svm, samples_features(ctx, p, pl, nv, S), pl.F, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight, distance);
     });
 }
 

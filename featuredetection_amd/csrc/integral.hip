@@ -579,29 +579,14 @@ int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, cons
         if (kind == FD_INTEGRAL_HAAR) len = prepare_haar(ctx, g, (const fd_haar_params*)params);
         else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_check((const fd_integral_hog_params*)params);
         else len = check_surf(sp->gradient_count, sp->cell_count);
-        if (fd_svm_is_u8(svm) || fd_svm_dim(svm) != len)
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: the SVM must work on f32 vectors of length %d (it has %d %s values)", len,
-                     fd_svm_dim(svm), fd_svm_is_u8(svm) ? "u8" : "f32");
+        fd_samples_require_f32_svm(svm, len, "fd_integral_svm_evaluate_samples");
         if (n == 0) return;
         upload_samples(ctx, g, n, xywh);
         if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
         else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
         else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
-        g->dist.reserve(sizeof(double) * (size_t)n);
-        fd_svm_generic_launch(ctx, svm, g->feat.p, nullptr, (int64_t)len * 4, n, g->dist.as<double>());
-        std::vector<double> dist(n);
-        HIP_CHECK(hipMemcpyAsync(dist.data(), g->dist.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(target, g->valid.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));   // the validity first
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        const double threshold = (double)fd_svm_threshold(svm);
-        for (int i = 0; i < n; ++i) {
-            if (target[i]) {   // SvmClassifier::classify: distance >= threshold; ProbabilisticSvmClassifier::getProbability
-                target[i] = dist[i] >= threshold ? 1 : 0;
-                weight[i] = fd_svm_probability(svm, dist[i]);
-            } else {
-                weight[i] = 0.0;
-            }
-        }
+        std::vector<double> dist(n);   // the validity comes from the kernels: no sampleOf
+        fd_samples_svm_tail(ctx, svm, g->feat.p, len, n, g->dist, dist.data(), nullptr, g->valid.p, target, weight, nullptr);
     });
 }
 

@@ -49,9 +49,7 @@ void patch_samples_check(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_sample
     if (rvm && (rvm->filter_w != pp->patch_w || rvm->filter_h != pp->patch_h))
         FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the RVM's filter size %d x %d is not the patch size %d x %d", who, rvm->filter_w, rvm->filter_h,
                  pp->patch_w, pp->patch_h);
-    if (svm && (fd_svm_is_u8(svm) || fd_svm_dim(svm) != dim))
-        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the SVM must work on f32 vectors of length %d (it has %d %s values)", who, dim, fd_svm_dim(svm),
-                 fd_svm_is_u8(svm) ? "u8" : "f32");
+    if (svm) fd_samples_require_f32_svm(svm, dim, who);
 }
 
 // which route fd_patch_rvm_evaluate_samples takes for nv listed windows: the one size rule
@@ -149,17 +147,7 @@ int fd_patch_extract_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0 || !features) return;
         fd_pyramid_wait(p, ctx->stream);
-        const float* dfeat = patch_f32_rows(ctx, p, pp, nv, S);
-        const size_t rowBytes = sizeof(float) * (size_t)dim;
-        if (nv == n) {   // every sample has a window: the rows are in place
-            HIP_CHECK(hipMemcpyAsync(features, dfeat, rowBytes * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            return;
-        }
-        std::vector<float> rows((size_t)nv * dim);
-        HIP_CHECK(hipMemcpyAsync(rows.data(), dfeat, rowBytes * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (int64_t k = 0; k < nv; ++k) std::memcpy(features + (size_t)sampleOf[k] * dim, rows.data() + (size_t)k * dim, rowBytes);
+        fd_samples_rows_to_host(ctx, patch_f32_rows(ctx, p, pp, nv, S), dim, nv, n, sampleOf, features);
     });
 }
 
@@ -170,27 +158,15 @@ int fd_patch_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_sam
         if (!ctx || !p || !pp || !svm || (n > 0 && (!xywh || !target || !weight))) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
         patch_samples_check(ctx, p, pp, n, nullptr, svm, who);
         if (n == 0) return;
-        std::memset(target, 0, (size_t)n);
-        for (int i = 0; i < n; ++i) weight[i] = 0.0;
-        if (distance) for (int i = 0; i < n; ++i) distance[i] = 0.0;
+        fd_samples_clear(n, target, weight, distance);
         PatchScratch& S = patch_scratch(ctx);
         std::vector<int> sampleOf;
         double* hdist = (double*)fd_samples_upload(ctx, p, pp->patch_w, pp->patch_h, n, xywh, nullptr, S.list, sampleOf, sizeof(double));
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0) return;
         fd_pyramid_wait(p, ctx->stream);
-        const float* dfeat = patch_f32_rows(ctx, p, pp, nv, S);
-        S.dist.reserve(sizeof(double) * (size_t)nv);
-        fd_svm_generic_launch(ctx, svm, dfeat, nullptr, (int64_t)pp->patch_w * pp->patch_h * 4, nv, S.dist.as<double>());
-        HIP_CHECK(hipMemcpyAsync(hdist, S.dist.p, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        const double threshold = (double)fd_svm_threshold(svm);
-        for (int64_t k = 0; k < nv; ++k) {   // SvmClassifier::classify: distance >= threshold; ProbabilisticSvmClassifier::getProbability
-            const int i = sampleOf[k];
-            target[i] = hdist[k] >= threshold ? 1 : 0;
-            weight[i] = fd_svm_probability(svm, hdist[k]);
-            if (distance) distance[i] = hdist[k];
-        }
+        fd_samples_svm_tail(ctx, svm, patch_f32_rows(ctx, p, pp, nv, S), pp->patch_w * pp->patch_h, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight,
+                            distance);
     });
 }
 

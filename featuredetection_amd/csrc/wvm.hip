@@ -2147,23 +2147,15 @@ int fd_wvm_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, 
         if (p->kept.size() > (size_t)WVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "pyramid has %zu layers, this backend supports %d", p->kept.size(), WVM_MAX_LAYERS);
         HIP_CHECK(hipSetDevice(ctx->device));
         const int pw = m->dev.fw, ph = m->dev.fh;
-        // sample -> window (ImagePyramid::getLayer(double) :307-310, getLayer(int) by index, extract bounds check)
+        // sample -> window: the shared rule (pyramid_sample_window, fd_internal.hpp)
         std::vector<int32_t> list;
         std::vector<int> sampleOf;
-        const int firstIndex = p->kept.empty() ? 0 : p->all[p->kept[0]].index;
         for (int i = 0; i < n; ++i) {
             target[i] = 0;
             weight[i] = 0;
-            const int x = xywh[4 * i], y = xywh[4 * i + 1], width = xywh[4 * i + 2], height = xywh[4 * i + 3];
-            if (width <= 0 || p->kept.empty()) continue;
-            const double power = std::log((double)pw / (double)width) / std::log(p->inc);
-            const long index = std::lround(power);   // std::round, then the int cast of the reference
-            const long realIndex = index - firstIndex;
-            if (realIndex < 0 || realIndex >= (long)p->kept.size()) continue;
-            const HostLayer& L = p->all[p->kept[realIndex]];
-            const int bx = fd_cvRound((x - width / 2) * L.scale), by = fd_cvRound((y - height / 2) * L.scale);
-            if (bx < 0 || by < 0 || bx + pw > L.w || by + ph > L.h) continue;
-            list.push_back((int32_t)realIndex); list.push_back(bx); list.push_back(by);
+            FdSampleWindow w;
+            if (!pyramid_sample_window(p, pw, ph, xywh + 4 * (size_t)i, w)) continue;
+            list.push_back(w.layer); list.push_back(w.bx); list.push_back(w.by);
             sampleOf.push_back(i);
         }
         const int64_t nv = (int64_t)sampleOf.size();

@@ -111,17 +111,25 @@ private:
     std::shared_ptr<classification::ProbabilisticSvmClassifier> svm;
 };
 
+// Not in the reference: how the models below score the samples of an extractor with a sampled chain (imageprocessing::SampledChain,
+// resolved by sampledChainOf) in one device call.  sampledClassifierOf resolves the classifier once: svm is the
+// ProbabilisticSvmClassifier (also the one behind a TrainableProbabilisticSvmClassifier) when it works on f32 vectors, rvm the
+// ProbabilisticRvmClassifier.  sampledRoute asks no device: Svm for any chain with such an SVM (SampledChain::svmEvaluate), PatchRvm for a
+// gray-patch chain with an RVM (fd_patch_rvm_evaluate_samples), Loop for everything else.
+struct SampledClassifier {
+    const classification::ProbabilisticSvmClassifier* svm;
+    classification::ProbabilisticRvmClassifier* rvm;
+};
+enum class SampledRoute { Loop, Svm, PatchRvm };
+SampledClassifier sampledClassifierOf(classification::ProbabilisticClassifier* classifier);
+SampledRoute sampledRoute(const imageprocessing::SampledChain& chain, const SampledClassifier& classifier);
+
 // SingleClassifierModel.hpp:30-69 / SingleClassifierModel.cpp:22-63: one feature extractor, one probabilistic classifier.  The
-// batched evaluate(image, samples) scores all samples with one fd_integral_svm_evaluate_samples when the extractor is a
-// DirectImageFeatureExtractor with the chain of createHaarExtractor or createSurfExtractor (BenchmarkRunner.cpp:202-233,278-286) and
-// the classifier a ProbabilisticSvmClassifier on f32 vectors, and with one fd_hist_svm_evaluate_samples when the extractor is a
-// DirectPyramidFeatureExtractor (itself, not wrapped in a PatchResizingFeatureExtractor) whose patch filter is one histogram filter or
-// one ExtendedHogFilter on bin-image layers (the hog, lbp, glbp and ehog feature types) and the classifier a ProbabilisticSvmClassifier
-// or a TrainableProbabilisticSvmClassifier on f32 vectors, and with one fd_patch_svm_evaluate_samples / fd_patch_rvm_evaluate_samples when
-// that extractor has a sampled gray-patch chain (getSampledPatchChain: the grayscale, h and whi feature types) and the classifier is such
-// an SVM classifier / a ProbabilisticRvmClassifier; any other combination runs the per-sample loop.  (The reference's
-// result cache per patch is not kept: the results are the same.)  getFusedEvaluationCount / getLoopEvaluationCount (not in the
-// reference) tell which of the two ran: the results do not.
+// batched evaluate(image, samples) scores all samples in one device call where sampledRoute finds one for the extractor's chain and the
+// classifier and the chain is ready (an integral image exists); any other combination runs the per-sample loop.  With an RVM the
+// verdict and the probability are the classifier's own getProbability(level, distance).  (The reference's result cache per patch is
+// not kept: the results are the same.)  getFusedEvaluationCount / getLoopEvaluationCount (not in the reference) tell which of the two
+// ran: the results do not.
 class SingleClassifierModel : public MeasurementModel {
 public:
     SingleClassifierModel(std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor, std::shared_ptr<classification::ProbabilisticClassifier> classifier);
@@ -141,11 +149,11 @@ private:
 // or behind (KEEP_WEIGHT) a measurement model.  RESET_WEIGHT: a sample that does not pass the filter (no patch included) gets target
 // false and weight 0 and never reaches the model.  KEEP_WEIGHT: the model evaluates every sample; a sample it marked as target loses the
 // flag when it does not pass the filter, and keeps its weight.  The batched evaluate asks the filter once for all samples it concerns
-// (fd_patch_rvm_evaluate_samples) when the filter is an RvmClassifier or a ProbabilisticRvmClassifier and the filter's extractor a
-// DirectPyramidFeatureExtractor (itself, not wrapped) with a sampled gray-patch chain, and hands the model the passing samples in one
-// batched evaluate (RESET_WEIGHT; KEEP_WEIGHT: all samples first); anything else asks per sample.  Targets and weights do not depend on
-// the route.  (The reference's result cache per patch is not kept: the results are the same.)  getFusedFilterCount /
-// getLoopFilterCount (not in the reference) count the batched evaluate calls by the route their filter took.
+// (fd_patch_rvm_evaluate_samples) when the filter is an RvmClassifier or a ProbabilisticRvmClassifier and the chain of the filter's
+// extractor a gray-patch one, and hands the model the passing samples in one batched evaluate (RESET_WEIGHT; KEEP_WEIGHT: all samples
+// first); anything else asks per sample.  Targets and weights do not depend on the route.  (The reference's result cache per patch is
+// not kept: the results are the same.)  getFusedFilterCount / getLoopFilterCount (not in the reference) count the batched evaluate
+// calls by the route their filter took.
 class FilteringClassifierModel : public MeasurementModel {
 public:
     enum class Behavior { RESET_WEIGHT, KEEP_WEIGHT };
@@ -174,8 +182,8 @@ private:
 // ClassificationBasedStateValidator.hpp / .cpp:28-45: the state is valid when the classifier accepts one window of a small grid around
 // it -- for every size factor size = round(factor * target size), for every x displacement x = target x + round(displacement * size),
 // for every y displacement likewise (std::round: half-way cases away from zero), in that order.  With an RvmClassifier (or a
-// ProbabilisticRvmClassifier) on a DirectPyramidFeatureExtractor with a sampled gray-patch chain the whole grid is one
-// fd_patch_rvm_evaluate_samples and the verdict is any(target); otherwise the windows are asked one by one up to the first accepted.
+// ProbabilisticRvmClassifier) on an extractor with a gray-patch chain the whole grid is one fd_patch_rvm_evaluate_samples and the verdict
+// is any(target); otherwise the windows are asked one by one up to the first accepted.
 // getLastCandidates (not in the reference) returns the grid of the last call as Rect(x, y, size, size): centre and size, not bounds.
 class ClassificationBasedStateValidator : public StateValidator {
 public:
@@ -199,14 +207,15 @@ private:
 // against the unfiltered one, exploitSymmetry (cv::flip(.., 1) of the patch data).
 // Not the reference's: a std::mt19937(seed) constructor argument replaces the default-constructed boost::mt19937, and
 // distribution(generator, n) is (uint64(engine()) * n) >> 32 -- one 32-bit draw per call, the result in [0, n); n <= 0 throws
-// invalid_argument (undefined in the reference).  With a DirectPyramidFeatureExtractor on a histogram or extended-HOG chain every
-// sample set of one adapt (positives, negatives, test negatives) is extracted in one device call, whether a random sample has a
-// window is decided on the host by the extractor's own rule (fd_pyramid_sample_windows), and with a (Trainable)ProbabilisticSvm
-// classifier the confidence predicates score all vectors of a set in one call.  exploitSymmetry mirrors patch data as cv::flip(.., 1)
-// mirrors the reference's Mat: an ExtendedHogFilter descriptor is rows x cols cells of bins (+ bins / 2) + 4 channels there and rows x
-// cols * channels CV_32FC1 here, so for a DirectPyramidFeatureExtractor on an ehog chain (also behind a PatchResizingFeatureExtractor) the
-// cells of a row change places and every cell keeps its channel order; all other patch data is flipped element by element, which is the
-// reference's result for single-channel data (an ExtendedHogFilter reached through any other extractor type is not recognised).
+// invalid_argument (undefined in the reference).  With an extractor whose chain is extractable (SampledChain: the pyramid kinds, and
+// integral HOG once an integral image exists) every sample set of one adapt (positives, negatives, test negatives) is extracted in
+// one device call (SampledChain::extract), whether a random sample has a window is decided on the host by the rule of the kernels
+// (SampledChain::hasWindow), and with a (Trainable)ProbabilisticSvm classifier the confidence predicates score all vectors of a set
+// in one call.  exploitSymmetry mirrors patch data as cv::flip(.., 1) mirrors the reference's Mat: an ExtendedHogFilter descriptor is
+// rows x cols cells of bins (+ bins / 2) + 4 channels there and rows x cols * channels CV_32FC1 here, so for a
+// DirectPyramidFeatureExtractor on an ehog chain (also behind a PatchResizingFeatureExtractor) the cells of a row change places and
+// every cell keeps its channel order; all other patch data is flipped element by element, which is the reference's result for
+// single-channel data (an ExtendedHogFilter reached through any other extractor type is not recognised).
 // getLastAdaptation / getAdaptationCount (not in the reference) tell what the last adapt that reached a retraining chose.
 class PositionDependentMeasurementModel : public AdaptiveMeasurementModel {
 public:

@@ -451,9 +451,8 @@ public:
                                                 int stepLayer = 1) const override;
     std::shared_ptr<Patch> extract(int layer, int x, int y) const override;
     // not in the reference: extract(x, y, width, height) for every sample {x - width / 2, y - height / 2, width, height} at once,
-    // null for a sample without a window.  One device call (fd_hist_extract_samples / fd_ehog_extract_samples) when the patch filter
-    // is one histogram filter or one ExtendedHogFilter (the hog, lbp, glbp and ehog feature types), one fd_patch_extract_samples for a
-    // sampled gray-patch chain (below: the grayscale, h and whi feature types); the per-sample path otherwise.
+    // null for a sample without a window.  One device call (SampledChain::extract) when the extractor has a sampled chain (below: the
+    // hog, lbp, glbp and ehog feature types, and the grayscale, h and whi feature types); the per-sample path otherwise.
     // The patch geometry is the one extractFromLayer computes.
     std::vector<std::shared_ptr<Patch>> extract(const std::vector<cv::Rect>& samples) const;
     // the parameters of that device call: kind FD_SAMPLES_HIST (hp) or FD_SAMPLES_EHOG (ep); false: no such chain
@@ -692,6 +691,44 @@ private:
     std::vector<const FeatureExtractor*> chain;
 };
 
+// Not in the reference: which batched device call serves the samples {x, y, width, height} of an extractor, answered once
+// (sampledChainOf) for every model that asks.  A DirectPyramidFeatureExtractor resolves when it is the extractor itself, not wrapped
+// (getSampledChain: Hist, Ehog; getSampledPatchChain: Patch); a DirectImageFeatureExtractor resolves through its wrappers, in the
+// precedence getHaarChain, getSurfChain, getIntegralHogChain.  Resolving asks no device; ready() does.
+class HaarFeatureFilter;
+class DirectImageFeatureExtractor;
+struct SampledChain {
+    enum class Kind { None, Hist, Ehog, Patch, Haar, Surf, IntegralHog };
+    explicit SampledChain(const FeatureExtractor* extractor) : wrappers(extractor) {}
+    Kind kind = Kind::None;
+    fd_hist_params hist{};                     // Hist
+    fd_ehog_patch_params ehog{};               // Ehog
+    fd_patch_samples_params patch{};           // Patch
+    std::shared_ptr<HaarFeatureFilter> haar;   // Haar: fd_haar_params points into the filter
+    fd_surf_params surf{};                     // Surf
+    fd_integral_hog_params ihog{};             // IntegralHog
+    ExtractorWrappers wrappers;                // the wrappers it walked; their inner extractor is one of these two, or neither
+    const DirectPyramidFeatureExtractor* pyramid = nullptr;
+    const DirectImageFeatureExtractor* image = nullptr;
+    bool onPyramid() const { return kind == Kind::Hist || kind == Kind::Ehog || kind == Kind::Patch; }
+    bool ready() const;   // the device object of the calls exists: a pyramid kind always, an integral kind after the first update
+    bool extractable() const { return onPyramid() || (kind == Kind::IntegralHog && ready()); }   // the kinds extract and hasWindow serve
+    int featureLength(int channels) const;   // floats per sample on layers of `channels` channels; negative: invalid, or Haar / Surf
+    int matRows() const;                     // of a sample's Mat: cell rows for an ExtendedHogFilter, the patch height for a gray patch, else 1
+    // floats per cell where the reference's Mat carries them as channels: those of the inner extractor's ExtendedHogFilter (also behind
+    // wrappers, or on layers the sampled calls do not serve), 1 for everything else
+    int cellChannels() const;
+    // The device conversations, on samples as the outermost extractor receives them.  extract: the patch data of every sample in one
+    // fd_hist_ / fd_ehog_ / fd_patch_extract_samples or fd_integral_extract_hog, each Mat as extract(x, y, width, height)->getData()
+    // gives it, empty where that returns null.  svmEvaluate: one fd_hist_ / fd_patch_ / fd_integral_svm_evaluate_samples.  hasWindow:
+    // whether extract(x, y, width, height) would return a patch, by the rule of the kernels on the host
+    std::vector<cv::Mat> extract(const std::vector<int32_t>& xywh) const;
+    void svmEvaluate(const fd_svm* svm, const std::vector<int32_t>& xywh, uint8_t* target, double* weight) const;
+    bool hasWindow(int x, int y, int width, int height) const;
+    std::vector<int32_t> mapped(const std::vector<int32_t>& xywh) const;   // the samples of an integral kind behind the wrappers' maps
+};
+SampledChain sampledChainOf(const FeatureExtractor* extractor);
+
 // ---- the integral-image family: image filters GrayscaleFilter -> IntegralImageFilter of a DirectImageFeatureExtractor, patch filters
 // that are a handful of rectangle sums (the "haar" and "surf" feature types of BenchmarkRunner.cpp:202-233,278-286)
 // IntegralImageFilter.hpp / IntegralImageFilter.cpp:16-21 (cv::integral): CV_8UC1 -> CV_32SC1, one row and column larger
@@ -800,9 +837,6 @@ public:
         const auto& f = patchFilter->getFilters();
         return f.empty() ? nullptr : std::dynamic_pointer_cast<ExtendedHogFilter>(f.back());
     }
-    // not in the reference: the patch data of n samples {x, y, width, height} of an integral HOG chain in one fd_integral_extract_hog,
-    // each as extract(x, y, width, height)->getData() gives it; an empty Mat where extract returns null
-    std::vector<cv::Mat> extractIntegralHog(const fd_integral_hog_params& hp, const std::vector<int32_t>& xywh) const;
 private:
     const cv::Mat& hostImage() const;
     Version version;

@@ -779,24 +779,6 @@ bool DirectImageFeatureExtractor::getIntegralHogChain(fd_integral_hog_params& hp
     }
     return fd_integral_hog_feature_length(&hp) > 0;   // anything the fused call refuses stays on the per-Mat composition
 }
-vector<Mat> DirectImageFeatureExtractor::extractIntegralHog(const fd_integral_hog_params& hp, const vector<int32_t>& xywh) const {
-    const int n = (int)(xywh.size() / 4), F = fd_integral_hog_feature_length(&hp);
-    vector<Mat> data((size_t)n);
-    if (n == 0) return data;
-    if (!native() || F <= 0) throw std::logic_error("DirectImageFeatureExtractor: extractIntegralHog needs an updated integral image and an integral HOG chain");
-    vector<float> rows((size_t)n * F);
-    vector<uint8_t> valid((size_t)n);
-    check(fd_integral_extract_hog(context(), integral, &hp, n, xywh.data(), rows.data(), valid.data()));
-    // ExtendedHogFilter::applyTo gives cell rows x (cell columns * channels), the histogram filters 1 x F
-    const int matRows = hp.kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(hp.grad_rows) / static_cast<double>(hp.ehog.cell_h > 0 ? hp.ehog.cell_h : hp.ehog.cell_w)) : 1;
-    for (int i = 0; i < n; ++i) {
-        if (!valid[i]) continue;
-        Mat m(matRows, F / matRows, CV_32FC1);
-        std::memcpy(m.ptr<float>(0), rows.data() + (size_t)i * F, sizeof(float) * (size_t)F);
-        data[i] = m;
-    }
-    return data;
-}
 
 namespace filtering {
 FhogFilter::FhogFilter(int cellSize, int unsignedBinCount, bool interpolateBins, bool interpolateCells, float alpha)
@@ -940,12 +922,8 @@ bool DirectPyramidFeatureExtractor::getSampledPatchChain(fd_patch_samples_params
 }
 vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv::Rect>& samples) const {
     vector<shared_ptr<Patch>> patches(samples.size());
-    int kind = 0;
-    fd_hist_params hp;
-    fd_ehog_patch_params ep;
-    fd_patch_samples_params pp;
-    const bool grayPatches = getSampledPatchChain(pp);
-    if (!grayPatches && !getSampledChain(kind, hp, ep)) {   // the per-sample path
+    const SampledChain chain = sampledChainOf(this);
+    if (!chain.onPyramid()) {   // the per-sample path
         for (size_t i = 0; i < samples.size(); ++i)
             patches[i] = extract(samples[i].x + samples[i].width / 2, samples[i].y + samples[i].height / 2, samples[i].width, samples[i].height);
         return patches;
@@ -958,32 +936,113 @@ vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv
         xywh[4 * i] = samples[i].x + samples[i].width / 2; xywh[4 * i + 1] = samples[i].y + samples[i].height / 2;
         xywh[4 * i + 2] = samples[i].width; xywh[4 * i + 3] = samples[i].height;
     }
-    int index, lw, lh, ch = 1; double scale;
-    if (fd_pyramid_layer_count(pyramid->native()) > 0) fd_pyramid_layer_info(pyramid->native(), 0, &index, &scale, &lw, &lh, &ch);
-    const int F = grayPatches ? fd_patch_feature_length(&pp) : (kind == FD_SAMPLES_EHOG ? fd_ehog_feature_length(&ep, ch) : fd_hist_feature_length(&hp, ch));
-    if (F < 0) throw std::invalid_argument("DirectPyramidFeatureExtractor: invalid histogram filter parameters for this patch size");
-    Mat all(n, F, CV_32FC1);
-    vector<uint8_t> valid((size_t)n);
-    if (grayPatches) check(fd_patch_extract_samples(context(), pyramid->native(), &pp, n, xywh.data(), valid.data(), all.ptr<float>(0)));
-    else if (kind == FD_SAMPLES_EHOG) check(fd_ehog_extract_samples(context(), pyramid->native(), &ep, n, xywh.data(), valid.data(), all.ptr<float>(0)));
-    else check(fd_hist_extract_samples(context(), pyramid->native(), &hp, n, xywh.data(), valid.data(), all.ptr<float>(0)));
+    const vector<Mat> data = chain.extract(xywh);
     check(fd_pyramid_sample_windows(pyramid->native(), patchWidth, patchHeight, n, xywh.data(), windows.data()));
-    const int ehogRows = grayPatches ? patchHeight : kind == FD_SAMPLES_EHOG ? cv::cvRound(static_cast<double>(patchHeight) / static_cast<double>(ehog->cellHeight)) : 1;
     for (int i = 0; i < n; ++i) {
-        if (!valid[i]) continue;
+        if (data[i].empty()) continue;
+        int index, lw, lh, ch; double scale;
         fd_pyramid_layer_info(pyramid->native(), windows[4 * i], &index, &scale, &lw, &lh, &ch);
         // extractFromLayer's geometry (ImagePyramidLayer::getOriginal)
         const int ow = cv::cvRound(patchWidth / scale), oh = cv::cvRound(patchHeight / scale);
         const int ox = cv::cvRound(windows[4 * i + 1] / scale) + ow / 2, oy = cv::cvRound(windows[4 * i + 2] / scale) + oh / 2;
-        Mat row = Mat(all, cv::Rect(0, i, F, 1)).clone();
-        if (grayPatches || kind == FD_SAMPLES_EHOG) {   // rows x cols * channels, as ExtendedHogFilter::applyTo stores it; a gray patch keeps its shape
-            Mat shaped(ehogRows, F / ehogRows, CV_32FC1);
-            std::memcpy(shaped.data, row.data, sizeof(float) * (size_t)F);
-            row = shaped;
-        }
-        patches[i] = make_shared<Patch>(ox, oy, ow, oh, row);
+        patches[i] = make_shared<Patch>(ox, oy, ow, oh, data[i]);
     }
     return patches;
+}
+
+// ---- SampledChain ---------------------------------------------------------------------------------
+SampledChain sampledChainOf(const FeatureExtractor* extractor) {
+    using Kind = SampledChain::Kind;
+    SampledChain c(extractor);
+    c.pyramid = dynamic_cast<const DirectPyramidFeatureExtractor*>(c.wrappers.inner());
+    c.image = dynamic_cast<const DirectImageFeatureExtractor*>(c.wrappers.inner());
+    int kind = 0, gradientCount = 0, cellCount = 0;
+    if (c.pyramid && !c.wrappers.wrapped()) {   // the extractor itself: a wrapper's map moves the sample off the layer rule
+        if (c.pyramid->getSampledChain(kind, c.hist, c.ehog)) c.kind = kind == FD_SAMPLES_EHOG ? Kind::Ehog : Kind::Hist;
+        else if (c.pyramid->getSampledPatchChain(c.patch)) c.kind = Kind::Patch;
+    } else if (c.image) {
+        if ((c.haar = c.image->getHaarChain())) c.kind = Kind::Haar;
+        else if (c.image->getSurfChain(gradientCount, cellCount) && gradientCount > 0) { c.surf = fd_surf_params{gradientCount, cellCount}; c.kind = Kind::Surf; }
+        else if (c.image->getIntegralHogChain(c.ihog)) c.kind = Kind::IntegralHog;
+    }
+    return c;
+}
+bool SampledChain::ready() const { return onPyramid() || (kind != Kind::None && image->native()); }
+int SampledChain::featureLength(int channels) const {
+    return kind == Kind::Hist ? fd_hist_feature_length(&hist, channels) : kind == Kind::Ehog ? fd_ehog_feature_length(&ehog, channels) :
+           kind == Kind::Patch ? fd_patch_feature_length(&patch) : kind == Kind::IntegralHog ? fd_integral_hog_feature_length(&ihog) : -1;
+}
+int SampledChain::matRows() const {
+    // ExtendedHogFilter::applyTo gives cell rows x (cell columns * channels), the histogram filters 1 x F; a gray patch keeps its shape
+    const fd_ehog_patch_params* e = kind == Kind::Ehog ? &ehog : (kind == Kind::IntegralHog && ihog.kind == FD_SAMPLES_EHOG ? &ihog.ehog : nullptr);
+    if (e) return cv::cvRound(static_cast<double>(e->patch_h) / static_cast<double>(e->cell_h > 0 ? e->cell_h : e->cell_w));
+    return kind == Kind::Patch ? patch.patch_h : 1;
+}
+int SampledChain::cellChannels() const {
+    const shared_ptr<ExtendedHogFilter> f = pyramid ? pyramid->getExtendedHogFilter() : (image ? image->getExtendedHogFilter() : nullptr);
+    return f ? f->binCount + (f->signedAndUnsigned ? f->binCount / 2 : 0) + 4 : 1;
+}
+vector<int32_t> SampledChain::mapped(const vector<int32_t>& xywh) const {
+    vector<int32_t> m = onPyramid() ? vector<int32_t>() : xywh;   // the pyramid kinds take the samples as they are
+    for (size_t i = 0; i + 4 <= m.size(); i += 4) wrappers.map(m.data() + i);
+    return m;
+}
+vector<Mat> SampledChain::extract(const vector<int32_t>& xywh) const {
+    const int n = (int)(xywh.size() / 4);
+    vector<Mat> data((size_t)n);
+    if (n == 0) return data;
+    fd_pyramid* native = onPyramid() ? pyramid->getPyramid()->native() : nullptr;
+    int index, lw, lh, ch = 1; double scale;
+    if (native && fd_pyramid_layer_count(native) > 0) fd_pyramid_layer_info(native, 0, &index, &scale, &lw, &lh, &ch);
+    const int F = featureLength(ch);
+    if (native && F < 0) throw std::invalid_argument("DirectPyramidFeatureExtractor: invalid histogram filter parameters for this patch size");
+    if (!native && (kind != Kind::IntegralHog || !ready() || F <= 0))
+        throw std::logic_error("DirectImageFeatureExtractor: extractIntegralHog needs an updated integral image and an integral HOG chain");
+    const vector<int32_t> m = mapped(xywh);
+    vector<float> rows((size_t)n * F);
+    vector<uint8_t> valid((size_t)n);
+    if (kind == Kind::Patch) check(fd_patch_extract_samples(context(), native, &patch, n, xywh.data(), valid.data(), rows.data()));
+    else if (kind == Kind::Ehog) check(fd_ehog_extract_samples(context(), native, &ehog, n, xywh.data(), valid.data(), rows.data()));
+    else if (kind == Kind::Hist) check(fd_hist_extract_samples(context(), native, &hist, n, xywh.data(), valid.data(), rows.data()));
+    else check(fd_integral_extract_hog(context(), image->native(), &ihog, n, m.data(), rows.data(), valid.data()));
+    const int r = matRows();
+    for (int i = 0; i < n; ++i) {
+        if (!valid[i]) continue;
+        data[i] = Mat(r, F / r, CV_32FC1);
+        std::memcpy(data[i].ptr<float>(0), rows.data() + (size_t)i * F, sizeof(float) * (size_t)F);
+    }
+    return data;
+}
+void SampledChain::svmEvaluate(const fd_svm* svm, const vector<int32_t>& xywh, uint8_t* target, double* weight) const {
+    const int n = (int)(xywh.size() / 4);
+    if (kind == Kind::Patch) {
+        check(fd_patch_svm_evaluate_samples(context(), pyramid->getPyramid()->native(), &patch, svm, n, xywh.data(), target, weight, nullptr));
+    } else if (onPyramid()) {
+        check(fd_hist_svm_evaluate_samples(context(), pyramid->getPyramid()->native(), kind == Kind::Ehog ? FD_SAMPLES_EHOG : FD_SAMPLES_HIST,
+                                           kind == Kind::Ehog ? (const void*)&ehog : (const void*)&hist, svm, n, xywh.data(), target, weight));
+    } else {   // the wrappers are integer maps of the sample, applied here
+        fd_haar_params hp;
+        if (haar) hp = haar->params();
+        const int integralKind = haar ? (int)FD_INTEGRAL_HAAR : (kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
+        const void* prm = haar ? (const void*)&hp : (kind == Kind::IntegralHog ? (const void*)&ihog : (const void*)&surf);
+        check(fd_integral_svm_evaluate_samples(context(), image->native(), integralKind, prm, svm, n, mapped(xywh).data(), target, weight));
+    }
+}
+bool SampledChain::hasWindow(int x, int y, int width, int height) const {
+    int32_t s[4] = {x, y, width, height};
+    if (onPyramid()) {   // the extractor's rule
+        int32_t w[4];
+        check(fd_pyramid_sample_windows(pyramid->getPyramid()->native(), pyramid->getPatchWidth(), pyramid->getPatchHeight(), 1, s, w));
+        return w[3] != 0;
+    }
+    if (kind != Kind::IntegralHog) throw std::logic_error("SampledChain: hasWindow serves the pyramid kinds and integral HOG");
+    wrappers.map(s);   // the rule of the kernels on the mapped sample
+    int iw = 0, ih = 0;
+    check(fd_integral_size(image->native(), &iw, &ih));
+    uint8_t valid = 0;
+    if (fd_integral_gradient_samples_valid(iw - 1, ih - 1, ihog.grad_rows, ihog.grad_cols, 1, s, &valid) != FD_OK)
+        throw std::invalid_argument("PositionDependentMeasurementModel: the integral image has no size");
+    return valid != 0;
 }
 shared_ptr<Patch> DirectPyramidFeatureExtractor::extract(int layerIndex, int x, int y) const {
     auto layer = pyramid->getLayer(layerIndex);
@@ -2763,49 +2822,23 @@ void SingleClassifierModel::evaluate(Sample& sample) const {
         sample.setWeight(0);
     }
 }
+SampledClassifier sampledClassifierOf(classification::ProbabilisticClassifier* classifier) {
+    auto* psvm = dynamic_cast<classification::ProbabilisticSvmClassifier*>(classifier);
+    if (!psvm)
+        if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier)) psvm = trainable->getProbabilisticSvm().get();
+    return SampledClassifier{detection::hasF32SupportVectors(psvm) ? psvm : nullptr, dynamic_cast<classification::ProbabilisticRvmClassifier*>(classifier)};
+}
+SampledRoute sampledRoute(const imageprocessing::SampledChain& chain, const SampledClassifier& classifier) {
+    if (chain.kind == imageprocessing::SampledChain::Kind::None) return SampledRoute::Loop;
+    if (classifier.svm) return SampledRoute::Svm;
+    return chain.kind == imageprocessing::SampledChain::Kind::Patch && classifier.rvm ? SampledRoute::PatchRvm : SampledRoute::Loop;
+}
 void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
     update(image);
-    // the integral chains (haar, surf, ihog / iehog), also behind PatchResizingFeatureExtractor / IntegralFeatureExtractor wrappers: the
-    // wrappers are integer maps of the sample, applied here, and the features of all samples come from one device call
-    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
-    auto* direct = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
-    auto* psvm = dynamic_cast<classification::ProbabilisticSvmClassifier*>(classifier.get());
-    if (direct && !psvm)
-        if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
-    shared_ptr<imageprocessing::HaarFeatureFilter> haar;
-    fd_surf_params surf = {0, 0};
-    fd_integral_hog_params ihog;
-    bool integralHog = false;
-    bool fused = direct && direct->native() && detection::hasF32SupportVectors(psvm);
-    if (fused) {
-        haar = direct->getHaarChain();
-        int g = 0, c = 0;
-        if (!haar && direct->getSurfChain(g, c)) { surf.gradient_count = g; surf.cell_count = c; }
-        if (!haar && surf.gradient_count == 0) integralHog = direct->getIntegralHogChain(ihog);
-        fused = haar || surf.gradient_count > 0 || integralHog;
-    }
-    // sampled pyramid windows: a native DirectPyramidFeatureExtractor (not wrapped) on a histogram or extended-HOG chain with a
-    // ProbabilisticSvmClassifier or a TrainableProbabilisticSvmClassifier on f32 vectors: one fd_hist_svm_evaluate_samples
-    auto* pyramidDirect = fused ? nullptr : dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
-    int sampledKind = 0;
-    fd_hist_params histParams;
-    fd_ehog_patch_params ehogParams;
-    fd_patch_samples_params patchParams;
-    bool grayPatches = false;
-    classification::ProbabilisticRvmClassifier* prvm = nullptr;
-    if (pyramidDirect) {
-        if (!psvm)
-            if (auto* trainable = dynamic_cast<classification::TrainableProbabilisticSvmClassifier*>(classifier.get())) psvm = trainable->getProbabilisticSvm().get();
-        fused = detection::hasF32SupportVectors(psvm) && pyramidDirect->getSampledChain(sampledKind, histParams, ehogParams);
-        // ... or on a sampled gray-patch chain (the grayscale, h and whi feature types) with such an SVM classifier or a
-        // ProbabilisticRvmClassifier: one fd_patch_svm_evaluate_samples / fd_patch_rvm_evaluate_samples
-        if (!fused && pyramidDirect->getSampledPatchChain(patchParams)) {
-            prvm = dynamic_cast<classification::ProbabilisticRvmClassifier*>(classifier.get());
-            fused = grayPatches = prvm || detection::hasF32SupportVectors(psvm);
-        }
-        if (!fused) pyramidDirect = nullptr;
-    }
-    if (!fused) {   // MeasurementModel.hpp: the per-sample loop
+    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(featureExtractor.get());
+    const SampledClassifier scorer = sampledClassifierOf(classifier.get());
+    const SampledRoute route = chain.ready() ? sampledRoute(chain, scorer) : SampledRoute::Loop;
+    if (route == SampledRoute::Loop) {   // MeasurementModel.hpp: the per-sample loop
         ++loopEvaluations;
         for (shared_ptr<Sample> sample : samples) evaluate(*sample);
         return;
@@ -2813,39 +2846,22 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     ++fusedEvaluations;
     const int n = (int)samples.size();
     if (n == 0) return;
-    vector<int32_t> xywh = pack_samples(samples);
-    if (!pyramidDirect)
-        for (int i = 0; i < n; ++i) wrappers.map(xywh.data() + 4 * (size_t)i);
+    const vector<int32_t> xywh = pack_samples(samples);
     vector<uint8_t> target((size_t)n);
     vector<double> weight((size_t)n);
-    if (grayPatches && prvm) {   // level and distance from the device, verdict and probability by the classifier's own getProbability
+    if (route == SampledRoute::PatchRvm) {   // level and distance from the device, verdict and probability by the classifier's own getProbability
         vector<uint8_t> valid((size_t)n);
         vector<int32_t> level((size_t)n);
         vector<double> distance((size_t)n);
-        check(fd_patch_rvm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), &patchParams, prvm->getRvm()->distanceModel(), n, xywh.data(),
+        check(fd_patch_rvm_evaluate_samples(context(), chain.pyramid->getPyramid()->native(), &chain.patch, scorer.rvm->getRvm()->distanceModel(), n, xywh.data(),
                                             valid.data(), level.data(), distance.data(), nullptr));
         for (int i = 0; i < n; ++i) {
-            const std::pair<bool, double> result = valid[i] ? prvm->getProbability(std::make_pair((int)level[i], distance[i])) : std::make_pair(false, 0.0);
+            const std::pair<bool, double> result = valid[i] ? scorer.rvm->getProbability(std::make_pair((int)level[i], distance[i])) : std::make_pair(false, 0.0);
             target[i] = result.first ? 1 : 0;
             weight[i] = result.second;
         }
-        unpack_samples(target, weight, samples);
-        return;
-    }
-    const fd_svm* svm = psvm->getSvm()->native(psvm->getLogisticA(), psvm->getLogisticB());
-    if (grayPatches) {
-        check(fd_patch_svm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), &patchParams, svm, n, xywh.data(), target.data(), weight.data(),
-                                            nullptr));
-    } else if (pyramidDirect) {
-        check(fd_hist_svm_evaluate_samples(context(), pyramidDirect->getPyramid()->native(), sampledKind,
-                                           sampledKind == FD_SAMPLES_EHOG ? (const void*)&ehogParams : (const void*)&histParams, svm, n, xywh.data(),
-                                           target.data(), weight.data()));
     } else {
-        fd_haar_params hp;
-        if (haar) hp = haar->params();
-        const int kind = haar ? (int)FD_INTEGRAL_HAAR : (integralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
-        const void* prm = haar ? (const void*)&hp : (integralHog ? (const void*)&ihog : (const void*)&surf);
-        check(fd_integral_svm_evaluate_samples(context(), direct->native(), kind, prm, svm, n, xywh.data(), target.data(), weight.data()));
+        chain.svmEvaluate(scorer.svm->getSvm()->native(scorer.svm->getLogisticA(), scorer.svm->getLogisticB()), xywh, target.data(), weight.data());
     }
     unpack_samples(target, weight, samples);
 }
@@ -2863,17 +2879,16 @@ static const classification::RvmClassifier* rvm_of(const classification::BinaryC
 static bool rvm_classify_samples(const imageprocessing::FeatureExtractor* extractor, const classification::BinaryClassifier* classifier,
                                  const vector<int32_t>& xywh, vector<char>& verdict) {
     const classification::RvmClassifier* rvm = rvm_of(classifier);
-    auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor);
-    fd_patch_samples_params pp;
-    if (!rvm || !direct || !direct->getSampledPatchChain(pp)) return false;
+    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(extractor);
+    if (!rvm || chain.kind != imageprocessing::SampledChain::Kind::Patch) return false;
     const int n = (int)(xywh.size() / 4);
     verdict.assign((size_t)n, 0);
     if (n == 0) return true;
     vector<uint8_t> valid((size_t)n);
     vector<int32_t> level((size_t)n);
     vector<double> distance((size_t)n);
-    check(fd_patch_rvm_evaluate_samples(context(), direct->getPyramid()->native(), &pp, rvm->distanceModel(), n, xywh.data(), valid.data(), level.data(),
-                                        distance.data(), nullptr));
+    check(fd_patch_rvm_evaluate_samples(context(), chain.pyramid->getPyramid()->native(), &chain.patch, rvm->distanceModel(), n, xywh.data(), valid.data(),
+                                        level.data(), distance.data(), nullptr));
     for (int i = 0; i < n; ++i) verdict[i] = valid[i] && rvm->classify(std::make_pair((int)level[i], distance[i])) ? 1 : 0;
     return true;
 }
@@ -3009,60 +3024,18 @@ Sample PositionDependentMeasurementModel::createRandomSample(const Mat& image) {
     return Sample(x, y, size);
 }
 bool PositionDependentMeasurementModel::hasWindow(int x, int y, int width, int height) const {
-    auto* direct = dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
-    int kind;
-    fd_hist_params hp;
-    fd_ehog_patch_params ep;
-    fd_patch_samples_params pp;
-    if (direct && (direct->getSampledChain(kind, hp, ep) || direct->getSampledPatchChain(pp))) {   // the extractor's rule, on the host
-        const int32_t s[4] = {x, y, width, height};
-        int32_t w[4];
-        check(fd_pyramid_sample_windows(direct->getPyramid()->native(), direct->getPatchWidth(), direct->getPatchHeight(), 1, s, w));
-        return w[3] != 0;
-    }
-    // an integral HOG chain (ihog / iehog, also behind its wrappers): the rule of the kernels on the mapped sample, on the host
-    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
-    auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
-    fd_integral_hog_params ihog;
-    if (image && image->native() && image->getIntegralHogChain(ihog)) {
-        int32_t s[4] = {x, y, width, height};
-        wrappers.map(s);
-        int iw = 0, ih = 0;
-        check(fd_integral_size(image->native(), &iw, &ih));
-        uint8_t valid = 0;
-        if (fd_integral_gradient_samples_valid(iw - 1, ih - 1, ihog.grad_rows, ihog.grad_cols, 1, s, &valid) != FD_OK)
-            throw std::invalid_argument("PositionDependentMeasurementModel: the integral image has no size");
-        return valid != 0;
-    }
-    return (bool)featureExtractor->extract(x, y, width, height);
+    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(featureExtractor.get());
+    return chain.extractable() ? chain.hasWindow(x, y, width, height) : (bool)featureExtractor->extract(x, y, width, height);
 }
 vector<Mat> PositionDependentMeasurementModel::extractAll(const vector<Sample>& samples, bool square) const {
     vector<Mat> data;
     data.reserve(samples.size());
-    auto* direct = dynamic_cast<imageprocessing::DirectPyramidFeatureExtractor*>(featureExtractor.get());
-    if (direct) {   // one batched extract for the set (the per-sample path inside when the chain is not a sampled one)
-        vector<cv::Rect> rects;
-        rects.reserve(samples.size());
-        for (const Sample& s : samples) {
-            const int w = s.getWidth(), h = square ? s.getSize() : s.getHeight();
-            rects.push_back(cv::Rect(s.getX() - w / 2, s.getY() - h / 2, w, h));
-        }
-        for (const auto& patch : direct->extract(rects))
-            if (patch) data.push_back(patch->getData());
-        return data;
-    }
-    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
-    auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(wrappers.inner());
-    fd_integral_hog_params ihog;
-    if (image && image->native() && image->getIntegralHogChain(ihog)) {   // one fd_integral_extract_hog for the set
+    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(featureExtractor.get());
+    if (chain.extractable()) {   // one device call for the set
         vector<int32_t> xywh;
         xywh.reserve(4 * samples.size());
-        for (const Sample& s : samples) {
-            int32_t m[4] = {s.getX(), s.getY(), s.getWidth(), square ? s.getSize() : s.getHeight()};
-            wrappers.map(m);
-            xywh.insert(xywh.end(), m, m + 4);
-        }
-        for (const Mat& m : image->extractIntegralHog(ihog, xywh))
+        for (const Sample& s : samples) xywh.insert(xywh.end(), {s.getX(), s.getY(), s.getWidth(), square ? s.getSize() : s.getHeight()});
+        for (const Mat& m : chain.extract(xywh))
             if (!m.empty()) data.push_back(m);
         return data;
     }
@@ -3093,16 +3066,6 @@ vector<double> PositionDependentMeasurementModel::probabilities(const vector<Mat
     for (size_t i = 0; i < vectors.size(); ++i) p[i] = classifier->getProbability(vectors[i]).second;
     return p;
 }
-// floats per cell of an extractor's patch data where the reference's Mat would carry them as channels: the descriptor of the
-// ExtendedHogFilter of an ehog or iehog chain (also behind its wrapper extractors), 1 for everything else
-static int patch_channels(const imageprocessing::FeatureExtractor* extractor) {
-    extractor = imageprocessing::ExtractorWrappers(extractor).inner();
-    std::shared_ptr<imageprocessing::ExtendedHogFilter> f;
-    if (auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(extractor)) f = direct->getExtendedHogFilter();
-    else if (auto* image = dynamic_cast<const imageprocessing::DirectImageFeatureExtractor*>(extractor)) f = image->getExtendedHogFilter();
-    if (!f) return 1;
-    return f->binCount + (f->signedAndUnsigned ? f->binCount / 2 : 0) + 4;
-}
 // cv::flip(data, mirrored, 1) of a Mat whose columns are cells of `channels` floats: the cells of a row in reverse order, each as it is
 static Mat flip_cells(const Mat& data, int channels) {
     if (channels <= 1 || data.type() != CV_32FC1 || data.cols % channels != 0) {
@@ -3123,7 +3086,7 @@ vector<Mat> PositionDependentMeasurementModel::getFeatureVectors(const vector<Sa
     if (predicate != 0) p = probabilities(patches);
     vector<Mat> trainingExamples;
     trainingExamples.reserve(exploitSymmetry ? 2 * patches.size() : patches.size());
-    const int channels = exploitSymmetry ? patch_channels(featureExtractor.get()) : 1;
+    const int channels = exploitSymmetry ? imageprocessing::sampledChainOf(featureExtractor.get()).cellChannels() : 1;
     for (size_t i = 0; i < patches.size(); ++i) {
         if (predicate == 1 && !(p[i] < confidenceThreshold)) continue;
         if (predicate == 2 && !(p[i] > 1 - confidenceThreshold)) continue;
