@@ -156,6 +156,15 @@ class fd_flow_motion(C.Structure):
                 ("median_ratio", C.c_float), ("order", C.c_void_p)]
 
 
+class fd_flow_motion_info(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("n_valid", C.c_int32), ("n_correct", C.c_int32), ("median_x", C.c_float), ("median_y", C.c_float),
+                ("median_ratio", C.c_float)]
+
+
+class fd_sample_map(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("factor", C.c_double), ("x_offset", C.c_double), ("y_offset", C.c_double)]
+
+
 class fd_svm_train_problem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("d", C.c_int32), ("is_device", C.c_int32),
                 ("weights", C.c_void_p), ("bias", C.c_void_p), ("alpha", C.c_void_p)]
@@ -414,6 +423,17 @@ _SIGS = {
     "fd_debug_flow_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fd_flow_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "fd_flow_median": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(fd_flow_motion)]),
+    "fd_particles_create_unbound": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "fd_sample_maps_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "fd_particles_evaluate_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
+    "fd_particles_weigh_classifier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "fd_flow_track_fb_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "fd_flow_get_tracks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_debug_flow_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.POINTER(fd_flow_motion_info)]),
+    "fd_particles_sample_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "fd_particles_state_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_particles_info), C.POINTER(fd_flow_motion_info)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1438,9 +1458,17 @@ class Particles:
 
     def __init__(self, ctx, tracker, capacity):
         self.ctx = ctx
-        self.tracker = tracker   # must outlive the set
+        self.tracker = tracker   # must outlive the set; None: an unbound set (Particles.unbound)
         self.h = C.c_void_p()
-        ctx.check(lib().fd_particles_create(ctx.h, tracker.h, capacity, C.byref(self.h)))
+        if tracker is None:
+            ctx.check(lib().fd_particles_create_unbound(ctx.h, capacity, C.byref(self.h)))
+        else:
+            ctx.check(lib().fd_particles_create(ctx.h, tracker.h, capacity, C.byref(self.h)))
+
+    @classmethod
+    def unbound(cls, ctx, capacity):
+        """fd_particles_create_unbound: a set without a tracker, for evaluate_integral / weigh_classifier"""
+        return cls(ctx, None, capacity)
 
     def close(self):
         if self.h:
@@ -1504,16 +1532,77 @@ class Particles:
     def weigh(self, logistic_a, logistic_b, svm_threshold, mode, rejection_threshold):
         self.ctx.check(lib().fd_particles_weigh(self.ctx.h, self.h, logistic_a, logistic_b, svm_threshold, mode, rejection_threshold))
 
-    def state(self):
-        """fd_particles_state: the info as a dict; FdError (with .info) when a weight is negative or not finite"""
-        info = fd_particles_info()
-        rc = lib().fd_particles_state(self.ctx.h, self.h, C.byref(info))
+    def _state(self, rc, info):
         out = {name: getattr(info, name) for name, _ in fd_particles_info._fields_}
         if rc != FD_OK:
             e = FdError(rc, lib().fd_last_error(self.ctx.h).decode())
             e.info = out
             raise e
         return out
+
+    def state(self):
+        """fd_particles_state: the info as a dict; FdError (with .info) when a weight is negative or not finite"""
+        info = fd_particles_info()
+        return self._state(lib().fd_particles_state(self.ctx.h, self.h, C.byref(info)), info)
+
+    def evaluate_integral(self, integral, svm, aspect_ratio, maps=(), haar=None, surf=None, hog=None):
+        """fd_particles_evaluate_integral on an updated Integral: haar / surf / hog as Integral.svm_evaluate_samples takes them, maps a
+        sequence of ("resize", factor, x_offset, y_offset) and ("integral",) from the outermost wrapper in"""
+        kind, prm, _keep = _integral_kind(haar, surf, hog)
+        chain = sample_maps(maps)
+        self.ctx.check(lib().fd_particles_evaluate_integral(self.ctx.h, self.h, integral.h, kind, prm, svm.h, aspect_ratio, chain, len(chain)))
+
+    def weigh_classifier(self, logistic_a, logistic_b, threshold):
+        self.ctx.check(lib().fd_particles_weigh_classifier(self.ctx.h, self.h, logistic_a, logistic_b, threshold))
+
+    def sample_flow(self, flow, count, n_resampled, u, flow_diffusion, fallback_diffusion, fresh, first_fresh_cluster_id):
+        """fd_particles_sample_flow: sample() with the motion `flow` holds on the device and a block of draws for either transition"""
+        flow_diffusion = _c(np.asarray(flow_diffusion, np.float64).reshape(-1, 3), np.float64)
+        fallback_diffusion = _c(np.asarray(fallback_diffusion, np.float64).reshape(-1, 3), np.float64)
+        fresh = _c(np.asarray(fresh, np.int32).reshape(-1, 3), np.int32)
+        if len(flow_diffusion) < n_resampled or len(fallback_diffusion) < n_resampled or len(fresh) < count - n_resampled:
+            raise ValueError("too few draws")
+        self.ctx.check(lib().fd_particles_sample_flow(self.ctx.h, self.h, flow.h, count, n_resampled, u, _ptr(flow_diffusion), _ptr(fallback_diffusion),
+                                                      _ptr(fresh), first_fresh_cluster_id))
+
+    def state_flow(self, flow):
+        """fd_particles_state_flow: (info as state() gives it, the flow handle's motion as a dict) in one read-back"""
+        info, motion = fd_particles_info(), fd_flow_motion_info()
+        out = self._state(lib().fd_particles_state_flow(self.ctx.h, self.h, flow.h, C.byref(info), C.byref(motion)), info)
+        return out, _motion_dict(motion)
+
+
+FD_SAMPLE_MAP_RESIZE, FD_SAMPLE_MAP_INTEGRAL, FD_SAMPLE_MAPS_MAX = 0, 1, 4
+FD_FLOW_RESIDENT_MAX_POINTS = 1024
+
+
+def sample_maps(maps):
+    """an array of fd_sample_map from ("resize", factor[, x_offset[, y_offset]]) and ("integral",) entries, outer to inner"""
+    chain = (fd_sample_map * len(maps))()
+    for k, entry in enumerate(maps):
+        if entry[0] == "resize":
+            values = list(entry[1:]) + [0.0] * (4 - len(entry))
+            chain[k] = fd_sample_map(FD_SAMPLE_MAP_RESIZE, float(values[0]), float(values[1]), float(values[2]))
+        elif entry[0] == "integral":
+            chain[k] = fd_sample_map(FD_SAMPLE_MAP_INTEGRAL, 0.0, 0.0, 0.0)
+        else:
+            chain[k] = fd_sample_map(int(entry[0]), 0.0, 0.0, 0.0)   # an unknown kind, for the library to refuse
+    return chain
+
+
+def sample_maps_apply(maps, samples):
+    """fd_sample_maps_apply (host only): the mapped copy of samples int32 (n, 4) {x, y, width, height}"""
+    s = _c(samples, np.int32).reshape(-1, 4).copy()
+    chain = sample_maps(maps)
+    rc = lib().fd_sample_maps_apply(chain, len(chain), len(s), _ptr(s))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_sample_maps_apply")
+    return s
+
+
+def _motion_dict(m):
+    return dict(ok=bool(m.ok), n_valid=m.n_valid, n_correct=m.n_correct, median_x=np.float32(m.median_x), median_y=np.float32(m.median_y),
+                median_ratio=np.float32(m.median_ratio))
 
 
 FD_FLOW_MAX_POINTS, FD_FLOW_MAX_LEVELS = 16384, 8
@@ -1622,6 +1711,36 @@ class Flow:
         fst, bst = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
         self.ctx.check(lib().fd_flow_track_fb(self.ctx.h, self.h, _ptr(points), n, _ptr(fwd), _ptr(bwd), _ptr(fst), _ptr(bst)))
         return fwd, bwd, fst, bst
+
+    def track_fb_resident(self, points):
+        """fd_flow_track_fb_resident: queues both trackings and the median flow of the tracks; nothing comes back"""
+        points = _c(np.asarray(points, np.float32).reshape(-1, 2), np.float32)
+        self.ctx.check(lib().fd_flow_track_fb_resident(self.ctx.h, self.h, _ptr(points), len(points)))
+
+    def get_tracks(self):
+        """fd_flow_get_tracks: dict(fwd, bwd float32 (n, 2), fstatus, bstatus uint8 (n,), order int32 (n_valid,), n_valid, n_correct) of the
+        last resident track"""
+        cap = FD_FLOW_RESIDENT_MAX_POINTS
+        fwd, bwd = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        fst, bst, order = np.zeros(cap, np.uint8), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        n, nv, nc = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(lib().fd_flow_get_tracks(self.ctx.h, self.h, cap, C.byref(n), _ptr(fwd), _ptr(bwd), _ptr(fst), _ptr(bst), _ptr(order), C.byref(nv),
+                                                C.byref(nc)))
+        k = n.value
+        return dict(fwd=fwd[:k].copy(), bwd=bwd[:k].copy(), fstatus=fst[:k].copy(), bstatus=bst[:k].copy(), order=order[:nv.value].copy(),
+                    n_valid=nv.value, n_correct=nc.value)
+
+    def debug_motion(self, points, fwd, bwd, fstatus, bstatus):
+        """fd_debug_flow_motion: the median-flow kernel on the caller's arrays -> dict(ok, n_valid, n_correct, median_x, median_y,
+        median_ratio); the motion stays in the handle for Particles.sample_flow"""
+        points, fwd, bwd = (_c(np.asarray(a, np.float32).reshape(-1, 2), np.float32) for a in (points, fwd, bwd))
+        fstatus, bstatus = _c(fstatus, np.uint8).ravel(), _c(bstatus, np.uint8).ravel()
+        n = len(points)
+        if not (len(fwd) == len(bwd) == len(fstatus) == len(bstatus) == n):
+            raise ValueError("the arrays of the tracked points have one length")
+        m = fd_flow_motion_info()
+        self.ctx.check(lib().fd_debug_flow_motion(self.ctx.h, self.h, _ptr(points), _ptr(fwd), _ptr(bwd), _ptr(fstatus), _ptr(bstatus), n, C.byref(m)))
+        return _motion_dict(m)
 
     def level(self, level, previous=False):
         """fd_debug_flow_level: (image uint8 (ph, pw), derivatives int16 (ph, pw, 2)) of a stored level, border included"""
@@ -2634,6 +2753,19 @@ def gradient_sum_batch(ctx, grad2ch, cell_rows, cell_cols=None):
     return out
 
 
+def _integral_kind(haar=None, surf=None, hog=None, kind=None):
+    """(FD_INTEGRAL_* kind, pointer to its parameters, the object the pointer needs alive) of exactly one of haar, surf and hog"""
+    given = [k for k, v in (("haar", haar), ("surf", surf), ("hog", hog)) if v is not None]
+    if len(given) != 1 or (kind is not None and kind != given[0]):
+        raise ValueError("exactly one of haar, surf and hog (and kind, when given, names it)")
+    if haar is not None:
+        return INTEGRAL_HAAR, C.byref(haar.c), haar
+    if hog is not None:
+        return INTEGRAL_HOG, C.byref(hog), hog
+    sp = fd_surf_params(int(surf[0]), int(surf[1]))
+    return INTEGRAL_SURF, C.byref(sp), sp
+
+
 class Integral:
     """fd_integral: the integral image of a frame and the patch filters of a DirectImageFeatureExtractor on sampled windows.
     samples: (n, 4) {x, y, width, height}; every extraction returns (rows, valid bool[n])."""
@@ -2710,16 +2842,7 @@ class Integral:
         s = self._samples(samples)
         target = np.zeros(len(s), np.uint8)
         weight = np.zeros(len(s), np.float64)
-        given = [k for k, v in (("haar", haar), ("surf", surf), ("hog", hog)) if v is not None]
-        if len(given) != 1 or (kind is not None and kind != given[0]):
-            raise ValueError("exactly one of haar, surf and hog (and kind, when given, names it)")
-        if haar is not None:
-            kind, prm = INTEGRAL_HAAR, C.byref(haar.c)
-        elif hog is not None:
-            kind, prm = INTEGRAL_HOG, C.byref(hog)
-        else:
-            sp = fd_surf_params(int(surf[0]), int(surf[1]))
-            kind, prm = INTEGRAL_SURF, C.byref(sp)
+        kind, prm, _keep = _integral_kind(haar, surf, hog, kind)
         self.ctx.check(lib().fd_integral_svm_evaluate_samples(self.ctx.h, self.h, kind, prm, svm.h, len(s), _ptr(s), _ptr(target), _ptr(weight)))
         return target.astype(bool), weight
 

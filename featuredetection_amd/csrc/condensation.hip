@@ -2,7 +2,9 @@
 // samples as structure-of-arrays and the per-frame steps of ResamplingSampler(LowVarianceSampling, SimpleTransitionModel)
 // (ResamplingSampler.cpp:50-59, LowVarianceSampling.cpp:20-46, SimpleTransitionModel.cpp:25-44), of
 // ExtendedHogBasedMeasurementModel's weighting (.cpp:173-205) and of FilteringStateExtractor(WeightedMeanStateExtractor)
-// (WeightedMeanStateExtractor.cpp:23-62).  The scoring of the samples is the tracker's (ehog_tracker.hpp).  DESIGN.md 4.7.
+// (WeightedMeanStateExtractor.cpp:23-62).  The scoring of the samples is the tracker's (ehog_tracker.hpp).  A set without a tracker serves
+// SingleClassifierModel on the integral family (scored by integral.hip, weighed by k_particles_weigh's classifier mode) and
+// OpticalFlowTransitionModel::predict (k_particles_sample with the motion optflow.hip leaves on the device).  DESIGN.md 4.7.
 //
 // Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
 // needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
@@ -20,6 +22,7 @@ namespace {
 
 constexpr int PT = 256;                        // threads of the three kernels
 constexpr int32_t PARTICLE_NO_CLUSTER = INT32_MIN;   // the empty key of the cluster table
+constexpr int PARTICLES_CLASSIFIER = 3;        // k_particles_weigh as SingleClassifierModel: behind the FD_PARTICLES_* modes of fd_particles_weigh
 
 struct ParticleGen {
     int32_t *x, *y, *size, *vx, *vy;
@@ -35,11 +38,16 @@ __host__ __device__ inline bool particle_weight_ok(double w) { return w >= 0.0 &
 // cum[k]: the weights added up in index order, by one lane.  The forward walk of the reference (advance while pointer > sum) ends at
 // the smallest k with pointer <= cum[k] (weights are not negative, so cum does not decrease): every copy finds its k by bisection.
 // Where rounding leaves the last pointers above the total the walk stops at the last sample (the reference walks off the end).
+// With `motion` (OpticalFlowTransitionModel::predict, .cpp:173-190): where it is ok a copy's velocity is the median flow, moved by the
+// draws of `flowDiffusion`; otherwise the copy is moved as without a motion.  The branch is uniform over the launch.
 __global__ __launch_bounds__(PT) void k_particles_sample(ParticleGen src, ParticleGen dst, int nOld, int nCopies, int nFresh, double step, double start,
                                                          const double* __restrict__ diffusion, const int32_t* __restrict__ fresh, int32_t firstFreshId,
-                                                         int32_t* __restrict__ source, fd_particles_info* __restrict__ info) {
+                                                         int32_t* __restrict__ source, fd_particles_info* __restrict__ info,
+                                                         const fd_flow_motion_info* __restrict__ motion, const double* __restrict__ flowDiffusion) {
     extern __shared__ double cum[];
     const int tid = threadIdx.x;
+    const bool byFlow = motion && motion->ok;
+    if (byFlow) diffusion = flowDiffusion;
     if (nCopies > 0) {
         for (int i = tid; i < nOld; i += PT) cum[i] = src.weight[i];
         __syncthreads();
@@ -62,6 +70,7 @@ __global__ __launch_bounds__(PT) void k_particles_sample(ParticleGen src, Partic
         }
         const int k = lo;
         double vx = src.vx[k], vy = src.vy[k], vs = src.vsize[k];
+        if (byFlow) { vx = motion->median_x; vy = motion->median_y; vs = motion->median_ratio; }
         vx = vx + diffusion[3 * i];
         vy = vy + diffusion[3 * i + 1];
         vs = vs * diffusion[3 * i + 2];
@@ -93,6 +102,7 @@ __global__ __launch_bounds__(PT) void k_particles_sample(ParticleGen src, Partic
 
 // ExtendedHogBasedMeasurementModel::scored for every sample, ProbabilisticSvmClassifier::getProbability (.cpp:54-58) in double.  Two
 // passes: the first only looks for a product that is negative or not finite; with one, nothing is written but the flag.
+// mode PARTICLES_CLASSIFIER is SingleClassifierModel.cpp:32-42: the weight is the probability itself, target = score >= svmThreshold.
 __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, const uint8_t* __restrict__ valid, double logisticA, double logisticB,
                                                         double svmThreshold, int mode, double rejectionThreshold, fd_particles_info* __restrict__ info) {
     __shared__ double sBest[PT];
@@ -101,7 +111,7 @@ __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, co
     auto weighed = [&](int i) {
         const double fABp = logisticA + logisticB * g.score[i];
         const double p = fABp >= 0 ? exp(-fABp) / (1.0 + exp(-fABp)) : 1.0 / (1.0 + exp(fABp));
-        return g.weight[i] * p;
+        return mode == PARTICLES_CLASSIFIER ? p : g.weight[i] * p;
     };
     int bad = 0;
     for (int i = tid; i < n; i += PT)
@@ -121,7 +131,8 @@ __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, co
         } else {
             score = g.score[i];
             g.weight[i] = weighed(i);
-            g.target[i] = mode == FD_PARTICLES_TARGET_LOST ? score >= svmThreshold : (mode == FD_PARTICLES_SLIDING_WINDOW ? score > rejectionThreshold : 1);
+            g.target[i] = mode == FD_PARTICLES_TARGET_LOST || mode == PARTICLES_CLASSIFIER ? score >= svmThreshold
+                                                                                           : (mode == FD_PARTICLES_SLIDING_WINDOW ? score > rejectionThreshold : 1);
             ++nValid;
         }
         if (best < score) best = score;
@@ -249,16 +260,16 @@ int particle_state_slots(int n) {
 
 struct fd_particles {
     fd_ctx* ctx = nullptr;
-    fd_ehog_tracker* tracker = nullptr;
+    fd_ehog_tracker* tracker = nullptr;   // NULL: an unbound set (fd_particles_create_unbound)
     int capacity = 0, n = 0, cur = 0;
     bool sumKnown = true, bad = false, evaluated = false;
     double sum = 0.0;   // the weights of the current generation added in index order, when sumKnown
     DevBuf arena, staging, dinfo;
     ParticleGen gen[2];
     int32_t* source = nullptr;
-    int32_t* windows = nullptr;   // {layer, bx, by, valid} per sample, written by fd_particles_evaluate
+    int32_t* windows = nullptr;   // per sample {layer, bx, by, valid} of fd_particles_evaluate, or the mapped {x, y, width, height} of _evaluate_integral
     uint8_t* valid = nullptr;
-    HostBuf pinned;   // the draws of one fd_particles_sample on their way to the device
+    HostBuf pinned;   // the draws of one fd_particles_sample / _sample_flow on their way to the device
     hipEvent_t uploaded = nullptr;
     ~fd_particles() { if (uploaded) (void)hipEventDestroy(uploaded); }
 };
@@ -273,7 +284,8 @@ fd_particles* particles_checked(fd_ctx* ctx, fd_particles* p, const char* what) 
 }
 
 // state kernel + the read-back of the info; refreshes what the host knows about the generation
-void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out) {
+void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out, const fd_flow_motion_info* dmotion = nullptr,
+                          fd_flow_motion_info* motion = nullptr) {
     static uint64_t allowed = 0;
     const int slots = particle_state_slots(p->n);
     const size_t lds = sizeof(int32_t) * 2 * (size_t)slots;
@@ -281,10 +293,106 @@ void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out) 
     hipLaunchKernelGGL(k_particles_state, dim3(1), dim3(PT), lds, ctx->stream, p->gen[p->cur], p->n, slots, p->dinfo.as<fd_particles_info>());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, p->dinfo.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+    if (dmotion) HIP_CHECK(hipMemcpyAsync(motion, dmotion, sizeof(*motion), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     p->sum = out->weight_sum;
     p->sumKnown = true;
     p->bad = out->bad_weight != 0;
+}
+
+void particles_create(fd_ctx* ctx, fd_ehog_tracker* t, int capacity, fd_particles** out) {
+    if (capacity < 1 || capacity > FD_PARTICLES_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create: the capacity must be 1 .. %d", FD_PARTICLES_MAX);
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::unique_ptr<fd_particles> p(new fd_particles());
+    p->ctx = ctx;
+    p->tracker = t;
+    p->capacity = capacity;
+    const size_t N = (size_t)capacity;
+    // per generation: weight, score (8 N each), x, y, size, vx, vy, vsize, cluster (4 N each), target (N); then the window list (16 N), source (4 N) and valid (N)
+    const size_t perGen = (16 * N + 28 * N + N + 63) & ~(size_t)63;   // the doubles of the second generation stay aligned
+    p->arena.reserve(2 * perGen + 20 * N + N);
+    HIP_CHECK(hipMemset(p->arena.p, 0, 2 * perGen + 20 * N + N));
+    unsigned char* base = p->arena.as<unsigned char>();
+    for (int gi = 0; gi < 2; ++gi) {
+        unsigned char* b = base + perGen * gi;
+        ParticleGen& G = p->gen[gi];
+        G.weight = (double*)b; G.score = (double*)(b + 8 * N);
+        int32_t* q = (int32_t*)(b + 16 * N);
+        G.x = q; G.y = q + N; G.size = q + 2 * N; G.vx = q + 3 * N; G.vy = q + 4 * N; G.vsize = (float*)(q + 5 * N); G.cluster = q + 6 * N;
+        G.target = (uint8_t*)(q + 7 * N);
+    }
+    p->windows = (int32_t*)(base + 2 * perGen);   // 16-byte elements at a 64-byte boundary
+    p->source = (int32_t*)(base + 2 * perGen + 16 * N);
+    p->valid = (uint8_t*)(base + 2 * perGen + 20 * N);
+    p->staging.reserve(60 * N);   // two blocks of draws (24 N each) and the fresh samples (12 N)
+    p->pinned.reserve(60 * N);
+    p->dinfo.reserve(sizeof(fd_particles_info));
+    fd_particles_info zero;
+    std::memset(&zero, 0, sizeof(zero));
+    zero.best_score = -DBL_MAX;
+    HIP_CHECK(hipMemcpy(p->dinfo.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    HIP_CHECK(hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming));
+    *out = p.release();
+}
+
+// fd_particles_sample (flow NULL), and fd_particles_sample_flow: `diffusion` is then the fallback block
+void particles_sample(fd_ctx* ctx, fd_particles* p, const char* who, fd_flow* flow, int count, int n_resampled, double u, const double* flow_diffusion,
+                      const double* diffusion, const int32_t* fresh, int32_t first_fresh_cluster_id) {
+    particles_checked(ctx, p, who);
+    if (count < 0 || count > p->capacity) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d samples, the capacity is %d", who, count, p->capacity);
+    if (n_resampled < 0 || n_resampled > count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d of %d samples resampled", who, n_resampled, count);
+    const int nFresh = count - n_resampled;
+    if ((n_resampled > 0 && (!diffusion || (flow && !flow_diffusion))) || (nFresh > 0 && !fresh)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    if (nFresh > 0 && ((int64_t)first_fresh_cluster_id + nFresh - 1 > INT32_MAX || first_fresh_cluster_id == PARTICLE_NO_CLUSTER))
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the fresh cluster ids leave the int range", who);
+    const fd_flow_motion_info* dmotion = flow ? fd_flow_device_motion(ctx, flow, who) : nullptr;
+    if (!p->sumKnown) {   // weighed since the last read-back: ask the device for the sum the step is made of
+        fd_particles_info info;
+        particles_read_state(ctx, p, &info);
+    }
+    if (p->bad) FD_THROW(FD_ERR_RUNTIME, "%s: the generation holds a weight that is negative or not finite", who);
+    // LowVarianceSampling.cpp:22-26
+    int nCopies = 0;
+    double step = 0.0, start = 0.0;
+    if (p->n > 0 && n_resampled > 0) {
+        step = p->sum / (size_t)n_resampled;
+        if (step > 0) {
+            start = step * u;
+            nCopies = n_resampled;
+        }
+    }
+    // the draws: one pinned block, one copy
+    HIP_CHECK(hipEventSynchronize(p->uploaded));
+    unsigned char* pin = p->pinned.as<unsigned char>();
+    const size_t diffBytes = sizeof(double) * 3 * (size_t)nCopies, freshBytes = sizeof(int32_t) * 3 * (size_t)nFresh;
+    const size_t flowBytes = flow ? diffBytes : 0;
+    if (diffBytes) std::memcpy(pin, diffusion, diffBytes);
+    if (flowBytes) std::memcpy(pin + diffBytes, flow_diffusion, flowBytes);
+    if (freshBytes) std::memcpy(pin + diffBytes + flowBytes, fresh, freshBytes);
+    if (diffBytes + flowBytes + freshBytes) {
+        HIP_CHECK(hipMemcpyAsync(p->staging.p, pin, diffBytes + flowBytes + freshBytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipEventRecord(p->uploaded, ctx->stream));
+    }
+    const int next = p->cur ^ 1;
+    const unsigned char* staged = p->staging.as<unsigned char>();
+    hipLaunchKernelGGL(k_particles_sample, dim3(1), dim3(PT), nCopies > 0 ? sizeof(double) * (size_t)p->n : 0, ctx->stream, p->gen[p->cur], p->gen[next],
+                       p->n, nCopies, nFresh, step, start, (const double*)staged, (const int32_t*)(staged + diffBytes + flowBytes), first_fresh_cluster_id,
+                       p->source, p->dinfo.as<fd_particles_info>(), dmotion, (const double*)(staged + diffBytes));
+    HIP_CHECK(hipGetLastError());
+    p->cur = next;
+    p->n = nCopies + nFresh;
+    p->sum = (double)p->n;   // every new sample has weight 1: n times 1 added up is exact
+    p->sumKnown = true;
+    p->evaluated = false;
+}
+
+void particles_weigh(fd_ctx* ctx, fd_particles* p, const char* who, double logistic_a, double logistic_b, double svm_threshold, int mode,
+                     double rejection_threshold) {
+    if (!p->evaluated) FD_THROW(FD_ERR_RUNTIME, "%s: the generation has not been evaluated (fd_particles_evaluate, _evaluate_integral)", who);
+    hipLaunchKernelGGL(k_particles_weigh, dim3(1), dim3(PT), 0, ctx->stream, p->gen[p->cur], p->n, p->valid, logistic_a, logistic_b, svm_threshold, mode,
+                       rejection_threshold, p->dinfo.as<fd_particles_info>());
+    HIP_CHECK(hipGetLastError());
+    p->sumKnown = false;
 }
 
 }  // namespace
@@ -294,38 +402,14 @@ extern "C" {
 int fd_particles_create(fd_ctx* ctx, fd_ehog_tracker* t, int capacity, fd_particles** out) {
     return fd_guard(ctx, [&] {
         if (!ctx || !t || !out) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create: NULL argument");
-        if (capacity < 1 || capacity > FD_PARTICLES_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create: the capacity must be 1 .. %d", FD_PARTICLES_MAX);
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::unique_ptr<fd_particles> p(new fd_particles());
-        p->ctx = ctx;
-        p->tracker = t;
-        p->capacity = capacity;
-        const size_t N = (size_t)capacity;
-        // per generation: weight, score (8 N each), x, y, size, vx, vy, vsize, cluster (4 N each), target (N); then the window list (16 N), source (4 N) and valid (N)
-        const size_t perGen = (16 * N + 28 * N + N + 63) & ~(size_t)63;   // the doubles of the second generation stay aligned
-        p->arena.reserve(2 * perGen + 20 * N + N);
-        HIP_CHECK(hipMemset(p->arena.p, 0, 2 * perGen + 20 * N + N));
-        unsigned char* base = p->arena.as<unsigned char>();
-        for (int gi = 0; gi < 2; ++gi) {
-            unsigned char* b = base + perGen * gi;
-            ParticleGen& G = p->gen[gi];
-            G.weight = (double*)b; G.score = (double*)(b + 8 * N);
-            int32_t* q = (int32_t*)(b + 16 * N);
-            G.x = q; G.y = q + N; G.size = q + 2 * N; G.vx = q + 3 * N; G.vy = q + 4 * N; G.vsize = (float*)(q + 5 * N); G.cluster = q + 6 * N;
-            G.target = (uint8_t*)(q + 7 * N);
-        }
-        p->windows = (int32_t*)(base + 2 * perGen);   // 16-byte elements at a 64-byte boundary
-        p->source = (int32_t*)(base + 2 * perGen + 16 * N);
-        p->valid = (uint8_t*)(base + 2 * perGen + 20 * N);
-        p->staging.reserve(36 * N);
-        p->pinned.reserve(36 * N);
-        p->dinfo.reserve(sizeof(fd_particles_info));
-        fd_particles_info zero;
-        std::memset(&zero, 0, sizeof(zero));
-        zero.best_score = -DBL_MAX;
-        HIP_CHECK(hipMemcpy(p->dinfo.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
-        HIP_CHECK(hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming));
-        *out = p.release();
+        particles_create(ctx, t, capacity, out);
+    });
+}
+
+int fd_particles_create_unbound(fd_ctx* ctx, int capacity, fd_particles** out) {
+    return fd_guard(ctx, [&] {
+        if (!ctx || !out) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_create_unbound: NULL argument");
+        particles_create(ctx, nullptr, capacity, out);
     });
 }
 
@@ -416,54 +500,22 @@ int fd_particles_get_trace(fd_ctx* ctx, fd_particles* p, int32_t* source, int32_
 int fd_particles_sample(fd_ctx* ctx, fd_particles* p, int count, int n_resampled, double u, const double* diffusion, const int32_t* fresh,
                         int32_t first_fresh_cluster_id) {
     return fd_guard(ctx, [&] {
-        particles_checked(ctx, p, "fd_particles_sample");
-        if (count < 0 || count > p->capacity) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: %d samples, the capacity is %d", count, p->capacity);
-        if (n_resampled < 0 || n_resampled > count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: %d of %d samples resampled", n_resampled, count);
-        const int nFresh = count - n_resampled;
-        if ((n_resampled > 0 && !diffusion) || (nFresh > 0 && !fresh)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: NULL argument");
-        if (nFresh > 0 && ((int64_t)first_fresh_cluster_id + nFresh - 1 > INT32_MAX || first_fresh_cluster_id == PARTICLE_NO_CLUSTER))
-            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample: the fresh cluster ids leave the int range");
-        if (!p->sumKnown) {   // weighed since the last read-back: ask the device for the sum the step is made of
-            fd_particles_info info;
-            particles_read_state(ctx, p, &info);
-        }
-        if (p->bad) FD_THROW(FD_ERR_RUNTIME, "fd_particles_sample: the generation holds a weight that is negative or not finite");
-        // LowVarianceSampling.cpp:22-26
-        int nCopies = 0;
-        double step = 0.0, start = 0.0;
-        if (p->n > 0 && n_resampled > 0) {
-            step = p->sum / (size_t)n_resampled;
-            if (step > 0) {
-                start = step * u;
-                nCopies = n_resampled;
-            }
-        }
-        // the draws: one pinned block, one copy
-        HIP_CHECK(hipEventSynchronize(p->uploaded));
-        unsigned char* pin = p->pinned.as<unsigned char>();
-        const size_t diffBytes = sizeof(double) * 3 * (size_t)nCopies, freshBytes = sizeof(int32_t) * 3 * (size_t)nFresh;
-        if (diffBytes) std::memcpy(pin, diffusion, diffBytes);
-        if (freshBytes) std::memcpy(pin + diffBytes, fresh, freshBytes);
-        if (diffBytes + freshBytes) {
-            HIP_CHECK(hipMemcpyAsync(p->staging.p, pin, diffBytes + freshBytes, hipMemcpyHostToDevice, ctx->stream));
-            HIP_CHECK(hipEventRecord(p->uploaded, ctx->stream));
-        }
-        const int next = p->cur ^ 1;
-        hipLaunchKernelGGL(k_particles_sample, dim3(1), dim3(PT), nCopies > 0 ? sizeof(double) * (size_t)p->n : 0, ctx->stream, p->gen[p->cur], p->gen[next],
-                           p->n, nCopies, nFresh, step, start, p->staging.as<double>(), (const int32_t*)(p->staging.as<unsigned char>() + diffBytes),
-                           first_fresh_cluster_id, p->source, p->dinfo.as<fd_particles_info>());
-        HIP_CHECK(hipGetLastError());
-        p->cur = next;
-        p->n = nCopies + nFresh;
-        p->sum = (double)p->n;   // every new sample has weight 1: n times 1 added up is exact
-        p->sumKnown = true;
-        p->evaluated = false;
+        particles_sample(ctx, p, "fd_particles_sample", nullptr, count, n_resampled, u, nullptr, diffusion, fresh, first_fresh_cluster_id);
+    });
+}
+
+int fd_particles_sample_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, int count, int n_resampled, double u, const double* flow_diffusion,
+                             const double* fallback_diffusion, const int32_t* fresh, int32_t first_fresh_cluster_id) {
+    return fd_guard(ctx, [&] {
+        if (!flow) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_sample_flow: NULL argument");
+        particles_sample(ctx, p, "fd_particles_sample_flow", flow, count, n_resampled, u, flow_diffusion, fallback_diffusion, fresh, first_fresh_cluster_id);
     });
 }
 
 int fd_particles_evaluate(fd_ctx* ctx, fd_particles* p, int use_patches, double aspect_ratio) {
     return fd_guard(ctx, [&] {
         particles_checked(ctx, p, "fd_particles_evaluate");
+        if (!p->tracker) FD_THROW(FD_ERR_RUNTIME, "fd_particles_evaluate: the set is bound to no tracker (fd_particles_create_unbound)");
         const ParticleGen& G = p->gen[p->cur];
         fd_ehog_tracker_score_particles(ctx, p->tracker, p->n, G.x, G.y, G.size, aspect_ratio, use_patches != 0, p->windows, p->valid, G.score);
         p->evaluated = true;
@@ -475,11 +527,14 @@ int fd_particles_weigh(fd_ctx* ctx, fd_particles* p, double logistic_a, double l
         particles_checked(ctx, p, "fd_particles_weigh");
         if (mode != FD_PARTICLES_TARGET_LOST && mode != FD_PARTICLES_SLIDING_WINDOW && mode != FD_PARTICLES_ALL_TARGETS)
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_weigh: unknown mode %d", mode);
-        if (!p->evaluated) FD_THROW(FD_ERR_RUNTIME, "fd_particles_weigh: the generation has not been evaluated (fd_particles_evaluate)");
-        hipLaunchKernelGGL(k_particles_weigh, dim3(1), dim3(PT), 0, ctx->stream, p->gen[p->cur], p->n, p->valid, logistic_a, logistic_b, svm_threshold, mode,
-                           rejection_threshold, p->dinfo.as<fd_particles_info>());
-        HIP_CHECK(hipGetLastError());
-        p->sumKnown = false;
+        particles_weigh(ctx, p, "fd_particles_weigh", logistic_a, logistic_b, svm_threshold, mode, rejection_threshold);
+    });
+}
+
+int fd_particles_weigh_classifier(fd_ctx* ctx, fd_particles* p, double logistic_a, double logistic_b, double threshold) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_weigh_classifier");
+        particles_weigh(ctx, p, "fd_particles_weigh_classifier", logistic_a, logistic_b, threshold, PARTICLES_CLASSIFIER, 0.0);
     });
 }
 
@@ -492,4 +547,21 @@ int fd_particles_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out) {
     });
 }
 
+int fd_particles_state_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_particles_info* info, fd_flow_motion_info* motion) {
+    return fd_guard(ctx, [&] {
+        particles_checked(ctx, p, "fd_particles_state_flow");
+        if (!flow || !info || !motion) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_state_flow: NULL argument");
+        particles_read_state(ctx, p, info, fd_flow_device_motion(ctx, flow, "fd_particles_state_flow"), motion);
+        if (info->bad_weight) FD_THROW(FD_ERR_RUNTIME, "fd_particles_state_flow: the generation holds a weight that is negative or not finite");
+    });
+}
+
 }  // extern "C"
+
+FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who) {
+    particles_checked(ctx, p, who);
+    const ParticleGen& G = p->gen[p->cur];
+    return FdParticlesView{p->n, G.x, G.y, G.size, G.score, p->valid, p->windows};
+}
+
+void fd_particles_set_evaluated(fd_particles* p) { p->evaluated = true; }

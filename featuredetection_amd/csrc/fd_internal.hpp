@@ -646,6 +646,48 @@ void fd_svm_train_run(fd_ctx* ctx, const FdSvmRunSpec& spec, int count, const fd
 void fd_ehog_tracker_score_particles(fd_ctx* ctx, fd_ehog_tracker* t, int n, const int32_t* x, const int32_t* y, const int32_t* size, double aspect,
                                      int use_patches, int32_t* windows, uint8_t* valid, double* score);
 
+// ---------------- resident particle set on the integral family and the optical flow (condensation.hip, integral.hip, optflow.hip) ----------------
+// the current generation as the scoring kernels of another file need it (device memory); checks p against ctx.  Throws FdError.
+struct FdParticlesView {
+    int n;
+    const int32_t *x, *y, *size;
+    double* score;
+    uint8_t* valid;
+    int32_t* windows;   // 4 n ints: the trace of the evaluation
+};
+// one wrapper's map of a sample {x, y, width, height} (fd_sample_map, fd_hip.h): PatchResizingFeatureExtractor::mapSample and
+// IntegralFeatureExtractor::mapSample, the one copy of these expressions for the host (fd_sample_maps_apply) and the device
+// (k_particles_xywh).  cvRound is to the nearest even on a tie on both sides; the sums and products are doubles in this order.
+// A value outside the int range saturates and a NaN gives 0 on both sides (what the device's conversion does by itself).
+__host__ __device__ inline int fd_sample_cvround(double v) {
+    if (!(v == v)) return 0;
+    if (v >= 2147483647.0) return INT32_MAX;
+    if (v <= -2147483648.0) return INT32_MIN;
+#ifdef __HIP_DEVICE_COMPILE__
+    return __double2int_rn(v);
+#else
+    return fd_cvRound(v);
+#endif
+}
+__host__ __device__ inline void fd_sample_map_apply(const fd_sample_map& m, int32_t& x, int32_t& y, int32_t& width, int32_t& height) {
+    if (m.kind == FD_SAMPLE_MAP_RESIZE) {
+        x = fd_sample_cvround(x + m.x_offset * width);
+        y = fd_sample_cvround(y + m.y_offset * height);
+        width = fd_sample_cvround(m.factor * width);
+        height = fd_sample_cvround(m.factor * height);
+    } else {
+        x += width % 2 == 0 ? 0 : 1;
+        y += height % 2 == 0 ? 0 : 1;
+        width += 1;
+        height += 1;
+    }
+}
+FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who);
+void fd_particles_set_evaluated(fd_particles* p);
+// the motion a resident track (or fd_debug_flow_motion) left in the handle (device memory); checks flow against ctx, throws FdError
+// (FD_ERR_RUNTIME) when there is none
+const fd_flow_motion_info* fd_flow_device_motion(fd_ctx* ctx, fd_flow* flow, const char* who);
+
 // ---------------- host-side detection logic (hostalgo.cpp) ----------------
 void fd_host_overlap_elimination(const fd_detection* in, int n, float dist, float ratio, std::vector<int>& keep);
 void fd_host_block_nms_sparse(const std::vector<fd_detection>& pos, int imgW, int imgH, int sz, bool masked,

@@ -509,6 +509,18 @@ extern "C" int fd_surf_feature_length(int gradient_count, int cell_count) {
     return 4 * cell_count * cell_count;
 }
 
+// ---- the wrapper chain of a feature extractor on a list of samples, host only; the device's copy is k_particles_xywh (integral.hip) ----
+extern "C" int fd_sample_maps_apply(const fd_sample_map* maps, int n_maps, int n, int32_t* xywh) {
+    if (n_maps < 0 || n_maps > FD_SAMPLE_MAPS_MAX || n < 0 || (n_maps > 0 && !maps) || (n > 0 && !xywh)) return FD_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < n_maps; ++k)
+        if (maps[k].kind != FD_SAMPLE_MAP_RESIZE && maps[k].kind != FD_SAMPLE_MAP_INTEGRAL) return FD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; ++i) {
+        int32_t* s = xywh + 4 * (size_t)i;
+        for (int k = 0; k < n_maps; ++k) fd_sample_map_apply(maps[k], s[0], s[1], s[2], s[3]);
+    }
+    return FD_OK;
+}
+
 // ---- OpticalFlowTransitionModel's host arithmetic; the tracking itself is optflow.hip ----
 
 // OpticalFlowTransitionModel.cpp:63-75, operation for operation: gridPoint's first value is formed in double (0.5 * gridX is a double

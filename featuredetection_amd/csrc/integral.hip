@@ -259,6 +259,24 @@ __global__ __launch_bounds__(256) void k_surf(const int32_t* __restrict__ img, i
     }
 }
 
+// the samples of a resident particle set (x, y, size; height = cvRound(aspect * size), Sample.hpp:127-129) through the wrapper
+// chain of their feature extractor (outer to inner) into the sample list the kernels above read; `trace` keeps a copy for
+// fd_particles_get_trace
+struct SampleMaps {
+    int32_t n;
+    fd_sample_map m[FD_SAMPLE_MAPS_MAX];
+};
+__global__ __launch_bounds__(256) void k_particles_xywh(const int32_t* __restrict__ x, const int32_t* __restrict__ y, const int32_t* __restrict__ size, int n,
+                                                        double aspect, SampleMaps maps, int4* __restrict__ xywh, int4* __restrict__ trace) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int32_t sx = x[i], sy = y[i], sw = size[i], sh = fd_sample_cvround(aspect * (double)sw);
+    for (int k = 0; k < maps.n; ++k) fd_sample_map_apply(maps.m[k], sx, sy, sw, sh);
+    const int4 s = make_int4(sx, sy, sw, sh);
+    xywh[i] = s;
+    trace[i] = s;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 int sample_grid(fd_ctx* ctx, int n) { return std::max(1, std::min((n + 3) / 4, ctx->num_cus * 32)); }
 
@@ -587,6 +605,46 @@ int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, cons
         else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
         std::vector<double> dist(n);   // the validity comes from the kernels: no sampleOf
         fd_samples_svm_tail(ctx, svm, g->feat.p, len, n, g->dist, dist.data(), nullptr, g->valid.p, target, weight, nullptr);
+    });
+}
+
+int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g, int kind, const void* params, const fd_svm* svm, double aspect_ratio,
+                                   const fd_sample_map* maps, int n_maps) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_evaluate_integral";
+        if (!ctx || !p || !g || !params || !svm || n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
+        SampleMaps chain;
+        std::memset(&chain, 0, sizeof(chain));
+        chain.n = n_maps;
+        for (int k = 0; k < n_maps; ++k) {
+            if (maps[k].kind != FD_SAMPLE_MAP_RESIZE && maps[k].kind != FD_SAMPLE_MAP_INTEGRAL)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown sample map kind %d", who, maps[k].kind);
+            chain.m[k] = maps[k];
+        }
+        if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF && kind != FD_INTEGRAL_HOG) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
+        const FdParticlesView v = fd_particles_view(ctx, p, who);
+        require_updated(ctx, g, who);
+        const fd_surf_params* sp = (const fd_surf_params*)params;
+        int len;
+        if (kind == FD_INTEGRAL_HAAR) len = prepare_haar(ctx, g, (const fd_haar_params*)params);
+        else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_check((const fd_integral_hog_params*)params);
+        else len = check_surf(sp->gradient_count, sp->cell_count);
+        fd_samples_require_f32_svm(svm, len, who);
+        const int n = v.n;
+        if (n > 0) {
+            g->xywh.reserve(sizeof(int32_t) * 4 * (size_t)n);
+            g->valid.reserve((size_t)n);
+            hipLaunchKernelGGL(k_particles_xywh, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, v.x, v.y, v.size, n, aspect_ratio, chain, g->xywh.as<int4>(),
+                               (int4*)v.windows);
+            HIP_CHECK(hipGetLastError());
+            if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
+            else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
+            else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
+            fd_svm_generic_launch(ctx, svm, g->feat.p, nullptr, (int64_t)len * 4, n, v.score);
+            HIP_CHECK(hipMemcpyAsync(v.valid, g->valid.p, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        fd_particles_set_evaluated(p);
     });
 }
 

@@ -6,7 +6,8 @@
 // Kernels: k_flow_level0 (gray conversion + border of level 0), k_flow_pyrdown_pad (cv::pyrDown of a level + border),
 // k_flow_scharr_pad (Scharr derivatives of a level + border) -- one thread per stored pixel, border pixels compute the value of the
 // edge pixel they replicate, so a level is written once and no second pass touches it; k_lk_track -- one wavefront per point, all
-// levels and iterations inside, the five window sums exact in int64.  All loops are counted; nothing waits on another workgroup.
+// levels and iterations inside, the five window sums exact in int64; k_flow_motion -- one workgroup, the median flow of a resident
+// track (fd_flow_median restated by radix selection).  All loops are counted; nothing waits on another workgroup.
 #include "fd_internal.hpp"
 #include <algorithm>
 #include <cfloat>
@@ -228,6 +229,141 @@ __global__ __launch_bounds__(64) void k_lk_track(const uint8_t* __restrict__ fro
     }
 }
 
+// ---- the median flow of n tracked points on the device: fd_flow_median (hostalgo.cpp) restated, DESIGN.md 4.7 ----
+constexpr int MT = FD_FLOW_RESIDENT_MAX_POINTS;   // threads of k_flow_motion: one per point
+
+// an unsigned key in the host's nanLast order: a < b as floats <=> key(a) < key(b); every NaN has the largest key
+__device__ inline uint32_t flow_key(float v) {
+    if (v != v) return 0xffffffffu;
+    const uint32_t b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ inline float flow_unkey(uint32_t k) {
+    if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// one more key in its bin.  The lanes that share the bin of the first taking lane go in as one addition (the ratios of a rigid motion
+// crowd into one bin); integer additions, so the histogram does not depend on who adds first.
+__device__ inline void flow_hist_add(unsigned int* hist, unsigned int bin, bool take) {
+    const unsigned long long takers = __ballot(take);
+    if (!takers) return;
+    const int leader = __ffsll((long long)takers) - 1;
+    const unsigned int leaderBin = (unsigned int)__shfl((int)bin, leader);
+    const unsigned long long same = __ballot(take && bin == leaderBin);
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[leaderBin], (unsigned int)__popcll(same));
+    else if (take && bin != leaderBin) atomicAdd(&hist[bin], 1u);
+}
+
+// The k-th smallest (from 0) of the keys `each` emits, by radix selection: four passes of eight bits from the top; a pass counts the
+// keys that agree with the digits chosen so far by their next digit, and the first wavefront walks the 256 counts to the digit that
+// holds rank k.  `each` emits the same multiset of keys in every pass; every thread of the workgroup calls this.
+template <class Each>
+__device__ uint32_t flow_select(unsigned int* hist, unsigned int* chosen, unsigned int k, Each each) {
+    const int tid = threadIdx.x;
+    uint32_t prefix = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t above = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        each([&](uint32_t key, bool take) { flow_hist_add(hist, (key >> shift) & 255u, take && (key & above) == prefix); });
+        __syncthreads();
+        if (tid < 64) {   // lane l: bins 4 l .. 4 l + 3
+            const unsigned int c0 = hist[4 * tid], c1 = hist[4 * tid + 1], c2 = hist[4 * tid + 2], c3 = hist[4 * tid + 3];
+            const unsigned int mine = c0 + c1 + c2 + c3;
+            unsigned int incl = mine;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned int t = (unsigned int)__shfl_up((int)incl, o, 64);
+                if (tid >= o) incl += t;
+            }
+            const unsigned int before = incl - mine;
+            if (before <= k && k < incl) {   // one lane: the counts add up to more than k
+                unsigned int r = k - before, bin = 4 * tid;
+                if (r >= c0) { r -= c0; ++bin; if (r >= c1) { r -= c1; ++bin; if (r >= c2) { r -= c2; ++bin; } } }
+                chosen[0] = bin;
+                chosen[1] = r;
+            }
+        }
+        __syncthreads();
+        prefix |= chosen[0] << shift;
+        k = chosen[1];
+    }
+    return prefix;
+}
+
+// OpticalFlowTransitionModel.cpp:114-170 as fd_flow_median has it, one workgroup, thread i owns point i.  A pair is correct when both
+// status bytes are set and its squared forward-backward distance d is a number not above 0.5f: that is the set fd_flow_median's sort
+// puts in front, and only its members matter, not their order (each median is an order statistic of a multiset; the ratio of a pair
+// is symmetric in its two points because (-v) * (-v) == v * v).  The correct points are compacted in index order.  The medians of
+// x and y are the keys of rank n_correct / 2; the ratio median is the key of rank pairs / 2 over all pairs, every ratio recomputed
+// in each pass (thread j: the pairs (i, j), i < j).  All loops are counted; nothing waits on another workgroup.
+__global__ __launch_bounds__(MT) void k_flow_motion(const float2* __restrict__ pts, const float2* __restrict__ fwd, const float2* __restrict__ bwd,
+                                                    const uint8_t* __restrict__ fstatus, const uint8_t* __restrict__ bstatus, int n,
+                                                    fd_flow_motion_info* __restrict__ out) {
+    __shared__ float2 sP[MT], sF[MT];
+    __shared__ unsigned int hist[256], chosen[2], waveValid[MT / 64], waveCorrect[MT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bool valid = false, correct = false;
+    float2 P = make_float2(0.f, 0.f), F = P;
+    if (tid < n) {
+        P = pts[tid];
+        F = fwd[tid];
+        if (fstatus[tid] && bstatus[tid]) {
+            const float2 B = bwd[tid];
+            const float dx = B.x - P.x, dy = B.y - P.y;
+            const float d = dx * dx + dy * dy;
+            valid = d == d;
+            correct = valid && !(d > 0.5f);
+        }
+    }
+    const unsigned long long validMask = __ballot(valid), correctMask = __ballot(correct);
+    if (lane == 0) { waveValid[wave] = (unsigned int)__popcll(validMask); waveCorrect[wave] = (unsigned int)__popcll(correctMask); }
+    __syncthreads();
+    int nValid = 0, m = 0, before = 0;
+    for (int w = 0; w < MT / 64; ++w) {
+        nValid += (int)waveValid[w];
+        if (w < wave) before += (int)waveCorrect[w];
+        m += (int)waveCorrect[w];
+    }
+    if (correct) {
+        const int slot = before + __popcll(correctMask & ((1ull << lane) - 1ull));
+        sP[slot] = P;
+        sF[slot] = F;
+    }
+    __syncthreads();
+    const int half = n / 2;
+    const bool ok = nValid >= half && m >= half && m >= 2;   // uniform over the workgroup
+    float medianX = 0.f, medianY = 0.f, medianRatio = 1.f;
+    if (ok) {
+        const bool mine = tid < m;
+        const float fx = mine ? sF[tid].x - sP[tid].x : 0.f, fy = mine ? sF[tid].y - sP[tid].y : 0.f;
+        medianX = flow_unkey(flow_select(hist, chosen, (unsigned int)(m / 2), [&](auto emit) { emit(flow_key(fx), mine); }));
+        medianY = flow_unkey(flow_select(hist, chosen, (unsigned int)(m / 2), [&](auto emit) { emit(flow_key(fy), mine); }));
+        const unsigned int pairs = (unsigned int)m * (unsigned int)(m - 1) / 2u;
+        const int rows = mine ? tid : 0;
+        const float2 Pj = mine ? sP[tid] : make_float2(0.f, 0.f), Fj = mine ? sF[tid] : make_float2(0.f, 0.f);
+        const float ratio = flow_unkey(flow_select(hist, chosen, pairs / 2u, [&](auto emit) {
+            for (int i = 0; i < rows; ++i) {
+                const float2 Pi = sP[i], Fi = sF[i];
+                const float bx = Pi.x - Pj.x, by = Pi.y - Pj.y;
+                const float ax = Fi.x - Fj.x, ay = Fi.y - Fj.y;
+                emit(flow_key((ax * ax + ay * ay) / (bx * bx + by * by)), true);
+            }
+        }));
+        medianRatio = sqrtf(ratio);
+    }
+    if (tid == 0) {
+        out->ok = ok ? 1 : 0;
+        out->n_valid = nValid;
+        out->n_correct = nValid >= half ? m : 0;
+        out->median_x = medianX;
+        out->median_y = medianY;
+        out->median_ratio = medianRatio;
+    }
+}
+
 }  // namespace
 
 struct fd_flow {
@@ -240,9 +376,17 @@ struct fd_flow {
     int cur = 0;                     // the slot of the current frame
     int updates = 0;                 // saturates at 2: both slots hold a frame
     DevBuf arena, table, input, points;
+    DevBuf motion, motionIn;         // fd_flow_motion_info of the last resident track; the arrays of fd_debug_flow_motion
+    bool hasMotion = false;
+    int residentN = -1;              // points of the resident track whose results `points` still holds, or -1
+    HostBuf pinnedPts;               // the points of a resident track on their way to the device
+    hipEvent_t ptsUploaded = nullptr;
     HostBuf pinned;                  // a host image on its way to the device
     hipEvent_t uploaded = nullptr;   // recorded behind the copy out of `pinned`
-    ~fd_flow() { if (uploaded) (void)hipEventDestroy(uploaded); }
+    ~fd_flow() {
+        if (uploaded) (void)hipEventDestroy(uploaded);
+        if (ptsUploaded) (void)hipEventDestroy(ptsUploaded);
+    }
 };
 
 namespace {
@@ -400,6 +544,7 @@ int fd_flow_track(fd_ctx* ctx, fd_flow* flow, int backward, const float* pts_xy,
         flow_check_points(f, "fd_flow_track", pts_xy, n);
         if (n == 0) return;
         if (!out_xy || !status) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_flow_track: NULL argument");
+        f->residentN = -1;
         const FlowPointBufs q = flow_point_bufs(f);
         const size_t N = (size_t)n;
         HIP_CHECK(hipMemcpyAsync(q.pts, pts_xy, 8 * N, hipMemcpyHostToDevice, ctx->stream));
@@ -417,6 +562,7 @@ int fd_flow_track_fb(fd_ctx* ctx, fd_flow* flow, const float* pts_xy, int n, flo
         flow_check_points(f, "fd_flow_track_fb", pts_xy, n);
         if (n == 0) return;
         if (!fwd || !bwd || !fstatus || !bstatus) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_flow_track_fb: NULL argument");
+        f->residentN = -1;
         const FlowPointBufs q = flow_point_bufs(f);
         const size_t N = (size_t)n;
         HIP_CHECK(hipMemcpyAsync(q.pts, pts_xy, 8 * N, hipMemcpyHostToDevice, ctx->stream));
@@ -427,6 +573,96 @@ int fd_flow_track_fb(fd_ctx* ctx, fd_flow* flow, const float* pts_xy, int n, flo
         HIP_CHECK(hipMemcpyAsync(fstatus, q.fstatus, N, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(bstatus, q.bstatus, N, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int fd_flow_track_fb_resident(fd_ctx* ctx, fd_flow* flow, const float* pts_xy, int n) {
+    return fd_guard(ctx, [&] {
+        fd_flow* f = flow_checked(ctx, flow, "fd_flow_track_fb_resident");
+        if (n > FD_FLOW_RESIDENT_MAX_POINTS)
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_flow_track_fb_resident: %d points, at most %d stay on the device", n, FD_FLOW_RESIDENT_MAX_POINTS);
+        flow_check_points(f, "fd_flow_track_fb_resident", pts_xy, n);
+        const FlowPointBufs q = flow_point_bufs(f);
+        f->motion.reserve(sizeof(fd_flow_motion_info));
+        if (n > 0) {
+            // through pinned memory: the caller's points are free when the call returns, and the copy does not wait for the stream
+            if (!f->ptsUploaded) HIP_CHECK(hipEventCreateWithFlags(&f->ptsUploaded, hipEventDisableTiming));
+            HIP_CHECK(hipEventSynchronize(f->ptsUploaded));
+            f->pinnedPts.reserve(8 * (size_t)FD_FLOW_RESIDENT_MAX_POINTS);
+            std::memcpy(f->pinnedPts.p, pts_xy, 8 * (size_t)n);
+            HIP_CHECK(hipMemcpyAsync(q.pts, f->pinnedPts.p, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipEventRecord(f->ptsUploaded, ctx->stream));
+            flow_launch_track(ctx, f, 0, q.pts, n, q.fwd, q.fstatus, nullptr);
+            flow_launch_track(ctx, f, 1, q.fwd, n, q.bwd, q.bstatus, nullptr);
+        }
+        hipLaunchKernelGGL(k_flow_motion, dim3(1), dim3(MT), 0, ctx->stream, (const float2*)q.pts, (const float2*)q.fwd, (const float2*)q.bwd, q.fstatus,
+                           q.bstatus, n, f->motion.as<fd_flow_motion_info>());
+        HIP_CHECK(hipGetLastError());
+        f->hasMotion = true;
+        f->residentN = n;
+    });
+}
+
+int fd_flow_get_tracks(fd_ctx* ctx, fd_flow* flow, int cap, int* n, float* fwd, float* bwd, uint8_t* fstatus, uint8_t* bstatus, int32_t* order,
+                       int* n_valid, int* n_correct) {
+    return fd_guard(ctx, [&] {
+        fd_flow* f = flow_checked(ctx, flow, "fd_flow_get_tracks");
+        if (cap < 0) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_flow_get_tracks: bad argument");
+        if (f->residentN < 0) FD_THROW(FD_ERR_RUNTIME, "fd_flow_get_tracks: the handle holds no resident track (fd_flow_track_fb_resident)");
+        const int count = f->residentN;
+        if (n) *n = count;
+        if (count > cap) FD_THROW(FD_ERR_CAPACITY, "fd_flow_get_tracks: %d points, capacity %d", count, cap);
+        const size_t N = (size_t)count;
+        const FlowPointBufs q = flow_point_bufs(f);
+        std::vector<float> host(6 * N);
+        std::vector<uint8_t> st(2 * N);
+        if (N) {
+            HIP_CHECK(hipMemcpyAsync(host.data(), q.pts, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(host.data() + 2 * N, q.fwd, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(host.data() + 4 * N, q.bwd, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(st.data(), q.fstatus, N, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(st.data() + N, q.bstatus, N, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (fwd && N) std::memcpy(fwd, host.data() + 2 * N, 8 * N);
+        if (bwd && N) std::memcpy(bwd, host.data() + 4 * N, 8 * N);
+        if (fstatus && N) std::memcpy(fstatus, st.data(), N);
+        if (bstatus && N) std::memcpy(bstatus, st.data() + N, N);
+        if (order || n_valid || n_correct) {
+            fd_flow_motion m;
+            m.order = order;
+            const int rc = fd_flow_median(host.data(), host.data() + 2 * N, host.data() + 4 * N, st.data(), st.data() + N, count, &m);
+            if (rc != FD_OK) FD_THROW(rc, "fd_flow_get_tracks: fd_flow_median refused the tracks");
+            if (n_valid) *n_valid = m.n_valid;
+            if (n_correct) *n_correct = m.n_correct;
+        }
+    });
+}
+
+int fd_debug_flow_motion(fd_ctx* ctx, fd_flow* flow, const float* pts, const float* fwd, const float* bwd, const uint8_t* fstatus,
+                         const uint8_t* bstatus, int n, fd_flow_motion_info* out) {
+    return fd_guard(ctx, [&] {
+        fd_flow* f = flow_checked(ctx, flow, "fd_debug_flow_motion");
+        if (n < 0 || n > FD_FLOW_RESIDENT_MAX_POINTS)
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_flow_motion: %d points, must be 0 .. %d", n, FD_FLOW_RESIDENT_MAX_POINTS);
+        if (!out || (n > 0 && (!pts || !fwd || !bwd || !fstatus || !bstatus))) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_debug_flow_motion: NULL argument");
+        const size_t M = FD_FLOW_RESIDENT_MAX_POINTS, N = (size_t)n;
+        f->motionIn.reserve(26 * M);   // pts, fwd, bwd (8 M each), fstatus, bstatus (M each)
+        f->motion.reserve(sizeof(fd_flow_motion_info));
+        unsigned char* b = f->motionIn.as<unsigned char>();
+        if (N) {
+            HIP_CHECK(hipMemcpyAsync(b, pts, 8 * N, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(b + 8 * M, fwd, 8 * N, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(b + 16 * M, bwd, 8 * N, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(b + 24 * M, fstatus, N, hipMemcpyHostToDevice, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(b + 25 * M, bstatus, N, hipMemcpyHostToDevice, ctx->stream));
+        }
+        hipLaunchKernelGGL(k_flow_motion, dim3(1), dim3(MT), 0, ctx->stream, (const float2*)b, (const float2*)(b + 8 * M), (const float2*)(b + 16 * M),
+                           b + 24 * M, b + 25 * M, n, f->motion.as<fd_flow_motion_info>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, f->motion.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        f->hasMotion = true;
     });
 }
 
@@ -448,3 +684,9 @@ int fd_debug_flow_level(fd_ctx* ctx, fd_flow* flow, int which, int level, uint8_
 }
 
 }  // extern "C"
+
+const fd_flow_motion_info* fd_flow_device_motion(fd_ctx* ctx, fd_flow* flow, const char* who) {
+    fd_flow* f = flow_checked(ctx, flow, who);
+    if (!f->hasMotion) FD_THROW(FD_ERR_RUNTIME, "%s: the flow handle holds no motion (fd_flow_track_fb_resident)", who);
+    return f->motion.as<fd_flow_motion_info>();
+}

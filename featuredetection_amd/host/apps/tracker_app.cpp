@@ -74,6 +74,11 @@ static cv::Mat read_pnm(const string& path) {
     return img;
 }
 
+// a subclass that changes nothing: the device route restates the class itself and must leave any subclass to the generic route
+struct SubclassedFlowModel : public OpticalFlowTransitionModel {
+    using OpticalFlowTransitionModel::OpticalFlowTransitionModel;
+};
+
 // the optical-flow transition model of a sampler, if it has one
 static shared_ptr<OpticalFlowTransitionModel> flow_model(const shared_ptr<Sampler>& sampler) {
     auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
@@ -173,8 +178,15 @@ int main(int argc, char** argv) {
         } else if (transition == "opticalFlow") {   // HeadTracking.cpp:545-550
             if (pt.get("transition.fallback", string("simple")) != "simple") throw std::invalid_argument("tracker_app: only `fallback simple` is supported");
             auto fallback = make_shared<SimpleTransitionModel>(pt.get("transition.fallback.positionDeviation", 12.8), pt.get("transition.fallback.sizeDeviation", 0.1), seed + 1);
-            transitionModel = make_shared<OpticalFlowTransitionModel>(fallback, pt.get("transition.positionDeviation", 10.0), pt.get("transition.sizeDeviation", 0.08),
-                                                                      cv::Size(10, 10), true, cv::Size(15, 15), 2, seed + 3);
+            // gridSize (default 10) and subclass (default 0: the class itself) are not the reference's keys: they let a test build the
+            // configurations that must keep the generic route under FD_COND_DEVICE=1
+            const int grid = pt.get("transition.gridSize", 10);
+            const double positionDeviation = pt.get("transition.positionDeviation", 10.0), sizeDeviation = pt.get("transition.sizeDeviation", 0.08);
+            if (pt.get("transition.subclass", 0) != 0)
+                transitionModel = make_shared<SubclassedFlowModel>(fallback, positionDeviation, sizeDeviation, cv::Size(grid, grid), true, cv::Size(15, 15), 2, seed + 3);
+            else
+                transitionModel = make_shared<OpticalFlowTransitionModel>(fallback, positionDeviation, sizeDeviation, cv::Size(grid, grid), true, cv::Size(15, 15), 2,
+                                                                          seed + 3);
         } else {
             throw std::invalid_argument("tracker_app: invalid transition model type: " + transition);
         }

@@ -139,6 +139,14 @@ public:
     // calls of evaluate(image, samples) that scored their samples with one fd_integral_svm_evaluate_samples / with the per-sample loop
     int getFusedEvaluationCount() const { return fusedEvaluations; }
     int getLoopEvaluationCount() const { return loopEvaluations; }
+    std::shared_ptr<imageprocessing::FeatureExtractor> getFeatureExtractor() const { return featureExtractor; }
+    std::shared_ptr<classification::ProbabilisticClassifier> getClassifier() const { return classifier; }
+    // evaluate(image, samples) for a generation that lives in `particles`: update, then one
+    // fd_particles_evaluate_integral and one fd_particles_weigh_classifier, nothing copied back.  The caller has checked residentPossible()
+    void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles);
+    // the extractor resolves to a Haar, SURF or integral HOG chain with at most FD_SAMPLE_MAPS_MAX wrappers that is ready, and the
+    // classifier is a (Trainable)ProbabilisticSvmClassifier on f32 vectors
+    bool residentPossible() const;
 private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticClassifier> classifier;
@@ -434,6 +442,17 @@ public:
     // predict for one sample with its draws (the arithmetic of k_particles_sample)
     static void apply(Sample& sample, const double diffusion[3]);
     const std::vector<double>& getLastDiffusion() const { return lastDiffusion; }   // the draws of the last predict, 3 per sample
+    // the draws of a predict over `samples` samples without the samples: they become the last diffusion
+    const std::vector<double>& drawBlock(size_t samples);
+    // what the next draw depends on -- the distribution caches its second value, so it is part of the state -- and the last diffusion:
+    // a device frame that drew a block it did not use puts the snapshot back
+    struct DrawState {
+        std::mt19937 generator;
+        std::normal_distribution<> distribution;
+        std::vector<double> lastDiffusion;
+    };
+    DrawState drawState() const { return DrawState{generator, distribution, lastDiffusion}; }
+    void restoreDrawState(const DrawState& state) { generator = state.generator; distribution = state.distribution; lastDiffusion = state.lastDiffusion; }
 private:
     std::vector<double> lastDiffusion;
     double positionDeviation, sizeDeviation;
@@ -468,15 +487,27 @@ public:
     std::shared_ptr<TransitionModel> getFallback() const { return fallback; }
     const std::vector<cv::Point2f>& getTemplatePoints() const { return templatePoints; }
     const std::vector<cv::Point2f>& getPoints() const { return points; }                 // of the last predict; empty when it did not track
-    const std::vector<cv::Point2f>& getForwardPoints() const { return forwardPoints; }
-    const std::vector<cv::Point2f>& getBackwardPoints() const { return backwardPoints; }
+    // after a resident predict the tracks are still on the device: these three fetch them on demand (fd_flow_get_tracks)
+    const std::vector<cv::Point2f>& getForwardPoints() const { fetchTracks(); return forwardPoints; }
+    const std::vector<cv::Point2f>& getBackwardPoints() const { fetchTracks(); return backwardPoints; }
     // the point indices of the correct flows, ordered by forward-backward distance (squaredDistances[0 .. correctFlowCount) of the reference)
-    const std::vector<int>& getCorrectFlowIndices() const { return correctFlowIndices; }
+    const std::vector<int>& getCorrectFlowIndices() const { fetchTracks(); return correctFlowIndices; }
     bool usedFlow() const { return flowUsed; }                                           // the last predict moved the samples by the flow
     const fd_flow_motion& getLastMotion() const { return lastMotion; }                   // of the last predict; all zero when it did not track (order is not set)
     const std::vector<double>& getLastDraws() const { return lastDraws; }                // the normal draws of the last flow prediction, 3 per sample
     // predict for one sample with its three normal draws
     static void apply(Sample& sample, float medianX, float medianY, float medianRatio, double positionDeviation, double sizeDeviation, const double z[3]);
+    // predict for a generation that lives on the device, in three steps.  residentPossible: the fallback is exactly a
+    // SimpleTransitionModel and the grid has at most FD_FLOW_RESIDENT_MAX_POINTS points.  beginResident: the frame becomes the current
+    // one; true when the points of `target` were queued for tracking (fd_flow_track_fb_resident), false where predict would hand over
+    // to the fallback before tracking (no previous pyramid, no target).  drawResident: the normal draws of `samples` samples, as
+    // fd_particles_sample_flow takes them, behind a snapshot of the generator and the distribution.  endResident: what the device's
+    // motion says happened; a motion that is not ok puts the snapshot back, as if the draws had not been taken.
+    bool residentPossible() const;
+    bool beginResident(const cv::Mat& image, const std::shared_ptr<Sample> target);
+    const std::vector<double>& drawResident(size_t samples);
+    void endResident(const fd_flow_motion_info& motion);
+    fd_flow* native() const { return flow; }
 protected:
     // the frame becomes the current one (fd_flow_update); tracks `points` forward and the results backward (fd_flow_track_fb)
     virtual void updatePyramid(const cv::Mat& image);
@@ -490,9 +521,15 @@ private:
     fd_flow* flow = nullptr;
     int flowWidth = 0, flowHeight = 0;
     bool hasPrevious = false;
-    std::vector<cv::Point2f> points, forwardPoints, backwardPoints;
-    std::vector<cv::uchar> forwardStatus, backwardStatus;
-    std::vector<int> correctFlowIndices;
+    void fetchTracks() const;
+    std::vector<cv::Point2f> points;
+    mutable std::vector<cv::Point2f> forwardPoints, backwardPoints;
+    mutable std::vector<cv::uchar> forwardStatus, backwardStatus;
+    mutable std::vector<int> correctFlowIndices;
+    mutable bool tracksOnDevice = false;   // a resident predict tracked `points`: the four arrays and the indices are fetched on demand
+    std::vector<double> residentDiffusion;
+    std::mt19937 generatorBefore;
+    std::normal_distribution<> distributionBefore;
     fd_flow_motion lastMotion{};
     bool flowUsed = false;
     std::vector<double> lastDraws;
@@ -528,8 +565,9 @@ public:
     };
     const Draws& getLastDraws() const { return lastDraws; }
     // the draws of one frame without the Sample objects, in sample()'s order: for an old generation of oldCount samples whose weights
-    // add up (in index order) to oldWeightSum.  Needs LowVarianceSampling and SimpleTransitionModel.
-    const Draws& drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows);
+    // add up (in index order) to oldWeightSum.  Needs LowVarianceSampling; the diffusion is drawn from `simple`, by default the
+    // sampler's own SimpleTransitionModel (an OpticalFlowTransitionModel's fallback is the caller's to pass).
+    const Draws& drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows, SimpleTransitionModel* simple = nullptr);
 private:
     Draws lastDraws;
     void sampleValues(Sample& sample, const cv::Mat& image);
@@ -590,7 +628,10 @@ public:
 // validators and adapt (AdaptiveCondensationTracker.cpp:67-95).  Not in the reference: the device route.  With
 // FD_COND_DEVICE=1 a frame whose sampler is a ResamplingSampler on LowVarianceSampling + SimpleTransitionModel, whose model is an
 // ExtendedHogBasedMeasurementModel with adaptation NONE or POSITION and whose extractor is
-// FilteringStateExtractor(WeightedMeanStateExtractor) -- these classes exactly: a subclass of any of them may override what the route
+// FilteringStateExtractor(WeightedMeanStateExtractor) -- or whose transition model is an OpticalFlowTransitionModel with a
+// SimpleTransitionModel fallback and a grid of at most 1024 points, or a SimpleTransitionModel, and whose model is a SingleClassifierModel
+// (also the one inside a PositionDependentMeasurementModel) with a ProbabilisticSvmClassifier on f32 vectors on a Haar, SURF or integral
+// HOG extractor -- these classes exactly: a subclass of any of them may override what the route
 // restates and therefore keeps the generic route -- runs on a particle set that stays on the device (fd_particles): the host draws the
 // same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample objects on demand;
 // they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
@@ -599,6 +640,8 @@ public:
     enum class Route { NONE, GENERIC, DEVICE };
     Route getLastRoute() const { return lastRoute; }
 protected:
+    // the last frame left its samples on the device and neither the model's isValid nor its adapt reads them
+    bool samplesUnread() const { return lastRoute == Route::DEVICE && lastKind == ResidentKind::Ehog; }
     ParticleFrameLoop(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
     ~ParticleFrameLoop();
     ParticleFrameLoop(const ParticleFrameLoop&) = delete;
@@ -617,13 +660,20 @@ private:
     bool deviceRoutePossible() const;
     void deviceStep();
     void releaseParticles();
+    // which resident frame the configuration has: Ehog is ExtendedHogBasedMeasurementModel on its tracker, Integral a
+    // SingleClassifierModel (also inside a PositionDependentMeasurementModel) on an unbound set
+    enum class ResidentKind { None, Ehog, Integral };
+    ResidentKind residentKind() const;
+    void integralDeviceStep();
+    void uploadGeneration();
     fd_particles* particles = nullptr;
-    fd_ehog_tracker* particlesOn = nullptr;   // the tracker handle `particles` is bound to
+    fd_ehog_tracker* particlesOn = nullptr;   // the tracker handle `particles` is bound to; NULL: an unbound set
     bool resident = false;                    // the current generation lives in `particles`
     mutable bool materialized = true;         // `samples` holds it as well
     int residentCount = 0;
     double residentWeightSum = 0;
     Route lastRoute = Route::NONE;
+    ResidentKind lastKind = ResidentKind::None;
 };
 
 // CondensationTracker.hpp / .cpp:25-47

@@ -6,6 +6,7 @@
 // its stand-alone ImageFilter::applyTo(const Mat&) form (one kernel launch per Mat: for composition and
 // tests, not for the sliding-window hot loop).
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <utility>
@@ -595,6 +596,13 @@ private:
     std::shared_ptr<ExtendedHogFeatureExtractor> base;
 };
 
+// one sample map on one sample, through the library's fd_sample_maps_apply (no allocation: extract calls this per patch)
+inline void applySampleMap(const fd_sample_map& map, int& x, int& y, int& width, int& height) {
+    int32_t s[4] = {x, y, width, height};
+    if (fd_sample_maps_apply(&map, 1, 1, s) != FD_OK) throw std::logic_error("applySampleMap: fd_sample_maps_apply refused the map");
+    x = s[0]; y = s[1]; width = s[2]; height = s[3];
+}
+
 // PatchResizingFeatureExtractor.hpp:21-60 (the `scale` key of createFeatureExtractor): asks the underlying extractor for a patch of
 // another size and position and reports the patch with the size and position that were asked for
 class PatchResizingFeatureExtractor : public FeatureExtractor {
@@ -603,13 +611,10 @@ public:
     PatchResizingFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor, double factor, double yOffset = 0, double xOffset = 0)
         : extractor(extractor), factor(factor), yOffset(yOffset), xOffset(xOffset) {}
     void update(std::shared_ptr<VersionedImage> image) override { extractor->update(image); }
-    // what the underlying extractor is asked for (not in the reference: the one copy of these expressions)
-    void mapSample(int& x, int& y, int& width, int& height) const {
-        x = cv::cvRound(x + xOffset * width);
-        y = cv::cvRound(y + yOffset * height);
-        width = cv::cvRound(factor * width);
-        height = cv::cvRound(factor * height);
-    }
+    // what the underlying extractor is asked for, as data: the library holds the one copy of the expressions (fd_sample_maps_apply on
+    // the host, k_particles_xywh on the device)
+    fd_sample_map sampleMap() const { return fd_sample_map{FD_SAMPLE_MAP_RESIZE, factor, xOffset, yOffset}; }
+    void mapSample(int& x, int& y, int& width, int& height) const { applySampleMap(sampleMap(), x, y, width, height); }
     std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override {
         mapSample(x, y, width, height);
         std::shared_ptr<Patch> patch = extractor->extract(x, y, width, height);
@@ -637,13 +642,9 @@ public:
     using FeatureExtractor::update;
     explicit IntegralFeatureExtractor(std::shared_ptr<FeatureExtractor> extractor) : extractor(extractor) {}
     void update(std::shared_ptr<VersionedImage> image) override { extractor->update(image); }
-    // what the underlying extractor is asked for (not in the reference: the one copy of these expressions)
-    void mapSample(int& x, int& y, int& width, int& height) const {
-        x += width % 2 == 0 ? 0 : 1;
-        y += height % 2 == 0 ? 0 : 1;
-        width += 1;
-        height += 1;
-    }
+    // what the underlying extractor is asked for, as data (see PatchResizingFeatureExtractor::sampleMap)
+    fd_sample_map sampleMap() const { return fd_sample_map{FD_SAMPLE_MAP_INTEGRAL, 0.0, 0.0, 0.0}; }
+    void mapSample(int& x, int& y, int& width, int& height) const { applySampleMap(sampleMap(), x, y, width, height); }
     std::shared_ptr<Patch> extract(int x, int y, int width, int height) const override {
         const int offsetX = width % 2 == 0 ? 0 : 1, offsetY = height % 2 == 0 ? 0 : 1;
         mapSample(x, y, width, height);
@@ -668,27 +669,29 @@ class ExtractorWrappers {
 public:
     explicit ExtractorWrappers(const FeatureExtractor* outer) : innermost(outer) {
         for (;;) {
-            if (auto* resizing = dynamic_cast<const PatchResizingFeatureExtractor*>(innermost)) { chain.push_back(innermost); innermost = resizing->getExtractor().get(); }
-            else if (auto* integral = dynamic_cast<const IntegralFeatureExtractor*>(innermost)) { chain.push_back(innermost); innermost = integral->getExtractor().get(); }
+            if (auto* resizing = dynamic_cast<const PatchResizingFeatureExtractor*>(innermost)) { maps.push_back(resizing->sampleMap()); innermost = resizing->getExtractor().get(); }
+            else if (auto* integral = dynamic_cast<const IntegralFeatureExtractor*>(innermost)) { maps.push_back(integral->sampleMap()); innermost = integral->getExtractor().get(); }
             else break;
         }
     }
     const FeatureExtractor* inner() const { return innermost; }
-    bool wrapped() const { return !chain.empty(); }
-    void map(int& x, int& y, int& width, int& height) const {
-        for (const FeatureExtractor* w : chain) {
-            if (auto* resizing = dynamic_cast<const PatchResizingFeatureExtractor*>(w)) resizing->mapSample(x, y, width, height);
-            else static_cast<const IntegralFeatureExtractor*>(w)->mapSample(x, y, width, height);
-        }
+    bool wrapped() const { return !maps.empty(); }
+    // the chain as data, outer to inner, walked once by the constructor: what fd_sample_maps_apply and fd_particles_evaluate_integral take
+    const std::vector<fd_sample_map>& sampleMaps() const { return maps; }
+    // n samples {x, y, width, height} in place: one library call per FD_SAMPLE_MAPS_MAX wrappers (a longer chain maps the same, in pieces)
+    void map(int32_t* xywh, size_t n = 1) const {
+        for (size_t first = 0; first < maps.size(); first += FD_SAMPLE_MAPS_MAX)
+            if (fd_sample_maps_apply(maps.data() + first, (int)std::min(maps.size() - first, (size_t)FD_SAMPLE_MAPS_MAX), (int)n, xywh) != FD_OK)
+                throw std::logic_error("ExtractorWrappers: fd_sample_maps_apply refused the chain");
     }
-    void map(int32_t* xywh) const {
-        int x = xywh[0], y = xywh[1], w = xywh[2], h = xywh[3];
-        map(x, y, w, h);
-        xywh[0] = x; xywh[1] = y; xywh[2] = w; xywh[3] = h;
+    void map(int& x, int& y, int& width, int& height) const {
+        int32_t s[4] = {x, y, width, height};
+        map(s);
+        x = s[0]; y = s[1]; width = s[2]; height = s[3];
     }
 private:
     const FeatureExtractor* innermost;
-    std::vector<const FeatureExtractor*> chain;
+    std::vector<fd_sample_map> maps;
 };
 
 // Not in the reference: which batched device call serves the samples {x, y, width, height} of an extractor, answered once

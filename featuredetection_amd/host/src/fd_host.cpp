@@ -984,7 +984,7 @@ int SampledChain::cellChannels() const {
 }
 vector<int32_t> SampledChain::mapped(const vector<int32_t>& xywh) const {
     vector<int32_t> m = onPyramid() ? vector<int32_t>() : xywh;   // the pyramid kinds take the samples as they are
-    for (size_t i = 0; i + 4 <= m.size(); i += 4) wrappers.map(m.data() + i);
+    wrappers.map(m.data(), m.size() / 4);
     return m;
 }
 vector<Mat> SampledChain::extract(const vector<int32_t>& xywh) const {
@@ -2866,6 +2866,34 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
     unpack_samples(target, weight, samples);
 }
 
+// the integral kind, its parameters and the SVM of a resident evaluation; false where the combination has none
+static bool resident_integral(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer) {
+    using Kind = imageprocessing::SampledChain::Kind;
+    return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && scorer.svm &&
+           chain.wrappers.sampleMaps().size() <= (size_t)FD_SAMPLE_MAPS_MAX && chain.ready();
+}
+bool SingleClassifierModel::residentPossible() const {
+    return resident_integral(imageprocessing::sampledChainOf(featureExtractor.get()), sampledClassifierOf(classifier.get()));
+}
+void SingleClassifierModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) {
+    using Kind = imageprocessing::SampledChain::Kind;
+    update(image);
+    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(featureExtractor.get());
+    const SampledClassifier scorer = sampledClassifierOf(classifier.get());
+    if (!resident_integral(chain, scorer)) throw std::logic_error("SingleClassifierModel: no resident evaluation for this extractor and classifier");
+    ++fusedEvaluations;
+    fd_haar_params hp;
+    if (chain.haar) hp = chain.haar->params();
+    const int kind = chain.kind == Kind::Haar ? (int)FD_INTEGRAL_HAAR : (chain.kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
+    const void* prm = chain.kind == Kind::Haar ? (const void*)&hp : (chain.kind == Kind::IntegralHog ? (const void*)&chain.ihog : (const void*)&chain.surf);
+    const vector<fd_sample_map> maps = chain.wrappers.sampleMaps();
+    const double a = scorer.svm->getLogisticA(), b = scorer.svm->getLogisticB();
+    check(fd_particles_evaluate_integral(context(), particles, chain.image->native(), kind, prm, scorer.svm->getSvm()->native(a, b), Sample::getAspectRatio(),
+                                         maps.data(), (int)maps.size()));
+    // SvmClassifier::classify compares with the threshold the device model holds as a float (fd_samples_svm_tail does the same)
+    check(fd_particles_weigh_classifier(context(), particles, a, b, (double)(float)scorer.svm->getSvm()->getThreshold()));
+}
+
 // ---- FilteringClassifierModel (FilteringClassifierModel.cpp:27-103) --------------------------------------------------------------------
 // the RVM behind a binary classifier that is an RvmClassifier or a ProbabilisticRvmClassifier; null: another classifier
 static const classification::RvmClassifier* rvm_of(const classification::BinaryClassifier* c) {
@@ -3706,6 +3734,12 @@ void SimpleTransitionModel::drawDiffusion(double out[3]) {
     out[2] = pow(2, sizeDeviation * distribution(generator));
 }
 
+const vector<double>& SimpleTransitionModel::drawBlock(size_t samples) {
+    lastDiffusion.resize(3 * samples);
+    for (size_t i = 0; i < samples; ++i) drawDiffusion(&lastDiffusion[3 * i]);
+    return lastDiffusion;
+}
+
 void SimpleTransitionModel::apply(Sample& sample, const double diffusion[3]) {   // .cpp:27-42
     double vx = sample.getVx();
     double vy = sample.getVy();
@@ -3805,7 +3839,83 @@ void OpticalFlowTransitionModel::apply(Sample& sample, float medianX, float medi
     sample.setSize(static_cast<int>(std::round(sample.getSize() * sample.getVSize())));   // int * float: a float product
 }
 
+bool OpticalFlowTransitionModel::residentPossible() const {
+    return fallback && typeid(*fallback) == typeid(SimpleTransitionModel) && templatePoints.size() <= (size_t)FD_FLOW_RESIDENT_MAX_POINTS;
+}
+
+bool OpticalFlowTransitionModel::beginResident(const Mat& image, const shared_ptr<Sample> target) {   // predict up to the tracking
+    points.clear();
+    forwardPoints.clear();
+    backwardPoints.clear();
+    forwardStatus.clear();
+    backwardStatus.clear();
+    correctFlowIndices.clear();
+    lastDraws.clear();
+    tracksOnDevice = false;
+    flowUsed = false;
+    lastMotion = fd_flow_motion{};
+    lastMotion.median_ratio = 1.f;
+    const bool hadPrevious = hasPrevious;
+    updatePyramid(image);   // may reset hasPrevious (another frame size)
+    const bool previous = hadPrevious && hasPrevious;
+    hasPrevious = true;
+    if (!previous || !target) return false;
+    for (const cv::Point2f& point : templatePoints)
+        points.push_back(cv::Point2f(target->getWidth() * point.x + target->getX(), target->getHeight() * point.y + target->getY()));
+    static const float none[2] = {0.f, 0.f};
+    check(fd_flow_track_fb_resident(context(), flow, points.empty() ? none : &points[0].x, (int)points.size()));
+    tracksOnDevice = true;
+    return true;
+}
+
+const vector<double>& OpticalFlowTransitionModel::drawResident(size_t samples) {
+    generatorBefore = generator;
+    distributionBefore = distribution;
+    lastDraws.resize(3 * samples);
+    residentDiffusion.resize(3 * samples);
+    for (size_t i = 0; i < 3 * samples; i += 3) {   // apply's expressions on the draws
+        for (int c = 0; c < 3; ++c) lastDraws[i + c] = distribution(generator);
+        residentDiffusion[i] = positionDeviation * lastDraws[i];
+        residentDiffusion[i + 1] = positionDeviation * lastDraws[i + 1];
+        residentDiffusion[i + 2] = pow(2, sizeDeviation * lastDraws[i + 2]);
+    }
+    return residentDiffusion;
+}
+
+void OpticalFlowTransitionModel::endResident(const fd_flow_motion_info& motion) {
+    lastMotion.ok = motion.ok;
+    lastMotion.n_valid = motion.n_valid;
+    lastMotion.n_correct = motion.n_correct;
+    lastMotion.median_x = motion.median_x;
+    lastMotion.median_y = motion.median_y;
+    lastMotion.median_ratio = motion.median_ratio;
+    flowUsed = motion.ok != 0;
+    if (!flowUsed) {   // the fallback predicted: this model drew nothing
+        generator = generatorBefore;
+        distribution = distributionBefore;
+        lastDraws.clear();
+    }
+}
+
+void OpticalFlowTransitionModel::fetchTracks() const {
+    if (!tracksOnDevice) return;
+    tracksOnDevice = false;
+    const size_t n = points.size();
+    forwardPoints.resize(n);
+    backwardPoints.resize(n);
+    forwardStatus.resize(n);
+    backwardStatus.resize(n);
+    vector<int32_t> order(std::max<size_t>(n, 1));
+    int count = 0, valid = 0, correct = 0;
+    static float none[2];
+    static uchar noStatus[1];
+    check(fd_flow_get_tracks(context(), flow, (int)n, &count, n ? &forwardPoints[0].x : none, n ? &backwardPoints[0].x : none, n ? forwardStatus.data() : noStatus,
+                             n ? backwardStatus.data() : noStatus, order.data(), &valid, &correct));
+    correctFlowIndices.assign(order.begin(), order.begin() + correct);
+}
+
 void OpticalFlowTransitionModel::predict(vector<shared_ptr<Sample>>& samples, const Mat& image, const shared_ptr<Sample> target) {   // .cpp:90-191
+    tracksOnDevice = false;
     points.clear();
     forwardPoints.clear();
     backwardPoints.clear();
@@ -3912,10 +4022,10 @@ void ResamplingSampler::sample(const vector<shared_ptr<Sample>>& samples, vector
     }
 }
 
-const ResamplingSampler::Draws& ResamplingSampler::drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows) {
+const ResamplingSampler::Draws& ResamplingSampler::drawFrame(size_t oldCount, double oldWeightSum, int cols, int rows, SimpleTransitionModel* simple) {
     lastDraws = Draws();
     auto lowVariance = std::dynamic_pointer_cast<LowVarianceSampling>(resamplingAlgorithm);
-    auto simple = std::dynamic_pointer_cast<SimpleTransitionModel>(transitionModel);
+    if (!simple) simple = dynamic_cast<SimpleTransitionModel*>(transitionModel.get());
     if (!lowVariance || !simple) throw std::logic_error("ResamplingSampler::drawFrame needs LowVarianceSampling and SimpleTransitionModel");
     const size_t resampled = (size_t)(int)((1 - randomRate) * count);
     size_t copies = 0;
@@ -3924,8 +4034,7 @@ const ResamplingSampler::Draws& ResamplingSampler::drawFrame(size_t oldCount, do
         lastDraws.u = lowVariance->draw();
         copies = resampled;
     }
-    lastDraws.diffusion.resize(3 * copies);
-    for (size_t i = 0; i < copies; ++i) simple->drawDiffusion(&lastDraws.diffusion[3 * i]);
+    lastDraws.diffusion = simple->drawBlock(copies);
     for (size_t i = copies; i < count; ++i) {
         int32_t v[3];
         drawValues(cols, rows, v);
@@ -4115,21 +4224,42 @@ void ParticleFrameLoop::releaseParticles() {
 template <class T, class U>
 static bool is_exactly(const shared_ptr<U>& p) { return p && typeid(*p) == typeid(T); }
 
-bool ParticleFrameLoop::deviceRoutePossible() const {
-    if (!fd_particles_route_enabled()) return false;
-    if (!is_exactly<ResamplingSampler>(sampler)) return false;
-    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
-    if (!is_exactly<LowVarianceSampling>(resampling->getResamplingAlgorithm()) || !is_exactly<SimpleTransitionModel>(resampling->getTransitionModel())) return false;
-    if (!is_exactly<ExtendedHogBasedMeasurementModel>(measurementModel)) return false;
-    auto model = std::static_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
-    if (!model->native() || !model->isUsable()) return false;
-    if (model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::NONE && model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::POSITION)
-        return false;
-    if (!is_exactly<FilteringStateExtractor>(extractor)) return false;
-    if (!is_exactly<WeightedMeanStateExtractor>(std::static_pointer_cast<FilteringStateExtractor>(extractor)->getExtractor())) return false;
-    const size_t old = resident ? (size_t)residentCount : samples.size();
-    return old <= FD_PARTICLES_MAX && resampling->getCount() >= 0 && resampling->getCount() <= FD_PARTICLES_MAX;
+// the SingleClassifierModel a resident frame would evaluate: the model itself, or the one inside a PositionDependentMeasurementModel
+static shared_ptr<SingleClassifierModel> resident_single_model(const shared_ptr<MeasurementModel>& model) {
+    if (is_exactly<SingleClassifierModel>(model)) return std::static_pointer_cast<SingleClassifierModel>(model);
+    if (is_exactly<PositionDependentMeasurementModel>(model)) {
+        auto dependent = std::static_pointer_cast<PositionDependentMeasurementModel>(model);
+        if (dependent->isUsable() && is_exactly<SingleClassifierModel>(dependent->getMeasurementModel()))
+            return std::static_pointer_cast<SingleClassifierModel>(dependent->getMeasurementModel());
+    }
+    return nullptr;
 }
+
+ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
+    if (!fd_particles_route_enabled()) return ResidentKind::None;
+    if (!is_exactly<ResamplingSampler>(sampler)) return ResidentKind::None;
+    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
+    if (!is_exactly<LowVarianceSampling>(resampling->getResamplingAlgorithm())) return ResidentKind::None;
+    if (!is_exactly<FilteringStateExtractor>(extractor)) return ResidentKind::None;
+    if (!is_exactly<WeightedMeanStateExtractor>(std::static_pointer_cast<FilteringStateExtractor>(extractor)->getExtractor())) return ResidentKind::None;
+    const size_t old = resident ? (size_t)residentCount : samples.size();
+    if (old > FD_PARTICLES_MAX || resampling->getCount() < 0 || resampling->getCount() > FD_PARTICLES_MAX) return ResidentKind::None;
+    const bool simple = is_exactly<SimpleTransitionModel>(resampling->getTransitionModel());
+    if (is_exactly<ExtendedHogBasedMeasurementModel>(measurementModel)) {
+        auto model = std::static_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
+        if (!simple || !model->native() || !model->isUsable()) return ResidentKind::None;
+        if (model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::NONE && model->getAdaptation() != ExtendedHogBasedMeasurementModel::Adaptation::POSITION)
+            return ResidentKind::None;
+        return ResidentKind::Ehog;
+    }
+    const bool flow = is_exactly<OpticalFlowTransitionModel>(resampling->getTransitionModel()) &&
+                      std::static_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel())->residentPossible();
+    if (!simple && !flow) return ResidentKind::None;
+    const shared_ptr<SingleClassifierModel> single = resident_single_model(measurementModel);
+    return single && single->residentPossible() ? ResidentKind::Integral : ResidentKind::None;
+}
+
+bool ParticleFrameLoop::deviceRoutePossible() const { return residentKind() != ResidentKind::None; }
 
 const vector<shared_ptr<Sample>>& ParticleFrameLoop::currentSamples() const {
     if (resident && !materialized) {   // the Sample objects of the resident generation: no ancestors on this route
@@ -4163,7 +4293,80 @@ void ParticleFrameLoop::replaceSamples(const vector<shared_ptr<Sample>>& newSamp
     materialized = true;
 }
 
+// the generation of the generic route (or of initialize) moves to the device
+void ParticleFrameLoop::uploadGeneration() {
+    const int n = (int)samples.size();
+    vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
+    vector<float> vsize(n);
+    vector<double> weight(n), score(n);
+    vector<uint8_t> target(n);
+    residentWeightSum = 0;
+    for (int i = 0; i < n; ++i) {
+        const Sample& s = *samples[i];
+        x[i] = s.getX(); y[i] = s.getY(); size[i] = s.getSize(); vx[i] = s.getVx(); vy[i] = s.getVy(); vsize[i] = s.getVSize();
+        weight[i] = s.getWeight(); score[i] = s.getScore(); target[i] = s.isTarget(); cluster[i] = s.getClusterId();
+        residentWeightSum += weight[i];
+    }
+    fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
+    check(fd_particles_set(context(), particles, n, &arrays));
+    residentCount = n;
+    resident = true;
+}
+
+// SingleClassifierModel on the integral family, SimpleTransitionModel or OpticalFlowTransitionModel: an unbound set.  The host draws
+// every random number the generic route would draw: the three generators (resampling, transition, fresh samples) are separate, so only
+// the order within each matters.  With the flow model the branch is the device's: both blocks are drawn behind snapshots and the model
+// that did not predict gets its snapshot back after the read-back.
+void ParticleFrameLoop::integralDeviceStep() {
+    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
+    const shared_ptr<SingleClassifierModel> model = resident_single_model(measurementModel);
+    auto flow = std::dynamic_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel());
+    if (particles && particlesOn) {   // a set bound to a tracker: the generation comes back and moves to an unbound one
+        currentSamples();
+        resident = false;
+        releaseParticles();
+    }
+    if (!particles) {
+        if (resident) throw std::logic_error("ParticleFrameLoop: the resident generation was lost with its particle set");
+        check(fd_particles_create_unbound(context(), FD_PARTICLES_MAX, &particles));
+    }
+    if (!resident) uploadGeneration();
+    const Mat& data = image->getData();
+    const bool tracked = flow && flow->beginResident(data, state);
+    SimpleTransitionModel* simple = flow ? static_cast<SimpleTransitionModel*>(flow->getFallback().get()) : nullptr;   // null: the sampler's own
+    SimpleTransitionModel::DrawState before;
+    if (tracked) before = simple->drawState();
+    const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows, simple);
+    const int copies = (int)(draws.diffusion.size() / 3), fresh = (int)(draws.fresh.size() / 3);
+    const int firstFreshId = Sample::nextClusterId;
+    Sample::nextClusterId += fresh;
+    if (tracked) {
+        const vector<double>& flowDiffusion = flow->drawResident((size_t)copies);
+        check(fd_particles_sample_flow(context(), particles, flow->native(), copies + fresh, copies, draws.u, flowDiffusion.data(), draws.diffusion.data(),
+                                       draws.fresh.data(), firstFreshId));
+    } else {
+        check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
+    }
+    model->evaluateResident(image, particles);
+    fd_particles_info info;
+    if (tracked) {
+        fd_flow_motion_info motion;
+        check(fd_particles_state_flow(context(), particles, flow->native(), &info, &motion));
+        flow->endResident(motion);
+        if (motion.ok) simple->restoreDrawState(before);   // the flow predicted: the fallback drew nothing
+    } else {
+        check(fd_particles_state(context(), particles, &info));
+    }
+    residentCount = info.count;
+    residentWeightSum = info.weight_sum;
+    materialized = false;
+    samples.clear();
+    oldSamples.clear();
+    state = info.found ? make_shared<Sample>(info.x, info.y, info.size, info.vx, info.vy, info.vsize) : shared_ptr<Sample>();
+}
+
 void ParticleFrameLoop::deviceStep() {
+    if (lastKind == ResidentKind::Integral) return integralDeviceStep();
     auto model = std::dynamic_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
     auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
     if (particles && particlesOn != model->native()) releaseParticles();   // the model was initialised again: another tracker handle
@@ -4172,24 +4375,7 @@ void ParticleFrameLoop::deviceStep() {
         particlesOn = model->native();
         if (resident) throw std::logic_error("ParticleFrameLoop: the resident generation was lost with its tracker");
     }
-    if (!resident) {   // the generation of the generic route (or of initialize) moves to the device
-        const int n = (int)samples.size();
-        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
-        vector<float> vsize(n);
-        vector<double> weight(n), score(n);
-        vector<uint8_t> target(n);
-        residentWeightSum = 0;
-        for (int i = 0; i < n; ++i) {
-            const Sample& s = *samples[i];
-            x[i] = s.getX(); y[i] = s.getY(); size[i] = s.getSize(); vx[i] = s.getVx(); vy[i] = s.getVy(); vsize[i] = s.getVSize();
-            weight[i] = s.getWeight(); score[i] = s.getScore(); target[i] = s.isTarget(); cluster[i] = s.getClusterId();
-            residentWeightSum += weight[i];
-        }
-        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
-        check(fd_particles_set(context(), particles, n, &arrays));
-        residentCount = n;
-        resident = true;
-    }
+    if (!resident) uploadGeneration();
     const Mat& data = image->getData();
     const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows);
     const int copies = (int)(draws.diffusion.size() / 3), fresh = (int)(draws.fresh.size() / 3);
@@ -4208,7 +4394,8 @@ void ParticleFrameLoop::deviceStep() {
 
 void ParticleFrameLoop::step(const Mat& imageData) {
     image->setData(imageData);
-    if (deviceRoutePossible()) {
+    lastKind = residentKind();
+    if (lastKind != ResidentKind::None) {
         lastRoute = Route::DEVICE;
         deviceStep();
         return;
@@ -4265,7 +4452,7 @@ boost::optional<cv::Rect> AdaptiveCondensationTracker::process(const Mat& imageD
         for (shared_ptr<StateValidator>& validator : validators) {
             const bool isModel = std::dynamic_pointer_cast<StateValidator>(measurementModel) == validator;
             static const vector<shared_ptr<Sample>> none;
-            const bool onDevice = getLastRoute() == Route::DEVICE && isModel;
+            const bool onDevice = samplesUnread() && isModel;
             if (!validator->isValid(*state, onDevice ? none : currentSamples(), image)) {
                 state.reset();
                 break;
@@ -4274,7 +4461,7 @@ boost::optional<cv::Rect> AdaptiveCondensationTracker::process(const Mat& imageD
     }
     // update model: ExtendedHogBasedMeasurementModel::adapt does not read the samples
     static const vector<shared_ptr<Sample>> unread;
-    const vector<shared_ptr<Sample>>& forAdapt = getLastRoute() == Route::DEVICE ? unread : currentSamples();
+    const vector<shared_ptr<Sample>>& forAdapt = samplesUnread() ? unread : currentSamples();
     if (state) adapted = adaptiveModel->adapt(image, forAdapt, *state);
     else adapted = adaptiveModel->adapt(image, forAdapt);
     if (state) return boost::optional<cv::Rect>(state->getBounds());

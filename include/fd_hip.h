@@ -1094,6 +1094,70 @@ int fd_integral_gradient_length(int rows, int cols);
 int fd_gradient_sum_length(int rows, int cols, int cell_rows, int cell_cols);
 int fd_surf_feature_length(int gradient_count, int cell_count);
 
+/* ---- the resident particle set (fd_particles, above) on the integral-feature models with an optical-flow transition
+ *  -----------------
+ * A frame of ResamplingSampler(LowVarianceSampling, OpticalFlowTransitionModel(fallback SimpleTransitionModel)) +
+ * SingleClassifierModel on a Haar / SURF / integral HOG extractor + FilteringStateExtractor(WeightedMeanStateExtractor) is
+ * fd_flow_update, fd_integral_update, fd_flow_track_fb_resident, fd_particles_sample_flow, _evaluate_integral, _weigh_classifier and
+ * _state_flow: one chain of kernels on the context's stream and one read-back. */
+/* A particle set like fd_particles_create's with no tracker.  fd_particles_evaluate on it is FD_ERR_RUNTIME (nothing is launched);
+ * every other call works on it unchanged. */
+int fd_particles_create_unbound(fd_ctx* ctx, int capacity, fd_particles** out);
+/* The wrapper chain of a feature extractor as data, outer to inner: what each wrapper asks its inner extractor for.
+ * FD_SAMPLE_MAP_RESIZE is PatchResizingFeatureExtractor (x = cvRound(x + x_offset * width), y = cvRound(y + y_offset * height),
+ * width = cvRound(factor * width), height = cvRound(factor * height), the sums and products in double, cvRound to the nearest even
+ * on a tie; a result outside the int range saturates, a NaN gives 0 -- the same on the host and on the device);
+ * FD_SAMPLE_MAP_INTEGRAL is IntegralFeatureExtractor (x, y += 1 where the width, height is odd; width, height += 1; sizes are expected
+ * below INT32_MAX). */
+enum { FD_SAMPLE_MAP_RESIZE = 0, FD_SAMPLE_MAP_INTEGRAL = 1 };
+#define FD_SAMPLE_MAPS_MAX 4
+typedef struct {
+    int32_t kind;                      /* FD_SAMPLE_MAP_* */
+    double factor, x_offset, y_offset; /* FD_SAMPLE_MAP_RESIZE only */
+} fd_sample_map;
+/* host only: the n_maps <= FD_SAMPLE_MAPS_MAX maps applied in order to each of the n samples {x, y, width, height}, in place */
+int fd_sample_maps_apply(const fd_sample_map* maps, int n_maps, int n, int32_t* xywh);
+/* SingleClassifierModel::evaluate's scoring for the current generation, nothing copied back: every sample {x, y, size,
+ * cvRound(aspect_ratio * size)} goes through the maps on the device into g's sample list, the kernels of
+ * fd_integral_svm_evaluate_samples (kind, params, svm as there) extract and score it, the distances become the generation's scores
+ * and the kernels' validity bytes the set's valid flags.  fd_particles_get_trace then reports the mapped {x, y, width, height} as
+ * the windows.  FD_ERR_INVALID_ARGUMENT for more than FD_SAMPLE_MAPS_MAX maps, an unknown map kind, an SVM that is u8 or of
+ * another dimension; FD_ERR_RUNTIME when g holds no image. */
+int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g, int kind, const void* params, const fd_svm* svm,
+                                   double aspect_ratio, const fd_sample_map* maps, int n_maps);
+/* SingleClassifierModel.cpp:32-42 on the scores of an _evaluate: a sample without a valid patch gets target 0, weight 0, score 0;
+ * any other target = score >= threshold and weight = p(score) with ProbabilisticSvmClassifier's logistic (a, b): the weight is set,
+ * not multiplied.  best_score, n_valid and bad_weight as fd_particles_weigh leaves them. */
+int fd_particles_weigh_classifier(fd_ctx* ctx, fd_particles* p, double logistic_a, double logistic_b, double threshold);
+/* OpticalFlowTransitionModel's median flow (fd_flow_median) as the device leaves it */
+typedef struct {
+    int32_t ok, n_valid, n_correct;
+    float median_x, median_y, median_ratio;
+} fd_flow_motion_info;
+#define FD_FLOW_RESIDENT_MAX_POINTS 1024
+/* fd_flow_track_fb whose results stay on the device: uploads the n <= FD_FLOW_RESIDENT_MAX_POINTS points, queues both trackings and
+ * the median flow of the tracks (fd_flow_median's values, bit for bit; a median that is a NaN is the default NaN) and waits for
+ * nothing.  FD_ERR_RUNTIME before the second fd_flow_update. */
+int fd_flow_track_fb_resident(fd_ctx* ctx, fd_flow* flow, const float* pts_xy, int n);
+/* what the last fd_flow_track_fb_resident left (FD_ERR_RUNTIME without one): fwd, bwd (2 n floats each), the status bytes, and
+ * order / *n_valid / *n_correct as fd_flow_median reports them (the order is computed on the host from the downloaded tracks).  Any
+ * pointer may be NULL; *n receives the point count.  Waits; not for the frame path. */
+int fd_flow_get_tracks(fd_ctx* ctx, fd_flow* flow, int cap, int* n, float* fwd, float* bwd, uint8_t* fstatus, uint8_t* bstatus, int32_t* order,
+                       int* n_valid, int* n_correct);
+/* test hook: the median-flow kernel on the caller's arrays (host memory, n <= FD_FLOW_RESIDENT_MAX_POINTS); the result is written to
+ * *out and stays in the handle as the motion of a resident track does (fd_flow_get_tracks does not see these arrays) */
+int fd_debug_flow_motion(fd_ctx* ctx, fd_flow* flow, const float* pts, const float* fwd, const float* bwd, const uint8_t* fstatus,
+                         const uint8_t* bstatus, int n, fd_flow_motion_info* out);
+/* fd_particles_sample with the motion the flow handle holds on the device (fd_flow_track_fb_resident): where it is ok, copy i is moved as
+ * OpticalFlowTransitionModel::predict moves it (.cpp:173-190: vx = median_x + d0, vy = median_y + d1, vsize = median_ratio * d2 in
+ * double with flow_diffusion[3 i .. 3 i + 2] = {positionDeviation * z, positionDeviation * z, pow(2, sizeDeviation * z)}),
+ * otherwise as fd_particles_sample moves it with fallback_diffusion.  The device takes the branch; both blocks hold
+ * 3 * n_resampled draws.  FD_ERR_RUNTIME when the flow handle holds no motion. */
+int fd_particles_sample_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, int count, int n_resampled, double u, const double* flow_diffusion,
+                             const double* fallback_diffusion, const int32_t* fresh, int32_t first_fresh_cluster_id);
+/* fd_particles_state that brings the flow handle's motion back in the same wait: the one read-back of such a frame */
+int fd_particles_state_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_particles_info* info, fd_flow_motion_info* motion);
+
 /* ---- classification::RvmClassifier / ProbabilisticRvmClassifier -----------------
  * Cascaded reduced-vector machine (RvmClassifier.cpp:75-126): level k evaluates kernel(x, rsv_k) on the whole
  * vector; through the reference's cached path the running distance is d_0 = -bias + c[0][0] K_0,
