@@ -13,7 +13,8 @@ LIB_PATH = os.environ.get("FD_HIP_LIB", os.path.join(_HERE, "libfd_hip.so"))   #
 
 FD_OK, FD_ERR_INVALID_ARGUMENT, FD_ERR_RUNTIME, FD_ERR_LOGIC, FD_ERR_HIP, FD_ERR_CAPACITY, FD_ERR_DEVICE_CAPACITY = range(7)
 FD_LAYER_NONE, FD_LAYER_GRADBIN, FD_LAYER_LBP, FD_LAYER_GRADMAG_LBP = 0, 1, 2, 3
-FD_SAMPLES_HIST, FD_SAMPLES_EHOG = 0, 1
+FD_SAMPLES_HIST, FD_SAMPLES_EHOG, FD_SAMPLES_PATCH = 0, 1, 2
+FD_SAMPLE_TABLE_MAX = 65536
 FD_HIST_SAMPLES_MAX = 1 << 20
 IMAGE_GRAY, IMAGE_GREYWORLD_GRAY = 0, 1   # fd_pyramid_set_image_filter
 FD_KERNEL_LINEAR, FD_KERNEL_POLY, FD_KERNEL_RBF, FD_KERNEL_HIK = 0, 1, 2, 3
@@ -427,6 +428,8 @@ _SIGS = {
     "fd_sample_maps_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "fd_particles_evaluate_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
     "fd_particles_weigh_classifier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "fd_particles_evaluate_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
+    "fd_sample_layer_table": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fd_flow_track_fb_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fd_flow_get_tracks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1552,6 +1555,18 @@ class Particles:
         chain = sample_maps(maps)
         self.ctx.check(lib().fd_particles_evaluate_integral(self.ctx.h, self.h, integral.h, kind, prm, svm.h, aspect_ratio, chain, len(chain)))
 
+    def evaluate_pyramid(self, pyr, svm, aspect_ratio, maps=(), hist=None, ehog=None, patch=None):
+        """fd_particles_evaluate_pyramid on an updated Pyramid: exactly one of hist (fd_hist_params), ehog (fd_ehog_patch_params) and patch
+        (fd_patch_samples_params), as hist_svm_evaluate_samples / patch_svm_evaluate_samples take them; maps a sequence of ("resize",
+        factor, x_offset, y_offset) from the outermost wrapper in"""
+        given = [(FD_SAMPLES_HIST, hist), (FD_SAMPLES_EHOG, ehog), (FD_SAMPLES_PATCH, patch)]
+        given = [(kind, prm) for kind, prm in given if prm is not None]
+        if len(given) != 1:
+            raise ValueError("exactly one of hist, ehog and patch")
+        kind, prm = given[0]
+        chain = sample_maps(maps)
+        self.ctx.check(lib().fd_particles_evaluate_pyramid(self.ctx.h, self.h, pyr.h, kind, C.byref(prm), svm.h, aspect_ratio, chain, len(chain)))
+
     def weigh_classifier(self, logistic_a, logistic_b, threshold):
         self.ctx.check(lib().fd_particles_weigh_classifier(self.ctx.h, self.h, logistic_a, logistic_b, threshold))
 
@@ -2529,6 +2544,22 @@ def sample_windows(layers, inc, pw, ph, samples):
     if rc != FD_OK:
         raise FdError(rc, "fd_sample_windows: invalid arguments")
     return out
+
+
+def sample_layer_table(n_layers, first_index, inc, patch_w, cap=FD_SAMPLE_TABLE_MAX):
+    """fd_sample_layer_table (host only): int16[length], entry w the position in the kept-layer list of a sample of width w, -1 for
+    none.  FdError FD_ERR_CAPACITY (with .length, the entries it needs) when the table is longer than cap"""
+    length = C.c_int(0)
+    table = np.zeros(0, np.int16)
+    rc = lib().fd_sample_layer_table(n_layers, first_index, inc, patch_w, 0, None, C.byref(length))
+    if rc in (FD_OK, FD_ERR_CAPACITY) and length.value <= cap:
+        table = np.zeros(length.value, np.int16)
+        rc = lib().fd_sample_layer_table(n_layers, first_index, inc, patch_w, len(table), _ptr(table), C.byref(length))
+    if rc != FD_OK:
+        e = FdError(rc, "fd_sample_layer_table: %s" % ("a table of %d entries" % length.value if rc == FD_ERR_CAPACITY else "invalid arguments"))
+        e.length = length.value
+        raise e
+    return table
 
 
 def hist_samples_limits():

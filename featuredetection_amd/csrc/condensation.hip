@@ -4,13 +4,16 @@
 // ExtendedHogBasedMeasurementModel's weighting (.cpp:173-205) and of FilteringStateExtractor(WeightedMeanStateExtractor)
 // (WeightedMeanStateExtractor.cpp:23-62).  The scoring of the samples is the tracker's (ehog_tracker.hpp).  A set without a tracker serves
 // SingleClassifierModel on the integral family (scored by integral.hip, weighed by k_particles_weigh's classifier mode) and
-// OpticalFlowTransitionModel::predict (k_particles_sample with the motion optflow.hip leaves on the device).  DESIGN.md 4.7.
+// OpticalFlowTransitionModel::predict (k_particles_sample with the motion optflow.hip leaves on the device), and SingleClassifierModel
+// on the pyramid families: fd_particles_evaluate_pyramid resolves the samples to windows here (particle_windows.hpp) and hands the list to
+// the scoring kernels of hog.hip / rvm.hip.  DESIGN.md 4.7.
 //
 // Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
 // needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
 // against them, so another association would select other samples); they are walked by single lanes in LDS, everything around them
 // is parallel.  All loops are counted; nothing waits on another workgroup.
 #include "fd_internal.hpp"
+#include "particle_windows.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -265,6 +268,7 @@ struct fd_particles {
     bool sumKnown = true, bad = false, evaluated = false;
     double sum = 0.0;   // the weights of the current generation added in index order, when sumKnown
     DevBuf arena, staging, dinfo;
+    DevBuf list;   // fd_particles_evaluate_pyramid: the window {layer, bx, by} of every sample, slot i for sample i
     ParticleGen gen[2];
     int32_t* source = nullptr;
     int32_t* windows = nullptr;   // per sample {layer, bx, by, valid} of fd_particles_evaluate, or the mapped {x, y, width, height} of _evaluate_integral
@@ -388,7 +392,7 @@ void particles_sample(fd_ctx* ctx, fd_particles* p, const char* who, fd_flow* fl
 
 void particles_weigh(fd_ctx* ctx, fd_particles* p, const char* who, double logistic_a, double logistic_b, double svm_threshold, int mode,
                      double rejection_threshold) {
-    if (!p->evaluated) FD_THROW(FD_ERR_RUNTIME, "%s: the generation has not been evaluated (fd_particles_evaluate, _evaluate_integral)", who);
+    if (!p->evaluated) FD_THROW(FD_ERR_RUNTIME, "%s: the generation has not been evaluated (fd_particles_evaluate, _evaluate_integral, _evaluate_pyramid)", who);
     hipLaunchKernelGGL(k_particles_weigh, dim3(1), dim3(PT), 0, ctx->stream, p->gen[p->cur], p->n, p->valid, logistic_a, logistic_b, svm_threshold, mode,
                        rejection_threshold, p->dinfo.as<fd_particles_info>());
     HIP_CHECK(hipGetLastError());
@@ -518,6 +522,56 @@ int fd_particles_evaluate(fd_ctx* ctx, fd_particles* p, int use_patches, double 
         if (!p->tracker) FD_THROW(FD_ERR_RUNTIME, "fd_particles_evaluate: the set is bound to no tracker (fd_particles_create_unbound)");
         const ParticleGen& G = p->gen[p->cur];
         fd_ehog_tracker_score_particles(ctx, p->tracker, p->n, G.x, G.y, G.size, aspect_ratio, use_patches != 0, p->windows, p->valid, G.score);
+        p->evaluated = true;
+    });
+}
+
+int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int kind, const void* params, const fd_svm* svm, double aspect_ratio,
+                                  const fd_sample_map* maps, int n_maps) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_evaluate_pyramid";
+        if (!ctx || !p || !pyr || !params || !svm || n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
+        FdSampleMaps chain;
+        std::memset(&chain, 0, sizeof(chain));
+        chain.n = n_maps;
+        for (int k = 0; k < n_maps; ++k) {
+            if (maps[k].kind != FD_SAMPLE_MAP_RESIZE)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: sample map kind %d; a pyramid chain takes FD_SAMPLE_MAP_RESIZE only", who, maps[k].kind);
+            chain.m[k] = maps[k];
+        }
+        if (kind != FD_SAMPLES_HIST && kind != FD_SAMPLES_EHOG && kind != FD_SAMPLES_PATCH) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
+        particles_checked(ctx, p, who);
+        if (pyr->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: objects belong to different contexts", who);
+        fd_pyramid_require_single(pyr, who);
+        fd_pyramid_require_image(pyr);
+        if (pyr->kept.size() > (size_t)FD_WIN_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: too many pyramid layers (%zu)", who, pyr->kept.size());
+        const int n = p->n;
+        const ParticleGen& G = p->gen[p->cur];
+        auto score_list = [&](const int32_t* dlist, int* pw, int* ph) {   // dlist NULL: the argument rules alone
+            if (kind == FD_SAMPLES_PATCH) fd_patch_samples_score_list(ctx, pyr, (const fd_patch_samples_params*)params, svm, who, dlist, n, G.score, pw, ph);
+            else fd_hist_samples_score_list(ctx, pyr, kind, params, svm, who, dlist, n, G.score, pw, ph);
+        };
+        int pw = 0, ph = 0;
+        score_list(nullptr, &pw, &ph);
+        particle_windows_table(ctx, pyr, pw, who);
+        if (n > 0) {
+            ParticleLayers layers;
+            std::memset(&layers, 0, sizeof(layers));
+            layers.n = (int32_t)pyr->kept.size();
+            FdSampleWindow spare{-1, 0, 0};   // the first kept layer that holds a window at all
+            for (int l = 0; l < layers.n; ++l) {
+                const HostLayer& L = pyr->all[pyr->kept[l]];
+                layers.l[l].scale = L.scale; layers.l[l].w = L.w; layers.l[l].h = L.h;
+                if (spare.layer < 0 && L.w >= pw && L.h >= ph) spare.layer = l;
+            }
+            p->list.reserve(sizeof(int32_t) * 3 * (size_t)p->capacity);
+            hipLaunchKernelGGL(k_particles_windows, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, G.x, G.y, G.size, n, aspect_ratio, chain, layers,
+                               pyr->sample_table.dev.as<int16_t>(), pyr->sample_table.length, pw, ph, spare, p->list.as<int32_t>(), (int4*)p->windows,
+                               p->valid);
+            HIP_CHECK(hipGetLastError());
+            if (spare.layer >= 0) score_list(p->list.as<int32_t>(), &pw, &ph);   // otherwise no layer holds a window: every sample is invalid
+        }
         p->evaluated = true;
     });
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -377,6 +378,18 @@ struct FdStreamSwap {   // temporarily redirects everything that launches on ctx
 };
 
 static inline int fd_cvRound(double v) { return (int)std::lrint(v); }  // cvRound: half-to-even
+// cvRound on the host and on the device (the sample maps and the window placement below): to the nearest even on a tie on both sides.
+// A value outside the int range saturates and a NaN gives 0 on both sides (what the device's conversion does by itself).
+__host__ __device__ inline int fd_sample_cvround(double v) {
+    if (!(v == v)) return 0;
+    if (v >= 2147483647.0) return INT32_MAX;
+    if (v <= -2147483648.0) return INT32_MIN;
+#ifdef __HIP_DEVICE_COMPILE__
+    return __double2int_rn(v);
+#else
+    return fd_cvRound(v);
+#endif
+}
 
 // ---------------- pyramid ----------------
 struct LayerDesc {          // device-visible layer descriptor
@@ -444,6 +457,14 @@ struct fd_pyramid {
     // batch entry points) wait for it; consumers on the same stream are ordered anyway
     hipEvent_t ready = nullptr;
     hipStream_t readyStream = nullptr;
+    // fd_particles_evaluate_pyramid: the uploaded width -> layer table (fd_sample_layer_table) of the patch width and kept-layer layout
+    // it was built for; rebuilt only when one of them changes
+    struct SampleTable {
+        DevBuf dev;
+        std::vector<int16_t> host;   // what the upload reads
+        int length = -1, patch_w = 0, n_layers = 0, first_index = 0;
+        double inc = 0.0;
+    } sample_table;
     ~fd_pyramid();                   // pyramid.hip, where Plan is complete (handles are created and destroyed only there)
 };
 
@@ -465,23 +486,36 @@ static inline void fd_pyramid_wait(const fd_pyramid* p, hipStream_t consumer) {
 // 134-153; ImagePyramid::getLayer(double), ImagePyramid.hpp:307-310), stated once: the layer with pyramid index
 // lround(log(patch_w / width) / log(inc)) must be a kept one (the kept layers have consecutive indices from first_index on);
 // layer(pos, scale, w, h) reports the kept layer at list position pos.  Returns false for a sample without a window.
+// The rule has two parts.  (a) fd_sample_layer_position, width -> layer, goes through libm's log and is the host's alone: the device reads
+// it from a table of the host's values (fd_sample_layer_table).  (b) fd_sample_place, the window in that layer, is exact arithmetic (one
+// double product, one rounding to the nearest even) and gives the same bits on both sides.
 struct FdSampleWindow { int32_t layer, bx, by; };
+// (a) the list position of the layer a sample of this width (> 0) is taken from, before the range check: below 0 or from the layer count
+// on there is none.  An index that is not finite or not representable is reported on the side its sign names.
+static inline long fd_sample_layer_position(int first_index, double inc, int pw, int width) {
+    const double power = std::log((double)pw / (double)width) / std::log(inc);
+    if (!(std::fabs(power) < 1e9)) return power > 0 ? LONG_MAX : LONG_MIN;   // not a finite, representable index
+    const long index = std::lround(power);   // std::round, then the int cast of the reference
+    return index - first_index;
+}
+// (b) the pw x ph window of the sample in a layer of lw x lh pixels; false: it does not lie inside
+__host__ __device__ inline bool fd_sample_place(double scale, int lw, int lh, int pw, int ph, int x, int y, int width, int height, int32_t& bx, int32_t& by) {
+    const double fx = (double)((int64_t)x - width / 2) * scale, fy = (double)((int64_t)y - height / 2) * scale;
+    if (!(fx >= -1.0 && fx <= (double)lw && fy >= -1.0 && fy <= (double)lh)) return false;   // far outside (and nothing the int cast could wrap)
+    bx = fd_sample_cvround(fx); by = fd_sample_cvround(fy);   // inside [-1, lw]: fd_cvRound on the host
+    return !(bx < 0 || by < 0 || (int64_t)bx + pw > lw || (int64_t)by + ph > lh);
+}
 template <class LayerAt>
 static inline bool fd_sample_window(int n_layers, int first_index, double inc, int pw, int ph, int x, int y, int width, int height, LayerAt&& layer,
                                     FdSampleWindow& out) {
     if (width <= 0 || n_layers <= 0) return false;
-    const double power = std::log((double)pw / (double)width) / std::log(inc);
-    if (!(std::fabs(power) < 1e9)) return false;   // not a finite, representable index
-    const long index = std::lround(power);   // std::round, then the int cast of the reference
-    const long realIndex = index - first_index;
+    const long realIndex = fd_sample_layer_position(first_index, inc, pw, width);
     if (realIndex < 0 || realIndex >= (long)n_layers) return false;
     double scale;
     int lw, lh;
     layer((int)realIndex, scale, lw, lh);
-    const double fx = (double)((int64_t)x - width / 2) * scale, fy = (double)((int64_t)y - height / 2) * scale;
-    if (!(fx >= -1.0 && fx <= (double)lw && fy >= -1.0 && fy <= (double)lh)) return false;   // far outside (and nothing the int cast could wrap)
-    const int bx = fd_cvRound(fx), by = fd_cvRound(fy);
-    if (bx < 0 || by < 0 || (int64_t)bx + pw > lw || (int64_t)by + ph > lh) return false;
+    int32_t bx, by;
+    if (!fd_sample_place(scale, lw, lh, pw, ph, x, y, width, height, bx, by)) return false;
     out.layer = (int32_t)realIndex; out.bx = bx; out.by = by;
     return true;
 }
@@ -657,18 +691,7 @@ struct FdParticlesView {
 };
 // one wrapper's map of a sample {x, y, width, height} (fd_sample_map, fd_hip.h): PatchResizingFeatureExtractor::mapSample and
 // IntegralFeatureExtractor::mapSample, the one copy of these expressions for the host (fd_sample_maps_apply) and the device
-// (k_particles_xywh).  cvRound is to the nearest even on a tie on both sides; the sums and products are doubles in this order.
-// A value outside the int range saturates and a NaN gives 0 on both sides (what the device's conversion does by itself).
-__host__ __device__ inline int fd_sample_cvround(double v) {
-    if (!(v == v)) return 0;
-    if (v >= 2147483647.0) return INT32_MAX;
-    if (v <= -2147483648.0) return INT32_MIN;
-#ifdef __HIP_DEVICE_COMPILE__
-    return __double2int_rn(v);
-#else
-    return fd_cvRound(v);
-#endif
-}
+// (k_particles_xywh, k_particles_windows).  cvRound is fd_sample_cvround; the sums and products are doubles in this order.
 __host__ __device__ inline void fd_sample_map_apply(const fd_sample_map& m, int32_t& x, int32_t& y, int32_t& width, int32_t& height) {
     if (m.kind == FD_SAMPLE_MAP_RESIZE) {
         x = fd_sample_cvround(x + m.x_offset * width);
@@ -682,8 +705,22 @@ __host__ __device__ inline void fd_sample_map_apply(const fd_sample_map& m, int3
         height += 1;
     }
 }
+// the wrapper chain of a call as a kernel argument
+struct FdSampleMaps {
+    int32_t n;
+    fd_sample_map m[FD_SAMPLE_MAPS_MAX];
+};
 FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who);
 void fd_particles_set_evaluated(fd_particles* p);
+// ---- resident particle set on the pyramid families (condensation.hip launches k_particles_windows; the scoring kernels are hog.hip's and rvm.hip's) ----
+// "Score this device list of n windows {layer, bx, by} of p into this device score array": the kernels of fd_hist_svm_evaluate_samples
+// (kind FD_SAMPLES_HIST / FD_SAMPLES_EHOG, hog.hip) and of fd_patch_svm_evaluate_samples (rvm.hip) and the SVM launch, queued on
+// ctx->stream, no host wait.  Every argument rule of those entry points is checked first (FdError, nothing queued); with dlist NULL that is
+// all the call does.  patch_w / patch_h receive the window size of the parameters.
+void fd_hist_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, int kind, const void* params, const fd_svm* svm, const char* who, const int32_t* dlist,
+                                int n, double* dscore, int* patch_w, int* patch_h);
+void fd_patch_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const fd_svm* svm, const char* who,
+                                 const int32_t* dlist, int n, double* dscore, int* patch_w, int* patch_h);
 // the motion a resident track (or fd_debug_flow_motion) left in the handle (device memory); checks flow against ctx, throws FdError
 // (FD_ERR_RUNTIME) when there is none
 const fd_flow_motion_info* fd_flow_device_motion(fd_ctx* ctx, fd_flow* flow, const char* who);

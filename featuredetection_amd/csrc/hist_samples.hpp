@@ -47,11 +47,11 @@ void* samples_upload(fd_ctx* ctx, const fd_pyramid* p, const SamplesPlan& pl, in
     return fd_samples_upload(ctx, p, pl.hp.patch_w, pl.hp.patch_h, n, xywh, valid, S.list, sampleOf, extraPinnedPerValid);
 }
 
-// the features of the nv listed windows, [nv][pl.F] floats on the device: queued on ctx->stream
-const float* samples_features(fd_ctx* ctx, const fd_pyramid* p, const SamplesPlan& pl, int64_t nv, HogScratch& S) {
+// the features of the nv windows listed at dlist (device), [nv][pl.F] floats on the device: queued on ctx->stream
+const float* samples_features(fd_ctx* ctx, const fd_pyramid* p, const SamplesPlan& pl, const int32_t* dlist, int64_t nv, HogScratch& S) {
     fd_pyramid_wait(p, ctx->stream);
     FdWinTable wt;
-    fd_win_table_list(p, S.list.as<int32_t>(), nv, /*filtered=*/true, wt);
+    fd_win_table_list(p, dlist, nv, /*filtered=*/true, wt);
     launch_hist_features(ctx, p->arena.as<uint8_t>(), wt, pl.hd, S);
     if (!pl.ehog) return S.feat.as<float>();
     const int64_t total = nv * pl.F;   // S.feat: the raw cell histograms, as in fd_ehog_patch_batch
@@ -73,10 +73,20 @@ void extract_samples(fd_ctx* ctx, fd_pyramid* p, int kind, const void* params, i
     samples_upload(ctx, p, pl, n, xywh, valid, S, sampleOf, 0);
     const int64_t nv = (int64_t)sampleOf.size();
     if (nv == 0 || !features) return;
-    fd_samples_rows_to_host(ctx, samples_features(ctx, p, pl, nv, S), pl.F, nv, n, sampleOf, features);
+    fd_samples_rows_to_host(ctx, samples_features(ctx, p, pl, S.list.as<int32_t>(), nv, S), pl.F, nv, n, sampleOf, features);
 }
 
 }  // namespace
+
+// the resident particle set's bridge (fd_internal.hpp): the argument rules of fd_hist_svm_evaluate_samples, then its kernels on the list
+void fd_hist_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, int kind, const void* params, const fd_svm* svm, const char* who, const int32_t* dlist,
+                                int n, double* dscore, int* patch_w, int* patch_h) {
+    const SamplesPlan pl = samples_plan(ctx, p, kind, params, n, who);
+    fd_samples_require_f32_svm(svm, pl.F, who);
+    *patch_w = pl.hp.patch_w; *patch_h = pl.hp.patch_h;
+    if (!dlist || n == 0) return;
+    fd_svm_generic_launch(ctx, svm, samples_features(ctx, p, pl, dlist, n, scratch(ctx)), nullptr, (int64_t)pl.F * 4, n, dscore);
+}
 
 extern "C" {
 
@@ -140,7 +150,7 @@ int fd_hist_svm_evaluate_samples_distance(fd_ctx* ctx, fd_pyramid* p, int kind, 
         double* hdist = (double*)samples_upload(ctx, p, pl, n, xywh, nullptr, S, sampleOf, sizeof(double));
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0) return;
-        fd_samples_svm_tail(ctx, svm, samples_features(ctx, p, pl, nv, S), pl.F, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight, distance);
+        fd_samples_svm_tail(ctx, svm, samples_features(ctx, p, pl, S.list.as<int32_t>(), nv, S), pl.F, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight, distance);
     });
 }
 

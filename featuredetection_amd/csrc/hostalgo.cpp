@@ -521,6 +521,35 @@ extern "C" int fd_sample_maps_apply(const fd_sample_map* maps, int n_maps, int n
     return FD_OK;
 }
 
+// ---- part (a) of the sample -> window rule as a table for the device (k_particles_windows): fd_sample_layer_position, the function
+// fd_sample_window itself calls, evaluated once per width ----
+extern "C" int fd_sample_layer_table(int n_layers, int first_index, double incremental_scale, int patch_w, int cap, int16_t* layer_of_width, int* length) {
+    if (n_layers < 0 || n_layers > INT16_MAX || patch_w < 1 || !(incremental_scale > 0 && incremental_scale < 1) || cap < 0 || !length ||
+        (cap > 0 && !layer_of_width))
+        return FD_ERR_INVALID_ARGUMENT;
+    auto position = [&](int width) { return fd_sample_layer_position(first_index, incremental_scale, patch_w, width); };
+    // The largest width that maps to a kept layer.  The position does not decrease with the width: patch_w / width of neighbouring
+    // widths differs by 2^-31 of its value or more, log's error stays below 2^-52 of its value.  So the widths whose position lies below
+    // n_layers are the ones up to some width, which a bisection with the function itself finds; that width maps to a kept layer, or none does.
+    int last = 0;
+    if (n_layers > 0 && position(1) < (long)n_layers) {
+        int lo = 1, hi = INT32_MAX;
+        while (lo < hi) {
+            const int mid = lo + (int)(((int64_t)hi - lo + 1) / 2);
+            if (position(mid) < (long)n_layers) lo = mid;
+            else hi = mid - 1;
+        }
+        if (position(lo) >= 0) last = lo;
+    }
+    *length = last == INT32_MAX ? INT32_MAX : (last > 0 ? last + 1 : 0);
+    if (*length > cap) return FD_ERR_CAPACITY;
+    for (int w = 0; w < *length; ++w) {
+        const long pos = w > 0 ? position(w) : -1;
+        layer_of_width[w] = pos >= 0 && pos < (long)n_layers ? (int16_t)pos : (int16_t)-1;
+    }
+    return FD_OK;
+}
+
 // ---- OpticalFlowTransitionModel's host arithmetic; the tracking itself is optflow.hip ----
 
 // OpticalFlowTransitionModel.cpp:63-75, operation for operation: gridPoint's first value is formed in double (0.5 * gridX is a double

@@ -262,12 +262,8 @@ __global__ __launch_bounds__(256) void k_surf(const int32_t* __restrict__ img, i
 // the samples of a resident particle set (x, y, size; height = cvRound(aspect * size), Sample.hpp:127-129) through the wrapper
 // chain of their feature extractor (outer to inner) into the sample list the kernels above read; `trace` keeps a copy for
 // fd_particles_get_trace
-struct SampleMaps {
-    int32_t n;
-    fd_sample_map m[FD_SAMPLE_MAPS_MAX];
-};
 __global__ __launch_bounds__(256) void k_particles_xywh(const int32_t* __restrict__ x, const int32_t* __restrict__ y, const int32_t* __restrict__ size, int n,
-                                                        double aspect, SampleMaps maps, int4* __restrict__ xywh, int4* __restrict__ trace) {
+                                                        double aspect, FdSampleMaps maps, int4* __restrict__ xywh, int4* __restrict__ trace) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int32_t sx = x[i], sy = y[i], sw = size[i], sh = fd_sample_cvround(aspect * (double)sw);
@@ -614,7 +610,7 @@ int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g,
         static const char* const who = "fd_particles_evaluate_integral";
         if (!ctx || !p || !g || !params || !svm || n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
         if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
-        SampleMaps chain;
+        FdSampleMaps chain;
         std::memset(&chain, 0, sizeof(chain));
         chain.n = n_maps;
         for (int k = 0; k < n_maps; ++k) {

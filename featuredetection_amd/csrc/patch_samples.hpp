@@ -102,31 +102,41 @@ __global__ __launch_bounds__(256) void k_rvm_samples(const uint8_t* __restrict__
     }
 }
 
-// the u8 rows of the nv listed windows into S.u8 (GRAY / HQ64 / HISTEQ): k_window_patches in list mode
-void patch_u8_rows(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, int64_t nv, PatchScratch& S) {
+// the u8 rows of the nv windows listed at dlist (device) into S.u8 (GRAY / HQ64 / HISTEQ): k_window_patches in list mode
+void patch_u8_rows(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const int32_t* dlist, int64_t nv, PatchScratch& S) {
     const int dim = pp->patch_w * pp->patch_h;
     FdWinTable wt;
-    fd_win_table_list(p, S.list.as<int32_t>(), nv, /*filtered=*/false, wt);
+    fd_win_table_list(p, dlist, nv, /*filtered=*/false, wt);
     S.u8.reserve((size_t)nv * dim + 16);
     hipLaunchKernelGGL(k_window_patches, dim3((unsigned)std::min<int64_t>(nv, (int64_t)ctx->num_cus * 32)), dim3(64), 0, ctx->stream,
                        p->arena.as<uint8_t>(), wt, pp->patch_w, pp->patch_h, pp->feature_space, S.u8.as<uint8_t>());
     HIP_CHECK(hipGetLastError());
 }
 
-// the f32 feature rows of the nv listed windows, [nv][dim] on the device: queued on ctx->stream
-const float* patch_f32_rows(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, int64_t nv, PatchScratch& S) {
+// the f32 feature rows of the nv windows listed at dlist (device), [nv][dim] on the device: queued on ctx->stream
+const float* patch_f32_rows(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const int32_t* dlist, int64_t nv, PatchScratch& S) {
     const int dim = pp->patch_w * pp->patch_h;
     S.feat.reserve(sizeof(float) * (size_t)nv * dim);
     if (pp->feature_space == FD_FEATURE_WHI) {
-        fd_whi_list_launch(ctx, p, S.list.as<int32_t>(), nv, pp->patch_w, pp->patch_h, pp->whi_alpha, pp->whi_cutoff, S.feat.as<float>());
+        fd_whi_list_launch(ctx, p, dlist, nv, pp->patch_w, pp->patch_h, pp->whi_alpha, pp->whi_cutoff, S.feat.as<float>());
     } else {
-        patch_u8_rows(ctx, p, pp, nv, S);
+        patch_u8_rows(ctx, p, pp, dlist, nv, S);
         fd_convert_u8_f32_launch(ctx, S.u8.as<uint8_t>(), nv * dim, pp->conv_scale, pp->conv_shift, S.feat.as<float>());
     }
     return S.feat.as<float>();
 }
 
 }  // namespace
+
+// the resident particle set's bridge (fd_internal.hpp): the argument rules of fd_patch_svm_evaluate_samples, then its kernels on the list
+void fd_patch_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const fd_svm* svm, const char* who,
+                                 const int32_t* dlist, int n, double* dscore, int* patch_w, int* patch_h) {
+    patch_samples_check(ctx, p, pp, n, nullptr, svm, who);
+    *patch_w = pp->patch_w; *patch_h = pp->patch_h;
+    if (!dlist || n == 0) return;
+    fd_pyramid_wait(p, ctx->stream);
+    fd_svm_generic_launch(ctx, svm, patch_f32_rows(ctx, p, pp, dlist, n, patch_scratch(ctx)), nullptr, (int64_t)pp->patch_w * pp->patch_h * 4, n, dscore);
+}
 
 extern "C" {
 
@@ -147,7 +157,7 @@ int fd_patch_extract_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0 || !features) return;
         fd_pyramid_wait(p, ctx->stream);
-        fd_samples_rows_to_host(ctx, patch_f32_rows(ctx, p, pp, nv, S), dim, nv, n, sampleOf, features);
+        fd_samples_rows_to_host(ctx, patch_f32_rows(ctx, p, pp, S.list.as<int32_t>(), nv, S), dim, nv, n, sampleOf, features);
     });
 }
 
@@ -165,7 +175,7 @@ int fd_patch_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_sam
         const int64_t nv = (int64_t)sampleOf.size();
         if (nv == 0) return;
         fd_pyramid_wait(p, ctx->stream);
-        fd_samples_svm_tail(ctx, svm, patch_f32_rows(ctx, p, pp, nv, S), pp->patch_w * pp->patch_h, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight,
+        fd_samples_svm_tail(ctx, svm, patch_f32_rows(ctx, p, pp, S.list.as<int32_t>(), nv, S), pp->patch_w * pp->patch_h, nv, S.dist, hdist, sampleOf.data(), nullptr, target, weight,
                             distance);
     });
 }
@@ -204,9 +214,9 @@ int fd_patch_rvm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_sam
             HIP_CHECK(hipMemcpyAsync(hout, S.dist.p, sizeof(PatchRvmOut) * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));
         } else {
             if (pp->feature_space == FD_FEATURE_WHI) {
-                run_cascade<false>(ctx, m, patch_f32_rows(ctx, p, pp, nv, S), (int64_t)dim * 4, 1.f, 0.f, nv, true, 0u);
+                run_cascade<false>(ctx, m, patch_f32_rows(ctx, p, pp, S.list.as<int32_t>(), nv, S), (int64_t)dim * 4, 1.f, 0.f, nv, true, 0u);
             } else {
-                patch_u8_rows(ctx, p, pp, nv, S);
+                patch_u8_rows(ctx, p, pp, S.list.as<int32_t>(), nv, S);
                 run_cascade<true>(ctx, m, S.u8.p, (int64_t)dim, pp->conv_scale, pp->conv_shift, nv, true, 0u);
             }
             HIP_CHECK(hipMemcpyAsync(hdist, m->dist.p, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, ctx->stream));

@@ -2,7 +2,7 @@
 // a condensation::AdaptiveCondensationTracker on ResamplingSampler(LowVarianceSampling, SimpleTransitionModel or OpticalFlowTransitionModel)
 // or GridSampler, an
 // ExtendedHogBasedMeasurementModel and FilteringStateExtractor(WeightedMeanStateExtractor).
-//   usage: tracker_app [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
+//   usage: tracker_app [--counts] [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
 // config (boost info format), the `tracking` block of algorithm.cfg:
 //   tracking {
 //     transition simple { positionDeviation 10  sizeDeviation 0.1 }
@@ -34,6 +34,8 @@
 // With --dump every frame is followed by "draws u <0|1> <u> copies <n> fresh <m>", one "d <dx> <dy> <factor>" per copy, one "f <x> <y>
 // <size>" per random sample, "samples <n>" and one "s <x> <y> <size> <vx> <vy> <vsize> <weight> <score> <target> <clusterId>" per sample
 // (%.17g / %.9g: the values round-trip), so that tests/condensation_model.py can replay the run.
+// With --counts (before --dump) a last line "evaluations fused <n> loop <m>" reports, for `measurement positionDependent` on a
+// SingleClassifierModel, how many batched evaluations scored their samples in device calls and how many in the per-sample loop.
 //   tracker_app --selftest <seed> <frames> <count> <randomRate>
 // runs the samplers, the transition model and the extractors without a device: a CondensationTracker on a stub measurement model that
 // weighs a sample by its distance to a moving point, on 64 x 48 frames; it dumps every frame as above, and the GridSampler's samples.
@@ -161,10 +163,11 @@ static int selftest(int argc, char** argv) {
 int main(int argc, char** argv) {
     try {
         if (argc > 1 && string(argv[1]) == "--selftest") return selftest(argc, argv);
-        const bool dumping = argc > 1 && string(argv[1]) == "--dump";
-        const int a = dumping ? 2 : 1;
+        const bool counting = argc > 1 && string(argv[1]) == "--counts";
+        const bool dumping = argc > (counting ? 2 : 1) && string(argv[counting ? 2 : 1]) == "--dump";
+        const int a = 1 + (counting ? 1 : 0) + (dumping ? 1 : 0);
         if (argc < a + 6) {
-            std::fprintf(stderr, "usage: %s [--dump] <config.cfg> <x> <y> <width> <height> <frame0> [<frame1> ...]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [--counts] [--dump] <config.cfg> <x> <y> <width> <height> <frame0> [<frame1> ...]\n", argv[0]);
             return 2;
         }
         ptree all;
@@ -248,6 +251,11 @@ int main(int argc, char** argv) {
                         tracker.hasAdapted() ? 1 : 0, tracker.getLastRoute() == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
             if (auto flow = flow_model(tracker.getSampler())) print_flow(*flow);
             if (dumping) dump(tracker.getSampler(), tracker.getSamples());
+        }
+        if (counting) {
+            auto dependent = std::dynamic_pointer_cast<PositionDependentMeasurementModel>(adaptiveModel);
+            auto single = dependent ? std::dynamic_pointer_cast<SingleClassifierModel>(dependent->getMeasurementModel()) : nullptr;
+            if (single) std::printf("evaluations fused %d loop %d\n", single->getFusedEvaluationCount(), single->getLoopEvaluationCount());
         }
         return 0;
     } catch (const std::exception& e) {

@@ -142,11 +142,15 @@ public:
     std::shared_ptr<imageprocessing::FeatureExtractor> getFeatureExtractor() const { return featureExtractor; }
     std::shared_ptr<classification::ProbabilisticClassifier> getClassifier() const { return classifier; }
     // evaluate(image, samples) for a generation that lives in `particles`: update, then one
-    // fd_particles_evaluate_integral and one fd_particles_weigh_classifier, nothing copied back.  The caller has checked residentPossible()
+    // fd_particles_evaluate_integral or fd_particles_evaluate_pyramid and one fd_particles_weigh_classifier, nothing copied back.  The
+    // caller has checked residentPossible()
     void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles);
-    // the extractor resolves to a Haar, SURF or integral HOG chain with at most FD_SAMPLE_MAPS_MAX wrappers that is ready, and the
-    // classifier is a (Trainable)ProbabilisticSvmClassifier on f32 vectors
+    // The classifier is a (Trainable)ProbabilisticSvmClassifier on f32 vectors and the extractor resolves to a chain with at most
+    // FD_SAMPLE_MAPS_MAX wrappers that is ready: a Haar, SURF or integral HOG chain, or (residentOnPyramid) a DirectPyramidFeatureExtractor
+    // with a histogram, extended HOG or gray-patch chain behind PatchResizingFeatureExtractors only, on a pyramid that holds an image and
+    // whose width -> layer table fits FD_SAMPLE_TABLE_MAX
     bool residentPossible() const;
+    bool residentOnPyramid() const;
 private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticClassifier> classifier;
@@ -631,7 +635,9 @@ public:
 // FilteringStateExtractor(WeightedMeanStateExtractor) -- or whose transition model is an OpticalFlowTransitionModel with a
 // SimpleTransitionModel fallback and a grid of at most 1024 points, or a SimpleTransitionModel, and whose model is a SingleClassifierModel
 // (also the one inside a PositionDependentMeasurementModel) with a ProbabilisticSvmClassifier on f32 vectors on a Haar, SURF or integral
-// HOG extractor -- these classes exactly: a subclass of any of them may override what the route
+// HOG extractor, or whose transition model is a SimpleTransitionModel and whose SingleClassifierModel is on a
+// DirectPyramidFeatureExtractor with a histogram, extended HOG or gray-patch chain (also behind PatchResizingFeatureExtractors) -- these
+// classes exactly: a subclass of any of them may override what the route
 // restates and therefore keeps the generic route -- runs on a particle set that stays on the device (fd_particles): the host draws the
 // same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample objects on demand;
 // they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
@@ -661,8 +667,8 @@ private:
     void deviceStep();
     void releaseParticles();
     // which resident frame the configuration has: Ehog is ExtendedHogBasedMeasurementModel on its tracker, Integral a
-    // SingleClassifierModel (also inside a PositionDependentMeasurementModel) on an unbound set
-    enum class ResidentKind { None, Ehog, Integral };
+    // SingleClassifierModel (also inside a PositionDependentMeasurementModel) on an unbound set, Pyramid the same on a pyramid chain (SimpleTransitionModel only)
+    enum class ResidentKind { None, Ehog, Integral, Pyramid };
     ResidentKind residentKind() const;
     void integralDeviceStep();
     void uploadGeneration();

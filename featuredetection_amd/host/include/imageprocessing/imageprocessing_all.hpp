@@ -730,7 +730,9 @@ struct SampledChain {
     bool hasWindow(int x, int y, int width, int height) const;
     std::vector<int32_t> mapped(const std::vector<int32_t>& xywh) const;   // the samples of an integral kind behind the wrappers' maps
 };
-SampledChain sampledChainOf(const FeatureExtractor* extractor);
+// mapsApplied: the caller puts every sample through the wrappers' maps itself before the layer rule (the resident particle set, DESIGN.md
+// 4.7), so a wrapped DirectPyramidFeatureExtractor resolves too; extract, svmEvaluate and hasWindow are not for such a chain
+SampledChain sampledChainOf(const FeatureExtractor* extractor, bool mapsApplied = false);
 
 // ---- the integral-image family: image filters GrayscaleFilter -> IntegralImageFilter of a DirectImageFeatureExtractor, patch filters
 // that are a handful of rectangle sums (the "haar" and "surf" feature types of BenchmarkRunner.cpp:202-233,278-286)

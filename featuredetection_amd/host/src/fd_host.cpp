@@ -951,13 +951,13 @@ vector<shared_ptr<Patch>> DirectPyramidFeatureExtractor::extract(const vector<cv
 }
 
 // ---- SampledChain ---------------------------------------------------------------------------------
-SampledChain sampledChainOf(const FeatureExtractor* extractor) {
+SampledChain sampledChainOf(const FeatureExtractor* extractor, bool mapsApplied) {
     using Kind = SampledChain::Kind;
     SampledChain c(extractor);
     c.pyramid = dynamic_cast<const DirectPyramidFeatureExtractor*>(c.wrappers.inner());
     c.image = dynamic_cast<const DirectImageFeatureExtractor*>(c.wrappers.inner());
     int kind = 0, gradientCount = 0, cellCount = 0;
-    if (c.pyramid && !c.wrappers.wrapped()) {   // the extractor itself: a wrapper's map moves the sample off the layer rule
+    if (c.pyramid && (mapsApplied || !c.wrappers.wrapped())) {   // the extractor itself: a wrapper's map moves the sample off the layer rule
         if (c.pyramid->getSampledChain(kind, c.hist, c.ehog)) c.kind = kind == FD_SAMPLES_EHOG ? Kind::Ehog : Kind::Hist;
         else if (c.pyramid->getSampledPatchChain(c.patch)) c.kind = Kind::Patch;
     } else if (c.image) {
@@ -2872,24 +2872,62 @@ static bool resident_integral(const imageprocessing::SampledChain& chain, const 
     return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && scorer.svm &&
            chain.wrappers.sampleMaps().size() <= (size_t)FD_SAMPLE_MAPS_MAX && chain.ready();
 }
+// The chain of a resident evaluation: the device maps every sample through the wrappers first (k_particles_xywh, k_particles_windows), so a
+// pyramid chain behind wrappers resolves too
+static imageprocessing::SampledChain resident_chain(const imageprocessing::FeatureExtractor* extractor) {
+    return imageprocessing::sampledChainOf(extractor, /*mapsApplied=*/true);
+}
+// fd_particles_evaluate_pyramid serves the chain: a pyramid kind with an f32 SVM behind at most FD_SAMPLE_MAPS_MAX wrappers, all of them
+// PatchResizingFeatureExtractors, on a pyramid that holds an image, has no more layers than the window table and whose width -> layer
+// table fits (fd_sample_layer_table)
+static bool resident_pyramid(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer) {
+    if (!chain.onPyramid() || !scorer.svm || !chain.ready()) return false;
+    const vector<fd_sample_map>& maps = chain.wrappers.sampleMaps();
+    if (maps.size() > (size_t)FD_SAMPLE_MAPS_MAX) return false;
+    for (const fd_sample_map& m : maps)
+        if (m.kind != FD_SAMPLE_MAP_RESIZE) return false;
+    const fd_pyramid* native = chain.pyramid->getPyramid()->native();
+    const int layers = native ? fd_pyramid_layer_count(native) : 0;
+    if (layers < 1 || layers > 64) return false;
+    int first = 0, lw, lh, ch, length = 0;
+    double scale;
+    fd_pyramid_layer_info(native, 0, &first, &scale, &lw, &lh, &ch);
+    const int patchWidth = chain.kind == imageprocessing::SampledChain::Kind::Patch ? chain.patch.patch_w
+                           : (chain.kind == imageprocessing::SampledChain::Kind::Ehog ? chain.ehog.patch_w : chain.hist.patch_w);
+    const int rc = fd_sample_layer_table(layers, first, fd_pyramid_incremental_scale(native), patchWidth, 0, nullptr, &length);
+    return (rc == FD_OK || rc == FD_ERR_CAPACITY) && length <= FD_SAMPLE_TABLE_MAX;
+}
 bool SingleClassifierModel::residentPossible() const {
-    return resident_integral(imageprocessing::sampledChainOf(featureExtractor.get()), sampledClassifierOf(classifier.get()));
+    const imageprocessing::SampledChain chain = resident_chain(featureExtractor.get());
+    const SampledClassifier scorer = sampledClassifierOf(classifier.get());
+    return resident_integral(chain, scorer) || resident_pyramid(chain, scorer);
+}
+bool SingleClassifierModel::residentOnPyramid() const {
+    return resident_pyramid(resident_chain(featureExtractor.get()), sampledClassifierOf(classifier.get()));
 }
 void SingleClassifierModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) {
     using Kind = imageprocessing::SampledChain::Kind;
     update(image);
-    const imageprocessing::SampledChain chain = imageprocessing::sampledChainOf(featureExtractor.get());
+    const imageprocessing::SampledChain chain = resident_chain(featureExtractor.get());
     const SampledClassifier scorer = sampledClassifierOf(classifier.get());
-    if (!resident_integral(chain, scorer)) throw std::logic_error("SingleClassifierModel: no resident evaluation for this extractor and classifier");
+    const bool onPyramid = resident_pyramid(chain, scorer);
+    if (!onPyramid && !resident_integral(chain, scorer)) throw std::logic_error("SingleClassifierModel: no resident evaluation for this extractor and classifier");
     ++fusedEvaluations;
-    fd_haar_params hp;
-    if (chain.haar) hp = chain.haar->params();
-    const int kind = chain.kind == Kind::Haar ? (int)FD_INTEGRAL_HAAR : (chain.kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
-    const void* prm = chain.kind == Kind::Haar ? (const void*)&hp : (chain.kind == Kind::IntegralHog ? (const void*)&chain.ihog : (const void*)&chain.surf);
     const vector<fd_sample_map> maps = chain.wrappers.sampleMaps();
     const double a = scorer.svm->getLogisticA(), b = scorer.svm->getLogisticB();
-    check(fd_particles_evaluate_integral(context(), particles, chain.image->native(), kind, prm, scorer.svm->getSvm()->native(a, b), Sample::getAspectRatio(),
-                                         maps.data(), (int)maps.size()));
+    if (onPyramid) {
+        const int kind = chain.kind == Kind::Patch ? (int)FD_SAMPLES_PATCH : (chain.kind == Kind::Ehog ? (int)FD_SAMPLES_EHOG : (int)FD_SAMPLES_HIST);
+        const void* prm = chain.kind == Kind::Patch ? (const void*)&chain.patch : (chain.kind == Kind::Ehog ? (const void*)&chain.ehog : (const void*)&chain.hist);
+        check(fd_particles_evaluate_pyramid(context(), particles, chain.pyramid->getPyramid()->native(), kind, prm, scorer.svm->getSvm()->native(a, b),
+                                            Sample::getAspectRatio(), maps.data(), (int)maps.size()));
+    } else {
+        fd_haar_params hp;
+        if (chain.haar) hp = chain.haar->params();
+        const int kind = chain.kind == Kind::Haar ? (int)FD_INTEGRAL_HAAR : (chain.kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
+        const void* prm = chain.kind == Kind::Haar ? (const void*)&hp : (chain.kind == Kind::IntegralHog ? (const void*)&chain.ihog : (const void*)&chain.surf);
+        check(fd_particles_evaluate_integral(context(), particles, chain.image->native(), kind, prm, scorer.svm->getSvm()->native(a, b), Sample::getAspectRatio(),
+                                             maps.data(), (int)maps.size()));
+    }
     // SvmClassifier::classify compares with the threshold the device model holds as a float (fd_samples_svm_tail does the same)
     check(fd_particles_weigh_classifier(context(), particles, a, b, (double)(float)scorer.svm->getSvm()->getThreshold()));
 }
@@ -4256,7 +4294,11 @@ ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
                       std::static_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel())->residentPossible();
     if (!simple && !flow) return ResidentKind::None;
     const shared_ptr<SingleClassifierModel> single = resident_single_model(measurementModel);
-    return single && single->residentPossible() ? ResidentKind::Integral : ResidentKind::None;
+    if (!single || !single->residentPossible()) return ResidentKind::None;
+    if (!single->residentOnPyramid()) return ResidentKind::Integral;
+    // a pyramid chain under OpticalFlowTransitionModel keeps the generic route: the library serves that frame (fd_particles_sample_flow,
+    // then _evaluate_pyramid), but the route comparison of tracker_app pins `generic` for this combination
+    return simple ? ResidentKind::Pyramid : ResidentKind::None;
 }
 
 bool ParticleFrameLoop::deviceRoutePossible() const { return residentKind() != ResidentKind::None; }
@@ -4313,7 +4355,7 @@ void ParticleFrameLoop::uploadGeneration() {
     resident = true;
 }
 
-// SingleClassifierModel on the integral family, SimpleTransitionModel or OpticalFlowTransitionModel: an unbound set.  The host draws
+// SingleClassifierModel on the integral family or on a pyramid family, SimpleTransitionModel or OpticalFlowTransitionModel: an unbound set.  The host draws
 // every random number the generic route would draw: the three generators (resampling, transition, fresh samples) are separate, so only
 // the order within each matters.  With the flow model the branch is the device's: both blocks are drawn behind snapshots and the model
 // that did not predict gets its snapshot back after the read-back.
@@ -4366,7 +4408,7 @@ void ParticleFrameLoop::integralDeviceStep() {
 }
 
 void ParticleFrameLoop::deviceStep() {
-    if (lastKind == ResidentKind::Integral) return integralDeviceStep();
+    if (lastKind == ResidentKind::Integral || lastKind == ResidentKind::Pyramid) return integralDeviceStep();
     auto model = std::dynamic_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
     auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
     if (particles && particlesOn != model->native()) releaseParticles();   // the model was initialised again: another tracker handle

@@ -1239,6 +1239,31 @@ int fd_patch_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_sam
 int fd_patch_rvm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_patch_samples_params* pp, const fd_rvm* rvm, int n,
                                   const int32_t* xywh, uint8_t* valid, int32_t* level, double* distance, uint8_t* target);
 
+/* ---- the resident particle set (fd_particles_create_unbound) on the pyramid families: the feature types hog, ehog, lbp, glbp, grayscale,
+ *      h and whi of the tracking apps -------------------------------------------------------------------------------------------------
+ * The device resolves a sample to its window itself.  Of the rule of fd_sample_windows the placement in the layer is exact arithmetic and
+ * is evaluated there; the layer of a width goes through log and is read from a table of the host's values: */
+/* host only: layer_of_width[w] = position in the kept-layer list of a sample of width w (the index expression of fd_sample_window,
+ * evaluated by the host for every w), -1 for none; [0] = -1.  *length = 1 + the largest width that maps to a kept layer (0: none;
+ * INT32_MAX when that width is INT32_MAX).  FD_ERR_CAPACITY with *length set when length > cap.  FD_ERR_INVALID_ARGUMENT as
+ * fd_sample_windows for its arguments, and for more than INT16_MAX layers. */
+#define FD_SAMPLE_TABLE_MAX 65536
+int fd_sample_layer_table(int n_layers, int first_index, double incremental_scale, int patch_w, int cap, int16_t* layer_of_width, int* length);
+enum { FD_SAMPLES_PATCH = 2 };   /* next to FD_SAMPLES_HIST / FD_SAMPLES_EHOG; params: const fd_patch_samples_params* */
+/* SingleClassifierModel::evaluate's scoring for the current generation of an unbound or bound set on a pyramid chain, nothing copied
+ * back: sample -> maps -> window on the device (k_particles_windows), the kernels of fd_hist_svm_evaluate_samples /
+ * fd_patch_svm_evaluate_samples on the list, the distances into the generation's scores, the validity into the set's flags;
+ * fd_particles_get_trace reports {layer, bx, by, valid}.  Then fd_particles_weigh_classifier as after _evaluate_integral.
+ * Every particle keeps its own slot of the window list; the slot of a particle without a window names a window that exists, and its
+ * score means nothing until fd_particles_weigh_classifier has set it to 0.  The table above stays in the pyramid handle and is uploaded
+ * again only when the patch width or the kept layers change.
+ * The argument rules are those of the two calls named (kind, params, svm, pyr as there), except that a pyramid without an image is
+ * FD_ERR_RUNTIME.  FD_ERR_INVALID_ARGUMENT also for more than FD_SAMPLE_MAPS_MAX maps, a map other than FD_SAMPLE_MAP_RESIZE, and a
+ * pyramid whose table would be longer than FD_SAMPLE_TABLE_MAX.  A refused call launches nothing and leaves the generation "not
+ * evaluated".  An empty generation is FD_OK. */
+int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int kind, const void* params, const fd_svm* svm,
+                                  double aspect_ratio, const fd_sample_map* maps, int n_maps);
+
 /* ---- supervised descent: superviseddescent::SdmLandmarkModel / SdmLandmarkModelFitting ---------- */
 typedef struct {
     int32_t num_landmarks;      /* L */

@@ -10,7 +10,14 @@ SVM -- on 640 x 480 frames in HBM, at 100, 1000 and 8192 particles, as the libra
   resident   fd_flow_update, fd_integral_update, fd_flow_track_fb_resident, fd_particles_sample_flow, _evaluate_integral,
              _weigh_classifier, _state_flow: the whole frame, draws uploaded, one read-back.
 
-  python tools/resident_tracker_probe.py [--frames 60] [--warmup 10] [--rounds 5]
+  python tools/resident_tracker_probe.py [--frames 60] [--warmup 10] [--rounds 5] [--counts 100,1000,8192]
+  python tools/resident_tracker_probe.py --pyramid hog|ehog|glbp|whi
+                 the same two routes with the measurement on a pyramid feature type (20 x 20 patches of a pyramid with five layers per
+                 octave between the scales 0.1 and 0.5; a linear SVM): the pyramid's update in place of fd_integral_update on both
+                 routes, fd_hist_svm_evaluate_samples / fd_patch_svm_evaluate_samples on the generic one (resolves the windows on the
+                 host, uploads the compacted list, waits), fd_particles_evaluate_pyramid on the resident one.  With --host:
+                 tracker_app on `feature hog|ehog|glbp|whi` with `transition simple` (the host trackers take the device route on
+                 these feature types with that transition model only)
   python tools/resident_tracker_probe.py --host [--frames 40] [--rounds 3]
                  the same configuration through the host classes: tracker_app (AdaptiveCondensationTracker, `measurement
                  positionDependent`, adaptation included) on 640 x 480 PGM frames, once with FD_COND_DEVICE=0 and once with =1 per round
@@ -50,7 +57,78 @@ def textured(seed):
     return np.rint(a * 255).astype(np.uint8)
 
 
-def run(frames_per_round, warmup, rounds):
+PATCH = 20
+PYRAMID = dict(octave_layers=5, min_scale=0.1, max_scale=0.5)
+
+
+class IntegralMeasurement:
+    """the default: `ihog` behind scale 1.1 on an integral image"""
+
+    def __init__(self, capi, ctx):
+        self.capi, self.integral = capi, capi.Integral(ctx)
+        hist = capi.hist_params(kind=capi.HIST_SPATIAL, pw=G, ph=G, sx=1, sy=1, bins=BINS, cell=6, block=1, normalization=1)
+        self.hp = capi.integral_hog_params(G, G, bins=BINS, interpolate_bins=True, hist=hist)
+        self.maps = [("resize", float(np.float32(1.1))), ("integral",)]
+
+    def update(self, frame):
+        self.integral.update_device(frame.data_ptr(), W, H, 1)
+
+    def features(self, xywh):
+        return self.integral.extract_hog(self.hp, self.capi.sample_maps_apply(self.maps, xywh))
+
+    def evaluate_host(self, svm, xywh):
+        self.integral.svm_evaluate_samples(svm, self.capi.sample_maps_apply(self.maps, xywh), hog=self.hp)
+
+    def evaluate_resident(self, particles, svm):
+        particles.evaluate_integral(self.integral, svm, 1.0, self.maps, hog=self.hp)
+
+    def close(self):
+        self.integral.close()
+
+
+class PyramidMeasurement:
+    """--pyramid: a DirectPyramidFeatureExtractor's chain, not wrapped"""
+
+    def __init__(self, capi, ctx, kind):
+        self.capi, self.ctx, self.pyr = capi, ctx, capi.Pyramid(ctx, **PYRAMID)
+        self.kw = None
+        if kind in ("hog", "ehog"):
+            self.pyr.set_layer_filter(capi.FD_LAYER_GRADBIN, bins=BINS)
+        elif kind == "glbp":
+            self.pyr.set_layer_filter(capi.FD_LAYER_GRADMAG_LBP, lbp_type=1, grad_kernel=3, blur_kernel=3)
+        if kind == "hog":
+            self.kw = dict(hist=capi.hist_params(kind=capi.HIST_SPATIAL, pw=PATCH, ph=PATCH, sx=1, sy=1, bins=BINS, cell=5, block=1, normalization=2))
+        elif kind == "glbp":
+            self.kw = dict(hist=capi.hist_params(kind=capi.HIST_SPATIAL, pw=PATCH, ph=PATCH, sx=1, sy=1, bins=59, cell=5, block=1, normalization=2))
+        elif kind == "ehog":
+            self.kw = dict(ehog=capi.ehog_patch_params(PATCH, PATCH, bins=BINS, cell_w=5))
+        else:
+            self.kw = dict(patch=capi.patch_samples_params(PATCH, PATCH, capi.FD_FEATURE_WHI))
+        self.prm = list(self.kw.values())[0]
+
+    def update(self, frame):
+        self.pyr.update_device(frame.data_ptr(), W, H, 1)
+
+    def features(self, xywh):
+        if "patch" in self.kw:
+            return self.capi.patch_extract_samples(self.ctx, self.pyr, self.prm, xywh)
+        extract = self.capi.ehog_extract_samples if "ehog" in self.kw else self.capi.hist_extract_samples
+        return extract(self.ctx, self.pyr, self.prm, xywh)
+
+    def evaluate_host(self, svm, xywh):
+        if "patch" in self.kw:
+            self.capi.patch_svm_evaluate_samples(self.ctx, self.pyr, self.prm, svm, xywh)
+        else:
+            self.capi.hist_svm_evaluate_samples(self.ctx, self.pyr, self.prm, svm, xywh)
+
+    def evaluate_resident(self, particles, svm):
+        particles.evaluate_pyramid(self.pyr, svm, 1.0, (), **self.kw)
+
+    def close(self):
+        self.pyr.close()
+
+
+def run(frames_per_round, warmup, rounds, counts=COUNTS, pyramid=None):
     from featuredetection_amd import capi
     stream = torch.cuda.Stream()
     ctx = capi.Context(0, stream=stream.cuda_stream)
@@ -58,23 +136,21 @@ def run(frames_per_round, warmup, rounds):
     cycle = 8   # the texture moves by SHIFT per frame and jumps back every `cycle` frames (one frame without a usable flow)
     frames = [torch.from_numpy(np.roll(base, (SHIFT[1] * k, SHIFT[0] * k), axis=(0, 1)).copy()).cuda() for k in range(cycle)]
     torch.cuda.synchronize()
-    hist = capi.hist_params(kind=capi.HIST_SPATIAL, pw=G, ph=G, sx=1, sy=1, bins=BINS, cell=6, block=1, normalization=1)
-    hp = capi.integral_hog_params(G, G, bins=BINS, interpolate_bins=True, hist=hist)
-    maps = [("resize", float(np.float32(1.1))), ("integral",)]
     x, y, size = TARGET
     pts_of = lambda k: (capi.flow_grid(10, 10, True) * np.float32(size) + np.array([x + SHIFT[0] * k, y + SHIFT[1] * k], np.float32)).astype(np.float32)
-    out = dict(size="%dx%d" % (W, H), frames_per_round=frames_per_round, rounds=rounds, grid_points=int(len(pts_of(0))), routes={})
+    out = dict(size="%dx%d" % (W, H), feature=pyramid or "ihog", frames_per_round=frames_per_round, rounds=rounds, grid_points=int(len(pts_of(0))),
+               routes={})
     with torch.cuda.stream(stream):
-        flow, integral = capi.Flow(ctx, W, H), capi.Integral(ctx)
-        integral.update_device(frames[0].data_ptr(), W, H, 1)
-        box = capi.sample_maps_apply(maps, [(x, y, size, size)])
-        feat, valid = integral.extract_hog(hp, box)
+        flow = capi.Flow(ctx, W, H)
+        measurement = PyramidMeasurement(capi, ctx, pyramid) if pyramid else IntegralMeasurement(capi, ctx)
+        measurement.update(frames[0])
+        feat, valid = measurement.features(np.array([(x, y, size, size)], np.int32))
         assert valid[0]
         w = feat[0] - feat[0].mean()
         svm = capi.Svm(ctx, dict(kernel=0, dtype=1, sv=w[None, :].astype(np.float32), coeff=np.ones(1, np.float32), bias=np.float32(0)))
         own = float(svm.distance(feat)[0])
         threshold, logistic_a, logistic_b = 0.5 * own, 2.0, -4.0 / own
-        for n in COUNTS:
+        for n in counts:
             rng = np.random.default_rng(n)
             n_resampled = int((1 - RANDOM_RATE) * n)
 
@@ -108,11 +184,10 @@ def run(frames_per_round, warmup, rounds):
                 pts = pts_of((k - 1) % cycle)
                 t0 = time.perf_counter()
                 flow.update(frames[k % cycle])
-                integral.update_device(frames[k % cycle].data_ptr(), W, H, 1)
+                measurement.update(frames[k % cycle])
                 fwd, bwd, fst, bst = flow.track_fb(pts)
                 motion = capi.flow_median(pts, fwd, bwd, fst, bst)
-                mapped = capi.sample_maps_apply(maps, xywh)
-                integral.svm_evaluate_samples(svm, mapped, hog=hp)
+                measurement.evaluate_host(svm, xywh)
                 t1 = time.perf_counter()
                 used["generic"] += bool(motion["ok"])
                 return t1 - t0
@@ -123,10 +198,10 @@ def run(frames_per_round, warmup, rounds):
                 pts = pts_of((k - 1) % cycle)
                 t0 = time.perf_counter()
                 flow.update(frames[k % cycle])
-                integral.update_device(frames[k % cycle].data_ptr(), W, H, 1)
+                measurement.update(frames[k % cycle])
                 flow.track_fb_resident(pts)
                 particles.sample_flow(flow, n, n_resampled, u, d0, d1, fresh, next_id[0])
-                particles.evaluate_integral(integral, svm, 1.0, maps, hog=hp)
+                measurement.evaluate_resident(particles, svm)
                 particles.weigh_classifier(logistic_a, logistic_b, threshold)
                 info, motion = particles.state_flow(flow)
                 t1 = time.perf_counter()
@@ -151,19 +226,19 @@ def run(frames_per_round, warmup, rounds):
                                                                    flow_used_fraction=used[route] / float(rounds * (warmup + frames_per_round)))
             particles.close()
         flow.close()
-        integral.close()
+        measurement.close()
+        torch.cuda.synchronize()
     ctx.close()
     return out
 
 
 HOST_CONFIG = """tracking {
   seed 7
-  transition opticalFlow { positionDeviation 10 sizeDeviation 0.08 fallback simple { positionDeviation 12.8 sizeDeviation 0.1 } }
+  transition %(transition)s
   adaptive { resampling { particleCount %(n)d randomRate 0.35 minSize 40 maxSize 200 } }
   initialCount %(n)d
   measurement positionDependent {
-    feature ihog { scale 1.1  signed false  interpolate true  bins 9  gradientCount 30
-                   histogram spatial { cellSize 6  blockSize 1  interpolate false  normalization l2norm } }
+    %(feature)s
     filter none  startFrameCount 1  stopFrameCount 0  targetThreshold 0.1  confidenceThreshold 0.95
     positiveOffsetFactor 0.05  negativeOffsetFactor 0.5  sampleNegativesAroundTarget 2  sampleAdditionalNegatives 10  sampleTestNegatives 10
     exploitSymmetry 0
@@ -173,11 +248,28 @@ HOST_CONFIG = """tracking {
 """
 
 
-def run_host(frames, rounds):
+# the host trackers take the device route on a pyramid feature type with `transition simple` only
+HOST_TRANSITIONS = {False: "opticalFlow { positionDeviation 10 sizeDeviation 0.08 fallback simple { positionDeviation 12.8 sizeDeviation 0.1 } }",
+                    True: "simple { positionDeviation 12.8 sizeDeviation 0.1 }"}
+HOST_PYRAMID = "pyramid direct { patch { width 20 height 20 minWidth 40 maxWidth 200 } interval 5 }"
+HOST_FEATURES = {
+    None: """feature ihog { scale 1.1  signed false  interpolate true  bins 9  gradientCount 30
+                   histogram spatial { cellSize 6  blockSize 1  interpolate false  normalization l2norm } }""",
+    "hog": "feature hog { %s gradientKernel 3 blurKernel 0 bins 9 signed 0 interpolate 0 histogram spatial { cellSize 5 blockSize 2 interpolate 0 "
+           "signedAndUnsigned 0 concatenate 0 normalization l2hys } }" % HOST_PYRAMID,
+    "ehog": "feature ehog { %s gradientKernel 3 blurKernel 0 bins 9 signed 0 interpolate 0 histogram { cellSize 5 interpolate 0 signedAndUnsigned 0 "
+            "alpha 0.2 } }" % HOST_PYRAMID,
+    "glbp": "feature glbp { %s gradientKernel 3 blurKernel 3 type lbp8uniform histogram spatial { cellSize 5 blockSize 1 interpolate 0 concatenate 0 "
+            "normalization l2hys } }" % HOST_PYRAMID,
+    "whi": "feature whi { %s }" % HOST_PYRAMID,
+}
+
+
+def run_host(frames, rounds, counts=COUNTS, pyramid=None):
     import subprocess
     import tempfile
     app = os.path.join(ROOT, "featuredetection_amd", "tracker_app")
-    out = dict(size="%dx%d" % (W, H), frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
+    out = dict(size="%dx%d" % (W, H), feature=pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
     with tempfile.TemporaryDirectory() as tmp:
         base = textured(5)
         paths = []
@@ -188,10 +280,10 @@ def run_host(frames, rounds):
                 f.write(np.roll(base, (SHIFT[1] * (k % 8), SHIFT[0] * (k % 8)), axis=(0, 1)).tobytes())
             paths.append(path)
         x, y, size = TARGET
-        for n in COUNTS:
+        for n in counts:
             cfg = os.path.join(tmp, "tracking%d.cfg" % n)
             with open(cfg, "w") as f:
-                f.write(HOST_CONFIG % dict(n=n))
+                f.write(HOST_CONFIG % dict(n=n, feature=HOST_FEATURES[pyramid], transition=HOST_TRANSITIONS[pyramid is not None]))
             times = {"generic": [], "device": []}
             for r in range(rounds):
                 for route in (("generic", "device") if r % 2 == 0 else ("device", "generic")):
@@ -218,7 +310,11 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--pyramid", choices=("hog", "ehog", "glbp", "whi"), default=None)
+    ap.add_argument("--counts", default=",".join(str(c) for c in COUNTS), help="particle counts, comma separated")
     a = ap.parse_args()
+    counts = tuple(int(c) for c in a.counts.split(","))
     if not torch.cuda.is_available():
         sys.exit("resident_tracker_probe: no GPU; a frame time cannot be measured without one")
-    print(json.dumps(run_host(a.frames, a.rounds) if a.host else run(a.frames, a.warmup, a.rounds)))
+    print(json.dumps(run_host(a.frames, a.rounds, counts, a.pyramid) if a.host else run(a.frames, a.warmup, a.rounds, counts, a.pyramid)))
+    torch.cuda.synchronize()
