@@ -530,16 +530,8 @@ int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr,
                                   const fd_sample_map* maps, int n_maps) {
     return fd_guard(ctx, [&] {
         static const char* const who = "fd_particles_evaluate_pyramid";
-        if (!ctx || !p || !pyr || !params || !svm || n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
-        if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
-        FdSampleMaps chain;
-        std::memset(&chain, 0, sizeof(chain));
-        chain.n = n_maps;
-        for (int k = 0; k < n_maps; ++k) {
-            if (maps[k].kind != FD_SAMPLE_MAP_RESIZE)
-                FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: sample map kind %d; a pyramid chain takes FD_SAMPLE_MAP_RESIZE only", who, maps[k].kind);
-            chain.m[k] = maps[k];
-        }
+        if (!ctx || !p || !pyr || !params || !svm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        const FdSampleMaps chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE, who);
         if (kind != FD_SAMPLES_HIST && kind != FD_SAMPLES_EHOG && kind != FD_SAMPLES_PATCH) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
         particles_checked(ctx, p, who);
         if (pyr->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: objects belong to different contexts", who);

@@ -691,7 +691,7 @@ struct FdParticlesView {
 };
 // one wrapper's map of a sample {x, y, width, height} (fd_sample_map, fd_hip.h): PatchResizingFeatureExtractor::mapSample and
 // IntegralFeatureExtractor::mapSample, the one copy of these expressions for the host (fd_sample_maps_apply) and the device
-// (k_particles_xywh, k_particles_windows).  cvRound is fd_sample_cvround; the sums and products are doubles in this order.
+// (fd_particle_sample).  cvRound is fd_sample_cvround; the sums and products are doubles in this order.
 __host__ __device__ inline void fd_sample_map_apply(const fd_sample_map& m, int32_t& x, int32_t& y, int32_t& width, int32_t& height) {
     if (m.kind == FD_SAMPLE_MAP_RESIZE) {
         x = fd_sample_cvround(x + m.x_offset * width);
@@ -710,6 +710,16 @@ struct FdSampleMaps {
     int32_t n;
     fd_sample_map m[FD_SAMPLE_MAPS_MAX];
 };
+// The chain of a call, checked: FD_ERR_INVALID_ARGUMENT for a negative count or NULL with a positive one ("bad argument"), for more than
+// FD_SAMPLE_MAPS_MAX maps, and for a kind whose bit (1 << kind) allowedKindsMask does not hold.  hostalgo.cpp
+FdSampleMaps fd_sample_maps_checked(const fd_sample_map* maps, int n_maps, unsigned allowedKindsMask, const char* who);
+// the sample of a particle (x, y, size; height = cvRound(aspect * size), Sample.hpp:127-129) through the wrapper chain of its feature
+// extractor, outer to inner: what k_particles_xywh and k_particles_windows start from
+__host__ __device__ inline void fd_particle_sample(int32_t px, int32_t py, int32_t size, double aspect, const FdSampleMaps& maps, int32_t& x, int32_t& y,
+                                                   int32_t& width, int32_t& height) {
+    x = px; y = py; width = size; height = fd_sample_cvround(aspect * (double)size);
+    for (int k = 0; k < maps.n; ++k) fd_sample_map_apply(maps.m[k], x, y, width, height);
+}
 FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who);
 void fd_particles_set_evaluated(fd_particles* p);
 // ---- resident particle set on the pyramid families (condensation.hip launches k_particles_windows; the scoring kernels are hog.hip's and rvm.hip's) ----

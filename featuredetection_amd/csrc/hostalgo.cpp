@@ -509,14 +509,36 @@ extern "C" int fd_surf_feature_length(int gradient_count, int cell_count) {
     return 4 * cell_count * cell_count;
 }
 
-// ---- the wrapper chain of a feature extractor on a list of samples, host only; the device's copy is k_particles_xywh (integral.hip) ----
+// ---- the wrapper chain of a feature extractor: checked and copied for a call; applied to a list of samples on the host (the device
+// applies it in fd_particle_sample) ----
+FdSampleMaps fd_sample_maps_checked(const fd_sample_map* maps, int n_maps, unsigned allowedKindsMask, const char* who) {
+    if (n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+    if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
+    FdSampleMaps chain;
+    std::memset(&chain, 0, sizeof(chain));
+    chain.n = n_maps;
+    for (int k = 0; k < n_maps; ++k) {
+        const int32_t kind = maps[k].kind;
+        if (kind < 0 || kind > 31 || !((allowedKindsMask >> kind) & 1u)) {
+            if (allowedKindsMask == 1u << FD_SAMPLE_MAP_RESIZE)
+                FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: sample map kind %d; a pyramid chain takes FD_SAMPLE_MAP_RESIZE only", who, kind);
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown sample map kind %d", who, kind);
+        }
+        chain.m[k] = maps[k];
+    }
+    return chain;
+}
 extern "C" int fd_sample_maps_apply(const fd_sample_map* maps, int n_maps, int n, int32_t* xywh) {
-    if (n_maps < 0 || n_maps > FD_SAMPLE_MAPS_MAX || n < 0 || (n_maps > 0 && !maps) || (n > 0 && !xywh)) return FD_ERR_INVALID_ARGUMENT;
-    for (int k = 0; k < n_maps; ++k)
-        if (maps[k].kind != FD_SAMPLE_MAP_RESIZE && maps[k].kind != FD_SAMPLE_MAP_INTEGRAL) return FD_ERR_INVALID_ARGUMENT;
+    if (n < 0 || (n > 0 && !xywh)) return FD_ERR_INVALID_ARGUMENT;
+    FdSampleMaps chain;
+    try {
+        chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE | 1u << FD_SAMPLE_MAP_INTEGRAL, "fd_sample_maps_apply");
+    } catch (const FdError& e) {
+        return e.code;
+    }
     for (int i = 0; i < n; ++i) {
         int32_t* s = xywh + 4 * (size_t)i;
-        for (int k = 0; k < n_maps; ++k) fd_sample_map_apply(maps[k], s[0], s[1], s[2], s[3]);
+        for (int k = 0; k < chain.n; ++k) fd_sample_map_apply(chain.m[k], s[0], s[1], s[2], s[3]);
     }
     return FD_OK;
 }

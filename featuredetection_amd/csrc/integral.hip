@@ -259,15 +259,14 @@ __global__ __launch_bounds__(256) void k_surf(const int32_t* __restrict__ img, i
     }
 }
 
-// the samples of a resident particle set (x, y, size; height = cvRound(aspect * size), Sample.hpp:127-129) through the wrapper
-// chain of their feature extractor (outer to inner) into the sample list the kernels above read; `trace` keeps a copy for
+// the samples of a resident particle set (fd_particle_sample) into the sample list the kernels above read; `trace` keeps a copy for
 // fd_particles_get_trace
 __global__ __launch_bounds__(256) void k_particles_xywh(const int32_t* __restrict__ x, const int32_t* __restrict__ y, const int32_t* __restrict__ size, int n,
                                                         double aspect, FdSampleMaps maps, int4* __restrict__ xywh, int4* __restrict__ trace) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int32_t sx = x[i], sy = y[i], sw = size[i], sh = fd_sample_cvround(aspect * (double)sw);
-    for (int k = 0; k < maps.n; ++k) fd_sample_map_apply(maps.m[k], sx, sy, sw, sh);
+    int32_t sx, sy, sw, sh;
+    fd_particle_sample(x[i], y[i], size[i], aspect, maps, sx, sy, sw, sh);
     const int4 s = make_int4(sx, sy, sw, sh);
     xywh[i] = s;
     trace[i] = s;
@@ -410,6 +409,23 @@ int run_surf(fd_ctx* ctx, fd_integral* g, int G, int C, int n) {
     return len;
 }
 
+// The two halves of a scoring call on any integral kind.  integral_prepare: the kind, the image and the parameters checked, the
+// Haar table on the device; returns the feature length.  integral_run: the features of the n samples in g->xywh into g->feat / g->valid
+int integral_prepare(fd_ctx* ctx, fd_integral* g, int kind, const void* params, const char* who) {
+    if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF && kind != FD_INTEGRAL_HOG) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
+    require_updated(ctx, g, who);
+    if (kind == FD_INTEGRAL_HAAR) return prepare_haar(ctx, g, (const fd_haar_params*)params);
+    if (kind == FD_INTEGRAL_HOG) return fd_integral_hog_check((const fd_integral_hog_params*)params);
+    const fd_surf_params* sp = (const fd_surf_params*)params;
+    return check_surf(sp->gradient_count, sp->cell_count);
+}
+void integral_run(fd_ctx* ctx, fd_integral* g, int kind, const void* params, int len, int n) {
+    const fd_surf_params* sp = (const fd_surf_params*)params;
+    if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
+    else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
+    else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -497,11 +513,10 @@ int fd_integral_image(fd_ctx* ctx, const uint8_t* gray, int width, int height, i
 int fd_integral_extract_haar(fd_ctx* ctx, fd_integral* g, const fd_haar_params* hp, int n, const int32_t* xywh, float* features, uint8_t* valid) {
     return fd_guard(ctx, [&] {
         if (!ctx || !g || !hp || n < 0 || (n > 0 && !xywh)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_extract_haar: bad argument");
-        require_updated(ctx, g, "fd_integral_extract_haar");
-        const int F = prepare_haar(ctx, g, hp);
+        const int F = integral_prepare(ctx, g, FD_INTEGRAL_HAAR, hp, "fd_integral_extract_haar");
         if (n == 0) return;
         upload_samples(ctx, g, n, xywh);
-        run_haar(ctx, g, F, n);
+        integral_run(ctx, g, FD_INTEGRAL_HAAR, hp, F, n);
         download_rows(ctx, g, n, F ? features : nullptr, sizeof(float) * (size_t)F, valid);
     });
 }
@@ -586,19 +601,11 @@ int fd_integral_svm_evaluate_samples(fd_ctx* ctx, fd_integral* g, int kind, cons
     return fd_guard(ctx, [&] {
         if (!ctx || !g || !params || !svm || n < 0 || (n > 0 && (!xywh || !target || !weight)))
             FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: bad argument");
-        if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF && kind != FD_INTEGRAL_HOG) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_integral_svm_evaluate_samples: unknown feature kind %d", kind);
-        require_updated(ctx, g, "fd_integral_svm_evaluate_samples");
-        const fd_surf_params* sp = (const fd_surf_params*)params;
-        int len;
-        if (kind == FD_INTEGRAL_HAAR) len = prepare_haar(ctx, g, (const fd_haar_params*)params);
-        else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_check((const fd_integral_hog_params*)params);
-        else len = check_surf(sp->gradient_count, sp->cell_count);
+        const int len = integral_prepare(ctx, g, kind, params, "fd_integral_svm_evaluate_samples");
         fd_samples_require_f32_svm(svm, len, "fd_integral_svm_evaluate_samples");
         if (n == 0) return;
         upload_samples(ctx, g, n, xywh);
-        if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
-        else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
-        else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
+        integral_run(ctx, g, kind, params, len, n);
         std::vector<double> dist(n);   // the validity comes from the kernels: no sampleOf
         fd_samples_svm_tail(ctx, svm, g->feat.p, len, n, g->dist, dist.data(), nullptr, g->valid.p, target, weight, nullptr);
     });
@@ -608,24 +615,10 @@ int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g,
                                    const fd_sample_map* maps, int n_maps) {
     return fd_guard(ctx, [&] {
         static const char* const who = "fd_particles_evaluate_integral";
-        if (!ctx || !p || !g || !params || !svm || n_maps < 0 || (n_maps > 0 && !maps)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
-        if (n_maps > FD_SAMPLE_MAPS_MAX) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: %d sample maps, at most %d", who, n_maps, FD_SAMPLE_MAPS_MAX);
-        FdSampleMaps chain;
-        std::memset(&chain, 0, sizeof(chain));
-        chain.n = n_maps;
-        for (int k = 0; k < n_maps; ++k) {
-            if (maps[k].kind != FD_SAMPLE_MAP_RESIZE && maps[k].kind != FD_SAMPLE_MAP_INTEGRAL)
-                FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown sample map kind %d", who, maps[k].kind);
-            chain.m[k] = maps[k];
-        }
-        if (kind != FD_INTEGRAL_HAAR && kind != FD_INTEGRAL_SURF && kind != FD_INTEGRAL_HOG) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
+        if (!ctx || !p || !g || !params || !svm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        const FdSampleMaps chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE | 1u << FD_SAMPLE_MAP_INTEGRAL, who);
         const FdParticlesView v = fd_particles_view(ctx, p, who);
-        require_updated(ctx, g, who);
-        const fd_surf_params* sp = (const fd_surf_params*)params;
-        int len;
-        if (kind == FD_INTEGRAL_HAAR) len = prepare_haar(ctx, g, (const fd_haar_params*)params);
-        else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_check((const fd_integral_hog_params*)params);
-        else len = check_surf(sp->gradient_count, sp->cell_count);
+        const int len = integral_prepare(ctx, g, kind, params, who);
         fd_samples_require_f32_svm(svm, len, who);
         const int n = v.n;
         if (n > 0) {
@@ -634,9 +627,7 @@ int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g,
             hipLaunchKernelGGL(k_particles_xywh, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, v.x, v.y, v.size, n, aspect_ratio, chain, g->xywh.as<int4>(),
                                (int4*)v.windows);
             HIP_CHECK(hipGetLastError());
-            if (kind == FD_INTEGRAL_HAAR) run_haar(ctx, g, len, n);
-            else if (kind == FD_INTEGRAL_HOG) run_hog(ctx, g, (const fd_integral_hog_params*)params, n);
-            else run_surf(ctx, g, sp->gradient_count, sp->cell_count, n);
+            integral_run(ctx, g, kind, params, len, n);
             fd_svm_generic_launch(ctx, svm, g->feat.p, nullptr, (int64_t)len * 4, n, v.score);
             HIP_CHECK(hipMemcpyAsync(v.valid, g->valid.p, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
         }

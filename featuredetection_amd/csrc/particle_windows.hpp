@@ -13,8 +13,8 @@ struct ParticleLayers {   // the kept layers as part (b) needs them, by value
     struct { double scale; int32_t w, h; } l[FD_WIN_MAX_LAYERS];
 };
 
-// One thread per particle: {x, y, size, cvRound(aspect * size)} through the wrapper chain (as k_particles_xywh), the layer from the table
-// (layerOf[w], widths from tableLen on have none), the window by fd_sample_place.  Every particle keeps slot i of the list: one without a
+// One thread per particle: its sample (fd_particle_sample), the layer from the table (layerOf[w], widths from tableLen on have none), the
+// window by fd_sample_place.  Every particle keeps slot i of the list: one without a
 // window gets `spare`, a window that exists, so that the scoring kernels read valid memory; its row's score is never used
 // (k_particles_weigh).  trace[i] = {layer, bx, by, valid} as fd_pyramid_sample_windows reports it.
 __global__ __launch_bounds__(256) void k_particles_windows(const int32_t* __restrict__ x, const int32_t* __restrict__ y, const int32_t* __restrict__ size,
@@ -23,8 +23,8 @@ __global__ __launch_bounds__(256) void k_particles_windows(const int32_t* __rest
                                                            int32_t* __restrict__ list, int4* __restrict__ trace, uint8_t* __restrict__ valid) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int32_t sx = x[i], sy = y[i], sw = size[i], sh = fd_sample_cvround(aspect * (double)sw);
-    for (int k = 0; k < maps.n; ++k) fd_sample_map_apply(maps.m[k], sx, sy, sw, sh);
+    int32_t sx, sy, sw, sh;
+    fd_particle_sample(x[i], y[i], size[i], aspect, maps, sx, sy, sw, sh);
     const int pos = sw > 0 && sw < tableLen ? (int)layerOf[sw] : -1;
     FdSampleWindow w = spare;
     bool ok = false;

@@ -142,15 +142,21 @@ public:
     std::shared_ptr<imageprocessing::FeatureExtractor> getFeatureExtractor() const { return featureExtractor; }
     std::shared_ptr<classification::ProbabilisticClassifier> getClassifier() const { return classifier; }
     // evaluate(image, samples) for a generation that lives in `particles`: update, then one
-    // fd_particles_evaluate_integral or fd_particles_evaluate_pyramid and one fd_particles_weigh_classifier, nothing copied back.  The
-    // caller has checked residentPossible()
+    // fd_particles_evaluate_integral or fd_particles_evaluate_pyramid and one fd_particles_weigh_classifier, nothing copied back.  It
+    // resolves its own plan after the update; logic_error where that plan is None
     void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles);
-    // The classifier is a (Trainable)ProbabilisticSvmClassifier on f32 vectors and the extractor resolves to a chain with at most
-    // FD_SAMPLE_MAPS_MAX wrappers that is ready: a Haar, SURF or integral HOG chain, or (residentOnPyramid) a DirectPyramidFeatureExtractor
-    // with a histogram, extended HOG or gray-patch chain behind PatchResizingFeatureExtractors only, on a pyramid that holds an image and
-    // whose width -> layer table fits FD_SAMPLE_TABLE_MAX
-    bool residentPossible() const;
-    bool residentOnPyramid() const;
+    // Which resident evaluation the model has right now, resolved once.  The classifier is a (Trainable)ProbabilisticSvmClassifier on f32
+    // vectors and the extractor resolves to a chain with at most FD_SAMPLE_MAPS_MAX wrappers that is ready.  Integral: a Haar, SURF or
+    // integral HOG chain.  Pyramid: a DirectPyramidFeatureExtractor with a histogram, extended HOG or gray-patch chain behind
+    // PatchResizingFeatureExtractors only, on a pyramid that holds an image and whose width -> layer table fits FD_SAMPLE_TABLE_MAX.
+    // The answer is about what the extractor holds now: update(image) can change it (the first image of a pyramid, another layer count)
+    struct ResidentPlan {
+        enum class Family { None, Integral, Pyramid } family;
+        imageprocessing::SampledChain chain;   // resolved with mapsApplied
+        SampledClassifier scorer;
+        const std::vector<fd_sample_map>& maps() const { return chain.wrappers.sampleMaps(); }
+    };
+    ResidentPlan residentPlan() const;
 private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticClassifier> classifier;
@@ -630,17 +636,17 @@ public:
 
 // The two trackers share the frame loop: sample -> evaluate -> extract (CondensationTracker.cpp:35-47), and for the adaptive one
 // validators and adapt (AdaptiveCondensationTracker.cpp:67-95).  Not in the reference: the device route.  With
-// FD_COND_DEVICE=1 a frame whose sampler is a ResamplingSampler on LowVarianceSampling + SimpleTransitionModel, whose model is an
-// ExtendedHogBasedMeasurementModel with adaptation NONE or POSITION and whose extractor is
-// FilteringStateExtractor(WeightedMeanStateExtractor) -- or whose transition model is an OpticalFlowTransitionModel with a
-// SimpleTransitionModel fallback and a grid of at most 1024 points, or a SimpleTransitionModel, and whose model is a SingleClassifierModel
-// (also the one inside a PositionDependentMeasurementModel) with a ProbabilisticSvmClassifier on f32 vectors on a Haar, SURF or integral
-// HOG extractor, or whose transition model is a SimpleTransitionModel and whose SingleClassifierModel is on a
-// DirectPyramidFeatureExtractor with a histogram, extended HOG or gray-patch chain (also behind PatchResizingFeatureExtractors) -- these
-// classes exactly: a subclass of any of them may override what the route
-// restates and therefore keeps the generic route -- runs on a particle set that stays on the device (fd_particles): the host draws the
-// same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample objects on demand;
-// they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
+// FD_COND_DEVICE=1 a frame runs on a particle set that stays on the device (fd_particles) when its sampler is a ResamplingSampler on
+// LowVarianceSampling, its extractor FilteringStateExtractor(WeightedMeanStateExtractor), and model and transition model are one of
+//  - ExtendedHogBasedMeasurementModel with adaptation NONE or POSITION, under SimpleTransitionModel;
+//  - SingleClassifierModel (also the one inside a PositionDependentMeasurementModel) with a ProbabilisticSvmClassifier on f32 vectors on
+//    a Haar, SURF or integral HOG extractor, under SimpleTransitionModel or an OpticalFlowTransitionModel with a SimpleTransitionModel
+//    fallback and a grid of at most 1024 points;
+//  - the same SingleClassifierModel on a DirectPyramidFeatureExtractor with a histogram, extended HOG or gray-patch chain (also behind
+//    PatchResizingFeatureExtractors), under SimpleTransitionModel only.
+// These classes exactly: a subclass of any of them may override what the route restates and therefore keeps the generic route.  The
+// host draws the same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample
+// objects on demand; they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
 class ParticleFrameLoop {
 public:
     enum class Route { NONE, GENERIC, DEVICE };
@@ -663,14 +669,13 @@ protected:
     std::shared_ptr<MeasurementModel> measurementModel;
     std::shared_ptr<StateExtractor> extractor;
 private:
-    bool deviceRoutePossible() const;
-    void deviceStep();
-    void releaseParticles();
-    // which resident frame the configuration has: Ehog is ExtendedHogBasedMeasurementModel on its tracker, Integral a
-    // SingleClassifierModel (also inside a PositionDependentMeasurementModel) on an unbound set, Pyramid the same on a pyramid chain (SimpleTransitionModel only)
+    // which resident frame the configuration has, decided before the model's update(image): Ehog is ExtendedHogBasedMeasurementModel on a
+    // set bound to its tracker; Integral and Pyramid are the two families of SingleClassifierModel::residentPlan, on an unbound set
     enum class ResidentKind { None, Ehog, Integral, Pyramid };
     ResidentKind residentKind() const;
-    void integralDeviceStep();
+    void deviceStep();
+    void bindParticles(fd_ehog_tracker* tracker);
+    void releaseParticles();
     void uploadGeneration();
     fd_particles* particles = nullptr;
     fd_ehog_tracker* particlesOn = nullptr;   // the tracker handle `particles` is bound to; NULL: an unbound set

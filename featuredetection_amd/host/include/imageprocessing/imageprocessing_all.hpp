@@ -721,6 +721,19 @@ struct SampledChain {
     // floats per cell where the reference's Mat carries them as channels: those of the inner extractor's ExtendedHogFilter (also behind
     // wrappers, or on layers the sampled calls do not serve), 1 for everything else
     int cellChannels() const;
+    // How the library is told about the chain: the handle of its family (one of the two; an integral image is NULL before the first
+    // update), the C kind (FD_SAMPLES_* on a pyramid, FD_INTEGRAL_* on an integral image) and the parameter block of that kind.  The
+    // blocks live in the chain, which therefore outlives the call; fd_haar_params, which points into the filter, lives in the descriptor
+    struct DeviceCall {
+        bool onPyramid = false;
+        fd_pyramid* pyramid = nullptr;
+        fd_integral* integral = nullptr;
+        int kind = 0;
+        const void* params() const { return block ? block : &haar; }
+        const void* block = nullptr;   // into the chain; NULL: haar
+        fd_haar_params haar{};
+    };
+    DeviceCall deviceCall() const;
     // The device conversations, on samples as the outermost extractor receives them.  extract: the patch data of every sample in one
     // fd_hist_ / fd_ehog_ / fd_patch_extract_samples or fd_integral_extract_hog, each Mat as extract(x, y, width, height)->getData()
     // gives it, empty where that returns null.  svmEvaluate: one fd_hist_ / fd_patch_ / fd_integral_svm_evaluate_samples.  hasWindow:

@@ -1013,20 +1013,30 @@ vector<Mat> SampledChain::extract(const vector<int32_t>& xywh) const {
     }
     return data;
 }
+SampledChain::DeviceCall SampledChain::deviceCall() const {
+    DeviceCall call;
+    call.onPyramid = onPyramid();
+    if (call.onPyramid) {
+        call.pyramid = pyramid->getPyramid()->native();
+        call.kind = kind == Kind::Patch ? (int)FD_SAMPLES_PATCH : (kind == Kind::Ehog ? (int)FD_SAMPLES_EHOG : (int)FD_SAMPLES_HIST);
+        call.block = kind == Kind::Patch ? (const void*)&patch : (kind == Kind::Ehog ? (const void*)&ehog : (const void*)&hist);
+    } else if (kind != Kind::None) {
+        call.integral = image->native();
+        call.kind = kind == Kind::Haar ? (int)FD_INTEGRAL_HAAR : (kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
+        call.block = kind == Kind::Haar ? nullptr : (kind == Kind::IntegralHog ? (const void*)&ihog : (const void*)&surf);
+        if (haar) call.haar = haar->params();
+    }
+    return call;
+}
 void SampledChain::svmEvaluate(const fd_svm* svm, const vector<int32_t>& xywh, uint8_t* target, double* weight) const {
     const int n = (int)(xywh.size() / 4);
-    if (kind == Kind::Patch) {
-        check(fd_patch_svm_evaluate_samples(context(), pyramid->getPyramid()->native(), &patch, svm, n, xywh.data(), target, weight, nullptr));
-    } else if (onPyramid()) {
-        check(fd_hist_svm_evaluate_samples(context(), pyramid->getPyramid()->native(), kind == Kind::Ehog ? FD_SAMPLES_EHOG : FD_SAMPLES_HIST,
-                                           kind == Kind::Ehog ? (const void*)&ehog : (const void*)&hist, svm, n, xywh.data(), target, weight));
-    } else {   // the wrappers are integer maps of the sample, applied here
-        fd_haar_params hp;
-        if (haar) hp = haar->params();
-        const int integralKind = haar ? (int)FD_INTEGRAL_HAAR : (kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
-        const void* prm = haar ? (const void*)&hp : (kind == Kind::IntegralHog ? (const void*)&ihog : (const void*)&surf);
-        check(fd_integral_svm_evaluate_samples(context(), image->native(), integralKind, prm, svm, n, mapped(xywh).data(), target, weight));
-    }
+    const DeviceCall call = deviceCall();
+    if (kind == Kind::Patch)
+        check(fd_patch_svm_evaluate_samples(context(), call.pyramid, &patch, svm, n, xywh.data(), target, weight, nullptr));
+    else if (call.onPyramid)
+        check(fd_hist_svm_evaluate_samples(context(), call.pyramid, call.kind, call.params(), svm, n, xywh.data(), target, weight));
+    else   // the wrappers are integer maps of the sample, applied here
+        check(fd_integral_svm_evaluate_samples(context(), call.integral, call.kind, call.params(), svm, n, mapped(xywh).data(), target, weight));
 }
 bool SampledChain::hasWindow(int x, int y, int width, int height) const {
     int32_t s[4] = {x, y, width, height};
@@ -2872,11 +2882,6 @@ static bool resident_integral(const imageprocessing::SampledChain& chain, const 
     return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && scorer.svm &&
            chain.wrappers.sampleMaps().size() <= (size_t)FD_SAMPLE_MAPS_MAX && chain.ready();
 }
-// The chain of a resident evaluation: the device maps every sample through the wrappers first (k_particles_xywh, k_particles_windows), so a
-// pyramid chain behind wrappers resolves too
-static imageprocessing::SampledChain resident_chain(const imageprocessing::FeatureExtractor* extractor) {
-    return imageprocessing::sampledChainOf(extractor, /*mapsApplied=*/true);
-}
 // fd_particles_evaluate_pyramid serves the chain: a pyramid kind with an f32 SVM behind at most FD_SAMPLE_MAPS_MAX wrappers, all of them
 // PatchResizingFeatureExtractors, on a pyramid that holds an image, has no more layers than the window table and whose width -> layer
 // table fits (fd_sample_layer_table)
@@ -2897,39 +2902,28 @@ static bool resident_pyramid(const imageprocessing::SampledChain& chain, const S
     const int rc = fd_sample_layer_table(layers, first, fd_pyramid_incremental_scale(native), patchWidth, 0, nullptr, &length);
     return (rc == FD_OK || rc == FD_ERR_CAPACITY) && length <= FD_SAMPLE_TABLE_MAX;
 }
-bool SingleClassifierModel::residentPossible() const {
-    const imageprocessing::SampledChain chain = resident_chain(featureExtractor.get());
-    const SampledClassifier scorer = sampledClassifierOf(classifier.get());
-    return resident_integral(chain, scorer) || resident_pyramid(chain, scorer);
-}
-bool SingleClassifierModel::residentOnPyramid() const {
-    return resident_pyramid(resident_chain(featureExtractor.get()), sampledClassifierOf(classifier.get()));
+// The device maps every sample through the wrappers first (fd_particle_sample), so a pyramid chain behind wrappers resolves too
+SingleClassifierModel::ResidentPlan SingleClassifierModel::residentPlan() const {
+    ResidentPlan plan{ResidentPlan::Family::None, imageprocessing::sampledChainOf(featureExtractor.get(), /*mapsApplied=*/true), sampledClassifierOf(classifier.get())};
+    if (resident_integral(plan.chain, plan.scorer)) plan.family = ResidentPlan::Family::Integral;
+    else if (resident_pyramid(plan.chain, plan.scorer)) plan.family = ResidentPlan::Family::Pyramid;
+    return plan;
 }
 void SingleClassifierModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) {
-    using Kind = imageprocessing::SampledChain::Kind;
     update(image);
-    const imageprocessing::SampledChain chain = resident_chain(featureExtractor.get());
-    const SampledClassifier scorer = sampledClassifierOf(classifier.get());
-    const bool onPyramid = resident_pyramid(chain, scorer);
-    if (!onPyramid && !resident_integral(chain, scorer)) throw std::logic_error("SingleClassifierModel: no resident evaluation for this extractor and classifier");
+    const ResidentPlan plan = residentPlan();   // after the update: the plan of the frame loop is from before it
+    if (plan.family == ResidentPlan::Family::None) throw std::logic_error("SingleClassifierModel: no resident evaluation for this extractor and classifier");
     ++fusedEvaluations;
-    const vector<fd_sample_map> maps = chain.wrappers.sampleMaps();
-    const double a = scorer.svm->getLogisticA(), b = scorer.svm->getLogisticB();
-    if (onPyramid) {
-        const int kind = chain.kind == Kind::Patch ? (int)FD_SAMPLES_PATCH : (chain.kind == Kind::Ehog ? (int)FD_SAMPLES_EHOG : (int)FD_SAMPLES_HIST);
-        const void* prm = chain.kind == Kind::Patch ? (const void*)&chain.patch : (chain.kind == Kind::Ehog ? (const void*)&chain.ehog : (const void*)&chain.hist);
-        check(fd_particles_evaluate_pyramid(context(), particles, chain.pyramid->getPyramid()->native(), kind, prm, scorer.svm->getSvm()->native(a, b),
-                                            Sample::getAspectRatio(), maps.data(), (int)maps.size()));
-    } else {
-        fd_haar_params hp;
-        if (chain.haar) hp = chain.haar->params();
-        const int kind = chain.kind == Kind::Haar ? (int)FD_INTEGRAL_HAAR : (chain.kind == Kind::IntegralHog ? (int)FD_INTEGRAL_HOG : (int)FD_INTEGRAL_SURF);
-        const void* prm = chain.kind == Kind::Haar ? (const void*)&hp : (chain.kind == Kind::IntegralHog ? (const void*)&chain.ihog : (const void*)&chain.surf);
-        check(fd_particles_evaluate_integral(context(), particles, chain.image->native(), kind, prm, scorer.svm->getSvm()->native(a, b), Sample::getAspectRatio(),
-                                             maps.data(), (int)maps.size()));
-    }
+    const imageprocessing::SampledChain::DeviceCall call = plan.chain.deviceCall();
+    const vector<fd_sample_map>& maps = plan.maps();
+    const double a = plan.scorer.svm->getLogisticA(), b = plan.scorer.svm->getLogisticB();
+    const fd_svm* svm = plan.scorer.svm->getSvm()->native(a, b);
+    if (call.onPyramid)
+        check(fd_particles_evaluate_pyramid(context(), particles, call.pyramid, call.kind, call.params(), svm, Sample::getAspectRatio(), maps.data(), (int)maps.size()));
+    else
+        check(fd_particles_evaluate_integral(context(), particles, call.integral, call.kind, call.params(), svm, Sample::getAspectRatio(), maps.data(), (int)maps.size()));
     // SvmClassifier::classify compares with the threshold the device model holds as a float (fd_samples_svm_tail does the same)
-    check(fd_particles_weigh_classifier(context(), particles, a, b, (double)(float)scorer.svm->getSvm()->getThreshold()));
+    check(fd_particles_weigh_classifier(context(), particles, a, b, (double)(float)plan.scorer.svm->getSvm()->getThreshold()));
 }
 
 // ---- FilteringClassifierModel (FilteringClassifierModel.cpp:27-103) --------------------------------------------------------------------
@@ -4173,6 +4167,29 @@ shared_ptr<Sample> MaxWeightStateExtractor::extract(const vector<shared_ptr<Samp
     return shared_ptr<Sample>();
 }
 
+// One generation on the host, as fd_particles_get and fd_particles_set move it
+struct ParticleArrays {
+    explicit ParticleArrays(int n) : n(n), x(n), y(n), size(n), vx(n), vy(n), cluster(n), vsize(n), weight(n), score(n), target(n) {}
+    static ParticleArrays of(fd_particles* particles) {   // the current generation of the set
+        int n = 0;
+        check(fd_particles_get(context(), particles, FD_PARTICLES_MAX, &n, nullptr));
+        ParticleArrays g(n);
+        fd_particles_arrays arrays = g.view();
+        check(fd_particles_get(context(), particles, n, &g.n, &arrays));
+        return g;
+    }
+    void set(fd_particles* particles) {
+        fd_particles_arrays arrays = view();
+        check(fd_particles_set(context(), particles, n, &arrays));
+    }
+    fd_particles_arrays view() { return {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()}; }
+    int n;
+    vector<int32_t> x, y, size, vx, vy, cluster;
+    vector<float> vsize;
+    vector<double> weight, score;
+    vector<uint8_t> target;
+};
+
 // evaluate(image, samples) (:107-168) on a resident particle set.  The heat peak is read before the samples are scored only where
 // the branch needs it first (target lost); a re-initialisation downloads the generation, rewrites it with the draws of the generic
 // route and scores it again.
@@ -4192,16 +4209,10 @@ void ExtendedHogBasedMeasurementModel::evaluateResident(shared_ptr<imageprocessi
     }
     // the generation on the host, rewritten by f, and back
     auto rewrite = [&](const std::function<void(int, fd_particles_arrays&)>& f) {
-        int n = 0;
-        check(fd_particles_get(context(), particles, FD_PARTICLES_MAX, &n, nullptr));
-        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
-        vector<float> vsize(n);
-        vector<double> weight(n), sc(n);
-        vector<uint8_t> target(n);
-        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), sc.data(), target.data(), cluster.data()};
-        check(fd_particles_get(context(), particles, n, &n, &arrays));
-        f(n, arrays);
-        check(fd_particles_set(context(), particles, n, &arrays));
+        ParticleArrays generation = ParticleArrays::of(particles);
+        fd_particles_arrays arrays = generation.view();
+        f(generation.n, arrays);
+        generation.set(particles);
     };
     std::pair<double, cv::Rect> peak;
     auto reinitialize = [&]() {
@@ -4294,33 +4305,26 @@ ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
                       std::static_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel())->residentPossible();
     if (!simple && !flow) return ResidentKind::None;
     const shared_ptr<SingleClassifierModel> single = resident_single_model(measurementModel);
-    if (!single || !single->residentPossible()) return ResidentKind::None;
-    if (!single->residentOnPyramid()) return ResidentKind::Integral;
+    using Family = SingleClassifierModel::ResidentPlan::Family;
+    const Family family = single ? single->residentPlan().family : Family::None;   // on what the extractor holds from the previous frame
+    if (family == Family::None) return ResidentKind::None;
+    if (family == Family::Integral) return ResidentKind::Integral;
     // a pyramid chain under OpticalFlowTransitionModel keeps the generic route: the library serves that frame (fd_particles_sample_flow,
     // then _evaluate_pyramid), but the route comparison of tracker_app pins `generic` for this combination
     return simple ? ResidentKind::Pyramid : ResidentKind::None;
 }
 
-bool ParticleFrameLoop::deviceRoutePossible() const { return residentKind() != ResidentKind::None; }
-
 const vector<shared_ptr<Sample>>& ParticleFrameLoop::currentSamples() const {
     if (resident && !materialized) {   // the Sample objects of the resident generation: no ancestors on this route
-        int n = 0;
-        check(fd_particles_get(context(), particles, FD_PARTICLES_MAX, &n, nullptr));
-        vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
-        vector<float> vsize(n);
-        vector<double> weight(n), score(n);
-        vector<uint8_t> target(n);
-        fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
-        check(fd_particles_get(context(), particles, n, &n, &arrays));
+        const ParticleArrays g = ParticleArrays::of(particles);
         samples.clear();
         const int nextId = Sample::nextClusterId;
-        for (int i = 0; i < n; ++i) {
-            auto sample = make_shared<Sample>(x[i], y[i], size[i], vx[i], vy[i], vsize[i]);
-            sample->setWeight(weight[i]);
-            sample->setScore(score[i]);
-            sample->setTarget(target[i] != 0);
-            sample->setClusterId(cluster[i]);
+        for (int i = 0; i < g.n; ++i) {
+            auto sample = make_shared<Sample>(g.x[i], g.y[i], g.size[i], g.vx[i], g.vy[i], g.vsize[i]);
+            sample->setWeight(g.weight[i]);
+            sample->setScore(g.score[i]);
+            sample->setTarget(g.target[i] != 0);
+            sample->setClusterId(g.cluster[i]);
             samples.push_back(sample);
         }
         Sample::nextClusterId = nextId;   // building the objects draws no cluster ids
@@ -4337,95 +4341,88 @@ void ParticleFrameLoop::replaceSamples(const vector<shared_ptr<Sample>>& newSamp
 
 // the generation of the generic route (or of initialize) moves to the device
 void ParticleFrameLoop::uploadGeneration() {
-    const int n = (int)samples.size();
-    vector<int32_t> x(n), y(n), size(n), vx(n), vy(n), cluster(n);
-    vector<float> vsize(n);
-    vector<double> weight(n), score(n);
-    vector<uint8_t> target(n);
+    ParticleArrays g((int)samples.size());
     residentWeightSum = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < g.n; ++i) {
         const Sample& s = *samples[i];
-        x[i] = s.getX(); y[i] = s.getY(); size[i] = s.getSize(); vx[i] = s.getVx(); vy[i] = s.getVy(); vsize[i] = s.getVSize();
-        weight[i] = s.getWeight(); score[i] = s.getScore(); target[i] = s.isTarget(); cluster[i] = s.getClusterId();
-        residentWeightSum += weight[i];
+        g.x[i] = s.getX(); g.y[i] = s.getY(); g.size[i] = s.getSize(); g.vx[i] = s.getVx(); g.vy[i] = s.getVy(); g.vsize[i] = s.getVSize();
+        g.weight[i] = s.getWeight(); g.score[i] = s.getScore(); g.target[i] = s.isTarget(); g.cluster[i] = s.getClusterId();
+        residentWeightSum += g.weight[i];
     }
-    fd_particles_arrays arrays = {x.data(), y.data(), size.data(), vx.data(), vy.data(), vsize.data(), weight.data(), score.data(), target.data(), cluster.data()};
-    check(fd_particles_set(context(), particles, n, &arrays));
-    residentCount = n;
+    g.set(particles);
+    residentCount = g.n;
     resident = true;
 }
 
-// SingleClassifierModel on the integral family or on a pyramid family, SimpleTransitionModel or OpticalFlowTransitionModel: an unbound set.  The host draws
-// every random number the generic route would draw: the three generators (resampling, transition, fresh samples) are separate, so only
-// the order within each matters.  With the flow model the branch is the device's: both blocks are drawn behind snapshots and the model
-// that did not predict gets its snapshot back after the read-back.
-void ParticleFrameLoop::integralDeviceStep() {
-    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
-    const shared_ptr<SingleClassifierModel> model = resident_single_model(measurementModel);
-    auto flow = std::dynamic_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel());
-    if (particles && particlesOn) {   // a set bound to a tracker: the generation comes back and moves to an unbound one
-        currentSamples();
-        resident = false;
-        releaseParticles();
+// The set this frame needs: bound to `tracker` (ExtendedHogBasedMeasurementModel), or unbound (NULL).  A set on hand that is another one
+// -- the model was initialised again and has another tracker handle -- is released, and a generation that lived in it is lost with it
+void ParticleFrameLoop::bindParticles(fd_ehog_tracker* tracker) {
+    if (particles && particlesOn != tracker) releaseParticles();
+    if (particles) return;
+    if (resident)
+        throw std::logic_error(tracker ? "ParticleFrameLoop: the resident generation was lost with its tracker"
+                                       : "ParticleFrameLoop: the resident generation was lost with its particle set");
+    if (tracker) check(fd_particles_create(context(), tracker, FD_PARTICLES_MAX, &particles));
+    else check(fd_particles_create_unbound(context(), FD_PARTICLES_MAX, &particles));
+    particlesOn = tracker;
+}
+
+// The bracket of an OpticalFlowTransitionModel around a resident frame; without one (flow NULL) the plain sample call and state.  The
+// branch between the flow and its fallback is the device's: both blocks are drawn behind snapshots and the model that did not predict
+// gets its snapshot back after the read-back.
+struct ResidentFlow {
+    ResidentFlow(OpticalFlowTransitionModel* flow, const Mat& data, const shared_ptr<Sample>& state)
+        : flow(flow), tracked(flow && flow->beginResident(data, state)),
+          fallback(flow ? static_cast<SimpleTransitionModel*>(flow->getFallback().get()) : nullptr) {   // null: the sampler's own
+        if (tracked) before = fallback->drawState();
     }
-    if (!particles) {
-        if (resident) throw std::logic_error("ParticleFrameLoop: the resident generation was lost with its particle set");
-        check(fd_particles_create_unbound(context(), FD_PARTICLES_MAX, &particles));
+    void sample(fd_particles* particles, const ResamplingSampler::Draws& draws, int copies, int fresh, int firstFreshId) {
+        if (tracked) {
+            const vector<double>& flowDiffusion = flow->drawResident((size_t)copies);
+            check(fd_particles_sample_flow(context(), particles, flow->native(), copies + fresh, copies, draws.u, flowDiffusion.data(), draws.diffusion.data(),
+                                           draws.fresh.data(), firstFreshId));
+        } else {
+            check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
+        }
     }
-    if (!resident) uploadGeneration();
-    const Mat& data = image->getData();
-    const bool tracked = flow && flow->beginResident(data, state);
-    SimpleTransitionModel* simple = flow ? static_cast<SimpleTransitionModel*>(flow->getFallback().get()) : nullptr;   // null: the sampler's own
-    SimpleTransitionModel::DrawState before;
-    if (tracked) before = simple->drawState();
-    const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows, simple);
-    const int copies = (int)(draws.diffusion.size() / 3), fresh = (int)(draws.fresh.size() / 3);
-    const int firstFreshId = Sample::nextClusterId;
-    Sample::nextClusterId += fresh;
-    if (tracked) {
-        const vector<double>& flowDiffusion = flow->drawResident((size_t)copies);
-        check(fd_particles_sample_flow(context(), particles, flow->native(), copies + fresh, copies, draws.u, flowDiffusion.data(), draws.diffusion.data(),
-                                       draws.fresh.data(), firstFreshId));
-    } else {
-        check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
-    }
-    model->evaluateResident(image, particles);
-    fd_particles_info info;
-    if (tracked) {
+    void readState(fd_particles* particles, fd_particles_info& info) {
+        if (!tracked) {
+            check(fd_particles_state(context(), particles, &info));
+            return;
+        }
         fd_flow_motion_info motion;
         check(fd_particles_state_flow(context(), particles, flow->native(), &info, &motion));
         flow->endResident(motion);
-        if (motion.ok) simple->restoreDrawState(before);   // the flow predicted: the fallback drew nothing
-    } else {
-        check(fd_particles_state(context(), particles, &info));
+        if (motion.ok) fallback->restoreDrawState(before);   // the flow predicted: the fallback drew nothing
     }
-    residentCount = info.count;
-    residentWeightSum = info.weight_sum;
-    materialized = false;
-    samples.clear();
-    oldSamples.clear();
-    state = info.found ? make_shared<Sample>(info.x, info.y, info.size, info.vx, info.vy, info.vsize) : shared_ptr<Sample>();
-}
+    OpticalFlowTransitionModel* flow;
+    bool tracked;
+    SimpleTransitionModel* fallback;
+    SimpleTransitionModel::DrawState before;
+};
 
+// One frame on the resident set.  The host draws every random number the generic route would draw: the three generators (resampling,
+// transition, fresh samples) are separate, so only the order within each matters.
 void ParticleFrameLoop::deviceStep() {
-    if (lastKind == ResidentKind::Integral || lastKind == ResidentKind::Pyramid) return integralDeviceStep();
-    auto model = std::dynamic_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
-    auto resampling = std::dynamic_pointer_cast<ResamplingSampler>(sampler);
-    if (particles && particlesOn != model->native()) releaseParticles();   // the model was initialised again: another tracker handle
-    if (!particles) {
-        check(fd_particles_create(context(), model->native(), FD_PARTICLES_MAX, &particles));
-        particlesOn = model->native();
-        if (resident) throw std::logic_error("ParticleFrameLoop: the resident generation was lost with its tracker");
-    }
+    auto resampling = std::static_pointer_cast<ResamplingSampler>(sampler);
+    const bool onTracker = lastKind == ResidentKind::Ehog;
+    auto ehog = onTracker ? std::static_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel) : nullptr;
+    bindParticles(onTracker ? ehog->native() : nullptr);
     if (!resident) uploadGeneration();
     const Mat& data = image->getData();
-    const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows);
+    ResidentFlow flow(dynamic_cast<OpticalFlowTransitionModel*>(resampling->getTransitionModel().get()), data, state);   // Ehog: never one
+    const ResamplingSampler::Draws& draws = resampling->drawFrame((size_t)residentCount, residentWeightSum, data.cols, data.rows, flow.fallback);
     const int copies = (int)(draws.diffusion.size() / 3), fresh = (int)(draws.fresh.size() / 3);
     const int firstFreshId = Sample::nextClusterId;
     Sample::nextClusterId += fresh;   // the ids the random samples of the generic route would have drawn, in order
-    check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
+    flow.sample(particles, draws, copies, fresh, firstFreshId);
     fd_particles_info info;
-    model->evaluateResident(image, particles, info);
+    if (onTracker) {   // the model reads the state itself: its re-initialisation needs the best score in the middle
+        ehog->evaluateResident(image, particles, info);
+    } else {
+        resident_single_model(measurementModel)->evaluateResident(image, particles);
+        flow.readState(particles, info);
+    }
     residentCount = info.count;
     residentWeightSum = info.weight_sum;
     materialized = false;
