@@ -429,6 +429,9 @@ _SIGS = {
     "fd_particles_evaluate_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
     "fd_particles_weigh_classifier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]),
     "fd_particles_evaluate_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
+    "fd_particles_evaluate_wvm_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int]),
+    "fd_particles_weigh_wvm_svm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fd_particles_get_wvm_svm_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "fd_sample_layer_table": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fd_flow_track_fb_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "fd_flow_get_tracks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1569,6 +1572,21 @@ class Particles:
 
     def weigh_classifier(self, logistic_a, logistic_b, threshold):
         self.ctx.check(lib().fd_particles_weigh_classifier(self.ctx.h, self.h, logistic_a, logistic_b, threshold))
+
+    def evaluate_wvm_svm(self, pyr, wvm, svm, aspect_ratio, maps=()):
+        """fd_particles_evaluate_wvm_svm on an updated gray Pyramid: the WVM cascade on every particle's window; maps as evaluate_pyramid"""
+        chain = sample_maps(maps)
+        self.ctx.check(lib().fd_particles_evaluate_wvm_svm(self.ctx.h, self.h, pyr.h, wvm.h, svm.h, aspect_ratio, chain, len(chain)))
+
+    def weigh_wvm_svm(self, wvm, svm):
+        """fd_particles_weigh_wvm_svm: the SVM on the up to 8 most probable WVM positives, then WvmSvmModel's targets and weights"""
+        self.ctx.check(lib().fd_particles_weigh_wvm_svm(self.ctx.h, self.h, wvm.h, svm.h))
+
+    def wvm_svm_trace(self):
+        """fd_particles_get_wvm_svm_trace: (selected particle indices int32 (count,), most probable first, their SVM distances float64)"""
+        count, index, distance = C.c_int(), np.zeros(8, np.int32), np.zeros(8, np.float64)
+        self.ctx.check(lib().fd_particles_get_wvm_svm_trace(self.ctx.h, self.h, C.byref(count), _ptr(index), _ptr(distance)))
+        return index[:count.value].copy(), distance[:count.value].copy()
 
     def sample_flow(self, flow, count, n_resampled, u, flow_diffusion, fallback_diffusion, fresh, first_fresh_cluster_id):
         """fd_particles_sample_flow: sample() with the motion `flow` holds on the device and a block of draws for either transition"""

@@ -6,7 +6,8 @@
 // SingleClassifierModel on the integral family (scored by integral.hip, weighed by k_particles_weigh's classifier mode) and
 // OpticalFlowTransitionModel::predict (k_particles_sample with the motion optflow.hip leaves on the device), and SingleClassifierModel
 // on the pyramid families: fd_particles_evaluate_pyramid resolves the samples to windows here (particle_windows.hpp) and hands the list to
-// the scoring kernels of hog.hip / rvm.hip.  DESIGN.md 4.7.
+// the scoring kernels of hog.hip / rvm.hip.  condensation::WvmSvmModel takes the same window list through wvm.hip's cascade
+// (fd_particles_evaluate_wvm_svm); its selection rule and its weighting are particle_wvm_svm.hpp.  DESIGN.md 4.7.
 //
 // Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
 // needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
@@ -103,17 +104,38 @@ __global__ __launch_bounds__(PT) void k_particles_sample(ParticleGen src, Partic
     }
 }
 
+// ProbabilisticSvmClassifier::getProbability (.cpp:54-58) on fABp = logisticA + logisticB * score, in double
+__device__ inline double particle_logistic(double fABp) { return fABp >= 0 ? exp(-fABp) / (1.0 + exp(-fABp)) : 1.0 / (1.0 + exp(fABp)); }
+
+// the end of a weighing kernel: the largest of the threads' best scores and the sum of their valid counts into the info
+__device__ inline void particles_publish_best(double best, int nValid, fd_particles_info* __restrict__ info) {
+    __shared__ double sBest[PT];
+    __shared__ int sValid[PT];
+    const int tid = threadIdx.x;
+    sBest[tid] = best;
+    sValid[tid] = nValid;
+    __syncthreads();
+    for (int s = PT / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            if (sBest[tid] < sBest[tid + s]) sBest[tid] = sBest[tid + s];
+            sValid[tid] += sValid[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        info->best_score = sBest[0];
+        info->n_valid = sValid[0];
+    }
+}
+
 // ExtendedHogBasedMeasurementModel::scored for every sample, ProbabilisticSvmClassifier::getProbability (.cpp:54-58) in double.  Two
 // passes: the first only looks for a product that is negative or not finite; with one, nothing is written but the flag.
 // mode PARTICLES_CLASSIFIER is SingleClassifierModel.cpp:32-42: the weight is the probability itself, target = score >= svmThreshold.
 __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, const uint8_t* __restrict__ valid, double logisticA, double logisticB,
                                                         double svmThreshold, int mode, double rejectionThreshold, fd_particles_info* __restrict__ info) {
-    __shared__ double sBest[PT];
-    __shared__ int sValid[PT];
     const int tid = threadIdx.x;
     auto weighed = [&](int i) {
-        const double fABp = logisticA + logisticB * g.score[i];
-        const double p = fABp >= 0 ? exp(-fABp) / (1.0 + exp(-fABp)) : 1.0 / (1.0 + exp(fABp));
+        const double p = particle_logistic(logisticA + logisticB * g.score[i]);
         return mode == PARTICLES_CLASSIFIER ? p : g.weight[i] * p;
     };
     int bad = 0;
@@ -140,21 +162,14 @@ __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, co
         }
         if (best < score) best = score;
     }
-    sBest[tid] = best;
-    sValid[tid] = nValid;
-    __syncthreads();
-    for (int s = PT / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            if (sBest[tid] < sBest[tid + s]) sBest[tid] = sBest[tid + s];
-            sValid[tid] += sValid[tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        info->best_score = sBest[0];
-        info->n_valid = sValid[0];
-    }
+    particles_publish_best(best, nValid, info);
 }
+
+}  // namespace
+
+#include "particle_wvm_svm.hpp"
+
+namespace {
 
 __device__ inline unsigned int particle_hash(int32_t id) { return (unsigned int)id * 2654435761u; }
 
@@ -274,6 +289,14 @@ struct fd_particles {
     int32_t* windows = nullptr;   // per sample {layer, bx, by, valid} of fd_particles_evaluate, or the mapped {x, y, width, height} of _evaluate_integral
     uint8_t* valid = nullptr;
     HostBuf pinned;   // the draws of one fd_particles_sample / _sample_flow on their way to the device
+    // fd_particles_evaluate_wvm_svm: the model the current generation was evaluated with (NULL: none, or another kind of evaluate), what its
+    // cascade left on the device (wvmCascaded: it ran at all), and the selection of fd_particles_weigh_wvm_svm
+    const fd_wvm* wvm = nullptr;
+    bool wvmCascaded = false, wvmWeighed = false;
+    FdWvmResidentRun wvmRun{};
+    DevBuf wvmSel;
+    void evaluatedBy(const fd_wvm* m) { evaluated = true; wvm = m; wvmWeighed = false; }
+    void notEvaluated() { evaluated = false; wvm = nullptr; wvmWeighed = false; }
     hipEvent_t uploaded = nullptr;
     ~fd_particles() { if (uploaded) (void)hipEventDestroy(uploaded); }
 };
@@ -387,7 +410,27 @@ void particles_sample(fd_ctx* ctx, fd_particles* p, const char* who, fd_flow* fl
     p->n = nCopies + nFresh;
     p->sum = (double)p->n;   // every new sample has weight 1: n times 1 added up is exact
     p->sumKnown = true;
-    p->evaluated = false;
+    p->notEvaluated();
+}
+
+// k_particles_windows for the current generation (n > 0) and patches of pw x ph: fills p->list, the trace and the valid flags.  False:
+// no kept layer holds a window at all, every sample is invalid and the list must not be scored.
+bool particles_windows(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int pw, int ph, double aspect_ratio, const FdSampleMaps& chain) {
+    const ParticleGen& G = p->gen[p->cur];
+    ParticleLayers layers;
+    std::memset(&layers, 0, sizeof(layers));
+    layers.n = (int32_t)pyr->kept.size();
+    FdSampleWindow spare{-1, 0, 0};   // the first kept layer that holds a window at all
+    for (int l = 0; l < layers.n; ++l) {
+        const HostLayer& L = pyr->all[pyr->kept[l]];
+        layers.l[l].scale = L.scale; layers.l[l].w = L.w; layers.l[l].h = L.h;
+        if (spare.layer < 0 && L.w >= pw && L.h >= ph) spare.layer = l;
+    }
+    p->list.reserve(sizeof(int32_t) * 3 * (size_t)p->capacity);
+    hipLaunchKernelGGL(k_particles_windows, dim3((p->n + 255) / 256), dim3(256), 0, ctx->stream, G.x, G.y, G.size, p->n, aspect_ratio, chain, layers,
+                       pyr->sample_table.dev.as<int16_t>(), pyr->sample_table.length, pw, ph, spare, p->list.as<int32_t>(), (int4*)p->windows, p->valid);
+    HIP_CHECK(hipGetLastError());
+    return spare.layer >= 0;
 }
 
 void particles_weigh(fd_ctx* ctx, fd_particles* p, const char* who, double logistic_a, double logistic_b, double svm_threshold, int mode,
@@ -465,7 +508,7 @@ int fd_particles_set(fd_ctx* ctx, fd_particles* p, int n, const fd_particles_arr
         p->sum = sum;
         p->sumKnown = true;
         p->bad = bad;
-        p->evaluated = false;
+        p->notEvaluated();
     });
 }
 
@@ -522,7 +565,7 @@ int fd_particles_evaluate(fd_ctx* ctx, fd_particles* p, int use_patches, double 
         if (!p->tracker) FD_THROW(FD_ERR_RUNTIME, "fd_particles_evaluate: the set is bound to no tracker (fd_particles_create_unbound)");
         const ParticleGen& G = p->gen[p->cur];
         fd_ehog_tracker_score_particles(ctx, p->tracker, p->n, G.x, G.y, G.size, aspect_ratio, use_patches != 0, p->windows, p->valid, G.score);
-        p->evaluated = true;
+        p->evaluatedBy(nullptr);
     });
 }
 
@@ -547,24 +590,87 @@ int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr,
         int pw = 0, ph = 0;
         score_list(nullptr, &pw, &ph);
         particle_windows_table(ctx, pyr, pw, who);
-        if (n > 0) {
-            ParticleLayers layers;
-            std::memset(&layers, 0, sizeof(layers));
-            layers.n = (int32_t)pyr->kept.size();
-            FdSampleWindow spare{-1, 0, 0};   // the first kept layer that holds a window at all
-            for (int l = 0; l < layers.n; ++l) {
-                const HostLayer& L = pyr->all[pyr->kept[l]];
-                layers.l[l].scale = L.scale; layers.l[l].w = L.w; layers.l[l].h = L.h;
-                if (spare.layer < 0 && L.w >= pw && L.h >= ph) spare.layer = l;
-            }
-            p->list.reserve(sizeof(int32_t) * 3 * (size_t)p->capacity);
-            hipLaunchKernelGGL(k_particles_windows, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, G.x, G.y, G.size, n, aspect_ratio, chain, layers,
-                               pyr->sample_table.dev.as<int16_t>(), pyr->sample_table.length, pw, ph, spare, p->list.as<int32_t>(), (int4*)p->windows,
-                               p->valid);
+        if (n > 0 && particles_windows(ctx, p, pyr, pw, ph, aspect_ratio, chain)) score_list(p->list.as<int32_t>(), &pw, &ph);
+        p->evaluatedBy(nullptr);
+    });
+}
+
+int fd_particles_evaluate_wvm_svm(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, const fd_wvm* wvm, const fd_svm* svm, double aspect_ratio,
+                                  const fd_sample_map* maps, int n_maps) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_evaluate_wvm_svm";
+        if (!ctx || !p || !pyr || !wvm || !svm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        particles_checked(ctx, p, who);
+        p->notEvaluated();   // a refused call leaves the generation "not evaluated"
+        const FdSampleMaps chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE, who);
+        fd_wvm_resident_check(ctx, pyr, wvm, svm, p->n, who);
+        fd_pyramid_require_single(pyr, who);
+        fd_pyramid_require_image(pyr);
+        int pw = 0, ph = 0;
+        fd_wvm_patch_size(wvm, &pw, &ph);
+        particle_windows_table(ctx, pyr, pw, who);
+        const int n = p->n;
+        p->wvmCascaded = false;
+        if (n > 0 && particles_windows(ctx, p, pyr, pw, ph, aspect_ratio, chain)) {
+            fd_wvm_list_launch_resident(ctx, pyr, const_cast<fd_wvm*>(wvm), p->list.as<int32_t>(), n, p->wvmRun);
+            p->wvmCascaded = true;
+            hipLaunchKernelGGL(k_particles_fout_scores, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, p->wvmRun.fout, n, p->gen[p->cur].score);
             HIP_CHECK(hipGetLastError());
-            if (spare.layer >= 0) score_list(p->list.as<int32_t>(), &pw, &ph);   // otherwise no layer holds a window: every sample is invalid
         }
-        p->evaluated = true;
+        p->evaluatedBy(wvm);
+    });
+}
+
+int fd_particles_weigh_wvm_svm(fd_ctx* ctx, fd_particles* p, const fd_wvm* wvm, const fd_svm* svm) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_weigh_wvm_svm";
+        if (!ctx || !p || !wvm || !svm) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        particles_checked(ctx, p, who);
+        fd_wvm_svm_pair_check(ctx, wvm, svm, who);   // this call's SVM reads the patch rows: the evaluate's check was of its own argument
+        if (!p->evaluated || p->wvm != wvm)
+            FD_THROW(FD_ERR_RUNTIME, "%s: the generation has not been evaluated by fd_particles_evaluate_wvm_svm with this WVM", who);
+        if (p->wvmCascaded && fd_wvm_run_serial(wvm) != p->wvmRun.serial)
+            FD_THROW(FD_ERR_RUNTIME, "%s: the WVM handle has run again since fd_particles_evaluate_wvm_svm: the positives of that run are gone", who);
+        if (p->n == 0) { p->wvmWeighed = true; return; }
+        double wvmA, wvmB, svmA, svmB;
+        fd_wvm_logistic(wvm, &wvmA, &wvmB);
+        fd_svm_logistic(svm, &svmA, &svmB);
+        const bool fresh = !p->wvmSel.p;
+        p->wvmSel.reserve(sizeof(ParticleWvmSvmSel));
+        if (fresh) HIP_CHECK(hipMemsetAsync(p->wvmSel.p, 0, sizeof(ParticleWvmSvmSel), ctx->stream));
+        ParticleWvmSvmSel* sel = p->wvmSel.as<ParticleWvmSvmSel>();
+        const FdWvmResidentRun& run = p->wvmRun;
+        hipLaunchKernelGGL(k_particles_wvm_svm_select, dim3(1), dim3(PT), 0, ctx->stream, run.pos, p->wvmCascaded ? run.pos_count : nullptr, p->n, p->valid,
+                           wvmA, wvmB, sel);
+        HIP_CHECK(hipGetLastError());
+        // a fixed 8 rows: the unused entries name row 0, which exists, and their distances are never read
+        if (p->wvmCascaded) fd_svm_generic_launch(ctx, svm, run.patches, sel->row, (int64_t)run.dim, WVM_SVM_RESCORED, sel->distance);
+        hipLaunchKernelGGL(k_particles_wvm_svm_weigh, dim3(1), dim3(PT), 0, ctx->stream, p->gen[p->cur], p->n, p->valid, wvmA, wvmB, svmA, svmB,
+                           (double)fd_svm_threshold(svm), sel, p->dinfo.as<fd_particles_info>());
+        HIP_CHECK(hipGetLastError());
+        p->sumKnown = false;
+        p->wvmWeighed = true;
+    });
+}
+
+int fd_particles_get_wvm_svm_trace(fd_ctx* ctx, fd_particles* p, int* count, int32_t* index, double* distance) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_get_wvm_svm_trace";
+        if (!ctx || !p || !count) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
+        particles_checked(ctx, p, who);
+        if (!p->evaluated || !p->wvm || !p->wvmWeighed)
+            FD_THROW(FD_ERR_RUNTIME, "%s: the generation has not been evaluated and weighed by fd_particles_evaluate_wvm_svm / _weigh_wvm_svm", who);
+        ParticleWvmSvmSel sel;
+        std::memset(&sel, 0, sizeof(sel));
+        if (p->n > 0) {
+            HIP_CHECK(hipMemcpyAsync(&sel, p->wvmSel.p, sizeof(sel), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        }
+        *count = sel.count;
+        for (int k = 0; k < WVM_SVM_RESCORED; ++k) {
+            if (index) index[k] = k < sel.count ? sel.index[k] : -1;
+            if (distance) distance[k] = k < sel.count ? sel.distance[k] : 0.0;
+        }
     });
 }
 
@@ -610,4 +716,4 @@ FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who)
     return FdParticlesView{p->n, G.x, G.y, G.size, G.score, p->valid, p->windows};
 }
 
-void fd_particles_set_evaluated(fd_particles* p) { p->evaluated = true; }
+void fd_particles_set_evaluated(fd_particles* p) { p->evaluatedBy(nullptr); }

@@ -731,6 +731,31 @@ void fd_hist_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, int kind, cons
                                 int n, double* dscore, int* patch_w, int* patch_h);
 void fd_patch_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const fd_svm* svm, const char* who,
                                  const int32_t* dlist, int n, double* dscore, int* patch_w, int* patch_h);
+// ---- resident particle set on condensation::WvmSvmModel (condensation.hip with particle_wvm_svm.hpp; the cascade is wvm.hip's) ----
+// What a list-mode cascade run with per-window outputs leaves on the device, for the kernels queued behind it on ctx->stream.  The
+// buffers are the WVM handle's: they hold until its next run.
+struct FdWvmResidentRun {
+    const uint4* pos;               // positive records {window id low, high, level, fp32 bits of fout}; the record's place is its patch row
+    const unsigned int* pos_count;  // their number (at most the windows of the list)
+    const uint8_t* patches;         // dim bytes per row: the equalised patch of the positive at that place
+    const float* fout;              // per window of the list
+    const int32_t* level;
+    int dim;
+    uint64_t serial;                // fd_wvm_run_serial behind this run: another one afterwards means the buffers are another run's
+};
+// the rules of the pair: both belong to ctx, the SVM works on u8 vectors of the WVM's dimension (five_stage_check).  Throws FdError
+void fd_wvm_svm_pair_check(fd_ctx* ctx, const fd_wvm* m, const fd_svm* svm, const char* who);
+// every argument rule of a resident run of (m, svm) on n windows of p; throws FdError before anything is queued
+void fd_wvm_resident_check(fd_ctx* ctx, const fd_pyramid* p, const fd_wvm* m, const fd_svm* svm, int n, const char* who);
+// counts the cascade runs launched on the handle (every run reuses, and may reallocate, its output buffers)
+uint64_t fd_wvm_run_serial(const fd_wvm* m);
+// the exact cascade (stage A, stage B) on the n >= 1 windows {layer, bx, by} at dlist, queued on ctx->stream: no wait, no copy.  The positive
+// buffer and stage B's state hold all n windows whatever FD_WVM_POS_CAP says.  Leaves the handle as a run with per-window outputs does.
+void fd_wvm_list_launch_resident(fd_ctx* ctx, fd_pyramid* p, fd_wvm* m, const int32_t* dlist, int n, FdWvmResidentRun& out);
+void fd_wvm_patch_size(const fd_wvm* m, int* fw, int* fh);
+void fd_wvm_logistic(const fd_wvm* m, double* a, double* b);
+void fd_svm_logistic(const fd_svm* m, double* a, double* b);
+const fd_ctx* fd_svm_context(const fd_svm* m);
 // the motion a resident track (or fd_debug_flow_motion) left in the handle (device memory); checks flow against ctx, throws FdError
 // (FD_ERR_RUNTIME) when there is none
 const fd_flow_motion_info* fd_flow_device_motion(fd_ctx* ctx, fd_flow* flow, const char* who);

@@ -584,6 +584,8 @@ int fd_svm_KP(const fd_svm* m) { return m->dev.KP; }
 float fd_svm_threshold(const fd_svm* m) { return m->threshold; }
 int fd_svm_dim(const fd_svm* m) { return m->dev.dim; }
 bool fd_svm_is_u8(const fd_svm* m) { return m->dev.dtype == FD_DTYPE_U8; }
+void fd_svm_logistic(const fd_svm* m, double* a, double* b) { *a = m->logisticA; *b = m->logisticB; }
+const fd_ctx* fd_svm_context(const fd_svm* m) { return m->ctx; }
 double fd_svm_probability(const fd_svm* m, double d) {  // ProbabilisticSvmClassifier.cpp:54-58 (host, libm)
     double fABp = m->logisticA + m->logisticB * d;
     return fABp >= 0 ? std::exp(-fABp) / (1.0 + std::exp(-fABp)) : 1.0 / (1.0 + std::exp(fABp));

@@ -162,6 +162,7 @@ struct fd_wvm {
     int sbPlanN = 0, sbPlanCut[WVB_MAXPHASE] = {};   // cuts of the run in flight
     int sbLastN = 0, sbLastGen[WVB_MAXPHASE + 1] = {};   // phases of the last launch and their generation boundaries (fd_wvm_last_stage_b_plan)
     int64_t sbGrown = 0;             // capacity a queue overflow made the handle grow to
+    uint64_t runSerial = 0;          // cascade runs launched on the handle (wvm_launch_head); fd_wvm_run_serial
     int64_t prevPos = 0;             // positives of the handle's previous run (the batch entry points start the heaviest host tails first)
     std::shared_ptr<void> relaunch;   // WvbRelaunch: what fd_wvm_finish needs to run stage B again with a larger state (queue overflow)
     // five-stage tail on the device (fs_tail.hpp): overlap elimination + SVM queued behind the cascade
@@ -1288,11 +1289,15 @@ static int64_t wvb_cap_env() {   // read per run (the tests provoke the overflow
     if (const char* e = getenv("FD_WVM_DEEP_CAP")) if (atoll(e) > 0) return (int64_t)atoll(e);
     return 0;
 }
-static void wvb_reserve(fd_wvm* m, int64_t total, int64_t minCap = 0) {
+// the windows the state of a run over `total` windows holds (what wvb_reserve makes of them)
+static int64_t wvb_capacity(const fd_wvm* m, int64_t total, int64_t minCap) {
     const int64_t capEnv = wvb_cap_env();
+    const int64_t cap = capEnv ? capEnv : std::max<int64_t>(std::max<int64_t>(minCap, m->sbGrown), (int64_t)1 << 18);
+    return std::max<int64_t>(64, std::min<int64_t>(total, cap));
+}
+static void wvb_reserve(fd_wvm* m, int64_t total, int64_t minCap = 0) {
     const WvbDev& mv = m->wvb;
-    int64_t cap = capEnv ? capEnv : std::max<int64_t>(std::max<int64_t>(minCap, m->sbGrown), (int64_t)1 << 18);
-    cap = std::max<int64_t>(64, std::min<int64_t>(total, cap));
+    const int64_t cap = wvb_capacity(m, total, minCap);
     const int64_t tilesCap = (cap + 63) / 64;
     WvbState& s = m->sb;
     for (int i = 0; i < 2; ++i) {
@@ -1607,11 +1612,14 @@ struct WvmLaunch {
     bool headerMemset = false;   // a memset of the device header was queued on the stream
     bool queued = false;         // the head queued anything at all on the stream (header / counter clears)
 };
-static bool wvm_launch_head(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const WinTable& wt, bool want_all, WvmRun& run, bool time_kernel, WvmLaunch& L) {
+// minPos: rows the positive buffers hold at least, whatever FD_WVM_POS_CAP says (fd_wvm_list_launch_resident: nobody reads an overflow back)
+static bool wvm_launch_head(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const WinTable& wt, bool want_all, WvmRun& run, bool time_kernel, WvmLaunch& L,
+                            int64_t minPos = 0) {
     run.total = wt.total;
     run.pos.clear();
     run.slots.clear();
     run.timed = time_kernel;
+    ++m->runSerial;
     const bool tailWanted = m->tailWanted;
     m->tailWanted = false;
     m->tailRun = false;
@@ -1627,7 +1635,7 @@ static bool wvm_launch_head(fd_ctx* ctx, hipStream_t st, fd_wvm* m, const WinTab
     {   // capacity of the positive buffers (records + 1 patch each): never more than the window count, 2^18 at most unless
         // FD_WVM_POS_CAP says otherwise; grows with the largest run seen (a 640x480 FaceFrontal handle holds 6.5 MB, not 105 MB)
         static const int64_t capEnv = [] { const char* e = getenv("FD_WVM_POS_CAP"); return e && atoll(e) > 0 ? (int64_t)atoll(e) : (int64_t)0; }();
-        const int64_t want = capEnv ? capEnv : std::min<int64_t>(wt.total, (int64_t)1 << 18);
+        const int64_t want = std::max<int64_t>(capEnv ? capEnv : std::min<int64_t>(wt.total, (int64_t)1 << 18), minPos);
         if (want > m->pos_cap) { m->pos_cap = want; m->hdrClean = false; }
     }
     // pos buffer: record 0 is the header (positive counter), records 1.. are the positives, so that the
@@ -2128,6 +2136,19 @@ int fd_wvm_eval_batch(fd_ctx* ctx, const fd_wvm* wvm_, const uint8_t* patches, i
 
 #include "five_stage.hpp"
 
+// the cascade's window table in list mode: `total` explicit windows {kept-layer position, lx, ly} at dlist (device memory)
+static void wvm_list_table(const fd_pyramid* p, const int32_t* dlist, int64_t total, WinTable& wt) {
+    std::memset(&wt, 0, sizeof(wt));
+    wt.n = (int32_t)p->kept.size();
+    wt.sx = wt.sy = 1;
+    wt.total = total;
+    wt.list = dlist;
+    for (size_t i = 0; i < p->kept.size(); ++i) {
+        const HostLayer& L = p->all[p->kept[i]];
+        wt.l[i].lw = L.w; wt.l[i].off = L.gray_off; wt.l[i].nx = 1; wt.l[i].ny = 1; wt.l[i].magic = 0xffffffffu; wt.l[i].first = INT64_MAX;
+    }
+}
+
 // condensation::WvmSvmModel::evaluate(image, samples) (WvmSvmModel.cpp:69-118) on top of a DirectPyramidFeatureExtractor
 // + HistEq64Filter: every sample {x, y, width, height} maps to one pyramid window (DirectPyramidFeatureExtractor::extract
 // (x, y, width, height), :67-73,134-153); all windows run through the WVM cascade in one launch (explicit window list);
@@ -2166,15 +2187,7 @@ int fd_wvm_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, 
         std::memcpy(pin, list.data(), sizeof(int32_t) * list.size());
         HIP_CHECK(hipMemcpyAsync(m->list.p, pin, sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, st));
         WinTable wt;
-        std::memset(&wt, 0, sizeof(wt));
-        wt.n = (int32_t)p->kept.size();
-        wt.sx = wt.sy = 1;
-        wt.total = nv;
-        wt.list = m->list.as<int32_t>();
-        for (size_t i = 0; i < p->kept.size(); ++i) {
-            const HostLayer& L = p->all[p->kept[i]];
-            wt.l[i].lw = L.w; wt.l[i].off = L.gray_off; wt.l[i].nx = 1; wt.l[i].ny = 1; wt.l[i].magic = 0xffffffffu; wt.l[i].first = INT64_MAX;
-        }
+        wvm_list_table(p, m->list.as<int32_t>(), nv, wt);
         WvmRun run;
         wvm_launch_table(ctx, ctx->stream, p, m, wt, true, run, false);
         fd_wvm_finish(ctx, m, run);
@@ -2213,6 +2226,51 @@ int fd_wvm_svm_evaluate_samples(fd_ctx* ctx, fd_pyramid* p, const fd_wvm* wvm_, 
         }
     });
 }
+
+}  // extern "C"
+
+// ---- the cascade for a resident particle set (condensation.hip, particle_wvm_svm.hpp) ----
+static_assert(sizeof(PosRec) == 16 && offsetof(PosRec, wid_lo) == 0 && offsetof(PosRec, fout) == 12, "FdWvmResidentRun::pos is read as uint4 {wid_lo, wid_hi, level, fout}");
+
+void fd_wvm_svm_pair_check(fd_ctx* ctx, const fd_wvm* m, const fd_svm* svm, const char* who) {
+    if (m->ctx != ctx || fd_svm_context(svm) != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: objects belong to different contexts", who);
+    five_stage_check(m, svm);
+}
+
+uint64_t fd_wvm_run_serial(const fd_wvm* m) { return m->runSerial; }
+
+void fd_wvm_resident_check(fd_ctx* ctx, const fd_pyramid* p, const fd_wvm* m, const fd_svm* svm, int n, const char* who) {
+    if (p->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: objects belong to different contexts", who);
+    fd_wvm_svm_pair_check(ctx, m, svm, who);
+    if (p->filter_kind != FD_LAYER_NONE) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: WVM evaluation needs a gray pyramid (no layer filter)", who);
+    if (p->kept.size() > (size_t)WVM_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: pyramid has %zu layers, this backend supports %d", who, p->kept.size(), WVM_MAX_LAYERS);
+    // fd_wvm_finish's overflow branch runs stage B again when more windows were queued than its state holds.  Nobody reads this run's
+    // header back, so the state must hold every window: wvb_reserve gives min(n, 2^18) >= n unless FD_WVM_DEEP_CAP fixes less.
+    if (m->wvbOk && m->dev.numUsed > WVM_LCAP && wvb_capacity(m, n, 0) < n)
+        FD_THROW(FD_ERR_DEVICE_CAPACITY, "%s: %d windows, FD_WVM_DEEP_CAP fixes stage B's state at %lld", who, n, (long long)wvb_cap_env());
+}
+
+void fd_wvm_list_launch_resident(fd_ctx* ctx, fd_pyramid* p, fd_wvm* m, const int32_t* dlist, int n, FdWvmResidentRun& out) {
+    WinTable wt;
+    wvm_list_table(p, dlist, n, wt);
+    WvmRun run;
+    WvmLaunch L;
+    if (!wvm_launch_head(ctx, ctx->stream, m, wt, true, run, false, L, n)) FD_THROW(FD_ERR_LOGIC, "fd_wvm_list_launch_resident: no windows");
+    launch_cascade<false>(ctx, ctx->stream, wt.total, m, p->arena.as<uint8_t>(), wt, L.o, false);
+    HIP_CHECK(hipGetLastError());
+    out.pos = (const uint4*)L.o.pos;
+    out.pos_count = L.o.pos_count;
+    out.patches = L.o.pos_patches;
+    out.fout = L.o.all_fout;
+    out.level = L.o.all_level;
+    out.dim = m->dev.d;
+    out.serial = m->runSerial;
+}
+
+void fd_wvm_patch_size(const fd_wvm* m, int* fw, int* fh) { *fw = m->dev.fw; *fh = m->dev.fh; }
+void fd_wvm_logistic(const fd_wvm* m, double* a, double* b) { *a = m->logisticA; *b = m->logisticB; }
+
+extern "C" {
 
 #ifdef FD_WVB_PROF
 // dev tool (tools/wvb_phases.py, -DFD_WVB_PROF builds only): the accumulated timestamps of the stage-B kernels

@@ -22,6 +22,12 @@
 //                        (filter before|after { classifierFile .. feature .. { ... } }: an RVM in front of / behind the adaptive classifier)
 //                        (in place of `measurement ehog`: a condensation::PositionDependentMeasurementModel, keys in tracking_setup.hpp; the
 //                         AdaptiveCondensationTracker initialises its model once, so startFrameCount must be 1 for it to start; its generator gets seed + 4)
+//     measurement wvmSvm { firstClassifier { classifierFile <FDWVM1 file> }  secondClassifier { classifierFile <SVM text file> threshold 0 }
+//                          patch { width 20 height 20 minWidth 80 maxWidth 480 octaveLayerCount 5 } }
+//                        (in place of `measurement ehog`: the reference's face tracker, FaceTracking.cpp:73-129 -- a CondensationTracker on
+//                         condensation::WvmSvmModel; the classifier nodes are those of ffp_detect_app.  The sampler's minSize / maxSize default to
+//                         the patch's minWidth / maxWidth.  This tracker has no initialisation: the box is not read, frame 0 is processed like
+//                         every other frame and reported as "init <found> [x y w h]", and `adapted` is always 0)
 //     validator rvm { classifierFile <FDRVM1 file> feature grayscale|h|whi { ... } sizes "0.9 1 1.1" displacements "-0.1 0 0.1" }
 //                        (optional: a ClassificationBasedStateValidator on the tracker; keys in tracking_setup.hpp)
 //   }
@@ -35,7 +41,8 @@
 // <size>" per random sample, "samples <n>" and one "s <x> <y> <size> <vx> <vy> <vsize> <weight> <score> <target> <clusterId>" per sample
 // (%.17g / %.9g: the values round-trip), so that tests/condensation_model.py can replay the run.
 // With --counts (before --dump) a last line "evaluations fused <n> loop <m>" reports, for `measurement positionDependent` on a
-// SingleClassifierModel, how many batched evaluations scored their samples in device calls and how many in the per-sample loop.
+// SingleClassifierModel, how many batched evaluations scored their samples in device calls and how many in the per-sample loop; for
+// `measurement wvmSvm` the batched evaluations (frame 0 included) and the calls of the single-sample evaluate.
 //   tracker_app --selftest <seed> <frames> <count> <randomRate>
 // runs the samplers, the transition model and the extractors without a device: a CondensationTracker on a stub measurement model that
 // weighs a sample by its distance to a moving point, on 64 x 48 frames; it dumps every frame as above, and the GridSampler's samples.
@@ -128,6 +135,39 @@ struct StubModel : public MeasurementModel {
     }
 };
 
+static void print_frame(int f, const boost::optional<cv::Rect>& found, bool adapted, ParticleFrameLoop::Route route, double ms) {
+    const cv::Rect r = found ? *found : cv::Rect();
+    std::printf("frame %d found %d %d %d %d %d adapted %d route %s ms %.3f\n", f, found ? 1 : 0, r.x, r.y, r.width, r.height, adapted ? 1 : 0,
+                route == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
+}
+
+// `measurement wvmSvm`: the face tracker's graph (FaceTracking.cpp:73-129) over the frames argv[first ..]
+static int track_wvm_svm(const ptree& pt, const shared_ptr<TransitionModel>& transitionModel, unsigned seed, bool counting, bool dumping, int first, int argc,
+                         char** argv) {
+    const tracking_setup::WvmSvmSetup setup = tracking_setup::createWvmSvm(pt.get_child("measurement"));
+    auto sampler = make_shared<ResamplingSampler>(pt.get("adaptive.resampling.particleCount", 800), pt.get("adaptive.resampling.randomRate", 0.35),
+                                                  make_shared<LowVarianceSampling>(seed), transitionModel, pt.get("adaptive.resampling.minSize", setup.minWidth),
+                                                  pt.get("adaptive.resampling.maxSize", setup.maxWidth), seed + 2);
+    CondensationTracker tracker(sampler, setup.model, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()));
+    for (int f = first; f < argc; ++f) {
+        const cv::Mat frame = read_pnm(argv[f]);
+        if (f == first) sampler->init(frame);
+        const auto t0 = std::chrono::steady_clock::now();
+        boost::optional<cv::Rect> found = tracker.process(frame);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (f == first) {
+            if (found) std::printf("init 1 %d %d %d %d\n", found->x, found->y, found->width, found->height);
+            else std::printf("init 0\n");
+            continue;
+        }
+        print_frame(f - first, found, false, tracker.getLastRoute(), ms);
+        if (auto flow = flow_model(tracker.getSampler())) print_flow(*flow);
+        if (dumping) dump(tracker.getSampler(), tracker.getSamples());
+    }
+    if (counting) std::printf("evaluations fused %d loop %d\n", setup.model->getFusedEvaluationCount(), setup.model->getLoopEvaluationCount());
+    return 0;
+}
+
 static int selftest(int argc, char** argv) {
     if (argc < 6) return 2;
     const unsigned seed = (unsigned)std::atoi(argv[2]);
@@ -193,6 +233,10 @@ int main(int argc, char** argv) {
         } else {
             throw std::invalid_argument("tracker_app: invalid transition model type: " + transition);
         }
+        const string measurement = pt.get("measurement", string("ehog"));
+        if (measurement != "ehog" && measurement != "positionDependent" && measurement != "wvmSvm")
+            throw std::invalid_argument("tracker_app: invalid measurement model type: " + measurement + " (ehog, positionDependent and wvmSvm are supported)");
+        if (measurement == "wvmSvm") return track_wvm_svm(pt, transitionModel, seed, counting, dumping, a + 5, argc, argv);
         shared_ptr<Sampler> sampler;
         if (pt.count("grid"))
             sampler = make_shared<GridSampler>(pt.get("grid.minSize", 20), pt.get("grid.maxSize", 80), (float)pt.get("grid.sizeScale", 1.2), (float)pt.get("grid.stepSize", 0.1));
@@ -201,9 +245,6 @@ int main(int argc, char** argv) {
                                                      make_shared<LowVarianceSampling>(seed), transitionModel,
                                                      pt.get("adaptive.resampling.minSize", 40), pt.get("adaptive.resampling.maxSize", 200), seed + 2);
         const ptree& mt = pt.get_child("measurement");
-        const string measurement = pt.get("measurement", string("ehog"));
-        if (measurement != "ehog" && measurement != "positionDependent")
-            throw std::invalid_argument("tracker_app: invalid measurement model type: " + measurement + " (ehog and positionDependent are supported)");
         const ptree& ct = mt.get_child("classifier");
         shared_ptr<AdaptiveMeasurementModel> adaptiveModel;
         shared_ptr<ExtendedHogBasedMeasurementModel> model;
@@ -246,9 +287,7 @@ int main(int argc, char** argv) {
             const auto t0 = std::chrono::steady_clock::now();
             boost::optional<cv::Rect> found = tracker.process(frame);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            const cv::Rect r = found ? *found : cv::Rect();
-            std::printf("frame %d found %d %d %d %d %d adapted %d route %s ms %.3f\n", f - a - 5, found ? 1 : 0, r.x, r.y, r.width, r.height,
-                        tracker.hasAdapted() ? 1 : 0, tracker.getLastRoute() == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
+            print_frame(f - a - 5, found, tracker.hasAdapted(), tracker.getLastRoute(), ms);
             if (auto flow = flow_model(tracker.getSampler())) print_flow(*flow);
             if (dumping) dump(tracker.getSampler(), tracker.getSamples());
         }

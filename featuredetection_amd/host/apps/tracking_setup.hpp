@@ -27,6 +27,9 @@
 //     feature surf { gradientCount 12 cellCount 4   scale 1 }
 //                        (the integral feature types of AdaptiveTracking.cpp:152-221: a DirectImageFeatureExtractor on the integral image,
 //                         behind an IntegralFeatureExtractor except for haar, behind a PatchResizingFeatureExtractor when scale != 1)
+//   measurement wvmSvm { firstClassifier { classifierFile .. } secondClassifier { classifierFile .. threshold .. }
+//                        patch { width 20 height 20 minWidth 80 maxWidth 480 octaveLayerCount 5 } }
+//                        (condensation::WvmSvmModel on DirectPyramidFeatureExtractor + GrayscaleFilter + HistEq64Filter: FaceTracking.cpp:75-84)
 // Not built, each an invalid_argument that names it: the feature type histeq (u8 vectors: this host layer's RvmClassifier and the
 // trainers take CV_32F) and `pyramid derived`.  A bare `filter before` / `filter after` without its block is refused with what the
 // block needs.
@@ -60,14 +63,18 @@ inline bool flag(const ptree& config, const std::string& key, bool dflt = false)
     return config.get<int>(key, dflt ? 1 : 0) != 0;
 }
 
-// createPyramidExtractor, `direct` (DirectPyramidFeatureExtractor.cpp:27-36,41-43)
+// DirectPyramidFeatureExtractor(width, height, minWidth, maxWidth, octaveLayerCount) with a GrayscaleFilter (DirectPyramidFeatureExtractor.cpp:27-36)
+inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(int width, int height, int minWidth, int maxWidth, int interval);
+// createPyramidExtractor, `direct` (DirectPyramidFeatureExtractor.cpp:41-43)
 inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(const ptree& config) {
     if (config.get_value<std::string>() == "derived")
         throw std::invalid_argument("tracking: `pyramid derived` (a pyramid on the layers of another extractor's pyramid) is not built; use `pyramid direct`");
     if (config.get_value<std::string>() != "direct")
         throw std::invalid_argument("tracking: pyramid type `" + config.get_value<std::string>() + "` is not built (only `pyramid direct`)");
-    const int width = config.get<int>("patch.width"), height = config.get<int>("patch.height");
-    const int minWidth = config.get<int>("patch.minWidth"), maxWidth = config.get<int>("patch.maxWidth"), interval = config.get<int>("interval");
+    return createPyramidExtractor(config.get<int>("patch.width"), config.get<int>("patch.height"), config.get<int>("patch.minWidth"), config.get<int>("patch.maxWidth"),
+                                  config.get<int>("interval"));
+}
+inline std::shared_ptr<DirectPyramidFeatureExtractor> createPyramidExtractor(int width, int height, int minWidth, int maxWidth, int interval) {
     const double inc = std::pow(0.5, 1. / interval);
     double minScale = static_cast<double>(width) / maxWidth, maxScale = static_cast<double>(width) / minWidth;
     const int maxLayerIndex = cv::cvRound(std::log(minScale) / std::log(inc)), minLayerIndex = cv::cvRound(std::log(maxScale) / std::log(inc));
@@ -297,6 +304,29 @@ inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned 
     s.model->setOffsetFactors(mt.get("positiveOffsetFactor", 0.05f), mt.get("negativeOffsetFactor", 0.5f));
     s.model->setSamplingProperties(mt.get("sampleNegativesAroundTarget", 0u), mt.get("sampleAdditionalNegatives", 10u), mt.get("sampleTestNegatives", 10u),
                                    flag(mt, "exploitSymmetry"));
+    return s;
+}
+
+// `measurement wvmSvm { firstClassifier { .. } secondClassifier { .. } patch { width 20 height 20 minWidth 80 maxWidth 480 octaveLayerCount 5 } }`:
+// the measurement model of the reference's face tracker (FaceTracking.cpp:75-84), the classifier nodes as ffp_detect_app and
+// condensation_eval_app load them, the patch defaults those of FaceTracking.cpp:75
+struct WvmSvmSetup {
+    std::shared_ptr<DirectPyramidFeatureExtractor> featureExtractor;
+    std::shared_ptr<condensation::WvmSvmModel> model;
+    int minWidth, maxWidth;
+};
+inline WvmSvmSetup createWvmSvm(const ptree& mt) {
+    if (!mt.count("firstClassifier") || !mt.count("secondClassifier"))
+        throw std::invalid_argument("tracking: `measurement wvmSvm` (condensation::WvmSvmModel) needs a block: measurement wvmSvm { firstClassifier { classifierFile "
+                                    "<FDWVM1 file> } secondClassifier { classifierFile <SVM text file> [threshold t] } [patch { width 20 height 20 minWidth 80 "
+                                    "maxWidth 480 octaveLayerCount 5 }] }");
+    WvmSvmSetup s;
+    s.minWidth = mt.get("patch.minWidth", 80);
+    s.maxWidth = mt.get("patch.maxWidth", 480);
+    s.featureExtractor = createPyramidExtractor(mt.get("patch.width", 20), mt.get("patch.height", 20), s.minWidth, s.maxWidth, mt.get("patch.octaveLayerCount", 5));
+    s.featureExtractor->addPatchFilter(std::make_shared<HistEq64Filter>());
+    s.model = std::make_shared<condensation::WvmSvmModel>(s.featureExtractor, ProbabilisticWvmClassifier::load(mt.get_child("firstClassifier")),
+                                                          ProbabilisticSvmClassifier::load(mt.get_child("secondClassifier")));
     return s;
 }
 

@@ -105,10 +105,23 @@ public:
     void update(std::shared_ptr<imageprocessing::VersionedImage> image) override;
     void evaluate(Sample& sample) const override;
     void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override;
+    // Not in the reference.  Whether the model has a resident evaluation right now: the extractor is a
+    // DirectPyramidFeatureExtractor with a HistEq64Filter on a gray pyramid (what evaluate(image, samples) needs), also behind at most
+    // FD_SAMPLE_MAPS_MAX PatchResizingFeatureExtractors, its pyramid holds an image, has at most 64 layers and a width -> layer table that
+    // fits FD_SAMPLE_TABLE_MAX.  About what the extractor holds now, as SingleClassifierModel::residentPlan
+    bool residentPossible() const;
+    // evaluate(image, samples) for a generation that lives in `particles`: update, fd_particles_evaluate_wvm_svm, fd_particles_weigh_wvm_svm,
+    // nothing copied back.  logic_error where residentPossible() does not hold after the update
+    void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles);
+    // calls of evaluate(image, samples) / evaluateResident, each one set of device calls for all samples, and calls of evaluate(sample)
+    int getFusedEvaluationCount() const { return fusedEvaluations; }
+    int getLoopEvaluationCount() const { return loopEvaluations; }
 private:
     std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
     std::shared_ptr<classification::ProbabilisticWvmClassifier> wvm;
     std::shared_ptr<classification::ProbabilisticSvmClassifier> svm;
+    int fusedEvaluations = 0;
+    mutable int loopEvaluations = 0;
 };
 
 // Not in the reference: how the models below score the samples of an extractor with a sampled chain (imageprocessing::SampledChain,
@@ -643,7 +656,8 @@ public:
 //    a Haar, SURF or integral HOG extractor, under SimpleTransitionModel or an OpticalFlowTransitionModel with a SimpleTransitionModel
 //    fallback and a grid of at most 1024 points;
 //  - the same SingleClassifierModel on a DirectPyramidFeatureExtractor with a histogram, extended HOG or gray-patch chain (also behind
-//    PatchResizingFeatureExtractors), under SimpleTransitionModel only.
+//    PatchResizingFeatureExtractors), under SimpleTransitionModel only;
+//  - WvmSvmModel where WvmSvmModel::residentPossible holds, under SimpleTransitionModel only.
 // These classes exactly: a subclass of any of them may override what the route restates and therefore keeps the generic route.  The
 // host draws the same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample
 // objects on demand; they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
@@ -670,8 +684,9 @@ protected:
     std::shared_ptr<StateExtractor> extractor;
 private:
     // which resident frame the configuration has, decided before the model's update(image): Ehog is ExtendedHogBasedMeasurementModel on a
-    // set bound to its tracker; Integral and Pyramid are the two families of SingleClassifierModel::residentPlan, on an unbound set
-    enum class ResidentKind { None, Ehog, Integral, Pyramid };
+    // set bound to its tracker; Integral and Pyramid are the two families of SingleClassifierModel::residentPlan, WvmSvm is WvmSvmModel,
+    // all three on an unbound set
+    enum class ResidentKind { None, Ehog, Integral, Pyramid, WvmSvm };
     ResidentKind residentKind() const;
     void deviceStep();
     void bindParticles(fd_ehog_tracker* tracker);

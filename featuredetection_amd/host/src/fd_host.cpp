@@ -2788,6 +2788,7 @@ static imageprocessing::DirectPyramidFeatureExtractor* fused_extractor(const sha
     return d;
 }
 void WvmSvmModel::evaluate(Sample& sample) const {   // WvmSvmModel.cpp:44-67 (single sample: no top-8 selection)
+    ++loopEvaluations;
     auto patch = featureExtractor->extract(sample.getX(), sample.getY(), sample.getWidth(), sample.getHeight());
     if (!patch) {
         sample.setTarget(false);
@@ -2807,6 +2808,7 @@ void WvmSvmModel::evaluate(Sample& sample) const {   // WvmSvmModel.cpp:44-67 (s
 void WvmSvmModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {   // :69-118
     update(image);
     auto* direct = fused_extractor(featureExtractor);
+    ++fusedEvaluations;
     const int n = (int)samples.size();
     if (n == 0) return;
     const vector<int32_t> xywh = pack_samples(samples);
@@ -2882,6 +2884,17 @@ static bool resident_integral(const imageprocessing::SampledChain& chain, const 
     return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && scorer.svm &&
            chain.wrappers.sampleMaps().size() <= (size_t)FD_SAMPLE_MAPS_MAX && chain.ready();
 }
+// the window list of a resident set can be resolved on this pyramid for patches of this width: it holds an image, has no more layers than
+// the window table, and its width -> layer table fits (fd_sample_layer_table)
+static bool resident_layer_table(const fd_pyramid* native, int patchWidth) {
+    const int layers = native ? fd_pyramid_layer_count(native) : 0;
+    if (layers < 1 || layers > 64) return false;
+    int first = 0, lw, lh, ch, length = 0;
+    double scale;
+    fd_pyramid_layer_info(native, 0, &first, &scale, &lw, &lh, &ch);
+    const int rc = fd_sample_layer_table(layers, first, fd_pyramid_incremental_scale(native), patchWidth, 0, nullptr, &length);
+    return (rc == FD_OK || rc == FD_ERR_CAPACITY) && length <= FD_SAMPLE_TABLE_MAX;
+}
 // fd_particles_evaluate_pyramid serves the chain: a pyramid kind with an f32 SVM behind at most FD_SAMPLE_MAPS_MAX wrappers, all of them
 // PatchResizingFeatureExtractors, on a pyramid that holds an image, has no more layers than the window table and whose width -> layer
 // table fits (fd_sample_layer_table)
@@ -2891,16 +2904,9 @@ static bool resident_pyramid(const imageprocessing::SampledChain& chain, const S
     if (maps.size() > (size_t)FD_SAMPLE_MAPS_MAX) return false;
     for (const fd_sample_map& m : maps)
         if (m.kind != FD_SAMPLE_MAP_RESIZE) return false;
-    const fd_pyramid* native = chain.pyramid->getPyramid()->native();
-    const int layers = native ? fd_pyramid_layer_count(native) : 0;
-    if (layers < 1 || layers > 64) return false;
-    int first = 0, lw, lh, ch, length = 0;
-    double scale;
-    fd_pyramid_layer_info(native, 0, &first, &scale, &lw, &lh, &ch);
     const int patchWidth = chain.kind == imageprocessing::SampledChain::Kind::Patch ? chain.patch.patch_w
                            : (chain.kind == imageprocessing::SampledChain::Kind::Ehog ? chain.ehog.patch_w : chain.hist.patch_w);
-    const int rc = fd_sample_layer_table(layers, first, fd_pyramid_incremental_scale(native), patchWidth, 0, nullptr, &length);
-    return (rc == FD_OK || rc == FD_ERR_CAPACITY) && length <= FD_SAMPLE_TABLE_MAX;
+    return resident_layer_table(chain.pyramid->getPyramid()->native(), patchWidth);
 }
 // The device maps every sample through the wrappers first (fd_particle_sample), so a pyramid chain behind wrappers resolves too
 SingleClassifierModel::ResidentPlan SingleClassifierModel::residentPlan() const {
@@ -2924,6 +2930,30 @@ void SingleClassifierModel::evaluateResident(shared_ptr<imageprocessing::Version
         check(fd_particles_evaluate_integral(context(), particles, call.integral, call.kind, call.params(), svm, Sample::getAspectRatio(), maps.data(), (int)maps.size()));
     // SvmClassifier::classify compares with the threshold the device model holds as a float (fd_samples_svm_tail does the same)
     check(fd_particles_weigh_classifier(context(), particles, a, b, (double)(float)plan.scorer.svm->getSvm()->getThreshold()));
+}
+
+// WvmSvmModel on a resident set.  The wrappers are walked here: the device maps every sample through them before the layer rule
+bool WvmSvmModel::residentPossible() const {
+    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
+    auto* direct = dynamic_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(wrappers.inner());
+    if (!direct || !direct->hasHistEq64() || wrappers.sampleMaps().size() > (size_t)FD_SAMPLE_MAPS_MAX) return false;
+    for (const fd_sample_map& m : wrappers.sampleMaps())
+        if (m.kind != FD_SAMPLE_MAP_RESIZE) return false;
+    if (direct->getPyramid()->getLayerFilterKind() != FD_LAYER_NONE || direct->getPyramid()->getSourcePyramid()) return false;
+    return resident_layer_table(direct->getPyramid()->native(), direct->getPatchWidth());
+}
+void WvmSvmModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) {
+    update(image);
+    if (!residentPossible()) throw std::logic_error("WvmSvmModel: no resident evaluation for this extractor");
+    ++fusedEvaluations;
+    const imageprocessing::ExtractorWrappers wrappers(featureExtractor.get());
+    auto* direct = static_cast<const imageprocessing::DirectPyramidFeatureExtractor*>(wrappers.inner());
+    const vector<fd_sample_map>& maps = wrappers.sampleMaps();
+    const fd_wvm* nativeWvm = wvm->getWvm()->native(wvm->getLogisticA(), wvm->getLogisticB());
+    const fd_svm* nativeSvm = svm->getSvm()->native(svm->getLogisticA(), svm->getLogisticB());
+    check(fd_particles_evaluate_wvm_svm(context(), particles, direct->getPyramid()->native(), nativeWvm, nativeSvm, Sample::getAspectRatio(), maps.data(),
+                                        (int)maps.size()));
+    check(fd_particles_weigh_wvm_svm(context(), particles, nativeWvm, nativeSvm));
 }
 
 // ---- FilteringClassifierModel (FilteringClassifierModel.cpp:27-103) --------------------------------------------------------------------
@@ -4301,6 +4331,9 @@ ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
             return ResidentKind::None;
         return ResidentKind::Ehog;
     }
+    // OpticalFlowTransitionModel with this model keeps the generic route, as the pyramid families of SingleClassifierModel do
+    if (is_exactly<WvmSvmModel>(measurementModel))
+        return simple && std::static_pointer_cast<WvmSvmModel>(measurementModel)->residentPossible() ? ResidentKind::WvmSvm : ResidentKind::None;
     const bool flow = is_exactly<OpticalFlowTransitionModel>(resampling->getTransitionModel()) &&
                       std::static_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel())->residentPossible();
     if (!simple && !flow) return ResidentKind::None;
@@ -4420,7 +4453,8 @@ void ParticleFrameLoop::deviceStep() {
     if (onTracker) {   // the model reads the state itself: its re-initialisation needs the best score in the middle
         ehog->evaluateResident(image, particles, info);
     } else {
-        resident_single_model(measurementModel)->evaluateResident(image, particles);
+        if (lastKind == ResidentKind::WvmSvm) std::static_pointer_cast<WvmSvmModel>(measurementModel)->evaluateResident(image, particles);
+        else resident_single_model(measurementModel)->evaluateResident(image, particles);
         flow.readState(particles, info);
     }
     residentCount = info.count;

@@ -1264,6 +1264,40 @@ enum { FD_SAMPLES_PATCH = 2 };   /* next to FD_SAMPLES_HIST / FD_SAMPLES_EHOG; p
 int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int kind, const void* params, const fd_svm* svm,
                                   double aspect_ratio, const fd_sample_map* maps, int n_maps);
 
+/* ---- the resident particle set on condensation::WvmSvmModel (WvmSvmModel.cpp:69-118), the measurement model of the face tracker ------
+ * A frame of this model is one chain on the context's stream: fd_pyramid_update, fd_particles_sample, _evaluate_wvm_svm, _weigh_wvm_svm,
+ * fd_particles_state; the only read-back is fd_particles_state's. */
+/* The WVM's part: sample -> maps -> window on the device as for _evaluate_pyramid (the patch is the WVM's filter size), then the exact
+ * cascade of fd_wvm_svm_evaluate_samples on the list with per-window outputs.  Waits for nothing, copies nothing back.  Leaves
+ * score[i] = (double) the WVM's output of particle i's window, the valid flags and the fd_particles_get_trace records as
+ * _evaluate_pyramid does; the positives and their equalised patches stay in the WVM handle until its next run, so nothing else may run on
+ * that handle before _weigh_wvm_svm.  Every particle keeps its own slot of the list; one without a window is scored on a window that
+ * exists and is never selected.  The positive buffer and the second cascade stage's state are reserved for all particles before the
+ * launch, whatever FD_WVM_POS_CAP says; the handle's header and its wishes for a device tail or speculative SVM scores are left as a
+ * fd_detect_wvm call with per-window outputs leaves them (nothing is read back, so what such a call learns from the header -- the
+ * windows its second stage saw, its positive count -- stays what the previous run left).
+ * FD_ERR_INVALID_ARGUMENT, before anything is queued: objects of different contexts, a multi-frame or layer-filtered pyramid, more than
+ * FD_SAMPLE_MAPS_MAX maps or a map other than FD_SAMPLE_MAP_RESIZE, an SVM that does not work on u8 vectors of the WVM's dimension, more
+ * than 64 kept layers, a width -> layer table longer than FD_SAMPLE_TABLE_MAX.  FD_ERR_DEVICE_CAPACITY when FD_WVM_DEEP_CAP fixes the
+ * second stage's state below the particle count.  FD_ERR_RUNTIME for a pyramid without an image.  A refused call launches nothing and
+ * leaves the generation "not evaluated".  An empty generation is FD_OK. */
+int fd_particles_evaluate_wvm_svm(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, const fd_wvm* wvm, const fd_svm* svm, double aspect_ratio,
+                                  const fd_sample_map* maps, int n_maps);
+/* The rest of the model, behind _evaluate_wvm_svm with the same WVM: of the WVM positives whose particle is valid, the up to 8 with the
+ * smallest (t, particle index), t = logistic_a + logistic_b * output (p_wvm = 1 / (1 + exp(t)) falls as t rises; equal t goes to the lower
+ * index, a NaN behind every number), are scored by the SVM (a fixed launch of 8 rows).  Then per particle: invalid -> target 0, weight
+ * 0, score 0; valid -> target 0, weight 0.5 * p_wvm; selected -> target = distance >= threshold, weight 2 * (0.5 * p_wvm) * p_svm.
+ * best_score, n_valid and bad_weight as fd_particles_weigh_classifier leaves them.  Waits for nothing, copies nothing back.
+ * FD_ERR_INVALID_ARGUMENT, before anything is queued, for objects of different contexts and for an SVM that does not work on u8 vectors of
+ * the WVM's dimension (this call's SVM reads the patch rows; it need not be the handle _evaluate_wvm_svm checked).  FD_ERR_RUNTIME without a
+ * preceding _evaluate_wvm_svm with this WVM on the current generation, and when anything else has run on the WVM handle since (its
+ * positives are then another run's).  A refused weighing leaves the generation evaluated and unweighed. */
+int fd_particles_weigh_wvm_svm(fd_ctx* ctx, fd_particles* p, const fd_wvm* wvm, const fd_svm* svm);
+/* for tests, not for the frame path (it waits): the selection of the last _weigh_wvm_svm.  *count of 0..8, index[8] the selected
+ * particles, most probable first, distance[8] their SVM outputs; entries from *count on are -1 and 0.  index and distance may be NULL.
+ * FD_ERR_RUNTIME unless the current generation has been evaluated and weighed by the two calls above. */
+int fd_particles_get_wvm_svm_trace(fd_ctx* ctx, fd_particles* p, int* count, int32_t* index, double* distance);
+
 /* ---- supervised descent: superviseddescent::SdmLandmarkModel / SdmLandmarkModelFitting ---------- */
 typedef struct {
     int32_t num_landmarks;      /* L */

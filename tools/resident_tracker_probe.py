@@ -23,6 +23,18 @@ SVM -- on 640 x 480 frames in HBM, at 100, 1000 and 8192 particles, as the libra
                  positionDependent`, adaptation included) on 640 x 480 PGM frames, once with FD_COND_DEVICE=0 and once with =1 per round
                  in turns; the app's own per-frame clock around tracker.process, the first 5 frames of a run left out
 
+  python tools/resident_tracker_probe.py --wvm-svm [--counts 800] [--routes generic,resident]
+                 the reference's face tracker (FaceTracking.cpp:73-129): condensation::WvmSvmModel on 20 x 20 HistEq64 patches of a
+                 pyramid with five layers per octave for widths 80 .. 480, ResamplingSampler(800, 0.35, LowVarianceSampling,
+                 SimpleTransitionModel(10, 0.1)), FilteringStateExtractor(WeightedMeanStateExtractor); a synthetic 280-filter WVM and a
+                 1024-vector RBF SVM calibrated on the frames.  generic: the pyramid's update, the sampler on the host,
+                 fd_wvm_svm_evaluate_samples (three blocking round trips), the state extraction on the host -- sampler and extraction as
+                 vectorised numpy restatements, inside the clock and also reported on their own (host_ms_*: they cost far more than the
+                 C++ classes' loops, so the generic figure is a Python baseline, not the host layer's).  resident: the pyramid's
+                 update, fd_particles_sample, _evaluate_wvm_svm, _weigh_wvm_svm, fd_particles_state.  --routes generic runs on a library
+                 without the resident calls.  With --host: tracker_app on `measurement wvmSvm` with the same models, once per route and
+                 round in turns -- the C++ sampler and state extractor on the generic route
+
 Both routes run in one process on the same build, alternating round by round.  A frame is timed by the host clock from its first
 call to the return of its last, which waits for the stream on both routes.  Reported per route and particle count: the median
 frame time over all rounds, the 10th and 90th percentile, and the spread of the per-round medians (the run-to-run noise a
@@ -232,6 +244,158 @@ def run(frames_per_round, warmup, rounds, counts=COUNTS, pyramid=None):
     return out
 
 
+WVM_SVM_PATCH, WVM_SVM_MIN, WVM_SVM_MAX, WVM_SVM_LAYERS = 20, 80, 480, 5   # DirectPyramidFeatureExtractor(20, 20, 80, 480, 5)
+
+
+def host_sample(gen, n, n_resampled, u, diffusion, fresh, first_id):
+    """ResamplingSampler::sample with LowVarianceSampling and SimpleTransitionModel on arrays (numpy; the draws are given)"""
+    cum = np.cumsum(gen["weight"])
+    step = cum[-1] / n_resampled
+    if step > 0:
+        k = np.minimum(np.searchsorted(cum, step * u + np.arange(n_resampled) * step, "left"), len(cum) - 1)
+    else:
+        k = np.arange(n_resampled) % len(cum)
+    vx = np.rint(gen["vx"][k] + diffusion[:, 0]).astype(np.int32)
+    vy = np.rint(gen["vy"][k] + diffusion[:, 1]).astype(np.int32)
+    vs = (gen["vsize"][k] * diffusion[:, 2]).astype(np.float32)
+    size = np.rint(gen["size"][k].astype(np.float32) * vs).astype(np.int32)
+    zeros = np.zeros(len(fresh), np.int32)
+    return dict(x=np.concatenate([gen["x"][k] + vx, fresh[:, 0]]), y=np.concatenate([gen["y"][k] + vy, fresh[:, 1]]), size=np.concatenate([size, fresh[:, 2]]),
+                vx=np.concatenate([vx, zeros]), vy=np.concatenate([vy, zeros]), vsize=np.concatenate([vs, np.ones(len(fresh), np.float32)]),
+                cluster=np.concatenate([gen["cluster"][k], first_id + np.arange(len(fresh), dtype=np.int32)]))
+
+
+def host_state(gen, target, weight):
+    """FilteringStateExtractor(WeightedMeanStateExtractor) on arrays (numpy): the weighted mean over the largest cluster of targets"""
+    if not target.any():
+        return None
+    ids, counts = np.unique(gen["cluster"][target], return_counts=True)
+    member = target & (gen["cluster"] == ids[np.argmax(counts)])
+    w = weight[member]
+    total = w.sum()
+    if total == 0:
+        return None
+    return tuple(int(np.dot(w, gen[k][member]) / total + 0.5) for k in ("x", "y", "size", "vx", "vy", "vsize"))
+
+
+def wvm_svm_pyramid(capi, ctx):
+    inc = 0.5 ** (1.0 / WVM_SVM_LAYERS)
+    scale_of = lambda width: inc ** round(np.log(WVM_SVM_PATCH / width) / np.log(inc))
+    return capi.Pyramid(ctx, octave_layers=WVM_SVM_LAYERS, min_scale=scale_of(WVM_SVM_MAX), max_scale=scale_of(WVM_SVM_MIN))
+
+
+def wvm_svm_models(synth, layer):
+    """the models see what the tracker's windows look like: patches of the pyramid's own first layer"""
+    rng = np.random.default_rng(1)
+    calib = synth.random_patches(layer, WVM_SVM_PATCH, WVM_SVM_PATCH, 2000, rng)
+    wvm = synth.make_wvm(3, calib_patches=calib, min_survivors=200)
+    eq = synth.histeq64_np(synth.random_patches(layer, WVM_SVM_PATCH, WVM_SVM_PATCH, 1400, rng))
+    return wvm, synth.make_svm_u8(4, eq, nsv=1024, calib=eq[1024:], positive_fraction=0.5)
+
+
+def run_wvm_svm(frames_per_round, warmup, rounds, counts, routes):
+    from featuredetection_amd import capi, synth
+    stream = torch.cuda.Stream()
+    ctx = capi.Context(0, stream=stream.cuda_stream)
+    base = textured(5)
+    cycle = 8
+    frames = [torch.from_numpy(np.roll(base, (SHIFT[1] * k, SHIFT[0] * k), axis=(0, 1)).copy()).cuda() for k in range(cycle)]
+    torch.cuda.synchronize()
+    x, y, size = TARGET
+    out = dict(size="%dx%d" % (W, H), feature="wvmSvm", frames_per_round=frames_per_round, rounds=rounds, routes={})
+    with torch.cuda.stream(stream):
+        pyr = wvm_svm_pyramid(capi, ctx)
+        pyr.update_device(frames[0].data_ptr(), W, H, 1)
+        wvm, svm = wvm_svm_models(synth, pyr.layer(0))
+        wg, sg = capi.Wvm(ctx, wvm), capi.Svm(ctx, svm)
+        out["wvm_filters"], out["svm_vectors"] = int(wvm["num_filters"]), 1024
+        for n in counts:
+            rng = np.random.default_rng(n)
+            n_resampled = int((1 - RANDOM_RATE) * n)
+
+            def draws():
+                z = rng.standard_normal((n_resampled, 3))
+                return np.stack([POSITION_DEVIATION * z[:, 0], POSITION_DEVIATION * z[:, 1], np.exp2(SIZE_DEVIATION * z[:, 2])], 1)
+
+            def fresh_samples():
+                s = rng.integers(WVM_SVM_MIN, WVM_SVM_MAX + 1, n - n_resampled)
+                return np.stack([rng.integers(0, W - s + 1) + s // 2, rng.integers(0, H - s + 1) + s // 2, s], 1).astype(np.int32)
+
+            particles = capi.Particles.unbound(ctx, n) if "resident" in routes else None
+            state = dict(turn=0, next_id=2, gen=None, weight=None, positives=0, found=0)
+            host_ms = []
+
+            def restart(route):
+                state.update(turn=0, next_id=2)
+                if route == "resident":
+                    particles.set(x=np.full(n, x), y=np.full(n, y), size=np.full(n, size), cluster_id=np.full(n, 1))
+                else:
+                    state["gen"] = dict(x=np.full(n, x, np.int32), y=np.full(n, y, np.int32), size=np.full(n, size, np.int32), vx=np.zeros(n, np.int32),
+                                        vy=np.zeros(n, np.int32), vsize=np.ones(n, np.float32), cluster=np.ones(n, np.int32), weight=np.ones(n))
+
+            def generic_frame():
+                k = state["turn"] = state["turn"] + 1
+                d, fresh, u = draws(), fresh_samples(), rng.random()
+                t0 = time.perf_counter()
+                pyr.update_device(frames[k % cycle].data_ptr(), W, H, 1)
+                ta = time.perf_counter()
+                gen = host_sample(state["gen"], n, n_resampled, u, d, fresh, state["next_id"])
+                tb = time.perf_counter()
+                target, weight = capi.wvm_svm_evaluate(ctx, pyr, wg, sg, np.stack([gen["x"], gen["y"], gen["size"], gen["size"]], 1))
+                tc = time.perf_counter()
+                found = host_state(gen, target.astype(bool), weight)
+                t1 = time.perf_counter()
+                host_ms.append(((tb - ta) + (t1 - tc)) * 1e3)   # the two numpy parts of this frame
+                gen["weight"] = weight
+                state["gen"] = gen
+                state["next_id"] += n - n_resampled
+                state["found"] += found is not None
+                return t1 - t0
+
+            def resident_frame():
+                k = state["turn"] = state["turn"] + 1
+                d, fresh, u = draws(), fresh_samples(), rng.random()
+                t0 = time.perf_counter()
+                pyr.update_device(frames[k % cycle].data_ptr(), W, H, 1)
+                particles.sample(n, n_resampled, u, d, fresh, state["next_id"])
+                particles.evaluate_wvm_svm(pyr, wg, sg, 1.0)
+                particles.weigh_wvm_svm(wg, sg)
+                info = particles.state()
+                t1 = time.perf_counter()
+                state["next_id"] += n - n_resampled
+                state["found"] += info["found"]
+                return t1 - t0
+
+            step = {"generic": generic_frame, "resident": resident_frame}
+            times = {route: [] for route in routes}
+            found = {route: 0 for route in routes}
+            for r in range(rounds):
+                for route in (routes if r % 2 == 0 else routes[::-1]):
+                    restart(route)
+                    state["found"] = 0
+                    for _ in range(warmup):
+                        step[route]()
+                    times[route].append([step[route]() * 1e3 for _ in range(frames_per_round)])
+                    found[route] += state["found"]
+            for route, per_round in times.items():
+                flat = np.concatenate(per_round)
+                medians = [float(np.median(r)) for r in per_round]
+                out["routes"].setdefault(route, {})[str(n)] = dict(ms_median=float(np.median(flat)), ms_p10=float(np.percentile(flat, 10)),
+                                                                   ms_p90=float(np.percentile(flat, 90)), round_medians_min=min(medians),
+                                                                   round_medians_max=max(medians),
+                                                                   found_fraction=found[route] / float(rounds * (warmup + frames_per_round)))
+            if host_ms:
+                out["routes"]["generic"][str(n)].update(host_ms_median=float(np.median(host_ms)), host_ms_p10=float(np.percentile(host_ms, 10)),
+                                                        host_ms_p90=float(np.percentile(host_ms, 90)))
+            if particles:
+                particles.close()
+        for h in (wg, sg, pyr):
+            h.close()
+        torch.cuda.synchronize()
+    ctx.close()
+    return out
+
+
 HOST_CONFIG = """tracking {
   seed 7
   transition %(transition)s
@@ -265,13 +429,36 @@ HOST_FEATURES = {
 }
 
 
-def run_host(frames, rounds, counts=COUNTS, pyramid=None):
+WVM_SVM_HOST_CONFIG = """tracking {
+  seed 7
+  transition simple { positionDeviation 10 sizeDeviation 0.1 }
+  adaptive { resampling { particleCount %(n)d randomRate 0.35 } }
+  measurement wvmSvm {
+    firstClassifier pwvm { classifierFile %(wvm)s }
+    secondClassifier psvm { classifierFile %(svm)s threshold %(threshold)s }
+  }
+}
+"""
+
+
+def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False):
     import subprocess
     import tempfile
     app = os.path.join(ROOT, "featuredetection_amd", "tracker_app")
-    out = dict(size="%dx%d" % (W, H), feature=pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
+    out = dict(size="%dx%d" % (W, H), feature="wvmSvm" if wvm_svm else pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
     with tempfile.TemporaryDirectory() as tmp:
         base = textured(5)
+        if wvm_svm:   # the models of run_wvm_svm, in the files the app loads
+            from featuredetection_amd import capi, synth
+            ctx = capi.Context(0)
+            pyr = wvm_svm_pyramid(capi, ctx)
+            pyr.update(base)
+            wvm, svm = wvm_svm_models(synth, pyr.layer(0))
+            pyr.close()
+            ctx.close()
+            models = dict(wvm=os.path.join(tmp, "face.fdwvm"), svm=os.path.join(tmp, "face.svm.txt"), threshold=repr(float(svm["threshold"])))
+            synth.save_wvm(models["wvm"], wvm)
+            synth.save_svm_text(models["svm"], svm, rows=WVM_SVM_PATCH, cols=WVM_SVM_PATCH)
         paths = []
         for k in range(frames + 1):
             path = os.path.join(tmp, "frame%d.pgm" % k)
@@ -283,7 +470,10 @@ def run_host(frames, rounds, counts=COUNTS, pyramid=None):
         for n in counts:
             cfg = os.path.join(tmp, "tracking%d.cfg" % n)
             with open(cfg, "w") as f:
-                f.write(HOST_CONFIG % dict(n=n, feature=HOST_FEATURES[pyramid], transition=HOST_TRANSITIONS[pyramid is not None]))
+                if wvm_svm:
+                    f.write(WVM_SVM_HOST_CONFIG % dict(models, n=n))
+                else:
+                    f.write(HOST_CONFIG % dict(n=n, feature=HOST_FEATURES[pyramid], transition=HOST_TRANSITIONS[pyramid is not None]))
             times = {"generic": [], "device": []}
             for r in range(rounds):
                 for route in (("generic", "device") if r % 2 == 0 else ("device", "generic")):
@@ -311,10 +501,19 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--pyramid", choices=("hog", "ehog", "glbp", "whi"), default=None)
-    ap.add_argument("--counts", default=",".join(str(c) for c in COUNTS), help="particle counts, comma separated")
+    ap.add_argument("--wvm-svm", action="store_true", help="the face tracker's frame (WvmSvmModel); counts default to 800")
+    ap.add_argument("--routes", default="generic,resident", help="with --wvm-svm: the routes to run, comma separated")
+    ap.add_argument("--counts", default=None, help="particle counts, comma separated")
     a = ap.parse_args()
-    counts = tuple(int(c) for c in a.counts.split(","))
+    counts = tuple(int(c) for c in a.counts.split(",")) if a.counts else ((800,) if a.wvm_svm else COUNTS)
     if not torch.cuda.is_available():
         sys.exit("resident_tracker_probe: no GPU; a frame time cannot be measured without one")
+    if a.wvm_svm and a.host:
+        print(json.dumps(run_host(a.frames, a.rounds, counts, wvm_svm=True)))
+        sys.exit(0)
+    if a.wvm_svm:
+        print(json.dumps(run_wvm_svm(a.frames, a.warmup, a.rounds, counts, tuple(a.routes.split(",")))))
+        torch.cuda.synchronize()
+        sys.exit(0)
     print(json.dumps(run_host(a.frames, a.rounds, counts, a.pyramid) if a.host else run(a.frames, a.warmup, a.rounds, counts, a.pyramid)))
     torch.cuda.synchronize()
