@@ -147,6 +147,14 @@ class fd_particles_info(C.Structure):
                 ("bad_weight", C.c_int32), ("best_score", C.c_double), ("weight_sum", C.c_double)]
 
 
+class fd_particles_negatives_params(C.Structure):
+    _fields_ = [("max_count", C.c_int32), ("offset_factor", C.c_float), ("down_scale", C.c_float), ("up_scale", C.c_float)]
+
+
+class fd_particles_negative(C.Structure):
+    _fields_ = [("index", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("size", C.c_int32), ("weight", C.c_double)]
+
+
 class fd_flow_params(C.Structure):
     _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double),
                 ("min_eig_threshold", C.c_double)]
@@ -440,6 +448,9 @@ _SIGS = {
                                        C.POINTER(fd_flow_motion_info)]),
     "fd_particles_sample_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "fd_particles_state_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_particles_info), C.POINTER(fd_flow_motion_info)]),
+    "fd_particles_negatives_bounds": (C.c_int, [C.POINTER(fd_particles_negatives_params), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "fd_particles_state_negatives": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_particles_negatives_params), C.POINTER(fd_particles_info),
+                                               C.POINTER(fd_flow_motion_info), C.POINTER(C.c_int), C.POINTER(fd_particles_negative)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1603,6 +1614,45 @@ class Particles:
         info, motion = fd_particles_info(), fd_flow_motion_info()
         out = self._state(lib().fd_particles_state_flow(self.ctx.h, self.h, flow.h, C.byref(info), C.byref(motion)), info)
         return out, _motion_dict(motion)
+
+    def state_negatives(self, params, flow=None):
+        """fd_particles_state_negatives: (info as state() gives it, the flow handle's motion as a dict or None without a flow, the chosen
+        negatives as a dict of arrays index, x, y, size (int32) and weight (float64) in the list order of
+        PositionDependentMeasurementModel::adapt) in one read-back; params from negatives_params().  FdError carries .info."""
+        info, motion, count = fd_particles_info(), fd_flow_motion_info(), C.c_int()
+        records = (fd_particles_negative * FD_PARTICLES_NEGATIVES_MAX)()
+        rc = lib().fd_particles_state_negatives(self.ctx.h, self.h, flow.h if flow is not None else None, C.byref(params), C.byref(info),
+                                                C.byref(motion) if flow is not None else None, C.byref(count), records)
+        try:
+            out = self._state(rc, info)
+        except FdError as e:
+            e.count = count.value
+            raise
+        chosen = {name: np.array([getattr(records[k], name) for k in range(count.value)], np.float64 if name == "weight" else np.int32)
+                  for name, _ in fd_particles_negative._fields_}
+        return out, (_motion_dict(motion) if flow is not None else None), chosen
+
+
+FD_PARTICLES_NEGATIVES_MAX = 64
+
+
+def negatives_params(max_count, offset_factor):
+    """fd_particles_negatives_params as the host layer forms them from sampleAdditionalNegatives and negativeOffsetFactor: down_scale =
+    1 - offset_factor and up_scale = 1 / down_scale in float"""
+    with np.errstate(divide="ignore"):
+        f = np.float32(offset_factor)
+        down = np.float32(1) - f
+        up = np.float32(1) / down
+    return fd_particles_negatives_params(int(max_count), float(f), float(down), float(up))
+
+
+def particles_negatives_bounds(params, x, y, size):
+    """fd_particles_negatives_bounds (host only): int32 (6,) {xLow, xHigh, yLow, yHigh, sizeLow, sizeHigh} of the state {x, y, size}"""
+    bounds = np.zeros(6, np.int32)
+    rc = lib().fd_particles_negatives_bounds(C.byref(params), int(x), int(y), int(size), _ptr(bounds))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_particles_negatives_bounds")
+    return bounds
 
 
 FD_SAMPLE_MAP_RESIZE, FD_SAMPLE_MAP_INTEGRAL, FD_SAMPLE_MAPS_MAX = 0, 1, 4

@@ -7,12 +7,14 @@
 // OpticalFlowTransitionModel::predict (k_particles_sample with the motion optflow.hip leaves on the device), and SingleClassifierModel
 // on the pyramid families: fd_particles_evaluate_pyramid resolves the samples to windows here (particle_windows.hpp) and hands the list to
 // the scoring kernels of hog.hip / rvm.hip.  condensation::WvmSvmModel takes the same window list through wvm.hip's cascade
-// (fd_particles_evaluate_wvm_svm); its selection rule and its weighting are particle_wvm_svm.hpp.  DESIGN.md 4.7.
+// (fd_particles_evaluate_wvm_svm); its selection rule and its weighting are particle_wvm_svm.hpp.  The additional negatives of
+// PositionDependentMeasurementModel::adapt are chosen behind the state (fd_particles_state_negatives, particle_negatives.hpp).  DESIGN.md 4.7.
 //
 // Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
 // needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
 // against them, so another association would select other samples); they are walked by single lanes in LDS, everything around them
-// is parallel.  All loops are counted; nothing waits on another workgroup.
+// is parallel.  k_particles_negatives (particle_negatives.hpp) is a fourth of this shape: its selection needs every weight.  All loops are
+// counted; nothing waits on another workgroup.
 #include "fd_internal.hpp"
 #include "particle_windows.hpp"
 #include <algorithm>
@@ -24,7 +26,7 @@
 
 namespace {
 
-constexpr int PT = 256;                        // threads of the three kernels
+constexpr int PT = 256;                        // threads of the single-workgroup kernels
 constexpr int32_t PARTICLE_NO_CLUSTER = INT32_MIN;   // the empty key of the cluster table
 constexpr int PARTICLES_CLASSIFIER = 3;        // k_particles_weigh as SingleClassifierModel: behind the FD_PARTICLES_* modes of fd_particles_weigh
 
@@ -168,6 +170,7 @@ __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, co
 }  // namespace
 
 #include "particle_wvm_svm.hpp"
+#include "particle_negatives.hpp"
 
 namespace {
 
@@ -282,7 +285,8 @@ struct fd_particles {
     int capacity = 0, n = 0, cur = 0;
     bool sumKnown = true, bad = false, evaluated = false;
     double sum = 0.0;   // the weights of the current generation added in index order, when sumKnown
-    DevBuf arena, staging, dinfo;
+    DevBuf arena, staging;
+    DevBuf dinfo;   // a ParticleReadBack: the fd_particles_info every kernel writes, and behind it what k_particles_negatives leaves
     DevBuf list;   // fd_particles_evaluate_pyramid: the window {layer, bx, by} of every sample, slot i for sample i
     ParticleGen gen[2];
     int32_t* source = nullptr;
@@ -310,18 +314,35 @@ fd_particles* particles_checked(fd_ctx* ctx, fd_particles* p, const char* what) 
     return p;
 }
 
-// state kernel + the read-back of the info; refreshes what the host knows about the generation
+// state kernel + the read-back of the info; refreshes what the host knows about the generation.  With `negatives` the selection is
+// queued behind the state kernel and comes back in the same copy: *count records into `records`
 void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out, const fd_flow_motion_info* dmotion = nullptr,
-                          fd_flow_motion_info* motion = nullptr) {
-    static uint64_t allowed = 0;
+                          fd_flow_motion_info* motion = nullptr, const fd_particles_negatives_params* negatives = nullptr, int* count = nullptr,
+                          fd_particles_negative* records = nullptr) {
+    static uint64_t allowed = 0, allowedNegatives = 0;
     const int slots = particle_state_slots(p->n);
     const size_t lds = sizeof(int32_t) * 2 * (size_t)slots;
     fd_allow_lds(ctx, (const void*)k_particles_state, (int)(sizeof(int32_t) * 2 * (size_t)particle_state_slots(FD_PARTICLES_MAX)), allowed);
     hipLaunchKernelGGL(k_particles_state, dim3(1), dim3(PT), lds, ctx->stream, p->gen[p->cur], p->n, slots, p->dinfo.as<fd_particles_info>());
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, p->dinfo.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+    ParticleReadBack back;
+    if (negatives) {
+        fd_allow_lds(ctx, (const void*)k_particles_negatives, (int)(sizeof(unsigned long long) * FD_PARTICLES_MAX), allowedNegatives);
+        hipLaunchKernelGGL(k_particles_negatives, dim3(1), dim3(PT), sizeof(unsigned long long) * (size_t)p->n, ctx->stream, p->gen[p->cur], p->n, *negatives,
+                           p->dinfo.as<fd_particles_info>(), &p->dinfo.as<ParticleReadBack>()->negatives);
+        HIP_CHECK(hipGetLastError());
+        const size_t bytes = offsetof(ParticleReadBack, negatives.rec) + sizeof(fd_particles_negative) * (size_t)negatives->max_count;
+        HIP_CHECK(hipMemcpyAsync(&back, p->dinfo.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        HIP_CHECK(hipMemcpyAsync(out, p->dinfo.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (dmotion) HIP_CHECK(hipMemcpyAsync(motion, dmotion, sizeof(*motion), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (negatives) {
+        *out = back.info;
+        *count = std::min(std::max(back.negatives.count, 0), negatives->max_count);
+        std::memcpy(records, back.negatives.rec, sizeof(fd_particles_negative) * (size_t)*count);
+    }
     p->sum = out->weight_sum;
     p->sumKnown = true;
     p->bad = out->bad_weight != 0;
@@ -353,7 +374,7 @@ void particles_create(fd_ctx* ctx, fd_ehog_tracker* t, int capacity, fd_particle
     p->valid = (uint8_t*)(base + 2 * perGen + 20 * N);
     p->staging.reserve(60 * N);   // two blocks of draws (24 N each) and the fresh samples (12 N)
     p->pinned.reserve(60 * N);
-    p->dinfo.reserve(sizeof(fd_particles_info));
+    p->dinfo.reserve(sizeof(ParticleReadBack));
     fd_particles_info zero;
     std::memset(&zero, 0, sizeof(zero));
     zero.best_score = -DBL_MAX;
@@ -705,6 +726,23 @@ int fd_particles_state_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_part
         if (!flow || !info || !motion) FD_THROW(FD_ERR_INVALID_ARGUMENT, "fd_particles_state_flow: NULL argument");
         particles_read_state(ctx, p, info, fd_flow_device_motion(ctx, flow, "fd_particles_state_flow"), motion);
         if (info->bad_weight) FD_THROW(FD_ERR_RUNTIME, "fd_particles_state_flow: the generation holds a weight that is negative or not finite");
+    });
+}
+
+int fd_particles_state_negatives(fd_ctx* ctx, fd_particles* p, fd_flow* flow, const fd_particles_negatives_params* params, fd_particles_info* info,
+                                 fd_flow_motion_info* motion, int* count, fd_particles_negative* out) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_state_negatives";
+        if (count) *count = 0;
+        if (!params || !info || !count || !out || (flow != nullptr) != (motion != nullptr)) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+        if (params->max_count < 1 || params->max_count > FD_PARTICLES_NEGATIVES_MAX)
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: max_count %d, it must be 1 .. %d", who, params->max_count, FD_PARTICLES_NEGATIVES_MAX);
+        if (!std::isfinite(params->offset_factor) || !std::isfinite(params->down_scale) || !std::isfinite(params->up_scale))
+            FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the bounds (offset_factor %g, down_scale %g, up_scale %g) must be finite", who, (double)params->offset_factor,
+                     (double)params->down_scale, (double)params->up_scale);
+        particles_checked(ctx, p, who);
+        particles_read_state(ctx, p, info, flow ? fd_flow_device_motion(ctx, flow, who) : nullptr, motion, params, count, out);
+        if (info->bad_weight) FD_THROW(FD_ERR_RUNTIME, "%s: the generation holds a weight that is negative or not finite", who);
     });
 }
 

@@ -722,6 +722,29 @@ __host__ __device__ inline void fd_particle_sample(int32_t px, int32_t py, int32
 }
 FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who);
 void fd_particles_set_evaluated(fd_particles* p);
+// ---- the box of PositionDependentMeasurementModel::adapt's additional negatives (PositionDependentMeasurementModel.cpp:155-170): the one
+// copy of these expressions for the host (fd_particles_negatives_bounds, hostalgo.cpp) and the device (k_particles_negatives) ----
+// (int) of a float: truncated; saturated where the cast would not be defined, 0 for a NaN (what the device's conversion does by itself)
+__host__ __device__ inline int32_t fd_float_to_int(float v) {
+    if (!(v == v)) return 0;
+    if (v >= 2147483648.f) return INT32_MAX;
+    if (v <= -2147483648.f) return INT32_MIN;
+    return (int32_t)v;
+}
+struct FdNegativeBounds { int32_t xLow, xHigh, yLow, yHigh, sizeLow, sizeHigh; };
+// float * int is a float product; the sums wrap (the reference's overflow there)
+__host__ __device__ inline FdNegativeBounds fd_negative_bounds(float offsetFactor, float downScale, float upScale, int32_t x, int32_t y, int32_t size) {
+    const uint32_t offset = (uint32_t)fd_float_to_int(offsetFactor * (float)size);
+    FdNegativeBounds b;
+    b.xLow = (int32_t)((uint32_t)x - offset); b.xHigh = (int32_t)((uint32_t)x + offset);
+    b.yLow = (int32_t)((uint32_t)y - offset); b.yHigh = (int32_t)((uint32_t)y + offset);
+    b.sizeLow = fd_float_to_int(downScale * (float)size);
+    b.sizeHigh = fd_float_to_int(upScale * (float)size);
+    return b;
+}
+__host__ __device__ inline bool fd_negative_outside(const FdNegativeBounds& b, int32_t x, int32_t y, int32_t size) {
+    return x <= b.xLow || x >= b.xHigh || y <= b.yLow || y >= b.yHigh || size <= b.sizeLow || size >= b.sizeHigh;
+}
 // ---- resident particle set on the pyramid families (condensation.hip launches k_particles_windows; the scoring kernels are hog.hip's and rvm.hip's) ----
 // "Score this device list of n windows {layer, bx, by} of p into this device score array": the kernels of fd_hist_svm_evaluate_samples
 // (kind FD_SAMPLES_HIST / FD_SAMPLES_EHOG, hog.hip) and of fd_patch_svm_evaluate_samples (rvm.hip) and the SVM launch, queued on

@@ -543,6 +543,14 @@ extern "C" int fd_sample_maps_apply(const fd_sample_map* maps, int n_maps, int n
     return FD_OK;
 }
 
+// ---- the box of the additional negatives on the host: fd_negative_bounds, the function k_particles_negatives itself calls ----
+extern "C" int fd_particles_negatives_bounds(const fd_particles_negatives_params* params, int32_t x, int32_t y, int32_t size, int32_t bounds[6]) {
+    if (!params || !bounds) return FD_ERR_INVALID_ARGUMENT;
+    const FdNegativeBounds b = fd_negative_bounds(params->offset_factor, params->down_scale, params->up_scale, x, y, size);
+    bounds[0] = b.xLow; bounds[1] = b.xHigh; bounds[2] = b.yLow; bounds[3] = b.yHigh; bounds[4] = b.sizeLow; bounds[5] = b.sizeHigh;
+    return FD_OK;
+}
+
 // ---- part (a) of the sample -> window rule as a table for the device (k_particles_windows): fd_sample_layer_position, the function
 // fd_sample_window itself calls, evaluated once per width ----
 extern "C" int fd_sample_layer_table(int n_layers, int first_index, double incremental_scale, int patch_w, int cap, int16_t* layer_of_width, int* length) {

@@ -2,7 +2,7 @@
 // a condensation::AdaptiveCondensationTracker on ResamplingSampler(LowVarianceSampling, SimpleTransitionModel or OpticalFlowTransitionModel)
 // or GridSampler, an
 // ExtendedHogBasedMeasurementModel and FilteringStateExtractor(WeightedMeanStateExtractor).
-//   usage: tracker_app [--counts] [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
+//   usage: tracker_app [--counts] [--adaptation] [--dump] <config.cfg> <x> <y> <width> <height> <frame0.ppm|pgm> [<frame1> ...]
 // config (boost info format), the `tracking` block of algorithm.cfg:
 //   tracking {
 //     transition simple { positionDeviation 10  sizeDeviation 0.1 }
@@ -43,6 +43,11 @@
 // With --counts (before --dump) a last line "evaluations fused <n> loop <m>" reports, for `measurement positionDependent` on a
 // SingleClassifierModel, how many batched evaluations scored their samples in device calls and how many in the per-sample loop; for
 // `measurement wvmSvm` the batched evaluations (frame 0 included) and the calls of the single-sample evaluate.
+// With --adaptation (behind --counts, before --dump; `measurement ehog` and `positionDependent`) every frame line is followed by
+// "adaptation <0|1> materialized <0|1>": whether the model adapted, and whether process() left the generation as Sample objects (always
+// on the generic route; on the device route only where a validator or the model's adapt had to read them -- the line is printed before
+// --dump asks for the samples).  For an adapted frame of `measurement positionDependent` the record of the adaptation follows:
+// "positives <n>", "negatives <n>" and "testNegatives <n>", each followed by its samples as "ap|an|at <x> <y> <size>".
 //   tracker_app --selftest <seed> <frames> <count> <randomRate>
 // runs the samplers, the transition model and the extractors without a device: a CondensationTracker on a stub measurement model that
 // weighs a sample by its distance to a moving point, on 64 x 48 frames; it dumps every frame as above, and the GridSampler's samples.
@@ -141,6 +146,20 @@ static void print_frame(int f, const boost::optional<cv::Rect>& found, bool adap
                 route == ParticleFrameLoop::Route::DEVICE ? "device" : "generic", ms);
 }
 
+// --adaptation: what the frame's adapt did, and for PositionDependentMeasurementModel the samples it chose
+static void print_adaptation(bool adapted, bool materialized, const PositionDependentMeasurementModel* dependent) {
+    std::printf("adaptation %d materialized %d\n", adapted ? 1 : 0, materialized ? 1 : 0);
+    if (!adapted || !dependent) return;
+    const PositionDependentMeasurementModel::AdaptationRecord& r = dependent->getLastAdaptation();
+    auto list = [](const char* name, const char* tag, const std::vector<cv::Rect>& rects) {
+        std::printf("%s %zu\n", name, rects.size());
+        for (const cv::Rect& s : rects) std::printf("%s %d %d %d\n", tag, s.x, s.y, s.width);
+    };
+    list("positives", "ap", r.positives);
+    list("negatives", "an", r.negatives);
+    list("testNegatives", "at", r.testNegatives);
+}
+
 // `measurement wvmSvm`: the face tracker's graph (FaceTracking.cpp:73-129) over the frames argv[first ..]
 static int track_wvm_svm(const ptree& pt, const shared_ptr<TransitionModel>& transitionModel, unsigned seed, bool counting, bool dumping, int first, int argc,
                          char** argv) {
@@ -204,10 +223,13 @@ int main(int argc, char** argv) {
     try {
         if (argc > 1 && string(argv[1]) == "--selftest") return selftest(argc, argv);
         const bool counting = argc > 1 && string(argv[1]) == "--counts";
-        const bool dumping = argc > (counting ? 2 : 1) && string(argv[counting ? 2 : 1]) == "--dump";
-        const int a = 1 + (counting ? 1 : 0) + (dumping ? 1 : 0);
+        const int afterCounts = counting ? 2 : 1;
+        const bool adaptation = argc > afterCounts && string(argv[afterCounts]) == "--adaptation";
+        const int afterAdaptation = afterCounts + (adaptation ? 1 : 0);
+        const bool dumping = argc > afterAdaptation && string(argv[afterAdaptation]) == "--dump";
+        const int a = afterAdaptation + (dumping ? 1 : 0);
         if (argc < a + 6) {
-            std::fprintf(stderr, "usage: %s [--counts] [--dump] <config.cfg> <x> <y> <width> <height> <frame0> [<frame1> ...]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [--counts] [--adaptation] [--dump] <config.cfg> <x> <y> <width> <height> <frame0> [<frame1> ...]\n", argv[0]);
             return 2;
         }
         ptree all;
@@ -287,7 +309,9 @@ int main(int argc, char** argv) {
             const auto t0 = std::chrono::steady_clock::now();
             boost::optional<cv::Rect> found = tracker.process(frame);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            const bool materialized = tracker.samplesMaterialized();   // before anything below asks for the samples
             print_frame(f - a - 5, found, tracker.hasAdapted(), tracker.getLastRoute(), ms);
+            if (adaptation) print_adaptation(tracker.hasAdapted(), materialized, std::dynamic_pointer_cast<PositionDependentMeasurementModel>(adaptiveModel).get());
             if (auto flow = flow_model(tracker.getSampler())) print_flow(*flow);
             if (dumping) dump(tracker.getSampler(), tracker.getSamples());
         }

@@ -18,6 +18,7 @@
 //     filter none   startFrameCount 3  stopFrameCount 0  targetThreshold 0.7  confidenceThreshold 0.95  positiveOffsetFactor 0.05
 //     negativeOffsetFactor 0.5  sampleNegativesAroundTarget 0  sampleAdditionalNegatives 10  sampleTestNegatives 10  exploitSymmetry 0
 //     classifier { training { type libSvm|libLinear c 1 ... }  logisticA 0.00556  logisticB -2.95  threshold 0 }
+//     subclass 0         (1, with `filter none`: a subclass of the model that overrides nothing, for the tests of the device route)
 //   }
 //   validator rvm { classifierFile <FDRVM1 file>  [numFiltersToUse n]  feature grayscale|h|whi { ... }  sizes "0.9 1 1.1"  displacements "-0.1 0 0.1" }
 //                        (beside `measurement`, in the `tracking` block: a condensation::ClassificationBasedStateValidator on the adaptive tracker)
@@ -284,6 +285,11 @@ inline bool filterBehavior(const ptree& mt, condensation::FilteringClassifierMod
     behavior = filter == "before" ? condensation::FilteringClassifierModel::Behavior::RESET_WEIGHT : condensation::FilteringClassifierModel::Behavior::KEEP_WEIGHT;
     return true;
 }
+// a subclass that changes nothing (`subclass 1`, not one of the reference's keys): the device route restates the class itself and must
+// leave any subclass to the generic route
+struct SubclassedPositionDependentModel : public condensation::PositionDependentMeasurementModel {
+    using condensation::PositionDependentMeasurementModel::PositionDependentMeasurementModel;
+};
 inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned int seed) {
     PositionDependentSetup s;
     condensation::FilteringClassifierModel::Behavior behavior;
@@ -296,6 +302,8 @@ inline PositionDependentSetup createPositionDependent(const ptree& mt, unsigned 
         s.filter = createRvm(mt.get_child("filter"));
         s.filteringModel = std::make_shared<condensation::FilteringClassifierModel>(s.filterExtractor, s.filter, s.featureExtractor, s.classifier, behavior);
         s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.filteringModel, s.featureExtractor, s.classifier, seed);
+    } else if (mt.get("subclass", 0) != 0) {
+        s.model = std::make_shared<SubclassedPositionDependentModel>(s.featureExtractor, s.classifier, seed);
     } else {
         s.model = std::make_shared<condensation::PositionDependentMeasurementModel>(s.featureExtractor, s.classifier, seed);
     }

@@ -292,7 +292,27 @@ public:
     const AdaptationRecord& getLastAdaptation() const { return lastAdaptation; }
     size_t getAdaptationCount() const { return adaptationCount; }
     std::shared_ptr<MeasurementModel> getMeasurementModel() const { return measurementModel; }
+    // not in the reference: adapt(image, samples, target) in its two parts, for a generation that lives on the device.
+    // The samples are read for one thing, the sampleAdditionalNegatives samples with the largest weights outside the box around the
+    // target (:172-192): chooseAdditionalNegatives makes that choice on the host, fd_particles_state_negatives on the device.
+    // adaptResident is adapt with the choice already made (`chosen` in the list's order, at most sampleAdditionalNegatives samples);
+    // adapt itself is adaptResident(image, target, chooseAdditionalNegatives(samples, target)), so both routes draw the same random
+    // samples and pass the same examples on in the same order.
+    std::vector<Sample> chooseAdditionalNegatives(const std::vector<std::shared_ptr<Sample>>& samples, const Sample& target) const;
+    bool adaptResident(std::shared_ptr<imageprocessing::VersionedImage> image, const Sample& target, const std::vector<Sample>& chosen);
+    // what fd_particles_state_negatives needs for this model's choice: {sampleAdditionalNegatives, negativeOffsetFactor, 1 - factor,
+    // 1 / (1 - factor)}, the floats as adapt forms them.  False where the device is not asked: sampleAdditionalNegatives is 0 (nothing is
+    // read from the samples) or above FD_PARTICLES_NEGATIVES_MAX, or a bound is not finite.
+    bool residentNegatives(fd_particles_negatives_params& params) const;
 private:
+    // the box around the target: {xLow, xHigh, yLow, yHigh, sizeLow, sizeHigh} (fd_particles_negatives_bounds)
+    struct NegativeBounds {
+        int32_t v[6];
+        bool outside(const Sample& s) const {
+            return s.getX() <= v[0] || s.getX() >= v[1] || s.getY() <= v[2] || s.getY() >= v[3] || s.getSize() <= v[4] || s.getSize() >= v[5];
+        }
+    };
+    NegativeBounds negativeBounds(const Sample& target) const;
     int draw(int n);   // distribution(generator, n)
     Sample createRandomSample(const cv::Mat& image);
     bool hasWindow(int x, int y, int width, int height) const;
@@ -661,13 +681,25 @@ public:
 // These classes exactly: a subclass of any of them may override what the route restates and therefore keeps the generic route.  The
 // host draws the same random numbers in the same order and reads one fd_particles_info back.  getSamples() then builds the Sample
 // objects on demand; they carry no ancestors.  Every other configuration takes the generic route over vector<shared_ptr<Sample>>.
+// A model that is exactly PositionDependentMeasurementModel gets the samples its adapt reads chosen on the device in that one read-back
+// (PositionDependentMeasurementModel::residentNegatives), so its frames do not build the Sample objects at all; a validator that is
+// exactly ClassificationBasedStateValidator (it ignores its samples) does not make them either.
 class ParticleFrameLoop {
 public:
     enum class Route { NONE, GENERIC, DEVICE };
     Route getLastRoute() const { return lastRoute; }
+    // the current generation exists as Sample objects: always on the generic route; on the device route once something has asked for
+    // them (getSamples(), a validator or a model that reads samples)
+    bool samplesMaterialized() const { return materialized; }
 protected:
     // the last frame left its samples on the device and neither the model's isValid nor its adapt reads them
     bool samplesUnread() const { return lastRoute == Route::DEVICE && lastKind == ResidentKind::Ehog; }
+    // the last frame left its samples on the device and brought back, with the state, what PositionDependentMeasurementModel::adapt reads
+    // of them (fd_particles_state_negatives): chosenNegatives() is the argument of adaptResident
+    bool negativesChosen() const { return lastRoute == Route::DEVICE && residentChose; }
+    const std::vector<Sample>& chosenNegatives() const { return residentChosen; }
+    // the generation lives on the device alone (a validator that does not read its samples argument need not get it)
+    bool samplesOnDeviceOnly() const { return resident && !materialized; }
     ParticleFrameLoop(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
     ~ParticleFrameLoop();
     ParticleFrameLoop(const ParticleFrameLoop&) = delete;
@@ -698,6 +730,8 @@ private:
     mutable bool materialized = true;         // `samples` holds it as well
     int residentCount = 0;
     double residentWeightSum = 0;
+    bool residentChose = false;               // the last device frame read its state through fd_particles_state_negatives
+    std::vector<Sample> residentChosen;       // what it chose, in the list order of adapt
     Route lastRoute = Route::NONE;
     ResidentKind lastKind = ResidentKind::None;
 };

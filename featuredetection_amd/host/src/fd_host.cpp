@@ -3185,7 +3185,44 @@ vector<Mat> PositionDependentMeasurementModel::getFeatureVectors(const vector<Sa
     }
     return trainingExamples;
 }
+bool PositionDependentMeasurementModel::residentNegatives(fd_particles_negatives_params& params) const {
+    const float downScaleBound = (1 - negativeOffsetFactor);
+    const float upScaleBound = 1 / downScaleBound;
+    params = fd_particles_negatives_params{(int32_t)std::min(sampleAdditionalNegatives, (unsigned int)INT32_MAX), negativeOffsetFactor, downScaleBound, upScaleBound};
+    return sampleAdditionalNegatives >= 1 && sampleAdditionalNegatives <= FD_PARTICLES_NEGATIVES_MAX && std::isfinite(negativeOffsetFactor) &&
+           std::isfinite(downScaleBound) && std::isfinite(upScaleBound);
+}
+PositionDependentMeasurementModel::NegativeBounds PositionDependentMeasurementModel::negativeBounds(const Sample& target) const {
+    fd_particles_negatives_params params;
+    residentNegatives(params);   // the floats, whatever they are
+    NegativeBounds bounds;
+    check(fd_particles_negatives_bounds(&params, target.getX(), target.getY(), target.getSize(), bounds.v));
+    return bounds;
+}
+// :172-192: the list is ascending by weight; a new element goes before equal ones
+vector<Sample> PositionDependentMeasurementModel::chooseAdditionalNegatives(const vector<shared_ptr<Sample>>& samples, const Sample& target) const {
+    vector<Sample> additionalNegatives;
+    if (sampleAdditionalNegatives == 0) return additionalNegatives;
+    const NegativeBounds bounds = negativeBounds(target);
+    additionalNegatives.reserve(sampleAdditionalNegatives);
+    for (const shared_ptr<Sample>& sample : samples) {
+        if (!bounds.outside(*sample)) continue;
+        if (additionalNegatives.size() < sampleAdditionalNegatives) {
+            auto low = std::lower_bound(additionalNegatives.begin(), additionalNegatives.end(), *sample,
+                                        [](const Sample& a, const Sample& b) { return a.getWeight() < b.getWeight(); });
+            additionalNegatives.insert(low, *sample);
+        } else if (additionalNegatives.front().getWeight() < sample->getWeight()) {
+            additionalNegatives.front() = *sample;
+            for (unsigned int i = 1; i < additionalNegatives.size() && additionalNegatives[i - 1].getWeight() > additionalNegatives[i].getWeight(); ++i)
+                std::swap(additionalNegatives[i - 1], additionalNegatives[i]);
+        }
+    }
+    return additionalNegatives;
+}
 bool PositionDependentMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage> image, const vector<shared_ptr<Sample>>& samples, const Sample& target) {
+    return adaptResident(image, target, chooseAdditionalNegatives(samples, target));
+}
+bool PositionDependentMeasurementModel::adaptResident(shared_ptr<imageprocessing::VersionedImage> image, const Sample& target, const vector<Sample>& chosen) {
     if (!isUsable()) {
         frameCount++;
         if (frameCount < startFrameCount) return false;
@@ -3210,15 +3247,9 @@ bool PositionDependentMeasurementModel::adapt(shared_ptr<imageprocessing::Versio
     }
 
     vector<Sample> negativeSamples;
-    int boundOffset = (int)(negativeOffsetFactor * target.getSize());
-    int xLowBound = target.getX() - boundOffset;
-    int xHighBound = target.getX() + boundOffset;
-    int yLowBound = target.getY() - boundOffset;
-    int yHighBound = target.getY() + boundOffset;
-    float downScaleBound = (1 - negativeOffsetFactor);
-    float upScaleBound = 1 / downScaleBound;
-    int sizeLowBound = (int)(downScaleBound * target.getSize());
-    int sizeHighBound = (int)(upScaleBound * target.getSize());
+    const NegativeBounds bounds = negativeBounds(target);
+    const int xLowBound = bounds.v[0], xHighBound = bounds.v[1], yLowBound = bounds.v[2], yHighBound = bounds.v[3];
+    const int sizeLowBound = bounds.v[4], sizeHighBound = bounds.v[5];
     const int tx = target.getX(), ty = target.getY(), ts = target.getSize();
     if (sampleNegativesAroundTarget > 0) {
         negativeSamples.push_back(Sample(xLowBound, ty, ts));
@@ -3252,25 +3283,10 @@ bool PositionDependentMeasurementModel::adapt(shared_ptr<imageprocessing::Versio
             }
         }
     }
-    auto outside = [&](const Sample& s) {
-        return s.getX() <= xLowBound || s.getX() >= xHighBound || s.getY() <= yLowBound || s.getY() >= yHighBound || s.getSize() <= sizeLowBound ||
-               s.getSize() >= sizeHighBound;
-    };
+    auto outside = [&](const Sample& s) { return bounds.outside(s); };
     if (sampleAdditionalNegatives > 0) {
-        vector<Sample> additionalNegatives;
+        vector<Sample> additionalNegatives = chosen;
         additionalNegatives.reserve(sampleAdditionalNegatives);
-        for (const shared_ptr<Sample>& sample : samples) {
-            if (!outside(*sample)) continue;
-            if (additionalNegatives.size() < sampleAdditionalNegatives) {
-                auto low = std::lower_bound(additionalNegatives.begin(), additionalNegatives.end(), *sample,
-                                            [](const Sample& a, const Sample& b) { return a.getWeight() < b.getWeight(); });
-                additionalNegatives.insert(low, *sample);
-            } else if (additionalNegatives.front().getWeight() < sample->getWeight()) {
-                additionalNegatives.front() = *sample;
-                for (unsigned int i = 1; i < additionalNegatives.size() && additionalNegatives[i - 1].getWeight() > additionalNegatives[i].getWeight(); ++i)
-                    std::swap(additionalNegatives[i - 1], additionalNegatives[i]);
-            }
-        }
         while (additionalNegatives.size() < sampleAdditionalNegatives) {
             Sample sample = createRandomSample(image->getData());
             if (outside(sample) && hasWindow(sample.getX(), sample.getY(), sample.getSize(), sample.getSize())) additionalNegatives.push_back(sample);
@@ -4418,13 +4434,16 @@ struct ResidentFlow {
             check(fd_particles_sample(context(), particles, copies + fresh, copies, draws.u, draws.diffusion.data(), draws.fresh.data(), firstFreshId));
         }
     }
-    void readState(fd_particles* particles, fd_particles_info& info) {
-        if (!tracked) {
-            check(fd_particles_state(context(), particles, &info));
-            return;
-        }
+    // negatives: the state through fd_particles_state_negatives, *count records into `records` (room for max_count)
+    void readState(fd_particles* particles, fd_particles_info& info, const fd_particles_negatives_params* negatives = nullptr, int* count = nullptr,
+                   fd_particles_negative* records = nullptr) {
         fd_flow_motion_info motion;
-        check(fd_particles_state_flow(context(), particles, flow->native(), &info, &motion));
+        if (negatives)
+            check(fd_particles_state_negatives(context(), particles, tracked ? flow->native() : nullptr, negatives, &info, tracked ? &motion : nullptr, count,
+                                               records));
+        else if (tracked) check(fd_particles_state_flow(context(), particles, flow->native(), &info, &motion));
+        else check(fd_particles_state(context(), particles, &info));
+        if (!tracked) return;
         flow->endResident(motion);
         if (motion.ok) fallback->restoreDrawState(before);   // the flow predicted: the fallback drew nothing
     }
@@ -4450,12 +4469,30 @@ void ParticleFrameLoop::deviceStep() {
     Sample::nextClusterId += fresh;   // the ids the random samples of the generic route would have drawn, in order
     flow.sample(particles, draws, copies, fresh, firstFreshId);
     fd_particles_info info;
+    residentChose = false;
+    residentChosen.clear();
     if (onTracker) {   // the model reads the state itself: its re-initialisation needs the best score in the middle
         ehog->evaluateResident(image, particles, info);
     } else {
         if (lastKind == ResidentKind::WvmSvm) std::static_pointer_cast<WvmSvmModel>(measurementModel)->evaluateResident(image, particles);
         else resident_single_model(measurementModel)->evaluateResident(image, particles);
-        flow.readState(particles, info);
+        // exactly that model: its adapt reads of the samples what the device chooses behind the state (a subclass never gets here)
+        fd_particles_negatives_params negatives;
+        residentChose = is_exactly<PositionDependentMeasurementModel>(measurementModel) &&
+                        std::static_pointer_cast<PositionDependentMeasurementModel>(measurementModel)->residentNegatives(negatives);
+        if (residentChose) {
+            fd_particles_negative records[FD_PARTICLES_NEGATIVES_MAX];
+            int count = 0;
+            flow.readState(particles, info, &negatives, &count, records);
+            const int nextId = Sample::nextClusterId;
+            for (int k = 0; k < count; ++k) {
+                residentChosen.emplace_back(records[k].x, records[k].y, records[k].size);
+                residentChosen.back().setWeight(records[k].weight);
+            }
+            Sample::nextClusterId = nextId;   // building the objects draws no cluster ids
+        } else {
+            flow.readState(particles, info);
+        }
     }
     residentCount = info.count;
     residentWeightSum = info.weight_sum;
@@ -4520,23 +4557,30 @@ boost::optional<cv::Rect> AdaptiveCondensationTracker::initialize(const Mat& ima
 boost::optional<cv::Rect> AdaptiveCondensationTracker::process(const Mat& imageData) {   // .cpp:67-95
     if (!adaptiveModel->isUsable()) throw std::runtime_error("AdaptiveCondensationTracker: Is not usable (was not initialized or was resetted)");
     step(imageData);
-    // validate target state; the measurement model looks at the state alone, any other validator gets the samples
+    // validate target state; the measurement model looks at the state alone and ClassificationBasedStateValidator ignores its samples
+    // argument, any other validator gets the samples
     if (state) {
         for (shared_ptr<StateValidator>& validator : validators) {
             const bool isModel = std::dynamic_pointer_cast<StateValidator>(measurementModel) == validator;
             static const vector<shared_ptr<Sample>> none;
-            const bool onDevice = samplesUnread() && isModel;
+            const bool onDevice = (samplesUnread() && isModel) || (samplesOnDeviceOnly() && is_exactly<ClassificationBasedStateValidator>(validator));
             if (!validator->isValid(*state, onDevice ? none : currentSamples(), image)) {
                 state.reset();
                 break;
             }
         }
     }
-    // update model: ExtendedHogBasedMeasurementModel::adapt does not read the samples
+    // update model: ExtendedHogBasedMeasurementModel::adapt does not read the samples; PositionDependentMeasurementModel::adapt reads
+    // what the device frame has brought back with the state, and nothing without a state
     static const vector<shared_ptr<Sample>> unread;
-    const vector<shared_ptr<Sample>>& forAdapt = samplesUnread() ? unread : currentSamples();
-    if (state) adapted = adaptiveModel->adapt(image, forAdapt, *state);
-    else adapted = adaptiveModel->adapt(image, forAdapt);
+    if (negativesChosen()) {
+        if (state) adapted = std::static_pointer_cast<PositionDependentMeasurementModel>(measurementModel)->adaptResident(image, *state, chosenNegatives());
+        else adapted = adaptiveModel->adapt(image, unread);
+    } else {
+        const vector<shared_ptr<Sample>>& forAdapt = samplesUnread() ? unread : currentSamples();
+        if (state) adapted = adaptiveModel->adapt(image, forAdapt, *state);
+        else adapted = adaptiveModel->adapt(image, forAdapt);
+    }
     if (state) return boost::optional<cv::Rect>(state->getBounds());
     return boost::optional<cv::Rect>();
 }

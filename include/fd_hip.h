@@ -1158,6 +1158,38 @@ int fd_particles_sample_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, int co
 /* fd_particles_state that brings the flow handle's motion back in the same wait: the one read-back of such a frame */
 int fd_particles_state_flow(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_particles_info* info, fd_flow_motion_info* motion);
 
+/* ---- the additional negatives of condensation::PositionDependentMeasurementModel::adapt (PositionDependentMeasurementModel.cpp:172-192),
+ * chosen on the device behind the state: of the samples outside a box around the extracted state the max_count with
+ * the largest weights.  The reference walks the samples in index order and keeps a list ascending by weight that puts a new element
+ * before equal ones; in closed form the result is the max_count samples largest under (weight descending, index ascending), listed
+ * by (weight ascending, index descending).  Every sample of the generation is a candidate, those without a window (weight 0) too.
+ * A sample {x, y, size} is outside when x <= xLow || x >= xHigh || y <= yLow || y >= yHigh || size <= sizeLow || size >= sizeHigh
+ * with, for the state {X, Y, S}: offset = (int)(offset_factor * S) in float, xLow = X - offset, xHigh = X + offset, the same for y,
+ * sizeLow = (int)(down_scale * S), sizeHigh = (int)(up_scale * S).  The caller forms down_scale = 1 - offset_factor and up_scale =
+ * 1 / down_scale as floats; the float -> int conversions truncate and saturate, the int sums wrap. */
+#define FD_PARTICLES_NEGATIVES_MAX 64
+typedef struct {
+    int32_t max_count;                 /* 1 .. FD_PARTICLES_NEGATIVES_MAX: sampleAdditionalNegatives */
+    float offset_factor;               /* negativeOffsetFactor */
+    float down_scale, up_scale;
+} fd_particles_negatives_params;
+typedef struct {
+    int32_t index;                     /* of the sample in the generation */
+    int32_t x, y, size;
+    double weight;
+} fd_particles_negative;
+/* host only, no context: the six bounds {xLow, xHigh, yLow, yHigh, sizeLow, sizeHigh} of a state by the expressions above, the one copy
+ * the kernel uses as well.  Defined for every float (the host layer's generic route calls it whatever its factor is: a product that
+ * is infinite saturates, a NaN gives 0); max_count is not read.  FD_ERR_INVALID_ARGUMENT for NULL. */
+int fd_particles_negatives_bounds(const fd_particles_negatives_params* params, int32_t x, int32_t y, int32_t size, int32_t bounds[6]);
+/* fd_particles_state (flow NULL, motion NULL) or fd_particles_state_flow with the selection queued behind the state kernel: *info and
+ * *motion as those calls report them, *count <= max_count records in out[0 .. *count) (room for max_count), all in the one wait.
+ * Without a state, and with bad_weight (FD_ERR_RUNTIME, *info filled), *count is 0.  FD_ERR_INVALID_ARGUMENT before anything is queued
+ * for max_count outside 1 .. FD_PARTICLES_NEGATIVES_MAX, floats of params that are not finite, NULL arguments (motion must be NULL
+ * exactly when flow is) and objects of different contexts. */
+int fd_particles_state_negatives(fd_ctx* ctx, fd_particles* p, fd_flow* flow, const fd_particles_negatives_params* params, fd_particles_info* info,
+                                 fd_flow_motion_info* motion, int* count, fd_particles_negative* out);
+
 /* ---- classification::RvmClassifier / ProbabilisticRvmClassifier -----------------
  * Cascaded reduced-vector machine (RvmClassifier.cpp:75-126): level k evaluates kernel(x, rsv_k) on the whole
  * vector; through the reference's cached path the running distance is d_0 = -bias + c[0][0] K_0,

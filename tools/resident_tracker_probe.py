@@ -21,7 +21,9 @@ SVM -- on 640 x 480 frames in HBM, at 100, 1000 and 8192 particles, as the libra
   python tools/resident_tracker_probe.py --host [--frames 40] [--rounds 3]
                  the same configuration through the host classes: tracker_app (AdaptiveCondensationTracker, `measurement
                  positionDependent`, adaptation included) on 640 x 480 PGM frames, once with FD_COND_DEVICE=0 and once with =1 per round
-                 in turns; the app's own per-frame clock around tracker.process, the first 5 frames of a run left out
+                 in turns; the app's own per-frame clock around tracker.process, the first 5 frames of a run left out.  --app PATH
+                 runs another build's tracker_app (beside its own libraries) in place of this tree's, to compare two builds in one
+                 session
 
   python tools/resident_tracker_probe.py --wvm-svm [--counts 800] [--routes generic,resident]
                  the reference's face tracker (FaceTracking.cpp:73-129): condensation::WvmSvmModel on 20 x 20 HistEq64 patches of a
@@ -441,11 +443,11 @@ WVM_SVM_HOST_CONFIG = """tracking {
 """
 
 
-def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False):
+def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False, app=None):
     import subprocess
     import tempfile
-    app = os.path.join(ROOT, "featuredetection_amd", "tracker_app")
-    out = dict(size="%dx%d" % (W, H), feature="wvmSvm" if wvm_svm else pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
+    app = app or os.path.join(ROOT, "featuredetection_amd", "tracker_app")
+    out = dict(app=os.path.relpath(app, ROOT), size="%dx%d" % (W, H), feature="wvmSvm" if wvm_svm else pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
     with tempfile.TemporaryDirectory() as tmp:
         base = textured(5)
         if wvm_svm:   # the models of run_wvm_svm, in the files the app loads
@@ -504,16 +506,17 @@ if __name__ == "__main__":
     ap.add_argument("--wvm-svm", action="store_true", help="the face tracker's frame (WvmSvmModel); counts default to 800")
     ap.add_argument("--routes", default="generic,resident", help="with --wvm-svm: the routes to run, comma separated")
     ap.add_argument("--counts", default=None, help="particle counts, comma separated")
+    ap.add_argument("--app", default=None, help="with --host: the tracker_app to run (default: this tree's)")
     a = ap.parse_args()
     counts = tuple(int(c) for c in a.counts.split(",")) if a.counts else ((800,) if a.wvm_svm else COUNTS)
     if not torch.cuda.is_available():
         sys.exit("resident_tracker_probe: no GPU; a frame time cannot be measured without one")
     if a.wvm_svm and a.host:
-        print(json.dumps(run_host(a.frames, a.rounds, counts, wvm_svm=True)))
+        print(json.dumps(run_host(a.frames, a.rounds, counts, wvm_svm=True, app=a.app)))
         sys.exit(0)
     if a.wvm_svm:
         print(json.dumps(run_wvm_svm(a.frames, a.warmup, a.rounds, counts, tuple(a.routes.split(",")))))
         torch.cuda.synchronize()
         sys.exit(0)
-    print(json.dumps(run_host(a.frames, a.rounds, counts, a.pyramid) if a.host else run(a.frames, a.warmup, a.rounds, counts, a.pyramid)))
+    print(json.dumps(run_host(a.frames, a.rounds, counts, a.pyramid, app=a.app) if a.host else run(a.frames, a.warmup, a.rounds, counts, a.pyramid)))
     torch.cuda.synchronize()
