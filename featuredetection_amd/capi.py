@@ -155,6 +155,14 @@ class fd_particles_negative(C.Structure):
     _fields_ = [("index", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("size", C.c_int32), ("weight", C.c_double)]
 
 
+class fd_particles_examples_params(C.Structure):
+    _fields_ = [("positive_threshold", C.c_double), ("negative_threshold", C.c_double), ("max_count", C.c_int32), ("require_window", C.c_int32)]
+
+
+class fd_particles_example(C.Structure):
+    _fields_ = [("index", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("size", C.c_int32), ("valid", C.c_int32), ("weight", C.c_double)]
+
+
 class fd_flow_params(C.Structure):
     _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("max_level", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double),
                 ("min_eig_threshold", C.c_double)]
@@ -451,6 +459,17 @@ _SIGS = {
     "fd_particles_negatives_bounds": (C.c_int, [C.POINTER(fd_particles_negatives_params), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "fd_particles_state_negatives": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fd_particles_negatives_params), C.POINTER(fd_particles_info),
                                                C.POINTER(fd_flow_motion_info), C.POINTER(C.c_int), C.POINTER(fd_particles_negative)]),
+    "fd_particles_examples_select": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fd_particles_examples_params), C.POINTER(C.c_int), C.c_void_p,
+                                               C.POINTER(C.c_int), C.c_void_p]),
+    "fd_particles_examples_bounds": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fd_particles_state_examples_pyramid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int,
+                                                      C.POINTER(fd_particles_examples_params), C.POINTER(fd_particles_info), C.POINTER(fd_flow_motion_info),
+                                                      C.POINTER(C.c_int), C.POINTER(fd_particles_example), C.POINTER(C.c_int),
+                                                      C.POINTER(fd_particles_example), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fd_particles_state_examples_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int,
+                                                       C.POINTER(fd_particles_examples_params), C.POINTER(fd_particles_info), C.POINTER(fd_flow_motion_info),
+                                                       C.POINTER(C.c_int), C.POINTER(fd_particles_example), C.POINTER(C.c_int),
+                                                       C.POINTER(fd_particles_example), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "fd_aggregated_create": (C.c_int, [C.c_void_p, C.POINTER(fd_aggregated_params), C.POINTER(C.c_void_p)]),
     "fd_aggregated_destroy": (None, [C.c_void_p]),
     "fd_aggregated_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1631,6 +1650,87 @@ class Particles:
         chosen = {name: np.array([getattr(records[k], name) for k in range(count.value)], np.float64 if name == "weight" else np.int32)
                   for name, _ in fd_particles_negative._fields_}
         return out, (_motion_dict(motion) if flow is not None else None), chosen
+
+    def state_examples(self, params, source, aspect_ratio, maps=(), haar=None, surf=None, hog=None, hist=None, ehog=None, patch=None, flow=None,
+                       row_capacity=None, channels=1):
+        """fd_particles_state_examples_integral (source an updated Integral; haar / surf / hog as evaluate_integral takes them) or
+        fd_particles_state_examples_pyramid (source an updated Pyramid; hist / ehog / patch as evaluate_pyramid takes them): (info as
+        state() gives it, the flow handle's motion as a dict or None without a flow, the positive examples, the negative examples, rows)
+        in one read-back.  params from examples_params(); maps the adaptive extractor's chain.  Each list is a dict of arrays index, x, y,
+        size, valid (int32) and weight (float64) in SelfLearningMeasurementModel::adapt's order; rows is float32 (n_pos + n_neg, row
+        length), the positives' rows first, zero where the record is not valid.  row_capacity (floats) defaults to what
+        particles_examples_bounds reports for `channels`, the channel count of the pyramid's bin image (hist / ehog only: 2 with bin
+        interpolation).  FdError carries .info and .counts."""
+        family, kind, prm, _keep = _examples_kind(haar, surf, hog, hist, ehog, patch)
+        chain = sample_maps(maps)
+        info, motion, n_pos, n_neg, row_length = fd_particles_info(), fd_flow_motion_info(), C.c_int(), C.c_int(), C.c_int()
+        pos, neg = (fd_particles_example * FD_PARTICLES_EXAMPLES_MAX)(), (fd_particles_example * FD_PARTICLES_EXAMPLES_MAX)()
+        if row_capacity is None:
+            row_capacity = 0
+            length, capacity = C.c_int(), C.c_int()
+            if lib().fd_particles_examples_bounds(family, kind, prm, int(channels), params.max_count, C.byref(length), C.byref(capacity)) == FD_OK:
+                row_capacity = capacity.value   # otherwise the call itself refuses the parameters, with its message
+        rows = np.zeros(max(int(row_capacity), 1), np.float32)
+        call = lib().fd_particles_state_examples_integral if family == FD_EXAMPLES_INTEGRAL else lib().fd_particles_state_examples_pyramid
+        rc = call(self.ctx.h, self.h, flow.h if flow is not None else None, source.h, kind, prm, aspect_ratio, chain, len(chain), C.byref(params),
+                  C.byref(info), C.byref(motion) if flow is not None else None, C.byref(n_pos), pos, C.byref(n_neg), neg, _ptr(rows), int(row_capacity),
+                  C.byref(row_length))
+        try:
+            out = self._state(rc, info)
+        except FdError as e:
+            e.counts = (n_pos.value, n_neg.value)
+            raise
+
+        def records(rec, count):
+            return {name: np.array([getattr(rec[k], name) for k in range(count)], np.float64 if name == "weight" else np.int32)
+                    for name, _ in fd_particles_example._fields_}
+        total = n_pos.value + n_neg.value
+        return (out, (_motion_dict(motion) if flow is not None else None), records(pos, n_pos.value), records(neg, n_neg.value),
+                rows[:total * row_length.value].reshape(total, row_length.value).copy())
+
+
+FD_PARTICLES_EXAMPLES_MAX = 32
+
+
+def examples_params(positive_threshold, negative_threshold, max_count=10, require_window=False):
+    """fd_particles_examples_params: SelfLearningMeasurementModel's thresholds, its 10 examples per side, and whether a candidate needs
+    the valid flag of the generation's evaluate (the usable branch) or not (the bootstrap branch)"""
+    return fd_particles_examples_params(float(positive_threshold), float(negative_threshold), int(max_count), int(require_window))
+
+
+def particles_examples_select(weight, params, valid=None):
+    """fd_particles_examples_select (host only): (positive indices, negative indices), int32, in list order"""
+    weight = _c(np.asarray(weight, np.float64), np.float64)
+    valid = None if valid is None else _c(np.asarray(valid, np.uint8), np.uint8)
+    n_pos, n_neg = C.c_int(), C.c_int()
+    pos, neg = np.zeros(FD_PARTICLES_EXAMPLES_MAX, np.int32), np.zeros(FD_PARTICLES_EXAMPLES_MAX, np.int32)
+    rc = lib().fd_particles_examples_select(len(weight), _ptr(weight), _ptr(valid), C.byref(params), C.byref(n_pos), _ptr(pos), C.byref(n_neg), _ptr(neg))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_particles_examples_select")
+    return pos[:n_pos.value].copy(), neg[:n_neg.value].copy()
+
+
+FD_EXAMPLES_INTEGRAL, FD_EXAMPLES_PYRAMID = 0, 1
+
+
+def _examples_kind(haar=None, surf=None, hog=None, hist=None, ehog=None, patch=None):
+    """(family, kind, pointer to the parameters, the object the pointer needs alive) of exactly one feature extractor"""
+    pyramid = [(kind, prm) for kind, prm in ((FD_SAMPLES_HIST, hist), (FD_SAMPLES_EHOG, ehog), (FD_SAMPLES_PATCH, patch)) if prm is not None]
+    if pyramid:
+        if len(pyramid) != 1 or haar is not None or surf is not None or hog is not None:
+            raise ValueError("exactly one of haar, surf, hog, hist, ehog and patch")
+        return FD_EXAMPLES_PYRAMID, pyramid[0][0], C.byref(pyramid[0][1]), pyramid[0][1]
+    return (FD_EXAMPLES_INTEGRAL,) + _integral_kind(haar, surf, hog)
+
+
+def particles_examples_bounds(max_count, channels=1, **extractor):
+    """fd_particles_examples_bounds (host only): (row length, row capacity) in floats; the extractor as state_examples takes it"""
+    family, kind, prm, _keep = _examples_kind(**extractor)
+    length, capacity = C.c_int(), C.c_int()
+    rc = lib().fd_particles_examples_bounds(family, kind, prm, int(channels), int(max_count), C.byref(length), C.byref(capacity))
+    if rc != FD_OK:
+        raise FdError(rc, "fd_particles_examples_bounds")
+    return length.value, capacity.value
 
 
 FD_PARTICLES_NEGATIVES_MAX = 64

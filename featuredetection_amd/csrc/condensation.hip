@@ -8,12 +8,13 @@
 // on the pyramid families: fd_particles_evaluate_pyramid resolves the samples to windows here (particle_windows.hpp) and hands the list to
 // the scoring kernels of hog.hip / rvm.hip.  condensation::WvmSvmModel takes the same window list through wvm.hip's cascade
 // (fd_particles_evaluate_wvm_svm); its selection rule and its weighting are particle_wvm_svm.hpp.  The additional negatives of
-// PositionDependentMeasurementModel::adapt are chosen behind the state (fd_particles_state_negatives, particle_negatives.hpp).  DESIGN.md 4.7.
+// PositionDependentMeasurementModel::adapt are chosen behind the state (fd_particles_state_negatives, particle_negatives.hpp), and so are
+// the examples of SelfLearningMeasurementModel::adapt, with their feature rows (fd_particles_state_examples_*, particle_examples.hpp).  DESIGN.md 4.7.
 //
 // Kernels: k_particles_sample, k_particles_weigh, k_particles_state -- one workgroup of 256 threads each, because every one of them
 // needs the whole set: the cumulative weights and the state sums are sequential double sums in index order (the resampler compares
 // against them, so another association would select other samples); they are walked by single lanes in LDS, everything around them
-// is parallel.  k_particles_negatives (particle_negatives.hpp) is a fourth of this shape: its selection needs every weight.  All loops are
+// is parallel.  k_particles_negatives (particle_negatives.hpp) is a fourth of this shape: its selection needs every weight; k_particles_examples (particle_examples.hpp) a fifth.  All loops are
 // counted; nothing waits on another workgroup.
 #include "fd_internal.hpp"
 #include "particle_windows.hpp"
@@ -171,6 +172,7 @@ __global__ __launch_bounds__(PT) void k_particles_weigh(ParticleGen g, int n, co
 
 #include "particle_wvm_svm.hpp"
 #include "particle_negatives.hpp"
+#include "particle_examples.hpp"
 
 namespace {
 
@@ -287,6 +289,9 @@ struct fd_particles {
     double sum = 0.0;   // the weights of the current generation added in index order, when sumKnown
     DevBuf arena, staging;
     DevBuf dinfo;   // a ParticleReadBack: the fd_particles_info every kernel writes, and behind it what k_particles_negatives leaves
+    DevBuf examples;   // fd_particles_state_examples_*: a ParticleExamplesHead and the feature rows behind it, the frame's one read-back
+    std::vector<unsigned char> examplesHost;
+    DevBuf exampleList;   // fd_particles_state_examples_pyramid: the window {layer, bx, by} of every slot
     DevBuf list;   // fd_particles_evaluate_pyramid: the window {layer, bx, by} of every sample, slot i for sample i
     ParticleGen gen[2];
     int32_t* source = nullptr;
@@ -314,17 +319,23 @@ fd_particles* particles_checked(fd_ctx* ctx, fd_particles* p, const char* what) 
     return p;
 }
 
-// state kernel + the read-back of the info; refreshes what the host knows about the generation.  With `negatives` the selection is
-// queued behind the state kernel and comes back in the same copy: *count records into `records`
-void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out, const fd_flow_motion_info* dmotion = nullptr,
-                          fd_flow_motion_info* motion = nullptr, const fd_particles_negatives_params* negatives = nullptr, int* count = nullptr,
-                          fd_particles_negative* records = nullptr) {
-    static uint64_t allowed = 0, allowedNegatives = 0;
+// the state kernel on the current generation, into p->dinfo
+void particles_queue_state(fd_ctx* ctx, fd_particles* p) {
+    static uint64_t allowed = 0;
     const int slots = particle_state_slots(p->n);
     const size_t lds = sizeof(int32_t) * 2 * (size_t)slots;
     fd_allow_lds(ctx, (const void*)k_particles_state, (int)(sizeof(int32_t) * 2 * (size_t)particle_state_slots(FD_PARTICLES_MAX)), allowed);
     hipLaunchKernelGGL(k_particles_state, dim3(1), dim3(PT), lds, ctx->stream, p->gen[p->cur], p->n, slots, p->dinfo.as<fd_particles_info>());
     HIP_CHECK(hipGetLastError());
+}
+
+// state kernel + the read-back of the info; refreshes what the host knows about the generation.  With `negatives` the selection is
+// queued behind the state kernel and comes back in the same copy: *count records into `records`
+void particles_read_state(fd_ctx* ctx, fd_particles* p, fd_particles_info* out, const fd_flow_motion_info* dmotion = nullptr,
+                          fd_flow_motion_info* motion = nullptr, const fd_particles_negatives_params* negatives = nullptr, int* count = nullptr,
+                          fd_particles_negative* records = nullptr) {
+    static uint64_t allowedNegatives = 0;
+    particles_queue_state(ctx, p);
     ParticleReadBack back;
     if (negatives) {
         fd_allow_lds(ctx, (const void*)k_particles_negatives, (int)(sizeof(unsigned long long) * FD_PARTICLES_MAX), allowedNegatives);
@@ -434,19 +445,26 @@ void particles_sample(fd_ctx* ctx, fd_particles* p, const char* who, fd_flow* fl
     p->notEvaluated();
 }
 
-// k_particles_windows for the current generation (n > 0) and patches of pw x ph: fills p->list, the trace and the valid flags.  False:
-// no kept layer holds a window at all, every sample is invalid and the list must not be scored.
-bool particles_windows(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int pw, int ph, double aspect_ratio, const FdSampleMaps& chain) {
-    const ParticleGen& G = p->gen[p->cur];
+// the kept layers of pyr as the window kernels take them; spare: the first kept layer that holds a pw x ph window at all (layer -1: none)
+ParticleLayers particle_layers(const fd_pyramid* pyr, int pw, int ph, FdSampleWindow& spare) {
     ParticleLayers layers;
     std::memset(&layers, 0, sizeof(layers));
     layers.n = (int32_t)pyr->kept.size();
-    FdSampleWindow spare{-1, 0, 0};   // the first kept layer that holds a window at all
+    spare = FdSampleWindow{-1, 0, 0};
     for (int l = 0; l < layers.n; ++l) {
         const HostLayer& L = pyr->all[pyr->kept[l]];
         layers.l[l].scale = L.scale; layers.l[l].w = L.w; layers.l[l].h = L.h;
         if (spare.layer < 0 && L.w >= pw && L.h >= ph) spare.layer = l;
     }
+    return layers;
+}
+
+// k_particles_windows for the current generation (n > 0) and patches of pw x ph: fills p->list, the trace and the valid flags.  False:
+// no kept layer holds a window at all, every sample is invalid and the list must not be scored.
+bool particles_windows(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int pw, int ph, double aspect_ratio, const FdSampleMaps& chain) {
+    const ParticleGen& G = p->gen[p->cur];
+    FdSampleWindow spare;
+    const ParticleLayers layers = particle_layers(pyr, pw, ph, spare);
     p->list.reserve(sizeof(int32_t) * 3 * (size_t)p->capacity);
     hipLaunchKernelGGL(k_particles_windows, dim3((p->n + 255) / 256), dim3(256), 0, ctx->stream, G.x, G.y, G.size, p->n, aspect_ratio, chain, layers,
                        pyr->sample_table.dev.as<int16_t>(), pyr->sample_table.length, pw, ph, spare, p->list.as<int32_t>(), (int4*)p->windows, p->valid);
@@ -755,3 +773,114 @@ FdParticlesView fd_particles_view(fd_ctx* ctx, fd_particles* p, const char* who)
 }
 
 void fd_particles_set_evaluated(fd_particles* p) { p->evaluatedBy(nullptr); }
+
+// ---- fd_particles_state_examples_*: the halves around the family's feature kernel (fd_internal.hpp) ----
+void fd_particles_examples_check(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, const char* who) {
+    if (a.n_pos) *a.n_pos = 0;
+    if (a.n_neg) *a.n_neg = 0;
+    if (!a.params || !a.info || !a.n_pos || !a.pos || !a.n_neg || !a.neg || !a.rows || (a.flow != nullptr) != (a.motion != nullptr))
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+    const fd_particles_examples_params& prm = *a.params;
+    if (prm.max_count < 1 || prm.max_count > FD_PARTICLES_EXAMPLES_MAX)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: max_count %d, it must be 1 .. %d", who, prm.max_count, FD_PARTICLES_EXAMPLES_MAX);
+    if (!std::isfinite(prm.positive_threshold) || !std::isfinite(prm.negative_threshold))
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: the thresholds (positive %g, negative %g) must be finite", who, prm.positive_threshold, prm.negative_threshold);
+    if (prm.negative_threshold > prm.positive_threshold)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: negative_threshold %g lies above positive_threshold %g", who, prm.negative_threshold, prm.positive_threshold);
+    if (prm.require_window != 0 && prm.require_window != 1) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: require_window %d, it must be 0 or 1", who, prm.require_window);
+    particles_checked(ctx, p, who);
+}
+
+FdExamplesRun fd_particles_examples_begin(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, int rowLength, const char* who) {
+    static uint64_t allowed = 0;
+    const fd_particles_examples_params& prm = *a.params;
+    const long long need = 2LL * prm.max_count * rowLength;
+    if (a.row_length) *a.row_length = rowLength;
+    if (a.row_capacity < 0 || (long long)a.row_capacity < need)
+        FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: row_capacity %d, 2 * max_count (%d) rows of %d floats need %lld", who, a.row_capacity, prm.max_count, rowLength, need);
+    const fd_flow_motion_info* dmotion = a.flow ? fd_flow_device_motion(ctx, a.flow, who) : nullptr;
+    if (prm.require_window && !p->evaluated)
+        FD_THROW(FD_ERR_RUNTIME, "%s: require_window on a generation that has not been evaluated (fd_particles_evaluate*)", who);
+    p->examples.reserve(examples_rows_offset() + sizeof(float) * (size_t)need);
+    ParticleExamplesHead* head = p->examples.as<ParticleExamplesHead>();
+    particles_queue_state(ctx, p);
+    fd_allow_lds(ctx, (const void*)k_particles_examples, (int)(sizeof(unsigned long long) * FD_PARTICLES_MAX), allowed);
+    hipLaunchKernelGGL(k_particles_examples, dim3(1), dim3(PT), sizeof(unsigned long long) * (size_t)p->n, ctx->stream, p->gen[p->cur], p->valid, p->n, prm,
+                       p->dinfo.as<fd_particles_info>(), dmotion, head);
+    HIP_CHECK(hipGetLastError());
+    return FdExamplesRun{(float*)(p->examples.as<unsigned char>() + examples_rows_offset()), head->rowValid};
+}
+
+void fd_particles_examples_xywh(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, double aspect, const FdSampleMaps& chain, int32_t* dxywh) {
+    hipLaunchKernelGGL(k_particles_examples_xywh, dim3(1), dim3(2 * FD_PARTICLES_EXAMPLES_MAX), 0, ctx->stream, p->examples.as<ParticleExamplesHead>(),
+                       a.params->max_count, aspect, chain, (int4*)dxywh);
+    HIP_CHECK(hipGetLastError());
+}
+
+void fd_particles_examples_end(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, int rowLength, const char* who) {
+    const int K = a.params->max_count;
+    const size_t rowBytes = sizeof(float) * (size_t)rowLength, bytes = examples_rows_offset() + rowBytes * 2 * (size_t)K;
+    p->examplesHost.resize(bytes);
+    HIP_CHECK(hipMemcpyAsync(p->examplesHost.data(), p->examples.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ParticleExamplesHead head;
+    std::memcpy(&head, p->examplesHost.data(), sizeof(head));
+    const unsigned char* hostRows = p->examplesHost.data() + examples_rows_offset();
+    *a.info = head.info;
+    if (a.motion) *a.motion = head.motion;
+    p->sum = head.info.weight_sum;
+    p->sumKnown = true;
+    p->bad = head.info.bad_weight != 0;
+    if (head.info.bad_weight) FD_THROW(FD_ERR_RUNTIME, "%s: the generation holds a weight that is negative or not finite", who);
+    const int nPos = std::min(std::max(head.nPos, 0), K), nNeg = std::min(std::max(head.nNeg, 0), K);
+    for (int r = 0; r < nPos + nNeg; ++r) {
+        const bool negative = r >= nPos;
+        const int k = negative ? r - nPos : r, slot = negative ? K + k : k;
+        fd_particles_example rec = negative ? head.neg[k] : head.pos[k];
+        rec.valid = head.rowValid[slot] ? 1 : 0;
+        (negative ? a.neg : a.pos)[k] = rec;
+        if (rec.valid && rowBytes) std::memcpy(a.rows + (size_t)r * rowLength, hostRows + (size_t)slot * rowBytes, rowBytes);
+    }
+    *a.n_pos = nPos;
+    *a.n_neg = nNeg;
+}
+
+extern "C" int fd_particles_state_examples_pyramid(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_pyramid* pyr, int kind, const void* params,
+                                                   double aspect_ratio, const fd_sample_map* maps, int n_maps,
+                                                   const fd_particles_examples_params* examples_params, fd_particles_info* info, fd_flow_motion_info* motion,
+                                                   int* n_pos, fd_particles_example* pos, int* n_neg, fd_particles_example* neg, float* rows, int row_capacity,
+                                                   int* row_length) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_state_examples_pyramid";
+        if (!ctx || !p || !pyr || !params) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+        const FdExamplesArgs a{flow, examples_params, info, motion, n_pos, n_neg, pos, neg, rows, row_capacity, row_length};
+        fd_particles_examples_check(ctx, p, a, who);
+        const FdSampleMaps chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE, who);
+        if (kind != FD_SAMPLES_HIST && kind != FD_SAMPLES_EHOG && kind != FD_SAMPLES_PATCH) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: unknown feature kind %d", who, kind);
+        if (pyr->ctx != ctx) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: objects belong to different contexts", who);
+        fd_pyramid_require_single(pyr, who);
+        fd_pyramid_require_image(pyr);
+        if (pyr->kept.size() > (size_t)FD_WIN_MAX_LAYERS) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: too many pyramid layers (%zu)", who, pyr->kept.size());
+        const int slots = 2 * examples_params->max_count;   // the launch size does not depend on what was chosen
+        int len = 0, pw = 0, ph = 0;
+        auto features = [&](const int32_t* dlist) {   // dlist NULL: the argument rules alone
+            return kind == FD_SAMPLES_PATCH ? fd_patch_samples_features_list(ctx, pyr, (const fd_patch_samples_params*)params, who, dlist, slots, &len, &pw, &ph)
+                                            : fd_hist_samples_features_list(ctx, pyr, kind, params, who, dlist, slots, &len, &pw, &ph);
+        };
+        features(nullptr);
+        particle_windows_table(ctx, pyr, pw, who);
+        FdSampleWindow spare;
+        const ParticleLayers layers = particle_layers(pyr, pw, ph, spare);
+        p->exampleList.reserve(sizeof(int32_t) * 3 * 2 * FD_PARTICLES_EXAMPLES_MAX);
+        const FdExamplesRun run = fd_particles_examples_begin(ctx, p, a, len, who);
+        hipLaunchKernelGGL(k_particles_examples_windows, dim3(1), dim3(2 * FD_PARTICLES_EXAMPLES_MAX), 0, ctx->stream, p->examples.as<ParticleExamplesHead>(),
+                           examples_params->max_count, aspect_ratio, chain, layers, pyr->sample_table.dev.as<int16_t>(), pyr->sample_table.length, pw, ph, spare,
+                           p->exampleList.as<int32_t>(), run.valid);
+        HIP_CHECK(hipGetLastError());
+        if (spare.layer >= 0) {   // otherwise no kept layer holds a window: every slot is invalid and the list must not be read
+            const float* dfeat = features(p->exampleList.as<int32_t>());
+            if (len > 0) HIP_CHECK(hipMemcpyAsync(run.rows, dfeat, sizeof(float) * (size_t)len * slots, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        fd_particles_examples_end(ctx, p, a, len, who);
+    });
+}

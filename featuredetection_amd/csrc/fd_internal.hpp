@@ -745,6 +745,39 @@ __host__ __device__ inline FdNegativeBounds fd_negative_bounds(float offsetFacto
 __host__ __device__ inline bool fd_negative_outside(const FdNegativeBounds& b, int32_t x, int32_t y, int32_t size) {
     return x <= b.xLow || x >= b.xHigh || y <= b.yLow || y >= b.yHigh || size <= b.sizeLow || size >= b.sizeHigh;
 }
+// ---- the examples of SelfLearningMeasurementModel::adapt (SelfLearningMeasurementModel.cpp:89-125): the one copy of the rule's
+// comparisons for the host (fd_particles_examples_select, hostalgo.cpp) and the device (k_particles_examples, particle_examples.hpp) ----
+__host__ __device__ inline bool fd_example_candidate(bool positive, double weight, double threshold) { return positive ? weight > threshold : weight < threshold; }
+// the list order of a side with more than max_count candidates: a before b.  Equal weights (-0 and +0 are equal): the lower index
+__host__ __device__ inline bool fd_example_before(bool positive, double wa, int32_t ia, double wb, int32_t ib) {
+    if (wa != wb) return positive ? wa > wb : wa < wb;
+    return ia < ib;
+}
+// The device half of fd_particles_state_examples_*, for the family's file (integral.hip).  _check throws FdError for every argument of
+// the call that does not belong to the extractor; _begin checks the row capacity, then queues k_particles_state and k_particles_examples and
+// returns where the family's rows (2 * max_count x rowLength floats, slot s < max_count: positive s, slot max_count + s: negative s)
+// and their validity bytes go in the read-back block.  _xywh queues the chosen samples through the chain as {x, y, width, height}
+// into dxywh (2 * max_count entries; an unused slot gets {0, 0, 0, 0}, which no extractor computes).  _end brings the block back in
+// one copy and one wait and fills the caller's arguments; throws FD_ERR_RUNTIME with bad_weight.
+struct FdExamplesArgs {
+    fd_flow* flow;
+    const fd_particles_examples_params* params;
+    fd_particles_info* info;
+    fd_flow_motion_info* motion;
+    int *n_pos, *n_neg;
+    fd_particles_example *pos, *neg;
+    float* rows;
+    int row_capacity;
+    int* row_length;
+};
+struct FdExamplesRun {
+    float* rows;
+    uint8_t* valid;
+};
+void fd_particles_examples_check(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, const char* who);   // all of a but the row capacity
+FdExamplesRun fd_particles_examples_begin(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, int rowLength, const char* who);
+void fd_particles_examples_xywh(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, double aspect, const FdSampleMaps& chain, int32_t* dxywh);
+void fd_particles_examples_end(fd_ctx* ctx, fd_particles* p, const FdExamplesArgs& a, int rowLength, const char* who);
 // ---- resident particle set on the pyramid families (condensation.hip launches k_particles_windows; the scoring kernels are hog.hip's and rvm.hip's) ----
 // "Score this device list of n windows {layer, bx, by} of p into this device score array": the kernels of fd_hist_svm_evaluate_samples
 // (kind FD_SAMPLES_HIST / FD_SAMPLES_EHOG, hog.hip) and of fd_patch_svm_evaluate_samples (rvm.hip) and the SVM launch, queued on
@@ -754,6 +787,13 @@ void fd_hist_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, int kind, cons
                                 int n, double* dscore, int* patch_w, int* patch_h);
 void fd_patch_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const fd_svm* svm, const char* who,
                                  const int32_t* dlist, int n, double* dscore, int* patch_w, int* patch_h);
+// "Leave the feature rows of this device list of n windows on the device": the kernels of fd_hist_extract_samples / fd_ehog_extract_samples
+// (hog.hip) and of fd_patch_extract_samples (rvm.hip), queued on ctx->stream, no host wait; the rows are the family's scratch and hold
+// until its next call.  Every argument rule of those entry points is checked first; with dlist NULL that is all the call does.
+const float* fd_hist_samples_features_list(fd_ctx* ctx, const fd_pyramid* p, int kind, const void* params, const char* who, const int32_t* dlist, int n,
+                                           int* row_length, int* patch_w, int* patch_h);
+const float* fd_patch_samples_features_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const char* who, const int32_t* dlist, int n,
+                                            int* row_length, int* patch_w, int* patch_h);
 // ---- resident particle set on condensation::WvmSvmModel (condensation.hip with particle_wvm_svm.hpp; the cascade is wvm.hip's) ----
 // What a list-mode cascade run with per-window outputs leaves on the device, for the kernels queued behind it on ctx->stream.  The
 // buffers are the WVM handle's: they hold until its next run.

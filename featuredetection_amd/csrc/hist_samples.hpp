@@ -88,6 +88,16 @@ void fd_hist_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, int kind, cons
     fd_svm_generic_launch(ctx, svm, samples_features(ctx, p, pl, dlist, n, scratch(ctx)), nullptr, (int64_t)pl.F * 4, n, dscore);
 }
 
+// the same list's feature rows, left on the device ([n][*row_length] floats, the handle's scratch: they hold until its next call), for
+// fd_particles_state_examples_pyramid; with dlist NULL the argument rules of fd_hist_extract_samples / fd_ehog_extract_samples alone
+const float* fd_hist_samples_features_list(fd_ctx* ctx, const fd_pyramid* p, int kind, const void* params, const char* who, const int32_t* dlist, int n,
+                                           int* row_length, int* patch_w, int* patch_h) {
+    const SamplesPlan pl = samples_plan(ctx, p, kind, params, n, who);
+    *row_length = pl.F; *patch_w = pl.hp.patch_w; *patch_h = pl.hp.patch_h;
+    if (!dlist || n == 0) return nullptr;
+    return samples_features(ctx, p, pl, dlist, n, scratch(ctx));
+}
+
 extern "C" {
 
 int fd_sample_windows(int n_layers, const int32_t* layer_index, const double* layer_scale, const int32_t* layer_w, const int32_t* layer_h,

@@ -4,6 +4,8 @@
 // thousand records and the algorithms are sequential by definition (sort + greedy erase).
 #include "fd_internal.hpp"
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstring>
 #include <map>
 
@@ -548,6 +550,54 @@ extern "C" int fd_particles_negatives_bounds(const fd_particles_negatives_params
     if (!params || !bounds) return FD_ERR_INVALID_ARGUMENT;
     const FdNegativeBounds b = fd_negative_bounds(params->offset_factor, params->down_scale, params->up_scale, x, y, size);
     bounds[0] = b.xLow; bounds[1] = b.xHigh; bounds[2] = b.yLow; bounds[3] = b.yHigh; bounds[4] = b.sizeLow; bounds[5] = b.sizeHigh;
+    return FD_OK;
+}
+
+// ---- the examples of SelfLearningMeasurementModel::adapt on the host (SelfLearningMeasurementModel.cpp:89-125): the candidates in
+// index order, sorted only when there are more than max_count, by fd_example_candidate / fd_example_before, the comparisons
+// k_particles_examples runs ----
+extern "C" int fd_particles_examples_select(int n, const double* weight, const uint8_t* valid, const fd_particles_examples_params* params, int* n_pos,
+                                            int32_t* pos_index, int* n_neg, int32_t* neg_index) {
+    if (n_pos) *n_pos = 0;
+    if (n_neg) *n_neg = 0;
+    if (n < 0 || !params || !n_pos || !pos_index || !n_neg || !neg_index || (n > 0 && !weight)) return FD_ERR_INVALID_ARGUMENT;
+    if (params->max_count < 1 || params->max_count > FD_PARTICLES_EXAMPLES_MAX || !std::isfinite(params->positive_threshold) ||
+        !std::isfinite(params->negative_threshold) || params->negative_threshold > params->positive_threshold || (params->require_window != 0 && params->require_window != 1) || (params->require_window && n > 0 && !valid))
+        return FD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; ++i)
+        if (!(weight[i] >= 0.0 && weight[i] <= DBL_MAX)) return FD_ERR_RUNTIME;
+    const size_t K = (size_t)params->max_count;
+    auto side = [&](bool positive, double threshold, int32_t* out) {
+        std::vector<int32_t> chosen;
+        for (int i = 0; i < n; ++i)
+            if (fd_example_candidate(positive, weight[i], threshold) && (!params->require_window || valid[i])) chosen.push_back(i);
+        if (chosen.size() > K) {
+            std::sort(chosen.begin(), chosen.end(), [&](int32_t a, int32_t b) { return fd_example_before(positive, weight[a], a, weight[b], b); });
+            chosen.resize(K);
+        }
+        std::copy(chosen.begin(), chosen.end(), out);
+        return (int)chosen.size();
+    };
+    *n_pos = side(true, params->positive_threshold, pos_index);
+    *n_neg = side(false, params->negative_threshold, neg_index);
+    return FD_OK;
+}
+
+extern "C" int fd_particles_examples_bounds(int family, int kind, const void* params, int channels, int max_count, int* row_length, int* row_capacity) {
+    if (!params || !row_length || !row_capacity || max_count < 1 || max_count > FD_PARTICLES_EXAMPLES_MAX) return FD_ERR_INVALID_ARGUMENT;
+    int len = -1;
+    if (family == FD_EXAMPLES_INTEGRAL) {
+        if (kind == FD_INTEGRAL_HAAR) len = fd_haar_feature_count((const fd_haar_params*)params);
+        else if (kind == FD_INTEGRAL_SURF) len = fd_surf_feature_length(((const fd_surf_params*)params)->gradient_count, ((const fd_surf_params*)params)->cell_count);
+        else if (kind == FD_INTEGRAL_HOG) len = fd_integral_hog_feature_length((const fd_integral_hog_params*)params);
+    } else if (family == FD_EXAMPLES_PYRAMID) {
+        if (kind == FD_SAMPLES_HIST) len = fd_hist_feature_length((const fd_hist_params*)params, channels);
+        else if (kind == FD_SAMPLES_EHOG) len = fd_ehog_feature_length((const fd_ehog_patch_params*)params, channels);
+        else if (kind == FD_SAMPLES_PATCH) len = fd_patch_feature_length((const fd_patch_samples_params*)params);
+    }
+    if (len < 0 || (long long)len * 2 * max_count > INT32_MAX) return FD_ERR_INVALID_ARGUMENT;
+    *row_length = len;
+    *row_capacity = len * 2 * max_count;
     return FD_OK;
 }
 

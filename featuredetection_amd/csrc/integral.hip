@@ -635,4 +635,27 @@ int fd_particles_evaluate_integral(fd_ctx* ctx, fd_particles* p, fd_integral* g,
     });
 }
 
+int fd_particles_state_examples_integral(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_integral* g, int kind, const void* params, double aspect_ratio,
+                                         const fd_sample_map* maps, int n_maps, const fd_particles_examples_params* examples_params, fd_particles_info* info,
+                                         fd_flow_motion_info* motion, int* n_pos, fd_particles_example* pos, int* n_neg, fd_particles_example* neg, float* rows,
+                                         int row_capacity, int* row_length) {
+    return fd_guard(ctx, [&] {
+        static const char* const who = "fd_particles_state_examples_integral";
+        if (!ctx || !p || !g || !params) FD_THROW(FD_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+        const FdExamplesArgs a{flow, examples_params, info, motion, n_pos, n_neg, pos, neg, rows, row_capacity, row_length};
+        fd_particles_examples_check(ctx, p, a, who);
+        const FdSampleMaps chain = fd_sample_maps_checked(maps, n_maps, 1u << FD_SAMPLE_MAP_RESIZE | 1u << FD_SAMPLE_MAP_INTEGRAL, who);
+        const int len = integral_prepare(ctx, g, kind, params, who);
+        const int slots = 2 * examples_params->max_count;   // the launch size does not depend on what was chosen
+        g->xywh.reserve(sizeof(int32_t) * 4 * (size_t)slots);
+        g->valid.reserve((size_t)slots);
+        const FdExamplesRun run = fd_particles_examples_begin(ctx, p, a, len, who);
+        fd_particles_examples_xywh(ctx, p, a, aspect_ratio, chain, g->xywh.as<int32_t>());
+        integral_run(ctx, g, kind, params, len, slots);
+        if (len > 0) HIP_CHECK(hipMemcpyAsync(run.rows, g->feat.p, sizeof(float) * (size_t)len * slots, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(run.valid, g->valid.p, (size_t)slots, hipMemcpyDeviceToDevice, ctx->stream));
+        fd_particles_examples_end(ctx, p, a, len, who);
+    });
+}
+
 }  // extern "C"

@@ -83,6 +83,46 @@ __device__ inline unsigned long long negatives_select(const unsigned long long* 
     return prefix;
 }
 
+// The survivors of a selection in index order, by the whole workgroup (shared with k_particles_examples, particle_examples.hpp): of the M
+// non-zero keys[0 .. n) those above the cut T and, of those equal to T, the first with the lowest indices, min(M, K) in all (M <= K: T is 0
+// and every candidate lies above it).  Every wavefront walks a contiguous quarter of the samples twice, 64 at a time: first it counts
+// its keys above and equal to T; with the counts of the wavefronts in front of it, ballots then give every survivor its place in index
+// order, and store(slot, index, key) is called for it once, slot < min(M, K) <= cap.  Returns that count; the caller synchronises
+// before it reads what store wrote.  waveEqual / waveAbove: PT / 64 ints of LDS each.
+template <class Store>
+__device__ inline int negatives_survivors(const unsigned long long* keys, int n, unsigned long long T, int M, int K, int cap, int* waveEqual, int* waveAbove,
+                                          Store store) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int segment = ((n + PT - 1) / PT) * 64, begin = wave * segment;   // a wavefront's quarter, whole steps of 64
+    int equalHere = 0, aboveHere = 0;
+    for (int o = 0; o < segment; o += 64) {
+        const int i = begin + o + lane;
+        const unsigned long long key = i < n ? keys[i] : 0ull;
+        equalHere += __popcll(__ballot(i < n && key == T));
+        aboveHere += __popcll(__ballot(key > T));
+    }
+    if (lane == 0) { waveEqual[wave] = equalHere; waveAbove[wave] = aboveHere; }
+    __syncthreads();
+    int G = 0, equalRun = 0, aboveRun = 0;
+    for (int w = 0; w < PT / 64; ++w) {
+        G += waveAbove[w];
+        if (w < wave) { equalRun += waveEqual[w]; aboveRun += waveAbove[w]; }
+    }
+    const int need = M > K ? K - G : 0;     // of the keys equal to T (with M <= K those are no candidates)
+    for (int o = 0; o < segment; o += 64) {
+        const int i = begin + o + lane;
+        const unsigned long long key = i < n ? keys[i] : 0ull;
+        const bool above = key > T, equal = i < n && key == T;
+        const unsigned long long aboveMask = __ballot(above), equalMask = __ballot(equal), below = (1ull << lane) - 1ull;
+        const int aboveRank = aboveRun + __popcll(aboveMask & below), equalRank = equalRun + __popcll(equalMask & below);
+        const int slot = aboveRank + min(equalRank, need);   // of a survivor: < G + need
+        if ((above || (equal && equalRank < need)) && slot < cap) store(slot, i, key);
+        aboveRun += __popcll(aboveMask);
+        equalRun += __popcll(equalMask);
+    }
+    return M > K ? K : M;   // G + need
+}
+
 // One workgroup behind k_particles_state.  Without a state, or with bad_weight, the count is 0.  Otherwise, with M candidates (the
 // samples outside the box; their keys in LDS, 0 for every other sample):
 //  - M > K: T, the K-th largest key, by radix selection; the survivors are the G < K candidates above T and of those equal to T the
@@ -119,37 +159,8 @@ __global__ __launch_bounds__(PT) void k_particles_negatives(ParticleGen g, int n
     for (int w = 0; w < PT / 64; ++w) M += waveCandidates[w];
     const unsigned long long T = M > K ? negatives_select(negKeys, n, hist, chosen, (unsigned int)(M - K)) : 0ull;
 
-    const int segment = ((n + PT - 1) / PT) * 64, begin = wave * segment;   // a wavefront's quarter, whole steps of 64
-    int equalHere = 0, aboveHere = 0;
-    for (int o = 0; o < segment; o += 64) {
-        const int i = begin + o + lane;
-        const unsigned long long key = i < n ? negKeys[i] : 0ull;
-        equalHere += __popcll(__ballot(i < n && key == T));
-        aboveHere += __popcll(__ballot(key > T));
-    }
-    if (lane == 0) { waveEqual[wave] = equalHere; waveAbove[wave] = aboveHere; }
-    __syncthreads();
-    int G = 0, equalRun = 0, aboveRun = 0;
-    for (int w = 0; w < PT / 64; ++w) {
-        G += waveAbove[w];
-        if (w < wave) { equalRun += waveEqual[w]; aboveRun += waveAbove[w]; }
-    }
-    const int need = M > K ? K - G : 0;     // of the keys equal to T (with M <= K those are no candidates)
-    const int count = M > K ? K : M;        // G + need
-    for (int o = 0; o < segment; o += 64) {
-        const int i = begin + o + lane;
-        const unsigned long long key = i < n ? negKeys[i] : 0ull;
-        const bool above = key > T, equal = i < n && key == T;
-        const unsigned long long aboveMask = __ballot(above), equalMask = __ballot(equal), below = (1ull << lane) - 1ull;
-        const int aboveRank = aboveRun + __popcll(aboveMask & below), equalRank = equalRun + __popcll(equalMask & below);
-        if (above || (equal && equalRank < need)) {
-            const int slot = aboveRank + min(equalRank, need);   // < G + need = count <= FD_PARTICLES_NEGATIVES_MAX
-            sKey[slot] = key;
-            sIdx[slot] = i;
-        }
-        aboveRun += __popcll(aboveMask);
-        equalRun += __popcll(equalMask);
-    }
+    const int count = negatives_survivors(negKeys, n, T, M, K, FD_PARTICLES_NEGATIVES_MAX, waveEqual, waveAbove,
+                                          [&](int slot, int i, unsigned long long key) { sKey[slot] = key; sIdx[slot] = i; });
     __syncthreads();
     if (tid < count) {
         const unsigned long long key = sKey[tid];

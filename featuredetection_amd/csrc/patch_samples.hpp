@@ -138,6 +138,17 @@ void fd_patch_samples_score_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patc
     fd_svm_generic_launch(ctx, svm, patch_f32_rows(ctx, p, pp, dlist, n, patch_scratch(ctx)), nullptr, (int64_t)pp->patch_w * pp->patch_h * 4, n, dscore);
 }
 
+// the same list's feature rows, left on the device ([n][patch_w * patch_h] floats, the context's scratch: they hold until its next
+// call), for fd_particles_state_examples_pyramid; with dlist NULL the argument rules of fd_patch_extract_samples alone
+const float* fd_patch_samples_features_list(fd_ctx* ctx, const fd_pyramid* p, const fd_patch_samples_params* pp, const char* who, const int32_t* dlist, int n,
+                                            int* row_length, int* patch_w, int* patch_h) {
+    patch_samples_check(ctx, p, pp, n, nullptr, nullptr, who);
+    *row_length = pp->patch_w * pp->patch_h; *patch_w = pp->patch_w; *patch_h = pp->patch_h;
+    if (!dlist || n == 0) return nullptr;
+    fd_pyramid_wait(p, ctx->stream);
+    return patch_f32_rows(ctx, p, pp, dlist, n, patch_scratch(ctx));
+}
+
 extern "C" {
 
 int fd_patch_feature_length(const fd_patch_samples_params* pp) { return patch_params_ok(pp) ? pp->patch_w * pp->patch_h : -1; }

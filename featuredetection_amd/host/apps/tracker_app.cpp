@@ -9,6 +9,8 @@
 //     transition opticalFlow { positionDeviation 10  sizeDeviation 0.08  fallback simple { positionDeviation 12.8  sizeDeviation 0.1 } }
 //                                                                              (headTrackingApp/default.cfg:16-27; in place of the line above)
 //     adaptive { resampling { particleCount 800  randomRate 0.35  minSize 40  maxSize 200 } }
+//     tracker partiallyAdaptive: `measurement wvmSvm { .. }` as the static model and `adaptive selfLearning { .. }` (tracking_setup.hpp) as the
+//                        adaptive one; no initialisation, every frame is printed
 //     grid { minSize 20 maxSize 80 sizeScale 1.2 stepSize 0.1 }                (optional: a GridSampler in place of the resampling sampler)
 //     initialCount 800   seed 1                                                (seed: the samplers' generators get seed, seed + 1, seed + 2;
 //                                                                               seed + 1 is the simple model's, also as the fallback; the flow model's seed + 3)
@@ -187,6 +189,45 @@ static int track_wvm_svm(const ptree& pt, const shared_ptr<TransitionModel>& tra
     return 0;
 }
 
+// `tracker partiallyAdaptive`: the graph of the reference's partiallyAdaptiveTrackingApp -- WvmSvmModel until the self-learning model,
+// bootstrapped from its samples, is usable -- over the frames argv[first ..].  The frame line gains `model <static|adaptive>`; with
+// --adaptation the chosen examples follow as `sp|sn <index> <x> <y> <size> <valid>`
+static int track_partially_adaptive(const ptree& pt, const shared_ptr<TransitionModel>& transitionModel, unsigned seed, bool adaptation, bool dumping, int first,
+                                    int argc, char** argv) {
+    if (pt.get("measurement", string("")) != "wvmSvm") throw std::invalid_argument("tracker_app: `tracker partiallyAdaptive` needs `measurement wvmSvm` as its static model");
+    if (pt.get("adaptive", string("")) != "selfLearning")
+        throw std::invalid_argument("tracker_app: `tracker partiallyAdaptive` needs `adaptive selfLearning { .. }` as its adaptive model");
+    if (std::dynamic_pointer_cast<OpticalFlowTransitionModel>(transitionModel))
+        throw std::invalid_argument("tracker_app: `transition opticalFlow` is not built under `tracker partiallyAdaptive`");
+    const tracking_setup::WvmSvmSetup setup = tracking_setup::createWvmSvm(pt.get_child("measurement"));
+    shared_ptr<SelfLearningMeasurementModel> adaptive = tracking_setup::createSelfLearning(pt.get_child("adaptive"));
+    auto sampler = make_shared<ResamplingSampler>(pt.get("adaptive.resampling.particleCount", 800), pt.get("adaptive.resampling.randomRate", 0.35),
+                                                  make_shared<LowVarianceSampling>(seed), transitionModel, pt.get("adaptive.resampling.minSize", setup.minWidth),
+                                                  pt.get("adaptive.resampling.maxSize", setup.maxWidth), seed + 2);
+    PartiallyAdaptiveCondensationTracker tracker(sampler, setup.model, adaptive, make_shared<FilteringStateExtractor>(make_shared<WeightedMeanStateExtractor>()));
+    for (int f = first; f < argc; ++f) {
+        const cv::Mat frame = read_pnm(argv[f]);
+        if (f == first) sampler->init(frame);
+        const bool wasUsable = adaptive->isUsable();
+        const auto t0 = std::chrono::steady_clock::now();
+        boost::optional<cv::Rect> found = tracker.process(frame);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const bool materialized = tracker.samplesMaterialized();   // before anything below asks for the samples
+        const cv::Rect r = found ? *found : cv::Rect();
+        std::printf("frame %d found %d %d %d %d %d adapted %d route %s model %s ms %.3f\n", f - first, found ? 1 : 0, r.x, r.y, r.width, r.height,
+                    adaptive->isUsable() ? 1 : 0, tracker.getLastRoute() == ParticleFrameLoop::Route::DEVICE ? "device" : "generic",
+                    tracker.hasUsedAdaptiveModel() ? "adaptive" : "static", ms);
+        if (adaptation) {
+            std::printf("adaptation %d materialized %d usable %d positives %zu negatives %zu\n", wasUsable ? 1 : 0, materialized ? 1 : 0, adaptive->isUsable() ? 1 : 0,
+                        adaptive->getLastPositives().size(), adaptive->getLastNegatives().size());
+            for (const fd_particles_example& e : adaptive->getLastPositives()) std::printf("sp %d %d %d %d %d\n", e.index, e.x, e.y, e.size, e.valid);
+            for (const fd_particles_example& e : adaptive->getLastNegatives()) std::printf("sn %d %d %d %d %d\n", e.index, e.x, e.y, e.size, e.valid);
+        }
+        if (dumping) dump(tracker.getSampler(), tracker.getSamples());
+    }
+    return 0;
+}
+
 static int selftest(int argc, char** argv) {
     if (argc < 6) return 2;
     const unsigned seed = (unsigned)std::atoi(argv[2]);
@@ -255,6 +296,9 @@ int main(int argc, char** argv) {
         } else {
             throw std::invalid_argument("tracker_app: invalid transition model type: " + transition);
         }
+        const string trackerType = pt.get("tracker", string("adaptive"));
+        if (trackerType == "partiallyAdaptive") return track_partially_adaptive(pt, transitionModel, seed, adaptation, dumping, a + 5, argc, argv);
+        if (trackerType != "adaptive") throw std::invalid_argument("tracker_app: invalid tracker type: " + trackerType + " (adaptive and partiallyAdaptive are supported)");
         const string measurement = pt.get("measurement", string("ehog"));
         if (measurement != "ehog" && measurement != "positionDependent" && measurement != "wvmSvm")
             throw std::invalid_argument("tracker_app: invalid measurement model type: " + measurement + " (ehog, positionDependent and wvmSvm are supported)");

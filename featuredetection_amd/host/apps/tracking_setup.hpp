@@ -338,4 +338,49 @@ inline WvmSvmSetup createWvmSvm(const ptree& mt) {
     return s;
 }
 
+// `adaptive selfLearning { positiveThreshold 0.85 negativeThreshold 0.05 feature <type> { .. } classifier { kernel rbf { gamma g } | poly {
+// alpha a constant c degree d }  training { c 1 compensateImbalance 0 examples fixedsize positiveExamples 10 negativeExamples 50
+// minPositiveExamples 3 }  probabilistic fixed { logisticA a logisticB b } | default { positiveExamples 10 negativeExamples 50 } } }`: the
+// adaptive model of the reference's partiallyAdaptiveTrackingApp, as far as the classes behind its keys exist here.  `fixedsize` is an
+// AgeBasedExampleManagement of that capacity (minPositiveExamples is its required size); `subclass 1` (not one of the reference's keys)
+// builds a subclass that changes nothing, which must keep the generic route
+struct SubclassedSelfLearningModel : public condensation::SelfLearningMeasurementModel {
+    using condensation::SelfLearningMeasurementModel::SelfLearningMeasurementModel;
+};
+inline std::shared_ptr<condensation::SelfLearningMeasurementModel> createSelfLearning(const ptree& at) {
+    if (!at.count("feature") || !at.count("classifier"))
+        throw std::invalid_argument("tracking: `adaptive selfLearning` (condensation::SelfLearningMeasurementModel) needs a block: adaptive selfLearning { "
+                                    "positiveThreshold p negativeThreshold n feature <type> { .. } classifier { kernel rbf { gamma g } training { c 1 } "
+                                    "probabilistic fixed { logisticA a logisticB b } } }");
+    const ptree& ct = at.get_child("classifier");
+    if (flag(ct, "withWvm")) throw std::invalid_argument("tracking: `withWvm true` (TrainableProbabilisticTwoStageClassifier) is not built");
+    if (ct.count("training") && ct.get_child("training").count("staticNegatives"))
+        throw std::invalid_argument("tracking: `staticNegatives` is not built (LibSvmClassifier::loadStaticNegatives)");
+    const std::string kernelType = ct.get("kernel", std::string("rbf"));
+    std::shared_ptr<Kernel> kernel;
+    if (kernelType == "rbf") kernel = std::make_shared<RbfKernel>(ct.get("kernel.gamma", 0.002));
+    else if (kernelType == "poly") kernel = std::make_shared<PolynomialKernel>(ct.get("kernel.alpha", 0.05), ct.get("kernel.constant", 0.0), ct.get("kernel.degree", 2));
+    else throw std::invalid_argument("tracking: invalid kernel type: " + kernelType + " (rbf and poly are supported)");
+    const std::string examples = ct.get("training.examples", std::string("fixedsize"));
+    if (examples == "framebased") throw std::invalid_argument("tracking: `examples framebased` (FrameBasedExampleManagement) is not built: use `fixedsize`");
+    if (examples != "fixedsize") throw std::invalid_argument("tracking: invalid example management: " + examples);
+    auto svm = libsvm::LibSvmClassifier::createBinaryKernelSvm(kernel, ct.get("training.c", 1.0), ct.get("training.compensateImbalance", 0) != 0);
+    svm->setPositiveExampleManagement(std::unique_ptr<ExampleManagement>(
+        new AgeBasedExampleManagement(ct.get("training.positiveExamples", 10), ct.get("training.minPositiveExamples", 3))));
+    svm->setNegativeExampleManagement(std::unique_ptr<ExampleManagement>(new AgeBasedExampleManagement(ct.get("training.negativeExamples", 50))));
+    svm->getSvm()->setThreshold(ct.get("threshold", 0.0f));
+    const std::string probabilistic = ct.get("probabilistic", std::string("fixed"));
+    std::shared_ptr<TrainableProbabilisticSvmClassifier> classifier;
+    if (probabilistic == "fixed")
+        classifier = std::make_shared<FixedTrainableProbabilisticSvmClassifier>(svm, ct.get("probabilistic.logisticA", 0.00556), ct.get("probabilistic.logisticB", -2.95));
+    else if (probabilistic == "default")
+        classifier = std::make_shared<TrainableProbabilisticSvmClassifier>(svm, ct.get("probabilistic.positiveExamples", 10), ct.get("probabilistic.negativeExamples", 50));
+    else
+        throw std::invalid_argument("tracking: invalid probabilistic type: " + probabilistic + " (default and fixed are supported)");
+    std::shared_ptr<FeatureExtractor> extractor = createFeatureExtractor(at.get_child("feature"));
+    const double positiveThreshold = at.get("positiveThreshold", 0.85), negativeThreshold = at.get("negativeThreshold", 0.05);
+    if (at.get("subclass", 0) != 0) return std::make_shared<SubclassedSelfLearningModel>(extractor, classifier, positiveThreshold, negativeThreshold);
+    return std::make_shared<condensation::SelfLearningMeasurementModel>(extractor, classifier, positiveThreshold, negativeThreshold);
+}
+
 }  // namespace tracking_setup

@@ -426,6 +426,51 @@ private:
 };
 
 // Sampler.hpp:24-48
+// SelfLearningMeasurementModel.hpp / .cpp:26-133: a classifier that is retrained on the frame's own most and least confident samples,
+// at most 10 per side.  evaluate is SingleClassifierModel's (target and weight, .cpp:53-74).  adapt picks the examples by the library's
+// rule (fd_particles_examples_select, the comparisons k_particles_examples runs): while the model is usable only samples
+// with a patch are examples, before that every sample is a candidate and the extraction decides; a side with more than 10 candidates
+// keeps the best 10 in sorted order, equal weights to the lower index (the reference's std::sort is unstable).  The feature vectors go to
+// retrain as 1 x n rows.  Thresholds with negativeThreshold > positiveThreshold are refused (std::invalid_argument).
+class SelfLearningMeasurementModel : public AdaptiveMeasurementModel {
+public:
+    SelfLearningMeasurementModel(std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                 std::shared_ptr<classification::TrainableProbabilisticClassifier> classifier, double positiveThreshold = 0.85,
+                                 double negativeThreshold = 0.05);
+    void update(std::shared_ptr<imageprocessing::VersionedImage> image) override { model.update(image); }
+    void evaluate(Sample& sample) const override { model.evaluate(sample); }
+    void evaluate(std::shared_ptr<imageprocessing::VersionedImage> image, std::vector<std::shared_ptr<Sample>>& samples) override { model.evaluate(image, samples); }
+    bool isUsable() const override { return usable; }
+    bool initialize(std::shared_ptr<imageprocessing::VersionedImage>, Sample&) override { return false; }
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples, const Sample&) override {
+        return adapt(image, samples);
+    }
+    bool adapt(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<std::shared_ptr<Sample>>& samples) override;
+    void reset() override;
+    // Not in the reference.  The resident evaluation is SingleClassifierModel's; readExamples updates the extractor with
+    // the image and reads the state of the generation in `particles` through fd_particles_state_examples_*, with require_window =
+    // isUsable(): the examples and their rows stay in the model until adaptResident, which ends in the retrain call adapt ends in.
+    SingleClassifierModel::ResidentPlan residentPlan() const;   // while not usable: the extraction alone, no scoring classifier needed
+    void evaluateResident(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) { model.evaluateResident(image, particles); }
+    void readExamples(std::shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles, fd_particles_info& info);
+    bool adaptResident(std::shared_ptr<imageprocessing::VersionedImage> image, const std::vector<fd_particles_example>& positives,
+                       const std::vector<fd_particles_example>& negatives, const std::vector<float>& rows);
+    bool adaptResident(std::shared_ptr<imageprocessing::VersionedImage> image) { return adaptResident(image, lastPositives, lastNegatives, lastRows); }
+    // the examples of the last adaptation, in list order (valid: the sample had a patch and went to retrain)
+    const std::vector<fd_particles_example>& getLastPositives() const { return lastPositives; }
+    const std::vector<fd_particles_example>& getLastNegatives() const { return lastNegatives; }
+private:
+    fd_particles_examples_params examplesParams() const;
+    SingleClassifierModel model;
+    std::shared_ptr<imageprocessing::FeatureExtractor> featureExtractor;
+    std::shared_ptr<classification::TrainableProbabilisticClassifier> classifier;
+    double positiveThreshold, negativeThreshold;
+    bool usable = false;
+    std::vector<fd_particles_example> lastPositives, lastNegatives;
+    std::vector<float> lastRows;
+    int lastRowLength = 0;
+};
+
 class Sampler {
 public:
     virtual ~Sampler() {}
@@ -700,6 +745,10 @@ protected:
     const std::vector<Sample>& chosenNegatives() const { return residentChosen; }
     // the generation lives on the device alone (a validator that does not read its samples argument need not get it)
     bool samplesOnDeviceOnly() const { return resident && !materialized; }
+    // PartiallyAdaptiveCondensationTracker: the model whose examples a device frame reads with its state (readExamples) in place of the
+    // plain state; the frame takes the device route only while this model has a resident plan.  examplesRead(): the last frame did so
+    std::shared_ptr<SelfLearningMeasurementModel> examplesModel;
+    bool examplesRead() const { return lastRoute == Route::DEVICE && residentExamples; }
     ParticleFrameLoop(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
     ~ParticleFrameLoop();
     ParticleFrameLoop(const ParticleFrameLoop&) = delete;
@@ -730,6 +779,7 @@ private:
     mutable bool materialized = true;         // `samples` holds it as well
     int residentCount = 0;
     double residentWeightSum = 0;
+    bool residentExamples = false;            // the last device frame read its state through SelfLearningMeasurementModel::readExamples
     bool residentChose = false;               // the last device frame read its state through fd_particles_state_negatives
     std::vector<Sample> residentChosen;       // what it chose, in the list order of adapt
     Route lastRoute = Route::NONE;
@@ -766,6 +816,29 @@ private:
     bool adapted;
     std::shared_ptr<AdaptiveMeasurementModel> adaptiveModel;
     std::vector<std::shared_ptr<StateValidator>> validators;
+};
+
+// PartiallyAdaptiveCondensationTracker.hpp / .cpp:26-71: a static model until the adaptive one, bootstrapped from the static model's most
+// and least confident samples, is usable.  On ParticleFrameLoop: under FD_COND_DEVICE=1 a frame takes the device route when the initial
+// model is exactly WvmSvmModel with residentPossible, the adaptive model exactly SelfLearningMeasurementModel with a resident plan, and
+// sampler, SimpleTransitionModel and state extractor are the ones the route requires; no Sample objects are built then unless
+// getSamples() asks for them.
+class PartiallyAdaptiveCondensationTracker : public ParticleFrameLoop {
+public:
+    PartiallyAdaptiveCondensationTracker(std::shared_ptr<Sampler> sampler, std::shared_ptr<MeasurementModel> initialMeasurementModel,
+                                         std::shared_ptr<AdaptiveMeasurementModel> measurementModel, std::shared_ptr<StateExtractor> extractor);
+    boost::optional<cv::Rect> process(const cv::Mat& image);
+    std::shared_ptr<Sample> getState() { return state; }
+    const std::vector<std::shared_ptr<Sample>>& getSamples() const { return currentSamples(); }
+    std::shared_ptr<Sampler> getSampler() { return sampler; }
+    void setSampler(std::shared_ptr<Sampler> sampler) { this->sampler = sampler; }
+    bool isUsingAdaptiveModel() { return useAdaptiveModel; }
+    bool hasUsedAdaptiveModel() { return usedAdaptiveModel; }
+    void setUseAdaptiveModel(bool useAdaptive);
+private:
+    bool useAdaptiveModel = true, usedAdaptiveModel = false;
+    std::shared_ptr<MeasurementModel> initialModel;
+    std::shared_ptr<AdaptiveMeasurementModel> adaptiveModel;
 };
 
 }  // namespace condensation

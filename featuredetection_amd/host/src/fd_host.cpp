@@ -2879,9 +2879,9 @@ void SingleClassifierModel::evaluate(shared_ptr<imageprocessing::VersionedImage>
 }
 
 // the integral kind, its parameters and the SVM of a resident evaluation; false where the combination has none
-static bool resident_integral(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer) {
+static bool resident_integral(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer, bool needSvm = true) {
     using Kind = imageprocessing::SampledChain::Kind;
-    return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && scorer.svm &&
+    return (chain.kind == Kind::Haar || chain.kind == Kind::Surf || chain.kind == Kind::IntegralHog) && (scorer.svm || !needSvm) &&
            chain.wrappers.sampleMaps().size() <= (size_t)FD_SAMPLE_MAPS_MAX && chain.ready();
 }
 // the window list of a resident set can be resolved on this pyramid for patches of this width: it holds an image, has no more layers than
@@ -2898,8 +2898,8 @@ static bool resident_layer_table(const fd_pyramid* native, int patchWidth) {
 // fd_particles_evaluate_pyramid serves the chain: a pyramid kind with an f32 SVM behind at most FD_SAMPLE_MAPS_MAX wrappers, all of them
 // PatchResizingFeatureExtractors, on a pyramid that holds an image, has no more layers than the window table and whose width -> layer
 // table fits (fd_sample_layer_table)
-static bool resident_pyramid(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer) {
-    if (!chain.onPyramid() || !scorer.svm || !chain.ready()) return false;
+static bool resident_pyramid(const imageprocessing::SampledChain& chain, const SampledClassifier& scorer, bool needSvm = true) {
+    if (!chain.onPyramid() || (!scorer.svm && needSvm) || !chain.ready()) return false;
     const vector<fd_sample_map>& maps = chain.wrappers.sampleMaps();
     if (maps.size() > (size_t)FD_SAMPLE_MAPS_MAX) return false;
     for (const fd_sample_map& m : maps)
@@ -2913,6 +2913,15 @@ SingleClassifierModel::ResidentPlan SingleClassifierModel::residentPlan() const 
     ResidentPlan plan{ResidentPlan::Family::None, imageprocessing::sampledChainOf(featureExtractor.get(), /*mapsApplied=*/true), sampledClassifierOf(classifier.get())};
     if (resident_integral(plan.chain, plan.scorer)) plan.family = ResidentPlan::Family::Integral;
     else if (resident_pyramid(plan.chain, plan.scorer)) plan.family = ResidentPlan::Family::Pyramid;
+    return plan;
+}
+// while the model is not usable nothing is scored with its classifier: the plan then asks for the extraction alone
+SingleClassifierModel::ResidentPlan SelfLearningMeasurementModel::residentPlan() const {
+    SingleClassifierModel::ResidentPlan plan = model.residentPlan();
+    if (plan.family == SingleClassifierModel::ResidentPlan::Family::None && !usable) {
+        if (resident_integral(plan.chain, plan.scorer, false)) plan.family = SingleClassifierModel::ResidentPlan::Family::Integral;
+        else if (resident_pyramid(plan.chain, plan.scorer, false)) plan.family = SingleClassifierModel::ResidentPlan::Family::Pyramid;
+    }
     return plan;
 }
 void SingleClassifierModel::evaluateResident(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles) {
@@ -3087,6 +3096,119 @@ PositionDependentMeasurementModel::PositionDependentMeasurementModel(shared_ptr<
     : generator(seed), measurementModel(measurementModel), featureExtractor(featureExtractor), classifier(classifier), usable(false), frameCount(0),
       startFrameCount(3), stopFrameCount(0), targetThreshold(0.7f), confidenceThreshold(0.95f), positiveOffsetFactor(0.05f), negativeOffsetFactor(0.5f),
       sampleNegativesAroundTarget(0), sampleAdditionalNegatives(10), sampleTestNegatives(10), exploitSymmetry(false) {}
+SelfLearningMeasurementModel::SelfLearningMeasurementModel(shared_ptr<imageprocessing::FeatureExtractor> featureExtractor,
+                                                           shared_ptr<classification::TrainableProbabilisticClassifier> classifier, double positiveThreshold,
+                                                           double negativeThreshold)
+    : model(featureExtractor, classifier), featureExtractor(featureExtractor), classifier(classifier), positiveThreshold(positiveThreshold),
+      negativeThreshold(negativeThreshold) {
+    if (!(negativeThreshold <= positiveThreshold) || !std::isfinite(positiveThreshold) || !std::isfinite(negativeThreshold))
+        throw std::invalid_argument("SelfLearningMeasurementModel: the thresholds must be finite and negativeThreshold <= positiveThreshold");
+}
+void SelfLearningMeasurementModel::reset() {   // .cpp:76-79
+    classifier->reset();
+    usable = false;
+}
+fd_particles_examples_params SelfLearningMeasurementModel::examplesParams() const {
+    fd_particles_examples_params p;
+    p.positive_threshold = positiveThreshold; p.negative_threshold = negativeThreshold; p.max_count = 10; p.require_window = usable ? 1 : 0;
+    return p;
+}
+// .cpp:89-125 with the choice made by the library's rule; the patches of the chosen samples become the rows adaptResident takes
+bool SelfLearningMeasurementModel::adapt(shared_ptr<imageprocessing::VersionedImage> image, const vector<shared_ptr<Sample>>& samples) {
+    const int n = (int)samples.size();
+    const fd_particles_examples_params params = examplesParams();
+    if (!usable) featureExtractor->update(image);   // :119; a usable model was evaluated on this image already
+    vector<double> weight((size_t)n);
+    vector<uint8_t> valid((size_t)n, 1);
+    vector<shared_ptr<imageprocessing::Patch>> patches((size_t)n);
+    auto patchOf = [&](int i) {
+        const Sample& s = *samples[i];
+        if (!patches[i]) patches[i] = featureExtractor->extract(s.getX(), s.getY(), s.getWidth(), s.getHeight());
+        return patches[i];
+    };
+    for (int i = 0; i < n; ++i) {
+        weight[i] = samples[i]->getWeight();
+        // only a sample with a patch entered evaluate's lists (:68-71); a positive weight tells that it had one
+        if (usable) valid[i] = weight[i] > 0 || patchOf(i) ? 1 : 0;
+    }
+    int32_t positive[FD_PARTICLES_EXAMPLES_MAX], negative[FD_PARTICLES_EXAMPLES_MAX];
+    int nPositive = 0, nNegative = 0;
+    check(fd_particles_examples_select(n, weight.data(), valid.data(), &params, &nPositive, positive, &nNegative, negative));
+    lastPositives.clear(); lastNegatives.clear(); lastRows.clear();
+    lastRowLength = 0;
+    auto take = [&](const int32_t* chosen, int count, vector<fd_particles_example>& records) {
+        for (int k = 0; k < count; ++k) {
+            const int i = chosen[k];
+            const Sample& s = *samples[i];
+            const shared_ptr<imageprocessing::Patch> patch = patchOf(i);
+            fd_particles_example r{};
+            r.index = i; r.x = s.getX(); r.y = s.getY(); r.size = s.getSize(); r.valid = patch ? 1 : 0; r.weight = weight[i];
+            records.push_back(r);
+            if (!patch) continue;
+            const Mat& data = patch->getData();
+            if (data.depth() != CV_32F) throw std::invalid_argument("SelfLearningMeasurementModel: the feature vectors must be CV_32F");
+            const int perRow = data.cols * data.channels();
+            lastRowLength = data.rows * perRow;
+            for (int y = 0; y < data.rows; ++y) lastRows.insert(lastRows.end(), data.ptr<float>(y), data.ptr<float>(y) + perRow);
+        }
+    };
+    take(positive, nPositive, lastPositives);
+    take(negative, nNegative, lastNegatives);
+    return adaptResident(image, lastPositives, lastNegatives, lastRows);
+}
+// rows: one row of the feature length per valid record, the positives' first, in list order
+bool SelfLearningMeasurementModel::adaptResident(shared_ptr<imageprocessing::VersionedImage>, const vector<fd_particles_example>& positives,
+                                                 const vector<fd_particles_example>& negatives, const vector<float>& rows) {
+    size_t validCount = 0;
+    for (const fd_particles_example& r : positives) validCount += r.valid ? 1 : 0;
+    for (const fd_particles_example& r : negatives) validCount += r.valid ? 1 : 0;
+    const size_t length = validCount ? rows.size() / validCount : 0;
+    size_t next = 0;
+    auto vectors = [&](const vector<fd_particles_example>& records) {
+        vector<Mat> out;
+        for (const fd_particles_example& r : records)
+            if (r.valid) out.push_back(Mat(1, (int)length, CV_32F, const_cast<float*>(rows.data() + length * next++)).clone());
+        return out;
+    };
+    const vector<Mat> positiveExamples = vectors(positives), negativeExamples = vectors(negatives);
+    usable = classifier->retrain(positiveExamples, negativeExamples);
+    return true;
+}
+void SelfLearningMeasurementModel::readExamples(shared_ptr<imageprocessing::VersionedImage> image, fd_particles* particles, fd_particles_info& info) {
+    featureExtractor->update(image);   // the bootstrap branch's update (:119); after evaluateResident it changes nothing
+    const SingleClassifierModel::ResidentPlan plan = residentPlan();
+    if (plan.family == SingleClassifierModel::ResidentPlan::Family::None)
+        throw std::logic_error("SelfLearningMeasurementModel: no resident extraction for this extractor and classifier");
+    const imageprocessing::SampledChain::DeviceCall call = plan.chain.deviceCall();
+    const vector<fd_sample_map>& maps = plan.maps();
+    const fd_particles_examples_params params = examplesParams();
+    int channels = 1, length = 0, capacity = 0;
+    if (call.onPyramid) {
+        int first, lw, lh;
+        double scale;
+        fd_pyramid_layer_info(call.pyramid, 0, &first, &scale, &lw, &lh, &channels);
+    }
+    check(fd_particles_examples_bounds(call.onPyramid ? FD_EXAMPLES_PYRAMID : FD_EXAMPLES_INTEGRAL, call.kind, call.params(), channels, params.max_count, &length,
+                                       &capacity));
+    fd_particles_example positives[FD_PARTICLES_EXAMPLES_MAX], negatives[FD_PARTICLES_EXAMPLES_MAX];
+    int nPositive = 0, nNegative = 0, rowLength = 0;
+    vector<float> all((size_t)capacity + 1);
+    if (call.onPyramid)
+        check(fd_particles_state_examples_pyramid(context(), particles, nullptr, call.pyramid, call.kind, call.params(), Sample::getAspectRatio(), maps.data(),
+                                                  (int)maps.size(), &params, &info, nullptr, &nPositive, positives, &nNegative, negatives, all.data(),
+                                                  capacity, &rowLength));
+    else
+        check(fd_particles_state_examples_integral(context(), particles, nullptr, call.integral, call.kind, call.params(), Sample::getAspectRatio(), maps.data(),
+                                                   (int)maps.size(), &params, &info, nullptr, &nPositive, positives, &nNegative, negatives, all.data(),
+                                                   capacity, &rowLength));
+    lastPositives.assign(positives, positives + nPositive);
+    lastNegatives.assign(negatives, negatives + nNegative);
+    lastRows.clear();
+    lastRowLength = rowLength;
+    for (int r = 0; r < nPositive + nNegative; ++r)   // the library leaves the row of a record without a patch unwritten: keep the others, packed
+        if ((r < nPositive ? positives[r] : negatives[r - nPositive]).valid) lastRows.insert(lastRows.end(), all.begin() + (size_t)r * rowLength, all.begin() + (size_t)(r + 1) * rowLength);
+}
+
 void PositionDependentMeasurementModel::update(shared_ptr<imageprocessing::VersionedImage> image) { measurementModel->update(image); }
 void PositionDependentMeasurementModel::evaluate(Sample& sample) const { measurementModel->evaluate(sample); }
 void PositionDependentMeasurementModel::evaluate(shared_ptr<imageprocessing::VersionedImage> image, vector<shared_ptr<Sample>>& samples) {
@@ -4322,6 +4444,7 @@ static bool is_exactly(const shared_ptr<U>& p) { return p && typeid(*p) == typei
 // the SingleClassifierModel a resident frame would evaluate: the model itself, or the one inside a PositionDependentMeasurementModel
 static shared_ptr<SingleClassifierModel> resident_single_model(const shared_ptr<MeasurementModel>& model) {
     if (is_exactly<SingleClassifierModel>(model)) return std::static_pointer_cast<SingleClassifierModel>(model);
+    if (is_exactly<SelfLearningMeasurementModel>(model)) return nullptr;   // evaluated through the model's own evaluateResident
     if (is_exactly<PositionDependentMeasurementModel>(model)) {
         auto dependent = std::static_pointer_cast<PositionDependentMeasurementModel>(model);
         if (dependent->isUsable() && is_exactly<SingleClassifierModel>(dependent->getMeasurementModel()))
@@ -4340,6 +4463,15 @@ ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
     const size_t old = resident ? (size_t)residentCount : samples.size();
     if (old > FD_PARTICLES_MAX || resampling->getCount() < 0 || resampling->getCount() > FD_PARTICLES_MAX) return ResidentKind::None;
     const bool simple = is_exactly<SimpleTransitionModel>(resampling->getTransitionModel());
+    using Family = SingleClassifierModel::ResidentPlan::Family;
+    if (examplesModel) {   // PartiallyAdaptiveCondensationTracker: both models resident, or the generic route
+        if (!simple || typeid(*examplesModel) != typeid(SelfLearningMeasurementModel)) return ResidentKind::None;
+        const Family family = examplesModel->residentPlan().family;
+        if (family == Family::None) return ResidentKind::None;
+        if (measurementModel == examplesModel) return family == Family::Integral ? ResidentKind::Integral : ResidentKind::Pyramid;
+        return is_exactly<WvmSvmModel>(measurementModel) && std::static_pointer_cast<WvmSvmModel>(measurementModel)->residentPossible() ? ResidentKind::WvmSvm
+                                                                                                                                     : ResidentKind::None;
+    }
     if (is_exactly<ExtendedHogBasedMeasurementModel>(measurementModel)) {
         auto model = std::static_pointer_cast<ExtendedHogBasedMeasurementModel>(measurementModel);
         if (!simple || !model->native() || !model->isUsable()) return ResidentKind::None;
@@ -4354,7 +4486,6 @@ ParticleFrameLoop::ResidentKind ParticleFrameLoop::residentKind() const {
                       std::static_pointer_cast<OpticalFlowTransitionModel>(resampling->getTransitionModel())->residentPossible();
     if (!simple && !flow) return ResidentKind::None;
     const shared_ptr<SingleClassifierModel> single = resident_single_model(measurementModel);
-    using Family = SingleClassifierModel::ResidentPlan::Family;
     const Family family = single ? single->residentPlan().family : Family::None;   // on what the extractor holds from the previous frame
     if (family == Family::None) return ResidentKind::None;
     if (family == Family::Integral) return ResidentKind::Integral;
@@ -4470,8 +4601,14 @@ void ParticleFrameLoop::deviceStep() {
     flow.sample(particles, draws, copies, fresh, firstFreshId);
     fd_particles_info info;
     residentChose = false;
+    residentExamples = false;
     residentChosen.clear();
-    if (onTracker) {   // the model reads the state itself: its re-initialisation needs the best score in the middle
+    if (examplesModel) {   // either model evaluates; the adaptive one reads its examples with the state, in the frame's one wait
+        if (measurementModel == examplesModel) examplesModel->evaluateResident(image, particles);
+        else std::static_pointer_cast<WvmSvmModel>(measurementModel)->evaluateResident(image, particles);
+        examplesModel->readExamples(image, particles, info);
+        residentExamples = true;
+    } else if (onTracker) {   // the model reads the state itself: its re-initialisation needs the best score in the middle
         ehog->evaluateResident(image, particles, info);
     } else {
         if (lastKind == ResidentKind::WvmSvm) std::static_pointer_cast<WvmSvmModel>(measurementModel)->evaluateResident(image, particles);
@@ -4527,6 +4664,35 @@ boost::optional<cv::Rect> CondensationTracker::process(const Mat& imageData) {  
     step(imageData);
     if (state) return boost::optional<cv::Rect>(state->getBounds());
     return boost::optional<cv::Rect>();
+}
+
+PartiallyAdaptiveCondensationTracker::PartiallyAdaptiveCondensationTracker(shared_ptr<Sampler> sampler, shared_ptr<MeasurementModel> initialMeasurementModel,
+                                                                           shared_ptr<AdaptiveMeasurementModel> measurementModel, shared_ptr<StateExtractor> extractor)
+    : ParticleFrameLoop(sampler, initialMeasurementModel, extractor), initialModel(initialMeasurementModel), adaptiveModel(measurementModel) {
+    examplesModel = std::dynamic_pointer_cast<SelfLearningMeasurementModel>(measurementModel);   // null: every frame takes the generic route
+}
+
+boost::optional<cv::Rect> PartiallyAdaptiveCondensationTracker::process(const Mat& imageData) {   // .cpp:40-65
+    usedAdaptiveModel = useAdaptiveModel && adaptiveModel->isUsable();
+    measurementModel = usedAdaptiveModel ? shared_ptr<MeasurementModel>(adaptiveModel) : initialModel;
+    const shared_ptr<SelfLearningMeasurementModel> reads = examplesModel;
+    if (!useAdaptiveModel || !examplesModel) {   // nothing reads examples: the frame is the measurement model's own
+        examplesModel.reset();
+    }
+    step(imageData);
+    examplesModel = reads;
+    if (useAdaptiveModel) {
+        if (examplesRead()) reads->adaptResident(image);
+        else if (state) adaptiveModel->adapt(image, currentSamples(), *state);
+        else adaptiveModel->adapt(image, currentSamples());
+    }
+    if (state) return boost::optional<cv::Rect>(state->getBounds());
+    return boost::optional<cv::Rect>();
+}
+
+void PartiallyAdaptiveCondensationTracker::setUseAdaptiveModel(bool useAdaptive) {
+    useAdaptiveModel = useAdaptive;
+    if (!useAdaptive) adaptiveModel->reset();
 }
 
 AdaptiveCondensationTracker::AdaptiveCondensationTracker(shared_ptr<Sampler> sampler, shared_ptr<AdaptiveMeasurementModel> measurementModel,

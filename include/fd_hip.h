@@ -1190,6 +1190,59 @@ int fd_particles_negatives_bounds(const fd_particles_negatives_params* params, i
 int fd_particles_state_negatives(fd_ctx* ctx, fd_particles* p, fd_flow* flow, const fd_particles_negatives_params* params, fd_particles_info* info,
                                  fd_flow_motion_info* motion, int* count, fd_particles_negative* out);
 
+/* ---- the examples of condensation::SelfLearningMeasurementModel::adapt (SelfLearningMeasurementModel.cpp:89-125), chosen on the
+ * device behind the state and extracted there.  Two lists over the generation's weights: the positive candidates have
+ * weight > positive_threshold, the negative ones weight < negative_threshold, both strict and in double; with require_window a
+ * candidate also needs the valid flag the generation's evaluate left (the usable branch, .cpp:68-71), without it every sample is a
+ * candidate (the bootstrap branch, :103-110) and the extraction decides.  A side with at most max_count candidates lists them in index
+ * order (the reference does not sort then); a side with more lists the max_count best in sorted order: positives by (weight
+ * descending, index ascending), negatives by (weight ascending, index ascending).  The reference's std::sort is unstable; "lower
+ * index first" is this project's rule.  The lists do not depend on whether a state was found.  The reference tests the negative
+ * threshold only where the positive one was not passed; the two tests here are independent, which is the same for negative_threshold <=
+ * positive_threshold, and a negative_threshold above the positive one is refused (FD_ERR_INVALID_ARGUMENT). */
+#define FD_PARTICLES_EXAMPLES_MAX 32
+typedef struct {
+    double positive_threshold, negative_threshold;   /* finite, negative_threshold <= positive_threshold */
+    int32_t max_count;                                /* 1 .. FD_PARTICLES_EXAMPLES_MAX per side; the reference's 10 */
+    int32_t require_window;                           /* 0 / 1 */
+} fd_particles_examples_params;
+typedef struct {
+    int32_t index;                     /* of the sample in the generation */
+    int32_t x, y, size;
+    int32_t valid;                     /* the extraction found a patch: the record has a feature row */
+    double weight;
+} fd_particles_example;
+/* host only, no context: the two lists of a generation given as arrays (valid may be NULL when require_window is 0), by the
+ * comparisons k_particles_examples runs: the indices of the chosen samples in list order, room for max_count each.
+ * FD_ERR_INVALID_ARGUMENT for NULL, n < 0, max_count outside 1 .. FD_PARTICLES_EXAMPLES_MAX, thresholds that are not finite or inverted;
+ * FD_ERR_RUNTIME (both counts 0) when a weight is negative or not finite. */
+int fd_particles_examples_select(int n, const double* weight, const uint8_t* valid, const fd_particles_examples_params* params, int* n_pos,
+                                 int32_t* pos_index, int* n_neg, int32_t* neg_index);
+/* host only: floats per feature row of an extractor and the floats `rows` must hold, 2 * max_count rows.  family
+ * FD_EXAMPLES_INTEGRAL: kind FD_INTEGRAL_*, params as fd_particles_evaluate_integral takes them; family FD_EXAMPLES_PYRAMID: kind
+ * FD_SAMPLES_HIST / _EHOG / _PATCH, params as fd_particles_evaluate_pyramid takes them, channels the channel count of the pyramid's bin
+ * image as fd_hist_feature_length / fd_ehog_feature_length take it (not read for the other kinds).  FD_ERR_INVALID_ARGUMENT where the
+ * extractor's own length query refuses the parameters, for an unknown family or kind, NULL and max_count outside
+ * 1 .. FD_PARTICLES_EXAMPLES_MAX. */
+enum { FD_EXAMPLES_INTEGRAL = 0, FD_EXAMPLES_PYRAMID = 1 };
+int fd_particles_examples_bounds(int family, int kind, const void* params, int channels, int max_count, int* row_length, int* row_capacity);
+/* fd_particles_state (flow NULL, motion NULL) or fd_particles_state_flow with the selection queued behind the state kernel and the
+ * chosen samples' feature rows behind that: the up to 2 * max_count samples {x, y, size, cvRound(aspect_ratio * size)} go through the
+ * maps on the device (the adaptive extractor's chain, whatever chain the generation was evaluated with) and the family's list kernel
+ * of fd_integral_extract_haar / _surf / _hog runs on that list with a fixed launch size; unused slots hold an empty window and are
+ * not computed.  *info, *motion, both record lists (room for max_count each) with their valid flags, and the rows come back in one
+ * copy and one wait.  Row r of `rows` (*row_length floats) belongs to pos[r] for r < *n_pos and to neg[r - *n_pos] after that, bit for
+ * bit the row the extract call returns for that sample; the row of a record that is not valid is not written.  With bad_weight
+ * (FD_ERR_RUNTIME, *info filled) both counts are 0.  FD_ERR_INVALID_ARGUMENT before anything is queued: max_count outside
+ * 1 .. FD_PARTICLES_EXAMPLES_MAX, thresholds that are not finite or inverted, require_window other than 0 / 1, row_capacity below
+ * 2 * max_count * row length, the maps' and the extractor's own rules, NULL arguments (motion NULL exactly when flow is), objects of
+ * different contexts.  FD_ERR_RUNTIME with require_window on a generation that has not been evaluated. */
+int fd_particles_state_examples_integral(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_integral* g, int kind, const void* params,
+                                         double aspect_ratio, const fd_sample_map* maps, int n_maps,
+                                         const fd_particles_examples_params* examples_params, fd_particles_info* info, fd_flow_motion_info* motion,
+                                         int* n_pos, fd_particles_example* pos, int* n_neg, fd_particles_example* neg, float* rows, int row_capacity,
+                                         int* row_length);
+
 /* ---- classification::RvmClassifier / ProbabilisticRvmClassifier -----------------
  * Cascaded reduced-vector machine (RvmClassifier.cpp:75-126): level k evaluates kernel(x, rsv_k) on the whole
  * vector; through the reference's cached path the running distance is d_0 = -bias + c[0][0] K_0,
@@ -1295,6 +1348,17 @@ enum { FD_SAMPLES_PATCH = 2 };   /* next to FD_SAMPLES_HIST / FD_SAMPLES_EHOG; p
  * evaluated".  An empty generation is FD_OK. */
 int fd_particles_evaluate_pyramid(fd_ctx* ctx, fd_particles* p, fd_pyramid* pyr, int kind, const void* params, const fd_svm* svm,
                                   double aspect_ratio, const fd_sample_map* maps, int n_maps);
+/* fd_particles_state_examples_integral on a pyramid family: the chosen samples go through the maps (FD_SAMPLE_MAP_RESIZE only) and are
+ * resolved to windows of pyr on the device by the rule of fd_pyramid_sample_windows (k_particles_windows in list form); the list kernel
+ * of fd_hist_extract_samples, fd_ehog_extract_samples (kind FD_SAMPLES_HIST / FD_SAMPLES_EHOG) or fd_patch_extract_samples
+ * (FD_SAMPLES_PATCH; every feature space, FD_FEATURE_WHI among them) runs on the 2 * max_count slots.  A slot without a record or
+ * without a window is flagged invalid; it lists a spare window so that the kernel reads valid memory, and its row stays on the device.
+ * Rows, flags and errors as there, and the argument rules of fd_particles_evaluate_pyramid for pyr, kind, params and the maps. */
+int fd_particles_state_examples_pyramid(fd_ctx* ctx, fd_particles* p, fd_flow* flow, fd_pyramid* pyr, int kind, const void* params,
+                                        double aspect_ratio, const fd_sample_map* maps, int n_maps,
+                                        const fd_particles_examples_params* examples_params, fd_particles_info* info, fd_flow_motion_info* motion,
+                                        int* n_pos, fd_particles_example* pos, int* n_neg, fd_particles_example* neg, float* rows, int row_capacity,
+                                        int* row_length);
 
 /* ---- the resident particle set on condensation::WvmSvmModel (WvmSvmModel.cpp:69-118), the measurement model of the face tracker ------
  * A frame of this model is one chain on the context's stream: fd_pyramid_update, fd_particles_sample, _evaluate_wvm_svm, _weigh_wvm_svm,

@@ -443,11 +443,32 @@ WVM_SVM_HOST_CONFIG = """tracking {
 """
 
 
-def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False, app=None):
+# --self-learning: the reference's partiallyAdaptiveTrackingApp graph (its thresholds and its 10 examples per side) on the face tracker's
+# models, the self-learning model on hog features of the probe's pyramid
+SELF_LEARNING_HOST_CONFIG = """tracking {
+  seed 7
+  tracker partiallyAdaptive
+  transition simple { positionDeviation 10 sizeDeviation 0.1 }
+  measurement wvmSvm {
+    firstClassifier pwvm { classifierFile %(wvm)s }
+    secondClassifier psvm { classifierFile %(svm)s threshold %(threshold)s }
+  }
+  adaptive selfLearning {
+    resampling { particleCount %(n)d randomRate 0.35 }
+    positiveThreshold 0.85  negativeThreshold 0.05
+    %(feature)s
+    classifier { kernel rbf { gamma 0.5 } training { c 1 examples fixedsize positiveExamples 10 negativeExamples 50 minPositiveExamples 3 }
+                 probabilistic fixed { logisticA 0.00556 logisticB -2.95 } }
+  }
+}
+"""
+
+
+def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False, app=None, self_learning=False):
     import subprocess
     import tempfile
     app = app or os.path.join(ROOT, "featuredetection_amd", "tracker_app")
-    out = dict(app=os.path.relpath(app, ROOT), size="%dx%d" % (W, H), feature="wvmSvm" if wvm_svm else pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
+    out = dict(app=os.path.relpath(app, ROOT), size="%dx%d" % (W, H), feature="selfLearning" if self_learning else "wvmSvm" if wvm_svm else pyramid or "ihog", frames=frames, rounds=rounds, routes={"generic": {}, "device": {}})
     with tempfile.TemporaryDirectory() as tmp:
         base = textured(5)
         if wvm_svm:   # the models of run_wvm_svm, in the files the app loads
@@ -472,7 +493,9 @@ def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False, app=Non
         for n in counts:
             cfg = os.path.join(tmp, "tracking%d.cfg" % n)
             with open(cfg, "w") as f:
-                if wvm_svm:
+                if self_learning:
+                    f.write(SELF_LEARNING_HOST_CONFIG % dict(models, n=n, feature=HOST_FEATURES["hog"]))
+                elif wvm_svm:
                     f.write(WVM_SVM_HOST_CONFIG % dict(models, n=n))
                 else:
                     f.write(HOST_CONFIG % dict(n=n, feature=HOST_FEATURES[pyramid], transition=HOST_TRANSITIONS[pyramid is not None]))
@@ -485,9 +508,11 @@ def run_host(frames, rounds, counts=COUNTS, pyramid=None, wvm_svm=False, app=Non
                     if run.returncode != 0:
                         sys.exit("tracker_app failed: " + run.stderr[-500:])
                     lines = [l.split() for l in run.stdout.splitlines() if l.startswith("frame ")]
-                    if any(t[11] != route for t in lines):
-                        sys.exit("tracker_app took another route than %s" % route)
-                    times[route].append([float(t[13]) for t in lines[5:]])
+                    if any(t[11] != route for t in lines[5:] if self_learning) or any(t[11] != route for t in lines if not self_learning):
+                        sys.exit("tracker_app took another route than %s" % route)   # the self-learning tracker's first frame is generic
+                    times[route].append([float(t[-1]) for t in lines[5:]])
+                    if self_learning:
+                        out.setdefault("adaptive_frames", {})[route] = sum(1 for t in lines[5:] if t[13] == "adaptive")
             for route, per_round in times.items():
                 flat = np.concatenate(per_round)
                 medians = [float(np.median(r)) for r in per_round]
@@ -504,13 +529,18 @@ if __name__ == "__main__":
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--pyramid", choices=("hog", "ehog", "glbp", "whi"), default=None)
     ap.add_argument("--wvm-svm", action="store_true", help="the face tracker's frame (WvmSvmModel); counts default to 800")
+    ap.add_argument("--self-learning", action="store_true", help="through tracker_app: `tracker partiallyAdaptive` (WvmSvmModel + SelfLearningMeasurementModel "
+                    "on hog), both routes; counts default to 800, the reference's particle count")
     ap.add_argument("--routes", default="generic,resident", help="with --wvm-svm: the routes to run, comma separated")
     ap.add_argument("--counts", default=None, help="particle counts, comma separated")
     ap.add_argument("--app", default=None, help="with --host: the tracker_app to run (default: this tree's)")
     a = ap.parse_args()
-    counts = tuple(int(c) for c in a.counts.split(",")) if a.counts else ((800,) if a.wvm_svm else COUNTS)
+    counts = tuple(int(c) for c in a.counts.split(",")) if a.counts else ((800,) if a.wvm_svm or a.self_learning else COUNTS)
     if not torch.cuda.is_available():
         sys.exit("resident_tracker_probe: no GPU; a frame time cannot be measured without one")
+    if a.self_learning:
+        print(json.dumps(run_host(a.frames, a.rounds, counts, wvm_svm=True, app=a.app, self_learning=True)))
+        sys.exit(0)
     if a.wvm_svm and a.host:
         print(json.dumps(run_host(a.frames, a.rounds, counts, wvm_svm=True, app=a.app)))
         sys.exit(0)
